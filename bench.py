@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec (1024x1024 uint16) through the compute_branches hot path on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one pass of the whole hot path (Lanczos4 + rescale, 200-patch tiled UNet with D4 TTA and
@@ -10,6 +10,11 @@ batch of `--images` (default 256 = BASELINE.json configs[1]) synthetic 1024x1024
 GPU, with the inputs already resident in HBM.  Images are independent, so ranks shard them with no
 data-path collective (weak scaling); the result rows are all-gathered over RCCL once at the end.
 Prints ONE JSON line on rank 0 (see README / DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what runs outside the
+timed region: the host-pointer steps (`value_host_inputs`), the HIP-event pass of the dominant kernel
+(`roofline`), the determinism / copy checks, the opt-in split-precision lines (`alt`) and the CPU baseline.
+`--dump-outputs DIR` writes the rows of the last timed step (all ranks') as DIR/rows_<field>.npy, float64.
 """
 import argparse
 import ctypes
@@ -136,9 +141,14 @@ def main():
     ap.add_argument("--images", type=int, default=256, help="images per GPU per step")
     ap.add_argument("--distinct", type=int, default=0, help="distinct synthetic images generated (0 = all of them, SURVEY 8d; fewer are tiled)")
     ap.add_argument("--max-patches", type=int, default=1600, help="UNet patches resident per pass (200 per image)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the opt-in split-precision (bf16x3 / bf16x6) lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the opt-in split-precision (bf16x3 / bf16x6) lines")
+    ap.add_argument("--full", action="store_true", help="also run what lies outside the timed region: host-pointer steps, the "
+                    "dominant kernel's HIP-event pass, determinism checks, split-precision lines, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the rows of the last timed step as DIR/rows_<field>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     t_start = time.perf_counter()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -255,48 +265,83 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     log(f"timed region {elapsed:.2f} s")
-    # second figure, outside the contract's timed region: the same step through the host-pointer entry (PCIe inclusive), a few steps
-    n_host_steps = max(1, min(2, args.steps))
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(n_host_steps):
-        host_rows = step_host()
-    barrier()
-    elapsed_host = time.perf_counter() - t0
-    if [r[1:] for r in host_rows] != [r[1:] for r in rows]:
-        raise SystemExit("bench: the host-pointer entry and the device-pointer entry produced different rows")
-    log(f"host-input steps: {n_host_steps} in {elapsed_host:.2f} s")
-    # HIP-event timing of the dominant kernel in a SEPARATE pass after the timed region (same kernels, same 1600-patch
-    # launches: two passes of 8 images), on the stream the kernels are launched on.  Its rows double as a determinism /
-    # race screen: the same images in another position of another run must give identical rows; tiled copies likewise.
-    n_prof = min(16, n_img)
-    handle.prof_enable(True)
-    handle.prof_read(True)
-    prof_rows = step(n_prof)
-    conv_ms, conv_launches, conv_flops = handle.prof_read(True)
-    handle.prof_enable(False)
-    for i in range(n_prof):
-        if prof_rows[i][1:] != rows[i][1:]:
-            raise SystemExit(f"bench: image {i} gave different rows in two runs: {prof_rows[i]} vs {rows[i]}")
-    nd = len(distinct)
-    for i, r in enumerate(rows):
-        if r[1:] != rows[i % nd][1:]:
-            raise SystemExit(f"bench: image {i} and its copy {i % nd} produced different rows: {r} vs {rows[i % nd]}")
+    if args.full:
+        # second figure, outside the contract's timed region: the same step through the host-pointer entry (PCIe inclusive), a few steps
+        n_host_steps = max(1, min(2, args.steps))
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(n_host_steps):
+            host_rows = step_host()
+        barrier()
+        elapsed_host = time.perf_counter() - t0
+        if [r[1:] for r in host_rows] != [r[1:] for r in rows]:
+            raise SystemExit("bench: the host-pointer entry and the device-pointer entry produced different rows")
+        log(f"host-input steps: {n_host_steps} in {elapsed_host:.2f} s")
+        # HIP-event timing of the dominant kernel in a SEPARATE pass after the timed region (same kernels, same 1600-patch
+        # launches: two passes of 8 images), on the stream the kernels are launched on.  Its rows double as a determinism /
+        # race screen: the same images in another position of another run must give identical rows; tiled copies likewise.
+        n_prof = min(16, n_img)
+        handle.prof_enable(True)
+        handle.prof_read(True)
+        prof_rows = step(n_prof)
+        conv_ms, conv_launches, conv_flops = handle.prof_read(True)
+        handle.prof_enable(False)
+        for i in range(n_prof):
+            if prof_rows[i][1:] != rows[i][1:]:
+                raise SystemExit(f"bench: image {i} gave different rows in two runs: {prof_rows[i]} vs {rows[i]}")
+        nd = len(distinct)
+        for i, r in enumerate(rows):
+            if r[1:] != rows[i % nd][1:]:
+                raise SystemExit(f"bench: image {i} and its copy {i % nd} produced different rows: {r} vs {rows[i % nd]}")
 
+    all_rows = rows
     if dist is not None:
-        t = torch.tensor([elapsed, elapsed_host], dtype=torch.float64, device="cpu" if (stub or rehearse) else "cuda")
+        t = torch.tensor([elapsed, elapsed_host if args.full else 0.0], dtype=torch.float64, device="cpu" if (stub or rehearse) else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, elapsed_host = float(t[0].item()), float(t[1].item())
         # the one collective of the path: a single fixed-size all-gather of the 32-byte result rows over RCCL/xGMI
         from tmat_amd import distributed
-        n_rows = len(distributed.gather_rows(rows, n_total=n_img * world))
-    else:
-        n_rows = len(rows)
+        all_rows = distributed.gather_rows(rows, n_total=n_img * world)
+    n_rows = len(all_rows)
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives: the (index, count, total_px, avg_px) rows of the last timed step, every rank's
+        d = Path(args.dump_outputs)
+        d.mkdir(parents=True, exist_ok=True)
+        for k, field in enumerate(("index", "count", "total_px", "avg_px")):
+            np.save(d / f"rows_{field}.npy", np.array([r[k] for r in all_rows], np.float64))
+        log(f"rows of the last timed step written to {d}")
 
     out = None
     if rank == 0:
         total_images = n_img * world * args.steps
         value = total_images / elapsed
+        # path-level figure: every FLOP the step runs on the matrix cores (all 3x3 / sub-pixel / 1x1 layers) over the
+        # whole step time (which also holds the vector-ALU layers, morphology, blending and the host stages)
+        path_flops = synth.mfma_flops_per_patch() * 200.0 * n_img * world * args.steps
+        path_tflops = path_flops / elapsed / 1e12 / world
+        out = {
+            "metric": "images/sec (1024x1024 uint16) through compute_branches",
+            "value": round(value, 4), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{n_img} synthetic 1024x1024 uint16 Z-projections per GPU ({len(distinct)} distinct), inputs pre-resident "
+                                   "in HBM (host-pointer entry adds 2 MB/image of H2D), tiled UNet seg (200 patches/image, random-init "
+                                   "structured weights) + DMT branch extraction, default_branching_computation.json",
+                       "images_per_gpu": n_img, "distinct_images": len(distinct), "patches_per_image": 200,
+                       "rows_gathered": n_rows, "host_threads": int(os.environ["TMAT_HOST_THREADS"])},
+            "roofline": {"bound": "mfma", "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                         "path_achieved": round(path_tflops, 2), "path_frac": round(path_tflops / MFMA_F32_PEAK_TFLOPS, 4),
+                         "path_note": "executed MFMA FLOPs of the whole step (19.08 GFLOP/patch: every 3x3 / sub-pixel / 1x1 layer) / ms_per_step, per GPU"},
+            "alt": None, "cpu_baseline": None,
+        }
+        sample = [r for r in rows[:4]]
+        out["config"]["sample_rows"] = [[int(r[0]), int(r[1]), round(r[2], 3)] for r in sample]
+    if rank == 0 and args.full:
+        out["value_host_inputs"] = round(n_img * world * n_host_steps / elapsed_host, 4)
+        out["value_host_inputs_note"] = (f"SURVEY 8d's metric as written -- uint16 arrays in HOST memory when the clock starts (tmat_analyze_batch, "
+                                         f"2 MB/image of H2D inside the timed region), {n_host_steps} step(s) after the contract's timed region; "
+                                         "`value` is the contract's figure (inputs resident in HBM)")
+        out["config"]["copies_identical"] = True
         achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
         # HBM traffic of the dominant kernel comes from the committed PMC summary of the same pipeline (separate
         # rocprofv3 --pmc passes, tools/profile_round.sh); it is per launch of 1600 patches, like `achieved`
@@ -309,42 +354,19 @@ def main():
             traffic = sj.get("traffic_bytes_per_launch")
             top_by_time = sj.get("top_kernels_by_total_time")
             traffic_source = f"profiles/{summ[-1].name} (committed rocprofv3 --pmc / --kernel-trace passes of this command; not re-measured in this run)"
-        # path-level figure: every FLOP the step runs on the matrix cores (all 3x3 / sub-pixel / 1x1 layers) over the
-        # whole step time (which also holds the vector-ALU layers, morphology, blending and the host stages)
-        path_flops = synth.mfma_flops_per_patch() * 200.0 * n_img * world * args.steps
-        path_tflops = path_flops / elapsed / 1e12 / world
-        out = {
-            "metric": "images/sec (1024x1024 uint16) through compute_branches",
-            "value": round(value, 4), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "value_host_inputs": round(n_img * world * n_host_steps / elapsed_host, 4),
-            "value_host_inputs_note": f"SURVEY 8d's metric as written -- uint16 arrays in HOST memory when the clock starts (tmat_analyze_batch, "
-                                      f"2 MB/image of H2D inside the timed region), {n_host_steps} step(s) after the contract's timed region; "
-                                      "`value` is the contract's figure (inputs resident in HBM)",
-            "config": {"workload": f"{n_img} synthetic 1024x1024 uint16 Z-projections per GPU ({len(distinct)} distinct), inputs pre-resident "
-                                   "in HBM (host-pointer entry adds 2 MB/image of H2D), tiled UNet seg (200 patches/image, random-init "
-                                   "structured weights) + DMT branch extraction, default_branching_computation.json",
-                       "images_per_gpu": n_img, "distinct_images": len(distinct), "patches_per_image": 200,
-                       "rows_gathered": n_rows, "copies_identical": True, "host_threads": int(os.environ["TMAT_HOST_THREADS"])},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / MFMA_F32_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": "tmat::conv_mfma_kernel<128, 128, 4, 2, 3, false> (3x3 implicit-GEMM on v_mfma_f32_32x32x2_f32; "
-                                   "4 of the 8 transposed-conv layers -- both convolutions of up block 0 and the second one of blocks 1 and 2 --, "
-                                   "52 % of the 3x3 / sub-pixel MFMA FLOPs; the largest kernel by total time)",
-                         "launches": int(conv_launches), "avg_launch_ms": round(conv_ms / max(conv_launches, 1), 4),
-                         "timed_in": f"separate pass of {n_prof} images after the timed region (HIP events on the launch stream)",
-                         "path_achieved": round(path_tflops, 2), "path_frac": round(path_tflops / MFMA_F32_PEAK_TFLOPS, 4),
-                         "path_note": "executed MFMA FLOPs of the whole step (19.08 GFLOP/patch: every 3x3 / sub-pixel / 1x1 layer) / ms_per_step, per GPU",
-                         "top_kernels_by_total_time": top_by_time, "top_kernels_source": traffic_source},
-        }
-        sample = [r for r in rows[:4]]
-        out["config"]["sample_rows"] = [[int(r[0]), int(r[1]), round(r[2], 3)] for r in sample]
+        out["roofline"].update({
+            "achieved": round(achieved, 2), "frac": round(achieved / MFMA_F32_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_source,
+            "kernel": "tmat::conv_mfma_kernel<128, 128, 4, 2, 3, false> (3x3 implicit-GEMM on v_mfma_f32_32x32x2_f32; "
+                      "4 of the 8 transposed-conv layers -- both convolutions of up block 0 and the second one of blocks 1 and 2 --, "
+                      "52 % of the 3x3 / sub-pixel MFMA FLOPs; the largest kernel by total time)",
+            "launches": int(conv_launches), "avg_launch_ms": round(conv_ms / max(conv_launches, 1), 4),
+            "timed_in": f"separate pass of {n_prof} images after the timed region (HIP events on the launch stream)",
+            "top_kernels_by_total_time": top_by_time, "top_kernels_source": traffic_source})
 
     # opt-in split-precision lines (tmat_set_precision("bf16x3" | "bf16x6")): never the headline; one full step of the same images
     # per mode, its rows checked against the f32 rows with the north-star tolerance (counts equal, lengths within 1e-4 relative)
     # and REPORTED either way
-    if rank == 0 and world == 1 and not stub and not args.no_alt:
+    if args.full and rank == 0 and world == 1 and not stub and not args.no_alt:
         BF16_PEAK_TFLOPS = 2500.0                        # MI355X_MICROARCH.md: dense bf16 MFMA
         out["alt"] = []
         for mode, nprod, what in (("bf16x3", 3, "bf16 hi/lo split of the f32 operands, 3 bf16 MFMA products per MAC"),
@@ -383,13 +405,9 @@ def main():
             log(f"alt {mode}: {out['alt'][-1]['value']} images/s, parity pass {out['alt'][-1]['parity_vs_f32']['pass']} "
                 f"({len(bad)} count mismatches, {n_same} of {n_img} rows bit-identical)")
         handle.set_precision("f32")
-    elif rank == 0:
-        out["alt"] = None
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:
         out["cpu_baseline"] = cpu_baseline(host[0], weights, handle, log)
-    elif rank == 0:
-        out["cpu_baseline"] = None
     if rank == 0 and stub:
         out["data"] = "synthetic (TMAT_BENCH_STUB: stand-in analyser on the CPU, not a measurement)"
     if rank == 0 and rehearse:

@@ -22,7 +22,7 @@ def test_two_ranks_on_one_gpu():
         env.pop(k, None)
     images = 16
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           str(REPO / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--images", str(images), "--max-patches", "400"]
+           str(REPO / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--images", str(images), "--max-patches", "400", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
