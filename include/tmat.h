@@ -361,6 +361,35 @@ int tmat_inv_depth_predict(tmat_handle h, const int *model_ids, int n_models, co
 int tmat_inv_depth_predict_multi(tmat_handle h, const int *model_ids, int n_models, const uint16_t *const *stacks, const int *Zs,
                                  int n_stacks, int H, int W, int size, float *probs);
 
+/*
+ * Arithmetic of the classifier's convolutions (the 40 trunk convolutions and the im2col stem convolution of every model).
+ *   TMAT_RESNET_PRECISION_F32 (default) f32 operands on v_mfma_f32_32x32x2_f32: bit-exact with oracle/resnet.py.
+ *   TMAT_RESNET_PRECISION_F16 opt-in: in each of those convolutions the input activation and the weight are each rounded ONCE to
+ *       IEEE binary16, round to nearest even, magnitudes above 65504 saturating to +-65504 (never inf / NaN; f16 subnormals are
+ *       kept, the matrix instruction does not flush them); products exact; accumulation in f32 on v_mfma_f32_32x32x16_f16 in a
+ *       fixed order (same input -> same bits, call after call); everything behind the accumulator is the f32 code of the default
+ *       mode (fmaf(acc, scale, shift), residual add, ReLU) and activations stay f32 in memory.  Data preparation, im2col,
+ *       max-pool, global average, dense unit and sigmoid are unchanged.  NOT bit-exact with oracle/resnet.py: on synthetic
+ *       ensembles a member's probability moves by up to ~2e-3 and the ensemble mean by a few 1e-4, so the 4th decimal of the
+ *       printed probability changes on most slices (DESIGN 7c has the measured figures; fine-tuned checkpoints are unmeasured).
+ * Works on any handle (tmat_create_plain included), independent of tmat_set_precision; drains the handle's streams, then
+ * applies to the calls that follow (tmat_resnet_predict, tmat_inv_depth_predict, tmat_inv_depth_predict_multi).  The f16
+ * copy of a model's weights is made on the host when the mode is first on and freed with the model.  Other values:
+ * TMAT_E_ARG.  TMAT_INV_DEPTH_PRECISION=f32|f16 selects the mode at handle creation (any other value fails creation).
+ */
+#define TMAT_RESNET_PRECISION_F32 0
+#define TMAT_RESNET_PRECISION_F16 1
+int tmat_resnet_set_precision(tmat_handle h, int mode);
+/*
+ * Stage-wise test entry point: ONE convolution of conv_mfma_kernel on host buffers.  x (n, hh, ww, cin) f32; w in the Keras
+ * layout (ksize, ksize, cin, cout); ksize 1 (stride 1 or 2, TF SAME: even indices) or 3 (stride 1, SAME); cin % 32 == 0 (and
+ * 9 cin / 32 even for ksize 3), cout 64 or a multiple of 128; v = scale ? fmaf(acc, scale, shift) : acc + shift, + resid
+ * (nullable, shaped like out), ReLU on load / on store as asked; out (n, hh / stride, ww / stride, cout).  prec 0: the f32
+ * contract (bit-exact with oracle/unet.py:_conv); prec 3: the f16 contract above.
+ */
+int tmat_conv2d(tmat_handle h, int prec, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int stride, int cout,
+                const float *scale, const float *shift, const float *resid, int relu_in, int relu_out, float *out);
+
 /* device memory helpers so a ctypes host can stage inputs in HBM without torch */
 int tmat_dev_alloc(tmat_handle h, size_t bytes, void **dev_ptr);
 int tmat_dev_free(tmat_handle h, void *dev_ptr);

@@ -175,17 +175,65 @@ static bool load_conv(ResNetModel &m, const std::map<std::string, Tensor> &t, co
     return up(m, k_contiguous(W.data, ksize * ksize, c.cin, c.cout), &c.w) && up(m, sc, &c.scale) && up(m, sh, &c.shift);
 }
 
-static bool run_conv(const ResConv &c, const float *in, int N, int h, const float *resid, int relu, float *out, hipStream_t s)
+// IEEE binary16 bits of x: round to nearest even, magnitudes above 65504 saturate to +-65504 (never inf; no NaNs in weights), results
+// below 2^-14 are f16 subnormals (kept as such: DESIGN 7c says what the matrix instruction does with them).
+static uint16_t f16_rne_sat(float x)
+{
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+    u &= 0x7fffffffu;
+    if (u >= 0x477fe000u) return sign | 0x7bffu;          // |x| >= 65504 (and inf / NaN): saturate
+    float ax;
+    memcpy(&ax, &u, 4);
+    if (u < 0x38800000u) {                                  // |x| < 2^-14: subnormal f16, grid 2^-24
+        // |x| 2^24 < 2^10 (exact) rounds to an integer, nearest even, in the addition of 2^23
+        float r = ax * 16777216.0f + 8388608.0f;
+        uint32_t ru;
+        memcpy(&ru, &r, 4);
+        return sign | (uint16_t)(ru - 0x4b000000u);         // 0 .. 1024 (1024 = the smallest normal)
+    }
+    // normal: keep 10 mantissa bits, nearest even on the 13 dropped ones (a carry into the exponent is the right answer)
+    const uint32_t rounded = u + 0x00000fffu + ((u >> 13) & 1u);
+    return sign | (uint16_t)(((rounded >> 13) - ((127u - 15u) << 10)) & 0x7fffu);
+}
+// one f16 plane of a device f32 weight tensor (n elements, the tensor's own [tap][Cout][Cin] layout), converted on the host
+static bool f16_plane(ResNetModel &m, const float *dev, size_t n, void **out)
+{
+    std::vector<float> w(n);
+    if (!hip_ok(hipMemcpy(w.data(), dev, n * 4, hipMemcpyDeviceToHost), "hipMemcpy(resnet weights, D2H)")) return false;
+    std::vector<uint16_t> q(n);
+    for (size_t i = 0; i < n; i++) q[i] = f16_rne_sat(w[i]);
+    if (!hip_ok(hipMalloc(out, n * 2), "hipMalloc(resnet f16 weights)")) return false;
+    m.owned.push_back(*out);
+    return hip_ok(hipMemcpy(*out, q.data(), n * 2, hipMemcpyHostToDevice), "hipMemcpy(resnet f16 weights)");
+}
+static bool ensure_f16(ResNetModel &m)
+{
+    if (m.has_f16) return true;
+    auto one = [&](ResConv &c) { return c.w16 || f16_plane(m, c.w, (size_t)c.ksize * c.ksize * c.cin * c.cout, &c.w16); };
+    if (!m.stem_w16 && !f16_plane(m, m.stem_w, (size_t)64 * STEM_K, &m.stem_w16)) return false;
+    for (ResBlock &k : m.blocks)
+        if (!one(k.c1) || !one(k.c2) || !one(k.c3) || (k.has_sc && !one(k.sc))) return false;
+    m.has_f16 = true;
+    return true;
+}
+
+// prec: 0 (f32, bit-exact contract) or 3 (f16 operands: the model's f16 planes, made by ensure_f16)
+static bool run_conv(const ResConv &c, int prec, const float *in, int N, int h, const float *resid, int relu, float *out, hipStream_t s)
 {
     ConvArgs a{};
     a.in = in; a.N = N; a.h = h; a.w = h; a.Cin = c.cin; a.relu_in = 0; a.ksize = c.ksize; a.stride = c.stride; a.W = c.w; a.Cout = c.cout;
     a.scale = c.scale; a.shift = c.shift; a.resid = resid; a.rs = 0; a.relu_out = relu; a.out = out;
+    if (prec == 3) { a.W = (const float *)c.w16; a.prec = 3; }
     return launch_conv(a, s);
 }
 
 // x (N, S, S, 3) f32 on the device -> prob (N) on the device; bufs: 4 activation buffers of N * (S/2)^2 * 64 floats; col: N * (S/2)^2 * 192
-static int resnet_forward_dev(const ResNetModel &m, const float *x, int N, int S, float *const bufs[4], float *col, float *prob, hipStream_t s)
+static int resnet_forward_dev(const ResNetModel &m, int mode, const float *x, int N, int S, float *const bufs[4], float *col, float *prob, hipStream_t s)
 {
+    const int prec = mode == TMAT_RESNET_PRECISION_F16 ? 3 : 0;
+    if (prec == 3 && !m.has_f16) { set_error("resnet: the model has no f16 weights (tmat_resnet_set_precision makes them)"); return TMAT_E_ARG; }
     float *a = bufs[0], *b = bufs[1], *t1 = bufs[2], *t2 = bufs[3];
     const int S2 = S / 2, S4 = S / 4;
     {
@@ -194,6 +242,7 @@ static int resnet_forward_dev(const ResNetModel &m, const float *x, int N, int S
         ConvArgs st{};
         st.in = col; st.N = N; st.h = S2; st.w = S2; st.Cin = STEM_K; st.relu_in = 0; st.ksize = 1; st.stride = 1; st.W = m.stem_w; st.Cout = 64;
         st.scale = m.stem_scale; st.shift = m.stem_shift; st.resid = nullptr; st.rs = 0; st.relu_out = 1; st.out = a;
+        if (prec == 3) { st.W = (const float *)m.stem_w16; st.prec = 3; }
         if (!launch_conv(st, s)) return TMAT_E_ARG;
     }
     const size_t ptotal = (size_t)N * S4 * S4 * 64;
@@ -204,13 +253,13 @@ static int resnet_forward_dev(const ResNetModel &m, const float *x, int N, int S
         const int ho = h / k.c1.stride;
         const float *shortcut = cur;
         if (k.has_sc) {
-            if (!run_conv(k.sc, cur, N, h, nullptr, 0, t2, s)) return TMAT_E_ARG;
+            if (!run_conv(k.sc, prec, cur, N, h, nullptr, 0, t2, s)) return TMAT_E_ARG;
             shortcut = t2;
         }
-        if (!run_conv(k.c1, cur, N, h, nullptr, 1, t1, s)) return TMAT_E_ARG;
-        if (!run_conv(k.c2, t1, N, ho, nullptr, 1, nxt, s)) return TMAT_E_ARG;
+        if (!run_conv(k.c1, prec, cur, N, h, nullptr, 1, t1, s)) return TMAT_E_ARG;
+        if (!run_conv(k.c2, prec, t1, N, ho, nullptr, 1, nxt, s)) return TMAT_E_ARG;
         // c3 writes over t1 (its input is nxt), then the roles rotate: out -> cur
-        if (!run_conv(k.c3, nxt, N, ho, shortcut, 1, t1, s)) return TMAT_E_ARG;
+        if (!run_conv(k.c3, prec, nxt, N, ho, shortcut, 1, t1, s)) return TMAT_E_ARG;
         float *old = cur;
         cur = t1; t1 = old;
         h = ho;
@@ -218,6 +267,15 @@ static int resnet_forward_dev(const ResNetModel &m, const float *x, int N, int S
     if (m.feat > 1024) { set_error("resnet: head supports at most 1024 channels"); return TMAT_E_ARG; }
     hipLaunchKernelGGL(resnet_head_kernel, dim3(N), dim3(1024), 0, s, cur, h * h, m.feat, m.fc_w, m.fc_b, prob);
     return hipGetLastError() == hipSuccess ? TMAT_OK : TMAT_E_HIP;
+}
+
+int resnet_precision_from_env(Ctx *c)
+{
+    const char *e = getenv("TMAT_INV_DEPTH_PRECISION");
+    if (!e || !strcmp(e, "f32")) return TMAT_OK;
+    if (strcmp(e, "f16")) { set_error("TMAT_INV_DEPTH_PRECISION must be f32 or f16"); return TMAT_E_ARG; }
+    c->resnet_precision = TMAT_RESNET_PRECISION_F16;      // no classifier is loaded yet: tmat_resnet_load makes the f16 planes
+    return TMAT_OK;
 }
 
 int launch_resize_linear_dev(const uint16_t *din, int n, int H, int W, int oh, int ow, bool eight_bit, int *tab, uint16_t *dsm, hipStream_t s);      // cellarea_kernels.hip
@@ -271,9 +329,63 @@ int tmat_resnet_load(tmat_handle hd, const void *weights_blob, size_t n_bytes, i
     m.feat = cin;
     m.fc_b = fb->second.data[0];
     if (!up(m, std::vector<float>(fw->second.data, fw->second.data + cin), &m.fc_w)) return fail();
+    if (c->resnet_precision == TMAT_RESNET_PRECISION_F16 && !ensure_f16(m)) return fail();
     c->resnets.push_back(std::move(m));
     *model_id = (int)c->resnets.size() - 1;
     return TMAT_OK;
+}
+
+int tmat_resnet_set_precision(tmat_handle hd, int mode)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!c || (mode != TMAT_RESNET_PRECISION_F32 && mode != TMAT_RESNET_PRECISION_F16)) {
+        set_error("tmat_resnet_set_precision: needs a handle and mode TMAT_RESNET_PRECISION_F32 or TMAT_RESNET_PRECISION_F16");
+        return TMAT_E_ARG;
+    }
+    TMAT_HIP(hipSetDevice(c->device));
+    { const int rc = tmat_sync(hd); if (rc) return rc; }      // nothing in flight runs across the switch
+    if (mode == TMAT_RESNET_PRECISION_F16)
+        for (ResNetModel &m : c->resnets) if (!ensure_f16(m)) return TMAT_E_HIP;
+    c->resnet_precision = mode;
+    return TMAT_OK;
+}
+
+// Stage-wise test entry point: ONE launch_conv on host buffers.  x (n, hh, ww, cin); w in the Keras layout (ksize, ksize, cin, cout);
+// scale nullable (plain bias); resid nullable, (n, hh / stride, ww / stride, cout); out the same shape.  prec 0: f32, 3: f16 operands.
+int tmat_conv2d(tmat_handle hd, int prec, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int stride, int cout,
+                const float *scale, const float *shift, const float *resid, int relu_in, int relu_out, float *out)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!c || !x || !w || !shift || !out || (prec != 0 && prec != 3) || n < 1 || hh < 1 || ww < 1 || cin < 1 || cout < 1 || (ksize != 1 && ksize != 3) ||
+        (stride != 1 && stride != 2) || hh % stride || ww % stride) {
+        set_error("tmat_conv2d: bad argument (prec 0 or 3, ksize 1 or 3, stride 1 or 2)");
+        return TMAT_E_ARG;
+    }
+    TMAT_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t nx = (size_t)n * hh * ww * cin, nw = (size_t)ksize * ksize * cin * cout, no = (size_t)n * (hh / stride) * (ww / stride) * cout;
+    const std::vector<float> wk = k_contiguous(w, ksize * ksize, cin, cout);
+    std::vector<uint16_t> wq;
+    if (prec == 3) { wq.resize(nw); for (size_t i = 0; i < nw; i++) wq[i] = f16_rne_sat(wk[i]); }
+    float *dx = nullptr, *dsc = nullptr, *dsh = nullptr, *dr = nullptr, *dout = nullptr;
+    void *dw = nullptr;
+    int rc = TMAT_OK;
+    auto put = [&](void **d, const void *src, size_t bytes) {
+        return hip_ok(hipMalloc(d, bytes), "hipMalloc(tmat_conv2d)") && hip_ok(hipMemcpyAsync(*d, src, bytes, hipMemcpyHostToDevice, s), "H2D");
+    };
+    if (!put((void **)&dx, x, nx * 4) || !put(&dw, prec == 3 ? (const void *)wq.data() : (const void *)wk.data(), prec == 3 ? nw * 2 : nw * 4) ||
+        !put((void **)&dsh, shift, (size_t)cout * 4) || (scale && !put((void **)&dsc, scale, (size_t)cout * 4)) ||
+        (resid && !put((void **)&dr, resid, no * 4)) || !hip_ok(hipMalloc((void **)&dout, no * 4), "hipMalloc(tmat_conv2d)")) rc = TMAT_E_HIP;
+    if (!rc) {
+        ConvArgs a{};
+        a.in = dx; a.N = n; a.h = hh; a.w = ww; a.Cin = cin; a.relu_in = relu_in != 0; a.ksize = ksize; a.stride = stride; a.W = (const float *)dw;
+        a.Cout = cout; a.scale = dsc; a.shift = dsh; a.resid = dr; a.rs = 0; a.relu_out = relu_out != 0; a.out = dout; a.prec = prec;
+        if (!launch_conv(a, s)) rc = TMAT_E_ARG;
+        else if (!hip_ok(hipGetLastError(), "tmat_conv2d launch") || !hip_ok(hipMemcpyAsync(out, dout, no * 4, hipMemcpyDeviceToHost, s), "D2H")) rc = TMAT_E_HIP;
+    }
+    if (!hip_ok(hipStreamSynchronize(s), "sync") && !rc) rc = TMAT_E_HIP;      // also drains the uploads from wk / wq before they go out of scope
+    hipFree(dx); hipFree(dw); hipFree(dsc); hipFree(dsh); hipFree(dr); hipFree(dout);
+    return rc;
 }
 
 int tmat_resnet_predict(tmat_handle hd, int model_id, const float *x, int n, int size, float *prob)
@@ -290,7 +402,7 @@ int tmat_resnet_predict(tmat_handle hd, int model_id, const float *x, int n, int
         !hip_ok(hipMalloc((void **)&col, nb * 3 * 4), "hipMalloc")) rc = TMAT_E_HIP;      // 192 = 3 x 64 values per stem output pixel
     for (int i = 0; i < 4 && !rc; i++) if (!hip_ok(hipMalloc((void **)&bufs[i], nb * 4), "hipMalloc")) rc = TMAT_E_HIP;
     if (!rc && !hip_ok(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s), "H2D")) rc = TMAT_E_HIP;
-    if (!rc) rc = resnet_forward_dev(c->resnets[model_id], dx, n, size, bufs, col, dp, s);
+    if (!rc) rc = resnet_forward_dev(c->resnets[model_id], c->resnet_precision, dx, n, size, bufs, col, dp, s);
     if (!rc && (!hip_ok(hipMemcpyAsync(prob, dp, n * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))) rc = TMAT_E_HIP;
     hipFree(dx); hipFree(dp); hipFree(col);
     for (float *b : bufs) hipFree(b);
@@ -343,7 +455,7 @@ static int inv_depth_impl(tmat_handle hd, const int *model_ids, int n_models, co
             for (int mi = 0; mi < n_models && !rc; mi++)
                 for (int z0 = 0; z0 < Z && !rc; z0 += CH) {
                     const int k = std::min(CH, Z - z0);
-                    rc = resnet_forward_dev(c->resnets[model_ids[mi]], dx + (size_t)z0 * npx * 3, k, size, bufs, col, dp + (size_t)mi * Z + z0, s);
+                    rc = resnet_forward_dev(c->resnets[model_ids[mi]], c->resnet_precision, dx + (size_t)z0 * npx * 3, k, size, bufs, col, dp + (size_t)mi * Z + z0, s);
                 }
             std::vector<float> ph((size_t)Z * n_models);
             if (!rc && (!hip_ok(hipMemcpyAsync(ph.data(), dp, ph.size() * 4, hipMemcpyDeviceToHost, s), "D2H") ||

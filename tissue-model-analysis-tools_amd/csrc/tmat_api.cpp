@@ -513,6 +513,7 @@ int tmat_create_plain(int device_id, tmat_handle *out)
     Ctx *c = new Ctx();
     c->device = device_id;
     if (!hip_ok(hipStreamCreate(&c->stream), "hipStreamCreate")) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
+    { const int rc = resnet_precision_from_env(c); if (rc) { tmat_destroy((tmat_handle)c); return rc; } }
     *out = (tmat_handle)c;
     return TMAT_OK;
 }
@@ -545,6 +546,7 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
         delete c;
         return TMAT_E_ARG;
     }
+    { const int rc = resnet_precision_from_env(c); if (rc) { delete c; return rc; } }
     if (const char *e = getenv("TMAT_DMT_DEVICE")) c->dmt_device = atoi(e) != 0;
     if (const char *e = getenv("TMAT_DMT_SWEEP_DEVICE")) c->dmt_sweep_device = atoi(e) != 0;
     if (const char *e = getenv("TMAT_PRE_STREAM")) c->pre_side = atoi(e) != 0;

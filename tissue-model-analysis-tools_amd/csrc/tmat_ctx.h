@@ -78,10 +78,16 @@ bool parse_blob(const void *blob, size_t nbytes, std::map<std::string, Tensor> &
 std::vector<float> k_contiguous(const float *w, int taps, int I, int O);        // [taps][I][O] -> [taps][O][I]
 
 // ResNet50 classifier of the invasion-depth tool (resnet_kernels.hip)
-struct ResConv { int cin = 0, cout = 0, ksize = 1, stride = 1; float *w = nullptr, *scale = nullptr, *shift = nullptr; };
+struct ResConv {
+    int cin = 0, cout = 0, ksize = 1, stride = 1;
+    float *w = nullptr, *scale = nullptr, *shift = nullptr;
+    void *w16 = nullptr;      // the same [tap][Cout][Cin] tensor as one IEEE f16 plane (TMAT_RESNET_PRECISION_F16; made when the mode is first on)
+};
 struct ResBlock { ResConv c1, c2, c3, sc; bool has_sc = false; };
 struct ResNetModel {
     float *stem_w = nullptr, *stem_scale = nullptr, *stem_shift = nullptr;      // [147][64], folded BN
+    void *stem_w16 = nullptr;                                                   // f16 plane of stem_w (see ResConv::w16)
+    bool has_f16 = false;                                                       // every w16 / stem_w16 of the model is made (they are in `owned`)
     std::vector<ResBlock> blocks;
     float *fc_w = nullptr;
     float fc_b = 0.f;
@@ -168,6 +174,7 @@ struct Ctx {
     bool fused_pool = true;                                  // max-pool + residual add fused behind the second separable convolution (TMAT_FUSED_POOL=0: separate kernel)
     bool norm_on = false;                                    // models.py:636-637 input normalisation in front of the smooth prediction (tmat_set_input_norm)
     float norm_mean = 0.f, norm_std = 1.f;
+    int resnet_precision = 0;                                // invasion-depth classifiers: TMAT_RESNET_PRECISION_F32 (bit-exact contract) or _F16 (opt-in, tmat_resnet_set_precision)
     int precision = 0;                                       // TMAT_PRECISION_F32 (bit-exact contract) or TMAT_PRECISION_BF16X3 / _BF16X6 (opt-in, tmat_set_precision)
     std::map<const float *, ConvWHost> conv_w_host;          // device pointer of every MFMA convolution weight tensor -> its host copy
     std::map<int, std::map<const float *, float *>> wsplit;  // precision mode -> (... -> its split-precision copy on the device, made on first use)
@@ -228,6 +235,9 @@ inline void *ws_get(Ctx *c, int slot, size_t bytes)
     c->tool_ws_bytes[slot] = bytes ? bytes : 16;
     return c->tool_ws[slot];
 }
+
+// TMAT_INV_DEPTH_PRECISION=f32|f16 at handle creation (resnet_kernels.hip): TMAT_OK, or TMAT_E_ARG with the error set for any other value
+int resnet_precision_from_env(Ctx *c);
 
 // handles made by tmat_create_plain carry no model
 inline bool has_model(const Ctx *c) { return c && !c->up.empty(); }

@@ -27,7 +27,8 @@ struct ConvArgs {
     int relu_out;
     float *out;           // (N, h/stride, w/stride, Cout); ksize 2: (N, 2h, 2w, Cout)
     float *out_relu;      // nullable (ksize 1 / 3 only): a second, activated copy max(v, +0) of the output -- for a consumer that would otherwise apply ReLU on load
-    int prec;             // 0: f32 MFMA (bit-exact contract); 1: bf16x3 split precision, W then points to the split copy of the weights
+    int prec;             // 0: f32 MFMA (bit-exact contract); 1 / 2: bf16x3 / bf16x6 split precision, W then points to the split copy of the weights;
+                          // 3: f16 operands, one product (ksize 1 / 3 only), W points to the f16 plane of the weights
 };
 // returns false (and sets the error) on unsupported shapes
 bool launch_conv(const ConvArgs &a, hipStream_t s);

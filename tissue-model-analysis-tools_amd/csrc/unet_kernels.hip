@@ -41,6 +41,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // Exact division of a non-negative int (< 2^31) by a launch constant d >= 2 as one v_mul_hi_u32 and one shift: with
 // l = ceil(log2 d) and mul = ceil(2^(31 + l) / d) < 2^32, floor(n mul / 2^(31 + l)) = floor(n / d) for every n < 2^31 (the
@@ -77,6 +78,12 @@ __device__ __forceinline__ float relu_pos0(float v) { return __builtin_bit_cast(
 //   matrix pipe run side by side, unlike the f32 MFMA).  The WEIGHTS are split once on the host (tmat_api.cpp:split_bf16)
 //   into NPL = 2 / 3 bf16 PLANES [plane][tap][Cout][Cin]; a stage holds the A rows as in the f32 path and NPL weight planes
 //   of [BN rows][32 bf16] (64-byte rows, 16-byte unit u of row r in slot u ^ ((r >> 2) & 3): conflict-free ds_read_b128).
+// PREC = 3: "f16", the opt-in mode of the invasion-depth classifier (tmat_resnet_set_precision): ONE product per k step on
+//   v_mfma_f32_32x32x16_f16.  Each activation (after the load-side ReLU) and each weight is rounded once to IEEE binary16, round to
+//   nearest even, magnitudes above 65504 saturating to +-65504 (v_med3_f32 in front of the conversion: never inf); products exact, f32
+//   accumulation in a fixed order.  The weights are ONE f16 plane [tap][Cout][Cin] made on the host (resnet_kernels.hip:f16_plane), staged
+//   exactly as a bf16 plane of PREC = 1; the A tile is DMA'd as f32 and converted in registers after the fragment read.  The epilogue is the
+//   f32 code of every other form.  Not instantiated for the sub-pixel form (KS == 2: UNet only).
 #ifdef TMAT_DIAG
 __device__ long long conv_diag[2048 * 8 * 8];      // [workgroup < 2048][wave][work, dma wait, barrier, fill, chunks, 1, epilogue]
 #endif
@@ -104,9 +111,10 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
     constexpr int KC = 32;
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int NPA = BM / RP, NPB = BN / RP;      // DMA passes
-    constexpr int NPL = PREC == 0 ? 0 : PREC + 1;                            // bf16 weight planes of the split-precision forms
+    constexpr int NPL = PREC == 0 ? 0 : PREC == 3 ? 1 : PREC + 1;            // 16-bit weight planes: bf16 of the split-precision forms, one f16 plane of PREC = 3
     constexpr int NPLA = NPL > 0 ? NPL : 1;                                  // array extent (the f32 instantiation never runs that code)
-    constexpr int STAGE = PREC == 0 ? (BM + BN) * KC : BM * KC + NPL * BN * 16;   // floats per stage: A rows, then B rows / B planes
+    // floats per stage: A rows, then B rows / B planes (PREC = 3: at least the epilogue's wave-private slabs, BM BN / 2 -- one 16-bit plane of a 128 x 128 tile is less)
+    constexpr int STAGE = PREC == 0 ? (BM + BN) * KC : PREC == 3 && BM * KC + BN * 16 < BM * BN / 2 ? BM * BN / 2 : BM * KC + NPL * BN * 16;
     static_assert(NPA >= 1 && NPA <= 8 && NPA * RP == BM, "A passes");
     static_assert(NPB >= 1 && NPB <= 4 && NPB * RP == BN, "B passes");
     static_assert(TM >= 1 && TN >= 1, "wave tile");
@@ -476,6 +484,42 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
         TMAT_LOOP_SYNC()                                                               \
     }
 
+    // f16 step (PREC = 3): the fragment geometry of the split-precision step (k step tk = channels 16 tk .. 16 tk + 15, a lane's 8 values are
+    // channels 16 tk + 8 h + j), one weight plane, one MFMA per (k step, wave tile).  All fragments of the chunk are read first (2 TM x 2
+    // + 2 TN ds_read_b128), the next chunk's DMA goes out behind them -- a chunk is 2 TM TN MFMAs, far too short to hide a DMA issued later --
+    // then conversion (v_med3_f32 clamp, which is also the ReLU of the RELU form: relu then clamp = med3(x, 0, 65504); RNE v_cvt) and MFMAs.
+#define TMAT_STEP_F16(cur, nxt, more, T_)                                              \
+    {                                                                                  \
+        float4 af[2][TM][2];                                                           \
+        f16x8 bh[2][TN];                                                               \
+        _Pragma("unroll") for (int tk = 0; tk < 2; tk++) {                             \
+            const int sa = ((4 * tk + 2 * hi) ^ key) * 4, sb = ((4 * tk + 2 * hi + 1) ^ key) * 4; \
+            _Pragma("unroll") for (int i = 0; i < TM; i++) {                           \
+                af[tk][i][0] = *reinterpret_cast<const float4 *>((cur) + arow + i * 32 * KC + sa); \
+                af[tk][i][1] = *reinterpret_cast<const float4 *>((cur) + arow + i * 32 * KC + sb); \
+            }                                                                          \
+            _Pragma("unroll") for (int jn = 0; jn < TN; jn++)                          \
+                bh[tk][jn] = *reinterpret_cast<const f16x8 *>((cur) + browp + jn * 32 * 16 + (((2 * tk + hi) ^ keyb) * 4)); \
+        }                                                                              \
+        TMAT_PIN()                                                                     \
+        if (more) TMAT_LOOP_ISSUE(nxt, T_)                                             \
+        TMAT_PIN()                                                                     \
+        _Pragma("unroll") for (int tk = 0; tk < 2; tk++) {                             \
+            f16x8 ah[TM];                                                              \
+            _Pragma("unroll") for (int i = 0; i < TM; i++) {                           \
+                const float xs[8] = {af[tk][i][0].x, af[tk][i][0].y, af[tk][i][0].z, af[tk][i][0].w, \
+                                     af[tk][i][1].x, af[tk][i][1].y, af[tk][i][1].z, af[tk][i][1].w}; \
+                _Pragma("unroll") for (int j = 0; j < 8; j++)                          \
+                    ah[i][j] = (_Float16)__builtin_amdgcn_fmed3f(xs[j], RELU ? 0.f : -65504.f, 65504.f); \
+            }                                                                          \
+            _Pragma("unroll") for (int i = 0; i < TM; i++)                             \
+                _Pragma("unroll") for (int jn = 0; jn < TN; jn++)                      \
+                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[tk][jn], acc[i][jn], 0, 0, 0); \
+        }                                                                              \
+        TMAT_PIN()                                                                     \
+        TMAT_LOOP_SYNC()                                                               \
+    }
+
 #ifdef TMAT_DIAG
     long long dg_work = 0, dg_vm = 0, dg_bar = 0;
     const long long dg_t0 = (long long)__builtin_readcyclecounter();
@@ -501,6 +545,15 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
                 else TMAT_STEP(stage0, stage1, more, (u + 1) % taps)
             }
         }
+    } else if constexpr (PREC == 3) {
+        for (int c = 0; c < nchunks; c += UNR) {
+#pragma unroll
+            for (int u = 0; u < UNR; u++) {
+                const bool more = u + 1 < UNR || c + UNR < nchunks;
+                if (u & 1) TMAT_STEP_F16(stage1, stage0, more, (u + 1) % taps)
+                else TMAT_STEP_F16(stage0, stage1, more, (u + 1) % taps)
+            }
+        }
     } else {
         for (int c = 0; c < nchunks; c += UNR) {
 #pragma unroll
@@ -511,6 +564,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
             }
         }
     }
+#undef TMAT_STEP_F16
 #undef TMAT_STEP_BF16
 #undef TMAT_STEP
 #undef TMAT_ORDER
@@ -690,6 +744,15 @@ static void launch_conv_ks(const ConvArgs &a, int M, int Ho, int Wo, hipStream_t
             hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, false, 2>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
         return;
     }
+    if constexpr (KS != 2) {
+        if (a.prec == 3) {
+            if (a.relu_in)
+                hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, true, 3>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
+            else
+                hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, false, 3>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
+            return;
+        }
+    }
     if (a.relu_in)
         hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, true>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
     else
@@ -740,7 +803,7 @@ bool launch_conv(const ConvArgs &a, hipStream_t s)
     const int Ho = a.h / a.stride, Wo = a.w / a.stride;
     const long long Mll = (long long)a.N * Ho * Wo;
     if (!((a.ksize == 3 && a.stride == 1) || (a.ksize == 2 && a.stride == 1 && !a.resid) ||
-          (a.ksize == 1 && (a.stride == 1 || a.stride == 2))) || a.Cin % 32 || a.Cout % 64 ||
+          (a.ksize == 1 && (a.stride == 1 || a.stride == 2))) || a.prec < 0 || a.prec > 3 || (a.prec == 3 && a.ksize == 2) || a.Cin % 32 || a.Cout % 64 ||
         ((a.ksize == 2 ? 4 : a.ksize * a.ksize) * (a.Cin / 32)) % ((a.ksize & 1) ? 2 * a.ksize * a.ksize : 4) || Mll <= 0 ||
         Mll > 0x7fffffffLL / 2 || (a.resid && a.rs && ((Ho | Wo) & 1)) || Wo < 2 || (a.out_relu && a.ksize == 2)) {
         set_error("launch_conv: unsupported shape");

@@ -82,6 +82,8 @@ def lib():
     L.tmat_resnet_predict.argtypes = [vp, i, vp, i, i, vp]
     L.tmat_inv_depth_predict.argtypes = [vp, vp, i, vp, i, i, i, i, vp, vp]
     L.tmat_inv_depth_predict_multi.argtypes = [vp, vp, i, vp, vp, i, i, i, i, vp]
+    L.tmat_resnet_set_precision.argtypes = [vp, i]
+    L.tmat_conv2d.argtypes = [vp, i, vp, i, i, i, i, vp, i, i, i, vp, vp, vp, i, i, vp]
     L.tmat_prof_enable.argtypes = [vp, i]
     L.tmat_debug_poison.argtypes = [vp, i]
     L.tmat_set_precision.argtypes = [vp, i]
@@ -109,7 +111,7 @@ EXPORTS = [
     "tmat_host_permutation", "tmat_host_postprocess",
     "tmat_set_gaussian_table", "tmat_host_gaussian_kernel1d", "tmat_gaussian_f32", "tmat_sato_batch", "tmat_stack_prepare", "tmat_vessel_field",
     "tmat_analyze_stack", "tmat_field_stats", "tmat_field_stats_pruned", "tmat_resize_aa_u16", "tmat_cell_area_batch", "tmat_cell_area_masked", "tmat_resize_linear_u16",
-    "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi",
+    "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi", "tmat_resnet_set_precision", "tmat_conv2d",
 ]
 
 
@@ -238,6 +240,36 @@ class Handle:
         if mode not in modes:
             raise ValueError(f"precision must be one of {sorted(modes)}")
         check(lib().tmat_set_precision(self._h, modes[mode]), "tmat_set_precision")
+
+    def resnet_set_precision(self, mode="f32"):
+        """arithmetic of the invasion-depth classifiers' convolutions: "f32" (bit-exact contract, default) or "f16" (opt-in: operands
+        rounded to IEEE f16, f32 accumulation on the f16 matrix cores; include/tmat.h:tmat_resnet_set_precision)"""
+        modes = {"f32": 0, "f16": 1}
+        if mode not in modes:
+            raise ValueError(f"precision must be one of {sorted(modes)}")
+        check(lib().tmat_resnet_set_precision(self._h, modes[mode]), "tmat_resnet_set_precision")
+
+    def conv2d(self, x, w, scale, shift, stride=1, resid=None, relu_in=False, relu_out=False, prec=0):
+        """stage-wise test entry point (include/tmat.h:tmat_conv2d): one convolution of the MFMA kernel.  x (n, h, w, cin), w in the Keras
+        layout (k, k, cin, cout), scale (nullable) / shift (cout), resid (nullable) shaped like the result; prec 0 (f32) or 3 (f16 operands)"""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(w, np.float32)
+        n, hh, ww, cin = x.shape
+        k, k2, ci2, cout = w.shape
+        if k != k2 or ci2 != cin:
+            raise ValueError("conv2d: weight shape does not match the input")
+        shift = np.ascontiguousarray(shift, np.float32)
+        scale = None if scale is None else np.ascontiguousarray(scale, np.float32)
+        out = np.empty((n, hh // stride, ww // stride, cout), np.float32)
+        if resid is not None:
+            resid = np.ascontiguousarray(resid, np.float32)
+            if resid.shape != out.shape:
+                raise ValueError("conv2d: resid must have the shape of the result")
+        if shift.shape != (cout,) or (scale is not None and scale.shape != (cout,)):
+            raise ValueError("conv2d: scale / shift must have cout entries")
+        check(lib().tmat_conv2d(self._h, int(prec), ptr(x), n, hh, ww, cin, ptr(w), k, int(stride), cout, None if scale is None else ptr(scale), ptr(shift),
+                                None if resid is None else ptr(resid), int(bool(relu_in)), int(bool(relu_out)), ptr(out)), "tmat_conv2d")
+        return out
 
     def debug_poison(self, byte_pattern=0xFF):
         """test-only: fill every scratch workspace of the handle with a byte pattern (include/tmat.h:tmat_debug_poison)"""
