@@ -490,6 +490,23 @@ int tmat_prof_read(tmat_handle h, double *ms, int64_t *launches, double *flops, 
  */
 int tmat_debug_poison(tmat_handle h, int byte_pattern);
 
+/*
+ * Region plan of the UNet up path for an (hh, ww) image tiled with `patch`-wide windows (host arithmetic, no GPU and no handle).
+ * The smooth blend discards the padding ring, so of every patch it reads the rectangle  patch ∩ interior  only; the tiled entry points
+ * compute just that rectangle, grown layer by layer by the taps' reach, in every up-path layer (TMAT_ROI=0 at tmat_create: whole
+ * patches, as tmat_unet_predict always does).  Patches with the same rectangle form a class (at most max_classes <= 16; *n_classes = 0
+ * reports the fall-back "everything" when there are more).  Within a pass of k images the patches are stored class-major:
+ *   position(img, tile) = k * base[c] + img * class_count[c] + tile_rank[tile],  c = tile_class[tile],  base[c] = sum of class_count[< c],
+ * tile = the image-major index (orientation-major, then a, then b) of a patch in its image; *tiles_per_img <= tiles_cap of them.
+ * channels: n_up + 1 entries, the input channels of up block 0, then the output channels of every up block.
+ * Layers l = 0 .. 3 n_up: per up block j the first convolution (3 j; sub-pixel form for j > 0: STORED pixels are enumerated), the residual
+ * 1x1 (3 j + 1) and the second convolution (3 j + 2), then the final convolution (stored pixels).
+ * rects: [3 n_up + 1][max_classes][4] = y0, x0, rows, columns of what the layer computes for a patch of the class.
+ * mac_planned / mac_full: [3 n_up + 1] multiply-accumulates per image, planned and full-frame.
+ */
+int tmat_roi_plan(int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
+                  int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full);
+
 #ifdef __cplusplus
 }
 #endif

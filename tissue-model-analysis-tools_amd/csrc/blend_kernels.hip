@@ -28,6 +28,7 @@ TileGeom make_geom(int hh, int ww, int ws)
     int off = 0;
     for (int k = 0; k < 8; k++) { g.tile_off[k] = off; off += g.na[k & 1] * g.nb[k & 1]; }
     g.tiles_per_img = off;
+    g.order = nullptr;
     return g;
 }
 
@@ -50,6 +51,14 @@ __device__ __forceinline__ void pad_to_frame(int g, int y, int x, int Hp, int Wp
     else if (k == 1) { u = Wp - 1 - xp; v = y; }
     else if (k == 2) { u = Hp - 1 - y; v = Wp - 1 - xp; }
     else { u = xp; v = Hp - 1 - y; }
+}
+
+// where patch `tile` of image `img` lives in the patch batch of a pass of k images (TileGeom::order)
+__device__ __forceinline__ size_t patch_slot(const TileGeom &gm, int k, int img, int tile)
+{
+    if (!gm.order) return (size_t)img * gm.tiles_per_img + tile;
+    const int4 o = gm.order[tile];
+    return (size_t)k * o.x + (size_t)img * o.y + o.z;
 }
 
 // min / max of each image (float), one block per image; used for the pad value (x.min(), :77)
@@ -102,7 +111,7 @@ __global__ __launch_bounds__(256) void extract_tiles_kernel(const float *__restr
     y -= gm.aug; xx -= gm.aug;
     float v = padval[img];
     if (y >= 0 && y < gm.hh && xx >= 0 && xx < gm.ww) v = x[((size_t)img * gm.hh + y) * gm.ww + xx];
-    patches[(((size_t)img * gm.tiles_per_img + tile) * gm.ws + p) * gm.ws + q] = v;
+    patches[((patch_slot(gm, gridDim.z, img, tile)) * gm.ws + p) * gm.ws + q] = v;
 }
 void launch_extract_tiles(const float *x, const float *padval, int n, const TileGeom &g, float *patches, hipStream_t s)
 {
@@ -118,7 +127,6 @@ __global__ __launch_bounds__(256) void blend_kernel(const float *__restrict__ pr
     const int yo = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (xo >= gm.ww || yo >= gm.hh) return;
     const int y = yo + gm.aug, x = xo + gm.aug;
-    const float *pimg = pred + (size_t)img * gm.tiles_per_img * gm.ws * gm.ws;
     double total = 0.0;
 #pragma unroll
     for (int g = 0; g < 8; g++) {
@@ -136,7 +144,7 @@ __global__ __launch_bounds__(256) void blend_kernel(const float *__restrict__ pr
             for (int b = b_lo; b <= b_hi; b++) {
                 const int q = v - b * gm.step;
                 if (q >= gm.ws) continue;
-                const float pv = pimg[(((size_t)gm.tile_off[g] + a * nb + b) * gm.ws + p) * gm.ws + q];
+                const float pv = pred[(patch_slot(gm, gridDim.z, img, gm.tile_off[g] + a * nb + b) * gm.ws + p) * gm.ws + q];
                 const double w2 = win[p] * win[q];
                 acc = acc + (double)pv * w2;
             }

@@ -202,7 +202,7 @@ static int enqueue_back(Ctx *c, int k, int slot, const TileGeom &g)
     // waits for this pass's blend.  (Round 2 tried the same with a low-priority stream and saw nothing; the second stream has normal priority.)
     const bool tail_side = tail_on_side_stream();
     if (tail_side && c->blend_pending[slot ^ 1]) TMAT_HIP(hipStreamWaitEvent(s, c->ev_blend[slot ^ 1], 0));
-    int rc = g.tiles_per_img > c->max_patches ? TMAT_OK : unet_up_dev(c, c->dout[slot], k * g.tiles_per_img, c->patch_out, s);
+    int rc = g.tiles_per_img > c->max_patches ? TMAT_OK : unet_up_dev(c, c->dout[slot], k * g.tiles_per_img, c->patch_out, s, roi_find(c, g));
     if (rc) return rc;
     if (tail_side) {
         TMAT_HIP(hipEventRecord(c->ev_up[slot], s));
@@ -344,6 +344,7 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
     gp.fh = round_half_even((double)H * ((double)ds_width / (double)W));
     gp.fw = round_half_even((double)W * ((double)ds_width / (double)W));
     TileGeom g = make_geom(h, w, c->patch);
+    roi_attach(c, g);       // region form of the up path: g carries the class-major patch order for enqueue_pre / enqueue_back
     const int K = std::min(n, std::max(1, c->max_patches / g.tiles_per_img));      // one image per pass when it needs > max_patches
     { int rc0 = ensure_patch_io(c, K * g.tiles_per_img); if (rc0) return rc0; }
     int rc = ensure_pass_buffers(c, K, H, W, h, w, gp.fh, gp.fw);

@@ -284,19 +284,19 @@ static void prof_end(Ctx *c, hipStream_t st)
     hipEventRecord(c->ev_open.back().e1, st);
 }
 
-static bool conv(Ctx *c, ConvArgs a, hipStream_t st)
+static bool conv(Ctx *c, ConvArgs a, hipStream_t st, const RoiSegs *roi = nullptr)
 {
     bool dom = a.ksize == 3 && a.Cout % 128 == 0 && !a.relu_in;     // the conv_mfma_kernel<128,128,4,2,3,false> instantiation
-    if (dom) {
-        double H = (double)a.h, W = (double)a.w;
-        prof_begin(c, 2.0 * a.N * H * W * 9.0 * a.Cin * a.Cout, st);
+    if (dom) {      // the FLOPs the launch executes: region form -- its segments' pixels only
+        const double px = roi ? (double)roi->pixels() : (double)a.N * a.h * a.w;
+        prof_begin(c, 2.0 * px * 9.0 * a.Cin * a.Cout, st);
     }
     if (c->precision != TMAT_PRECISION_F32) {        // opt-in split precision: the same launch on the split copy of the weights
         auto &mp = c->wsplit[c->precision];
         auto it = mp.find(a.W);
         if (it != mp.end()) { a.W = it->second; a.prec = c->precision; }
     }
-    bool ok = launch_conv(a, st);
+    bool ok = launch_conv(a, st, roi);
     if (dom) prof_end(c, st);
     return ok;
 }
@@ -383,9 +383,63 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s)
 }
 
 // Up path (the MFMA-bound 3x3 transposed convolutions) + final conv: dout -> Y (n, P, P)
-int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s)
+// the segments of layer l for a pass of k images: one per class with a non-empty rectangle, in the class-major patch order
+static RoiSegs roi_segs(const RoiPlan &p, int l, int k)
+{
+    RoiSegs r{};
+    for (int cl = 0; cl < p.n_classes; cl++) {
+        const RoiRect &q = p.rect[l][cl];
+        if (q.rh <= 0 || q.rw <= 0 || p.class_count[cl] <= 0) continue;
+        RoiSeg &g = r.s[r.nseg++];
+        g.p0 = k * p.class_base[cl]; g.np = k * p.class_count[cl];
+        g.y0 = q.y0; g.x0 = q.x0; g.rh = q.rh; g.rw = q.rw;
+    }
+    return r;
+}
+
+const RoiPlan *roi_find(const Ctx *c, const TileGeom &g)
+{
+    if (!g.order) return nullptr;
+    for (const RoiEntry *e : c->roi_cache) if (e->order == g.order) return &e->plan;
+    return nullptr;
+}
+
+const RoiPlan *roi_attach(Ctx *c, TileGeom &g)
+{
+    g.order = nullptr;
+    if (!c->roi_on || g.tiles_per_img > c->max_patches || c->up.empty() || (int)c->up.size() > ROI_MAX_UP) return nullptr;
+    for (const RoiEntry *e : c->roi_cache)
+        if (e->plan.hh == g.hh && e->plan.ww == g.ww && e->plan.ws == g.ws) { g.order = e->order; return e->order ? &e->plan : nullptr; }
+    RoiEntry *e = new RoiEntry();
+    c->roi_cache.push_back(e);
+    int chan[ROI_MAX_UP + 1];
+    chan[0] = c->up[0].cin;
+    for (size_t j = 0; j < c->up.size(); j++) chan[j + 1] = c->up[j].cout;
+    if (!roi_make_plan(g.hh, g.ww, g.ws, (int)c->up.size(), chan, ROI_MAX_CLASSES, e->plan) || e->plan.n_classes == 0) {
+        e->plan.hh = g.hh; e->plan.ww = g.ww; e->plan.ws = g.ws; e->plan.n_classes = 0;       // remembered: this geometry stays full-frame
+        return nullptr;
+    }
+    const RoiPlan &p = e->plan;
+    std::vector<int4> tab(p.tiles_per_img);
+    for (int t = 0; t < p.tiles_per_img; t++) tab[t] = make_int4(p.class_base[p.tile_class[t]], p.class_count[p.tile_class[t]], p.tile_rank[t], 0);
+    // (a blocking copy into a fresh allocation, once per geometry and handle: nothing in flight reads it)
+    if (!hip_ok(hipMalloc((void **)&e->order, tab.size() * sizeof(int4)), "hipMalloc(patch order)") ||
+        !hip_ok(hipMemcpy(e->order, tab.data(), tab.size() * sizeof(int4), hipMemcpyHostToDevice), "hipMemcpy(patch order)")) {
+        if (e->order) hipFree(e->order);
+        e->order = nullptr; e->plan.n_classes = 0;
+        return nullptr;
+    }
+    g.order = e->order;
+    return &e->plan;
+}
+
+int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s, const RoiPlan *plan)
 {
     if (n <= 0) return TMAT_OK;
+    if (plan && (plan->n_classes <= 0 || plan->n_up != (int)c->up.size() || n % plan->tiles_per_img)) { set_error("unet_up_dev: region plan does not fit the batch"); return TMAT_E_ARG; }
+    const int kimg = plan ? n / plan->tiles_per_img : 0;
+    RoiSegs sg{};
+    auto segs = [&](int l) -> const RoiSegs * { if (!plan) return nullptr; sg = roi_segs(*plan, l, kimg); return &sg; };
     // S = stored tensor at resolution Hs; logical block input = Up^up(S).  `dout` is never recycled.
     const float *S = dout;
     int Hs = c->patch >> (1 + c->down.size()), up = 0;
@@ -402,11 +456,11 @@ int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s)
         a.W = u.ct[0];
         if (up) { a.ksize = 2; a.W = u.ct_sub; }      // 4 taps per output parity class instead of 9
         a.Cout = u.cout; a.scale = u.scale[0]; a.shift = u.shift[0]; a.relu_out = 1; a.out = t1;
-        if (!conv(c, a, s)) return TMAT_E_ARG;
+        if (!conv(c, a, s, segs(3 * (int)j))) return TMAT_E_ARG;
         ConvArgs r{};
         r.in = S; r.N = n; r.h = Hs; r.w = Hs; r.Cin = u.cin; r.ksize = 1; r.stride = 1; r.W = u.res_w; r.Cout = u.cout;
         r.scale = nullptr; r.shift = u.res_b; r.out = rr;
-        if (!conv(c, r, s)) return TMAT_E_ARG;
+        if (!conv(c, r, s, segs(3 * (int)j + 1))) return TMAT_E_ARG;
         const int Hl = Hs << up;
         ConvArgs b{};
         b.in = t1; b.N = n; b.h = Hl; b.w = Hl; b.Cin = u.cout; b.relu_in = 0; b.ksize = 3; b.stride = 1;
@@ -415,11 +469,11 @@ int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s)
         // the next block's first convolution reads relu(so): written here as a second output (the last block's output feeds the final conv as is)
         float *so_act = (c->relu_copy && j + 1 < c->up.size()) ? c->urelu[j & 1] : nullptr;
         b.out_relu = so_act;
-        if (!conv(c, b, s)) return TMAT_E_ARG;
+        if (!conv(c, b, s, segs(3 * (int)j + 2))) return TMAT_E_ARG;
         S = so; S_act = so_act; so_idx = so_idx == 2 ? 3 : 2;
         Hs = Hl; up = 1;
     }
-    launch_final(S, n, Hs, Hs, c->f_last, c->final_w, c->final_b, Y, s);
+    launch_final(S, n, Hs, Hs, c->f_last, c->final_w, c->final_b, Y, s, segs(3 * (int)c->up.size()));
     TMAT_HIP(hipGetLastError());
     return TMAT_OK;
 }
@@ -464,6 +518,7 @@ int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred
     if (c->norm_on) launch_norm_f32(x_dev, (size_t)n * hh * ww, c->norm_mean, c->norm_std, c->stream);
     const int P = c->patch;
     TileGeom g = make_geom(hh, ww, P);
+    const RoiPlan *plan = roi_attach(c, g);       // region form of the up path (null: oversize image, or TMAT_ROI=0)
     const int per_pass = std::max(1, c->max_patches / g.tiles_per_img);
     { int rc = ensure_patch_io(c, per_pass * g.tiles_per_img); if (rc) return rc; }
     size_t need_pv = (size_t)std::min(n, per_pass) * 2 * sizeof(float);
@@ -474,7 +529,9 @@ int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred
         const float *xi = x_dev + (size_t)i0 * hh * ww;
         launch_minmax_f32(xi, k, (size_t)hh * ww, mn, mx, c->stream);
         launch_extract_tiles(xi, mn, k, g, c->patch_in, c->stream);
-        int rc = unet_forward_dev(c, c->patch_in, k * g.tiles_per_img, c->patch_out, c->stream);
+        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream)
+                      : unet_forward_dev(c, c->patch_in, k * g.tiles_per_img, c->patch_out, c->stream);
+        if (!rc && plan) rc = unet_up_dev(c, c->dout[0], k * g.tiles_per_img, c->patch_out, c->stream, plan);
         if (rc) return rc;
         launch_blend(c->patch_out, c->win1d, k, g, pred_dev + (size_t)i0 * hh * ww, c->stream);
     }
@@ -537,6 +594,7 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     c->patch = patch;
     c->max_patches = max_patches > 0 ? max_patches : 400;
     if (const char *e = getenv("TMAT_FUSED_SEP")) c->fused_sep = atoi(e) != 0;
+    if (const char *e = getenv("TMAT_ROI")) c->roi_on = atoi(e) != 0;
     if (const char *e = getenv("TMAT_FUSED_POOL")) c->fused_pool = atoi(e) != 0;
     if (const char *e = getenv("TMAT_STEM_FUSED")) c->stem_fused = atoi(e) != 0;
     if (const char *e = getenv("TMAT_SEP_BF16")) c->sep_bf16 = atoi(e) != 0;
@@ -659,6 +717,7 @@ void tmat_destroy(tmat_handle h)
     if (c->patch_in) hipFree(c->patch_in);
     if (c->patch_in2) hipFree(c->patch_in2);
     if (c->patch_out) hipFree(c->patch_out);
+    for (RoiEntry *e : c->roi_cache) { if (e->order) hipFree(e->order); delete e; }
     if (c->scratch) hipFree(c->scratch);
     if (c->win1d) hipFree(c->win1d);
     if (c->ma_table) hipFree(c->ma_table);

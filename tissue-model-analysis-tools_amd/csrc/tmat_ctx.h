@@ -2,6 +2,7 @@
 #pragma once
 #include "tmat_internal.h"
 #include "gauss_tables.h"
+#include "roi_plan.h"
 
 #include <map>
 
@@ -22,6 +23,7 @@ struct UpBlock {
     float *res_w = nullptr, *res_b = nullptr;
 };
 struct ProfEv { hipEvent_t e0, e1; double flops; };
+struct RoiEntry { RoiPlan plan; int4 *order = nullptr; };       // order: device, [tiles_per_img] (TileGeom::order)
 // a device / pinned workspace a forward or a pass writes before it reads (tmat_debug_poison fills exactly these)
 struct WsEnt { void *p; size_t bytes; bool host; };
 struct ConvWHost { std::vector<float> w; int cin; };        // host copy of an MFMA convolution's weights ([rows][cin])
@@ -180,6 +182,10 @@ struct Ctx {
     std::map<int, std::map<const float *, float *>> wsplit;  // precision mode -> (... -> its split-precision copy on the device, made on first use)
     bool sep_bf16 = true;                                    // bf16x3 mode also runs the separable layers' pointwise part on the bf16 cores (TMAT_SEP_BF16=0: f32)
     bool stem_fused = true;                                  // the stem recomputed inside block 0's first separable convolution (TMAT_STEM_FUSED=0: stem_kernel writes its tensor)
+    // region form of the tiled up path (roi_plan.h): plans per image geometry, made on first use, with the device table of the class-major
+    // patch order (TileGeom::order).  TMAT_ROI=0: whole patches in every layer, image-major order
+    bool roi_on = true;
+    std::vector<RoiEntry *> roi_cache;
     bool fused_sep = true;                                   // fused depthwise -> pointwise kernel (sepconv_ws_kernel) where the level allows (TMAT_FUSED_SEP=0: separate kernels)
     // call-scoped device workspaces of the side tools (cell area, invasion depth), kept between calls: with the reference's default batch of 4 images a
     // hipMalloc / hipFree pair per buffer and call costs more than the batch's kernels.  Slot = a fixed id per buffer (ws_get below).
@@ -198,7 +204,12 @@ struct Ctx {
 int unet_forward_dev(Ctx *c, const float *X, int n, float *Y, hipStream_t s);
 int ensure_patch_io(Ctx *c, int n_patches);
 int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s);
-int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s);
+// plan (nullable): region form; n is then a whole number of images' patches in the plan's class-major order
+int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s, const RoiPlan *plan = nullptr);
+// the region plan of g's geometry (cached on the handle) and, in g.order, its patch order; null and the image-major order when the region
+// form is off, the image needs more patches than the workspace holds, or it has more classes than a launch carries
+const RoiPlan *roi_attach(Ctx *c, TileGeom &g);
+const RoiPlan *roi_find(const Ctx *c, const TileGeom &g);
 int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred_dev);      // x_dev is normalised in place when tmat_set_input_norm is on
 
 // numpy's pairwise summation of a contiguous f64 vector (np.add.reduce / np.mean inner loop):

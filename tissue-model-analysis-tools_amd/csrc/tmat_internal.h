@@ -30,8 +30,22 @@ struct ConvArgs {
     int prec;             // 0: f32 MFMA (bit-exact contract); 1 / 2: bf16x3 / bf16x6 split precision, W then points to the split copy of the weights;
                           // 3: f16 operands, one product (ksize 1 / 3 only), W points to the f16 plane of the weights
 };
-// returns false (and sets the error) on unsupported shapes
-bool launch_conv(const ConvArgs &a, hipStream_t s);
+// Region form of a launch (the tiled up path, roi_plan.h): the patches [p0, p0 + np) compute the rectangle (y0, x0, rh, rw) of their
+// output only (sub-pixel form and final convolution: of their STORED pixels).  The caller fills p0 .. rw of the non-empty segments, in
+// ascending patch order; launch_conv fills the rest for its tile size.
+struct RoiSeg {
+    int p0, np, y0, x0, rh, rw;
+    int mt0, M;                      // first M tile of the segment; its pixels np rh rw
+    unsigned dhw_mul; int dhw_sh;    // exact division by rh rw and by rw (unet_kernels.hip:FastDiv)
+    unsigned dw_mul; int dw_sh;
+};
+struct RoiSegs {
+    int nseg;
+    RoiSeg s[16];
+    long long pixels() const { long long t = 0; for (int i = 0; i < nseg; i++) t += (long long)s[i].np * s[i].rh * s[i].rw; return t; }
+};
+// returns false (and sets the error) on unsupported shapes; roi (nullable, stride 1 only): region form
+bool launch_conv(const ConvArgs &a, hipStream_t s, const RoiSegs *roi = nullptr);
 // strips of the pooled separable convolution (floats): sepconv_ws_kernels.hip
 size_t sepconv_pool_scratch_floats(int N, int H, int W, int Cout);
 // fused SeparableConv2D, wave-specialised (sepconv_ws_kernels.hip): depthwise taps dw9 [9][Cin], pointwise pwk [Cout][Cin] (k contiguous);
@@ -54,7 +68,8 @@ bool launch_sepconv_ws_stem(const float *x, int N, int H, int W, int Cin, const 
                             const float *dw9, const float *pwk, int Cout, const float *scale, const float *shift, int relu_out, float *out,
                             hipStream_t s);
 void launch_maxpool_add(const float *p2, int N, int H, int W, int C, const float *r, float *out, hipStream_t s, float *out_relu = nullptr);
-void launch_final(const float *S, int N, int h, int w, int C, const float *Wf, float bias, float *out, hipStream_t s);
+// roi (nullable): workgroups whose 8 x 16 stored pixels lie outside their patch's rectangle return at once
+void launch_final(const float *S, int N, int h, int w, int C, const float *Wf, float bias, float *out, hipStream_t s, const RoiSegs *roi = nullptr);
 
 // ---- tiling / blending (blend_kernels.hip) -------------------------------------------------
 // x: (n, hh, ww) f32; padval[n]; patches out: (n, 8, na_g, nb_g, ws, ws)
@@ -65,6 +80,9 @@ struct TileGeom {
     int na[2], nb[2];   // tile counts for even (k=0,2) / odd (k=1,3) rotations
     int tiles_per_img;  // sum over 8 orientations
     int tile_off[8];    // first tile index of orientation g within the image
+    // Patch order of a pass of k images.  Null: image-major, patch = img tiles_per_img + tile.  Else the class-major order of the region
+    // plan (roi_plan.h), a device table [tiles_per_img] of (class base, class count, rank in class, 0): patch = k base + img count + rank.
+    const int4 *order;
 };
 TileGeom make_geom(int hh, int ww, int ws);
 void launch_minmax_f32(const float *x, int n, size_t per, float *mn, float *mx, hipStream_t s);

@@ -16,6 +16,7 @@
 #include "../../include/tmat.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace tmat {
 
@@ -87,7 +88,15 @@ __device__ __forceinline__ float relu_pos0(float v) { return __builtin_bit_cast(
 #ifdef TMAT_DIAG
 __device__ long long conv_diag[2048 * 8 * 8];      // [workgroup < 2048][wave][work, dma wait, barrier, fill, chunks, 1, epilogue]
 #endif
-template <int BM, int BN, int WM, int WN, int KS, bool RELU, int PREC = 0>
+// ROI = true: the region form of the tiled up path (roi_plan.h).  M is cut into SEGMENTS, one per patch class: the patches [p0, p0 + np)
+// compute the rectangle (y0, x0, rh, rw) of their output only, so inside a segment pixel m is (p0 + m / (rh rw), y0 + (m / rw) % rh,
+// x0 + m % rw); a tile never straddles two segments, pixels past a segment's end take the out-of-range route of pixels past M, and the
+// border tests stay against the PATCH (a region edge is not an image edge).  Only the pixel <-> address conversions of the prologue and
+// the epilogue differ; the K loop, the LDS layout and the MFMA order are those of the full-frame form, so a computed pixel gets the same
+// bits.  A template flag and not a uniform branch: full-frame launches (tmat_unet_predict, oversize images, the ResNet) keep the code they
+// had, and the region form's longer address arithmetic stays out of their register budget.
+struct RoiNone {};
+template <int BM, int BN, int WM, int WN, int KS, bool RELU, int PREC = 0, bool ROI = false>
 #ifndef TMAT_CONV_WPS
 #define TMAT_CONV_WPS 4     // waves per SIMD the 8-wave conv kernel is compiled for (VGPR budget 512 / this)
 #endif
@@ -97,7 +106,7 @@ template <int BM, int BN, int WM, int WN, int KS, bool RELU, int PREC = 0>
 #ifndef TMAT_CONV4_WPS
 #define TMAT_CONV4_WPS 2    // 4-wave workgroups
 #endif
-__global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 > 65536 ? 2 : WM * WN == 8 ? (BM == 128 && BN == 64 ? TMAT_CONV64_WPS : TMAT_CONV_WPS) : TMAT_CONV4_WPS)) void conv_mfma_kernel(ConvArgs a, int M, int Ho, int Wo, int nMt, int nNt, FastDiv dHW, FastDiv dW, int nstat)
+__global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 > 65536 ? 2 : WM * WN == 8 ? (BM == 128 && BN == 64 ? TMAT_CONV64_WPS : TMAT_CONV_WPS) : TMAT_CONV4_WPS)) void conv_mfma_kernel(ConvArgs a, int Mf, int Ho, int Wo, int nMt, int nNt, FastDiv dHWf, FastDiv dWf, int nstat, std::conditional_t<ROI, RoiSegs, RoiNone> roi)
 {
     // KS (1, 2 or 3) is a template parameter so that the 3x3 and the pointwise instantiations are distinct kernels
     // (distinct names in rocprofv3 traces: the 3x3 <128,128,2,2,3,*> instantiations are the dominant kernel).
@@ -138,7 +147,25 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
     const int nt = nstat ? xcd % nNt : j % nNt;
     const int mt = nstat ? j * (8 / nNt) + xcd / nNt : (j / nNt) * 8 + xcd;
     if (mt >= nMt) return;
-    const int m0 = mt * BM, n0 = nt * BN;
+    // pixels m of this tile's segment: M of them, HW per patch in rows of Wr, first one (patch sn, row sy0, column sx0); full-frame: everything
+    int M = Mf, HW = Ho * Wo, Wr = Wo, sn = 0, sy0 = 0, sx0 = 0, mtl = mt;
+    FastDiv dHW = dHWf, dW = dWf;
+    if constexpr (ROI) {
+        int si = 0;
+        for (int k = 1; k < roi.nseg; k++) si = mt >= roi.s[k].mt0 ? k : si;        // scalar: mt and the table are uniform
+        M = roi.s[si].M; Wr = roi.s[si].rw; HW = roi.s[si].rh * Wr;
+        sn = roi.s[si].p0; sy0 = roi.s[si].y0; sx0 = roi.s[si].x0; mtl = mt - roi.s[si].mt0;
+        dHW = FastDiv{roi.s[si].dhw_mul, roi.s[si].dhw_sh}; dW = FastDiv{roi.s[si].dw_mul, roi.s[si].dw_sh};
+    }
+    // pixel m -> (patch, row, column) of the layer's output (sub-pixel form: of the stored tensor)
+    auto pixel_of = [&](int m, int &n, int &y, int &x) {
+        n = fdiv(m, dHW);
+        const int r = m - n * HW;
+        y = fdiv(r, dW);
+        x = r - y * Wr + sx0;
+        n += sn; y += sy0;
+    };
+    const int m0 = mtl * BM, n0 = nt * BN;
 
     const int t = threadIdx.x;
     const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -160,12 +187,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
     constexpr unsigned OOB = 0x80000000u;
     // pointwise, stride 1: the stored pixel of output m is m itself -- no index arithmetic at all (these layers have
     // K = Cin as small as 64, i.e. two chunks per tile, so a division-heavy prologue would show)
-    const bool flat = KS == 1 && a.stride == 1;
+    const bool flat = !ROI && KS == 1 && a.stride == 1;
     auto stored_pixel = [&](int m) {     // linear index of the stored pixel that output pixel m is centred on
-        const int n = fdiv(m, dHW);
-        const int r = m - n * (Ho * Wo);
-        const int yo = fdiv(r, dW);
-        return (n * a.h + yo * a.stride) * a.w + (r - yo * Wo) * a.stride;
+        int n, yo, xo;
+        pixel_of(m, n, yo, xo);
+        return (n * a.h + yo * a.stride) * a.w + xo * a.stride;
     };
     const int p0 = flat ? m0 : __builtin_amdgcn_readfirstlane(stored_pixel(m0));
     // Row-uniform form (round 4): a wave stages 8 consecutive output pixels per pass (rows 8 wave .. 8 wave + 7 of the pass), and with
@@ -173,7 +199,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
     // masks and the "past M" test run on the SCALAR unit (s_mul_hi_u32), and a lane only adds its column.  The generic form below costs
     // ~35 vector instructions per pass, a dozen of them quarter-rate (v_mul_hi / v_mul_lo / v_mad_u64), and every vector instruction of an
     // f32-MFMA kernel is matrix time: with K = 576 (the Cout = 64 layers) the prologue was 3 % of a tile.
-    const bool rowfast = !flat && (Wo & 7) == 0;
+    const bool rowfast = !flat && (Wr & 7) == 0;
     unsigned pv[NPA];       // voffset (bytes) of the staged pixel's channel group
     unsigned pm[NPA];       // generic form: mask of the taps that fall inside the image
     unsigned pvt[taps][NPA];
@@ -187,10 +213,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
             const int mb = m0 + i * RP + wave * 8;           // uniform; M % 8 == 0, so the 8 pixels are inside M or past it together
             const bool ok = mb < M;
             const int mm = ok ? mb : m0;
-            const int n = fdiv(mm, dHW);
-            const int r = mm - n * (Ho * Wo);
-            const int yo = fdiv(r, dW);
-            const int y = yo * a.stride, xs = (r - yo * Wo) * a.stride;
+            int n, yo, xo;
+            pixel_of(mm, n, yo, xo);
+            const int y = yo * a.stride, xs = xo * a.stride;
             const int x = xs + lx;
             pv[i] = (unsigned)(((n * a.h + y) * a.w + xs - p0) * a.Cin) * 4u + lane_pv;
             if (KS == 3) {
@@ -219,10 +244,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
             continue;
         }
         const int mm = ok ? m : m0;
-        const int n = fdiv(mm, dHW);
-        const int r = mm - n * (Ho * Wo);
-        const int yo = fdiv(r, dW);
-        const int y = yo * a.stride, x = (r - yo * Wo) * a.stride;
+        int n, yo, xo;
+        pixel_of(mm, n, yo, xo);
+        const int y = yo * a.stride, x = xo * a.stride;
         pv[i] = (unsigned)(((n * a.h + y) * a.w + x - p0) * a.Cin + c4) * 4u;
         // tap masks without branches: bit ky * 3 + kx is set when row y + ky - 1 and column x + kx - 1 lie inside the image
         unsigned msk = 1u;
@@ -633,7 +657,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
         // (and, M being a multiple of RPW then, inside M or past it together), so pixel -> (n, y, x) is SCALAR arithmetic (s_mul_hi_u32) on
         // the iteration's first pixel and a lane adds a kernel-constant offset.  The per-lane form cost ~23 vector instructions per iteration,
         // ten of them quarter-rate 32 / 64-bit multiplies: 4-5 % of a K = 576 tile (every vector instruction here is matrix time).
-        const bool efast = (Wo % RPW) == 0 && (RPW >> a.rs) >= 1;
+        const bool efast = (Wr % RPW) == 0 && (RPW >> a.rs) >= 1 && (sx0 & ((1 << a.rs) - 1)) == 0;
         const unsigned vo_r = (unsigned)((rsub >> a.rs) * a.Cout + quad * 4) * 4u;         // low-resolution residual: column (x0 + rsub) >> rs
         const unsigned vo_s = (unsigned)(2 * rsub * a.Cout + quad * 4) * 4u;               // sub-pixel scatter: column 2 (x0 + rsub) + spx
         // The residual rows are requested FIRST, all NIT of them, before the accumulators go through LDS: one wait for the lot under the
@@ -644,20 +668,17 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
             for (int it = 0; it < NIT; it++) {
                 float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
                 const int m_it = mw + it * RPW;
-                if (a.rs) {
+                if (a.rs || ROI) {       // (region form: the residual's address comes from the pixel's coordinates at rs = 0 as well)
                     if (efast) {
                         if (full || m_it < M) {
-                            const int un = fdiv(m_it, dHW);
-                            const int rr = m_it - un * (Ho * Wo);
-                            const int uy = fdiv(rr, dW), ux = rr - uy * Wo;
+                            int un, uy, ux;
+                            pixel_of(m_it, un, uy, ux);
                             const size_t ridx = ((size_t)un * rH + (uy >> a.rs)) * rW + (ux >> a.rs);
                             rv = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(a.resid + ridx * a.Cout + cbase) + vo_r);
                         }
                     } else if (full || m_it + rsub < M) {
-                        const int m = m_it + rsub;
-                        const int n = fdiv(m, dHW);
-                        const int rr = m - n * (Ho * Wo);
-                        const int y = fdiv(rr, dW), x = rr - y * Wo;
+                        int n, y, x;
+                        pixel_of(m_it + rsub, n, y, x);
                         const size_t ridx = ((size_t)n * rH + (y >> a.rs)) * rW + (x >> a.rs);
                         rv = *reinterpret_cast<const float4 *>(a.resid + ridx * a.Cout + co);
                     }
@@ -687,18 +708,29 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
                 if (efast) {
                     const int m_it = mw + it * RPW;
                     if (full || m_it < M) {
-                        const int un = fdiv(m_it, dHW);
-                        const int rr = m_it - un * (Ho * Wo);
-                        const int uy = fdiv(rr, dW), ux = rr - uy * Wo;
+                        int un, uy, ux;
+                        pixel_of(m_it, un, uy, ux);
                         const size_t oidx = ((size_t)un * 2 * Ho + 2 * uy + spy) * (2 * Wo) + 2 * ux + spx;
                         *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out + oidx * a.Cout + cbase) + vo_s) = v;
                     }
                 } else if (ok) {
-                    const int n = fdiv(m, dHW);
-                    const int rr = m - n * (Ho * Wo);
-                    const int y = fdiv(rr, dW), x = rr - y * Wo;
+                    int n, y, x;
+                    pixel_of(m, n, y, x);
                     const size_t oidx = ((size_t)n * 2 * Ho + 2 * y + spy) * (2 * Wo) + 2 * x + spx;
                     *reinterpret_cast<float4 *>(a.out + oidx * a.Cout + co) = v;
+                }
+            }
+            else if (ROI) {     // region form: the row's address from the pixel's coordinates (row-uniform when the segment's rows allow)
+                if (ok) {
+                    int n, y, x;
+                    pixel_of(efast ? mw + it * RPW : m, n, y, x);
+                    const size_t oofs = (((size_t)n * Ho + y) * Wo + x) * a.Cout + cbase;
+                    const unsigned lo = efast ? vo : (unsigned)(quad * 16);
+                    *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out + oofs) + lo) = v;
+                    if (a.out_relu) {
+                        v.x = relu_pos0(v.x); v.y = relu_pos0(v.y); v.z = relu_pos0(v.z); v.w = relu_pos0(v.w);
+                        *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out_relu + oofs) + lo) = v;
+                    }
                 }
             }
             else if (ok) {
@@ -722,41 +754,49 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
 #endif
 }
 
+template <int BM, int BN, int WM, int WN, int KS, int PREC, bool ROI>
+static void launch_conv_inst(const ConvArgs &a, int M, int Ho, int Wo, int nMt, int nNt, dim3 grid, FastDiv dHW, FastDiv dW, int nstat,
+                             std::conditional_t<ROI, RoiSegs, RoiNone> roi, hipStream_t s)
+{
+    if (a.relu_in)
+        hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, true, PREC, ROI>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat, roi);
+    else
+        hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, false, PREC, ROI>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat, roi);
+}
+
 template <int BM, int BN, int WM, int WN, int KS>
-static void launch_conv_ks(const ConvArgs &a, int M, int Ho, int Wo, hipStream_t s)
+static void launch_conv_ks(const ConvArgs &a, int M, int Ho, int Wo, hipStream_t s, const RoiSegs *roi)
 {
     int nMt = (M + BM - 1) / BM, nNt = a.Cout / BN;
+    RoiSegs rs{};
+    if (roi) {          // region form: the M tiles of the segments one after the other, a tile never straddling two of them
+        rs = *roi;
+        nMt = 0;
+        for (int i = 0; i < rs.nseg; i++) {
+            RoiSeg &g = rs.s[i];
+            g.M = g.np * g.rh * g.rw;
+            g.mt0 = nMt;
+            nMt += (g.M + BM - 1) / BM;
+            const FastDiv f = make_fastdiv(g.rh * g.rw), fw = make_fastdiv(g.rw);
+            g.dhw_mul = f.mul; g.dhw_sh = f.sh; g.dw_mul = fw.mul; g.dw_sh = fw.sh;
+        }
+    }
     dim3 grid(((nMt + 7) / 8) * 8 * nNt, KS == 2 ? 4 : 1);
     const FastDiv dHW = make_fastdiv(Ho * Wo), dW = make_fastdiv(Wo);
     // N-stationary block mapping (see the kernel) for layers whose weights do not stay in an XCD's L2
     const int nstat = (nNt > 1 && nNt <= 8 && 8 % nNt == 0 && (size_t)(KS == 2 ? 4 : KS * KS) * a.Cin * a.Cout * 4 > ((size_t)3 << 20)) ? 1 : 0;
-    if (a.prec == 1) {
-        if (a.relu_in)
-            hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, true, 1>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
-        else
-            hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, false, 1>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
+    if (roi) {          // (the UNet's precisions only: the f16 form belongs to the ResNet, which has no tiled blend)
+        if (a.prec == 1) launch_conv_inst<BM, BN, WM, WN, KS, 1, true>(a, M, Ho, Wo, nMt, nNt, grid, dHW, dW, nstat, rs, s);
+        else if (a.prec == 2) launch_conv_inst<BM, BN, WM, WN, KS, 2, true>(a, M, Ho, Wo, nMt, nNt, grid, dHW, dW, nstat, rs, s);
+        else launch_conv_inst<BM, BN, WM, WN, KS, 0, true>(a, M, Ho, Wo, nMt, nNt, grid, dHW, dW, nstat, rs, s);
         return;
     }
-    if (a.prec == 2) {
-        if (a.relu_in)
-            hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, true, 2>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
-        else
-            hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, false, 2>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
-        return;
-    }
+    if (a.prec == 1) { launch_conv_inst<BM, BN, WM, WN, KS, 1, false>(a, M, Ho, Wo, nMt, nNt, grid, dHW, dW, nstat, RoiNone{}, s); return; }
+    if (a.prec == 2) { launch_conv_inst<BM, BN, WM, WN, KS, 2, false>(a, M, Ho, Wo, nMt, nNt, grid, dHW, dW, nstat, RoiNone{}, s); return; }
     if constexpr (KS != 2) {
-        if (a.prec == 3) {
-            if (a.relu_in)
-                hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, true, 3>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
-            else
-                hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, false, 3>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
-            return;
-        }
+        if (a.prec == 3) { launch_conv_inst<BM, BN, WM, WN, KS, 3, false>(a, M, Ho, Wo, nMt, nNt, grid, dHW, dW, nstat, RoiNone{}, s); return; }
     }
-    if (a.relu_in)
-        hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, true>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
-    else
-        hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, false>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat);
+    launch_conv_inst<BM, BN, WM, WN, KS, 0, false>(a, M, Ho, Wo, nMt, nNt, grid, dHW, dW, nstat, RoiNone{}, s);
 #ifdef TMAT_DIAG
     if (KS == 3 && BN == 128 && !a.relu_in) {
         static long long zz[2048 * 8 * 8];
@@ -773,11 +813,11 @@ static void launch_conv_ks(const ConvArgs &a, int M, int Ho, int Wo, hipStream_t
 }
 
 template <int BM, int BN, int WM, int WN>
-static void launch_conv_cfg(const ConvArgs &a, int M, int Ho, int Wo, hipStream_t s)
+static void launch_conv_cfg(const ConvArgs &a, int M, int Ho, int Wo, hipStream_t s, const RoiSegs *roi)
 {
-    if (a.ksize == 3) launch_conv_ks<BM, BN, WM, WN, 3>(a, M, Ho, Wo, s);
-    else if (a.ksize == 2) launch_conv_ks<BM, BN, WM, WN, 2>(a, M, Ho, Wo, s);
-    else launch_conv_ks<BM, BN, WM, WN, 1>(a, M, Ho, Wo, s);
+    if (a.ksize == 3) launch_conv_ks<BM, BN, WM, WN, 3>(a, M, Ho, Wo, s, roi);
+    else if (a.ksize == 2) launch_conv_ks<BM, BN, WM, WN, 2>(a, M, Ho, Wo, s, roi);
+    else launch_conv_ks<BM, BN, WM, WN, 1>(a, M, Ho, Wo, s, roi);
 }
 
 #ifndef TMAT_WM
@@ -798,7 +838,7 @@ static void launch_conv_cfg(const ConvArgs &a, int M, int Ho, int Wo, hipStream_
 #define TMAT_64S_WN 1
 #endif
 
-bool launch_conv(const ConvArgs &a, hipStream_t s)
+bool launch_conv(const ConvArgs &a, hipStream_t s, const RoiSegs *roi)
 {
     const int Ho = a.h / a.stride, Wo = a.w / a.stride;
     const long long Mll = (long long)a.N * Ho * Wo;
@@ -810,16 +850,25 @@ bool launch_conv(const ConvArgs &a, hipStream_t s)
         return false;
     }
     const int M = (int)Mll;
+    if (roi) {      // every segment inside the batch and the patch, in ascending patch order, at least two pixels wide
+        bool ok = a.stride == 1 && a.prec != 3 && roi->nseg >= 1 && roi->nseg <= 16;
+        for (int i = 0, p = 0; ok && i < roi->nseg; i++) {
+            const RoiSeg &g = roi->s[i];
+            ok = g.p0 >= p && g.np >= 1 && g.p0 + g.np <= a.N && g.y0 >= 0 && g.x0 >= 0 && g.rh >= 1 && g.rw >= 2 && g.y0 + g.rh <= Ho && g.x0 + g.rw <= Wo;
+            p = g.p0 + g.np;
+        }
+        if (!ok) { set_error("launch_conv: bad region table"); return false; }
+    }
     if (a.Cout % 128 == 0)
-        launch_conv_cfg<TMAT_BM, 128, TMAT_WM, TMAT_WN>(a, M, Ho, Wo, s);
+        launch_conv_cfg<TMAT_BM, 128, TMAT_WM, TMAT_WN>(a, M, Ho, Wo, s, roi);
     else if (a.ksize == 2)
         // the sub-pixel layer with 64 output channels (16 chunks per tile, four parity classes): 256 x 64 tiles of eight 32 x 64 wave blocks
         // -- 32 MFMAs per wave and chunk instead of 16 -- measure 20.6 against 21.5 ms; the 3 x 3 layer prefers 128 x 64 (22.7 against 23.2)
-        launch_conv_ks<TMAT_64S_BM, 64, TMAT_64S_WM, TMAT_64S_WN, 2>(a, M, Ho, Wo, s);
+        launch_conv_ks<TMAT_64S_BM, 64, TMAT_64S_WM, TMAT_64S_WN, 2>(a, M, Ho, Wo, s, roi);
     else if (a.ksize == 3 && a.prec != 0)          // split precision: a chunk is short, the A-tile traffic per MFMA decides (12.5 -> 11.4 ms in bf16x3)
-        launch_conv_ks<256, 64, 8, 1, 3>(a, M, Ho, Wo, s);
+        launch_conv_ks<256, 64, 8, 1, 3>(a, M, Ho, Wo, s, roi);
     else
-        launch_conv_cfg<TMAT_64_BM, 64, TMAT_64_WM, TMAT_64_WN>(a, M, Ho, Wo, s);
+        launch_conv_cfg<TMAT_64_BM, 64, TMAT_64_WM, TMAT_64_WN>(a, M, Ho, Wo, s, roi);
     return true;
 }
 
@@ -1098,7 +1147,7 @@ __device__ __forceinline__ float exp_det(float x)
 // (15.6 GB of fabric reads for an 11.1 GB tensor).
 template <int CB>
 __global__ __launch_bounds__(128) void final_kernel(const float *__restrict__ S, int N, int h, int w, int C, int tw, int tpp,
-                                                    const float *__restrict__ Wq, float bias, float *__restrict__ out)
+                                                    const float *__restrict__ Wq, float bias, float *__restrict__ out, RoiSegs roi)
 {
     // The channels go through LDS in blocks of CB (the chain order -- 4-channel groups ascending -- is unchanged, the four
     // accumulators live in registers across the blocks): a workgroup holds 15 KiB at CB = 16 (28 at 32, 49 for all 64 channels),
@@ -1113,6 +1162,11 @@ __global__ __launch_bounds__(128) void final_kernel(const float *__restrict__ S,
     if (n >= N) return;
     const int tile_id = bj % tpp;
     const int j0 = (tile_id % tw) * 16, i0 = (tile_id / tw) * 8;
+    // region form (roi.nseg != 0; tiled callers, roi_plan.h): the blend reads nothing of a workgroup whose stored pixels lie outside its
+    // patch's rectangle -- it returns (scalar tests: the patch, the tile and the table are uniform)
+    for (int k = 0; k < roi.nseg; k++)
+        if (n >= roi.s[k].p0 && n < roi.s[k].p0 + roi.s[k].np &&
+            (i0 >= roi.s[k].y0 + roi.s[k].rh || i0 + 8 <= roi.s[k].y0 || j0 >= roi.s[k].x0 + roi.s[k].rw || j0 + 16 <= roi.s[k].x0)) return;
     const int qy = threadIdx.x >> 4, qx = threadIdx.x & 15;
     const int i = i0 + qy, jj = j0 + qx;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};             // classes (py, px) = (0,0), (0,1), (1,0), (1,1)
@@ -1175,18 +1229,20 @@ __global__ __launch_bounds__(128) void final_kernel(const float *__restrict__ S,
 }
 
 // Wq: [C/4][4][4][4] (tmat_api.cpp:final_subpixel_weights)
-void launch_final(const float *S, int N, int h, int w, int C, const float *Wq, float bias, float *out, hipStream_t s)
+void launch_final(const float *S, int N, int h, int w, int C, const float *Wq, float bias, float *out, hipStream_t s, const RoiSegs *roi)
 {
+    RoiSegs rs{};
+    if (roi) rs = *roi;
     const int tw = (w + 15) / 16, tpp = tw * ((h + 7) / 8);
     const dim3 grid((unsigned)(((N + 7) / 8) * 8 * tpp));           // N <= max_patches and tpp = 200 at 160 x 160: far below 2^31
     // channels per LDS block: 32 when the channel count allows (every shipped model: C = 64), else 16 / 8 / 4 (C % 4 == 0: tmat_create)
 #ifndef TMAT_FINAL_CB
 #define TMAT_FINAL_CB 16    // measured per launch of 1600 patches: 16 channels per LDS block 2.51 ms (15 KB of LDS: 8 workgroups = 16 waves per CU), 32: 3.22 ms (5 workgroups), 8: 4.16 ms
 #endif
-    if (C % 32 == 0) hipLaunchKernelGGL(final_kernel<TMAT_FINAL_CB>, grid, dim3(128), 0, s, S, N, h, w, C, tw, tpp, Wq, bias, out);
-    else if (C % 16 == 0) hipLaunchKernelGGL(final_kernel<16>, grid, dim3(128), 0, s, S, N, h, w, C, tw, tpp, Wq, bias, out);
-    else if (C % 8 == 0) hipLaunchKernelGGL(final_kernel<8>, grid, dim3(128), 0, s, S, N, h, w, C, tw, tpp, Wq, bias, out);
-    else hipLaunchKernelGGL(final_kernel<4>, grid, dim3(128), 0, s, S, N, h, w, C, tw, tpp, Wq, bias, out);
+    if (C % 32 == 0) hipLaunchKernelGGL(final_kernel<TMAT_FINAL_CB>, grid, dim3(128), 0, s, S, N, h, w, C, tw, tpp, Wq, bias, out, rs);
+    else if (C % 16 == 0) hipLaunchKernelGGL(final_kernel<16>, grid, dim3(128), 0, s, S, N, h, w, C, tw, tpp, Wq, bias, out, rs);
+    else if (C % 8 == 0) hipLaunchKernelGGL(final_kernel<8>, grid, dim3(128), 0, s, S, N, h, w, C, tw, tpp, Wq, bias, out, rs);
+    else hipLaunchKernelGGL(final_kernel<4>, grid, dim3(128), 0, s, S, N, h, w, C, tw, tpp, Wq, bias, out, rs);
 }
 
 }  // namespace tmat
