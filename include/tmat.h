@@ -188,6 +188,62 @@ int tmat_morse_stats(const int32_t *verts, int n_verts, const int32_t *edges, in
                      int remove_isolated_branches, const uint8_t *pruning_mask, int64_t *count,
                      double *total_px, double *avg_px, double *bars, int cap);
 
+/*
+ * The branch geometry MorseGraph.__compute_colored_tree_and_barcode(scaling_factor) builds (reference topology.py:358-389)
+ * for the branches that survive __filter_graph (:318-347), in the reference's order.  Same inputs and the same graph code
+ * as tmat_morse_stats, plus scaling_factor; needs no handle and no GPU.
+ * Per branch, _vertices[branch_vertices] * scaling_factor (float32, :380) goes through __moving_average_fixed_ends(., 3)
+ * (:458-515; branches of one or two vertices are returned unchanged, :470-471) and every pair of neighbours becomes one
+ * segment with the coordinates reversed (:386): x = column, y = row.
+ * segs (cap_s, 4) f64 [x1, y1, x2, y2]; seg_branch (cap_s) i32: index of the segment's branch; bars (cap_b, 2) f64
+ * [birth, death] * scaling_factor (:377), branch order; *n_segs, *n_bars: what was (or would be) written.
+ * *count, *total_px, *avg_px: as tmat_morse_stats returns them (unscaled).  TMAT_E_CAP when cap_s or cap_b is too small
+ * (*n_segs and *n_bars then hold the sizes needed).
+ */
+int tmat_morse_tree(const int32_t *verts, int n_verts, const int32_t *edges, int n_edges, int rows, int cols,
+                    int smoothing_window, int min_branch_length, int max_branch_length,
+                    int remove_isolated_branches, const uint8_t *pruning_mask, double scaling_factor, int64_t *count,
+                    double *total_px, double *avg_px, double *segs, int32_t *seg_branch, int cap_s, double *bars,
+                    int cap_b, int *n_segs, int *n_bars);
+
+/*
+ * Colour of branch i (reference topology.py:518-527, __random_color): hue byte = floor(180 * 0.618033988749895 * i) mod 256
+ * (the uint8 wrap of the reference's pinned numpy), H = 2 * hue byte degrees mod 360, S = 220 / 255, V = 1, the standard
+ * HSV -> RGB sextant formula in f64, each channel floor(255 v + 0.5).  The reference hands cv2's (B, G, R) triple to
+ * matplotlib as (R, G, B); rgb[] keeps that swap: rgb = (B, G, R).  cv2's own 8-bit HSV rounding is not pinned.
+ */
+int tmat_branch_color(int i, uint8_t *rgb);
+
+/*
+ * The tree overlay of compute_branches.py:431-450 (morse_tree*.png) as an RGB8 raster of the project's own specification
+ * (DESIGN.md "Tree overlay and barcode pictures"; matplotlib's pixels are not reproduced): the min-max rescaled background
+ * (:447) sampled nearest onto a vis_width x round_half_even(vis_width bh / bw) canvas, every segment a capsule of
+ * matplotlib's default 1.5 pt line width at 200 dpi, composited in segment order.  Batched: n backgrounds (n, bh, bw),
+ * bg_dtype 0 = u16, 1 = f32; segs (seg_offsets[n], 4) f64 in background pixels and seg_branch as tmat_morse_tree returns
+ * them, image i owning [seg_offsets[i], seg_offsets[i + 1]); rgb_out (n, vh, vw, 3) u8.  All pointers are host pointers.
+ * f32 backgrounds must be finite (a NaN or infinity makes the minimum / maximum, and so the picture, undefined); segments with a
+ * non-finite coordinate are skipped.
+ * tmat_render_tree rasterises on the handle's device (overlay_kernels.hip); tmat_host_render_tree is its host twin:
+ * the same bytes, no handle, no GPU.  tmat_render_tree_timed is tmat_render_tree that also reports where the call's time goes:
+ * ms4 = HIP-event milliseconds on the call's stream of {upload, min-max kernels, render kernels, copy back of the overlays}
+ * (tools/bench_overlay.py).
+ */
+int tmat_render_tree(tmat_handle h, const void *background, int bg_dtype, int n, int bh, int bw, const double *segs,
+                     const int32_t *seg_branch, const int32_t *seg_offsets, int vis_width, uint8_t *rgb_out);
+int tmat_render_tree_timed(tmat_handle h, const void *background, int bg_dtype, int n, int bh, int bw, const double *segs,
+                           const int32_t *seg_branch, const int32_t *seg_offsets, int vis_width, uint8_t *rgb_out, float *ms4);
+int tmat_host_render_tree(const void *background, int bg_dtype, int n, int bh, int bw, const double *segs,
+                          const int32_t *seg_branch, const int32_t *seg_offsets, int vis_width, uint8_t *rgb_out);
+
+/*
+ * plot_colored_barcode (reference topology.py:67-107) without axes or text: a white square canvas of
+ * round_half_even(0.9 vis_width) pixels, the bars (n, 2) f64 of tmat_morse_tree sorted by birth, descending and stable, bar k
+ * a rectangle of 0.8 row pitch on row k (row 0 lowest) from birth to death in the colour of its branch, the range
+ * [min birth, max death] mapped onto the width; integer pixel edges, no anti-aliasing.  Host only: a few
+ * hundred rectangles on a canvas that would cost more to copy back than to fill.  rgb_out (S, S, 3) u8.
+ */
+int tmat_host_render_barcode(const double *bars, int n, int vis_width, uint8_t *rgb_out);
+
 /* One result row per image, the payload gathered across ranks. */
 typedef struct tmat_row {
     int64_t index;   /* image index in the run                      */
@@ -213,6 +269,25 @@ int tmat_analyze_batch(tmat_handle h, const uint16_t *imgs, int n, int H, int W,
                        float graph_thresh_1, float graph_thresh_2, int smoothing_window_px,
                        int min_branch_length_px, int max_branch_length_px, int remove_isolated,
                        int64_t first_index, tmat_row *rows);
+
+/*
+ * tmat_analyze_batch / tmat_analyze_batch_dev "with tree": the same passes, the same rows bit for bit, and per image the tree overlay
+ * picture (compute_branches.py:440-449) and the scaled barcode (:377) out of the batched pipeline.  The host graph stage of a pass runs
+ * tmat_morse_tree's code instead of tmat_morse_stats' (one shared core), then the pass's segments are uploaded and rasterised on the
+ * handle's third stream (overlay_kernels.hip, one launch set per pass) over the pass's Lanczos-down-sampled u16 image, which is kept in
+ * HBM for the call; the overlays are copied back per pass.  scaling factor = down-sampled width / field width (:437).
+ * rgb_out (n, vh, vw, 3) u8 with vw = vis_width, vh = round_half_even(vis_width h / w) for the (h, w) = (round(W ds_ratio),
+ * round(H ds_ratio)) down-sampled image; bars_out (n, cap_b, 2) f64; n_bars (n).  TMAT_E_CAP when an image has more than cap_b bars.
+ * Scratch comes from the handle's tool workspaces, sized on first use; the plain entries allocate and do nothing extra.
+ */
+int tmat_analyze_batch_tree_dev(tmat_handle h, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width,
+                                float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
+                                int max_branch_length_px, int remove_isolated, int64_t first_index, tmat_row *rows, int vis_width,
+                                uint8_t *rgb_out, double *bars_out, int cap_b, int *n_bars);
+int tmat_analyze_batch_tree(tmat_handle h, const uint16_t *imgs, int n, int H, int W, double ds_ratio, int ds_width,
+                            float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
+                            int max_branch_length_px, int remove_isolated, int64_t first_index, tmat_row *rows, int vis_width,
+                            uint8_t *rgb_out, double *bars_out, int cap_b, int *n_bars);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Z-stack (Sato) branch of analyze_img: reference scripts/compute_branches.py:224-306 (csrc/sato_kernels.hip,

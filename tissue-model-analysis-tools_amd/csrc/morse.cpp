@@ -379,23 +379,27 @@ static OrdGraph trim_graph(const OrdGraph &G0, const std::vector<V2f> &verts, in
     return G;
 }
 
-}  // namespace
-}  // namespace tmat
+// What both entry points share: the graph stages up to the filtered barcode and its statistics.  With `branches` non-null the
+// vertex path of every surviving branch is kept too ([b[0] for b in branch] + [branch[-1][1]], topology.py:379).
+struct MorseOut {
+    std::vector<V2f> verts;              // smoothed vertex positions (float32 [row, col])
+    std::vector<double> births, deaths;  // filtered barcode, branch order
+    int64_t count = 0;
+    double total = 0.0, avg = 0.0;
+};
 
-using namespace tmat;
-
-extern "C" int tmat_morse_stats(const int32_t *verts_in, int n_verts, const int32_t *edges, int n_edges, int rows, int cols,
-                                int smoothing_window, int min_branch_length, int max_branch_length,
-                                int remove_isolated_branches, const uint8_t *pruning_mask, int64_t *count,
-                                double *total_px, double *avg_px, double *bars, int cap)
+static int morse_core(const char *who, const int32_t *verts_in, int n_verts, const int32_t *edges, int n_edges, int rows, int cols,
+                      int smoothing_window, int min_branch_length, int max_branch_length, int remove_isolated_branches,
+                      const uint8_t *pruning_mask, MorseOut &out, std::vector<std::vector<int32_t>> *branches)
 {
-    if (n_verts < 0 || n_edges < 0 || (n_verts && !verts_in) || (n_edges && !edges) || !count || !total_px || !avg_px) {
-        set_error("tmat_morse_stats: bad argument");
+    if (n_verts < 0 || n_edges < 0 || (n_verts && !verts_in) || (n_edges && !edges)) {
+        set_error(std::string(who) + ": bad argument");
         return TMAT_E_ARG;
     }
     for (int i = 0; i < 2 * n_edges; i++)
-        if (edges[i] < 0 || edges[i] >= n_verts) { set_error("tmat_morse_stats: edge index out of range"); return TMAT_E_ARG; }
-    std::vector<V2f> verts(n_verts);
+        if (edges[i] < 0 || edges[i] >= n_verts) { set_error(std::string(who) + ": edge index out of range"); return TMAT_E_ARG; }
+    std::vector<V2f> &verts = out.verts;
+    verts.resize(n_verts);
     for (int i = 0; i < n_verts; i++) verts[i] = {(float)verts_in[2 * i], (float)verts_in[2 * i + 1]};
     OrdGraph G((size_t)n_verts);
     for (int i = 0; i < n_edges; i++) G.add_edge(edges[2 * i], edges[2 * i + 1]);
@@ -482,29 +486,133 @@ extern "C" int tmat_morse_stats(const int32_t *verts_in, int n_verts, const int3
         }
     }
     // ---- barcode (:224-271) + min-length filter (:318-347) ----
-    std::vector<double> births, deaths;
+    std::vector<double> &births = out.births, &deaths = out.deaths;
+    std::vector<int32_t> path;
     for (int32_t leaf : leaves) {
         int32_t cur = leaf, lab = leaf, par = parent[leaf];
         double d = 0.0;
+        path.clear();
+        path.push_back(leaf);
         while (lab == leaf && cur != par) {
             d += edge_len32(verts, par, cur);
             cur = par; par = parent[cur];
             lab = label[cur];
+            if (branches) path.push_back(cur);
         }
         const double birth = -dist_root[leaf];
         const double death = birth + d;
-        if (death - birth >= (double)min_branch_length) { births.push_back(birth); deaths.push_back(death); }
+        if (death - birth >= (double)min_branch_length) {
+            births.push_back(birth); deaths.push_back(death);
+            if (branches) branches->push_back(path);
+        }
     }
     // ---- statistics (:54-65, :349-356) ----
     std::vector<double> lens;
     for (size_t i = 0; i < births.size(); i++) { double l = deaths[i] - births[i]; if (!std::isinf(l)) lens.push_back(l); }
     const double total = lens.empty() ? 0.0 : numpy_pairwise_sum(lens.data(), (long)lens.size());
-    *count = (int64_t)births.size();
-    *total_px = total;
-    *avg_px = total == 0.0 ? 0.0 : total / (double)lens.size();
+    out.count = (int64_t)births.size();
+    out.total = total;
+    out.avg = total == 0.0 ? 0.0 : total / (double)lens.size();
+    return TMAT_OK;
+}
+
+}  // namespace
+}  // namespace tmat
+
+using namespace tmat;
+
+extern "C" int tmat_morse_stats(const int32_t *verts_in, int n_verts, const int32_t *edges, int n_edges, int rows, int cols,
+                                int smoothing_window, int min_branch_length, int max_branch_length,
+                                int remove_isolated_branches, const uint8_t *pruning_mask, int64_t *count,
+                                double *total_px, double *avg_px, double *bars, int cap)
+{
+    if (!count || !total_px || !avg_px) { set_error("tmat_morse_stats: bad argument"); return TMAT_E_ARG; }
+    MorseOut m;
+    const int rc = morse_core("tmat_morse_stats", verts_in, n_verts, edges, n_edges, rows, cols, smoothing_window, min_branch_length,
+                              max_branch_length, remove_isolated_branches, pruning_mask, m, nullptr);
+    if (rc) return rc;
+    *count = m.count;
+    *total_px = m.total;
+    *avg_px = m.avg;
     if (bars) {
-        if ((size_t)cap < births.size()) { set_error("tmat_morse_stats: bars capacity too small"); return TMAT_E_CAP; }
-        for (size_t i = 0; i < births.size(); i++) { bars[2 * i] = births[i]; bars[2 * i + 1] = deaths[i]; }
+        if ((size_t)cap < m.births.size()) { set_error("tmat_morse_stats: bars capacity too small"); return TMAT_E_CAP; }
+        for (size_t i = 0; i < m.births.size(); i++) { bars[2 * i] = m.births[i]; bars[2 * i + 1] = m.deaths[i]; }
     }
+    return TMAT_OK;
+}
+
+// topology.py:358-389 (__compute_colored_tree_and_barcode) for the branches that survive __filter_graph (:318-347)
+extern "C" int tmat_morse_tree(const int32_t *verts_in, int n_verts, const int32_t *edges, int n_edges, int rows, int cols,
+                               int smoothing_window, int min_branch_length, int max_branch_length,
+                               int remove_isolated_branches, const uint8_t *pruning_mask, double scaling_factor, int64_t *count,
+                               double *total_px, double *avg_px, double *segs, int32_t *seg_branch, int cap_s, double *bars,
+                               int cap_b, int *n_segs, int *n_bars)
+{
+    if (!count || !total_px || !avg_px || !n_segs || !n_bars || cap_s < 0 || cap_b < 0 || (cap_s && (!segs || !seg_branch)) || (cap_b && !bars)) {
+        set_error("tmat_morse_tree: bad argument");
+        return TMAT_E_ARG;
+    }
+    MorseOut m;
+    std::vector<std::vector<int32_t>> branches;
+    const int rc = morse_core("tmat_morse_tree", verts_in, n_verts, edges, n_edges, rows, cols, smoothing_window, min_branch_length,
+                              max_branch_length, remove_isolated_branches, pruning_mask, m, &branches);
+    if (rc) return rc;
+    *count = m.count;
+    *total_px = m.total;
+    *avg_px = m.avg;
+    size_t total_segs = 0;
+    for (const auto &b : branches) total_segs += b.size() - 1;
+    *n_segs = (int)total_segs;
+    *n_bars = (int)branches.size();
+    if ((size_t)cap_b < branches.size()) { set_error("tmat_morse_tree: bars capacity too small"); return TMAT_E_CAP; }
+    if ((size_t)cap_s < total_segs) { set_error("tmat_morse_tree: segment capacity too small"); return TMAT_E_CAP; }
+    // float32 vertices times a Python float stay float32 in numpy (the factor is rounded to float32 first), :380
+    const float sf = (float)scaling_factor;
+    size_t at = 0;
+    std::vector<V2f> pos;
+    std::vector<V2d> sm;
+    for (size_t bi = 0; bi < branches.size(); bi++) {
+        bars[2 * bi] = m.births[bi] * scaling_factor;            // :377
+        bars[2 * bi + 1] = m.deaths[bi] * scaling_factor;
+        const auto &path = branches[bi];
+        pos.resize(path.size());
+        for (size_t i = 0; i < path.size(); i++) pos[i] = {m.verts[path[i]].x * sf, m.verts[path[i]].y * sf};
+        if (!moving_average_fixed_ends(pos, 3, sm)) {               // n == 1: the float32 positions unchanged (:470-471)
+            sm.resize(pos.size());
+            for (size_t i = 0; i < pos.size(); i++) sm[i] = {(double)pos[i].x, (double)pos[i].y};
+        }
+        for (size_t j = 0; j + 1 < sm.size(); j++, at++) {          // v[::-1]: x = column, y = row (:386)
+            segs[4 * at] = sm[j].y; segs[4 * at + 1] = sm[j].x;
+            segs[4 * at + 2] = sm[j + 1].y; segs[4 * at + 3] = sm[j + 1].x;
+            seg_branch[at] = (int32_t)bi;
+        }
+    }
+    return TMAT_OK;
+}
+
+// topology.py:518-527 (__random_color) as include/tmat.h defines it
+extern "C" int tmat_branch_color(int i, uint8_t *rgb)
+{
+    if (i < 0 || !rgb) { set_error("tmat_branch_color: bad argument"); return TMAT_E_ARG; }
+    const double step = 180 * 0.618033988749895;
+    const int hue = (int)((long long)std::floor(step * (double)i) % 256);
+    const double H = (double)((2 * hue) % 360), S = 220.0 / 255.0, V = 1.0;
+    const double hh = H / 60.0;
+    const int sector = (int)hh;                     // 0..5
+    const double f = hh - (double)sector;
+    const double p = V * (1.0 - S), q = V * (1.0 - S * f), t = V * (1.0 - S * (1.0 - f));
+    double r, g, b;
+    switch (sector) {
+    case 0: r = V; g = t; b = p; break;
+    case 1: r = q; g = V; b = p; break;
+    case 2: r = p; g = V; b = t; break;
+    case 3: r = p; g = q; b = V; break;
+    case 4: r = t; g = p; b = V; break;
+    default: r = V; g = p; b = q; break;
+    }
+    // the reference hands cv2's (B, G, R) to matplotlib as (R, G, B): keep the swap
+    rgb[0] = (uint8_t)std::floor(b * 255.0 + 0.5);
+    rgb[1] = (uint8_t)std::floor(g * 255.0 + 0.5);
+    rgb[2] = (uint8_t)std::floor(r * 255.0 + 0.5);
     return TMAT_OK;
 }

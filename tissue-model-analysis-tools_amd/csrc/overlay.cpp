@@ -1,0 +1,227 @@
+// Tree overlay and barcode pictures (reference compute_branches.py:431-450, topology.py:67-144) as RGB8 rasters of our own
+// specification (DESIGN.md "Tree overlay and barcode pictures"): the host twin of overlay_kernels.hip, the barcode raster, and the
+// C-ABI entry that runs the rasteriser on the device.  Host twin and kernel share every formula through overlay.h.
+#include "../../include/tmat.h"
+#include "overlay.h"
+#include "tmat_ctx.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+
+namespace tmat {
+
+bool canvas_of(int bh, int bw, int vis_width, Canvas &cv)
+{
+    if (bh < 1 || bw < 1 || vis_width < 1) return false;
+    cv.vw = vis_width;
+    cv.vh = (int)std::nearbyint((double)vis_width * (double)bh / (double)bw);       // round half to even
+    if (cv.vh < 1) return false;
+    const float r = (float)(0.75 * (200.0 / 72.0) * ((double)vis_width / 2000.0));   // matplotlib's 1.5 pt line at 200 dpi
+    cv.rp = r + 0.5f;
+    return true;
+}
+
+// background pixels -> canvas coordinates (float32), colour of the branch; segments with a non-finite coordinate are dropped
+int prep_segments(const double *segs, const int32_t *seg_branch, int count, int bh, int bw, const Canvas &cv, std::vector<OverlaySeg> &out)
+{
+    auto map = [](double v, int dst, int src) {
+        float f = (float)v;
+        float a = f + 0.5f;
+        float b = a * (float)dst;
+        float c = b / (float)src;
+        return c - 0.5f;
+    };
+    for (int i = 0; i < count; i++) {
+        const double *p = segs + 4 * (size_t)i;
+        if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && std::isfinite(p[3]))) continue;
+        if (seg_branch[i] < 0) { set_error("render_tree: negative branch index"); return TMAT_E_ARG; }
+        uint8_t rgb[3];
+        tmat_branch_color(seg_branch[i], rgb);
+        OverlaySeg s;
+        s.x1 = map(p[0], cv.vw, bw); s.y1 = map(p[1], cv.vh, bh);
+        s.x2 = map(p[2], cv.vw, bw); s.y2 = map(p[3], cv.vh, bh);
+        s.r = (float)rgb[0]; s.g = (float)rgb[1]; s.b = (float)rgb[2]; s.pad = 0.0f;
+        if (!(std::isfinite(s.x1) && std::isfinite(s.y1) && std::isfinite(s.x2) && std::isfinite(s.y2))) continue;
+        out.push_back(s);
+    }
+    return TMAT_OK;
+}
+
+namespace {
+
+static bool offsets_ok(const int32_t *off, int n)
+{
+    if (off[0] != 0) return false;
+    for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) return false;
+    return true;
+}
+
+static float bg_at(const void *bg, int dtype, size_t i) { return dtype == 0 ? (float)((const uint16_t *)bg)[i] : ((const float *)bg)[i]; }
+
+}  // namespace
+}  // namespace tmat
+
+using namespace tmat;
+
+extern "C" int tmat_host_render_tree(const void *background, int bg_dtype, int n, int bh, int bw, const double *segs, const int32_t *seg_branch,
+                                     const int32_t *seg_offsets, int vis_width, uint8_t *rgb_out)
+{
+    Canvas cv;
+    if (!background || (bg_dtype != 0 && bg_dtype != 1) || n < 0 || !seg_offsets || !rgb_out || !canvas_of(bh, bw, vis_width, cv) || !offsets_ok(seg_offsets, n) ||
+        (seg_offsets[n] && (!segs || !seg_branch))) {
+        set_error("tmat_host_render_tree: bad argument");
+        return TMAT_E_ARG;
+    }
+    const size_t per = (size_t)bh * bw, cper = (size_t)cv.vh * cv.vw;
+    std::vector<float> C(cper * 3);
+    std::vector<int> sx(cv.vw);
+    for (int x = 0; x < cv.vw; x++) sx[x] = ovl_sample_index(x, bw, cv.vw);
+    for (int img = 0; img < n; img++) {
+        float mn = bg_at(background, bg_dtype, img * per), mx = mn;
+        for (size_t i = 1; i < per; i++) { float v = bg_at(background, bg_dtype, img * per + i); mn = std::min(mn, v); mx = std::max(mx, v); }
+        for (int y = 0; y < cv.vh; y++) {
+            const int sy = ovl_sample_index(y, bh, cv.vh);
+            for (int x = 0; x < cv.vw; x++) {
+                const float g = ovl_grey(bg_at(background, bg_dtype, img * per + (size_t)sy * bw + sx[x]), mn, mx);
+                float *c = &C[((size_t)y * cv.vw + x) * 3];
+                c[0] = g; c[1] = g; c[2] = g;
+            }
+        }
+        std::vector<OverlaySeg> ss;
+        const int s0 = seg_offsets[img], cnt = seg_offsets[img + 1] - s0;
+        int rc = prep_segments(segs + 4 * (size_t)s0, seg_branch + s0, cnt, bh, bw, cv, ss);
+        if (rc) return rc;
+        const float reach = cv.rp + 1.0f;
+        for (const OverlaySeg &s : ss) {            // painter's order; pixels beyond the capsule's reach have coverage 0 and keep their value exactly
+            const float lox = std::min(s.x1, s.x2) - reach, hix = std::max(s.x1, s.x2) + reach;
+            const float loy = std::min(s.y1, s.y2) - reach, hiy = std::max(s.y1, s.y2) + reach;
+            if (hix < 0.0f || hiy < 0.0f || lox > (float)(cv.vw - 1) || loy > (float)(cv.vh - 1)) continue;
+            const int xa = (int)std::max(0.0f, std::floor(lox)), xb = (int)std::min((float)(cv.vw - 1), std::ceil(hix));
+            const int ya = (int)std::max(0.0f, std::floor(loy)), yb = (int)std::min((float)(cv.vh - 1), std::ceil(hiy));
+            for (int y = ya; y <= yb; y++)
+                for (int x = xa; x <= xb; x++) {
+                    const float a = ovl_coverage(s, (float)x, (float)y, cv.rp);
+                    float *c = &C[((size_t)y * cv.vw + x) * 3];
+                    c[0] = ovl_blend(c[0], s.r, a); c[1] = ovl_blend(c[1], s.g, a); c[2] = ovl_blend(c[2], s.b, a);
+                }
+        }
+        uint8_t *o = rgb_out + (size_t)img * cper * 3;
+        for (size_t i = 0; i < cper * 3; i++) o[i] = (uint8_t)std::floor(C[i] + 0.5f);
+    }
+    return TMAT_OK;
+}
+
+// ms (may be null): HIP-event times of the call's four phases on its stream -- upload, min-max, render kernels, copy back
+static int render_tree_impl(tmat_handle hd, const void *background, int bg_dtype, int n, int bh, int bw, const double *segs, const int32_t *seg_branch,
+                            const int32_t *seg_offsets, int vis_width, uint8_t *rgb_out, float *ms)
+{
+    Ctx *c = (Ctx *)hd;
+    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0f;
+    Canvas cv;
+    if (!c || !background || (bg_dtype != 0 && bg_dtype != 1) || n < 0 || !seg_offsets || !rgb_out || !canvas_of(bh, bw, vis_width, cv) ||
+        !offsets_ok(seg_offsets, n) || (seg_offsets[n] && (!segs || !seg_branch))) {
+        set_error("tmat_render_tree: bad argument");
+        return TMAT_E_ARG;
+    }
+    if (n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    const size_t per = (size_t)bh * bw, esz = bg_dtype == 0 ? 2 : 4, cper = (size_t)cv.vh * cv.vw * 3;
+    // canvas-space segments of all images, with the offsets of what survived the non-finite filter
+    std::vector<OverlaySeg> ss;
+    std::vector<int> off(n + 1, 0);
+    for (int img = 0; img < n; img++) {
+        const int s0 = seg_offsets[img];
+        int rc = prep_segments(segs + 4 * (size_t)s0, seg_branch + s0, seg_offsets[img + 1] - s0, bh, bw, cv, ss);
+        if (rc) return rc;
+        off[img + 1] = (int)ss.size();
+    }
+    const int K = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)512 << 20) / cper));      // <= 512 MiB of canvases per launch
+    uint8_t *dbg = (uint8_t *)ws_get(c, 24, (size_t)n * per * esz);
+    OverlaySeg *dseg = (OverlaySeg *)ws_get(c, 25, ss.size() * sizeof(OverlaySeg));
+    float *dmm = (float *)ws_get(c, 26, (size_t)n * 4 * sizeof(float) + (size_t)(n + 1) * sizeof(int));
+    uint8_t *drgb = (uint8_t *)ws_get(c, 27, (size_t)K * cper);
+    if (!dbg || !dseg || !dmm || !drgb) return TMAT_E_HIP;
+    int *doff = (int *)(dmm + 4 * (size_t)n);
+    hipStream_t s = c->stream;
+    int rc = TMAT_OK;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (ms) for (hipEvent_t &e : ev) if (hipEventCreate(&e) != hipSuccess) rc = TMAT_E_HIP;
+    auto mark = [&](int i) { if (ms && !rc && hipEventRecord(ev[i], s) != hipSuccess) rc = TMAT_E_HIP; };
+    auto span = [&](int a, int b, int slot) { float t = 0.0f; if (ms && !rc && hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess) ms[slot] += t; };
+    mark(0);
+    if (!rc && (!hip_ok(hipMemcpyAsync(dbg, background, (size_t)n * per * esz, hipMemcpyHostToDevice, s), "H2D") ||
+        (!ss.empty() && !hip_ok(hipMemcpyAsync(dseg, ss.data(), ss.size() * sizeof(OverlaySeg), hipMemcpyHostToDevice, s), "H2D")) ||
+        !hip_ok(hipMemcpyAsync(doff, off.data(), (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice, s), "H2D"))) rc = TMAT_E_HIP;
+    mark(1);
+    if (!rc && overlay_minmax_dev(dbg, bg_dtype, n, bh, bw, dmm, s)) { set_error("tmat_render_tree: min-max launch failed"); rc = TMAT_E_HIP; }
+    mark(2);
+    if (ms && !rc) {
+        if (!hip_ok(hipStreamSynchronize(s), "sync")) rc = TMAT_E_HIP;
+        span(0, 1, 0); span(1, 2, 1);
+    }
+    for (int i0 = 0; i0 < n && !rc; i0 += K) {
+        const int k = std::min(K, n - i0);
+        mark(0);
+        const int r = overlay_render_dev(dbg + (size_t)i0 * per * esz, bg_dtype, dmm + 2 * (size_t)i0, k, bh, bw, dseg, doff + i0, cv.vh, cv.vw, cv.rp, drgb, s);
+        if (r == -1) { set_error("tmat_render_tree: canvas too large for one launch"); rc = TMAT_E_ARG; break; }
+        if (r) { set_error("tmat_render_tree: kernel launch failed"); rc = TMAT_E_HIP; break; }
+        mark(1);
+        if (!hip_ok(hipMemcpyAsync(rgb_out + (size_t)i0 * cper, drgb, (size_t)k * cper, hipMemcpyDeviceToHost, s), "D2H")) rc = TMAT_E_HIP;
+        mark(2);
+        if (!hip_ok(hipStreamSynchronize(s), "sync")) rc = TMAT_E_HIP;
+        span(0, 1, 2); span(1, 2, 3);
+    }
+    if (rc) hipStreamSynchronize(s);
+    else if (!hip_ok(hipStreamSynchronize(s), "sync")) rc = TMAT_E_HIP;     // off / ss are released on return
+    for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+    return rc;
+}
+
+extern "C" int tmat_render_tree(tmat_handle hd, const void *background, int bg_dtype, int n, int bh, int bw, const double *segs, const int32_t *seg_branch,
+                                const int32_t *seg_offsets, int vis_width, uint8_t *rgb_out)
+{
+    return render_tree_impl(hd, background, bg_dtype, n, bh, bw, segs, seg_branch, seg_offsets, vis_width, rgb_out, nullptr);
+}
+
+extern "C" int tmat_render_tree_timed(tmat_handle hd, const void *background, int bg_dtype, int n, int bh, int bw, const double *segs,
+                                      const int32_t *seg_branch, const int32_t *seg_offsets, int vis_width, uint8_t *rgb_out, float *ms4)
+{
+    if (!ms4) { set_error("tmat_render_tree_timed: bad argument"); return TMAT_E_ARG; }
+    return render_tree_impl(hd, background, bg_dtype, n, bh, bw, segs, seg_branch, seg_offsets, vis_width, rgb_out, ms4);
+}
+
+// plot_colored_barcode (topology.py:67-107) without axes or text
+extern "C" int tmat_host_render_barcode(const double *bars, int n, int vis_width, uint8_t *rgb_out)
+{
+    if (n < 0 || (n && !bars) || vis_width < 1 || !rgb_out) { set_error("tmat_host_render_barcode: bad argument"); return TMAT_E_ARG; }
+    const int S = (int)std::nearbyint((double)vis_width * 0.9);
+    if (S < 1) { set_error("tmat_host_render_barcode: empty canvas"); return TMAT_E_ARG; }
+    std::memset(rgb_out, 255, (size_t)S * S * 3);
+    if (n == 0) return TMAT_OK;
+    double lo = bars[0], hi = bars[1];
+    for (int i = 0; i < n; i++) { lo = std::min(lo, bars[2 * i]); hi = std::max(hi, bars[2 * i + 1]); }
+    const double span = hi - lo;
+    if (!(span > 0.0) || !std::isfinite(span)) return TMAT_OK;
+    std::vector<int> order(n);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bars[2 * a] > bars[2 * b]; });     // birth, descending
+    const double pitch = (double)S / (double)n;
+    auto edge = [&](double v) {
+        double e = std::floor((v - lo) / span * (double)S + 0.5);
+        return (int)std::min((double)S, std::max(0.0, e));
+    };
+    for (int k = 0; k < n; k++) {
+        const int bi = order[k];
+        uint8_t col[3];
+        tmat_branch_color(bi, col);
+        const int xa = edge(bars[2 * bi]), xb = edge(bars[2 * bi + 1]);
+        const int ya = (int)std::floor(((double)k + 0.1) * pitch + 0.5), yb = (int)std::floor(((double)k + 0.9) * pitch + 0.5);
+        for (int y = ya; y < yb; y++) {            // bar 0 is the lowest row of the picture, as on matplotlib's upward y axis
+            uint8_t *row = rgb_out + (size_t)(S - 1 - y) * S * 3;
+            for (int x = xa; x < xb; x++) { row[3 * x] = col[0]; row[3 * x + 1] = col[1]; row[3 * x + 2] = col[2]; }
+        }
+    }
+    return TMAT_OK;
+}

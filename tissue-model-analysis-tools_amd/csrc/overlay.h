@@ -1,0 +1,90 @@
+// Tree overlay rasteriser (DESIGN.md "Tree overlay and barcode pictures"): declarations shared by overlay.cpp (host twin, C-ABI)
+// and overlay_kernels.hip (device).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <vector>
+
+namespace tmat {
+
+// one drawn segment in canvas coordinates (float32, already mapped from background pixels) with its branch colour
+struct OverlaySeg {
+    float x1, y1, x2, y2;
+    float r, g, b;          // 0..255, exact integers
+    float pad;
+};
+
+constexpr int OVL_TW = 64, OVL_TH = 16;     // canvas tile of one workgroup
+
+// Every formula of the picture specification, shared by the host twin and the kernels: float32, one operation per statement,
+// no contraction (the build passes -ffp-contract=off).
+__host__ __device__ inline int ovl_sample_index(int p, int src, int dst)
+{
+    float a = (float)p + 0.5f;
+    float b = a * (float)src;
+    float c = b / (float)dst;
+    float u = c - 0.5f;
+    float v = floorf(u + 0.5f);
+    int k = (int)v;
+    return k < 0 ? 0 : (k > src - 1 ? src - 1 : k);
+}
+
+// grey byte of a background value v for the image's minimum mn and maximum mx (a constant image gives 0)
+__host__ __device__ inline float ovl_grey(float v, float mn, float mx)
+{
+    float range = mx - mn;
+    if (!(range > 0.0f)) return 0.0f;
+    float a = v - mn;
+    float t = a / range;
+    float s = t * 255.0f;
+    return floorf(s + 0.5f);
+}
+
+// coverage of the pixel centre (cx, cy) by the capsule of segment s; rp = half-width + 0.5
+__host__ __device__ inline float ovl_coverage(const OverlaySeg &s, float cx, float cy, float rp)
+{
+    float dx = s.x2 - s.x1;
+    float dy = s.y2 - s.y1;
+    float dxx = dx * dx;
+    float dyy = dy * dy;
+    float len2 = dxx + dyy;
+    float px = cx - s.x1;
+    float py = cy - s.y1;
+    float t = 0.0f;
+    if (len2 > 0.0f) {
+        float pdx = px * dx;
+        float pdy = py * dy;
+        float dot = pdx + pdy;
+        t = dot / len2;
+        t = fminf(fmaxf(t, 0.0f), 1.0f);
+    }
+    float tx = t * dx;
+    float ty = t * dy;
+    float ex = px - tx;
+    float ey = py - ty;
+    float exx = ex * ex;
+    float eyy = ey * ey;
+    float d = sqrtf(exx + eyy);
+    float a = rp - d;
+    return fminf(fmaxf(a, 0.0f), 1.0f);
+}
+
+__host__ __device__ inline float ovl_blend(float C, float col, float a)
+{
+    float diff = col - C;
+    float step = a * diff;
+    return C + step;
+}
+
+// canvas of a (bh, bw) background at vis_width: vw, vh = round_half_even(vw bh / bw), rp = capsule half-width + 0.5; false when empty
+struct Canvas { int vh, vw; float rp; };
+bool canvas_of(int bh, int bw, int vis_width, Canvas &cv);
+// background pixels -> canvas coordinates (float32) + branch colour, appended to out; segments with a non-finite coordinate are dropped
+int prep_segments(const double *segs, const int32_t *seg_branch, int count, int bh, int bw, const Canvas &cv, std::vector<OverlaySeg> &out);
+
+// background minima / maxima (mnmx: [n][2] floats) and the overlay of n images; bg_dtype 0: u16, 1: f32.  0 on success.
+int overlay_minmax_dev(const void *bg, int bg_dtype, int n, int bh, int bw, float *mnmx, hipStream_t s);
+int overlay_render_dev(const void *bg, int bg_dtype, const float *mnmx, int n, int bh, int bw, const OverlaySeg *segs, const int *seg_offsets,
+                       int vh, int vw, float rp, uint8_t *rgb, hipStream_t s);
+
+}  // namespace tmat

@@ -10,6 +10,7 @@
 // works on the next pass.  Nothing is shared between images, so this is also how the path shards
 // across GPUs (one process per GPU, see tmat_amd/distributed.py).
 #include "../../include/tmat.h"
+#include "overlay.h"
 #include "tmat_ctx.h"
 #include "postproc.h"
 #include "morph.h"
@@ -153,7 +154,8 @@ static bool tail_on_side_stream()
 // old route: everything on the main stream, one input buffer.
 static bool pre_on_side_stream(const Ctx *c, const TileGeom &g) { return c->pre_side && tail_on_side_stream() && g.tiles_per_img <= c->max_patches && c->patch_in2; }
 static float *patch_in_of(Ctx *c, int slot, const TileGeom &g) { return pre_on_side_stream(c, g) && (slot & 1) ? c->patch_in2 : c->patch_in; }
-static int enqueue_pre(Ctx *c, const uint16_t *imgs_dev, int k, int slot, const TileGeom &g)
+// bg_keep (nullable, the "with tree" form only): the pass's down-sampled images are copied there, b.small itself is rewritten by the next pass
+static int enqueue_pre(Ctx *c, const uint16_t *imgs_dev, int k, int slot, const TileGeom &g, uint16_t *bg_keep = nullptr)
 {
     PassBuf &b = c->pass;
     const bool oversize = g.tiles_per_img > c->max_patches;
@@ -162,6 +164,7 @@ static int enqueue_pre(Ctx *c, const uint16_t *imgs_dev, int k, int slot, const 
     // the down path of the pass before last read this buffer (long finished: its whole pass has ended; stated for the record)
     if (side && c->down_pending[slot]) TMAT_HIP(hipStreamWaitEvent(s, c->ev_down[slot], 0));
     launch_lanczos(imgs_dev, k, b.H, b.W, b.h, b.w, b.xi, b.xc, b.yi, b.yc, b.tmp, b.small, c->input_sat, s);
+    if (bg_keep) TMAT_HIP(hipMemcpyAsync(bg_keep, b.small, (size_t)k * b.h * b.w * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
     launch_rescale01(b.small, k, (size_t)b.h * b.w, b.mn, b.mx, b.x, s);
     if (c->norm_on) launch_norm_f32(b.x, (size_t)k * b.h * b.w, c->norm_mean, c->norm_std, s);      // models.py:636-637
     float *mn = (float *)c->scratch, *mx = mn + k;
@@ -269,7 +272,17 @@ struct PassJob {
     void join() { if (th.joinable()) th.join(); }
 };
 
-static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_row *rows, PassJob *job)
+// The "with tree" form of a call (tmat_analyze_batch_tree*): per image the branch geometry instead of the statistics alone, and per pass
+// one rasteriser launch set on the third stream over the pass's down-sampled images (kept in bg_all), overlays copied to the caller.
+struct TreeJob {
+    Canvas cv;
+    double sf;                      // compute_branches.py:437: original_image.shape[1] / img_dsamp_res[1]
+    uint8_t *rgb_out; double *bars_out; int cap_b; int *n_bars;     // caller's, whole call
+    const uint16_t *bg_all;         // (n, h, w) u16 on the device
+    OverlaySeg *dseg; size_t seg_cap; float *dmm; int *doff; uint8_t *drgb;
+};
+
+static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_row *rows, PassJob *job, const TreeJob *tree = nullptr, int first_img = 0)
 {
     PassBuf &b = c->pass;
     const int h = b.h, w = b.w;
@@ -315,6 +328,8 @@ static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_ro
     ok = ok && hipStreamSynchronize(s) == hipSuccess;
     if (!ok) { job->rc = TMAT_E_HIP; return; }
     const double t2 = now_s();
+    std::vector<std::vector<double>> tsegs(tree ? k : 0);
+    std::vector<std::vector<int32_t>> tbranch(tree ? k : 0);
     parallel_images(k, [&](int i) {
         const int cap_v = (int)fper + 4, cap_e = 3 * (int)fper + 4;
         std::vector<int32_t> V((size_t)cap_v * 2), E((size_t)cap_e * 2);
@@ -322,18 +337,50 @@ static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_ro
         int rc = dmt_graph_host_sorted(b.f255_host[slot] + i * fper, gp.fh, gp.fw, gp.t1, gp.t2, dmt_dev ? b.dmt_ids_host[slot] + i * nE : nullptr,
                                        dmt_dev ? b.dmt_m_host[slot][i] : 0, V.data(), cap_v, E.data(), cap_e, &nv, &ne,
                                        sweep_dev ? b.dmt_kind_host[slot] + i * nE : nullptr, sweep_dev ? b.dmt_pers_host[slot] + i * nE : nullptr);
-        if (!rc)
+        if (!rc && !tree)
             rc = tmat_morse_stats(V.data(), nv, E.data(), ne, gp.fh, gp.fw, gp.smooth, gp.min_len, gp.max_len, gp.remove_isolated, nullptr,
                                   &rows[i].count, &rows[i].total_px, &rows[i].avg_px, nullptr, 0);
+        if (!rc && tree) {
+            const int cap_s = std::max(nv, 1);       // a forest has fewer edges than vertices
+            tsegs[i].resize((size_t)cap_s * 4); tbranch[i].resize(cap_s);
+            int ns = 0;
+            rc = tmat_morse_tree(V.data(), nv, E.data(), ne, gp.fh, gp.fw, gp.smooth, gp.min_len, gp.max_len, gp.remove_isolated, nullptr, tree->sf,
+                                 &rows[i].count, &rows[i].total_px, &rows[i].avg_px, tsegs[i].data(), tbranch[i].data(), cap_s,
+                                 tree->bars_out + (size_t)(first_img + i) * tree->cap_b * 2, tree->cap_b, &ns, tree->n_bars + first_img + i);
+            tsegs[i].resize((size_t)ns * 4); tbranch[i].resize(ns);
+        }
         if (rc) job->rc = rc;
     });
+    if (tree && !job->rc) {
+        std::vector<OverlaySeg> ss;
+        std::vector<int> off(k + 1, 0);
+        int rc = TMAT_OK;
+        for (int i = 0; i < k && !rc; i++) {
+            rc = prep_segments(tsegs[i].data(), tbranch[i].data(), (int)tbranch[i].size(), h, w, tree->cv, ss);
+            off[i + 1] = (int)ss.size();
+        }
+        if (!rc && ss.size() > tree->seg_cap) { set_error("analyze (tree): segment workspace too small"); rc = TMAT_E_CAP; }
+        const size_t cper = (size_t)tree->cv.vh * tree->cv.vw * 3;
+        if (!rc && ((!ss.empty() && hipMemcpyAsync(tree->dseg, ss.data(), ss.size() * sizeof(OverlaySeg), hipMemcpyHostToDevice, s) != hipSuccess) ||
+                    hipMemcpyAsync(tree->doff, off.data(), (size_t)(k + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess)) rc = TMAT_E_HIP;
+        const uint16_t *bg = tree->bg_all + (size_t)first_img * per;
+        if (!rc && overlay_minmax_dev(bg, 0, k, h, w, tree->dmm, s)) rc = TMAT_E_HIP;
+        if (!rc && overlay_render_dev(bg, 0, tree->dmm, k, h, w, tree->dseg, tree->doff, tree->cv.vh, tree->cv.vw, tree->cv.rp, tree->drgb, s)) {
+            set_error("analyze (tree): overlay launch failed"); rc = TMAT_E_HIP;
+        }
+        if (!rc && hipMemcpyAsync(tree->rgb_out + (size_t)first_img * cper, tree->drgb, (size_t)k * cper, hipMemcpyDeviceToHost, s) != hipSuccess) rc = TMAT_E_HIP;
+        if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = TMAT_E_HIP;       // ss / off are released here
+        if (rc) job->rc = rc;
+    }
     if (trace_on())
         fprintf(stderr, "[tmat] host pass (%d images): ordered thinning %.1f ms (host permutations %.1f, the rest = its launches and convergence polls on the low-priority stream), finish + DMT on the GPU %.1f ms, collect + Morse %.1f ms\n", k,
                 (t1 - t0) * 1e3, (t_perm - t0) * 1e3, (t2 - t1) * 1e3, (now_s() - t2) * 1e3);
 }
 
+struct TreeReq { int vis_width; uint8_t *rgb_out; double *bars_out; int cap_b; int *n_bars; };
+
 static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width, GraphParams gp,
-                       int64_t first_index, tmat_row *rows)
+                       int64_t first_index, tmat_row *rows, const TreeReq *req = nullptr)
 {
     // compute_branches.py:309-312 hands target_shape = round(shape * ds_ratio) = (round(H r), round(W r)) to cv2.resize as
     // dsize, which cv2 reads as (width, height): the resized image has round(W r) rows and round(H r) columns.  Square
@@ -351,6 +398,23 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
     if (!rc) rc = ensure_ma_table(c);
     if (rc) return rc;
     for (int i = 0; i < n; i++) { rows[i].index = first_index + i; rows[i].count = 0; rows[i].total_px = 0; rows[i].avg_px = 0; }
+    TreeJob tj{}, *tree = nullptr;
+    if (req) {      // scratch of the "with tree" form: the handle's tool workspaces, sized here before any pass is in flight
+        if (!canvas_of(h, w, req->vis_width, tj.cv)) { set_error("analyze (tree): empty canvas"); return TMAT_E_ARG; }
+        const size_t cper = (size_t)tj.cv.vh * tj.cv.vw * 3, fper = (size_t)gp.fh * gp.fw;
+        tj.sf = (double)w / (double)gp.fw;
+        tj.rgb_out = req->rgb_out; tj.bars_out = req->bars_out; tj.cap_b = req->cap_b; tj.n_bars = req->n_bars;
+        tj.seg_cap = (size_t)K * fper;
+        uint16_t *bg_all = (uint16_t *)ws_get(c, 24, (size_t)n * h * w * sizeof(uint16_t));
+        tj.dseg = (OverlaySeg *)ws_get(c, 25, tj.seg_cap * sizeof(OverlaySeg));
+        tj.dmm = (float *)ws_get(c, 26, (size_t)K * 4 * sizeof(float) + (size_t)(K + 1) * sizeof(int));
+        tj.drgb = (uint8_t *)ws_get(c, 27, (size_t)K * cper);
+        if (!bg_all || !tj.dseg || !tj.dmm || !tj.drgb) return TMAT_E_HIP;
+        tj.bg_all = bg_all;
+        tj.doff = (int *)(tj.dmm + 4 * (size_t)K);
+        tree = &tj;
+    }
+    auto bg_at = [&](int p) { return tree ? const_cast<uint16_t *>(tj.bg_all) + (size_t)p * K * h * w : nullptr; };
     const int P = (n + K - 1) / K;
     PassJob jobs[2];
     auto cnt = [&](int p) { return std::min(K, n - p * K); };
@@ -367,9 +431,9 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
     // (order of the calls = order on the second stream: the front end of pass p + 2 in front of the tail of pass p + 1, which only
     // starts when that pass's up path has ended)
     c->down_pending[0] = c->down_pending[1] = false;
-    rc = enqueue_pre(c, img_at(0), cnt(0), 0, g);
+    rc = enqueue_pre(c, img_at(0), cnt(0), 0, g, bg_at(0));
     if (!rc) rc = enqueue_down(c, cnt(0), 0, g);
-    if (!rc && P > 1) rc = enqueue_pre(c, img_at(1), cnt(1), 1, g);
+    if (!rc && P > 1) rc = enqueue_pre(c, img_at(1), cnt(1), 1, g, bg_at(1));
     if (!rc) rc = enqueue_back(c, cnt(0), 0, g);
     if (!rc && P > 1) rc = enqueue_down(c, cnt(1), 1, g);
     for (int p = 0; p < P && !rc; p++) {
@@ -381,12 +445,12 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
         if (trace_on())
             fprintf(stderr, "[tmat] pass %d/%d (%d images): waited %.1f ms for the GPU, %.1f ms for host jobs of the previous pass\n",
                     p + 1, P, cnt(p), (tw1 - tw0) * 1e3, (now_s() - tw1) * 1e3);
-        if (p + 2 < P && !rc) rc = enqueue_pre(c, img_at(p + 2), cnt(p + 2), slot, g);
+        if (p + 2 < P && !rc) rc = enqueue_pre(c, img_at(p + 2), cnt(p + 2), slot, g, bg_at(p + 2));
         if (p + 1 < P && !rc) rc = enqueue_back(c, cnt(p + 1), slot ^ 1, g);
         if (p + 2 < P && !rc) rc = enqueue_down(c, cnt(p + 2), slot, g);
         for (int i = 0; i < cnt(p) && !rc; i++)
             if (!c->pass.conv_host[slot][i]) { set_error("analyze: Zhang thinning did not converge within its launch budget"); rc = TMAT_E_HIP; }
-        if (!rc) jobs[slot].th = std::thread(run_pass_host, c, slot, cnt(p), gp, rows + (size_t)p * K, &jobs[slot]);
+        if (!rc) jobs[slot].th = std::thread(run_pass_host, c, slot, cnt(p), gp, rows + (size_t)p * K, &jobs[slot], tree, p * K);
     }
     for (auto &j : jobs) { j.join(); if (j.rc && !rc) rc = j.rc; }
     hipStreamSynchronize(c->stream2);
@@ -723,6 +787,45 @@ int tmat_analyze_batch_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int 
     TMAT_HIP(hipSetDevice(c->device));
     GraphParams gp{0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated};
     return analyze_dev(c, imgs_dev, n, H, W, ds_ratio, ds_width, gp, first_index, rows);
+}
+
+int tmat_analyze_batch_tree_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width,
+                                float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
+                                int max_branch_length_px, int remove_isolated, int64_t first_index, tmat_row *rows, int vis_width,
+                                uint8_t *rgb_out, double *bars_out, int cap_b, int *n_bars)
+{
+    Ctx *c = (Ctx *)hd;
+    if (c && !has_model(c)) { set_error("tmat_analyze_batch_tree_dev: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
+    if (!c || !imgs_dev || !rows || n < 0 || H < 1 || W < 1 || ds_width < 1 || vis_width < 1 || !rgb_out || !bars_out || cap_b < 0 || !n_bars) {
+        set_error("tmat_analyze_batch_tree_dev: bad argument");
+        return TMAT_E_ARG;
+    }
+    if (n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    GraphParams gp{0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated};
+    TreeReq req{vis_width, rgb_out, bars_out, cap_b, n_bars};
+    return analyze_dev(c, imgs_dev, n, H, W, ds_ratio, ds_width, gp, first_index, rows, &req);
+}
+
+int tmat_analyze_batch_tree(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, double ds_ratio, int ds_width,
+                            float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
+                            int max_branch_length_px, int remove_isolated, int64_t first_index, tmat_row *rows, int vis_width,
+                            uint8_t *rgb_out, double *bars_out, int cap_b, int *n_bars)
+{
+    Ctx *c = (Ctx *)hd;
+    if (c && !has_model(c)) { set_error("tmat_analyze_batch_tree: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
+    if (!c || !imgs || !rows || n < 0 || H < 1 || W < 1) { set_error("tmat_analyze_batch_tree: bad argument"); return TMAT_E_ARG; }
+    if (n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    uint16_t *dimg = nullptr;
+    TMAT_HIP(hipMalloc((void **)&dimg, (size_t)n * H * W * sizeof(uint16_t)));
+    int rc = TMAT_OK;
+    if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) rc = TMAT_E_HIP;
+    if (!rc) rc = tmat_analyze_batch_tree_dev(hd, dimg, n, H, W, ds_ratio, ds_width, graph_thresh_1, graph_thresh_2, smoothing_window_px,
+                                              min_branch_length_px, max_branch_length_px, remove_isolated, first_index, rows, vis_width,
+                                              rgb_out, bars_out, cap_b, n_bars);
+    hipFree(dimg);
+    return rc;
 }
 
 int tmat_analyze_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, double ds_ratio, int ds_width,

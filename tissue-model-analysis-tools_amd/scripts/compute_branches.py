@@ -11,9 +11,9 @@ branch (:224-306), both on the GPU.
 
 Differences (documented in INTEGRATION.md): images are analysed in batches on the GPU (one process
 per GPU under torch.distributed.run; rows are gathered over RCCL and rank 0 writes the CSV);
---detect-well takes an explicit --well-seed (the reference's random search is unseeded); the PNG image dumps are opt-in (--visualizations; the
-matplotlib barcode / tree plots are not reproduced); --sato-hessian picks the Hessian of skimage.filters.sato
-(gaussian_derivatives = scikit-image >= 0.20, what the reference's pinned 0.22.0 runs; gradient = <= 0.19);
+--detect-well takes an explicit --well-seed (the reference's random search is unseeded); the PNG image dumps are opt-in (--visualizations;
+--tree-visualizations [--vis-width N] for the Morse tree and barcode pictures, which are the library's own rasters, not matplotlib's);
+--sato-hessian picks the Hessian of skimage.filters.sato (gaussian_derivatives = scikit-image >= 0.20, what the reference's pinned 0.22.0 runs; gradient = <= 0.19);
 without --image-width-microns (or the config key) the width comes from OME / ImageJ TIFF metadata
 (tmat_amd/helper.py), as in the reference.
 """
@@ -56,6 +56,11 @@ def parse_branching_args(arg_defaults):
     p.add_argument("--remove-isolated-branches", action="store_true")
     p.add_argument("--graph-smoothing-window", type=float, default=None)
     p.add_argument("-c", "--config", type=str, default=arg_defaults["default_config_path"])
+    p.add_argument("--tree-visualizations", action="store_true",
+                   help="also write visualizations/<image>/{morse_tree,barcode}<_CONFIG...>.png per threshold configuration: the fitted branch "
+                        "tree over the down-sampled image (Z stacks: over the full-resolution max projection) and the barcode; drawn on the GPU, for "
+                        "2-D images inside the batched analysis")
+    p.add_argument("--vis-width", type=int, default=2000, help="width in pixels of the morse_tree picture (default 2000)")
     p.add_argument("--visualizations", action="store_true",
                    help="also write visualizations/<image>/{original_image,prediction,segmentation_mask,distance_transform}.png "
                         "(the reference always does; here it is opt-in: it re-runs the image through the staged entry points)")
@@ -219,6 +224,9 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
     vis = bool(getattr(args, "visualizations", False))
     detect_well = bool(getattr(args, "detect_well", False))
     well_seed = int(getattr(args, "well_seed", 0) or 0)
+    tree_vis = bool(getattr(args, "tree_visualizations", False))
+    vis_width = int(getattr(args, "vis_width", 2000) or 2000)
+    suffix_of = {(cfg["thresh1"], cfg["thresh2"]): sfx for cfg, sfx in branches.threshold_grid(config)}
     ids = sorted(paths)
     fields = {}
 
@@ -241,7 +249,7 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
             width_um = st.shape[-1] * px
         return width_um
 
-    def analyze_fn(batch, width_um, thresh, input_bits):
+    def analyze_fn(batch, width_um, thresh, input_bits, ids):
         # the vesselness image does not depend on the graph thresholds: one field per stack, swept over the grid
         sw_px, min_px, max_px = branches.graph_px_params(config, DOWNSAMPLE_WIDTH, width_um)
         rows = []
@@ -256,6 +264,14 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
                 fields[i] = (field, pruning)
             rows.append((i,) + sato.field_stats(handle, fields[i][0], thresh[0], thresh[1], sw_px, min_px, max_px,
                                                 bool(config.get("remove_isolated_branches", False)), pruning_mask=fields[i][1]))
+            if tree_vis:
+                # compute_branches.py:431-450: the tree of the 0..255 field over the full-resolution max projection, scaled by W / 384 (:437)
+                background = st.max(0)
+                tree, bars, _ = branches.field_tree(handle, _lib.host_rescale255_f32(fields[i][0]), config, width_um, thresh, fields[i][1],
+                                                    background.shape[1] / fields[i][0].shape[1])
+                if len(bars) == 0:
+                    print(f"No branches found for {ids[i]}.", flush=True)
+                branches.save_tree_visualizations(handle, background, tree, bars, out_root / "visualizations" / ids[i], suffix_of[thresh], vis_width)
         return rows
 
     def load_and_keep(img_id):
@@ -270,7 +286,8 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
 
     # one stack per analysis call (chunk=1): a stack is the unit the reference streams, and it can be gigabytes
     try:
-        gathered = branches.run_sharded(ids, load_and_keep, width_fn, analyze_fn, config, rank, ws, chunk=1, log=lambda m: print(m, flush=True))
+        gathered = branches.run_sharded(ids, load_and_keep, width_fn, analyze_fn, config, rank, ws, chunk=1, log=lambda m: print(m, flush=True),
+                                        pass_ids=True)
     except distributed.RankFailed:
         handle.close()
         finish_distributed(ws)
@@ -361,7 +378,20 @@ def main(args=None):
 
     well_cache = {}
 
-    def analyze_fn(batch, width_um, thresh, input_bits):
+    # --tree-visualizations (compute_branches.py:431-450): the pictures are written per image and threshold configuration inside analyze_fn
+    tree_vis = bool(getattr(args, "tree_visualizations", False))
+    vis_width = int(getattr(args, "vis_width", 2000) or 2000)
+    suffix_of = {(cfg["thresh1"], cfg["thresh2"]): sfx for cfg, sfx in branches.threshold_grid(config)}
+
+    def analyze_fn(batch, width_um, thresh, input_bits, ids):
+        if tree_vis and not detect_well:
+            rows, overlays, bars = branches.analyze_batch_tree(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh,
+                                                               input_bits=input_bits, vis_width=vis_width)
+            for img_id, ov, br in zip(ids, overlays, bars):
+                if len(br) == 0:
+                    print(f"No branches found for {img_id}.", flush=True)
+                branches.save_tree_pictures(ov, br, out_root / "visualizations" / img_id, suffix_of[thresh], vis_width)
+            return rows
         if not detect_well:
             return branches.analyze_batch(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits)
         # --detect-well (compute_branches.py:318-337): the fields do not depend on the graph thresholds -- one staged pass per
@@ -369,9 +399,21 @@ def main(args=None):
         if well_cache.get("batch") is not batch:
             well_cache.clear()
             well_cache["batch"] = batch
-            well_cache["fields"] = branches.well_fields(model.handle, batch, model.ds_ratio, input_bits, well_seed,
-                                                        warn=lambda m: print(f"\033[93m[WARNING]\033[0m {m}", flush=True))
-        return branches.well_rows(model.handle, well_cache["fields"], config, width_um, thresh)
+            well_cache["fields"], well_cache["backgrounds"] = branches.well_fields(
+                model.handle, batch, model.ds_ratio, input_bits, well_seed, warn=lambda m: print(f"\033[93m[WARNING]\033[0m {m}", flush=True),
+                return_backgrounds=True)
+        if not tree_vis:
+            return branches.well_rows(model.handle, well_cache["fields"], config, width_um, thresh)
+        # the tree of each pruned graph over the image's own down-sampled picture; count, total and average come out of the same
+        # call (tmat_morse_tree shares tmat_morse_stats' code), so the rows are well_rows' rows
+        rows = []
+        for i, ((f255, pruning, _), background) in enumerate(zip(well_cache["fields"], well_cache["backgrounds"])):
+            tree, bars, stats = branches.field_tree(model.handle, f255, config, width_um, thresh, pruning, background.shape[1] / f255.shape[1])
+            if len(bars) == 0:
+                print(f"No branches found for {ids[i]}.", flush=True)
+            branches.save_tree_visualizations(model.handle, background, tree, bars, out_root / "visualizations" / ids[i], suffix_of[thresh], vis_width)
+            rows.append((i,) + stats)
+        return rows
 
     vis = bool(getattr(args, "visualizations", False))
 
@@ -383,7 +425,7 @@ def main(args=None):
 
     try:
         gathered = branches.run_sharded(ids, load_and_keep, width_fn, analyze_fn, config, rank, ws,
-                                        log=lambda m: print(m, flush=True))
+                                        log=lambda m: print(m, flush=True), pass_ids=True)
     except distributed.RankFailed:          # the failing rank has printed the reference's message; every rank exits with code 1
         model.handle.close()
         finish_distributed(ws)

@@ -21,6 +21,9 @@ class TmatError(RuntimeError):
     pass
 
 
+E_CAP = -4          # TMAT_E_CAP (include/tmat.h): a caller-provided output capacity is too small
+
+
 class Row(C.Structure):
     _fields_ = [("index", C.c_int64), ("count", C.c_int64), ("total_px", C.c_double), ("avg_px", C.c_double)]
 
@@ -59,8 +62,17 @@ def lib():
     L.tmat_dmt_graph_batch.argtypes = [vp, vp, i, i, i, f, f, vp, i, vp, i, vp, vp]
     L.tmat_morse_stats.argtypes = [vp, i, vp, i, i, i, i, i, i, i, vp, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), vp, i]
+    L.tmat_morse_tree.argtypes = [vp, i, vp, i, i, i, i, i, i, i, vp, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double), vp, vp, i, vp, i, C.POINTER(i), C.POINTER(i)]
+    L.tmat_branch_color.argtypes = [i, vp]
+    L.tmat_render_tree.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, i, vp]
+    L.tmat_render_tree_timed.argtypes = L.tmat_render_tree.argtypes + [vp]
+    L.tmat_host_render_tree.argtypes = [vp, i, i, i, i, vp, vp, vp, i, vp]
+    L.tmat_host_render_barcode.argtypes = [vp, i, i, vp]
     L.tmat_analyze_batch_dev.argtypes = [vp, vp, i, i, i, C.c_double, i, f, f, i, i, i, i, C.c_int64, vp]
     L.tmat_analyze_batch.argtypes = [vp, vp, i, i, i, C.c_double, i, f, f, i, i, i, i, C.c_int64, vp]
+    L.tmat_analyze_batch_tree_dev.argtypes = L.tmat_analyze_batch_dev.argtypes + [i, vp, vp, i, vp]
+    L.tmat_analyze_batch_tree.argtypes = L.tmat_analyze_batch.argtypes + [i, vp, vp, i, vp]
     L.tmat_dev_alloc.argtypes = [vp, sz, C.POINTER(vp)]
     L.tmat_dev_free.argtypes = [vp, vp]
     L.tmat_dev_upload.argtypes = [vp, vp, vp, sz]
@@ -105,7 +117,8 @@ EXPORTS = [
     "tmat_last_error", "tmat_version", "tmat_create", "tmat_create_plain", "tmat_destroy", "tmat_sync", "tmat_set_input_depth", "tmat_unet_predict",
     "tmat_predict_smooth", "tmat_segment_batch", "tmat_postprocess_batch", "tmat_filter_edt_batch", "tmat_medial_axis_batch", "tmat_finish_batch", "tmat_filter_mask_batch", "tmat_zproj_batch", "tmat_zproj_dev", "tmat_gather_rows",
     "tmat_dmt_graph", "tmat_dmt_graph_batch", "tmat_morse_stats",
-    "tmat_analyze_batch_dev", "tmat_analyze_batch", "tmat_dev_alloc", "tmat_dev_free", "tmat_dev_upload",
+    "tmat_morse_tree", "tmat_branch_color", "tmat_render_tree", "tmat_render_tree_timed", "tmat_host_render_tree", "tmat_host_render_barcode",
+    "tmat_analyze_batch_dev", "tmat_analyze_batch", "tmat_analyze_batch_tree_dev", "tmat_analyze_batch_tree", "tmat_dev_alloc", "tmat_dev_free", "tmat_dev_upload",
     "tmat_prof_enable", "tmat_prof_read", "tmat_debug_poison", "tmat_set_precision", "tmat_set_input_norm", "tmat_preprocess_batch", "tmat_well_threshold", "tmat_well_threshold_f64", "tmat_canny_mask", "tmat_host_lanczos4_u16", "tmat_host_rescale01_u16",
     "tmat_host_rescale255_f32", "tmat_host_filter_mask", "tmat_host_skeletonize", "tmat_host_medial_axis",
     "tmat_host_permutation", "tmat_host_postprocess",
@@ -272,6 +285,22 @@ class Handle:
                                 None if resid is None else ptr(resid), int(bool(relu_in)), int(bool(relu_out)), ptr(out)), "tmat_conv2d")
         return out
 
+    def render_tree(self, backgrounds, trees, vis_width=2000):
+        """tmat_render_tree: the tree overlays of n backgrounds (n, bh, bw) u16 / f32 on the device -> (n, vh, vw, 3) u8;
+        trees: one (segs (k, 4) f64, seg_branch (k) i32) pair per image, as morse_tree returns them"""
+        bg, dt, segs, sb, off, out = _render_tree_args(backgrounds, trees, vis_width)
+        check(lib().tmat_render_tree(self._h, ptr(bg), dt, bg.shape[0], bg.shape[1], bg.shape[2], ptr(segs), ptr(sb), ptr(off), int(vis_width),
+                                     ptr(out)), "tmat_render_tree")
+        return out
+
+    def render_tree_timed(self, backgrounds, trees, vis_width=2000):
+        """tmat_render_tree_timed: (overlays, {phase: HIP-event ms}) with the phases upload, minmax, render, copy_back"""
+        bg, dt, segs, sb, off, out = _render_tree_args(backgrounds, trees, vis_width)
+        ms = np.zeros(4, np.float32)
+        check(lib().tmat_render_tree_timed(self._h, ptr(bg), dt, bg.shape[0], bg.shape[1], bg.shape[2], ptr(segs), ptr(sb), ptr(off), int(vis_width),
+                                           ptr(out), ptr(ms)), "tmat_render_tree_timed")
+        return out, dict(zip(("upload", "minmax", "render", "copy_back"), (float(v) for v in ms)))
+
     def debug_poison(self, byte_pattern=0xFF):
         """test-only: fill every scratch workspace of the handle with a byte pattern (include/tmat.h:tmat_debug_poison)"""
         check(lib().tmat_debug_poison(self._h, int(byte_pattern)), "tmat_debug_poison")
@@ -328,6 +357,71 @@ def morse_stats(V, E, shape, smoothing_window, min_branch_length, max_branch_len
                                  ptr(pm) if pm is not None else None, C.byref(cnt), C.byref(tot), C.byref(avg), ptr(bars), cap),
           "tmat_morse_stats")
     return bars[: cnt.value].copy(), cnt.value, tot.value, avg.value
+
+
+def morse_tree(V, E, shape, smoothing_window, min_branch_length, max_branch_length=None, remove_isolated_branches=False,
+               pruning_mask=None, scaling_factor=1.0):
+    """tmat_morse_tree: (segs (s, 4) f64 [x1, y1, x2, y2], seg_branch (s) i32, bars (k, 2) f64 scaled, count, total_px, avg_px)."""
+    V = np.ascontiguousarray(V, np.int32).reshape(-1, 2)
+    E = np.ascontiguousarray(E, np.int32).reshape(-1, 2)
+    pm = None
+    if pruning_mask is not None:
+        pm = np.ascontiguousarray(np.asarray(pruning_mask) > 0, np.uint8)
+    cap = max(len(V), 1)                      # a forest has fewer edges than vertices, and every segment is one of its edges
+    segs = np.empty((cap, 4), np.float64)
+    sb = np.empty(cap, np.int32)
+    bars = np.empty((cap, 2), np.float64)
+    cnt, tot, avg, ns, nb = C.c_int64(), C.c_double(), C.c_double(), C.c_int(), C.c_int()
+    check(lib().tmat_morse_tree(ptr(V), len(V), ptr(E), len(E), int(shape[0]), int(shape[1]), int(smoothing_window),
+                                int(min_branch_length), int(max_branch_length or 0), int(bool(remove_isolated_branches)),
+                                ptr(pm) if pm is not None else None, float(scaling_factor), C.byref(cnt), C.byref(tot), C.byref(avg),
+                                ptr(segs), ptr(sb), cap, ptr(bars), cap, C.byref(ns), C.byref(nb)), "tmat_morse_tree")
+    return segs[: ns.value].copy(), sb[: ns.value].copy(), bars[: nb.value].copy(), cnt.value, tot.value, avg.value
+
+
+def branch_color(i):
+    """tmat_branch_color: the (R, G, B) bytes branch i is drawn in"""
+    rgb = np.zeros(3, np.uint8)
+    check(lib().tmat_branch_color(int(i), ptr(rgb)), "tmat_branch_color")
+    return rgb
+
+
+def tree_canvas_shape(bh, bw, vis_width=2000):
+    """(vh, vw) of the overlay of a (bh, bw) background: Python's round() is round-half-even, as the library's"""
+    return int(round(vis_width * bh / bw)), int(vis_width)
+
+
+def _render_tree_args(backgrounds, trees, vis_width):
+    bg = np.asarray(backgrounds)
+    if bg.ndim == 2:
+        bg = bg[None]
+    if bg.ndim != 3 or len(trees) != bg.shape[0]:
+        raise ValueError("render_tree: expected (n, bh, bw) backgrounds and one (segs, seg_branch) pair per image")
+    bg = np.ascontiguousarray(bg, np.uint16 if bg.dtype == np.uint16 else np.float32)
+    off = np.zeros(len(trees) + 1, np.int32)
+    off[1:] = np.cumsum([len(t[0]) for t in trees])
+    segs = np.ascontiguousarray(np.concatenate([np.asarray(t[0], np.float64).reshape(-1, 4) for t in trees] + [np.zeros((1, 4))]))
+    sb = np.ascontiguousarray(np.concatenate([np.asarray(t[1], np.int32).reshape(-1) for t in trees] + [np.zeros(1, np.int32)]))
+    vh, vw = tree_canvas_shape(bg.shape[1], bg.shape[2], vis_width)
+    out = np.empty((bg.shape[0], vh, vw, 3), np.uint8)
+    return bg, 0 if bg.dtype == np.uint16 else 1, segs, sb, off, out
+
+
+def host_render_tree(backgrounds, trees, vis_width=2000):
+    """tmat_host_render_tree: the host twin of Handle.render_tree (same bytes, no GPU)"""
+    bg, dt, segs, sb, off, out = _render_tree_args(backgrounds, trees, vis_width)
+    check(lib().tmat_host_render_tree(ptr(bg), dt, bg.shape[0], bg.shape[1], bg.shape[2], ptr(segs), ptr(sb), ptr(off), int(vis_width), ptr(out)),
+          "tmat_host_render_tree")
+    return out
+
+
+def host_render_barcode(bars, vis_width=2000):
+    """tmat_host_render_barcode: (S, S, 3) u8 with S = round(0.9 vis_width)"""
+    bars = np.ascontiguousarray(bars, np.float64).reshape(-1, 2)
+    S = int(round(vis_width * 0.9))
+    out = np.empty((S, S, 3), np.uint8)
+    check(lib().tmat_host_render_barcode(ptr(bars), len(bars), int(vis_width), ptr(out)), "tmat_host_render_barcode")
+    return out
 
 
 # -- host pixel stages (csrc/postproc.cpp); exposed for stage-wise parity tests --------------------

@@ -75,18 +75,72 @@ def analyze_batch(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_wid
     return [(r.index, r.count, r.total_px, r.avg_px) for r in rows]
 
 
+def analyze_batch_tree(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_width_microns: float, ds_ratio: float = 0.625,
+                       thresh=(5.0, 10.0), first_index: int = 0, input_bits: int = 16, vis_width: int = 2000, cap_bars: int = 4096):
+    """analyze_batch "with tree" (tmat_analyze_batch_tree): imgs (n, H, W) uint16 -> (rows as analyze_batch returns them, overlays
+    (n, vh, vw, 3) u8 drawn per pass on the device over the down-sampled images, [bars (k, 2) f64 scaled] per image)."""
+    imgs = np.ascontiguousarray(imgs, np.uint16)
+    n, H, W = imgs.shape
+    sw_px, min_px, max_px = graph_px_params(config, DOWNSAMPLE_WIDTH, image_width_microns)
+    rows = (_lib.Row * n)()
+    hh, ww = int(round(W * ds_ratio)), int(round(H * ds_ratio))            # cv2 reads dsize as (width, height)
+    vh, vw = _lib.tree_canvas_shape(hh, ww, vis_width)
+    rgb = np.empty((n, vh, vw, 3), np.uint8)
+    nb = np.zeros(n, np.int32)
+    L = _lib.lib()
+    _lib.check(L.tmat_set_input_depth(handle.raw, int(input_bits)), "tmat_set_input_depth")
+    fh, fw = dsamp_shape((H, W))
+    # a branch holds at least one vertex of its own, so fh * fw bars always suffice: one retry with that capacity when cap_bars is too small
+    for cap in (int(cap_bars), max(int(cap_bars), fh * fw)):
+        bars = np.empty((n, cap, 2), np.float64)
+        rc = L.tmat_analyze_batch_tree(handle.raw, _lib.ptr(imgs), n, H, W, float(ds_ratio), DOWNSAMPLE_WIDTH, float(thresh[0]), float(thresh[1]),
+                                       int(sw_px), int(min_px), int(max_px or 0), int(bool(config.get("remove_isolated_branches", False))),
+                                       int(first_index), rows, int(vis_width), _lib.ptr(rgb), _lib.ptr(bars), cap, _lib.ptr(nb))
+        if rc != _lib.E_CAP or cap >= fh * fw:
+            break
+    _lib.check(rc, "tmat_analyze_batch_tree")
+    return [(r.index, r.count, r.total_px, r.avg_px) for r in rows], rgb, [bars[i, : nb[i]].copy() for i in range(n)]
+
+
+def save_tree_pictures(overlay, bars, vis_dir, suffix: str = "", vis_width: int = 2000):
+    """morse_tree{suffix}.png (a finished overlay) and barcode{suffix}.png into vis_dir, "-N" unique names; nothing for an image without
+    branches (the reference prints "No branches found" and skips its plots, compute_branches.py:426-429).  Returns the written paths."""
+    import os
+    from pathlib import Path
+    from PIL import Image
+
+    if len(bars) == 0:
+        return []
+    vis_dir = Path(vis_dir)
+    vis_dir.mkdir(parents=True, exist_ok=True)
+
+    def save(a, name):
+        file = vis_dir / name
+        stem, ext = os.path.splitext(file.name)
+        n = 1
+        while file.exists():                                # helper.get_unique_output_filepath
+            n += 1
+            file = vis_dir / f"{stem}-{n}{ext}"
+        Image.fromarray(np.ascontiguousarray(a), "RGB").save(file)
+        return str(file)
+    return [save(overlay, f"morse_tree{suffix}.png"), save(_lib.host_render_barcode(bars, vis_width), f"barcode{suffix}.png")]
+
+
 def dsamp_shape(img_shape, width: int = DOWNSAMPLE_WIDTH):
     """compute_branches.py:218-222: img_dsamp_res = round(shape * width / W)"""
     r = width / img_shape[1]
     return tuple(int(v) for v in np.round(np.multiply(img_shape[:2], r)).astype(int))
 
 
-def well_fields(handle: _lib.Handle, imgs: np.ndarray, ds_ratio: float = 0.625, input_bits: int = 16, well_seed: int = 0, warn=print):
+def well_fields(handle: _lib.Handle, imgs: np.ndarray, ds_ratio: float = 0.625, input_bits: int = 16, well_seed: int = 0, warn=print,
+                return_backgrounds: bool = False):
     """The 2-D branch of analyze_img with use_well_mask=True up to the vesselness field (compute_branches.py:309-361), image by
     image through the staged GPU entry points: Lanczos + rescale (tmat_preprocess_batch) -> make_well_mask on THAT image
     (:318-319, tmat_amd/well_mask_generation.py) -> predict(img * well_mask) (:328) -> (pred > 0.5) * well_mask ->
     filter_branch_seg_mask (:334-337) -> medial axis, centre-line weighting of the unmasked prediction, resize (:340-357).
-    Returns [(field255 (fh, fw) f32, pruning_mask (fh, fw) bool, well_mask)] per image: the graph stages follow per threshold."""
+    Returns [(field255 (fh, fw) f32, pruning_mask (fh, fw) bool, well_mask)] per image: the graph stages follow per threshold.
+    return_backgrounds: also return the (n, hh, ww) f32 down-sampled images (:312-314 original_image, min-max rescaled to 0..1: the tree
+    overlay rescales its background itself, so the grey levels are those of the Lanczos image)."""
     from . import well_mask_generation as wmg
     imgs = np.ascontiguousarray(imgs, np.uint16)
     n, H, W = imgs.shape
@@ -108,7 +162,7 @@ def well_fields(handle: _lib.Handle, imgs: np.ndarray, ds_ratio: float = 0.625, 
     for i in range(n):
         pruning = wmg._resize_nearest(np.logical_not(masks[i][1]), fshape).astype(bool)      # resize(order=0) (:359-361)
         out.append((f255[i], pruning, well[i]))
-    return out
+    return (out, x) if return_backgrounds else out
 
 
 def well_rows(handle: _lib.Handle, fields, config: dict, image_width_microns: float, thresh=(5.0, 10.0), first_index: int = 0):
@@ -124,13 +178,25 @@ def well_rows(handle: _lib.Handle, fields, config: dict, image_width_microns: fl
     return rows
 
 
+def field_tree(handle, field255: np.ndarray, config: dict, image_width_microns: float, thresh=(5.0, 10.0), pruning_mask=None,
+               scaling_factor: float = 1.0):
+    """The colored tree of one 0..255 field (compute_branches.py:401-426 + topology.py:358-389): DMT graph, MorseGraph with the pruning mask
+    -> ((segs, seg_branch), bars scaled, (count, total_px, avg_px)) through tmat_morse_tree.  The --detect-well and Z-stack forms of
+    --tree-visualizations draw this over their own backgrounds (save_tree_visualizations)."""
+    sw_px, min_px, max_px = graph_px_params(config, field255.shape[1], image_width_microns)
+    V, E = _lib.dmt_graph(field255, thresh[0], thresh[1], handle=handle)
+    segs, sb, bars, cnt, tot, avg = _lib.morse_tree(V, E, field255.shape, sw_px, min_px, max_px, bool(config.get("remove_isolated_branches", False)),
+                                                    pruning_mask, scaling_factor)
+    return (segs, sb), bars, (cnt, tot, avg)
+
+
 class InputError(Exception):
     """an image of the run cannot be loaded / lacks its physical width: raised by run_sharded's callbacks (after they have
     printed the reference's message); the run then fails on EVERY rank after the gather instead of leaving the others blocked"""
 
 
 def run_sharded(ids, load_fn, width_fn, analyze_fn, config: dict, rank: int = 0, world_size: int = 1, chunk: int = 64,
-                log=print):
+                log=print, pass_ids: bool = False):
     """The per-run driver of scripts/compute_branches.py (reference :585-594 loops over the images one by one):
     rank `rank` of `world_size` takes a contiguous block of `ids`, loads its images in bounded chunks of at most `chunk`
     (images of equal shape, physical width and bit depth are analysed as one batch), and all ranks exchange their rows
@@ -138,6 +204,8 @@ def run_sharded(ids, load_fn, width_fn, analyze_fn, config: dict, rank: int = 0,
 
     load_fn(img_id) -> uint8/uint16 (H, W) array; width_fn(img_id, img) -> image width in microns;
     analyze_fn(batch uint16 (n, H, W), width_um, thresh=(t1, t2), input_bits=8|16) -> [(i, count, total_px, avg_px)].
+    pass_ids: analyze_fn also takes ids=[the id of every image of the batch, in batch order] (the pictures of --tree-visualizations
+    are written per image inside analyze_fn).
     Returns {file-name suffix: [(global index, count, total_um, avg_um)] sorted by index}, on every rank."""
     from . import distributed
     ids = list(ids)
@@ -148,8 +216,9 @@ def run_sharded(ids, load_fn, width_fn, analyze_fn, config: dict, rank: int = 0,
     def flush(groups):
         for (shape, width_um, bits), items in groups.items():
             batch = np.stack([im for _, im in items]).astype(np.uint16)
+            extra = {"ids": [ids[g] for g, _ in items]} if pass_ids else {}
             for cfg, suffix in grid:
-                rows = analyze_fn(batch, width_um, thresh=(cfg["thresh1"], cfg["thresh2"]), input_bits=bits)
+                rows = analyze_fn(batch, width_um, thresh=(cfg["thresh1"], cfg["thresh2"]), input_bits=bits, **extra)
                 for (gidx, _), r in zip(items, rows):
                     results[suffix].append((gidx, r[1], pixels_to_microns(r[2], DOWNSAMPLE_WIDTH, width_um),
                                             pixels_to_microns(r[3], DOWNSAMPLE_WIDTH, width_um)))
@@ -188,7 +257,7 @@ def save_visualizations(handle: _lib.Handle, img: np.ndarray, vis_dir, ds_ratio:
     0..255 + cv2.imwrite; :315 original_image.png, :331 prediction.png, :347 segmentation_mask.png, :348
     distance_transform.png) for one image, through the staged entry points of the same GPU path (segment ->
     filter + EDT -> medial axis); the centre-line weighting of :341-344 is evaluated here with the scipy call the
-    reference makes.  The matplotlib barcode / tree plots (:431-450) are not reproduced.  Returns the written paths."""
+    reference makes.  The barcode / tree pictures (:431-450) are save_tree_visualizations' job.  Returns the written paths."""
     import os
     from pathlib import Path
     from PIL import Image
@@ -253,3 +322,17 @@ def save_stack_visualizations(handle: _lib.Handle, stack: np.ndarray, vis_dir, h
         Image.fromarray(np.rint(a).astype(np.uint8)).save(file)
         return str(file)
     return [save_vis(np.asarray(stack).max(0), "original_image.png"), save_vis(field, "vesselness_image.png")]
+
+
+def save_tree_visualizations(handle, background: np.ndarray, tree, bars, vis_dir, suffix: str = "", vis_width: int = 2000):
+    """morse_tree{suffix}.png and barcode{suffix}.png of one image (compute_branches.py:431-450) as the library's rasters (DESIGN.md
+    "Tree overlay and barcode pictures"), PNG-encoded with PIL.  background: the (bh, bw) u16 / f32 image the tree is drawn over; tree:
+    (segs, seg_branch) and bars as _lib.morse_tree returns them, in background pixels; suffix: threshold_grid's "_CONFIG..." string.
+    handle: the _lib.Handle whose device rasterises the overlay (tmat_render_tree); None asks for the host twin (tmat_host_render_tree, the
+    same bytes).  Names follow the reference's "-N" unique-name rule.  An image without branches (the reference prints "No branches
+    found" and skips its plots) writes nothing.  Returns the written paths."""
+    if len(bars) == 0:
+        return []
+    render = handle.render_tree if handle is not None else _lib.host_render_tree
+    overlay = render(np.asarray(background)[None], [tree], vis_width)[0]
+    return save_tree_pictures(overlay, bars, vis_dir, suffix, vis_width)
