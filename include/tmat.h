@@ -566,6 +566,13 @@ int tmat_prof_read(tmat_handle h, double *ms, int64_t *launches, double *flops, 
 int tmat_debug_poison(tmat_handle h, int byte_pattern);
 
 /*
+ * Test-only (tests/test_gpu_held_memory.py): what the handle retains between calls, in bytes -- exactly the workspaces
+ * tmat_debug_poison fills (handle-lifetime buffers, the buffers of the current pass geometry, the side tools' workspaces and the
+ * pool of the Z-stack entry points), device and pinned separately.  Constants are not counted.
+ */
+int tmat_debug_held_bytes(tmat_handle h, size_t *device_bytes, size_t *pinned_bytes);
+
+/*
  * Region plan of the UNet up path for an (hh, ww) image tiled with `patch`-wide windows (host arithmetic, no GPU and no handle).
  * The smooth blend discards the padding ring, so of every patch it reads the rectangle  patch ∩ interior  only; the tiled entry points
  * compute just that rectangle, grown layer by layer by the taps' reach, in every up-path layer (TMAT_ROI=0 at tmat_create: whole

@@ -138,10 +138,10 @@ static int render_tree_impl(tmat_handle hd, const void *background, int bg_dtype
         off[img + 1] = (int)ss.size();
     }
     const int K = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)512 << 20) / cper));      // <= 512 MiB of canvases per launch
-    uint8_t *dbg = (uint8_t *)ws_get(c, 24, (size_t)n * per * esz);
-    OverlaySeg *dseg = (OverlaySeg *)ws_get(c, 25, ss.size() * sizeof(OverlaySeg));
-    float *dmm = (float *)ws_get(c, 26, (size_t)n * 4 * sizeof(float) + (size_t)(n + 1) * sizeof(int));
-    uint8_t *drgb = (uint8_t *)ws_get(c, 27, (size_t)K * cper);
+    uint8_t *dbg = (uint8_t *)ws_get(c, WS_TREE_BG, (size_t)n * per * esz);
+    OverlaySeg *dseg = (OverlaySeg *)ws_get(c, WS_TREE_SEG, ss.size() * sizeof(OverlaySeg));
+    float *dmm = (float *)ws_get(c, WS_TREE_MM, (size_t)n * 4 * sizeof(float) + (size_t)(n + 1) * sizeof(int));
+    uint8_t *drgb = (uint8_t *)ws_get(c, WS_TREE_RGB, (size_t)K * cper);
     if (!dbg || !dseg || !dmm || !drgb) return TMAT_E_HIP;
     int *doff = (int *)(dmm + 4 * (size_t)n);
     hipStream_t s = c->stream;

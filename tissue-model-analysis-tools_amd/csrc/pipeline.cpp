@@ -31,6 +31,8 @@ void launch_rescale01(const uint16_t *x, int n, size_t per, int *mn, int *mx, fl
 
 static int round_half_even(double v) { return (int)std::nearbyint(v); }
 
+template <class T> static bool set_ptr(T *&ptr, void *p) { ptr = (T *)p; return p != nullptr; }
+
 // device / pinned buffers for one image geometry, cached on the handle
 static int ensure_pass_buffers(Ctx *c, int K, int H, int W, int h, int w, int fh, int fw)
 {
@@ -47,63 +49,40 @@ static int ensure_pass_buffers(Ctx *c, int K, int H, int W, int h, int w, int fh
     TMAT_HIP(hipMemcpy(b.xc, xc.data(), xc.size() * 4, hipMemcpyHostToDevice));
     TMAT_HIP(hipMemcpy(b.yi, yi.data(), yi.size() * 4, hipMemcpyHostToDevice));
     TMAT_HIP(hipMemcpy(b.yc, yc.data(), yc.size() * 4, hipMemcpyHostToDevice));
-    // every scratch buffer is recorded with its size: tmat_debug_poison (test-only) fills them between calls
-#define DALLOC(ptr_, bytes_) { const size_t nb_ = (bytes_); TMAT_HIP(hipMalloc((void **)&(ptr_), nb_)); b.ws.push_back(WsEnt{(void *)(ptr_), nb_, false}); }
-#define HALLOC(ptr_, bytes_) { const size_t nb_ = (bytes_); TMAT_HIP(hipHostMalloc((void **)&(ptr_), nb_, hipHostMallocDefault)); b.ws.push_back(WsEnt{(void *)(ptr_), nb_, true}); }
-    DALLOC(b.tmp, (size_t)K * H * w * sizeof(float));
-    DALLOC(b.small, (size_t)K * h * w * sizeof(uint16_t));
-    DALLOC(b.x, (size_t)K * h * w * sizeof(float));
-    DALLOC(b.mn, (size_t)K * sizeof(int)); DALLOC(b.mx, (size_t)K * sizeof(int));
-    DALLOC(b.morph_ws, morph_workspace_bytes(K, h, w));
-    DALLOC(b.finish_ws, finish_workspace_bytes(K, h, w, fh, fw));
-    for (int i = 0; i < 2; i++) {
-        DALLOC(b.skel[i], (size_t)K * h * w);
-        HALLOC(b.skel_host[i], (size_t)K * h * w);
-        DALLOC(b.field[i], (size_t)K * fh * fw * sizeof(float));
-        DALLOC(b.f255[i], (size_t)K * fh * fw * sizeof(float));
-        HALLOC(b.f255_host[i], (size_t)K * fh * fw * sizeof(float));
+    // every scratch buffer is owned by b.ws: free_pass releases that list, tmat_debug_poison (test-only) fills it between calls
+    WsList &ws = b.ws;
+    auto dev = [&ws](auto *&ptr, size_t bytes) { return set_ptr(ptr, ws.dev(bytes)); };
+    auto pin = [&ws](auto *&ptr, size_t bytes) { return set_ptr(ptr, ws.pinned(bytes)); };
+    const size_t px = (size_t)K * h * w, fpx = (size_t)K * fh * fw;
+    bool ok = dev(b.tmp, (size_t)K * H * w * sizeof(float)) && dev(b.small, px * sizeof(uint16_t)) && dev(b.x, px * sizeof(float)) &&
+              dev(b.mn, (size_t)K * sizeof(int)) && dev(b.mx, (size_t)K * sizeof(int)) && dev(b.morph_ws, morph_workspace_bytes(K, h, w)) &&
+              dev(b.finish_ws, finish_workspace_bytes(K, h, w, fh, fw));
+    for (int i = 0; i < 2 && ok; i++)
+        ok = dev(b.skel[i], px) && pin(b.skel_host[i], px) && dev(b.field[i], fpx * sizeof(float)) && dev(b.f255[i], fpx * sizeof(float)) &&
+             pin(b.f255_host[i], fpx * sizeof(float));
+    if (ok && thin_dev_supported(h, w)) {
+        ok = dev(b.thin_ws, thin_workspace_bytes(K, h, w)) && dev(b.tie, px * sizeof(uint32_t));
+        for (int i = 0; i < 2 && ok; i++)
+            ok = dev(b.nfg[i], (size_t)K * sizeof(int)) && pin(b.nfg_host[i], (size_t)K * sizeof(int)) && pin(b.tie_host[i], px * sizeof(uint32_t));
     }
-    if (thin_dev_supported(h, w)) {
-        DALLOC(b.thin_ws, thin_workspace_bytes(K, h, w));
-        DALLOC(b.tie, (size_t)K * h * w * sizeof(uint32_t));
-        for (int i = 0; i < 2; i++) {
-            DALLOC(b.nfg[i], (size_t)K * sizeof(int));
-            HALLOC(b.nfg_host[i], (size_t)K * sizeof(int));
-            HALLOC(b.tie_host[i], (size_t)K * h * w * sizeof(uint32_t));
-        }
-    }
-    if (fh >= 2 && fw >= 2) {
-        const size_t nE = dmt_edge_count(fh, fw);
-        DALLOC(b.dmt_ws, dmt_workspace_bytes(K, fh, fw));
-        for (int i = 0; i < 2; i++) {
-            DALLOC(b.dmt_ids[i], (size_t)K * nE * sizeof(int32_t));
-            HALLOC(b.dmt_ids_host[i], (size_t)K * nE * sizeof(int32_t));
-            DALLOC(b.dmt_m[i], (size_t)K * sizeof(int));
-            HALLOC(b.dmt_m_host[i], (size_t)K * sizeof(int));
-        }
-        if (c->dmt_device && c->dmt_sweep_device) {
-            DALLOC(b.dmt_sweep_ws, dmt_sweep_workspace_bytes(K, fh, fw));
-            for (int i = 0; i < 2; i++) {
-                DALLOC(b.dmt_kind[i], (size_t)K * nE);
-                HALLOC(b.dmt_kind_host[i], (size_t)K * nE);
-                DALLOC(b.dmt_pers[i], (size_t)K * nE * sizeof(float));
-                HALLOC(b.dmt_pers_host[i], (size_t)K * nE * sizeof(float));
-            }
+    if (ok && fh >= 2 && fw >= 2) {
+        const size_t nE = (size_t)K * dmt_edge_count(fh, fw);
+        ok = dev(b.dmt_ws, dmt_workspace_bytes(K, fh, fw));
+        for (int i = 0; i < 2 && ok; i++)
+            ok = dev(b.dmt_ids[i], nE * sizeof(int32_t)) && pin(b.dmt_ids_host[i], nE * sizeof(int32_t)) && dev(b.dmt_m[i], (size_t)K * sizeof(int)) &&
+                 pin(b.dmt_m_host[i], (size_t)K * sizeof(int));
+        if (ok && c->dmt_device && c->dmt_sweep_device) {
+            ok = dev(b.dmt_sweep_ws, dmt_sweep_workspace_bytes(K, fh, fw));
+            for (int i = 0; i < 2 && ok; i++)
+                ok = dev(b.dmt_kind[i], nE) && pin(b.dmt_kind_host[i], nE) && dev(b.dmt_pers[i], nE * sizeof(float)) && pin(b.dmt_pers_host[i], nE * sizeof(float));
         }
     }
     b.fh = fh; b.fw = fw;
-    for (int i = 0; i < 2; i++) {
-        DALLOC(b.pred[i], (size_t)K * h * w * sizeof(double));
-        HALLOC(b.pred_host[i], (size_t)K * h * w * sizeof(double));
-        DALLOC(b.filt[i], (size_t)K * h * w);
-        DALLOC(b.dist[i], (size_t)K * h * w * sizeof(double));
-        HALLOC(b.filt_host[i], (size_t)K * h * w);
-        HALLOC(b.dist_host[i], (size_t)K * h * w * sizeof(double));
-        HALLOC(b.conv_host[i], (size_t)K * sizeof(int));
-        TMAT_HIP(hipEventCreateWithFlags(&b.done[i], hipEventDisableTiming));
-    }
-#undef DALLOC
-#undef HALLOC
+    for (int i = 0; i < 2 && ok; i++)
+        ok = dev(b.pred[i], px * sizeof(double)) && pin(b.pred_host[i], px * sizeof(double)) && dev(b.filt[i], px) && dev(b.dist[i], px * sizeof(double)) &&
+             pin(b.filt_host[i], px) && pin(b.dist_host[i], px * sizeof(double)) && pin(b.conv_host[i], (size_t)K * sizeof(int)) &&
+             hip_ok(hipEventCreateWithFlags(&b.done[i], hipEventDisableTiming), "hipEventCreate");
+    if (!ok) return TMAT_E_HIP;
     b.K = K; b.H = H; b.W = W; b.h = h; b.w = w;
     return TMAT_OK;
 }
@@ -405,10 +384,10 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
         tj.sf = (double)w / (double)gp.fw;
         tj.rgb_out = req->rgb_out; tj.bars_out = req->bars_out; tj.cap_b = req->cap_b; tj.n_bars = req->n_bars;
         tj.seg_cap = (size_t)K * fper;
-        uint16_t *bg_all = (uint16_t *)ws_get(c, 24, (size_t)n * h * w * sizeof(uint16_t));
-        tj.dseg = (OverlaySeg *)ws_get(c, 25, tj.seg_cap * sizeof(OverlaySeg));
-        tj.dmm = (float *)ws_get(c, 26, (size_t)K * 4 * sizeof(float) + (size_t)(K + 1) * sizeof(int));
-        tj.drgb = (uint8_t *)ws_get(c, 27, (size_t)K * cper);
+        uint16_t *bg_all = (uint16_t *)ws_get(c, WS_TREE_BG, (size_t)n * h * w * sizeof(uint16_t));
+        tj.dseg = (OverlaySeg *)ws_get(c, WS_TREE_SEG, tj.seg_cap * sizeof(OverlaySeg));
+        tj.dmm = (float *)ws_get(c, WS_TREE_MM, (size_t)K * 4 * sizeof(float) + (size_t)(K + 1) * sizeof(int));
+        tj.drgb = (uint8_t *)ws_get(c, WS_TREE_RGB, (size_t)K * cper);
         if (!bg_all || !tj.dseg || !tj.dmm || !tj.drgb) return TMAT_E_HIP;
         tj.bg_all = bg_all;
         tj.doff = (int *)(tj.dmm + 4 * (size_t)K);
@@ -422,8 +401,8 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
     // the caller may have queued work that produces the images on the main stream (tmat_zproj_dev, tmat_dev_upload)
     if (!use_one_stream() && !hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize")) return TMAT_E_HIP;
     // second input buffer for the front end that runs ahead on the second stream (enqueue_pre)
-    if (c->pre_side && tail_on_side_stream() && g.tiles_per_img <= c->max_patches && !c->patch_in2)
-        TMAT_HIP(hipMalloc((void **)&c->patch_in2, (size_t)c->patch * c->patch * c->patch_cap * sizeof(float)));
+    if (c->pre_side && tail_on_side_stream() && g.tiles_per_img <= c->max_patches && !c->patch_in2 &&
+        !set_ptr(c->patch_in2, c->ws.dev((size_t)c->patch * c->patch * c->patch_cap * sizeof(float), "hipMalloc(patch_in2)"))) return TMAT_E_HIP;
     if (pre_on_side_stream(c, g)) {         // what the caller queued on the main stream (the images) comes first on the second one too
         TMAT_HIP(hipEventRecord(c->ev_pre[0], c->stream));
         TMAT_HIP(hipStreamWaitEvent(c->stream2, c->ev_pre[0], 0));
@@ -465,19 +444,20 @@ int medial_thin_batch_dev(Ctx *c, const uint8_t *mask_dev, const double *dist_de
     int rc = ensure_ma_table(c);
     if (rc) return rc;
     const size_t per = (size_t)hh * ww;
-    int *nfg = nullptr; uint32_t *tie = nullptr; void *ws = nullptr;
     std::vector<int> nfg_host(k, 0);
-    if (!hip_ok(hipMalloc((void **)&nfg, k * sizeof(int)), "hipMalloc") || !hip_ok(hipMalloc((void **)&tie, k * per * sizeof(uint32_t)), "hipMalloc") ||
-        !hip_ok(hipMalloc(&ws, thin_workspace_bytes(k, hh, ww)), "hipMalloc")) rc = TMAT_E_HIP;
+    std::vector<std::vector<uint32_t>> perms(k);
+    DevScope mem(c->ws_pool, s);          // perms / nfg_host must outlive the copies
+    int *nfg = mem.alloc<int>(k);
+    uint32_t *tie = mem.alloc<uint32_t>(k * per);
+    void *ws = mem.alloc_bytes(thin_workspace_bytes(k, hh, ww));
+    if (!mem.ok) rc = TMAT_E_HIP;
     if (!rc && thin_count_dev(mask_dev, k, hh, ww, nfg, s)) rc = TMAT_E_HIP;
     if (!rc && (!hip_ok(hipMemcpyAsync(nfg_host.data(), nfg, k * sizeof(int), hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))) rc = TMAT_E_HIP;
-    std::vector<std::vector<uint32_t>> perms(k);
     if (!rc) parallel_images(k, [&](int i) { legacy_permutation(0, (size_t)nfg_host[i], perms[i]); });
     for (int i = 0; i < k && !rc; i++)
         if (!perms[i].empty() && !hip_ok(hipMemcpyAsync(tie + i * per, perms[i].data(), perms[i].size() * sizeof(uint32_t), hipMemcpyHostToDevice, s), "H2D")) rc = TMAT_E_HIP;
     if (!rc && thin_dev(mask_dev, dist_dev, tie, nfg, k, hh, ww, ws, c->ma_table, skel_dev, s)) { set_error("medial axis: device thinning failed"); rc = TMAT_E_HIP; }
-    if (!rc && !hip_ok(hipStreamSynchronize(s), "sync")) rc = TMAT_E_HIP;      // perms / scratch are released below
-    hipFree(nfg); hipFree(tie); hipFree(ws);
+    if (!rc && !hip_ok(hipStreamSynchronize(s), "sync")) rc = TMAT_E_HIP;      // perms / scratch are released on return
     return rc;
 }
 
@@ -489,23 +469,26 @@ int dmt_graph_device_batch(void *handle, const float *imgs, int n, int R, int C,
     Ctx *c = (Ctx *)handle;
     TMAT_HIP(hipSetDevice(c->device));
     const size_t nE = dmt_edge_count(R, C), npx = (size_t)R * C;
-    float *df = nullptr; void *ws = nullptr; int32_t *ids = nullptr; int *m = nullptr;
     std::vector<int32_t> ids_host((size_t)n * nE);
     std::vector<int> m_host(n, 0);
-    int rc = TMAT_OK;
-    if (!hip_ok(hipMalloc((void **)&df, n * npx * sizeof(float)), "hipMalloc") || !hip_ok(hipMalloc(&ws, dmt_workspace_bytes(n, R, C)), "hipMalloc") ||
-        !hip_ok(hipMalloc((void **)&ids, n * nE * sizeof(int32_t)), "hipMalloc") || !hip_ok(hipMalloc((void **)&m, n * sizeof(int)), "hipMalloc")) rc = TMAT_E_HIP;
+    std::vector<uint8_t> kind_host;
+    std::vector<float> pers_host;
+    DevScope mem(c->ws_pool, c->stream);
+    float *df = mem.alloc<float>(n * npx);
+    void *ws = mem.alloc_bytes(dmt_workspace_bytes(n, R, C));
+    int32_t *ids = mem.alloc<int32_t>(n * nE);
+    int *m = mem.alloc<int>(n);
+    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
     if (!rc && !hip_ok(hipMemcpyAsync(df, imgs, n * npx * sizeof(float), hipMemcpyHostToDevice, c->stream), "H2D")) rc = TMAT_E_HIP;
     if (!rc && dmt_sorted_edges_dev(df, n, R, C, ws, ids, m, c->stream)) { set_error("tmat_dmt_graph: device front end failed"); rc = TMAT_E_HIP; }
     // the two persistence sweeps on the device too (dmt_sweep_kernels.hip; TMAT_DMT_SWEEP_DEVICE=0: on the host); `collect` stays on the host
     const bool sweep_dev = c->dmt_sweep_device;
-    std::vector<uint8_t> kind_host;
-    std::vector<float> pers_host;
-    void *sws = nullptr; uint8_t *dkind = nullptr; float *dpers = nullptr;
     if (!rc && sweep_dev) {
         kind_host.resize((size_t)n * nE); pers_host.resize((size_t)n * nE);
-        if (!hip_ok(hipMalloc(&sws, dmt_sweep_workspace_bytes(n, R, C)), "hipMalloc") || !hip_ok(hipMalloc((void **)&dkind, n * nE), "hipMalloc") ||
-            !hip_ok(hipMalloc((void **)&dpers, n * nE * sizeof(float)), "hipMalloc")) rc = TMAT_E_HIP;
+        void *sws = mem.alloc_bytes(dmt_sweep_workspace_bytes(n, R, C));
+        uint8_t *dkind = mem.alloc<uint8_t>(n * nE);
+        float *dpers = mem.alloc<float>(n * nE);
+        if (!mem.ok) rc = TMAT_E_HIP;
         if (!rc && dmt_sweeps_dev(df, ids, m, n, R, C, sws, dkind, dpers, c->stream)) { set_error("tmat_dmt_graph: device sweeps failed"); rc = TMAT_E_HIP; }
         if (!rc && (!hip_ok(hipMemcpyAsync(kind_host.data(), dkind, n * nE, hipMemcpyDeviceToHost, c->stream), "D2H") ||
                     !hip_ok(hipMemcpyAsync(pers_host.data(), dpers, n * nE * sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H"))) rc = TMAT_E_HIP;
@@ -513,7 +496,6 @@ int dmt_graph_device_batch(void *handle, const float *imgs, int n, int R, int C,
     if (!rc && (!hip_ok(hipMemcpyAsync(ids_host.data(), ids, n * nE * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream), "D2H") ||
                 !hip_ok(hipMemcpyAsync(m_host.data(), m, n * sizeof(int), hipMemcpyDeviceToHost, c->stream), "D2H"))) rc = TMAT_E_HIP;
     if (!hip_ok(hipStreamSynchronize(c->stream), "sync") && !rc) rc = TMAT_E_HIP;
-    hipFree(df); hipFree(ws); hipFree(ids); hipFree(m); hipFree(sws); hipFree(dkind); hipFree(dpers);
     if (rc) return rc;
     std::vector<int> rcs(n, TMAT_OK);
     parallel_images(n, [&](int i) {
@@ -550,8 +532,9 @@ int tmat_segment_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W
     const int K = std::min(n, std::max(1, c->max_patches / g.tiles_per_img));
     int rc = ensure_pass_buffers(c, K, H, W, h, w, std::max(1, c->pass.fh), std::max(1, c->pass.fw));
     if (rc) return rc;
-    uint16_t *dimg = nullptr;
-    TMAT_HIP(hipMalloc((void **)&dimg, (size_t)K * H * W * sizeof(uint16_t)));
+    DevScope mem(c->ws_pool, c->stream);
+    uint16_t *dimg = mem.alloc<uint16_t>((size_t)K * H * W);
+    if (!mem.ok) return TMAT_E_HIP;
     for (int i0 = 0; i0 < n && !rc; i0 += K) {
         const int k = std::min(K, n - i0);
         if (!hip_ok(hipMemcpyAsync(dimg, imgs + (size_t)i0 * H * W, (size_t)k * H * W * 2, hipMemcpyHostToDevice, c->stream), "H2D")) { rc = TMAT_E_HIP; break; }
@@ -560,7 +543,6 @@ int tmat_segment_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W
         if (!hip_ok(hipStreamSynchronize(c->stream), "sync")) { rc = TMAT_E_HIP; break; }
         std::memcpy(pred + (size_t)i0 * h * w, c->pass.pred_host[0], (size_t)k * h * w * sizeof(double));
     }
-    hipFree(dimg);
     return rc;
 }
 
@@ -577,8 +559,9 @@ int tmat_preprocess_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, in
     const int K = std::min(n, std::max(1, c->max_patches / g.tiles_per_img));
     int rc = ensure_pass_buffers(c, K, H, W, h, w, std::max(1, c->pass.fh), std::max(1, c->pass.fw));
     if (rc) return rc;
-    uint16_t *dimg = nullptr;
-    TMAT_HIP(hipMalloc((void **)&dimg, (size_t)K * H * W * sizeof(uint16_t)));
+    DevScope mem(c->ws_pool, c->stream);
+    uint16_t *dimg = mem.alloc<uint16_t>((size_t)K * H * W);
+    if (!mem.ok) return TMAT_E_HIP;
     PassBuf &b = c->pass;
     for (int i0 = 0; i0 < n && !rc; i0 += K) {
         const int k = std::min(K, n - i0);
@@ -586,9 +569,8 @@ int tmat_preprocess_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, in
         launch_lanczos(dimg, k, b.H, b.W, b.h, b.w, b.xi, b.xc, b.yi, b.yc, b.tmp, b.small, c->input_sat, c->stream);
         launch_rescale01(b.small, k, (size_t)b.h * b.w, b.mn, b.mx, b.x, c->stream);
         if (!hip_ok(hipMemcpyAsync(x + (size_t)i0 * h * w, b.x, (size_t)k * h * w * sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H") ||
-            !hip_ok(hipStreamSynchronize(c->stream), "sync")) { hipStreamSynchronize(c->stream); rc = TMAT_E_HIP; break; }
+            !hip_ok(hipStreamSynchronize(c->stream), "sync")) { rc = TMAT_E_HIP; break; }
     }
-    hipFree(dimg);
     return rc;
 }
 
@@ -599,11 +581,12 @@ int tmat_filter_edt_batch(tmat_handle hd, const double *pred, int n, int hh, int
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
     const size_t npx = (size_t)n * hh * ww;
-    double *dp = nullptr, *dd = nullptr; uint8_t *df = nullptr; void *ws = nullptr;
-    int rc = TMAT_OK;
     std::vector<int> conv(n, 0);
-    if (!hip_ok(hipMalloc((void **)&dp, npx * 8), "hipMalloc") || !hip_ok(hipMalloc((void **)&dd, npx * 8), "hipMalloc") ||
-        !hip_ok(hipMalloc((void **)&df, npx), "hipMalloc") || !hip_ok(hipMalloc(&ws, morph_workspace_bytes(n, hh, ww)), "hipMalloc")) rc = TMAT_E_HIP;
+    DevScope mem(c->ws_pool, c->stream);
+    double *dp = mem.alloc<double>(npx), *dd = mem.alloc<double>(npx);
+    uint8_t *df = mem.alloc<uint8_t>(npx);
+    void *ws = mem.alloc_bytes(morph_workspace_bytes(n, hh, ww));
+    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
     if (!rc && !hip_ok(hipMemcpyAsync(dp, pred, npx * 8, hipMemcpyHostToDevice, c->stream), "H2D")) rc = TMAT_E_HIP;
     if (!rc && filter_edt_dev(dp, n, hh, ww, 1, ws, df, dd, c->stream)) rc = TMAT_E_HIP;
     if (!rc && (!hip_ok(hipMemcpyAsync(filtered, df, npx, hipMemcpyDeviceToHost, c->stream), "D2H") ||
@@ -611,7 +594,6 @@ int tmat_filter_edt_batch(tmat_handle hd, const double *pred, int n, int hh, int
                 !hip_ok(hipMemcpyAsync(conv.data(), morph_done_flags(ws, n, hh, ww), n * sizeof(int), hipMemcpyDeviceToHost, c->stream), "D2H") ||
                 !hip_ok(hipStreamSynchronize(c->stream), "sync"))) rc = TMAT_E_HIP;
     for (int i = 0; i < n && !rc; i++) if (!conv[i]) { set_error("tmat_filter_edt_batch: thinning did not converge"); rc = TMAT_E_HIP; }
-    hipFree(dp); hipFree(dd); hipFree(df); hipFree(ws);
     return rc;
 }
 
@@ -622,18 +604,17 @@ int tmat_filter_mask_batch(tmat_handle hd, const uint8_t *mask, int n, int hh, i
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
     const size_t npx = (size_t)n * hh * ww;
-    uint8_t *dm = nullptr, *df = nullptr; void *ws = nullptr;
-    int rc = TMAT_OK;
     std::vector<int> conv(n, 0);
-    if (!hip_ok(hipMalloc((void **)&dm, npx), "hipMalloc") || !hip_ok(hipMalloc((void **)&df, npx), "hipMalloc") ||
-        !hip_ok(hipMalloc(&ws, morph_workspace_bytes(n, hh, ww)), "hipMalloc")) rc = TMAT_E_HIP;
+    DevScope mem(c->ws_pool, c->stream);
+    uint8_t *dm = mem.alloc<uint8_t>(npx), *df = mem.alloc<uint8_t>(npx);
+    void *ws = mem.alloc_bytes(morph_workspace_bytes(n, hh, ww));
+    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
     if (!rc && !hip_ok(hipMemcpyAsync(dm, mask, npx, hipMemcpyHostToDevice, c->stream), "H2D")) rc = TMAT_E_HIP;
     if (!rc && filter_mask_dev(nullptr, dm, n, hh, ww, use_median != 0, remove_isolated != 0, ws, df, nullptr, c->stream)) rc = TMAT_E_HIP;
     if (!rc && (!hip_ok(hipMemcpyAsync(filtered, df, npx, hipMemcpyDeviceToHost, c->stream), "D2H") ||
                 !hip_ok(hipMemcpyAsync(conv.data(), morph_done_flags(ws, n, hh, ww), n * sizeof(int), hipMemcpyDeviceToHost, c->stream), "D2H") ||
                 !hip_ok(hipStreamSynchronize(c->stream), "sync"))) rc = TMAT_E_HIP;
     for (int i = 0; i < n && !rc; i++) if (!conv[i]) { set_error("tmat_filter_mask_batch: thinning did not converge"); rc = TMAT_E_HIP; }
-    hipFree(dm); hipFree(df); hipFree(ws);
     return rc;
 }
 
@@ -648,11 +629,12 @@ int tmat_finish_batch(tmat_handle hd, const double *pred, const double *dist, co
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
     const size_t npx = (size_t)n * hh * ww, onpx = (size_t)n * out_h * out_w;
-    double *dp = nullptr, *dd = nullptr; uint8_t *ds = nullptr; void *ws = nullptr; float *df = nullptr, *d255 = nullptr;
-    int rc = TMAT_OK;
-    if (!hip_ok(hipMalloc((void **)&dp, npx * 8), "hipMalloc") || !hip_ok(hipMalloc((void **)&dd, npx * 8), "hipMalloc") ||
-        !hip_ok(hipMalloc((void **)&ds, npx), "hipMalloc") || !hip_ok(hipMalloc(&ws, finish_workspace_bytes(n, hh, ww, out_h, out_w)), "hipMalloc") ||
-        !hip_ok(hipMalloc((void **)&df, onpx * 4), "hipMalloc") || !hip_ok(hipMalloc((void **)&d255, onpx * 4), "hipMalloc")) rc = TMAT_E_HIP;
+    DevScope mem(c->ws_pool, c->stream);
+    double *dp = mem.alloc<double>(npx), *dd = mem.alloc<double>(npx);
+    uint8_t *ds = mem.alloc<uint8_t>(npx);
+    void *ws = mem.alloc_bytes(finish_workspace_bytes(n, hh, ww, out_h, out_w));
+    float *df = mem.alloc<float>(onpx), *d255 = mem.alloc<float>(onpx);
+    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
     if (!rc && (!hip_ok(hipMemcpyAsync(dp, pred, npx * 8, hipMemcpyHostToDevice, c->stream), "H2D") ||
                 !hip_ok(hipMemcpyAsync(dd, dist, npx * 8, hipMemcpyHostToDevice, c->stream), "H2D") ||
                 !hip_ok(hipMemcpyAsync(ds, skel, npx, hipMemcpyHostToDevice, c->stream), "H2D"))) rc = TMAT_E_HIP;
@@ -660,7 +642,6 @@ int tmat_finish_batch(tmat_handle hd, const double *pred, const double *dist, co
     if (!rc && (!hip_ok(hipMemcpyAsync(field, df, onpx * 4, hipMemcpyDeviceToHost, c->stream), "D2H") ||
                 !hip_ok(hipMemcpyAsync(field255, d255, onpx * 4, hipMemcpyDeviceToHost, c->stream), "D2H") ||
                 !hip_ok(hipStreamSynchronize(c->stream), "sync"))) rc = TMAT_E_HIP;
-    hipFree(dp); hipFree(dd); hipFree(ds); hipFree(ws); hipFree(df); hipFree(d255);
     return rc;
 }
 
@@ -691,8 +672,8 @@ int tmat_zproj_batch(tmat_handle hd, const uint16_t *stacks, int n, int Z, int H
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)1 << 30) / per_in));   // <= 1 GiB of stacks at a time
     uint16_t *din = nullptr; void *dout = nullptr;
     int rc = TMAT_OK;
-    // the staging buffers stay on the handle between calls (tmat_ctx.h:ws_get, slots 9 and 10)
-    din = (uint16_t *)ws_get(c, 9, (size_t)chunk * per_in); dout = ws_get(c, 10, (size_t)chunk * npx * osz);
+    // the staging buffers stay on the handle between calls (tmat_ctx.h:ws_get)
+    din = (uint16_t *)ws_get(c, WS_ZPROJ_IN, (size_t)chunk * per_in); dout = ws_get(c, WS_ZPROJ_OUT, (size_t)chunk * npx * osz);
     if (!din || !dout) rc = TMAT_E_HIP;
     for (int i0 = 0; i0 < n && !rc; i0 += chunk) {
         const int k = std::min(chunk, n - i0);
@@ -717,17 +698,16 @@ int tmat_postprocess_batch(tmat_handle hd, const double *pred, int n, int hh, in
     TMAT_HIP(hipSetDevice(c->device));
     const size_t per = (size_t)hh * ww, oper = (size_t)out_h * out_w;
     const int K = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)256 << 20) / (per * 8)));      // <= 256 MiB of f64 maps per chunk
-    double *dp = nullptr, *dd = nullptr; uint8_t *df = nullptr, *dsk = nullptr; void *ws = nullptr, *fws = nullptr; float *dfield = nullptr, *d255 = nullptr;
     std::vector<uint8_t> filt((size_t)K * per), skel((size_t)K * per);
     std::vector<double> dist((size_t)K * per);
     std::vector<int> conv(K, 0);
-    int rc = TMAT_OK;
-    if (!hip_ok(hipMalloc((void **)&dp, K * per * 8), "hipMalloc") || !hip_ok(hipMalloc((void **)&dd, K * per * 8), "hipMalloc") ||
-        !hip_ok(hipMalloc((void **)&df, K * per), "hipMalloc") || !hip_ok(hipMalloc((void **)&dsk, K * per), "hipMalloc") ||
-        !hip_ok(hipMalloc(&ws, morph_workspace_bytes(K, hh, ww)), "hipMalloc") ||
-        !hip_ok(hipMalloc(&fws, finish_workspace_bytes(K, hh, ww, out_h, out_w)), "hipMalloc") ||
-        !hip_ok(hipMalloc((void **)&dfield, K * oper * 4), "hipMalloc") || !hip_ok(hipMalloc((void **)&d255, K * oper * 4), "hipMalloc")) rc = TMAT_E_HIP;
     hipStream_t s = c->stream;
+    DevScope mem(c->ws_pool, s);
+    double *dp = mem.alloc<double>(K * per), *dd = mem.alloc<double>(K * per);
+    uint8_t *df = mem.alloc<uint8_t>(K * per), *dsk = mem.alloc<uint8_t>(K * per);
+    void *ws = mem.alloc_bytes(morph_workspace_bytes(K, hh, ww)), *fws = mem.alloc_bytes(finish_workspace_bytes(K, hh, ww, out_h, out_w));
+    float *dfield = mem.alloc<float>(K * oper), *d255 = mem.alloc<float>(K * oper);
+    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
     for (int i0 = 0; i0 < n && !rc; i0 += K) {
         const int k = std::min(K, n - i0);
         if (!hip_ok(hipMemcpyAsync(dp, pred + (size_t)i0 * per, k * per * 8, hipMemcpyHostToDevice, s), "H2D")) { rc = TMAT_E_HIP; break; }
@@ -749,7 +729,6 @@ int tmat_postprocess_batch(tmat_handle hd, const double *pred, int n, int hh, in
         if (!hip_ok(hipMemcpyAsync(field + (size_t)i0 * oper, dfield, k * oper * 4, hipMemcpyDeviceToHost, s), "D2H") ||
             !hip_ok(hipStreamSynchronize(s), "sync")) rc = TMAT_E_HIP;
     }
-    hipFree(dp); hipFree(dd); hipFree(df); hipFree(dsk); hipFree(ws); hipFree(fws); hipFree(dfield); hipFree(d255);
     return rc;
 }
 
@@ -761,18 +740,17 @@ int tmat_medial_axis_batch(tmat_handle hd, const uint8_t *mask, int n, int hh, i
     if (!thin_dev_supported(hh, ww)) { set_error("tmat_medial_axis_batch: image too large for the device thinning kernel (use tmat_host_medial_axis)"); return TMAT_E_ARG; }
     TMAT_HIP(hipSetDevice(c->device));
     const size_t npx = (size_t)n * hh * ww;
-    uint8_t *dm = nullptr, *dsk = nullptr; double *dd = nullptr; int *g = nullptr, *anyz = nullptr;
-    int rc = TMAT_OK;
     hipStream_t s = c->stream;
-    if (!hip_ok(hipMalloc((void **)&dm, npx), "hipMalloc") || !hip_ok(hipMalloc((void **)&dsk, npx), "hipMalloc") ||
-        !hip_ok(hipMalloc((void **)&dd, npx * 8), "hipMalloc") || !hip_ok(hipMalloc((void **)&g, npx * sizeof(int)), "hipMalloc") ||
-        !hip_ok(hipMalloc((void **)&anyz, n * sizeof(int)), "hipMalloc")) rc = TMAT_E_HIP;
+    DevScope mem(c->ws_pool, s);
+    uint8_t *dm = mem.alloc<uint8_t>(npx), *dsk = mem.alloc<uint8_t>(npx);
+    double *dd = mem.alloc<double>(npx);
+    int *g = mem.alloc<int>(npx), *anyz = mem.alloc<int>(n);
+    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
     if (!rc && !hip_ok(hipMemcpyAsync(dm, mask, npx, hipMemcpyHostToDevice, s), "H2D")) rc = TMAT_E_HIP;
     if (!rc) launch_edt(dm, n, hh, ww, g, nullptr, anyz, dd, s);
     if (!rc) rc = medial_thin_batch_dev(c, dm, dd, n, hh, ww, dsk, s);
     if (!rc && (!hip_ok(hipMemcpyAsync(skel, dsk, npx, hipMemcpyDeviceToHost, s), "D2H") ||
                 !hip_ok(hipMemcpyAsync(dist, dd, npx * 8, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))) rc = TMAT_E_HIP;
-    hipFree(dm); hipFree(dsk); hipFree(dd); hipFree(g); hipFree(anyz);
     return rc;
 }
 
@@ -817,14 +795,14 @@ int tmat_analyze_batch_tree(tmat_handle hd, const uint16_t *imgs, int n, int H, 
     if (!c || !imgs || !rows || n < 0 || H < 1 || W < 1) { set_error("tmat_analyze_batch_tree: bad argument"); return TMAT_E_ARG; }
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
-    uint16_t *dimg = nullptr;
-    TMAT_HIP(hipMalloc((void **)&dimg, (size_t)n * H * W * sizeof(uint16_t)));
+    DevScope mem(c->ws_pool);
+    uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
+    if (!mem.ok) return TMAT_E_HIP;
     int rc = TMAT_OK;
     if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) rc = TMAT_E_HIP;
     if (!rc) rc = tmat_analyze_batch_tree_dev(hd, dimg, n, H, W, ds_ratio, ds_width, graph_thresh_1, graph_thresh_2, smoothing_window_px,
                                               min_branch_length_px, max_branch_length_px, remove_isolated, first_index, rows, vis_width,
                                               rgb_out, bars_out, cap_b, n_bars);
-    hipFree(dimg);
     return rc;
 }
 
@@ -837,13 +815,13 @@ int tmat_analyze_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W
     if (!c || !imgs || !rows || n < 0) { set_error("tmat_analyze_batch: bad argument"); return TMAT_E_ARG; }
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
-    uint16_t *dimg = nullptr;
-    TMAT_HIP(hipMalloc((void **)&dimg, (size_t)n * H * W * sizeof(uint16_t)));
+    DevScope mem(c->ws_pool);
+    uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
+    if (!mem.ok) return TMAT_E_HIP;
     int rc = TMAT_OK;
     if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) rc = TMAT_E_HIP;
     if (!rc) rc = tmat_analyze_batch_dev(hd, dimg, n, H, W, ds_ratio, ds_width, graph_thresh_1, graph_thresh_2, smoothing_window_px,
                                          min_branch_length_px, max_branch_length_px, remove_isolated, first_index, rows);
-    hipFree(dimg);
     return rc;
 }
 

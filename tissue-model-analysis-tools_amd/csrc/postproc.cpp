@@ -12,11 +12,11 @@
 //   a16 anti-aliased bilinear resize (gaussian 'mirror' + zoom grid_mode)           -> resize_aa
 //   a17 rescale_intensity(out_range=(0,255)) in float32                             -> rescale255_f32
 //
-// Round-1 status: these stages run on the host (C++, one image per worker thread, overlapped with
-// the GPU segmenting the next batch); they are the only implementation of these stages (not a
-// fallback).  The thinning loops (Zhang sub-iterations to convergence, medial-axis ordered
-// thinning) and component labelling are the parts that do not map to one-pass kernels; moving the
-// one-pass stages (median, EDT, resize) into HIP is tracked in DESIGN.md.
+// These are the host twins of the device stages (preproc_kernels.hip, morph_kernels.hip, thin_kernels.hip,
+// finish_kernels.hip), which are what the batch pipeline runs: the tmat_host_* entry points expose them to the
+// stage-wise parity tests.  The product path still calls four of them: lanczos_axis, legacy_permutation and
+// medial_table_bits (tables for the device kernels) and medial_axis_thin (images too large for the LDS-resident thinning kernel, or
+// TMAT_THIN_DEVICE=0).
 // All arithmetic is ordered exactly as in oracle/morph.py (compiled with -ffp-contract=off).
 #include "../../include/tmat.h"
 #include "tmat_ctx.h"

@@ -367,15 +367,19 @@ int tmat_conv2d(tmat_handle hd, int prec, const float *x, int n, int hh, int ww,
     const std::vector<float> wk = k_contiguous(w, ksize * ksize, cin, cout);
     std::vector<uint16_t> wq;
     if (prec == 3) { wq.resize(nw); for (size_t i = 0; i < nw; i++) wq[i] = f16_rne_sat(wk[i]); }
-    float *dx = nullptr, *dsc = nullptr, *dsh = nullptr, *dr = nullptr, *dout = nullptr;
+    float *dx = nullptr, *dsc = nullptr, *dsh = nullptr, *dr = nullptr;
     void *dw = nullptr;
     int rc = TMAT_OK;
+    DevScope mem(c->ws_pool, s);          // the uploads read wk / wq
     auto put = [&](void **d, const void *src, size_t bytes) {
-        return hip_ok(hipMalloc(d, bytes), "hipMalloc(tmat_conv2d)") && hip_ok(hipMemcpyAsync(*d, src, bytes, hipMemcpyHostToDevice, s), "H2D");
+        *d = mem.alloc_bytes(bytes, "hipMalloc(tmat_conv2d)");
+        return *d && hip_ok(hipMemcpyAsync(*d, src, bytes, hipMemcpyHostToDevice, s), "H2D");
     };
     if (!put((void **)&dx, x, nx * 4) || !put(&dw, prec == 3 ? (const void *)wq.data() : (const void *)wk.data(), prec == 3 ? nw * 2 : nw * 4) ||
         !put((void **)&dsh, shift, (size_t)cout * 4) || (scale && !put((void **)&dsc, scale, (size_t)cout * 4)) ||
-        (resid && !put((void **)&dr, resid, no * 4)) || !hip_ok(hipMalloc((void **)&dout, no * 4), "hipMalloc(tmat_conv2d)")) rc = TMAT_E_HIP;
+        (resid && !put((void **)&dr, resid, no * 4))) rc = TMAT_E_HIP;
+    float *dout = mem.alloc<float>(no, "hipMalloc(tmat_conv2d)");
+    if (!mem.ok) rc = TMAT_E_HIP;
     if (!rc) {
         ConvArgs a{};
         a.in = dx; a.N = n; a.h = hh; a.w = ww; a.Cin = cin; a.relu_in = relu_in != 0; a.ksize = ksize; a.stride = stride; a.W = (const float *)dw;
@@ -384,7 +388,6 @@ int tmat_conv2d(tmat_handle hd, int prec, const float *x, int n, int hh, int ww,
         else if (!hip_ok(hipGetLastError(), "tmat_conv2d launch") || !hip_ok(hipMemcpyAsync(out, dout, no * 4, hipMemcpyDeviceToHost, s), "D2H")) rc = TMAT_E_HIP;
     }
     if (!hip_ok(hipStreamSynchronize(s), "sync") && !rc) rc = TMAT_E_HIP;      // also drains the uploads from wk / wq before they go out of scope
-    hipFree(dx); hipFree(dw); hipFree(dsc); hipFree(dsh); hipFree(dr); hipFree(dout);
     return rc;
 }
 
@@ -396,16 +399,13 @@ int tmat_resnet_predict(tmat_handle hd, int model_id, const float *x, int n, int
     TMAT_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t nx = (size_t)n * size * size * 3, nb = (size_t)n * (size / 2) * (size / 2) * 64;
-    float *dx = nullptr, *dp = nullptr, *col = nullptr, *bufs[4] = {nullptr, nullptr, nullptr, nullptr};
-    int rc = TMAT_OK;
-    if (!hip_ok(hipMalloc((void **)&dx, nx * 4), "hipMalloc") || !hip_ok(hipMalloc((void **)&dp, n * 4), "hipMalloc") ||
-        !hip_ok(hipMalloc((void **)&col, nb * 3 * 4), "hipMalloc")) rc = TMAT_E_HIP;      // 192 = 3 x 64 values per stem output pixel
-    for (int i = 0; i < 4 && !rc; i++) if (!hip_ok(hipMalloc((void **)&bufs[i], nb * 4), "hipMalloc")) rc = TMAT_E_HIP;
+    DevScope mem(c->ws_pool, s);
+    float *dx = mem.alloc<float>(nx), *dp = mem.alloc<float>(n), *col = mem.alloc<float>(nb * 3), *bufs[4];      // col: 192 = 3 x 64 values per stem output pixel
+    for (float *&b : bufs) b = mem.alloc<float>(nb);
+    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
     if (!rc && !hip_ok(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s), "H2D")) rc = TMAT_E_HIP;
     if (!rc) rc = resnet_forward_dev(c->resnets[model_id], c->resnet_precision, dx, n, size, bufs, col, dp, s);
     if (!rc && (!hip_ok(hipMemcpyAsync(prob, dp, n * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))) rc = TMAT_E_HIP;
-    hipFree(dx); hipFree(dp); hipFree(col);
-    for (float *b : bufs) hipFree(b);
     return rc;
 }
 
@@ -428,12 +428,12 @@ static int inv_depth_impl(tmat_handle hd, const int *model_ids, int n_models, co
     // cv2.resize(img, img_hw, cv2.INTER_LANCZOS4) (data_prep.py:36): the third positional parameter is `dst`: bilinear
     int rc = TMAT_OK;
     const int nb = std::min(Z, CH);
-    // workspaces live on the handle between calls (tmat_ctx.h:ws_get): slots 12..22 of this tool
-    din = (uint16_t *)ws_get(c, 12, (size_t)Z * H * W * 2); dsm = (uint16_t *)ws_get(c, 13, (size_t)Z * npx * 2);
-    itab = (int *)ws_get(c, 14, (size_t)size * 2 * 4 * 4); mnmx = (int *)ws_get(c, 15, (size_t)Z * 2 * 4);
-    dx = (float *)ws_get(c, 16, (size_t)Z * npx * 3 * 4); dp = (float *)ws_get(c, 17, (size_t)Z * n_models * 4);
-    for (int i = 0; i < 4; i++) bufs[i] = (float *)ws_get(c, 18 + i, (size_t)nb * (size / 2) * (size / 2) * 64 * 4);
-    col = (float *)ws_get(c, 22, (size_t)nb * (size / 2) * (size / 2) * STEM_K * 4);
+    // workspaces live on the handle between calls (tmat_ctx.h:ws_get)
+    din = (uint16_t *)ws_get(c, WS_INV_IN, (size_t)Z * H * W * 2); dsm = (uint16_t *)ws_get(c, WS_INV_SMALL, (size_t)Z * npx * 2);
+    itab = (int *)ws_get(c, WS_INV_TAB, (size_t)size * 2 * 4 * 4); mnmx = (int *)ws_get(c, WS_INV_MNMX, (size_t)Z * 2 * 4);
+    dx = (float *)ws_get(c, WS_INV_X, (size_t)Z * npx * 3 * 4); dp = (float *)ws_get(c, WS_INV_PROB, (size_t)Z * n_models * 4);
+    for (int i = 0; i < 4; i++) bufs[i] = (float *)ws_get(c, (ToolWs)(WS_INV_BUF0 + i), (size_t)nb * (size / 2) * (size / 2) * 64 * 4);
+    col = (float *)ws_get(c, WS_INV_COL, (size_t)nb * (size / 2) * (size / 2) * STEM_K * 4);
     if (!din || !dsm || !itab || !mnmx || !dx || !dp || !bufs[0] || !bufs[1] || !bufs[2] || !bufs[3] || !col) rc = TMAT_E_HIP;
     if (!rc) {
         // cv::resize takes INTER_AREA's integer mean for an exact halving on both axes (a 512 x 512 slice at the configured 256 x 256);

@@ -21,45 +21,6 @@ void zoom_axis_table(int n_in, int n_out, std::vector<int> &i0, std::vector<int>
 
 namespace {
 
-// device allocations of one call, released together -- back into the handle's pool (Ctx::ws_pool: blocks by size), from which the next call
-// takes them again: a Z-stack call makes some thirty allocations of a dozen sizes, and a hipMalloc / hipFree pair per block was a tenth of
-// its time.  The pool only ever holds what one call of each geometry needs; tmat_destroy frees it.
-struct Arena {
-    Ctx *c;
-    std::vector<std::pair<void *, size_t>> blocks;
-    std::vector<void *> ptrs;               // blocks that are not the pool's (morph / DMT workspaces allocated by the caller): freed
-    bool ok = true;
-    explicit Arena(Ctx *ctx) : c(ctx) {}
-    template <typename T> T *get(size_t count)
-    {
-        if (!ok) return nullptr;
-        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-        return (T *)get_bytes(bytes);
-    }
-    void *get_bytes(size_t bytes)
-    {
-        if (!ok) return nullptr;
-        auto it = c->ws_pool.lower_bound(bytes);
-        if (it != c->ws_pool.end() && it->first <= bytes + bytes / 4 + 4096) {          // close enough in size: reuse
-            void *p = it->second;
-            blocks.push_back({p, it->first});
-            c->ws_pool.erase(it);
-            return p;
-        }
-        void *p = nullptr;
-        if (!hip_ok(hipMalloc(&p, bytes), "hipMalloc")) { ok = false; return nullptr; }
-        blocks.push_back({p, bytes});
-        return p;
-    }
-    hipStream_t drain = nullptr;            // synchronised before anything is released: an early error return must not leave async work behind
-    ~Arena()
-    {
-        if (drain) hipStreamSynchronize(drain);
-        for (auto &b : blocks) c->ws_pool.insert({b.second, b.first});
-        for (void *p : ptrs) hipFree(p);
-    }
-};
-
 // device copy of a gaussian table, made on first use (synchronous copy: a few hundred doubles)
 const double *table_dev(Ctx *c, const GaussTable &t)
 {
@@ -137,22 +98,20 @@ int vessel_field_dev(Ctx *c, const float *vol, int Z, int h, int w, int form, fl
     if (!thin_dev_supported(h, w)) { set_error("vessel field: image too large for the device thinning kernel"); return TMAT_E_ARG; }
     const int D = Z - 1;
     const size_t npx = (size_t)h * w, nv = (size_t)D * npx;
-    Arena A(c);
-    A.drain = s;
-    float *x = A.get<float>(nv), *vess = A.get<float>(nv), *bufs[7];
-    for (float *&b : bufs) b = A.get<float>(nv);
-    float *vessels = A.get<float>(npx), *vcur = A.get<float>(npx), *vblur = A.get<float>(npx), *vtmp = A.get<float>(npx);
+    DevScope A(c->ws_pool, s);
+    float *x = A.pooled<float>(nv), *vess = A.pooled<float>(nv), *bufs[7];
+    for (float *&b : bufs) b = A.pooled<float>(nv);
+    float *vessels = A.pooled<float>(npx), *vcur = A.pooled<float>(npx), *vblur = A.pooled<float>(npx), *vtmp = A.pooled<float>(npx);
     CannyWs cw{};
-    cw.sm = A.get<double>(npx); cw.t0 = A.get<double>(npx); cw.is_ = A.get<double>(npx); cw.js = A.get<double>(npx); cw.mag = A.get<double>(npx);
-    cw.low = A.get<uint8_t>(npx); cw.high = A.get<uint8_t>(npx); cw.L = A.get<int>(npx); cw.flag = A.get<int>(npx);
-    double *tabs = A.get<double>(6);
-    uint8_t *edges = A.get<uint8_t>(npx), *skel = A.get<uint8_t>(npx), *m0 = A.get<uint8_t>(npx), *m1 = A.get<uint8_t>(npx), *filt = A.get<uint8_t>(npx);
-    double *dist = A.get<double>(npx);
-    int *edt_g = A.get<int>(npx), *anyz = A.get<int>(4);
-    unsigned long long *mom = A.get<unsigned long long>(npx * 6);
-    int *offs = A.get<int>(2 * (13 + 9));
-    void *mws = nullptr;
-    mws = A.get_bytes(morph_workspace_bytes(1, h, w));
+    cw.sm = A.pooled<double>(npx); cw.t0 = A.pooled<double>(npx); cw.is_ = A.pooled<double>(npx); cw.js = A.pooled<double>(npx); cw.mag = A.pooled<double>(npx);
+    cw.low = A.pooled<uint8_t>(npx); cw.high = A.pooled<uint8_t>(npx); cw.L = A.pooled<int>(npx); cw.flag = A.pooled<int>(npx);
+    double *tabs = A.pooled<double>(6);
+    uint8_t *edges = A.pooled<uint8_t>(npx), *skel = A.pooled<uint8_t>(npx), *m0 = A.pooled<uint8_t>(npx), *m1 = A.pooled<uint8_t>(npx), *filt = A.pooled<uint8_t>(npx);
+    double *dist = A.pooled<double>(npx);
+    int *edt_g = A.pooled<int>(npx), *anyz = A.pooled<int>(4);
+    unsigned long long *mom = A.pooled<unsigned long long>(npx * 6);
+    int *offs = A.pooled<int>(2 * (13 + 9));
+    void *mws = A.pooled_bytes(morph_workspace_bytes(1, h, w));
     if (!A.ok) return TMAT_E_HIP;
     {
         const double t[6] = {-1.0, 0.0, 1.0, 1.0, 2.0, 1.0};
@@ -223,16 +182,15 @@ int vessel_field_dev(Ctx *c, const float *vol, int Z, int h, int w, int form, fl
 int stack_resize_aa_dev(Ctx *c, const uint16_t *stack, int Z, int H, int W, int oh, int ow, double *zoomed, float *vol, hipStream_t s)
 {
     const size_t nin = (size_t)Z * H * W;
-    Arena A(c);
-    A.drain = s;
-    double *fa = A.get<double>(nin), *fb = A.get<double>(nin), *lohi = A.get<double>(4);
-    unsigned long long *mm = A.get<unsigned long long>(2);
+    DevScope A(c->ws_pool, s);
+    double *fa = A.pooled<double>(nin), *fb = A.pooled<double>(nin), *lohi = A.pooled<double>(4);
+    unsigned long long *mm = A.pooled<unsigned long long>(2);
     std::vector<int> r0, r1, c0, c1;
     std::vector<double> wr0, wr1, wc0, wc1;
     zoom_axis_table(H, oh, r0, r1, wr0, wr1);
     zoom_axis_table(W, ow, c0, c1, wc0, wc1);
-    int *dr0 = A.get<int>(oh), *dr1 = A.get<int>(oh), *dc0 = A.get<int>(ow), *dc1 = A.get<int>(ow);
-    double *dwr0 = A.get<double>(oh), *dwr1 = A.get<double>(oh), *dwc0 = A.get<double>(ow), *dwc1 = A.get<double>(ow);
+    int *dr0 = A.pooled<int>(oh), *dr1 = A.pooled<int>(oh), *dc0 = A.pooled<int>(ow), *dc1 = A.pooled<int>(ow);
+    double *dwr0 = A.pooled<double>(oh), *dwr1 = A.pooled<double>(oh), *dwc0 = A.pooled<double>(ow), *dwc1 = A.pooled<double>(ow);
     if (!A.ok) return TMAT_E_HIP;
     TMAT_HIP(hipMemcpyAsync(dr0, r0.data(), oh * 4, hipMemcpyHostToDevice, s)); TMAT_HIP(hipMemcpyAsync(dr1, r1.data(), oh * 4, hipMemcpyHostToDevice, s));
     TMAT_HIP(hipMemcpyAsync(dc0, c0.data(), ow * 4, hipMemcpyHostToDevice, s)); TMAT_HIP(hipMemcpyAsync(dc1, c1.data(), ow * 4, hipMemcpyHostToDevice, s));
@@ -276,9 +234,8 @@ int stack_resize_aa_dev(Ctx *c, const uint16_t *stack, int Z, int H, int W, int 
 int stack_prepare_dev(Ctx *c, uint16_t *stack, int Z, int H, int W, int oh, int ow, float *vol, hipStream_t s)
 {
     const size_t nin = (size_t)Z * H * W, nout = (size_t)Z * oh * ow;
-    Arena A(c);
-    A.drain = s;
-    double *fa = A.get<double>(nin), *zoomed = A.get<double>(nout);
+    DevScope A(c->ws_pool, s);
+    double *fa = A.pooled<double>(nin), *zoomed = A.pooled<double>(nout);
     if (!A.ok) return TMAT_E_HIP;
     // z1: gaussian(slice, sigma 1, 'nearest') in f64, written back into the integer stack (C truncation)
     const GaussTable &g1 = gauss_table(c, 1.0, 0, gauss_radius(1.0, 4.0));
@@ -303,9 +260,8 @@ int tmat_gaussian_f32(tmat_handle hd, const float *x, int d0, int d1, int d2, do
     TMAT_HIP(hipSetDevice(c->device));
     const size_t n = (size_t)d0 * d1 * d2;
     hipStream_t s = c->stream;
-    Arena A(c);
-    A.drain = s;
-    float *a = A.get<float>(n), *b = A.get<float>(n);
+    DevScope A(c->ws_pool, s);
+    float *a = A.pooled<float>(n), *b = A.pooled<float>(n);
     if (!A.ok) return TMAT_E_HIP;
     TMAT_HIP(hipMemcpyAsync(a, x, n * 4, hipMemcpyHostToDevice, s));
     // ndi.gaussian_filter: every axis in order (the caller folds leading axes of length 1 away by passing d0 = 1 -> two passes)
@@ -328,13 +284,12 @@ static int well_threshold(tmat_handle hd, const void *img, int is_f64, int H, in
     TMAT_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t n = (size_t)H * W;
-    Arena A(c);
-    A.drain = s;
-    float *a = A.get<float>(is_f64 ? 1 : n), *b = A.get<float>(is_f64 ? 1 : n), *mm = A.get<float>(2);
-    double *da = A.get<double>(is_f64 ? n : 1), *db = A.get<double>(is_f64 ? n : 1), *dmm = A.get<double>(2);
-    uint8_t *u8 = A.get<uint8_t>(n), *th = A.get<uint8_t>(n), *er = A.get<uint8_t>(n);
-    unsigned *hist = A.get<unsigned>(5 * 256);
-    int *decision = A.get<int>(2), *offs = A.get<int>(2 * 81);
+    DevScope A(c->ws_pool, s);
+    float *a = A.pooled<float>(is_f64 ? 1 : n), *b = A.pooled<float>(is_f64 ? 1 : n), *mm = A.pooled<float>(2);
+    double *da = A.pooled<double>(is_f64 ? n : 1), *db = A.pooled<double>(is_f64 ? n : 1), *dmm = A.pooled<double>(2);
+    uint8_t *u8 = A.pooled<uint8_t>(n), *th = A.pooled<uint8_t>(n), *er = A.pooled<uint8_t>(n);
+    unsigned *hist = A.pooled<unsigned>(5 * 256);
+    int *decision = A.pooled<int>(2), *offs = A.pooled<int>(2 * 81);
     if (!A.ok) return TMAT_E_HIP;
     int o[2 * 81], k = 0;
     for (int dy = -5; dy <= 5; dy++) for (int dx = -5; dx <= 5; dx++) if (dy * dy + dx * dx <= 25) { o[2 * k] = dy; o[2 * k + 1] = dx; k++; }     // disk(5): 81
@@ -379,14 +334,13 @@ int tmat_canny_mask(tmat_handle hd, const uint8_t *mask, int H, int W, double si
     const int r = gauss_radius(sigma, 4.0);
     const int Hp = H + 2 * r, Wp = W + 2 * r;
     const size_t npx = (size_t)H * W, npad = (size_t)Hp * Wp;
-    Arena A(c);
-    A.drain = s;
-    uint8_t *m = A.get<uint8_t>(npx), *e = A.get<uint8_t>(npx);
-    double *pa = A.get<double>(npad), *pb = A.get<double>(npad), *pt = A.get<double>(npad);
+    DevScope A(c->ws_pool, s);
+    uint8_t *m = A.pooled<uint8_t>(npx), *e = A.pooled<uint8_t>(npx);
+    double *pa = A.pooled<double>(npad), *pb = A.pooled<double>(npad), *pt = A.pooled<double>(npad);
     CannyWs cw{};
-    cw.sm = A.get<double>(npx); cw.t0 = A.get<double>(npx); cw.is_ = A.get<double>(npx); cw.js = A.get<double>(npx); cw.mag = A.get<double>(npx);
-    cw.low = A.get<uint8_t>(npx); cw.high = A.get<uint8_t>(npx); cw.L = A.get<int>(npx); cw.flag = A.get<int>(npx);
-    double *tabs = A.get<double>(6);
+    cw.sm = A.pooled<double>(npx); cw.t0 = A.pooled<double>(npx); cw.is_ = A.pooled<double>(npx); cw.js = A.pooled<double>(npx); cw.mag = A.pooled<double>(npx);
+    cw.low = A.pooled<uint8_t>(npx); cw.high = A.pooled<uint8_t>(npx); cw.L = A.pooled<int>(npx); cw.flag = A.pooled<int>(npx);
+    double *tabs = A.pooled<double>(6);
     if (!A.ok) return TMAT_E_HIP;
     const double t[6] = {-1.0, 0.0, 1.0, 1.0, 2.0, 1.0};
     TMAT_HIP(hipMemcpyAsync(tabs, t, sizeof(t), hipMemcpyHostToDevice, s));
@@ -419,10 +373,9 @@ int tmat_sato_batch(tmat_handle hd, const float *imgs, int n, int hh, int ww, co
     TMAT_HIP(hipSetDevice(c->device));
     const size_t total = (size_t)n * hh * ww;
     hipStream_t s = c->stream;
-    Arena A(c);
-    A.drain = s;
-    float *raw = A.get<float>(total), *x = A.get<float>(total), *best = A.get<float>(total), *bufs[7];
-    for (float *&b : bufs) b = A.get<float>(total);
+    DevScope A(c->ws_pool, s);
+    float *raw = A.pooled<float>(total), *x = A.pooled<float>(total), *best = A.pooled<float>(total), *bufs[7];
+    for (float *&b : bufs) b = A.pooled<float>(total);
     if (!A.ok) return TMAT_E_HIP;
     TMAT_HIP(hipMemcpyAsync(raw, imgs, total * 4, hipMemcpyHostToDevice, s));
     launch_prep_single(raw, total, hessian == TMAT_SATO_GAUSSIAN_DERIVATIVES, x, s);
@@ -438,10 +391,9 @@ int tmat_stack_prepare(tmat_handle hd, const uint16_t *stack, int Z, int H, int 
     if (!c || !stack || !vol || Z < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) { set_error("tmat_stack_prepare: bad argument"); return TMAT_E_ARG; }
     TMAT_HIP(hipSetDevice(c->device));
     const size_t nin = (size_t)Z * H * W, nout = (size_t)Z * out_h * out_w;
-    Arena A(c);
-    A.drain = c->stream;
-    uint16_t *ds = A.get<uint16_t>(nin);
-    float *dv = A.get<float>(nout);
+    DevScope A(c->ws_pool, c->stream);
+    uint16_t *ds = A.pooled<uint16_t>(nin);
+    float *dv = A.pooled<float>(nout);
     if (!A.ok) return TMAT_E_HIP;
     TMAT_HIP(hipMemcpyAsync(ds, stack, nin * 2, hipMemcpyHostToDevice, c->stream));
     int rc = stack_prepare_dev(c, ds, Z, H, W, out_h, out_w, dv, c->stream);
@@ -460,9 +412,8 @@ int tmat_vessel_field(tmat_handle hd, const float *vol, int Z, int hh, int ww, i
     }
     TMAT_HIP(hipSetDevice(c->device));
     const size_t nvol = (size_t)Z * hh * ww, npx = (size_t)hh * ww;
-    Arena A(c);
-    A.drain = c->stream;
-    float *dv = A.get<float>(nvol), *df = A.get<float>(npx);
+    DevScope A(c->ws_pool, c->stream);
+    float *dv = A.pooled<float>(nvol), *df = A.pooled<float>(npx);
     if (!A.ok) return TMAT_E_HIP;
     TMAT_HIP(hipMemcpyAsync(dv, vol, nvol * 4, hipMemcpyHostToDevice, c->stream));
     int rc = vessel_field_dev(c, dv, Z, hh, ww, hessian, df, stages, c->stream);
@@ -477,13 +428,11 @@ static int field_stats_dev(Ctx *c, const float *field, int fh, int fw, float t1,
                            const uint8_t *pruning_mask, int64_t index, tmat_row *row, hipStream_t s)
 {
     const size_t npx = (size_t)fh * fw, nE = dmt_edge_count(fh, fw);
-    Arena A(c);
-    A.drain = s;
-    float *f255 = A.get<float>(npx), *mnmx = A.get<float>(2);
-    int32_t *ids = A.get<int32_t>(nE);
-    int *m = A.get<int>(1);
-    void *dws = nullptr;
-    dws = A.get_bytes(dmt_workspace_bytes(1, fh, fw));
+    DevScope A(c->ws_pool, s);
+    float *f255 = A.pooled<float>(npx), *mnmx = A.pooled<float>(2);
+    int32_t *ids = A.pooled<int32_t>(nE);
+    int *m = A.pooled<int>(1);
+    void *dws = A.pooled_bytes(dmt_workspace_bytes(1, fh, fw));
     if (!A.ok) return TMAT_E_HIP;
     launch_rescale255(field, 1, (int)npx, mnmx, mnmx + 1, f255, s);
     std::vector<float> f255_host(npx);
@@ -494,10 +443,9 @@ static int field_stats_dev(Ctx *c, const float *field, int fh, int fw, float t1,
     std::vector<uint8_t> kind_host;
     std::vector<float> pers_host;
     if (c->dmt_sweep_device) {
-        uint8_t *dkind = A.get<uint8_t>(nE);
-        float *dpers = A.get<float>(nE);
-        void *sws = nullptr;
-        sws = A.get_bytes(dmt_sweep_workspace_bytes(1, fh, fw));
+        uint8_t *dkind = A.pooled<uint8_t>(nE);
+        float *dpers = A.pooled<float>(nE);
+        void *sws = A.pooled_bytes(dmt_sweep_workspace_bytes(1, fh, fw));
         if (!A.ok) return TMAT_E_HIP;
         if (dmt_sweeps_dev(f255, ids, m, 1, fh, fw, sws, dkind, dpers, s)) { set_error("field stats: device sweeps failed"); return TMAT_E_HIP; }
         kind_host.resize(nE); pers_host.resize(nE);
@@ -527,9 +475,8 @@ int tmat_field_stats_pruned(tmat_handle hd, const float *field, int fh, int fw, 
     Ctx *c = (Ctx *)hd;
     if (!c || !field || !row || fh < 2 || fw < 2) { set_error("tmat_field_stats: bad argument"); return TMAT_E_ARG; }
     TMAT_HIP(hipSetDevice(c->device));
-    Arena A(c);
-    A.drain = c->stream;
-    float *df = A.get<float>((size_t)fh * fw);
+    DevScope A(c->ws_pool, c->stream);
+    float *df = A.pooled<float>((size_t)fh * fw);
     if (!A.ok) return TMAT_E_HIP;
     TMAT_HIP(hipMemcpyAsync(df, field, (size_t)fh * fw * 4, hipMemcpyHostToDevice, c->stream));
     return field_stats_dev(c, df, fh, fw, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated,
@@ -549,10 +496,9 @@ int tmat_resize_aa_u16(tmat_handle hd, const uint16_t *imgs, int n, int H, int W
     if (!c || !imgs || !out || n < 1 || H < 1 || W < 1 || out_h < 1 || out_w < 1) { set_error("tmat_resize_aa_u16: bad argument"); return TMAT_E_ARG; }
     TMAT_HIP(hipSetDevice(c->device));
     const size_t nin = (size_t)n * H * W, nout = (size_t)n * out_h * out_w;
-    Arena A(c);
-    A.drain = c->stream;
-    uint16_t *ds = A.get<uint16_t>(nin);
-    double *dz = A.get<double>(nout);
+    DevScope A(c->ws_pool, c->stream);
+    uint16_t *ds = A.pooled<uint16_t>(nin);
+    double *dz = A.pooled<double>(nout);
     if (!A.ok) return TMAT_E_HIP;
     TMAT_HIP(hipMemcpyAsync(ds, imgs, nin * 2, hipMemcpyHostToDevice, c->stream));
     int rc = stack_resize_aa_dev(c, ds, n, H, W, out_h, out_w, dz, nullptr, c->stream);
@@ -577,10 +523,9 @@ int tmat_analyze_stack(tmat_handle hd, const uint16_t *stack, int Z, int H, int 
     if (fh < 2 || fw < 2) { set_error("tmat_analyze_stack: downsampled shape is empty"); return TMAT_E_ARG; }
     const size_t nin = (size_t)Z * H * W, npx = (size_t)fh * fw;
     hipStream_t s = c->stream;
-    Arena A(c);
-    A.drain = s;
-    uint16_t *ds = A.get<uint16_t>(nin);
-    float *vol = A.get<float>((size_t)Z * npx), *field = A.get<float>(npx);
+    DevScope A(c->ws_pool, s);
+    uint16_t *ds = A.pooled<uint16_t>(nin);
+    float *vol = A.pooled<float>((size_t)Z * npx), *field = A.pooled<float>(npx);
     if (!A.ok) return TMAT_E_HIP;
     TMAT_HIP(hipMemcpyAsync(ds, stack, nin * 2, hipMemcpyHostToDevice, s));
     int rc = stack_prepare_dev(c, ds, Z, H, W, fh, fw, vol, s);

@@ -500,14 +500,13 @@ int ensure_patch_io(Ctx *c, int n_patches)
     if (n_patches <= c->patch_cap) return TMAT_OK;
     TMAT_HIP(hipStreamSynchronize(c->stream));
     TMAT_HIP(hipStreamSynchronize(c->stream2));
-    if (c->patch_in) hipFree(c->patch_in);
-    if (c->patch_in2) hipFree(c->patch_in2);
-    if (c->patch_out) hipFree(c->patch_out);
+    for (float *p : {c->patch_in, c->patch_in2, c->patch_out}) c->ws.release(p);
     c->patch_in = c->patch_in2 = c->patch_out = nullptr;
     c->patch_cap = 0;
     const size_t bytes = (size_t)c->patch * c->patch * n_patches * sizeof(float);
-    TMAT_HIP(hipMalloc((void **)&c->patch_in, bytes));
-    TMAT_HIP(hipMalloc((void **)&c->patch_out, bytes));
+    c->patch_in = (float *)c->ws.dev(bytes, "hipMalloc(patch_in)");
+    c->patch_out = (float *)c->ws.dev(bytes, "hipMalloc(patch_out)");
+    if (!c->patch_in || !c->patch_out) return TMAT_E_HIP;
     c->patch_cap = n_patches;
     return TMAT_OK;
 }
@@ -618,26 +617,17 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     // activation workspace: per patch (P/2)^2 * f0 floats for buf0/buf1 and twice that for buf2/buf3
     const size_t unit = (size_t)(patch / 2) * (patch / 2) * c->f0;
     const size_t sizes[4] = {unit, unit, 2 * unit, 2 * unit};
-    for (int i = 0; i < 4; i++) {
-        c->buf_bytes[i] = sizes[i] * c->max_patches * sizeof(float);
-        if (!hip_ok(hipMalloc((void **)&c->buf[i], c->buf_bytes[i]), "hipMalloc(activations)")) {
-            tmat_destroy((tmat_handle)c); return TMAT_E_HIP;
-        }
-    }
+    auto dev_f32 = [c](size_t bytes, const char *what) { return (float *)c->ws.dev(bytes, what); };
+    for (int i = 0; i < 4; i++)
+        if (!(c->buf[i] = dev_f32(sizes[i] * c->max_patches * sizeof(float), "hipMalloc(activations)"))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
     // up-path buffers: t1 (unit), hoisted residual (unit/4), block outputs alternate (unit/2, unit); down-path output x2
     const size_t usizes[4] = {unit, unit / 4, unit / 2, unit};
-    for (int i = 0; i < 4; i++) {
-        c->ubuf_bytes[i] = usizes[i] * c->max_patches * sizeof(float);
-        if (!hip_ok(hipMalloc((void **)&c->ubuf[i], c->ubuf_bytes[i]), "hipMalloc(up buffers)")) {
-            tmat_destroy((tmat_handle)c); return TMAT_E_HIP;
-        }
-    }
+    for (int i = 0; i < 4; i++)
+        if (!(c->ubuf[i] = dev_f32(usizes[i] * c->max_patches * sizeof(float), "hipMalloc(up buffers)"))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
     const size_t dsz = (size_t)(patch >> (1 + c->down.size())) * (patch >> (1 + c->down.size())) * c->up[0].cin;
-    c->dout_bytes = dsz * c->max_patches * sizeof(float);
+    const size_t dout_bytes = dsz * c->max_patches * sizeof(float);
     for (int i = 0; i < 2; i++)
-        if (!hip_ok(hipMalloc((void **)&c->dout[i], c->dout_bytes), "hipMalloc(dout)")) {
-            tmat_destroy((tmat_handle)c); return TMAT_E_HIP;
-        }
+        if (!(c->dout[i] = dev_f32(dout_bytes, "hipMalloc(dout)"))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
     if (const char *e = getenv("TMAT_RELU_COPY")) c->relu_copy = atoi(e) != 0;
     if (c->relu_copy) {
         // up block j's output has (P/16 << j)^2 x cout_j values per patch: the larger of the even / odd blocks sizes each buffer
@@ -646,11 +636,9 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
             const size_t side = (size_t)(patch >> (1 + c->down.size())) << j;
             need[j & 1] = std::max(need[j & 1], side * side * c->up[j].cout);
         }
-        for (int i = 0; i < 2; i++) {
-            c->urelu_bytes[i] = need[i] * c->max_patches * sizeof(float);
-            if (!hip_ok(hipMalloc((void **)&c->dout_relu[i], c->dout_bytes), "hipMalloc(dout_relu)") ||
-                (need[i] && !hip_ok(hipMalloc((void **)&c->urelu[i], c->urelu_bytes[i]), "hipMalloc(urelu)"))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
-        }
+        for (int i = 0; i < 2; i++)
+            if (!(c->dout_relu[i] = dev_f32(dout_bytes, "hipMalloc(dout_relu)")) ||
+                (need[i] && !(c->urelu[i] = dev_f32(need[i] * c->max_patches * sizeof(float), "hipMalloc(urelu)")))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
     }
     if (!hip_ok(hipStreamCreate(&c->stream2), "hipStreamCreate(2)") || !hip_ok(hipStreamCreateWithPriority(&c->stream3, hipStreamDefault, prio_least), "hipStreamCreate(3)")) {
         tmat_destroy((tmat_handle)c); return TMAT_E_HIP;
@@ -662,9 +650,8 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
             !hip_ok(hipEventCreateWithFlags(&c->ev_blend[i], hipEventDisableTiming), "hipEventCreate")) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
     const size_t pp = (size_t)patch * patch * c->max_patches * sizeof(float);
     c->scratch_bytes = 64 << 20;
-    if (!hip_ok(hipMalloc((void **)&c->patch_in, pp), "hipMalloc(patch_in)") ||
-        !hip_ok(hipMalloc((void **)&c->patch_out, pp), "hipMalloc(patch_out)") ||
-        !hip_ok(hipMalloc((void **)&c->scratch, c->scratch_bytes), "hipMalloc(scratch)")) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
+    if (!(c->patch_in = dev_f32(pp, "hipMalloc(patch_in)")) || !(c->patch_out = dev_f32(pp, "hipMalloc(patch_out)")) ||
+        !(c->scratch = c->ws.dev(c->scratch_bytes, "hipMalloc(scratch)"))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
     c->patch_cap = c->max_patches;
     // squared-spline window (smooth_tiled_predictions.py:26-41), f64, on host then uploaded
     {
@@ -708,17 +695,11 @@ void tmat_destroy(tmat_handle h)
     if (c->stream) hipStreamSynchronize(c->stream);
     for (void *p : c->owned) hipFree(p);
     if (c->stream2) hipStreamSynchronize(c->stream2);
-    for (int i = 0; i < 4; i++) if (c->buf[i]) hipFree(c->buf[i]);
-    for (int i = 0; i < 4; i++) if (c->ubuf[i]) hipFree(c->ubuf[i]);
-    for (int i = 0; i < 2; i++) { if (c->dout_relu[i]) hipFree(c->dout_relu[i]); if (c->urelu[i]) hipFree(c->urelu[i]); }
-    for (int i = 0; i < 2; i++) { if (c->dout[i]) hipFree(c->dout[i]); if (c->ev_down[i]) hipEventDestroy(c->ev_down[i]); if (c->ev_up[i]) hipEventDestroy(c->ev_up[i]); if (c->ev_pre[i]) hipEventDestroy(c->ev_pre[i]); if (c->ev_blend[i]) hipEventDestroy(c->ev_blend[i]); }
+    for (int i = 0; i < 2; i++) { if (c->ev_down[i]) hipEventDestroy(c->ev_down[i]); if (c->ev_up[i]) hipEventDestroy(c->ev_up[i]); if (c->ev_pre[i]) hipEventDestroy(c->ev_pre[i]); if (c->ev_blend[i]) hipEventDestroy(c->ev_blend[i]); }
     if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->stream3) { hipStreamSynchronize(c->stream3); hipStreamDestroy(c->stream3); }
-    if (c->patch_in) hipFree(c->patch_in);
-    if (c->patch_in2) hipFree(c->patch_in2);
-    if (c->patch_out) hipFree(c->patch_out);
+    c->ws.free_all();
     for (RoiEntry *e : c->roi_cache) { if (e->order) hipFree(e->order); delete e; }
-    if (c->scratch) hipFree(c->scratch);
     if (c->win1d) hipFree(c->win1d);
     if (c->ma_table) hipFree(c->ma_table);
     for (void *p : c->tool_ws) if (p) hipFree(p);
@@ -768,15 +749,15 @@ int tmat_predict_smooth(tmat_handle h, const float *x, int n, int hh, int ww, do
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
     const size_t per = (size_t)hh * ww;
-    float *xd = nullptr; double *pd = nullptr;
-    TMAT_HIP(hipMalloc((void **)&xd, n * per * sizeof(float)));
-    if (!hip_ok(hipMalloc((void **)&pd, n * per * sizeof(double)), "hipMalloc(pred)")) { hipFree(xd); return TMAT_E_HIP; }
+    DevScope mem(c->ws_pool, c->stream);
+    float *xd = mem.alloc<float>(n * per);
+    double *pd = mem.alloc<double>(n * per, "hipMalloc(pred)");
+    if (!mem.ok) return TMAT_E_HIP;
     int rc = TMAT_OK;
     if (!hip_ok(hipMemcpyAsync(xd, x, n * per * sizeof(float), hipMemcpyHostToDevice, c->stream), "H2D")) rc = TMAT_E_HIP;
     if (!rc) rc = predict_smooth_dev(c, xd, n, hh, ww, pd);
     if (!rc && !hip_ok(hipMemcpyAsync(pred, pd, n * per * sizeof(double), hipMemcpyDeviceToHost, c->stream), "D2H")) rc = TMAT_E_HIP;
     if (!hip_ok(hipStreamSynchronize(c->stream), "sync") && !rc) rc = TMAT_E_HIP;
-    hipFree(xd); hipFree(pd);
     return rc;
 }
 
@@ -851,6 +832,16 @@ int tmat_set_precision(tmat_handle h, int mode)
     return TMAT_OK;
 }
 
+// every workspace the handle retains between calls: the handle-lifetime list, the per-pass buffers, the side tools' slots and the pool
+static std::vector<WsEnt> held_blocks(const Ctx *c)
+{
+    std::vector<WsEnt> all(c->ws.begin(), c->ws.end());
+    all.insert(all.end(), c->pass.ws.begin(), c->pass.ws.end());
+    for (int i = 0; i < N_TOOL_WS; i++) if (c->tool_ws[i]) all.push_back({c->tool_ws[i], c->tool_ws_bytes[i], false});
+    for (auto &b : c->ws_pool) all.push_back({b.second, b.first, false});
+    return all;
+}
+
 // Test-only (tests/test_gpu_poison.py): fill every scratch workspace of the handle -- the activation ping-pong sets, the pooled-tile
 // strips that live in them, patch_in / patch_out, the scratch block and every per-pass device / pinned buffer -- with `byte_pattern`
 // (0xFF: NaN as f32 / f64, -1 as int).  Weights, the spline window and the Lanczos tables are constants and stay.  A forward or a pass
@@ -862,23 +853,22 @@ int tmat_debug_poison(tmat_handle h, int byte_pattern)
     if (!c) { set_error("null handle"); return TMAT_E_ARG; }
     TMAT_HIP(hipSetDevice(c->device));
     { const int rc = tmat_sync(h); if (rc) return rc; }
-    std::vector<WsEnt> all;
-    for (int i = 0; i < 4; i++) { if (c->buf[i]) all.push_back({c->buf[i], c->buf_bytes[i], false}); if (c->ubuf[i]) all.push_back({c->ubuf[i], c->ubuf_bytes[i], false}); }
-    for (int i = 0; i < 2; i++) if (c->dout[i]) all.push_back({c->dout[i], c->dout_bytes, false});
-    for (int i = 0; i < 2; i++) { if (c->dout_relu[i]) all.push_back({c->dout_relu[i], c->dout_bytes, false}); if (c->urelu[i]) all.push_back({c->urelu[i], c->urelu_bytes[i], false}); }
-    const size_t pio = (size_t)c->patch * c->patch * c->patch_cap * sizeof(float);
-    if (c->patch_in) all.push_back({c->patch_in, pio, false});
-    if (c->patch_in2) all.push_back({c->patch_in2, pio, false});
-    if (c->patch_out) all.push_back({c->patch_out, pio, false});
-    if (c->scratch) all.push_back({c->scratch, c->scratch_bytes, false});
-    for (int i = 0; i < Ctx::N_TOOL_WS; i++) if (c->tool_ws[i]) all.push_back({c->tool_ws[i], c->tool_ws_bytes[i], false});
-    for (auto &b : c->ws_pool) all.push_back({b.second, b.first, false});
-    all.insert(all.end(), c->pass.ws.begin(), c->pass.ws.end());
+    std::vector<WsEnt> all = held_blocks(c);
     for (const WsEnt &e : all) {
         if (e.host) memset(e.p, byte_pattern, e.bytes);
         else TMAT_HIP(hipMemsetAsync(e.p, byte_pattern, e.bytes, c->stream));
     }
     TMAT_HIP(hipStreamSynchronize(c->stream));
+    return TMAT_OK;
+}
+
+// Test-only (tests/test_gpu_held_memory.py): bytes of the workspaces tmat_debug_poison fills, device and pinned
+int tmat_debug_held_bytes(tmat_handle h, size_t *device_bytes, size_t *pinned_bytes)
+{
+    Ctx *c = (Ctx *)h;
+    if (!c || !device_bytes || !pinned_bytes) { set_error("tmat_debug_held_bytes: bad argument"); return TMAT_E_ARG; }
+    *device_bytes = *pinned_bytes = 0;
+    for (const WsEnt &e : held_blocks(c)) *(e.host ? pinned_bytes : device_bytes) += e.bytes;
     return TMAT_OK;
 }
 

@@ -1,6 +1,7 @@
 // Handle state of libtmat_hip.so.
 #pragma once
 #include "tmat_internal.h"
+#include "dev_mem.h"
 #include "gauss_tables.h"
 #include "roi_plan.h"
 
@@ -24,8 +25,6 @@ struct UpBlock {
 };
 struct ProfEv { hipEvent_t e0, e1; double flops; };
 struct RoiEntry { RoiPlan plan; int4 *order = nullptr; };       // order: device, [tiles_per_img] (TileGeom::order)
-// a device / pinned workspace a forward or a pass writes before it reads (tmat_debug_poison fills exactly these)
-struct WsEnt { void *p; size_t bytes; bool host; };
 struct ConvWHost { std::vector<float> w; int cin; };        // host copy of an MFMA convolution's weights ([rows][cin])
 
 // per-geometry buffers of the batch pipeline (pipeline.cpp)
@@ -71,7 +70,7 @@ struct PassBuf {
     float *dmt_pers[2] = {nullptr, nullptr};
     float *dmt_pers_host[2] = {nullptr, nullptr};
     hipEvent_t done[2] = {nullptr, nullptr};
-    std::vector<WsEnt> ws;                                  // every scratch allocation above with its size (not the Lanczos tables: they are constants)
+    WsList ws;                                              // owns every scratch allocation above (not the Lanczos tables: they are constants)
 };
 
 // weight container ("TMATW001", tmat_amd/synth.py:pack_weights): tensors by name, pointing into the caller's blob
@@ -102,6 +101,18 @@ struct GaussKey {
     bool operator<(const GaussKey &o) const { return sigma != o.sigma ? sigma < o.sigma : order != o.order ? order < o.order : radius < o.radius; }
 };
 
+// slots of ws_get: one per buffer of a side tool.  The overlay and tree slots are shared by tmat_render_tree (overlay.cpp) and the
+// "with tree" form of tmat_analyze_batch_tree* (pipeline.cpp): both hold them for one call only, synchronise before they return, and
+// a handle runs one entry point at a time, so the two are never live together.
+enum ToolWs {
+    WS_CELL_IN, WS_CELL_HIST, WS_CELL_KEPT, WS_CELL_PAR, WS_CELL_THR, WS_CELL_SMALL, WS_CELL_TAB, WS_CELL_MASK, WS_CELL_LOHI,       // cell area
+    WS_ZPROJ_IN, WS_ZPROJ_OUT,                                                                                                      // Z projection
+    WS_INV_IN, WS_INV_SMALL, WS_INV_TAB, WS_INV_MNMX, WS_INV_X, WS_INV_PROB, WS_INV_BUF0, WS_INV_BUF1, WS_INV_BUF2, WS_INV_BUF3,    // invasion depth
+    WS_INV_COL,
+    WS_TREE_BG, WS_TREE_SEG, WS_TREE_MM, WS_TREE_RGB,                                                                               // tree overlay
+    N_TOOL_WS
+};
+
 struct Ctx {
     int device = 0;
     std::vector<ResNetModel> resnets;                        // invasion-depth classifiers loaded on this handle (tmat_resnet_load)
@@ -125,7 +136,6 @@ struct Ctx {
     float *dout_relu[2] = {nullptr, nullptr};
     bool dout_relu_ok[2] = {false, false};                   // the last down-path call wrote dout_relu[i] (only the unfused last block does)
     float *urelu[2] = {nullptr, nullptr};
-    size_t urelu_bytes[2] = {0, 0};
     hipStream_t stream2 = nullptr;                           // second stream: down path of pass p+1 overlaps up path of pass p
     hipStream_t stream3 = nullptr;                           // third stream: finish stage of pass p-1 (after the host thinning)
     hipEvent_t ev_down[2] = {nullptr, nullptr};
@@ -136,37 +146,22 @@ struct Ctx {
     float *patch_in = nullptr, *patch_out = nullptr;
     float *patch_in2 = nullptr;                              // second input buffer of the batch path: the front end of pass p + 2 runs beside pass p + 1's network (pipeline.cpp)
     bool pre_side = true;                                    // that front end on the second stream (TMAT_PRE_STREAM=0: on the main stream)
-    size_t buf_bytes[4] = {0, 0, 0, 0}, ubuf_bytes[4] = {0, 0, 0, 0}, dout_bytes = 0;      // sizes of the activation workspaces (tmat_debug_poison)
     float input_sat = 65535.f;                               // Lanczos saturation: 65535, or 255 for 8-bit sources (tmat_set_input_depth)
     int patch_cap = 0;                                       // patches patch_in / patch_out hold (>= max_patches)
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
+    // owns the handle-lifetime workspaces above: buf, ubuf, dout, dout_relu, urelu, patch_in, patch_in2, patch_out, scratch
+    WsList ws;
     double *win1d = nullptr;
     std::vector<double> win_host;
     PassBuf pass;
     void free_pass()
     {
         PassBuf &b = pass;
-        void *dev[] = {b.xi, b.yi, b.xc, b.yc, b.tmp, b.x, b.small, b.mn, b.mx, b.pred[0], b.pred[1], b.morph_ws,
-                       b.filt[0], b.filt[1], b.dist[0], b.dist[1], b.finish_ws, b.skel[0], b.skel[1], b.field[0], b.field[1],
-                       b.f255[0], b.f255[1], b.dmt_ws, b.dmt_ids[0], b.dmt_ids[1], b.dmt_m[0], b.dmt_m[1], b.thin_ws, b.nfg[0], b.nfg[1], b.tie,
-                       b.dmt_sweep_ws, b.dmt_kind[0], b.dmt_kind[1], b.dmt_pers[0], b.dmt_pers[1]};
-        for (void *p : dev) if (p) hipFree(p);
-        for (int i = 0; i < 2; i++) {
-            if (b.pred_host[i]) hipHostFree(b.pred_host[i]);
-            if (b.filt_host[i]) hipHostFree(b.filt_host[i]);
-            if (b.dist_host[i]) hipHostFree(b.dist_host[i]);
-            if (b.conv_host[i]) hipHostFree(b.conv_host[i]);
-            if (b.skel_host[i]) hipHostFree(b.skel_host[i]);
-            if (b.f255_host[i]) hipHostFree(b.f255_host[i]);
-            if (b.dmt_ids_host[i]) hipHostFree(b.dmt_ids_host[i]);
-            if (b.dmt_m_host[i]) hipHostFree(b.dmt_m_host[i]);
-            if (b.dmt_kind_host[i]) hipHostFree(b.dmt_kind_host[i]);
-            if (b.dmt_pers_host[i]) hipHostFree(b.dmt_pers_host[i]);
-            if (b.nfg_host[i]) hipHostFree(b.nfg_host[i]);
-            if (b.tie_host[i]) hipHostFree(b.tie_host[i]);
-            if (b.done[i]) hipEventDestroy(b.done[i]);
-        }
+        b.ws.free_all();
+        void *lanczos[] = {b.xi, b.yi, b.xc, b.yc};
+        for (void *p : lanczos) if (p) hipFree(p);
+        for (hipEvent_t e : b.done) if (e) hipEventDestroy(e);
         pass = PassBuf();
     }
     bool thin_device = true;                                 // ordered medial-axis thinning on the device (TMAT_THIN_DEVICE=0: host threads)
@@ -188,11 +183,10 @@ struct Ctx {
     std::vector<RoiEntry *> roi_cache;
     bool fused_sep = true;                                   // fused depthwise -> pointwise kernel (sepconv_ws_kernel) where the level allows (TMAT_FUSED_SEP=0: separate kernels)
     // call-scoped device workspaces of the side tools (cell area, invasion depth), kept between calls: with the reference's default batch of 4 images a
-    // hipMalloc / hipFree pair per buffer and call costs more than the batch's kernels.  Slot = a fixed id per buffer (ws_get below).
-    static constexpr int N_TOOL_WS = 28;                     // 0-8 cell area, 9-10 Z projection, 12-22 invasion depth, 24-27 tree overlay
+    // hipMalloc / hipFree pair per buffer and call costs more than the batch's kernels.  Slot = a ToolWs id per buffer (ws_get below).
     void *tool_ws[N_TOOL_WS] = {};
     size_t tool_ws_bytes[N_TOOL_WS] = {};
-    std::multimap<size_t, void *> ws_pool;                   // released call-scoped blocks of the Z-stack tool, by size (stack_pipeline.cpp:Arena)
+    WsPool ws_pool;                                          // released call-scoped blocks of the Z-stack tool, by size (dev_mem.h:DevScope::pooled)
     // profiling of the dominant kernel family
     bool prof_on = false;
     std::vector<ProfEv> ev_open;
@@ -238,7 +232,7 @@ inline double numpy_pairwise_sum(const double *a, long n)
 
 // device workspace `slot` of the handle with room for `bytes` (grown by reallocation: the caller's stream must not have work in flight on
 // the old buffer -- every user synchronises before it returns); nullptr + set_error on failure
-inline void *ws_get(Ctx *c, int slot, size_t bytes)
+inline void *ws_get(Ctx *c, ToolWs slot, size_t bytes)
 {
     if (c->tool_ws_bytes[slot] >= bytes && c->tool_ws[slot]) return c->tool_ws[slot];
     if (c->tool_ws[slot]) { hipFree(c->tool_ws[slot]); c->tool_ws[slot] = nullptr; c->tool_ws_bytes[slot] = 0; }

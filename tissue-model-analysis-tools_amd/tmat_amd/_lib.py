@@ -98,6 +98,7 @@ def lib():
     L.tmat_conv2d.argtypes = [vp, i, vp, i, i, i, i, vp, i, i, i, vp, vp, vp, i, i, vp]
     L.tmat_prof_enable.argtypes = [vp, i]
     L.tmat_debug_poison.argtypes = [vp, i]
+    L.tmat_debug_held_bytes.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
     L.tmat_set_precision.argtypes = [vp, i]
     L.tmat_set_input_norm.argtypes = [vp, i, C.c_double, C.c_double]
     L.tmat_preprocess_batch.argtypes = [vp, vp, i, i, i, C.c_double, vp]
@@ -119,7 +120,7 @@ EXPORTS = [
     "tmat_dmt_graph", "tmat_dmt_graph_batch", "tmat_morse_stats",
     "tmat_morse_tree", "tmat_branch_color", "tmat_render_tree", "tmat_render_tree_timed", "tmat_host_render_tree", "tmat_host_render_barcode",
     "tmat_analyze_batch_dev", "tmat_analyze_batch", "tmat_analyze_batch_tree_dev", "tmat_analyze_batch_tree", "tmat_dev_alloc", "tmat_dev_free", "tmat_dev_upload",
-    "tmat_prof_enable", "tmat_prof_read", "tmat_debug_poison", "tmat_set_precision", "tmat_set_input_norm", "tmat_preprocess_batch", "tmat_well_threshold", "tmat_well_threshold_f64", "tmat_canny_mask", "tmat_host_lanczos4_u16", "tmat_host_rescale01_u16",
+    "tmat_prof_enable", "tmat_prof_read", "tmat_debug_poison", "tmat_debug_held_bytes", "tmat_set_precision", "tmat_set_input_norm", "tmat_preprocess_batch", "tmat_well_threshold", "tmat_well_threshold_f64", "tmat_canny_mask", "tmat_host_lanczos4_u16", "tmat_host_rescale01_u16",
     "tmat_host_rescale255_f32", "tmat_host_filter_mask", "tmat_host_skeletonize", "tmat_host_medial_axis",
     "tmat_host_permutation", "tmat_host_postprocess",
     "tmat_set_gaussian_table", "tmat_host_gaussian_kernel1d", "tmat_gaussian_f32", "tmat_sato_batch", "tmat_stack_prepare", "tmat_vessel_field",
@@ -304,6 +305,12 @@ class Handle:
     def debug_poison(self, byte_pattern=0xFF):
         """test-only: fill every scratch workspace of the handle with a byte pattern (include/tmat.h:tmat_debug_poison)"""
         check(lib().tmat_debug_poison(self._h, int(byte_pattern)), "tmat_debug_poison")
+
+    def debug_held_bytes(self):
+        """test-only: (device bytes, pinned bytes) the handle retains between calls (include/tmat.h:tmat_debug_held_bytes)"""
+        dev, pin = C.c_size_t(), C.c_size_t()
+        check(lib().tmat_debug_held_bytes(self._h, C.byref(dev), C.byref(pin)), "tmat_debug_held_bytes")
+        return dev.value, pin.value
 
     def prof_enable(self, on=True):
         check(lib().tmat_prof_enable(self._h, int(on)), "tmat_prof_enable")
