@@ -465,10 +465,12 @@ int tmat_resnet_set_precision(tmat_handle h, int mode);
 int tmat_conv2d(tmat_handle h, int prec, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int stride, int cout,
                 const float *scale, const float *shift, const float *resid, int relu_in, int relu_out, float *out);
 
-/* device memory helpers so a ctypes host can stage inputs in HBM without torch */
+/* device memory helpers so a ctypes host can stage inputs in HBM without torch; upload and download are ordered on the handle's
+ * stream (a download sees the work queued before it, e.g. tmat_zproj_dev) and return when the copy is done */
 int tmat_dev_alloc(tmat_handle h, size_t bytes, void **dev_ptr);
 int tmat_dev_free(tmat_handle h, void *dev_ptr);
 int tmat_dev_upload(tmat_handle h, void *dev_dst, const void *host_src, size_t bytes);
+int tmat_dev_download(tmat_handle h, void *host_dst, const void *dev_src, size_t bytes);
 
 /*
  * Host pixel stages, exposed one by one for stage-wise parity tests (csrc/postproc.cpp): host twins of the device

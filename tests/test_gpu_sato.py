@@ -40,6 +40,77 @@ def test_gaussian_f32_equals_scipy(plain, inputs, sigma, mode, name):
     assert same_bits(sato.gaussian(plain, vol, sigma, mode), ndi.gaussian_filter(vol, sigma, mode=name))
 
 
+MODES = [(0, "nearest"), (1, "reflect"), (2, "mirror")]
+FLAT_GRID_LIMIT = 16384 * 256          # sato_kernels.hip:grid_for caps a launch at 16384 blocks of 256 threads; beyond it the kernels stride
+
+
+@pytest.mark.parametrize("mode,name", MODES)
+@pytest.mark.parametrize("sigma", [1.0, 3.7, 15.0])
+@pytest.mark.parametrize("W", [512, 513, 1023, 1100])
+def test_gaussian_rows_of_several_segments(plain, W, sigma, mode, name):
+    """corr1d_row_kernel stages 512 outputs plus halo per block: one full segment, a one-pixel tail, a partial last segment, three
+    segments; at sigma 15 (r = 60) the halos reach far across the joins, and a one-pixel tail's halo is all extension"""
+    from tmat_amd import sato
+    rs = np.random.RandomState(W)
+    for shape in ((9, W), (2, 7, W)):
+        x = rs.standard_normal(shape).astype(np.float32)
+        assert same_bits(sato.gaussian(plain, x, sigma, mode), ndi.gaussian_filter(x, sigma, mode=name)), shape
+
+
+@pytest.mark.parametrize("mode,name", MODES)
+@pytest.mark.parametrize("shape,sigma", [((6, 40), 15.0), ((5, 1), 2.0), ((5, 2), 2.0)])
+def test_gaussian_lines_shorter_than_the_kernel_radius(plain, shape, sigma, mode, name):
+    """L <= r on the contiguous axis (40 columns at r = 60; 1 and 2 columns at r = 8): the boundary extension wraps more than once"""
+    from tmat_amd import sato
+    x = np.random.RandomState(shape[1]).standard_normal(shape).astype(np.float32)
+    assert same_bits(sato.gaussian(plain, x, sigma, mode), ndi.gaussian_filter(x, sigma, mode=name))
+
+
+def _smooth_stack(shape, bits, seed):
+    rs = np.random.RandomState(seed)
+    stack = ndi.gaussian_filter(rs.uniform(0, 1, shape) ** 4, (0,) * (len(shape) - 2) + (2, 2))
+    return (stack / stack.max() * (2 ** bits - 1)).astype(np.uint16 if bits == 16 else np.uint8)
+
+
+@pytest.mark.parametrize("out_hw,bits", [((35, 550), 16), ((70, 1100), 8)])
+def test_stack_prepare_wider_than_a_segment(plain, out_hw, bits):
+    """1100 columns, three segments per row: the u16 -> f64 and f64 -> u16 forms of the row kernel, with and without the resize"""
+    from oracle import sato as osato
+    from tmat_amd import sato
+    stack = _smooth_stack((2, 70, 1100), bits, 70)
+    assert same_bits(sato.stack_prepare(plain, stack, out_hw), osato.stack_prepare(stack, out_hw))
+
+
+def test_resize_aa_wider_than_a_segment(plain):
+    from oracle import sato as osato
+    from tmat_amd import sato
+    img = _smooth_stack((70, 1100), 16, 71)
+    got = sato.resize_aa(plain, img, (35, 550))
+    want = osato.resize_aa(img, (35, 550))
+    assert got.dtype == np.float64 and got.shape == want.shape and np.array_equal(got.view(np.uint64), want.view(np.uint64))
+
+
+@pytest.mark.parametrize("shape,sigma", [((3, 1200, 1300), 2.0),        # 10800 row-kernel blocks, three segments each
+                                         ((3, 1200, 1300), 0.8),        # r = 3: the strided axes go through the flat corr1d_kernel, which strides
+                                         ((2, 2050, 2050), 2.0)])       # a plane above the limit: corr1d_col_kernel strides on axis 0
+def test_gaussian_above_the_flat_grid_limit(plain, shape, sigma):
+    from tmat_amd import sato
+    x = np.random.RandomState(shape[0]).standard_normal(shape).astype(np.float32)
+    assert x.size > FLAT_GRID_LIMIT
+    if shape[0] == 2:
+        assert x[0].size > FLAT_GRID_LIMIT
+    assert same_bits(sato.gaussian(plain, x, sigma, sato.REFLECT), ndi.gaussian_filter(x, sigma, mode="reflect"))
+
+
+def test_stack_prepare_above_the_flat_grid_limit(plain):
+    """4.5 M samples: the anti-aliasing pass over the rows (sigma 0.5, r = 2) runs in the flat corr1d_kernel beyond its grid cap"""
+    from oracle import sato as osato
+    from tmat_amd import sato
+    stack = _smooth_stack((2, 1500, 1500), 16, 15)
+    assert stack.size > FLAT_GRID_LIMIT
+    assert same_bits(sato.stack_prepare(plain, stack, (750, 750)), osato.stack_prepare(stack, (750, 750)))
+
+
 def test_gaussian_matches_skimage_golden(plain, inputs):
     from tmat_amd import sato
     for k in ("t1", "t2"):

@@ -786,6 +786,15 @@ int tmat_dev_upload(tmat_handle h, void *dev_dst, const void *host_src, size_t b
     TMAT_HIP(hipStreamSynchronize(c->stream));
     return TMAT_OK;
 }
+int tmat_dev_download(tmat_handle h, void *host_dst, const void *dev_src, size_t bytes)
+{
+    Ctx *c = (Ctx *)h;
+    if (!c || !host_dst || !dev_src) { set_error("tmat_dev_download: bad argument"); return TMAT_E_ARG; }
+    TMAT_HIP(hipSetDevice(c->device));
+    TMAT_HIP(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, c->stream));
+    TMAT_HIP(hipStreamSynchronize(c->stream));
+    return TMAT_OK;
+}
 
 int tmat_set_input_depth(tmat_handle h, int bits)
 {

@@ -76,6 +76,7 @@ def lib():
     L.tmat_dev_alloc.argtypes = [vp, sz, C.POINTER(vp)]
     L.tmat_dev_free.argtypes = [vp, vp]
     L.tmat_dev_upload.argtypes = [vp, vp, vp, sz]
+    L.tmat_dev_download.argtypes = [vp, vp, vp, sz]
     d = C.c_double
     L.tmat_set_gaussian_table.argtypes = [vp, d, i, i, vp]
     L.tmat_host_gaussian_kernel1d.argtypes = [d, i, i, vp]
@@ -119,7 +120,7 @@ EXPORTS = [
     "tmat_predict_smooth", "tmat_segment_batch", "tmat_postprocess_batch", "tmat_filter_edt_batch", "tmat_medial_axis_batch", "tmat_finish_batch", "tmat_filter_mask_batch", "tmat_zproj_batch", "tmat_zproj_dev", "tmat_gather_rows",
     "tmat_dmt_graph", "tmat_dmt_graph_batch", "tmat_morse_stats",
     "tmat_morse_tree", "tmat_branch_color", "tmat_render_tree", "tmat_render_tree_timed", "tmat_host_render_tree", "tmat_host_render_barcode",
-    "tmat_analyze_batch_dev", "tmat_analyze_batch", "tmat_analyze_batch_tree_dev", "tmat_analyze_batch_tree", "tmat_dev_alloc", "tmat_dev_free", "tmat_dev_upload",
+    "tmat_analyze_batch_dev", "tmat_analyze_batch", "tmat_analyze_batch_tree_dev", "tmat_analyze_batch_tree", "tmat_dev_alloc", "tmat_dev_free", "tmat_dev_upload", "tmat_dev_download",
     "tmat_prof_enable", "tmat_prof_read", "tmat_debug_poison", "tmat_debug_held_bytes", "tmat_set_precision", "tmat_set_input_norm", "tmat_preprocess_batch", "tmat_well_threshold", "tmat_well_threshold_f64", "tmat_canny_mask", "tmat_host_lanczos4_u16", "tmat_host_rescale01_u16",
     "tmat_host_rescale255_f32", "tmat_host_filter_mask", "tmat_host_skeletonize", "tmat_host_medial_axis",
     "tmat_host_permutation", "tmat_host_postprocess",
