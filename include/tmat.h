@@ -591,6 +591,27 @@ int tmat_debug_held_bytes(tmat_handle h, size_t *device_bytes, size_t *pinned_by
 int tmat_roi_plan(int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
                   int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full);
 
+/*
+ * The same plan continued through the down path (classes and patch order are those of tmat_roi_plan): from the rectangle of the
+ * bottleneck tensor that up block 0 reads back to the input window.  TMAT_ROI_DOWN at tmat_create is a bit mask of what the tiled entry
+ * points run in this form (default 1; 0: the whole down path full-frame; TMAT_ROI=0 switches all region forms off):
+ *   bit 0: the unfused level's kernels, the residual 1x1 layers, the stem at the even pixels and the pooling fix-ups.
+ * No other bit exists yet (the fused separable layers stay full-frame): tmat_create refuses any value but 0 and 1.
+ * up_channels as for tmat_roi_plan; down_channels: n_down + 1 entries (n_down = n_up - 1), the stem's channels, then the output channels
+ * of every down block; fused_mask bit b: down block b runs on the fused separable kernel, which computes whole 16 x 16 tiles.
+ * Layers l = 0 .. 6 n_down + 3: per down block b (input side patch / 2 >> b) 6 b + 0 .. 3 the first depthwise, first pointwise, second
+ * depthwise and second pointwise layer, 6 b + 4 the stride-2 residual 1x1 and 6 b + 5 the max-pool + add (both in OUTPUT pixels); then
+ * the stem at its even pixels (side patch / 4), the stem (patch / 2), the input window (patch) and, where the walk starts, the rectangle
+ * of the network's output that the blend reads (patch).  The walk follows what that rectangle DEPENDS on, not the rounded rectangles
+ * the up-path kernels compute: their extra pixels may see unwritten operands and feed nothing the blend reads.
+ * needs: [layers][max_classes][4] = y0, x0, rows, columns the blend depends on; rects: the same rounded outwards to what the layer's
+ * kernel computes.  mac_* (pointwise and residual layers) and bytes_* (kernels without matrix work): [layers], per image.
+ * free_tile: [n_down], 1 when some class skips a whole tile of a fused level.
+ */
+int tmat_roi_plan_down(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                       unsigned fused_mask, int max_classes, int *n_classes, int *rects, int *needs, double *mac_planned,
+                       double *mac_full, double *bytes_planned, double *bytes_full, int *free_tile);
+
 #ifdef __cplusplus
 }
 #endif

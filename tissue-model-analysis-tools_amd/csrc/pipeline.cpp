@@ -167,7 +167,7 @@ static int enqueue_down(Ctx *c, int k, int slot, const TileGeom &g)
     if (oversize && tail_on_side_stream() && c->blend_pending[slot ^ 1]) TMAT_HIP(hipStreamWaitEvent(s, c->ev_blend[slot ^ 1], 0));
     float *pin = patch_in_of(c, slot, g);
     int rc = oversize ? unet_forward_dev(c, pin, k * g.tiles_per_img, c->patch_out, s)
-                      : unet_down_dev(c, pin, k * g.tiles_per_img, c->dout[slot], s);
+                      : unet_down_dev(c, pin, k * g.tiles_per_img, c->dout[slot], s, roi_find(c, g));
     if (rc) return rc;
     TMAT_HIP(hipEventRecord(c->ev_down[slot], s));
     c->down_pending[slot] = true;

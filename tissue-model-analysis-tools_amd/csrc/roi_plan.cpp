@@ -31,27 +31,30 @@ Iv align_cols(Iv v, int R)
     }
     return Iv{lo, hi};
 }
+Iv round_cols(Iv v, int R, bool exact) { return exact ? v : align_cols(v, R); }
 Iv align_to(Iv v, int al, int R) { return Iv{v.lo / al * al, std::min(R, (v.hi + al - 1) / al * al)}; }
 
 // one class: rows[l] / cols[l] for every layer, from the interval of final outputs the blend reads on each axis
-void walk_back(Iv orow, Iv ocol, int ws, int n_up, Iv *rows, Iv *cols)
+// exact: no rounding -- the pixels the blend DEPENDS on (the down plan starts from those: roi_plan_down)
+void walk_back(Iv orow, Iv ocol, int ws, int n_up, Iv *rows, Iv *cols, bool exact = false)
 {
+
     const int L = 3 * n_up + 1;
     int R = ws / 2;                                          // stored resolution of the final convolution
     // final_kernel: one thread = the 2 x 2 outputs above a stored pixel, one workgroup = 8 x 16 stored pixels, skipped or run as a whole
-    rows[L - 1] = align_to(halve(orow), 8, R);
-    cols[L - 1] = align_to(halve(ocol), 16, R);
+    rows[L - 1] = exact ? halve(orow) : align_to(halve(orow), 8, R);
+    cols[L - 1] = exact ? halve(ocol) : align_to(halve(ocol), 16, R);
     Iv need_r = dilate(rows[L - 1], 1, R), need_c = dilate(cols[L - 1], 1, R);      // of the last block's output
     for (int j = n_up - 1; j >= 0; j--) {
         const int Hl = R, Hs = j ? R / 2 : R;
         // second 3x3 (writes the block output and its activated copy): reads t1 one pixel around, the residual at (y >> up, x >> up)
-        const Iv c2r = need_r, c2c = align_cols(need_c, Hl);
+        const Iv c2r = need_r, c2c = round_cols(need_c, Hl, exact);
         rows[3 * j + 2] = c2r; cols[3 * j + 2] = c2c;
         const Iv t1r = dilate(c2r, 1, Hl), t1c = dilate(c2c, 1, Hl);
-        const Iv rsr = j ? halve(c2r) : c2r, rsc = align_cols(j ? halve(c2c) : c2c, Hs);
+        const Iv rsr = j ? halve(c2r) : c2r, rsc = round_cols(j ? halve(c2c) : c2c, Hs, exact);
         rows[3 * j + 1] = rsr; cols[3 * j + 1] = rsc;
         // first convolution.  Sub-pixel form (j > 0): stored pixel i makes the outputs 2 i and 2 i + 1 from the stored pixels i - 1 .. i + 1
-        const Iv c1r = j ? halve(t1r) : t1r, c1c = align_cols(j ? halve(t1c) : t1c, Hs);
+        const Iv c1r = j ? halve(t1r) : t1r, c1c = round_cols(j ? halve(t1c) : t1c, Hs, exact);
         rows[3 * j] = c1r; cols[3 * j] = c1c;
         // what the block reads of the previous block's output: the residual 1x1 its plain form, the first convolution its activated copy
         need_r = hull(rsr, dilate(c1r, 1, Hs));
@@ -60,7 +63,92 @@ void walk_back(Iv orow, Iv ocol, int ws, int n_up, Iv *rows, Iv *cols)
     }
 }
 
+// one axis of one class through the down path: need[l] / rect[l] for every layer of RoiDownPlan, from the interval `out` of the
+// bottleneck tensor that up block 0 reads
+void walk_down_axis(Iv out, bool cols, int ws, int n_down, unsigned fused_mask, Iv *need, Iv *rect)
+{
+    for (int b = n_down - 1; b >= 0; b--) {
+        const int H = (ws / 2) >> b, Ho = H / 2;
+        Iv *nd = need + 6 * b, *rc = rect + 6 * b;
+        nd[5] = rc[5] = out;                                     // max-pool + add: one thread per pixel
+        nd[4] = out;                                             // the residual 1x1 makes the pixels the add takes
+        rc[4] = cols ? align_cols(out, Ho) : out;
+        // MaxPooling2D(3, 2, "same") on an even side pads behind only (oracle/unet_exact.c:orc_maxpool_add): output i reads 2 i .. 2 i + 2
+        nd[3] = nd[2] = clip(Iv{2 * out.lo, 2 * out.hi + 1}, H);
+        nd[1] = nd[0] = dilate(nd[2], 1, H);
+        for (int k = 0; k < 4; k++)
+            rc[k] = ((fused_mask >> b) & 1u) ? align_to(nd[k], 16, H) : cols ? align_cols(nd[k], H) : nd[k];
+        // the block's input: one pixel around the first depthwise layer's needed outputs, and the even pixels under the stride-2 residual
+        out = hull(dilate(nd[0], 1, H), Iv{2 * out.lo, 2 * out.hi - 1});
+    }
+    const int L = 6 * n_down;
+    need[L + 3] = rect[L + 3] = Iv{0, 0};                        // (the blend's own rectangle: filled by the caller)
+    need[L] = need[4]; rect[L] = rect[4];                        // the stem at its even pixels: exactly what block 0's residual 1x1 enumerates
+    need[L + 1] = out;
+    rect[L + 1] = (fused_mask & 1u) ? dilate(rect[0], 1, ws / 2) : Iv{0, ws / 2};       // recomputed under the first depthwise tiles' halos, or the whole stem tensor
+    // Conv2D(3, strides 2, "same") on an even side: stem pixel i reads input 2 i .. 2 i + 2
+    need[L + 2] = clip(Iv{2 * out.lo, 2 * out.hi + 1}, ws);
+    rect[L + 2] = Iv{0, ws};                                     // the tile gather writes whole patches
+}
+
 }  // namespace
+
+bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask)
+{
+    p.down = RoiDownPlan();
+    if (p.n_classes <= 0 || n_down < 1 || n_down > ROI_MAX_DOWN || n_down + 1 != p.n_up || !chan) return false;      // (ws is a multiple of 4 << n_up: roi_make_plan)
+    for (int b = 0; b < n_down; b++)
+        if (((fused_mask >> b) & 1u) && (((p.ws / 2) >> b) % 16) != 0) return false;
+    RoiDownPlan &d = p.down;
+    const int L = 6 * n_down, ws = p.ws;
+    double mpp[ROI_MAX_DOWN_LAYERS] = {}, bpp[ROI_MAX_DOWN_LAYERS] = {};       // multiply-accumulates / bytes per enumerated pixel
+    for (int b = 0; b < n_down; b++) {
+        const int H = (ws / 2) >> b, cin = chan[b], cout = chan[b + 1];
+        const bool fused = (fused_mask >> b) & 1u;
+        for (int k = 0; k < 4; k++) d.res[6 * b + k] = H;
+        d.res[6 * b + 4] = d.res[6 * b + 5] = H / 2;
+        mpp[6 * b + 1] = (double)cin * cout; mpp[6 * b + 3] = (double)cout * cout; mpp[6 * b + 4] = (double)cin * cout;
+        if (!fused) {           // the streaming kernels of an unfused level: depthwise reads and writes a pixel, the pooling reads 4 and the residual, writes 1
+            bpp[6 * b] = 8.0 * cin; bpp[6 * b + 2] = 8.0 * cout; bpp[6 * b + 5] = 24.0 * cout;
+        }
+    }
+    d.res[L] = ws / 4; d.res[L + 1] = ws / 2; d.res[L + 2] = ws;
+    if (fused_mask & 1u) bpp[L] = 4.0 * chan[0];
+    bpp[L + 2] = 4.0;
+    d.res[L + 3] = ws;
+    d.n_down = n_down; d.n_layers = L + 4; d.fused_mask = fused_mask;
+    for (int l = 0; l < d.n_layers; l++) {
+        d.mac_full[l] = mpp[l] * d.res[l] * d.res[l] * p.tiles_per_img;
+        d.bytes_full[l] = bpp[l] * d.res[l] * d.res[l] * p.tiles_per_img;
+    }
+    const int R0 = ws >> p.n_up;
+    for (int k = 0; k < p.n_classes; k++) {
+        const RoiRect &rd = p.read[k];
+        if (rd.rh <= 0 || rd.rw <= 0) continue;         // a class the blend reads nothing of: empty rectangles throughout
+        // What the blend's rectangle DEPENDS on of the bottleneck tensor: the up path walked once more without its rounding (its kernels
+        // compute the rounded rectangles of p.rect; their extra pixels may see operands the down path leaves unwritten, and feed nothing
+        // the blend reads).  Up block 0 reads the plain tensor under its residual 1x1, the activated copy one pixel around its first 3x3.
+        Iv ur[ROI_MAX_LAYERS], uc[ROI_MAX_LAYERS];
+        walk_back(Iv{rd.y0, rd.y0 + rd.rh}, Iv{rd.x0, rd.x0 + rd.rw}, ws, p.n_up, ur, uc, true);
+        const Iv orow = hull(ur[1], dilate(ur[0], 1, R0)), ocol = hull(uc[1], dilate(uc[0], 1, R0));
+        Iv nr[ROI_MAX_DOWN_LAYERS], nc[ROI_MAX_DOWN_LAYERS], rr[ROI_MAX_DOWN_LAYERS], rc[ROI_MAX_DOWN_LAYERS];
+        walk_down_axis(orow, false, ws, n_down, fused_mask, nr, rr);
+        walk_down_axis(ocol, true, ws, n_down, fused_mask, nc, rc);
+        nr[L + 3] = rr[L + 3] = Iv{rd.y0, rd.y0 + rd.rh}; nc[L + 3] = rc[L + 3] = Iv{rd.x0, rd.x0 + rd.rw};
+        for (int l = 0; l < d.n_layers; l++) {
+            d.need[l][k] = RoiRect{nr[l].lo, nc[l].lo, nr[l].hi - nr[l].lo, nc[l].hi - nc[l].lo};
+            const RoiRect q{rr[l].lo, rc[l].lo, rr[l].hi - rr[l].lo, rc[l].hi - rc[l].lo};
+            d.rect[l][k] = q;
+            d.mac_planned[l] += mpp[l] * q.rh * q.rw * p.class_count[k];
+            d.bytes_planned[l] += bpp[l] * q.rh * q.rw * p.class_count[k];
+        }
+        for (int b = 0; b < n_down; b++)
+            if ((fused_mask >> b) & 1u)
+                for (int l = 6 * b + 1; l <= 6 * b + 3; l += 2)
+                    if (d.rect[l][k].rh < d.res[l] || d.rect[l][k].rw < d.res[l]) d.free_tile[b] = true;
+    }
+    return true;
+}
 
 bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_classes, RoiPlan &out)
 {
@@ -123,6 +211,7 @@ bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_cl
     for (int k = 0; k < out.n_classes; k++) {
         Iv rows[ROI_MAX_LAYERS], cols[ROI_MAX_LAYERS];
         const bool empty = keys[k].r.hi <= keys[k].r.lo;
+        out.read[k] = RoiRect{keys[k].r.lo, keys[k].c.lo, keys[k].r.hi - keys[k].r.lo, keys[k].c.hi - keys[k].c.lo};
         if (!empty) walk_back(keys[k].r, keys[k].c, ws, n_up, rows, cols);
         for (int l = 0; l < out.n_layers; l++) {
             RoiRect q{0, 0, 0, 0};
@@ -162,5 +251,37 @@ extern "C" int tmat_roi_plan(int hh, int ww, int patch, int n_up, const int *cha
         mac_planned[l] = p.mac_planned[l];
         mac_full[l] = p.mac_full[l];
     }
+    return TMAT_OK;
+}
+
+// The down-path tables of the same plan (roi_plan_down): rects and needs [6 n_down + 4][max_classes][4] as (y0, x0, rows, columns),
+// the four per-layer totals [6 n_down + 4], free_tile [n_down].  down_channels: n_down + 1 entries, the stem's first.
+extern "C" int tmat_roi_plan_down(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                  unsigned fused_mask, int max_classes, int *n_classes, int *rects, int *needs, double *mac_planned,
+                                  double *mac_full, double *bytes_planned, double *bytes_full, int *free_tile)
+{
+    if (!up_channels || !down_channels || !n_classes || !rects || !needs || !mac_planned || !mac_full || !bytes_planned || !bytes_full ||
+        !free_tile || max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
+        set_error("tmat_roi_plan_down: bad argument");
+        return TMAT_E_ARG;
+    }
+    RoiPlan p;
+    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, max_classes, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
+        set_error("tmat_roi_plan_down: unsupported geometry");
+        return TMAT_E_ARG;
+    }
+    *n_classes = p.n_classes;
+    const RoiDownPlan &d = p.down;
+    for (int l = 0; l < d.n_layers; l++) {
+        for (int k = 0; k < max_classes; k++) {
+            const RoiRect q = k < p.n_classes ? d.rect[l][k] : RoiRect{0, 0, 0, 0}, u = k < p.n_classes ? d.need[l][k] : RoiRect{0, 0, 0, 0};
+            int *o = rects + ((size_t)l * max_classes + k) * 4, *w = needs + ((size_t)l * max_classes + k) * 4;
+            o[0] = q.y0; o[1] = q.x0; o[2] = q.rh; o[3] = q.rw;
+            w[0] = u.y0; w[1] = u.x0; w[2] = u.rh; w[3] = u.rw;
+        }
+        mac_planned[l] = d.mac_planned[l]; mac_full[l] = d.mac_full[l];
+        bytes_planned[l] = d.bytes_planned[l]; bytes_full[l] = d.bytes_full[l];
+    }
+    for (int b = 0; b < d.n_down; b++) free_tile[b] = d.free_tile[b] ? 1 : 0;
     return TMAT_OK;
 }

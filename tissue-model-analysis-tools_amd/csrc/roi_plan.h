@@ -16,8 +16,33 @@ namespace tmat {
 constexpr int ROI_MAX_CLASSES = 16;
 constexpr int ROI_MAX_UP = 5;
 constexpr int ROI_MAX_LAYERS = 3 * ROI_MAX_UP + 1;
+constexpr int ROI_MAX_DOWN = 4;
+constexpr int ROI_MAX_DOWN_LAYERS = 6 * ROI_MAX_DOWN + 4;
 
 struct RoiRect { int y0, x0, rh, rw; };
+
+// The same walk continued through the down path (roi_plan_down), from what up block 0 reads of the bottleneck tensor to the input window.
+// Layer 6 b + k belongs to down block b (input side (ws / 2) >> b): k = 0 first depthwise, 1 first pointwise, 2 second depthwise,
+// 3 second pointwise (all at the block's input resolution), 4 the stride-2 residual 1x1, 5 max-pool + add (both enumerate OUTPUT pixels,
+// half the side).  Then 6 n_down: the stem at its even pixels (side ws / 4: the residual's input when the stem lives inside the first
+// separable layer), 6 n_down + 1: the stem (side ws / 2), 6 n_down + 2: the input window (side ws), 6 n_down + 3: the rectangle of the
+// network's output that the blend reads (side ws), where the walk starts.
+// need: the pixels the blend depends on, exactly, each from its consumers' NEED dilated by their taps (MaxPooling2D(3, 2, "same") on an
+// even side reads 2 i .. 2 i + 2, the stem likewise; a depthwise layer one pixel around; the residual the even pixels).  rect: what the
+// layer's kernel computes, need rounded outwards: whole 16 x 16 tiles on the fused separable kernel (a level in fused_mask), the column
+// rule of conv_mfma_kernel<..., ROI> for the pointwise and residual layers and the depthwise strips in front of them, single pixels for
+// the pooling.  A pixel of rect outside need may be computed from operands nobody wrote; nothing needed depends on it.
+struct RoiDownPlan {
+    int n_down = 0, n_layers = 0;               // 6 n_down + 4; 0: no down plan
+    unsigned fused_mask = 0;
+    int res[ROI_MAX_DOWN_LAYERS] = {};
+    RoiRect need[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {}, rect[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {};
+    // per image: multiply-accumulates of the matrix work (pointwise and residual layers), bytes moved by the kernels without any
+    // (unfused depthwise, pooling, stem at the even pixels)
+    double mac_planned[ROI_MAX_DOWN_LAYERS] = {}, mac_full[ROI_MAX_DOWN_LAYERS] = {};
+    double bytes_planned[ROI_MAX_DOWN_LAYERS] = {}, bytes_full[ROI_MAX_DOWN_LAYERS] = {};
+    bool free_tile[ROI_MAX_DOWN] = {};          // fused level b: some class skips a whole 16 x 16 tile of either separable layer
+};
 
 struct RoiPlan {
     int hh = 0, ww = 0, ws = 0, n_up = 0;
@@ -33,10 +58,16 @@ struct RoiPlan {
     // 3 j + 1: its residual 1x1, 3 j + 2: its second 3x3, 3 n_up: the final convolution (stored pixels; whole 8 x 16 blocks of final_kernel)
     int res[ROI_MAX_LAYERS] = {};               // side of the square a layer enumerates
     RoiRect rect[ROI_MAX_LAYERS][ROI_MAX_CLASSES] = {};
+    RoiRect read[ROI_MAX_CLASSES] = {};         // patch ∩ interior: the output pixels the blend reads of a patch of the class
     double mac_planned[ROI_MAX_LAYERS] = {}, mac_full[ROI_MAX_LAYERS] = {};      // multiply-accumulates per image
+    RoiDownPlan down;                           // filled by roi_plan_down
 };
 
 // chan[0]: input channels of up block 0, chan[j + 1]: output channels of up block j (n_up + 1 entries)
 bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_classes, RoiPlan &out);
+// chan[0]: channels of the stem, chan[b + 1]: output channels of down block b (n_down + 1 entries); fused_mask bit b: block b runs on the
+// tile-granular fused separable kernel (bit 0 then also means: the stem is recomputed inside the first separable layer).  Needs a plan
+// with classes; false (p.down left empty) otherwise or on a geometry the down path's kernels do not take.
+bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask);
 
 }  // namespace tmat

@@ -30,6 +30,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 namespace tmat {
 
@@ -881,9 +882,10 @@ bool launch_sepconv_ws_stem(const float *x, int N, int H, int W, int Cin, const 
 // column take the missing row / column from the strips of the tile below / to the right (nothing at the patch border: TF pads
 // with -inf) and get their residual, in place.  A tile has PR x 8 pooled pixels (PR = waves per workgroup of the convolution);
 // one thread = 4 channels of one of its 8 + PR - 1 boundary pixels.
+template <bool ROI>
 __global__ __launch_bounds__(256) void pool_fix_add_kernel(float *__restrict__ out, const float *__restrict__ strip_h, const float *__restrict__ strip_v,
                                                            const float *__restrict__ corner, const float *__restrict__ resid, int Hp, int Wp, int C,
-                                                           int c4shift, int total, int PR)
+                                                           int c4shift, int total, int PR, std::conditional_t<ROI, RoiSegs, RoiNone> roi)
 {
     const int n = blockIdx.y;
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -894,6 +896,10 @@ __global__ __launch_bounds__(256) void pool_fix_add_kernel(float *__restrict__ o
     const int tile = bp / NB, k = bp - tile * NB;
     const int TH = Hp / PR, TW = Wp >> 3, ty = tile / TW, tx = tile - ty * TW;
     const int pl = k < 8 ? PR - 1 : k - 8, ql = k < 8 ? k : 7;
+    // region form: only the boundary pixels inside the patch's box of pooled pixels (the others nobody reads)
+    RoiBox rb{};
+    if (!roi_box_of(roi, n, rb)) return;
+    if (ROI && (ty * PR + pl < rb.y0 || ty * PR + pl >= rb.y1 || tx * 8 + ql < rb.x0 || tx * 8 + ql >= rb.x1)) return;
     const size_t o = (((size_t)n * Hp + ty * PR + pl) * Wp + tx * 8 + ql) * C + cq * 4;
     float4 m = *reinterpret_cast<const float4 *>(out + o);
     auto take = [&](const float *src) {
@@ -911,12 +917,14 @@ __global__ __launch_bounds__(256) void pool_fix_add_kernel(float *__restrict__ o
 
 // finishes the tile edges of a pooled separable convolution (tiles of 2 nw rows x 16 columns; Cout / 4 a power of two)
 static void launch_pool_fix_add(float *out, const float *sh, const float *sv, const float *co, const float *resid, int N, int H, int W, int Cout, int nw,
-                         hipStream_t s)
+                         hipStream_t s, const RoiSegs *roi)
 {
     int c4shift = 0;
     while ((1 << c4shift) < Cout / 4) c4shift++;
     const int total = (H / (2 * nw)) * (W / 16) * (8 + nw - 1) * (Cout / 4);
-    hipLaunchKernelGGL(pool_fix_add_kernel, dim3((total + 255) / 256, N), dim3(256), 0, s, out, sh, sv, co, resid, H / 2, W / 2, Cout, c4shift, total, nw);
+    const dim3 grid((total + 255) / 256, N);
+    if (roi) hipLaunchKernelGGL(pool_fix_add_kernel<true>, grid, dim3(256), 0, s, out, sh, sv, co, resid, H / 2, W / 2, Cout, c4shift, total, nw, *roi);
+    else hipLaunchKernelGGL(pool_fix_add_kernel<false>, grid, dim3(256), 0, s, out, sh, sv, co, resid, H / 2, W / 2, Cout, c4shift, total, nw, RoiNone{});
 }
 
 // strips of the pooled form: row 0 / column 0 of every tile, already pooled along the row / column, and its corner pixel (8 + 8 + 1 pixels per 16 x 16 tile)
@@ -927,7 +935,8 @@ size_t sepconv_pool_scratch_floats(int N, int H, int W, int Cout)
 
 
 bool launch_sepconv_pool_ws(const float *in, int N, int H, int W, int Cin, int relu_in, const float *dw9, const float *pwk, int Cout,
-                            const float *scale, const float *shift, int relu_out, float *scratch, const float *resid, float *out, hipStream_t s, int prec)
+                            const float *scale, const float *shift, int relu_out, float *scratch, const float *resid, float *out, hipStream_t s, int prec,
+                            const RoiSegs *roi_fix)
 {
     if (!sepconv_ws_supported(H, W, Cin, Cout) || N <= 0 || (long long)N * (H / 16) * (W / 16) * (Cout / 128) > 0x3fffffffLL ||
         ((Cout / 4) & (Cout / 4 - 1))) {
@@ -938,7 +947,7 @@ bool launch_sepconv_pool_ws(const float *in, int N, int H, int W, int Cin, int r
     float *sh = scratch, *sv = sh + tiles * 8 * Cout, *co = sv + tiles * 8 * Cout;
     WsArgs a{in, N, H, W, Cin, Cout, dw9, pwk, scale, shift, relu_out, out, resid, sh, sv, co, nullptr, nullptr, nullptr};
     launch_ws_any<true>(a, relu_in, prec, s);
-    launch_pool_fix_add(out, sh, sv, co, resid, N, H, W, Cout, 8, s);
+    launch_pool_fix_add(out, sh, sv, co, resid, N, H, W, Cout, 8, s, roi_fix);
     return true;
 }
 

@@ -310,11 +310,37 @@ static bool down_block_ws(const Ctx *c, size_t bi)
            ((d.cout / 4) & (d.cout / 4 - 1)) == 0;
 }
 
+// the segments of a layer for a pass of k images: one per class with a non-empty rectangle, in the class-major patch order
+static RoiSegs roi_segs_of(const RoiPlan &p, const RoiRect *rects, int k)
+{
+    RoiSegs r{};
+    for (int cl = 0; cl < p.n_classes; cl++) {
+        const RoiRect &q = rects[cl];
+        if (q.rh <= 0 || q.rw <= 0 || p.class_count[cl] <= 0) continue;
+        RoiSeg &g = r.s[r.nseg++];
+        g.p0 = k * p.class_base[cl]; g.np = k * p.class_count[cl];
+        g.y0 = q.y0; g.x0 = q.x0; g.rh = q.rh; g.rw = q.rw;
+    }
+    return r;
+}
+static RoiSegs roi_segs(const RoiPlan &p, int l, int k) { return roi_segs_of(p, p.rect[l], k); }
+
 // Down path (memory-bound kernels + small pointwise GEMMs): X (n, P, P) -> dout (n, P/16, P/16, f_deep)
-int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s)
+// plan (tiled callers; null: whole patches): with a down plan (roi_plan.h:RoiDownPlan) the kernels named by c->roi_down compute only what
+// the region-form up path reads of dout, grown backwards; the patches are then in the plan's class-major order
+int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan)
 {
     if (n <= 0) return TMAT_OK;
     if (n > c->max_patches) { set_error("unet_down_dev: n > max_patches"); return TMAT_E_ARG; }
+    const bool roi_b = plan && plan->n_classes > 0 && plan->down.n_down == (int)c->down.size() && (c->roi_down & 1u) && n % plan->tiles_per_img == 0;
+    const int kimg = roi_b ? n / plan->tiles_per_img : 0;
+    RoiSegs sg{};
+    // the segments of layer k of down block bi (null: full-frame)
+    auto segs = [&](size_t bi, int k) -> const RoiSegs * {
+        if (!roi_b) return nullptr;
+        sg = roi_segs_of(*plan, plan->down.rect[6 * bi + k], kimg);
+        return &sg;
+    };
     const int P = c->patch;
     float *b0 = c->buf[0], *b1 = c->buf[1], *b2 = c->buf[2], *b3 = c->buf[3];
     const int di = dout == c->dout[1] ? 1 : 0;
@@ -324,7 +350,7 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s)
     // even pixels only, reads those from stem_even_kernel's quarter-size tensor as a unit-stride 1x1 convolution.
     const bool stem_in_sep = c->stem_fused && !c->down.empty() && down_block_ws(c, 0) && c->down[0].cin == c->f0 &&
                              !(c->precision == TMAT_PRECISION_BF16X3 && c->sep_bf16);
-    if (stem_in_sep) launch_stem_even(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s);
+    if (stem_in_sep) launch_stem_even(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s, segs(0, 4));      // the pixels block 0's residual 1x1 takes
     else launch_stem(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s);
     int H = P / 2;
     for (size_t bi = 0; bi < c->down.size(); bi++) {
@@ -348,33 +374,34 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s)
             r.in = b0; r.N = n; r.h = H; r.w = H; r.Cin = d.cin; r.ksize = 1; r.stride = 2; r.W = d.res_w; r.Cout = d.cout;
             r.scale = nullptr; r.shift = d.res_b; r.out = b1;
             if (stem_here) { r.h = H / 2; r.w = H / 2; r.stride = 1; }      // b0 holds the even pixels only
-            if (!conv(c, r, s)) return TMAT_E_ARG;
+            if (!conv(c, r, s, segs(bi, 4))) return TMAT_E_ARG;
             float *nxt = bi + 1 == c->down.size() ? dout : b0;
+            // (the separable layers themselves stay full-frame: outside the residual's rectangle their pooled pixels take values nobody wrote and nobody reads)
             if (c->fused_pool) {
-                if (!launch_sepconv_pool_ws(b2, n, H, H, d.cout, 0, d.dw[1], pw1, d.cout, d.scale[1], d.shift[1], 0, b3, b1, nxt, s, sprec)) return TMAT_E_ARG;
+                if (!launch_sepconv_pool_ws(b2, n, H, H, d.cout, 0, d.dw[1], pw1, d.cout, d.scale[1], d.shift[1], 0, b3, b1, nxt, s, sprec, segs(bi, 5))) return TMAT_E_ARG;
             } else {
                 if (!launch_sepconv_ws(b2, n, H, H, d.cout, 0, d.dw[1], pw1, d.cout, d.scale[1], d.shift[1], 0, b3, s, sprec)) return TMAT_E_ARG;
-                launch_maxpool_add(b3, n, H, H, d.cout, b1, nxt, s);
+                launch_maxpool_add(b3, n, H, H, d.cout, b1, nxt, s, nullptr, segs(bi, 5));
             }
             H /= 2;
             continue;
         }
-        launch_dwconv(b0, n, H, H, d.cin, 1, d.dw[0], b1, s);
+        launch_dwconv(b0, n, H, H, d.cin, 1, d.dw[0], b1, s, segs(bi, 0));
         ConvArgs a{};
         a.in = b1; a.N = n; a.h = H; a.w = H; a.Cin = d.cin; a.relu_in = 0; a.ksize = 1; a.stride = 1;
         a.W = d.pw[0]; a.Cout = d.cout; a.scale = d.scale[0]; a.shift = d.shift[0]; a.resid = nullptr; a.rs = 0;
         a.relu_out = 1; a.out = b2;
-        if (!conv(c, a, s)) return TMAT_E_ARG;
-        launch_dwconv(b2, n, H, H, d.cout, 0, d.dw[1], b3, s);
+        if (!conv(c, a, s, segs(bi, 1))) return TMAT_E_ARG;
+        launch_dwconv(b2, n, H, H, d.cout, 0, d.dw[1], b3, s, segs(bi, 2));
         a.in = b3; a.Cin = d.cout; a.W = d.pw[1]; a.scale = d.scale[1]; a.shift = d.shift[1]; a.relu_out = 0; a.out = b2;
-        if (!conv(c, a, s)) return TMAT_E_ARG;
+        if (!conv(c, a, s, segs(bi, 3))) return TMAT_E_ARG;
         ConvArgs r{};
         r.in = b0; r.N = n; r.h = H; r.w = H; r.Cin = d.cin; r.ksize = 1; r.stride = 2; r.W = d.res_w; r.Cout = d.cout;
         r.scale = nullptr; r.shift = d.res_b; r.out = b1;
-        if (!conv(c, r, s)) return TMAT_E_ARG;
+        if (!conv(c, r, s, segs(bi, 4))) return TMAT_E_ARG;
         const bool last = bi + 1 == c->down.size();
         float *dr = (last && c->relu_copy && dout == c->dout[di]) ? c->dout_relu[di] : nullptr;      // activated copy for the first up block
-        launch_maxpool_add(b2, n, H, H, d.cout, b1, last ? dout : b0, s, dr);
+        launch_maxpool_add(b2, n, H, H, d.cout, b1, last ? dout : b0, s, dr, segs(bi, 5));
         if (dr) c->dout_relu_ok[di] = true;
         H /= 2;
     }
@@ -383,19 +410,6 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s)
 }
 
 // Up path (the MFMA-bound 3x3 transposed convolutions) + final conv: dout -> Y (n, P, P)
-// the segments of layer l for a pass of k images: one per class with a non-empty rectangle, in the class-major patch order
-static RoiSegs roi_segs(const RoiPlan &p, int l, int k)
-{
-    RoiSegs r{};
-    for (int cl = 0; cl < p.n_classes; cl++) {
-        const RoiRect &q = p.rect[l][cl];
-        if (q.rh <= 0 || q.rw <= 0 || p.class_count[cl] <= 0) continue;
-        RoiSeg &g = r.s[r.nseg++];
-        g.p0 = k * p.class_base[cl]; g.np = k * p.class_count[cl];
-        g.y0 = q.y0; g.x0 = q.x0; g.rh = q.rh; g.rw = q.rw;
-    }
-    return r;
-}
 
 const RoiPlan *roi_find(const Ctx *c, const TileGeom &g)
 {
@@ -418,6 +432,13 @@ const RoiPlan *roi_attach(Ctx *c, TileGeom &g)
     if (!roi_make_plan(g.hh, g.ww, g.ws, (int)c->up.size(), chan, ROI_MAX_CLASSES, e->plan) || e->plan.n_classes == 0) {
         e->plan.hh = g.hh; e->plan.ww = g.ww; e->plan.ws = g.ws; e->plan.n_classes = 0;       // remembered: this geometry stays full-frame
         return nullptr;
+    }
+    if (c->roi_down && c->down.size() <= (size_t)ROI_MAX_DOWN) {      // the down-path tables (a geometry they do not take keeps the down path full-frame)
+        int dchan[ROI_MAX_DOWN + 1];
+        unsigned fused = 0;
+        dchan[0] = c->f0;
+        for (size_t b = 0; b < c->down.size(); b++) { dchan[b + 1] = c->down[b].cout; if (down_block_ws(c, b)) fused |= 1u << b; }
+        roi_plan_down(e->plan, (int)c->down.size(), dchan, fused);
     }
     const RoiPlan &p = e->plan;
     std::vector<int4> tab(p.tiles_per_img);
@@ -528,7 +549,7 @@ int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred
         const float *xi = x_dev + (size_t)i0 * hh * ww;
         launch_minmax_f32(xi, k, (size_t)hh * ww, mn, mx, c->stream);
         launch_extract_tiles(xi, mn, k, g, c->patch_in, c->stream);
-        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream)
+        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan)
                       : unet_forward_dev(c, c->patch_in, k * g.tiles_per_img, c->patch_out, c->stream);
         if (!rc && plan) rc = unet_up_dev(c, c->dout[0], k * g.tiles_per_img, c->patch_out, c->stream, plan);
         if (rc) return rc;
@@ -594,6 +615,12 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     c->max_patches = max_patches > 0 ? max_patches : 400;
     if (const char *e = getenv("TMAT_FUSED_SEP")) c->fused_sep = atoi(e) != 0;
     if (const char *e = getenv("TMAT_ROI")) c->roi_on = atoi(e) != 0;
+    if (const char *e = getenv("TMAT_ROI_DOWN")) {
+        // a bit mask; only bit 0 exists (bit 1, the tile-granular form of the fused separable layers, is not built): anything else is an
+        // error, not a silent full-frame run
+        if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_DOWN must be 0 or 1"); delete c; return TMAT_E_ARG; }
+        c->roi_down = (unsigned)atoi(e);
+    }
     if (const char *e = getenv("TMAT_FUSED_POOL")) c->fused_pool = atoi(e) != 0;
     if (const char *e = getenv("TMAT_STEM_FUSED")) c->stem_fused = atoi(e) != 0;
     if (const char *e = getenv("TMAT_SEP_BF16")) c->sep_bf16 = atoi(e) != 0;

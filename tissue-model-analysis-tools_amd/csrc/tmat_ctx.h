@@ -180,6 +180,9 @@ struct Ctx {
     // region form of the tiled up path (roi_plan.h): plans per image geometry, made on first use, with the device table of the class-major
     // patch order (TileGeom::order).  TMAT_ROI=0: whole patches in every layer, image-major order
     bool roi_on = true;
+    // TMAT_ROI_DOWN: what of the down path the tiled entry points run in region form too (roi_plan.h:RoiDownPlan).  Bit 0: the unfused
+    // level, the residual 1x1 layers, the stem at the even pixels, the pooling fix-ups.  0: the down path stays full-frame
+    unsigned roi_down = 1u;
     std::vector<RoiEntry *> roi_cache;
     bool fused_sep = true;                                   // fused depthwise -> pointwise kernel (sepconv_ws_kernel) where the level allows (TMAT_FUSED_SEP=0: separate kernels)
     // call-scoped device workspaces of the side tools (cell area, invasion depth), kept between calls: with the reference's default batch of 4 images a
@@ -197,7 +200,7 @@ struct Ctx {
 
 int unet_forward_dev(Ctx *c, const float *X, int n, float *Y, hipStream_t s);
 int ensure_patch_io(Ctx *c, int n_patches);
-int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s);
+int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan = nullptr);
 // plan (nullable): region form; n is then a whole number of images' patches in the plan's class-major order
 int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s, const RoiPlan *plan = nullptr);
 // the region plan of g's geometry (cached on the handle) and, in g.order, its patch order; null and the image-major order when the region

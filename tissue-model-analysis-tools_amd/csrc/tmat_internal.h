@@ -44,7 +44,25 @@ struct RoiSegs {
     RoiSeg s[16];
     long long pixels() const { long long t = 0; for (int i = 0; i < nseg; i++) t += (long long)s[i].np * s[i].rh * s[i].rw; return t; }
 };
-// returns false (and sets the error) on unsupported shapes; roi (nullable, stride 1 only): region form
+// The kernels without matrix work (depthwise, pooling, stem at the even pixels, pooling fix-ups) take the same table: a patch computes
+// the pixels [y0, y1) x [x0, x1) of its segment, a patch no segment names computes nothing.  A thread whose pixels lie outside its
+// patch's box returns before its first load; border tests stay against the patch.
+struct RoiBox { int y0, y1, x0, x1; };
+struct RoiNone {};
+#ifdef __HIPCC__
+// the box of patch n (n and the table are uniform: scalar compares); false: nothing to compute
+__device__ __forceinline__ bool roi_box_of(const RoiSegs &r, int n, RoiBox &q)
+{
+    bool hit = false;
+    q = RoiBox{0, 0, 0, 0};
+    for (int k = 0; k < r.nseg; k++)
+        if (n >= r.s[k].p0 && n < r.s[k].p0 + r.s[k].np) { q = RoiBox{r.s[k].y0, r.s[k].y0 + r.s[k].rh, r.s[k].x0, r.s[k].x0 + r.s[k].rw}; hit = true; }
+    return hit;
+}
+__device__ __forceinline__ bool roi_box_of(const RoiNone &, int, RoiBox &) { return true; }
+#endif
+// returns false (and sets the error) on unsupported shapes; roi (nullable; stride 2 with the 1x1 form only: the rectangles are output
+// pixels): region form
 bool launch_conv(const ConvArgs &a, hipStream_t s, const RoiSegs *roi = nullptr);
 // strips of the pooled separable convolution (floats): sepconv_ws_kernels.hip
 size_t sepconv_pool_scratch_floats(int N, int H, int W, int Cout);
@@ -54,20 +72,23 @@ bool sepconv_ws_supported(int H, int W, int Cin, int Cout);
 bool launch_sepconv_ws(const float *in, int N, int H, int W, int Cin, int relu_in, const float *dw9, const float *pwk, int Cout,
                        const float *scale, const float *shift, int relu_out, float *out, hipStream_t s, int prec = 0);
 bool launch_sepconv_pool_ws(const float *in, int N, int H, int W, int Cin, int relu_in, const float *dw9, const float *pwk, int Cout,
-                            const float *scale, const float *shift, int relu_out, float *scratch, const float *resid, float *out, hipStream_t s, int prec = 0);
-void launch_dwconv(const float *in, int N, int H, int W, int C, int relu_in, const float *Wd, float *out, hipStream_t s);
+                            const float *scale, const float *shift, int relu_out, float *scratch, const float *resid, float *out, hipStream_t s, int prec = 0,
+                            const RoiSegs *roi_fix = nullptr);      // roi_fix: pooled pixels the fix-up pass finishes (the convolution itself stays full-frame)
+// roi (nullable, here and below): the region form -- rows of a strip outside the box are neither loaded for nor computed
+void launch_dwconv(const float *in, int N, int H, int W, int C, int relu_in, const float *Wd, float *out, hipStream_t s, const RoiSegs *roi = nullptr);
 void launch_stem(const float *x, int N, int H, int W, const float *Ws, int Cout, const float *scale,
                  const float *shift, float *out, hipStream_t s);
 // the stem at the even output pixels only: out (N, H/4, W/4, Cout); the input of block 0's stride-2 residual convolution when the stem
 // itself is recomputed inside the first separable convolution (launch_sepconv_ws_stem)
 void launch_stem_even(const float *x, int N, int H, int W, const float *Ws, int Cout, const float *scale,
-                      const float *shift, float *out, hipStream_t s);
+                      const float *shift, float *out, hipStream_t s, const RoiSegs *roi = nullptr);
 // SeparableConv2D over the stem's output WITHOUT the stem tensor in memory: x (N, 2H, 2W) single-channel patches; the depthwise
 // producers recompute stem = relu(bn(conv3x3/s2(x))) (H x W x Cin) for their halo.  Same results as launch_stem + launch_sepconv_ws.
 bool launch_sepconv_ws_stem(const float *x, int N, int H, int W, int Cin, const float *stem_w, const float *stem_scale, const float *stem_shift,
                             const float *dw9, const float *pwk, int Cout, const float *scale, const float *shift, int relu_out, float *out,
                             hipStream_t s);
-void launch_maxpool_add(const float *p2, int N, int H, int W, int C, const float *r, float *out, hipStream_t s, float *out_relu = nullptr);
+void launch_maxpool_add(const float *p2, int N, int H, int W, int C, const float *r, float *out, hipStream_t s, float *out_relu = nullptr,
+                        const RoiSegs *roi = nullptr);
 // roi (nullable): workgroups whose 8 x 16 stored pixels lie outside their patch's rectangle return at once
 void launch_final(const float *S, int N, int h, int w, int C, const float *Wf, float bias, float *out, hipStream_t s, const RoiSegs *roi = nullptr);
 

@@ -95,7 +95,6 @@ __device__ long long conv_diag[2048 * 8 * 8];      // [workgroup < 2048][wave][w
 // the epilogue differ; the K loop, the LDS layout and the MFMA order are those of the full-frame form, so a computed pixel gets the same
 // bits.  A template flag and not a uniform branch: full-frame launches (tmat_unet_predict, oversize images, the ResNet) keep the code they
 // had, and the region form's longer address arithmetic stays out of their register budget.
-struct RoiNone {};
 template <int BM, int BN, int WM, int WN, int KS, bool RELU, int PREC = 0, bool ROI = false>
 #ifndef TMAT_CONV_WPS
 #define TMAT_CONV_WPS 4     // waves per SIMD the 8-wave conv kernel is compiled for (VGPR budget 512 / this)
@@ -851,7 +850,7 @@ bool launch_conv(const ConvArgs &a, hipStream_t s, const RoiSegs *roi)
     }
     const int M = (int)Mll;
     if (roi) {      // every segment inside the batch and the patch, in ascending patch order, at least two pixels wide
-        bool ok = a.stride == 1 && a.prec != 3 && roi->nseg >= 1 && roi->nseg <= 16;
+        bool ok = (a.stride == 1 || a.ksize == 1) && a.prec != 3 && roi->nseg >= 1 && roi->nseg <= 16;
         for (int i = 0, p = 0; ok && i < roi->nseg; i++) {
             const RoiSeg &g = roi->s[i];
             ok = g.p0 >= p && g.np >= 1 && g.p0 + g.np <= a.N && g.y0 >= 0 && g.x0 >= 0 && g.rh >= 1 && g.rw >= 2 && g.y0 + g.rh <= Ho && g.x0 + g.rw <= Wo;
@@ -880,8 +879,10 @@ constexpr int DW_ROWS = 8;      // output rows per thread (a 3-row window slides
 #ifndef TMAT_DW_WPS
 #define TMAT_DW_WPS 1
 #endif
+template <bool ROI>
 __global__ __launch_bounds__(256, TMAT_DW_WPS) void dwconv_kernel(const float *__restrict__ in, int N, int H, int W, int C, int c4shift,
-                                                     int relu_in, const float *__restrict__ Wd, float *__restrict__ out, int bpp)
+                                                     int relu_in, const float *__restrict__ Wd, float *__restrict__ out, int bpp,
+                                                     std::conditional_t<ROI, RoiSegs, RoiNone> roi)
 {
     // grid: (ceil((H/8) * (W/4) * C4 / 256), N).  One thread = a strip of 4 consecutive pixels x 8 rows x 4 channels.
     // The 3 x 6 input window slides down the strip: every new output row costs 6 float4 loads for 4 float4 stores
@@ -900,6 +901,11 @@ __global__ __launch_bounds__(256, TMAT_DW_WPS) void dwconv_kernel(const float *_
     const int WG = W >> 2;
     if (g >= (H / DW_ROWS) * WG) return;
     const int ys = (g / WG) * DW_ROWS, x0 = (g % WG) * 4;
+    // region form (template flag: the full-frame launches keep their code): the strip's rows inside the patch's box only; the box's columns
+    // are whole strips (roi_plan.cpp: multiples of 4)
+    RoiBox rb{};
+    if (!roi_box_of(roi, n, rb)) return;
+    if (ROI && (x0 < rb.x0 || x0 >= rb.x1 || ys >= rb.y1 || ys + DW_ROWS <= rb.y0)) return;
     const float *base = in + (size_t)n * H * W * C + cq * 4;
     const float lo = relu_in ? 0.f : -INFINITY;
     float4 wt[9];
@@ -910,6 +916,11 @@ __global__ __launch_bounds__(256, TMAT_DW_WPS) void dwconv_kernel(const float *_
     for (int c = 0; c < 6; c++) xok[c] = x0 + c - 1 >= 0 && x0 + c - 1 < W;
     auto load_row = [&](int yy, float4 *row) {
         const bool yok = yy >= 0 && yy < H;
+        if (ROI && (yy < rb.y0 - 1 || yy > rb.y1)) {       // under no output row of the box: never used
+#pragma unroll
+            for (int c = 0; c < 6; c++) row[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+            return;
+        }
 #pragma unroll
         for (int c = 0; c < 6; c++) {
             const bool ok = yok && xok[c];
@@ -927,6 +938,7 @@ __global__ __launch_bounds__(256, TMAT_DW_WPS) void dwconv_kernel(const float *_
     for (int r = 0; r < DW_ROWS; r++) {
         // rows (r, r + 1, r + 2) mod 3 of `win` hold input rows ys + r - 1, ys + r, ys + r + 1
         load_row(ys + r + 1, win[(r + 2) % 3]);
+        if (ROI && (ys + r < rb.y0 || ys + r >= rb.y1)) continue;
 #pragma unroll
         for (int px = 0; px < 4; px++) {
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -943,12 +955,14 @@ __global__ __launch_bounds__(256, TMAT_DW_WPS) void dwconv_kernel(const float *_
 
 static int ilog2(int v) { int s = 0; while ((1 << s) < v) s++; return s; }
 
-void launch_dwconv(const float *in, int N, int H, int W, int C, int relu_in, const float *Wd, float *out, hipStream_t s)
+void launch_dwconv(const float *in, int N, int H, int W, int C, int relu_in, const float *Wd, float *out, hipStream_t s, const RoiSegs *roi)
 {
     const int C4 = C / 4;
     const int total = (H / DW_ROWS) * (W / 4) * C4;     // H % 8 == 0 and W % 4 == 0 for every level of the model (checked in tmat_create)
     const int bpp = (total + 255) / 256;
-    hipLaunchKernelGGL(dwconv_kernel, dim3((unsigned)(((N + 7) / 8) * 8 * bpp)), dim3(256), 0, s, in, N, H, W, C, ilog2(C4), relu_in, Wd, out, bpp);
+    const dim3 grid((unsigned)(((N + 7) / 8) * 8 * bpp));
+    if (roi) hipLaunchKernelGGL(dwconv_kernel<true>, grid, dim3(256), 0, s, in, N, H, W, C, ilog2(C4), relu_in, Wd, out, bpp, *roi);
+    else hipLaunchKernelGGL(dwconv_kernel<false>, grid, dim3(256), 0, s, in, N, H, W, C, ilog2(C4), relu_in, Wd, out, bpp, RoiNone{});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1006,9 +1020,11 @@ __global__ __launch_bounds__(256) void stem_kernel(const float *__restrict__ x, 
 // stem tensor is block 0's 1x1 / stride-2 residual convolution (models.py:140), which samples exactly these pixels: a quarter of the
 // tensor (2.6 instead of 10.5 GB per pass of 1600 patches) and a unit-stride 1x1 convolution behind it.  Same chain as stem_kernel.
 constexpr int SE_PX = 4;        // output pixels per thread (measured on one box: 4 pixels 1.05 ms, 2 pixels -- fewer registers, more waves -- 1.22 ms)
+template <bool ROI>
 __global__ __launch_bounds__(256) void stem_even_kernel(const float *__restrict__ x, int H, int W, const float *__restrict__ Ws,
                                                         int Cout, int c4shift, const float *__restrict__ scale,
-                                                        const float *__restrict__ shift, float *__restrict__ out)
+                                                        const float *__restrict__ shift, float *__restrict__ out,
+                                                        std::conditional_t<ROI, RoiSegs, RoiNone> roi)
 {
     // One thread = SE_PX consecutive output pixels of a row x 4 channels: the 3 rows x 4 SE_PX input columns they touch as aligned
     // 16-byte loads shared by the 16 channel-quad lanes of a pixel group, the taps and the folded BN once per thread.
@@ -1019,6 +1035,10 @@ __global__ __launch_bounds__(256) void stem_even_kernel(const float *__restrict_
     const int g = e >> c4shift;
     if (g >= Ho * WG) return;
     const int yo = g / WG, xg = g - yo * WG;
+    // region form: the box's columns are whole pixel groups (roi_plan.cpp: multiples of 4)
+    RoiBox rb{};
+    if (!roi_box_of(roi, n, rb)) return;
+    if (ROI && (yo < rb.y0 || yo >= rb.y1 || SE_PX * xg < rb.x0 || SE_PX * xg >= rb.x1)) return;
     const float *xin = x + (size_t)n * H * W + (size_t)(4 * yo) * W + 4 * SE_PX * xg;      // rows 4 yo .. 4 yo + 2 < H, columns < W
     float win[3][4 * SE_PX];
 #pragma unroll
@@ -1050,10 +1070,12 @@ __global__ __launch_bounds__(256) void stem_even_kernel(const float *__restrict_
 }
 
 void launch_stem_even(const float *x, int N, int H, int W, const float *Ws, int Cout, const float *scale,
-                      const float *shift, float *out, hipStream_t s)
+                      const float *shift, float *out, hipStream_t s, const RoiSegs *roi)
 {
     const int total = (H / 4) * (W / 4 / SE_PX) * (Cout / 4);
-    hipLaunchKernelGGL(stem_even_kernel, dim3((total + 255) / 256, N), dim3(256), 0, s, x, H, W, Ws, Cout, ilog2(Cout / 4), scale, shift, out);
+    const dim3 grid((total + 255) / 256, N);
+    if (roi) hipLaunchKernelGGL(stem_even_kernel<true>, grid, dim3(256), 0, s, x, H, W, Ws, Cout, ilog2(Cout / 4), scale, shift, out, *roi);
+    else hipLaunchKernelGGL(stem_even_kernel<false>, grid, dim3(256), 0, s, x, H, W, Ws, Cout, ilog2(Cout / 4), scale, shift, out, RoiNone{});
 }
 
 void launch_stem(const float *x, int N, int H, int W, const float *Ws, int Cout, const float *scale,
@@ -1066,8 +1088,10 @@ void launch_stem(const float *x, int N, int H, int W, const float *Ws, int Cout,
 // ---------------------------------------------------------------------------------------------
 // MaxPooling2D(3, strides=2, "same") + residual add (models.py:138-144)
 // ---------------------------------------------------------------------------------------------
+template <bool ROI>
 __global__ __launch_bounds__(256) void maxpool_add_kernel(const float *__restrict__ p2, int H, int W, int C, int c4shift,
-                                                          const float *__restrict__ r, float *__restrict__ out, float *__restrict__ out_relu)
+                                                          const float *__restrict__ r, float *__restrict__ out, float *__restrict__ out_relu,
+                                                          std::conditional_t<ROI, RoiSegs, RoiNone> roi)
 {
     const int Ho = H >> 1, Wo = W >> 1;
     const int n = blockIdx.y;
@@ -1076,6 +1100,9 @@ __global__ __launch_bounds__(256) void maxpool_add_kernel(const float *__restric
     const int p = e >> c4shift;
     if (p >= Ho * Wo) return;
     const int yo = p / Wo, xo = p - yo * Wo;
+    RoiBox rb{};
+    if (!roi_box_of(roi, n, rb)) return;
+    if (ROI && (yo < rb.y0 || yo >= rb.y1 || xo < rb.x0 || xo >= rb.x1)) return;
     const float *base = p2 + (size_t)n * H * W * C + cq * 4;
     float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
 #pragma unroll
@@ -1097,10 +1124,12 @@ __global__ __launch_bounds__(256) void maxpool_add_kernel(const float *__restric
     }
 }
 
-void launch_maxpool_add(const float *p2, int N, int H, int W, int C, const float *r, float *out, hipStream_t s, float *out_relu)
+void launch_maxpool_add(const float *p2, int N, int H, int W, int C, const float *r, float *out, hipStream_t s, float *out_relu, const RoiSegs *roi)
 {
     const int total = (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(maxpool_add_kernel, dim3((total + 255) / 256, N), dim3(256), 0, s, p2, H, W, C, ilog2(C / 4), r, out, out_relu);
+    const dim3 grid((total + 255) / 256, N);
+    if (roi) hipLaunchKernelGGL(maxpool_add_kernel<true>, grid, dim3(256), 0, s, p2, H, W, C, ilog2(C / 4), r, out, out_relu, *roi);
+    else hipLaunchKernelGGL(maxpool_add_kernel<false>, grid, dim3(256), 0, s, p2, H, W, C, ilog2(C / 4), r, out, out_relu, RoiNone{});
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -127,7 +127,7 @@ EXPORTS = [
     "tmat_set_gaussian_table", "tmat_host_gaussian_kernel1d", "tmat_gaussian_f32", "tmat_sato_batch", "tmat_stack_prepare", "tmat_vessel_field",
     "tmat_analyze_stack", "tmat_field_stats", "tmat_field_stats_pruned", "tmat_resize_aa_u16", "tmat_cell_area_batch", "tmat_cell_area_masked", "tmat_resize_linear_u16",
     "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi", "tmat_resnet_set_precision", "tmat_conv2d",
-    "tmat_roi_plan",
+    "tmat_roi_plan", "tmat_roi_plan_down",
 ]
 
 
@@ -453,6 +453,24 @@ def roi_plan(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), max_classes=1
     n = int(tpi[0])
     return dict(tiles_per_img=n, n_classes=int(ncls[0]), tile_class=tcls[:n], tile_rank=trank[:n], class_count=ccount, rects=rects,
                 mac_planned=mp, mac_full=mf)
+
+
+def roi_plan_down(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3, max_classes=16):
+    """tmat_roi_plan_down (include/tmat.h): the down-path tables of roi_plan's classes; host arithmetic, no GPU.
+    Returns a dict: n_classes, rects / needs [6 n_down + 4][max_classes][4] (y0, x0, rows, columns), mac_planned / mac_full /
+    bytes_planned / bytes_full [6 n_down + 4], free_tile [n_down]."""
+    L = lib()
+    L.tmat_roi_plan_down.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint, C.c_int] + [C.c_void_p] * 8
+    n_up, n_down = len(channels) - 1, len(down_channels) - 1
+    ch, dch = np.asarray(channels, np.int32), np.asarray(down_channels, np.int32)
+    nl = 6 * n_down + 4
+    ncls = np.zeros(1, np.int32)
+    rects, needs = np.zeros((nl, max_classes, 4), np.int32), np.zeros((nl, max_classes, 4), np.int32)
+    mp, mf, bp, bf = np.zeros(nl), np.zeros(nl), np.zeros(nl), np.zeros(nl)
+    free = np.zeros(n_down, np.int32)
+    check(L.tmat_roi_plan_down(hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), max_classes, ptr(ncls), ptr(rects), ptr(needs),
+                               ptr(mp), ptr(mf), ptr(bp), ptr(bf), ptr(free)), "roi_plan_down")
+    return dict(n_classes=int(ncls[0]), rects=rects, needs=needs, mac_planned=mp, mac_full=mf, bytes_planned=bp, bytes_full=bf, free_tile=free)
 
 
 def host_lanczos4_u16(img, out_hw):
