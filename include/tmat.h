@@ -594,9 +594,11 @@ int tmat_roi_plan(int hh, int ww, int patch, int n_up, const int *channels, int 
 /*
  * The same plan continued through the down path (classes and patch order are those of tmat_roi_plan): from the rectangle of the
  * bottleneck tensor that up block 0 reads back to the input window.  TMAT_ROI_DOWN at tmat_create is a bit mask of what the tiled entry
- * points run in this form (default 1; 0: the whole down path full-frame; TMAT_ROI=0 switches all region forms off):
- *   bit 0: the unfused level's kernels, the residual 1x1 layers, the stem at the even pixels and the pooling fix-ups.
- * No other bit exists yet (the fused separable layers stay full-frame): tmat_create refuses any value but 0 and 1.
+ * points run in this form (default 3; 0: the whole down path full-frame; TMAT_ROI=0 switches all region forms off):
+ *   bit 0: the unfused level's kernels, the residual 1x1 layers, the stem at the even pixels and the pooling fix-ups;
+ *   bit 1: the fused separable layers visit only the 16 x 16 tiles of their rectangles (tmat_roi_sep_tiles; f32 path only, and a
+ *          layer whose rectangles are all whole patches keeps the full-frame launch).
+ * tmat_create refuses any value but 0 .. 3.
  * up_channels as for tmat_roi_plan; down_channels: n_down + 1 entries (n_down = n_up - 1), the stem's channels, then the output channels
  * of every down block; fused_mask bit b: down block b runs on the fused separable kernel, which computes whole 16 x 16 tiles.
  * Layers l = 0 .. 6 n_down + 3: per down block b (input side patch / 2 >> b) 6 b + 0 .. 3 the first depthwise, first pointwise, second
@@ -611,6 +613,23 @@ int tmat_roi_plan(int hh, int ww, int patch, int n_up, const int *channels, int 
 int tmat_roi_plan_down(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
                        unsigned fused_mask, int max_classes, int *n_classes, int *rects, int *needs, double *mac_planned,
                        double *mac_full, double *bytes_planned, double *bytes_full, int *free_tile);
+
+/*
+ * The tiles a fused separable layer of that plan visits in a pass of k images (TMAT_ROI_DOWN bit 1): layer = 6 b + 1 or 6 b + 3 of a
+ * level b in fused_mask.  With TW = (patch / 2 >> b) / 16 tiles per row and TPP = TW * TW per patch, tiles[] takes the full-frame ids
+ *   position(img, tile) * TPP + ty * TW + tx
+ * of the planned tiles: patches in ascending position (class-major, as above), row-major inside the class's rectangle of whole tiles.
+ * *n_tiles: their number (<= cap when tiles is given; tiles may be null to ask for the counts only), *n_full = k * tiles_per_img * TPP.
+ */
+int tmat_roi_sep_tiles(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                       unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles);
+
+/*
+ * Test-only (tests/test_gpu_roi_sep.py): the fused separable launches of the handle's last down pass, in launch order -- planned[i]
+ * tiles visited of full[i] (equal for a full-frame launch), counted on the host at launch time.  *n: their number (at most cap are
+ * written).
+ */
+int tmat_debug_sep_tiles(tmat_handle h, int cap, int *n, long long *planned, long long *full);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,25 @@ bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask)
     return true;
 }
 
+long long roi_sep_tile_table(const RoiPlan &p, int layer, int k, std::vector<int> &out)
+{
+    out.clear();
+    const RoiDownPlan &d = p.down;
+    const int b = layer / 6, kk = layer % 6;
+    if (k < 1 || layer < 0 || b >= d.n_down || (kk != 1 && kk != 3) || !((d.fused_mask >> b) & 1u)) return 0;
+    const int TW = d.res[layer] / 16, TPP = TW * TW;
+    const long long full = (long long)k * p.tiles_per_img * TPP;
+    if (full > 0x7fffffffLL) return 0;
+    for (int cl = 0; cl < p.n_classes; cl++) {
+        const RoiRect &q = d.rect[layer][cl];          // whole tiles (walk_down_axis rounds a fused level's rectangles to 16)
+        const int ty0 = q.y0 / 16, ty1 = (q.y0 + q.rh) / 16, tx0 = q.x0 / 16, tx1 = (q.x0 + q.rw) / 16;
+        for (int pt = k * p.class_base[cl]; pt < k * p.class_base[cl + 1]; pt++)
+            for (int ty = ty0; ty < ty1; ty++)
+                for (int tx = tx0; tx < tx1; tx++) out.push_back(pt * TPP + ty * TW + tx);
+    }
+    return full;
+}
+
 bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_classes, RoiPlan &out)
 {
     out = RoiPlan();
@@ -283,5 +302,28 @@ extern "C" int tmat_roi_plan_down(int hh, int ww, int patch, int n_up, const int
         bytes_planned[l] = d.bytes_planned[l]; bytes_full[l] = d.bytes_full[l];
     }
     for (int b = 0; b < d.n_down; b++) free_tile[b] = d.free_tile[b] ? 1 : 0;
+    return TMAT_OK;
+}
+
+// The tile table of a fused separable layer of the same plan for a pass of k images (roi_sep_tile_table): *n_full the full-frame tile
+// count, *n_tiles the planned one; tiles (nullable: counts only) takes the planned tiles' full-frame ids, cap its room.
+extern "C" int tmat_roi_sep_tiles(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                  unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
+{
+    if (!up_channels || !down_channels || !n_tiles || !n_full || k < 1) { set_error("tmat_roi_sep_tiles: bad argument"); return TMAT_E_ARG; }
+    RoiPlan p;
+    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, ROI_MAX_CLASSES, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
+        set_error("tmat_roi_sep_tiles: unsupported geometry");
+        return TMAT_E_ARG;
+    }
+    std::vector<int> tab;
+    const long long full = roi_sep_tile_table(p, layer, k, tab);
+    if (full <= 0) { set_error("tmat_roi_sep_tiles: not a fused separable layer of the plan"); return TMAT_E_ARG; }
+    *n_full = (int)full;
+    *n_tiles = (int)tab.size();
+    if (tiles) {
+        if ((int)tab.size() > cap) { set_error("tmat_roi_sep_tiles: cap too small"); return TMAT_E_ARG; }
+        std::copy(tab.begin(), tab.end(), tiles);
+    }
     return TMAT_OK;
 }

@@ -69,5 +69,11 @@ bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_cl
 // tile-granular fused separable kernel (bit 0 then also means: the stem is recomputed inside the first separable layer).  Needs a plan
 // with classes; false (p.down left empty) otherwise or on a geometry the down path's kernels do not take.
 bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask);
+// The tiles a fused separable layer of the down plan visits in a pass of k images (layer = 6 b + 1 or 6 b + 3 of a level in fused_mask):
+// full-frame tile ids  patch * TPP + ty * TW + tx  (TW = res / 16 tiles per row, TPP = TW * TW per patch), the patches in the pass's
+// class-major order (class c holds the patches k class_base[c] .. k class_base[c + 1] - 1), row-major inside the class's rectangle of
+// whole tiles.  The table depends on k: a shorter last pass has its own.  Returns the full-frame tile count k tiles_per_img TPP, 0 when
+// the layer has no tile rectangles; out.size() == that count means every patch is computed whole.
+long long roi_sep_tile_table(const RoiPlan &p, int layer, int k, std::vector<int> &out);
 
 }  // namespace tmat

@@ -94,9 +94,26 @@ __device__ long long ws_tl[12 * 2 * 14];         // absolute stamps of workgroup
 // writes it where the LDS-DMA of the plain form would have put it.  The stem tensor (10.5 GB per pass of 1600 patches) is then neither
 // written nor read: 9 multiply-adds per value are cheaper than 8 bytes of HBM traffic.  Halo pixels outside the image are the depthwise
 // convolution's zero padding (zeros, not stem values).
-template <bool RELU_IN, bool POOL, int PREC = 0, bool STEM = false>
-__global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, int nNt, int G)
+//
+// ROI (region form, roi_plan.h): the launch visits only the 16 x 16 tiles the region plan names.  nMt is then the number of PLANNED tiles and
+// tab[mt] the full-frame tile n TPP + tr of planned tile mt (roi_sep_tile_table: class-major patch order, row-major inside a patch's
+// rectangle, so consecutive entries stay neighbouring tiles of one patch and the per-XCD ranges keep their L2 locality).  Only the walk
+// changes: the four places that derive (n, tr) from mt take the table's entry instead, and everything behind that -- addresses, border
+// tests against the patch, the strip index T = n TPP + tr (pool_fix_add_kernel addresses the strips by the full-frame tile), phases, LDS
+// map, MFMA order, epilogues -- is the code of the full-frame form, so a visited tile gets the same bits.  Skipped tiles leave their
+// outputs and strips unwritten: the plan's rectangles hold every tile a needed pixel depends on.
+// The full-frame instantiations take an empty RoiNone in the table's place (one more byte of kernel arguments, the same instructions).
+__device__ __forceinline__ int ws_tab_read(int mt, RoiNone) { return mt; }
+__device__ __forceinline__ int ws_tab_read(int mt, const int *tab)
 {
+    // mt is wave-uniform: a scalar load from the constant address space (the table is written once, before any launch that reads it)
+    return *((const __attribute__((address_space(4))) int *)(unsigned long long)tab + mt);
+}
+
+template <bool RELU_IN, bool POOL, int PREC = 0, bool STEM = false, bool ROI = false>
+__global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, int nNt, int G, std::conditional_t<ROI, const int *, RoiNone> tab)
+{
+    static_assert(!ROI || PREC == 0, "ROI: f32 path only");
     __shared__ __attribute__((aligned(16))) float smem[STEM ? WS_TOTAL_STEM : WS_TOTAL];
 
     // persistent ranges: blocks b and b + 8 share an XCD; every XCD gets a contiguous super-range of the (pixel tile, channel tile) pairs and
@@ -184,8 +201,13 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
             }
         }
         const float *hA = a.in;
+        // ROI: the table entry of the tile the next tile_setup starts, requested one tile ahead -- tile_setup runs in the vector phase, and
+        // a scalar load's latency in front of its address arithmetic would lengthen that phase; requested here, it returns under the
+        // producers' own wait for their LDS-DMA in the next MFMA phase
+        int tnext = ws_tab_read(j0 / nNt, tab);
         auto tile_setup = [&](int jj) {
-            const int mt = jj / nNt;
+            const int mt = ROI ? tnext : jj / nNt;
+            if (ROI) tnext = ws_tab_read((jj + 1 < j1 ? jj + 1 : jj) / nNt, tab);
             const int n = mt / TPP, tr = mt - n * TPP;
             const int Y0 = (tr / TW) * 16 + oy - 1, X0 = (tr % TW) * 16 + ox - 1;      // image position of the halo's first pixel
             const unsigned bad = m_inv | (Y0 < 0 ? m_top : 0u) | (Y0 + 9 >= a.H ? m_bot : 0u) | (X0 < 0 ? m_left : 0u) | (X0 + 9 >= a.W ? m_right : 0u);
@@ -475,8 +497,12 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
     const float relu_lo = a.relu_out ? 0.f : -__builtin_inff();        // fmaxf(v, relu_lo): ReLU or identity without a select per value
     const unsigned vo_pool = (unsigned)(4 * h * a.Cout + r) * 4u;        // pooled pixel 4h (+ q), channel r (+ 32 jn)
     float rv[4][4];
+    // ROI: the full-frame tile of the pair cj the consumers work on, re-read behind every epilogue (nothing of a tile uses it before the
+    // next step: the load returns while the wave waits at the step's closing barrier)
+    int ctile = ws_tab_read(j0 / nNt, tab);
     auto load_resid = [&](int jj) {
-        const int mt = jj / nNt, nt = jj - mt * nNt;
+        const int mc = jj / nNt, nt = jj - mc * nNt;
+        const int mt = ROI ? ctile : mc;
         const int n = mt / TPP, tr = mt - n * TPP;
         const int ty = tr / TW, tx = tr - ty * TW;
         const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(
@@ -504,7 +530,8 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
         vo_t[i] = (unsigned)(((pix >> 4) * a.W + (pix & 15)) * a.Cout + (lane & 7) * 4) * 4u;
     }
     auto store_tile = [&](int jj, float *xw) {
-        const int mt = jj / nNt, nt = jj - mt * nNt;
+        const int mc = jj / nNt, nt = jj - mc * nNt;
+        const int mt = ROI ? ctile : mc;
         const int n = mt / TPP, tr = mt - n * TPP;
         const int ty0 = (tr / TW) * 16, tx0 = (tr % TW) * 16;
         const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(
@@ -540,7 +567,8 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
         const int s = tl_s;
 #endif
         constexpr int NW = 8, XC = 128;
-        const int mt = jj / nNt, nt = jj - mt * nNt;
+        const int mc = jj / nNt, nt = jj - mc * nNt;
+        const int mt = ROI ? ctile : mc;
         const int n = mt / TPP, tr = mt - n * TPP;
         const int ty = tr / TW, tx = tr - ty * TW;
         const int n0 = nt * 128;
@@ -758,6 +786,7 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
             if (POOL) store_tile_pool(cj, smem + (stage ? WS_A : 0));
             else store_tile(cj, smem + (stage ? WS_A1 : WS_A0) + wave * 1024);
             cj++;
+            if (ROI && s + 1 < total) ctile = ws_tab_read(cj / nNt, tab);
         }
         WS_PIN()
         if (s + 1 < total) {
@@ -798,6 +827,12 @@ bool sepconv_ws_supported(int H, int W, int Cin, int Cout)
            (long long)H * W * Cin * 4 < 0x7fffffffLL && (long long)Cout * Cin * 4 < 0x7fffffffLL;
 }
 
+// region form: a table of 1 .. N TPP tile ids (the caller built it for this N and geometry), f32 path only
+static bool ws_tiles_ok(const int *tiles, int n_tiles, int N, int H, int W, int prec)
+{
+    return !tiles || (prec == 0 && n_tiles > 0 && (long long)n_tiles <= (long long)N * (H / 16) * (W / 16));
+}
+
 static int ws_cus()
 {
     static int n_cu = 0;
@@ -810,16 +845,20 @@ static int ws_cus()
     return n_cu;
 }
 
+// tiles (nullable, prec 0 only): region form -- the n_tiles full-frame tile ids the launch visits (device, roi_sep_tile_table)
 template <bool POOL>
-static void launch_ws_any(const WsArgs &a, int relu_in, int prec, hipStream_t s)
+static void launch_ws_any(const WsArgs &a, int relu_in, int prec, hipStream_t s, const int *tiles = nullptr, int n_tiles = 0)
 {
-    const int nMt = a.N * (a.H / 16) * (a.W / 16), nNt = a.Cout / 128;
+    const int nMt = tiles ? n_tiles : a.N * (a.H / 16) * (a.W / 16), nNt = a.Cout / 128;
     const int G = (ws_cus() / 8) * 8;                       // one persistent 12-wave workgroup per CU (152 KiB of LDS)
     if (prec == 1) {
-        if (relu_in) hipLaunchKernelGGL((sepconv_ws_kernel<true, POOL, 1>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G);
-        else hipLaunchKernelGGL((sepconv_ws_kernel<false, POOL, 1>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G);
-    } else if (relu_in) hipLaunchKernelGGL((sepconv_ws_kernel<true, POOL>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G);
-    else hipLaunchKernelGGL((sepconv_ws_kernel<false, POOL>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G);
+        if (relu_in) hipLaunchKernelGGL((sepconv_ws_kernel<true, POOL, 1>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, RoiNone{});
+        else hipLaunchKernelGGL((sepconv_ws_kernel<false, POOL, 1>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, RoiNone{});
+    } else if (tiles) {
+        if (relu_in) hipLaunchKernelGGL((sepconv_ws_kernel<true, POOL, 0, false, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, tiles);
+        else hipLaunchKernelGGL((sepconv_ws_kernel<false, POOL, 0, false, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, tiles);
+    } else if (relu_in) hipLaunchKernelGGL((sepconv_ws_kernel<true, POOL>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, RoiNone{});
+    else hipLaunchKernelGGL((sepconv_ws_kernel<false, POOL>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, RoiNone{});
 #ifdef WS_DIAG
     {
         static long long hbuf[256 * 12 * 8];
@@ -850,31 +889,34 @@ static void launch_ws_any(const WsArgs &a, int relu_in, int prec, hipStream_t s)
 }
 
 bool launch_sepconv_ws(const float *in, int N, int H, int W, int Cin, int relu_in, const float *dw9, const float *pwk, int Cout,
-                       const float *scale, const float *shift, int relu_out, float *out, hipStream_t s, int prec)
+                       const float *scale, const float *shift, int relu_out, float *out, hipStream_t s, int prec, const int *tiles, int n_tiles)
 {
-    if (!sepconv_ws_supported(H, W, Cin, Cout) || N <= 0 || (long long)N * (H / 16) * (W / 16) * (Cout / 128) > 0x3fffffffLL) {
+    if (!sepconv_ws_supported(H, W, Cin, Cout) || N <= 0 || (long long)N * (H / 16) * (W / 16) * (Cout / 128) > 0x3fffffffLL ||
+        !ws_tiles_ok(tiles, n_tiles, N, H, W, prec)) {
         set_error("launch_sepconv_ws: unsupported shape");
         return false;
     }
     WsArgs a{in, N, H, W, Cin, Cout, dw9, pwk, scale, shift, relu_out, out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    launch_ws_any<false>(a, relu_in, prec, s);
+    launch_ws_any<false>(a, relu_in, prec, s, tiles, n_tiles);
     return true;
 }
 
 bool launch_sepconv_ws_stem(const float *x, int N, int H, int W, int Cin, const float *stem_w, const float *stem_scale, const float *stem_shift,
                             const float *dw9, const float *pwk, int Cout, const float *scale, const float *shift, int relu_out, float *out,
-                            hipStream_t s)
+                            hipStream_t s, const int *tiles, int n_tiles)
 {
     // the patch window offsets are 32-bit byte offsets from the tile's first window pixel: (21 rows of 2 W floats) always fits; the patch
     // itself is addressed through a 64-bit base
-    if (!sepconv_ws_supported(H, W, Cin, Cout) || N <= 0 || (long long)N * (H / 16) * (W / 16) * (Cout / 128) > 0x3fffffffLL || 9 * Cin > WS_X) {
+    if (!sepconv_ws_supported(H, W, Cin, Cout) || N <= 0 || (long long)N * (H / 16) * (W / 16) * (Cout / 128) > 0x3fffffffLL || 9 * Cin > WS_X ||
+        !ws_tiles_ok(tiles, n_tiles, N, H, W, 0)) {
         set_error("launch_sepconv_ws_stem: unsupported shape");
         return false;
     }
     WsArgs a{x, N, H, W, Cin, Cout, dw9, pwk, scale, shift, relu_out, out, nullptr, nullptr, nullptr, nullptr, stem_w, stem_scale, stem_shift};
-    const int nMt = N * (H / 16) * (W / 16), nNt = Cout / 128;
+    const int nMt = tiles ? n_tiles : N * (H / 16) * (W / 16), nNt = Cout / 128;
     const int G = (ws_cus() / 8) * 8;
-    hipLaunchKernelGGL((sepconv_ws_kernel<false, false, 0, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G);
+    if (tiles) hipLaunchKernelGGL((sepconv_ws_kernel<false, false, 0, true, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, tiles);
+    else hipLaunchKernelGGL((sepconv_ws_kernel<false, false, 0, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, RoiNone{});
     return true;
 }
 
@@ -936,17 +978,17 @@ size_t sepconv_pool_scratch_floats(int N, int H, int W, int Cout)
 
 bool launch_sepconv_pool_ws(const float *in, int N, int H, int W, int Cin, int relu_in, const float *dw9, const float *pwk, int Cout,
                             const float *scale, const float *shift, int relu_out, float *scratch, const float *resid, float *out, hipStream_t s, int prec,
-                            const RoiSegs *roi_fix)
+                            const RoiSegs *roi_fix, const int *tiles, int n_tiles)
 {
     if (!sepconv_ws_supported(H, W, Cin, Cout) || N <= 0 || (long long)N * (H / 16) * (W / 16) * (Cout / 128) > 0x3fffffffLL ||
-        ((Cout / 4) & (Cout / 4 - 1))) {
+        ((Cout / 4) & (Cout / 4 - 1)) || !ws_tiles_ok(tiles, n_tiles, N, H, W, prec)) {
         set_error("launch_sepconv_pool_ws: unsupported shape");
         return false;
     }
-    const size_t tiles = (size_t)N * (H / 16) * (W / 16);
-    float *sh = scratch, *sv = sh + tiles * 8 * Cout, *co = sv + tiles * 8 * Cout;
+    const size_t ntl = (size_t)N * (H / 16) * (W / 16);
+    float *sh = scratch, *sv = sh + ntl * 8 * Cout, *co = sv + ntl * 8 * Cout;
     WsArgs a{in, N, H, W, Cin, Cout, dw9, pwk, scale, shift, relu_out, out, resid, sh, sv, co, nullptr, nullptr, nullptr};
-    launch_ws_any<true>(a, relu_in, prec, s);
+    launch_ws_any<true>(a, relu_in, prec, s, tiles, n_tiles);
     launch_pool_fix_add(out, sh, sv, co, resid, N, H, W, Cout, 8, s, roi_fix);
     return true;
 }

@@ -301,6 +301,26 @@ static bool conv(Ctx *c, ConvArgs a, hipStream_t st, const RoiSegs *roi = nullpt
     return ok;
 }
 
+// The tile table of fused separable layer `layer` for passes of k images, cached on the plan's entry: built and uploaded on first use (a
+// blocking copy into a fresh allocation, as for the patch order), never per pass.  dev stays null when every patch is computed whole.
+// Null + error set: the allocation or the copy failed.
+static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k)
+{
+    for (const RoiTileTab &t : e->tabs) if (t.layer == layer && t.k == k) return &t;
+    std::vector<int> ids;
+    RoiTileTab t;
+    t.layer = layer; t.k = k;
+    t.full = roi_sep_tile_table(e->plan, layer, k, ids);
+    t.n = (int)ids.size();
+    if (t.full <= 0 || ids.empty()) { set_error("roi_tile_tab: no tile table for this layer"); return nullptr; }
+    if ((long long)ids.size() < t.full) {
+        if (!hip_ok(hipMalloc((void **)&t.dev, ids.size() * sizeof(int)), "hipMalloc(tile table)")) return nullptr;
+        if (!hip_ok(hipMemcpy(t.dev, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy(tile table)")) { hipFree(t.dev); return nullptr; }
+    }
+    e->tabs.push_back(t);
+    return &e->tabs.back();
+}
+
 // does down block bi (input resolution P / 2 >> bi) run on the wave-specialised fused separable kernel?
 static bool down_block_ws(const Ctx *c, size_t bi)
 {
@@ -332,14 +352,32 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
 {
     if (n <= 0) return TMAT_OK;
     if (n > c->max_patches) { set_error("unet_down_dev: n > max_patches"); return TMAT_E_ARG; }
-    const bool roi_b = plan && plan->n_classes > 0 && plan->down.n_down == (int)c->down.size() && (c->roi_down & 1u) && n % plan->tiles_per_img == 0;
-    const int kimg = roi_b ? n / plan->tiles_per_img : 0;
+    const bool roi_any = plan && plan->n_classes > 0 && plan->down.n_down == (int)c->down.size() && n % plan->tiles_per_img == 0;
+    const bool roi_b = roi_any && (c->roi_down & 1u);
+    const int kimg = roi_any ? n / plan->tiles_per_img : 0;
     RoiSegs sg{};
     // the segments of layer k of down block bi (null: full-frame)
     auto segs = [&](size_t bi, int k) -> const RoiSegs * {
         if (!roi_b) return nullptr;
         sg = roi_segs_of(*plan, plan->down.rect[6 * bi + k], kimg);
         return &sg;
+    };
+    // TMAT_ROI_DOWN bit 1: the tile table of fused layer k (1 or 3) of down block bi.  dev null: the launch stays full-frame (no plan, bf16x3
+    // weights, or every patch whole).  A table that could not be made clears tab_ok (the error is set)
+    RoiEntry *ent = nullptr;
+    if (roi_any && (c->roi_down & 2u))
+        for (RoiEntry *e : c->roi_cache) if (&e->plan == plan) ent = e;
+    c->sep_tiles.clear();
+    bool tab_ok = true;
+    auto tiles = [&](size_t bi, int k, int H, bool f32) -> RoiTileTab {
+        RoiTileTab t;
+        t.full = t.n = n * (H / 16) * (H / 16);
+        if (ent && f32) {
+            if (const RoiTileTab *made = roi_tile_tab(ent, 6 * (int)bi + k, kimg)) t = *made;
+            else tab_ok = false;
+        }
+        c->sep_tiles.push_back({t.dev ? t.n : t.full, t.full});
+        return t;
     };
     const int P = c->patch;
     float *b0 = c->buf[0], *b1 = c->buf[1], *b2 = c->buf[2], *b3 = c->buf[3];
@@ -367,20 +405,25 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
                 if (i0 != mp.end() && i1 != mp.end()) { pw0 = i0->second; pw1 = i1->second; sprec = 1; }
             }
             const bool stem_here = bi == 0 && stem_in_sep;
+            const RoiTileTab t0 = tiles(bi, 1, H, sprec == 0), t1 = tiles(bi, 3, H, sprec == 0);
+            if (!tab_ok) return TMAT_E_HIP;
             if (stem_here) {
-                if (!launch_sepconv_ws_stem(X, n, H, H, d.cin, c->stem_w, c->stem_scale, c->stem_shift, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s)) return TMAT_E_ARG;
-            } else if (!launch_sepconv_ws(b0, n, H, H, d.cin, bi > 0, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s, sprec)) return TMAT_E_ARG;
+                if (!launch_sepconv_ws_stem(X, n, H, H, d.cin, c->stem_w, c->stem_scale, c->stem_shift, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s,
+                                            t0.dev, t0.n)) return TMAT_E_ARG;
+            } else if (!launch_sepconv_ws(b0, n, H, H, d.cin, bi > 0, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s, sprec, t0.dev, t0.n)) return TMAT_E_ARG;
             ConvArgs r{};
             r.in = b0; r.N = n; r.h = H; r.w = H; r.Cin = d.cin; r.ksize = 1; r.stride = 2; r.W = d.res_w; r.Cout = d.cout;
             r.scale = nullptr; r.shift = d.res_b; r.out = b1;
             if (stem_here) { r.h = H / 2; r.w = H / 2; r.stride = 1; }      // b0 holds the even pixels only
             if (!conv(c, r, s, segs(bi, 4))) return TMAT_E_ARG;
             float *nxt = bi + 1 == c->down.size() ? dout : b0;
-            // (the separable layers themselves stay full-frame: outside the residual's rectangle their pooled pixels take values nobody wrote and nobody reads)
+            // (outside the residual's rectangle the pooled pixels take values nobody wrote and nobody reads; a tile the table skips leaves
+            // its pixels and strips unwritten: a needed pooled pixel's 2 i .. 2 i + 2 lie in the layer's rectangle, strips included)
             if (c->fused_pool) {
-                if (!launch_sepconv_pool_ws(b2, n, H, H, d.cout, 0, d.dw[1], pw1, d.cout, d.scale[1], d.shift[1], 0, b3, b1, nxt, s, sprec, segs(bi, 5))) return TMAT_E_ARG;
+                if (!launch_sepconv_pool_ws(b2, n, H, H, d.cout, 0, d.dw[1], pw1, d.cout, d.scale[1], d.shift[1], 0, b3, b1, nxt, s, sprec, segs(bi, 5),
+                                            t1.dev, t1.n)) return TMAT_E_ARG;
             } else {
-                if (!launch_sepconv_ws(b2, n, H, H, d.cout, 0, d.dw[1], pw1, d.cout, d.scale[1], d.shift[1], 0, b3, s, sprec)) return TMAT_E_ARG;
+                if (!launch_sepconv_ws(b2, n, H, H, d.cout, 0, d.dw[1], pw1, d.cout, d.scale[1], d.shift[1], 0, b3, s, sprec, t1.dev, t1.n)) return TMAT_E_ARG;
                 launch_maxpool_add(b3, n, H, H, d.cout, b1, nxt, s, nullptr, segs(bi, 5));
             }
             H /= 2;
@@ -422,6 +465,8 @@ const RoiPlan *roi_attach(Ctx *c, TileGeom &g)
 {
     g.order = nullptr;
     if (!c->roi_on || g.tiles_per_img > c->max_patches || c->up.empty() || (int)c->up.size() > ROI_MAX_UP) return nullptr;
+    for (RoiEntry *e : c->roi_cache)          // the tile tables of the other geometries go (entry points drain their streams before they return)
+        if (!(e->plan.hh == g.hh && e->plan.ww == g.ww && e->plan.ws == g.ws)) e->free_tabs();
     for (const RoiEntry *e : c->roi_cache)
         if (e->plan.hh == g.hh && e->plan.ww == g.ww && e->plan.ws == g.ws) { g.order = e->order; return e->order ? &e->plan : nullptr; }
     RoiEntry *e = new RoiEntry();
@@ -616,9 +661,9 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     if (const char *e = getenv("TMAT_FUSED_SEP")) c->fused_sep = atoi(e) != 0;
     if (const char *e = getenv("TMAT_ROI")) c->roi_on = atoi(e) != 0;
     if (const char *e = getenv("TMAT_ROI_DOWN")) {
-        // a bit mask; only bit 0 exists (bit 1, the tile-granular form of the fused separable layers, is not built): anything else is an
-        // error, not a silent full-frame run
-        if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_DOWN must be 0 or 1"); delete c; return TMAT_E_ARG; }
+        // a bit mask of bit 0 (the unfused level and the small kernels) and bit 1 (the fused separable layers' tile tables): anything else
+        // is an error, not a silent full-frame run
+        if (strcmp(e, "0") && strcmp(e, "1") && strcmp(e, "2") && strcmp(e, "3")) { set_error("tmat_create: TMAT_ROI_DOWN must be 0, 1, 2 or 3"); delete c; return TMAT_E_ARG; }
         c->roi_down = (unsigned)atoi(e);
     }
     if (const char *e = getenv("TMAT_FUSED_POOL")) c->fused_pool = atoi(e) != 0;
@@ -726,7 +771,7 @@ void tmat_destroy(tmat_handle h)
     if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->stream3) { hipStreamSynchronize(c->stream3); hipStreamDestroy(c->stream3); }
     c->ws.free_all();
-    for (RoiEntry *e : c->roi_cache) { if (e->order) hipFree(e->order); delete e; }
+    for (RoiEntry *e : c->roi_cache) { e->free_tabs(); if (e->order) hipFree(e->order); delete e; }
     if (c->win1d) hipFree(c->win1d);
     if (c->ma_table) hipFree(c->ma_table);
     for (void *p : c->tool_ws) if (p) hipFree(p);
@@ -905,6 +950,16 @@ int tmat_debug_held_bytes(tmat_handle h, size_t *device_bytes, size_t *pinned_by
     if (!c || !device_bytes || !pinned_bytes) { set_error("tmat_debug_held_bytes: bad argument"); return TMAT_E_ARG; }
     *device_bytes = *pinned_bytes = 0;
     for (const WsEnt &e : held_blocks(c)) *(e.host ? pinned_bytes : device_bytes) += e.bytes;
+    return TMAT_OK;
+}
+
+// Test-only (tests/test_gpu_roi_sep.py): planned and full tile counts of the fused separable launches of the last down pass
+int tmat_debug_sep_tiles(tmat_handle h, int cap, int *n, long long *planned, long long *full)
+{
+    Ctx *c = (Ctx *)h;
+    if (!c || !n || cap < 0 || (cap > 0 && (!planned || !full))) { set_error("tmat_debug_sep_tiles: bad argument"); return TMAT_E_ARG; }
+    *n = (int)c->sep_tiles.size();
+    for (int i = 0; i < *n && i < cap; i++) { planned[i] = c->sep_tiles[i].first; full[i] = c->sep_tiles[i].second; }
     return TMAT_OK;
 }
 

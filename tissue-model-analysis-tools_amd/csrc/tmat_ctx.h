@@ -24,7 +24,15 @@ struct UpBlock {
     float *res_w = nullptr, *res_b = nullptr;
 };
 struct ProfEv { hipEvent_t e0, e1; double flops; };
-struct RoiEntry { RoiPlan plan; int4 *order = nullptr; };       // order: device, [tiles_per_img] (TileGeom::order)
+// tile table of a fused separable layer for passes of k images (roi_plan.h:roi_sep_tile_table): dev (null: every patch whole, the launch
+// stays full-frame) holds n ids; a constant like `order` -- uploaded once, outside the workspaces tmat_debug_poison fills
+struct RoiTileTab { int layer = 0, k = 0, n = 0; long long full = 0; int *dev = nullptr; };
+struct RoiEntry {
+    RoiPlan plan;
+    int4 *order = nullptr;                  // device, [tiles_per_img] (TileGeom::order)
+    std::vector<RoiTileTab> tabs;           // made on first use; released when the handle moves to another geometry, and by tmat_destroy
+    void free_tabs() { for (RoiTileTab &t : tabs) if (t.dev) hipFree(t.dev); tabs.clear(); }
+};
 struct ConvWHost { std::vector<float> w; int cin; };        // host copy of an MFMA convolution's weights ([rows][cin])
 
 // per-geometry buffers of the batch pipeline (pipeline.cpp)
@@ -181,9 +189,11 @@ struct Ctx {
     // patch order (TileGeom::order).  TMAT_ROI=0: whole patches in every layer, image-major order
     bool roi_on = true;
     // TMAT_ROI_DOWN: what of the down path the tiled entry points run in region form too (roi_plan.h:RoiDownPlan).  Bit 0: the unfused
-    // level, the residual 1x1 layers, the stem at the even pixels, the pooling fix-ups.  0: the down path stays full-frame
-    unsigned roi_down = 1u;
+    // level, the residual 1x1 layers, the stem at the even pixels, the pooling fix-ups.  Bit 1: the fused separable layers visit only
+    // the tiles of their rectangles (RoiEntry::tabs).  0: the down path stays full-frame
+    unsigned roi_down = 3u;
     std::vector<RoiEntry *> roi_cache;
+    std::vector<std::pair<long long, long long>> sep_tiles;  // (planned, full) tiles of the fused separable launches of the last down pass (tmat_debug_sep_tiles)
     bool fused_sep = true;                                   // fused depthwise -> pointwise kernel (sepconv_ws_kernel) where the level allows (TMAT_FUSED_SEP=0: separate kernels)
     // call-scoped device workspaces of the side tools (cell area, invasion depth), kept between calls: with the reference's default batch of 4 images a
     // hipMalloc / hipFree pair per buffer and call costs more than the batch's kernels.  Slot = a ToolWs id per buffer (ws_get below).

@@ -127,7 +127,7 @@ EXPORTS = [
     "tmat_set_gaussian_table", "tmat_host_gaussian_kernel1d", "tmat_gaussian_f32", "tmat_sato_batch", "tmat_stack_prepare", "tmat_vessel_field",
     "tmat_analyze_stack", "tmat_field_stats", "tmat_field_stats_pruned", "tmat_resize_aa_u16", "tmat_cell_area_batch", "tmat_cell_area_masked", "tmat_resize_linear_u16",
     "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi", "tmat_resnet_set_precision", "tmat_conv2d",
-    "tmat_roi_plan", "tmat_roi_plan_down",
+    "tmat_roi_plan", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles",
 ]
 
 
@@ -307,6 +307,15 @@ class Handle:
         """test-only: fill every scratch workspace of the handle with a byte pattern (include/tmat.h:tmat_debug_poison)"""
         check(lib().tmat_debug_poison(self._h, int(byte_pattern)), "tmat_debug_poison")
 
+    def debug_sep_tiles(self):
+        """test-only: [(planned tiles, full-frame tiles)] of the fused separable launches of the last down pass (include/tmat.h:tmat_debug_sep_tiles)"""
+        L = lib()
+        L.tmat_debug_sep_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        n = np.zeros(1, np.int32)
+        planned, full = np.zeros(16, np.int64), np.zeros(16, np.int64)
+        check(L.tmat_debug_sep_tiles(self._h, 16, ptr(n), ptr(planned), ptr(full)), "tmat_debug_sep_tiles")
+        return [(int(planned[i]), int(full[i])) for i in range(min(int(n[0]), 16))]
+
     def debug_held_bytes(self):
         """test-only: (device bytes, pinned bytes) the handle retains between calls (include/tmat.h:tmat_debug_held_bytes)"""
         dev, pin = C.c_size_t(), C.c_size_t()
@@ -471,6 +480,21 @@ def roi_plan_down(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), down_cha
     check(L.tmat_roi_plan_down(hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), max_classes, ptr(ncls), ptr(rects), ptr(needs),
                                ptr(mp), ptr(mf), ptr(bp), ptr(bf), ptr(free)), "roi_plan_down")
     return dict(n_classes=int(ncls[0]), rects=rects, needs=needs, mac_planned=mp, mac_full=mf, bytes_planned=bp, bytes_full=bf, free_tile=free)
+
+
+def roi_sep_tiles(hh, ww, layer, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
+    """tmat_roi_sep_tiles (include/tmat.h): the full-frame ids of the tiles fused separable layer `layer` visits in a pass of k images;
+    host arithmetic, no GPU.  Returns (ids int32 [planned], full-frame tile count)."""
+    L = lib()
+    L.tmat_roi_sep_tiles.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint] + [C.c_int] * 3 + [C.c_void_p] * 3
+    n_up, n_down = len(channels) - 1, len(down_channels) - 1
+    ch, dch = np.asarray(channels, np.int32), np.asarray(down_channels, np.int32)
+    nt, nf = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    args = (hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), int(layer), int(k))
+    check(L.tmat_roi_sep_tiles(*args, 0, ptr(nt), ptr(nf), None), "roi_sep_tiles")
+    ids = np.zeros(max(int(nt[0]), 1), np.int32)
+    check(L.tmat_roi_sep_tiles(*args, len(ids), ptr(nt), ptr(nf), ptr(ids)), "roi_sep_tiles")
+    return ids[:int(nt[0])], int(nf[0])
 
 
 def host_lanczos4_u16(img, out_hw):
