@@ -447,20 +447,35 @@ int tmat_inv_depth_predict_multi(tmat_handle h, const int *model_ids, int n_mode
  *       max-pool, global average, dense unit and sigmoid are unchanged.  NOT bit-exact with oracle/resnet.py: on synthetic
  *       ensembles a member's probability moves by up to ~2e-3 and the ensemble mean by a few 1e-4, so the 4th decimal of the
  *       printed probability changes on most slices (DESIGN 7c has the measured figures; fine-tuned checkpoints are unmeasured).
+ *   TMAT_RESNET_PRECISION_F16ACT opt-in: the f16 mode with every activation tensor of the classifier -- the im2col tensor, the stem
+ *       output, the pool output, every trunk convolution's output, the shortcut -- living in memory as IEEE binary16.  Weights: the
+ *       same single f16 plane as the f16 mode.  im2col rounds the prepared f32 input ONCE (nearest even, magnitudes above 65504
+ *       saturating to +-65504).  A convolution multiplies the stored f16 values as they are (no further rounding), accumulates in f32
+ *       on v_mfma_f32_32x32x16_f16 with the f16 mode's k-step geometry and order (a k step = 16 consecutive channels of one tap, a
+ *       lane half carrying 8 of them; per accumulator: 32-channel blocks ascending, inside a block tap-major, k steps ascending --
+ *       on the same f16-exact operands the accumulator equals the f16 mode's bit for bit), runs the f32 epilogue
+ *       (fmaf(acc, scale, shift), + the residual, an f16 value widened exactly, ReLU) and rounds the result ONCE to f16 with the
+ *       same rounding and saturation before it is stored.  Max-pool takes the maximum of f16 values (exact); global average, dense
+ *       unit and sigmoid are the f32 code of the other modes reading widened f16.  Data preparation is unchanged.  The activation
+ *       buffers of the other modes are reused at half their bytes.  Same input -> same bits, call after call.  NOT bit-exact with
+ *       oracle/resnet.py and NOT equal to the f16 mode: every stored activation carries an f16 rounding (DESIGN 7c has the figures).
  * Works on any handle (tmat_create_plain included), independent of tmat_set_precision; drains the handle's streams, then
  * applies to the calls that follow (tmat_resnet_predict, tmat_inv_depth_predict, tmat_inv_depth_predict_multi).  The f16
- * copy of a model's weights is made on the host when the mode is first on and freed with the model.  Other values:
- * TMAT_E_ARG.  TMAT_INV_DEPTH_PRECISION=f32|f16 selects the mode at handle creation (any other value fails creation).
+ * copy of a model's weights is made on the host when a 16-bit mode is first on and freed with the model.  Other values (2
+ * included): TMAT_E_ARG.  TMAT_INV_DEPTH_PRECISION=f32|f16|f16act selects the mode at handle creation (any other value fails creation).
  */
 #define TMAT_RESNET_PRECISION_F32 0
 #define TMAT_RESNET_PRECISION_F16 1
+#define TMAT_RESNET_PRECISION_F16ACT 3
 int tmat_resnet_set_precision(tmat_handle h, int mode);
 /*
  * Stage-wise test entry point: ONE convolution of conv_mfma_kernel on host buffers.  x (n, hh, ww, cin) f32; w in the Keras
  * layout (ksize, ksize, cin, cout); ksize 1 (stride 1 or 2, TF SAME: even indices) or 3 (stride 1, SAME); cin % 32 == 0 (and
  * 9 cin / 32 even for ksize 3), cout 64 or a multiple of 128; v = scale ? fmaf(acc, scale, shift) : acc + shift, + resid
  * (nullable, shaped like out), ReLU on load / on store as asked; out (n, hh / stride, ww / stride, cout).  prec 0: the f32
- * contract (bit-exact with oracle/unet.py:_conv); prec 3: the f16 contract above.
+ * contract (bit-exact with oracle/unet.py:_conv); prec 3: the f16 contract above; prec 4: ONE f16act convolution (every restriction
+ * of prec 3, and cin % 64 == 0): x -- after the load-side ReLU -- and resid are rounded to f16 on the host, the convolution runs on
+ * f16 device buffers, out is its f16 output widened to f32: round_f16(the prec 3 result on the same f16-exact operands), bit for bit.
  */
 int tmat_conv2d(tmat_handle h, int prec, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int stride, int cout,
                 const float *scale, const float *shift, const float *resid, int relu_in, int relu_out, float *out);

@@ -16,6 +16,9 @@
 // Arithmetic of the new kernels (shared with oracle/resnet.py): float32, multiply and add kept separate (no FMA) in pool and
 // head; stem: orc_conv's chain over k (the MFMA order) on the im2col tensor, fmaf(acc, scale, shift), ReLU; head: per channel sum over the 256 pixels in raster order, times 1/256, dot product over
 // the channels in order, plus bias, 1 / (1 + exp_det(-z)).
+// Opt-in modes (tmat_resnet_set_precision): f16 -- the convolutions on conv_mfma_kernel's PREC = 3 form, activations f32 in memory;
+// f16act -- every activation tensor IEEE binary16 in memory: conv_f16act_kernels.hip, resnet_im2col_f16_kernel and the _Float16 forms of
+// the pool and head kernels below, in the first half of the same buffers (resnet_forward_f16act_dev).
 #include "../../include/tmat.h"
 #include "tmat_ctx.h"
 
@@ -81,8 +84,37 @@ __global__ __launch_bounds__(256) void resnet_im2col_kernel(const float *__restr
     }
 }
 
+// the f16act form: the same tensor as IEEE binary16 -- THE one rounding of the prepared input (nearest even, magnitudes above
+// 65504 saturating).  One thread = 8 consecutive k of one output pixel (one 16-byte store).
+typedef _Float16 f16x8_r __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ _Float16 f16_sat_r(float v) { return (_Float16)__builtin_amdgcn_fmed3f(v, -65504.f, 65504.f); }
+__global__ __launch_bounds__(256) void resnet_im2col_f16_kernel(const float *__restrict__ x, int S, _Float16 *__restrict__ col, size_t total)
+{
+    const int So = S >> 1;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const int q = (int)(e % (STEM_K / 8));
+        const size_t pix = e / (STEM_K / 8);
+        const int xo = (int)(pix % So), yo = (int)((pix / So) % So);
+        const size_t n = pix / ((size_t)So * So);
+        const float *xi = x + n * S * S * 3;
+        f16x8_r v;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const int k = 8 * q + j;
+            const int tap = k / 3, c = k - tap * 3;
+            const int ky = tap / 7, kx = tap - ky * 7;
+            const int iy = 2 * yo + ky - 3, ix = 2 * xo + kx - 3;
+            const bool in = k < STEM_TAPS && iy >= 0 && iy < S && ix >= 0 && ix < S;
+            v[j] = f16_sat_r(in ? xi[((size_t)iy * S + ix) * 3 + c] : 0.0f);
+        }
+        *reinterpret_cast<f16x8_r *>(col + e * 8) = v;
+    }
+}
+
 // pool1: ZeroPadding2D(1) + MaxPooling2D(3, strides 2, valid): (N, S, S, C) -> (N, S/2, S/2, C); the padding is ZEROS
-__global__ __launch_bounds__(256) void resnet_pool_kernel(const float *__restrict__ x, int S, int C, float *__restrict__ out, size_t total)
+// T = float, or _Float16 (f16act: the maximum of f16 values is one of them: exact)
+template <typename T>
+__global__ __launch_bounds__(256) void resnet_pool_kernel(const T *__restrict__ x, int S, int C, T *__restrict__ out, size_t total)
 {
     const int So = S >> 1;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
@@ -94,10 +126,10 @@ __global__ __launch_bounds__(256) void resnet_pool_kernel(const float *__restric
         for (int ky = 0; ky < 3; ky++)
             for (int kx = 0; kx < 3; kx++) {
                 const int iy = 2 * yo + ky - 1, ix = 2 * xo + kx - 1;
-                const float v = (iy >= 0 && iy < S && ix >= 0 && ix < S) ? x[((n * S + iy) * S + ix) * C + c] : 0.0f;
+                const float v = (iy >= 0 && iy < S && ix >= 0 && ix < S) ? (float)x[((n * S + iy) * S + ix) * C + c] : 0.0f;
                 m = v > m ? v : m;
             }
-        out[e] = m;
+        out[e] = (T)m;
     }
 }
 
@@ -119,14 +151,16 @@ __device__ __forceinline__ float exp_det_r(float x)        // the deterministic 
 }
 
 // GlobalAveragePooling2D + Dense(1) + sigmoid: feat (N, P, C) -> prob (N); one block per image, thread = channel (C <= 1024)
-__global__ __launch_bounds__(1024) void resnet_head_kernel(const float *__restrict__ feat, int P, int C, const float *__restrict__ w, float b, float *__restrict__ prob)
+// T = float, or _Float16 (f16act: the features widened exactly, the arithmetic unchanged)
+template <typename T>
+__global__ __launch_bounds__(1024) void resnet_head_kernel(const T *__restrict__ feat, int P, int C, const float *__restrict__ w, float b, float *__restrict__ prob)
 {
     __shared__ float sm[1024];
     const int c = threadIdx.x;
     if (c < C) {
-        const float *f = feat + (size_t)blockIdx.x * P * C + c;
+        const T *f = feat + (size_t)blockIdx.x * P * C + c;
         float s = 0.0f;
-        for (int p = 0; p < P; p++) s = s + f[(size_t)p * C];
+        for (int p = 0; p < P; p++) s = s + (float)f[(size_t)p * C];
         sm[c] = s * (1.0f / (float)P);
     }
     __syncthreads();
@@ -229,11 +263,57 @@ static bool run_conv(const ResConv &c, int prec, const float *in, int N, int h, 
     return launch_conv(a, s);
 }
 
+static bool run_conv_f16act(const ResConv &c, const uint16_t *in, int N, int h, const uint16_t *resid, int relu, uint16_t *out, hipStream_t s)
+{
+    ConvF16Args a{};
+    a.in = in; a.N = N; a.h = h; a.w = h; a.Cin = c.cin; a.ksize = c.ksize; a.stride = c.stride; a.W = (const uint16_t *)c.w16; a.Cout = c.cout;
+    a.scale = c.scale; a.shift = c.shift; a.resid = resid; a.relu_out = relu; a.out = out;
+    return launch_conv_f16act(a, s);
+}
+
+// The f16act form of resnet_forward_dev: the same launches and the same buffer rotation, every activation tensor IEEE binary16 in the
+// first half of the buffer the f32 forms use (no allocation of its own, no host-side conversion).
+static int resnet_forward_f16act_dev(const ResNetModel &m, const float *x, int N, int S, float *const bufs[4], float *col32, float *prob, hipStream_t s)
+{
+    uint16_t *a = (uint16_t *)bufs[0], *b = (uint16_t *)bufs[1], *t1 = (uint16_t *)bufs[2], *t2 = (uint16_t *)bufs[3], *col = (uint16_t *)col32;
+    const int S2 = S / 2, S4 = S / 4;
+    {
+        const size_t octs = (size_t)N * S2 * S2 * (STEM_K / 8);
+        hipLaunchKernelGGL(resnet_im2col_f16_kernel, dim3((unsigned)std::min<size_t>((octs + 255) / 256, 1u << 20)), dim3(256), 0, s, x, S, (_Float16 *)col, octs);
+        ConvF16Args st{};
+        st.in = col; st.N = N; st.h = S2; st.w = S2; st.Cin = STEM_K; st.ksize = 1; st.stride = 1; st.W = (const uint16_t *)m.stem_w16; st.Cout = 64;
+        st.scale = m.stem_scale; st.shift = m.stem_shift; st.resid = nullptr; st.relu_out = 1; st.out = a;
+        if (!launch_conv_f16act(st, s)) return TMAT_E_ARG;
+    }
+    const size_t ptotal = (size_t)N * S4 * S4 * 64;
+    hipLaunchKernelGGL(resnet_pool_kernel<_Float16>, dim3((unsigned)std::min<size_t>((ptotal + 255) / 256, 16384)), dim3(256), 0, s, (const _Float16 *)a, S2, 64, (_Float16 *)b, ptotal);
+    uint16_t *cur = b, *nxt = a;
+    int h = S4;
+    for (const ResBlock &k : m.blocks) {
+        const int ho = h / k.c1.stride;
+        const uint16_t *shortcut = cur;
+        if (k.has_sc) {
+            if (!run_conv_f16act(k.sc, cur, N, h, nullptr, 0, t2, s)) return TMAT_E_ARG;
+            shortcut = t2;
+        }
+        if (!run_conv_f16act(k.c1, cur, N, h, nullptr, 1, t1, s)) return TMAT_E_ARG;
+        if (!run_conv_f16act(k.c2, t1, N, ho, nullptr, 1, nxt, s)) return TMAT_E_ARG;
+        if (!run_conv_f16act(k.c3, nxt, N, ho, shortcut, 1, t1, s)) return TMAT_E_ARG;
+        uint16_t *old = cur;
+        cur = t1; t1 = old;
+        h = ho;
+    }
+    hipLaunchKernelGGL(resnet_head_kernel<_Float16>, dim3(N), dim3(1024), 0, s, (const _Float16 *)cur, h * h, m.feat, m.fc_w, m.fc_b, prob);
+    return hipGetLastError() == hipSuccess ? TMAT_OK : TMAT_E_HIP;
+}
+
 // x (N, S, S, 3) f32 on the device -> prob (N) on the device; bufs: 4 activation buffers of N * (S/2)^2 * 64 floats; col: N * (S/2)^2 * 192
 static int resnet_forward_dev(const ResNetModel &m, int mode, const float *x, int N, int S, float *const bufs[4], float *col, float *prob, hipStream_t s)
 {
-    const int prec = mode == TMAT_RESNET_PRECISION_F16 ? 3 : 0;
+    const int prec = mode == TMAT_RESNET_PRECISION_F32 ? 0 : 3;
+    if (m.feat > 1024) { set_error("resnet: head supports at most 1024 channels"); return TMAT_E_ARG; }
     if (prec == 3 && !m.has_f16) { set_error("resnet: the model has no f16 weights (tmat_resnet_set_precision makes them)"); return TMAT_E_ARG; }
+    if (mode == TMAT_RESNET_PRECISION_F16ACT) return resnet_forward_f16act_dev(m, x, N, S, bufs, col, prob, s);
     float *a = bufs[0], *b = bufs[1], *t1 = bufs[2], *t2 = bufs[3];
     const int S2 = S / 2, S4 = S / 4;
     {
@@ -246,7 +326,7 @@ static int resnet_forward_dev(const ResNetModel &m, int mode, const float *x, in
         if (!launch_conv(st, s)) return TMAT_E_ARG;
     }
     const size_t ptotal = (size_t)N * S4 * S4 * 64;
-    hipLaunchKernelGGL(resnet_pool_kernel, dim3((unsigned)std::min<size_t>((ptotal + 255) / 256, 16384)), dim3(256), 0, s, a, S2, 64, b, ptotal);
+    hipLaunchKernelGGL(resnet_pool_kernel<float>, dim3((unsigned)std::min<size_t>((ptotal + 255) / 256, 16384)), dim3(256), 0, s, (const float *)a, S2, 64, b, ptotal);
     float *cur = b, *nxt = a;
     int h = S4;
     for (const ResBlock &k : m.blocks) {
@@ -264,8 +344,7 @@ static int resnet_forward_dev(const ResNetModel &m, int mode, const float *x, in
         cur = t1; t1 = old;
         h = ho;
     }
-    if (m.feat > 1024) { set_error("resnet: head supports at most 1024 channels"); return TMAT_E_ARG; }
-    hipLaunchKernelGGL(resnet_head_kernel, dim3(N), dim3(1024), 0, s, cur, h * h, m.feat, m.fc_w, m.fc_b, prob);
+    hipLaunchKernelGGL(resnet_head_kernel<float>, dim3(N), dim3(1024), 0, s, (const float *)cur, h * h, m.feat, m.fc_w, m.fc_b, prob);
     return hipGetLastError() == hipSuccess ? TMAT_OK : TMAT_E_HIP;
 }
 
@@ -273,8 +352,8 @@ int resnet_precision_from_env(Ctx *c)
 {
     const char *e = getenv("TMAT_INV_DEPTH_PRECISION");
     if (!e || !strcmp(e, "f32")) return TMAT_OK;
-    if (strcmp(e, "f16")) { set_error("TMAT_INV_DEPTH_PRECISION must be f32 or f16"); return TMAT_E_ARG; }
-    c->resnet_precision = TMAT_RESNET_PRECISION_F16;      // no classifier is loaded yet: tmat_resnet_load makes the f16 planes
+    if (strcmp(e, "f16") && strcmp(e, "f16act")) { set_error("TMAT_INV_DEPTH_PRECISION must be f32, f16 or f16act"); return TMAT_E_ARG; }
+    c->resnet_precision = strcmp(e, "f16") ? TMAT_RESNET_PRECISION_F16ACT : TMAT_RESNET_PRECISION_F16;      // no classifier is loaded yet: tmat_resnet_load makes the f16 planes
     return TMAT_OK;
 }
 
@@ -329,36 +408,74 @@ int tmat_resnet_load(tmat_handle hd, const void *weights_blob, size_t n_bytes, i
     m.feat = cin;
     m.fc_b = fb->second.data[0];
     if (!up(m, std::vector<float>(fw->second.data, fw->second.data + cin), &m.fc_w)) return fail();
-    if (c->resnet_precision == TMAT_RESNET_PRECISION_F16 && !ensure_f16(m)) return fail();
+    if (c->resnet_precision != TMAT_RESNET_PRECISION_F32 && !ensure_f16(m)) return fail();
     c->resnets.push_back(std::move(m));
     *model_id = (int)c->resnets.size() - 1;
     return TMAT_OK;
 }
 
+// tmat_conv2d(prec = 4): one f16act convolution; wq is the f16 plane of the k-contiguous weights
+static int conv2d_f16act(Ctx *c, const float *x, size_t nx, int n, int hh, int ww, int cin, const std::vector<uint16_t> &wq, int ksize, int stride, int cout,
+                         const float *scale, const float *shift, const float *resid, size_t no, int relu_in, int relu_out, float *out)
+{
+    hipStream_t s = c->stream;
+    std::vector<uint16_t> xq(nx), rq(resid ? no : 0), oq(no);
+    for (size_t i = 0; i < nx; i++) xq[i] = f16_rne_sat(relu_in && !(x[i] > 0.f) ? 0.f : x[i]);
+    for (size_t i = 0; i < rq.size(); i++) rq[i] = f16_rne_sat(resid[i]);
+    uint16_t *dx = nullptr, *dw = nullptr, *dr = nullptr;
+    float *dsc = nullptr, *dsh = nullptr;
+    int rc = TMAT_OK;
+    DevScope mem(c->ws_pool, s);          // the uploads read xq / wq / rq
+    auto put = [&](void **d, const void *src, size_t bytes) {
+        *d = mem.alloc_bytes(bytes, "hipMalloc(tmat_conv2d)");
+        return *d && hip_ok(hipMemcpyAsync(*d, src, bytes, hipMemcpyHostToDevice, s), "H2D");
+    };
+    if (!put((void **)&dx, xq.data(), nx * 2) || !put((void **)&dw, wq.data(), wq.size() * 2) || !put((void **)&dsh, shift, (size_t)cout * 4) ||
+        (scale && !put((void **)&dsc, scale, (size_t)cout * 4)) || (resid && !put((void **)&dr, rq.data(), no * 2))) rc = TMAT_E_HIP;
+    uint16_t *dout = (uint16_t *)mem.alloc_bytes(no * 2, "hipMalloc(tmat_conv2d)");
+    if (!mem.ok || !dout) rc = TMAT_E_HIP;
+    if (!rc) {
+        ConvF16Args a{};
+        a.in = dx; a.N = n; a.h = hh; a.w = ww; a.Cin = cin; a.ksize = ksize; a.stride = stride; a.W = dw; a.Cout = cout;
+        a.scale = dsc; a.shift = dsh; a.resid = dr; a.relu_out = relu_out != 0; a.out = dout;
+        if (!launch_conv_f16act(a, s)) rc = TMAT_E_ARG;
+        else if (!hip_ok(hipGetLastError(), "tmat_conv2d launch") || !hip_ok(hipMemcpyAsync(oq.data(), dout, no * 2, hipMemcpyDeviceToHost, s), "D2H")) rc = TMAT_E_HIP;
+    }
+    if (!hip_ok(hipStreamSynchronize(s), "sync") && !rc) rc = TMAT_E_HIP;      // also drains the uploads before their sources go out of scope
+    if (!rc)
+        for (size_t i = 0; i < no; i++) {
+            const _Float16 hv = __builtin_bit_cast(_Float16, oq[i]);
+            out[i] = (float)hv;
+        }
+    return rc;
+}
+
 int tmat_resnet_set_precision(tmat_handle hd, int mode)
 {
     Ctx *c = (Ctx *)hd;
-    if (!c || (mode != TMAT_RESNET_PRECISION_F32 && mode != TMAT_RESNET_PRECISION_F16)) {
-        set_error("tmat_resnet_set_precision: needs a handle and mode TMAT_RESNET_PRECISION_F32 or TMAT_RESNET_PRECISION_F16");
+    if (!c || (mode != TMAT_RESNET_PRECISION_F32 && mode != TMAT_RESNET_PRECISION_F16 && mode != TMAT_RESNET_PRECISION_F16ACT)) {
+        set_error("tmat_resnet_set_precision: needs a handle and mode TMAT_RESNET_PRECISION_F32, TMAT_RESNET_PRECISION_F16 or TMAT_RESNET_PRECISION_F16ACT");
         return TMAT_E_ARG;
     }
     TMAT_HIP(hipSetDevice(c->device));
     { const int rc = tmat_sync(hd); if (rc) return rc; }      // nothing in flight runs across the switch
-    if (mode == TMAT_RESNET_PRECISION_F16)
+    if (mode != TMAT_RESNET_PRECISION_F32)          // both 16-bit modes multiply the same f16 weight planes
         for (ResNetModel &m : c->resnets) if (!ensure_f16(m)) return TMAT_E_HIP;
     c->resnet_precision = mode;
     return TMAT_OK;
 }
 
 // Stage-wise test entry point: ONE launch_conv on host buffers.  x (n, hh, ww, cin); w in the Keras layout (ksize, ksize, cin, cout);
-// scale nullable (plain bias); resid nullable, (n, hh / stride, ww / stride, cout); out the same shape.  prec 0: f32, 3: f16 operands.
+// scale nullable (plain bias); resid nullable, (n, hh / stride, ww / stride, cout); out the same shape.  prec 0: f32, 3: f16 operands,
+// 4: the f16act convolution -- x (after the load-side ReLU, which commutes with the rounding) and resid rounded to f16 on the host, f16
+// device buffers, the f16 output widened to f32 on the host.
 int tmat_conv2d(tmat_handle hd, int prec, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int stride, int cout,
                 const float *scale, const float *shift, const float *resid, int relu_in, int relu_out, float *out)
 {
     Ctx *c = (Ctx *)hd;
-    if (!c || !x || !w || !shift || !out || (prec != 0 && prec != 3) || n < 1 || hh < 1 || ww < 1 || cin < 1 || cout < 1 || (ksize != 1 && ksize != 3) ||
+    if (!c || !x || !w || !shift || !out || (prec != 0 && prec != 3 && prec != 4) || n < 1 || hh < 1 || ww < 1 || cin < 1 || cout < 1 || (ksize != 1 && ksize != 3) ||
         (stride != 1 && stride != 2) || hh % stride || ww % stride) {
-        set_error("tmat_conv2d: bad argument (prec 0 or 3, ksize 1 or 3, stride 1 or 2)");
+        set_error("tmat_conv2d: bad argument (prec 0, 3 or 4, ksize 1 or 3, stride 1 or 2)");
         return TMAT_E_ARG;
     }
     TMAT_HIP(hipSetDevice(c->device));
@@ -366,7 +483,8 @@ int tmat_conv2d(tmat_handle hd, int prec, const float *x, int n, int hh, int ww,
     const size_t nx = (size_t)n * hh * ww * cin, nw = (size_t)ksize * ksize * cin * cout, no = (size_t)n * (hh / stride) * (ww / stride) * cout;
     const std::vector<float> wk = k_contiguous(w, ksize * ksize, cin, cout);
     std::vector<uint16_t> wq;
-    if (prec == 3) { wq.resize(nw); for (size_t i = 0; i < nw; i++) wq[i] = f16_rne_sat(wk[i]); }
+    if (prec >= 3) { wq.resize(nw); for (size_t i = 0; i < nw; i++) wq[i] = f16_rne_sat(wk[i]); }
+    if (prec == 4) return conv2d_f16act(c, x, nx, n, hh, ww, cin, wq, ksize, stride, cout, scale, shift, resid, no, relu_in, relu_out, out);
     float *dx = nullptr, *dsc = nullptr, *dsh = nullptr, *dr = nullptr;
     void *dw = nullptr;
     int rc = TMAT_OK;

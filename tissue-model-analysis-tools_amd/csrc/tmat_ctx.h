@@ -179,7 +179,7 @@ struct Ctx {
     bool fused_pool = true;                                  // max-pool + residual add fused behind the second separable convolution (TMAT_FUSED_POOL=0: separate kernel)
     bool norm_on = false;                                    // models.py:636-637 input normalisation in front of the smooth prediction (tmat_set_input_norm)
     float norm_mean = 0.f, norm_std = 1.f;
-    int resnet_precision = 0;                                // invasion-depth classifiers: TMAT_RESNET_PRECISION_F32 (bit-exact contract) or _F16 (opt-in, tmat_resnet_set_precision)
+    int resnet_precision = 0;                                // invasion-depth classifiers: TMAT_RESNET_PRECISION_F32 (bit-exact contract), _F16 or _F16ACT (opt-in, tmat_resnet_set_precision)
     int precision = 0;                                       // TMAT_PRECISION_F32 (bit-exact contract) or TMAT_PRECISION_BF16X3 / _BF16X6 (opt-in, tmat_set_precision)
     std::map<const float *, ConvWHost> conv_w_host;          // device pointer of every MFMA convolution weight tensor -> its host copy
     std::map<int, std::map<const float *, float *>> wsplit;  // precision mode -> (... -> its split-precision copy on the device, made on first use)
@@ -254,7 +254,7 @@ inline void *ws_get(Ctx *c, ToolWs slot, size_t bytes)
     return c->tool_ws[slot];
 }
 
-// TMAT_INV_DEPTH_PRECISION=f32|f16 at handle creation (resnet_kernels.hip): TMAT_OK, or TMAT_E_ARG with the error set for any other value
+// TMAT_INV_DEPTH_PRECISION=f32|f16|f16act at handle creation (resnet_kernels.hip): TMAT_OK, or TMAT_E_ARG with the error set for any other value
 int resnet_precision_from_env(Ctx *c);
 
 // handles made by tmat_create_plain carry no model

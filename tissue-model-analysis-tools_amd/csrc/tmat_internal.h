@@ -64,6 +64,22 @@ __device__ __forceinline__ bool roi_box_of(const RoiNone &, int, RoiBox &) { ret
 // returns false (and sets the error) on unsupported shapes; roi (nullable; stride 2 with the 1x1 form only: the rectangles are output
 // pixels): region form
 bool launch_conv(const ConvArgs &a, hipStream_t s, const RoiSegs *roi = nullptr);
+// Convolution with f16 activations in memory (conv_f16act_kernels.hip; the invasion-depth classifier's TMAT_RESNET_PRECISION_F16ACT):
+// in / resid / out NHWC IEEE binary16 bits, W the f16 plane [ksize*ksize][Cout][Cin], scale (nullable) / shift f32.  ksize 1 (stride 1
+// or 2) or 3 (stride 1), Cin and Cout multiples of 64.  Returns false (and sets the error) on unsupported shapes.
+struct ConvF16Args {
+    const uint16_t *in;
+    int N, h, w, Cin;
+    int ksize, stride;
+    const uint16_t *W;
+    int Cout;
+    const float *scale;
+    const float *shift;
+    const uint16_t *resid;   // nullable, shaped like out
+    int relu_out;
+    uint16_t *out;           // (N, h/stride, w/stride, Cout)
+};
+bool launch_conv_f16act(const ConvF16Args &a, hipStream_t s);
 // strips of the pooled separable convolution (floats): sepconv_ws_kernels.hip
 size_t sepconv_pool_scratch_floats(int N, int H, int W, int Cout);
 // fused SeparableConv2D, wave-specialised (sepconv_ws_kernels.hip): depthwise taps dw9 [9][Cin], pointwise pwk [Cout][Cin] (k contiguous);

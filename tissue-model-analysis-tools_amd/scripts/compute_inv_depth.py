@@ -39,12 +39,15 @@ def parse_inv_depth_args(argv=None):
     p.add_argument("--channel", type=int, default=None)
     p.add_argument("--time", type=int, default=None)
     p.add_argument("-c", "--config", type=str, default=DEFAULT_CONFIG_PATH)
-    p.add_argument("--precision", choices=("f32", "f16"), default="f32",
+    p.add_argument("--precision", choices=("f32", "f16", "f16act"), default="f32",
                    help="arithmetic of the classifiers' convolutions.  f32 (default): the bit-exact contract.  f16: operands rounded to IEEE f16, f32 "
                         "accumulation on the f16 matrix cores (faster).  Measured on synthetic ensembles of 3 members: the printed probability moves "
                         "by up to about 5e-4, so its 4th decimal differs from the f32 run on nearly every slice, and a slice whose probability lies within "
                         "that distance of the threshold can change its label (8 of 512 synthetic slices with means of 0.49 .. 0.54 did; none of 32 "
-                        "whose means lay 1e-3 or more away).  Unmeasured on fine-tuned checkpoints.")
+                        "whose means lay 1e-3 or more away).  f16act: the f16 mode with every activation tensor stored as IEEE f16 (half the memory "
+                        "traffic).  Measured on the same synthetic ensembles: a deviation of the f16 mode's size -- a member's probability moves by up "
+                        "to 1.6e-3 and the printed mean by up to about 4e-4 (32 slices, none of them changed its label) -- but not the f16 mode's "
+                        "numbers.  Both unmeasured on fine-tuned checkpoints.")
     args = p.parse_args(argv)
     for k, v in vars(args).items():
         if isinstance(v, str):

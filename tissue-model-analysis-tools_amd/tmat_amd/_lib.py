@@ -258,16 +258,18 @@ class Handle:
         check(lib().tmat_set_precision(self._h, modes[mode]), "tmat_set_precision")
 
     def resnet_set_precision(self, mode="f32"):
-        """arithmetic of the invasion-depth classifiers' convolutions: "f32" (bit-exact contract, default) or "f16" (opt-in: operands
-        rounded to IEEE f16, f32 accumulation on the f16 matrix cores; include/tmat.h:tmat_resnet_set_precision)"""
-        modes = {"f32": 0, "f16": 1}
+        """arithmetic of the invasion-depth classifiers' convolutions: "f32" (bit-exact contract, default), "f16" (opt-in: operands
+        rounded to IEEE f16, f32 accumulation on the f16 matrix cores) or "f16act" (opt-in: the f16 mode with every activation tensor
+        stored as IEEE f16; include/tmat.h:tmat_resnet_set_precision)"""
+        modes = {"f32": 0, "f16": 1, "f16act": 3}
         if mode not in modes:
             raise ValueError(f"precision must be one of {sorted(modes)}")
         check(lib().tmat_resnet_set_precision(self._h, modes[mode]), "tmat_resnet_set_precision")
 
     def conv2d(self, x, w, scale, shift, stride=1, resid=None, relu_in=False, relu_out=False, prec=0):
         """stage-wise test entry point (include/tmat.h:tmat_conv2d): one convolution of the MFMA kernel.  x (n, h, w, cin), w in the Keras
-        layout (k, k, cin, cout), scale (nullable) / shift (cout), resid (nullable) shaped like the result; prec 0 (f32) or 3 (f16 operands)"""
+        layout (k, k, cin, cout), scale (nullable) / shift (cout), resid (nullable) shaped like the result; prec 0 (f32), 3 (f16 operands) or
+        4 (one f16act convolution: x and resid rounded to f16, f16 buffers on the device, the f16 result widened)"""
         x = np.ascontiguousarray(x, np.float32)
         w = np.ascontiguousarray(w, np.float32)
         n, hh, ww, cin = x.shape

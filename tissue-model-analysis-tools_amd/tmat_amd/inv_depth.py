@@ -97,7 +97,7 @@ class InvDepthEnsemble:
     """the classifiers of compute_inv_depth.py:96-121 on one handle"""
 
     def __init__(self, handle: Handle, weight_sets, size: int = 256, precision: "str | None" = None):
-        """precision: "f32" (bit-exact contract) or "f16" (opt-in, see set_precision); None leaves the handle's mode as it is (f32 unless
+        """precision: "f32" (bit-exact contract), "f16" or "f16act" (opt-in, see set_precision); None leaves the handle's mode as it is (f32 unless
         TMAT_INV_DEPTH_PRECISION or an earlier set_precision chose otherwise)"""
         self.handle, self.size, self.ids = handle, int(size), []
         if precision is not None:
@@ -112,7 +112,8 @@ class InvDepthEnsemble:
     def set_precision(self, mode: str = "f32"):
         """arithmetic of the classifiers' convolutions for the calls that follow (a property of the HANDLE: every ensemble on it follows).
         "f16": operands rounded to IEEE f16, f32 accumulation on the f16 matrix cores -- not bit-exact with the f32 contract; on synthetic
-        ensembles the mean probability moves by a few 1e-4"""
+        ensembles the mean probability moves by a few 1e-4.  "f16act": the f16 mode with every activation tensor stored as
+        IEEE f16 (one more rounding per stored value; a deviation of the same size)"""
         self.handle.resnet_set_precision(mode)
 
     def predict(self, x: np.ndarray, model: int = 0) -> np.ndarray:

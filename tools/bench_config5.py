@@ -5,7 +5,7 @@ synthetic images, host buffers in (PCIe inclusive).  Prints two JSON lines in be
   * invasion depth: Z slices/s for 32-slice 512 x 512 stacks through 3 ResNet50(conv4_block6_out) classifiers at 256 x 256.
 cpu_baseline: the oracles (numpy / scikit-learn-equivalent EM; oracle/resnet.py through the C convolution) on a bounded sample.
 
-    python tools/bench_config5.py [--images 256] [--stacks 8] [--steps 3] [--no-cpu] [--precision f32|f16|both] [--skip-cell-area]
+    python tools/bench_config5.py [--images 256] [--stacks 8] [--steps 3] [--no-cpu] [--precision f32|f16|f16act|both|all] [--skip-cell-area]
 """
 import argparse
 import json
@@ -26,8 +26,9 @@ def main():
     ap.add_argument("--stacks", type=int, default=16, help="16 stacks x 32 slices = 512 images for the invasion-depth tool")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--precision", choices=("f32", "f16", "both"), default="f32",
-                    help="invasion-depth line(s): f32 (bit-exact contract), f16 (opt-in f16 matrix-core mode) or both; the f16 line carries its ratio and parity against the f32 result of the same run")
+    ap.add_argument("--precision", choices=("f32", "f16", "f16act", "both", "all"), default="f32",
+                    help="invasion-depth line(s): f32 (bit-exact contract), f16 (opt-in f16 matrix-core mode), f16act (opt-in: f16 mode with f16 activations in memory), "
+                         "both (f32 and f16) or all (the three); the f16 and f16act lines carry their ratio and parity against the f32 result of the same run")
     ap.add_argument("--skip-cell-area", action="store_true", help="only the invasion-depth line(s)")
     a = ap.parse_args()
     from tmat_amd import _lib, inv_depth, preprocessing, synth
@@ -80,7 +81,7 @@ def inv_depth_lines(a, h):
     nsl = a.stacks * 32
     flops = inv_depth.flops_per_slice(ws[0], 256) * 3 * nsl
     f32_line = f32_probs = None
-    for mode in (("f32", "f16") if a.precision == "both" else (a.precision,)):
+    for mode in {"both": ("f32", "f16"), "all": ("f32", "f16", "f16act")}.get(a.precision, (a.precision,)):
         ens.set_precision(mode)
         ens.predict_stack(stacks[0])                         # warm-up (and, in f16 mode, the f16 copy of the weights)
         t0 = time.perf_counter()
@@ -91,7 +92,7 @@ def inv_depth_lines(a, h):
         peak = 157.3 if mode == "f32" else 2516.6            # dense f32 / f16 matrix peak of one MI355X, TFLOP/s
         line = {"metric": "Z slices/sec through compute_inv_depth (3 x ResNet50 conv4_block6_out at 256x256)", "value": nsl / dt, "unit": "slices/s", "n_gpus": 1,
                 "steps": a.steps, "warmup": 1, "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                "dtype": "f32" if mode == "f32" else "f16 operands, f32 accumulate",
+                "dtype": {"f32": "f32", "f16": "f16 operands, f32 accumulate", "f16act": "f16 operands and activations, f32 accumulate"}[mode],
                 "data": "synthetic", "config": {"workload": f"{a.stacks} stacks of 32 x 512 x 512 u16, host buffers in, 4 stacks per call; 3 ensemble members, random-init weights",
                                                 "precision": mode},
                 "roofline": {"bound": "mfma", "achieved": flops / dt / 1e12, "peak": peak, "unit": "TFLOP/s", "frac": flops / dt / 1e12 / peak, "traffic": None,
@@ -108,7 +109,10 @@ def inv_depth_lines(a, h):
                 line["cpu_baseline"] = {"value": 4 / (c1 - c0), "unit": "slices/s", "cores": "all (OpenMP C convolution)", "kind": "port", "sample": "4 slices x 3 models through oracle/resnet.py"}
                 line["parity"] = bool(np.array_equal(probs[:4].view(np.uint32), ref.view(np.uint32)))
         else:
-            line["roofline"]["note"] += "; against the dense f16 peak -- the f32 activations (HBM traffic, A-tile DMA + LDS reads), not the matrix pipe, bound the f16 convolution (DESIGN 7c)"
+            if mode == "f16act":
+                line["roofline"]["note"] += "; against the dense f16 peak -- activations are f16 in HBM and in LDS (DESIGN 7c)"
+            else:
+                line["roofline"]["note"] += "; against the dense f16 peak -- the f32 activations (HBM traffic, A-tile DMA + LDS reads), not the matrix pipe, bound the f16 convolution (DESIGN 7c)"
             if f32_line is not None:                     # reported, pass or fail, as the UNet's "alt" block is: the mode is not bit-exact by contract
                 p16, p32 = np.concatenate(all_probs).astype(np.float64), f32_probs.astype(np.float64)
                 e16, e32 = inv_depth.ensemble_predictions(p16.astype(np.float32)), inv_depth.ensemble_predictions(f32_probs)
