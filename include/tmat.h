@@ -125,6 +125,37 @@ int tmat_well_threshold_f64(tmat_handle h, const double *img, int H, int W, uint
 int tmat_canny_mask(tmat_handle h, const uint8_t *mask, int H, int W, double sigma, uint8_t *edges);
 
 /*
+ * The superellipse fit of well detection on the device (csrc/wellfit_kernels.hip), for a batch of images.
+ *
+ * tmat_superellipse_table: the candidates of get_superellipse_hull (well_mask_generation.py:35-45) depend on (seed, num_iters) alone.
+ *   The host draws them once and uploads table (num_iters, 7) f64 = c_x, c_y, cos t, sin t, d s_a, d s_b, area per candidate, area by
+ *   the reference's expression (:79-82: 4 d^2 s_a s_b gamma(1 + 1/n)^2 / gamma(1 + 2/n), so it belongs to ONE exponent n: a caller with
+ *   images of several exponents uploads and searches once per exponent).  The table stays on the handle; the device evaluates no cos,
+ *   sin or gamma.
+ * tmat_superellipse_search replaces :47-91.  xy: the (x, y) f64 hull points of all images, concatenated; offs (n_imgs + 1): image i owns
+ *   the points offs[i] .. offs[i + 1] - 1, 1 to 1024 of them (more: TMAT_E_CAP); n_exp (n_imgs): the exponent per image, 1..64 (else
+ *   TMAT_E_ARG).  best[i]: index of the smallest-area candidate whose maximum over the image's points is certainly below 1, -1 when
+ *   there is none; equal areas resolve to the lowest index, as np.argmin does.  n == 2 (the reference squares, without rotation) is
+ *   bit-identical to numpy and decides every candidate.  For n != 2 the reference calls pow and the device multiplies n - 1 times (at
+ *   most (n - 1) 2^-53 relative per term), so a candidate is decided only when |max - 1| > 1e-12; the others come back in band_idx
+ *   (cap_band, 2) i32 as (image, candidate) pairs in ascending order, *n_band of them (more than cap_band: TMAT_E_CAP with *n_band set),
+ *   for the caller to evaluate with the reference's expression and to merge with best by (area, index).
+ * tmat_superellipse_masks replaces gen_superellipse_mask (:94-118) for n_masks masks of one shape.  params (n_masks, 6) f64 = c_x, c_y,
+ *   cos t, sin t, d s_a, d s_b; xs (H), ys (W): np.linspace(-1, 1, .) made by the host; out (n_masks, H, W) u8:
+ *   out[m, i, j] = |u|^n + |v|^n < 1 at x = xs[i], y = ys[j] (the orientation after the reference's swapaxes).  The same band rule per
+ *   pixel for n != 2: band_px (cap_band) i64 flat indices into out, ascending, which the caller patches.
+ * tmat_resize_nearest_u8: skimage resize(order=0) of n u8 images (n, H, W) -> (n, out_h, out_w), source index
+ *   floor((i + 0.5) n_in / n_out) in f64 (:209 takes the small-shape well mask to the image shape with it).
+ * Host buffers throughout.  A handle from tmat_create_plain is enough.
+ */
+int tmat_superellipse_table(tmat_handle h, const double *table, int num_iters);
+int tmat_superellipse_search(tmat_handle h, const double *xy, const int *offs, int n_imgs, const int *n_exp, int *best, int *band_idx,
+                             int cap_band, int *n_band);
+int tmat_superellipse_masks(tmat_handle h, const double *params, int n_masks, const int *n_exp, const double *xs, const double *ys, int H, int W,
+                            uint8_t *out, long long *band_px, int cap_band, int *n_band);
+int tmat_resize_nearest_u8(tmat_handle h, const uint8_t *in, int n, int H, int W, int out_h, int out_w, uint8_t *out);
+
+/*
  * transforms.filter_branch_seg_mask(mask, footprint, remove_isolated) (transforms.py:306-361) on the GPU for a batch of
  * uint8 masks: use_median 1 = footprint disk(2) (the default), 0 = footprint None (compute_branches.py:293).
  * mask, filtered (n, h, w) u8.  A handle from tmat_create_plain is enough.
@@ -269,6 +300,19 @@ int tmat_analyze_batch(tmat_handle h, const uint16_t *imgs, int n, int H, int W,
                        float graph_thresh_1, float graph_thresh_2, int smoothing_window_px,
                        int min_branch_length_px, int max_branch_length_px, int remove_isolated,
                        int64_t first_index, tmat_row *rows);
+
+/*
+ * tmat_analyze_batch with well masks: the --detect-well form of the 2-D branch (compute_branches.py:318-337, 359-361, 425) through the
+ * same two-stage pipeline.  well_masks (n, h, w) u8 host or NULL, (h, w) = (round(W ds_ratio), round(H ds_ratio)) the down-sampled
+ * shape: non-zero = inside the well.  They multiply the rescaled image in front of the network (:328, before the input normalisation)
+ * and the thresholded mask in front of filter_branch_seg_mask (:334); the centre-line weighting reads the unmasked prediction (:344).
+ * pruning_masks (n, fh, fw) u8 host or NULL, (fh, fw) = round((H, W) ds_width / W) the field shape: MorseGraph's pruning_mask per
+ * image (:359-361, :425).  With both NULL the rows are tmat_analyze_batch's.
+ */
+int tmat_analyze_batch_masked(tmat_handle h, const uint16_t *imgs, int n, int H, int W, double ds_ratio, int ds_width,
+                              float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
+                              int max_branch_length_px, int remove_isolated, int64_t first_index, const uint8_t *well_masks,
+                              const uint8_t *pruning_masks, tmat_row *rows);
 
 /*
  * tmat_analyze_batch / tmat_analyze_batch_dev "with tree": the same passes, the same rows bit for bit, and per image the tree overlay

@@ -28,6 +28,8 @@ namespace tmat {
 void launch_lanczos(const uint16_t *img, int n, int H, int W, int h, int w, const int *xi, const float *xc, const int *yi,
                     const float *yc, float *tmp, uint16_t *out, float sat, hipStream_t s);
 void launch_rescale01(const uint16_t *x, int n, size_t per, int *mn, int *mx, float *out, hipStream_t s);
+void launch_well_zero_f32(float *x, const uint8_t *well, size_t n, hipStream_t s);                             // wellfit_kernels.hip
+void launch_well_seg(const double *pred, const uint8_t *well, uint8_t *seg, size_t n, hipStream_t s);
 
 static int round_half_even(double v) { return (int)std::nearbyint(v); }
 
@@ -134,7 +136,9 @@ static bool tail_on_side_stream()
 static bool pre_on_side_stream(const Ctx *c, const TileGeom &g) { return c->pre_side && tail_on_side_stream() && g.tiles_per_img <= c->max_patches && c->patch_in2; }
 static float *patch_in_of(Ctx *c, int slot, const TileGeom &g) { return pre_on_side_stream(c, g) && (slot & 1) ? c->patch_in2 : c->patch_in; }
 // bg_keep (nullable, the "with tree" form only): the pass's down-sampled images are copied there, b.small itself is rewritten by the next pass
-static int enqueue_pre(Ctx *c, const uint16_t *imgs_dev, int k, int slot, const TileGeom &g, uint16_t *bg_keep = nullptr)
+// well (nullable, the masked form only): the pass's (k, h, w) well masks on the device -- img * well_mask (compute_branches.py:328) in front
+// of the normalisation, as predict() sees it; the pad minimum is taken after it
+static int enqueue_pre(Ctx *c, const uint16_t *imgs_dev, int k, int slot, const TileGeom &g, uint16_t *bg_keep = nullptr, const uint8_t *well = nullptr)
 {
     PassBuf &b = c->pass;
     const bool oversize = g.tiles_per_img > c->max_patches;
@@ -145,6 +149,7 @@ static int enqueue_pre(Ctx *c, const uint16_t *imgs_dev, int k, int slot, const 
     launch_lanczos(imgs_dev, k, b.H, b.W, b.h, b.w, b.xi, b.xc, b.yi, b.yc, b.tmp, b.small, c->input_sat, s);
     if (bg_keep) TMAT_HIP(hipMemcpyAsync(bg_keep, b.small, (size_t)k * b.h * b.w * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
     launch_rescale01(b.small, k, (size_t)b.h * b.w, b.mn, b.mx, b.x, s);
+    if (well) launch_well_zero_f32(b.x, well, (size_t)k * b.h * b.w, s);
     if (c->norm_on) launch_norm_f32(b.x, (size_t)k * b.h * b.w, c->norm_mean, c->norm_std, s);      // models.py:636-637
     float *mn = (float *)c->scratch, *mx = mn + k;
     launch_minmax_f32(b.x, k, (size_t)b.h * b.w, mn, mx, s);
@@ -173,7 +178,9 @@ static int enqueue_down(Ctx *c, int k, int slot, const TileGeom &g)
     c->down_pending[slot] = true;
     return TMAT_OK;
 }
-static int enqueue_back(Ctx *c, int k, int slot, const TileGeom &g)
+// well / seg (nullable, the masked form only): the mask filter starts from (pred > 0.5) & well (compute_branches.py:334), formed in seg;
+// b.pred stays unmasked -- the centre-line weighting reads it (:344)
+static int enqueue_back(Ctx *c, int k, int slot, const TileGeom &g, const uint8_t *well = nullptr, uint8_t *seg = nullptr)
 {
     PassBuf &b = c->pass;
     hipStream_t s = c->stream;
@@ -195,9 +202,14 @@ static int enqueue_back(Ctx *c, int k, int slot, const TileGeom &g)
     if (tail_side) { TMAT_HIP(hipEventRecord(c->ev_blend[slot], s)); c->blend_pending[slot] = true; }
     // binary morphology on the GPU: threshold, median, labelling, perimeter, thinning, fork test, EDT (remove_isolated=True
     // is filter_branch_seg_mask's default, compute_branches.py:337)
-    rc = filter_edt_dev(b.pred[slot], k, b.h, b.w, 1, b.morph_ws, b.filt[slot], b.dist[slot], s);
-    if (rc) return TMAT_E_HIP;
     const size_t npx = (size_t)k * b.h * b.w;
+    if (well) {
+        launch_well_seg(b.pred[slot], well, seg, npx, s);
+        rc = filter_mask_dev(nullptr, seg, k, b.h, b.w, 1, 1, b.morph_ws, b.filt[slot], b.dist[slot], s);
+    } else {
+        rc = filter_edt_dev(b.pred[slot], k, b.h, b.w, 1, b.morph_ws, b.filt[slot], b.dist[slot], s);
+    }
+    if (rc) return TMAT_E_HIP;
     if (thin_on_device(c)) {
         // the ordered thinning runs on the device too: the host only needs the foreground counts (for the permutations)
         if (thin_count_dev(b.filt[slot], k, b.h, b.w, b.nfg[slot], s)) return TMAT_E_HIP;
@@ -261,7 +273,9 @@ struct TreeJob {
     OverlaySeg *dseg; size_t seg_cap; float *dmm; int *doff; uint8_t *drgb;
 };
 
-static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_row *rows, PassJob *job, const TreeJob *tree = nullptr, int first_img = 0)
+// pruning (nullable, the masked form only): the pass's (k, fh, fw) u8 pruning masks on the host, MorseGraph's pruning_mask per image
+static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_row *rows, PassJob *job, const TreeJob *tree = nullptr, int first_img = 0,
+                          const uint8_t *pruning = nullptr)
 {
     PassBuf &b = c->pass;
     const int h = b.h, w = b.w;
@@ -317,8 +331,8 @@ static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_ro
                                        dmt_dev ? b.dmt_m_host[slot][i] : 0, V.data(), cap_v, E.data(), cap_e, &nv, &ne,
                                        sweep_dev ? b.dmt_kind_host[slot] + i * nE : nullptr, sweep_dev ? b.dmt_pers_host[slot] + i * nE : nullptr);
         if (!rc && !tree)
-            rc = tmat_morse_stats(V.data(), nv, E.data(), ne, gp.fh, gp.fw, gp.smooth, gp.min_len, gp.max_len, gp.remove_isolated, nullptr,
-                                  &rows[i].count, &rows[i].total_px, &rows[i].avg_px, nullptr, 0);
+            rc = tmat_morse_stats(V.data(), nv, E.data(), ne, gp.fh, gp.fw, gp.smooth, gp.min_len, gp.max_len, gp.remove_isolated,
+                                  pruning ? pruning + i * fper : nullptr, &rows[i].count, &rows[i].total_px, &rows[i].avg_px, nullptr, 0);
         if (!rc && tree) {
             const int cap_s = std::max(nv, 1);       // a forest has fewer edges than vertices
             tsegs[i].resize((size_t)cap_s * 4); tbranch[i].resize(cap_s);
@@ -357,9 +371,12 @@ static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_ro
 }
 
 struct TreeReq { int vis_width; uint8_t *rgb_out; double *bars_out; int cap_b; int *n_bars; };
+// The masked form of a call (tmat_analyze_batch_masked), both on the HOST and either may be null: well (n, h, w) u8 multiplies the
+// network input and the thresholded mask, pruning (n, fh, fw) u8 is MorseGraph's pruning mask
+struct MaskReq { const uint8_t *well; const uint8_t *pruning; };
 
 static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width, GraphParams gp,
-                       int64_t first_index, tmat_row *rows, const TreeReq *req = nullptr)
+                       int64_t first_index, tmat_row *rows, const TreeReq *req = nullptr, const MaskReq *masks = nullptr)
 {
     // compute_branches.py:309-312 hands target_shape = round(shape * ds_ratio) = (round(H r), round(W r)) to cv2.resize as
     // dsize, which cv2 reads as (width, height): the resized image has round(W r) rows and round(H r) columns.  Square
@@ -394,6 +411,18 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
         tree = &tj;
     }
     auto bg_at = [&](int p) { return tree ? const_cast<uint16_t *>(tj.bg_all) + (size_t)p * K * h * w : nullptr; };
+    // the well masks go up once per call, into a workspace of the handle; one seg buffer serves every pass (the tails share a stream)
+    const uint8_t *well_all = nullptr, *pruning = masks ? masks->pruning : nullptr;
+    uint8_t *seg = nullptr;
+    if (masks && masks->well) {
+        uint8_t *wd = (uint8_t *)ws_get(c, WS_WELL_MASK, (size_t)n * h * w);
+        seg = (uint8_t *)ws_get(c, WS_WELL_SEG, (size_t)K * h * w);
+        if (!wd || !seg) return TMAT_E_HIP;
+        if (!hip_ok(hipMemcpy(wd, masks->well, (size_t)n * h * w, hipMemcpyHostToDevice), "H2D(well masks)")) return TMAT_E_HIP;
+        well_all = wd;
+    }
+    auto well_at = [&](int p) { return well_all ? well_all + (size_t)p * K * h * w : nullptr; };
+    auto prune_at = [&](int p) { return pruning ? pruning + (size_t)p * K * gp.fh * gp.fw : nullptr; };
     const int P = (n + K - 1) / K;
     PassJob jobs[2];
     auto cnt = [&](int p) { return std::min(K, n - p * K); };
@@ -410,10 +439,10 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
     // (order of the calls = order on the second stream: the front end of pass p + 2 in front of the tail of pass p + 1, which only
     // starts when that pass's up path has ended)
     c->down_pending[0] = c->down_pending[1] = false;
-    rc = enqueue_pre(c, img_at(0), cnt(0), 0, g, bg_at(0));
+    rc = enqueue_pre(c, img_at(0), cnt(0), 0, g, bg_at(0), well_at(0));
     if (!rc) rc = enqueue_down(c, cnt(0), 0, g);
-    if (!rc && P > 1) rc = enqueue_pre(c, img_at(1), cnt(1), 1, g, bg_at(1));
-    if (!rc) rc = enqueue_back(c, cnt(0), 0, g);
+    if (!rc && P > 1) rc = enqueue_pre(c, img_at(1), cnt(1), 1, g, bg_at(1), well_at(1));
+    if (!rc) rc = enqueue_back(c, cnt(0), 0, g, well_at(0), seg);
     if (!rc && P > 1) rc = enqueue_down(c, cnt(1), 1, g);
     for (int p = 0; p < P && !rc; p++) {
         const int slot = p & 1;
@@ -424,12 +453,12 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
         if (trace_on())
             fprintf(stderr, "[tmat] pass %d/%d (%d images): waited %.1f ms for the GPU, %.1f ms for host jobs of the previous pass\n",
                     p + 1, P, cnt(p), (tw1 - tw0) * 1e3, (now_s() - tw1) * 1e3);
-        if (p + 2 < P && !rc) rc = enqueue_pre(c, img_at(p + 2), cnt(p + 2), slot, g, bg_at(p + 2));
-        if (p + 1 < P && !rc) rc = enqueue_back(c, cnt(p + 1), slot ^ 1, g);
+        if (p + 2 < P && !rc) rc = enqueue_pre(c, img_at(p + 2), cnt(p + 2), slot, g, bg_at(p + 2), well_at(p + 2));
+        if (p + 1 < P && !rc) rc = enqueue_back(c, cnt(p + 1), slot ^ 1, g, well_at(p + 1), seg);
         if (p + 2 < P && !rc) rc = enqueue_down(c, cnt(p + 2), slot, g);
         for (int i = 0; i < cnt(p) && !rc; i++)
             if (!c->pass.conv_host[slot][i]) { set_error("analyze: Zhang thinning did not converge within its launch budget"); rc = TMAT_E_HIP; }
-        if (!rc) jobs[slot].th = std::thread(run_pass_host, c, slot, cnt(p), gp, rows + (size_t)p * K, &jobs[slot], tree, p * K);
+        if (!rc) jobs[slot].th = std::thread(run_pass_host, c, slot, cnt(p), gp, rows + (size_t)p * K, &jobs[slot], tree, p * K, prune_at(p));
     }
     for (auto &j : jobs) { j.join(); if (j.rc && !rc) rc = j.rc; }
     hipStreamSynchronize(c->stream2);
@@ -765,6 +794,25 @@ int tmat_analyze_batch_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int 
     TMAT_HIP(hipSetDevice(c->device));
     GraphParams gp{0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated};
     return analyze_dev(c, imgs_dev, n, H, W, ds_ratio, ds_width, gp, first_index, rows);
+}
+
+int tmat_analyze_batch_masked(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, double ds_ratio, int ds_width,
+                              float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
+                              int max_branch_length_px, int remove_isolated, int64_t first_index, const uint8_t *well_masks,
+                              const uint8_t *pruning_masks, tmat_row *rows)
+{
+    Ctx *c = (Ctx *)hd;
+    if (c && !has_model(c)) { set_error("tmat_analyze_batch_masked: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
+    if (!c || !imgs || !rows || n < 0 || H < 1 || W < 1 || ds_width < 1) { set_error("tmat_analyze_batch_masked: bad argument"); return TMAT_E_ARG; }
+    if (n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    DevScope mem(c->ws_pool);
+    uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
+    if (!mem.ok) return TMAT_E_HIP;
+    if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) return TMAT_E_HIP;
+    GraphParams gp{0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated};
+    MaskReq mr{well_masks, pruning_masks};
+    return analyze_dev(c, dimg, n, H, W, ds_ratio, ds_width, gp, first_index, rows, nullptr, &mr);
 }
 
 int tmat_analyze_batch_tree_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width,

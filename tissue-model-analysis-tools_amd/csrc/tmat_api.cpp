@@ -774,6 +774,7 @@ void tmat_destroy(tmat_handle h)
     for (RoiEntry *e : c->roi_cache) { e->free_tabs(); if (e->order) hipFree(e->order); delete e; }
     if (c->win1d) hipFree(c->win1d);
     if (c->ma_table) hipFree(c->ma_table);
+    if (c->se_table) hipFree(c->se_table);
     for (void *p : c->tool_ws) if (p) hipFree(p);
     for (auto &b : c->ws_pool) hipFree(b.second);
     for (auto &g : c->gauss_dev) hipFree(g.second);

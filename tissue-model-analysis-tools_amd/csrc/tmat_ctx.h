@@ -118,6 +118,7 @@ enum ToolWs {
     WS_INV_IN, WS_INV_SMALL, WS_INV_TAB, WS_INV_MNMX, WS_INV_X, WS_INV_PROB, WS_INV_BUF0, WS_INV_BUF1, WS_INV_BUF2, WS_INV_BUF3,    // invasion depth
     WS_INV_COL,
     WS_TREE_BG, WS_TREE_SEG, WS_TREE_MM, WS_TREE_RGB,                                                                               // tree overlay
+    WS_WELL_MASK, WS_WELL_SEG,                                                                                                      // masked batch pipeline
     N_TOOL_WS
 };
 
@@ -174,6 +175,8 @@ struct Ctx {
     }
     bool thin_device = true;                                 // ordered medial-axis thinning on the device (TMAT_THIN_DEVICE=0: host threads)
     uint32_t *ma_table = nullptr;                            // its 512-entry decision table, 16 words
+    double *se_table = nullptr;                              // candidate table of the superellipse search, [se_iters][7] (wellfit_kernels.hip): a constant, like ma_table
+    int se_iters = 0;
     bool dmt_device = true;                                  // DMT key build + lower-star sort on the device (TMAT_DMT_DEVICE=0: host)
     bool dmt_sweep_device = true;                            // the two persistence sweeps on the device as well (TMAT_DMT_SWEEP_DEVICE=0: host threads)
     bool fused_pool = true;                                  // max-pool + residual add fused behind the second separable convolution (TMAT_FUSED_POOL=0: separate kernel)

@@ -394,16 +394,25 @@ def main(args=None):
             return rows
         if not detect_well:
             return branches.analyze_batch(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits)
+        warn_fn = lambda m: print(f"\033[93m[WARNING]\033[0m {m}", flush=True)       # noqa: E731
+        if not tree_vis:
+            # --detect-well through the batch pipeline (branches.analyze_batch_well): the masks do not depend on the graph thresholds --
+            # made once per batch (run_sharded hands the same array to every configuration of the grid), reused over the grid
+            if well_cache.get("batch") is not batch:
+                well_cache.clear()
+                well_cache["batch"] = batch
+            rows, well, pruning = branches.analyze_batch_well(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits,
+                                                              well_seed=well_seed, warn=warn_fn, masks=well_cache.get("masks"))
+            well_cache["masks"] = (well, pruning)
+            return rows
+        # with --tree-visualizations the pictures need the fields themselves: the staged entry points, image by image
         # --detect-well (compute_branches.py:318-337): the fields do not depend on the graph thresholds -- one staged pass per
         # batch (run_sharded hands the same array to every configuration of the grid), then the graph stages per configuration
         if well_cache.get("batch") is not batch:
             well_cache.clear()
             well_cache["batch"] = batch
             well_cache["fields"], well_cache["backgrounds"] = branches.well_fields(
-                model.handle, batch, model.ds_ratio, input_bits, well_seed, warn=lambda m: print(f"\033[93m[WARNING]\033[0m {m}", flush=True),
-                return_backgrounds=True)
-        if not tree_vis:
-            return branches.well_rows(model.handle, well_cache["fields"], config, width_um, thresh)
+                model.handle, batch, model.ds_ratio, input_bits, well_seed, warn=warn_fn, return_backgrounds=True)
         # the tree of each pruned graph over the image's own down-sampled picture; count, total and average come out of the same
         # call (tmat_morse_tree shares tmat_morse_stats' code), so the rows are well_rows' rows
         rows = []

@@ -21,6 +21,7 @@ class TmatError(RuntimeError):
     pass
 
 
+E_ARG = -1          # TMAT_E_ARG (include/tmat.h): bad argument / unsupported shape
 E_CAP = -4          # TMAT_E_CAP (include/tmat.h): a caller-provided output capacity is too small
 
 
@@ -106,6 +107,11 @@ def lib():
     L.tmat_well_threshold.argtypes = [vp, vp, i, i, vp]
     L.tmat_well_threshold_f64.argtypes = [vp, vp, i, i, vp]
     L.tmat_canny_mask.argtypes = [vp, vp, i, i, C.c_double, vp]
+    L.tmat_superellipse_table.argtypes = [vp, vp, i]
+    L.tmat_superellipse_search.argtypes = [vp, vp, vp, i, vp, vp, vp, i, C.POINTER(i)]
+    L.tmat_superellipse_masks.argtypes = [vp, vp, i, vp, vp, vp, i, i, vp, vp, i, C.POINTER(i)]
+    L.tmat_resize_nearest_u8.argtypes = [vp, vp, i, i, i, i, i, vp]
+    L.tmat_analyze_batch_masked.argtypes = [vp, vp, i, i, i, C.c_double, i, f, f, i, i, i, i, C.c_int64, vp, vp, vp]
     L.tmat_prof_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), i]
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -121,7 +127,8 @@ EXPORTS = [
     "tmat_dmt_graph", "tmat_dmt_graph_batch", "tmat_morse_stats",
     "tmat_morse_tree", "tmat_branch_color", "tmat_render_tree", "tmat_render_tree_timed", "tmat_host_render_tree", "tmat_host_render_barcode",
     "tmat_analyze_batch_dev", "tmat_analyze_batch", "tmat_analyze_batch_tree_dev", "tmat_analyze_batch_tree", "tmat_dev_alloc", "tmat_dev_free", "tmat_dev_upload", "tmat_dev_download",
-    "tmat_prof_enable", "tmat_prof_read", "tmat_debug_poison", "tmat_debug_held_bytes", "tmat_set_precision", "tmat_set_input_norm", "tmat_preprocess_batch", "tmat_well_threshold", "tmat_well_threshold_f64", "tmat_canny_mask", "tmat_host_lanczos4_u16", "tmat_host_rescale01_u16",
+    "tmat_prof_enable", "tmat_prof_read", "tmat_debug_poison", "tmat_debug_held_bytes", "tmat_set_precision", "tmat_set_input_norm", "tmat_preprocess_batch", "tmat_well_threshold", "tmat_well_threshold_f64", "tmat_canny_mask", "tmat_superellipse_table", "tmat_superellipse_search",
+    "tmat_superellipse_masks", "tmat_resize_nearest_u8", "tmat_analyze_batch_masked", "tmat_host_lanczos4_u16", "tmat_host_rescale01_u16",
     "tmat_host_rescale255_f32", "tmat_host_filter_mask", "tmat_host_skeletonize", "tmat_host_medial_axis",
     "tmat_host_permutation", "tmat_host_postprocess",
     "tmat_set_gaussian_table", "tmat_host_gaussian_kernel1d", "tmat_gaussian_f32", "tmat_sato_batch", "tmat_stack_prepare", "tmat_vessel_field",

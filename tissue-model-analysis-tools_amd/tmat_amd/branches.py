@@ -178,6 +178,61 @@ def well_rows(handle: _lib.Handle, fields, config: dict, image_width_microns: fl
     return rows
 
 
+def analyze_batch_masked(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_width_microns: float, ds_ratio: float = 0.625,
+                         thresh=(5.0, 10.0), first_index: int = 0, input_bits: int = 16, well_masks=None, pruning_masks=None):
+    """analyze_batch with well masks (tmat_analyze_batch_masked): well_masks (n, h, w) over the down-sampled images, (h, w) =
+    (round(W ds_ratio), round(H ds_ratio)), multiply the network input and the thresholded mask; pruning_masks (n, fh, fw) over the
+    fields, (fh, fw) = dsamp_shape((H, W)), prune the graphs.  Either may be None; with both None the rows are analyze_batch's."""
+    imgs = np.ascontiguousarray(imgs, np.uint16)
+    n, H, W = imgs.shape
+    hh, ww = int(round(W * ds_ratio)), int(round(H * ds_ratio))            # cv2 reads dsize as (width, height)
+    fshape = dsamp_shape((H, W))
+
+    def as_u8(m, shape, what):
+        if m is None:
+            return None
+        m = np.asarray(m)
+        if m.shape != (n,) + tuple(shape):
+            raise ValueError(f"analyze_batch_masked: {what} have shape {m.shape}, expected {(n,) + tuple(shape)}")
+        return np.ascontiguousarray(m != 0, np.uint8)
+    well = as_u8(well_masks, (hh, ww), "well_masks")
+    pruning = as_u8(pruning_masks, fshape, "pruning_masks")
+    sw_px, min_px, max_px = graph_px_params(config, DOWNSAMPLE_WIDTH, image_width_microns)
+    rows = (_lib.Row * n)()
+    L = _lib.lib()
+    _lib.check(L.tmat_set_input_depth(handle.raw, int(input_bits)), "tmat_set_input_depth")
+    _lib.check(L.tmat_analyze_batch_masked(handle.raw, _lib.ptr(imgs), n, H, W, float(ds_ratio), DOWNSAMPLE_WIDTH, float(thresh[0]), float(thresh[1]),
+                                           int(sw_px), int(min_px), int(max_px or 0), int(bool(config.get("remove_isolated_branches", False))),
+                                           int(first_index), None if well is None else _lib.ptr(well), None if pruning is None else _lib.ptr(pruning),
+                                           rows), "tmat_analyze_batch_masked")
+    return [(r.index, r.count, r.total_px, r.avg_px) for r in rows]
+
+
+def analyze_batch_well(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_width_microns: float, ds_ratio: float = 0.625,
+                       thresh=(5.0, 10.0), first_index: int = 0, input_bits: int = 16, well_seed: int = 0, warn=print, masks=None):
+    """The --detect-well form of the 2-D branch through the batch pipeline: the rows of well_fields + well_rows.  Lanczos + rescale
+    (tmat_preprocess_batch) -> make_well_masks_batch on those images (the superellipse fit of the whole batch on the device) ->
+    pruning masks = resize(~shrunken, field shape, order 0) (compute_branches.py:359-361) -> tmat_analyze_batch_masked, which repeats
+    the Lanczos pass inside its pipeline.  masks: a (well, pruning) pair from an earlier call on the same images (the masks do not depend
+    on the graph thresholds).  Returns (rows, well (n, h, w) bool, pruning (n, fh, fw) bool)."""
+    from . import well_mask_generation as wmg
+    imgs = np.ascontiguousarray(imgs, np.uint16)
+    n, H, W = imgs.shape
+    if masks is None:
+        hh, ww = int(round(W * ds_ratio)), int(round(H * ds_ratio))        # cv2 reads dsize as (width, height)
+        L = _lib.lib()
+        x = np.empty((n, hh, ww), np.float32)
+        _lib.check(L.tmat_set_input_depth(handle.raw, int(input_bits)), "tmat_set_input_depth")
+        _lib.check(L.tmat_preprocess_batch(handle.raw, _lib.ptr(imgs), n, H, W, float(ds_ratio), _lib.ptr(x)), "tmat_preprocess_batch")
+        well, shrunken = wmg.make_well_masks_batch(x, handle, seed=well_seed, warn=warn)
+        fshape = dsamp_shape((H, W))
+        pruning = np.stack([wmg._resize_nearest(np.logical_not(shrunken[i]), fshape) for i in range(n)]).astype(bool)
+    else:
+        well, pruning = masks
+    rows = analyze_batch_masked(handle, imgs, config, image_width_microns, ds_ratio, thresh, first_index, input_bits, well, pruning)
+    return rows, well, pruning
+
+
 def field_tree(handle, field255: np.ndarray, config: dict, image_width_microns: float, thresh=(5.0, 10.0), pruning_mask=None,
                scaling_factor: float = 1.0):
     """The colored tree of one 0..255 field (compute_branches.py:401-426 + topology.py:358-389): DMT graph, MorseGraph with the pruning mask

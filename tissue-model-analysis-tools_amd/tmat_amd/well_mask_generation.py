@@ -11,6 +11,11 @@ The reference draws its 25 000 candidates from the GLOBAL numpy generator and ne
 reference give different masks.  Here the draw is `numpy.random.RandomState(seed).rand(num_iters, 6)` with an explicit `seed`
 (scripts: --well-seed, default 0): the same stream the reference consumes after `numpy.random.seed(seed)`.
 
+Batched form (`make_well_masks_batch`, used by branches.analyze_batch_well): the per-image steps above stay as they are; the random
+search (tmat_superellipse_search: one thread per candidate, all images of the batch in one launch) and the two superellipse
+rasterisations with the nearest resize (tmat_superellipse_masks, tmat_resize_nearest_u8) run on the GPU once per batch.  The device
+decides a candidate / pixel only when it is certain (include/tmat.h); the rest is evaluated here with the reference's expression.
+
 scikit-image version note (reference pins 0.22.0): `rescale` / `resize` with order 0 follow scipy.ndimage.zoom(order=0,
 grid_mode=True), i.e. source index floor((i + 0.5) * n_in / n_out); canny follows the 0.18.3 source (magnitude by hypot).
 """
@@ -207,3 +212,219 @@ def _erode_disk5(mask: np.ndarray) -> np.ndarray:
             if dy * dy + dx * dx <= 25:
                 out &= pad[5 + dy:5 + dy + H, 5 + dx:5 + dx + W]
     return out
+
+
+# ---- batched form: the superellipse fit on the device (csrc/wellfit_kernels.hip) ----------------------------------------------------
+
+_CANDIDATES = {}
+
+
+def superellipse_candidates(seed: int = 0, num_iters: int = 25000) -> dict:
+    """The random candidates of get_superellipse_hull (:35-45) for (seed, num_iters), drawn once: t, d, s_a, s_b, c_x, c_y as the
+    (num_iters, 1) views the reference evaluates, and cos t, sin t, d * s_a, d * s_b from the reference's own numpy calls on them"""
+    key = (int(seed), int(num_iters))
+    if key not in _CANDIDATES:
+        linear_weights = np.random.RandomState(seed).rand(num_iters, 6)
+        param_values = (SUPERELLIPSE_BOUNDS[:, 1] - SUPERELLIPSE_BOUNDS[:, 0]) * linear_weights + SUPERELLIPSE_BOUNDS[:, 0]
+        t, d, s_a, s_b, c_x, c_y = param_values.T[..., np.newaxis]
+        _CANDIDATES.clear()                              # one draw is kept: a run uses one seed
+        _CANDIDATES[key] = dict(t=t, d=d, s_a=s_a, s_b=s_b, c_x=c_x, c_y=c_y, cos=np.cos(t), sin=np.sin(t), da=d * s_a, db=d * s_b)
+    return _CANDIDATES[key]
+
+
+def superellipse_area(cand: dict, n: int) -> np.ndarray:
+    """(num_iters,) areas by the reference's expression (:79-82), gamma factor of exponent n included"""
+    n = int(n)
+    d, s_a, s_b = cand["d"], cand["s_a"], cand["s_b"]
+    return np.ascontiguousarray((4 * d ** 2 * s_a * s_b * _gamma(1 + 1 / n) ** 2 / _gamma(1 + 2 / n))[:, 0])
+
+
+def superellipse_table(n: int, seed: int = 0, num_iters: int = 25000) -> np.ndarray:
+    """(num_iters, 7) f64 table of tmat_superellipse_table: c_x, c_y, cos t, sin t, d s_a, d s_b, area (for exponent n)"""
+    c = superellipse_candidates(seed, num_iters)
+    cols = [c["c_x"][:, 0], c["c_y"][:, 0], c["cos"][:, 0], c["sin"][:, 0], c["da"][:, 0], c["db"][:, 0], superellipse_area(c, n)]
+    return np.ascontiguousarray(np.stack(cols, axis=1), np.float64)
+
+
+def _reference_max(cand: dict, rows, x, y, n: int) -> np.ndarray:
+    """max over the points of the reference's value (:47-72) for the candidates `rows` only"""
+    rows = np.asarray(rows, np.int64)
+    c_x, c_y, da, db = (cand[k][rows] for k in ("c_x", "c_y", "da", "db"))
+    cos, sin = cand["cos"][rows], cand["sin"][rows]
+    if n == 2:
+        val = ((x - c_x) / da) ** 2 + ((y - c_y) / db) ** 2
+    elif n % 2 == 0:
+        val = ((((x - c_x) * cos - ((y - c_y) * sin)) / da) ** n + (((x - c_x) * sin + (y - c_y) * cos) / db) ** n)
+    else:
+        val = (np.abs(((x - c_x) * cos - ((y - c_y) * sin)) / da) ** n + np.abs(((x - c_x) * sin + (y - c_y) * cos) / db) ** n)
+    return np.max(val, axis=1)
+
+
+def merge_band(best: int, accepted, area: np.ndarray) -> int:
+    """The candidate np.argmin would return: the lowest (area, index) among the device's `best` (-1: none) and the banded candidates
+    the host accepted.  ValueError when there is none (the reference's np.argmin of an empty sequence)."""
+    pool = sorted({int(j) for j in accepted} | ({int(best)} if best >= 0 else set()))
+    if not pool:
+        raise ValueError("attempt to get argmin of an empty sequence")
+    return min(pool, key=lambda j: (area[j], j))
+
+
+def superellipse_search_raw(handle: _lib.Handle, points, n_exps, cap_band: int = 4096):
+    """tmat_superellipse_search on the table the handle holds: points = [(x, y)] per image -> (best (n_imgs,) i32, band (k, 2) i32)"""
+    offs = np.zeros(len(points) + 1, np.int32)
+    offs[1:] = np.cumsum([len(p[0]) for p in points])
+    xy = np.ascontiguousarray(np.concatenate([np.stack([np.asarray(p[0], np.float64), np.asarray(p[1], np.float64)], axis=1) for p in points]))
+    n_exp = np.ascontiguousarray(n_exps, np.int32)
+    best = np.full(len(points), -2, np.int32)
+    import ctypes as C
+    L = _lib.lib()
+    while True:
+        band = np.zeros((max(cap_band, 1), 2), np.int32)
+        n_band = C.c_int(0)
+        rc = L.tmat_superellipse_search(handle.raw, _lib.ptr(xy), _lib.ptr(offs), len(points), _lib.ptr(n_exp), _lib.ptr(best), _lib.ptr(band),
+                                        int(cap_band), C.byref(n_band))
+        if rc == _lib.E_CAP and n_band.value > cap_band:            # the band list was too short: once more with what it needs
+            cap_band = n_band.value
+            continue
+        _lib.check(rc, "tmat_superellipse_search")
+        return best, band[: n_band.value].copy()
+
+
+def superellipse_search_batch(handle: _lib.Handle, points, n_exps, seed: int = 0, num_iters: int = 25000):
+    """get_superellipse_hull for a batch: points = [(x, y)] per image, n_exps = the exponent per image -> per image
+    (t, d, s_a, s_b, c_x, c_y), or None where no candidate encloses the points.  One table upload and one search per distinct exponent
+    (the area carries the exponent's gamma factor)."""
+    cand = superellipse_candidates(seed, num_iters)
+    out = [None] * len(points)
+    L = _lib.lib()
+    for n in sorted({int(v) for v in n_exps}):
+        idx = [i for i, v in enumerate(n_exps) if int(v) == n]
+        key = (int(seed), int(num_iters), n)
+        table = None
+        if getattr(handle, "_se_table_key", None) != key:
+            table = superellipse_table(n, seed, num_iters)
+            _lib.check(L.tmat_superellipse_table(handle.raw, _lib.ptr(table), int(num_iters)), "tmat_superellipse_table")
+            handle._se_table_key = key
+        area = superellipse_area(cand, n) if table is None else table[:, 6]
+        best, band = superellipse_search_raw(handle, [points[i] for i in idx], [n] * len(idx))
+        for k, i in enumerate(idx):
+            rows = band[band[:, 0] == k, 1]
+            accepted = rows[_reference_max(cand, rows, points[i][0], points[i][1], n) < 1] if len(rows) else []
+            try:
+                j = merge_band(int(best[k]), accepted, area)
+            except ValueError:
+                continue
+            out[i] = tuple(cand[q][j][0] for q in ("t", "d", "s_a", "s_b", "c_x", "c_y"))
+    return out
+
+
+def get_superellipse_hull_dev(x, y, n, handle: _lib.Handle, num_iters: int = 25000, seed: int = 0):
+    """get_superellipse_hull with the search on the device; raises ValueError when no candidate encloses the points"""
+    res = superellipse_search_batch(handle, [(x, y)], [n], seed, num_iters)[0]
+    if res is None:
+        raise ValueError("attempt to get argmin of an empty sequence")
+    return res
+
+
+def gen_superellipse_masks_dev(handle: _lib.Handle, params, n_exps, shape, cap_band: int = 4096, return_band: bool = False):
+    """gen_superellipse_mask for a batch of one shape on the device: params = [(t, d, s_a, s_b, c_x, c_y)], n_exps = the exponent per
+    mask -> (len(params), shape[0], shape[1]) bool.  A mask with a pixel the device leaves undecided is evaluated again with the
+    reference's expression on the reference's arrays.  return_band: also return the flat indices of those pixels."""
+    import ctypes as C
+    m = len(params)
+    H, W = int(shape[0]), int(shape[1])
+    out = np.zeros((m, H, W), np.uint8)
+    if m == 0:
+        return (out.astype(bool), np.zeros(0, np.int64)) if return_band else out.astype(bool)
+    par = np.ascontiguousarray([[c_x, c_y, np.cos(t), np.sin(t), d * s_a, d * s_b] for t, d, s_a, s_b, c_x, c_y in params], np.float64)
+    n_exp = np.ascontiguousarray(n_exps, np.int32)
+    xs, ys = np.linspace(-1, 1, H), np.linspace(-1, 1, W)
+    L = _lib.lib()
+    while True:
+        band = np.zeros(max(cap_band, 1), np.int64)
+        n_band = C.c_int(0)
+        rc = L.tmat_superellipse_masks(handle.raw, _lib.ptr(par), m, _lib.ptr(n_exp), _lib.ptr(xs), _lib.ptr(ys), H, W, _lib.ptr(out), _lib.ptr(band),
+                                       int(cap_band), C.byref(n_band))
+        if rc == _lib.E_CAP and n_band.value > cap_band:
+            cap_band = n_band.value
+            continue
+        _lib.check(rc, "tmat_superellipse_masks")
+        break
+    out = out.astype(bool)
+    for k in sorted({int(v) // (H * W) for v in band[: n_band.value]}):
+        out[k] = gen_superellipse_mask(*params[k], int(n_exps[k]), (H, W))
+    return (out, band[: n_band.value].copy()) if return_band else out
+
+
+def resize_nearest_dev(handle: _lib.Handle, masks: np.ndarray, shape) -> np.ndarray:
+    """_resize_nearest of a batch of masks (n, H, W) on the device -> (n, shape[0], shape[1]) u8"""
+    a = np.ascontiguousarray(masks, np.uint8)
+    out = np.empty((a.shape[0], int(shape[0]), int(shape[1])), np.uint8)
+    _lib.check(_lib.lib().tmat_resize_nearest_u8(handle.raw, _lib.ptr(a), a.shape[0], a.shape[1], a.shape[2], out.shape[1], out.shape[2], _lib.ptr(out)),
+               "tmat_resize_nearest_u8")
+    return out
+
+
+def make_well_masks_batch(x, handle: _lib.Handle, seed: int = 0, warn=print):
+    """make_well_mask for a batch of images of one shape: x (n, h, w), or a sequence of n (h, w) images (their dtypes may differ) ->
+    (well (n, h, w) bool, shrunken (n, h, w) bool), equal to [make_well_mask(x[i]) for i].  Per image: threshold, nearest rescale, canny twice, convex hull, hull mask, the choice of the
+    exponent (generate_well_mask up to :187); then one superellipse search, one rasterisation + resize of the well masks and one
+    rasterisation of the shrunken masks for the whole batch."""
+    from scipy.spatial import ConvexHull
+    try:
+        from scipy.spatial import QhullError
+    except ImportError:                                     # older scipy
+        from scipy.spatial.qhull import QhullError
+    x = [np.asarray(im) for im in x]
+    if any(im.ndim != 2 or im.shape != x[0].shape for im in x):
+        raise ValueError("make_well_masks_batch: 2-D images of one shape expected")
+    if not x:
+        return np.zeros((0, 0, 0), bool), np.zeros((0, 0, 0), bool)
+    n_img, shape = len(x), x[0].shape
+    hulls = {}                                              # image -> (small hull mask, exponent, (x, y) of the hull vertices)
+    small_shape = None
+    for i in range(n_img):
+        im_thresh = auto_threshold_well(x[i], handle)
+        downsamp_ratio = min(1, 200 / np.max(im_thresh.shape))
+        small_shape = tuple(int(v) for v in np.round(np.asarray(im_thresh.shape) * downsamp_ratio))
+        im_thresh = _resize_nearest(im_thresh, small_shape)
+        border_points = np.argwhere(_border(handle, im_thresh))
+        try:
+            hull = ConvexHull(border_points)
+        except (ValueError, QhullError):
+            continue
+        hull_vertices = border_points[hull.vertices]
+        hull_mask = create_convex_hull_mask(im_thresh.shape, hull_vertices)
+        n = 8 if np.sum(_border(handle, hull_mask)) / np.sum(hull_mask) > .027 else 2
+        hulls[i] = (hull_mask, n, (hull_vertices[:, 0] / im_thresh.shape[0] * 2 - 1, hull_vertices[:, 1] / im_thresh.shape[1] * 2 - 1))
+    order = sorted(hulls)
+    fits = dict(zip(order, superellipse_search_batch(handle, [hulls[i][2] for i in order], [hulls[i][1] for i in order], seed))) if order else {}
+    found = [i for i in order if fits[i] is not None]
+    for i in order:
+        if fits[i] is None:
+            print("Falling back to convex hull well mask.", flush=True)
+    # generate_well_mask: d *= 0.9, the mask at the small shape, resized; make_well_mask: d *= 0.9 once more, at the image shape
+    p_well = [(t, d * 0.9, s_a, s_b, c_x, c_y) for t, d, s_a, s_b, c_x, c_y in (fits[i] for i in found)]
+    p_shrunk = [(t, d * 0.9, s_a, s_b, c_x, c_y) for t, d, s_a, s_b, c_x, c_y in p_well]
+    n_found = [hulls[i][1] for i in found]
+    small = {i: hulls[i][0] for i in order}
+    if found:
+        small.update(zip(found, gen_superellipse_masks_dev(handle, p_well, n_found, small_shape)))
+    well = np.zeros((n_img,) + tuple(shape), bool)
+    if order:
+        well[order] = resize_nearest_dev(handle, np.stack([small[i] for i in order]), shape) > 0
+    shrunken = np.zeros_like(well)
+    if found:
+        shrunken[found] = gen_superellipse_masks_dev(handle, p_shrunk, n_found, shape)
+    for i in range(n_img):
+        if i not in hulls:                                  # get_circ_mask (:172-182)
+            rr, cc = np.indices(shape)
+            well[i] = (rr - shape[0] // 2) ** 2 + (cc - shape[1] // 2) ** 2 < int(shape[0] * 0.5 * (1 - 0.95)) ** 2
+        if i not in found:
+            shrunken[i] = _erode_disk5(well[i])
+        coverage = np.sum(well[i]) / well[i].size
+        if coverage < 0.4:
+            warn(f"Well mask coverage is too low ({coverage * 100:.2f}%) so it will not be used for analysis.")
+            well[i] = True
+            shrunken[i] = True
+    return well, shrunken
