@@ -57,6 +57,67 @@ def test_call_scoped_entry_points_retain_nothing():
         h.close()
 
 
+def _tool_inputs():
+    """the smallest inputs the tool entry points accept that still take every branch of their staging"""
+    rs = np.random.RandomState(11)
+    well = rs.uniform(0.0, 0.2, (24, 20)).astype(np.float32)
+    well[5:19, 4:16] += 0.6                                              # a bright well on a dark plate
+    mask = np.zeros((24, 20), np.uint8)
+    mask[6:18, 5:15] = 1
+    cells = rs.randint(200, 900, (2, 32, 32)).astype(np.uint16)
+    cells[:, 8:20, 10:26] += rs.randint(3000, 9000, (2, 12, 16)).astype(np.uint16)
+    cmask = np.zeros((2, 32, 32), np.uint8)
+    cmask[:, 4:28, 3:29] = 1
+    return dict(g2=rs.uniform(0, 1, (24, 20)).astype(np.float32), g3=rs.uniform(0, 1, (3, 24, 20)).astype(np.float32), well=well, mask=mask,
+                masks=np.stack([mask, 1 - mask]), stacks=rs.randint(0, 65536, (2, 3, 16, 16)).astype(np.uint16),
+                x=rs.uniform(-1, 1, (1, 8, 8, 64)).astype(np.float32), w=(rs.uniform(-1, 1, (3, 3, 64, 64)) / 24).astype(np.float32),
+                scale=rs.uniform(0.5, 1.5, 64).astype(np.float32), shift=rs.uniform(-0.1, 0.1, 64).astype(np.float32),
+                resid=rs.uniform(-1, 1, (1, 8, 8, 64)).astype(np.float32), cells=cells, cmask=cmask)
+
+
+SE_PARAMS = [(0.11, 0.81, 1.04, 0.93, 0.17, -0.12), (-0.14, 0.7, 0.95, 1.08, -0.21, 0.09), (0.0, 1.3, 1.1, 1.1, 0.0, 0.0)]
+
+
+def _tool_round(h, t):
+    """the converted entry points _round does not reach, once each; all outputs as bytes"""
+    from tmat_amd import _lib, preprocessing, sato
+    from tmat_amd import well_mask_generation as wm
+    out = [sato.gaussian(h, t["g2"]), sato.gaussian(h, t["g3"])]                                   # two and three passes
+    out += [wm.auto_threshold_well(t["well"], h), wm.auto_threshold_well(t["well"].astype(np.float64), h), wm._border(h, t["mask"])]
+    out += [wm.resize_nearest_dev(h, t["masks"], (12, 10))]
+    out += [h.zproj(t["stacks"], "fs"), h.zproj(t["stacks"], "avg")]                               # u16 and f64 output
+    out += [h.conv2d(t["x"], t["w"], t["scale"], t["shift"], resid=t["resid"], relu_out=True, prec=p) for p in (0, 3, 4)]
+    masks, band = wm.gen_superellipse_masks_dev(h, SE_PARAMS, [2] * 3, (7, 5), return_band=True)
+    out += [masks, band]
+    # a superellipse through grid points of the 5-point linspace: four undecided pixels, so the band comes back as well
+    out += list(wm.gen_superellipse_masks_dev(h, [(0.0, 0.5, 1.0, 1.0, 0.0, 0.0)], [8], (5, 5), return_band=True))
+    out += list(preprocessing.cell_area_batch(h, t["cells"], 16, 0.0, return_params=True))         # resized, thresholded and params
+    area, thr, par = np.empty(2, np.float64), np.empty((2, 32, 32), np.uint8), np.empty((2, 9), np.float64)
+    _lib.check(_lib.lib().tmat_cell_area_masked(h.raw, _lib.ptr(t["cells"]), _lib.ptr(t["cmask"]), 2, 32, 32, 0.0, _lib.ptr(area), _lib.ptr(thr),
+                                                _lib.ptr(par)), "tmat_cell_area_masked")          # the host-built init table
+    out += [area, thr, par]
+    return [np.ascontiguousarray(a).tobytes() for a in out]
+
+
+def test_tool_entry_points_retain_nothing():
+    """gaussian, well threshold (f32 / f64), canny, nearest resize, Z projection, conv2d (prec 0 / 3 / 4), superellipse masks and cell
+    area (plain and masked) twice on a plain handle: held bytes after the second round equal those after the first, and the two rounds'
+    outputs are byte-identical"""
+    from tmat_amd import _lib
+    t = _tool_inputs()
+    h = _lib.Handle(None)
+    try:
+        first = _tool_round(h, t)
+        held1 = h.debug_held_bytes()
+        second = _tool_round(h, t)
+        held2 = h.debug_held_bytes()
+        print("held after round 1 / 2 (device, pinned):", held1, held2)
+        assert held2 == held1
+        assert second == first
+    finally:
+        h.close()
+
+
 def test_new_geometry_releases_the_old_pass_buffers(weights):
     """patch 64, max_patches 8: two identical analyze_batch calls on 2 images of 128 x 128 hold the same bytes and give the same rows;
     after one call on 128 x 192 the handle holds what a fresh handle that only ever saw 128 x 192 holds -- pinned bytes, and the device

@@ -325,8 +325,6 @@ using namespace tmat;
 static int cell_area_impl(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, int out_h, int out_w, double sd_coef, double *area,
                           uint8_t *thresholded, double *params, const uint8_t *masks, uint16_t *small_out, int fit)
 {
-    uint8_t *dmaskbuf = nullptr;
-    int *lohibuf = nullptr;
     if (!hd || !imgs || !area || n < 0 || H < 1 || W < 1 || out_h < 0 || out_w < 0 || (out_h == 0) != (out_w == 0)) {
         set_error("tmat_cell_area_batch: bad argument");
         return TMAT_E_ARG;
@@ -337,68 +335,57 @@ static int cell_area_impl(tmat_handle hd, const uint16_t *imgs, int n, int H, in
     hipStream_t s = c->stream;
     const int oh = out_h ? out_h : H, ow = out_w ? out_w : W;
     const size_t nin = (size_t)n * H * W, nout = (size_t)n * oh * ow;
-    uint16_t *din = nullptr, *dsm = nullptr;
-    unsigned *hist = nullptr, *kept = nullptr;
-    double *dpar = nullptr;
-    uint8_t *dthr = nullptr;
-    int *itab = nullptr;
-    int rc = TMAT_OK;
-    auto fail = [&](int code) { rc = code; };
-    // workspaces live on the handle between calls (tmat_ctx.h:ws_get)
-    din = (uint16_t *)ws_get(c, WS_CELL_IN, nin * 2); hist = (unsigned *)ws_get(c, WS_CELL_HIST, (size_t)n * 65536 * 4);
-    kept = (unsigned *)ws_get(c, WS_CELL_KEPT, (size_t)n * 4); dpar = (double *)ws_get(c, WS_CELL_PAR, (size_t)n * 11 * 8);
-    if (thresholded) dthr = (uint8_t *)ws_get(c, WS_CELL_THR, nout);
-    if (!din || !hist || !kept || !dpar || (thresholded && !dthr)) fail(TMAT_E_HIP);
-    if (!rc && !hip_ok(hipMemcpyAsync(din, imgs, nin * 2, hipMemcpyHostToDevice, s), "H2D")) fail(TMAT_E_HIP);
+    // workspaces live on the handle between calls (tmat_ctx.h:ws_get); the scope carries the copies, and a failed call leaves nothing in
+    // flight on them
+    uint16_t *din = (uint16_t *)ws_get(c, WS_CELL_IN, nin * 2);
+    unsigned *hist = (unsigned *)ws_get(c, WS_CELL_HIST, (size_t)n * 65536 * 4), *kept = (unsigned *)ws_get(c, WS_CELL_KEPT, (size_t)n * 4);
+    double *dpar = (double *)ws_get(c, WS_CELL_PAR, (size_t)n * 11 * 8);
+    uint8_t *dthr = thresholded ? (uint8_t *)ws_get(c, WS_CELL_THR, nout) : nullptr;
+    if (!din || !hist || !kept || !dpar || (thresholded && !dthr)) return TMAT_E_HIP;
+    DevScope mem(c->ws_pool, s);
+    if (!mem.h2d(din, imgs, nin * 2)) return TMAT_E_HIP;
     const uint16_t *small = din;
-    if (!rc && out_h) {
-        dsm = (uint16_t *)ws_get(c, WS_CELL_SMALL, nout * 2); itab = (int *)ws_get(c, WS_CELL_TAB, (size_t)(oh + ow) * 4 * 4);
-        if (!dsm || !itab) fail(TMAT_E_HIP);
+    if (out_h) {
+        uint16_t *dsm = (uint16_t *)ws_get(c, WS_CELL_SMALL, nout * 2);
+        int *itab = (int *)ws_get(c, WS_CELL_TAB, (size_t)(oh + ow) * 4 * 4);
         // 8-bit sources (tmat_set_input_depth(h, 8)) take cv2's fixed-point arithmetic
-        else if (launch_resize_linear_dev(din, n, H, W, oh, ow, c->input_sat == 255.f, itab, dsm, s)) fail(TMAT_E_HIP);
-        else small = dsm;
+        if (!dsm || !itab || launch_resize_linear_dev(din, n, H, W, oh, ow, c->input_sat == 255.f, itab, dsm, s)) return TMAT_E_HIP;
+        small = dsm;
     }
-    if (!rc && !fit) {          // tmat_resize_linear_u16: only the down-sampled images are wanted
-        if (!hip_ok(hipGetLastError(), "launch") || !hip_ok(hipMemcpyAsync(small_out, small, nout * 2, hipMemcpyDeviceToHost, s), "D2H") ||
-            !hip_ok(hipStreamSynchronize(s), "sync")) { hipStreamSynchronize(s); fail(TMAT_E_HIP); }
+    if (!fit) {          // tmat_resize_linear_u16: only the down-sampled images are wanted
+        mem.check(hipGetLastError(), "launch");
+        mem.d2h(small_out, small, nout * 2);
+        return mem.finish();
     }
-    if (!rc && fit) {
-        const int npx = oh * ow, blocks = (npx + 255) / 256;
-        const dim3 grid(blocks < 512 ? blocks : 512, n);
-        if (!hip_ok(hipMemsetAsync(hist, 0, (size_t)n * 65536 * 4, s), "memset") || !hip_ok(hipMemsetAsync(kept, 0, n * 4, s), "memset")) fail(TMAT_E_HIP);
-        else {
-            if (small_out && !hip_ok(hipMemcpyAsync(small_out, small, nout * 2, hipMemcpyDeviceToHost, s), "D2H")) fail(TMAT_E_HIP);
-            const uint8_t *dmask = nullptr;
-            int *lohi = nullptr;
-            if (!rc && masks) {
-                std::vector<int> init((size_t)2 * n);
-                for (int i = 0; i < n; i++) { init[2 * i] = 65536; init[2 * i + 1] = -1; }
-                dmaskbuf = (uint8_t *)ws_get(c, WS_CELL_MASK, nout); lohibuf = (int *)ws_get(c, WS_CELL_LOHI, (size_t)2 * n * 4);
-                if (!dmaskbuf || !lohibuf ||
-                    !hip_ok(hipMemcpyAsync(dmaskbuf, masks, nout, hipMemcpyHostToDevice, s), "H2D") ||
-                    !hip_ok(hipMemcpy(lohibuf, init.data(), init.size() * 4, hipMemcpyHostToDevice), "H2D")) fail(TMAT_E_HIP);
-                else {
-                    dmask = dmaskbuf; lohi = lohibuf;
-                    hipLaunchKernelGGL(lohi_u16_kernel, grid, dim3(256), 0, s, small, npx, lohi);
-                }
-            }
-            hipLaunchKernelGGL(hist_u16_kernel, grid, dim3(256), 0, s, small, dmask, npx, hist);
-            hipLaunchKernelGGL(gmm_hist_kernel, dim3(n), dim3(1024), 0, s, hist, sd_coef, dpar, lohi);
-            hipLaunchKernelGGL(apply_threshold_kernel, grid, dim3(256), 0, s, small, dmask, npx, dpar, dthr, kept);
-            std::vector<unsigned> kh(n);
-            std::vector<double> ph((size_t)n * 11);
-            if (!hip_ok(hipGetLastError(), "launch") || !hip_ok(hipMemcpyAsync(kh.data(), kept, n * 4, hipMemcpyDeviceToHost, s), "D2H") ||
-                !hip_ok(hipMemcpyAsync(ph.data(), dpar, (size_t)n * 11 * 8, hipMemcpyDeviceToHost, s), "D2H") ||
-                (thresholded && !hip_ok(hipMemcpyAsync(thresholded, dthr, nout, hipMemcpyDeviceToHost, s), "D2H")) ||
-                !hip_ok(hipStreamSynchronize(s), "sync")) { hipStreamSynchronize(s); fail(TMAT_E_HIP); }      // nothing may still be copying into kh / ph when they go out of scope
-            else {
-                for (int i = 0; i < n; i++) area[i] = (double)kh[i] / (double)npx;          // compute_area_prop: np.sum(img > 0) / img.size
-                if (params) for (int i = 0; i < n; i++) for (int k = 0; k < 9; k++) params[(size_t)i * 9 + k] = ph[(size_t)i * 11 + k];
-            }
-        }
+    const int npx = oh * ow, blocks = (npx + 255) / 256;
+    const dim3 grid(blocks < 512 ? blocks : 512, n);
+    if (!mem.check(hipMemsetAsync(hist, 0, (size_t)n * 65536 * 4, s), "memset") || !mem.check(hipMemsetAsync(kept, 0, n * 4, s), "memset") ||
+        !mem.d2h(small_out, small, nout * 2)) return TMAT_E_HIP;
+    const uint8_t *dmask = nullptr;
+    int *lohi = nullptr;
+    if (masks) {
+        std::vector<int> init((size_t)2 * n);
+        for (int i = 0; i < n; i++) { init[2 * i] = 65536; init[2 * i + 1] = -1; }
+        uint8_t *dmaskbuf = (uint8_t *)ws_get(c, WS_CELL_MASK, nout);
+        lohi = (int *)ws_get(c, WS_CELL_LOHI, (size_t)2 * n * 4);
+        if (!dmaskbuf || !lohi || !mem.h2d(dmaskbuf, masks, nout) ||
+            !mem.check(hipMemcpy(lohi, init.data(), init.size() * 4, hipMemcpyHostToDevice), "H2D")) return TMAT_E_HIP;      // blocking: init may go
+        dmask = dmaskbuf;
+        hipLaunchKernelGGL(lohi_u16_kernel, grid, dim3(256), 0, s, small, npx, lohi);
     }
-    if (rc) hipStreamSynchronize(s);      // nothing of a failed call stays in flight on the handle's workspaces
-    return rc;
+    hipLaunchKernelGGL(hist_u16_kernel, grid, dim3(256), 0, s, small, dmask, npx, hist);
+    hipLaunchKernelGGL(gmm_hist_kernel, dim3(n), dim3(1024), 0, s, hist, sd_coef, dpar, lohi);
+    hipLaunchKernelGGL(apply_threshold_kernel, grid, dim3(256), 0, s, small, dmask, npx, dpar, dthr, kept);
+    unsigned *kh = mem.host<unsigned>(n);
+    double *ph = mem.host<double>((size_t)n * 11);
+    mem.check(hipGetLastError(), "launch");
+    mem.d2h(kh, kept, n * 4);
+    mem.d2h(ph, dpar, (size_t)n * 11 * 8);
+    mem.d2h(thresholded, dthr, nout);
+    if (mem.finish()) return TMAT_E_HIP;
+    for (int i = 0; i < n; i++) area[i] = (double)kh[i] / (double)npx;          // compute_area_prop: np.sum(img > 0) / img.size
+    if (params) for (int i = 0; i < n; i++) for (int k = 0; k < 9; k++) params[(size_t)i * 9 + k] = ph[(size_t)i * 11 + k];
+    return TMAT_OK;
 }
 
 extern "C" int tmat_cell_area_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, int out_h, int out_w, double sd_coef, double *area,

@@ -137,46 +137,45 @@ static int render_tree_impl(tmat_handle hd, const void *background, int bg_dtype
         if (rc) return rc;
         off[img + 1] = (int)ss.size();
     }
+    const size_t nseg = ss.size();
     const int K = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)512 << 20) / cper));      // <= 512 MiB of canvases per launch
     uint8_t *dbg = (uint8_t *)ws_get(c, WS_TREE_BG, (size_t)n * per * esz);
-    OverlaySeg *dseg = (OverlaySeg *)ws_get(c, WS_TREE_SEG, ss.size() * sizeof(OverlaySeg));
+    OverlaySeg *dseg = (OverlaySeg *)ws_get(c, WS_TREE_SEG, nseg * sizeof(OverlaySeg));
     float *dmm = (float *)ws_get(c, WS_TREE_MM, (size_t)n * 4 * sizeof(float) + (size_t)(n + 1) * sizeof(int));
     uint8_t *drgb = (uint8_t *)ws_get(c, WS_TREE_RGB, (size_t)K * cper);
     if (!dbg || !dseg || !dmm || !drgb) return TMAT_E_HIP;
     int *doff = (int *)(dmm + 4 * (size_t)n);
     hipStream_t s = c->stream;
-    int rc = TMAT_OK;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (ms) for (hipEvent_t &e : ev) if (hipEventCreate(&e) != hipSuccess) rc = TMAT_E_HIP;
-    auto mark = [&](int i) { if (ms && !rc && hipEventRecord(ev[i], s) != hipSuccess) rc = TMAT_E_HIP; };
-    auto span = [&](int a, int b, int slot) { float t = 0.0f; if (ms && !rc && hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess) ms[slot] += t; };
+    struct Events { hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) hipEventDestroy(x); } } ev;
+    DevScope mem(c->ws_pool, s);        // after ev: the events go when the stream has drained
+    if (ms) for (hipEvent_t &e : ev.e) mem.check(hipEventCreate(&e), "hipEventCreate");
+    auto mark = [&](int i) { if (ms && mem.ok) mem.check(hipEventRecord(ev.e[i], s), "hipEventRecord"); };
+    auto span = [&](int a, int b, int slot) { float t = 0.0f; if (ms && hipEventElapsedTime(&t, ev.e[a], ev.e[b]) == hipSuccess) ms[slot] += t; };
     mark(0);
-    if (!rc && (!hip_ok(hipMemcpyAsync(dbg, background, (size_t)n * per * esz, hipMemcpyHostToDevice, s), "H2D") ||
-        (!ss.empty() && !hip_ok(hipMemcpyAsync(dseg, ss.data(), ss.size() * sizeof(OverlaySeg), hipMemcpyHostToDevice, s), "H2D")) ||
-        !hip_ok(hipMemcpyAsync(doff, off.data(), (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice, s), "H2D"))) rc = TMAT_E_HIP;
+    mem.h2d(dbg, background, (size_t)n * per * esz);
+    if (nseg) mem.h2d(dseg, mem.keep(std::move(ss)), nseg * sizeof(OverlaySeg));
+    mem.h2d(doff, mem.keep(std::move(off)), (size_t)(n + 1) * sizeof(int));
     mark(1);
-    if (!rc && overlay_minmax_dev(dbg, bg_dtype, n, bh, bw, dmm, s)) { set_error("tmat_render_tree: min-max launch failed"); rc = TMAT_E_HIP; }
+    if (!mem.ok) return TMAT_E_HIP;
+    if (overlay_minmax_dev(dbg, bg_dtype, n, bh, bw, dmm, s)) { set_error("tmat_render_tree: min-max launch failed"); return TMAT_E_HIP; }
     mark(2);
-    if (ms && !rc) {
-        if (!hip_ok(hipStreamSynchronize(s), "sync")) rc = TMAT_E_HIP;
+    if (ms) {
+        if (mem.finish()) return TMAT_E_HIP;
         span(0, 1, 0); span(1, 2, 1);
     }
-    for (int i0 = 0; i0 < n && !rc; i0 += K) {
+    for (int i0 = 0; i0 < n; i0 += K) {
         const int k = std::min(K, n - i0);
         mark(0);
         const int r = overlay_render_dev(dbg + (size_t)i0 * per * esz, bg_dtype, dmm + 2 * (size_t)i0, k, bh, bw, dseg, doff + i0, cv.vh, cv.vw, cv.rp, drgb, s);
-        if (r == -1) { set_error("tmat_render_tree: canvas too large for one launch"); rc = TMAT_E_ARG; break; }
-        if (r) { set_error("tmat_render_tree: kernel launch failed"); rc = TMAT_E_HIP; break; }
+        if (r == -1) { set_error("tmat_render_tree: canvas too large for one launch"); return TMAT_E_ARG; }
+        if (r) { set_error("tmat_render_tree: kernel launch failed"); return TMAT_E_HIP; }
         mark(1);
-        if (!hip_ok(hipMemcpyAsync(rgb_out + (size_t)i0 * cper, drgb, (size_t)k * cper, hipMemcpyDeviceToHost, s), "D2H")) rc = TMAT_E_HIP;
+        mem.d2h(rgb_out + (size_t)i0 * cper, drgb, (size_t)k * cper);
         mark(2);
-        if (!hip_ok(hipStreamSynchronize(s), "sync")) rc = TMAT_E_HIP;
+        if (mem.finish()) return TMAT_E_HIP;
         span(0, 1, 2); span(1, 2, 3);
     }
-    if (rc) hipStreamSynchronize(s);
-    else if (!hip_ok(hipStreamSynchronize(s), "sync")) rc = TMAT_E_HIP;     // off / ss are released on return
-    for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-    return rc;
+    return TMAT_OK;
 }
 
 extern "C" int tmat_render_tree(tmat_handle hd, const void *background, int bg_dtype, int n, int bh, int bw, const double *segs, const int32_t *seg_branch,

@@ -473,21 +473,23 @@ int medial_thin_batch_dev(Ctx *c, const uint8_t *mask_dev, const double *dist_de
     int rc = ensure_ma_table(c);
     if (rc) return rc;
     const size_t per = (size_t)hh * ww;
-    std::vector<int> nfg_host(k, 0);
-    std::vector<std::vector<uint32_t>> perms(k);
-    DevScope mem(c->ws_pool, s);          // perms / nfg_host must outlive the copies
+    DevScope mem(c->ws_pool, s);
+    int *nfg_host = mem.host<int>(k);
     int *nfg = mem.alloc<int>(k);
     uint32_t *tie = mem.alloc<uint32_t>(k * per);
     void *ws = mem.alloc_bytes(thin_workspace_bytes(k, hh, ww));
-    if (!mem.ok) rc = TMAT_E_HIP;
-    if (!rc && thin_count_dev(mask_dev, k, hh, ww, nfg, s)) rc = TMAT_E_HIP;
-    if (!rc && (!hip_ok(hipMemcpyAsync(nfg_host.data(), nfg, k * sizeof(int), hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))) rc = TMAT_E_HIP;
-    if (!rc) parallel_images(k, [&](int i) { legacy_permutation(0, (size_t)nfg_host[i], perms[i]); });
-    for (int i = 0; i < k && !rc; i++)
-        if (!perms[i].empty() && !hip_ok(hipMemcpyAsync(tie + i * per, perms[i].data(), perms[i].size() * sizeof(uint32_t), hipMemcpyHostToDevice, s), "H2D")) rc = TMAT_E_HIP;
-    if (!rc && thin_dev(mask_dev, dist_dev, tie, nfg, k, hh, ww, ws, c->ma_table, skel_dev, s)) { set_error("medial axis: device thinning failed"); rc = TMAT_E_HIP; }
-    if (!rc && !hip_ok(hipStreamSynchronize(s), "sync")) rc = TMAT_E_HIP;      // perms / scratch are released on return
-    return rc;
+    if (!mem.ok || thin_count_dev(mask_dev, k, hh, ww, nfg, s)) return TMAT_E_HIP;
+    mem.d2h(nfg_host, nfg, k * sizeof(int));
+    if (mem.finish()) return TMAT_E_HIP;
+    std::vector<std::vector<uint32_t>> perms(k);
+    parallel_images(k, [&](int i) { legacy_permutation(0, (size_t)nfg_host[i], perms[i]); });
+    for (int i = 0; i < k; i++) {
+        const size_t bytes = perms[i].size() * sizeof(uint32_t);
+        if (bytes) mem.h2d(tie + i * per, mem.keep(std::move(perms[i])), bytes);
+    }
+    if (!mem.ok) return TMAT_E_HIP;
+    if (thin_dev(mask_dev, dist_dev, tie, nfg, k, hh, ww, ws, c->ma_table, skel_dev, s)) { set_error("medial axis: device thinning failed"); return TMAT_E_HIP; }
+    return mem.finish();
 }
 
 // tmat_dmt_graph / tmat_dmt_graph_batch with a handle: key build + sort + the two persistence sweeps of all n fields on the handle's
@@ -498,39 +500,35 @@ int dmt_graph_device_batch(void *handle, const float *imgs, int n, int R, int C,
     Ctx *c = (Ctx *)handle;
     TMAT_HIP(hipSetDevice(c->device));
     const size_t nE = dmt_edge_count(R, C), npx = (size_t)R * C;
-    std::vector<int32_t> ids_host((size_t)n * nE);
-    std::vector<int> m_host(n, 0);
-    std::vector<uint8_t> kind_host;
-    std::vector<float> pers_host;
     DevScope mem(c->ws_pool, c->stream);
-    float *df = mem.alloc<float>(n * npx);
+    int32_t *ids_host = mem.host<int32_t>(n * nE);
+    int *m_host = mem.host<int>(n);
+    uint8_t *kind_host = nullptr;
+    float *pers_host = nullptr;
+    float *df = mem.alloc_from(imgs, n * npx);
     void *ws = mem.alloc_bytes(dmt_workspace_bytes(n, R, C));
     int32_t *ids = mem.alloc<int32_t>(n * nE);
     int *m = mem.alloc<int>(n);
-    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
-    if (!rc && !hip_ok(hipMemcpyAsync(df, imgs, n * npx * sizeof(float), hipMemcpyHostToDevice, c->stream), "H2D")) rc = TMAT_E_HIP;
-    if (!rc && dmt_sorted_edges_dev(df, n, R, C, ws, ids, m, c->stream)) { set_error("tmat_dmt_graph: device front end failed"); rc = TMAT_E_HIP; }
+    if (!mem.ok) return TMAT_E_HIP;
+    if (dmt_sorted_edges_dev(df, n, R, C, ws, ids, m, c->stream)) { set_error("tmat_dmt_graph: device front end failed"); return TMAT_E_HIP; }
     // the two persistence sweeps on the device too (dmt_sweep_kernels.hip; TMAT_DMT_SWEEP_DEVICE=0: on the host); `collect` stays on the host
-    const bool sweep_dev = c->dmt_sweep_device;
-    if (!rc && sweep_dev) {
-        kind_host.resize((size_t)n * nE); pers_host.resize((size_t)n * nE);
+    if (c->dmt_sweep_device) {
         void *sws = mem.alloc_bytes(dmt_sweep_workspace_bytes(n, R, C));
         uint8_t *dkind = mem.alloc<uint8_t>(n * nE);
         float *dpers = mem.alloc<float>(n * nE);
-        if (!mem.ok) rc = TMAT_E_HIP;
-        if (!rc && dmt_sweeps_dev(df, ids, m, n, R, C, sws, dkind, dpers, c->stream)) { set_error("tmat_dmt_graph: device sweeps failed"); rc = TMAT_E_HIP; }
-        if (!rc && (!hip_ok(hipMemcpyAsync(kind_host.data(), dkind, n * nE, hipMemcpyDeviceToHost, c->stream), "D2H") ||
-                    !hip_ok(hipMemcpyAsync(pers_host.data(), dpers, n * nE * sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H"))) rc = TMAT_E_HIP;
+        if (!mem.ok) return TMAT_E_HIP;
+        if (dmt_sweeps_dev(df, ids, m, n, R, C, sws, dkind, dpers, c->stream)) { set_error("tmat_dmt_graph: device sweeps failed"); return TMAT_E_HIP; }
+        mem.d2h(kind_host = mem.host<uint8_t>(n * nE), dkind, n * nE);
+        mem.d2h(pers_host = mem.host<float>(n * nE), dpers, n * nE * sizeof(float));
     }
-    if (!rc && (!hip_ok(hipMemcpyAsync(ids_host.data(), ids, n * nE * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream), "D2H") ||
-                !hip_ok(hipMemcpyAsync(m_host.data(), m, n * sizeof(int), hipMemcpyDeviceToHost, c->stream), "D2H"))) rc = TMAT_E_HIP;
-    if (!hip_ok(hipStreamSynchronize(c->stream), "sync") && !rc) rc = TMAT_E_HIP;
-    if (rc) return rc;
+    mem.d2h(ids_host, ids, n * nE * sizeof(int32_t));
+    mem.d2h(m_host, m, n * sizeof(int));
+    if (mem.finish()) return TMAT_E_HIP;
     std::vector<int> rcs(n, TMAT_OK);
     parallel_images(n, [&](int i) {
-        rcs[i] = dmt_graph_host_sorted(imgs + i * npx, R, C, delta1, delta2, ids_host.data() + i * nE, m_host[i], verts + (size_t)i * 2 * cap_v, cap_v,
-                                       edges + (size_t)i * 2 * cap_e, cap_e, n_verts + i, n_edges + i, sweep_dev ? kind_host.data() + i * nE : nullptr,
-                                       sweep_dev ? pers_host.data() + i * nE : nullptr);
+        rcs[i] = dmt_graph_host_sorted(imgs + i * npx, R, C, delta1, delta2, ids_host + i * nE, m_host[i], verts + (size_t)i * 2 * cap_v, cap_v,
+                                       edges + (size_t)i * 2 * cap_e, cap_e, n_verts + i, n_edges + i, kind_host ? kind_host + i * nE : nullptr,
+                                       pers_host ? pers_host + i * nE : nullptr);
     });
     for (int i = 0; i < n; i++) if (rcs[i]) return rcs[i];
     return TMAT_OK;
@@ -546,6 +544,31 @@ int dmt_graph_device_front(void *handle, const float *img, int R, int C, float d
 
 using namespace tmat;
 
+// The chunked entry points (tmat_segment_batch, tmat_preprocess_batch): the network's input shape (h, w) -- see analyze_dev --, K
+// images per pass and the pass buffers; `name` heads the error text
+static int chunked_setup(Ctx *c, const char *name, int n, int H, int W, double ds_ratio, int &h, int &w, int &K)
+{
+    h = round_half_even((double)W * ds_ratio); w = round_half_even((double)H * ds_ratio);
+    if (h < 1 || w < 1) { set_error(std::string(name) + ": target shape is empty"); return TMAT_E_ARG; }
+    const TileGeom g = make_geom(h, w, c->patch);
+    K = std::min(n, std::max(1, c->max_patches / g.tiles_per_img));
+    return ensure_pass_buffers(c, K, H, W, h, w, std::max(1, c->pass.fh), std::max(1, c->pass.fw));
+}
+// ... and their loop: the images go up K at a time through one staging buffer; pass(mem, dimg, i0, k) works on a chunk and ends with
+// mem.finish()
+template <class F>
+static int chunked_upload(Ctx *c, const uint16_t *imgs, int n, int K, size_t per, F pass)
+{
+    DevScope mem(c->ws_pool, c->stream);
+    uint16_t *dimg = mem.alloc<uint16_t>(K * per);
+    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
+    for (int i0 = 0; i0 < n && !rc; i0 += K) {
+        const int k = std::min(K, n - i0);
+        rc = mem.h2d(dimg, imgs + i0 * per, k * per * sizeof(uint16_t)) ? pass(mem, dimg, i0, k) : TMAT_E_HIP;
+    }
+    return rc;
+}
+
 extern "C" {
 
 int tmat_segment_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, double ds_ratio, double *pred)
@@ -555,24 +578,15 @@ int tmat_segment_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W
     if (!c || !imgs || !pred || n < 0 || H < 1 || W < 1) { set_error("tmat_segment_batch: bad argument"); return TMAT_E_ARG; }
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
-    const int h = round_half_even((double)W * ds_ratio), w = round_half_even((double)H * ds_ratio);    // see analyze_dev
-    if (h < 1 || w < 1) { set_error("tmat_segment_batch: target shape is empty"); return TMAT_E_ARG; }
-    TileGeom g = make_geom(h, w, c->patch);
-    const int K = std::min(n, std::max(1, c->max_patches / g.tiles_per_img));
-    int rc = ensure_pass_buffers(c, K, H, W, h, w, std::max(1, c->pass.fh), std::max(1, c->pass.fw));
+    int h, w, K;
+    int rc = chunked_setup(c, "tmat_segment_batch", n, H, W, ds_ratio, h, w, K);
     if (rc) return rc;
-    DevScope mem(c->ws_pool, c->stream);
-    uint16_t *dimg = mem.alloc<uint16_t>((size_t)K * H * W);
-    if (!mem.ok) return TMAT_E_HIP;
-    for (int i0 = 0; i0 < n && !rc; i0 += K) {
-        const int k = std::min(K, n - i0);
-        if (!hip_ok(hipMemcpyAsync(dimg, imgs + (size_t)i0 * H * W, (size_t)k * H * W * 2, hipMemcpyHostToDevice, c->stream), "H2D")) { rc = TMAT_E_HIP; break; }
-        rc = enqueue_segment(c, dimg, k, 0);
-        if (rc) break;
-        if (!hip_ok(hipStreamSynchronize(c->stream), "sync")) { rc = TMAT_E_HIP; break; }
-        std::memcpy(pred + (size_t)i0 * h * w, c->pass.pred_host[0], (size_t)k * h * w * sizeof(double));
-    }
-    return rc;
+    return chunked_upload(c, imgs, n, K, (size_t)H * W, [&](DevScope &mem, const uint16_t *dimg, int i0, int k) {
+        int rc = enqueue_segment(c, dimg, k, 0);
+        if (!rc) rc = mem.finish();
+        if (!rc) std::memcpy(pred + (size_t)i0 * h * w, c->pass.pred_host[0], (size_t)k * h * w * sizeof(double));
+        return rc;
+    });
 }
 
 int tmat_preprocess_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, double ds_ratio, float *x)
@@ -582,25 +596,16 @@ int tmat_preprocess_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, in
     if (!c || !imgs || !x || n < 0 || H < 1 || W < 1) { set_error("tmat_preprocess_batch: bad argument"); return TMAT_E_ARG; }
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
-    const int h = round_half_even((double)W * ds_ratio), w = round_half_even((double)H * ds_ratio);    // see analyze_dev
-    if (h < 1 || w < 1) { set_error("tmat_preprocess_batch: target shape is empty"); return TMAT_E_ARG; }
-    TileGeom g = make_geom(h, w, c->patch);
-    const int K = std::min(n, std::max(1, c->max_patches / g.tiles_per_img));
-    int rc = ensure_pass_buffers(c, K, H, W, h, w, std::max(1, c->pass.fh), std::max(1, c->pass.fw));
+    int h, w, K;
+    int rc = chunked_setup(c, "tmat_preprocess_batch", n, H, W, ds_ratio, h, w, K);
     if (rc) return rc;
-    DevScope mem(c->ws_pool, c->stream);
-    uint16_t *dimg = mem.alloc<uint16_t>((size_t)K * H * W);
-    if (!mem.ok) return TMAT_E_HIP;
     PassBuf &b = c->pass;
-    for (int i0 = 0; i0 < n && !rc; i0 += K) {
-        const int k = std::min(K, n - i0);
-        if (!hip_ok(hipMemcpyAsync(dimg, imgs + (size_t)i0 * H * W, (size_t)k * H * W * 2, hipMemcpyHostToDevice, c->stream), "H2D")) { rc = TMAT_E_HIP; break; }
+    return chunked_upload(c, imgs, n, K, (size_t)H * W, [&](DevScope &mem, const uint16_t *dimg, int i0, int k) {
         launch_lanczos(dimg, k, b.H, b.W, b.h, b.w, b.xi, b.xc, b.yi, b.yc, b.tmp, b.small, c->input_sat, c->stream);
         launch_rescale01(b.small, k, (size_t)b.h * b.w, b.mn, b.mx, b.x, c->stream);
-        if (!hip_ok(hipMemcpyAsync(x + (size_t)i0 * h * w, b.x, (size_t)k * h * w * sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H") ||
-            !hip_ok(hipStreamSynchronize(c->stream), "sync")) { rc = TMAT_E_HIP; break; }
-    }
-    return rc;
+        mem.d2h(x + (size_t)i0 * h * w, b.x, (size_t)k * h * w * sizeof(float));
+        return mem.finish();
+    });
 }
 
 int tmat_filter_edt_batch(tmat_handle hd, const double *pred, int n, int hh, int ww, uint8_t *filtered, double *dist)
@@ -610,20 +615,18 @@ int tmat_filter_edt_batch(tmat_handle hd, const double *pred, int n, int hh, int
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
     const size_t npx = (size_t)n * hh * ww;
-    std::vector<int> conv(n, 0);
     DevScope mem(c->ws_pool, c->stream);
-    double *dp = mem.alloc<double>(npx), *dd = mem.alloc<double>(npx);
+    int *conv = mem.host<int>(n);
+    double *dp = mem.alloc_from(pred, npx), *dd = mem.alloc<double>(npx);
     uint8_t *df = mem.alloc<uint8_t>(npx);
     void *ws = mem.alloc_bytes(morph_workspace_bytes(n, hh, ww));
-    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
-    if (!rc && !hip_ok(hipMemcpyAsync(dp, pred, npx * 8, hipMemcpyHostToDevice, c->stream), "H2D")) rc = TMAT_E_HIP;
-    if (!rc && filter_edt_dev(dp, n, hh, ww, 1, ws, df, dd, c->stream)) rc = TMAT_E_HIP;
-    if (!rc && (!hip_ok(hipMemcpyAsync(filtered, df, npx, hipMemcpyDeviceToHost, c->stream), "D2H") ||
-                !hip_ok(hipMemcpyAsync(dist, dd, npx * 8, hipMemcpyDeviceToHost, c->stream), "D2H") ||
-                !hip_ok(hipMemcpyAsync(conv.data(), morph_done_flags(ws, n, hh, ww), n * sizeof(int), hipMemcpyDeviceToHost, c->stream), "D2H") ||
-                !hip_ok(hipStreamSynchronize(c->stream), "sync"))) rc = TMAT_E_HIP;
-    for (int i = 0; i < n && !rc; i++) if (!conv[i]) { set_error("tmat_filter_edt_batch: thinning did not converge"); rc = TMAT_E_HIP; }
-    return rc;
+    if (!mem.ok || filter_edt_dev(dp, n, hh, ww, 1, ws, df, dd, c->stream)) return TMAT_E_HIP;
+    mem.d2h(filtered, df, npx);
+    mem.d2h(dist, dd, npx * 8);
+    mem.d2h(conv, morph_done_flags(ws, n, hh, ww), n * sizeof(int));
+    if (mem.finish()) return TMAT_E_HIP;
+    for (int i = 0; i < n; i++) if (!conv[i]) { set_error("tmat_filter_edt_batch: thinning did not converge"); return TMAT_E_HIP; }
+    return TMAT_OK;
 }
 
 int tmat_filter_mask_batch(tmat_handle hd, const uint8_t *mask, int n, int hh, int ww, int use_median, int remove_isolated, uint8_t *filtered)
@@ -633,18 +636,16 @@ int tmat_filter_mask_batch(tmat_handle hd, const uint8_t *mask, int n, int hh, i
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
     const size_t npx = (size_t)n * hh * ww;
-    std::vector<int> conv(n, 0);
     DevScope mem(c->ws_pool, c->stream);
-    uint8_t *dm = mem.alloc<uint8_t>(npx), *df = mem.alloc<uint8_t>(npx);
+    int *conv = mem.host<int>(n);
+    uint8_t *dm = mem.alloc_from(mask, npx), *df = mem.alloc<uint8_t>(npx);
     void *ws = mem.alloc_bytes(morph_workspace_bytes(n, hh, ww));
-    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
-    if (!rc && !hip_ok(hipMemcpyAsync(dm, mask, npx, hipMemcpyHostToDevice, c->stream), "H2D")) rc = TMAT_E_HIP;
-    if (!rc && filter_mask_dev(nullptr, dm, n, hh, ww, use_median != 0, remove_isolated != 0, ws, df, nullptr, c->stream)) rc = TMAT_E_HIP;
-    if (!rc && (!hip_ok(hipMemcpyAsync(filtered, df, npx, hipMemcpyDeviceToHost, c->stream), "D2H") ||
-                !hip_ok(hipMemcpyAsync(conv.data(), morph_done_flags(ws, n, hh, ww), n * sizeof(int), hipMemcpyDeviceToHost, c->stream), "D2H") ||
-                !hip_ok(hipStreamSynchronize(c->stream), "sync"))) rc = TMAT_E_HIP;
-    for (int i = 0; i < n && !rc; i++) if (!conv[i]) { set_error("tmat_filter_mask_batch: thinning did not converge"); rc = TMAT_E_HIP; }
-    return rc;
+    if (!mem.ok || filter_mask_dev(nullptr, dm, n, hh, ww, use_median != 0, remove_isolated != 0, ws, df, nullptr, c->stream)) return TMAT_E_HIP;
+    mem.d2h(filtered, df, npx);
+    mem.d2h(conv, morph_done_flags(ws, n, hh, ww), n * sizeof(int));
+    if (mem.finish()) return TMAT_E_HIP;
+    for (int i = 0; i < n; i++) if (!conv[i]) { set_error("tmat_filter_mask_batch: thinning did not converge"); return TMAT_E_HIP; }
+    return TMAT_OK;
 }
 
 int tmat_finish_batch(tmat_handle hd, const double *pred, const double *dist, const uint8_t *skel, int n, int hh, int ww, int out_h,
@@ -659,19 +660,14 @@ int tmat_finish_batch(tmat_handle hd, const double *pred, const double *dist, co
     TMAT_HIP(hipSetDevice(c->device));
     const size_t npx = (size_t)n * hh * ww, onpx = (size_t)n * out_h * out_w;
     DevScope mem(c->ws_pool, c->stream);
-    double *dp = mem.alloc<double>(npx), *dd = mem.alloc<double>(npx);
-    uint8_t *ds = mem.alloc<uint8_t>(npx);
+    double *dp = mem.alloc_from(pred, npx), *dd = mem.alloc_from(dist, npx);
+    uint8_t *ds = mem.alloc_from(skel, npx);
     void *ws = mem.alloc_bytes(finish_workspace_bytes(n, hh, ww, out_h, out_w));
     float *df = mem.alloc<float>(onpx), *d255 = mem.alloc<float>(onpx);
-    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
-    if (!rc && (!hip_ok(hipMemcpyAsync(dp, pred, npx * 8, hipMemcpyHostToDevice, c->stream), "H2D") ||
-                !hip_ok(hipMemcpyAsync(dd, dist, npx * 8, hipMemcpyHostToDevice, c->stream), "H2D") ||
-                !hip_ok(hipMemcpyAsync(ds, skel, npx, hipMemcpyHostToDevice, c->stream), "H2D"))) rc = TMAT_E_HIP;
-    if (!rc && finish_dev(dp, dd, ds, n, hh, ww, out_h, out_w, ws, df, d255, c->stream)) rc = TMAT_E_HIP;
-    if (!rc && (!hip_ok(hipMemcpyAsync(field, df, onpx * 4, hipMemcpyDeviceToHost, c->stream), "D2H") ||
-                !hip_ok(hipMemcpyAsync(field255, d255, onpx * 4, hipMemcpyDeviceToHost, c->stream), "D2H") ||
-                !hip_ok(hipStreamSynchronize(c->stream), "sync"))) rc = TMAT_E_HIP;
-    return rc;
+    if (!mem.ok || finish_dev(dp, dd, ds, n, hh, ww, out_h, out_w, ws, df, d255, c->stream)) return TMAT_E_HIP;
+    mem.d2h(field, df, onpx * 4);
+    mem.d2h(field255, d255, onpx * 4);
+    return mem.finish();
 }
 
 int tmat_zproj_dev(tmat_handle hd, const uint16_t *stacks_dev, int n, int Z, int H, int W, int method, void *out_dev)
@@ -699,21 +695,20 @@ int tmat_zproj_batch(tmat_handle hd, const uint16_t *stacks, int n, int Z, int H
     const size_t npx = (size_t)H * W, per_in = (size_t)Z * npx * sizeof(uint16_t);
     const size_t osz = (method == TMAT_ZPROJ_AVG || method == TMAT_ZPROJ_MED) ? sizeof(double) : sizeof(uint16_t);
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)1 << 30) / per_in));   // <= 1 GiB of stacks at a time
-    uint16_t *din = nullptr; void *dout = nullptr;
-    int rc = TMAT_OK;
-    // the staging buffers stay on the handle between calls (tmat_ctx.h:ws_get)
-    din = (uint16_t *)ws_get(c, WS_ZPROJ_IN, (size_t)chunk * per_in); dout = ws_get(c, WS_ZPROJ_OUT, (size_t)chunk * npx * osz);
-    if (!din || !dout) rc = TMAT_E_HIP;
-    for (int i0 = 0; i0 < n && !rc; i0 += chunk) {
+    // the staging buffers stay on the handle between calls (tmat_ctx.h:ws_get); the scope only carries the copies
+    uint16_t *din = (uint16_t *)ws_get(c, WS_ZPROJ_IN, (size_t)chunk * per_in);
+    void *dout = ws_get(c, WS_ZPROJ_OUT, (size_t)chunk * npx * osz);
+    if (!din || !dout) return TMAT_E_HIP;
+    DevScope mem(c->ws_pool, c->stream);
+    for (int i0 = 0; i0 < n; i0 += chunk) {
         const int k = std::min(chunk, n - i0);
-        if (!hip_ok(hipMemcpyAsync(din, stacks + (size_t)i0 * Z * npx, (size_t)k * per_in, hipMemcpyHostToDevice, c->stream), "H2D")) { rc = TMAT_E_HIP; break; }
+        if (!mem.h2d(din, stacks + (size_t)i0 * Z * npx, (size_t)k * per_in)) return TMAT_E_HIP;
         const int r = zproj_dev(din, k, Z, H, W, method, dout, c->stream);
-        if (r) { rc = r == -1 ? TMAT_E_ARG : TMAT_E_HIP; break; }
-        if (!hip_ok(hipMemcpyAsync((char *)out + (size_t)i0 * npx * osz, dout, (size_t)k * npx * osz, hipMemcpyDeviceToHost, c->stream), "D2H") ||
-            !hip_ok(hipStreamSynchronize(c->stream), "sync")) rc = TMAT_E_HIP;
+        if (r) return r == -1 ? TMAT_E_ARG : TMAT_E_HIP;
+        mem.d2h((char *)out + (size_t)i0 * npx * osz, dout, (size_t)k * npx * osz);
+        if (mem.finish()) return TMAT_E_HIP;
     }
-    if (rc) hipStreamSynchronize(c->stream);
-    return rc;
+    return TMAT_OK;
 }
 
 // The post-processing of compute_branches.py:334-357 for a batch of probability maps, with the same split as the batch
@@ -727,38 +722,36 @@ int tmat_postprocess_batch(tmat_handle hd, const double *pred, int n, int hh, in
     TMAT_HIP(hipSetDevice(c->device));
     const size_t per = (size_t)hh * ww, oper = (size_t)out_h * out_w;
     const int K = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)256 << 20) / (per * 8)));      // <= 256 MiB of f64 maps per chunk
-    std::vector<uint8_t> filt((size_t)K * per), skel((size_t)K * per);
-    std::vector<double> dist((size_t)K * per);
-    std::vector<int> conv(K, 0);
     hipStream_t s = c->stream;
     DevScope mem(c->ws_pool, s);
+    uint8_t *filt = mem.host<uint8_t>(K * per), *skel = mem.host<uint8_t>(K * per);
+    double *dist = mem.host<double>(K * per);
+    int *conv = mem.host<int>(K);
     double *dp = mem.alloc<double>(K * per), *dd = mem.alloc<double>(K * per);
     uint8_t *df = mem.alloc<uint8_t>(K * per), *dsk = mem.alloc<uint8_t>(K * per);
     void *ws = mem.alloc_bytes(morph_workspace_bytes(K, hh, ww)), *fws = mem.alloc_bytes(finish_workspace_bytes(K, hh, ww, out_h, out_w));
     float *dfield = mem.alloc<float>(K * oper), *d255 = mem.alloc<float>(K * oper);
-    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
-    for (int i0 = 0; i0 < n && !rc; i0 += K) {
+    if (!mem.ok) return TMAT_E_HIP;
+    for (int i0 = 0; i0 < n; i0 += K) {
         const int k = std::min(K, n - i0);
-        if (!hip_ok(hipMemcpyAsync(dp, pred + (size_t)i0 * per, k * per * 8, hipMemcpyHostToDevice, s), "H2D")) { rc = TMAT_E_HIP; break; }
-        if (filter_edt_dev(dp, k, hh, ww, 1, ws, df, dd, s)) { rc = TMAT_E_HIP; break; }
-        if (!hip_ok(hipMemcpyAsync(filt.data(), df, k * per, hipMemcpyDeviceToHost, s), "D2H") ||
-            !hip_ok(hipMemcpyAsync(dist.data(), dd, k * per * 8, hipMemcpyDeviceToHost, s), "D2H") ||
-            !hip_ok(hipMemcpyAsync(conv.data(), morph_done_flags(ws, k, hh, ww), k * sizeof(int), hipMemcpyDeviceToHost, s), "D2H") ||
-            !hip_ok(hipStreamSynchronize(s), "sync")) { rc = TMAT_E_HIP; break; }
-        for (int i = 0; i < k && !rc; i++) if (!conv[i]) { set_error("tmat_postprocess_batch: thinning did not converge"); rc = TMAT_E_HIP; }
-        if (rc) break;
+        if (!mem.h2d(dp, pred + (size_t)i0 * per, k * per * 8) || filter_edt_dev(dp, k, hh, ww, 1, ws, df, dd, s)) return TMAT_E_HIP;
+        mem.d2h(filt, df, k * per);
+        mem.d2h(dist, dd, k * per * 8);
+        mem.d2h(conv, morph_done_flags(ws, k, hh, ww), k * sizeof(int));
+        if (mem.finish()) return TMAT_E_HIP;
+        for (int i = 0; i < k; i++) if (!conv[i]) { set_error("tmat_postprocess_batch: thinning did not converge"); return TMAT_E_HIP; }
         if (c->thin_device && thin_dev_supported(hh, ww)) {
-            rc = medial_thin_batch_dev(c, df, dd, k, hh, ww, dsk, s);
-            if (rc) break;
+            int rc = medial_thin_batch_dev(c, df, dd, k, hh, ww, dsk, s);
+            if (rc) return rc;
         } else {        // images too large for the LDS-resident thinning kernel: host threads
-            parallel_images(k, [&](int i) { medial_axis_thin(filt.data() + i * per, dist.data() + i * per, hh, ww, skel.data() + i * per); });
-            if (!hip_ok(hipMemcpyAsync(dsk, skel.data(), k * per, hipMemcpyHostToDevice, s), "H2D")) { rc = TMAT_E_HIP; break; }
+            parallel_images(k, [&](int i) { medial_axis_thin(filt + i * per, dist + i * per, hh, ww, skel + i * per); });
+            if (!mem.h2d(dsk, skel, k * per)) return TMAT_E_HIP;
         }
-        if (finish_dev(dp, dd, dsk, k, hh, ww, out_h, out_w, fws, dfield, d255, s)) { rc = TMAT_E_HIP; break; }
-        if (!hip_ok(hipMemcpyAsync(field + (size_t)i0 * oper, dfield, k * oper * 4, hipMemcpyDeviceToHost, s), "D2H") ||
-            !hip_ok(hipStreamSynchronize(s), "sync")) rc = TMAT_E_HIP;
+        if (finish_dev(dp, dd, dsk, k, hh, ww, out_h, out_w, fws, dfield, d255, s)) return TMAT_E_HIP;
+        mem.d2h(field + (size_t)i0 * oper, dfield, k * oper * 4);
+        if (mem.finish()) return TMAT_E_HIP;
     }
-    return rc;
+    return TMAT_OK;
 }
 
 int tmat_medial_axis_batch(tmat_handle hd, const uint8_t *mask, int n, int hh, int ww, uint8_t *skel, double *dist)
@@ -771,16 +764,16 @@ int tmat_medial_axis_batch(tmat_handle hd, const uint8_t *mask, int n, int hh, i
     const size_t npx = (size_t)n * hh * ww;
     hipStream_t s = c->stream;
     DevScope mem(c->ws_pool, s);
-    uint8_t *dm = mem.alloc<uint8_t>(npx), *dsk = mem.alloc<uint8_t>(npx);
+    uint8_t *dm = mem.alloc_from(mask, npx), *dsk = mem.alloc<uint8_t>(npx);
     double *dd = mem.alloc<double>(npx);
     int *g = mem.alloc<int>(npx), *anyz = mem.alloc<int>(n);
-    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
-    if (!rc && !hip_ok(hipMemcpyAsync(dm, mask, npx, hipMemcpyHostToDevice, s), "H2D")) rc = TMAT_E_HIP;
-    if (!rc) launch_edt(dm, n, hh, ww, g, nullptr, anyz, dd, s);
-    if (!rc) rc = medial_thin_batch_dev(c, dm, dd, n, hh, ww, dsk, s);
-    if (!rc && (!hip_ok(hipMemcpyAsync(skel, dsk, npx, hipMemcpyDeviceToHost, s), "D2H") ||
-                !hip_ok(hipMemcpyAsync(dist, dd, npx * 8, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))) rc = TMAT_E_HIP;
-    return rc;
+    if (!mem.ok) return TMAT_E_HIP;
+    launch_edt(dm, n, hh, ww, g, nullptr, anyz, dd, s);
+    int rc = medial_thin_batch_dev(c, dm, dd, n, hh, ww, dsk, s);
+    if (rc) return rc;
+    mem.d2h(skel, dsk, npx);
+    mem.d2h(dist, dd, npx * 8);
+    return mem.finish();
 }
 
 int tmat_analyze_batch_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width,
@@ -806,7 +799,7 @@ int tmat_analyze_batch_masked(tmat_handle hd, const uint16_t *imgs, int n, int H
     if (!c || !imgs || !rows || n < 0 || H < 1 || W < 1 || ds_width < 1) { set_error("tmat_analyze_batch_masked: bad argument"); return TMAT_E_ARG; }
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
-    DevScope mem(c->ws_pool);
+    DevScope mem(c->ws_pool, nullptr);       // blocking copy below: nothing to drain
     uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
     if (!mem.ok) return TMAT_E_HIP;
     if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) return TMAT_E_HIP;
@@ -843,7 +836,7 @@ int tmat_analyze_batch_tree(tmat_handle hd, const uint16_t *imgs, int n, int H, 
     if (!c || !imgs || !rows || n < 0 || H < 1 || W < 1) { set_error("tmat_analyze_batch_tree: bad argument"); return TMAT_E_ARG; }
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
-    DevScope mem(c->ws_pool);
+    DevScope mem(c->ws_pool, nullptr);       // blocking copy below: nothing to drain
     uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
     if (!mem.ok) return TMAT_E_HIP;
     int rc = TMAT_OK;
@@ -863,7 +856,7 @@ int tmat_analyze_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W
     if (!c || !imgs || !rows || n < 0) { set_error("tmat_analyze_batch: bad argument"); return TMAT_E_ARG; }
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
-    DevScope mem(c->ws_pool);
+    DevScope mem(c->ws_pool, nullptr);       // blocking copy below: nothing to drain
     uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
     if (!mem.ok) return TMAT_E_HIP;
     int rc = TMAT_OK;

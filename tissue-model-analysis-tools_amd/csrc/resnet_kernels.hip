@@ -253,7 +253,8 @@ static bool ensure_f16(ResNetModel &m)
     return true;
 }
 
-// prec: 0 (f32, bit-exact contract) or 3 (f16 operands: the model's f16 planes, made by ensure_f16)
+// One convolution of the forward, by activation type.  float: prec 0 (f32, bit-exact contract) or 3 (f16 operands: the model's f16
+// planes, made by ensure_f16); uint16_t (f16act): IEEE binary16 activations in memory, always the f16 planes
 static bool run_conv(const ResConv &c, int prec, const float *in, int N, int h, const float *resid, int relu, float *out, hipStream_t s)
 {
     ConvArgs a{};
@@ -262,48 +263,57 @@ static bool run_conv(const ResConv &c, int prec, const float *in, int N, int h, 
     if (prec == 3) { a.W = (const float *)c.w16; a.prec = 3; }
     return launch_conv(a, s);
 }
-
-static bool run_conv_f16act(const ResConv &c, const uint16_t *in, int N, int h, const uint16_t *resid, int relu, uint16_t *out, hipStream_t s)
+static bool run_conv(const ResConv &c, int, const uint16_t *in, int N, int h, const uint16_t *resid, int relu, uint16_t *out, hipStream_t s)
 {
     ConvF16Args a{};
     a.in = in; a.N = N; a.h = h; a.w = h; a.Cin = c.cin; a.ksize = c.ksize; a.stride = c.stride; a.W = (const uint16_t *)c.w16; a.Cout = c.cout;
     a.scale = c.scale; a.shift = c.shift; a.resid = resid; a.relu_out = relu; a.out = out;
     return launch_conv_f16act(a, s);
 }
-
-// The f16act form of resnet_forward_dev: the same launches and the same buffer rotation, every activation tensor IEEE binary16 in the
-// first half of the buffer the f32 forms use (no allocation of its own, no host-side conversion).
-static int resnet_forward_f16act_dev(const ResNetModel &m, const float *x, int N, int S, float *const bufs[4], float *col32, float *prob, hipStream_t s)
+// ... and the stem's im2col: x (N, S, S, 3) -> col, STEM_K values per output pixel; the stem itself is then a 1x1 convolution
+static void stem_im2col(const float *x, int N, int S, float *col, hipStream_t s)
 {
-    uint16_t *a = (uint16_t *)bufs[0], *b = (uint16_t *)bufs[1], *t1 = (uint16_t *)bufs[2], *t2 = (uint16_t *)bufs[3], *col = (uint16_t *)col32;
+    const size_t quads = (size_t)N * (S / 2) * (S / 2) * (STEM_K / 4);
+    hipLaunchKernelGGL(resnet_im2col_kernel, dim3((unsigned)std::min<size_t>((quads + 255) / 256, 1u << 20)), dim3(256), 0, s, x, S, col, quads);
+}
+static void stem_im2col(const float *x, int N, int S, uint16_t *col, hipStream_t s)
+{
+    const size_t octs = (size_t)N * (S / 2) * (S / 2) * (STEM_K / 8);
+    hipLaunchKernelGGL(resnet_im2col_f16_kernel, dim3((unsigned)std::min<size_t>((octs + 255) / 256, 1u << 20)), dim3(256), 0, s, x, S, (_Float16 *)col, octs);
+}
+
+// The forward on activations of type T: float, or uint16_t = IEEE binary16 bits in the first half of the buffers the f32 forms use (no
+// allocation of its own, no host-side conversion).  Both run the same launches with the same buffer rotation.
+template <typename T>
+static int resnet_forward_as(const ResNetModel &m, int prec, const float *x, int N, int S, float *const bufs[4], float *col, float *prob, hipStream_t s)
+{
+    using KT = std::conditional_t<std::is_same<T, float>::value, float, _Float16>;      // the kernels' name for T
+    T *a = (T *)bufs[0], *b = (T *)bufs[1], *t1 = (T *)bufs[2], *t2 = (T *)bufs[3];
     const int S2 = S / 2, S4 = S / 4;
-    {
-        const size_t octs = (size_t)N * S2 * S2 * (STEM_K / 8);
-        hipLaunchKernelGGL(resnet_im2col_f16_kernel, dim3((unsigned)std::min<size_t>((octs + 255) / 256, 1u << 20)), dim3(256), 0, s, x, S, (_Float16 *)col, octs);
-        ConvF16Args st{};
-        st.in = col; st.N = N; st.h = S2; st.w = S2; st.Cin = STEM_K; st.ksize = 1; st.stride = 1; st.W = (const uint16_t *)m.stem_w16; st.Cout = 64;
-        st.scale = m.stem_scale; st.shift = m.stem_shift; st.resid = nullptr; st.relu_out = 1; st.out = a;
-        if (!launch_conv_f16act(st, s)) return TMAT_E_ARG;
-    }
+    ResConv stem;
+    stem.cin = STEM_K; stem.cout = 64; stem.w = m.stem_w; stem.w16 = m.stem_w16; stem.scale = m.stem_scale; stem.shift = m.stem_shift;
+    stem_im2col(x, N, S, (T *)col, s);
+    if (!run_conv(stem, prec, (const T *)col, N, S2, nullptr, 1, a, s)) return TMAT_E_ARG;
     const size_t ptotal = (size_t)N * S4 * S4 * 64;
-    hipLaunchKernelGGL(resnet_pool_kernel<_Float16>, dim3((unsigned)std::min<size_t>((ptotal + 255) / 256, 16384)), dim3(256), 0, s, (const _Float16 *)a, S2, 64, (_Float16 *)b, ptotal);
-    uint16_t *cur = b, *nxt = a;
+    hipLaunchKernelGGL(resnet_pool_kernel<KT>, dim3((unsigned)std::min<size_t>((ptotal + 255) / 256, 16384)), dim3(256), 0, s, (const KT *)a, S2, 64, (KT *)b, ptotal);
+    T *cur = b, *nxt = a;
     int h = S4;
     for (const ResBlock &k : m.blocks) {
         const int ho = h / k.c1.stride;
-        const uint16_t *shortcut = cur;
+        const T *shortcut = cur;
         if (k.has_sc) {
-            if (!run_conv_f16act(k.sc, cur, N, h, nullptr, 0, t2, s)) return TMAT_E_ARG;
+            if (!run_conv(k.sc, prec, cur, N, h, nullptr, 0, t2, s)) return TMAT_E_ARG;
             shortcut = t2;
         }
-        if (!run_conv_f16act(k.c1, cur, N, h, nullptr, 1, t1, s)) return TMAT_E_ARG;
-        if (!run_conv_f16act(k.c2, t1, N, ho, nullptr, 1, nxt, s)) return TMAT_E_ARG;
-        if (!run_conv_f16act(k.c3, nxt, N, ho, shortcut, 1, t1, s)) return TMAT_E_ARG;
-        uint16_t *old = cur;
+        if (!run_conv(k.c1, prec, cur, N, h, nullptr, 1, t1, s)) return TMAT_E_ARG;
+        if (!run_conv(k.c2, prec, t1, N, ho, nullptr, 1, nxt, s)) return TMAT_E_ARG;
+        // c3 writes over t1 (its input is nxt), then the roles rotate: out -> cur
+        if (!run_conv(k.c3, prec, nxt, N, ho, shortcut, 1, t1, s)) return TMAT_E_ARG;
+        T *old = cur;
         cur = t1; t1 = old;
         h = ho;
     }
-    hipLaunchKernelGGL(resnet_head_kernel<_Float16>, dim3(N), dim3(1024), 0, s, (const _Float16 *)cur, h * h, m.feat, m.fc_w, m.fc_b, prob);
+    hipLaunchKernelGGL(resnet_head_kernel<KT>, dim3(N), dim3(1024), 0, s, (const KT *)cur, h * h, m.feat, m.fc_w, m.fc_b, prob);
     return hipGetLastError() == hipSuccess ? TMAT_OK : TMAT_E_HIP;
 }
 
@@ -313,39 +323,8 @@ static int resnet_forward_dev(const ResNetModel &m, int mode, const float *x, in
     const int prec = mode == TMAT_RESNET_PRECISION_F32 ? 0 : 3;
     if (m.feat > 1024) { set_error("resnet: head supports at most 1024 channels"); return TMAT_E_ARG; }
     if (prec == 3 && !m.has_f16) { set_error("resnet: the model has no f16 weights (tmat_resnet_set_precision makes them)"); return TMAT_E_ARG; }
-    if (mode == TMAT_RESNET_PRECISION_F16ACT) return resnet_forward_f16act_dev(m, x, N, S, bufs, col, prob, s);
-    float *a = bufs[0], *b = bufs[1], *t1 = bufs[2], *t2 = bufs[3];
-    const int S2 = S / 2, S4 = S / 4;
-    {
-        const size_t quads = (size_t)N * S2 * S2 * (STEM_K / 4);
-        hipLaunchKernelGGL(resnet_im2col_kernel, dim3((unsigned)std::min<size_t>((quads + 255) / 256, 1u << 20)), dim3(256), 0, s, x, S, col, quads);
-        ConvArgs st{};
-        st.in = col; st.N = N; st.h = S2; st.w = S2; st.Cin = STEM_K; st.relu_in = 0; st.ksize = 1; st.stride = 1; st.W = m.stem_w; st.Cout = 64;
-        st.scale = m.stem_scale; st.shift = m.stem_shift; st.resid = nullptr; st.rs = 0; st.relu_out = 1; st.out = a;
-        if (prec == 3) { st.W = (const float *)m.stem_w16; st.prec = 3; }
-        if (!launch_conv(st, s)) return TMAT_E_ARG;
-    }
-    const size_t ptotal = (size_t)N * S4 * S4 * 64;
-    hipLaunchKernelGGL(resnet_pool_kernel<float>, dim3((unsigned)std::min<size_t>((ptotal + 255) / 256, 16384)), dim3(256), 0, s, (const float *)a, S2, 64, b, ptotal);
-    float *cur = b, *nxt = a;
-    int h = S4;
-    for (const ResBlock &k : m.blocks) {
-        const int ho = h / k.c1.stride;
-        const float *shortcut = cur;
-        if (k.has_sc) {
-            if (!run_conv(k.sc, prec, cur, N, h, nullptr, 0, t2, s)) return TMAT_E_ARG;
-            shortcut = t2;
-        }
-        if (!run_conv(k.c1, prec, cur, N, h, nullptr, 1, t1, s)) return TMAT_E_ARG;
-        if (!run_conv(k.c2, prec, t1, N, ho, nullptr, 1, nxt, s)) return TMAT_E_ARG;
-        // c3 writes over t1 (its input is nxt), then the roles rotate: out -> cur
-        if (!run_conv(k.c3, prec, nxt, N, ho, shortcut, 1, t1, s)) return TMAT_E_ARG;
-        float *old = cur;
-        cur = t1; t1 = old;
-        h = ho;
-    }
-    hipLaunchKernelGGL(resnet_head_kernel<float>, dim3(N), dim3(1024), 0, s, (const float *)cur, h * h, m.feat, m.fc_w, m.fc_b, prob);
-    return hipGetLastError() == hipSuccess ? TMAT_OK : TMAT_E_HIP;
+    return mode == TMAT_RESNET_PRECISION_F16ACT ? resnet_forward_as<uint16_t>(m, prec, x, N, S, bufs, col, prob, s)
+                                                : resnet_forward_as<float>(m, prec, x, N, S, bufs, col, prob, s);
 }
 
 int resnet_precision_from_env(Ctx *c)
@@ -414,42 +393,6 @@ int tmat_resnet_load(tmat_handle hd, const void *weights_blob, size_t n_bytes, i
     return TMAT_OK;
 }
 
-// tmat_conv2d(prec = 4): one f16act convolution; wq is the f16 plane of the k-contiguous weights
-static int conv2d_f16act(Ctx *c, const float *x, size_t nx, int n, int hh, int ww, int cin, const std::vector<uint16_t> &wq, int ksize, int stride, int cout,
-                         const float *scale, const float *shift, const float *resid, size_t no, int relu_in, int relu_out, float *out)
-{
-    hipStream_t s = c->stream;
-    std::vector<uint16_t> xq(nx), rq(resid ? no : 0), oq(no);
-    for (size_t i = 0; i < nx; i++) xq[i] = f16_rne_sat(relu_in && !(x[i] > 0.f) ? 0.f : x[i]);
-    for (size_t i = 0; i < rq.size(); i++) rq[i] = f16_rne_sat(resid[i]);
-    uint16_t *dx = nullptr, *dw = nullptr, *dr = nullptr;
-    float *dsc = nullptr, *dsh = nullptr;
-    int rc = TMAT_OK;
-    DevScope mem(c->ws_pool, s);          // the uploads read xq / wq / rq
-    auto put = [&](void **d, const void *src, size_t bytes) {
-        *d = mem.alloc_bytes(bytes, "hipMalloc(tmat_conv2d)");
-        return *d && hip_ok(hipMemcpyAsync(*d, src, bytes, hipMemcpyHostToDevice, s), "H2D");
-    };
-    if (!put((void **)&dx, xq.data(), nx * 2) || !put((void **)&dw, wq.data(), wq.size() * 2) || !put((void **)&dsh, shift, (size_t)cout * 4) ||
-        (scale && !put((void **)&dsc, scale, (size_t)cout * 4)) || (resid && !put((void **)&dr, rq.data(), no * 2))) rc = TMAT_E_HIP;
-    uint16_t *dout = (uint16_t *)mem.alloc_bytes(no * 2, "hipMalloc(tmat_conv2d)");
-    if (!mem.ok || !dout) rc = TMAT_E_HIP;
-    if (!rc) {
-        ConvF16Args a{};
-        a.in = dx; a.N = n; a.h = hh; a.w = ww; a.Cin = cin; a.ksize = ksize; a.stride = stride; a.W = dw; a.Cout = cout;
-        a.scale = dsc; a.shift = dsh; a.resid = dr; a.relu_out = relu_out != 0; a.out = dout;
-        if (!launch_conv_f16act(a, s)) rc = TMAT_E_ARG;
-        else if (!hip_ok(hipGetLastError(), "tmat_conv2d launch") || !hip_ok(hipMemcpyAsync(oq.data(), dout, no * 2, hipMemcpyDeviceToHost, s), "D2H")) rc = TMAT_E_HIP;
-    }
-    if (!hip_ok(hipStreamSynchronize(s), "sync") && !rc) rc = TMAT_E_HIP;      // also drains the uploads before their sources go out of scope
-    if (!rc)
-        for (size_t i = 0; i < no; i++) {
-            const _Float16 hv = __builtin_bit_cast(_Float16, oq[i]);
-            out[i] = (float)hv;
-        }
-    return rc;
-}
-
 int tmat_resnet_set_precision(tmat_handle hd, int mode)
 {
     Ctx *c = (Ctx *)hd;
@@ -481,32 +424,42 @@ int tmat_conv2d(tmat_handle hd, int prec, const float *x, int n, int hh, int ww,
     TMAT_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t nx = (size_t)n * hh * ww * cin, nw = (size_t)ksize * ksize * cin * cout, no = (size_t)n * (hh / stride) * (ww / stride) * cout;
-    const std::vector<float> wk = k_contiguous(w, ksize * ksize, cin, cout);
-    std::vector<uint16_t> wq;
-    if (prec >= 3) { wq.resize(nw); for (size_t i = 0; i < nw; i++) wq[i] = f16_rne_sat(wk[i]); }
-    if (prec == 4) return conv2d_f16act(c, x, nx, n, hh, ww, cin, wq, ksize, stride, cout, scale, shift, resid, no, relu_in, relu_out, out);
-    float *dx = nullptr, *dsc = nullptr, *dsh = nullptr, *dr = nullptr;
-    void *dw = nullptr;
-    int rc = TMAT_OK;
-    DevScope mem(c->ws_pool, s);          // the uploads read wk / wq
-    auto put = [&](void **d, const void *src, size_t bytes) {
-        *d = mem.alloc_bytes(bytes, "hipMalloc(tmat_conv2d)");
-        return *d && hip_ok(hipMemcpyAsync(*d, src, bytes, hipMemcpyHostToDevice, s), "H2D");
+    const bool f16act = prec == 4;
+    const size_t asz = f16act ? 2 : 4, wsz = prec >= 3 ? 2 : 4;       // bytes per activation and per weight on the device
+    DevScope mem(c->ws_pool, s);
+    auto f16 = [&mem](const float *v, size_t count, bool relu) {
+        uint16_t *q = mem.host<uint16_t>(count);
+        for (size_t i = 0; i < count; i++) q[i] = f16_rne_sat(relu && !(v[i] > 0.f) ? 0.f : v[i]);
+        return (const char *)q;
     };
-    if (!put((void **)&dx, x, nx * 4) || !put(&dw, prec == 3 ? (const void *)wq.data() : (const void *)wk.data(), prec == 3 ? nw * 2 : nw * 4) ||
-        !put((void **)&dsh, shift, (size_t)cout * 4) || (scale && !put((void **)&dsc, scale, (size_t)cout * 4)) ||
-        (resid && !put((void **)&dr, resid, no * 4))) rc = TMAT_E_HIP;
-    float *dout = mem.alloc<float>(no, "hipMalloc(tmat_conv2d)");
-    if (!mem.ok) rc = TMAT_E_HIP;
-    if (!rc) {
+    // how each mode rounds its operands on the host: prec 3 the weights; prec 4 also x (after the load-side ReLU) and resid
+    std::vector<float> wk = k_contiguous(w, ksize * ksize, cin, cout);
+    const char *hw = prec >= 3 ? f16(wk.data(), nw, false) : (const char *)mem.keep(std::move(wk));
+    const char *hx = f16act ? f16(x, nx, relu_in != 0) : (const char *)x;
+    const char *hr = resid && f16act ? f16(resid, no, false) : (const char *)resid;
+    uint16_t *oq = f16act ? mem.host<uint16_t>(no) : nullptr;
+    char *dx = mem.alloc_from(hx, nx * asz), *dw = mem.alloc_from(hw, nw * wsz);
+    float *dsh = mem.alloc_from(shift, cout), *dsc = scale ? mem.alloc_from(scale, cout) : nullptr;
+    char *dr = hr ? mem.alloc_from(hr, no * asz) : nullptr, *dout = mem.alloc<char>(no * asz);
+    if (!mem.ok) return TMAT_E_HIP;
+    bool launched;
+    if (f16act) {
+        ConvF16Args a{};
+        a.in = (uint16_t *)dx; a.N = n; a.h = hh; a.w = ww; a.Cin = cin; a.ksize = ksize; a.stride = stride; a.W = (uint16_t *)dw; a.Cout = cout;
+        a.scale = dsc; a.shift = dsh; a.resid = (uint16_t *)dr; a.relu_out = relu_out != 0; a.out = (uint16_t *)dout;
+        launched = launch_conv_f16act(a, s);
+    } else {
         ConvArgs a{};
-        a.in = dx; a.N = n; a.h = hh; a.w = ww; a.Cin = cin; a.relu_in = relu_in != 0; a.ksize = ksize; a.stride = stride; a.W = (const float *)dw;
-        a.Cout = cout; a.scale = dsc; a.shift = dsh; a.resid = dr; a.rs = 0; a.relu_out = relu_out != 0; a.out = dout; a.prec = prec;
-        if (!launch_conv(a, s)) rc = TMAT_E_ARG;
-        else if (!hip_ok(hipGetLastError(), "tmat_conv2d launch") || !hip_ok(hipMemcpyAsync(out, dout, no * 4, hipMemcpyDeviceToHost, s), "D2H")) rc = TMAT_E_HIP;
+        a.in = (float *)dx; a.N = n; a.h = hh; a.w = ww; a.Cin = cin; a.relu_in = relu_in != 0; a.ksize = ksize; a.stride = stride; a.W = (const float *)dw;
+        a.Cout = cout; a.scale = dsc; a.shift = dsh; a.resid = (float *)dr; a.rs = 0; a.relu_out = relu_out != 0; a.out = (float *)dout; a.prec = prec;
+        launched = launch_conv(a, s);
     }
-    if (!hip_ok(hipStreamSynchronize(s), "sync") && !rc) rc = TMAT_E_HIP;      // also drains the uploads from wk / wq before they go out of scope
-    return rc;
+    if (!launched) return TMAT_E_ARG;
+    mem.check(hipGetLastError(), "tmat_conv2d launch");
+    mem.d2h(f16act ? (void *)oq : (void *)out, dout, no * asz);
+    if (mem.finish()) return TMAT_E_HIP;
+    for (size_t i = 0; oq && i < no; i++) out[i] = (float)__builtin_bit_cast(_Float16, oq[i]);
+    return TMAT_OK;
 }
 
 int tmat_resnet_predict(tmat_handle hd, int model_id, const float *x, int n, int size, float *prob)
@@ -518,13 +471,13 @@ int tmat_resnet_predict(tmat_handle hd, int model_id, const float *x, int n, int
     hipStream_t s = c->stream;
     const size_t nx = (size_t)n * size * size * 3, nb = (size_t)n * (size / 2) * (size / 2) * 64;
     DevScope mem(c->ws_pool, s);
-    float *dx = mem.alloc<float>(nx), *dp = mem.alloc<float>(n), *col = mem.alloc<float>(nb * 3), *bufs[4];      // col: 192 = 3 x 64 values per stem output pixel
+    float *dx = mem.alloc_from(x, nx), *dp = mem.alloc<float>(n), *col = mem.alloc<float>(nb * 3), *bufs[4];      // col: 192 = 3 x 64 values per stem output pixel
     for (float *&b : bufs) b = mem.alloc<float>(nb);
-    int rc = mem.ok ? TMAT_OK : TMAT_E_HIP;
-    if (!rc && !hip_ok(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s), "H2D")) rc = TMAT_E_HIP;
-    if (!rc) rc = resnet_forward_dev(c->resnets[model_id], c->resnet_precision, dx, n, size, bufs, col, dp, s);
-    if (!rc && (!hip_ok(hipMemcpyAsync(prob, dp, n * 4, hipMemcpyDeviceToHost, s), "D2H") || !hip_ok(hipStreamSynchronize(s), "sync"))) rc = TMAT_E_HIP;
-    return rc;
+    if (!mem.ok) return TMAT_E_HIP;
+    int rc = resnet_forward_dev(c->resnets[model_id], c->resnet_precision, dx, n, size, bufs, col, dp, s);
+    if (rc) return rc;
+    mem.d2h(prob, dp, n * 4);
+    return mem.finish();
 }
 
 }  // extern "C"
@@ -540,50 +493,39 @@ static int inv_depth_impl(tmat_handle hd, const int *model_ids, int n_models, co
     hipStream_t s = c->stream;
     const int CH = 128;                                    // slices per forward: M = 128 x 16^2 rows at the deepest stage (round 2: 32, launch bound)
     const size_t npx = (size_t)size * size;
-    uint16_t *din = nullptr, *dsm = nullptr;
-    int *itab = nullptr, *mnmx = nullptr;
-    float *dx = nullptr, *dp = nullptr, *col = nullptr, *bufs[4] = {nullptr, nullptr, nullptr, nullptr};
     // cv2.resize(img, img_hw, cv2.INTER_LANCZOS4) (data_prep.py:36): the third positional parameter is `dst`: bilinear
-    int rc = TMAT_OK;
     const int nb = std::min(Z, CH);
-    // workspaces live on the handle between calls (tmat_ctx.h:ws_get)
-    din = (uint16_t *)ws_get(c, WS_INV_IN, (size_t)Z * H * W * 2); dsm = (uint16_t *)ws_get(c, WS_INV_SMALL, (size_t)Z * npx * 2);
-    itab = (int *)ws_get(c, WS_INV_TAB, (size_t)size * 2 * 4 * 4); mnmx = (int *)ws_get(c, WS_INV_MNMX, (size_t)Z * 2 * 4);
-    dx = (float *)ws_get(c, WS_INV_X, (size_t)Z * npx * 3 * 4); dp = (float *)ws_get(c, WS_INV_PROB, (size_t)Z * n_models * 4);
+    // workspaces live on the handle between calls (tmat_ctx.h:ws_get); the scope carries the copies, and a failed call leaves nothing in
+    // flight on them
+    uint16_t *din = (uint16_t *)ws_get(c, WS_INV_IN, (size_t)Z * H * W * 2), *dsm = (uint16_t *)ws_get(c, WS_INV_SMALL, (size_t)Z * npx * 2);
+    int *itab = (int *)ws_get(c, WS_INV_TAB, (size_t)size * 2 * 4 * 4), *mnmx = (int *)ws_get(c, WS_INV_MNMX, (size_t)Z * 2 * 4);
+    float *dx = (float *)ws_get(c, WS_INV_X, (size_t)Z * npx * 3 * 4), *dp = (float *)ws_get(c, WS_INV_PROB, (size_t)Z * n_models * 4), *bufs[4];
     for (int i = 0; i < 4; i++) bufs[i] = (float *)ws_get(c, (ToolWs)(WS_INV_BUF0 + i), (size_t)nb * (size / 2) * (size / 2) * 64 * 4);
-    col = (float *)ws_get(c, WS_INV_COL, (size_t)nb * (size / 2) * (size / 2) * STEM_K * 4);
-    if (!din || !dsm || !itab || !mnmx || !dx || !dp || !bufs[0] || !bufs[1] || !bufs[2] || !bufs[3] || !col) rc = TMAT_E_HIP;
-    if (!rc) {
-        // cv::resize takes INTER_AREA's integer mean for an exact halving on both axes (a 512 x 512 slice at the configured 256 x 256);
-        // 8-bit sources (tmat_set_input_depth(h, 8)) take its fixed-point bilinear arithmetic
-        bool ok = true;
-        {
-            size_t z0 = 0;
-            for (int k = 0; k < n_stacks && ok; k++) {
-                ok = hipMemcpyAsync(din + z0 * H * W, stacks[k], (size_t)Zs[k] * H * W * 2, hipMemcpyHostToDevice, s) == hipSuccess;
-                z0 += (size_t)Zs[k];
-            }
-        }
-        ok = ok && launch_resize_linear_dev(din, Z, H, W, size, size, c->input_sat == 255.f, itab, dsm, s) == 0;
-        if (!ok) { set_error("tmat_inv_depth_predict: upload failed"); rc = TMAT_E_HIP; }
-        else {
-            const int blocks = (int)((npx + 255) / 256);
-            hipLaunchKernelGGL(minmax_u16_img_kernel, dim3(Z), dim3(256), 0, s, dsm, (int)npx, mnmx, mnmx + Z);
-            hipLaunchKernelGGL(inv_prep_kernel, dim3(blocks < 1024 ? blocks : 1024, Z), dim3(256), 0, s, dsm, (int)npx, mnmx, mnmx + Z, dx);
-            for (int mi = 0; mi < n_models && !rc; mi++)
-                for (int z0 = 0; z0 < Z && !rc; z0 += CH) {
-                    const int k = std::min(CH, Z - z0);
-                    rc = resnet_forward_dev(c->resnets[model_ids[mi]], c->resnet_precision, dx + (size_t)z0 * npx * 3, k, size, bufs, col, dp + (size_t)mi * Z + z0, s);
-                }
-            std::vector<float> ph((size_t)Z * n_models);
-            if (!rc && (!hip_ok(hipMemcpyAsync(ph.data(), dp, ph.size() * 4, hipMemcpyDeviceToHost, s), "D2H") ||
-                        (x_out && !hip_ok(hipMemcpyAsync(x_out, dx, (size_t)Z * npx * 3 * 4, hipMemcpyDeviceToHost, s), "D2H")) ||
-                        !hip_ok(hipStreamSynchronize(s), "sync"))) { hipStreamSynchronize(s); rc = TMAT_E_HIP; }      // drain before ph goes out of scope
-            if (!rc) for (int z = 0; z < Z; z++) for (int mi = 0; mi < n_models; mi++) probs[(size_t)z * n_models + mi] = ph[(size_t)mi * Z + z];     // (Z, n_models)
-        }
+    float *col = (float *)ws_get(c, WS_INV_COL, (size_t)nb * (size / 2) * (size / 2) * STEM_K * 4);
+    if (!din || !dsm || !itab || !mnmx || !dx || !dp || !bufs[0] || !bufs[1] || !bufs[2] || !bufs[3] || !col) return TMAT_E_HIP;
+    DevScope mem(c->ws_pool, s);
+    size_t z0 = 0;
+    for (int k = 0; k < n_stacks; k++) {
+        mem.h2d(din + z0 * H * W, stacks[k], (size_t)Zs[k] * H * W * 2);
+        z0 += (size_t)Zs[k];
     }
-    if (rc) hipStreamSynchronize(s);      // nothing of a failed call stays in flight on the handle's workspaces
-    return rc;
+    // cv::resize takes INTER_AREA's integer mean for an exact halving on both axes (a 512 x 512 slice at the configured 256 x 256);
+    // 8-bit sources (tmat_set_input_depth(h, 8)) take its fixed-point bilinear arithmetic
+    if (!mem.ok || launch_resize_linear_dev(din, Z, H, W, size, size, c->input_sat == 255.f, itab, dsm, s)) { set_error("tmat_inv_depth_predict: upload failed"); return TMAT_E_HIP; }
+    const int blocks = (int)((npx + 255) / 256);
+    hipLaunchKernelGGL(minmax_u16_img_kernel, dim3(Z), dim3(256), 0, s, dsm, (int)npx, mnmx, mnmx + Z);
+    hipLaunchKernelGGL(inv_prep_kernel, dim3(blocks < 1024 ? blocks : 1024, Z), dim3(256), 0, s, dsm, (int)npx, mnmx, mnmx + Z, dx);
+    for (int mi = 0; mi < n_models; mi++)
+        for (int z = 0; z < Z; z += CH) {
+            const int rc = resnet_forward_dev(c->resnets[model_ids[mi]], c->resnet_precision, dx + (size_t)z * npx * 3, std::min(CH, Z - z), size, bufs, col, dp + (size_t)mi * Z + z, s);
+            if (rc) return rc;
+        }
+    float *ph = mem.host<float>((size_t)Z * n_models);
+    mem.d2h(ph, dp, (size_t)Z * n_models * 4);
+    mem.d2h(x_out, dx, (size_t)Z * npx * 3 * 4);
+    if (mem.finish()) return TMAT_E_HIP;
+    for (int z = 0; z < Z; z++) for (int mi = 0; mi < n_models; mi++) probs[(size_t)z * n_models + mi] = ph[(size_t)mi * Z + z];     // (Z, n_models)
+    return TMAT_OK;
 }
 
 extern "C" {

@@ -87,8 +87,6 @@ bool sato_dev(Ctx *c, const float *x, int n, int h, int w, const double *sigmas,
 
 const double SATO_SIGMAS[10] = {1, 2, 3, 4, 5, 7, 9, 11, 13, 15};       // compute_branches.py:262
 
-bool d2h(void *dst, const void *src, size_t bytes, hipStream_t s) { return !dst || hip_ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s), "D2H"); }
-
 }  // namespace
 
 // vol (Z, h, w) f32 on the device -> field (h, w) f32 on the device; stage copies go to the host arrays of `st` that are non-null
@@ -114,13 +112,12 @@ int vessel_field_dev(Ctx *c, const float *vol, int Z, int h, int w, int form, fl
     void *mws = A.pooled_bytes(morph_workspace_bytes(1, h, w));
     if (!A.ok) return TMAT_E_HIP;
     {
-        const double t[6] = {-1.0, 0.0, 1.0, 1.0, 2.0, 1.0};
-        int o[2 * 22], k = 0;
-        for (int dy = -2; dy <= 2; dy++) for (int dx = -2; dx <= 2; dx++) if (dy * dy + dx * dx <= 4) { o[2 * k] = dy; o[2 * k + 1] = dx; k++; }   // disk(2): 13
-        for (int dy = -1; dy <= 1; dy++) for (int dx = -1; dx <= 1; dx++) { o[2 * k] = dy; o[2 * k + 1] = dx; k++; }                                // square(3): 9
-        TMAT_HIP(hipMemcpyAsync(tabs, t, sizeof(t), hipMemcpyHostToDevice, s));
-        TMAT_HIP(hipMemcpyAsync(offs, o, sizeof(o), hipMemcpyHostToDevice, s));
-        TMAT_HIP(hipStreamSynchronize(s));           // the two host arrays leave scope
+        std::vector<int> o;
+        for (int dy = -2; dy <= 2; dy++) for (int dx = -2; dx <= 2; dx++) if (dy * dy + dx * dx <= 4) { o.push_back(dy); o.push_back(dx); }       // disk(2): 13
+        for (int dy = -1; dy <= 1; dy++) for (int dx = -1; dx <= 1; dx++) { o.push_back(dy); o.push_back(dx); }                                   // square(3): 9
+        A.h2d(tabs, A.keep(std::vector<double>{-1.0, 0.0, 1.0, 1.0, 2.0, 1.0}), 6 * sizeof(double));
+        A.h2d(offs, A.keep(std::move(o)), 2 * 22 * sizeof(int));
+        if (!A.ok) return TMAT_E_HIP;
     }
     cw.w_diff = tabs; cw.w_smooth = tabs + 3;
     const bool deriv = form == TMAT_SATO_GAUSSIAN_DERIVATIVES;
@@ -128,7 +125,7 @@ int vessel_field_dev(Ctx *c, const float *vol, int Z, int h, int w, int form, fl
     // z4: Sato of max(slice z, slice z + 1), all D pairs in one launch per pass
     launch_pairmax(vol, D, npx, deriv ? 1 : 0, x, s);
     if (!sato_dev(c, x, D, h, w, SATO_SIGMAS, 10, form, bufs, vess, s)) { set_error("vessel field: Sato stage failed"); return TMAT_E_HIP; }
-    if (st && !d2h(st->vess, vess, nv * 4, s)) return TMAT_E_HIP;
+    if (st) A.d2h(st->vess, vess, nv * 4);
     // z5: unsharp_mask(volume, radius 2, amount 2): 3-D gaussian ('reflect', truncate 4) over Z, rows, columns
     float *sharp = x;                                                        // x is free from here on
     if (!gauss_pass_f32(c, vess, bufs[0], Pass{2.0, 0, D, (int)npx, 1}, 4.0, EXT_REFLECT, s) ||
@@ -136,17 +133,17 @@ int vessel_field_dev(Ctx *c, const float *vol, int Z, int h, int w, int form, fl
         !gauss_pass_f32(c, bufs[1], bufs[0], Pass{2.0, 0, w, 1, (size_t)D * h}, 4.0, EXT_REFLECT, s)) return TMAT_E_HIP;
     launch_unsharp(vess, bufs[0], 2.0f, nv, sharp, s);
     launch_zmax(sharp, D, npx, vessels, s);
-    if (st && (!d2h(st->sharp, sharp, nv * 4, s) || !d2h(st->vessels, vessels, npx * 4, s))) return TMAT_E_HIP;
+    if (st) { A.d2h(st->sharp, sharp, nv * 4); A.d2h(st->vessels, vessels, npx * 4); }
     // z6: canny
     if (canny0_dev(vessels, h, w, cw, edges, s)) { set_error("vessel field: canny stage failed"); return TMAT_E_HIP; }
-    if (st && !d2h(st->edges, edges, npx, s)) return TMAT_E_HIP;
+    if (st) A.d2h(st->edges, edges, npx);
     // z7: medial axis of the edges; keep skeleton components with eccentricity * equivalent diameter > 3.5
     launch_edt(edges, 1, h, w, edt_g, nullptr, anyz, dist, s);
     { int rc = medial_thin_batch_dev(c, edges, dist, 1, h, w, skel, s); if (rc) return rc; }
     if (ecc_diam_select_dev(skel, h, w, 3.5, cw.L, mom, m0, nullptr, s)) return TMAT_E_HIP;
-    if (st && (!d2h(st->skel, skel, npx, s) || !d2h(st->mask_sel, m0, npx, s))) return TMAT_E_HIP;
+    if (st) { A.d2h(st->skel, skel, npx); A.d2h(st->mask_sel, m0, npx); }
     // z8: three masked blurs of the projection
-    TMAT_HIP(hipMemcpyAsync(vcur, vessels, npx * 4, hipMemcpyDeviceToDevice, s));
+    if (!A.check(hipMemcpyAsync(vcur, vessels, npx * 4, hipMemcpyDeviceToDevice, s), "D2D")) return TMAT_E_HIP;
     for (int it = 0; it < 3; it++) {
         if (!gauss2d_f32(c, vcur, vtmp, vblur, 1, h, w, 1.0, 0, 0, 4.0, EXT_NEAREST, s)) return TMAT_E_HIP;
         launch_where(m0, vblur, vcur, npx, vtmp, s);
@@ -155,22 +152,22 @@ int vessel_field_dev(Ctx *c, const float *vol, int Z, int h, int w, int form, fl
     //     ten region-growing rounds, mask &= ~edges, closing with disk(2)
     uint8_t *ma = m0, *mb = m1;
     for (int it = 0; it < 10; it++) { launch_grow(ma, vcur, h, w, mb, s); std::swap(ma, mb); }
-    if (st && !d2h(st->grown, ma, npx, s)) return TMAT_E_HIP;
+    if (st) A.d2h(st->grown, ma, npx);
     launch_andnot(ma, edges, npx, mb, s);
     launch_morph(mb, h, w, offs, 13, 0, ma, s);
     launch_morph(ma, h, w, offs, 13, 1, mb, s);
-    if (st && !d2h(st->closed, mb, npx, s)) return TMAT_E_HIP;
+    if (st) A.d2h(st->closed, mb, npx);
     // z9: filter_branch_seg_mask(mask, None, False), dilation with square(3), mask the sharpened projection, gaussian
     if (filter_mask_dev(nullptr, mb, 1, h, w, 0, 0, mws, filt, nullptr, s)) return TMAT_E_HIP;
-    int conv = 0;
-    TMAT_HIP(hipMemcpyAsync(&conv, morph_done_flags(mws, 1, h, w), sizeof(int), hipMemcpyDeviceToHost, s));
+    int *conv = A.host<int>();
+    A.d2h(conv, morph_done_flags(mws, 1, h, w), sizeof(int));
     launch_morph(filt, h, w, offs + 26, 9, 0, ma, s);
     launch_where(ma, vessels, nullptr, npx, vtmp, s);
     if (!gauss2d_f32(c, vtmp, vblur, field, 1, h, w, 1.0, 0, 0, 4.0, EXT_NEAREST, s)) return TMAT_E_HIP;
-    if (st && !d2h(st->filt, filt, npx, s)) return TMAT_E_HIP;
-    TMAT_HIP(hipStreamSynchronize(s));
+    if (st) A.d2h(st->filt, filt, npx);
+    if (A.finish()) return TMAT_E_HIP;
     if (hipGetLastError() != hipSuccess) { set_error("vessel field: kernel launch failed"); return TMAT_E_HIP; }
-    if (!conv) { set_error("vessel field: thinning did not converge"); return TMAT_E_HIP; }
+    if (!*conv) { set_error("vessel field: thinning did not converge"); return TMAT_E_HIP; }
     return TMAT_OK;
 }
 
@@ -191,11 +188,10 @@ int stack_resize_aa_dev(Ctx *c, const uint16_t *stack, int Z, int H, int W, int 
     zoom_axis_table(W, ow, c0, c1, wc0, wc1);
     int *dr0 = A.pooled<int>(oh), *dr1 = A.pooled<int>(oh), *dc0 = A.pooled<int>(ow), *dc1 = A.pooled<int>(ow);
     double *dwr0 = A.pooled<double>(oh), *dwr1 = A.pooled<double>(oh), *dwc0 = A.pooled<double>(ow), *dwc1 = A.pooled<double>(ow);
+    auto up = [&A](auto *dst, auto &table, int count) { A.h2d(dst, A.keep(std::move(table)), count * sizeof(*dst)); };     // the scope keeps the tables
+    up(dr0, r0, oh); up(dr1, r1, oh); up(dc0, c0, ow); up(dc1, c1, ow);
+    up(dwr0, wr0, oh); up(dwr1, wr1, oh); up(dwc0, wc0, ow); up(dwc1, wc1, ow);
     if (!A.ok) return TMAT_E_HIP;
-    TMAT_HIP(hipMemcpyAsync(dr0, r0.data(), oh * 4, hipMemcpyHostToDevice, s)); TMAT_HIP(hipMemcpyAsync(dr1, r1.data(), oh * 4, hipMemcpyHostToDevice, s));
-    TMAT_HIP(hipMemcpyAsync(dc0, c0.data(), ow * 4, hipMemcpyHostToDevice, s)); TMAT_HIP(hipMemcpyAsync(dc1, c1.data(), ow * 4, hipMemcpyHostToDevice, s));
-    TMAT_HIP(hipMemcpyAsync(dwr0, wr0.data(), oh * 8, hipMemcpyHostToDevice, s)); TMAT_HIP(hipMemcpyAsync(dwr1, wr1.data(), oh * 8, hipMemcpyHostToDevice, s));
-    TMAT_HIP(hipMemcpyAsync(dwc0, wc0.data(), ow * 8, hipMemcpyHostToDevice, s)); TMAT_HIP(hipMemcpyAsync(dwc1, wc1.data(), ow * 8, hipMemcpyHostToDevice, s));
     // anti-aliasing gaussian over rows and columns ('mirror', sigma (factor - 1) / 2), zoom, clip to the stack's range
     const double f0 = (double)H / (double)oh, f1 = (double)W / (double)ow;
     const double s0 = std::max(0.0, (f0 - 1) / 2), s1 = std::max(0.0, (f1 - 1) / 2);
@@ -216,10 +212,8 @@ int stack_resize_aa_dev(Ctx *c, const uint16_t *stack, int Z, int H, int W, int 
         cur = fb;
     }
     if (!cur) {               // no smoothing at all (an image at most as wide as the target): the zoom reads the stack as f64
-        const double one = 1.0;
         double *w_id = lohi;   // borrowed for a moment: a 1-tap identity kernel
-        TMAT_HIP(hipMemcpyAsync(w_id, &one, 8, hipMemcpyHostToDevice, s));
-        TMAT_HIP(hipStreamSynchronize(s));
+        if (!A.h2d(w_id, A.keep(std::vector<double>{1.0}), 8)) return TMAT_E_HIP;
         launch_corr1d_u16_f64(stack, fa, (size_t)Z * H, W, 1, w_id, 0, 1, EXT_MIRROR, s);
         cur = fa;
     }
@@ -227,8 +221,7 @@ int stack_resize_aa_dev(Ctx *c, const uint16_t *stack, int Z, int H, int W, int 
         set_error("stack resize: kernel launch failed");
         return TMAT_E_HIP;
     }
-    TMAT_HIP(hipStreamSynchronize(s));       // the host tables leave scope
-    return TMAT_OK;
+    return A.finish();
 }
 
 int stack_prepare_dev(Ctx *c, uint16_t *stack, int Z, int H, int W, int oh, int ow, float *vol, hipStream_t s)
@@ -261,18 +254,16 @@ int tmat_gaussian_f32(tmat_handle hd, const float *x, int d0, int d1, int d2, do
     const size_t n = (size_t)d0 * d1 * d2;
     hipStream_t s = c->stream;
     DevScope A(c->ws_pool, s);
-    float *a = A.pooled<float>(n), *b = A.pooled<float>(n);
+    float *a = A.pooled_from(x, n), *b = A.pooled<float>(n);
     if (!A.ok) return TMAT_E_HIP;
-    TMAT_HIP(hipMemcpyAsync(a, x, n * 4, hipMemcpyHostToDevice, s));
     // ndi.gaussian_filter: every axis in order (the caller folds leading axes of length 1 away by passing d0 = 1 -> two passes)
     float *src = a, *dst = b;
     if (d0 > 1) { if (!gauss_pass_f32(c, src, dst, Pass{sigma, 0, d0, d1 * d2, 1}, 4.0, mode, s)) return TMAT_E_HIP; std::swap(src, dst); }
     if (!gauss_pass_f32(c, src, dst, Pass{sigma, 0, d1, d2, (size_t)d0}, 4.0, mode, s)) return TMAT_E_HIP;
     std::swap(src, dst);
     if (!gauss_pass_f32(c, src, dst, Pass{sigma, 0, d2, 1, (size_t)d0 * d1}, 4.0, mode, s)) return TMAT_E_HIP;
-    TMAT_HIP(hipMemcpyAsync(out, dst, n * 4, hipMemcpyDeviceToHost, s));
-    TMAT_HIP(hipStreamSynchronize(s));
-    return TMAT_OK;
+    A.d2h(out, dst, n * 4);
+    return A.finish();
 }
 
 /* well_mask_generation.auto_threshold_well (reference :236-277) on the device: img (H, W) -> thresholded, eroded mask u8.
@@ -290,13 +281,13 @@ static int well_threshold(tmat_handle hd, const void *img, int is_f64, int H, in
     uint8_t *u8 = A.pooled<uint8_t>(n), *th = A.pooled<uint8_t>(n), *er = A.pooled<uint8_t>(n);
     unsigned *hist = A.pooled<unsigned>(5 * 256);
     int *decision = A.pooled<int>(2), *offs = A.pooled<int>(2 * 81);
-    if (!A.ok) return TMAT_E_HIP;
-    int o[2 * 81], k = 0;
-    for (int dy = -5; dy <= 5; dy++) for (int dx = -5; dx <= 5; dx++) if (dy * dy + dx * dx <= 25) { o[2 * k] = dy; o[2 * k + 1] = dx; k++; }     // disk(5): 81
-    TMAT_HIP(hipMemcpyAsync(offs, o, sizeof(int) * 2 * k, hipMemcpyHostToDevice, s));
+    std::vector<int> o;
+    for (int dy = -5; dy <= 5; dy++) for (int dx = -5; dx <= 5; dx++) if (dy * dy + dx * dx <= 25) { o.push_back(dy); o.push_back(dx); }         // disk(5): 81
+    const int k = (int)o.size() / 2;
+    A.h2d(offs, A.keep(std::move(o)), sizeof(int) * 2 * k);
     // gaussian(image, sigma=1): ndi.gaussian_filter, mode 'nearest', truncate 4, the image's float type after each axis
     if (is_f64) {
-        TMAT_HIP(hipMemcpyAsync(da, img, n * 8, hipMemcpyHostToDevice, s));
+        if (!A.h2d(da, img, n * 8)) return TMAT_E_HIP;
         const GaussTable &gt = gauss_table(c, 1.0, 0, gauss_radius(1.0, 4.0));
         const double *w = table_dev(c, gt);
         if (!w) return TMAT_E_HIP;
@@ -304,7 +295,7 @@ static int well_threshold(tmat_handle hd, const void *img, int is_f64, int H, in
         launch_corr1d_f64(db, da, (size_t)H, W, 1, w, gt.r, gt.sym, EXT_NEAREST, s);
         launch_wm_rescale_u8_f64(da, n, dmm, u8, s);
     } else {
-        TMAT_HIP(hipMemcpyAsync(a, img, n * 4, hipMemcpyHostToDevice, s));
+        if (!A.h2d(a, img, n * 4)) return TMAT_E_HIP;
         if (!gauss_pass_f32(c, a, b, Pass{1.0, 0, H, W, 1}, 4.0, EXT_NEAREST, s) || !gauss_pass_f32(c, b, a, Pass{1.0, 0, W, 1, (size_t)H}, 4.0, EXT_NEAREST, s))
             return TMAT_E_HIP;
         launch_minmax_f32(a, 1, n, mm, mm + 1, s);
@@ -314,10 +305,9 @@ static int well_threshold(tmat_handle hd, const void *img, int is_f64, int H, in
     launch_wm_decide(hist, H, W, decision, s);
     launch_wm_threshold(u8, n, decision, th, s);
     launch_wm_erode(th, H, W, offs, k, er, s);
-    TMAT_HIP(hipGetLastError());
-    TMAT_HIP(hipMemcpyAsync(out, er, n, hipMemcpyDeviceToHost, s));
-    TMAT_HIP(hipStreamSynchronize(s));
-    return TMAT_OK;
+    A.check(hipGetLastError(), "tmat_well_threshold: kernel launch");
+    A.d2h(out, er, n);
+    return A.finish();
 }
 
 int tmat_well_threshold(tmat_handle hd, const float *img, int H, int W, uint8_t *out) { return well_threshold(hd, img, 0, H, W, out); }
@@ -341,11 +331,9 @@ int tmat_canny_mask(tmat_handle hd, const uint8_t *mask, int H, int W, double si
     cw.sm = A.pooled<double>(npx); cw.t0 = A.pooled<double>(npx); cw.is_ = A.pooled<double>(npx); cw.js = A.pooled<double>(npx); cw.mag = A.pooled<double>(npx);
     cw.low = A.pooled<uint8_t>(npx); cw.high = A.pooled<uint8_t>(npx); cw.L = A.pooled<int>(npx); cw.flag = A.pooled<int>(npx);
     double *tabs = A.pooled<double>(6);
-    if (!A.ok) return TMAT_E_HIP;
-    const double t[6] = {-1.0, 0.0, 1.0, 1.0, 2.0, 1.0};
-    TMAT_HIP(hipMemcpyAsync(tabs, t, sizeof(t), hipMemcpyHostToDevice, s));
+    A.h2d(tabs, A.keep(std::vector<double>{-1.0, 0.0, 1.0, 1.0, 2.0, 1.0}), 6 * sizeof(double));
     cw.w_diff = tabs; cw.w_smooth = tabs + 3;
-    TMAT_HIP(hipMemcpyAsync(m, mask, npx, hipMemcpyHostToDevice, s));
+    if (!A.h2d(m, mask, npx)) return TMAT_E_HIP;
     // gaussian(x, sigma, mode='constant') of the image and of the all-ones mask (0.18.3 smooth_with_function_and_mask): zero padding
     // by the kernel radius makes the boundary mode irrelevant
     launch_wm_pad(m, H, W, r, pa, pb, s);
@@ -358,9 +346,8 @@ int tmat_canny_mask(tmat_handle hd, const uint8_t *mask, int H, int W, double si
     launch_corr1d_f64(pt, pb, (size_t)Hp, Wp, 1, w, gt.r, gt.sym, EXT_NEAREST, s);
     launch_wm_crop_div(pa, pb, H, W, r, cw.sm, s);
     if (canny_core_dev(H, W, cw, e, s)) { set_error("tmat_canny_mask: kernel launch failed"); return TMAT_E_HIP; }
-    TMAT_HIP(hipMemcpyAsync(edges, e, npx, hipMemcpyDeviceToHost, s));
-    TMAT_HIP(hipStreamSynchronize(s));
-    return TMAT_OK;
+    A.d2h(edges, e, npx);
+    return A.finish();
 }
 
 int tmat_sato_batch(tmat_handle hd, const float *imgs, int n, int hh, int ww, const double *sigmas, int n_sigmas, int hessian, float *out)
@@ -374,15 +361,13 @@ int tmat_sato_batch(tmat_handle hd, const float *imgs, int n, int hh, int ww, co
     const size_t total = (size_t)n * hh * ww;
     hipStream_t s = c->stream;
     DevScope A(c->ws_pool, s);
-    float *raw = A.pooled<float>(total), *x = A.pooled<float>(total), *best = A.pooled<float>(total), *bufs[7];
+    float *raw = A.pooled_from(imgs, total), *x = A.pooled<float>(total), *best = A.pooled<float>(total), *bufs[7];
     for (float *&b : bufs) b = A.pooled<float>(total);
     if (!A.ok) return TMAT_E_HIP;
-    TMAT_HIP(hipMemcpyAsync(raw, imgs, total * 4, hipMemcpyHostToDevice, s));
     launch_prep_single(raw, total, hessian == TMAT_SATO_GAUSSIAN_DERIVATIVES, x, s);
     if (!sato_dev(c, x, n, hh, ww, sigmas, n_sigmas, hessian, bufs, best, s)) { set_error("tmat_sato_batch: kernel launch failed"); return TMAT_E_HIP; }
-    TMAT_HIP(hipMemcpyAsync(out, best, total * 4, hipMemcpyDeviceToHost, s));
-    TMAT_HIP(hipStreamSynchronize(s));
-    return TMAT_OK;
+    A.d2h(out, best, total * 4);
+    return A.finish();
 }
 
 int tmat_stack_prepare(tmat_handle hd, const uint16_t *stack, int Z, int H, int W, int out_h, int out_w, float *vol)
@@ -392,15 +377,13 @@ int tmat_stack_prepare(tmat_handle hd, const uint16_t *stack, int Z, int H, int 
     TMAT_HIP(hipSetDevice(c->device));
     const size_t nin = (size_t)Z * H * W, nout = (size_t)Z * out_h * out_w;
     DevScope A(c->ws_pool, c->stream);
-    uint16_t *ds = A.pooled<uint16_t>(nin);
+    uint16_t *ds = A.pooled_from(stack, nin);
     float *dv = A.pooled<float>(nout);
     if (!A.ok) return TMAT_E_HIP;
-    TMAT_HIP(hipMemcpyAsync(ds, stack, nin * 2, hipMemcpyHostToDevice, c->stream));
     int rc = stack_prepare_dev(c, ds, Z, H, W, out_h, out_w, dv, c->stream);
     if (rc) return rc;
-    TMAT_HIP(hipMemcpyAsync(vol, dv, nout * 4, hipMemcpyDeviceToHost, c->stream));
-    TMAT_HIP(hipStreamSynchronize(c->stream));
-    return TMAT_OK;
+    A.d2h(vol, dv, nout * 4);
+    return A.finish();
 }
 
 int tmat_vessel_field(tmat_handle hd, const float *vol, int Z, int hh, int ww, int hessian, float *field, const tmat_vessel_stages *stages)
@@ -413,14 +396,12 @@ int tmat_vessel_field(tmat_handle hd, const float *vol, int Z, int hh, int ww, i
     TMAT_HIP(hipSetDevice(c->device));
     const size_t nvol = (size_t)Z * hh * ww, npx = (size_t)hh * ww;
     DevScope A(c->ws_pool, c->stream);
-    float *dv = A.pooled<float>(nvol), *df = A.pooled<float>(npx);
+    float *dv = A.pooled_from(vol, nvol), *df = A.pooled<float>(npx);
     if (!A.ok) return TMAT_E_HIP;
-    TMAT_HIP(hipMemcpyAsync(dv, vol, nvol * 4, hipMemcpyHostToDevice, c->stream));
     int rc = vessel_field_dev(c, dv, Z, hh, ww, hessian, df, stages, c->stream);
     if (rc) return rc;
-    TMAT_HIP(hipMemcpyAsync(field, df, npx * 4, hipMemcpyDeviceToHost, c->stream));
-    TMAT_HIP(hipStreamSynchronize(c->stream));
-    return TMAT_OK;
+    A.d2h(field, df, npx * 4);
+    return A.finish();
 }
 
 // common tail of analyze_img from the vesselness image in HBM: rescale_intensity(0..255) (:419), DMT graph, MorseGraph statistics
@@ -435,32 +416,30 @@ static int field_stats_dev(Ctx *c, const float *field, int fh, int fw, float t1,
     void *dws = A.pooled_bytes(dmt_workspace_bytes(1, fh, fw));
     if (!A.ok) return TMAT_E_HIP;
     launch_rescale255(field, 1, (int)npx, mnmx, mnmx + 1, f255, s);
-    std::vector<float> f255_host(npx);
-    std::vector<int32_t> ids_host(nE);
-    int m_host = 0;
+    float *f255_host = A.host<float>(npx);
+    int32_t *ids_host = A.host<int32_t>(nE);
+    int *m_host = A.host<int>();
     if (dmt_sorted_edges_dev(f255, 1, fh, fw, dws, ids, m, s)) { set_error("field stats: DMT front end failed"); return TMAT_E_HIP; }
     // the two persistence sweeps on the device as well (dmt_sweep_kernels.hip; TMAT_DMT_SWEEP_DEVICE=0: inside dmt_graph_host_sorted)
-    std::vector<uint8_t> kind_host;
-    std::vector<float> pers_host;
+    uint8_t *kind_host = nullptr;
+    float *pers_host = nullptr;
     if (c->dmt_sweep_device) {
         uint8_t *dkind = A.pooled<uint8_t>(nE);
         float *dpers = A.pooled<float>(nE);
         void *sws = A.pooled_bytes(dmt_sweep_workspace_bytes(1, fh, fw));
         if (!A.ok) return TMAT_E_HIP;
         if (dmt_sweeps_dev(f255, ids, m, 1, fh, fw, sws, dkind, dpers, s)) { set_error("field stats: device sweeps failed"); return TMAT_E_HIP; }
-        kind_host.resize(nE); pers_host.resize(nE);
-        TMAT_HIP(hipMemcpyAsync(kind_host.data(), dkind, nE, hipMemcpyDeviceToHost, s));
-        TMAT_HIP(hipMemcpyAsync(pers_host.data(), dpers, nE * sizeof(float), hipMemcpyDeviceToHost, s));
+        A.d2h(kind_host = A.host<uint8_t>(nE), dkind, nE);
+        A.d2h(pers_host = A.host<float>(nE), dpers, nE * sizeof(float));
     }
-    TMAT_HIP(hipMemcpyAsync(f255_host.data(), f255, npx * 4, hipMemcpyDeviceToHost, s));
-    TMAT_HIP(hipMemcpyAsync(ids_host.data(), ids, nE * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    TMAT_HIP(hipMemcpyAsync(&m_host, m, sizeof(int), hipMemcpyDeviceToHost, s));
-    TMAT_HIP(hipStreamSynchronize(s));
+    A.d2h(f255_host, f255, npx * 4);
+    A.d2h(ids_host, ids, nE * sizeof(int32_t));
+    A.d2h(m_host, m, sizeof(int));
+    if (A.finish()) return TMAT_E_HIP;
     const int cap_v = (int)npx + 4, cap_e = 3 * (int)npx + 4;
     std::vector<int32_t> V((size_t)cap_v * 2), E((size_t)cap_e * 2);
     int nv = 0, ne = 0;
-    int rc = dmt_graph_host_sorted(f255_host.data(), fh, fw, t1, t2, ids_host.data(), m_host, V.data(), cap_v, E.data(), cap_e, &nv, &ne,
-                                   kind_host.empty() ? nullptr : kind_host.data(), pers_host.empty() ? nullptr : pers_host.data());
+    int rc = dmt_graph_host_sorted(f255_host, fh, fw, t1, t2, ids_host, *m_host, V.data(), cap_v, E.data(), cap_e, &nv, &ne, kind_host, pers_host);
     row->index = index; row->count = 0; row->total_px = 0; row->avg_px = 0;
     if (!rc)
         rc = tmat_morse_stats(V.data(), nv, E.data(), ne, fh, fw, smooth, min_len, max_len, remove_isolated, pruning_mask, &row->count, &row->total_px,
@@ -476,9 +455,8 @@ int tmat_field_stats_pruned(tmat_handle hd, const float *field, int fh, int fw, 
     if (!c || !field || !row || fh < 2 || fw < 2) { set_error("tmat_field_stats: bad argument"); return TMAT_E_ARG; }
     TMAT_HIP(hipSetDevice(c->device));
     DevScope A(c->ws_pool, c->stream);
-    float *df = A.pooled<float>((size_t)fh * fw);
+    float *df = A.pooled_from(field, (size_t)fh * fw);
     if (!A.ok) return TMAT_E_HIP;
-    TMAT_HIP(hipMemcpyAsync(df, field, (size_t)fh * fw * 4, hipMemcpyHostToDevice, c->stream));
     return field_stats_dev(c, df, fh, fw, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated,
                            pruning_mask, index, row, c->stream);
 }
@@ -497,15 +475,13 @@ int tmat_resize_aa_u16(tmat_handle hd, const uint16_t *imgs, int n, int H, int W
     TMAT_HIP(hipSetDevice(c->device));
     const size_t nin = (size_t)n * H * W, nout = (size_t)n * out_h * out_w;
     DevScope A(c->ws_pool, c->stream);
-    uint16_t *ds = A.pooled<uint16_t>(nin);
+    uint16_t *ds = A.pooled_from(imgs, nin);
     double *dz = A.pooled<double>(nout);
     if (!A.ok) return TMAT_E_HIP;
-    TMAT_HIP(hipMemcpyAsync(ds, imgs, nin * 2, hipMemcpyHostToDevice, c->stream));
     int rc = stack_resize_aa_dev(c, ds, n, H, W, out_h, out_w, dz, nullptr, c->stream);
     if (rc) return rc;
-    TMAT_HIP(hipMemcpyAsync(out, dz, nout * 8, hipMemcpyDeviceToHost, c->stream));
-    TMAT_HIP(hipStreamSynchronize(c->stream));
-    return TMAT_OK;
+    A.d2h(out, dz, nout * 8);
+    return A.finish();
 }
 
 int tmat_analyze_stack(tmat_handle hd, const uint16_t *stack, int Z, int H, int W, int ds_width, int hessian, float graph_thresh_1,
@@ -524,14 +500,13 @@ int tmat_analyze_stack(tmat_handle hd, const uint16_t *stack, int Z, int H, int 
     const size_t nin = (size_t)Z * H * W, npx = (size_t)fh * fw;
     hipStream_t s = c->stream;
     DevScope A(c->ws_pool, s);
-    uint16_t *ds = A.pooled<uint16_t>(nin);
+    uint16_t *ds = A.pooled_from(stack, nin);
     float *vol = A.pooled<float>((size_t)Z * npx), *field = A.pooled<float>(npx);
     if (!A.ok) return TMAT_E_HIP;
-    TMAT_HIP(hipMemcpyAsync(ds, stack, nin * 2, hipMemcpyHostToDevice, s));
     int rc = stack_prepare_dev(c, ds, Z, H, W, fh, fw, vol, s);
     if (!rc) rc = vessel_field_dev(c, vol, Z, fh, fw, hessian, field, nullptr, s);
     if (rc) return rc;
-    if (field_out) TMAT_HIP(hipMemcpyAsync(field_out, field, npx * 4, hipMemcpyDeviceToHost, s));
+    if (!A.d2h(field_out, field, npx * 4)) return TMAT_E_HIP;
     return field_stats_dev(c, field, fh, fw, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px,
                            remove_isolated, nullptr, index, row, s);
 }

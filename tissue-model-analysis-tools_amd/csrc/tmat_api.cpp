@@ -803,13 +803,14 @@ int tmat_unet_predict(tmat_handle h, const float *x, int n, float *y)
     if (!c || !x || !y || n < 0) { set_error("tmat_unet_predict: bad argument"); return TMAT_E_ARG; }
     TMAT_HIP(hipSetDevice(c->device));
     const size_t per = (size_t)c->patch * c->patch;
+    DevScope mem(c->ws_pool, c->stream);       // the handle's patch buffers; the scope only carries the copies
     for (int i0 = 0; i0 < n; i0 += c->max_patches) {
         int k = std::min(c->max_patches, n - i0);
-        TMAT_HIP(hipMemcpyAsync(c->patch_in, x + i0 * per, k * per * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (!mem.h2d(c->patch_in, x + i0 * per, k * per * sizeof(float))) return TMAT_E_HIP;
         int rc = unet_forward_dev(c, c->patch_in, k, c->patch_out, c->stream);
         if (rc) return rc;
-        TMAT_HIP(hipMemcpyAsync(y + i0 * per, c->patch_out, k * per * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        TMAT_HIP(hipStreamSynchronize(c->stream));
+        mem.d2h(y + i0 * per, c->patch_out, k * per * sizeof(float));
+        if (mem.finish()) return TMAT_E_HIP;
     }
     return TMAT_OK;
 }
@@ -823,15 +824,13 @@ int tmat_predict_smooth(tmat_handle h, const float *x, int n, int hh, int ww, do
     TMAT_HIP(hipSetDevice(c->device));
     const size_t per = (size_t)hh * ww;
     DevScope mem(c->ws_pool, c->stream);
-    float *xd = mem.alloc<float>(n * per);
+    float *xd = mem.alloc_from(x, n * per);
     double *pd = mem.alloc<double>(n * per, "hipMalloc(pred)");
     if (!mem.ok) return TMAT_E_HIP;
-    int rc = TMAT_OK;
-    if (!hip_ok(hipMemcpyAsync(xd, x, n * per * sizeof(float), hipMemcpyHostToDevice, c->stream), "H2D")) rc = TMAT_E_HIP;
-    if (!rc) rc = predict_smooth_dev(c, xd, n, hh, ww, pd);
-    if (!rc && !hip_ok(hipMemcpyAsync(pred, pd, n * per * sizeof(double), hipMemcpyDeviceToHost, c->stream), "D2H")) rc = TMAT_E_HIP;
-    if (!hip_ok(hipStreamSynchronize(c->stream), "sync") && !rc) rc = TMAT_E_HIP;
-    return rc;
+    int rc = predict_smooth_dev(c, xd, n, hh, ww, pd);
+    if (rc) return rc;
+    mem.d2h(pred, pd, n * per * sizeof(double));
+    return mem.finish();
 }
 
 int tmat_dev_alloc(tmat_handle h, size_t bytes, void **dev_ptr)
@@ -855,18 +854,18 @@ int tmat_dev_upload(tmat_handle h, void *dev_dst, const void *host_src, size_t b
     Ctx *c = (Ctx *)h;
     if (!c || !dev_dst || !host_src) { set_error("tmat_dev_upload: bad argument"); return TMAT_E_ARG; }
     TMAT_HIP(hipSetDevice(c->device));
-    TMAT_HIP(hipMemcpyAsync(dev_dst, host_src, bytes, hipMemcpyHostToDevice, c->stream));
-    TMAT_HIP(hipStreamSynchronize(c->stream));
-    return TMAT_OK;
+    DevScope mem(c->ws_pool, c->stream);
+    mem.h2d(dev_dst, host_src, bytes);
+    return mem.finish();
 }
 int tmat_dev_download(tmat_handle h, void *host_dst, const void *dev_src, size_t bytes)
 {
     Ctx *c = (Ctx *)h;
     if (!c || !host_dst || !dev_src) { set_error("tmat_dev_download: bad argument"); return TMAT_E_ARG; }
     TMAT_HIP(hipSetDevice(c->device));
-    TMAT_HIP(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, c->stream));
-    TMAT_HIP(hipStreamSynchronize(c->stream));
-    return TMAT_OK;
+    DevScope mem(c->ws_pool, c->stream);
+    mem.d2h(host_dst, dev_src, bytes);
+    return mem.finish();
 }
 
 int tmat_set_input_depth(tmat_handle h, int bits)

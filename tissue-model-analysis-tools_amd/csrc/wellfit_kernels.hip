@@ -229,26 +229,22 @@ int tmat_superellipse_search(tmat_handle hd, const double *xy, const int *offs, 
     const int nblk = (c->se_iters + SE_BLOCK - 1) / SE_BLOCK, npts = offs[n_imgs];
     hipStream_t s = c->stream;
     DevScope mem(c->ws_pool, s);
-    double *dxy = mem.alloc<double>((size_t)npts * 2);
-    int *doffs = mem.alloc<int>((size_t)n_imgs + 1), *dn = mem.alloc<int>(n_imgs), *dbest = mem.alloc<int>(n_imgs);
+    double *dxy = mem.alloc_from(xy, (size_t)npts * 2);
+    int *doffs = mem.alloc_from(offs, (size_t)n_imgs + 1), *dn = mem.alloc_from(n_exp, n_imgs), *dbest = mem.alloc<int>(n_imgs);
     int *dband = mem.alloc<int>((size_t)std::max(cap_band, 1) * 2), *dcount = mem.alloc<int>(1);
     SeBest *partial = mem.alloc<SeBest>((size_t)n_imgs * nblk);
-    if (!mem.ok) return TMAT_E_HIP;
-    int count = 0;
-    if (!hip_ok(hipMemcpyAsync(dxy, xy, (size_t)npts * 2 * sizeof(double), hipMemcpyHostToDevice, s), "H2D") ||
-        !hip_ok(hipMemcpyAsync(doffs, offs, ((size_t)n_imgs + 1) * sizeof(int), hipMemcpyHostToDevice, s), "H2D") ||
-        !hip_ok(hipMemcpyAsync(dn, n_exp, (size_t)n_imgs * sizeof(int), hipMemcpyHostToDevice, s), "H2D") ||
-        !hip_ok(hipMemsetAsync(dcount, 0, sizeof(int), s), "memset")) return TMAT_E_HIP;
+    if (!mem.ok || !mem.check(hipMemsetAsync(dcount, 0, sizeof(int), s), "memset")) return TMAT_E_HIP;
     hipLaunchKernelGGL(se_search_kernel, dim3(nblk, n_imgs), dim3(SE_BLOCK), 0, s, c->se_table, c->se_iters, dxy, doffs, dn, partial, dband, cap_band, dcount);
     hipLaunchKernelGGL(se_final_kernel, dim3(n_imgs), dim3(SE_BLOCK), 0, s, partial, nblk, dbest);
-    if (!hip_ok(hipGetLastError(), "superellipse search launch") ||
-        !hip_ok(hipMemcpyAsync(best, dbest, (size_t)n_imgs * sizeof(int), hipMemcpyDeviceToHost, s), "D2H") ||
-        !hip_ok(hipMemcpyAsync(&count, dcount, sizeof(int), hipMemcpyDeviceToHost, s), "D2H") ||
-        !hip_ok(hipStreamSynchronize(s), "sync")) return TMAT_E_HIP;
-    *n_band = count;
+    int *hcount = mem.host<int>();
+    mem.check(hipGetLastError(), "superellipse search launch");
+    mem.d2h(best, dbest, (size_t)n_imgs * sizeof(int));
+    mem.d2h(hcount, dcount, sizeof(int));
+    if (mem.finish()) return TMAT_E_HIP;
+    const int count = *n_band = *hcount;
     if (count > cap_band) { set_error("tmat_superellipse_search: more undecided candidates than cap_band"); return TMAT_E_CAP; }
     if (count > 0) {
-        if (!hip_ok(hipMemcpy(band_idx, dband, (size_t)count * 2 * sizeof(int), hipMemcpyDeviceToHost), "D2H")) return TMAT_E_HIP;
+        if (!mem.check(hipMemcpy(band_idx, dband, (size_t)count * 2 * sizeof(int), hipMemcpyDeviceToHost), "D2H")) return TMAT_E_HIP;
         // the slots were taken in arrival order: (image, candidate) ascending for the caller
         struct Pair { int img, cand; };
         Pair *pr = (Pair *)band_idx;
@@ -273,26 +269,21 @@ int tmat_superellipse_masks(tmat_handle hd, const double *params, int n_masks, c
     const size_t npx = (size_t)H * W;
     hipStream_t s = c->stream;
     DevScope mem(c->ws_pool, s);
-    double *dpar = mem.alloc<double>((size_t)n_masks * 6), *dxs = mem.alloc<double>(H), *dys = mem.alloc<double>(W);
-    int *dn = mem.alloc<int>(n_masks), *dcount = mem.alloc<int>(1);
+    double *dpar = mem.alloc_from(params, (size_t)n_masks * 6), *dxs = mem.alloc_from(xs, H), *dys = mem.alloc_from(ys, W);
+    int *dn = mem.alloc_from(n_exp, n_masks), *dcount = mem.alloc<int>(1);
     long long *dband = mem.alloc<long long>(std::max(cap_band, 1));
     uint8_t *dout = mem.alloc<uint8_t>((size_t)n_masks * npx);
-    if (!mem.ok) return TMAT_E_HIP;
-    int count = 0;
-    if (!hip_ok(hipMemcpyAsync(dpar, params, (size_t)n_masks * 6 * sizeof(double), hipMemcpyHostToDevice, s), "H2D") ||
-        !hip_ok(hipMemcpyAsync(dxs, xs, (size_t)H * sizeof(double), hipMemcpyHostToDevice, s), "H2D") ||
-        !hip_ok(hipMemcpyAsync(dys, ys, (size_t)W * sizeof(double), hipMemcpyHostToDevice, s), "H2D") ||
-        !hip_ok(hipMemcpyAsync(dn, n_exp, (size_t)n_masks * sizeof(int), hipMemcpyHostToDevice, s), "H2D") ||
-        !hip_ok(hipMemsetAsync(dcount, 0, sizeof(int), s), "memset")) return TMAT_E_HIP;
+    if (!mem.ok || !mem.check(hipMemsetAsync(dcount, 0, sizeof(int), s), "memset")) return TMAT_E_HIP;
     hipLaunchKernelGGL(se_mask_kernel, dim3(se_blocks(npx), n_masks), dim3(SE_BLOCK), 0, s, dpar, dn, dxs, dys, H, W, dout, dband, cap_band, dcount);
-    if (!hip_ok(hipGetLastError(), "superellipse mask launch") ||
-        !hip_ok(hipMemcpyAsync(out, dout, (size_t)n_masks * npx, hipMemcpyDeviceToHost, s), "D2H") ||
-        !hip_ok(hipMemcpyAsync(&count, dcount, sizeof(int), hipMemcpyDeviceToHost, s), "D2H") ||
-        !hip_ok(hipStreamSynchronize(s), "sync")) return TMAT_E_HIP;
-    *n_band = count;
+    int *hcount = mem.host<int>();
+    mem.check(hipGetLastError(), "superellipse mask launch");
+    mem.d2h(out, dout, (size_t)n_masks * npx);
+    mem.d2h(hcount, dcount, sizeof(int));
+    if (mem.finish()) return TMAT_E_HIP;
+    const int count = *n_band = *hcount;
     if (count > cap_band) { set_error("tmat_superellipse_masks: more undecided pixels than cap_band"); return TMAT_E_CAP; }
     if (count > 0) {
-        if (!hip_ok(hipMemcpy(band_px, dband, (size_t)count * sizeof(long long), hipMemcpyDeviceToHost), "D2H")) return TMAT_E_HIP;
+        if (!mem.check(hipMemcpy(band_px, dband, (size_t)count * sizeof(long long), hipMemcpyDeviceToHost), "D2H")) return TMAT_E_HIP;
         std::sort(band_px, band_px + count);
     }
     return TMAT_OK;
@@ -307,14 +298,12 @@ int tmat_resize_nearest_u8(tmat_handle hd, const uint8_t *in, int n, int H, int 
     const size_t npx = (size_t)H * W, onpx = (size_t)out_h * out_w;
     hipStream_t s = c->stream;
     DevScope mem(c->ws_pool, s);
-    uint8_t *din = mem.alloc<uint8_t>((size_t)n * npx), *dout = mem.alloc<uint8_t>((size_t)n * onpx);
+    uint8_t *din = mem.alloc_from(in, (size_t)n * npx), *dout = mem.alloc<uint8_t>((size_t)n * onpx);
     if (!mem.ok) return TMAT_E_HIP;
-    if (!hip_ok(hipMemcpyAsync(din, in, (size_t)n * npx, hipMemcpyHostToDevice, s), "H2D")) return TMAT_E_HIP;
     hipLaunchKernelGGL(se_resize_nearest_kernel, dim3(se_blocks(onpx), n), dim3(SE_BLOCK), 0, s, din, H, W, out_h, out_w, dout);
-    if (!hip_ok(hipGetLastError(), "nearest resize launch") ||
-        !hip_ok(hipMemcpyAsync(out, dout, (size_t)n * onpx, hipMemcpyDeviceToHost, s), "D2H") ||
-        !hip_ok(hipStreamSynchronize(s), "sync")) return TMAT_E_HIP;
-    return TMAT_OK;
+    mem.check(hipGetLastError(), "nearest resize launch");
+    mem.d2h(out, dout, (size_t)n * onpx);
+    return mem.finish();
 }
 
 }  // extern "C"
