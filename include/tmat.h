@@ -275,6 +275,23 @@ int tmat_host_render_tree(const void *background, int bg_dtype, int n, int bh, i
  */
 int tmat_host_render_barcode(const double *bars, int n, int vis_width, uint8_t *rgb_out);
 
+/*
+ * save_vis, the picture rule of the 2-D and Z-stack branches (compute_branches.py:74-78: rescale_intensity(out_range=(0, 255)) and
+ * cv2.imwrite's cast; :315 original_image.png, :331 prediction.png, :347 segmentation_mask.png, :348 distance_transform.png, :228-229
+ * and :303 the two pictures of a stack), for n images of `per` pixels.  Per image, in f64: lo / hi = minimum / maximum over the
+ * non-NaN values; v = ((a - lo) / (hi - lo)) * 255 when hi != lo, min(max(a, 0), 255) otherwise; NaN becomes 0; out = (u8) rint(v),
+ * ties to even.  An image that is all NaN gives an all-zero picture.  Infinities are outside the contract (the extrema, and so the
+ * picture, are then undefined), as they are for tmat_render_tree.
+ * a: (n, per) of dtype TMAT_PIC_*, out: (n, per) u8, both host pointers.  tmat_stage_pictures runs on the handle's device
+ * (vis_kernels.hip; a handle from tmat_create_plain is enough); tmat_host_stage_pictures is its host twin: the same bytes, no GPU.
+ */
+#define TMAT_PIC_U16 0
+#define TMAT_PIC_F32 1
+#define TMAT_PIC_F64 2
+#define TMAT_PIC_U8 3
+int tmat_stage_pictures(tmat_handle h, const void *a, int dtype, int n, size_t per, uint8_t *out);
+int tmat_host_stage_pictures(const void *a, int dtype, int n, size_t per, uint8_t *out);
+
 /* One result row per image, the payload gathered across ranks. */
 typedef struct tmat_row {
     int64_t index;   /* image index in the run                      */
@@ -332,6 +349,45 @@ int tmat_analyze_batch_tree(tmat_handle h, const uint16_t *imgs, int n, int H, i
                             float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
                             int max_branch_length_px, int remove_isolated, int64_t first_index, tmat_row *rows, int vis_width,
                             uint8_t *rgb_out, double *bars_out, int cap_b, int *n_bars);
+
+/*
+ * The extensible form of the entries above: one call that carries any combination of their requests, and the stage pictures.  The
+ * rows are those of the matching entry above, bit for bit, for every combination.
+ *   size                          sizeof(tmat_analyze_opts) as the caller compiled it; TMAT_E_ARG for a size this library does not know
+ *   ds_ratio .. first_index       as tmat_analyze_batch_dev (compute_branches.py:309-312, 401-426)
+ *   well_masks, pruning_masks     as tmat_analyze_batch_masked (:318-337, :359-361, :425), host pointers, either may be NULL
+ *   vis_width .. n_bars           as tmat_analyze_batch_tree (:431-450); rgb_out NULL: no tree, the other four are not read.  With masks
+ *                                 as well, the overlay is the PRUNED graph's tree over the u16 down-sampled (unmasked) image
+ *   stage_out                     NULL, or (n, 4, h, w) u8 host, (h, w) = (round(W ds_ratio), round(H ds_ratio)): save_vis (see
+ *                                 tmat_stage_pictures) of the four arrays the reference dumps, taken from the pass's buffers in HBM --
+ *                                 plane TMAT_STAGE_ORIGINAL the Lanczos-down-sampled image before any well mask (:312-315),
+ *                                 _PREDICTION the network's prediction, of the masked input when there are well masks (:328-331),
+ *                                 _MASK the filtered segmentation mask (:334-337, :347), _WEIGHTED the centre-line weighted prediction
+ *                                 (:341-344, :348 distance_transform.png).  Copied back per pass.
+ * Scratch for the tree and the pictures comes from the handle's tool workspaces, sized on first use; a call without them allocates and
+ * does nothing extra.  tmat_analyze_batch_ex takes host images, tmat_analyze_batch_ex_dev images ALREADY RESIDENT IN HBM.
+ */
+#define TMAT_STAGE_ORIGINAL 0
+#define TMAT_STAGE_PREDICTION 1
+#define TMAT_STAGE_MASK 2
+#define TMAT_STAGE_WEIGHTED 3
+typedef struct tmat_analyze_opts {
+    uint32_t size;
+    double ds_ratio;
+    int ds_width;
+    float graph_thresh_1, graph_thresh_2;
+    int smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated;
+    int64_t first_index;
+    const uint8_t *well_masks, *pruning_masks;
+    int vis_width;
+    uint8_t *rgb_out;
+    double *bars_out;
+    int cap_b;
+    int *n_bars;
+    uint8_t *stage_out;
+} tmat_analyze_opts;
+int tmat_analyze_batch_ex(tmat_handle h, const uint16_t *imgs, int n, int H, int W, const tmat_analyze_opts *o, tmat_row *rows);
+int tmat_analyze_batch_ex_dev(tmat_handle h, const uint16_t *imgs_dev, int n, int H, int W, const tmat_analyze_opts *o, tmat_row *rows);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Z-stack (Sato) branch of analyze_img: reference scripts/compute_branches.py:224-306 (csrc/sato_kernels.hip,

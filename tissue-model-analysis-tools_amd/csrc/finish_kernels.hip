@@ -173,6 +173,21 @@ static void build_tables(FinishTables &t, int H, int W, int oh, int ow)
     zoom_axis_table(W, ow, t.c0, t.c1, t.wc0, t.wc1);
 }
 
+// the first f64 plane of the workspace (cdt; wt and tmp follow, n doubles each, then the per-image lo / hi)
+static double *finish_cdt(void *workspace, size_t n)
+{
+    uint8_t *nskel = (uint8_t *)workspace;
+    int *g = (int *)(((uintptr_t)(nskel + n) + 15) & ~(uintptr_t)15);
+    int *st = g + n;
+    return (double *)(((uintptr_t)(st + 2 * n) + 15) & ~(uintptr_t)15);
+}
+void finish_weighted_view(void *workspace, int k, int H, int W, const double **wt, const double **lo, const double **hi)
+{
+    const size_t n = (size_t)k * H * W;
+    const double *cdt = finish_cdt(workspace, n);
+    *wt = cdt + n; *lo = cdt + 3 * n; *hi = cdt + 3 * n + k;
+}
+
 // pred, dist (k, H, W) f64 device; skel (k, H, W) u8 device -> field (k, oh, ow) f32 (before a17) and f255 (after), device
 int finish_dev(const double *pred, const double *dist, const uint8_t *skel, int k, int H, int W, int oh, int ow, void *workspace,
                float *field_out, float *f255_out, hipStream_t s)
@@ -185,7 +200,7 @@ int finish_dev(const double *pred, const double *dist, const uint8_t *skel, int 
     uint8_t *nskel = (uint8_t *)workspace;
     int *g = (int *)(((uintptr_t)(nskel + n) + 15) & ~(uintptr_t)15);
     int *st = g + n;
-    double *cdt = (double *)(((uintptr_t)(st + 2 * n) + 15) & ~(uintptr_t)15);
+    double *cdt = finish_cdt(workspace, n);
     double *wt = cdt + n, *tmp = wt + n;
     double *lo = tmp + n, *hi = lo + k;
     float *fmn = (float *)(hi + k), *fmx = fmn + k;

@@ -19,6 +19,17 @@ size_t finish_workspace_bytes(int k, int H, int W, int oh, int ow);
 int finish_dev(const double *pred, const double *dist, const uint8_t *skel, int k, int H, int W, int oh, int ow, void *workspace,
                float *field_out, float *f255_out, hipStream_t s);
 void launch_rescale255(const float *field, int k, int npx, float *mn, float *mx, float *out, hipStream_t s);
+// the weighted prediction (k, H, W) f64 and its per-image minimum / maximum inside finish_dev's workspace: valid from finish_dev until
+// the workspace's next finish_dev (the gaussian passes work in the other two f64 planes)
+void finish_weighted_view(void *workspace, int k, int H, int W, const double **wt, const double **lo, const double **hi);
+// vis_kernels.hip: save_vis pictures of (k, per) images of dtype TMAT_PIC_* in HBM -> (k, per) u8; 0, -1 (argument) or -2 (launch)
+size_t vis_scratch_bytes(int k);
+double *vis_scratch_lo(void *scratch, int k);          // lo [k] then hi [k], written by vis_minmax_dev
+int vis_minmax_dev(const void *a, int dtype, int k, size_t per, void *scratch, hipStream_t s);
+int vis_picture_dev(const void *a, int dtype, int k, size_t per, const double *lo, const double *hi, uint8_t *out, hipStream_t s);
+int vis_picture_u16_dev(const uint16_t *a, int k, size_t per, const int *mn, const int *mx, uint8_t *out, hipStream_t s);
+// postproc.cpp: the host twin of vis_minmax_dev + vis_picture_dev, the same bytes
+void vis_pictures_host(const void *a, int dtype, int n, size_t per, uint8_t *out);
 // zproj_kernels.hip: Z projection of n stacks (n, Z, H, W) u16 device -> (n, H, W) u16 (fs / min / max) or f64 (avg / med)
 int zproj_dev(const uint16_t *stacks, int n, int Z, int H, int W, int method, void *out, hipStream_t s);
 }  // namespace tmat

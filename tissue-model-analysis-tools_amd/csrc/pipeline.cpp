@@ -1,5 +1,5 @@
 // Batch drivers of the branching hot path (include/tmat.h): tmat_segment_batch,
-// tmat_postprocess_batch, tmat_analyze_batch(_dev).
+// tmat_postprocess_batch, tmat_analyze_batch(_dev) and its masked / tree / extensible forms, tmat_stage_pictures.
 //
 // Reference control flow: scripts/compute_branches.py:585-594 runs analyze_img one image at a time.
 // Here a run is cut into passes of K images (K = max_patches / patches-per-image).  Per pass the GPU
@@ -138,7 +138,10 @@ static float *patch_in_of(Ctx *c, int slot, const TileGeom &g) { return pre_on_s
 // bg_keep (nullable, the "with tree" form only): the pass's down-sampled images are copied there, b.small itself is rewritten by the next pass
 // well (nullable, the masked form only): the pass's (k, h, w) well masks on the device -- img * well_mask (compute_branches.py:328) in front
 // of the normalisation, as predict() sees it; the pad minimum is taken after it
-static int enqueue_pre(Ctx *c, const uint16_t *imgs_dev, int k, int slot, const TileGeom &g, uint16_t *bg_keep = nullptr, const uint8_t *well = nullptr)
+// orig_pic (nullable, stage pictures only): (k, h, w) u8 on the device for original_image.png (compute_branches.py:315) -- rendered HERE,
+// behind the rescale on its stream: b.small, b.mn and b.mx are single buffers that the front end of the pass after next rewrites
+static int enqueue_pre(Ctx *c, const uint16_t *imgs_dev, int k, int slot, const TileGeom &g, uint16_t *bg_keep = nullptr, const uint8_t *well = nullptr,
+                       uint8_t *orig_pic = nullptr)
 {
     PassBuf &b = c->pass;
     const bool oversize = g.tiles_per_img > c->max_patches;
@@ -149,6 +152,7 @@ static int enqueue_pre(Ctx *c, const uint16_t *imgs_dev, int k, int slot, const 
     launch_lanczos(imgs_dev, k, b.H, b.W, b.h, b.w, b.xi, b.xc, b.yi, b.yc, b.tmp, b.small, c->input_sat, s);
     if (bg_keep) TMAT_HIP(hipMemcpyAsync(bg_keep, b.small, (size_t)k * b.h * b.w * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
     launch_rescale01(b.small, k, (size_t)b.h * b.w, b.mn, b.mx, b.x, s);
+    if (orig_pic && vis_picture_u16_dev(b.small, k, (size_t)b.h * b.w, b.mn, b.mx, orig_pic, s)) { set_error("analyze (pictures): launch failed"); return TMAT_E_HIP; }
     if (well) launch_well_zero_f32(b.x, well, (size_t)k * b.h * b.w, s);
     if (c->norm_on) launch_norm_f32(b.x, (size_t)k * b.h * b.w, c->norm_mean, c->norm_std, s);      // models.py:636-637
     float *mn = (float *)c->scratch, *mx = mn + k;
@@ -273,9 +277,19 @@ struct TreeJob {
     OverlaySeg *dseg; size_t seg_cap; float *dmm; int *doff; uint8_t *drgb;
 };
 
+// The stage pictures of a call (tmat_analyze_batch_ex with stage_out): save_vis of the four arrays the reference dumps, rendered from
+// the pass's own buffers (vis_kernels.hip) and copied to the caller's (n, 4, h, w) array per pass.
+struct StageJob {
+    uint8_t *out;                   // caller's, whole call
+    const uint8_t *orig_all;        // (n, h, w) u8 on the device, written by enqueue_pre
+    uint8_t *pics;                  // (3, K, h, w) u8 on the device: prediction, mask, weighted of one pass
+    void *mm;                       // vis_scratch_bytes(K)
+    int K;
+};
+
 // pruning (nullable, the masked form only): the pass's (k, fh, fw) u8 pruning masks on the host, MorseGraph's pruning_mask per image
 static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_row *rows, PassJob *job, const TreeJob *tree = nullptr, int first_img = 0,
-                          const uint8_t *pruning = nullptr)
+                          const uint8_t *pruning = nullptr, const StageJob *stage = nullptr)
 {
     PassBuf &b = c->pass;
     const int h = b.h, w = b.w;
@@ -318,6 +332,24 @@ static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_ro
         ok = ok && hipMemcpyAsync(b.dmt_kind_host[slot], b.dmt_kind[slot], k * nE, hipMemcpyDeviceToHost, s) == hipSuccess;
         ok = ok && hipMemcpyAsync(b.dmt_pers_host[slot], b.dmt_pers[slot], k * nE * sizeof(float), hipMemcpyDeviceToHost, s) == hipSuccess;
     }
+    if (stage && ok) {
+        // b.pred / b.filt of this slot stay as they are until this job ends; wt and its extrema lie in finish_ws, which only this job uses
+        // (one host job runs at a time); the original picture was finished before the pass's `done` event
+        const double *wt, *wlo, *whi;
+        finish_weighted_view(b.finish_ws, k, h, w, &wt, &wlo, &whi);
+        double *lo = vis_scratch_lo(stage->mm, k), *hi = lo + k;
+        uint8_t *pic[3] = {stage->pics, stage->pics + (size_t)stage->K * per, stage->pics + 2 * (size_t)stage->K * per};
+        ok = vis_minmax_dev(b.pred[slot], TMAT_PIC_F64, k, per, stage->mm, s) == 0 && vis_picture_dev(b.pred[slot], TMAT_PIC_F64, k, per, lo, hi, pic[0], s) == 0 &&
+             vis_minmax_dev(b.filt[slot], TMAT_PIC_U8, k, per, stage->mm, s) == 0 && vis_picture_dev(b.filt[slot], TMAT_PIC_U8, k, per, lo, hi, pic[1], s) == 0 &&
+             vis_picture_dev(wt, TMAT_PIC_F64, k, per, wlo, whi, pic[2], s) == 0;
+        for (int i = 0; i < k && ok; i++) {
+            uint8_t *dst = stage->out + (size_t)(first_img + i) * 4 * per;
+            ok = hipMemcpyAsync(dst + TMAT_STAGE_ORIGINAL * per, stage->orig_all + (size_t)(first_img + i) * per, per, hipMemcpyDeviceToHost, s) == hipSuccess &&
+                 hipMemcpyAsync(dst + TMAT_STAGE_PREDICTION * per, pic[0] + i * per, per, hipMemcpyDeviceToHost, s) == hipSuccess &&
+                 hipMemcpyAsync(dst + TMAT_STAGE_MASK * per, pic[1] + i * per, per, hipMemcpyDeviceToHost, s) == hipSuccess &&
+                 hipMemcpyAsync(dst + TMAT_STAGE_WEIGHTED * per, pic[2] + i * per, per, hipMemcpyDeviceToHost, s) == hipSuccess;
+        }
+    }
     ok = ok && hipStreamSynchronize(s) == hipSuccess;
     if (!ok) { job->rc = TMAT_E_HIP; return; }
     const double t2 = now_s();
@@ -337,7 +369,8 @@ static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_ro
             const int cap_s = std::max(nv, 1);       // a forest has fewer edges than vertices
             tsegs[i].resize((size_t)cap_s * 4); tbranch[i].resize(cap_s);
             int ns = 0;
-            rc = tmat_morse_tree(V.data(), nv, E.data(), ne, gp.fh, gp.fw, gp.smooth, gp.min_len, gp.max_len, gp.remove_isolated, nullptr, tree->sf,
+            rc = tmat_morse_tree(V.data(), nv, E.data(), ne, gp.fh, gp.fw, gp.smooth, gp.min_len, gp.max_len, gp.remove_isolated,
+                                 pruning ? pruning + i * fper : nullptr, tree->sf,
                                  &rows[i].count, &rows[i].total_px, &rows[i].avg_px, tsegs[i].data(), tbranch[i].data(), cap_s,
                                  tree->bars_out + (size_t)(first_img + i) * tree->cap_b * 2, tree->cap_b, &ns, tree->n_bars + first_img + i);
             tsegs[i].resize((size_t)ns * 4); tbranch[i].resize(ns);
@@ -376,7 +409,7 @@ struct TreeReq { int vis_width; uint8_t *rgb_out; double *bars_out; int cap_b; i
 struct MaskReq { const uint8_t *well; const uint8_t *pruning; };
 
 static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width, GraphParams gp,
-                       int64_t first_index, tmat_row *rows, const TreeReq *req = nullptr, const MaskReq *masks = nullptr)
+                       int64_t first_index, tmat_row *rows, const TreeReq *req = nullptr, const MaskReq *masks = nullptr, uint8_t *stage_out = nullptr)
 {
     // compute_branches.py:309-312 hands target_shape = round(shape * ds_ratio) = (round(H r), round(W r)) to cv2.resize as
     // dsize, which cv2 reads as (width, height): the resized image has round(W r) rows and round(H r) columns.  Square
@@ -421,6 +454,16 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
         if (!hip_ok(hipMemcpy(wd, masks->well, (size_t)n * h * w, hipMemcpyHostToDevice), "H2D(well masks)")) return TMAT_E_HIP;
         well_all = wd;
     }
+    StageJob sj{}, *stage = nullptr;
+    if (stage_out) {    // scratch of the stage pictures: tool workspaces as well, sized here before any pass is in flight
+        uint8_t *orig_all = (uint8_t *)ws_get(c, WS_STAGE_ORIG, (size_t)n * h * w);
+        sj.pics = (uint8_t *)ws_get(c, WS_STAGE_PIC, 3 * (size_t)K * h * w);
+        sj.mm = ws_get(c, WS_STAGE_MM, vis_scratch_bytes(K));
+        if (!orig_all || !sj.pics || !sj.mm) return TMAT_E_HIP;
+        sj.out = stage_out; sj.orig_all = orig_all; sj.K = K;
+        stage = &sj;
+    }
+    auto orig_at = [&](int p) { return stage ? const_cast<uint8_t *>(sj.orig_all) + (size_t)p * K * h * w : nullptr; };
     auto well_at = [&](int p) { return well_all ? well_all + (size_t)p * K * h * w : nullptr; };
     auto prune_at = [&](int p) { return pruning ? pruning + (size_t)p * K * gp.fh * gp.fw : nullptr; };
     const int P = (n + K - 1) / K;
@@ -439,9 +482,9 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
     // (order of the calls = order on the second stream: the front end of pass p + 2 in front of the tail of pass p + 1, which only
     // starts when that pass's up path has ended)
     c->down_pending[0] = c->down_pending[1] = false;
-    rc = enqueue_pre(c, img_at(0), cnt(0), 0, g, bg_at(0), well_at(0));
+    rc = enqueue_pre(c, img_at(0), cnt(0), 0, g, bg_at(0), well_at(0), orig_at(0));
     if (!rc) rc = enqueue_down(c, cnt(0), 0, g);
-    if (!rc && P > 1) rc = enqueue_pre(c, img_at(1), cnt(1), 1, g, bg_at(1), well_at(1));
+    if (!rc && P > 1) rc = enqueue_pre(c, img_at(1), cnt(1), 1, g, bg_at(1), well_at(1), orig_at(1));
     if (!rc) rc = enqueue_back(c, cnt(0), 0, g, well_at(0), seg);
     if (!rc && P > 1) rc = enqueue_down(c, cnt(1), 1, g);
     for (int p = 0; p < P && !rc; p++) {
@@ -453,12 +496,12 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
         if (trace_on())
             fprintf(stderr, "[tmat] pass %d/%d (%d images): waited %.1f ms for the GPU, %.1f ms for host jobs of the previous pass\n",
                     p + 1, P, cnt(p), (tw1 - tw0) * 1e3, (now_s() - tw1) * 1e3);
-        if (p + 2 < P && !rc) rc = enqueue_pre(c, img_at(p + 2), cnt(p + 2), slot, g, bg_at(p + 2), well_at(p + 2));
+        if (p + 2 < P && !rc) rc = enqueue_pre(c, img_at(p + 2), cnt(p + 2), slot, g, bg_at(p + 2), well_at(p + 2), orig_at(p + 2));
         if (p + 1 < P && !rc) rc = enqueue_back(c, cnt(p + 1), slot ^ 1, g, well_at(p + 1), seg);
         if (p + 2 < P && !rc) rc = enqueue_down(c, cnt(p + 2), slot, g);
         for (int i = 0; i < cnt(p) && !rc; i++)
             if (!c->pass.conv_host[slot][i]) { set_error("analyze: Zhang thinning did not converge within its launch budget"); rc = TMAT_E_HIP; }
-        if (!rc) jobs[slot].th = std::thread(run_pass_host, c, slot, cnt(p), gp, rows + (size_t)p * K, &jobs[slot], tree, p * K, prune_at(p));
+        if (!rc) jobs[slot].th = std::thread(run_pass_host, c, slot, cnt(p), gp, rows + (size_t)p * K, &jobs[slot], tree, p * K, prune_at(p), stage);
     }
     for (auto &j : jobs) { j.join(); if (j.rc && !rc) rc = j.rc; }
     hipStreamSynchronize(c->stream2);
@@ -845,6 +888,69 @@ int tmat_analyze_batch_tree(tmat_handle hd, const uint16_t *imgs, int n, int H, 
                                               min_branch_length_px, max_branch_length_px, remove_isolated, first_index, rows, vis_width,
                                               rgb_out, bars_out, cap_b, n_bars);
     return rc;
+}
+
+int tmat_analyze_batch_ex_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, const tmat_analyze_opts *o, tmat_row *rows)
+{
+    Ctx *c = (Ctx *)hd;
+    if (c && !has_model(c)) { set_error("tmat_analyze_batch_ex: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
+    if (!o || o->size != (uint32_t)sizeof(tmat_analyze_opts)) { set_error("tmat_analyze_batch_ex: unknown tmat_analyze_opts size"); return TMAT_E_ARG; }
+    if (!c || !imgs_dev || !rows || n < 0 || H < 1 || W < 1 || o->ds_width < 1 ||
+        (o->rgb_out && (o->vis_width < 1 || !o->bars_out || o->cap_b < 0 || !o->n_bars))) {
+        set_error("tmat_analyze_batch_ex: bad argument");
+        return TMAT_E_ARG;
+    }
+    if (n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    GraphParams gp{0, 0, o->graph_thresh_1, o->graph_thresh_2, o->smoothing_window_px, o->min_branch_length_px, o->max_branch_length_px, o->remove_isolated};
+    TreeReq req{o->vis_width, o->rgb_out, o->bars_out, o->cap_b, o->n_bars};
+    MaskReq mr{o->well_masks, o->pruning_masks};
+    return analyze_dev(c, imgs_dev, n, H, W, o->ds_ratio, o->ds_width, gp, o->first_index, rows, o->rgb_out ? &req : nullptr,
+                       (o->well_masks || o->pruning_masks) ? &mr : nullptr, o->stage_out);
+}
+
+int tmat_analyze_batch_ex(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, const tmat_analyze_opts *o, tmat_row *rows)
+{
+    Ctx *c = (Ctx *)hd;
+    if (c && !has_model(c)) { set_error("tmat_analyze_batch_ex: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
+    if (!o || o->size != (uint32_t)sizeof(tmat_analyze_opts)) { set_error("tmat_analyze_batch_ex: unknown tmat_analyze_opts size"); return TMAT_E_ARG; }
+    if (!c || !imgs || !rows || n < 0 || H < 1 || W < 1) { set_error("tmat_analyze_batch_ex: bad argument"); return TMAT_E_ARG; }
+    if (n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    DevScope mem(c->ws_pool, nullptr);       // blocking copy below: nothing to drain
+    uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
+    if (!mem.ok) return TMAT_E_HIP;
+    if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) return TMAT_E_HIP;
+    return tmat_analyze_batch_ex_dev(hd, dimg, n, H, W, o, rows);
+}
+
+// a (n, per) of dtype TMAT_PIC_* -> out (n, per) u8: extrema and picture kernels of vis_kernels.hip, chunked to bound device memory
+int tmat_stage_pictures(tmat_handle hd, const void *a, int dtype, int n, size_t per, uint8_t *out)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!c || !a || !out || n < 0 || per < 1 || dtype < TMAT_PIC_U16 || dtype > TMAT_PIC_U8) { set_error("tmat_stage_pictures: bad argument"); return TMAT_E_ARG; }
+    if (n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    static const size_t esz[4] = {2, 4, 8, 1};
+    const size_t in_bytes = per * esz[dtype];
+    const int K = (int)std::max<size_t>(1, std::min<size_t>(std::min(n, 65535), ((size_t)256 << 20) / in_bytes));     // <= 256 MiB of input per chunk
+    DevScope mem(c->ws_pool, c->stream);
+    void *da = mem.alloc_bytes((size_t)K * in_bytes);
+    uint8_t *dout = mem.alloc<uint8_t>((size_t)K * per);
+    void *mm = mem.alloc_bytes(vis_scratch_bytes(K));
+    if (!mem.ok) return TMAT_E_HIP;
+    for (int i0 = 0; i0 < n; i0 += K) {
+        const int k = std::min(K, n - i0);
+        if (!mem.h2d(da, (const char *)a + (size_t)i0 * in_bytes, (size_t)k * in_bytes)) return TMAT_E_HIP;
+        double *lo = vis_scratch_lo(mm, k);
+        if (vis_minmax_dev(da, dtype, k, per, mm, c->stream) || vis_picture_dev(da, dtype, k, per, lo, lo + k, dout, c->stream)) {
+            set_error("tmat_stage_pictures: kernel launch failed");
+            return TMAT_E_HIP;
+        }
+        mem.d2h(out + (size_t)i0 * per, dout, (size_t)k * per);
+        if (mem.finish()) return TMAT_E_HIP;
+    }
+    return TMAT_OK;
 }
 
 int tmat_analyze_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, double ds_ratio, int ds_width,

@@ -530,6 +530,35 @@ void postprocess_image(const double *pred, int H, int W, int oh, int ow, float *
     resize_aa(wt.data(), H, W, oh, ow, field);
 }
 
+// save_vis (compute_branches.py:74-78) of n images of `per` pixels: the host twin of vis_kernels.hip, the same bytes
+template <typename T>
+static void vis_pictures_t(const T *a, int n, size_t per, uint8_t *out)
+{
+    for (int img = 0; img < n; img++) {
+        const T *p = a + (size_t)img * per;
+        uint8_t *o = out + (size_t)img * per;
+        double lo = std::numeric_limits<double>::infinity(), hi = -lo;
+        for (size_t i = 0; i < per; i++) { const double v = (double)p[i]; lo = v < lo ? v : lo; hi = v > hi ? v : hi; }     // a NaN fails both
+        if (lo > hi) lo = hi = std::numeric_limits<double>::quiet_NaN();
+        const bool scale = hi != lo;
+        for (size_t i = 0; i < per; i++) {
+            const double x = (double)p[i];
+            double v = scale ? ((x - lo) / (hi - lo)) * 255.0 : std::fmin(std::fmax(x, 0.0), 255.0);
+            if (!(v == v)) v = 0.0;
+            o[i] = (uint8_t)(int)std::nearbyint(v);
+        }
+    }
+}
+void vis_pictures_host(const void *a, int dtype, int n, size_t per, uint8_t *out)
+{
+    switch (dtype) {
+    case TMAT_PIC_U16: vis_pictures_t((const uint16_t *)a, n, per, out); break;
+    case TMAT_PIC_F32: vis_pictures_t((const float *)a, n, per, out); break;
+    case TMAT_PIC_F64: vis_pictures_t((const double *)a, n, per, out); break;
+    default: vis_pictures_t((const uint8_t *)a, n, per, out); break;
+    }
+}
+
 }  // namespace tmat
 
 using namespace tmat;
@@ -563,6 +592,12 @@ int tmat_host_postprocess(const double *pred, int H, int W, int oh, int ow, floa
 {
     if (!pred || !field || H < 1 || W < 1 || oh < 1 || ow < 1) { set_error("tmat_host_postprocess: bad argument"); return TMAT_E_ARG; }
     postprocess_image(pred, H, W, oh, ow, field);
+    return TMAT_OK;
+}
+int tmat_host_stage_pictures(const void *a, int dtype, int n, size_t per, uint8_t *out)
+{
+    if (!a || !out || n < 0 || per < 1 || dtype < TMAT_PIC_U16 || dtype > TMAT_PIC_U8) { set_error("tmat_host_stage_pictures: bad argument"); return TMAT_E_ARG; }
+    vis_pictures_host(a, dtype, n, per, out);
     return TMAT_OK;
 }
 }

@@ -119,6 +119,7 @@ enum ToolWs {
     WS_INV_COL,
     WS_TREE_BG, WS_TREE_SEG, WS_TREE_MM, WS_TREE_RGB,                                                                               // tree overlay
     WS_WELL_MASK, WS_WELL_SEG,                                                                                                      // masked batch pipeline
+    WS_STAGE_ORIG, WS_STAGE_PIC, WS_STAGE_MM,                                                                                       // stage pictures of the batch pipeline
     N_TOOL_WS
 };
 

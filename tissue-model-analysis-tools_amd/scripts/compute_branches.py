@@ -11,7 +11,8 @@ branch (:224-306), both on the GPU.
 
 Differences (documented in INTEGRATION.md): images are analysed in batches on the GPU (one process
 per GPU under torch.distributed.run; rows are gathered over RCCL and rank 0 writes the CSV);
---detect-well takes an explicit --well-seed (the reference's random search is unseeded); the PNG image dumps are opt-in (--visualizations;
+--detect-well takes an explicit --well-seed (the reference's random search is unseeded); the PNG image dumps are opt-in (--visualizations:
+rendered on the GPU inside the batched analysis;
 --tree-visualizations [--vis-width N] for the Morse tree and barcode pictures, which are the library's own rasters, not matplotlib's);
 --sato-hessian picks the Hessian of skimage.filters.sato (gaussian_derivatives = scikit-image >= 0.20, what the reference's pinned 0.22.0 runs; gradient = <= 0.19);
 without --image-width-microns (or the config key) the width comes from OME / ImageJ TIFF metadata
@@ -63,7 +64,8 @@ def parse_branching_args(arg_defaults):
     p.add_argument("--vis-width", type=int, default=2000, help="width in pixels of the morse_tree picture (default 2000)")
     p.add_argument("--visualizations", action="store_true",
                    help="also write visualizations/<image>/{original_image,prediction,segmentation_mask,distance_transform}.png "
-                        "(the reference always does; here it is opt-in: it re-runs the image through the staged entry points)")
+                        "(Z stacks: {original_image,vesselness_image}.png; with -w also well_mask.png).  The reference always does; here it is "
+                        "opt-in.  The pictures are rendered on the GPU from the arrays the batched analysis already holds, in the same pass")
     p.add_argument("--sato-hessian", choices=["gaussian_derivatives", "gradient"], default="gaussian_derivatives",
                    help="Z stacks: Hessian of skimage.filters.sato -- gaussian_derivatives (scikit-image >= 0.20, the reference's pinned "
                         "0.22.0) or gradient (scikit-image <= 0.19)")
@@ -262,6 +264,12 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
                 # --detect-well (compute_branches.py:231-243): the well mask of the resized max projection only prunes the graph here
                 pruning = sato.stack_well_masks(handle, st, field.shape, well_seed)[1] if detect_well else None
                 fields[i] = (field, pruning)
+                if vis:
+                    # compute_branches.py:228-229 original_image.png = the max projection, :303 vesselness_image.png: save_vis of the field
+                    # this call has just computed, on the device
+                    vis_dir = out_root / "visualizations" / ids[i]
+                    branches._save_png_unique(handle.stage_pictures(st.max(0)), vis_dir, "original_image.png")
+                    branches._save_png_unique(handle.stage_pictures(field), vis_dir, "vesselness_image.png")
             rows.append((i,) + sato.field_stats(handle, fields[i][0], thresh[0], thresh[1], sw_px, min_px, max_px,
                                                 bool(config.get("remove_isolated_branches", False)), pruning_mask=fields[i][1]))
             if tree_vis:
@@ -276,12 +284,11 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
 
     def load_and_keep(img_id):
         st = load_fn(img_id)
-        if vis:
-            branches.save_stack_visualizations(handle, st, out_root / "visualizations" / img_id, hessian)
-            if detect_well:
-                from PIL import Image
-                well = sato.stack_well_masks(handle, st, sato.dsamp_shape(st.shape, DOWNSAMPLE_WIDTH), well_seed)[0]
-                Image.fromarray((well * 255).astype(np.uint8)).save(out_root / "visualizations" / img_id / "well_mask.png")
+        if vis and detect_well:
+            from PIL import Image
+            (out_root / "visualizations" / img_id).mkdir(parents=True, exist_ok=True)
+            well = sato.stack_well_masks(handle, st, sato.dsamp_shape(st.shape, DOWNSAMPLE_WIDTH), well_seed)[0]
+            Image.fromarray((well * 255).astype(np.uint8)).save(out_root / "visualizations" / img_id / "well_mask.png")
         return st
 
     # one stack per analysis call (chunk=1): a stack is the unit the reference streams, and it can be gigabytes
@@ -383,14 +390,41 @@ def main(args=None):
     vis_width = int(getattr(args, "vis_width", 2000) or 2000)
     suffix_of = {(cfg["thresh1"], cfg["thresh2"]): sfx for cfg, sfx in branches.threshold_grid(config)}
 
+    # --visualizations (compute_branches.py:315, 331, 347, 348, 364): the pictures do not depend on the graph thresholds -- they come out
+    # of the batched call of the first configuration a batch sees (run_sharded hands the same array to every configuration of the grid)
+    vis = bool(getattr(args, "visualizations", False))
+    vis_cache = {}
+
+    def want_pictures(batch):
+        if not vis or vis_cache.get("batch") is batch:
+            return False
+        vis_cache["batch"] = batch
+        return True
+
+    def write_pictures(ids, pictures, well=None):
+        for i, img_id in enumerate(ids):
+            branches.save_stage_pictures(pictures[i], out_root / "visualizations" / img_id, None if well is None else well[i])
+
     def analyze_fn(batch, width_um, thresh, input_bits, ids):
+        pics = want_pictures(batch)
         if tree_vis and not detect_well:
-            rows, overlays, bars = branches.analyze_batch_tree(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh,
-                                                               input_bits=input_bits, vis_width=vis_width)
+            if pics:
+                rows, ex = branches.analyze_batch_ex(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits,
+                                                     tree=True, vis_width=vis_width, stage_pictures=True)
+                overlays, bars = ex["overlays"], ex["bars"]
+                write_pictures(ids, ex["pictures"])
+            else:
+                rows, overlays, bars = branches.analyze_batch_tree(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh,
+                                                                   input_bits=input_bits, vis_width=vis_width)
             for img_id, ov, br in zip(ids, overlays, bars):
                 if len(br) == 0:
                     print(f"No branches found for {img_id}.", flush=True)
                 branches.save_tree_pictures(ov, br, out_root / "visualizations" / img_id, suffix_of[thresh], vis_width)
+            return rows
+        if not detect_well and pics:
+            rows, ex = branches.analyze_batch_ex(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits,
+                                                 stage_pictures=True)
+            write_pictures(ids, ex["pictures"])
             return rows
         if not detect_well:
             return branches.analyze_batch(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits)
@@ -401,9 +435,12 @@ def main(args=None):
             if well_cache.get("batch") is not batch:
                 well_cache.clear()
                 well_cache["batch"] = batch
-            rows, well, pruning = branches.analyze_batch_well(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits,
-                                                              well_seed=well_seed, warn=warn_fn, masks=well_cache.get("masks"))
+            rows, well, pruning, *pictures = branches.analyze_batch_well(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh,
+                                                                         input_bits=input_bits, well_seed=well_seed, warn=warn_fn,
+                                                                         masks=well_cache.get("masks"), stage_pictures=pics)
             well_cache["masks"] = (well, pruning)
+            if pics:
+                write_pictures(ids, pictures[0], well)
             return rows
         # with --tree-visualizations the pictures need the fields themselves: the staged entry points, image by image
         # --detect-well (compute_branches.py:318-337): the fields do not depend on the graph thresholds -- one staged pass per
@@ -413,6 +450,12 @@ def main(args=None):
             well_cache["batch"] = batch
             well_cache["fields"], well_cache["backgrounds"] = branches.well_fields(
                 model.handle, batch, model.ds_ratio, input_bits, well_seed, warn=warn_fn, return_backgrounds=True)
+        if pics:
+            # this route stays staged (its overlays are drawn over the f32 background): the pictures come from one batched call with its masks
+            wells = np.stack([f[2] for f in well_cache["fields"]])
+            _, ex = branches.analyze_batch_ex(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits,
+                                              well_masks=wells, pruning_masks=np.stack([f[1] for f in well_cache["fields"]]), stage_pictures=True)
+            write_pictures(ids, ex["pictures"], wells)
         # the tree of each pruned graph over the image's own down-sampled picture; count, total and average come out of the same
         # call (tmat_morse_tree shares tmat_morse_stats' code), so the rows are well_rows' rows
         rows = []
@@ -424,16 +467,8 @@ def main(args=None):
             rows.append((i,) + stats)
         return rows
 
-    vis = bool(getattr(args, "visualizations", False))
-
-    def load_and_keep(img_id):
-        img = load_fn(img_id)
-        if vis:
-            branches.save_visualizations(model.handle, img, out_root / "visualizations" / img_id, model.ds_ratio, 8 * img.dtype.itemsize)
-        return img
-
     try:
-        gathered = branches.run_sharded(ids, load_and_keep, width_fn, analyze_fn, config, rank, ws,
+        gathered = branches.run_sharded(ids, load_fn, width_fn, analyze_fn, config, rank, ws,
                                         log=lambda m: print(m, flush=True), pass_ids=True)
     except distributed.RankFailed:          # the failing rank has printed the reference's message; every rank exits with code 1
         model.handle.close()

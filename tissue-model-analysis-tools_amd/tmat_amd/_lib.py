@@ -29,6 +29,18 @@ class Row(C.Structure):
     _fields_ = [("index", C.c_int64), ("count", C.c_int64), ("total_px", C.c_double), ("avg_px", C.c_double)]
 
 
+class AnalyzeOpts(C.Structure):
+    """tmat_analyze_opts (include/tmat.h)"""
+    _fields_ = [("size", C.c_uint32), ("ds_ratio", C.c_double), ("ds_width", C.c_int), ("graph_thresh_1", C.c_float), ("graph_thresh_2", C.c_float),
+                ("smoothing_window_px", C.c_int), ("min_branch_length_px", C.c_int), ("max_branch_length_px", C.c_int), ("remove_isolated", C.c_int),
+                ("first_index", C.c_int64), ("well_masks", C.c_void_p), ("pruning_masks", C.c_void_p), ("vis_width", C.c_int),
+                ("rgb_out", C.c_void_p), ("bars_out", C.c_void_p), ("cap_b", C.c_int), ("n_bars", C.c_void_p), ("stage_out", C.c_void_p)]
+
+
+PIC_DTYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2, np.dtype(np.uint8): 3}      # TMAT_PIC_*
+STAGE_PLANES = ("original", "prediction", "mask", "weighted")                                                       # TMAT_STAGE_*
+
+
 def lib():
     """Load libtmat_hip.so once; raise loudly when it is not built."""
     global _lib
@@ -112,6 +124,10 @@ def lib():
     L.tmat_superellipse_masks.argtypes = [vp, vp, i, vp, vp, vp, i, i, vp, vp, i, C.POINTER(i)]
     L.tmat_resize_nearest_u8.argtypes = [vp, vp, i, i, i, i, i, vp]
     L.tmat_analyze_batch_masked.argtypes = [vp, vp, i, i, i, C.c_double, i, f, f, i, i, i, i, C.c_int64, vp, vp, vp]
+    L.tmat_analyze_batch_ex.argtypes = [vp, vp, i, i, i, C.POINTER(AnalyzeOpts), vp]
+    L.tmat_analyze_batch_ex_dev.argtypes = [vp, vp, i, i, i, C.POINTER(AnalyzeOpts), vp]
+    L.tmat_stage_pictures.argtypes = [vp, vp, i, i, sz, vp]
+    L.tmat_host_stage_pictures.argtypes = [vp, i, i, sz, vp]
     L.tmat_prof_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), i]
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -135,6 +151,7 @@ EXPORTS = [
     "tmat_analyze_stack", "tmat_field_stats", "tmat_field_stats_pruned", "tmat_resize_aa_u16", "tmat_cell_area_batch", "tmat_cell_area_masked", "tmat_resize_linear_u16",
     "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi", "tmat_resnet_set_precision", "tmat_conv2d",
     "tmat_roi_plan", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles",
+    "tmat_stage_pictures", "tmat_host_stage_pictures", "tmat_analyze_batch_ex", "tmat_analyze_batch_ex_dev",
 ]
 
 
@@ -312,6 +329,15 @@ class Handle:
                                            ptr(out), ptr(ms)), "tmat_render_tree_timed")
         return out, dict(zip(("upload", "minmax", "render", "copy_back"), (float(v) for v in ms)))
 
+    def stage_pictures(self, a):
+        """tmat_stage_pictures: save_vis of (n, ...) images u16 / f32 / f64 / u8 (bool counts as u8) on the device -> u8 of the same shape;
+        a 2-D array is one image"""
+        a, shape = _stage_pictures_arg(a)
+        out = np.empty(a.shape, np.uint8)
+        if a.shape[0]:
+            check(lib().tmat_stage_pictures(self._h, ptr(a), PIC_DTYPES[a.dtype], a.shape[0], a[0].size, ptr(out)), "tmat_stage_pictures")
+        return out.reshape(shape)
+
     def debug_poison(self, byte_pattern=0xFF):
         """test-only: fill every scratch workspace of the handle with a byte pattern (include/tmat.h:tmat_debug_poison)"""
         check(lib().tmat_debug_poison(self._h, int(byte_pattern)), "tmat_debug_poison")
@@ -439,6 +465,27 @@ def host_render_tree(backgrounds, trees, vis_width=2000):
     check(lib().tmat_host_render_tree(ptr(bg), dt, bg.shape[0], bg.shape[1], bg.shape[2], ptr(segs), ptr(sb), ptr(off), int(vis_width), ptr(out)),
           "tmat_host_render_tree")
     return out
+
+
+def _stage_pictures_arg(a):
+    a = np.asarray(a)
+    shape = a.shape
+    if a.ndim < 2 or a.size == 0:
+        raise ValueError("stage_pictures: expected a non-empty (h, w) image or (n, h, w) batch")
+    if a.dtype == np.bool_:
+        a = a.astype(np.uint8)
+    if a.dtype not in PIC_DTYPES:
+        raise ValueError(f"stage_pictures: dtype {a.dtype} is not one of uint16, float32, float64, uint8")
+    a = np.ascontiguousarray(a)
+    return (a[None] if a.ndim == 2 else a), shape
+
+
+def host_stage_pictures(a):
+    """tmat_host_stage_pictures: the host twin of Handle.stage_pictures (same bytes, no GPU)"""
+    a, shape = _stage_pictures_arg(a)
+    out = np.empty(a.shape, np.uint8)
+    check(lib().tmat_host_stage_pictures(ptr(a), PIC_DTYPES[a.dtype], a.shape[0], a[0].size, ptr(out)), "tmat_host_stage_pictures")
+    return out.reshape(shape)
 
 
 def host_render_barcode(bars, vis_width=2000):

@@ -102,6 +102,94 @@ def analyze_batch_tree(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
     return [(r.index, r.count, r.total_px, r.avg_px) for r in rows], rgb, [bars[i, : nb[i]].copy() for i in range(n)]
 
 
+def analyze_batch_ex(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_width_microns: float, ds_ratio: float = 0.625,
+                     thresh=(5.0, 10.0), first_index: int = 0, input_bits: int = 16, well_masks=None, pruning_masks=None, tree: bool = False,
+                     vis_width: int = 2000, stage_pictures: bool = False, cap_bars: int = 4096):
+    """One batched call with any combination of requests (tmat_analyze_batch_ex): the rows of analyze_batch / analyze_batch_masked /
+    analyze_batch_tree, plus what was asked for.  well_masks (n, h, w), pruning_masks (n, fh, fw): as analyze_batch_masked.  tree: the
+    overlays and bars of analyze_batch_tree (with masks: the pruned graph's tree over the unmasked down-sampled image).
+    stage_pictures: the (n, 4, h, w) u8 pictures of the reference's four image dumps (compute_branches.py:315, 331, 347, 348), planes
+    in _lib.STAGE_PLANES order, rendered inside the pass from its buffers in HBM.
+    Returns (rows, extras) with extras a dict holding "overlays" and "bars" (tree) and "pictures" (stage_pictures)."""
+    imgs = np.ascontiguousarray(imgs, np.uint16)
+    n, H, W = imgs.shape
+    hh, ww = int(round(W * ds_ratio)), int(round(H * ds_ratio))            # cv2 reads dsize as (width, height)
+    fh, fw = dsamp_shape((H, W))
+
+    def as_u8(m, shape, what):
+        if m is None:
+            return None
+        m = np.asarray(m)
+        if m.shape != (n,) + tuple(shape):
+            raise ValueError(f"analyze_batch_ex: {what} have shape {m.shape}, expected {(n,) + tuple(shape)}")
+        return np.ascontiguousarray(m != 0, np.uint8)
+    well = as_u8(well_masks, (hh, ww), "well_masks")
+    pruning = as_u8(pruning_masks, (fh, fw), "pruning_masks")
+    sw_px, min_px, max_px = graph_px_params(config, DOWNSAMPLE_WIDTH, image_width_microns)
+    rows = (_lib.Row * n)()
+    o = _lib.AnalyzeOpts(size=C.sizeof(_lib.AnalyzeOpts), ds_ratio=float(ds_ratio), ds_width=DOWNSAMPLE_WIDTH, graph_thresh_1=float(thresh[0]),
+                         graph_thresh_2=float(thresh[1]), smoothing_window_px=int(sw_px), min_branch_length_px=int(min_px),
+                         max_branch_length_px=int(max_px or 0), remove_isolated=int(bool(config.get("remove_isolated_branches", False))),
+                         first_index=int(first_index), well_masks=None if well is None else well.ctypes.data,
+                         pruning_masks=None if pruning is None else pruning.ctypes.data)
+    extras = {}
+    if stage_pictures:
+        extras["pictures"] = np.empty((n, 4, hh, ww), np.uint8)
+        o.stage_out = extras["pictures"].ctypes.data
+    nb = np.zeros(n, np.int32)
+    if tree:
+        vh, vw = _lib.tree_canvas_shape(hh, ww, vis_width)
+        extras["overlays"] = np.empty((n, vh, vw, 3), np.uint8)
+        o.vis_width, o.rgb_out, o.n_bars = int(vis_width), extras["overlays"].ctypes.data, nb.ctypes.data
+    L = _lib.lib()
+    _lib.check(L.tmat_set_input_depth(handle.raw, int(input_bits)), "tmat_set_input_depth")
+    # a branch holds at least one vertex of its own, so fh * fw bars always suffice: one retry with that capacity when cap_bars is too small
+    for cap in (int(cap_bars), max(int(cap_bars), fh * fw)):
+        bars = np.empty((n, cap if tree else 0, 2), np.float64)
+        if tree:
+            o.bars_out, o.cap_b = bars.ctypes.data, cap
+        rc = L.tmat_analyze_batch_ex(handle.raw, _lib.ptr(imgs), n, H, W, C.byref(o), rows) if n else 0
+        if rc != _lib.E_CAP or cap >= fh * fw:
+            break
+    _lib.check(rc, "tmat_analyze_batch_ex")
+    if tree:
+        extras["bars"] = [bars[i, : nb[i]].copy() for i in range(n)]
+    return [(r.index, r.count, r.total_px, r.avg_px) for r in rows], extras
+
+
+def _save_png_unique(a, vis_dir, name):
+    """a finished u8 picture into vis_dir / name under the reference's "-N" unique-name rule (helper.get_unique_output_filepath)"""
+    import os
+    from pathlib import Path
+    from PIL import Image
+    vis_dir = Path(vis_dir)
+    vis_dir.mkdir(parents=True, exist_ok=True)
+    file = vis_dir / name
+    stem, ext = os.path.splitext(file.name)
+    n = 1
+    while file.exists():
+        n += 1
+        file = vis_dir / f"{stem}-{n}{ext}"
+    Image.fromarray(np.ascontiguousarray(a, np.uint8)).save(file)
+    return str(file)
+
+
+STAGE_PICTURE_FILES = ("original_image.png", "prediction.png", "segmentation_mask.png", "distance_transform.png")
+
+
+def save_stage_pictures(pictures, vis_dir, well_mask=None):
+    """One image's (4, h, w) u8 stage pictures (analyze_batch_ex(stage_pictures=True)["pictures"][i]) as the reference's four files
+    (compute_branches.py:315, 331, 347, 348), and with well_mask (h, w) also well_mask.png = save_vis(well_mask * 255) (:364).
+    Names follow the "-N" unique-name rule.  Returns the written paths."""
+    pictures = np.asarray(pictures)
+    if pictures.ndim != 3 or pictures.shape[0] != 4:
+        raise ValueError(f"save_stage_pictures: expected (4, h, w) pictures, got {pictures.shape}")
+    out = [_save_png_unique(pictures[k], vis_dir, name) for k, name in enumerate(STAGE_PICTURE_FILES)]
+    if well_mask is not None:
+        out.append(_save_png_unique(_lib.host_stage_pictures((np.asarray(well_mask) != 0).astype(np.uint8) * 255), vis_dir, "well_mask.png"))
+    return out
+
+
 def save_tree_pictures(overlay, bars, vis_dir, suffix: str = "", vis_width: int = 2000):
     """morse_tree{suffix}.png (a finished overlay) and barcode{suffix}.png into vis_dir, "-N" unique names; nothing for an image without
     branches (the reference prints "No branches found" and skips its plots, compute_branches.py:426-429).  Returns the written paths."""
@@ -209,12 +297,14 @@ def analyze_batch_masked(handle: _lib.Handle, imgs: np.ndarray, config: dict, im
 
 
 def analyze_batch_well(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_width_microns: float, ds_ratio: float = 0.625,
-                       thresh=(5.0, 10.0), first_index: int = 0, input_bits: int = 16, well_seed: int = 0, warn=print, masks=None):
+                       thresh=(5.0, 10.0), first_index: int = 0, input_bits: int = 16, well_seed: int = 0, warn=print, masks=None,
+                       stage_pictures: bool = False):
     """The --detect-well form of the 2-D branch through the batch pipeline: the rows of well_fields + well_rows.  Lanczos + rescale
     (tmat_preprocess_batch) -> make_well_masks_batch on those images (the superellipse fit of the whole batch on the device) ->
     pruning masks = resize(~shrunken, field shape, order 0) (compute_branches.py:359-361) -> tmat_analyze_batch_masked, which repeats
     the Lanczos pass inside its pipeline.  masks: a (well, pruning) pair from an earlier call on the same images (the masks do not depend
-    on the graph thresholds).  Returns (rows, well (n, h, w) bool, pruning (n, fh, fw) bool)."""
+    on the graph thresholds).  Returns (rows, well (n, h, w) bool, pruning (n, fh, fw) bool); with stage_pictures also the (n, 4, h, w) u8
+    pictures of analyze_batch_ex, out of the same call."""
     from . import well_mask_generation as wmg
     imgs = np.ascontiguousarray(imgs, np.uint16)
     n, H, W = imgs.shape
@@ -229,6 +319,10 @@ def analyze_batch_well(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
         pruning = np.stack([wmg._resize_nearest(np.logical_not(shrunken[i]), fshape) for i in range(n)]).astype(bool)
     else:
         well, pruning = masks
+    if stage_pictures:
+        rows, extras = analyze_batch_ex(handle, imgs, config, image_width_microns, ds_ratio, thresh, first_index, input_bits, well, pruning,
+                                        stage_pictures=True)
+        return rows, well, pruning, extras["pictures"]
     rows = analyze_batch_masked(handle, imgs, config, image_width_microns, ds_ratio, thresh, first_index, input_bits, well, pruning)
     return rows, well, pruning
 
@@ -307,19 +401,13 @@ def run_sharded(ids, load_fn, width_fn, analyze_fn, config: dict, rank: int = 0,
     return {suffix: distributed.gather_rows(results[suffix], n_total=len(ids), failed=failed) for _, suffix in grid}
 
 
-def save_visualizations(handle: _lib.Handle, img: np.ndarray, vis_dir, ds_ratio: float = 0.625, input_bits: int = 16):
-    """The four image dumps of the reference's 2-D branch (compute_branches.py:74-78 save_vis = rescale_intensity to
-    0..255 + cv2.imwrite; :315 original_image.png, :331 prediction.png, :347 segmentation_mask.png, :348
-    distance_transform.png) for one image, through the staged entry points of the same GPU path (segment ->
-    filter + EDT -> medial axis); the centre-line weighting of :341-344 is evaluated here with the scipy call the
-    reference makes.  The barcode / tree pictures (:431-450) are save_tree_visualizations' job.  Returns the written paths."""
-    import os
-    from pathlib import Path
-    from PIL import Image
+def stage_pictures_staged(handle: _lib.Handle, img: np.ndarray, ds_ratio: float = 0.625, input_bits: int = 16):
+    """The four stage pictures of one image the staged way, without the batch pipeline: segment -> filter + EDT -> host medial axis, the
+    centre-line weighting of compute_branches.py:341-344 with the scipy call the reference makes, a host Lanczos for the original, and
+    save_vis (:74-78) in numpy.  Returns [original, prediction, mask, weighted] u8 (h, w) arrays; writes no file.  This is what
+    save_visualizations has always computed, and the independent reference of analyze_batch_ex(stage_pictures=True)."""
     from scipy.ndimage import distance_transform_edt
 
-    vis_dir = Path(vis_dir)
-    vis_dir.mkdir(parents=True, exist_ok=True)
     img = np.ascontiguousarray(img, np.uint16)
     H, W = img.shape
     hh, ww = int(round(W * ds_ratio)), int(round(H * ds_ratio))            # cv2 reads dsize as (width, height)
@@ -334,22 +422,29 @@ def save_visualizations(handle: _lib.Handle, img: np.ndarray, vis_dir, ds_ratio:
     with np.errstate(invalid="ignore", divide="ignore"):
         weighted = pred[0] * (dist[0] / (dist[0] + cdt))
     original = _lib.host_lanczos4_u16(img, (hh, ww))        # uint8 sources: float path, a 1-LSB-level difference in a picture
+    return [save_vis_u8(original), save_vis_u8(pred[0]), save_vis_u8(filt[0].astype(np.float64)), save_vis_u8(weighted)]
 
-    def save_vis(a, name):
-        a = np.asarray(a, np.float64)
+
+def save_vis_u8(a):
+    """save_vis's arithmetic (compute_branches.py:74-78: rescale_intensity to 0..255 and cv2.imwrite's cast) in numpy -> u8"""
+    import warnings
+    a = np.asarray(a, np.float64)
+    with warnings.catch_warnings(), np.errstate(invalid="ignore"):
+        warnings.simplefilter("ignore", RuntimeWarning)         # an all-NaN image
         lo, hi = np.nanmin(a), np.nanmax(a)
         a = np.clip(a, lo, hi)
         a = (a - lo) / (hi - lo) * 255.0 if hi != lo else np.clip(a, 0, 255)
-        file = vis_dir / name
-        stem, ext = os.path.splitext(file.name)
-        n = 1
-        while file.exists():                                # helper.get_unique_output_filepath
-            n += 1
-            file = vis_dir / f"{stem}-{n}{ext}"
-        Image.fromarray(np.rint(np.nan_to_num(a)).astype(np.uint8)).save(file)
-        return str(file)
-    return [save_vis(original, "original_image.png"), save_vis(pred[0], "prediction.png"),
-            save_vis(filt[0].astype(np.float64), "segmentation_mask.png"), save_vis(weighted, "distance_transform.png")]
+    return np.rint(np.nan_to_num(a)).astype(np.uint8)
+
+
+def save_visualizations(handle: _lib.Handle, img: np.ndarray, vis_dir, ds_ratio: float = 0.625, input_bits: int = 16):
+    """The four image dumps of the reference's 2-D branch (compute_branches.py:74-78 save_vis = rescale_intensity to
+    0..255 + cv2.imwrite; :315 original_image.png, :331 prediction.png, :347 segmentation_mask.png, :348
+    distance_transform.png) for one image, through the staged entry points of the same GPU path (stage_pictures_staged: a second
+    pass over the image beside the batch pipeline; analyze_batch_ex(stage_pictures=True) + save_stage_pictures take them out of the
+    pipeline's own pass).  The barcode / tree pictures (:431-450) are save_tree_visualizations' job.  Returns the written paths."""
+    return [_save_png_unique(a, vis_dir, name)
+            for a, name in zip(stage_pictures_staged(handle, img, ds_ratio, input_bits), STAGE_PICTURE_FILES)]
 
 
 def save_stack_visualizations(handle: _lib.Handle, stack: np.ndarray, vis_dir, hessian: str = "gaussian_derivatives"):
