@@ -707,6 +707,19 @@ int tmat_roi_plan(int hh, int ww, int patch, int n_up, const int *channels, int 
                   int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full);
 
 /*
+ * tmat_roi_plan returns the NESTED rectangles: every producer covers its consumer's rounded rectangle plus the taps' reach and rounds
+ * its columns again (what TMAT_ROI_TIGHT=0 at tmat_create launches).  tmat_roi_plan_tight returns the TIGHT rectangles of the same
+ * classes, patch order and layers, which the tiled entry points launch by default: every layer computes its own need -- the exact
+ * dependency closure of the rectangle the blend reads -- with the columns rounded outwards once by the same rule (first column a
+ * multiple of 4; width a multiple of 8, or of 4 below 64 pixels a side, or the whole row), rows exact.  The final convolution's
+ * rectangle is the same in both.  A pixel of a tight rectangle outside the need may be computed from operands nobody wrote; nothing
+ * the blend reads depends on it.  A tight rectangle lies inside the nested one; mac_planned is that of the rectangles returned.
+ * Neither export looks at the environment.
+ */
+int tmat_roi_plan_tight(int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
+                        int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full);
+
+/*
  * The same plan continued through the down path (classes and patch order are those of tmat_roi_plan): from the rectangle of the
  * bottleneck tensor that up block 0 reads back to the input window.  TMAT_ROI_DOWN at tmat_create is a bit mask of what the tiled entry
  * points run in this form (default 3; 0: the whole down path full-frame; TMAT_ROI=0 switches all region forms off):

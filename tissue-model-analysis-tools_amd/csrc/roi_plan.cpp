@@ -32,6 +32,14 @@ Iv align_cols(Iv v, int R)
     return Iv{lo, hi};
 }
 Iv round_cols(Iv v, int R, bool exact) { return exact ? v : align_cols(v, R); }
+// align_cols kept inside `outer`, a rectangle of that form around v: a width that is 4 short of a multiple of 8 grows to the left where
+// outer has the room, else to the right (outer is 4 wider than the 4-aligned v at least, on one side or the other)
+Iv align_cols_in(Iv v, int R, Iv outer)
+{
+    Iv q = align_cols(v, R);
+    if (q.lo < outer.lo) q = Iv{q.lo + 4, q.hi + 4};
+    return q;
+}
 Iv align_to(Iv v, int al, int R) { return Iv{v.lo / al * al, std::min(R, (v.hi + al - 1) / al * al)}; }
 
 // one class: rows[l] / cols[l] for every layer, from the interval of final outputs the blend reads on each axis
@@ -222,7 +230,7 @@ bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_cl
         std::fill(out.tile_class.begin(), out.tile_class.end(), 0);
         for (int t = 0; t < g.tiles_per_img; t++) out.tile_rank[t] = t;
         std::fill(out.class_count, out.class_count + ROI_MAX_CLASSES, 0);
-        for (int l = 0; l < out.n_layers; l++) out.mac_planned[l] = out.mac_full[l];
+        for (int l = 0; l < out.n_layers; l++) out.mac_planned[l] = out.mac_planned_tight[l] = out.mac_full[l];
         return true;
     }
     out.n_classes = (int)keys.size();
@@ -238,6 +246,20 @@ bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_cl
             out.rect[l][k] = q;
             out.mac_planned[l] += mpp[l] * q.rh * q.rw * out.class_count[k];
         }
+        // The tight form: every layer rounds ITS OWN need -- the exact walk, as the down plan does (roi_plan_down) -- instead of growing
+        // from its consumer's rounded rectangle, whose extra columns would otherwise be rounded again in every producer.  Rows are never
+        // rounded.  The final convolution keeps its whole 8 x 16 blocks.
+        Iv er[ROI_MAX_LAYERS], ec[ROI_MAX_LAYERS];
+        if (!empty) walk_back(keys[k].r, keys[k].c, ws, n_up, er, ec, true);
+        for (int l = 0; l < out.n_layers; l++) {
+            RoiRect q = out.rect[l][k];
+            if (!empty && l + 1 < out.n_layers) {
+                const Iv c = align_cols_in(ec[l], out.res[l], cols[l]);
+                q = RoiRect{er[l].lo, c.lo, er[l].hi - er[l].lo, c.hi - c.lo};
+            }
+            out.rect_tight[l][k] = q;
+            out.mac_planned_tight[l] += mpp[l] * q.rh * q.rw * out.class_count[k];
+        }
     }
     return true;
 }
@@ -246,8 +268,8 @@ bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_cl
 
 using namespace tmat;
 
-extern "C" int tmat_roi_plan(int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
-                             int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full)
+static int roi_plan_export(bool tight, int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
+                           int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full)
 {
     if (!channels || !tiles_per_img || !n_classes || !tile_class || !tile_rank || !class_count || !rects || !mac_planned || !mac_full ||
         max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
@@ -263,14 +285,30 @@ extern "C" int tmat_roi_plan(int hh, int ww, int patch, int n_up, const int *cha
     for (int k = 0; k < max_classes; k++) class_count[k] = k < p.n_classes ? p.class_count[k] : 0;
     for (int l = 0; l < p.n_layers; l++) {
         for (int k = 0; k < max_classes; k++) {
-            const RoiRect q = k < p.n_classes ? p.rect[l][k] : RoiRect{0, 0, 0, 0};
+            const RoiRect q = k < p.n_classes ? (tight ? p.rect_tight : p.rect)[l][k] : RoiRect{0, 0, 0, 0};
             int *o = rects + ((size_t)l * max_classes + k) * 4;
             o[0] = q.y0; o[1] = q.x0; o[2] = q.rh; o[3] = q.rw;
         }
-        mac_planned[l] = p.mac_planned[l];
+        mac_planned[l] = tight ? p.mac_planned_tight[l] : p.mac_planned[l];
         mac_full[l] = p.mac_full[l];
     }
     return TMAT_OK;
+}
+
+// the nested rectangles (what TMAT_ROI_TIGHT=0 launches), whatever the environment says
+extern "C" int tmat_roi_plan(int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
+                             int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full)
+{
+    return roi_plan_export(false, hh, ww, patch, n_up, channels, max_classes, tiles_cap, tiles_per_img, n_classes, tile_class, tile_rank,
+                           class_count, rects, mac_planned, mac_full);
+}
+
+// the same plan with the tight rectangles (the default of the tiled entry points)
+extern "C" int tmat_roi_plan_tight(int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
+                                   int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full)
+{
+    return roi_plan_export(true, hh, ww, patch, n_up, channels, max_classes, tiles_cap, tiles_per_img, n_classes, tile_class, tile_rank,
+                           class_count, rects, mac_planned, mac_full);
 }
 
 // The down-path tables of the same plan (roi_plan_down): rects and needs [6 n_down + 4][max_classes][4] as (y0, x0, rows, columns),

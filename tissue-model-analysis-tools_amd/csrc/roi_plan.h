@@ -58,8 +58,19 @@ struct RoiPlan {
     // 3 j + 1: its residual 1x1, 3 j + 2: its second 3x3, 3 n_up: the final convolution (stored pixels; whole 8 x 16 blocks of final_kernel)
     int res[ROI_MAX_LAYERS] = {};               // side of the square a layer enumerates
     RoiRect rect[ROI_MAX_LAYERS][ROI_MAX_CLASSES] = {};
+    // The TIGHT rectangles of the same layers and classes, what the tiled entry points launch by default.  rect above is NESTED: a
+    // producer covers its consumer's ROUNDED rectangle plus the taps, and rounds again, so the columns drift outwards layer after layer.
+    // Here a layer's rectangle is its own need -- the exact dependency closure of `read`, walk_back(..., exact) -- with the columns rounded
+    // outwards once by the same rule (rows exact; the final convolution keeps rect's whole 8 x 16 blocks).  The contract is the down
+    // plan's: a pixel of a rectangle outside the need may be computed from operands nobody wrote (the kernels address every tensor by
+    // full-frame position, so such a read lands on an in-bounds word of the workspace), and nothing needed depends on it.
+    // rect_tight[l][k] lies inside rect[l][k].
+    RoiRect rect_tight[ROI_MAX_LAYERS][ROI_MAX_CLASSES] = {};
+    bool tight = false;                         // which set up_rects() names: set by the caller that launches (TMAT_ROI_TIGHT, tmat_api.cpp:roi_attach)
+    const RoiRect *up_rects(int l) const { return tight ? rect_tight[l] : rect[l]; }
     RoiRect read[ROI_MAX_CLASSES] = {};         // patch ∩ interior: the output pixels the blend reads of a patch of the class
     double mac_planned[ROI_MAX_LAYERS] = {}, mac_full[ROI_MAX_LAYERS] = {};      // multiply-accumulates per image
+    double mac_planned_tight[ROI_MAX_LAYERS] = {};                               // the same of rect_tight
     RoiDownPlan down;                           // filled by roi_plan_down
 };
 

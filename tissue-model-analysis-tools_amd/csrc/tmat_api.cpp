@@ -343,7 +343,8 @@ static RoiSegs roi_segs_of(const RoiPlan &p, const RoiRect *rects, int k)
     }
     return r;
 }
-static RoiSegs roi_segs(const RoiPlan &p, int l, int k) { return roi_segs_of(p, p.rect[l], k); }
+// (of the set of up-path rectangles the handle launches: RoiPlan::up_rects)
+static RoiSegs roi_segs(const RoiPlan &p, int l, int k) { return roi_segs_of(p, p.up_rects(l), k); }
 
 // Down path (memory-bound kernels + small pointwise GEMMs): X (n, P, P) -> dout (n, P/16, P/16, f_deep)
 // plan (tiled callers; null: whole patches): with a down plan (roi_plan.h:RoiDownPlan) the kernels named by c->roi_down compute only what
@@ -478,6 +479,7 @@ const RoiPlan *roi_attach(Ctx *c, TileGeom &g)
         e->plan.hh = g.hh; e->plan.ww = g.ww; e->plan.ws = g.ws; e->plan.n_classes = 0;       // remembered: this geometry stays full-frame
         return nullptr;
     }
+    e->plan.tight = c->roi_tight;
     if (c->roi_down && c->down.size() <= (size_t)ROI_MAX_DOWN) {      // the down-path tables (a geometry they do not take keeps the down path full-frame)
         int dchan[ROI_MAX_DOWN + 1];
         unsigned fused = 0;
@@ -660,6 +662,7 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     c->max_patches = max_patches > 0 ? max_patches : 400;
     if (const char *e = getenv("TMAT_FUSED_SEP")) c->fused_sep = atoi(e) != 0;
     if (const char *e = getenv("TMAT_ROI")) c->roi_on = atoi(e) != 0;
+    if (const char *e = getenv("TMAT_ROI_TIGHT")) c->roi_tight = atoi(e) != 0;
     if (const char *e = getenv("TMAT_ROI_DOWN")) {
         // a bit mask of bit 0 (the unfused level and the small kernels) and bit 1 (the fused separable layers' tile tables): anything else
         // is an error, not a silent full-frame run

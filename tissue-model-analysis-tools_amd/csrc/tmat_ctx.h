@@ -192,6 +192,8 @@ struct Ctx {
     // region form of the tiled up path (roi_plan.h): plans per image geometry, made on first use, with the device table of the class-major
     // patch order (TileGeom::order).  TMAT_ROI=0: whole patches in every layer, image-major order
     bool roi_on = true;
+    // TMAT_ROI_TIGHT: the up path launches the tight rectangles (RoiPlan::rect_tight: every layer rounds its own need); 0: the nested ones
+    bool roi_tight = true;
     // TMAT_ROI_DOWN: what of the down path the tiled entry points run in region form too (roi_plan.h:RoiDownPlan).  Bit 0: the unfused
     // level, the residual 1x1 layers, the stem at the even pixels, the pooling fix-ups.  Bit 1: the fused separable layers visit only
     // the tiles of their rectangles (RoiEntry::tabs).  0: the down path stays full-frame

@@ -150,7 +150,7 @@ EXPORTS = [
     "tmat_set_gaussian_table", "tmat_host_gaussian_kernel1d", "tmat_gaussian_f32", "tmat_sato_batch", "tmat_stack_prepare", "tmat_vessel_field",
     "tmat_analyze_stack", "tmat_field_stats", "tmat_field_stats_pruned", "tmat_resize_aa_u16", "tmat_cell_area_batch", "tmat_cell_area_masked", "tmat_resize_linear_u16",
     "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi", "tmat_resnet_set_precision", "tmat_conv2d",
-    "tmat_roi_plan", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles",
+    "tmat_roi_plan", "tmat_roi_plan_tight", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles",
     "tmat_stage_pictures", "tmat_host_stage_pictures", "tmat_analyze_batch_ex", "tmat_analyze_batch_ex_dev",
 ]
 
@@ -498,12 +498,14 @@ def host_render_barcode(bars, vis_width=2000):
 
 
 # -- host pixel stages (csrc/postproc.cpp); exposed for stage-wise parity tests --------------------
-def roi_plan(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), max_classes=16):
+def roi_plan(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), max_classes=16, _export="tmat_roi_plan"):
     """tmat_roi_plan (include/tmat.h): the region plan of the UNet up path for an (hh, ww) image; host arithmetic, no GPU.
+    The NESTED rectangles (TMAT_ROI_TIGHT=0); roi_plan_tight returns the ones launched by default.
     Returns a dict: tiles_per_img, n_classes (0: fall-back "everything"), tile_class / tile_rank [tiles_per_img], class_count [max_classes],
     rects [3 n_up + 1][max_classes][4] (y0, x0, rows, columns), mac_planned / mac_full [3 n_up + 1]."""
     L = lib()
-    L.tmat_roi_plan.argtypes = [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] * 8
+    fn = getattr(L, _export)
+    fn.argtypes = [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] * 8
     n_up = len(channels) - 1
     aug = (patch + 1) // 2
     cap = 8 * ((hh + 2 * aug - patch) // (patch // 2) + 1) * ((ww + 2 * aug - patch) // (patch // 2) + 1)
@@ -513,11 +515,17 @@ def roi_plan(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), max_classes=1
     ccount = np.zeros(max_classes, np.int32)
     rects = np.zeros((3 * n_up + 1, max_classes, 4), np.int32)
     mp, mf = np.zeros(3 * n_up + 1), np.zeros(3 * n_up + 1)
-    check(L.tmat_roi_plan(hh, ww, patch, n_up, ptr(ch), max_classes, cap, ptr(tpi), ptr(ncls), ptr(tcls), ptr(trank), ptr(ccount),
-                          ptr(rects), ptr(mp), ptr(mf)), "roi_plan")
+    check(fn(hh, ww, patch, n_up, ptr(ch), max_classes, cap, ptr(tpi), ptr(ncls), ptr(tcls), ptr(trank), ptr(ccount),
+             ptr(rects), ptr(mp), ptr(mf)), _export[5:])
     n = int(tpi[0])
     return dict(tiles_per_img=n, n_classes=int(ncls[0]), tile_class=tcls[:n], tile_rank=trank[:n], class_count=ccount, rects=rects,
                 mac_planned=mp, mac_full=mf)
+
+
+def roi_plan_tight(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), max_classes=16):
+    """tmat_roi_plan_tight (include/tmat.h): roi_plan's classes and patch order with the TIGHT rectangles -- every layer's own need, its
+    columns rounded once -- that the tiled entry points launch by default.  Same dict as roi_plan."""
+    return roi_plan(hh, ww, patch, channels, max_classes, _export="tmat_roi_plan_tight")
 
 
 def roi_plan_down(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3, max_classes=16):
