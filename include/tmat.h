@@ -579,6 +579,24 @@ int tmat_resnet_set_precision(tmat_handle h, int mode);
  */
 int tmat_conv2d(tmat_handle h, int prec, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int stride, int cout,
                 const float *scale, const float *shift, const float *resid, int relu_in, int relu_out, float *out);
+/*
+ * Stage-wise test entry point of the REGION form of that kernel (conv_mfma_kernel<..., ROI>, what the tiled entry points launch on the up
+ * path): the same contract, f32 only, stride 1, on host buffers, with a segment table.  segs: nseg <= 16 segments of six ints
+ * (p0, np, y0, x0, rh, rw), ascending and disjoint in the patches: the patches [p0, p0 + np) compute the rectangle of rh rows and rw >= 2
+ * columns from (y0, x0) of their output and nothing else.  nseg == 0: the full-frame launch of the same convolution.
+ *   rs (0 or 1): resid (nullable) is (n, hh >> rs, ww >> rs, cout) and pixel (y, x) adds resid[y >> rs][x >> rs] (hh, ww even for rs 1).
+ *   subpixel != 0 (ksize 3, no resid, no out_relu): the 3x3 convolution over the 2x nearest-upsampled x in its sub-pixel form, the weights
+ *     pre-summed per output parity class by the function the network's own packing uses; out is (n, 2 hh, 2 ww, cout) and the segments
+ *     enumerate STORED pixels (hh x ww): stored pixel (i, j) makes the outputs (2 i + {0, 1}, 2 j + {0, 1}).
+ *   out is filled by the CALLER and comes back with the computed pixels replaced: a word outside the rectangles keeps what it held.
+ *   out_relu (nullable; caller-filled likewise): the activated copy max(v, +0) that the up path's second convolutions write.
+ * Any first column and any width are taken: the epilogue runs its row-uniform form where a group of 4 or 8 pixels lies in one row, its
+ * row-split form on other widths >= 8 and the per-lane form below 8; the prologue is row-uniform for widths that are multiples of 8 and
+ * per-lane otherwise.  Inside the rectangles the bits are those of the full-frame launch.
+ */
+int tmat_conv2d_roi(tmat_handle h, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int subpixel, int cout,
+                    const float *scale, const float *shift, const float *resid, int rs, int relu_in, int relu_out, const int *segs, int nseg,
+                    float *out, float *out_relu);
 
 /* device memory helpers so a ctypes host can stage inputs in HBM without torch; upload and download are ordered on the handle's
  * stream (a download sees the work queued before it, e.g. tmat_zproj_dev) and return when the copy is done */
@@ -709,14 +727,20 @@ int tmat_roi_plan(int hh, int ww, int patch, int n_up, const int *channels, int 
 /*
  * tmat_roi_plan returns the NESTED rectangles: every producer covers its consumer's rounded rectangle plus the taps' reach and rounds
  * its columns again (what TMAT_ROI_TIGHT=0 at tmat_create launches).  tmat_roi_plan_tight returns the TIGHT rectangles of the same
- * classes, patch order and layers, which the tiled entry points launch by default: every layer computes its own need -- the exact
+ * classes, patch order and layers (what TMAT_ROI_EXACT=0 at tmat_create launches): every layer computes its own need -- the exact
  * dependency closure of the rectangle the blend reads -- with the columns rounded outwards once by the same rule (first column a
  * multiple of 4; width a multiple of 8, or of 4 below 64 pixels a side, or the whole row), rows exact.  The final convolution's
  * rectangle is the same in both.  A pixel of a tight rectangle outside the need may be computed from operands nobody wrote; nothing
  * the blend reads depends on it.  A tight rectangle lies inside the nested one; mac_planned is that of the rectangles returned.
- * Neither export looks at the environment.
+ * tmat_roi_plan_exact returns the EXACT rectangles, which the tiled entry points launch by default (TMAT_ROI_EXACT, read at tmat_create,
+ * default on; it has effect only while TMAT_ROI and TMAT_ROI_TIGHT are on): in every layer but the final convolution the rectangle IS
+ * the need, rows and columns, with no rounding -- odd first columns and odd widths are the normal case, and the region form of the
+ * convolution kernel takes them (tmat_conv2d_roi; the sub-pixel layers' reads follow the parity of their outputs).  An exact rectangle lies inside the tight one.
+ * No export looks at the environment.
  */
 int tmat_roi_plan_tight(int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
+                        int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full);
+int tmat_roi_plan_exact(int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
                         int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full);
 
 /*

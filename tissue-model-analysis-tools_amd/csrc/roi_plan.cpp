@@ -44,7 +44,11 @@ Iv align_to(Iv v, int al, int R) { return Iv{v.lo / al * al, std::min(R, (v.hi +
 
 // one class: rows[l] / cols[l] for every layer, from the interval of final outputs the blend reads on each axis
 // exact: no rounding -- the pixels the blend DEPENDS on (the down plan starts from those: roi_plan_down)
-void walk_back(Iv orow, Iv ocol, int ws, int n_up, Iv *rows, Iv *cols, bool exact = false)
+// parity (with exact): a sub-pixel layer's read of the previous block's output follows the parity of its outputs -- output 2 i + p sees
+// the stored pixels i + p - 1 and i + p, so the outputs [lo, hi) see [(lo - 1) >> 1, (hi >> 1) + 1) -- where the plain walk takes one pixel
+// around the stored pixels that make those outputs (one more on a side whose first output is odd / whose last is even).  The exact
+// rectangles of the up plan use it; the tight rectangles and the down plan keep the plain walk they were built on.
+void walk_back(Iv orow, Iv ocol, int ws, int n_up, Iv *rows, Iv *cols, bool exact = false, bool parity = false)
 {
 
     const int L = 3 * n_up + 1;
@@ -65,8 +69,9 @@ void walk_back(Iv orow, Iv ocol, int ws, int n_up, Iv *rows, Iv *cols, bool exac
         const Iv c1r = j ? halve(t1r) : t1r, c1c = round_cols(j ? halve(t1c) : t1c, Hs, exact);
         rows[3 * j] = c1r; cols[3 * j] = c1c;
         // what the block reads of the previous block's output: the residual 1x1 its plain form, the first convolution its activated copy
-        need_r = hull(rsr, dilate(c1r, 1, Hs));
-        need_c = hull(rsc, dilate(c1c, 1, Hs));
+        const bool sub = exact && parity && j;
+        need_r = hull(rsr, sub ? clip(Iv{(t1r.lo - 1) >> 1, (t1r.hi >> 1) + 1}, Hs) : dilate(c1r, 1, Hs));
+        need_c = hull(rsc, sub ? clip(Iv{(t1c.lo - 1) >> 1, (t1c.hi >> 1) + 1}, Hs) : dilate(c1c, 1, Hs));
         R = Hs;
     }
 }
@@ -230,7 +235,7 @@ bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_cl
         std::fill(out.tile_class.begin(), out.tile_class.end(), 0);
         for (int t = 0; t < g.tiles_per_img; t++) out.tile_rank[t] = t;
         std::fill(out.class_count, out.class_count + ROI_MAX_CLASSES, 0);
-        for (int l = 0; l < out.n_layers; l++) out.mac_planned[l] = out.mac_planned_tight[l] = out.mac_full[l];
+        for (int l = 0; l < out.n_layers; l++) out.mac_planned[l] = out.mac_planned_tight[l] = out.mac_planned_exact[l] = out.mac_full[l];
         return true;
     }
     out.n_classes = (int)keys.size();
@@ -251,6 +256,8 @@ bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_cl
         // rounded.  The final convolution keeps its whole 8 x 16 blocks.
         Iv er[ROI_MAX_LAYERS], ec[ROI_MAX_LAYERS];
         if (!empty) walk_back(keys[k].r, keys[k].c, ws, n_up, er, ec, true);
+        Iv xr[ROI_MAX_LAYERS], xc[ROI_MAX_LAYERS];          // the need with the sub-pixel layers' parity: the exact rectangles
+        if (!empty) walk_back(keys[k].r, keys[k].c, ws, n_up, xr, xc, true, true);
         for (int l = 0; l < out.n_layers; l++) {
             RoiRect q = out.rect[l][k];
             if (!empty && l + 1 < out.n_layers) {
@@ -259,6 +266,11 @@ bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_cl
             }
             out.rect_tight[l][k] = q;
             out.mac_planned_tight[l] += mpp[l] * q.rh * q.rw * out.class_count[k];
+            // The exact form: the need itself (conv_mfma_kernel<..., ROI> takes any first column and any width)
+            if (!empty && l + 1 < out.n_layers && !((ROI_EXACT_KEEP_TIGHT >> l) & 1u))
+                q = RoiRect{xr[l].lo, xc[l].lo, xr[l].hi - xr[l].lo, xc[l].hi - xc[l].lo};
+            out.rect_exact[l][k] = q;
+            out.mac_planned_exact[l] += mpp[l] * q.rh * q.rw * out.class_count[k];
         }
     }
     return true;
@@ -268,7 +280,7 @@ bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_cl
 
 using namespace tmat;
 
-static int roi_plan_export(bool tight, int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
+static int roi_plan_export(int set, int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
                            int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full)
 {
     if (!channels || !tiles_per_img || !n_classes || !tile_class || !tile_rank || !class_count || !rects || !mac_planned || !mac_full ||
@@ -285,11 +297,11 @@ static int roi_plan_export(bool tight, int hh, int ww, int patch, int n_up, cons
     for (int k = 0; k < max_classes; k++) class_count[k] = k < p.n_classes ? p.class_count[k] : 0;
     for (int l = 0; l < p.n_layers; l++) {
         for (int k = 0; k < max_classes; k++) {
-            const RoiRect q = k < p.n_classes ? (tight ? p.rect_tight : p.rect)[l][k] : RoiRect{0, 0, 0, 0};
+            const RoiRect q = k < p.n_classes ? (set == 2 ? p.rect_exact : set == 1 ? p.rect_tight : p.rect)[l][k] : RoiRect{0, 0, 0, 0};
             int *o = rects + ((size_t)l * max_classes + k) * 4;
             o[0] = q.y0; o[1] = q.x0; o[2] = q.rh; o[3] = q.rw;
         }
-        mac_planned[l] = tight ? p.mac_planned_tight[l] : p.mac_planned[l];
+        mac_planned[l] = set == 2 ? p.mac_planned_exact[l] : set == 1 ? p.mac_planned_tight[l] : p.mac_planned[l];
         mac_full[l] = p.mac_full[l];
     }
     return TMAT_OK;
@@ -299,15 +311,23 @@ static int roi_plan_export(bool tight, int hh, int ww, int patch, int n_up, cons
 extern "C" int tmat_roi_plan(int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
                              int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full)
 {
-    return roi_plan_export(false, hh, ww, patch, n_up, channels, max_classes, tiles_cap, tiles_per_img, n_classes, tile_class, tile_rank,
+    return roi_plan_export(0, hh, ww, patch, n_up, channels, max_classes, tiles_cap, tiles_per_img, n_classes, tile_class, tile_rank,
                            class_count, rects, mac_planned, mac_full);
 }
 
-// the same plan with the tight rectangles (the default of the tiled entry points)
+// the same plan with the tight rectangles (what TMAT_ROI_EXACT=0 launches)
 extern "C" int tmat_roi_plan_tight(int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
                                    int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full)
 {
-    return roi_plan_export(true, hh, ww, patch, n_up, channels, max_classes, tiles_cap, tiles_per_img, n_classes, tile_class, tile_rank,
+    return roi_plan_export(1, hh, ww, patch, n_up, channels, max_classes, tiles_cap, tiles_per_img, n_classes, tile_class, tile_rank,
+                           class_count, rects, mac_planned, mac_full);
+}
+
+// the same plan with the exact rectangles (the default of the tiled entry points)
+extern "C" int tmat_roi_plan_exact(int hh, int ww, int patch, int n_up, const int *channels, int max_classes, int tiles_cap, int *tiles_per_img,
+                                   int *n_classes, int *tile_class, int *tile_rank, int *class_count, int *rects, double *mac_planned, double *mac_full)
+{
+    return roi_plan_export(2, hh, ww, patch, n_up, channels, max_classes, tiles_cap, tiles_per_img, n_classes, tile_class, tile_rank,
                            class_count, rects, mac_planned, mac_full);
 }
 

@@ -21,6 +21,10 @@ constexpr int ROI_MAX_DOWN_LAYERS = 6 * ROI_MAX_DOWN + 4;
 
 struct RoiRect { int y0, x0, rh, rw; };
 
+// Layers of the up plan (bit l: layer l) whose EXACT rectangle is their tight one: none.  (The place for a layer that a per-launch trace
+// shows slower with unrounded columns than with rounded ones; DESIGN 4.1.1 has the trace.)
+constexpr unsigned ROI_EXACT_KEEP_TIGHT = 0u;
+
 // The same walk continued through the down path (roi_plan_down), from what up block 0 reads of the bottleneck tensor to the input window.
 // Layer 6 b + k belongs to down block b (input side (ws / 2) >> b): k = 0 first depthwise, 1 first pointwise, 2 second depthwise,
 // 3 second pointwise (all at the block's input resolution), 4 the stride-2 residual 1x1, 5 max-pool + add (both enumerate OUTPUT pixels,
@@ -66,11 +70,20 @@ struct RoiPlan {
     // full-frame position, so such a read lands on an in-bounds word of the workspace), and nothing needed depends on it.
     // rect_tight[l][k] lies inside rect[l][k].
     RoiRect rect_tight[ROI_MAX_LAYERS][ROI_MAX_CLASSES] = {};
-    bool tight = false;                         // which set up_rects() names: set by the caller that launches (TMAT_ROI_TIGHT, tmat_api.cpp:roi_attach)
-    const RoiRect *up_rects(int l) const { return tight ? rect_tight[l] : rect[l]; }
+    // The EXACT rectangles: a layer's rectangle IS its need, rows and columns (walk_back(..., exact, parity): the bounding box of the pixels
+    // the blend depends on, the sub-pixel layers' reads following the parity of their outputs), no rounding at all -- odd first
+    // columns and odd widths are the normal case; conv_mfma_kernel<..., ROI>'s per-lane prologue and row-split epilogue take them (a group
+    // of consecutive pixels may break into the next row once).  The final convolution keeps rect's whole 8 x 16 blocks.  A layer in
+    // ROI_EXACT_KEEP_TIGHT keeps its tight rectangle.  rect_exact[l][k] lies inside rect_tight[l][k]; the contract is the same.
+    RoiRect rect_exact[ROI_MAX_LAYERS][ROI_MAX_CLASSES] = {};
+    // which set up_rects() names: set by the caller that launches (TMAT_ROI_TIGHT, TMAT_ROI_EXACT, tmat_api.cpp:roi_attach); exact has
+    // effect only with tight
+    bool tight = false, exact = false;
+    const RoiRect *up_rects(int l) const { return tight ? (exact ? rect_exact[l] : rect_tight[l]) : rect[l]; }
     RoiRect read[ROI_MAX_CLASSES] = {};         // patch ∩ interior: the output pixels the blend reads of a patch of the class
     double mac_planned[ROI_MAX_LAYERS] = {}, mac_full[ROI_MAX_LAYERS] = {};      // multiply-accumulates per image
     double mac_planned_tight[ROI_MAX_LAYERS] = {};                               // the same of rect_tight
+    double mac_planned_exact[ROI_MAX_LAYERS] = {};                               // the same of rect_exact
     RoiDownPlan down;                           // filled by roi_plan_down
 };
 

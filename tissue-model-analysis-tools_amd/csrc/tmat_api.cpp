@@ -480,6 +480,7 @@ const RoiPlan *roi_attach(Ctx *c, TileGeom &g)
         return nullptr;
     }
     e->plan.tight = c->roi_tight;
+    e->plan.exact = c->roi_exact;
     if (c->roi_down && c->down.size() <= (size_t)ROI_MAX_DOWN) {      // the down-path tables (a geometry they do not take keeps the down path full-frame)
         int dchan[ROI_MAX_DOWN + 1];
         unsigned fused = 0;
@@ -663,6 +664,7 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     if (const char *e = getenv("TMAT_FUSED_SEP")) c->fused_sep = atoi(e) != 0;
     if (const char *e = getenv("TMAT_ROI")) c->roi_on = atoi(e) != 0;
     if (const char *e = getenv("TMAT_ROI_TIGHT")) c->roi_tight = atoi(e) != 0;
+    if (const char *e = getenv("TMAT_ROI_EXACT")) c->roi_exact = atoi(e) != 0;
     if (const char *e = getenv("TMAT_ROI_DOWN")) {
         // a bit mask of bit 0 (the unfused level and the small kernels) and bit 1 (the fused separable layers' tile tables): anything else
         // is an error, not a silent full-frame run
@@ -963,6 +965,50 @@ int tmat_debug_sep_tiles(tmat_handle h, int cap, int *n, long long *planned, lon
     if (!c || !n || cap < 0 || (cap > 0 && (!planned || !full))) { set_error("tmat_debug_sep_tiles: bad argument"); return TMAT_E_ARG; }
     *n = (int)c->sep_tiles.size();
     for (int i = 0; i < *n && i < cap; i++) { planned[i] = c->sep_tiles[i].first; full[i] = c->sep_tiles[i].second; }
+    return TMAT_OK;
+}
+
+// Stage-wise test entry point of the REGION form (tests/test_gpu_conv_roi.py): ONE launch_conv with a segment table on host buffers.
+// The caller fills out (and out_relu): words outside the segments' rectangles come back as they went in.  nseg == 0: the full-frame launch
+// of the same convolution.
+int tmat_conv2d_roi(tmat_handle hd, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int subpixel, int cout,
+                    const float *scale, const float *shift, const float *resid, int rs, int relu_in, int relu_out, const int *segs, int nseg,
+                    float *out, float *out_relu)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!c || !x || !w || !shift || !out || n < 1 || hh < 1 || ww < 1 || cin < 1 || cout < 1 || (ksize != 1 && ksize != 3) || (subpixel && ksize != 3) ||
+        (subpixel && (resid || out_relu)) || (rs != 0 && rs != 1) || (rs && ((hh | ww) & 1)) || nseg < 0 || nseg > 16 || (nseg && !segs)) {
+        set_error("tmat_conv2d_roi: bad argument (ksize 1 or 3, sub-pixel form of a 3x3 without residual or activated copy, rs 0 or 1, at most 16 segments)");
+        return TMAT_E_ARG;
+    }
+    TMAT_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int up = subpixel ? 2 : 1;
+    const size_t nx = (size_t)n * hh * ww * cin, no = (size_t)n * (hh * up) * (ww * up) * cout, nr = (size_t)n * (hh >> rs) * (ww >> rs) * cout;
+    DevScope mem(c->ws_pool, s);
+    // the weights as the network's own packing makes them (build_model): taps k-contiguous, the sub-pixel form pre-summed per parity class
+    std::vector<float> wk = subpixel ? k_contiguous(subpixel_weights(std::vector<float>(w, w + (size_t)9 * cin * cout), cin, cout).data(), 16, cin, cout)
+                                     : k_contiguous(w, ksize * ksize, cin, cout);
+    const size_t nw = wk.size();
+    const float *hw = mem.keep(std::move(wk));
+    float *dx = mem.alloc_from(x, nx), *dw = mem.alloc_from(hw, nw);
+    float *dsh = mem.alloc_from(shift, cout), *dsc = scale ? mem.alloc_from(scale, cout) : nullptr;
+    float *dr = resid ? mem.alloc_from(resid, nr) : nullptr, *dout = mem.alloc_from((const float *)out, no);
+    float *dout2 = out_relu ? mem.alloc_from((const float *)out_relu, no) : nullptr;
+    if (!mem.ok) return TMAT_E_HIP;
+    ConvArgs a{};
+    a.in = dx; a.N = n; a.h = hh; a.w = ww; a.Cin = cin; a.relu_in = relu_in != 0; a.ksize = subpixel ? 2 : ksize; a.stride = 1; a.W = dw;
+    a.Cout = cout; a.scale = dsc; a.shift = dsh; a.resid = dr; a.rs = rs; a.relu_out = relu_out != 0; a.out = dout; a.out_relu = dout2; a.prec = 0;
+    RoiSegs sg{};
+    for (int i = 0; i < nseg; i++) {
+        RoiSeg &g = sg.s[sg.nseg++];
+        g.p0 = segs[6 * i]; g.np = segs[6 * i + 1]; g.y0 = segs[6 * i + 2]; g.x0 = segs[6 * i + 3]; g.rh = segs[6 * i + 4]; g.rw = segs[6 * i + 5];
+    }
+    if (!launch_conv(a, s, nseg ? &sg : nullptr)) return TMAT_E_ARG;
+    mem.check(hipGetLastError(), "tmat_conv2d_roi launch");
+    mem.d2h(out, dout, no * sizeof(float));
+    if (out_relu) mem.d2h(out_relu, dout2, no * sizeof(float));
+    if (mem.finish()) return TMAT_E_HIP;
     return TMAT_OK;
 }
 

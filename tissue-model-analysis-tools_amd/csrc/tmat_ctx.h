@@ -194,6 +194,9 @@ struct Ctx {
     bool roi_on = true;
     // TMAT_ROI_TIGHT: the up path launches the tight rectangles (RoiPlan::rect_tight: every layer rounds its own need); 0: the nested ones
     bool roi_tight = true;
+    // TMAT_ROI_EXACT: with the tight plan, a layer's rectangle is its need itself, columns unrounded (RoiPlan::rect_exact; the row-split
+    // epilogue of conv_mfma_kernel<..., ROI> takes them); 0: the tight rectangles.  No effect without TMAT_ROI and TMAT_ROI_TIGHT
+    bool roi_exact = true;
     // TMAT_ROI_DOWN: what of the down path the tiled entry points run in region form too (roi_plan.h:RoiDownPlan).  Bit 0: the unfused
     // level, the residual 1x1 layers, the stem at the even pixels, the pooling fix-ups.  Bit 1: the fused separable layers visit only
     // the tiles of their rectangles (RoiEntry::tabs).  0: the down path stays full-frame

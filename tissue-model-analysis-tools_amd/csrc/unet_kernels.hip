@@ -95,7 +95,9 @@ __device__ long long conv_diag[2048 * 8 * 8];      // [workgroup < 2048][wave][w
 // the epilogue differ; the K loop, the LDS layout and the MFMA order are those of the full-frame form, so a computed pixel gets the same
 // bits.  A template flag and not a uniform branch: full-frame launches (tmat_unet_predict, oversize images, the ResNet) keep the code they
 // had, and the region form's longer address arithmetic stays out of their register budget.
-template <int BM, int BN, int WM, int WN, int KS, bool RELU, int PREC = 0, bool ROI = false>
+// SPLIT (with ROI): the instantiation that also holds the row-split epilogue, launched only when a segment needs it (launch_conv_ks): every
+// other region-form launch -- the tight and nested plans, the down path -- runs the code object it ran before that form existed.
+template <int BM, int BN, int WM, int WN, int KS, bool RELU, int PREC = 0, bool ROI = false, bool SPLIT = false>
 #ifndef TMAT_CONV_WPS
 #define TMAT_CONV_WPS 4     // waves per SIMD the 8-wave conv kernel is compiled for (VGPR budget 512 / this)
 #endif
@@ -148,11 +150,13 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
     if (mt >= nMt) return;
     // pixels m of this tile's segment: M of them, HW per patch in rows of Wr, first one (patch sn, row sy0, column sx0); full-frame: everything
     int M = Mf, HW = Ho * Wo, Wr = Wo, sn = 0, sy0 = 0, sx0 = 0, mtl = mt;
+    [[maybe_unused]] int Hr = Ho;      // rows of the segment's rectangle (the row-split forms of the region form)
     FastDiv dHW = dHWf, dW = dWf;
     if constexpr (ROI) {
         int si = 0;
         for (int k = 1; k < roi.nseg; k++) si = mt >= roi.s[k].mt0 ? k : si;        // scalar: mt and the table are uniform
         M = roi.s[si].M; Wr = roi.s[si].rw; HW = roi.s[si].rh * Wr;
+        if constexpr (SPLIT) Hr = roi.s[si].rh;
         sn = roi.s[si].p0; sy0 = roi.s[si].y0; sx0 = roi.s[si].x0; mtl = mt - roi.s[si].mt0;
         dHW = FastDiv{roi.s[si].dhw_mul, roi.s[si].dhw_sh}; dW = FastDiv{roi.s[si].dw_mul, roi.s[si].dw_sh};
     }
@@ -199,6 +203,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
     // ~35 vector instructions per pass, a dozen of them quarter-rate (v_mul_hi / v_mul_lo / v_mad_u64), and every vector instruction of an
     // f32-MFMA kernel is matrix time: with K = 576 (the Cout = 64 layers) the prologue was 3 % of a tile.
     const bool rowfast = !flat && (Wr & 7) == 0;
+    // (A rectangle of the exact plan (roi_plan.h) has any first column and any width: a width off the multiples of 8 takes the per-lane
+    // form below.  A row-split form of the row-uniform one -- two scalar bases per group of 8, a lane choosing by its pixel's index -- was
+    // built and measured: no launch gained, and its presence in the kernel cost the short-K 1x1 launches 3.5 %)
     unsigned pv[NPA];       // voffset (bytes) of the staged pixel's channel group
     unsigned pm[NPA];       // generic form: mask of the taps that fall inside the image
     unsigned pvt[taps][NPA];
@@ -657,33 +664,66 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
         // the iteration's first pixel and a lane adds a kernel-constant offset.  The per-lane form cost ~23 vector instructions per iteration,
         // ten of them quarter-rate 32 / 64-bit multiplies: 4-5 % of a K = 576 tile (every vector instruction here is matrix time).
         const bool efast = (Wr % RPW) == 0 && (RPW >> a.rs) >= 1 && (sx0 & ((1 << a.rs) - 1)) == 0;
+        // Row-split form (region form only, the rectangles of the exact plan): any first column, any width >= 8 (>= RPW: at most one row
+        // break inside an iteration's group).  The group's first pixel is converted on the scalar unit as above; with k = the pixels left
+        // in its row, the lanes of the rows rsub >= k take the next row of the rectangle (or row sy0 of the next patch): both row bases
+        // and their byte distance are scalars, a lane selects by rsub < k (one v_cmp, one v_cndmask, one add on top of the kernel-constant
+        // offsets; the low-resolution residual, whose column (x >> rs) depends on the parity of the half's first column, adds, shifts and
+        // multiplies its column -- a 24-bit multiply, full rate).  launch_conv keeps a patch plane below 2^31 bytes for the 32-bit distances.
+        const bool esplit = SPLIT && !efast && Wr >= 8;
+        [[maybe_unused]] auto split_of = [&](int m_it, int &nA, int &yA, int &xA, int &k, int &nB, int &yB) {
+            pixel_of(m_it, nA, yA, xA);
+            k = Wr - (xA - sx0);
+            const bool brk = yA - sy0 + 1 < Hr;
+            nB = brk ? nA : nA + 1; yB = brk ? yA + 1 : sy0;
+        };
         const unsigned vo_r = (unsigned)((rsub >> a.rs) * a.Cout + quad * 4) * 4u;         // low-resolution residual: column (x0 + rsub) >> rs
         const unsigned vo_s = (unsigned)(2 * rsub * a.Cout + quad * 4) * 4u;               // sub-pixel scatter: column 2 (x0 + rsub) + spx
         // The residual rows are requested FIRST, all NIT of them, before the accumulators go through LDS: one wait for the lot under the
         // transposition instead of a vmcnt(0) per iteration (which also waited for the previous iteration's store).
+        // (Both loops of the epilogue exist twice in the SPLIT instantiation, selected ONCE per tile by the uniform esplit: with the choice inside
+        // the unrolled iterations every iteration is a basic block of its own, and the row-uniform form loses the scheduling across
+        // iterations it had -- the short-K 1x1 launches measured 4-5 % slower that way.  Macros and not a generic lambda taking
+        // std::bool_constant<SPLIT>: with the lambda the ROI = false instantiations compiled to different code (<128,128,4,2,1,false,0,false>
+        // 1 961 instructions against 1 840), and those kernels are to stay what they were; the macro expands to the parent's text there.)
         float4 rvs[NIT];
-        if (a.resid) {
-#pragma unroll
-            for (int it = 0; it < NIT; it++) {
-                float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
-                const int m_it = mw + it * RPW;
-                if (a.rs || ROI) {       // (region form: the residual's address comes from the pixel's coordinates at rs = 0 as well)
-                    if (efast) {
-                        if (full || m_it < M) {
-                            int un, uy, ux;
-                            pixel_of(m_it, un, uy, ux);
-                            const size_t ridx = ((size_t)un * rH + (uy >> a.rs)) * rW + (ux >> a.rs);
-                            rv = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(a.resid + ridx * a.Cout + cbase) + vo_r);
-                        }
-                    } else if (full || m_it + rsub < M) {
-                        int n, y, x;
-                        pixel_of(m_it + rsub, n, y, x);
-                        const size_t ridx = ((size_t)n * rH + (y >> a.rs)) * rW + (x >> a.rs);
-                        rv = *reinterpret_cast<const float4 *>(a.resid + ridx * a.Cout + co);
-                    }
-                } else if (full || m_it + rsub < M) rv = *reinterpret_cast<const float4 *>(rbase + (size_t)(it * RPW) * a.Cout * 4 + vo);
-                rvs[it] = rv;
+#define TMAT_EPI_RESID(SPLIT) \
+        _Pragma("unroll") \
+            for (int it = 0; it < NIT; it++) { \
+                float4 rv = make_float4(0.f, 0.f, 0.f, 0.f); \
+                const int m_it = mw + it * RPW; \
+                if (a.rs || ROI) {      /* (region form: the residual's address comes from the pixel's coordinates at rs = 0 as well) */ \
+                    if (efast) { \
+                        if (full || m_it < M) { \
+                            int un, uy, ux; \
+                            pixel_of(m_it, un, uy, ux); \
+                            const size_t ridx = ((size_t)un * rH + (uy >> a.rs)) * rW + (ux >> a.rs); \
+                            rv = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(a.resid + ridx * a.Cout + cbase) + vo_r); \
+                        } \
+                    } else if (SPLIT) { \
+                        if (full || m_it < M) { \
+                            int nA, yA, xA, k, nB, yB; \
+                            split_of(m_it, nA, yA, xA, k, nB, yB); \
+                            const size_t rowA = ((size_t)nA * rH + (yA >> a.rs)) * rW; \
+                            const unsigned dB = (unsigned)((((nB - nA) * rH + (yB >> a.rs) - (yA >> a.rs)) * rW) * a.Cout) * 4u; \
+                            const bool first = rsub < k; \
+                            const int xl = (first ? xA : sx0 - k) + rsub; \
+                            const unsigned lo = (first ? 0u : dB) + (__umul24((unsigned)(xl >> a.rs), (unsigned)a.Cout) + (unsigned)(quad * 4)) * 4u; \
+                            if (full || m_it + rsub < M) \
+                                rv = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(a.resid + rowA * a.Cout + cbase) + lo); \
+                        } \
+                    } else if (full || m_it + rsub < M) { \
+                        int n, y, x; \
+                        pixel_of(m_it + rsub, n, y, x); \
+                        const size_t ridx = ((size_t)n * rH + (y >> a.rs)) * rW + (x >> a.rs); \
+                        rv = *reinterpret_cast<const float4 *>(a.resid + ridx * a.Cout + co); \
+                    } \
+                } else if (full || m_it + rsub < M) rv = *reinterpret_cast<const float4 *>(rbase + (size_t)(it * RPW) * a.Cout * 4 + vo); \
+                rvs[it] = rv; \
             }
+        if (a.resid) {
+            if constexpr (SPLIT) { if (esplit) { TMAT_EPI_RESID(true) } else { TMAT_EPI_RESID(false) } }
+            else { TMAT_EPI_RESID(false) }
         }
 #pragma unroll
         for (int i = 0; i < TM; i++)
@@ -693,74 +733,112 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 16 ? 4 : (BM + BN) * 256 
 #pragma unroll
                 for (int jn = 0; jn < TN; jn++) Ws[row * WCOLS + jn * 32 + (lane & 31)] = acc[i][jn][r];
             }
-#pragma unroll
-        for (int it = 0; it < NIT; it++) {
-            const int row = it * RPW + rsub;
-            const int m = mw + row;
-            const bool ok = full || m < M;
-            const size_t so = (size_t)(it * RPW) * a.Cout * 4;
-            float4 v = *reinterpret_cast<const float4 *>(Ws + row * WCOLS + quad * 4);
-            v.x = fmaf(v.x, sc.x, sh.x); v.y = fmaf(v.y, sc.y, sh.y); v.z = fmaf(v.z, sc.z, sh.z); v.w = fmaf(v.w, sc.w, sh.w);
-            if (a.resid) { const float4 rv = rvs[it]; v.x = v.x + rv.x; v.y = v.y + rv.y; v.z = v.z + rv.z; v.w = v.w + rv.w; }
-            if (a.relu_out) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }      // uniform branch
-            if (KS == 2) {      // scatter to the parity class's pixels of the (2 Ho, 2 Wo) output
-                if (efast) {
-                    const int m_it = mw + it * RPW;
-                    if (full || m_it < M) {
-                        int un, uy, ux;
-                        pixel_of(m_it, un, uy, ux);
-                        const size_t oidx = ((size_t)un * 2 * Ho + 2 * uy + spy) * (2 * Wo) + 2 * ux + spx;
-                        *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out + oidx * a.Cout + cbase) + vo_s) = v;
-                    }
-                } else if (ok) {
-                    int n, y, x;
-                    pixel_of(m, n, y, x);
-                    const size_t oidx = ((size_t)n * 2 * Ho + 2 * y + spy) * (2 * Wo) + 2 * x + spx;
-                    *reinterpret_cast<float4 *>(a.out + oidx * a.Cout + co) = v;
-                }
-            }
-            else if (ROI) {     // region form: the row's address from the pixel's coordinates (row-uniform when the segment's rows allow)
-                if (ok) {
-                    int n, y, x;
-                    pixel_of(efast ? mw + it * RPW : m, n, y, x);
-                    const size_t oofs = (((size_t)n * Ho + y) * Wo + x) * a.Cout + cbase;
-                    const unsigned lo = efast ? vo : (unsigned)(quad * 16);
-                    *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out + oofs) + lo) = v;
-                    if (a.out_relu) {
-                        v.x = relu_pos0(v.x); v.y = relu_pos0(v.y); v.z = relu_pos0(v.z); v.w = relu_pos0(v.w);
-                        *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out_relu + oofs) + lo) = v;
-                    }
-                }
-            }
-            else if (ok) {
 #ifdef TMAT_VAR_BUFSTORE       // round-3 incident (ii): the rows through raw_buffer_store_b128 (tile in the descriptor, iteration in soffset); see DESIGN "Incidents"
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v),
+#define TMAT_EPI_PLAIN_STORE()                                                                                                           \
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v),             \
                                                        __builtin_amdgcn_make_buffer_rsrc((void *)obase, 0, 0x7fffffff, 0x00020000), vo, (int)so, 0);
 #else
-                *reinterpret_cast<float4 *>(obase + so + vo) = v;
+#define TMAT_EPI_PLAIN_STORE() *reinterpret_cast<float4 *>(obase + so + vo) = v;
 #endif
-                // the activated copy for the next block's first convolution (uniform branch): four v_max per 16-byte store here instead of
-                // sixteen v_max_i32 per K chunk and wave in the consumer's RELU instantiation (0.7 ms per launch)
-                if (a.out_relu) {       // relu_pos0: negative values and -0.0 become +0.0, exactly what the RELU instantiation's load-side max does
-                    v.x = relu_pos0(v.x); v.y = relu_pos0(v.y); v.z = relu_pos0(v.z); v.w = relu_pos0(v.w);
-                    *reinterpret_cast<float4 *>(o2base + so + vo) = v;
-                }
-            }
+#define TMAT_EPI_STORE(SPLIT) \
+        _Pragma("unroll") \
+        for (int it = 0; it < NIT; it++) { \
+            const int row = it * RPW + rsub; \
+            const int m = mw + row; \
+            const bool ok = full || m < M; \
+            const size_t so = (size_t)(it * RPW) * a.Cout * 4; \
+            float4 v = *reinterpret_cast<const float4 *>(Ws + row * WCOLS + quad * 4); \
+            v.x = fmaf(v.x, sc.x, sh.x); v.y = fmaf(v.y, sc.y, sh.y); v.z = fmaf(v.z, sc.z, sh.z); v.w = fmaf(v.w, sc.w, sh.w); \
+            if (a.resid) { const float4 rv = rvs[it]; v.x = v.x + rv.x; v.y = v.y + rv.y; v.z = v.z + rv.z; v.w = v.w + rv.w; } \
+            if (a.relu_out) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }      /* uniform branch */ \
+            if (KS == 2) {      /* scatter to the parity class's pixels of the (2 Ho, 2 Wo) output */ \
+                if (efast) { \
+                    const int m_it = mw + it * RPW; \
+                    if (full || m_it < M) { \
+                        int un, uy, ux; \
+                        pixel_of(m_it, un, uy, ux); \
+                        const size_t oidx = ((size_t)un * 2 * Ho + 2 * uy + spy) * (2 * Wo) + 2 * ux + spx; \
+                        *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out + oidx * a.Cout + cbase) + vo_s) = v; \
+                    } \
+                } else if (SPLIT) { \
+                    const int m_it = mw + it * RPW; \
+                    if (full || m_it < M) { \
+                        int nA, yA, xA, k, nB, yB; \
+                        split_of(m_it, nA, yA, xA, k, nB, yB); \
+                        const size_t rowA = ((size_t)nA * 2 * Ho + 2 * yA + spy) * (2 * Wo) + spx; \
+                        const unsigned dB = (unsigned)((((nB - nA) * 2 * Ho + 2 * (yB - yA)) * (2 * Wo)) * a.Cout) * 4u; \
+                        const unsigned oA = (unsigned)(2 * xA * a.Cout) * 4u, oB = dB + (unsigned)(2 * (sx0 - k) * a.Cout) * 4u; \
+                        const unsigned lo = (rsub < k ? oA : oB) + vo_s; \
+                        if (ok) *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out + rowA * a.Cout + cbase) + lo) = v; \
+                    } \
+                } else if (ok) { \
+                    int n, y, x; \
+                    pixel_of(m, n, y, x); \
+                    const size_t oidx = ((size_t)n * 2 * Ho + 2 * y + spy) * (2 * Wo) + 2 * x + spx; \
+                    *reinterpret_cast<float4 *>(a.out + oidx * a.Cout + co) = v; \
+                } \
+            } \
+            else if (SPLIT) {      /* region form, row-split: two scalar row bases, a lane selects */ \
+                const int m_it = mw + it * RPW; \
+                if (full || m_it < M) { \
+                    int nA, yA, xA, k, nB, yB; \
+                    split_of(m_it, nA, yA, xA, k, nB, yB); \
+                    const size_t rowA = ((size_t)nA * Ho + yA) * Wo; \
+                    const unsigned dB = (unsigned)((((nB - nA) * Ho + yB - yA) * Wo) * a.Cout) * 4u; \
+                    const unsigned oA = (unsigned)(xA * a.Cout) * 4u, oB = dB + (unsigned)((sx0 - k) * a.Cout) * 4u; \
+                    const unsigned lo = (rsub < k ? oA : oB) + vo; \
+                    const size_t oofs = rowA * a.Cout + cbase; \
+                    if (ok) { \
+                        *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out + oofs) + lo) = v; \
+                        if (a.out_relu) { \
+                            v.x = relu_pos0(v.x); v.y = relu_pos0(v.y); v.z = relu_pos0(v.z); v.w = relu_pos0(v.w); \
+                            *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out_relu + oofs) + lo) = v; \
+                        } \
+                    } \
+                } \
+            } \
+            else if (ROI) {      /* region form: the row's address from the pixel's coordinates (row-uniform when the segment's rows allow) */ \
+                if (ok) { \
+                    int n, y, x; \
+                    pixel_of(efast ? mw + it * RPW : m, n, y, x); \
+                    const size_t oofs = (((size_t)n * Ho + y) * Wo + x) * a.Cout + cbase; \
+                    const unsigned lo = efast ? vo : (unsigned)(quad * 16); \
+                    *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out + oofs) + lo) = v; \
+                    if (a.out_relu) { \
+                        v.x = relu_pos0(v.x); v.y = relu_pos0(v.y); v.z = relu_pos0(v.z); v.w = relu_pos0(v.w); \
+                        *reinterpret_cast<float4 *>(reinterpret_cast<char *>(a.out_relu + oofs) + lo) = v; \
+                    } \
+                } \
+            } \
+            else if (ok) { \
+                TMAT_EPI_PLAIN_STORE() \
+      /* the activated copy for the next block's first convolution (uniform branch): four v_max per 16-byte store here instead of */ \
+      /* sixteen v_max_i32 per K chunk and wave in the consumer's RELU instantiation (0.7 ms per launch) */ \
+                if (a.out_relu) {      /* relu_pos0: negative values and -0.0 become +0.0, exactly what the RELU instantiation's load-side max does */ \
+                    v.x = relu_pos0(v.x); v.y = relu_pos0(v.y); v.z = relu_pos0(v.z); v.w = relu_pos0(v.w); \
+                    *reinterpret_cast<float4 *>(o2base + so + vo) = v; \
+                } \
+            } \
         }
+        if constexpr (SPLIT) { if (esplit) { TMAT_EPI_STORE(true) } else { TMAT_EPI_STORE(false) } }
+        else { TMAT_EPI_STORE(false) }
+#undef TMAT_EPI_RESID
+#undef TMAT_EPI_STORE
+#undef TMAT_EPI_PLAIN_STORE
     }
 #ifdef TMAT_DIAG
     if (dg_on) dg_slot[6] = (long long)__builtin_readcyclecounter() - dg_e0;
 #endif
 }
 
-template <int BM, int BN, int WM, int WN, int KS, int PREC, bool ROI>
+template <int BM, int BN, int WM, int WN, int KS, int PREC, bool ROI, bool SPLIT = false>
 static void launch_conv_inst(const ConvArgs &a, int M, int Ho, int Wo, int nMt, int nNt, dim3 grid, FastDiv dHW, FastDiv dW, int nstat,
                              std::conditional_t<ROI, RoiSegs, RoiNone> roi, hipStream_t s)
 {
     if (a.relu_in)
-        hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, true, PREC, ROI>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat, roi);
+        hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, true, PREC, ROI, SPLIT>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat, roi);
     else
-        hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, false, PREC, ROI>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat, roi);
+        hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, KS, false, PREC, ROI, SPLIT>), grid, dim3(64 * WM * WN), 0, s, a, M, Ho, Wo, nMt, nNt, dHW, dW, nstat, roi);
 }
 
 template <int BM, int BN, int WM, int WN, int KS>
@@ -768,6 +846,8 @@ static void launch_conv_ks(const ConvArgs &a, int M, int Ho, int Wo, hipStream_t
 {
     int nMt = (M + BM - 1) / BM, nNt = a.Cout / BN;
     RoiSegs rs{};
+    constexpr int RPW = 8 / (BN / WN / 32);      // pixels per epilogue iteration of a wave (the kernel's RPW)
+    bool split = false;
     if (roi) {          // region form: the M tiles of the segments one after the other, a tile never straddling two of them
         rs = *roi;
         nMt = 0;
@@ -778,6 +858,8 @@ static void launch_conv_ks(const ConvArgs &a, int M, int Ho, int Wo, hipStream_t
             nMt += (g.M + BM - 1) / BM;
             const FastDiv f = make_fastdiv(g.rh * g.rw), fw = make_fastdiv(g.rw);
             g.dhw_mul = f.mul; g.dhw_sh = f.sh; g.dw_mul = fw.mul; g.dw_sh = fw.sh;
+            // a segment the row-uniform epilogue does not take (the kernel's efast) and the row-split one does
+            if (g.rw >= 8 && ((g.rw % RPW) != 0 || (g.x0 & ((1 << a.rs) - 1)) != 0)) split = true;
         }
     }
     dim3 grid(((nMt + 7) / 8) * 8 * nNt, KS == 2 ? 4 : 1);
@@ -787,6 +869,7 @@ static void launch_conv_ks(const ConvArgs &a, int M, int Ho, int Wo, hipStream_t
     if (roi) {          // (the UNet's precisions only: the f16 form belongs to the ResNet, which has no tiled blend)
         if (a.prec == 1) launch_conv_inst<BM, BN, WM, WN, KS, 1, true>(a, M, Ho, Wo, nMt, nNt, grid, dHW, dW, nstat, rs, s);
         else if (a.prec == 2) launch_conv_inst<BM, BN, WM, WN, KS, 2, true>(a, M, Ho, Wo, nMt, nNt, grid, dHW, dW, nstat, rs, s);
+        else if (split) launch_conv_inst<BM, BN, WM, WN, KS, 0, true, true>(a, M, Ho, Wo, nMt, nNt, grid, dHW, dW, nstat, rs, s);
         else launch_conv_inst<BM, BN, WM, WN, KS, 0, true>(a, M, Ho, Wo, nMt, nNt, grid, dHW, dW, nstat, rs, s);
         return;
     }
@@ -857,6 +940,11 @@ bool launch_conv(const ConvArgs &a, hipStream_t s, const RoiSegs *roi)
             p = g.p0 + g.np;
         }
         if (!ok) { set_error("launch_conv: bad region table"); return false; }
+        // (the row-split epilogue keeps the byte distance between two rows of consecutive patches in 32 bits)
+        if ((long long)Ho * Wo * (a.ksize == 2 ? 4 : 1) * a.Cout * 4 >= 0x7fffffffLL) {
+            set_error("launch_conv: region form needs an output plane per patch below 2^31 bytes");
+            return false;
+        }
     }
     if (a.Cout % 128 == 0)
         launch_conv_cfg<TMAT_BM, 128, TMAT_WM, TMAT_WN>(a, M, Ho, Wo, s, roi);

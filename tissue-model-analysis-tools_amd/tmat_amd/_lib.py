@@ -110,6 +110,7 @@ def lib():
     L.tmat_inv_depth_predict_multi.argtypes = [vp, vp, i, vp, vp, i, i, i, i, vp]
     L.tmat_resnet_set_precision.argtypes = [vp, i]
     L.tmat_conv2d.argtypes = [vp, i, vp, i, i, i, i, vp, i, i, i, vp, vp, vp, i, i, vp]
+    L.tmat_conv2d_roi.argtypes = [vp, vp, i, i, i, i, vp, i, i, i, vp, vp, vp, i, i, i, vp, i, vp, vp]
     L.tmat_prof_enable.argtypes = [vp, i]
     L.tmat_debug_poison.argtypes = [vp, i]
     L.tmat_debug_held_bytes.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
@@ -150,7 +151,7 @@ EXPORTS = [
     "tmat_set_gaussian_table", "tmat_host_gaussian_kernel1d", "tmat_gaussian_f32", "tmat_sato_batch", "tmat_stack_prepare", "tmat_vessel_field",
     "tmat_analyze_stack", "tmat_field_stats", "tmat_field_stats_pruned", "tmat_resize_aa_u16", "tmat_cell_area_batch", "tmat_cell_area_masked", "tmat_resize_linear_u16",
     "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi", "tmat_resnet_set_precision", "tmat_conv2d",
-    "tmat_roi_plan", "tmat_roi_plan_tight", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles",
+    "tmat_roi_plan", "tmat_roi_plan_tight", "tmat_roi_plan_exact", "tmat_conv2d_roi", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles",
     "tmat_stage_pictures", "tmat_host_stage_pictures", "tmat_analyze_batch_ex", "tmat_analyze_batch_ex_dev",
 ]
 
@@ -311,6 +312,36 @@ class Handle:
             raise ValueError("conv2d: scale / shift must have cout entries")
         check(lib().tmat_conv2d(self._h, int(prec), ptr(x), n, hh, ww, cin, ptr(w), k, int(stride), cout, None if scale is None else ptr(scale), ptr(shift),
                                 None if resid is None else ptr(resid), int(bool(relu_in)), int(bool(relu_out)), ptr(out)), "tmat_conv2d")
+        return out
+
+    def conv2d_roi(self, x, w, scale, shift, segs, out, resid=None, rs=0, subpixel=False, relu_in=False, relu_out=False, out_relu=None):
+        """stage-wise test entry point of the region form (include/tmat.h:tmat_conv2d_roi): one f32 convolution of the MFMA kernel with a
+        segment table.  x (n, h, w, cin), w in the Keras layout (k, k, cin, cout); segs: at most 16 rows (p0, np, y0, x0, rh, rw), none for
+        the full-frame launch; resid (nullable) (n, h >> rs, w >> rs, cout); subpixel: the 3x3 over the 2x nearest-upsampled x, out
+        (n, 2 h, 2 w, cout), segments in stored pixels.  out (and out_relu, nullable) are caller-filled float32 arrays, changed in place:
+        words outside the rectangles keep their value.  Returns out."""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(w, np.float32)
+        n, hh, ww, cin = x.shape
+        k, k2, ci2, cout = w.shape
+        if k != k2 or ci2 != cin:
+            raise ValueError("conv2d_roi: weight shape does not match the input")
+        up = 2 if subpixel else 1
+        for o in (out, out_relu):
+            if o is not None and (o.dtype != np.float32 or not o.flags.c_contiguous or o.shape != (n, hh * up, ww * up, cout)):
+                raise ValueError("conv2d_roi: out / out_relu must be C-contiguous float32 arrays of the result's shape")
+        shift = np.ascontiguousarray(shift, np.float32)
+        scale = None if scale is None else np.ascontiguousarray(scale, np.float32)
+        if resid is not None:
+            resid = np.ascontiguousarray(resid, np.float32)
+            if resid.shape != (n, hh >> rs, ww >> rs, cout):
+                raise ValueError("conv2d_roi: resid must be (n, h >> rs, w >> rs, cout)")
+        if shift.shape != (cout,) or (scale is not None and scale.shape != (cout,)):
+            raise ValueError("conv2d_roi: scale / shift must have cout entries")
+        sg = np.ascontiguousarray(np.asarray(segs, np.int32).reshape(-1, 6))
+        check(lib().tmat_conv2d_roi(self._h, ptr(x), n, hh, ww, cin, ptr(w), k, int(bool(subpixel)), cout, None if scale is None else ptr(scale),
+                                    ptr(shift), None if resid is None else ptr(resid), int(rs), int(bool(relu_in)), int(bool(relu_out)),
+                                    ptr(sg) if len(sg) else None, len(sg), ptr(out), None if out_relu is None else ptr(out_relu)), "tmat_conv2d_roi")
         return out
 
     def render_tree(self, backgrounds, trees, vis_width=2000):
@@ -500,7 +531,7 @@ def host_render_barcode(bars, vis_width=2000):
 # -- host pixel stages (csrc/postproc.cpp); exposed for stage-wise parity tests --------------------
 def roi_plan(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), max_classes=16, _export="tmat_roi_plan"):
     """tmat_roi_plan (include/tmat.h): the region plan of the UNet up path for an (hh, ww) image; host arithmetic, no GPU.
-    The NESTED rectangles (TMAT_ROI_TIGHT=0); roi_plan_tight returns the ones launched by default.
+    The NESTED rectangles (TMAT_ROI_TIGHT=0); roi_plan_exact returns the ones launched by default.
     Returns a dict: tiles_per_img, n_classes (0: fall-back "everything"), tile_class / tile_rank [tiles_per_img], class_count [max_classes],
     rects [3 n_up + 1][max_classes][4] (y0, x0, rows, columns), mac_planned / mac_full [3 n_up + 1]."""
     L = lib()
@@ -524,8 +555,14 @@ def roi_plan(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), max_classes=1
 
 def roi_plan_tight(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), max_classes=16):
     """tmat_roi_plan_tight (include/tmat.h): roi_plan's classes and patch order with the TIGHT rectangles -- every layer's own need, its
-    columns rounded once -- that the tiled entry points launch by default.  Same dict as roi_plan."""
+    columns rounded once (what TMAT_ROI_EXACT=0 launches; roi_plan_exact returns the default).  Same dict as roi_plan."""
     return roi_plan(hh, ww, patch, channels, max_classes, _export="tmat_roi_plan_tight")
+
+
+def roi_plan_exact(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), max_classes=16):
+    """tmat_roi_plan_exact (include/tmat.h): roi_plan's classes and patch order with the EXACT rectangles -- every layer's own need, rows
+    and columns unrounded -- that the tiled entry points launch by default (TMAT_ROI_EXACT=0: the tight ones).  Same dict as roi_plan."""
+    return roi_plan(hh, ww, patch, channels, max_classes, _export="tmat_roi_plan_exact")
 
 
 def roi_plan_down(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3, max_classes=16):
