@@ -777,6 +777,25 @@ int tmat_roi_sep_tiles(int hh, int ww, int patch, int n_up, const int *up_channe
                        unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles);
 
 /*
+ * The constant-ring form of that plan (TMAT_ROI_CONST at tmat_create; the batch pipeline runs it unless the variable is 0,
+ * tmat_predict_smooth only when it is 1).  Outside the rectangle of its class that the blend reads, a patch holds one value per image,
+ * the pad value.  Per layer and class, all [layers][max_classes][4] = y0, x0, rows, columns:
+ *   nonconst:  the pixels whose receptive field, clipped to the patch, reaches the image data.  Outside it the tensor equals, bit for
+ *              bit, the tensor of a patch that is the pad value everywhere, at the same position;
+ *   live:      what is still computed, need ∩ nonconst; for a tensor that never reaches memory (stored[l] == 0 inside a fused level,
+ *              the stem inside the first separable layer) the taps of its consumer's live;
+ *   rect_live: live rounded outwards by the rule of rects, inside rects.
+ * fill: [layers][max_classes][4 strips][4], the pixels of a stored tensor outside nonconst that a consumer's live reads -- copied from
+ * the all-constant patch of the image, which every pass computes beside its patches.  mac_live / bytes_live: mac_planned / bytes_planned
+ * of rect_live.  tmat_roi_sep_tiles_live: tmat_roi_sep_tiles for rect_live, a subsequence of that table.
+ */
+int tmat_roi_plan_const(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                        unsigned fused_mask, int max_classes, int *n_classes, int *nonconst, int *live, int *rect_live, int *fill,
+                        int *stored, double *mac_live, double *bytes_live);
+int tmat_roi_sep_tiles_live(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                            unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles);
+
+/*
  * Test-only (tests/test_gpu_roi_sep.py): the fused separable launches of the handle's last down pass, in launch order -- planned[i]
  * tiles visited of full[i] (equal for a full-frame launch), counted on the host at launch time.  *n: their number (at most cap are
  * written).

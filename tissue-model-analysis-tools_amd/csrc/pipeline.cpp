@@ -158,6 +158,8 @@ static int enqueue_pre(Ctx *c, const uint16_t *imgs_dev, int k, int slot, const 
     float *mn = (float *)c->scratch, *mx = mn + k;
     launch_minmax_f32(b.x, k, (size_t)b.h * b.w, mn, mx, s);
     launch_extract_tiles(b.x, mn, k, g, patch_in_of(c, slot, g), s);
+    // the pad values until the pass's down path runs (the constant-ring form): mn is rewritten by the front end of the pass after next
+    if (c->roi_const != 0 && k <= c->const_cap) TMAT_HIP(hipMemcpyAsync(c->padval[slot], mn, (size_t)k * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (side) TMAT_HIP(hipEventRecord(c->ev_pre[slot], s));
     return TMAT_OK;
 }
@@ -176,7 +178,8 @@ static int enqueue_down(Ctx *c, int k, int slot, const TileGeom &g)
     if (oversize && tail_on_side_stream() && c->blend_pending[slot ^ 1]) TMAT_HIP(hipStreamWaitEvent(s, c->ev_blend[slot ^ 1], 0));
     float *pin = patch_in_of(c, slot, g);
     int rc = oversize ? unet_forward_dev(c, pin, k * g.tiles_per_img, c->patch_out, s)
-                      : unet_down_dev(c, pin, k * g.tiles_per_img, c->dout[slot], s, roi_find(c, g));
+                      : unet_down_dev(c, pin, k * g.tiles_per_img, c->dout[slot], s, roi_find(c, g),
+                                      c->roi_const != 0 && k <= c->const_cap ? c->padval[slot] : nullptr);
     if (rc) return rc;
     TMAT_HIP(hipEventRecord(c->ev_down[slot], s));
     c->down_pending[slot] = true;
@@ -474,7 +477,7 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
     if (!use_one_stream() && !hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize")) return TMAT_E_HIP;
     // second input buffer for the front end that runs ahead on the second stream (enqueue_pre)
     if (c->pre_side && tail_on_side_stream() && g.tiles_per_img <= c->max_patches && !c->patch_in2 &&
-        !set_ptr(c->patch_in2, c->ws.dev((size_t)c->patch * c->patch * c->patch_cap * sizeof(float), "hipMalloc(patch_in2)"))) return TMAT_E_HIP;
+        !set_ptr(c->patch_in2, c->ws.dev((size_t)c->patch * c->patch * (c->patch_cap + c->const_cap) * sizeof(float), "hipMalloc(patch_in2)"))) return TMAT_E_HIP;
     if (pre_on_side_stream(c, g)) {         // what the caller queued on the main stream (the images) comes first on the second one too
         TMAT_HIP(hipEventRecord(c->ev_pre[0], c->stream));
         TMAT_HIP(hipStreamWaitEvent(c->stream2, c->ev_pre[0], 0));

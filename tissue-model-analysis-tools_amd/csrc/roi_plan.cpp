@@ -104,6 +104,116 @@ void walk_down_axis(Iv out, bool cols, int ws, int n_down, unsigned fused_mask, 
     rect[L + 2] = Iv{0, ws};                                     // the tile gather writes whole patches
 }
 
+// The taps of the down path for the constant-ring form: output pixel i of a layer reads its producer at s i + a .. s i + b (one axis).
+struct Tap { int s, a, b; };
+constexpr Tap TAP_DW{1, -1, 1};         // depthwise 3 x 3, "same"
+constexpr Tap TAP_PW{1, 0, 0};          // pointwise, and the residual under the add
+constexpr Tap TAP_EVEN{2, 0, 0};        // the stride-2 residual 1x1, the stem at its even pixels
+constexpr Tap TAP_S2{2, 0, 2};          // MaxPooling2D(3, 2, "same") and the stem's Conv2D(3, strides 2, "same") on an even side
+
+bool empty(Iv v) { return v.hi <= v.lo; }
+Iv hull_e(Iv a, Iv b) { return empty(a) ? b : empty(b) ? a : hull(a, b); }
+Iv meet(Iv a, Iv b) { const Iv v{std::max(a.lo, b.lo), std::min(a.hi, b.hi)}; return empty(v) ? Iv{0, 0} : v; }
+int floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+// the outputs in [0, R) of which some tap lies in v
+Iv tap_fwd(Iv v, Tap t, int R)
+{
+    if (empty(v)) return Iv{0, 0};
+    const Iv o = clip(Iv{-floor_div(-(v.lo - t.b), t.s), floor_div(v.hi - 1 - t.a, t.s) + 1}, R);
+    return empty(o) ? Iv{0, 0} : o;
+}
+// the hull of the taps of the outputs v, clipped to the producer's side R
+Iv tap_back(Iv v, Tap t, int R)
+{
+    if (empty(v)) return Iv{0, 0};
+    const Iv o = clip(Iv{t.s * v.lo + t.a, t.s * (v.hi - 1) + t.b + 1}, R);
+    return empty(o) ? Iv{0, 0} : o;
+}
+
+// One axis of one class in the constant-ring form.  rd: the part of the input window that is image data.  need / rect: walk_down_axis.
+// Out: nonconst, live, rect_live and reads (the hull of the taps of the consumers' live: live ∪ fill of a stored tensor) per layer.
+void walk_const_axis(Iv rd, bool cols, int ws, int n_down, unsigned fused_mask, const Iv *need, const Iv *rect, Iv *nc, Iv *live, Iv *rl, Iv *reads)
+{
+    const int L = 6 * n_down;
+    // forwards: what the image data reaches
+    nc[L + 3] = nc[L + 2] = rd;
+    nc[L + 1] = tap_fwd(rd, TAP_S2, ws / 2);
+    nc[L] = tap_fwd(nc[L + 1], TAP_EVEN, ws / 4);
+    Iv in = nc[L + 1];
+    for (int b = 0; b < n_down; b++) {
+        const int H = (ws / 2) >> b, Ho = H / 2;
+        Iv *q = nc + 6 * b;
+        q[0] = tap_fwd(in, TAP_DW, H);
+        q[1] = tap_fwd(q[0], TAP_PW, H);
+        q[2] = tap_fwd(q[1], TAP_DW, H);
+        q[3] = tap_fwd(q[2], TAP_PW, H);
+        q[4] = tap_fwd(in, TAP_EVEN, Ho);
+        q[5] = hull_e(tap_fwd(q[3], TAP_S2, Ho), tap_fwd(q[4], TAP_PW, Ho));
+        in = q[5];
+    }
+    // backwards: a stored tensor computes need ∩ nonconst, a tensor that is never stored whatever its consumer's live reads
+    for (int b = n_down - 1; b >= 0; b--) {
+        const int H = (ws / 2) >> b, Ho = H / 2;
+        const bool fused = (fused_mask >> b) & 1u;
+        const Iv *nd = need + 6 * b, *q = nc + 6 * b;
+        Iv *lv = live + 6 * b, *rd_ = reads + 6 * b;
+        rd_[5] = b + 1 == n_down ? nd[5] : hull_e(tap_back(lv[6], TAP_DW, Ho), tap_back(lv[6 + 4], TAP_EVEN, Ho));
+        lv[5] = meet(nd[5], q[5]);
+        rd_[4] = tap_back(lv[5], TAP_PW, Ho);
+        lv[4] = meet(nd[4], q[4]);
+        rd_[3] = tap_back(lv[5], TAP_S2, H);
+        lv[3] = fused ? rd_[3] : meet(nd[3], q[3]);
+        rd_[2] = tap_back(lv[3], TAP_PW, H);
+        lv[2] = fused ? rd_[2] : meet(nd[2], q[2]);
+        rd_[1] = tap_back(lv[2], TAP_DW, H);
+        lv[1] = meet(nd[1], q[1]);
+        rd_[0] = tap_back(lv[1], TAP_PW, H);
+        lv[0] = fused ? rd_[0] : meet(nd[0], q[0]);
+    }
+    reads[L] = tap_back(live[4], TAP_PW, ws / 4);
+    live[L] = meet(need[L], nc[L]);
+    reads[L + 1] = hull_e(tap_back(live[0], TAP_DW, ws / 2), tap_back(live[L], TAP_EVEN, ws / 2));
+    live[L + 1] = (fused_mask & 1u) ? reads[L + 1] : need[L + 1];       // inside the STEM layer, or written whole by the stem's own kernel
+    reads[L + 2] = tap_back(live[L + 1], TAP_S2, ws);
+    live[L + 2] = need[L + 2];
+    reads[L + 3] = live[L + 3] = need[L + 3];
+    // live rounded by rect's rule (walk_down_axis), kept inside rect
+    for (int b = 0; b < n_down; b++) {
+        const int H = (ws / 2) >> b, Ho = H / 2;
+        const bool fused = (fused_mask >> b) & 1u;
+        for (int k = 0; k < 6; k++) {
+            const int l = 6 * b + k;
+            Iv v = live[l];
+            if (!empty(v)) {
+                if (k < 4 && fused) v = align_to(v, 16, H);
+                else if (k < 5 && cols) v = align_cols_in(v, k < 4 ? H : Ho, rect[l]);
+            }
+            if (!empty(v) && (v.lo < rect[l].lo || v.hi > rect[l].hi)) v = rect[l];
+            rl[l] = v;
+        }
+    }
+    rl[L] = rl[4];
+    rl[L + 1] = (fused_mask & 1u) ? (empty(rl[0]) ? Iv{0, 0} : dilate(rl[0], 1, ws / 2)) : rect[L + 1];
+    rl[L + 2] = rect[L + 2];
+    rl[L + 3] = rect[L + 3];
+}
+
+RoiRect rect_of(Iv r, Iv c) { return (empty(r) || empty(c)) ? RoiRect{0, 0, 0, 0} : RoiRect{r.lo, c.lo, r.hi - r.lo, c.hi - c.lo}; }
+
+// q \ nc as strips: above, below, left, right of nc (empty strips have rh = rw = 0)
+void fill_strips(RoiRect q, RoiRect nc, RoiRect *out)
+{
+    for (int i = 0; i < 4; i++) out[i] = RoiRect{0, 0, 0, 0};
+    if (q.rh <= 0 || q.rw <= 0) return;
+    const int y0 = std::max(q.y0, nc.y0), y1 = std::min(q.y0 + q.rh, nc.y0 + nc.rh);
+    const int x0 = std::max(q.x0, nc.x0), x1 = std::min(q.x0 + q.rw, nc.x0 + nc.rw);
+    if (nc.rh <= 0 || nc.rw <= 0 || y1 <= y0 || x1 <= x0) { out[0] = q; return; }
+    if (y0 > q.y0) out[0] = RoiRect{q.y0, q.x0, y0 - q.y0, q.rw};
+    if (y1 < q.y0 + q.rh) out[1] = RoiRect{y1, q.x0, q.y0 + q.rh - y1, q.rw};
+    if (x0 > q.x0) out[2] = RoiRect{y0, q.x0, y1 - y0, x0 - q.x0};
+    if (x1 < q.x0 + q.rw) out[3] = RoiRect{y0, x1, y1 - y0, q.x0 + q.rw - x1};
+}
+
 }  // namespace
 
 bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask)
@@ -130,6 +240,9 @@ bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask)
     bpp[L + 2] = 4.0;
     d.res[L + 3] = ws;
     d.n_down = n_down; d.n_layers = L + 4; d.fused_mask = fused_mask;
+    for (int b = 0; b < n_down; b++)
+        for (int k = 0; k < 6; k++) d.stored[6 * b + k] = !((fused_mask >> b) & 1u) || k == 1 || k >= 4;
+    d.stored[L] = true;         // (the stem and the input window are written whole)
     for (int l = 0; l < d.n_layers; l++) {
         d.mac_full[l] = mpp[l] * d.res[l] * d.res[l] * p.tiles_per_img;
         d.bytes_full[l] = bpp[l] * d.res[l] * d.res[l] * p.tiles_per_img;
@@ -155,6 +268,20 @@ bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask)
             d.mac_planned[l] += mpp[l] * q.rh * q.rw * p.class_count[k];
             d.bytes_planned[l] += bpp[l] * q.rh * q.rw * p.class_count[k];
         }
+        // the constant-ring form of the same class
+        Iv cr[ROI_MAX_DOWN_LAYERS], cc[ROI_MAX_DOWN_LAYERS], lr[ROI_MAX_DOWN_LAYERS], lc[ROI_MAX_DOWN_LAYERS];
+        Iv vr[ROI_MAX_DOWN_LAYERS], vc[ROI_MAX_DOWN_LAYERS], qr[ROI_MAX_DOWN_LAYERS], qc[ROI_MAX_DOWN_LAYERS];
+        walk_const_axis(Iv{rd.y0, rd.y0 + rd.rh}, false, ws, n_down, fused_mask, nr, rr, cr, lr, vr, qr);
+        walk_const_axis(Iv{rd.x0, rd.x0 + rd.rw}, true, ws, n_down, fused_mask, nc, rc, cc, lc, vc, qc);
+        for (int l = 0; l < d.n_layers; l++) {
+            d.nonconst[l][k] = rect_of(cr[l], cc[l]);
+            d.live[l][k] = rect_of(lr[l], lc[l]);
+            const RoiRect q = rect_of(vr[l], vc[l]);
+            d.rect_live[l][k] = q;
+            d.mac_live[l] += mpp[l] * q.rh * q.rw * p.class_count[k];
+            d.bytes_live[l] += bpp[l] * q.rh * q.rw * p.class_count[k];
+            if (d.stored[l]) fill_strips(rect_of(qr[l], qc[l]), d.nonconst[l][k], d.fill[l][k]);
+        }
         for (int b = 0; b < n_down; b++)
             if ((fused_mask >> b) & 1u)
                 for (int l = 6 * b + 1; l <= 6 * b + 3; l += 2)
@@ -163,7 +290,12 @@ bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask)
     return true;
 }
 
-long long roi_sep_tile_table(const RoiPlan &p, int layer, int k, std::vector<int> &out)
+static long long sep_tile_table(const RoiPlan &p, const RoiRect (*rects)[ROI_MAX_CLASSES], int layer, int k, std::vector<int> &out);
+
+long long roi_sep_tile_table(const RoiPlan &p, int layer, int k, std::vector<int> &out) { return sep_tile_table(p, p.down.rect, layer, k, out); }
+long long roi_sep_tile_table_live(const RoiPlan &p, int layer, int k, std::vector<int> &out) { return sep_tile_table(p, p.down.rect_live, layer, k, out); }
+
+static long long sep_tile_table(const RoiPlan &p, const RoiRect (*rects)[ROI_MAX_CLASSES], int layer, int k, std::vector<int> &out)
 {
     out.clear();
     const RoiDownPlan &d = p.down;
@@ -173,7 +305,7 @@ long long roi_sep_tile_table(const RoiPlan &p, int layer, int k, std::vector<int
     const long long full = (long long)k * p.tiles_per_img * TPP;
     if (full > 0x7fffffffLL) return 0;
     for (int cl = 0; cl < p.n_classes; cl++) {
-        const RoiRect &q = d.rect[layer][cl];          // whole tiles (walk_down_axis rounds a fused level's rectangles to 16)
+        const RoiRect &q = rects[layer][cl];           // whole tiles (walk_down_axis rounds a fused level's rectangles to 16)
         const int ty0 = q.y0 / 16, ty1 = (q.y0 + q.rh) / 16, tx0 = q.x0 / 16, tx1 = (q.x0 + q.rw) / 16;
         for (int pt = k * p.class_base[cl]; pt < k * p.class_base[cl + 1]; pt++)
             for (int ty = ty0; ty < ty1; ty++)
@@ -365,8 +497,8 @@ extern "C" int tmat_roi_plan_down(int hh, int ww, int patch, int n_up, const int
 
 // The tile table of a fused separable layer of the same plan for a pass of k images (roi_sep_tile_table): *n_full the full-frame tile
 // count, *n_tiles the planned one; tiles (nullable: counts only) takes the planned tiles' full-frame ids, cap its room.
-extern "C" int tmat_roi_sep_tiles(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
-                                  unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
+static int sep_tiles_export(bool live, int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                            unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
 {
     if (!up_channels || !down_channels || !n_tiles || !n_full || k < 1) { set_error("tmat_roi_sep_tiles: bad argument"); return TMAT_E_ARG; }
     RoiPlan p;
@@ -375,13 +507,60 @@ extern "C" int tmat_roi_sep_tiles(int hh, int ww, int patch, int n_up, const int
         return TMAT_E_ARG;
     }
     std::vector<int> tab;
-    const long long full = roi_sep_tile_table(p, layer, k, tab);
+    const long long full = live ? roi_sep_tile_table_live(p, layer, k, tab) : roi_sep_tile_table(p, layer, k, tab);
     if (full <= 0) { set_error("tmat_roi_sep_tiles: not a fused separable layer of the plan"); return TMAT_E_ARG; }
     *n_full = (int)full;
     *n_tiles = (int)tab.size();
     if (tiles) {
         if ((int)tab.size() > cap) { set_error("tmat_roi_sep_tiles: cap too small"); return TMAT_E_ARG; }
         std::copy(tab.begin(), tab.end(), tiles);
+    }
+    return TMAT_OK;
+}
+
+extern "C" int tmat_roi_sep_tiles(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                  unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
+{
+    return sep_tiles_export(false, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
+}
+
+// the same of the constant-ring form (roi_sep_tile_table_live): the tiles of rect_live, a subsequence of tmat_roi_sep_tiles' table
+extern "C" int tmat_roi_sep_tiles_live(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                       unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
+{
+    return sep_tiles_export(true, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
+}
+
+// The constant-ring tables of the same plan (RoiDownPlan::nonconst ...): nonconst, live and rect_live [6 n_down + 4][max_classes][4] as
+// (y0, x0, rows, columns), fill [6 n_down + 4][max_classes][4 strips][4], stored [6 n_down + 4], the two per-layer totals of rect_live.
+extern "C" int tmat_roi_plan_const(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                   unsigned fused_mask, int max_classes, int *n_classes, int *nonconst, int *live, int *rect_live, int *fill,
+                                   int *stored, double *mac_live, double *bytes_live)
+{
+    if (!up_channels || !down_channels || !n_classes || !nonconst || !live || !rect_live || !fill || !stored || !mac_live || !bytes_live ||
+        max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
+        set_error("tmat_roi_plan_const: bad argument");
+        return TMAT_E_ARG;
+    }
+    RoiPlan p;
+    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, max_classes, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
+        set_error("tmat_roi_plan_const: unsupported geometry");
+        return TMAT_E_ARG;
+    }
+    *n_classes = p.n_classes;
+    const RoiDownPlan &d = p.down;
+    auto put = [](int *o, const RoiRect &q) { o[0] = q.y0; o[1] = q.x0; o[2] = q.rh; o[3] = q.rw; };
+    for (int l = 0; l < d.n_layers; l++) {
+        for (int k = 0; k < max_classes; k++) {
+            const bool in = k < p.n_classes;
+            const size_t at = ((size_t)l * max_classes + k) * 4;
+            put(nonconst + at, in ? d.nonconst[l][k] : RoiRect{0, 0, 0, 0});
+            put(live + at, in ? d.live[l][k] : RoiRect{0, 0, 0, 0});
+            put(rect_live + at, in ? d.rect_live[l][k] : RoiRect{0, 0, 0, 0});
+            for (int i = 0; i < 4; i++) put(fill + (at + i) * 4, in ? d.fill[l][k][i] : RoiRect{0, 0, 0, 0});
+        }
+        stored[l] = d.stored[l] ? 1 : 0;
+        mac_live[l] = d.mac_live[l]; bytes_live[l] = d.bytes_live[l];
     }
     return TMAT_OK;
 }

@@ -46,6 +46,22 @@ struct RoiDownPlan {
     double mac_planned[ROI_MAX_DOWN_LAYERS] = {}, mac_full[ROI_MAX_DOWN_LAYERS] = {};
     double bytes_planned[ROI_MAX_DOWN_LAYERS] = {}, bytes_full[ROI_MAX_DOWN_LAYERS] = {};
     bool free_tile[ROI_MAX_DOWN] = {};          // fused level b: some class skips a whole 16 x 16 tile of either separable layer
+
+    // The CONSTANT-RING form (TMAT_ROI_CONST).  A patch is image data inside read[c] and one value per image (the pad value) outside.
+    // nonconst: the pixels whose receptive field, clipped to the patch, reaches read[c] -- the forward walk from the input window through
+    // the taps the backward walk uses (roi_plan.cpp:TAP_*).  Outside it a tensor equals, bit for bit, the same tensor of a patch that is
+    // the pad value everywhere, at the same position (not one vector per layer: SAME pads zeros, the borders differ).
+    // live: what a launch still has to compute, need ∩ nonconst.  A tensor that is never stored (the depthwise outputs and the second
+    // pointwise output of a fused level, the stem inside the STEM layer) cannot be copied: its live is the taps of its consumer's live.
+    // rect_live: live rounded outwards by rect's rule, inside rect.
+    // fill: the pixels of a STORED tensor outside nonconst that a consumer's live reads through its taps (for the bottleneck tensor:
+    // that up block 0 reads), as at most four strips -- above, below, left and right of nonconst.  The launches copy them from the
+    // all-constant patch of the image.  Every tap of a consumer's live lies in the producer's live ∪ fill.
+    RoiRect nonconst[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {}, live[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {};
+    RoiRect rect_live[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {};
+    RoiRect fill[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES][4] = {};
+    bool stored[ROI_MAX_DOWN_LAYERS] = {};      // the layer's output is a tensor in memory that a region-form launch writes
+    double mac_live[ROI_MAX_DOWN_LAYERS] = {}, bytes_live[ROI_MAX_DOWN_LAYERS] = {};       // mac_planned / bytes_planned of rect_live
 };
 
 struct RoiPlan {
@@ -99,5 +115,7 @@ bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask)
 // whole tiles.  The table depends on k: a shorter last pass has its own.  Returns the full-frame tile count k tiles_per_img TPP, 0 when
 // the layer has no tile rectangles; out.size() == that count means every patch is computed whole.
 long long roi_sep_tile_table(const RoiPlan &p, int layer, int k, std::vector<int> &out);
+// the same of the constant-ring form: the tiles of RoiDownPlan::rect_live, a subsequence of the table above
+long long roi_sep_tile_table_live(const RoiPlan &p, int layer, int k, std::vector<int> &out);
 
 }  // namespace tmat

@@ -304,15 +304,23 @@ static bool conv(Ctx *c, ConvArgs a, hipStream_t st, const RoiSegs *roi = nullpt
 // The tile table of fused separable layer `layer` for passes of k images, cached on the plan's entry: built and uploaded on first use (a
 // blocking copy into a fresh allocation, as for the patch order), never per pass.  dev stays null when every patch is computed whole.
 // Null + error set: the allocation or the copy failed.
-static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k)
+// live: the constant-ring form's table, then every tile of the k all-constant patches behind the pass's patches.
+static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, bool live)
 {
-    for (const RoiTileTab &t : e->tabs) if (t.layer == layer && t.k == k) return &t;
+    for (const RoiTileTab &t : e->tabs) if (t.layer == layer && t.k == k && t.live == live) return &t;
     std::vector<int> ids;
     RoiTileTab t;
-    t.layer = layer; t.k = k;
-    t.full = roi_sep_tile_table(e->plan, layer, k, ids);
-    t.n = (int)ids.size();
+    t.layer = layer; t.k = k; t.live = live;
+    t.full = live ? roi_sep_tile_table_live(e->plan, layer, k, ids) : roi_sep_tile_table(e->plan, layer, k, ids);
+    t.n_rep = (long long)ids.size(); t.full_rep = t.full;
     if (t.full <= 0 || ids.empty()) { set_error("roi_tile_tab: no tile table for this layer"); return nullptr; }
+    if (live) {
+        const int TW = e->plan.down.res[layer] / 16, TPP = TW * TW;
+        if (t.full + (long long)k * TPP > 0x7fffffffLL) { set_error("roi_tile_tab: too many tiles"); return nullptr; }
+        for (int id = (int)t.full; id < (int)t.full + k * TPP; id++) ids.push_back(id);
+        t.full += (long long)k * TPP;
+    }
+    t.n = (int)ids.size();
     if ((long long)ids.size() < t.full) {
         if (!hip_ok(hipMalloc((void **)&t.dev, ids.size() * sizeof(int)), "hipMalloc(tile table)")) return nullptr;
         if (!hip_ok(hipMemcpy(t.dev, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy(tile table)")) { hipFree(t.dev); return nullptr; }
@@ -349,20 +357,49 @@ static RoiSegs roi_segs(const RoiPlan &p, int l, int k) { return roi_segs_of(p, 
 // Down path (memory-bound kernels + small pointwise GEMMs): X (n, P, P) -> dout (n, P/16, P/16, f_deep)
 // plan (tiled callers; null: whole patches): with a down plan (roi_plan.h:RoiDownPlan) the kernels named by c->roi_down compute only what
 // the region-form up path reads of dout, grown backwards; the patches are then in the plan's class-major order
-int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan)
+// padval (nullable): the constant-ring form (tmat_ctx.h:Ctx::roi_const) -- the k all-constant patches of the pass are written behind X's
+// n patches and run through the same launches as one more segment of whole patches; the launches of the pass's own patches take
+// rect_live, and after each launch that writes a stored tensor the strips of RoiDownPlan::fill are copied out of the constant patches
+int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval)
 {
     if (n <= 0) return TMAT_OK;
     if (n > c->max_patches) { set_error("unet_down_dev: n > max_patches"); return TMAT_E_ARG; }
     const bool roi_any = plan && plan->n_classes > 0 && plan->down.n_down == (int)c->down.size() && n % plan->tiles_per_img == 0;
     const bool roi_b = roi_any && (c->roi_down & 1u);
     const int kimg = roi_any ? n / plan->tiles_per_img : 0;
+    // the constant-ring form: f32 path, some region form of the down path on, room for the constant patches and for their segment
+    const bool cst = roi_any && padval && c->roi_down && c->precision == TMAT_PRECISION_F32 && kimg <= c->const_cap &&
+                     plan->n_classes < ROI_MAX_CLASSES;
+    const int n_own = n;
+    if (cst) {
+        launch_const_patches(padval, kimg, c->patch * c->patch, const_cast<float *>(X) + (size_t)n * c->patch * c->patch, s);
+        n += kimg;              // every launch below runs the constant patches too
+    }
     RoiSegs sg{};
     // the segments of layer k of down block bi (null: full-frame)
     auto segs = [&](size_t bi, int k) -> const RoiSegs * {
         if (!roi_b) return nullptr;
-        sg = roi_segs_of(*plan, plan->down.rect[6 * bi + k], kimg);
+        sg = roi_segs_of(*plan, (cst ? plan->down.rect_live : plan->down.rect)[6 * bi + k], kimg);
+        if (cst) {
+            RoiSeg &g = sg.s[sg.nseg++];
+            g = RoiSeg{};
+            g.p0 = n_own; g.np = kimg; g.rh = g.rw = plan->down.res[6 * bi + k];
+        }
         return &sg;
     };
+    // the strips of layer l's tensor t (C channels) that the constant patches hold: after the launch that writes t, before its readers
+    auto fill = [&](float *t, int l, int C) -> bool {
+        if (!cst) return true;
+        FillItems f{};
+        for (int cl = 0; cl < plan->n_classes; cl++)
+            for (int i = 0; i < 4 && plan->class_count[cl] > 0; i++) {
+                const RoiRect &q = plan->down.fill[l][cl][i];
+                if (q.rh <= 0 || q.rw <= 0) continue;
+                f.it[f.n++] = FillItem{kimg * plan->class_base[cl], kimg * plan->class_count[cl], plan->class_count[cl], q.y0, q.x0, q.rh, q.rw};
+            }
+        return launch_const_fill(t, n_own, n, plan->down.res[l], C, f, s);
+    };
+    const int LD = 6 * (int)c->down.size();
     // TMAT_ROI_DOWN bit 1: the tile table of fused layer k (1 or 3) of down block bi.  dev null: the launch stays full-frame (no plan, bf16x3
     // weights, or every patch whole).  A table that could not be made clears tab_ok (the error is set)
     RoiEntry *ent = nullptr;
@@ -373,11 +410,12 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
     auto tiles = [&](size_t bi, int k, int H, bool f32) -> RoiTileTab {
         RoiTileTab t;
         t.full = t.n = n * (H / 16) * (H / 16);
+        t.full_rep = t.n_rep = (long long)n_own * (H / 16) * (H / 16);
         if (ent && f32) {
-            if (const RoiTileTab *made = roi_tile_tab(ent, 6 * (int)bi + k, kimg)) t = *made;
+            if (const RoiTileTab *made = roi_tile_tab(ent, 6 * (int)bi + k, kimg, cst)) t = *made;
             else tab_ok = false;
         }
-        c->sep_tiles.push_back({t.dev ? t.n : t.full, t.full});
+        c->sep_tiles.push_back({t.dev ? t.n_rep : t.full_rep, t.full_rep});       // (the constant patches' whole tiles are not counted)
         return t;
     };
     const int P = c->patch;
@@ -389,8 +427,10 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
     // even pixels only, reads those from stem_even_kernel's quarter-size tensor as a unit-stride 1x1 convolution.
     const bool stem_in_sep = c->stem_fused && !c->down.empty() && down_block_ws(c, 0) && c->down[0].cin == c->f0 &&
                              !(c->precision == TMAT_PRECISION_BF16X3 && c->sep_bf16);
-    if (stem_in_sep) launch_stem_even(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s, segs(0, 4));      // the pixels block 0's residual 1x1 takes
-    else launch_stem(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s);
+    if (stem_in_sep) {
+        launch_stem_even(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s, segs(0, 4));      // the pixels block 0's residual 1x1 takes
+        if (!fill(b0, LD, c->f0)) return TMAT_E_ARG;
+    } else launch_stem(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s);
     int H = P / 2;
     for (size_t bi = 0; bi < c->down.size(); bi++) {
         auto &d = c->down[bi];
@@ -412,11 +452,12 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
                 if (!launch_sepconv_ws_stem(X, n, H, H, d.cin, c->stem_w, c->stem_scale, c->stem_shift, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s,
                                             t0.dev, t0.n)) return TMAT_E_ARG;
             } else if (!launch_sepconv_ws(b0, n, H, H, d.cin, bi > 0, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s, sprec, t0.dev, t0.n)) return TMAT_E_ARG;
+            if (!fill(b2, 6 * (int)bi + 1, d.cout)) return TMAT_E_ARG;
             ConvArgs r{};
             r.in = b0; r.N = n; r.h = H; r.w = H; r.Cin = d.cin; r.ksize = 1; r.stride = 2; r.W = d.res_w; r.Cout = d.cout;
             r.scale = nullptr; r.shift = d.res_b; r.out = b1;
             if (stem_here) { r.h = H / 2; r.w = H / 2; r.stride = 1; }      // b0 holds the even pixels only
-            if (!conv(c, r, s, segs(bi, 4))) return TMAT_E_ARG;
+            if (!conv(c, r, s, segs(bi, 4)) || !fill(b1, 6 * (int)bi + 4, d.cout)) return TMAT_E_ARG;
             float *nxt = bi + 1 == c->down.size() ? dout : b0;
             // (outside the residual's rectangle the pooled pixels take values nobody wrote and nobody reads; a tile the table skips leaves
             // its pixels and strips unwritten: a needed pooled pixel's 2 i .. 2 i + 2 lie in the layer's rectangle, strips included)
@@ -427,25 +468,30 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
                 if (!launch_sepconv_ws(b2, n, H, H, d.cout, 0, d.dw[1], pw1, d.cout, d.scale[1], d.shift[1], 0, b3, s, sprec, t1.dev, t1.n)) return TMAT_E_ARG;
                 launch_maxpool_add(b3, n, H, H, d.cout, b1, nxt, s, nullptr, segs(bi, 5));
             }
+            if (!fill(nxt, 6 * (int)bi + 5, d.cout)) return TMAT_E_ARG;
             H /= 2;
             continue;
         }
+        const int l0 = 6 * (int)bi;
         launch_dwconv(b0, n, H, H, d.cin, 1, d.dw[0], b1, s, segs(bi, 0));
+        if (!fill(b1, l0, d.cin)) return TMAT_E_ARG;
         ConvArgs a{};
         a.in = b1; a.N = n; a.h = H; a.w = H; a.Cin = d.cin; a.relu_in = 0; a.ksize = 1; a.stride = 1;
         a.W = d.pw[0]; a.Cout = d.cout; a.scale = d.scale[0]; a.shift = d.shift[0]; a.resid = nullptr; a.rs = 0;
         a.relu_out = 1; a.out = b2;
-        if (!conv(c, a, s, segs(bi, 1))) return TMAT_E_ARG;
+        if (!conv(c, a, s, segs(bi, 1)) || !fill(b2, l0 + 1, d.cout)) return TMAT_E_ARG;
         launch_dwconv(b2, n, H, H, d.cout, 0, d.dw[1], b3, s, segs(bi, 2));
+        if (!fill(b3, l0 + 2, d.cout)) return TMAT_E_ARG;
         a.in = b3; a.Cin = d.cout; a.W = d.pw[1]; a.scale = d.scale[1]; a.shift = d.shift[1]; a.relu_out = 0; a.out = b2;
-        if (!conv(c, a, s, segs(bi, 3))) return TMAT_E_ARG;
+        if (!conv(c, a, s, segs(bi, 3)) || !fill(b2, l0 + 3, d.cout)) return TMAT_E_ARG;
         ConvArgs r{};
         r.in = b0; r.N = n; r.h = H; r.w = H; r.Cin = d.cin; r.ksize = 1; r.stride = 2; r.W = d.res_w; r.Cout = d.cout;
         r.scale = nullptr; r.shift = d.res_b; r.out = b1;
-        if (!conv(c, r, s, segs(bi, 4))) return TMAT_E_ARG;
+        if (!conv(c, r, s, segs(bi, 4)) || !fill(b1, l0 + 4, d.cout)) return TMAT_E_ARG;
         const bool last = bi + 1 == c->down.size();
         float *dr = (last && c->relu_copy && dout == c->dout[di]) ? c->dout_relu[di] : nullptr;      // activated copy for the first up block
         launch_maxpool_add(b2, n, H, H, d.cout, b1, last ? dout : b0, s, dr, segs(bi, 5));
+        if (!fill(last ? dout : b0, l0 + 5, d.cout) || (dr && !fill(dr, l0 + 5, d.cout))) return TMAT_E_ARG;
         if (dr) c->dout_relu_ok[di] = true;
         H /= 2;
     }
@@ -573,7 +619,7 @@ int ensure_patch_io(Ctx *c, int n_patches)
     c->patch_in = c->patch_in2 = c->patch_out = nullptr;
     c->patch_cap = 0;
     const size_t bytes = (size_t)c->patch * c->patch * n_patches * sizeof(float);
-    c->patch_in = (float *)c->ws.dev(bytes, "hipMalloc(patch_in)");
+    c->patch_in = (float *)c->ws.dev(bytes + (size_t)c->patch * c->patch * c->const_cap * sizeof(float), "hipMalloc(patch_in)");
     c->patch_out = (float *)c->ws.dev(bytes, "hipMalloc(patch_out)");
     if (!c->patch_in || !c->patch_out) return TMAT_E_HIP;
     c->patch_cap = n_patches;
@@ -597,7 +643,8 @@ int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred
         const float *xi = x_dev + (size_t)i0 * hh * ww;
         launch_minmax_f32(xi, k, (size_t)hh * ww, mn, mx, c->stream);
         launch_extract_tiles(xi, mn, k, g, c->patch_in, c->stream);
-        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan)
+        // (the constant-ring form only on request: the default launches of this entry point are pinned to the dependency plan's tiles)
+        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan, c->roi_const == 1 ? mn : nullptr)
                       : unet_forward_dev(c, c->patch_in, k * g.tiles_per_img, c->patch_out, c->stream);
         if (!rc && plan) rc = unet_up_dev(c, c->dout[0], k * g.tiles_per_img, c->patch_out, c->stream, plan);
         if (rc) return rc;
@@ -671,6 +718,12 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
         if (strcmp(e, "0") && strcmp(e, "1") && strcmp(e, "2") && strcmp(e, "3")) { set_error("tmat_create: TMAT_ROI_DOWN must be 0, 1, 2 or 3"); delete c; return TMAT_E_ARG; }
         c->roi_down = (unsigned)atoi(e);
     }
+    if (const char *e = getenv("TMAT_ROI_CONST")) {
+        if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_CONST must be 0 or 1"); delete c; return TMAT_E_ARG; }
+        c->roi_const = atoi(e);
+    }
+    // room for the all-constant patches of a pass behind its patches (tmat_ctx.h): the down-path workspaces and the input buffers only
+    c->const_cap = c->roi_const == 0 ? 0 : std::max(4, c->max_patches / 64);
     if (const char *e = getenv("TMAT_FUSED_POOL")) c->fused_pool = atoi(e) != 0;
     if (const char *e = getenv("TMAT_STEM_FUSED")) c->stem_fused = atoi(e) != 0;
     if (const char *e = getenv("TMAT_SEP_BF16")) c->sep_bf16 = atoi(e) != 0;
@@ -694,15 +747,16 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     // activation workspace: per patch (P/2)^2 * f0 floats for buf0/buf1 and twice that for buf2/buf3
     const size_t unit = (size_t)(patch / 2) * (patch / 2) * c->f0;
     const size_t sizes[4] = {unit, unit, 2 * unit, 2 * unit};
+    const size_t down_cap = (size_t)c->max_patches + c->const_cap;
     auto dev_f32 = [c](size_t bytes, const char *what) { return (float *)c->ws.dev(bytes, what); };
     for (int i = 0; i < 4; i++)
-        if (!(c->buf[i] = dev_f32(sizes[i] * c->max_patches * sizeof(float), "hipMalloc(activations)"))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
+        if (!(c->buf[i] = dev_f32(sizes[i] * down_cap * sizeof(float), "hipMalloc(activations)"))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
     // up-path buffers: t1 (unit), hoisted residual (unit/4), block outputs alternate (unit/2, unit); down-path output x2
     const size_t usizes[4] = {unit, unit / 4, unit / 2, unit};
     for (int i = 0; i < 4; i++)
         if (!(c->ubuf[i] = dev_f32(usizes[i] * c->max_patches * sizeof(float), "hipMalloc(up buffers)"))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
     const size_t dsz = (size_t)(patch >> (1 + c->down.size())) * (patch >> (1 + c->down.size())) * c->up[0].cin;
-    const size_t dout_bytes = dsz * c->max_patches * sizeof(float);
+    const size_t dout_bytes = dsz * down_cap * sizeof(float);
     for (int i = 0; i < 2; i++)
         if (!(c->dout[i] = dev_f32(dout_bytes, "hipMalloc(dout)"))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
     if (const char *e = getenv("TMAT_RELU_COPY")) c->relu_copy = atoi(e) != 0;
@@ -727,7 +781,9 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
             !hip_ok(hipEventCreateWithFlags(&c->ev_blend[i], hipEventDisableTiming), "hipEventCreate")) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
     const size_t pp = (size_t)patch * patch * c->max_patches * sizeof(float);
     c->scratch_bytes = 64 << 20;
-    if (!(c->patch_in = dev_f32(pp, "hipMalloc(patch_in)")) || !(c->patch_out = dev_f32(pp, "hipMalloc(patch_out)")) ||
+    for (int i = 0; i < 2 && c->const_cap; i++)
+        if (!(c->padval[i] = dev_f32((size_t)c->const_cap * sizeof(float), "hipMalloc(pad values)"))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
+    if (!(c->patch_in = dev_f32(pp + (size_t)patch * patch * c->const_cap * sizeof(float), "hipMalloc(patch_in)")) || !(c->patch_out = dev_f32(pp, "hipMalloc(patch_out)")) ||
         !(c->scratch = c->ws.dev(c->scratch_bytes, "hipMalloc(scratch)"))) { tmat_destroy((tmat_handle)c); return TMAT_E_HIP; }
     c->patch_cap = c->max_patches;
     // squared-spline window (smooth_tiled_predictions.py:26-41), f64, on host then uploaded

@@ -26,7 +26,9 @@ struct UpBlock {
 struct ProfEv { hipEvent_t e0, e1; double flops; };
 // tile table of a fused separable layer for passes of k images (roi_plan.h:roi_sep_tile_table): dev (null: every patch whole, the launch
 // stays full-frame) holds n ids; a constant like `order` -- uploaded once, outside the workspaces tmat_debug_poison fills
-struct RoiTileTab { int layer = 0, k = 0, n = 0; long long full = 0; int *dev = nullptr; };
+// live: the table of the constant-ring form (roi_sep_tile_table_live) followed by every tile of the pass's k all-constant patches, which
+// sit behind its patches; n_rep of full_rep: the planner's own counts, without those (what tmat_debug_sep_tiles reports)
+struct RoiTileTab { int layer = 0, k = 0, n = 0; long long full = 0; int *dev = nullptr; bool live = false; long long n_rep = 0, full_rep = 0; };
 struct RoiEntry {
     RoiPlan plan;
     int4 *order = nullptr;                  // device, [tiles_per_img] (TileGeom::order)
@@ -201,6 +203,14 @@ struct Ctx {
     // level, the residual 1x1 layers, the stem at the even pixels, the pooling fix-ups.  Bit 1: the fused separable layers visit only
     // the tiles of their rectangles (RoiEntry::tabs).  0: the down path stays full-frame
     unsigned roi_down = 3u;
+    // TMAT_ROI_CONST: the constant-ring form of the region-form down path (roi_plan.h:RoiDownPlan::live): what the padding ring makes
+    // constant is copied from an all-constant patch per image instead of computed.  -1 (unset): the batch pipeline runs it, predict_smooth
+    // does not (tests pin its launches to the dependency plan's tiles); 0: nobody; 1: both.  The k all-constant patches of a pass of k
+    // images ride behind its patches in the same launches: the down-path workspaces and the input buffers hold const_cap patches more
+    // than max_patches, and a pass of more images (fewer than 64 patches per image at the default size) keeps the dependency plan.
+    int roi_const = -1;
+    int const_cap = 0;
+    float *padval[2] = {nullptr, nullptr};                   // the pad values of a pipeline pass, per slot: c->scratch is rewritten by the front end of the pass after next
     std::vector<RoiEntry *> roi_cache;
     std::vector<std::pair<long long, long long>> sep_tiles;  // (planned, full) tiles of the fused separable launches of the last down pass (tmat_debug_sep_tiles)
     bool fused_sep = true;                                   // fused depthwise -> pointwise kernel (sepconv_ws_kernel) where the level allows (TMAT_FUSED_SEP=0: separate kernels)
@@ -219,7 +229,9 @@ struct Ctx {
 
 int unet_forward_dev(Ctx *c, const float *X, int n, float *Y, hipStream_t s);
 int ensure_patch_io(Ctx *c, int n_patches);
-int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan = nullptr);
+// padval (nullable, with a plan only): the pad values of the pass's images on the device -- the constant-ring form, where the handle and
+// the pass allow it.  X then has room for n + n / tiles_per_img patches (patch_in and patch_in2 do): the all-constant patches are written there
+int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan = nullptr, const float *padval = nullptr);
 // plan (nullable): region form; n is then a whole number of images' patches in the plan's class-major order
 int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s, const RoiPlan *plan = nullptr);
 // the region plan of g's geometry (cached on the handle) and, in g.order, its patch order; null and the image-major order when the region

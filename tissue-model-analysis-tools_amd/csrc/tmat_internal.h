@@ -113,6 +113,16 @@ void launch_maxpool_add(const float *p2, int N, int H, int W, int C, const float
 // roi (nullable): workgroups whose 8 x 16 stored pixels lie outside their patch's rectangle return at once
 void launch_final(const float *S, int N, int h, int w, int C, const float *Wf, float bias, float *out, hipStream_t s, const RoiSegs *roi = nullptr);
 
+// ---- constant-ring form of the down path (const_fill_kernels.hip; roi_plan.h:RoiDownPlan::fill) ----
+// one strip of one class: the patches [p0, p0 + np), cnt per image in image order, take the pixels [y0, y0 + rh) x [x0, x0 + rw), all
+// channels, from the all-constant patch src0 + (patch - p0) / cnt of the same tensor
+struct FillItem { int p0, np, cnt, y0, x0, rh, rw; };
+struct FillItems { int n; FillItem it[64]; };
+// t (N, H, H, C), C % 4 == 0; false (and the error set) when an item leaves the tensor
+bool launch_const_fill(float *t, int src0, int N, int H, int C, const FillItems &f, hipStream_t s);
+// out (k, pp): patch i filled with padval[i]; pp % 4 == 0
+void launch_const_patches(const float *padval, int k, int pp, float *out, hipStream_t s);
+
 // ---- tiling / blending (blend_kernels.hip) -------------------------------------------------
 // x: (n, hh, ww) f32; padval[n]; patches out: (n, 8, na_g, nb_g, ws, ws)
 struct TileGeom {

@@ -152,6 +152,7 @@ EXPORTS = [
     "tmat_analyze_stack", "tmat_field_stats", "tmat_field_stats_pruned", "tmat_resize_aa_u16", "tmat_cell_area_batch", "tmat_cell_area_masked", "tmat_resize_linear_u16",
     "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi", "tmat_resnet_set_precision", "tmat_conv2d",
     "tmat_roi_plan", "tmat_roi_plan_tight", "tmat_roi_plan_exact", "tmat_conv2d_roi", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles",
+    "tmat_roi_plan_const", "tmat_roi_sep_tiles_live",
     "tmat_stage_pictures", "tmat_host_stage_pictures", "tmat_analyze_batch_ex", "tmat_analyze_batch_ex_dev",
 ]
 
@@ -583,18 +584,44 @@ def roi_plan_down(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), down_cha
     return dict(n_classes=int(ncls[0]), rects=rects, needs=needs, mac_planned=mp, mac_full=mf, bytes_planned=bp, bytes_full=bf, free_tile=free)
 
 
-def roi_sep_tiles(hh, ww, layer, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
+def roi_plan_const(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3, max_classes=16):
+    """tmat_roi_plan_const (include/tmat.h): the constant-ring tables of roi_plan_down's plan; host arithmetic, no GPU.
+    Returns a dict: n_classes, nonconst / live / rect_live [6 n_down + 4][max_classes][4] (y0, x0, rows, columns),
+    fill [6 n_down + 4][max_classes][4 strips][4], stored / mac_live / bytes_live [6 n_down + 4]."""
+    L = lib()
+    L.tmat_roi_plan_const.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint, C.c_int] + [C.c_void_p] * 8
+    n_up, n_down = len(channels) - 1, len(down_channels) - 1
+    ch, dch = np.asarray(channels, np.int32), np.asarray(down_channels, np.int32)
+    nl = 6 * n_down + 4
+    ncls = np.zeros(1, np.int32)
+    nonconst, live, rect_live = (np.zeros((nl, max_classes, 4), np.int32) for _ in range(3))
+    fill = np.zeros((nl, max_classes, 4, 4), np.int32)
+    stored = np.zeros(nl, np.int32)
+    ml, bl = np.zeros(nl), np.zeros(nl)
+    check(L.tmat_roi_plan_const(hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), max_classes, ptr(ncls), ptr(nonconst),
+                                ptr(live), ptr(rect_live), ptr(fill), ptr(stored), ptr(ml), ptr(bl)), "roi_plan_const")
+    return dict(n_classes=int(ncls[0]), nonconst=nonconst, live=live, rect_live=rect_live, fill=fill, stored=stored, mac_live=ml, bytes_live=bl)
+
+
+def roi_sep_tiles_live(hh, ww, layer, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
+    """tmat_roi_sep_tiles_live (include/tmat.h): roi_sep_tiles for the constant-ring form's rectangles (rect_live)."""
+    return roi_sep_tiles(hh, ww, layer, k, patch, channels, down_channels, fused_mask, _export="tmat_roi_sep_tiles_live")
+
+
+def roi_sep_tiles(hh, ww, layer, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3,
+                  _export="tmat_roi_sep_tiles"):
     """tmat_roi_sep_tiles (include/tmat.h): the full-frame ids of the tiles fused separable layer `layer` visits in a pass of k images;
     host arithmetic, no GPU.  Returns (ids int32 [planned], full-frame tile count)."""
     L = lib()
-    L.tmat_roi_sep_tiles.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint] + [C.c_int] * 3 + [C.c_void_p] * 3
+    fn = getattr(L, _export)
+    fn.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint] + [C.c_int] * 3 + [C.c_void_p] * 3
     n_up, n_down = len(channels) - 1, len(down_channels) - 1
     ch, dch = np.asarray(channels, np.int32), np.asarray(down_channels, np.int32)
     nt, nf = np.zeros(1, np.int32), np.zeros(1, np.int32)
     args = (hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), int(layer), int(k))
-    check(L.tmat_roi_sep_tiles(*args, 0, ptr(nt), ptr(nf), None), "roi_sep_tiles")
+    check(fn(*args, 0, ptr(nt), ptr(nf), None), _export[5:])
     ids = np.zeros(max(int(nt[0]), 1), np.int32)
-    check(L.tmat_roi_sep_tiles(*args, len(ids), ptr(nt), ptr(nf), ptr(ids)), "roi_sep_tiles")
+    check(fn(*args, len(ids), ptr(nt), ptr(nf), ptr(ids)), _export[5:])
     return ids[:int(nt[0])], int(nf[0])
 
 
