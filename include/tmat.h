@@ -570,12 +570,20 @@ int tmat_inv_depth_predict_multi(tmat_handle h, const int *model_ids, int n_mode
 int tmat_resnet_set_precision(tmat_handle h, int mode);
 /*
  * Stage-wise test entry point: ONE convolution of conv_mfma_kernel on host buffers.  x (n, hh, ww, cin) f32; w in the Keras
- * layout (ksize, ksize, cin, cout); ksize 1 (stride 1 or 2, TF SAME: even indices) or 3 (stride 1, SAME); cin % 32 == 0 (and
- * 9 cin / 32 even for ksize 3), cout 64 or a multiple of 128; v = scale ? fmaf(acc, scale, shift) : acc + shift, + resid
- * (nullable, shaped like out), ReLU on load / on store as asked; out (n, hh / stride, ww / stride, cout).  prec 0: the f32
- * contract (bit-exact with oracle/unet.py:_conv); prec 3: the f16 contract above; prec 4: ONE f16act convolution (every restriction
- * of prec 3, and cin % 64 == 0): x -- after the load-side ReLU -- and resid are rounded to f16 on the host, the convolution runs on
- * f16 device buffers, out is its f16 output widened to f32: round_f16(the prec 3 result on the same f16-exact operands), bit for bit.
+ * layout (ksize, ksize, cin, cout); ksize 1 (stride 1 or 2, TF SAME: even indices) or 3 (stride 1, SAME);
+ * v = scale ? fmaf(acc, scale, shift) : acc + shift, + resid (nullable, shaped like out), ReLU on load / on store as asked; out
+ * (n, hh / stride, ww / stride, cout).  prec 0: the f32 contract (bit-exact with oracle/unet.py:_conv); prec 3: the f16 contract
+ * above; prec 4: ONE f16act convolution: x -- after the load-side ReLU -- and resid are rounded to f16 on the host, the convolution
+ * runs on f16 device buffers, out is its f16 output widened to f32: round_f16(the prec 3 result on the same f16-exact operands), bit
+ * for bit.
+ * Accepted shapes, in every precision (what launch_conv checks; tests/test_gpu_conv_shapes.py runs both sides of each):
+ *   cin % 64 == 0 (a K loop step is two 32-channel chunks; 32 and 96 are refused);
+ *   cout % 64 == 0: 128-wide column tiles when cout % 128 == 0, 64-wide ones otherwise (64, 192, 320, ...; 32 and 96 are refused);
+ *   hh and ww multiples of the stride, and an output at least two pixels wide (ww / stride >= 2; one row is fine);
+ *   n (hh / stride) (ww / stride) < 2^30.
+ * Anything else -- ksize 3 at stride 2 included -- returns TMAT_E_ARG with a message before a kernel is launched.  Any other
+ * width, height or pixel count is taken: the prologue is row-uniform for output widths that are multiples of 8 and per-lane
+ * otherwise, and the last pixel tile may end past the last pixel.
  */
 int tmat_conv2d(tmat_handle h, int prec, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int stride, int cout,
                 const float *scale, const float *shift, const float *resid, int relu_in, int relu_out, float *out);
@@ -590,6 +598,10 @@ int tmat_conv2d(tmat_handle h, int prec, const float *x, int n, int hh, int ww, 
  *     enumerate STORED pixels (hh x ww): stored pixel (i, j) makes the outputs (2 i + {0, 1}, 2 j + {0, 1}).
  *   out is filled by the CALLER and comes back with the computed pixels replaced: a word outside the rectangles keeps what it held.
  *   out_relu (nullable; caller-filled likewise): the activated copy max(v, +0) that the up path's second convolutions write.
+ * Accepted shapes (launch_conv's checks; anything else returns TMAT_E_ARG with a message, launches nothing and leaves out as it was):
+ * cin % 64 == 0 for ksize 1 and 3, cin % 32 == 0 for the sub-pixel form (its four taps per class make an even chunk count at 32);
+ * cout % 64 == 0 (128-wide column tiles when cout % 128 == 0, 64-wide otherwise); ww >= 2; n hh ww < 2^30; with segments, an output plane
+ * per patch below 2^31 bytes.
  * Any first column and any width are taken: the epilogue runs its row-uniform form where a group of 4 or 8 pixels lies in one row, its
  * row-split form on other widths >= 8 and the per-lane form below 8; the prologue is row-uniform for widths that are multiples of 8 and
  * per-lane otherwise.  Inside the rectangles the bits are those of the full-frame launch.

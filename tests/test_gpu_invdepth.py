@@ -30,6 +30,37 @@ def test_small_trunk_bitexact(plain):
     assert 0.01 < got.min() and got.max() < 0.99
 
 
+@pytest.mark.parametrize("size,n", [(96, 2), (160, 1), (224, 1)])
+def test_small_trunk_bitexact_at_other_input_sizes(plain, size, n):
+    """tmat_resnet_predict takes any size % 32 == 0.  The standard 224 gives the convolutions widths 56 / 28, 96 gives 24 / 12 and 160
+    gives 40 / 20: 28, 12 and 20 are no multiples of 8 (the per-lane prologue of conv_mfma_kernel, which the 64 and 256 of the other tests
+    never take), and the pixel counts 784, 288 and 400 end inside a tile"""
+    from oracle import resnet as orr
+    from tmat_amd import inv_depth
+    w = inv_depth.synth_resnet_weights(3, "conv3_block1_out")
+    ens = inv_depth.InvDepthEnsemble(plain, [w], size=size)
+    rs = np.random.RandomState(size)
+    x = (rs.uniform(0, 255, (n, size, size, 1)) - np.array([103.939, 116.779, 123.68])).astype(np.float32)
+    got = ens.predict(x)
+    ref = orr.forward(w, x)
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (got, ref)
+    assert 0.01 < got.min() and got.max() < 0.99
+
+
+def test_stack_pipeline_at_size_96(plain):
+    """a 300 x 360 stack prepared for 96 x 96 inputs: the resize, the rescaling and the probabilities equal the oracle's bit for bit"""
+    from oracle import resnet as orr
+    from tmat_amd import inv_depth, synth
+    w = inv_depth.synth_resnet_weights(3, "conv3_block1_out")
+    ens = inv_depth.InvDepthEnsemble(plain, [w], size=96)
+    stack = synth.synth_stack(13, 2, 300, 360, n_vessels=8)
+    probs, x = ens.predict_stack(stack, return_input=True)
+    ox = orr.prep_inv_depth_imgs(stack, 96)
+    assert x.shape == (2, 96, 96, 3) and np.array_equal(x.view(np.uint32), ox.view(np.uint32))
+    ref = orr.forward(w, ox)
+    assert probs.shape == (2, 1) and np.array_equal(probs[:, 0].view(np.uint32), ref.view(np.uint32)), (probs[:, 0], ref)
+
+
 def test_full_model_and_stack_pipeline(plain):
     """the configured model (conv4_block6_out, 256 x 256) on a small stack: data preparation equals the oracle bit for bit,
     probabilities of two ensemble members equal the oracle, the ensemble vote is the reference's rounding rule"""
