@@ -808,6 +808,34 @@ int tmat_roi_sep_tiles_live(int hh, int ww, int patch, int n_up, const int *up_c
                             unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles);
 
 /*
+ * The shared-interior form of that plan (TMAT_ROI_SHARE at tmat_create, on top of the constant-ring form: the batch pipeline runs it
+ * unless the variable or TMAT_ROI_CONST is 0, tmat_predict_smooth only when it is 1).  The patches of an orientation overlap by half a
+ * side, and the down path's tensors hold the same bits in both patches wherever the receptive field crosses neither patch's border.
+ * Per layer and class:
+ *   inner:  [layers][max_classes][4] = y0, x0, rows, columns: the complement of the ring, the outputs whose receptive field, clipped
+ *           to the patch, touches the patch border;
+ *   share:  [layers][max_classes][4] = row lo, row hi, column lo, column hi: the positions (per axis) that the next patch on the axis
+ *           holds at position - side / 2, computed by itself, whichever patch that is; empty without a successor;
+ *   comp:   [layers][max_classes][2][patch] bytes (rows, then columns; the layer's side used): the needed pixels the patch computes
+ *           itself, per axis; the 2-D set is the product.
+ * fills: [n_fill][7] = layer, class, direction, y0, x0, rows, columns -- the shared pixels of a stored tensor that a consumer taps,
+ * copied from the right (0), lower (1) or diagonal (2) neighbour at (y, x - S), (y - S, x), (y - S, x - S), S = side / 2.
+ * neighbours: [tiles_per_img][3] image-major tile right of, below, diagonally below a tile, or -1.
+ * tmat_roi_sep_tiles_share: the tiles the fused layers still visit, a subsequence of tmat_roi_sep_tiles_live's table in its order.
+ */
+int tmat_roi_plan_share(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                        unsigned fused_mask, int max_classes, int *n_classes, int *inner, int *share, unsigned char *comp,
+                        int fill_cap, int *n_fill, int *fills, int tiles_cap, int *neighbours);
+int tmat_roi_sep_tiles_share(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                             unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles);
+/*
+ * Test-only: the host-side argument checks of the share-fill launcher on a table of n_items items [7] = first patch, patches,
+ * direction, y0, x0, rows, columns of a tensor (n_patches, side, side, channels) and a neighbour table [n_patches][3].  Nothing is
+ * launched.  TMAT_OK when the launcher would take them; TMAT_E_ARG with the reason in tmat_last_error otherwise.
+ */
+int tmat_debug_share_fill_check(int n_patches, int side, int channels, const int *neighbours, int n_items, const int *items);
+
+/*
  * Test-only (tests/test_gpu_roi_sep.py): the fused separable launches of the handle's last down pass, in launch order -- planned[i]
  * tiles visited of full[i] (equal for a full-frame launch), counted on the host at launch time.  *n: their number (at most cap are
  * written).

@@ -287,6 +287,7 @@ bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask)
                 for (int l = 6 * b + 1; l <= 6 * b + 3; l += 2)
                     if (d.rect[l][k].rh < d.res[l] || d.rect[l][k].rw < d.res[l]) d.free_tile[b] = true;
     }
+    roi_plan_share(p);
     return true;
 }
 
@@ -310,6 +311,264 @@ static long long sep_tile_table(const RoiPlan &p, const RoiRect (*rects)[ROI_MAX
         for (int pt = k * p.class_base[cl]; pt < k * p.class_base[cl + 1]; pt++)
             for (int ty = ty0; ty < ty1; ty++)
                 for (int tx = tx0; tx < tx1; tx++) out.push_back(pt * TPP + ty * TW + tx);
+    }
+    return full;
+}
+
+// ---- the shared-interior form (roi_plan.h:RoiDownPlan::share) ----
+namespace {
+
+typedef std::vector<unsigned char> Mask;
+
+// the outputs in [0, R) of which EVERY tap lies in v (v inside the producer's side: a tap outside the tensor is outside v)
+Iv tap_fwd_all(Iv v, Tap t, int R)
+{
+    if (empty(v)) return Iv{0, 0};
+    const Iv o = clip(Iv{-floor_div(-(v.lo - t.a), t.s), floor_div(v.hi - 1 - t.b, t.s) + 1}, R);
+    return empty(o) ? Iv{0, 0} : o;
+}
+Mask mask_of(Iv v, int R)
+{
+    Mask m(R, 0);
+    for (int i = std::max(v.lo, 0); i < std::min(v.hi, R); i++) m[i] = 1;
+    return m;
+}
+// the taps of the outputs in m, inside the producer's side R
+Mask taps_of(const Mask &m, Tap t, int R)
+{
+    Mask o(R, 0);
+    for (int i = 0; i < (int)m.size(); i++)
+        if (m[i])
+            for (int j = std::max(t.s * i + t.a, 0); j <= std::min(t.s * i + t.b, R - 1); j++) o[j] = 1;
+    return o;
+}
+std::vector<Iv> runs_of(const Mask &m)
+{
+    std::vector<Iv> r;
+    for (int i = 0; i < (int)m.size(); i++)
+        if (m[i]) {
+            if (!r.empty() && r.back().hi == i) r.back().hi = i + 1;
+            else r.push_back(Iv{i, i + 1});
+        }
+    return r;
+}
+Iv longest_run(const Mask &m)
+{
+    Iv best{0, 0};
+    for (const Iv &v : runs_of(m)) if (v.hi - v.lo > best.hi - best.lo) best = v;
+    return best;
+}
+bool any(const Mask &m) { for (unsigned char c : m) if (c) return true; return false; }
+unsigned long long tiles_touching(const Mask &m)
+{
+    unsigned long long t = 0;
+    for (int i = 0; i < (int)m.size(); i++) if (m[i]) t |= 1ull << (i / 16);
+    return t;
+}
+
+// one axis key: the interval of `read` on the axis, the patches that follow a patch of the key, and the key's sets per layer
+struct AxisKey {
+    Iv rd{0, 0};
+    std::vector<int> next;                  // keys of the successors (no duplicates)
+    bool last = false;                      // some patch of the key has no successor on the axis
+    Iv live[ROI_MAX_DOWN_LAYERS] = {};
+    Mask low[ROI_MAX_DOWN_LAYERS];          // stored tensors of the shared levels: what the patch computes of its lower half whatever it shares itself
+    Iv share[ROI_MAX_DOWN_LAYERS] = {};
+    Mask comp[ROI_MAX_DOWN_LAYERS], sfill[ROI_MAX_DOWN_LAYERS];
+    unsigned long long tiles[ROI_MAX_DOWN_LAYERS] = {};     // ~0 where the key shares nothing at the level
+};
+
+void inner_axis(int ws, int n_down, Iv *in)
+{
+    const int L = 6 * n_down;
+    in[L + 3] = in[L + 2] = Iv{0, ws};
+    in[L + 1] = tap_fwd_all(in[L + 2], TAP_S2, ws / 2);
+    in[L] = tap_fwd_all(in[L + 1], TAP_EVEN, ws / 4);
+    Iv prev = in[L + 1];
+    for (int b = 0; b < n_down; b++) {
+        const int H = (ws / 2) >> b, Ho = H / 2;
+        Iv *q = in + 6 * b;
+        q[0] = tap_fwd_all(prev, TAP_DW, H);
+        q[1] = tap_fwd_all(q[0], TAP_PW, H);
+        q[2] = tap_fwd_all(q[1], TAP_DW, H);
+        q[3] = tap_fwd_all(q[2], TAP_PW, H);
+        q[4] = tap_fwd_all(prev, TAP_EVEN, Ho);
+        q[5] = meet(tap_fwd_all(q[3], TAP_S2, Ho), tap_fwd_all(q[4], TAP_PW, Ho));
+        prev = q[5];
+    }
+}
+
+bool in_iv(Iv v, int i) { return i >= v.lo && i < v.hi; }
+
+}  // namespace
+
+void roi_plan_share(RoiPlan &p)
+{
+    RoiDownPlan &d = p.down;
+    d.share_any = false;
+    d.comp.clear(); d.share_fill.clear(); d.nbr.clear();
+    if (d.n_down <= 0 || p.n_classes <= 0) return;
+    const int ws = p.ws, n_down = d.n_down, NL = d.n_layers;
+    const TileGeom g = make_geom(p.hh, p.ww, ws);
+    if (g.tiles_per_img != p.tiles_per_img) return;
+    // the ring: the same on both axes and for every class
+    Iv inner[ROI_MAX_DOWN_LAYERS];
+    inner_axis(ws, n_down, inner);
+    for (int l = 0; l < NL; l++)
+        for (int k = 0; k < p.n_classes; k++) d.inner[l][k] = rect_of(inner[l], inner[l]);
+    // the axis keys, their successors and the neighbour map
+    std::vector<AxisKey> keys;
+    auto key_of = [&](Iv rd) -> int {
+        for (int i = 0; i < (int)keys.size(); i++) if (keys[i].rd.lo == rd.lo && keys[i].rd.hi == rd.hi) return i;
+        keys.emplace_back();
+        keys.back().rd = rd;
+        return (int)keys.size() - 1;
+    };
+    int krow[ROI_MAX_CLASSES], kcol[ROI_MAX_CLASSES];
+    for (int k = 0; k < p.n_classes; k++) {
+        const RoiRect &rd = p.read[k];
+        krow[k] = key_of(Iv{rd.y0, rd.y0 + rd.rh});
+        kcol[k] = key_of(Iv{rd.x0, rd.x0 + rd.rw});
+    }
+    d.nbr.assign((size_t)p.tiles_per_img * 3, -1);
+    auto follow = [&](int key, int nxt) {
+        if (nxt < 0) { keys[key].last = true; return; }
+        if (std::find(keys[key].next.begin(), keys[key].next.end(), nxt) == keys[key].next.end()) keys[key].next.push_back(nxt);
+    };
+    for (int o = 0; o < 8; o++) {
+        const int na = g.na[o & 1], nb = g.nb[o & 1];
+        for (int a = 0; a < na; a++)
+            for (int b = 0; b < nb; b++) {
+                const int t = g.tile_off[o] + a * nb + b;
+                const int tr = b + 1 < nb ? t + 1 : -1, tb = a + 1 < na ? t + nb : -1;
+                d.nbr[3 * t] = tr; d.nbr[3 * t + 1] = tb; d.nbr[3 * t + 2] = (tr >= 0 && tb >= 0) ? t + nb + 1 : -1;
+                follow(kcol[p.tile_class[t]], tr >= 0 ? kcol[p.tile_class[tr]] : -1);
+                follow(krow[p.tile_class[t]], tb >= 0 ? krow[p.tile_class[tb]] : -1);
+            }
+    }
+    // every key's live, and what it computes of its lower half whatever it shares itself
+    const int L = 6 * n_down, R0 = ws >> p.n_up;
+    for (AxisKey &key : keys) {
+        if (empty(key.rd)) continue;
+        Iv ur[ROI_MAX_LAYERS], uc[ROI_MAX_LAYERS], need[ROI_MAX_DOWN_LAYERS], rect[ROI_MAX_DOWN_LAYERS], nc[ROI_MAX_DOWN_LAYERS];
+        Iv rl[ROI_MAX_DOWN_LAYERS], reads[ROI_MAX_DOWN_LAYERS];
+        walk_back(key.rd, key.rd, ws, p.n_up, ur, uc, true);
+        walk_down_axis(hull(ur[1], dilate(ur[0], 1, R0)), false, ws, n_down, d.fused_mask, need, rect);
+        need[L + 3] = rect[L + 3] = key.rd;
+        walk_const_axis(key.rd, false, ws, n_down, d.fused_mask, need, rect, nc, key.live, rl, reads);
+    }
+    auto shared_level = [&](int b) { return ((d.fused_mask & ROI_SHARE_LEVELS) >> b) & 1u; };
+    for (AxisKey &key : keys)
+        for (int b = 0; b < n_down; b++) {
+            if (!shared_level(b)) continue;
+            const int H = (ws / 2) >> b, Ho = H / 2;
+            key.low[6 * b + 5] = mask_of(meet(key.live[6 * b + 5], Iv{0, Ho / 2}), Ho);
+            const Mask t1 = taps_of(taps_of(key.low[6 * b + 5], TAP_S2, H), TAP_DW, H);
+            Mask &lo1 = key.low[6 * b + 1];
+            lo1.assign(H, 0);
+            for (int v = 0; v < H / 2; v++) lo1[v] = t1[v] && in_iv(key.live[6 * b + 1], v);
+        }
+    // share, comp and the tiles of every key
+    for (AxisKey &key : keys) {
+        for (int l = 0; l < NL; l++) { key.comp[l] = mask_of(key.live[l], d.res[l]); key.sfill[l].assign(d.res[l], 0); key.tiles[l] = ~0ull; }
+        if (key.last || key.next.empty() || empty(key.rd)) continue;
+        for (int b = 0; b < n_down; b++) {
+            if (!shared_level(b) || ((ws / 2) >> b) / 16 > 64) continue;
+            const int H = (ws / 2) >> b, Ho = H / 2;
+            // v of tensor l (side R) is shared when it is live and inner here, and v - R / 2 inner and computed in every successor
+            auto zone = [&](int l, int R) {
+                Mask m(R, 0);
+                for (int v = R / 2; v < R; v++) {
+                    bool ok = in_iv(key.live[l], v) && in_iv(inner[l], v) && in_iv(inner[l], v - R / 2);
+                    for (size_t i = 0; ok && i < key.next.size(); i++) {
+                        const Mask &lw = keys[key.next[i]].low[l];
+                        ok = !lw.empty() && lw[v - R / 2];
+                    }
+                    m[v] = ok;
+                }
+                return longest_run(m);
+            };
+            const int l0 = 6 * b;
+            key.share[l0 + 5] = zone(l0 + 5, Ho);
+            key.share[l0 + 1] = zone(l0 + 1, H);
+            if (empty(key.share[l0 + 5]) && empty(key.share[l0 + 1])) continue;
+            Mask &c5 = key.comp[l0 + 5];
+            for (int v = key.share[l0 + 5].lo; v < key.share[l0 + 5].hi; v++) c5[v] = 0;
+            key.sfill[l0 + 5] = mask_of(key.share[l0 + 5], Ho);
+            key.comp[l0 + 3] = key.comp[l0 + 2] = taps_of(c5, TAP_S2, H);
+            const Mask t1 = taps_of(key.comp[l0 + 2], TAP_DW, H);
+            Mask &c1 = key.comp[l0 + 1], &s1 = key.sfill[l0 + 1];
+            for (int v = 0; v < H; v++) {
+                const bool sh = in_iv(key.share[l0 + 1], v);
+                c1[v] = t1[v] && in_iv(key.live[l0 + 1], v) && !sh;
+                s1[v] = t1[v] && sh;
+            }
+            key.tiles[l0 + 3] = tiles_touching(key.comp[l0 + 3]);
+            key.tiles[l0 + 1] = tiles_touching(c1);
+            // a tapped shared pixel inside a tile that runs anyway is computed there, from the block's input, which is held whole: no copy
+            for (int v = 0; v < H; v++)
+                if (s1[v] && ((key.tiles[l0 + 1] >> (v / 16)) & 1ull)) { s1[v] = 0; c1[v] = 1; }
+            key.comp[l0] = c1;
+        }
+    }
+    // the classes: products of their two keys' sets
+    d.comp.assign((size_t)NL * ROI_MAX_CLASSES * 2 * ws, 0);
+    for (int k = 0; k < p.n_classes; k++) {
+        const AxisKey &kr = keys[krow[k]], &kc = keys[kcol[k]];
+        const bool live_cls = p.class_count[k] > 0 && p.read[k].rh > 0 && p.read[k].rw > 0;
+        for (int l = 0; l < NL; l++) {
+            int *sh = d.share[l][k];
+            sh[0] = sh[1] = sh[2] = sh[3] = 0;
+            d.tile_rows[l][k] = d.tile_cols[l][k] = ~0ull;
+            if (!live_cls) continue;
+            sh[0] = kr.share[l].lo; sh[1] = kr.share[l].hi; sh[2] = kc.share[l].lo; sh[3] = kc.share[l].hi;
+            d.tile_rows[l][k] = kr.tiles[l]; d.tile_cols[l][k] = kc.tiles[l];
+            unsigned char *cm = d.comp.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * ws;
+            std::copy(kr.comp[l].begin(), kr.comp[l].end(), cm);
+            std::copy(kc.comp[l].begin(), kc.comp[l].end(), cm + ws);
+            if (!any(kr.sfill[l]) && !any(kc.sfill[l])) continue;
+            d.share_any = true;
+            const std::vector<Iv> rc = runs_of(kr.comp[l]), rs = runs_of(kr.sfill[l]), cc = runs_of(kc.comp[l]), cs = runs_of(kc.sfill[l]);
+            auto put = [&](int dir, const std::vector<Iv> &rows, const std::vector<Iv> &cols) {
+                for (const Iv &r : rows)
+                    for (const Iv &c : cols) d.share_fill.push_back(RoiDownPlan::ShareFill{l, k, dir, r.lo, c.lo, r.hi - r.lo, c.hi - c.lo});
+            };
+            put(0, rc, cs); put(1, rs, cc); put(2, rs, cs);
+        }
+    }
+}
+
+void roi_share_neighbours(const RoiPlan &p, int k, std::vector<int> &out)
+{
+    const int T = p.tiles_per_img;
+    out.assign((size_t)std::max(k, 0) * T * 3, -1);
+    if ((int)p.down.nbr.size() != 3 * T) return;
+    auto pos = [&](int img, int t) { const int c = p.tile_class[t]; return k * p.class_base[c] + img * p.class_count[c] + p.tile_rank[t]; };
+    for (int img = 0; img < k; img++)
+        for (int t = 0; t < T; t++)
+            for (int j = 0; j < 3; j++)
+                if (p.down.nbr[3 * t + j] >= 0) out[(size_t)3 * pos(img, t) + j] = pos(img, p.down.nbr[3 * t + j]);
+}
+
+long long roi_sep_tile_table_share(const RoiPlan &p, int layer, int k, std::vector<int> &out)
+{
+    const RoiDownPlan &d = p.down;
+    if (!d.share_any) return roi_sep_tile_table_live(p, layer, k, out);
+    out.clear();
+    const int b = layer / 6, kk = layer % 6;
+    if (k < 1 || layer < 0 || b >= d.n_down || (kk != 1 && kk != 3) || !((d.fused_mask >> b) & 1u)) return 0;
+    const int TW = d.res[layer] / 16, TPP = TW * TW;
+    const long long full = (long long)k * p.tiles_per_img * TPP;
+    if (full > 0x7fffffffLL || TW > 64) return 0;
+    for (int cl = 0; cl < p.n_classes; cl++) {
+        const RoiRect &q = d.rect_live[layer][cl];
+        const int ty0 = q.y0 / 16, ty1 = (q.y0 + q.rh) / 16, tx0 = q.x0 / 16, tx1 = (q.x0 + q.rw) / 16;
+        for (int pt = k * p.class_base[cl]; pt < k * p.class_base[cl + 1]; pt++)
+            for (int ty = ty0; ty < ty1; ty++) {
+                if (!((d.tile_rows[layer][cl] >> ty) & 1ull)) continue;
+                for (int tx = tx0; tx < tx1; tx++)
+                    if ((d.tile_cols[layer][cl] >> tx) & 1ull) out.push_back(pt * TPP + ty * TW + tx);
+            }
     }
     return full;
 }
@@ -497,7 +756,7 @@ extern "C" int tmat_roi_plan_down(int hh, int ww, int patch, int n_up, const int
 
 // The tile table of a fused separable layer of the same plan for a pass of k images (roi_sep_tile_table): *n_full the full-frame tile
 // count, *n_tiles the planned one; tiles (nullable: counts only) takes the planned tiles' full-frame ids, cap its room.
-static int sep_tiles_export(bool live, int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+static int sep_tiles_export(int live, int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
                             unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
 {
     if (!up_channels || !down_channels || !n_tiles || !n_full || k < 1) { set_error("tmat_roi_sep_tiles: bad argument"); return TMAT_E_ARG; }
@@ -507,7 +766,7 @@ static int sep_tiles_export(bool live, int hh, int ww, int patch, int n_up, cons
         return TMAT_E_ARG;
     }
     std::vector<int> tab;
-    const long long full = live ? roi_sep_tile_table_live(p, layer, k, tab) : roi_sep_tile_table(p, layer, k, tab);
+    const long long full = live == 2 ? roi_sep_tile_table_share(p, layer, k, tab) : live ? roi_sep_tile_table_live(p, layer, k, tab) : roi_sep_tile_table(p, layer, k, tab);
     if (full <= 0) { set_error("tmat_roi_sep_tiles: not a fused separable layer of the plan"); return TMAT_E_ARG; }
     *n_full = (int)full;
     *n_tiles = (int)tab.size();
@@ -521,14 +780,14 @@ static int sep_tiles_export(bool live, int hh, int ww, int patch, int n_up, cons
 extern "C" int tmat_roi_sep_tiles(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
                                   unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
 {
-    return sep_tiles_export(false, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
+    return sep_tiles_export(0, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
 }
 
 // the same of the constant-ring form (roi_sep_tile_table_live): the tiles of rect_live, a subsequence of tmat_roi_sep_tiles' table
 extern "C" int tmat_roi_sep_tiles_live(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
                                        unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
 {
-    return sep_tiles_export(true, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
+    return sep_tiles_export(1, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
 }
 
 // The constant-ring tables of the same plan (RoiDownPlan::nonconst ...): nonconst, live and rect_live [6 n_down + 4][max_classes][4] as
@@ -562,5 +821,54 @@ extern "C" int tmat_roi_plan_const(int hh, int ww, int patch, int n_up, const in
         stored[l] = d.stored[l] ? 1 : 0;
         mac_live[l] = d.mac_live[l]; bytes_live[l] = d.bytes_live[l];
     }
+    return TMAT_OK;
+}
+
+// the same of the shared-interior form (roi_sep_tile_table_share): a subsequence of tmat_roi_sep_tiles_live's table, in its order
+extern "C" int tmat_roi_sep_tiles_share(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                        unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
+{
+    return sep_tiles_export(2, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
+}
+
+// The shared-interior tables of the same plan (RoiDownPlan::inner ...): inner [6 n_down + 4][max_classes][4] as (y0, x0, rows, columns),
+// share [6 n_down + 4][max_classes][4] as (row lo, row hi, column lo, column hi), comp [6 n_down + 4][max_classes][2 axes][patch] bytes,
+// fills [n_fill][7] as (layer, class, direction, y0, x0, rows, columns), neighbours [tiles_per_img][3] image-major tiles or -1.
+extern "C" int tmat_roi_plan_share(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                   unsigned fused_mask, int max_classes, int *n_classes, int *inner, int *share, unsigned char *comp,
+                                   int fill_cap, int *n_fill, int *fills, int tiles_cap, int *neighbours)
+{
+    if (!up_channels || !down_channels || !n_classes || !inner || !share || !comp || !n_fill || !fills || !neighbours || fill_cap < 0 ||
+        max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
+        set_error("tmat_roi_plan_share: bad argument");
+        return TMAT_E_ARG;
+    }
+    RoiPlan p;
+    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, max_classes, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
+        set_error("tmat_roi_plan_share: unsupported geometry");
+        return TMAT_E_ARG;
+    }
+    const RoiDownPlan &d = p.down;
+    if (p.tiles_per_img > tiles_cap || (int)d.nbr.size() != 3 * p.tiles_per_img) { set_error("tmat_roi_plan_share: tiles_cap too small"); return TMAT_E_ARG; }
+    *n_classes = p.n_classes;
+    for (int l = 0; l < d.n_layers; l++)
+        for (int k = 0; k < max_classes; k++) {
+            const bool in = k < p.n_classes;
+            const size_t at = ((size_t)l * max_classes + k) * 4;
+            const RoiRect q = in ? d.inner[l][k] : RoiRect{0, 0, 0, 0};
+            inner[at] = q.y0; inner[at + 1] = q.x0; inner[at + 2] = q.rh; inner[at + 3] = q.rw;
+            for (int i = 0; i < 4; i++) share[at + i] = in ? d.share[l][k][i] : 0;
+            unsigned char *o = comp + ((size_t)l * max_classes + k) * 2 * patch;
+            if (in && !d.comp.empty()) std::copy_n(d.comp.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * patch, 2 * patch, o);
+            else std::fill_n(o, 2 * patch, (unsigned char)0);
+        }
+    *n_fill = (int)d.share_fill.size();
+    if (*n_fill > fill_cap) { set_error("tmat_roi_plan_share: fill_cap too small"); return TMAT_E_ARG; }
+    for (int i = 0; i < *n_fill; i++) {
+        const RoiDownPlan::ShareFill &f = d.share_fill[i];
+        int *o = fills + (size_t)i * 7;
+        o[0] = f.layer; o[1] = f.cls; o[2] = f.dir; o[3] = f.y0; o[4] = f.x0; o[5] = f.rh; o[6] = f.rw;
+    }
+    std::copy(d.nbr.begin(), d.nbr.end(), neighbours);
     return TMAT_OK;
 }

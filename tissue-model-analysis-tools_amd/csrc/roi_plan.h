@@ -62,7 +62,39 @@ struct RoiDownPlan {
     RoiRect fill[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES][4] = {};
     bool stored[ROI_MAX_DOWN_LAYERS] = {};      // the layer's output is a tensor in memory that a region-form launch writes
     double mac_live[ROI_MAX_DOWN_LAYERS] = {}, bytes_live[ROI_MAX_DOWN_LAYERS] = {};       // mac_planned / bytes_planned of rect_live
+
+    // The SHARED-INTERIOR form (TMAT_ROI_SHARE), on top of the constant-ring form.  The patches of an orientation overlap by half a
+    // side: position v of a tensor of side H is position v - H / 2 of the next patch on that axis.  Both patches hold the same bits
+    // there unless the position's receptive field crosses either patch's border, where SAME pads zeros.  All sets are per AXIS and
+    // depend on the axis KEY only -- the interval of `read` on that axis -- so that patches in one row (column) of the grid agree on
+    // their row (column) sets; a class's 2-D set is the product.
+    // inner: the complement of the RING, the outputs whose receptive field, clipped to the patch, touches the patch border -- the
+    // forward walk from both borders through the taps of walk_const_axis (TAP_S2 pads at the far end only).
+    // share (rows [0..1], columns [2..3] as lo, hi): positions v in live and inner whose v - H / 2 is, in EVERY patch that follows a
+    // patch of this key on either axis anywhere, inner and computed by that patch itself; empty when some patch of the key has no
+    // successor.  Only the stored tensors of the fused levels in ROI_SHARE_LEVELS have one: the first layer's output (6 b + 1) and the
+    // pooled output (6 b + 5).
+    // comp ([layer][class][axis][ws] bytes, the first res[layer] used): the NEEDED pixels the patch computes itself -- live \ share for
+    // the pooled output, and backwards from there through the taps for the fused layers; live everywhere else (rectangle launches keep
+    // rect_live).  The fused layers run the tiles that hold a comp pixel (roi_sep_tile_table_share: tile_rows x tile_cols, bit t).
+    // share_fill: the pixels in share that a consumer's comp taps -- of 6 b + 1 the halo strips of the pooled layer's tiles, except
+    // where they lie in a tile of 6 b + 1 that runs anyway (they join comp: the block's input is held whole; at the network's sizes
+    // that is all of them), of 6 b + 5 all of share (the next level's rectangle launches read the tensor whole) -- as rectangles
+    // with a direction: copied from the
+    // right (0), lower (1) or diagonal (2) neighbour at (y, x - S), (y - S, x), (y - S, x - S).  Every source pixel is in its own
+    // patch's comp.  Every tap of a comp pixel lies in the producer's comp ∪ fill ∪ share_fill.
+    struct ShareFill { int layer, cls, dir, y0, x0, rh, rw; };
+    bool share_any = false;                     // some class shares: the form differs from the constant-ring form
+    RoiRect inner[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {};
+    int share[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES][4] = {};
+    unsigned long long tile_rows[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {}, tile_cols[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {};
+    std::vector<unsigned char> comp;
+    std::vector<ShareFill> share_fill;
+    std::vector<int> nbr;                       // [tiles_per_img][3]: the image-major tile right of, below and diagonally below a tile, or -1
 };
+
+// Fused levels (bit b) that take the shared-interior form: a level whose copies cost more than its skipped tiles save is taken out here
+constexpr unsigned ROI_SHARE_LEVELS = 3u;
 
 struct RoiPlan {
     int hh = 0, ww = 0, ws = 0, n_up = 0;
@@ -117,5 +149,12 @@ bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask)
 long long roi_sep_tile_table(const RoiPlan &p, int layer, int k, std::vector<int> &out);
 // the same of the constant-ring form: the tiles of RoiDownPlan::rect_live, a subsequence of the table above
 long long roi_sep_tile_table_live(const RoiPlan &p, int layer, int k, std::vector<int> &out);
+// the same of the shared-interior form: the tiles of RoiDownPlan::tile_rows x tile_cols, a subsequence of the live table in its order
+// (the live table itself where no class shares)
+long long roi_sep_tile_table_share(const RoiPlan &p, int layer, int k, std::vector<int> &out);
+// Fills the shared-interior tables of a plan with a down plan (called by roi_plan_down; p.down.share_any stays false where nothing is shared)
+void roi_plan_share(RoiPlan &p);
+// nbr in the class-major order of a pass of k images: [k tiles_per_img][3] positions, or -1
+void roi_share_neighbours(const RoiPlan &p, int k, std::vector<int> &out);
 
 }  // namespace tmat

@@ -305,13 +305,15 @@ static bool conv(Ctx *c, ConvArgs a, hipStream_t st, const RoiSegs *roi = nullpt
 // blocking copy into a fresh allocation, as for the patch order), never per pass.  dev stays null when every patch is computed whole.
 // Null + error set: the allocation or the copy failed.
 // live: the constant-ring form's table, then every tile of the k all-constant patches behind the pass's patches.
-static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, bool live)
+// share (with live): the shared-interior form's table
+static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, bool live, bool share = false)
 {
-    for (const RoiTileTab &t : e->tabs) if (t.layer == layer && t.k == k && t.live == live) return &t;
+    share = share && live;
+    for (const RoiTileTab &t : e->tabs) if (t.layer == layer && t.k == k && t.live == live && t.share == share) return &t;
     std::vector<int> ids;
     RoiTileTab t;
-    t.layer = layer; t.k = k; t.live = live;
-    t.full = live ? roi_sep_tile_table_live(e->plan, layer, k, ids) : roi_sep_tile_table(e->plan, layer, k, ids);
+    t.layer = layer; t.k = k; t.live = live; t.share = share;
+    t.full = share ? roi_sep_tile_table_share(e->plan, layer, k, ids) : live ? roi_sep_tile_table_live(e->plan, layer, k, ids) : roi_sep_tile_table(e->plan, layer, k, ids);
     t.n_rep = (long long)ids.size(); t.full_rep = t.full;
     if (t.full <= 0 || ids.empty()) { set_error("roi_tile_tab: no tile table for this layer"); return nullptr; }
     if (live) {
@@ -327,6 +329,36 @@ static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, bool live)
     }
     e->tabs.push_back(t);
     return &e->tabs.back();
+}
+
+// The copies of the shared-interior form for passes of k images, cached on the plan's entry like the tile tables: the neighbour table and
+// every stored tensor's items, built and uploaded on first use, never per pass.  Null + error set: an allocation or a copy failed.
+static const RoiShareTab *roi_share_tab(RoiEntry *e, int k)
+{
+    for (const RoiShareTab &t : e->shares) if (t.k == k) return &t;
+    const RoiPlan &p = e->plan;
+    RoiShareTab t;
+    t.k = k;
+    roi_share_neighbours(p, k, t.nbr);
+    for (const RoiDownPlan::ShareFill &f : p.down.share_fill) {
+        RoiShareTab::Layer *sl = nullptr;
+        for (RoiShareTab::Layer &l : t.layers) if (l.layer == f.layer) sl = &l;
+        if (!sl) { t.layers.emplace_back(); sl = &t.layers.back(); sl->layer = f.layer; }
+        sl->items.push_back(ShareItem{k * p.class_base[f.cls], k * p.class_count[f.cls], f.dir, f.y0, f.x0, f.rh, f.rw});
+    }
+    auto up = [](const void *src, size_t bytes, void **dev) {
+        return bytes == 0 || (hip_ok(hipMalloc(dev, bytes), "hipMalloc(share table)") &&
+                              hip_ok(hipMemcpy(*dev, src, bytes, hipMemcpyHostToDevice), "hipMemcpy(share table)"));
+    };
+    bool ok = up(t.nbr.data(), t.nbr.size() * sizeof(int), (void **)&t.nbr_dev);
+    for (RoiShareTab::Layer &l : t.layers) ok = ok && up(l.items.data(), l.items.size() * sizeof(ShareItem), (void **)&l.dev);
+    if (!ok) {
+        if (t.nbr_dev) hipFree(t.nbr_dev);
+        for (RoiShareTab::Layer &l : t.layers) if (l.dev) hipFree(l.dev);
+        return nullptr;
+    }
+    e->shares.push_back(t);
+    return &e->shares.back();
 }
 
 // does down block bi (input resolution P / 2 >> bi) run on the wave-specialised fused separable kernel?
@@ -360,7 +392,9 @@ static RoiSegs roi_segs(const RoiPlan &p, int l, int k) { return roi_segs_of(p, 
 // padval (nullable): the constant-ring form (tmat_ctx.h:Ctx::roi_const) -- the k all-constant patches of the pass are written behind X's
 // n patches and run through the same launches as one more segment of whole patches; the launches of the pass's own patches take
 // rect_live, and after each launch that writes a stored tensor the strips of RoiDownPlan::fill are copied out of the constant patches
-int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval)
+// share: the shared-interior form on top of it (tmat_ctx.h:Ctx::roi_share) -- the fused separable layers take the share tile table, and
+// each constant fill of a stored tensor of a fused level is followed by the copies out of the neighbour patches (RoiDownPlan::share_fill)
+int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval, bool share)
 {
     if (n <= 0) return TMAT_OK;
     if (n > c->max_patches) { set_error("unet_down_dev: n > max_patches"); return TMAT_E_ARG; }
@@ -407,12 +441,23 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
         for (RoiEntry *e : c->roi_cache) if (&e->plan == plan) ent = e;
     c->sep_tiles.clear();
     bool tab_ok = true;
+    // the shared-interior form: with the constant-ring form and the tile tables only, and where the plan shares anything
+    const RoiShareTab *shr = nullptr;
+    if (share && cst && ent && plan->down.share_any && !(shr = roi_share_tab(ent, kimg))) return TMAT_E_HIP;
+    // the copies of layer l's tensor t out of the neighbour patches: behind its constant fill, before its first reader
+    auto share_fill = [&](float *t, int l, int C) -> bool {
+        if (!shr) return true;
+        for (const RoiShareTab::Layer &sl : shr->layers)
+            if (sl.layer == l && !launch_share_fill(t, n_own, plan->down.res[l], C, shr->nbr.data(), shr->nbr_dev, sl.items.data(), sl.dev, (int)sl.items.size(), s))
+                return false;
+        return true;
+    };
     auto tiles = [&](size_t bi, int k, int H, bool f32) -> RoiTileTab {
         RoiTileTab t;
         t.full = t.n = n * (H / 16) * (H / 16);
         t.full_rep = t.n_rep = (long long)n_own * (H / 16) * (H / 16);
         if (ent && f32) {
-            if (const RoiTileTab *made = roi_tile_tab(ent, 6 * (int)bi + k, kimg, cst)) t = *made;
+            if (const RoiTileTab *made = roi_tile_tab(ent, 6 * (int)bi + k, kimg, cst, shr != nullptr)) t = *made;
             else tab_ok = false;
         }
         c->sep_tiles.push_back({t.dev ? t.n_rep : t.full_rep, t.full_rep});       // (the constant patches' whole tiles are not counted)
@@ -452,7 +497,7 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
                 if (!launch_sepconv_ws_stem(X, n, H, H, d.cin, c->stem_w, c->stem_scale, c->stem_shift, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s,
                                             t0.dev, t0.n)) return TMAT_E_ARG;
             } else if (!launch_sepconv_ws(b0, n, H, H, d.cin, bi > 0, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s, sprec, t0.dev, t0.n)) return TMAT_E_ARG;
-            if (!fill(b2, 6 * (int)bi + 1, d.cout)) return TMAT_E_ARG;
+            if (!fill(b2, 6 * (int)bi + 1, d.cout) || !share_fill(b2, 6 * (int)bi + 1, d.cout)) return TMAT_E_ARG;
             ConvArgs r{};
             r.in = b0; r.N = n; r.h = H; r.w = H; r.Cin = d.cin; r.ksize = 1; r.stride = 2; r.W = d.res_w; r.Cout = d.cout;
             r.scale = nullptr; r.shift = d.res_b; r.out = b1;
@@ -468,7 +513,8 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
                 if (!launch_sepconv_ws(b2, n, H, H, d.cout, 0, d.dw[1], pw1, d.cout, d.scale[1], d.shift[1], 0, b3, s, sprec, t1.dev, t1.n)) return TMAT_E_ARG;
                 launch_maxpool_add(b3, n, H, H, d.cout, b1, nxt, s, nullptr, segs(bi, 5));
             }
-            if (!fill(nxt, 6 * (int)bi + 5, d.cout)) return TMAT_E_ARG;
+            // (the fix-up pass may have written junk into pooled pixels of skipped tiles: the copies overwrite every one a consumer reads)
+            if (!fill(nxt, 6 * (int)bi + 5, d.cout) || !share_fill(nxt, 6 * (int)bi + 5, d.cout)) return TMAT_E_ARG;
             H /= 2;
             continue;
         }
@@ -644,7 +690,8 @@ int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred
         launch_minmax_f32(xi, k, (size_t)hh * ww, mn, mx, c->stream);
         launch_extract_tiles(xi, mn, k, g, c->patch_in, c->stream);
         // (the constant-ring form only on request: the default launches of this entry point are pinned to the dependency plan's tiles)
-        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan, c->roi_const == 1 ? mn : nullptr)
+        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan, c->roi_const == 1 ? mn : nullptr,
+                                      c->roi_share == 1)
                       : unet_forward_dev(c, c->patch_in, k * g.tiles_per_img, c->patch_out, c->stream);
         if (!rc && plan) rc = unet_up_dev(c, c->dout[0], k * g.tiles_per_img, c->patch_out, c->stream, plan);
         if (rc) return rc;
@@ -721,6 +768,10 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     if (const char *e = getenv("TMAT_ROI_CONST")) {
         if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_CONST must be 0 or 1"); delete c; return TMAT_E_ARG; }
         c->roi_const = atoi(e);
+    }
+    if (const char *e = getenv("TMAT_ROI_SHARE")) {
+        if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_SHARE must be 0 or 1"); delete c; return TMAT_E_ARG; }
+        c->roi_share = atoi(e);
     }
     // room for the all-constant patches of a pass behind its patches (tmat_ctx.h): the down-path workspaces and the input buffers only
     c->const_cap = c->roi_const == 0 ? 0 : std::max(4, c->max_patches / 64);

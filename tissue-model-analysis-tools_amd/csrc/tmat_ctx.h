@@ -28,12 +28,33 @@ struct ProfEv { hipEvent_t e0, e1; double flops; };
 // stays full-frame) holds n ids; a constant like `order` -- uploaded once, outside the workspaces tmat_debug_poison fills
 // live: the table of the constant-ring form (roi_sep_tile_table_live) followed by every tile of the pass's k all-constant patches, which
 // sit behind its patches; n_rep of full_rep: the planner's own counts, without those (what tmat_debug_sep_tiles reports)
-struct RoiTileTab { int layer = 0, k = 0, n = 0; long long full = 0; int *dev = nullptr; bool live = false; long long n_rep = 0, full_rep = 0; };
+// share (with live): the shared-interior form's table (roi_sep_tile_table_share) in place of the constant-ring form's
+struct RoiTileTab { int layer = 0, k = 0, n = 0; long long full = 0; int *dev = nullptr; bool live = false; long long n_rep = 0, full_rep = 0; bool share = false; };
+// the copies of the shared-interior form for passes of k images: the neighbour table in the pass's class-major order and, per stored
+// tensor (layer), the items of RoiDownPlan::share_fill with their classes' patch ranges -- host copies for the launcher's checks,
+// device copies (uploaded once, like the tile tables) for the kernel
+struct RoiShareTab {
+    int k = 0;
+    std::vector<int> nbr;
+    int *nbr_dev = nullptr;
+    struct Layer { int layer = 0; std::vector<ShareItem> items; ShareItem *dev = nullptr; };
+    std::vector<Layer> layers;
+};
 struct RoiEntry {
     RoiPlan plan;
     int4 *order = nullptr;                  // device, [tiles_per_img] (TileGeom::order)
     std::vector<RoiTileTab> tabs;           // made on first use; released when the handle moves to another geometry, and by tmat_destroy
-    void free_tabs() { for (RoiTileTab &t : tabs) if (t.dev) hipFree(t.dev); tabs.clear(); }
+    std::vector<RoiShareTab> shares;        // likewise
+    void free_tabs()
+    {
+        for (RoiTileTab &t : tabs) if (t.dev) hipFree(t.dev);
+        tabs.clear();
+        for (RoiShareTab &t : shares) {
+            if (t.nbr_dev) hipFree(t.nbr_dev);
+            for (RoiShareTab::Layer &l : t.layers) if (l.dev) hipFree(l.dev);
+        }
+        shares.clear();
+    }
 };
 struct ConvWHost { std::vector<float> w; int cin; };        // host copy of an MFMA convolution's weights ([rows][cin])
 
@@ -210,6 +231,11 @@ struct Ctx {
     // than max_patches, and a pass of more images (fewer than 64 patches per image at the default size) keeps the dependency plan.
     int roi_const = -1;
     int const_cap = 0;
+    // TMAT_ROI_SHARE: the shared-interior form on top of the constant-ring form (roi_plan.h:RoiDownPlan::share): what a patch's
+    // successor on an axis computes of their overlap is copied, not computed again; the fused separable layers skip the tiles that
+    // leaves without a needed pixel.  -1 (unset): the batch pipeline runs it, predict_smooth does not; 0: nobody; 1: both.  Only where
+    // the constant-ring form runs, and only with the tile tables (TMAT_ROI_DOWN bit 1).
+    int roi_share = -1;
     float *padval[2] = {nullptr, nullptr};                   // the pad values of a pipeline pass, per slot: c->scratch is rewritten by the front end of the pass after next
     std::vector<RoiEntry *> roi_cache;
     std::vector<std::pair<long long, long long>> sep_tiles;  // (planned, full) tiles of the fused separable launches of the last down pass (tmat_debug_sep_tiles)
@@ -231,7 +257,8 @@ int unet_forward_dev(Ctx *c, const float *X, int n, float *Y, hipStream_t s);
 int ensure_patch_io(Ctx *c, int n_patches);
 // padval (nullable, with a plan only): the pad values of the pass's images on the device -- the constant-ring form, where the handle and
 // the pass allow it.  X then has room for n + n / tiles_per_img patches (patch_in and patch_in2 do): the all-constant patches are written there
-int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan = nullptr, const float *padval = nullptr);
+int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan = nullptr, const float *padval = nullptr,
+                  bool share = false);
 // plan (nullable): region form; n is then a whole number of images' patches in the plan's class-major order
 int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s, const RoiPlan *plan = nullptr);
 // the region plan of g's geometry (cached on the handle) and, in g.order, its patch order; null and the image-major order when the region

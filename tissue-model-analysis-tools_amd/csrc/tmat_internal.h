@@ -120,6 +120,16 @@ struct FillItem { int p0, np, cnt, y0, x0, rh, rw; };
 struct FillItems { int n; FillItem it[64]; };
 // t (N, H, H, C), C % 4 == 0; false (and the error set) when an item leaves the tensor
 bool launch_const_fill(float *t, int src0, int N, int H, int C, const FillItems &f, hipStream_t s);
+// ---- shared-interior form (roi_plan.h:RoiDownPlan::share_fill) ----
+// one rectangle of one class: the patches [p0, p0 + np) take the pixels [y0, y0 + rh) x [x0, x0 + rw), all channels, from their
+// neighbour nbr[3 patch + dir] (dir 0 right, 1 below, 2 diagonal) at (y, x - H / 2), (y - H / 2, x), (y - H / 2, x - H / 2)
+struct ShareItem { int p0, np, dir, y0, x0, rh, rw; };
+// the launcher's host-side checks: false (and the error set) for an item that leaves its tensor, a source patch out of range, or a
+// source rectangle that overlaps a destination rectangle of the patch it is read from
+bool share_fill_check(int N, int H, int C, const int *nbr, const ShareItem *it, int n);
+// t (N, H, H, C), C % 4 == 0; the neighbour table [N][3] and the n items on the host (checked) and on the device (read by the kernel)
+bool launch_share_fill(float *t, int N, int H, int C, const int *nbr_host, const int *nbr_dev, const ShareItem *it_host, const ShareItem *it_dev, int n,
+                       hipStream_t s);
 // out (k, pp): patch i filled with padval[i]; pp % 4 == 0
 void launch_const_patches(const float *padval, int k, int pp, float *out, hipStream_t s);
 

@@ -152,7 +152,7 @@ EXPORTS = [
     "tmat_analyze_stack", "tmat_field_stats", "tmat_field_stats_pruned", "tmat_resize_aa_u16", "tmat_cell_area_batch", "tmat_cell_area_masked", "tmat_resize_linear_u16",
     "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi", "tmat_resnet_set_precision", "tmat_conv2d",
     "tmat_roi_plan", "tmat_roi_plan_tight", "tmat_roi_plan_exact", "tmat_conv2d_roi", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles",
-    "tmat_roi_plan_const", "tmat_roi_sep_tiles_live",
+    "tmat_roi_plan_const", "tmat_roi_sep_tiles_live", "tmat_roi_plan_share", "tmat_roi_sep_tiles_share", "tmat_debug_share_fill_check",
     "tmat_stage_pictures", "tmat_host_stage_pictures", "tmat_analyze_batch_ex", "tmat_analyze_batch_ex_dev",
 ]
 
@@ -606,6 +606,46 @@ def roi_plan_const(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), down_ch
 def roi_sep_tiles_live(hh, ww, layer, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
     """tmat_roi_sep_tiles_live (include/tmat.h): roi_sep_tiles for the constant-ring form's rectangles (rect_live)."""
     return roi_sep_tiles(hh, ww, layer, k, patch, channels, down_channels, fused_mask, _export="tmat_roi_sep_tiles_live")
+
+
+def roi_plan_share(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3, max_classes=16):
+    """tmat_roi_plan_share (include/tmat.h): the shared-interior tables of roi_plan_down's plan; host arithmetic, no GPU.
+    Returns a dict: n_classes, inner [6 n_down + 4][max_classes][4] (y0, x0, rows, columns), share [6 n_down + 4][max_classes][4]
+    (row lo, row hi, column lo, column hi), comp [6 n_down + 4][max_classes][2][patch] uint8, fills [n][7] (layer, class, direction,
+    y0, x0, rows, columns), neighbours [tiles_per_img][3]."""
+    L = lib()
+    L.tmat_roi_plan_share.argtypes = ([C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint, C.c_int] + [C.c_void_p] * 4 +
+                                      [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p])
+    n_up, n_down = len(channels) - 1, len(down_channels) - 1
+    ch, dch = np.asarray(channels, np.int32), np.asarray(down_channels, np.int32)
+    nl = 6 * n_down + 4
+    aug = (patch + 1) // 2
+    tiles = 8 * ((hh + 2 * aug - patch) // (patch // 2) + 1) * ((ww + 2 * aug - patch) // (patch // 2) + 1)
+    ncls, nfill = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    inner, share = np.zeros((nl, max_classes, 4), np.int32), np.zeros((nl, max_classes, 4), np.int32)
+    comp = np.zeros((nl, max_classes, 2, patch), np.uint8)
+    cap = nl * max_classes * 12
+    fills = np.zeros((cap, 7), np.int32)
+    nbr = np.zeros((tiles, 3), np.int32)
+    check(L.tmat_roi_plan_share(hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), max_classes, ptr(ncls), ptr(inner), ptr(share),
+                                ptr(comp), cap, ptr(nfill), ptr(fills), tiles, ptr(nbr)), "roi_plan_share")
+    return dict(n_classes=int(ncls[0]), inner=inner, share=share, comp=comp, fills=fills[:int(nfill[0])], neighbours=nbr)
+
+
+def roi_sep_tiles_share(hh, ww, layer, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
+    """tmat_roi_sep_tiles_share (include/tmat.h): roi_sep_tiles for the shared-interior form (the tiles that hold a comp pixel)."""
+    return roi_sep_tiles(hh, ww, layer, k, patch, channels, down_channels, fused_mask, _export="tmat_roi_sep_tiles_share")
+
+
+def debug_share_fill_check(n_patches, side, channels, neighbours, items):
+    """tmat_debug_share_fill_check (include/tmat.h): None when the share-fill launcher would take the table, its refusal otherwise.
+    Host-side checks only, nothing is launched."""
+    L = lib()
+    L.tmat_debug_share_fill_check.argtypes = [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p]
+    nb = np.ascontiguousarray(neighbours, np.int32).reshape(-1, 3)
+    it = np.ascontiguousarray(items, np.int32).reshape(-1, 7)
+    rc = L.tmat_debug_share_fill_check(int(n_patches), int(side), int(channels), ptr(nb), len(it), ptr(it))
+    return None if rc == 0 else L.tmat_last_error().decode()
 
 
 def roi_sep_tiles(hh, ww, layer, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3,
