@@ -292,6 +292,34 @@ int tmat_host_render_barcode(const double *bars, int n, int vis_width, uint8_t *
 int tmat_stage_pictures(tmat_handle h, const void *a, int dtype, int n, size_t per, uint8_t *out);
 int tmat_host_stage_pictures(const void *a, int dtype, int n, size_t per, uint8_t *out);
 
+/*
+ * PNG files made on the device (csrc/png_kernels.hip), for the pictures above: n pictures of one shape (H, W) with
+ * `channels` = 1 (grey, colour type 0) or 3 (RGB, colour type 2), u8, contiguous -> n complete files: signature, IHDR, IDAT chunks,
+ * IEND; bit depth 8, no interlace, no ancillary chunk.  One filter type per row out of None / Sub / Up / Average / Paeth by the
+ * minimum sum of absolute signed residuals (ties: the lowest type); the filtered stream cut into stripes of tmat_png_stripe bytes,
+ * each compressed on its own (LZ77 inside the stripe, one fixed-Huffman or stored block, whichever is smaller) into its own IDAT
+ * chunk, so that the chunks concatenate into one zlib stream.  The bytes of a file depend on the picture and (H, W, channels) only.
+ * File i occupies out + i * cap_each for sizes[i] bytes; out and sizes are host pointers, bytes past sizes[i] are not written.
+ * cap_each below the bound of tmat_png_bound: TMAT_E_CAP, nothing written.  H or W < 1, channels outside {1, 3}, or a filtered
+ * stream H (W channels + 1) of 2^31 bytes or more: TMAT_E_ARG.  n == 0 succeeds.  A handle from tmat_create_plain is enough; device
+ * memory comes from the handle's pool on first use.
+ * tmat_png_encode_batch takes host pictures, tmat_png_encode_batch_dev device pictures, tmat_host_png_encode_batch is the host twin:
+ * the same bytes, no handle, no GPU.  tmat_png_encode_batch_timed is tmat_png_encode_batch that also reports ms3 = HIP-event
+ * milliseconds on the handle's stream of {upload, kernels, copy back of sizes and files} (tools/bench_png.py).
+ * tmat_render_tree_png takes the arguments of tmat_render_tree and returns the overlays as PNG files: render and encoder run back to
+ * back on the handle's stream and the raw (n, vh, vw, 3) overlays stay on the device; its bound is tmat_png_bound of (vh, vw, 3).
+ */
+int tmat_png_stripe(void);
+int tmat_png_bound(int H, int W, int channels, size_t *bound);
+int tmat_png_encode_batch(tmat_handle h, const uint8_t *pics, int n, int H, int W, int channels, uint8_t *out, size_t cap_each, size_t *sizes);
+int tmat_png_encode_batch_dev(tmat_handle h, const uint8_t *pics_dev, int n, int H, int W, int channels, uint8_t *out, size_t cap_each,
+                              size_t *sizes);
+int tmat_png_encode_batch_timed(tmat_handle h, const uint8_t *pics, int n, int H, int W, int channels, uint8_t *out, size_t cap_each,
+                                size_t *sizes, float *ms3);
+int tmat_host_png_encode_batch(const uint8_t *pics, int n, int H, int W, int channels, uint8_t *out, size_t cap_each, size_t *sizes);
+int tmat_render_tree_png(tmat_handle h, const void *background, int bg_dtype, int n, int bh, int bw, const double *segs,
+                         const int32_t *seg_branch, const int32_t *seg_offsets, int vis_width, uint8_t *out, size_t cap_each, size_t *sizes);
+
 /* One result row per image, the payload gathered across ranks. */
 typedef struct tmat_row {
     int64_t index;   /* image index in the run                      */

@@ -3,6 +3,7 @@
 // C-ABI entry that runs the rasteriser on the device.  Host twin and kernel share every formula through overlay.h.
 #include "../../include/tmat.h"
 #include "overlay.h"
+#include "png.h"
 #include "tmat_ctx.h"
 
 #include <algorithm>
@@ -114,16 +115,23 @@ extern "C" int tmat_host_render_tree(const void *background, int bg_dtype, int n
 }
 
 // ms (may be null): HIP-event times of the call's four phases on its stream -- upload, min-max, render kernels, copy back
+// png_out (may be null): the overlays leave as PNG files (png.h) of at most cap_each bytes instead of as rasters; rgb_out is then not used
 static int render_tree_impl(tmat_handle hd, const void *background, int bg_dtype, int n, int bh, int bw, const double *segs, const int32_t *seg_branch,
-                            const int32_t *seg_offsets, int vis_width, uint8_t *rgb_out, float *ms)
+                            const int32_t *seg_offsets, int vis_width, uint8_t *rgb_out, float *ms, uint8_t *png_out = nullptr, size_t cap_each = 0,
+                            size_t *png_sizes = nullptr)
 {
     Ctx *c = (Ctx *)hd;
     if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0f;
     Canvas cv;
-    if (!c || !background || (bg_dtype != 0 && bg_dtype != 1) || n < 0 || !seg_offsets || !rgb_out || !canvas_of(bh, bw, vis_width, cv) ||
+    if (!c || !background || (bg_dtype != 0 && bg_dtype != 1) || n < 0 || !seg_offsets || !(png_out ? (void *)png_sizes : (void *)rgb_out) || !canvas_of(bh, bw, vis_width, cv) ||
         !offsets_ok(seg_offsets, n) || (seg_offsets[n] && (!segs || !seg_branch))) {
         set_error("tmat_render_tree: bad argument");
         return TMAT_E_ARG;
+    }
+    PngShape pg{};
+    if (png_out) {
+        if (!png_shape(cv.vh, cv.vw, 3, pg)) { set_error("tmat_render_tree_png: canvas too large for one PNG file"); return TMAT_E_ARG; }
+        if (cap_each < pg.bound) { set_error("tmat_render_tree_png: cap_each is below tmat_png_bound"); return TMAT_E_CAP; }
     }
     if (n == 0) return TMAT_OK;
     TMAT_HIP(hipSetDevice(c->device));
@@ -170,7 +178,11 @@ static int render_tree_impl(tmat_handle hd, const void *background, int bg_dtype
         if (r == -1) { set_error("tmat_render_tree: canvas too large for one launch"); return TMAT_E_ARG; }
         if (r) { set_error("tmat_render_tree: kernel launch failed"); return TMAT_E_HIP; }
         mark(1);
-        mem.d2h(rgb_out + (size_t)i0 * cper, drgb, (size_t)k * cper);
+        if (png_out) {      // the encoder follows on the same stream; only file bytes cross to the host
+            if (int rc = png_encode_ctx(c, drgb, false, k, pg, png_out + (size_t)i0 * cap_each, cap_each, png_sizes + i0, nullptr)) return rc;
+        } else {
+            mem.d2h(rgb_out + (size_t)i0 * cper, drgb, (size_t)k * cper);
+        }
         mark(2);
         if (mem.finish()) return TMAT_E_HIP;
         span(0, 1, 2); span(1, 2, 3);
@@ -189,6 +201,13 @@ extern "C" int tmat_render_tree_timed(tmat_handle hd, const void *background, in
 {
     if (!ms4) { set_error("tmat_render_tree_timed: bad argument"); return TMAT_E_ARG; }
     return render_tree_impl(hd, background, bg_dtype, n, bh, bw, segs, seg_branch, seg_offsets, vis_width, rgb_out, ms4);
+}
+
+extern "C" int tmat_render_tree_png(tmat_handle hd, const void *background, int bg_dtype, int n, int bh, int bw, const double *segs,
+                                    const int32_t *seg_branch, const int32_t *seg_offsets, int vis_width, uint8_t *out, size_t cap_each, size_t *sizes)
+{
+    if (!out) { set_error("tmat_render_tree_png: bad argument"); return TMAT_E_ARG; }
+    return render_tree_impl(hd, background, bg_dtype, n, bh, bw, segs, seg_branch, seg_offsets, vis_width, nullptr, nullptr, out, cap_each, sizes);
 }
 
 // plot_colored_barcode (topology.py:67-107) without axes or text

@@ -3,6 +3,7 @@
 // entry point needs a HIP device and fails loudly without one.
 #include "../../include/tmat.h"
 #include "tmat_ctx.h"
+#include "png.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1145,4 +1146,105 @@ int tmat_prof_read(tmat_handle h, double *ms, int64_t *launches, double *flops, 
     return TMAT_OK;
 }
 
+// ---- PNG encoder (png.h) ----
+
+int tmat_png_stripe(void) { return PNG_STRIPE; }
+
+int tmat_png_bound(int H, int W, int channels, size_t *bound)
+{
+    PngShape g;
+    if (!bound || !png_shape(H, W, channels, g)) { set_error("tmat_png_bound: bad argument (H, W >= 1, channels 1 or 3, below 2^31 bytes)"); return TMAT_E_ARG; }
+    *bound = g.bound;
+    return TMAT_OK;
+}
+
+static int png_args(const char *who, const void *pics, int n, int H, int W, int channels, const void *out, size_t cap_each, const size_t *sizes, PngShape &g)
+{
+    if (n < 0 || !png_shape(H, W, channels, g) || (n && (!pics || !out || !sizes))) {
+        set_error(std::string(who) + ": bad argument (H, W >= 1, channels 1 or 3, below 2^31 bytes)");
+        return TMAT_E_ARG;
+    }
+    if (cap_each < g.bound) { set_error(std::string(who) + ": cap_each is below tmat_png_bound"); return TMAT_E_CAP; }
+    return TMAT_OK;
+}
+
+int tmat_host_png_encode_batch(const uint8_t *pics, int n, int H, int W, int channels, uint8_t *out, size_t cap_each, size_t *sizes)
+{
+    PngShape g;
+    if (int rc = png_args("tmat_host_png_encode_batch", pics, n, H, W, channels, out, cap_each, sizes, g)) return rc;
+    for (int i = 0; i < n; i++) png_encode_host(pics + (size_t)i * H * g.rb, g, out + (size_t)i * cap_each, &sizes[i]);
+    return TMAT_OK;
+}
+
+static int png_encode_api(const char *who, tmat_handle hd, const uint8_t *pics, bool on_host, int n, int H, int W, int channels, uint8_t *out,
+                          size_t cap_each, size_t *sizes, float *ms3)
+{
+    Ctx *c = (Ctx *)hd;
+    PngShape g;
+    if (!c) { set_error(std::string(who) + ": null handle"); return TMAT_E_ARG; }
+    if (int rc = png_args(who, pics, n, H, W, channels, out, cap_each, sizes, g)) return rc;
+    if (ms3) ms3[0] = ms3[1] = ms3[2] = 0.0f;
+    if (n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    return png_encode_ctx(c, pics, on_host, n, g, out, cap_each, sizes, ms3);
+}
+
+int tmat_png_encode_batch(tmat_handle h, const uint8_t *pics, int n, int H, int W, int channels, uint8_t *out, size_t cap_each, size_t *sizes)
+{
+    return png_encode_api("tmat_png_encode_batch", h, pics, true, n, H, W, channels, out, cap_each, sizes, nullptr);
+}
+int tmat_png_encode_batch_dev(tmat_handle h, const uint8_t *pics_dev, int n, int H, int W, int channels, uint8_t *out, size_t cap_each, size_t *sizes)
+{
+    return png_encode_api("tmat_png_encode_batch_dev", h, pics_dev, false, n, H, W, channels, out, cap_each, sizes, nullptr);
+}
+int tmat_png_encode_batch_timed(tmat_handle h, const uint8_t *pics, int n, int H, int W, int channels, uint8_t *out, size_t cap_each, size_t *sizes,
+                                float *ms3)
+{
+    if (!ms3) { set_error("tmat_png_encode_batch_timed: bad argument"); return TMAT_E_ARG; }
+    return png_encode_api("tmat_png_encode_batch_timed", h, pics, true, n, H, W, channels, out, cap_each, sizes, ms3);
+}
+
 }  // extern "C"
+
+namespace tmat {
+
+int png_encode_ctx(Ctx *c, const uint8_t *pics, bool on_host, int n, const PngShape &g, uint8_t *out, size_t cap_each, size_t *sizes, float *ms3)
+{
+    hipStream_t s = c->stream;
+    const size_t pic_bytes = (size_t)g.H * g.rb, fcap = (g.bound + 15) & ~(size_t)15;
+    const int K = (int)std::max<size_t>(1, std::min<size_t>(std::min(n, 65535), ((size_t)128 << 20) / g.raw));     // <= 128 MiB of filtered stream per chunk
+    struct Events { hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) hipEventDestroy(x); } } ev;
+    DevScope mem(c->ws_pool, s);        // after ev: the events go when the stream has drained
+    if (ms3) for (hipEvent_t &e : ev.e) mem.check(hipEventCreate(&e), "hipEventCreate");
+    auto mark = [&](int i) { if (ms3 && mem.ok) mem.check(hipEventRecord(ev.e[i], s), "hipEventRecord"); };
+    auto span = [&](int a, int b, int slot) { float t = 0.0f; if (ms3 && hipEventElapsedTime(&t, ev.e[a], ev.e[b]) == hipSuccess) ms3[slot] += t; };
+    uint8_t *dpic = on_host ? mem.pooled<uint8_t>((size_t)K * pic_bytes) : nullptr;
+    uint8_t *filt = mem.pooled<uint8_t>((size_t)K * g.raw), *slots = mem.pooled<uint8_t>((size_t)K * g.ns * PNG_SLOT);
+    uint8_t *files = mem.pooled<uint8_t>((size_t)K * fcap);
+    uint32_t *meta = mem.pooled<uint32_t>((size_t)K * g.ns * 4), *dsz = mem.pooled<uint32_t>(K);
+    uint32_t *hsz = mem.host<uint32_t>(K);
+    if (!mem.ok) return TMAT_E_HIP;
+    for (int i0 = 0; i0 < n; i0 += K) {
+        const int k = std::min(K, n - i0);
+        const uint8_t *src = pics + (size_t)i0 * pic_bytes;
+        mark(0);
+        if (on_host) { mem.h2d(dpic, src, (size_t)k * pic_bytes); src = dpic; }
+        mark(1);
+        if (!mem.ok) return TMAT_E_HIP;
+        if (png_encode_launch(src, k, g, filt, slots, meta, files, fcap, dsz, s)) { set_error("png encoder: kernel launch failed"); return TMAT_E_HIP; }
+        mark(2);
+        mem.d2h(hsz, dsz, (size_t)k * sizeof(uint32_t));
+        if (mem.finish()) return TMAT_E_HIP;
+        for (int i = 0; i < k; i++) {
+            if (hsz[i] < PNG_HEAD + PNG_TAIL || hsz[i] > g.bound) { set_error("png encoder: a file left its bound"); return TMAT_E_HIP; }
+            mem.d2h(out + (size_t)(i0 + i) * cap_each, files + (size_t)i * fcap, hsz[i]);
+            sizes[i0 + i] = hsz[i];
+        }
+        mark(3);
+        if (mem.finish()) return TMAT_E_HIP;
+        span(0, 1, 0); span(1, 2, 1); span(2, 3, 2);
+    }
+    return TMAT_OK;
+}
+
+}  // namespace tmat

@@ -66,6 +66,10 @@ def parse_branching_args(arg_defaults):
                    help="also write visualizations/<image>/{original_image,prediction,segmentation_mask,distance_transform}.png "
                         "(Z stacks: {original_image,vesselness_image}.png; with -w also well_mask.png).  The reference always does; here it is "
                         "opt-in.  The pictures are rendered on the GPU from the arrays the batched analysis already holds, in the same pass")
+    p.add_argument("--png-encoder", choices=["pil", "device"], default="pil",
+                   help="who encodes the PNG pictures of --visualizations / --tree-visualizations: pil (the default: Pillow on the host, one "
+                        "file after the other) or device (the library's deflate / PNG kernels: all pictures of one shape of a pass in one "
+                        "batched call, only file bytes cross to the host).  The pixels are the same; the files differ in size")
     p.add_argument("--sato-hessian", choices=["gaussian_derivatives", "gradient"], default="gaussian_derivatives",
                    help="Z stacks: Hessian of skimage.filters.sato -- gaussian_derivatives (scikit-image >= 0.20, the reference's pinned "
                         "0.22.0) or gradient (scikit-image <= 0.19)")
@@ -228,6 +232,7 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
     well_seed = int(getattr(args, "well_seed", 0) or 0)
     tree_vis = bool(getattr(args, "tree_visualizations", False))
     vis_width = int(getattr(args, "vis_width", 2000) or 2000)
+    encoder = handle.png_encode if getattr(args, "png_encoder", "pil") == "device" else None
     suffix_of = {(cfg["thresh1"], cfg["thresh2"]): sfx for cfg, sfx in branches.threshold_grid(config)}
     ids = sorted(paths)
     fields = {}
@@ -268,8 +273,8 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
                     # compute_branches.py:228-229 original_image.png = the max projection, :303 vesselness_image.png: save_vis of the field
                     # this call has just computed, on the device
                     vis_dir = out_root / "visualizations" / ids[i]
-                    branches._save_png_unique(handle.stage_pictures(st.max(0)), vis_dir, "original_image.png")
-                    branches._save_png_unique(handle.stage_pictures(field), vis_dir, "vesselness_image.png")
+                    branches._save_png_unique(handle.stage_pictures(st.max(0)), vis_dir, "original_image.png", encoder)
+                    branches._save_png_unique(handle.stage_pictures(field), vis_dir, "vesselness_image.png", encoder)
             rows.append((i,) + sato.field_stats(handle, fields[i][0], thresh[0], thresh[1], sw_px, min_px, max_px,
                                                 bool(config.get("remove_isolated_branches", False)), pruning_mask=fields[i][1]))
             if tree_vis:
@@ -279,16 +284,20 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
                                                     background.shape[1] / fields[i][0].shape[1])
                 if len(bars) == 0:
                     print(f"No branches found for {ids[i]}.", flush=True)
-                branches.save_tree_visualizations(handle, background, tree, bars, out_root / "visualizations" / ids[i], suffix_of[thresh], vis_width)
+                branches.save_tree_visualizations(handle, background, tree, bars, out_root / "visualizations" / ids[i], suffix_of[thresh], vis_width,
+                                                  encoder)
         return rows
 
     def load_and_keep(img_id):
         st = load_fn(img_id)
         if vis and detect_well:
-            from PIL import Image
             (out_root / "visualizations" / img_id).mkdir(parents=True, exist_ok=True)
             well = sato.stack_well_masks(handle, st, sato.dsamp_shape(st.shape, DOWNSAMPLE_WIDTH), well_seed)[0]
-            Image.fromarray((well * 255).astype(np.uint8)).save(out_root / "visualizations" / img_id / "well_mask.png")
+            if encoder is not None:
+                (out_root / "visualizations" / img_id / "well_mask.png").write_bytes(encoder((well * 255).astype(np.uint8))[0])
+            else:
+                from PIL import Image
+                Image.fromarray((well * 255).astype(np.uint8)).save(out_root / "visualizations" / img_id / "well_mask.png")
         return st
 
     # one stack per analysis call (chunk=1): a stack is the unit the reference streams, and it can be gigabytes
@@ -358,6 +367,8 @@ def main(args=None):
     model.handle.set_input_norm(model.norm_mean, model.norm_std)
     detect_well = bool(getattr(args, "detect_well", False))
     well_seed = int(getattr(args, "well_seed", 0) or 0)
+    # --png-encoder device: every PNG below goes through the handle's encoder, batched by shape; pil (the default): Pillow, file by file
+    encoder = model.handle.png_encode if getattr(args, "png_encoder", "pil") == "device" else None
 
     # ids are file stems, as in the reference (compute_branches.py:565-569: two files with one stem are one entry there too)
     ids = sorted(paths)
@@ -402,6 +413,12 @@ def main(args=None):
         return True
 
     def write_pictures(ids, pictures, well=None):
+        if encoder is not None:         # the whole batch's pictures in one encoder call
+            items = []
+            for i, img_id in enumerate(ids):
+                items += branches.stage_picture_items(pictures[i], out_root / "visualizations" / img_id, None if well is None else well[i])
+            branches.write_png_batch(items, encoder)
+            return
         for i, img_id in enumerate(ids):
             branches.save_stage_pictures(pictures[i], out_root / "visualizations" / img_id, None if well is None else well[i])
 
@@ -416,10 +433,16 @@ def main(args=None):
             else:
                 rows, overlays, bars = branches.analyze_batch_tree(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh,
                                                                    input_bits=input_bits, vis_width=vis_width)
+            items = []
             for img_id, ov, br in zip(ids, overlays, bars):
                 if len(br) == 0:
                     print(f"No branches found for {img_id}.", flush=True)
-                branches.save_tree_pictures(ov, br, out_root / "visualizations" / img_id, suffix_of[thresh], vis_width)
+                if encoder is not None:
+                    items += branches.tree_picture_items(ov, br, out_root / "visualizations" / img_id, suffix_of[thresh], vis_width)
+                else:
+                    branches.save_tree_pictures(ov, br, out_root / "visualizations" / img_id, suffix_of[thresh], vis_width)
+            if items:                   # the batch's overlays in one encoder call, its barcodes in another
+                branches.write_png_batch(items, encoder)
             return rows
         if not detect_well and pics:
             rows, ex = branches.analyze_batch_ex(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits,
@@ -463,7 +486,8 @@ def main(args=None):
             tree, bars, stats = branches.field_tree(model.handle, f255, config, width_um, thresh, pruning, background.shape[1] / f255.shape[1])
             if len(bars) == 0:
                 print(f"No branches found for {ids[i]}.", flush=True)
-            branches.save_tree_visualizations(model.handle, background, tree, bars, out_root / "visualizations" / ids[i], suffix_of[thresh], vis_width)
+            branches.save_tree_visualizations(model.handle, background, tree, bars, out_root / "visualizations" / ids[i], suffix_of[thresh], vis_width,
+                                              encoder)
             rows.append((i,) + stats)
         return rows
 

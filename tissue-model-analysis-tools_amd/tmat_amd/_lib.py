@@ -129,6 +129,13 @@ def lib():
     L.tmat_analyze_batch_ex_dev.argtypes = [vp, vp, i, i, i, C.POINTER(AnalyzeOpts), vp]
     L.tmat_stage_pictures.argtypes = [vp, vp, i, i, sz, vp]
     L.tmat_host_stage_pictures.argtypes = [vp, i, i, sz, vp]
+    L.tmat_png_stripe.argtypes = []
+    L.tmat_png_bound.argtypes = [i, i, i, C.POINTER(sz)]
+    L.tmat_png_encode_batch.argtypes = [vp, vp, i, i, i, i, vp, sz, vp]
+    L.tmat_png_encode_batch_dev.argtypes = L.tmat_png_encode_batch.argtypes
+    L.tmat_png_encode_batch_timed.argtypes = L.tmat_png_encode_batch.argtypes + [vp]
+    L.tmat_host_png_encode_batch.argtypes = [vp, i, i, i, i, vp, sz, vp]
+    L.tmat_render_tree_png.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, i, vp, sz, vp]
     L.tmat_prof_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), i]
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -154,6 +161,8 @@ EXPORTS = [
     "tmat_roi_plan", "tmat_roi_plan_tight", "tmat_roi_plan_exact", "tmat_conv2d_roi", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles",
     "tmat_roi_plan_const", "tmat_roi_sep_tiles_live", "tmat_roi_plan_share", "tmat_roi_sep_tiles_share", "tmat_debug_share_fill_check",
     "tmat_stage_pictures", "tmat_host_stage_pictures", "tmat_analyze_batch_ex", "tmat_analyze_batch_ex_dev",
+    "tmat_png_stripe", "tmat_png_bound", "tmat_png_encode_batch", "tmat_png_encode_batch_dev", "tmat_png_encode_batch_timed",
+    "tmat_host_png_encode_batch", "tmat_render_tree_png",
 ]
 
 
@@ -370,6 +379,31 @@ class Handle:
             check(lib().tmat_stage_pictures(self._h, ptr(a), PIC_DTYPES[a.dtype], a.shape[0], a[0].size, ptr(out)), "tmat_stage_pictures")
         return out.reshape(shape)
 
+    def png_encode(self, pics):
+        """tmat_png_encode_batch: (n, H, W) grey or (n, H, W, 3) RGB u8 pictures -> n PNG files (bytes), encoded on the device; a 2-D or
+        (H, W, 3) array is one picture"""
+        pics = _png_arg(pics)
+        return _png_call(lambda *a: lib().tmat_png_encode_batch(self._h, *a), pics, "tmat_png_encode_batch")
+
+    def png_encode_dev(self, pics_dev, n, H, W, channels):
+        """tmat_png_encode_batch_dev: the same for n pictures already in device memory (a tmat_dev_alloc pointer)"""
+        return _png_call(lambda _, *a: lib().tmat_png_encode_batch_dev(self._h, pics_dev, *a), (n, H, W, channels), "tmat_png_encode_batch_dev")
+
+    def png_encode_timed(self, pics):
+        """tmat_png_encode_batch_timed: (files, {phase: HIP-event ms}) with the phases upload, kernels, copy_back"""
+        pics = _png_arg(pics)
+        ms = np.zeros(3, np.float32)
+        files = _png_call(lambda *a: lib().tmat_png_encode_batch_timed(self._h, *a, ptr(ms)), pics, "tmat_png_encode_batch_timed")
+        return files, dict(zip(("upload", "kernels", "copy_back"), (float(v) for v in ms)))
+
+    def render_tree_png(self, backgrounds, trees, vis_width=2000):
+        """tmat_render_tree_png: Handle.render_tree's overlays as n PNG files (bytes); the raw overlays stay on the device"""
+        bg, dt, segs, sb, off, _ = _render_tree_args(backgrounds, trees, vis_width, want_out=False)
+        vh, vw = tree_canvas_shape(bg.shape[1], bg.shape[2], vis_width)
+        return _png_call(lambda _, n, H, W, ch, *a: lib().tmat_render_tree_png(self._h, ptr(bg), dt, n, bg.shape[1], bg.shape[2], ptr(segs), ptr(sb),
+                                                                                ptr(off), int(vis_width), *a),
+                         (bg.shape[0], vh, vw, 3), "tmat_render_tree_png")
+
     def debug_poison(self, byte_pattern=0xFF):
         """test-only: fill every scratch workspace of the handle with a byte pattern (include/tmat.h:tmat_debug_poison)"""
         check(lib().tmat_debug_poison(self._h, int(byte_pattern)), "tmat_debug_poison")
@@ -475,7 +509,7 @@ def tree_canvas_shape(bh, bw, vis_width=2000):
     return int(round(vis_width * bh / bw)), int(vis_width)
 
 
-def _render_tree_args(backgrounds, trees, vis_width):
+def _render_tree_args(backgrounds, trees, vis_width, want_out=True):
     bg = np.asarray(backgrounds)
     if bg.ndim == 2:
         bg = bg[None]
@@ -487,7 +521,7 @@ def _render_tree_args(backgrounds, trees, vis_width):
     segs = np.ascontiguousarray(np.concatenate([np.asarray(t[0], np.float64).reshape(-1, 4) for t in trees] + [np.zeros((1, 4))]))
     sb = np.ascontiguousarray(np.concatenate([np.asarray(t[1], np.int32).reshape(-1) for t in trees] + [np.zeros(1, np.int32)]))
     vh, vw = tree_canvas_shape(bg.shape[1], bg.shape[2], vis_width)
-    out = np.empty((bg.shape[0], vh, vw, 3), np.uint8)
+    out = np.empty((bg.shape[0], vh, vw, 3), np.uint8) if want_out else None
     return bg, 0 if bg.dtype == np.uint16 else 1, segs, sb, off, out
 
 
@@ -497,6 +531,52 @@ def host_render_tree(backgrounds, trees, vis_width=2000):
     check(lib().tmat_host_render_tree(ptr(bg), dt, bg.shape[0], bg.shape[1], bg.shape[2], ptr(segs), ptr(sb), ptr(off), int(vis_width), ptr(out)),
           "tmat_host_render_tree")
     return out
+
+
+def png_stripe():
+    """tmat_png_stripe: bytes of filtered stream one stripe of the PNG encoder compresses"""
+    return int(lib().tmat_png_stripe())
+
+
+def png_bound(H, W, channels):
+    """tmat_png_bound: the worst-case size of one file"""
+    b = C.c_size_t()
+    check(lib().tmat_png_bound(int(H), int(W), int(channels), C.byref(b)), "tmat_png_bound")
+    return int(b.value)
+
+
+def _png_arg(pics):
+    a = np.asarray(pics)
+    if a.dtype == np.bool_:
+        a = a.view(np.uint8)
+    if a.dtype != np.uint8:
+        raise ValueError(f"png_encode: expected uint8 pictures, got {a.dtype}")
+    if a.ndim == 2 or (a.ndim == 3 and a.shape[-1] == 3):       # one grey picture; a 3-D array whose last axis is 3 is one RGB picture
+        a = a[None]
+    if a.ndim not in (3, 4) or (a.ndim == 4 and a.shape[3] != 3):
+        raise ValueError(f"png_encode: expected (n, H, W) or (n, H, W, 3) pictures, got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _png_call(fn, pics, what):
+    """fn(pics pointer, n, H, W, channels, out, cap_each, sizes) -> the n files; pics: an array, or (n, H, W, channels) for a call that brings its own"""
+    if isinstance(pics, tuple):
+        n, H, W, ch = (int(v) for v in pics)
+        src = None
+    else:
+        n, H, W = pics.shape[:3]
+        ch = 3 if pics.ndim == 4 else 1
+        src = ptr(pics)
+    cap = png_bound(H, W, ch)
+    out = np.empty((n, cap), np.uint8)
+    sizes = np.zeros(max(n, 1), np.uintp)
+    check(fn(src, n, H, W, ch, ptr(out), cap, ptr(sizes)), what)
+    return [out[i, : int(sizes[i])].tobytes() for i in range(n)]
+
+
+def host_png_encode(pics):
+    """tmat_host_png_encode_batch: the host twin of Handle.png_encode (same bytes, no GPU)"""
+    return _png_call(lib().tmat_host_png_encode_batch, _png_arg(pics), "tmat_host_png_encode_batch")
 
 
 def _stage_pictures_arg(a):

@@ -157,11 +157,10 @@ def analyze_batch_ex(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_
     return [(r.index, r.count, r.total_px, r.avg_px) for r in rows], extras
 
 
-def _save_png_unique(a, vis_dir, name):
-    """a finished u8 picture into vis_dir / name under the reference's "-N" unique-name rule (helper.get_unique_output_filepath)"""
+def _unique_path(vis_dir, name):
+    """vis_dir / name under the reference's "-N" unique-name rule (helper.get_unique_output_filepath); makes vis_dir"""
     import os
     from pathlib import Path
-    from PIL import Image
     vis_dir = Path(vis_dir)
     vis_dir.mkdir(parents=True, exist_ok=True)
     file = vis_dir / name
@@ -170,6 +169,37 @@ def _save_png_unique(a, vis_dir, name):
     while file.exists():
         n += 1
         file = vis_dir / f"{stem}-{n}{ext}"
+    return file
+
+
+def write_png_batch(items, encoder):
+    """items: [(picture, vis_dir, name)], a picture being an (h, w) / (h, w, 3) u8 array or a finished PNG file (bytes).  All arrays of
+    one shape are encoded in ONE call of encoder ((n, h, w[, 3]) u8 -> n files: _lib.Handle.png_encode, _lib.host_png_encode); the
+    files are then written in the order given, each under the "-N" unique-name rule.  Returns the written paths."""
+    groups = {}
+    for k, (a, _, _) in enumerate(items):
+        if not isinstance(a, (bytes, bytearray)):
+            a = np.ascontiguousarray(a, np.uint8)
+            groups.setdefault(a.shape, []).append((k, a))
+    data = {k: a for k, (a, _, _) in enumerate(items) if isinstance(a, (bytes, bytearray))}
+    for members in groups.values():
+        files = encoder(np.stack([a for _, a in members]))
+        data.update({k: f for (k, _), f in zip(members, files)})
+    out = []
+    for k, (_, vis_dir, name) in enumerate(items):
+        file = _unique_path(vis_dir, name)
+        file.write_bytes(data[k])
+        out.append(str(file))
+    return out
+
+
+def _save_png_unique(a, vis_dir, name, encoder=None):
+    """a finished u8 picture into vis_dir / name under the reference's "-N" unique-name rule (helper.get_unique_output_filepath).
+    encoder None: PIL; else the file comes from encoder (write_png_batch)"""
+    if encoder is not None:
+        return write_png_batch([(a, vis_dir, name)], encoder)[0]
+    from PIL import Image
+    file = _unique_path(vis_dir, name)
     Image.fromarray(np.ascontiguousarray(a, np.uint8)).save(file)
     return str(file)
 
@@ -177,41 +207,49 @@ def _save_png_unique(a, vis_dir, name):
 STAGE_PICTURE_FILES = ("original_image.png", "prediction.png", "segmentation_mask.png", "distance_transform.png")
 
 
-def save_stage_pictures(pictures, vis_dir, well_mask=None):
-    """One image's (4, h, w) u8 stage pictures (analyze_batch_ex(stage_pictures=True)["pictures"][i]) as the reference's four files
-    (compute_branches.py:315, 331, 347, 348), and with well_mask (h, w) also well_mask.png = save_vis(well_mask * 255) (:364).
-    Names follow the "-N" unique-name rule.  Returns the written paths."""
+def stage_picture_items(pictures, vis_dir, well_mask=None):
+    """write_png_batch's items of one image's (4, h, w) stage pictures (+ well_mask.png)"""
     pictures = np.asarray(pictures)
     if pictures.ndim != 3 or pictures.shape[0] != 4:
         raise ValueError(f"save_stage_pictures: expected (4, h, w) pictures, got {pictures.shape}")
-    out = [_save_png_unique(pictures[k], vis_dir, name) for k, name in enumerate(STAGE_PICTURE_FILES)]
+    items = [(pictures[k], vis_dir, name) for k, name in enumerate(STAGE_PICTURE_FILES)]
     if well_mask is not None:
-        out.append(_save_png_unique(_lib.host_stage_pictures((np.asarray(well_mask) != 0).astype(np.uint8) * 255), vis_dir, "well_mask.png"))
-    return out
+        items.append((_lib.host_stage_pictures((np.asarray(well_mask) != 0).astype(np.uint8) * 255), vis_dir, "well_mask.png"))
+    return items
 
 
-def save_tree_pictures(overlay, bars, vis_dir, suffix: str = "", vis_width: int = 2000):
-    """morse_tree{suffix}.png (a finished overlay) and barcode{suffix}.png into vis_dir, "-N" unique names; nothing for an image without
-    branches (the reference prints "No branches found" and skips its plots, compute_branches.py:426-429).  Returns the written paths."""
-    import os
-    from pathlib import Path
-    from PIL import Image
+def save_stage_pictures(pictures, vis_dir, well_mask=None, encoder=None):
+    """One image's (4, h, w) u8 stage pictures (analyze_batch_ex(stage_pictures=True)["pictures"][i]) as the reference's four files
+    (compute_branches.py:315, 331, 347, 348), and with well_mask (h, w) also well_mask.png = save_vis(well_mask * 255) (:364).
+    Names follow the "-N" unique-name rule.  encoder (write_png_batch) None: PIL, file by file; else one encoder call for the image's
+    pictures (a batch of images in one call: stage_picture_items + write_png_batch).  Returns the written paths."""
+    items = stage_picture_items(pictures, vis_dir, well_mask)
+    if encoder is not None:
+        return write_png_batch(items, encoder)
+    return [_save_png_unique(a, d, name) for a, d, name in items]
 
+
+def tree_picture_items(overlay, bars, vis_dir, suffix: str = "", vis_width: int = 2000):
+    """write_png_batch's items of one image's morse_tree / barcode pair (overlay: the raster, or its finished PNG file); none without branches"""
     if len(bars) == 0:
         return []
-    vis_dir = Path(vis_dir)
-    vis_dir.mkdir(parents=True, exist_ok=True)
+    return [(overlay, vis_dir, f"morse_tree{suffix}.png"), (_lib.host_render_barcode(bars, vis_width), vis_dir, f"barcode{suffix}.png")]
 
-    def save(a, name):
-        file = vis_dir / name
-        stem, ext = os.path.splitext(file.name)
-        n = 1
-        while file.exists():                                # helper.get_unique_output_filepath
-            n += 1
-            file = vis_dir / f"{stem}-{n}{ext}"
+
+def save_tree_pictures(overlay, bars, vis_dir, suffix: str = "", vis_width: int = 2000, encoder=None):
+    """morse_tree{suffix}.png (a finished overlay) and barcode{suffix}.png into vis_dir, "-N" unique names; nothing for an image without
+    branches (the reference prints "No branches found" and skips its plots, compute_branches.py:426-429).  encoder (write_png_batch)
+    None: PIL; with it the overlay may also be a finished PNG file (Handle.render_tree_png).  Returns the written paths."""
+    items = tree_picture_items(overlay, bars, vis_dir, suffix, vis_width)
+    if encoder is not None:
+        return write_png_batch(items, encoder)
+    from PIL import Image
+    out = []
+    for a, d, name in items:
+        file = _unique_path(d, name)
         Image.fromarray(np.ascontiguousarray(a), "RGB").save(file)
-        return str(file)
-    return [save(overlay, f"morse_tree{suffix}.png"), save(_lib.host_render_barcode(bars, vis_width), f"barcode{suffix}.png")]
+        out.append(str(file))
+    return out
 
 
 def dsamp_shape(img_shape, width: int = DOWNSAMPLE_WIDTH):
@@ -437,52 +475,46 @@ def save_vis_u8(a):
     return np.rint(np.nan_to_num(a)).astype(np.uint8)
 
 
-def save_visualizations(handle: _lib.Handle, img: np.ndarray, vis_dir, ds_ratio: float = 0.625, input_bits: int = 16):
+def save_visualizations(handle: _lib.Handle, img: np.ndarray, vis_dir, ds_ratio: float = 0.625, input_bits: int = 16, encoder=None):
     """The four image dumps of the reference's 2-D branch (compute_branches.py:74-78 save_vis = rescale_intensity to
     0..255 + cv2.imwrite; :315 original_image.png, :331 prediction.png, :347 segmentation_mask.png, :348
     distance_transform.png) for one image, through the staged entry points of the same GPU path (stage_pictures_staged: a second
     pass over the image beside the batch pipeline; analyze_batch_ex(stage_pictures=True) + save_stage_pictures take them out of the
-    pipeline's own pass).  The barcode / tree pictures (:431-450) are save_tree_visualizations' job.  Returns the written paths."""
-    return [_save_png_unique(a, vis_dir, name)
-            for a, name in zip(stage_pictures_staged(handle, img, ds_ratio, input_bits), STAGE_PICTURE_FILES)]
+    pipeline's own pass).  The barcode / tree pictures (:431-450) are save_tree_visualizations' job.  encoder: write_png_batch's (None:
+    PIL).  Returns the written paths."""
+    return save_stage_pictures(np.stack(stage_pictures_staged(handle, img, ds_ratio, input_bits)), vis_dir, encoder=encoder)
 
 
-def save_stack_visualizations(handle: _lib.Handle, stack: np.ndarray, vis_dir, hessian: str = "gaussian_derivatives"):
+def save_stack_visualizations(handle: _lib.Handle, stack: np.ndarray, vis_dir, hessian: str = "gaussian_derivatives", encoder=None):
     """The two image dumps of the reference's Z-stack branch (compute_branches.py:228-229 original_image.png = the max
-    projection, :303 vesselness_image.png) for one stack, through the same GPU path.  Returns the written paths."""
-    import os
-    from pathlib import Path
-    from PIL import Image
+    projection, :303 vesselness_image.png) for one stack, through the same GPU path.  encoder: write_png_batch's (None: PIL).
+    Returns the written paths."""
     from . import sato
 
-    vis_dir = Path(vis_dir)
-    vis_dir.mkdir(parents=True, exist_ok=True)
     field = sato.stack_field(handle, stack, DOWNSAMPLE_WIDTH, hessian)
 
     def save_vis(a, name):
         a = np.asarray(a, np.float64)
         lo, hi = a.min(), a.max()
         a = (a - lo) / (hi - lo) * 255.0 if hi != lo else np.clip(a, 0, 255)
-        file = vis_dir / name
-        stem, ext = os.path.splitext(file.name)
-        n = 1
-        while file.exists():                                # helper.get_unique_output_filepath
-            n += 1
-            file = vis_dir / f"{stem}-{n}{ext}"
-        Image.fromarray(np.rint(a).astype(np.uint8)).save(file)
-        return str(file)
+        return _save_png_unique(np.rint(a).astype(np.uint8), vis_dir, name, encoder)
     return [save_vis(np.asarray(stack).max(0), "original_image.png"), save_vis(field, "vesselness_image.png")]
 
 
-def save_tree_visualizations(handle, background: np.ndarray, tree, bars, vis_dir, suffix: str = "", vis_width: int = 2000):
+def save_tree_visualizations(handle, background: np.ndarray, tree, bars, vis_dir, suffix: str = "", vis_width: int = 2000, encoder=None):
     """morse_tree{suffix}.png and barcode{suffix}.png of one image (compute_branches.py:431-450) as the library's rasters (DESIGN.md
     "Tree overlay and barcode pictures"), PNG-encoded with PIL.  background: the (bh, bw) u16 / f32 image the tree is drawn over; tree:
     (segs, seg_branch) and bars as _lib.morse_tree returns them, in background pixels; suffix: threshold_grid's "_CONFIG..." string.
     handle: the _lib.Handle whose device rasterises the overlay (tmat_render_tree); None asks for the host twin (tmat_host_render_tree, the
     same bytes).  Names follow the reference's "-N" unique-name rule.  An image without branches (the reference prints "No branches
-    found" and skips its plots) writes nothing.  Returns the written paths."""
+    found" and skips its plots) writes nothing.  encoder (write_png_batch) None: PIL; with it and a handle the overlay is rendered and
+    encoded back to back on the device (tmat_render_tree_png: only file bytes come back) and the barcode goes through encoder.
+    Returns the written paths."""
     if len(bars) == 0:
         return []
-    render = handle.render_tree if handle is not None else _lib.host_render_tree
-    overlay = render(np.asarray(background)[None], [tree], vis_width)[0]
-    return save_tree_pictures(overlay, bars, vis_dir, suffix, vis_width)
+    if encoder is not None and handle is not None:
+        overlay = handle.render_tree_png(np.asarray(background)[None], [tree], vis_width)[0]
+    else:
+        render = handle.render_tree if handle is not None else _lib.host_render_tree
+        overlay = render(np.asarray(background)[None], [tree], vis_width)[0]
+    return save_tree_pictures(overlay, bars, vis_dir, suffix, vis_width, encoder)
