@@ -617,8 +617,9 @@ int tmat_conv2d(tmat_handle h, int prec, const float *x, int n, int hh, int ww, 
                 const float *scale, const float *shift, const float *resid, int relu_in, int relu_out, float *out);
 /*
  * Stage-wise test entry point of the REGION form of that kernel (conv_mfma_kernel<..., ROI>, what the tiled entry points launch on the up
- * path): the same contract, f32 only, stride 1, on host buffers, with a segment table.  segs: nseg <= 16 segments of six ints
- * (p0, np, y0, x0, rh, rw), ascending and disjoint in the patches: the patches [p0, p0 + np) compute the rectangle of rh rows and rw >= 2
+ * path): the same contract, f32 only, stride 1, on host buffers, with a segment table.  segs: nseg <= 64 segments of six ints
+ * (p0, np, y0, x0, rh, rw), ascending and disjoint in the patches -- or the previous segment's patch range again, with a rectangle
+ * disjoint from every other rectangle of that range: the patches [p0, p0 + np) compute the rectangle of rh rows and rw >= 2
  * columns from (y0, x0) of their output and nothing else.  nseg == 0: the full-frame launch of the same convolution.
  *   rs (0 or 1): resid (nullable) is (n, hh >> rs, ww >> rs, cout) and pixel (y, x) adds resid[y >> rs][x >> rs] (hh, ww even for rs 1).
  *   subpixel != 0 (ksize 3, no resid, no out_relu): the 3x3 convolution over the 2x nearest-upsampled x in its sub-pixel form, the weights
@@ -637,6 +638,10 @@ int tmat_conv2d(tmat_handle h, int prec, const float *x, int n, int hh, int ww, 
 int tmat_conv2d_roi(tmat_handle h, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int subpixel, int cout,
                     const float *scale, const float *shift, const float *resid, int rs, int relu_in, int relu_out, const int *segs, int nseg,
                     float *out, float *out_relu);
+/* The same for the 1x1 form at stride 2 (TF SAME samples the even pixels; the down path's residual launches): hh and ww even, no
+ * residual, out (and out_relu) (n, hh / 2, ww / 2, cout), the segments' rectangles in output pixels. */
+int tmat_conv2d_roi_s2(tmat_handle h, const float *x, int n, int hh, int ww, int cin, const float *w, int cout, const float *scale,
+                       const float *shift, int relu_in, int relu_out, const int *segs, int nseg, float *out, float *out_relu);
 
 /* device memory helpers so a ctypes host can stage inputs in HBM without torch; upload and download are ordered on the handle's
  * stream (a download sees the work queued before it, e.g. tmat_zproj_dev) and return when the copy is done */
@@ -857,6 +862,20 @@ int tmat_roi_plan_share(int hh, int ww, int patch, int n_up, const int *up_chann
 int tmat_roi_sep_tiles_share(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
                              unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles);
 /*
+ * The shared-interior form of the down path's RECTANGLE launches (the unfused 40² level; roi_plan.h:RoiDownPlan::rcomp), in tables of
+ * its own: share [6 n_down + 4][max_classes][4] (row lo, row hi, column lo, column hi: the zone of the bottleneck tensor that is copied
+ * from the neighbour patches), n_rects [6 n_down + 4][max_classes] and rects [6 n_down + 4][max_classes][4][4] (y0, x0, rows, columns:
+ * at most four disjoint rectangles per class, inside rect_live; rect_live itself where the form changes nothing), comp
+ * [6 n_down + 4][max_classes][2 axes][patch] bytes (the exact sets before the columns are rounded), fills [n_fill][7] (layer, class,
+ * direction, y0, x0, rows, columns), the planned multiply-accumulates and bytes per layer and image, info [3]: some class differs from
+ * rect_live, the level that takes the form (-1: none), the longest segment table of a launch.  Host arithmetic, no GPU.
+ * The launches take the form where the shared-interior form runs, by the switch TMAT_ROI_SHARE_RECT (read at tmat_create, 0 or 1):
+ * unset, the batch pipeline runs it and tmat_predict_smooth does not; 0: nobody; 1: both.
+ */
+int tmat_roi_plan_share_rect(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                             unsigned fused_mask, int max_classes, int *n_classes, int *share, int *n_rects, int *rects,
+                             unsigned char *comp, int fill_cap, int *n_fill, int *fills, double *mac_rect, double *bytes_rect, int *info);
+/*
  * Test-only: the host-side argument checks of the share-fill launcher on a table of n_items items [7] = first patch, patches,
  * direction, y0, x0, rows, columns of a tensor (n_patches, side, side, channels) and a neighbour table [n_patches][3].  Nothing is
  * launched.  TMAT_OK when the launcher would take them; TMAT_E_ARG with the reason in tmat_last_error otherwise.
@@ -869,6 +888,8 @@ int tmat_debug_share_fill_check(int n_patches, int side, int channels, const int
  * written).
  */
 int tmat_debug_sep_tiles(tmat_handle h, int cap, int *n, long long *planned, long long *full);
+/* Test-only: the longest segment table among the rectangle launches of the last down pass, the constant patches' segment included (0: full-frame). */
+int tmat_debug_down_segs(tmat_handle h, int *max_segs);
 
 #ifdef __cplusplus
 }

@@ -376,6 +376,9 @@ struct AxisKey {
     Iv share[ROI_MAX_DOWN_LAYERS] = {};
     Mask comp[ROI_MAX_DOWN_LAYERS], sfill[ROI_MAX_DOWN_LAYERS];
     unsigned long long tiles[ROI_MAX_DOWN_LAYERS] = {};     // ~0 where the key shares nothing at the level
+    // the rectangle launches' form (RoiDownPlan::rcomp), layers 6 b + 0 .. 6 b + 5 of the last level
+    Mask rlow, rc[6];
+    Iv rshare{0, 0};
 };
 
 void inner_axis(int ws, int n_down, Iv *in)
@@ -399,6 +402,126 @@ void inner_axis(int ws, int n_down, Iv *in)
 }
 
 bool in_iv(Iv v, int i) { return i >= v.lo && i < v.hi; }
+
+// the level whose rectangle launches take the shared-interior form: the last one, unfused and in ROI_SHARE_RECT_LEVELS; -1: none
+int share_rect_level(const RoiDownPlan &d)
+{
+    const int b = d.n_down - 1;
+    return (b >= 0 && !((d.fused_mask >> b) & 1u) && ((ROI_SHARE_RECT_LEVELS >> b) & 1u)) ? b : -1;
+}
+
+// per key: rshare and the exact comp of the level's six layers (live where the key shares nothing)
+void share_rect_keys(const RoiPlan &p, std::vector<AxisKey> &keys, const Iv *inner)
+{
+    const RoiDownPlan &d = p.down;
+    const int b = d.n_down - 1, l0 = 6 * b, H = (p.ws / 2) >> b, Ho = H / 2;
+    for (AxisKey &key : keys) key.rlow = mask_of(meet(key.live[l0 + 5], Iv{0, Ho / 2}), Ho);
+    for (AxisKey &key : keys) {
+        for (int kk = 0; kk < 6; kk++) key.rc[kk] = mask_of(key.live[l0 + kk], d.res[l0 + kk]);
+        key.rshare = Iv{0, 0};
+        if (share_rect_level(d) < 0 || key.last || key.next.empty() || empty(key.rd)) continue;
+        Mask m(Ho, 0);
+        for (int v = Ho / 2; v < Ho; v++) {
+            bool ok = in_iv(key.live[l0 + 5], v) && in_iv(inner[l0 + 5], v) && in_iv(inner[l0 + 5], v - Ho / 2);
+            for (size_t i = 0; ok && i < key.next.size(); i++) ok = keys[key.next[i]].rlow[v - Ho / 2];
+            m[v] = ok;
+        }
+        const Iv sh = longest_run(m);
+        if (empty(sh)) continue;
+        Mask c[6];
+        c[5] = key.rc[5];
+        for (int v = sh.lo; v < sh.hi; v++) c[5][v] = 0;
+        auto within = [](Mask a, const Mask &lv) { for (size_t i = 0; i < a.size(); i++) a[i] = a[i] && lv[i]; return a; };
+        c[4] = within(c[5], key.rc[4]);                                 // the residual under the add (outside its live it is constant: fill)
+        c[3] = within(taps_of(c[5], TAP_S2, H), key.rc[3]);             // the halo of the pooling joins comp
+        c[2] = within(c[3], key.rc[2]);
+        c[1] = within(taps_of(c[2], TAP_DW, H), key.rc[1]);             // the halo of the second depthwise layer joins comp
+        c[0] = within(c[1], key.rc[0]);
+        bool two = true;
+        for (int kk = 0; kk < 6; kk++) two = two && runs_of(c[kk]).size() <= 2;
+        if (!two) continue;
+        key.rshare = sh;
+        for (int kk = 0; kk < 6; kk++) key.rc[kk] = c[kk];
+    }
+}
+
+// per class: the rectangles as launched, the copies of the bottleneck tensor, the totals
+void share_rect_classes(RoiPlan &p, const std::vector<AxisKey> &keys, const int *krow, const int *kcol)
+{
+    RoiDownPlan &d = p.down;
+    const int NL = d.n_layers, ws = p.ws, bl = d.n_down - 1;
+    d.rect_any = false; d.rect_fill.clear(); d.rect_segs = 0;
+    d.rcomp_mask.assign((size_t)NL * ROI_MAX_CLASSES * 2 * ws, 0);
+    // A class takes the form in all six layers of the level or in none (a layer that fell back to rect_live on its own would compute live
+    // over producers whose comp was already cut): only where every layer's comp lies inside its rect_live
+    bool takes[ROI_MAX_CLASSES] = {};
+    for (int k = 0; k < p.n_classes; k++) {
+        const AxisKey &kr = keys[krow[k]], &kc = keys[kcol[k]];
+        takes[k] = bl >= 0 && p.class_count[k] > 0 && p.read[k].rh > 0 && p.read[k].rw > 0 && (!empty(kr.rshare) || !empty(kc.rshare));
+        for (int kk = 0; takes[k] && kk < 6; kk++) {
+            const RoiRect rl = d.rect_live[6 * bl + kk][k];
+            for (const Iv &r : runs_of(kr.rc[kk])) takes[k] = takes[k] && r.lo >= rl.y0 && r.hi <= rl.y0 + rl.rh;
+            for (const Iv &c : runs_of(kc.rc[kk])) takes[k] = takes[k] && c.lo >= rl.x0 && c.hi <= rl.x0 + rl.rw;
+        }
+    }
+    for (int l = 0; l < NL; l++) {
+        d.mac_rect[l] = d.bytes_rect[l] = 0;
+        const double area = (double)d.res[l] * d.res[l] * p.tiles_per_img;
+        const double mpp = area > 0 ? d.mac_full[l] / area : 0, bpp = area > 0 ? d.bytes_full[l] / area : 0;
+        int nseg = 0;
+        for (int k = 0; k < p.n_classes; k++) {
+            const AxisKey &kr = keys[krow[k]], &kc = keys[kcol[k]];
+            const RoiRect rl = d.rect_live[l][k];
+            int &n = d.rcomp_n[l][k];
+            n = 0;
+            for (int i = 0; i < 4; i++) { d.rshare[l][k][i] = 0; d.rcomp[l][k][i] = RoiRect{0, 0, 0, 0}; }
+            const bool live_cls = p.class_count[k] > 0 && p.read[k].rh > 0 && p.read[k].rw > 0;
+            unsigned char *cm = d.rcomp_mask.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * ws;
+            const int kk = l - 6 * bl;
+            const bool done = kk >= 0 && kk < 6 && takes[k];
+            if (done) {
+                std::vector<Iv> rows = runs_of(kr.rc[kk]), cols = runs_of(kc.rc[kk]);
+                for (Iv &c : cols)
+                    if (kk < 5) c = meet(Iv{c.lo & ~3, (c.hi + 3) & ~3}, Iv{rl.x0, rl.x0 + rl.rw});
+                if (cols.size() == 2 && cols[0].hi >= cols[1].lo) { cols[0].hi = cols[1].hi; cols.pop_back(); }
+                for (const Iv &r : rows)
+                    for (const Iv &c : cols) d.rcomp[l][k][n++] = RoiRect{r.lo, c.lo, r.hi - r.lo, c.hi - c.lo};
+                std::copy(kr.rc[kk].begin(), kr.rc[kk].end(), cm);
+                std::copy(kc.rc[kk].begin(), kc.rc[kk].end(), cm + ws);
+                if (n != 1 || d.rcomp[l][k][0].y0 != rl.y0 || d.rcomp[l][k][0].x0 != rl.x0 || d.rcomp[l][k][0].rh != rl.rh || d.rcomp[l][k][0].rw != rl.rw)
+                    d.rect_any = true;
+            } else {
+                if (rl.rh > 0 && rl.rw > 0) d.rcomp[l][k][n++] = rl;
+                if (live_cls) {
+                    const RoiRect lv = d.live[l][k];
+                    for (int v = lv.y0; v < lv.y0 + lv.rh; v++) cm[v] = 1;
+                    for (int v = lv.x0; v < lv.x0 + lv.rw; v++) cm[ws + v] = 1;
+                }
+            }
+            for (int i = 0; i < n; i++) {
+                d.mac_rect[l] += mpp * d.rcomp[l][k][i].rh * d.rcomp[l][k][i].rw * p.class_count[k];
+                d.bytes_rect[l] += bpp * d.rcomp[l][k][i].rh * d.rcomp[l][k][i].rw * p.class_count[k];
+            }
+            if (p.class_count[k] > 0) nseg += n;
+            // the copies: all of the bottleneck tensor's zone
+            if (done && kk == 5) {
+                int *sh = d.rshare[l][k];
+                sh[0] = kr.rshare.lo; sh[1] = kr.rshare.hi; sh[2] = kc.rshare.lo; sh[3] = kc.rshare.hi;
+                const std::vector<Iv> rc = runs_of(kr.rc[5]), cc = runs_of(kc.rc[5]);
+                std::vector<Iv> rs, cs;
+                if (!empty(kr.rshare)) rs.push_back(kr.rshare);
+                if (!empty(kc.rshare)) cs.push_back(kc.rshare);
+                auto put = [&](int dir, const std::vector<Iv> &rows, const std::vector<Iv> &cols) {
+                    for (const Iv &r : rows)
+                        for (const Iv &c : cols) d.rect_fill.push_back(RoiDownPlan::ShareFill{l, k, dir, r.lo, c.lo, r.hi - r.lo, c.hi - c.lo});
+                };
+                put(0, rc, cs); put(1, rs, cc); put(2, rs, cs);
+            }
+        }
+        d.rect_segs = std::max(d.rect_segs, nseg);
+    }
+    if (!d.rect_any) d.rect_fill.clear();
+}
 
 }  // namespace
 
@@ -511,6 +634,7 @@ void roi_plan_share(RoiPlan &p)
             key.comp[l0] = c1;
         }
     }
+    share_rect_keys(p, keys, inner);
     // the classes: products of their two keys' sets
     d.comp.assign((size_t)NL * ROI_MAX_CLASSES * 2 * ws, 0);
     for (int k = 0; k < p.n_classes; k++) {
@@ -536,6 +660,7 @@ void roi_plan_share(RoiPlan &p)
             put(0, rc, cs); put(1, rs, cc); put(2, rs, cs);
         }
     }
+    share_rect_classes(p, keys, krow, kcol);
 }
 
 void roi_share_neighbours(const RoiPlan &p, int k, std::vector<int> &out)
@@ -571,6 +696,19 @@ long long roi_sep_tile_table_share(const RoiPlan &p, int layer, int k, std::vect
             }
     }
     return full;
+}
+
+int roi_rect_comp(const RoiPlan &p, int l, int k, RoiRect *out)
+{
+    const RoiDownPlan &d = p.down;
+    if (d.rect_any) {
+        for (int i = 0; i < d.rcomp_n[l][k]; i++) out[i] = d.rcomp[l][k][i];
+        return d.rcomp_n[l][k];
+    }
+    const RoiRect &q = d.rect_live[l][k];
+    if (q.rh <= 0 || q.rw <= 0) return 0;
+    out[0] = q;
+    return 1;
 }
 
 bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_classes, RoiPlan &out)
@@ -870,5 +1008,58 @@ extern "C" int tmat_roi_plan_share(int hh, int ww, int patch, int n_up, const in
         o[0] = f.layer; o[1] = f.cls; o[2] = f.dir; o[3] = f.y0; o[4] = f.x0; o[5] = f.rh; o[6] = f.rw;
     }
     std::copy(d.nbr.begin(), d.nbr.end(), neighbours);
+    return TMAT_OK;
+}
+
+// The rectangle launches' shared-interior tables of the same plan (RoiDownPlan::rcomp ...): share [6 n_down + 4][max_classes][4] as (row
+// lo, row hi, column lo, column hi), n_rects [6 n_down + 4][max_classes], rects [6 n_down + 4][max_classes][4 rectangles][4] as (y0, x0,
+// rows, columns), comp [6 n_down + 4][max_classes][2 axes][patch] bytes (the exact sets, before the columns are rounded), fills [n_fill][7]
+// as (layer, class, direction, y0, x0, rows, columns), the planned multiply-accumulates and bytes per layer, info: (some class differs
+// from rect_live, the level that takes the form or -1, the longest segment table of a launch).
+extern "C" int tmat_roi_plan_share_rect(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                        unsigned fused_mask, int max_classes, int *n_classes, int *share, int *n_rects, int *rects,
+                                        unsigned char *comp, int fill_cap, int *n_fill, int *fills, double *mac_rect, double *bytes_rect, int *info)
+{
+    if (!up_channels || !down_channels || !n_classes || !share || !n_rects || !rects || !comp || !n_fill || !fills || !mac_rect || !bytes_rect ||
+        !info || fill_cap < 0 || max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
+        set_error("tmat_roi_plan_share_rect: bad argument");
+        return TMAT_E_ARG;
+    }
+    RoiPlan p;
+    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, max_classes, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
+        set_error("tmat_roi_plan_share_rect: unsupported geometry");
+        return TMAT_E_ARG;
+    }
+    const RoiDownPlan &d = p.down;
+    *n_classes = p.n_classes;
+    for (int l = 0; l < d.n_layers; l++) {
+        for (int k = 0; k < max_classes; k++) {
+            const bool in = k < p.n_classes;
+            const size_t at = (size_t)l * max_classes + k;
+            RoiRect q[4];
+            const int n = in ? roi_rect_comp(p, l, k, q) : 0;
+            n_rects[at] = n;
+            for (int i = 0; i < 4; i++) {
+                share[at * 4 + i] = in ? d.rshare[l][k][i] : 0;
+                int *o = rects + (at * 4 + i) * 4;
+                o[0] = i < n ? q[i].y0 : 0; o[1] = i < n ? q[i].x0 : 0; o[2] = i < n ? q[i].rh : 0; o[3] = i < n ? q[i].rw : 0;
+            }
+            unsigned char *o = comp + at * 2 * patch;
+            if (in && !d.rcomp_mask.empty()) std::copy_n(d.rcomp_mask.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * patch, 2 * patch, o);
+            else std::fill_n(o, 2 * patch, (unsigned char)0);
+        }
+        mac_rect[l] = d.rcomp_mask.empty() ? d.mac_live[l] : d.mac_rect[l];
+        bytes_rect[l] = d.rcomp_mask.empty() ? d.bytes_live[l] : d.bytes_rect[l];
+    }
+    *n_fill = (int)d.rect_fill.size();
+    if (*n_fill > fill_cap) { set_error("tmat_roi_plan_share_rect: fill_cap too small"); return TMAT_E_ARG; }
+    for (int i = 0; i < *n_fill; i++) {
+        const RoiDownPlan::ShareFill &f = d.rect_fill[i];
+        int *o = fills + (size_t)i * 7;
+        o[0] = f.layer; o[1] = f.cls; o[2] = f.dir; o[3] = f.y0; o[4] = f.x0; o[5] = f.rh; o[6] = f.rw;
+    }
+    info[0] = d.rect_any ? 1 : 0;
+    info[1] = d.rect_any ? d.n_down - 1 : -1;
+    info[2] = d.rect_segs;
     return TMAT_OK;
 }

@@ -91,10 +91,35 @@ struct RoiDownPlan {
     std::vector<unsigned char> comp;
     std::vector<ShareFill> share_fill;
     std::vector<int> nbr;                       // [tiles_per_img][3]: the image-major tile right of, below and diagonally below a tile, or -1
+
+    // The shared-interior form of the RECTANGLE launches (TMAT_ROI_SHARE_RECT), on top of the above: the last level, where it is unfused
+    // and in ROI_SHARE_RECT_LEVELS (layers 6 b + 0 .. 6 b + 5, b = n_down - 1: the 40² level of the network).  Built like share / comp,
+    // per axis and axis key, in fields of their own: everything above keeps its values.
+    // rshare (row lo, row hi, column lo, column hi): the zone of the bottleneck tensor 6 b + 5, same rule as share.  It is the only
+    // tensor of the level that is copied: all of rshare (it lies in live, which is what up block 0 reads), into the tensor and into
+    // its activated copy -- rect_fill, same directions as share_fill.
+    // rcomp_mask (layout of comp): live \ rshare for 6 b + 5, and backwards from there through the taps, inside live, for 6 b + 4 .. 6 b:
+    // the halo of a consumer's comp (1 pixel per side under a depthwise layer, 2 i .. 2 i + 2 under the pooling) JOINS comp, so no
+    // intermediate tensor needs a copy (DESIGN 4.1.5 has the pixels against the bytes).  Per axis comp is live minus one interval: at
+    // most two runs, and a class's 2-D set at most four disjoint rectangles.
+    // rcomp[l][k][0 .. rcomp_n[l][k]): those rectangles as launched, rows exact, the columns of layers 6 b + 0 .. 6 b + 4 rounded
+    // outwards to multiples of 4 inside rect_live (a rounded rectangle may reach into the shared gap: a superset only costs time; two
+    // runs that meet after rounding are one).  Every other layer, and every class that shares nothing: rect_live itself.
+    bool rect_any = false;                      // some class's rectangles differ from rect_live
+    int rshare[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES][4] = {};
+    int rcomp_n[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {};
+    RoiRect rcomp[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES][4] = {};
+    std::vector<unsigned char> rcomp_mask;
+    std::vector<ShareFill> rect_fill;
+    double mac_rect[ROI_MAX_DOWN_LAYERS] = {}, bytes_rect[ROI_MAX_DOWN_LAYERS] = {};       // mac_planned / bytes_planned of rcomp
+    int rect_segs = 0;                          // the longest segment table a launch of the form needs (without the constant patches' segment)
 };
 
 // Fused levels (bit b) that take the shared-interior form: a level whose copies cost more than its skipped tiles save is taken out here
 constexpr unsigned ROI_SHARE_LEVELS = 3u;
+// Levels (bit b) whose rectangle launches take it too (RoiDownPlan::rcomp).  Built for the last level where it is unfused -- bit 2, the
+// 40² level; the rectangle launches of the fused levels (bits 0 and 1) have no form yet
+constexpr unsigned ROI_SHARE_RECT_LEVELS = 4u;
 
 struct RoiPlan {
     int hh = 0, ww = 0, ws = 0, n_up = 0;
@@ -154,6 +179,9 @@ long long roi_sep_tile_table_live(const RoiPlan &p, int layer, int k, std::vecto
 long long roi_sep_tile_table_share(const RoiPlan &p, int layer, int k, std::vector<int> &out);
 // Fills the shared-interior tables of a plan with a down plan (called by roi_plan_down; p.down.share_any stays false where nothing is shared)
 void roi_plan_share(RoiPlan &p);
+// The rectangles layer l launches for class k in the rectangle launches' shared-interior form (RoiDownPlan::rcomp; rect_live where the
+// plan has no such form): at most four, disjoint, inside rect_live.  Returns their count.
+int roi_rect_comp(const RoiPlan &p, int l, int k, RoiRect *out);
 // nbr in the class-major order of a pass of k images: [k tiles_per_img][3] positions, or -1
 void roi_share_neighbours(const RoiPlan &p, int k, std::vector<int> &out);
 

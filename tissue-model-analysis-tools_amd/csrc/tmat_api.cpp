@@ -334,7 +334,9 @@ static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, bool live, 
 
 // The copies of the shared-interior form for passes of k images, cached on the plan's entry like the tile tables: the neighbour table and
 // every stored tensor's items, built and uploaded on first use, never per pass.  Null + error set: an allocation or a copy failed.
-static const RoiShareTab *roi_share_tab(RoiEntry *e, int k)
+// rect: the handle may run the rectangle launches' form (TMAT_ROI_SHARE_RECT is not 0: one value per handle, so per entry) -- its item
+// tables are made too; with the switch at 0 the handle holds what the parent form holds
+static const RoiShareTab *roi_share_tab(RoiEntry *e, int k, bool rect)
 {
     for (const RoiShareTab &t : e->shares) if (t.k == k) return &t;
     const RoiPlan &p = e->plan;
@@ -345,6 +347,13 @@ static const RoiShareTab *roi_share_tab(RoiEntry *e, int k)
         RoiShareTab::Layer *sl = nullptr;
         for (RoiShareTab::Layer &l : t.layers) if (l.layer == f.layer) sl = &l;
         if (!sl) { t.layers.emplace_back(); sl = &t.layers.back(); sl->layer = f.layer; }
+        sl->items.push_back(ShareItem{k * p.class_base[f.cls], k * p.class_count[f.cls], f.dir, f.y0, f.x0, f.rh, f.rw});
+    }
+    // the rectangle launches' form (RoiDownPlan::rect_fill): tables of its own, used only where that form runs
+    for (const RoiDownPlan::ShareFill &f : rect ? p.down.rect_fill : std::vector<RoiDownPlan::ShareFill>()) {
+        RoiShareTab::Layer *sl = nullptr;
+        for (RoiShareTab::Layer &l : t.layers) if (l.layer == f.layer && l.rect) sl = &l;
+        if (!sl) { t.layers.emplace_back(); sl = &t.layers.back(); sl->layer = f.layer; sl->rect = true; }
         sl->items.push_back(ShareItem{k * p.class_base[f.cls], k * p.class_count[f.cls], f.dir, f.y0, f.x0, f.rh, f.rw});
     }
     auto up = [](const void *src, size_t bytes, void **dev) {
@@ -395,7 +404,9 @@ static RoiSegs roi_segs(const RoiPlan &p, int l, int k) { return roi_segs_of(p, 
 // rect_live, and after each launch that writes a stored tensor the strips of RoiDownPlan::fill are copied out of the constant patches
 // share: the shared-interior form on top of it (tmat_ctx.h:Ctx::roi_share) -- the fused separable layers take the share tile table, and
 // each constant fill of a stored tensor of a fused level is followed by the copies out of the neighbour patches (RoiDownPlan::share_fill)
-int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval, bool share)
+// share_rect (with share): the rectangle launches of the unfused last level take the form too (RoiDownPlan::rcomp) -- several disjoint
+// rectangles per class in their segment tables, and the bottleneck tensor and its activated copy take their shared zone from the neighbours
+int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval, bool share, bool share_rect)
 {
     if (n <= 0) return TMAT_OK;
     if (n > c->max_patches) { set_error("unet_down_dev: n > max_patches"); return TMAT_E_ARG; }
@@ -411,15 +422,30 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
         n += kimg;              // every launch below runs the constant patches too
     }
     RoiSegs sg{};
+    bool rect_form = false;         // set below, once the share tables are there
     // the segments of layer k of down block bi (null: full-frame)
     auto segs = [&](size_t bi, int k) -> const RoiSegs * {
         if (!roi_b) return nullptr;
-        sg = roi_segs_of(*plan, (cst ? plan->down.rect_live : plan->down.rect)[6 * bi + k], kimg);
+        if (rect_form) {            // up to four rectangles per class, the classes in patch order (the table fits: checked where rect_form is set)
+            sg = RoiSegs{};
+            for (int cl = 0; cl < plan->n_classes; cl++) {
+                RoiRect q[4];
+                const int nq = plan->class_count[cl] > 0 ? roi_rect_comp(*plan, 6 * (int)bi + k, cl, q) : 0;
+                for (int i = 0; i < nq; i++) {
+                    RoiSeg &g = sg.s[sg.nseg++];
+                    g.p0 = kimg * plan->class_base[cl]; g.np = kimg * plan->class_count[cl];
+                    g.y0 = q[i].y0; g.x0 = q[i].x0; g.rh = q[i].rh; g.rw = q[i].rw;
+                }
+            }
+        } else {
+            sg = roi_segs_of(*plan, (cst ? plan->down.rect_live : plan->down.rect)[6 * bi + k], kimg);
+        }
         if (cst) {
             RoiSeg &g = sg.s[sg.nseg++];
             g = RoiSeg{};
             g.p0 = n_own; g.np = kimg; g.rh = g.rw = plan->down.res[6 * bi + k];
         }
+        c->down_segs = std::max(c->down_segs, sg.nseg);
         return &sg;
     };
     // the strips of layer l's tensor t (C channels) that the constant patches hold: after the launch that writes t, before its readers
@@ -441,15 +467,18 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
     if (roi_any && (c->roi_down & 2u))
         for (RoiEntry *e : c->roi_cache) if (&e->plan == plan) ent = e;
     c->sep_tiles.clear();
+    c->down_segs = 0;
     bool tab_ok = true;
     // the shared-interior form: with the constant-ring form and the tile tables only, and where the plan shares anything
     const RoiShareTab *shr = nullptr;
-    if (share && cst && ent && plan->down.share_any && !(shr = roi_share_tab(ent, kimg))) return TMAT_E_HIP;
+    if (share && cst && ent && plan->down.share_any && !(shr = roi_share_tab(ent, kimg, c->roi_share_rect != 0))) return TMAT_E_HIP;
+    // the rectangle launches' form: where the shared-interior form runs, bit 0 of TMAT_ROI_DOWN is on and the longest table fits
+    rect_form = shr && share_rect && roi_b && plan->down.rect_any && plan->down.rect_segs + 1 <= ROI_MAX_SEGS;
     // the copies of layer l's tensor t out of the neighbour patches: behind its constant fill, before its first reader
     auto share_fill = [&](float *t, int l, int C) -> bool {
         if (!shr) return true;
         for (const RoiShareTab::Layer &sl : shr->layers)
-            if (sl.layer == l && !launch_share_fill(t, n_own, plan->down.res[l], C, shr->nbr.data(), shr->nbr_dev, sl.items.data(), sl.dev, (int)sl.items.size(), s))
+            if (sl.layer == l && (!sl.rect || rect_form) && !launch_share_fill(t, n_own, plan->down.res[l], C, shr->nbr.data(), shr->nbr_dev, sl.items.data(), sl.dev, (int)sl.items.size(), s))
                 return false;
         return true;
     };
@@ -539,6 +568,8 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
         float *dr = (last && c->relu_copy && dout == c->dout[di]) ? c->dout_relu[di] : nullptr;      // activated copy for the first up block
         launch_maxpool_add(b2, n, H, H, d.cout, b1, last ? dout : b0, s, dr, segs(bi, 5));
         if (!fill(last ? dout : b0, l0 + 5, d.cout) || (dr && !fill(dr, l0 + 5, d.cout))) return TMAT_E_ARG;
+        // (the rectangle launches' form: the shared zone of the bottleneck tensor and of its activated copy)
+        if (!share_fill(last ? dout : b0, l0 + 5, d.cout) || (dr && !share_fill(dr, l0 + 5, d.cout))) return TMAT_E_ARG;
         if (dr) c->dout_relu_ok[di] = true;
         H /= 2;
     }
@@ -692,7 +723,7 @@ int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred
         launch_extract_tiles(xi, mn, k, g, c->patch_in, c->stream);
         // (the constant-ring form only on request: the default launches of this entry point are pinned to the dependency plan's tiles)
         int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan, c->roi_const == 1 ? mn : nullptr,
-                                      c->roi_share == 1)
+                                      c->roi_share == 1, c->roi_share_rect == 1)
                       : unet_forward_dev(c, c->patch_in, k * g.tiles_per_img, c->patch_out, c->stream);
         if (!rc && plan) rc = unet_up_dev(c, c->dout[0], k * g.tiles_per_img, c->patch_out, c->stream, plan);
         if (rc) return rc;
@@ -773,6 +804,10 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     if (const char *e = getenv("TMAT_ROI_SHARE")) {
         if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_SHARE must be 0 or 1"); delete c; return TMAT_E_ARG; }
         c->roi_share = atoi(e);
+    }
+    if (const char *e = getenv("TMAT_ROI_SHARE_RECT")) {
+        if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_SHARE_RECT must be 0 or 1"); delete c; return TMAT_E_ARG; }
+        c->roi_share_rect = atoi(e);
     }
     // room for the all-constant patches of a pass behind its patches (tmat_ctx.h): the down-path workspaces and the input buffers only
     c->const_cap = c->roi_const == 0 ? 0 : std::max(4, c->max_patches / 64);
@@ -1076,23 +1111,33 @@ int tmat_debug_sep_tiles(tmat_handle h, int cap, int *n, long long *planned, lon
     return TMAT_OK;
 }
 
+int tmat_debug_down_segs(tmat_handle h, int *max_segs)
+{
+    Ctx *c = (Ctx *)h;
+    if (!c || !max_segs) { set_error("tmat_debug_down_segs: bad argument"); return TMAT_E_ARG; }
+    *max_segs = c->down_segs;
+    return TMAT_OK;
+}
+
 // Stage-wise test entry point of the REGION form (tests/test_gpu_conv_roi.py): ONE launch_conv with a segment table on host buffers.
 // The caller fills out (and out_relu): words outside the segments' rectangles come back as they went in.  nseg == 0: the full-frame launch
 // of the same convolution.
-int tmat_conv2d_roi(tmat_handle hd, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int subpixel, int cout,
-                    const float *scale, const float *shift, const float *resid, int rs, int relu_in, int relu_out, const int *segs, int nseg,
-                    float *out, float *out_relu)
+static int conv2d_roi_impl(tmat_handle hd, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int stride, int subpixel, int cout,
+                           const float *scale, const float *shift, const float *resid, int rs, int relu_in, int relu_out, const int *segs, int nseg,
+                           float *out, float *out_relu)
 {
     Ctx *c = (Ctx *)hd;
     if (!c || !x || !w || !shift || !out || n < 1 || hh < 1 || ww < 1 || cin < 1 || cout < 1 || (ksize != 1 && ksize != 3) || (subpixel && ksize != 3) ||
-        (subpixel && (resid || out_relu)) || (rs != 0 && rs != 1) || (rs && ((hh | ww) & 1)) || nseg < 0 || nseg > 16 || (nseg && !segs)) {
-        set_error("tmat_conv2d_roi: bad argument (ksize 1 or 3, sub-pixel form of a 3x3 without residual or activated copy, rs 0 or 1, at most 16 segments)");
+        (subpixel && (resid || out_relu)) || (rs != 0 && rs != 1) || (rs && ((hh | ww) & 1)) || nseg < 0 || nseg > ROI_MAX_SEGS || (nseg && !segs) ||
+        (stride != 1 && (stride != 2 || ksize != 1 || subpixel || resid || ((hh | ww) & 1)))) {
+        set_error("tmat_conv2d_roi: bad argument (ksize 1 or 3, sub-pixel form of a 3x3 without residual or activated copy, rs 0 or 1, stride 2 with the "
+                  "1x1 form without residual on even sides only, at most 64 segments)");
         return TMAT_E_ARG;
     }
     TMAT_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int up = subpixel ? 2 : 1;
-    const size_t nx = (size_t)n * hh * ww * cin, no = (size_t)n * (hh * up) * (ww * up) * cout, nr = (size_t)n * (hh >> rs) * (ww >> rs) * cout;
+    const size_t nx = (size_t)n * hh * ww * cin, no = (size_t)n * (hh * up / stride) * (ww * up / stride) * cout, nr = (size_t)n * (hh >> rs) * (ww >> rs) * cout;
     DevScope mem(c->ws_pool, s);
     // the weights as the network's own packing makes them (build_model): taps k-contiguous, the sub-pixel form pre-summed per parity class
     std::vector<float> wk = subpixel ? k_contiguous(subpixel_weights(std::vector<float>(w, w + (size_t)9 * cin * cout), cin, cout).data(), 16, cin, cout)
@@ -1105,7 +1150,7 @@ int tmat_conv2d_roi(tmat_handle hd, const float *x, int n, int hh, int ww, int c
     float *dout2 = out_relu ? mem.alloc_from((const float *)out_relu, no) : nullptr;
     if (!mem.ok) return TMAT_E_HIP;
     ConvArgs a{};
-    a.in = dx; a.N = n; a.h = hh; a.w = ww; a.Cin = cin; a.relu_in = relu_in != 0; a.ksize = subpixel ? 2 : ksize; a.stride = 1; a.W = dw;
+    a.in = dx; a.N = n; a.h = hh; a.w = ww; a.Cin = cin; a.relu_in = relu_in != 0; a.ksize = subpixel ? 2 : ksize; a.stride = stride; a.W = dw;
     a.Cout = cout; a.scale = dsc; a.shift = dsh; a.resid = dr; a.rs = rs; a.relu_out = relu_out != 0; a.out = dout; a.out_relu = dout2; a.prec = 0;
     RoiSegs sg{};
     for (int i = 0; i < nseg; i++) {
@@ -1118,6 +1163,20 @@ int tmat_conv2d_roi(tmat_handle hd, const float *x, int n, int hh, int ww, int c
     if (out_relu) mem.d2h(out_relu, dout2, no * sizeof(float));
     if (mem.finish()) return TMAT_E_HIP;
     return TMAT_OK;
+}
+
+int tmat_conv2d_roi(tmat_handle hd, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int subpixel, int cout,
+                    const float *scale, const float *shift, const float *resid, int rs, int relu_in, int relu_out, const int *segs, int nseg,
+                    float *out, float *out_relu)
+{
+    return conv2d_roi_impl(hd, x, n, hh, ww, cin, w, ksize, 1, subpixel, cout, scale, shift, resid, rs, relu_in, relu_out, segs, nseg, out, out_relu);
+}
+
+// the 1x1 form at stride 2 (the down path's residual launches): out (n, hh / 2, ww / 2, cout), the segments' rectangles are output pixels
+int tmat_conv2d_roi_s2(tmat_handle hd, const float *x, int n, int hh, int ww, int cin, const float *w, int cout, const float *scale,
+                       const float *shift, int relu_in, int relu_out, const int *segs, int nseg, float *out, float *out_relu)
+{
+    return conv2d_roi_impl(hd, x, n, hh, ww, cin, w, 1, 2, 0, cout, scale, shift, nullptr, 0, relu_in, relu_out, segs, nseg, out, out_relu);
 }
 
 int tmat_prof_enable(tmat_handle h, int on)

@@ -37,7 +37,7 @@ struct RoiShareTab {
     int k = 0;
     std::vector<int> nbr;
     int *nbr_dev = nullptr;
-    struct Layer { int layer = 0; std::vector<ShareItem> items; ShareItem *dev = nullptr; };
+    struct Layer { int layer = 0; std::vector<ShareItem> items; ShareItem *dev = nullptr; bool rect = false; };     // rect: of RoiDownPlan::rect_fill
     std::vector<Layer> layers;
 };
 struct RoiEntry {
@@ -236,9 +236,14 @@ struct Ctx {
     // leaves without a needed pixel.  -1 (unset): the batch pipeline runs it, predict_smooth does not; 0: nobody; 1: both.  Only where
     // the constant-ring form runs, and only with the tile tables (TMAT_ROI_DOWN bit 1).
     int roi_share = -1;
+    // TMAT_ROI_SHARE_RECT: the rectangle launches of the unfused 40² level take the shared-interior form too (roi_plan.h:
+    // RoiDownPlan::rcomp): several disjoint rectangles per class in their segment tables, the bottleneck tensor's shared zone copied.
+    // -1 (unset): the batch pipeline runs it, predict_smooth does not; 0: nobody; 1: both.  Only where the shared-interior form runs.
+    int roi_share_rect = -1;
     float *padval[2] = {nullptr, nullptr};                   // the pad values of a pipeline pass, per slot: c->scratch is rewritten by the front end of the pass after next
     std::vector<RoiEntry *> roi_cache;
     std::vector<std::pair<long long, long long>> sep_tiles;  // (planned, full) tiles of the fused separable launches of the last down pass (tmat_debug_sep_tiles)
+    int down_segs = 0;                                       // the longest segment table of the last down pass's launches (tmat_debug_down_segs)
     bool fused_sep = true;                                   // fused depthwise -> pointwise kernel (sepconv_ws_kernel) where the level allows (TMAT_FUSED_SEP=0: separate kernels)
     // call-scoped device workspaces of the side tools (cell area, invasion depth), kept between calls: with the reference's default batch of 4 images a
     // hipMalloc / hipFree pair per buffer and call costs more than the batch's kernels.  Slot = a ToolWs id per buffer (ws_get below).
@@ -258,7 +263,7 @@ int ensure_patch_io(Ctx *c, int n_patches);
 // padval (nullable, with a plan only): the pad values of the pass's images on the device -- the constant-ring form, where the handle and
 // the pass allow it.  X then has room for n + n / tiles_per_img patches (patch_in and patch_in2 do): the all-constant patches are written there
 int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan = nullptr, const float *padval = nullptr,
-                  bool share = false);
+                  bool share = false, bool share_rect = false);
 // plan (nullable): region form; n is then a whole number of images' patches in the plan's class-major order
 int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s, const RoiPlan *plan = nullptr);
 // the region plan of g's geometry (cached on the handle) and, in g.order, its patch order; null and the image-major order when the region

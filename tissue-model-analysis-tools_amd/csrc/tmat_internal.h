@@ -39,15 +39,30 @@ struct RoiSeg {
     unsigned dhw_mul; int dhw_sh;    // exact division by rh rw and by rw (unet_kernels.hip:FastDiv)
     unsigned dw_mul; int dw_sh;
 };
+// Several segments may name the SAME patch range with disjoint rectangles (the rectangle launches' shared-interior form,
+// roi_plan.h:RoiDownPlan::rcomp: up to four per class); patch ranges never descend and never overlap otherwise.
+constexpr int ROI_MAX_SEGS = 64;         // 4 per class over 15 classes, the constant patches' segment, room to spare: 3 KB of the 4 KB of kernel arguments
 struct RoiSegs {
     int nseg;
-    RoiSeg s[16];
+    RoiSeg s[ROI_MAX_SEGS];
     long long pixels() const { long long t = 0; for (int i = 0; i < nseg; i++) t += (long long)s[i].np * s[i].rh * s[i].rw; return t; }
 };
 // The kernels without matrix work (depthwise, pooling, stem at the even pixels, pooling fix-ups) take the same table: a patch computes
 // the pixels [y0, y1) x [x0, x1) of its segment, a patch no segment names computes nothing.  A thread whose pixels lie outside its
 // patch's box returns before its first load; border tests stay against the patch.
 struct RoiBox { int y0, y1, x0, x1; };
+// The product form, for the kernels of the unfused level (depthwise, pooling), whose tables may name a patch range several times: the
+// segments of one patch are at most two row intervals times at most two column intervals (one segment: both intervals of an axis coincide).
+struct RoiBox2 {
+    int y0, y1, x0, x1;             // first row interval [y0, y1), first column interval [x0, x1)
+    int y2, y3, x2, x3;             // second ones (copies of the first where the patch has one)
+#ifdef __HIPCC__
+    __device__ __forceinline__ bool row(int y) const { return (y >= y0 && y < y1) || (y >= y2 && y < y3); }
+    __device__ __forceinline__ bool col(int x) const { return (x >= x0 && x < x1) || (x >= x2 && x < x3); }
+    // does [a, b) meet a row interval?
+    __device__ __forceinline__ bool rows_meet(int a, int b) const { return (a < y1 && b > y0) || (a < y3 && b > y2); }
+#endif
+};
 struct RoiNone {};
 #ifdef __HIPCC__
 // the box of patch n (n and the table are uniform: scalar compares); false: nothing to compute
@@ -59,6 +74,22 @@ __device__ __forceinline__ bool roi_box_of(const RoiSegs &r, int n, RoiBox &q)
         if (n >= r.s[k].p0 && n < r.s[k].p0 + r.s[k].np) { q = RoiBox{r.s[k].y0, r.s[k].y0 + r.s[k].rh, r.s[k].x0, r.s[k].x0 + r.s[k].rw}; hit = true; }
     return hit;
 }
+// the same in the product form: two more scalar compares per axis
+__device__ __forceinline__ bool roi_box_of(const RoiSegs &r, int n, RoiBox2 &q)
+{
+    bool hit = false;
+    q = RoiBox2{0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < r.nseg; k++)
+        if (n >= r.s[k].p0 && n < r.s[k].p0 + r.s[k].np) {
+            const int y0 = r.s[k].y0, y1 = y0 + r.s[k].rh, x0 = r.s[k].x0, x1 = x0 + r.s[k].rw;
+            if (!hit) q = RoiBox2{y0, y1, x0, x1, y0, y1, x0, x1};
+            if (y0 != q.y0) { q.y2 = y0; q.y3 = y1; }
+            if (x0 != q.x0) { q.x2 = x0; q.x3 = x1; }
+            hit = true;
+        }
+    return hit;
+}
+__device__ __forceinline__ bool roi_box_of(const RoiNone &, int, RoiBox2 &) { return true; }
 __device__ __forceinline__ bool roi_box_of(const RoiNone &, int, RoiBox &) { return true; }
 #endif
 // returns false (and sets the error) on unsupported shapes; roi (nullable; stride 2 with the 1x1 form only: the rectangles are output

@@ -932,11 +932,21 @@ bool launch_conv(const ConvArgs &a, hipStream_t s, const RoiSegs *roi)
         return false;
     }
     const int M = (int)Mll;
-    if (roi) {      // every segment inside the batch and the patch, in ascending patch order, at least two pixels wide
-        bool ok = (a.stride == 1 || a.ksize == 1) && a.prec != 3 && roi->nseg >= 1 && roi->nseg <= 16;
-        for (int i = 0, p = 0; ok && i < roi->nseg; i++) {
+    if (roi) {      // every segment inside the batch and the patch, at least two pixels wide; patch ranges in ascending order, or the
+                    // previous segment's range again with a rectangle disjoint from every other one of that range
+        bool ok = (a.stride == 1 || a.ksize == 1) && a.prec != 3 && roi->nseg >= 1 && roi->nseg <= ROI_MAX_SEGS;
+        for (int i = 0, p = 0, first = 0; ok && i < roi->nseg; i++) {
             const RoiSeg &g = roi->s[i];
-            ok = g.p0 >= p && g.np >= 1 && g.p0 + g.np <= a.N && g.y0 >= 0 && g.x0 >= 0 && g.rh >= 1 && g.rw >= 2 && g.y0 + g.rh <= Ho && g.x0 + g.rw <= Wo;
+            ok = g.np >= 1 && g.p0 >= 0 && g.p0 + g.np <= a.N && g.y0 >= 0 && g.x0 >= 0 && g.rh >= 1 && g.rw >= 2 && g.y0 + g.rh <= Ho && g.x0 + g.rw <= Wo;
+            if (ok && i > 0 && g.p0 == roi->s[first].p0 && g.np == roi->s[first].np) {
+                for (int j = first; ok && j < i; j++) {
+                    const RoiSeg &o = roi->s[j];
+                    ok = g.y0 >= o.y0 + o.rh || o.y0 >= g.y0 + g.rh || g.x0 >= o.x0 + o.rw || o.x0 >= g.x0 + g.rw;
+                }
+            } else {
+                ok = ok && g.p0 >= p;
+                first = i;
+            }
             p = g.p0 + g.np;
         }
         if (!ok) { set_error("launch_conv: bad region table"); return false; }
@@ -991,9 +1001,9 @@ __global__ __launch_bounds__(256, TMAT_DW_WPS) void dwconv_kernel(const float *_
     const int ys = (g / WG) * DW_ROWS, x0 = (g % WG) * 4;
     // region form (template flag: the full-frame launches keep their code): the strip's rows inside the patch's box only; the box's columns
     // are whole strips (roi_plan.cpp: multiples of 4)
-    RoiBox rb{};
+    RoiBox2 rb{};
     if (!roi_box_of(roi, n, rb)) return;
-    if (ROI && (x0 < rb.x0 || x0 >= rb.x1 || ys >= rb.y1 || ys + DW_ROWS <= rb.y0)) return;
+    if (ROI && (!rb.col(x0) || !rb.rows_meet(ys, ys + DW_ROWS))) return;
     const float *base = in + (size_t)n * H * W * C + cq * 4;
     const float lo = relu_in ? 0.f : -INFINITY;
     float4 wt[9];
@@ -1004,7 +1014,7 @@ __global__ __launch_bounds__(256, TMAT_DW_WPS) void dwconv_kernel(const float *_
     for (int c = 0; c < 6; c++) xok[c] = x0 + c - 1 >= 0 && x0 + c - 1 < W;
     auto load_row = [&](int yy, float4 *row) {
         const bool yok = yy >= 0 && yy < H;
-        if (ROI && (yy < rb.y0 - 1 || yy > rb.y1)) {       // under no output row of the box: never used
+        if (ROI && !rb.rows_meet(yy - 1, yy + 2)) {       // under no output row of the box: never used
 #pragma unroll
             for (int c = 0; c < 6; c++) row[c] = make_float4(0.f, 0.f, 0.f, 0.f);
             return;
@@ -1026,7 +1036,7 @@ __global__ __launch_bounds__(256, TMAT_DW_WPS) void dwconv_kernel(const float *_
     for (int r = 0; r < DW_ROWS; r++) {
         // rows (r, r + 1, r + 2) mod 3 of `win` hold input rows ys + r - 1, ys + r, ys + r + 1
         load_row(ys + r + 1, win[(r + 2) % 3]);
-        if (ROI && (ys + r < rb.y0 || ys + r >= rb.y1)) continue;
+        if (ROI && !rb.row(ys + r)) continue;
 #pragma unroll
         for (int px = 0; px < 4; px++) {
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1188,9 +1198,9 @@ __global__ __launch_bounds__(256) void maxpool_add_kernel(const float *__restric
     const int p = e >> c4shift;
     if (p >= Ho * Wo) return;
     const int yo = p / Wo, xo = p - yo * Wo;
-    RoiBox rb{};
+    RoiBox2 rb{};
     if (!roi_box_of(roi, n, rb)) return;
-    if (ROI && (yo < rb.y0 || yo >= rb.y1 || xo < rb.x0 || xo >= rb.x1)) return;
+    if (ROI && (!rb.row(yo) || !rb.col(xo))) return;
     const float *base = p2 + (size_t)n * H * W * C + cq * 4;
     float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
 #pragma unroll

@@ -158,8 +158,8 @@ EXPORTS = [
     "tmat_set_gaussian_table", "tmat_host_gaussian_kernel1d", "tmat_gaussian_f32", "tmat_sato_batch", "tmat_stack_prepare", "tmat_vessel_field",
     "tmat_analyze_stack", "tmat_field_stats", "tmat_field_stats_pruned", "tmat_resize_aa_u16", "tmat_cell_area_batch", "tmat_cell_area_masked", "tmat_resize_linear_u16",
     "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi", "tmat_resnet_set_precision", "tmat_conv2d",
-    "tmat_roi_plan", "tmat_roi_plan_tight", "tmat_roi_plan_exact", "tmat_conv2d_roi", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles",
-    "tmat_roi_plan_const", "tmat_roi_sep_tiles_live", "tmat_roi_plan_share", "tmat_roi_sep_tiles_share", "tmat_debug_share_fill_check",
+    "tmat_roi_plan", "tmat_roi_plan_tight", "tmat_roi_plan_exact", "tmat_conv2d_roi", "tmat_conv2d_roi_s2", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles", "tmat_debug_down_segs",
+    "tmat_roi_plan_const", "tmat_roi_sep_tiles_live", "tmat_roi_plan_share", "tmat_roi_sep_tiles_share", "tmat_roi_plan_share_rect", "tmat_debug_share_fill_check",
     "tmat_stage_pictures", "tmat_host_stage_pictures", "tmat_analyze_batch_ex", "tmat_analyze_batch_ex_dev",
     "tmat_png_stripe", "tmat_png_bound", "tmat_png_encode_batch", "tmat_png_encode_batch_dev", "tmat_png_encode_batch_timed",
     "tmat_host_png_encode_batch", "tmat_render_tree_png",
@@ -326,7 +326,7 @@ class Handle:
 
     def conv2d_roi(self, x, w, scale, shift, segs, out, resid=None, rs=0, subpixel=False, relu_in=False, relu_out=False, out_relu=None):
         """stage-wise test entry point of the region form (include/tmat.h:tmat_conv2d_roi): one f32 convolution of the MFMA kernel with a
-        segment table.  x (n, h, w, cin), w in the Keras layout (k, k, cin, cout); segs: at most 16 rows (p0, np, y0, x0, rh, rw), none for
+        segment table.  x (n, h, w, cin), w in the Keras layout (k, k, cin, cout); segs: at most 64 rows (p0, np, y0, x0, rh, rw; a patch range may repeat with disjoint rectangles), none for
         the full-frame launch; resid (nullable) (n, h >> rs, w >> rs, cout); subpixel: the 3x3 over the 2x nearest-upsampled x, out
         (n, 2 h, 2 w, cout), segments in stored pixels.  out (and out_relu, nullable) are caller-filled float32 arrays, changed in place:
         words outside the rectangles keep their value.  Returns out."""
@@ -352,6 +352,31 @@ class Handle:
         check(lib().tmat_conv2d_roi(self._h, ptr(x), n, hh, ww, cin, ptr(w), k, int(bool(subpixel)), cout, None if scale is None else ptr(scale),
                                     ptr(shift), None if resid is None else ptr(resid), int(rs), int(bool(relu_in)), int(bool(relu_out)),
                                     ptr(sg) if len(sg) else None, len(sg), ptr(out), None if out_relu is None else ptr(out_relu)), "tmat_conv2d_roi")
+        return out
+
+    def conv2d_roi_s2(self, x, w, scale, shift, segs, out, relu_in=False, relu_out=False, out_relu=None):
+        """conv2d_roi for the 1x1 form at stride 2 (include/tmat.h:tmat_conv2d_roi_s2): x (n, h, w, cin) with even h and w, w (1, 1, cin, cout),
+        out (and out_relu, nullable) caller-filled (n, h / 2, w / 2, cout), segs in output pixels.  Returns out."""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(w, np.float32)
+        n, hh, ww, cin = x.shape
+        if w.shape[:3] != (1, 1, cin) or (hh | ww) & 1:
+            raise ValueError("conv2d_roi_s2: w must be (1, 1, cin, cout), h and w even")
+        cout = w.shape[3]
+        for o in (out, out_relu):
+            if o is not None and (o.dtype != np.float32 or not o.flags.c_contiguous or o.shape != (n, hh // 2, ww // 2, cout)):
+                raise ValueError("conv2d_roi_s2: out / out_relu must be C-contiguous float32 arrays of the result's shape")
+        shift = np.ascontiguousarray(shift, np.float32)
+        scale = None if scale is None else np.ascontiguousarray(scale, np.float32)
+        if shift.shape != (cout,) or (scale is not None and scale.shape != (cout,)):
+            raise ValueError("conv2d_roi_s2: scale / shift must have cout entries")
+        sg = np.ascontiguousarray(np.asarray(segs, np.int32).reshape(-1, 6))
+        L = lib()
+        L.tmat_conv2d_roi_s2.argtypes = ([C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
+        check(L.tmat_conv2d_roi_s2(self._h, ptr(x), n, hh, ww, cin, ptr(w), cout, None if scale is None else ptr(scale), ptr(shift),
+                                   int(bool(relu_in)), int(bool(relu_out)), ptr(sg) if len(sg) else None, len(sg), ptr(out),
+                                   None if out_relu is None else ptr(out_relu)), "tmat_conv2d_roi_s2")
         return out
 
     def render_tree(self, backgrounds, trees, vis_width=2000):
@@ -416,6 +441,12 @@ class Handle:
         planned, full = np.zeros(16, np.int64), np.zeros(16, np.int64)
         check(L.tmat_debug_sep_tiles(self._h, 16, ptr(n), ptr(planned), ptr(full)), "tmat_debug_sep_tiles")
         return [(int(planned[i]), int(full[i])) for i in range(min(int(n[0]), 16))]
+
+    def debug_down_segs(self):
+        """test-only: the longest segment table among the rectangle launches of the last down pass (include/tmat.h:tmat_debug_down_segs)"""
+        n = C.c_int()
+        check(lib().tmat_debug_down_segs(self._h, C.byref(n)), "tmat_debug_down_segs")
+        return n.value
 
     def debug_held_bytes(self):
         """test-only: (device bytes, pinned bytes) the handle retains between calls (include/tmat.h:tmat_debug_held_bytes)"""
@@ -710,6 +741,31 @@ def roi_plan_share(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), down_ch
     check(L.tmat_roi_plan_share(hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), max_classes, ptr(ncls), ptr(inner), ptr(share),
                                 ptr(comp), cap, ptr(nfill), ptr(fills), tiles, ptr(nbr)), "roi_plan_share")
     return dict(n_classes=int(ncls[0]), inner=inner, share=share, comp=comp, fills=fills[:int(nfill[0])], neighbours=nbr)
+
+
+def roi_plan_share_rect(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3, max_classes=16):
+    """tmat_roi_plan_share_rect (include/tmat.h): the rectangle launches' shared-interior tables of roi_plan_down's plan; host arithmetic,
+    no GPU.  Returns a dict: n_classes, share [6 n_down + 4][max_classes][4] (row lo, row hi, column lo, column hi), n_rects
+    [6 n_down + 4][max_classes], rects [6 n_down + 4][max_classes][4][4] (y0, x0, rows, columns), comp [6 n_down + 4][max_classes][2][patch]
+    uint8, fills [n][7] (layer, class, direction, y0, x0, rows, columns), mac_rect and bytes_rect [6 n_down + 4], any, level, max_segs."""
+    L = lib()
+    L.tmat_roi_plan_share_rect.argtypes = ([C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint, C.c_int] + [C.c_void_p] * 5 +
+                                           [C.c_int] + [C.c_void_p] * 5)
+    n_up, n_down = len(channels) - 1, len(down_channels) - 1
+    ch, dch = np.asarray(channels, np.int32), np.asarray(down_channels, np.int32)
+    nl = 6 * n_down + 4
+    ncls, nfill, info = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(3, np.int32)
+    share, nrect = np.zeros((nl, max_classes, 4), np.int32), np.zeros((nl, max_classes), np.int32)
+    rects = np.zeros((nl, max_classes, 4, 4), np.int32)
+    comp = np.zeros((nl, max_classes, 2, patch), np.uint8)
+    cap = nl * max_classes * 12
+    fills = np.zeros((cap, 7), np.int32)
+    mac, byt = np.zeros(nl, np.float64), np.zeros(nl, np.float64)
+    check(L.tmat_roi_plan_share_rect(hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), max_classes, ptr(ncls), ptr(share),
+                                     ptr(nrect), ptr(rects), ptr(comp), cap, ptr(nfill), ptr(fills), ptr(mac), ptr(byt), ptr(info)),
+          "roi_plan_share_rect")
+    return dict(n_classes=int(ncls[0]), share=share, n_rects=nrect, rects=rects, comp=comp, fills=fills[:int(nfill[0])], mac_rect=mac,
+                bytes_rect=byt, any=bool(info[0]), level=int(info[1]), max_segs=int(info[2]))
 
 
 def roi_sep_tiles_share(hh, ww, layer, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
