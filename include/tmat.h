@@ -498,6 +498,47 @@ int tmat_field_stats_pruned(tmat_handle h, const float *field, int fh, int fw, f
                             int smoothing_window_px, int min_branch_length_px, int max_branch_length_px, int remove_isolated,
                             const uint8_t *pruning_mask, int64_t index, tmat_row *row);
 
+/*
+ * Batch form of the Z-stack branch.  n stacks of one shape (n, Z, H, W) u16 host go through the device stages in
+ * passes of K stacks, one launch set per pass (every per-image quantity -- extrema, labels, borders -- stays per stack); while the
+ * device works on pass p, a host thread runs the graph stage of pass p - 1 (DMT collect + MorseGraph statistics per stack and
+ * threshold pair, on the worker threads TMAT_HOST_THREADS sizes).  The field never leaves HBM between the stages, and the whole
+ * threshold grid (compute_branches.py:366-395) is swept from it.
+ * K = min(n, TMAT_STACK_PASS_MAX, TMAT_STACK_PASS_BUDGET / device bytes of one stack), at least 1; the bytes are summed over the
+ * blocks a pass takes (the three Z H W f64 planes of the resize dominate).  The budget is a fixed cap, not a tuned number.
+ * opts.pass_stacks > 0 overrides K.  tmat_stack_pass_plan (host only) reports K and the bytes for a geometry.
+ */
+#define TMAT_STACK_PASS_MAX 8
+#define TMAT_STACK_PASS_BUDGET (8ull << 30)   /* 8 GiB of device memory per pass */
+typedef struct tmat_stack_opts {
+    uint32_t size;                       /* sizeof as the caller compiled it; TMAT_E_ARG if unknown */
+    int ds_width, hessian;
+    int n_thresh; const float *thresh;   /* n_thresh pairs (graph_thresh_1, graph_thresh_2)          */
+    int smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated;
+    int64_t first_index;
+    const uint8_t *pruning_masks;        /* NULL or (n, fh, fw) u8 host, as tmat_field_stats_pruned  */
+    float *fields_out;                   /* NULL or (n, fh, fw) f32 host                              */
+    uint8_t *proj_pic_out;               /* NULL or (n, H, W) u8: save_vis of the max projection      */
+    uint8_t *field_pic_out;              /* NULL or (n, fh, fw) u8: save_vis of the field             */
+    int pass_stacks;                     /* 0 = automatic                                             */
+} tmat_stack_opts;
+/* compute_branches.py:224-306, 366-395, 391-426 for n stacks: rows (n_thresh, n), rows[t * n + i] = stack i at threshold pair t, equal
+ * to tmat_analyze_stack (or tmat_field_stats_pruned with the stack's pruning mask) at that pair bit for bit, whatever K is.  The two
+ * pictures (:228-229 original_image.png, :303 vesselness_image.png) are the bytes tmat_stage_pictures gives for the stack's max
+ * projection and for its field, rendered from the buffers in HBM. */
+int tmat_analyze_stack_batch(tmat_handle h, const uint16_t *stacks, int n, int Z, int H, int W,
+                             const tmat_stack_opts *o, tmat_row *rows /* (n_thresh, n) */);
+/* compute_branches.py:258-302 for n prepared stacks vols (n, Z, h, w) in one launch set -> fields (n, h, w); the arrays of `stages`
+ * carry a leading n */
+int tmat_vessel_field_batch(tmat_handle h, const float *vols, int n, int Z, int hh, int ww, int hessian,
+                            float *fields, const tmat_vessel_stages *stages /* arrays with leading n */);
+/* stacks per pass and device bytes per stack of tmat_analyze_stack_batch for n stacks of (Z, H, W) (either output may be NULL) */
+int tmat_stack_pass_plan(int n, int Z, int H, int W, int ds_width, int pass_stacks, int *stacks_per_pass,
+                         uint64_t *bytes_per_stack);
+/* Measurement aid (tools/bench_stack.py): per pass of the handle's last tmat_analyze_stack_batch, the wall milliseconds of its device
+ * stages (upload to the copy back of the DMT outputs) and of its host graph stage.  n_pass = passes of that call; at most cap are written. */
+int tmat_debug_stack_trace(tmat_handle h, int cap, int *n_pass, double *gpu_ms, double *host_ms);
+
 /* skimage.transform.resize(x, (n, out_h, out_w), order=1, preserve_range=True, anti_aliasing=True) of n integer images
  * (scikit-image >= 0.19: anti-aliasing gaussian + grid-mode linear zoom, clipped to the input's range), float64 out.
  * compute_branches.py:232-238 resizes the max projection of a Z stack with it before make_well_mask.

@@ -14,6 +14,7 @@
 #include "tmat_ctx.h"
 #include "postproc.h"
 #include "morph.h"
+#include "host_par.h"
 
 #include <algorithm>
 #include <atomic>
@@ -240,25 +241,7 @@ struct GraphParams {
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static bool trace_on() { static int t = -1; if (t < 0) { const char *e = getenv("TMAT_TRACE"); t = e && atoi(e) > 0; } return t; }
 
-static int n_workers(int k)
-{
-    int hw = (int)std::thread::hardware_concurrency();
-    if (hw <= 0) hw = 4;
-    const char *e = getenv("TMAT_HOST_THREADS");
-    if (e && atoi(e) > 0) hw = atoi(e);
-    return std::max(1, std::min(hw, k));
-}
-
-template <class F>
-static void parallel_images(int k, F f)
-{
-    std::atomic<int> next{0};
-    std::vector<std::thread> th;
-    const int nt = n_workers(k);
-    for (int t = 0; t < nt; t++)
-        th.emplace_back([&]() { for (;;) { const int i = next.fetch_add(1); if (i >= k) break; f(i); } });
-    for (auto &t : th) t.join();
-}
+// n_workers / parallel_images: host_par.h (shared with the Z-stack batch pipeline)
 
 // Host coordinator of one pass (runs in its own thread while the GPU works on the next pass):
 //   1. ordered medial-axis thinning per image (sequential by construction)            host threads

@@ -184,10 +184,14 @@ __device__ __forceinline__ double key_f64(unsigned long long k)
     const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
     return __longlong_as_double((long long)b);
 }
-__global__ void minmax_init_kernel(unsigned long long *mm) { mm[0] = ~0ull; mm[1] = 0ull; }
+// Extrema of n stacks of `n` values each in one launch: blockIdx.y (minmax_all) / blockIdx.x (init, decode) is the stack, mm holds one
+// (min, max) key pair per stack.  A batch never shares a pair: rescale_intensity and the resize's clip are "over the whole stack".
+__global__ void minmax_init_kernel(unsigned long long *mm) { mm[2 * blockIdx.x] = ~0ull; mm[2 * blockIdx.x + 1] = 0ull; }
 template <typename T>
 __global__ __launch_bounds__(256) void minmax_all_kernel(const T *__restrict__ x, size_t n, unsigned long long *mm)
 {
+    x += (size_t)blockIdx.y * n;
+    mm += 2 * (size_t)blockIdx.y;
     unsigned long long lo = ~0ull, hi = 0ull;
     FLAT_LOOP(p, n) { const unsigned long long k = f64_key((double)x[p]); lo = k < lo ? k : lo; hi = k > hi ? k : hi; }
     for (int o = 32; o > 0; o >>= 1) {
@@ -202,18 +206,24 @@ __global__ __launch_bounds__(256) void minmax_all_kernel(const T *__restrict__ x
         atomicMin(&mm[0], lo); atomicMax(&mm[1], hi);
     }
 }
-__global__ void minmax_decode_kernel(const unsigned long long *mm, double *out) { out[0] = key_f64(mm[0]); out[1] = key_f64(mm[1]); }
+__global__ void minmax_decode_kernel(const unsigned long long *mm, double *out)
+{
+    out[2 * blockIdx.x] = key_f64(mm[2 * blockIdx.x]);
+    out[2 * blockIdx.x + 1] = key_f64(mm[2 * blockIdx.x + 1]);
+}
 
-// scipy zoom order 1 on every slice (the Z axis has zoom 1: its taps are (1, 0) and add exact zeros), clipped to lohi
-__global__ void zoom_stack_kernel(const double *__restrict__ a, int H, int W, int oh, int ow, const int *__restrict__ r0,
+// scipy zoom order 1 on every slice (the Z axis has zoom 1: its taps are (1, 0) and add exact zeros), clipped to the lohi pair of the
+// slice's own stack (Z slices per stack)
+__global__ void zoom_stack_kernel(const double *__restrict__ a, int Z, int H, int W, int oh, int ow, const int *__restrict__ r0,
                                   const int *__restrict__ r1, const double *__restrict__ wr0, const double *__restrict__ wr1,
                                   const int *__restrict__ c0, const int *__restrict__ c1, const double *__restrict__ wc0,
                                   const double *__restrict__ wc1, const double *__restrict__ lohi, double *__restrict__ out, size_t total)
 {
-    const double l = lohi[0], h = lohi[1];
     const size_t onpx = (size_t)oh * ow;
     FLAT_LOOP(p, total) {
         const size_t z = p / onpx;
+        const size_t st = z / (size_t)Z;
+        const double l = lohi[2 * st], h = lohi[2 * st + 1];
         const int q = (int)(p - z * onpx);
         const int y = q / ow, x = q - y * ow;
         const double *src = a + z * (size_t)H * W;
@@ -224,43 +234,48 @@ __global__ void zoom_stack_kernel(const double *__restrict__ a, int H, int W, in
         out[p] = fmin(fmax(t, l), h);
     }
 }
-// rescale_intensity(out_range=(0, 1)) of an f64 array, then astype(f32)
-__global__ void rescale01_f64_kernel(const double *__restrict__ x, size_t n, const double *__restrict__ lohi, float *__restrict__ out)
+// rescale_intensity(out_range=(0, 1)) of f64 stacks of `per` values, each with its own lohi pair, then astype(f32)
+__global__ void rescale01_f64_kernel(const double *__restrict__ x, size_t n, size_t per, const double *__restrict__ lohi, float *__restrict__ out)
 {
-    const double lo = lohi[0], hi = lohi[1];
-    const double d = hi - lo;
     FLAT_LOOP(p, n) {
+        const size_t st = p / per;
+        const double lo = lohi[2 * st], hi = lohi[2 * st + 1];
+        const double d = hi - lo;
         double v = fmin(fmax(x[p], lo), hi);
         v = lo != hi ? ((v - lo) / d) * 1.0 + 0.0 : fmin(fmax(v, 0.0), 1.0);
         out[p] = (float)v;
     }
 }
 
-int stack_zoom_rescale_dev(const double *filtered, const uint16_t *stack_after_gauss, int Z, int H, int W, int oh, int ow, const int *r0,
+// n stacks of Z slices; mm: 2 n keys, lohi: 4 n doubles (the n input pairs, then the n output pairs)
+int stack_zoom_rescale_dev(const double *filtered, const uint16_t *stack_after_gauss, int n, int Z, int H, int W, int oh, int ow, const int *r0,
                            const int *r1, const double *wr0, const double *wr1, const int *c0, const int *c1, const double *wc0,
                            const double *wc1, double *zoomed, unsigned long long *mm, double *lohi, float *vol, hipStream_t s)
 {
-    const size_t nin = (size_t)Z * H * W, nout = (size_t)Z * oh * ow;
-    hipLaunchKernelGGL(minmax_init_kernel, dim3(1), dim3(1), 0, s, mm);
-    const dim3 rgrid_in((unsigned)std::min<size_t>(2048, (nin + 255) / 256)), rgrid_out((unsigned)std::min<size_t>(2048, (nout + 255) / 256));
+    const size_t nin = (size_t)Z * H * W, nout = (size_t)Z * oh * ow;       // per stack
+    hipLaunchKernelGGL(minmax_init_kernel, dim3(n), dim3(1), 0, s, mm);
+    const dim3 rgrid_in((unsigned)std::min<size_t>(2048, (nin + 255) / 256), n), rgrid_out((unsigned)std::min<size_t>(2048, (nout + 255) / 256), n);
     hipLaunchKernelGGL((minmax_all_kernel<uint16_t>), rgrid_in, dim3(256), 0, s, stack_after_gauss, nin, mm);
-    hipLaunchKernelGGL(minmax_decode_kernel, dim3(1), dim3(1), 0, s, mm, lohi);
-    hipLaunchKernelGGL(zoom_stack_kernel, grid_for(nout), dim3(256), 0, s, filtered, H, W, oh, ow, r0, r1, wr0, wr1, c0, c1, wc0, wc1, lohi, zoomed, nout);
+    hipLaunchKernelGGL(minmax_decode_kernel, dim3(n), dim3(1), 0, s, mm, lohi);
+    hipLaunchKernelGGL(zoom_stack_kernel, grid_for(n * nout), dim3(256), 0, s, filtered, Z, H, W, oh, ow, r0, r1, wr0, wr1, c0, c1, wc0, wc1, lohi, zoomed,
+                       n * nout);
     if (vol) {                // vol == nullptr: the caller wants the resized values themselves (tmat_resize_aa_u16)
-        hipLaunchKernelGGL(minmax_init_kernel, dim3(1), dim3(1), 0, s, mm);
+        hipLaunchKernelGGL(minmax_init_kernel, dim3(n), dim3(1), 0, s, mm);
         hipLaunchKernelGGL((minmax_all_kernel<double>), rgrid_out, dim3(256), 0, s, zoomed, nout, mm);
-        hipLaunchKernelGGL(minmax_decode_kernel, dim3(1), dim3(1), 0, s, mm, lohi + 2);
-        hipLaunchKernelGGL(rescale01_f64_kernel, grid_for(nout), dim3(256), 0, s, zoomed, nout, lohi + 2, vol);
+        hipLaunchKernelGGL(minmax_decode_kernel, dim3(n), dim3(1), 0, s, mm, lohi + 2 * (size_t)n);
+        hipLaunchKernelGGL(rescale01_f64_kernel, grid_for(n * nout), dim3(256), 0, s, zoomed, n * nout, nout, lohi + 2 * (size_t)n, vol);
     }
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // ---- z4: Sato ----------------------------------------------------------------------------------------------------------------
 // im = max(vol[z], vol[z+1]); gradient form (scikit-image <= 0.19): invert = 1 - im; gaussian-derivative form (>= 0.20): -im
-__global__ void pairmax_kernel(const float *__restrict__ vol, size_t npx, size_t total, int negate, float *__restrict__ out)
+// n stacks in one launch: out (n, Z - 1, npx) from vol (n, Z, npx); per = (Z - 1) npx, the outputs of one stack
+__global__ void pairmax_kernel(const float *__restrict__ vol, size_t npx, size_t per, size_t total, int negate, float *__restrict__ out)
 {
     FLAT_LOOP(p, total) {
-        const float m = fmaxf(vol[p], vol[p + npx]);
+        const size_t q = p + (p / per) * npx;           // a stack has one slice more than it has pairs
+        const float m = fmaxf(vol[q], vol[q + npx]);
         out[p] = negate ? -m : 1.0f - m;
     }
 }
@@ -308,10 +323,10 @@ __global__ void eig_derivative_kernel(const float *__restrict__ hrr, const float
         best[p] = fmaxf(b, v);
     }
 }
-void launch_pairmax(const float *vol, int Zm1, size_t npx, int negate, float *out, hipStream_t s)
+void launch_pairmax(const float *vol, int n, int Zm1, size_t npx, int negate, float *out, hipStream_t s)
 {
-    const size_t total = (size_t)Zm1 * npx;
-    hipLaunchKernelGGL(pairmax_kernel, grid_for(total), dim3(256), 0, s, vol, npx, total, negate, out);
+    const size_t per = (size_t)Zm1 * npx, total = (size_t)n * per;
+    hipLaunchKernelGGL(pairmax_kernel, grid_for(total), dim3(256), 0, s, vol, npx, per, total, negate, out);
 }
 void launch_prep_single(const float *img, size_t total, int negate, float *out, hipStream_t s)
 {
@@ -336,8 +351,11 @@ __global__ void unsharp_kernel(const float *__restrict__ v, const float *__restr
         out[p] = fminf(fmaxf(r, 0.0f), 1.0f);
     }
 }
+// blockIdx.y = the stack: v (n, Z, npx) -> out (n, npx)
 __global__ void zmax_kernel(const float *__restrict__ v, int Z, size_t npx, float *__restrict__ out)
 {
+    v += (size_t)blockIdx.y * Z * npx;
+    out += (size_t)blockIdx.y * npx;
     FLAT_LOOP(p, npx) {
         float m = v[p];
         for (int z = 1; z < Z; z++) m = fmaxf(m, v[(size_t)z * npx + p]);
@@ -348,9 +366,9 @@ void launch_unsharp(const float *v, const float *blurred, float amount, size_t t
 {
     hipLaunchKernelGGL(unsharp_kernel, grid_for(total), dim3(256), 0, s, v, blurred, amount, total, out);
 }
-void launch_zmax(const float *v, int Z, size_t npx, float *out, hipStream_t s)
+void launch_zmax(const float *v, int n, int Z, size_t npx, float *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(zmax_kernel, grid_for(npx), dim3(256), 0, s, v, Z, npx, out);
+    hipLaunchKernelGGL(zmax_kernel, dim3(grid_for(npx).x, n), dim3(256), 0, s, v, Z, npx, out);
 }
 
 // ---- z6: canny(sigma = 0) -------------------------------------------------------------------------------------------------
@@ -376,6 +394,9 @@ __global__ void canny_nms_kernel(const double *__restrict__ isob, const double *
                                  uint8_t *__restrict__ low, uint8_t *__restrict__ high)
 {
     const int npx = H * W;
+    // blockIdx.y = the image: the neighbours a pixel reads (mg) stay inside its own image, rows 0 and H - 1 are never local maxima
+    const size_t base = (size_t)blockIdx.y * npx;
+    isob += base; jsob += base; mag_out += base; low += base; high += base;
     FLAT_LOOP(p, (size_t)npx) {
         const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
         const double is_ = isob[p], js = jsob[p];
@@ -408,44 +429,52 @@ __global__ void canny_nms_kernel(const double *__restrict__ isob, const double *
         high[p] = lm && m >= 0.2;
     }
 }
-// hysteresis: components of `low` (labels L) that hold a `high` pixel
+// hysteresis: components of `low` (labels L) that hold a `high` pixel.  blockIdx.y = the image: launch_ccl's labels are pixel indices
+// inside the image, so the flag table is per image too
 __global__ void flag_roots_kernel(const uint8_t *__restrict__ on, const int *__restrict__ L, int npx, int *__restrict__ flag)
 {
-    FLAT_LOOP(p, (size_t)npx) if (on[p] && L[p] >= 0) flag[L[p]] = 1;
+    const size_t base = (size_t)blockIdx.y * npx;
+    FLAT_LOOP(p, (size_t)npx) if (on[base + p] && L[base + p] >= 0) flag[base + L[base + p]] = 1;
 }
 __global__ void keep_flagged_kernel(const int *__restrict__ L, const int *__restrict__ flag, int npx, uint8_t *__restrict__ out)
 {
-    FLAT_LOOP(p, (size_t)npx) out[p] = L[p] >= 0 && flag[L[p]];
+    const size_t base = (size_t)blockIdx.y * npx;
+    FLAT_LOOP(p, (size_t)npx) out[base + p] = L[base + p] >= 0 && flag[base + L[base + p]];
 }
 
-int canny0_dev(const float *img, int H, int W, const CannyWs &ws, uint8_t *edges, hipStream_t s)
+int canny0_dev(const float *img, int k, int H, int W, const CannyWs &ws, uint8_t *edges, hipStream_t s)
 {
-    const size_t n = (size_t)H * W;
+    const size_t n = (size_t)k * H * W;
     hipLaunchKernelGGL(canny_norm_kernel, grid_for(n), dim3(256), 0, s, img, n, ws.sm);
-    return canny_core_dev(H, W, ws, edges, s);
+    return canny_core_dev(k, H, W, ws, edges, s);
 }
 
-// feature/_canny.py after the smoothing step, from the smoothed image in ws.sm (f64)
-int canny_core_dev(int H, int W, const CannyWs &ws, uint8_t *edges, hipStream_t s)
+// feature/_canny.py after the smoothing step, from the smoothed images in ws.sm (k, H, W) f64: the Sobel lines are per image (`outer`
+// of the correlations), the labels, the flag table and the neighbourhoods of the suppression too (blockIdx.y)
+int canny_core_dev(int k, int H, int W, const CannyWs &ws, uint8_t *edges, hipStream_t s)
 {
     const size_t n = (size_t)H * W;
+    const dim3 grid(grid_for(n).x, k);
     // ndi.sobel(axis): correlate1d [-1, 0, 1] along the axis, then [1, 2, 1] along the other; 'reflect'
-    launch_corr1d_f64(ws.sm, ws.t0, (size_t)H, W, 1, ws.w_diff, 1, -1, EXT_REFLECT, s);       // jsobel: axis 1
-    launch_corr1d_f64(ws.t0, ws.js, 1, H, W, ws.w_smooth, 1, 1, EXT_REFLECT, s);
-    launch_corr1d_f64(ws.sm, ws.t0, 1, H, W, ws.w_diff, 1, -1, EXT_REFLECT, s);       // isobel: axis 0
-    launch_corr1d_f64(ws.t0, ws.is_, (size_t)H, W, 1, ws.w_smooth, 1, 1, EXT_REFLECT, s);
-    hipLaunchKernelGGL(canny_nms_kernel, grid_for(n), dim3(256), 0, s, ws.is_, ws.js, H, W, ws.mag, ws.low, ws.high);
-    launch_ccl(ws.low, 1, H, W, ws.L, s);
-    if (hipMemsetAsync(ws.flag, 0, n * sizeof(int), s) != hipSuccess) return -2;
-    hipLaunchKernelGGL(flag_roots_kernel, grid_for(n), dim3(256), 0, s, ws.high, ws.L, (int)n, ws.flag);
-    hipLaunchKernelGGL(keep_flagged_kernel, grid_for(n), dim3(256), 0, s, ws.L, ws.flag, (int)n, edges);
+    launch_corr1d_f64(ws.sm, ws.t0, (size_t)k * H, W, 1, ws.w_diff, 1, -1, EXT_REFLECT, s);       // jsobel: axis 1
+    launch_corr1d_f64(ws.t0, ws.js, (size_t)k, H, W, ws.w_smooth, 1, 1, EXT_REFLECT, s);
+    launch_corr1d_f64(ws.sm, ws.t0, (size_t)k, H, W, ws.w_diff, 1, -1, EXT_REFLECT, s);       // isobel: axis 0
+    launch_corr1d_f64(ws.t0, ws.is_, (size_t)k * H, W, 1, ws.w_smooth, 1, 1, EXT_REFLECT, s);
+    hipLaunchKernelGGL(canny_nms_kernel, grid, dim3(256), 0, s, ws.is_, ws.js, H, W, ws.mag, ws.low, ws.high);
+    launch_ccl(ws.low, k, H, W, ws.L, s);
+    if (hipMemsetAsync(ws.flag, 0, (size_t)k * n * sizeof(int), s) != hipSuccess) return -2;
+    hipLaunchKernelGGL(flag_roots_kernel, grid, dim3(256), 0, s, ws.high, ws.L, (int)n, ws.flag);
+    hipLaunchKernelGGL(keep_flagged_kernel, grid, dim3(256), 0, s, ws.L, ws.flag, (int)n, edges);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // ---- z7: eccentricity x equivalent diameter per 8-connected component ------------------------------------------------------
 // integer moments per root label: [area, sum r, sum c, sum r^2, sum c^2, sum r c]
+// blockIdx.y = the image (labels and moment table of its own)
 __global__ void moments_kernel(const int *__restrict__ L, int W, int npx, unsigned long long *__restrict__ mom)
 {
+    L += (size_t)blockIdx.y * npx;
+    mom += (size_t)blockIdx.y * npx * 6;
     FLAT_LOOP(p, (size_t)npx) {
         const int l = L[p];
         if (l < 0) continue;
@@ -461,6 +490,9 @@ __global__ void moments_kernel(const int *__restrict__ L, int W, int npx, unsign
 __global__ void ecc_diam_kernel(const int *__restrict__ L, const unsigned long long *__restrict__ mom, int npx, double thresh,
                                 const uint8_t *__restrict__ mask, uint8_t *__restrict__ out, double *__restrict__ val_out)
 {
+    const size_t base = (size_t)blockIdx.y * npx;
+    L += base; mom += base * 6; mask += base; out += base;
+    if (val_out) val_out += base;
     FLAT_LOOP(p, (size_t)npx) {
         const int l = L[p];
         double v = 0.0;
@@ -481,13 +513,14 @@ __global__ void ecc_diam_kernel(const int *__restrict__ L, const unsigned long l
         out[p] = mask[p] && v > thresh;
     }
 }
-int ecc_diam_select_dev(const uint8_t *mask, int H, int W, double thresh, int *L, unsigned long long *mom, uint8_t *out, double *val_out, hipStream_t s)
+int ecc_diam_select_dev(const uint8_t *mask, int k, int H, int W, double thresh, int *L, unsigned long long *mom, uint8_t *out, double *val_out, hipStream_t s)
 {
     const size_t n = (size_t)H * W;
-    launch_ccl(mask, 1, H, W, L, s);
-    if (hipMemsetAsync(mom, 0, n * 6 * sizeof(unsigned long long), s) != hipSuccess) return -2;
-    hipLaunchKernelGGL(moments_kernel, grid_for(n), dim3(256), 0, s, L, W, (int)n, mom);
-    hipLaunchKernelGGL(ecc_diam_kernel, grid_for(n), dim3(256), 0, s, L, mom, (int)n, thresh, mask, out, val_out);
+    const dim3 grid(grid_for(n).x, k);
+    launch_ccl(mask, k, H, W, L, s);
+    if (hipMemsetAsync(mom, 0, (size_t)k * n * 6 * sizeof(unsigned long long), s) != hipSuccess) return -2;
+    hipLaunchKernelGGL(moments_kernel, grid, dim3(256), 0, s, L, W, (int)n, mom);
+    hipLaunchKernelGGL(ecc_diam_kernel, grid, dim3(256), 0, s, L, mom, (int)n, thresh, mask, out, val_out);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -502,8 +535,11 @@ __global__ void where_zero_kernel(const uint8_t *__restrict__ m, const float *__
 }
 // one round of compute_branches.py:283-294: a pixel joins when some mask neighbour is not brighter than it, none is brighter,
 // and it is brighter than 0.01; all tests read the mask of the round's start
+// blockIdx.y = the image: the 8 neighbours are tested against the image's own border
 __global__ void grow_kernel(const uint8_t *__restrict__ m, const float *__restrict__ v, int H, int W, uint8_t *__restrict__ out)
 {
+    const size_t base = (size_t)blockIdx.y * H * W;
+    m += base; v += base; out += base;
     FLAT_LOOP(p, (size_t)H * W) {
         const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
         bool lo = false, hi = false;
@@ -528,6 +564,8 @@ __global__ void andnot_kernel(const uint8_t *__restrict__ a, const uint8_t *__re
 // grey_erosion default mode)
 __global__ void morph_kernel(const uint8_t *__restrict__ m, int H, int W, const int *__restrict__ off, int noff, int erode, uint8_t *__restrict__ out)
 {
+    const size_t base = (size_t)blockIdx.y * H * W;      // the image: the reflection is at its own border
+    m += base; out += base;
     FLAT_LOOP(p, (size_t)H * W) {
         const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
         bool acc = erode != 0;
@@ -544,17 +582,17 @@ void launch_where(const uint8_t *m, const float *a, const float *b, size_t n, fl
     if (b) hipLaunchKernelGGL(where_f32_kernel, grid_for(n), dim3(256), 0, s, m, a, b, n, out);
     else hipLaunchKernelGGL(where_zero_kernel, grid_for(n), dim3(256), 0, s, m, a, n, out);
 }
-void launch_grow(const uint8_t *m, const float *v, int H, int W, uint8_t *out, hipStream_t s)
+void launch_grow(const uint8_t *m, const float *v, int k, int H, int W, uint8_t *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(grow_kernel, grid_for((size_t)H * W), dim3(256), 0, s, m, v, H, W, out);
+    hipLaunchKernelGGL(grow_kernel, dim3(grid_for((size_t)H * W).x, k), dim3(256), 0, s, m, v, H, W, out);
 }
 void launch_andnot(const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out, hipStream_t s)
 {
     hipLaunchKernelGGL(andnot_kernel, grid_for(n), dim3(256), 0, s, a, b, n, out);
 }
-void launch_morph(const uint8_t *m, int H, int W, const int *off_dev, int noff, int erode, uint8_t *out, hipStream_t s)
+void launch_morph(const uint8_t *m, int k, int H, int W, const int *off_dev, int noff, int erode, uint8_t *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(morph_kernel, grid_for((size_t)H * W), dim3(256), 0, s, m, H, W, off_dev, noff, erode, out);
+    hipLaunchKernelGGL(morph_kernel, dim3(grid_for((size_t)H * W).x, k), dim3(256), 0, s, m, H, W, off_dev, noff, erode, out);
 }
 
 }  // namespace tmat

@@ -9,10 +9,14 @@
 #include "morph.h"
 #include "sato.h"
 #include "wellmask.h"
+#include "host_par.h"
 
 #include <algorithm>
 #include <cmath>
+#include <chrono>
+#include <cstdio>
 #include <cstring>
+#include <thread>
 
 namespace tmat {
 
@@ -89,13 +93,16 @@ const double SATO_SIGMAS[10] = {1, 2, 3, 4, 5, 7, 9, 11, 13, 15};       // compu
 
 }  // namespace
 
-// vol (Z, h, w) f32 on the device -> field (h, w) f32 on the device; stage copies go to the host arrays of `st` that are non-null
-int vessel_field_dev(Ctx *c, const float *vol, int Z, int h, int w, int form, float *field, const tmat_vessel_stages *st, hipStream_t s)
+// n volumes (n, Z, h, w) f32 on the device -> n fields (n, h, w) f32 on the device, one launch set for all of them; stage copies go to
+// the host arrays of `st` that are non-null (each with a leading n).  Every per-image quantity -- labels, moment tables, convergence
+// flags, borders of the neighbourhood stages -- is indexed by the volume; the Sato chain sees n (Z - 1) independent images.
+int vessel_field_dev(Ctx *c, const float *vol, int n, int Z, int h, int w, int form, float *field, const tmat_vessel_stages *st, hipStream_t s)
 {
+    if (n < 1) { set_error("vessel field: no volume"); return TMAT_E_ARG; }
     if (Z < 2) { set_error("vessel field: a Z stack needs at least 2 slices"); return TMAT_E_ARG; }
     if (!thin_dev_supported(h, w)) { set_error("vessel field: image too large for the device thinning kernel"); return TMAT_E_ARG; }
     const int D = Z - 1;
-    const size_t npx = (size_t)h * w, nv = (size_t)D * npx;
+    const size_t px1 = (size_t)h * w, npx = (size_t)n * px1, nv = (size_t)D * npx;     // npx, nv: over the n volumes
     DevScope A(c->ws_pool, s);
     float *x = A.pooled<float>(nv), *vess = A.pooled<float>(nv), *bufs[7];
     for (float *&b : bufs) b = A.pooled<float>(nv);
@@ -106,10 +113,10 @@ int vessel_field_dev(Ctx *c, const float *vol, int Z, int h, int w, int form, fl
     double *tabs = A.pooled<double>(6);
     uint8_t *edges = A.pooled<uint8_t>(npx), *skel = A.pooled<uint8_t>(npx), *m0 = A.pooled<uint8_t>(npx), *m1 = A.pooled<uint8_t>(npx), *filt = A.pooled<uint8_t>(npx);
     double *dist = A.pooled<double>(npx);
-    int *edt_g = A.pooled<int>(npx), *anyz = A.pooled<int>(4);
+    int *edt_g = A.pooled<int>(npx), *anyz = A.pooled<int>(std::max(n, 4));
     unsigned long long *mom = A.pooled<unsigned long long>(npx * 6);
     int *offs = A.pooled<int>(2 * (13 + 9));
-    void *mws = A.pooled_bytes(morph_workspace_bytes(1, h, w));
+    void *mws = A.pooled_bytes(morph_workspace_bytes(n, h, w));
     if (!A.ok) return TMAT_E_HIP;
     {
         std::vector<int> o;
@@ -123,51 +130,51 @@ int vessel_field_dev(Ctx *c, const float *vol, int Z, int h, int w, int form, fl
     const bool deriv = form == TMAT_SATO_GAUSSIAN_DERIVATIVES;
 
     // z4: Sato of max(slice z, slice z + 1), all D pairs in one launch per pass
-    launch_pairmax(vol, D, npx, deriv ? 1 : 0, x, s);
-    if (!sato_dev(c, x, D, h, w, SATO_SIGMAS, 10, form, bufs, vess, s)) { set_error("vessel field: Sato stage failed"); return TMAT_E_HIP; }
+    launch_pairmax(vol, n, D, px1, deriv ? 1 : 0, x, s);
+    if (!sato_dev(c, x, n * D, h, w, SATO_SIGMAS, 10, form, bufs, vess, s)) { set_error("vessel field: Sato stage failed"); return TMAT_E_HIP; }
     if (st) A.d2h(st->vess, vess, nv * 4);
     // z5: unsharp_mask(volume, radius 2, amount 2): 3-D gaussian ('reflect', truncate 4) over Z, rows, columns
     float *sharp = x;                                                        // x is free from here on
-    if (!gauss_pass_f32(c, vess, bufs[0], Pass{2.0, 0, D, (int)npx, 1}, 4.0, EXT_REFLECT, s) ||
-        !gauss_pass_f32(c, bufs[0], bufs[1], Pass{2.0, 0, h, w, (size_t)D}, 4.0, EXT_REFLECT, s) ||
-        !gauss_pass_f32(c, bufs[1], bufs[0], Pass{2.0, 0, w, 1, (size_t)D * h}, 4.0, EXT_REFLECT, s)) return TMAT_E_HIP;
+    if (!gauss_pass_f32(c, vess, bufs[0], Pass{2.0, 0, D, (int)px1, (size_t)n}, 4.0, EXT_REFLECT, s) ||
+        !gauss_pass_f32(c, bufs[0], bufs[1], Pass{2.0, 0, h, w, (size_t)n * D}, 4.0, EXT_REFLECT, s) ||
+        !gauss_pass_f32(c, bufs[1], bufs[0], Pass{2.0, 0, w, 1, (size_t)n * D * h}, 4.0, EXT_REFLECT, s)) return TMAT_E_HIP;
     launch_unsharp(vess, bufs[0], 2.0f, nv, sharp, s);
-    launch_zmax(sharp, D, npx, vessels, s);
+    launch_zmax(sharp, n, D, px1, vessels, s);
     if (st) { A.d2h(st->sharp, sharp, nv * 4); A.d2h(st->vessels, vessels, npx * 4); }
     // z6: canny
-    if (canny0_dev(vessels, h, w, cw, edges, s)) { set_error("vessel field: canny stage failed"); return TMAT_E_HIP; }
+    if (canny0_dev(vessels, n, h, w, cw, edges, s)) { set_error("vessel field: canny stage failed"); return TMAT_E_HIP; }
     if (st) A.d2h(st->edges, edges, npx);
     // z7: medial axis of the edges; keep skeleton components with eccentricity * equivalent diameter > 3.5
-    launch_edt(edges, 1, h, w, edt_g, nullptr, anyz, dist, s);
-    { int rc = medial_thin_batch_dev(c, edges, dist, 1, h, w, skel, s); if (rc) return rc; }
-    if (ecc_diam_select_dev(skel, h, w, 3.5, cw.L, mom, m0, nullptr, s)) return TMAT_E_HIP;
+    launch_edt(edges, n, h, w, edt_g, nullptr, anyz, dist, s);
+    { int rc = medial_thin_batch_dev(c, edges, dist, n, h, w, skel, s); if (rc) return rc; }
+    if (ecc_diam_select_dev(skel, n, h, w, 3.5, cw.L, mom, m0, nullptr, s)) return TMAT_E_HIP;
     if (st) { A.d2h(st->skel, skel, npx); A.d2h(st->mask_sel, m0, npx); }
     // z8: three masked blurs of the projection
     if (!A.check(hipMemcpyAsync(vcur, vessels, npx * 4, hipMemcpyDeviceToDevice, s), "D2D")) return TMAT_E_HIP;
     for (int it = 0; it < 3; it++) {
-        if (!gauss2d_f32(c, vcur, vtmp, vblur, 1, h, w, 1.0, 0, 0, 4.0, EXT_NEAREST, s)) return TMAT_E_HIP;
+        if (!gauss2d_f32(c, vcur, vtmp, vblur, n, h, w, 1.0, 0, 0, 4.0, EXT_NEAREST, s)) return TMAT_E_HIP;
         launch_where(m0, vblur, vcur, npx, vtmp, s);
         std::swap(vcur, vtmp);
     }
     //     ten region-growing rounds, mask &= ~edges, closing with disk(2)
     uint8_t *ma = m0, *mb = m1;
-    for (int it = 0; it < 10; it++) { launch_grow(ma, vcur, h, w, mb, s); std::swap(ma, mb); }
+    for (int it = 0; it < 10; it++) { launch_grow(ma, vcur, n, h, w, mb, s); std::swap(ma, mb); }
     if (st) A.d2h(st->grown, ma, npx);
     launch_andnot(ma, edges, npx, mb, s);
-    launch_morph(mb, h, w, offs, 13, 0, ma, s);
-    launch_morph(ma, h, w, offs, 13, 1, mb, s);
+    launch_morph(mb, n, h, w, offs, 13, 0, ma, s);
+    launch_morph(ma, n, h, w, offs, 13, 1, mb, s);
     if (st) A.d2h(st->closed, mb, npx);
     // z9: filter_branch_seg_mask(mask, None, False), dilation with square(3), mask the sharpened projection, gaussian
-    if (filter_mask_dev(nullptr, mb, 1, h, w, 0, 0, mws, filt, nullptr, s)) return TMAT_E_HIP;
-    int *conv = A.host<int>();
-    A.d2h(conv, morph_done_flags(mws, 1, h, w), sizeof(int));
-    launch_morph(filt, h, w, offs + 26, 9, 0, ma, s);
+    if (filter_mask_dev(nullptr, mb, n, h, w, 0, 0, mws, filt, nullptr, s)) return TMAT_E_HIP;
+    int *conv = A.host<int>(n);
+    A.d2h(conv, morph_done_flags(mws, n, h, w), n * sizeof(int));
+    launch_morph(filt, n, h, w, offs + 26, 9, 0, ma, s);
     launch_where(ma, vessels, nullptr, npx, vtmp, s);
-    if (!gauss2d_f32(c, vtmp, vblur, field, 1, h, w, 1.0, 0, 0, 4.0, EXT_NEAREST, s)) return TMAT_E_HIP;
+    if (!gauss2d_f32(c, vtmp, vblur, field, n, h, w, 1.0, 0, 0, 4.0, EXT_NEAREST, s)) return TMAT_E_HIP;
     if (st) A.d2h(st->filt, filt, npx);
     if (A.finish()) return TMAT_E_HIP;
     if (hipGetLastError() != hipSuccess) { set_error("vessel field: kernel launch failed"); return TMAT_E_HIP; }
-    if (!*conv) { set_error("vessel field: thinning did not converge"); return TMAT_E_HIP; }
+    for (int i = 0; i < n; i++) if (!conv[i]) { set_error("vessel field: thinning did not converge"); return TMAT_E_HIP; }
     return TMAT_OK;
 }
 
@@ -175,13 +182,13 @@ int vessel_field_dev(Ctx *c, const float *vol, int Z, int h, int w, int form, fl
 // skimage.transform.resize(stack, (Z, oh, ow), order=1, preserve_range=True, anti_aliasing=True) of an integer stack (scikit-image
 // >= 0.19: ndi.gaussian_filter(sigma (factor - 1) / 2, 'mirror') + ndi.zoom(order 1, grid_mode) on the 3-D array, the Z axis with sigma 0
 // and zoom 1), clipped to the stack's range: the float64 values in `zoomed` (device, Z oh ow); with `vol` also rescale_intensity(0..1) over
-// the whole stack as float32
-int stack_resize_aa_dev(Ctx *c, const uint16_t *stack, int Z, int H, int W, int oh, int ow, double *zoomed, float *vol, hipStream_t s)
+// the whole stack as float32.  n stacks (n, Z, H, W) go through one launch set; the clip range and the rescale are per stack
+int stack_resize_aa_dev(Ctx *c, const uint16_t *stack, int n, int Z, int H, int W, int oh, int ow, double *zoomed, float *vol, hipStream_t s)
 {
-    const size_t nin = (size_t)Z * H * W;
+    const size_t nin = (size_t)n * Z * H * W, NZ = (size_t)n * Z;
     DevScope A(c->ws_pool, s);
-    double *fa = A.pooled<double>(nin), *fb = A.pooled<double>(nin), *lohi = A.pooled<double>(4);
-    unsigned long long *mm = A.pooled<unsigned long long>(2);
+    double *fa = A.pooled<double>(nin), *fb = A.pooled<double>(nin), *lohi = A.pooled<double>(4 * (size_t)n);
+    unsigned long long *mm = A.pooled<unsigned long long>(2 * (size_t)n);
     std::vector<int> r0, r1, c0, c1;
     std::vector<double> wr0, wr1, wc0, wc1;
     zoom_axis_table(H, oh, r0, r1, wr0, wr1);
@@ -200,33 +207,34 @@ int stack_resize_aa_dev(Ctx *c, const uint16_t *stack, int Z, int H, int W, int 
         const GaussTable &t = gauss_table(c, s0, 0, gauss_radius(s0, 4.0));
         const double *wd = table_dev(c, t);
         if (!wd) return TMAT_E_HIP;
-        launch_corr1d_u16_f64(stack, fa, (size_t)Z, H, W, wd, t.r, t.sym, EXT_MIRROR, s);
+        launch_corr1d_u16_f64(stack, fa, NZ, H, W, wd, t.r, t.sym, EXT_MIRROR, s);
         cur = fa;
     }
     if (s1 > 1e-15) {
         const GaussTable &t = gauss_table(c, s1, 0, gauss_radius(s1, 4.0));
         const double *wd = table_dev(c, t);
         if (!wd) return TMAT_E_HIP;
-        if (cur) launch_corr1d_f64(cur, fb, (size_t)Z * H, W, 1, wd, t.r, t.sym, EXT_MIRROR, s);
-        else launch_corr1d_u16_f64(stack, fb, (size_t)Z * H, W, 1, wd, t.r, t.sym, EXT_MIRROR, s);
+        if (cur) launch_corr1d_f64(cur, fb, NZ * H, W, 1, wd, t.r, t.sym, EXT_MIRROR, s);
+        else launch_corr1d_u16_f64(stack, fb, NZ * H, W, 1, wd, t.r, t.sym, EXT_MIRROR, s);
         cur = fb;
     }
     if (!cur) {               // no smoothing at all (an image at most as wide as the target): the zoom reads the stack as f64
         double *w_id = lohi;   // borrowed for a moment: a 1-tap identity kernel
         if (!A.h2d(w_id, A.keep(std::vector<double>{1.0}), 8)) return TMAT_E_HIP;
-        launch_corr1d_u16_f64(stack, fa, (size_t)Z * H, W, 1, w_id, 0, 1, EXT_MIRROR, s);
+        launch_corr1d_u16_f64(stack, fa, NZ * H, W, 1, w_id, 0, 1, EXT_MIRROR, s);
         cur = fa;
     }
-    if (stack_zoom_rescale_dev(cur, stack, Z, H, W, oh, ow, dr0, dr1, dwr0, dwr1, dc0, dc1, dwc0, dwc1, zoomed, mm, lohi, vol, s)) {
+    if (stack_zoom_rescale_dev(cur, stack, n, Z, H, W, oh, ow, dr0, dr1, dwr0, dwr1, dc0, dc1, dwc0, dwc1, zoomed, mm, lohi, vol, s)) {
         set_error("stack resize: kernel launch failed");
         return TMAT_E_HIP;
     }
     return A.finish();
 }
 
-int stack_prepare_dev(Ctx *c, uint16_t *stack, int Z, int H, int W, int oh, int ow, float *vol, hipStream_t s)
+// n stacks (n, Z, H, W) u16 on the device (overwritten) -> vol (n, Z, oh, ow) f32 on the device
+int stack_prepare_dev(Ctx *c, uint16_t *stack, int n, int Z, int H, int W, int oh, int ow, float *vol, hipStream_t s)
 {
-    const size_t nin = (size_t)Z * H * W, nout = (size_t)Z * oh * ow;
+    const size_t NZ = (size_t)n * Z, nin = NZ * H * W, nout = NZ * oh * ow;
     DevScope A(c->ws_pool, s);
     double *fa = A.pooled<double>(nin), *zoomed = A.pooled<double>(nout);
     if (!A.ok) return TMAT_E_HIP;
@@ -234,10 +242,174 @@ int stack_prepare_dev(Ctx *c, uint16_t *stack, int Z, int H, int W, int oh, int 
     const GaussTable &g1 = gauss_table(c, 1.0, 0, gauss_radius(1.0, 4.0));
     const double *w1 = table_dev(c, g1);
     if (!w1) return TMAT_E_HIP;
-    launch_corr1d_u16_f64(stack, fa, (size_t)Z, H, W, w1, g1.r, g1.sym, EXT_NEAREST, s);
-    launch_corr1d_f64_u16(fa, stack, (size_t)Z * H, W, 1, w1, g1.r, g1.sym, EXT_NEAREST, s);
-    // z2 + z3: anti-aliased resize, rescale to 0..1 over the whole stack
-    return stack_resize_aa_dev(c, stack, Z, H, W, oh, ow, zoomed, vol, s);
+    launch_corr1d_u16_f64(stack, fa, NZ, H, W, w1, g1.r, g1.sym, EXT_NEAREST, s);
+    launch_corr1d_f64_u16(fa, stack, NZ * H, W, 1, w1, g1.r, g1.sym, EXT_NEAREST, s);
+    // z2 + z3: anti-aliased resize, rescale to 0..1 over each whole stack
+    return stack_resize_aa_dev(c, stack, n, Z, H, W, oh, ow, zoomed, vol, s);
+}
+
+// ---- batch entry point of the branch: K stacks per pass, the host graph stage of pass p - 1 beside the device stages of pass p ----------
+
+// Device bytes one stack of a pass holds at the pass's peak, from the blocks the stages take (DevScope::pooled in tmat_analyze_stack_batch,
+// stack_prepare_dev, stack_resize_aa_dev, vessel_field_dev, the DMT front end).  Two phases never overlap, the larger one counts:
+//   prepare   u16 stack, prepared volume, field + the per-slice gaussian's f64 plane, the zoomed f64 volume and the resize's two f64 planes
+//   field     u16 stack, prepared volume, field + nine (Z - 1) f32 volumes, the 2-D planes of canny / medial axis / mask stages, then the tail
+// The three Z H W f64 planes of the prepare phase dominate for any stack larger than its field.
+size_t stack_pass_bytes(int Z, int H, int W, int fh, int fw)
+{
+    const size_t nin = (size_t)Z * H * W, npx = (size_t)fh * fw, nE = dmt_edge_count(fh, fw);
+    const size_t held = nin * 2 + (size_t)Z * npx * 4 + npx * 4 + (size_t)H * W * 3;      // + projection and its picture
+    const size_t prepare = nin * 8 * 3 + (size_t)Z * npx * 8;
+    const size_t planes = npx * (4 * 4 + 5 * 8 + 2 + 2 * 4 + 5 + 8 + 4 + 6 * 8) + morph_workspace_bytes(1, fh, fw) + thin_workspace_bytes(1, fh, fw) + npx * 8;
+    const size_t field = (size_t)(Z - 1) * npx * 4 * 9 + planes;
+    const size_t tail = npx * 4 + nE * (4 + 1 + 4) + dmt_workspace_bytes(1, fh, fw) + dmt_sweep_workspace_bytes(1, fh, fw);
+    return held + std::max(prepare, std::max(field, tail));
+}
+
+// stacks per pass: min(n, TMAT_STACK_PASS_MAX, budget / bytes per stack), at least 1; pass_stacks > 0 overrides
+int stack_pass_count(int n, size_t bytes_per_stack, int pass_stacks)
+{
+    if (pass_stacks > 0) return std::max(1, std::min(n, pass_stacks));
+    const size_t fit = bytes_per_stack ? (size_t)TMAT_STACK_PASS_BUDGET / bytes_per_stack : (size_t)TMAT_STACK_PASS_MAX;
+    return (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n, TMAT_STACK_PASS_MAX), fit));
+}
+
+namespace {
+
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// pinned result buffers of one pass slot: what the host graph stage reads while the next pass fills the other slot
+struct StackSlot { float *f255; int32_t *ids; int *m; uint8_t *kind; float *pers; };
+
+bool ensure_stack_slots(Ctx *c, int K, size_t npx, size_t nE, StackSlot sl[2])
+{
+    const size_t need[5] = {(size_t)K * npx * 4, (size_t)K * nE * 4, (size_t)K * sizeof(int), (size_t)K * nE, (size_t)K * nE * 4};
+    bool fits = c->stack_host.ents.size() == 10;
+    for (int i = 0; fits && i < 10; i++) fits = c->stack_host.ents[i].bytes >= need[i % 5];
+    if (!fits) {
+        c->stack_host.free_all();
+        for (int i = 0; i < 10; i++) if (!c->stack_host.pinned(need[i % 5], "hipHostMalloc(stack pass results)")) { c->stack_host.free_all(); return false; }
+    }
+    for (int q = 0; q < 2; q++) {
+        const WsEnt *e = &c->stack_host.ents[5 * q];
+        sl[q] = StackSlot{(float *)e[0].p, (int32_t *)e[1].p, (int *)e[2].p, (uint8_t *)e[3].p, (float *)e[4].p};
+    }
+    return true;
+}
+
+struct StackJob {
+    std::thread th;
+    std::atomic<int> rc{0};
+    void join() { if (th.joinable()) th.join(); }
+};
+
+// host graph stage of one pass: DMT collect + MorseGraph statistics of every (threshold pair, stack) on the shared worker threads
+void stack_pass_host(const StackSlot sl, int k, int fh, int fw, const tmat_stack_opts o, const uint8_t *pruning, bool sweep_dev, tmat_row *rows, int n,
+                     StackJob *job, double *host_ms)
+{
+    const double t0 = now_ms();
+    const size_t npx = (size_t)fh * fw, nE = dmt_edge_count(fh, fw);
+    parallel_images(o.n_thresh * k, [&](int it) {
+        const int t = it / k, i = it - t * k;
+        const int cap_v = (int)npx + 4, cap_e = 3 * (int)npx + 4;
+        std::vector<int32_t> V((size_t)cap_v * 2), E((size_t)cap_e * 2);
+        int nv = 0, ne = 0;
+        int rc = dmt_graph_host_sorted(sl.f255 + i * npx, fh, fw, o.thresh[2 * t], o.thresh[2 * t + 1], sl.ids + i * nE, sl.m[i], V.data(), cap_v, E.data(),
+                                       cap_e, &nv, &ne, sweep_dev ? sl.kind + i * nE : nullptr, sweep_dev ? sl.pers + i * nE : nullptr);
+        tmat_row *row = rows + (size_t)t * n + i;
+        if (!rc)
+            rc = tmat_morse_stats(V.data(), nv, E.data(), ne, fh, fw, o.smoothing_window_px, o.min_branch_length_px, o.max_branch_length_px, o.remove_isolated,
+                                  pruning ? pruning + i * npx : nullptr, &row->count, &row->total_px, &row->avg_px, nullptr, 0);
+        if (rc) job->rc = rc;
+    });
+    *host_ms = now_ms() - t0;
+}
+
+bool hessian_ok(int h) { return h == TMAT_SATO_GAUSSIAN_DERIVATIVES || h == TMAT_SATO_GRADIENT; }
+
+}  // namespace
+
+int analyze_stack_batch(Ctx *c, const uint16_t *stacks, int n, int Z, int H, int W, const tmat_stack_opts &o, tmat_row *rows)
+{
+    const int fh = (int)std::nearbyint((double)H * ((double)o.ds_width / (double)W)), fw = (int)std::nearbyint((double)W * ((double)o.ds_width / (double)W));
+    if (fh < 2 || fw < 2) { set_error("tmat_analyze_stack_batch: downsampled shape is empty"); return TMAT_E_ARG; }
+    const size_t nin = (size_t)Z * H * W, hw = (size_t)H * W, npx = (size_t)fh * fw, nE = dmt_edge_count(fh, fw);
+    const int K = stack_pass_count(n, stack_pass_bytes(Z, H, W, fh, fw), o.pass_stacks), P = (n + K - 1) / K;
+    StackSlot slots[2];
+    if (!ensure_stack_slots(c, K, npx, nE, slots)) return TMAT_E_HIP;
+    for (int t = 0; t < o.n_thresh; t++)
+        for (int i = 0; i < n; i++) { tmat_row &r = rows[(size_t)t * n + i]; r.index = o.first_index + i; r.count = 0; r.total_px = 0; r.avg_px = 0; }
+    const bool sweep_dev = c->dmt_sweep_device;
+    hipStream_t s = c->stream;
+    StackJob jobs[2];
+    std::vector<double> gpu_ms(P, 0.0), host_ms(P, 0.0);
+    int rc = TMAT_OK;
+    for (int p = 0; p < P && !rc; p++) {
+        const int slot = p & 1, i0 = p * K, k = std::min(K, n - i0);
+        const double t0 = now_ms();
+        // every device stage of the pass in order on the handle's stream: passes never run side by side (the DMT sweep kernel's barrier
+        // between workgroups counts on having the chip), the overlap is with the HOST stage of the pass before
+        DevScope A(c->ws_pool, s);
+        uint16_t *ds = A.pooled_from(stacks + (size_t)i0 * nin, (size_t)k * nin);
+        float *vol = A.pooled<float>((size_t)k * Z * npx), *field = A.pooled<float>((size_t)k * npx);
+        if (!A.ok) { rc = TMAT_E_HIP; break; }
+        void *mm = (o.proj_pic_out || o.field_pic_out) ? A.pooled_bytes(vis_scratch_bytes(k)) : nullptr;
+        if (o.proj_pic_out) {
+            // compute_branches.py:228-229: save_vis of the max projection, taken before the per-slice gaussian overwrites the stack
+            uint16_t *proj = A.pooled<uint16_t>((size_t)k * hw);
+            uint8_t *pic = A.pooled<uint8_t>((size_t)k * hw);
+            if (!A.ok) { rc = TMAT_E_HIP; break; }
+            double *lo = vis_scratch_lo(mm, k);
+            if (zproj_dev(ds, k, Z, H, W, TMAT_ZPROJ_MAX, proj, s) || vis_minmax_dev(proj, TMAT_PIC_U16, k, hw, mm, s) ||
+                vis_picture_dev(proj, TMAT_PIC_U16, k, hw, lo, lo + k, pic, s)) { set_error("tmat_analyze_stack_batch: projection picture failed"); rc = TMAT_E_HIP; break; }
+            A.d2h(o.proj_pic_out + (size_t)i0 * hw, pic, (size_t)k * hw);
+        }
+        rc = stack_prepare_dev(c, ds, k, Z, H, W, fh, fw, vol, s);
+        if (!rc) rc = vessel_field_dev(c, vol, k, Z, fh, fw, o.hessian, field, nullptr, s);
+        if (rc) break;
+        if (o.fields_out) A.d2h(o.fields_out + (size_t)i0 * npx, field, (size_t)k * npx * 4);
+        if (o.field_pic_out) {      // :303 vesselness_image.png
+            uint8_t *pic = A.pooled<uint8_t>((size_t)k * npx);
+            if (!A.ok) { rc = TMAT_E_HIP; break; }
+            double *lo = vis_scratch_lo(mm, k);
+            if (vis_minmax_dev(field, TMAT_PIC_F32, k, npx, mm, s) || vis_picture_dev(field, TMAT_PIC_F32, k, npx, lo, lo + k, pic, s)) {
+                set_error("tmat_analyze_stack_batch: field picture failed"); rc = TMAT_E_HIP; break;
+            }
+            A.d2h(o.field_pic_out + (size_t)i0 * npx, pic, (size_t)k * npx);
+        }
+        // device front end of the tail for the k fields: rescale to 0..255 per image (:419), lower-star sort, the two persistence sweeps
+        float *f255 = A.pooled<float>((size_t)k * npx), *mnmx = A.pooled<float>(2 * (size_t)k);
+        int32_t *ids = A.pooled<int32_t>((size_t)k * nE);
+        int *m = A.pooled<int>(k);
+        void *dws = A.pooled_bytes(dmt_workspace_bytes(k, fh, fw));
+        uint8_t *dkind = sweep_dev ? A.pooled<uint8_t>((size_t)k * nE) : nullptr;
+        float *dpers = sweep_dev ? A.pooled<float>((size_t)k * nE) : nullptr;
+        void *sws = sweep_dev ? A.pooled_bytes(dmt_sweep_workspace_bytes(k, fh, fw)) : nullptr;
+        if (!A.ok) { rc = TMAT_E_HIP; break; }
+        launch_rescale255(field, k, (int)npx, mnmx, mnmx + k, f255, s);
+        if (dmt_sorted_edges_dev(f255, k, fh, fw, dws, ids, m, s)) { set_error("tmat_analyze_stack_batch: DMT front end failed"); rc = TMAT_E_HIP; break; }
+        if (sweep_dev && dmt_sweeps_dev(f255, ids, m, k, fh, fw, sws, dkind, dpers, s)) { set_error("tmat_analyze_stack_batch: device sweeps failed"); rc = TMAT_E_HIP; break; }
+        // the slot's host buffers are free once the job of the pass before last has ended
+        jobs[slot].join();
+        if (jobs[slot].rc) { rc = jobs[slot].rc; break; }
+        const StackSlot &sl = slots[slot];
+        A.d2h(sl.f255, f255, (size_t)k * npx * 4);
+        A.d2h(sl.ids, ids, (size_t)k * nE * sizeof(int32_t));
+        A.d2h(sl.m, m, (size_t)k * sizeof(int));
+        if (sweep_dev) { A.d2h(sl.kind, dkind, (size_t)k * nE); A.d2h(sl.pers, dpers, (size_t)k * nE * sizeof(float)); }
+        if (A.finish()) { rc = TMAT_E_HIP; break; }
+        gpu_ms[p] = now_ms() - t0;
+        jobs[slot].th = std::thread(stack_pass_host, sl, k, fh, fw, o, o.pruning_masks ? o.pruning_masks + (size_t)i0 * npx : nullptr, sweep_dev, rows + i0, n,
+                                    &jobs[slot], &host_ms[p]);
+    }
+    for (StackJob &j : jobs) { j.join(); if (j.rc && !rc) rc = j.rc; }
+    c->stack_trace.clear();
+    for (int p = 0; p < P; p++) c->stack_trace.push_back({gpu_ms[p], host_ms[p]});
+    static const bool trace = [] { const char *e = getenv("TMAT_TRACE"); return e && atoi(e) > 0; }();
+    if (trace)
+        for (int p = 0; p < P; p++)
+            fprintf(stderr, "[tmat] stack pass %d (%d stacks): device stages %.1f ms, host graph stage %.1f ms\n", p, std::min(K, n - p * K), gpu_ms[p], host_ms[p]);
+    return rc;
 }
 
 }  // namespace tmat
@@ -345,7 +517,7 @@ int tmat_canny_mask(tmat_handle hd, const uint8_t *mask, int H, int W, double si
     launch_corr1d_f64(pb, pt, 1, Hp, Wp, w, gt.r, gt.sym, EXT_NEAREST, s);
     launch_corr1d_f64(pt, pb, (size_t)Hp, Wp, 1, w, gt.r, gt.sym, EXT_NEAREST, s);
     launch_wm_crop_div(pa, pb, H, W, r, cw.sm, s);
-    if (canny_core_dev(H, W, cw, e, s)) { set_error("tmat_canny_mask: kernel launch failed"); return TMAT_E_HIP; }
+    if (canny_core_dev(1, H, W, cw, e, s)) { set_error("tmat_canny_mask: kernel launch failed"); return TMAT_E_HIP; }
     A.d2h(edges, e, npx);
     return A.finish();
 }
@@ -380,7 +552,7 @@ int tmat_stack_prepare(tmat_handle hd, const uint16_t *stack, int Z, int H, int 
     uint16_t *ds = A.pooled_from(stack, nin);
     float *dv = A.pooled<float>(nout);
     if (!A.ok) return TMAT_E_HIP;
-    int rc = stack_prepare_dev(c, ds, Z, H, W, out_h, out_w, dv, c->stream);
+    int rc = stack_prepare_dev(c, ds, 1, Z, H, W, out_h, out_w, dv, c->stream);
     if (rc) return rc;
     A.d2h(vol, dv, nout * 4);
     return A.finish();
@@ -398,7 +570,7 @@ int tmat_vessel_field(tmat_handle hd, const float *vol, int Z, int hh, int ww, i
     DevScope A(c->ws_pool, c->stream);
     float *dv = A.pooled_from(vol, nvol), *df = A.pooled<float>(npx);
     if (!A.ok) return TMAT_E_HIP;
-    int rc = vessel_field_dev(c, dv, Z, hh, ww, hessian, df, stages, c->stream);
+    int rc = vessel_field_dev(c, dv, 1, Z, hh, ww, hessian, df, stages, c->stream);
     if (rc) return rc;
     A.d2h(field, df, npx * 4);
     return A.finish();
@@ -478,7 +650,7 @@ int tmat_resize_aa_u16(tmat_handle hd, const uint16_t *imgs, int n, int H, int W
     uint16_t *ds = A.pooled_from(imgs, nin);
     double *dz = A.pooled<double>(nout);
     if (!A.ok) return TMAT_E_HIP;
-    int rc = stack_resize_aa_dev(c, ds, n, H, W, out_h, out_w, dz, nullptr, c->stream);
+    int rc = stack_resize_aa_dev(c, ds, 1, n, H, W, out_h, out_w, dz, nullptr, c->stream);      // one clip range over the n images, as ever
     if (rc) return rc;
     A.d2h(out, dz, nout * 8);
     return A.finish();
@@ -503,12 +675,61 @@ int tmat_analyze_stack(tmat_handle hd, const uint16_t *stack, int Z, int H, int 
     uint16_t *ds = A.pooled_from(stack, nin);
     float *vol = A.pooled<float>((size_t)Z * npx), *field = A.pooled<float>(npx);
     if (!A.ok) return TMAT_E_HIP;
-    int rc = stack_prepare_dev(c, ds, Z, H, W, fh, fw, vol, s);
-    if (!rc) rc = vessel_field_dev(c, vol, Z, fh, fw, hessian, field, nullptr, s);
+    int rc = stack_prepare_dev(c, ds, 1, Z, H, W, fh, fw, vol, s);
+    if (!rc) rc = vessel_field_dev(c, vol, 1, Z, fh, fw, hessian, field, nullptr, s);
     if (rc) return rc;
     if (!A.d2h(field_out, field, npx * 4)) return TMAT_E_HIP;
     return field_stats_dev(c, field, fh, fw, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px,
                            remove_isolated, nullptr, index, row, s);
+}
+
+int tmat_stack_pass_plan(int n, int Z, int H, int W, int ds_width, int pass_stacks, int *stacks_per_pass, uint64_t *bytes_per_stack)
+{
+    if (n < 1 || Z < 2 || H < 2 || W < 2 || ds_width < 2 || pass_stacks < 0 || (!stacks_per_pass && !bytes_per_stack)) { set_error("tmat_stack_pass_plan: bad argument"); return TMAT_E_ARG; }
+    const int fh = (int)std::nearbyint((double)H * ((double)ds_width / (double)W)), fw = (int)std::nearbyint((double)W * ((double)ds_width / (double)W));
+    if (fh < 2 || fw < 2) { set_error("tmat_stack_pass_plan: downsampled shape is empty"); return TMAT_E_ARG; }
+    const size_t b = stack_pass_bytes(Z, H, W, fh, fw);
+    if (bytes_per_stack) *bytes_per_stack = b;
+    if (stacks_per_pass) *stacks_per_pass = stack_pass_count(n, b, pass_stacks);
+    return TMAT_OK;
+}
+
+int tmat_analyze_stack_batch(tmat_handle hd, const uint16_t *stacks, int n, int Z, int H, int W, const tmat_stack_opts *o, tmat_row *rows)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!o || o->size != (uint32_t)sizeof(tmat_stack_opts)) { set_error("tmat_analyze_stack_batch: unknown tmat_stack_opts size"); return TMAT_E_ARG; }
+    if (!c || !stacks || !rows || n < 1 || Z < 2 || H < 2 || W < 2 || o->ds_width < 2 || o->pass_stacks < 0) {
+        set_error("tmat_analyze_stack_batch: bad argument (n >= 1 stacks of Z >= 2 slices)");
+        return TMAT_E_ARG;
+    }
+    if (!hessian_ok(o->hessian)) { set_error("tmat_analyze_stack_batch: unknown hessian form"); return TMAT_E_ARG; }
+    if (o->n_thresh < 1 || !o->thresh) { set_error("tmat_analyze_stack_batch: needs at least one threshold pair"); return TMAT_E_ARG; }
+    TMAT_HIP(hipSetDevice(c->device));
+    return analyze_stack_batch(c, stacks, n, Z, H, W, *o, rows);
+}
+
+int tmat_vessel_field_batch(tmat_handle hd, const float *vols, int n, int Z, int hh, int ww, int hessian, float *fields, const tmat_vessel_stages *stages)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!c || !vols || !fields || n < 1 || Z < 2 || hh < 2 || ww < 2 || !hessian_ok(hessian)) { set_error("tmat_vessel_field_batch: bad argument"); return TMAT_E_ARG; }
+    TMAT_HIP(hipSetDevice(c->device));
+    const size_t nvol = (size_t)n * Z * hh * ww, npx = (size_t)n * hh * ww;
+    DevScope A(c->ws_pool, c->stream);
+    float *dv = A.pooled_from(vols, nvol), *df = A.pooled<float>(npx);
+    if (!A.ok) return TMAT_E_HIP;
+    int rc = vessel_field_dev(c, dv, n, Z, hh, ww, hessian, df, stages, c->stream);
+    if (rc) return rc;
+    A.d2h(fields, df, npx * 4);
+    return A.finish();
+}
+
+int tmat_debug_stack_trace(tmat_handle hd, int cap, int *n_pass, double *gpu_ms, double *host_ms)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!c || !n_pass || cap < 0 || (cap > 0 && (!gpu_ms || !host_ms))) { set_error("tmat_debug_stack_trace: bad argument"); return TMAT_E_ARG; }
+    *n_pass = (int)c->stack_trace.size();
+    for (int i = 0; i < *n_pass && i < cap; i++) { gpu_ms[i] = c->stack_trace[i].first; host_ms[i] = c->stack_trace[i].second; }
+    return TMAT_OK;
 }
 
 int tmat_host_gaussian_kernel1d(double sigma, int order, int radius, double *weights)

@@ -925,6 +925,7 @@ void tmat_destroy(tmat_handle h)
     if (c->se_table) hipFree(c->se_table);
     for (void *p : c->tool_ws) if (p) hipFree(p);
     for (auto &b : c->ws_pool) hipFree(b.second);
+    c->stack_host.free_all();
     for (auto &g : c->gauss_dev) hipFree(g.second);
     for (auto &m : c->resnets) for (void *p : m.owned) hipFree(p);
     c->free_pass();
@@ -1068,6 +1069,7 @@ static std::vector<WsEnt> held_blocks(const Ctx *c)
     all.insert(all.end(), c->pass.ws.begin(), c->pass.ws.end());
     for (int i = 0; i < N_TOOL_WS; i++) if (c->tool_ws[i]) all.push_back({c->tool_ws[i], c->tool_ws_bytes[i], false});
     for (auto &b : c->ws_pool) all.push_back({b.second, b.first, false});
+    all.insert(all.end(), c->stack_host.begin(), c->stack_host.end());
     return all;
 }
 

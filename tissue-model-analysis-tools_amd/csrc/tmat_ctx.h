@@ -250,6 +250,8 @@ struct Ctx {
     void *tool_ws[N_TOOL_WS] = {};
     size_t tool_ws_bytes[N_TOOL_WS] = {};
     WsPool ws_pool;                                          // released call-scoped blocks of the Z-stack tool, by size (dev_mem.h:DevScope::pooled)
+    WsList stack_host;                                       // pinned result buffers of the Z-stack batch pipeline, two slots of five (stack_pipeline.cpp)
+    std::vector<std::pair<double, double>> stack_trace;      // (device stages ms, host graph stage ms) per pass of the last tmat_analyze_stack_batch
     // profiling of the dominant kernel family
     bool prof_on = false;
     std::vector<ProfEv> ev_open;

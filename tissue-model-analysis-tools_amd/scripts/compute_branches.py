@@ -34,6 +34,7 @@ import numpy as np  # noqa: E402
 
 DEFAULT_CONFIG_PATH = str(PKG / "config" / "default_branching_computation.json")
 DOWNSAMPLE_WIDTH = 384
+STACK_BATCH_DEFAULT = "1"          # TMAT_STACK_BATCH when unset: Z stacks of one shape go through tmat_analyze_stack_batch
 FAIL = "\033[91m[FAILURE]\033[0m"
 OK = "\033[92m[SUCCESS]\033[0m"
 
@@ -233,9 +234,14 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
     tree_vis = bool(getattr(args, "tree_visualizations", False))
     vis_width = int(getattr(args, "vis_width", 2000) or 2000)
     encoder = handle.png_encode if getattr(args, "png_encoder", "pil") == "device" else None
-    suffix_of = {(cfg["thresh1"], cfg["thresh2"]): sfx for cfg, sfx in branches.threshold_grid(config)}
+    grid = branches.threshold_grid(config)
+    suffix_of = {(cfg["thresh1"], cfg["thresh2"]): sfx for cfg, sfx in grid}
     ids = sorted(paths)
     fields = {}
+    # Batch path (tmat_analyze_stack_batch): consecutive stacks of one shape and width go through the device stages together, the host
+    # graph stage of a pass runs beside the device stages of the next, the threshold grid is swept from fields that stay in HBM.
+    # TMAT_STACK_BATCH=0 keeps every stack on the per-stack path; --tree-visualizations and stacks of a unique shape always take it.
+    batch_on = os.environ.get("TMAT_STACK_BATCH", STACK_BATCH_DEFAULT) != "0" and not tree_vis
 
     def load_fn(img_id):
         try:
@@ -256,7 +262,31 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
             width_um = st.shape[-1] * px
         return width_um
 
+    def analyze_batch_fn(batch, width_um, thresh, ids):
+        # one call for the whole chunk and the whole grid; run_sharded then asks configuration by configuration
+        if fields.get("batch") is not batch:
+            fields.clear()
+            fields["batch"] = batch
+            sw_px, min_px, max_px = branches.graph_px_params(config, DOWNSAMPLE_WIDTH, width_um)
+            pruning = None
+            if detect_well:
+                out_hw = sato.dsamp_shape(batch.shape, DOWNSAMPLE_WIDTH)
+                pruning = np.stack([sato.stack_well_masks(handle, st, out_hw, well_seed)[1] for st in batch])
+            pairs = [(cfg["thresh1"], cfg["thresh2"]) for cfg, _ in grid]
+            res = sato.analyze_stack_batch(handle, batch, pairs, sw_px, min_px, max_px, bool(config.get("remove_isolated_branches", False)),
+                                           DOWNSAMPLE_WIDTH, hessian, pruning_masks=pruning, return_pictures=vis)
+            rows_all, pics = res if vis else (res, None)
+            fields["rows"] = {pair: rows_all[t] for t, pair in enumerate(pairs)}
+            if vis:
+                for i, img_id in enumerate(ids):
+                    vis_dir = out_root / "visualizations" / img_id
+                    branches._save_png_unique(pics[0][i], vis_dir, "original_image.png", encoder)
+                    branches._save_png_unique(pics[1][i], vis_dir, "vesselness_image.png", encoder)
+        return [(i,) + tuple(r) for i, r in enumerate(fields["rows"][thresh])]
+
     def analyze_fn(batch, width_um, thresh, input_bits, ids):
+        if batch_on and len(batch) > 1:
+            return analyze_batch_fn(batch, width_um, thresh, ids)
         # the vesselness image does not depend on the graph thresholds: one field per stack, swept over the grid
         sw_px, min_px, max_px = branches.graph_px_params(config, DOWNSAMPLE_WIDTH, width_um)
         rows = []
@@ -300,10 +330,15 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
                 Image.fromarray((well * 255).astype(np.uint8)).save(out_root / "visualizations" / img_id / "well_mask.png")
         return st
 
-    # one stack per analysis call (chunk=1): a stack is the unit the reference streams, and it can be gigabytes
+    def stack_chunk_ends(held_keys, key, st):
+        # sato.chunk_stacks' rule on the stream of loaded stacks: one key per chunk, at most 8 stacks, the pass's device bytes under the budget
+        nb = sato.stack_pass_plan(1, st.shape[0], st.shape[1], st.shape[2], DOWNSAMPLE_WIDTH)[1]
+        return sato.chunk_ends(held_keys[0], len(held_keys), nb * len(held_keys), key, nb)
+
+    # per-stack path: one stack per analysis call (chunk=1): a stack is the unit the reference streams, and it can be gigabytes
     try:
-        gathered = branches.run_sharded(ids, load_and_keep, width_fn, analyze_fn, config, rank, ws, chunk=1, log=lambda m: print(m, flush=True),
-                                        pass_ids=True)
+        gathered = branches.run_sharded(ids, load_and_keep, width_fn, analyze_fn, config, rank, ws, chunk=sato.STACK_PASS_MAX if batch_on else 1,
+                                        log=lambda m: print(m, flush=True), pass_ids=True, chunk_ends=stack_chunk_ends if batch_on else None)
     except distributed.RankFailed:
         handle.close()
         finish_distributed(ws)

@@ -37,6 +37,16 @@ class AnalyzeOpts(C.Structure):
                 ("rgb_out", C.c_void_p), ("bars_out", C.c_void_p), ("cap_b", C.c_int), ("n_bars", C.c_void_p), ("stage_out", C.c_void_p)]
 
 
+class StackOpts(C.Structure):
+    """tmat_stack_opts (include/tmat.h)"""
+    _fields_ = [("size", C.c_uint32), ("ds_width", C.c_int), ("hessian", C.c_int), ("n_thresh", C.c_int), ("thresh", C.c_void_p),
+                ("smoothing_window_px", C.c_int), ("min_branch_length_px", C.c_int), ("max_branch_length_px", C.c_int), ("remove_isolated", C.c_int),
+                ("first_index", C.c_int64), ("pruning_masks", C.c_void_p), ("fields_out", C.c_void_p), ("proj_pic_out", C.c_void_p),
+                ("field_pic_out", C.c_void_p), ("pass_stacks", C.c_int)]
+
+
+STACK_PASS_MAX = 8                   # TMAT_STACK_PASS_MAX
+STACK_PASS_BUDGET = 8 << 30          # TMAT_STACK_PASS_BUDGET: device bytes of one pass of tmat_analyze_stack_batch
 PIC_DTYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2, np.dtype(np.uint8): 3}      # TMAT_PIC_*
 STAGE_PLANES = ("original", "prediction", "mask", "weighted")                                                       # TMAT_STAGE_*
 
@@ -101,6 +111,10 @@ def lib():
     L.tmat_field_stats.argtypes = [vp, vp, i, i, f, f, i, i, i, i, C.c_int64, vp]
     L.tmat_field_stats_pruned.argtypes = [vp, vp, i, i, f, f, i, i, i, i, vp, C.c_int64, vp]
     L.tmat_resize_aa_u16.argtypes = [vp, vp, i, i, i, i, i, vp]
+    L.tmat_analyze_stack_batch.argtypes = [vp, vp, i, i, i, i, C.POINTER(StackOpts), vp]
+    L.tmat_vessel_field_batch.argtypes = [vp, vp, i, i, i, i, i, vp, vp]
+    L.tmat_stack_pass_plan.argtypes = [i, i, i, i, i, i, C.POINTER(i), C.POINTER(C.c_uint64)]
+    L.tmat_debug_stack_trace.argtypes = [vp, i, C.POINTER(i), vp, vp]
     L.tmat_cell_area_batch.argtypes = [vp, vp, i, i, i, i, i, d, vp, vp, vp]
     L.tmat_cell_area_masked.argtypes = [vp, vp, vp, i, i, i, d, vp, vp, vp]
     L.tmat_resize_linear_u16.argtypes = [vp, vp, i, i, i, i, i, vp]
@@ -163,6 +177,7 @@ EXPORTS = [
     "tmat_stage_pictures", "tmat_host_stage_pictures", "tmat_analyze_batch_ex", "tmat_analyze_batch_ex_dev",
     "tmat_png_stripe", "tmat_png_bound", "tmat_png_encode_batch", "tmat_png_encode_batch_dev", "tmat_png_encode_batch_timed",
     "tmat_host_png_encode_batch", "tmat_render_tree_png",
+    "tmat_analyze_stack_batch", "tmat_vessel_field_batch", "tmat_stack_pass_plan", "tmat_debug_stack_trace",
 ]
 
 

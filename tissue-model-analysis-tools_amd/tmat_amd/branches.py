@@ -383,7 +383,7 @@ class InputError(Exception):
 
 
 def run_sharded(ids, load_fn, width_fn, analyze_fn, config: dict, rank: int = 0, world_size: int = 1, chunk: int = 64,
-                log=print, pass_ids: bool = False):
+                log=print, pass_ids: bool = False, chunk_ends=None):
     """The per-run driver of scripts/compute_branches.py (reference :585-594 loops over the images one by one):
     rank `rank` of `world_size` takes a contiguous block of `ids`, loads its images in bounded chunks of at most `chunk`
     (images of equal shape, physical width and bit depth are analysed as one batch), and all ranks exchange their rows
@@ -393,6 +393,8 @@ def run_sharded(ids, load_fn, width_fn, analyze_fn, config: dict, rank: int = 0,
     analyze_fn(batch uint16 (n, H, W), width_um, thresh=(t1, t2), input_bits=8|16) -> [(i, count, total_px, avg_px)].
     pass_ids: analyze_fn also takes ids=[the id of every image of the batch, in batch order] (the pictures of --tree-visualizations
     are written per image inside analyze_fn).
+    chunk_ends (optional): chunk_ends(keys of the images held, key of the next image, next image) -> bool, asked before an image joins
+    the held chunk; True analyses the held chunk first (the Z-stack path groups consecutive stacks of one key under a byte budget).
     Returns {file-name suffix: [(global index, count, total_um, avg_um)] sorted by index}, on every rank."""
     from . import distributed
     ids = list(ids)
@@ -413,7 +415,7 @@ def run_sharded(ids, load_fn, width_fn, analyze_fn, config: dict, rank: int = 0,
     # Whatever goes wrong on this rank -- an unreadable image (InputError), a HIP / library error out of analyze_fn, a shape
     # surprise in np.stack -- the rank must still enter the collective below: the other ranks are waiting in it and would block
     # until the launcher kills them.  The failure travels through the gather (distributed.gather_rows raises RankFailed everywhere).
-    groups, held, failed = {}, 0, False
+    groups, held, failed, held_keys = {}, 0, False, []
     try:
         for gidx in mine:
             img_id = ids[int(gidx)]
@@ -424,11 +426,16 @@ def run_sharded(ids, load_fn, width_fn, analyze_fn, config: dict, rank: int = 0,
             except InputError:
                 failed = True
                 break
-            groups.setdefault((img.shape, float(width_um), 8 * img.dtype.itemsize), []).append((int(gidx), img))
+            key = (img.shape, float(width_um), 8 * img.dtype.itemsize)
+            if chunk_ends is not None and held and chunk_ends(held_keys, key, img):
+                flush(groups)
+                groups, held, held_keys = {}, 0, []
+            groups.setdefault(key, []).append((int(gidx), img))
             held += 1
+            held_keys.append(key)
             if held >= chunk:           # bounded host / HBM footprint: the reference streams one image at a time
                 flush(groups)
-                groups, held = {}, 0
+                groups, held, held_keys = {}, 0, []
         if not failed:
             flush(groups)
     except Exception:                   # noqa: BLE001 -- reported here, re-raised as RankFailed by the gather on every rank

@@ -16,7 +16,7 @@ import math
 
 import numpy as np
 
-from ._lib import Handle, Row, VesselStages, check, lib, ptr
+from ._lib import STACK_PASS_BUDGET, STACK_PASS_MAX, Handle, Row, StackOpts, VesselStages, check, lib, ptr
 
 SATO_SIGMAS = (1, 2, 3, 4, 5, 7, 9, 11, 13, 15)            # compute_branches.py:262
 GAUSSIAN_DERIVATIVES, GRADIENT = 0, 1                      # TMAT_SATO_*: scikit-image >= 0.20 (the pinned 0.22.0) / <= 0.19
@@ -147,6 +147,123 @@ def vessel_field(handle: Handle, vol: np.ndarray, hessian="gaussian_derivatives"
     if return_stages:
         return field, {k: (a.astype(bool) if a.dtype == np.uint8 else a) for k, a in arrays.items()}
     return field
+
+
+def vessel_field_batch(handle: Handle, vols: np.ndarray, hessian="gaussian_derivatives", return_stages=False):
+    """tmat_vessel_field_batch: n prepared stacks (n, Z, h, w) float32 through one launch set -> fields (n, h, w) float32
+    [, stages: the arrays of vessel_field with a leading n]"""
+    v = np.ascontiguousarray(vols, np.float32)
+    if v.ndim != 4:
+        raise ValueError("vessel_field_batch: expected (n, Z, h, w)")
+    n, Z, h, w = v.shape
+    install_gaussian_tables(handle)
+    fields = np.empty((n, h, w), np.float32)
+    st = None
+    arrays = {}
+    if return_stages:
+        st = VesselStages()
+        for k in ("vess", "sharp"):
+            arrays[k] = np.empty((n, Z - 1, h, w), np.float32)
+        arrays["vessels"] = np.empty((n, h, w), np.float32)
+        for k in ("edges", "skel", "mask_sel", "grown", "closed", "filt"):
+            arrays[k] = np.empty((n, h, w), np.uint8)
+        for k, a in arrays.items():
+            setattr(st, k, a.ctypes.data)
+    check(lib().tmat_vessel_field_batch(handle.raw, ptr(v), n, Z, h, w, HESSIAN_FORMS[hessian], ptr(fields), C.byref(st) if st is not None else None),
+          "tmat_vessel_field_batch")
+    if return_stages:
+        return fields, {k: (a.astype(bool) if a.dtype == np.uint8 else a) for k, a in arrays.items()}
+    return fields
+
+
+def stack_pass_plan(n, Z, H, W, ds_width=384, pass_stacks=0):
+    """tmat_stack_pass_plan (host only): (stacks per pass, device bytes per stack) of analyze_stack_batch for n stacks of (Z, H, W)"""
+    k, b = C.c_int(), C.c_uint64()
+    check(lib().tmat_stack_pass_plan(int(n), int(Z), int(H), int(W), int(ds_width), int(pass_stacks), C.byref(k), C.byref(b)), "tmat_stack_pass_plan")
+    return k.value, b.value
+
+
+def stacks_per_pass(n, bytes_per_stack, pass_stacks=0, budget=STACK_PASS_BUDGET, max_stacks=STACK_PASS_MAX):
+    """the K rule of tmat_analyze_stack_batch (include/tmat.h): min(n, 8, budget // bytes per stack), at least 1; pass_stacks > 0 overrides"""
+    if pass_stacks > 0:
+        return max(1, min(n, pass_stacks))
+    return max(1, min(n, max_stacks, budget // bytes_per_stack if bytes_per_stack else max_stacks))
+
+
+def chunk_ends(cur_key, cur_len, cur_bytes, key, nbytes, budget=STACK_PASS_BUDGET, max_stacks=STACK_PASS_MAX):
+    """does a chunk of cur_len stacks of cur_key holding cur_bytes end before a stack of (key, nbytes)?  (chunk_stacks, and the
+    streaming loop of compute_branches.py)"""
+    return key != cur_key or cur_len >= max_stacks or cur_bytes + nbytes > budget
+
+
+def chunk_stacks(keys, nbytes, budget=STACK_PASS_BUDGET, max_stacks=STACK_PASS_MAX):
+    """Grouping rule of compute_branches.py's Z-stack path, as a pure function.  keys[i]: what must be equal for stacks to share a batch
+    call ((Z, H, W) and the width in microns); nbytes[i]: device bytes of stack i in a pass.  Consecutive stacks with equal keys form a
+    chunk; a chunk ends when the next stack would take it past `budget` bytes or `max_stacks` stacks.  Order is preserved; a stack
+    whose key differs from both neighbours is a chunk of one.  -> list of lists of indices"""
+    chunks, cur, cur_bytes = [], [], 0
+    for i, (key, nb) in enumerate(zip(keys, nbytes)):
+        if cur and chunk_ends(keys[cur[0]], len(cur), cur_bytes, key, nb, budget, max_stacks):
+            chunks.append(cur)
+            cur, cur_bytes = [], 0
+        cur.append(i)
+        cur_bytes += nb
+    if cur:
+        chunks.append(cur)
+    return chunks
+
+
+def analyze_stack_batch(handle: Handle, stacks, thresh_pairs, smoothing_window_px, min_branch_length_px, max_branch_length_px=None,
+                        remove_isolated=False, ds_width=384, hessian="gaussian_derivatives", first_index=0, pruning_masks=None,
+                        return_fields=False, return_pictures=False, pass_stacks=0):
+    """tmat_analyze_stack_batch: n stacks of one shape (n, Z, H, W) and a list of (graph_thresh_1, graph_thresh_2) pairs ->
+    rows[t][i] = (count, total_px, avg_px) of stack i at pair t [, fields (n, fh, fw) float32][, (projection pictures (n, H, W) uint8,
+    field pictures (n, fh, fw) uint8)].  pruning_masks: None or (n, fh, fw) bool, MorseGraph's pruning mask per stack"""
+    a = np.asarray(stacks)
+    if a.ndim != 4 or a.dtype not in (np.uint8, np.uint16):
+        raise ValueError("Z stacks: expected (n, Z, H, W) uint8 or uint16")
+    a = np.ascontiguousarray(a, np.uint16)
+    n, Z, H, W = a.shape
+    out_hw = dsamp_shape(a.shape, ds_width)
+    install_gaussian_tables(handle, a.shape[2:], out_hw)
+    th = np.ascontiguousarray(thresh_pairs, np.float32).reshape(-1, 2)
+    o = StackOpts()
+    o.size = C.sizeof(StackOpts)
+    o.ds_width, o.hessian = int(ds_width), HESSIAN_FORMS[hessian]
+    o.n_thresh, o.thresh = len(th), th.ctypes.data if len(th) else None
+    o.smoothing_window_px, o.min_branch_length_px = int(smoothing_window_px), int(min_branch_length_px)
+    o.max_branch_length_px, o.remove_isolated = int(max_branch_length_px or 0), int(bool(remove_isolated))
+    o.first_index, o.pass_stacks = int(first_index), int(pass_stacks)
+    pm = None
+    if pruning_masks is not None:
+        pm = np.ascontiguousarray(np.asarray(pruning_masks) > 0, np.uint8)
+        if pm.shape != (n,) + tuple(out_hw):
+            raise ValueError("analyze_stack_batch: pruning_masks must be (n,) + the field's shape")
+        o.pruning_masks = pm.ctypes.data
+    fields = np.empty((n,) + tuple(out_hw), np.float32) if return_fields else None
+    if return_fields:
+        o.fields_out = fields.ctypes.data
+    pics = None
+    if return_pictures:
+        pics = (np.empty((n, H, W), np.uint8), np.empty((n,) + tuple(out_hw), np.uint8))
+        o.proj_pic_out, o.field_pic_out = pics[0].ctypes.data, pics[1].ctypes.data
+    rows = (Row * (max(len(th), 1) * n))()
+    check(lib().tmat_analyze_stack_batch(handle.raw, ptr(a), n, Z, H, W, C.byref(o), rows), "tmat_analyze_stack_batch")
+    res = ([[(rows[t * n + i].count, rows[t * n + i].total_px, rows[t * n + i].avg_px) for i in range(n)] for t in range(len(th))],)
+    if return_fields:
+        res += (fields,)
+    if return_pictures:
+        res += (pics,)
+    return res[0] if len(res) == 1 else res
+
+
+def stack_trace(handle: Handle):
+    """tmat_debug_stack_trace: [(device stages ms, host graph stage ms)] per pass of the handle's last analyze_stack_batch"""
+    n = C.c_int()
+    check(lib().tmat_debug_stack_trace(handle.raw, 0, C.byref(n), None, None), "tmat_debug_stack_trace")
+    g, h = np.zeros(max(n.value, 1)), np.zeros(max(n.value, 1))
+    check(lib().tmat_debug_stack_trace(handle.raw, n.value, C.byref(n), ptr(g), ptr(h)), "tmat_debug_stack_trace")
+    return [(float(g[i]), float(h[i])) for i in range(n.value)]
 
 
 def analyze_stack(handle: Handle, stack: np.ndarray, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px,
