@@ -270,10 +270,21 @@ int tmat_host_render_tree(const void *background, int bg_dtype, int n, int bh, i
  * plot_colored_barcode (reference topology.py:67-107) without axes or text: a white square canvas of
  * round_half_even(0.9 vis_width) pixels, the bars (n, 2) f64 of tmat_morse_tree sorted by birth, descending and stable, bar k
  * a rectangle of 0.8 row pitch on row k (row 0 lowest) from birth to death in the colour of its branch, the range
- * [min birth, max death] mapped onto the width; integer pixel edges, no anti-aliasing.  Host only: a few
- * hundred rectangles on a canvas that would cost more to copy back than to fill.  rgb_out (S, S, 3) u8.
+ * [min birth, max death] mapped onto the width; integer pixel edges, no anti-aliasing.  rgb_out (S, S, 3) u8.
+ * tmat_host_render_barcode runs on the host.  tmat_render_barcode is the batched device form (overlay_kernels.hip): bars
+ * (bar_offsets[n_pics], 2) f64 and bar_offsets (n_pics + 1) int32, host pointers, picture p owning the bars
+ * [bar_offsets[p], bar_offsets[p + 1]); rgb_out (n_pics, S, S, 3) u8 host.  The host keeps the sort, the edge rounding and the colours
+ * and hands the device a table of rectangles; the bytes are the host form's for every input (no bars, a zero span, more bars than
+ * rows).  tmat_render_barcode_png returns the same canvases as PNG files (render and encoder back to back on the handle's stream, as
+ * tmat_render_tree_png; its bound is tmat_png_bound(S, S, 3)).  A handle from tmat_create_plain is enough.
+ * tmat_host_barcode_rects (tests): the rectangle table of one picture, five int32 each -- columns [xa, xb), rows [ya, yb) counted from
+ * the bottom row, rgb = r | g << 8 | b << 16 --, entry k being row k of the sorted order; *n_rects is 0 when nothing is drawn.
  */
 int tmat_host_render_barcode(const double *bars, int n, int vis_width, uint8_t *rgb_out);
+int tmat_render_barcode(tmat_handle h, const double *bars, const int32_t *bar_offsets, int n_pics, int vis_width, uint8_t *rgb_out);
+int tmat_render_barcode_png(tmat_handle h, const double *bars, const int32_t *bar_offsets, int n_pics, int vis_width, uint8_t *out,
+                            size_t cap_each, size_t *sizes);
+int tmat_host_barcode_rects(const double *bars, int n, int vis_width, int32_t *rects_out, int cap, int *n_rects);
 
 /*
  * save_vis, the picture rule of the 2-D and Z-stack branches (compute_branches.py:74-78: rescale_intensity(out_range=(0, 255)) and
@@ -416,6 +427,47 @@ typedef struct tmat_analyze_opts {
 } tmat_analyze_opts;
 int tmat_analyze_batch_ex(tmat_handle h, const uint16_t *imgs, int n, int H, int W, const tmat_analyze_opts *o, tmat_row *rows);
 int tmat_analyze_batch_ex_dev(tmat_handle h, const uint16_t *imgs_dev, int n, int H, int W, const tmat_analyze_opts *o, tmat_row *rows);
+
+/*
+ * The grid form of the extensible entry: graph_thresh_1 / graph_thresh_2 as lists (compute_branches.py:366-395, the parameter-tuning
+ * mode).  The reference analyses an image once and builds one MorseGraph per pair from the same field (:391-426); so does this call:
+ * every pass of the network, the filter, the thinning, the finish stage and the DMT front end runs ONCE, and only the tail that reads
+ * the thresholds (`collect`, then tmat_morse_stats / tmat_morse_tree) runs per pair, on the host workers over (pair, image).
+ *   size            sizeof(tmat_grid_opts) as the caller compiled it; TMAT_E_ARG for a size this library does not know
+ *   n_thresh, thresh   n_thresh >= 1 pairs (graph_thresh_1, graph_thresh_2), host, as tmat_stack_opts; o->graph_thresh_1 / _2 are not read
+ *   rows            (n_thresh, n): rows[t n + i] is image i at pair t -- bit for bit the row of tmat_analyze_batch_ex at that pair with
+ *                   the same masks
+ *   o->rgb_out, o->bars_out, o->n_bars   gain a leading n_thresh axis: (n_thresh, n, vh, vw, 3), (n_thresh, n, cap_b, 2), (n_thresh, n);
+ *                   each slice holds the bytes of tmat_analyze_batch_tree at that pair.  o->stage_out keeps (n, 4, h, w): the stage
+ *                   pictures do not depend on the pair.  TMAT_E_CAP when any (t, i) has more than cap_b bars
+ *   tree_png        NULL, or room for (n_thresh, n) files of tree_png_cap bytes each: the same overlays as complete PNG files, encoded
+ *                   on the device from the raster in HBM (png_kernels.hip); file (t, i) at tree_png + (t n + i) tree_png_cap for
+ *                   tree_png_sizes[t n + i] bytes, the bytes of tmat_png_encode_batch of the raw overlay; bytes behind a file are not
+ *                   written.  o->rgb_out may then be NULL -- no raw overlay crosses to the host --; vis_width, bars_out, cap_b and n_bars
+ *                   are still read.  tree_png_cap below tmat_png_bound(vh, vw, 3): TMAT_E_CAP before any pass starts
+ *   barcode_png     NULL, or the same for the barcode picture of (t, i): rasterised on the device from that pair's scaled bars
+ *                   (tmat_render_barcode), then encoded; the bytes of tmat_host_png_encode_batch(tmat_host_render_barcode(bars)).  Its
+ *                   bound is tmat_png_bound(S, S, 3), S = round_half_even(0.9 vis_width).  It takes the tree request's vis_width,
+ *                   bars_out, cap_b and n_bars, since the bars come from it
+ * TMAT_E_ARG: n_thresh < 1, thresh NULL, an unknown size of either struct, a handle from tmat_create_plain; nothing is then written.
+ * Scratch comes from the handle's tool workspaces, sized on first use.  The picture buffers grow with n_thresh: callers bound the
+ * images per call (tmat_amd/branches.py:grid_images_per_call).
+ */
+typedef struct tmat_grid_opts {
+    uint32_t size;
+    int n_thresh;
+    const float *thresh;
+    uint8_t *tree_png;
+    size_t tree_png_cap;
+    size_t *tree_png_sizes;
+    uint8_t *barcode_png;
+    size_t barcode_png_cap;
+    size_t *barcode_png_sizes;
+} tmat_grid_opts;
+int tmat_analyze_batch_grid(tmat_handle h, const uint16_t *imgs, int n, int H, int W, const tmat_analyze_opts *o, const tmat_grid_opts *g,
+                            tmat_row *rows);
+int tmat_analyze_batch_grid_dev(tmat_handle h, const uint16_t *imgs_dev, int n, int H, int W, const tmat_analyze_opts *o,
+                                const tmat_grid_opts *g, tmat_row *rows);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Z-stack (Sato) branch of analyze_img: reference scripts/compute_branches.py:224-306 (csrc/sato_kernels.hip,

@@ -210,18 +210,19 @@ extern "C" int tmat_render_tree_png(tmat_handle hd, const void *background, int 
     return render_tree_impl(hd, background, bg_dtype, n, bh, bw, segs, seg_branch, seg_offsets, vis_width, nullptr, nullptr, out, cap_each, sizes);
 }
 
-// plot_colored_barcode (topology.py:67-107) without axes or text
-extern "C" int tmat_host_render_barcode(const double *bars, int n, int vis_width, uint8_t *rgb_out)
+// plot_colored_barcode (topology.py:67-107) without axes or text.  What needs a sequential host -- the stable sort by birth, the edge
+// rounding, the branch colours -- ends in a table of rectangles; the host twin and barcode_kernel (overlay_kernels.hip) fill the same table.
+namespace tmat {
+
+int barcode_side(int vis_width) { return (int)std::nearbyint((double)vis_width * 0.9); }
+
+void barcode_rects(const double *bars, int n, int S, std::vector<BarRect> &out)
 {
-    if (n < 0 || (n && !bars) || vis_width < 1 || !rgb_out) { set_error("tmat_host_render_barcode: bad argument"); return TMAT_E_ARG; }
-    const int S = (int)std::nearbyint((double)vis_width * 0.9);
-    if (S < 1) { set_error("tmat_host_render_barcode: empty canvas"); return TMAT_E_ARG; }
-    std::memset(rgb_out, 255, (size_t)S * S * 3);
-    if (n == 0) return TMAT_OK;
+    if (n < 1) return;
     double lo = bars[0], hi = bars[1];
     for (int i = 0; i < n; i++) { lo = std::min(lo, bars[2 * i]); hi = std::max(hi, bars[2 * i + 1]); }
     const double span = hi - lo;
-    if (!(span > 0.0) || !std::isfinite(span)) return TMAT_OK;
+    if (!(span > 0.0) || !std::isfinite(span)) return;
     std::vector<int> order(n);
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bars[2 * a] > bars[2 * b]; });     // birth, descending
@@ -234,12 +235,114 @@ extern "C" int tmat_host_render_barcode(const double *bars, int n, int vis_width
         const int bi = order[k];
         uint8_t col[3];
         tmat_branch_color(bi, col);
-        const int xa = edge(bars[2 * bi]), xb = edge(bars[2 * bi + 1]);
-        const int ya = (int)std::floor(((double)k + 0.1) * pitch + 0.5), yb = (int)std::floor(((double)k + 0.9) * pitch + 0.5);
-        for (int y = ya; y < yb; y++) {            // bar 0 is the lowest row of the picture, as on matplotlib's upward y axis
-            uint8_t *row = rgb_out + (size_t)(S - 1 - y) * S * 3;
-            for (int x = xa; x < xb; x++) { row[3 * x] = col[0]; row[3 * x + 1] = col[1]; row[3 * x + 2] = col[2]; }
+        BarRect r;
+        r.xa = edge(bars[2 * bi]); r.xb = edge(bars[2 * bi + 1]);
+        r.ya = (int)std::floor(((double)k + 0.1) * pitch + 0.5); r.yb = (int)std::floor(((double)k + 0.9) * pitch + 0.5);
+        r.rgb = (uint32_t)col[0] | ((uint32_t)col[1] << 8) | ((uint32_t)col[2] << 16);
+        out.push_back(r);
+    }
+}
+
+void barcode_fill_host(const BarRect *rects, int n, int S, uint8_t *rgb)
+{
+    std::memset(rgb, 255, (size_t)S * S * 3);
+    for (int k = 0; k < n; k++) {
+        const BarRect &r = rects[k];
+        const uint8_t col[3] = {(uint8_t)(r.rgb & 255u), (uint8_t)((r.rgb >> 8) & 255u), (uint8_t)((r.rgb >> 16) & 255u)};
+        for (int y = r.ya; y < r.yb; y++) {        // bar 0 is the lowest row of the picture, as on matplotlib's upward y axis
+            uint8_t *row = rgb + (size_t)(S - 1 - y) * S * 3;
+            for (int x = r.xa; x < r.xb; x++) { row[3 * x] = col[0]; row[3 * x + 1] = col[1]; row[3 * x + 2] = col[2]; }
         }
+    }
+}
+
+}  // namespace tmat
+
+extern "C" int tmat_host_render_barcode(const double *bars, int n, int vis_width, uint8_t *rgb_out)
+{
+    if (n < 0 || (n && !bars) || vis_width < 1 || !rgb_out) { set_error("tmat_host_render_barcode: bad argument"); return TMAT_E_ARG; }
+    const int S = barcode_side(vis_width);
+    if (S < 1) { set_error("tmat_host_render_barcode: empty canvas"); return TMAT_E_ARG; }
+    std::vector<BarRect> rects;
+    barcode_rects(bars, n, S, rects);
+    barcode_fill_host(rects.data(), (int)rects.size(), S, rgb_out);
+    return TMAT_OK;
+}
+
+// test entry of the shared helper: the rectangles of one picture, (xa, xb, ya, yb, rgb) as five int32 each; *n_rects may be 0 (nothing drawn)
+extern "C" int tmat_host_barcode_rects(const double *bars, int n, int vis_width, int32_t *rects_out, int cap, int *n_rects)
+{
+    if (n < 0 || (n && !bars) || vis_width < 1 || cap < 0 || (cap && !rects_out) || !n_rects) { set_error("tmat_host_barcode_rects: bad argument"); return TMAT_E_ARG; }
+    const int S = barcode_side(vis_width);
+    if (S < 1) { set_error("tmat_host_barcode_rects: empty canvas"); return TMAT_E_ARG; }
+    std::vector<BarRect> rects;
+    barcode_rects(bars, n, S, rects);
+    *n_rects = (int)rects.size();
+    if ((int)rects.size() > cap) { set_error("tmat_host_barcode_rects: cap is below the number of rectangles"); return TMAT_E_CAP; }
+    for (size_t k = 0; k < rects.size(); k++) {
+        int32_t *o = rects_out + 5 * k;
+        o[0] = rects[k].xa; o[1] = rects[k].xb; o[2] = rects[k].ya; o[3] = rects[k].yb; o[4] = (int32_t)rects[k].rgb;
     }
     return TMAT_OK;
 }
+
+// png_out (may be null): the canvases leave as PNG files (png.h) instead of as rasters; rgb_out is then not used
+static int render_barcode_impl(tmat_handle hd, const char *who, const double *bars, const int32_t *bar_offsets, int n_pics, int vis_width, uint8_t *rgb_out,
+                               uint8_t *png_out, size_t cap_each, size_t *png_sizes)
+{
+    Ctx *c = (Ctx *)hd;
+    const int S = vis_width >= 1 ? barcode_side(vis_width) : 0;
+    if (!c || n_pics < 0 || !bar_offsets || vis_width < 1 || S < 1 || !(png_out ? (void *)png_sizes : (void *)rgb_out) || !offsets_ok(bar_offsets, n_pics) ||
+        (bar_offsets[n_pics] && !bars)) {
+        set_error(std::string(who) + ": bad argument");
+        return TMAT_E_ARG;
+    }
+    PngShape pg{};
+    if (png_out) {
+        if (!png_shape(S, S, 3, pg)) { set_error(std::string(who) + ": canvas too large for one PNG file"); return TMAT_E_ARG; }
+        if (cap_each < pg.bound) { set_error(std::string(who) + ": cap_each is below tmat_png_bound"); return TMAT_E_CAP; }
+    }
+    if (n_pics == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    std::vector<BarRect> rects;
+    std::vector<int> off(n_pics + 1, 0);
+    for (int p = 0; p < n_pics; p++) {
+        barcode_rects(bars + 2 * (size_t)bar_offsets[p], bar_offsets[p + 1] - bar_offsets[p], S, rects);
+        off[p + 1] = (int)rects.size();
+    }
+    const size_t cper = (size_t)S * S * 3, nrect = rects.size();
+    const int K = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_pics, ((size_t)512 << 20) / cper));      // <= 512 MiB of canvases per launch
+    hipStream_t s = c->stream;
+    DevScope mem(c->ws_pool, s);
+    BarRect *drect = mem.pooled<BarRect>(nrect);
+    int *doff = mem.pooled<int>((size_t)n_pics + 1);
+    uint8_t *drgb = mem.pooled<uint8_t>((size_t)K * cper);
+    if (nrect) mem.h2d(drect, mem.keep(std::move(rects)), nrect * sizeof(BarRect));
+    mem.h2d(doff, mem.keep(std::move(off)), ((size_t)n_pics + 1) * sizeof(int));
+    if (!mem.ok) return TMAT_E_HIP;
+    for (int i0 = 0; i0 < n_pics; i0 += K) {
+        const int k = std::min(K, n_pics - i0);
+        const int r = barcode_render_dev(drect, doff + i0, k, S, drgb, s);
+        if (r) { set_error(std::string(who) + (r == -1 ? ": canvas too large for one launch" : ": kernel launch failed")); return r == -1 ? TMAT_E_ARG : TMAT_E_HIP; }
+        if (png_out) {      // the encoder follows on the same stream; only file bytes cross to the host
+            if (int rc = png_encode_ctx(c, drgb, false, k, pg, png_out + (size_t)i0 * cap_each, cap_each, png_sizes + i0, nullptr)) return rc;
+        } else {
+            mem.d2h(rgb_out + (size_t)i0 * cper, drgb, (size_t)k * cper);
+        }
+        if (mem.finish()) return TMAT_E_HIP;
+    }
+    return TMAT_OK;
+}
+
+extern "C" int tmat_render_barcode(tmat_handle hd, const double *bars, const int32_t *bar_offsets, int n_pics, int vis_width, uint8_t *rgb_out)
+{
+    return render_barcode_impl(hd, "tmat_render_barcode", bars, bar_offsets, n_pics, vis_width, rgb_out, nullptr, 0, nullptr);
+}
+
+extern "C" int tmat_render_barcode_png(tmat_handle hd, const double *bars, const int32_t *bar_offsets, int n_pics, int vis_width, uint8_t *out, size_t cap_each,
+                                       size_t *sizes)
+{
+    if (!out) { set_error("tmat_render_barcode_png: bad argument"); return TMAT_E_ARG; }
+    return render_barcode_impl(hd, "tmat_render_barcode_png", bars, bar_offsets, n_pics, vis_width, nullptr, out, cap_each, sizes);
+}
+

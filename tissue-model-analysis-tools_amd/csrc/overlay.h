@@ -87,4 +87,16 @@ int overlay_minmax_dev(const void *bg, int bg_dtype, int n, int bh, int bw, floa
 int overlay_render_dev(const void *bg, int bg_dtype, const float *mnmx, int n, int bh, int bw, const OverlaySeg *segs, const int *seg_offsets,
                        int vh, int vw, float rp, uint8_t *rgb, hipStream_t s);
 
+// Barcode picture (tmat_host_render_barcode / tmat_render_barcode): the host keeps the stable sort by birth, the edge rounding and the
+// branch colours, and emits one rectangle per bar; host twin and barcode_kernel only fill them over a white S x S canvas.
+// Columns [xa, xb), rows [ya, yb) counted from the BOTTOM row of the canvas; rgb = r | g << 8 | b << 16.  Entry k of a picture's table is
+// row k of the sorted order: its rows lie inside [k pitch, (k + 1) pitch), pitch = S / n, and the rows of different bars are disjoint.
+struct BarRect { int xa, xb, ya, yb; uint32_t rgb; };
+int barcode_side(int vis_width);        // S = round_half_even(0.9 vis_width)
+// appends the n rectangles of one picture to out -- or none when nothing is drawn (n == 0, a span that is zero or not finite)
+void barcode_rects(const double *bars, int n, int S, std::vector<BarRect> &out);
+void barcode_fill_host(const BarRect *rects, int n, int S, uint8_t *rgb);
+// n_pics canvases (n_pics, S, S, 3) on the device from the concatenated tables; picture p owns [rect_off[p], rect_off[p + 1]).  0 on success.
+int barcode_render_dev(const BarRect *rects, const int *rect_off, int n_pics, int S, uint8_t *rgb, hipStream_t s);
+
 }  // namespace tmat

@@ -3,6 +3,7 @@
 // per thread; the ones whose bounding box touches the tile are compacted into LDS IN SEGMENT ORDER (wave ballots + a prefix over the
 // waves), so painter's order never depends on scheduling and no atomics or global lists are involved.  Each thread owns four
 // neighbouring pixels of a row and writes their twelve bytes as three dwords: a wave writes 4 rows x 192 contiguous bytes.
+// barcode_kernel (further down) fills the barcode canvases from the host's rectangle tables.
 #include "overlay.h"
 
 #include <algorithm>
@@ -127,7 +128,62 @@ __global__ __launch_bounds__(OVL_THREADS) void ovl_render(const void *bg, int dt
     }
 }
 
+// Barcode canvases: HBM-bound fill, no LDS.  A thread owns 16 consecutive bytes of the FLAT batch buffer (pictures, rows and pixels run
+// through: S * 3 is rarely a multiple of 16) and writes them with one 16-byte store; the last, short group of the buffer is written
+// byte by byte.  The bar of a canvas row comes from index arithmetic -- row y (from the bottom) can only belong to bar floor((y + 0.5) /
+// pitch) -- plus a check of its two neighbours against the table's own row ranges, which absorbs the rounding of the division.
+__device__ inline bool bar_of_row(const BarRect *__restrict__ rects, const int *__restrict__ rect_off, size_t pic, int yimg, int S, BarRect &r)
+{
+    const int r0 = rect_off[pic], n = rect_off[pic + 1] - r0;
+    if (n < 1) return false;
+    const int y = S - 1 - yimg;
+    const double pitch = (double)S / (double)n;
+    const int k0 = (int)floor(((double)y + 0.5) / pitch);
+    for (int k = k0 - 1; k <= k0 + 1; k++) {
+        if (k < 0 || k >= n) continue;
+        const BarRect c = rects[r0 + k];
+        if (y >= c.ya && y < c.yb) { r = c; return true; }
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(OVL_THREADS) void barcode_kernel(const BarRect *__restrict__ rects, const int *__restrict__ rect_off, int n_pics, int S,
+                                                              uint8_t *__restrict__ rgb, int vec_ok)
+{
+    const size_t rowb = (size_t)S * 3, per = rowb * S, total = per * n_pics, ngroups = (total + 15) / 16;
+    for (size_t g = (size_t)blockIdx.x * OVL_THREADS + threadIdx.x; g < ngroups; g += (size_t)gridDim.x * OVL_THREADS) {
+        const size_t b0 = g * 16;
+        const int cnt = total - b0 < 16 ? (int)(total - b0) : 16;
+        size_t pic = b0 / per;
+        const size_t rem = b0 - pic * per;
+        int yimg = (int)(rem / rowb), cb = (int)(rem - (size_t)yimg * rowb);
+        BarRect r;
+        bool have = bar_of_row(rects, rect_off, pic, yimg, S, r);
+        union { uint4 q; uint8_t b[16]; } o;
+        for (int j = 0; j < cnt; j++) {
+            const int x = cb / 3, ch = cb - 3 * x;
+            o.b[j] = (have && x >= r.xa && x < r.xb) ? (uint8_t)((r.rgb >> (8 * ch)) & 255u) : (uint8_t)255;
+            if (++cb == (int)rowb) {
+                cb = 0;
+                if (++yimg == S) { yimg = 0; pic++; }
+                if (j + 1 < cnt) have = bar_of_row(rects, rect_off, pic, yimg, S, r);       // only then is (pic, yimg) still on the buffer
+            }
+        }
+        if (cnt == 16 && vec_ok) *(uint4 *)(rgb + b0) = o.q;
+        else for (int j = 0; j < cnt; j++) rgb[b0 + j] = o.b[j];
+    }
+}
+
 }  // namespace
+
+int barcode_render_dev(const BarRect *rects, const int *rect_off, int n_pics, int S, uint8_t *rgb, hipStream_t s)
+{
+    if (n_pics < 1 || S < 1 || (size_t)S * 3 > 0x7fffffffu) return -1;
+    const size_t total = (size_t)S * S * 3 * n_pics, ngroups = (total + 15) / 16, blocks = (ngroups + OVL_THREADS - 1) / OVL_THREADS;
+    const int vec_ok = ((uintptr_t)rgb & 15) == 0;
+    hipLaunchKernelGGL(barcode_kernel, dim3((unsigned)std::min<size_t>(blocks, 65536)), dim3(OVL_THREADS), 0, s, rects, rect_off, n_pics, S, rgb, vec_ok);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
 
 int overlay_minmax_dev(const void *bg, int bg_dtype, int n, int bh, int bw, float *mnmx, hipStream_t s)
 {

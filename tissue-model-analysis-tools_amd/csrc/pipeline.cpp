@@ -1,5 +1,5 @@
 // Batch drivers of the branching hot path (include/tmat.h): tmat_segment_batch,
-// tmat_postprocess_batch, tmat_analyze_batch(_dev) and its masked / tree / extensible forms, tmat_stage_pictures.
+// tmat_postprocess_batch, tmat_analyze_batch(_dev) and its masked / tree / extensible / grid forms, tmat_stage_pictures.
 //
 // Reference control flow: scripts/compute_branches.py:585-594 runs analyze_img one image at a time.
 // Here a run is cut into passes of K images (K = max_patches / patches-per-image).  Per pass the GPU
@@ -11,6 +11,7 @@
 // across GPUs (one process per GPU, see tmat_amd/distributed.py).
 #include "../../include/tmat.h"
 #include "overlay.h"
+#include "png.h"
 #include "tmat_ctx.h"
 #include "postproc.h"
 #include "morph.h"
@@ -261,7 +262,45 @@ struct TreeJob {
     uint8_t *rgb_out; double *bars_out; int cap_b; int *n_bars;     // caller's, whole call
     const uint16_t *bg_all;         // (n, h, w) u16 on the device
     OverlaySeg *dseg; size_t seg_cap; float *dmm; int *doff; uint8_t *drgb;
+    // the grid form only (tmat_analyze_batch_grid*): rgb_out may then be null, and the pictures may leave as PNG files, encoded on the
+    // third stream from the rasters in HBM (png_kernels.hip) -- the overlays from drgb, the barcodes from dbar (overlay_kernels.hip)
+    uint8_t *tree_png; size_t tree_png_cap; size_t *tree_png_sizes; PngShape pg_tree;
+    uint8_t *barcode_png; size_t barcode_png_cap; size_t *barcode_png_sizes; PngShape pg_bar;
+    int S; BarRect *drect; int *drect_off; uint8_t *dbar;
+    uint8_t *png_filt, *png_slots, *png_files; uint32_t *png_meta, *png_dsz;
 };
+
+// The pairs of a call: tmat_analyze_batch_grid* sweeps T (graph_thresh_1, graph_thresh_2) pairs from ONE pass of the network; every
+// other entry is the grid of its one pair.  Per-pair outputs carry a leading T axis: item (t, i) of a call of n images sits at t n + i.
+struct GridJob { int T; const float *thresh; int n; };
+
+// images of one encoder launch set: <= 128 MiB of filtered stream, as png_encode_ctx
+static int png_chunk(const PngShape &g, int k) { return (int)std::max<size_t>(1, std::min<size_t>((size_t)k, ((size_t)128 << 20) / g.raw)); }
+static size_t png_fcap(const PngShape &g) { return (g.bound + 15) & ~(size_t)15; }
+
+// k pictures of shape g in HBM -> k files at out + i cap_each on the host, on stream s with the job's encoder scratch (two
+// synchronisations per launch set: the sizes come back first, then exactly the files' bytes)
+static int png_encode_job(const TreeJob &tj, const uint8_t *pics_dev, int k, const PngShape &g, uint8_t *out, size_t cap_each, size_t *sizes, hipStream_t s)
+{
+    const size_t pic_bytes = (size_t)g.H * g.rb, fcap = png_fcap(g);
+    const int Kp = png_chunk(g, k);
+    std::vector<uint32_t> hsz(Kp);
+    for (int i0 = 0; i0 < k; i0 += Kp) {
+        const int kk = std::min(Kp, k - i0);
+        if (png_encode_launch(pics_dev + (size_t)i0 * pic_bytes, kk, g, tj.png_filt, tj.png_slots, tj.png_meta, tj.png_files, fcap, tj.png_dsz, s)) {
+            set_error("analyze (grid): png encoder launch failed");
+            return TMAT_E_HIP;
+        }
+        if (hipMemcpyAsync(hsz.data(), tj.png_dsz, (size_t)kk * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return TMAT_E_HIP;
+        for (int i = 0; i < kk; i++) {
+            if (hsz[i] < PNG_HEAD + PNG_TAIL || hsz[i] > g.bound) { set_error("png encoder: a file left its bound"); return TMAT_E_HIP; }
+            if (hipMemcpyAsync(out + (size_t)(i0 + i) * cap_each, tj.png_files + (size_t)i * fcap, hsz[i], hipMemcpyDeviceToHost, s) != hipSuccess) return TMAT_E_HIP;
+            sizes[i0 + i] = hsz[i];
+        }
+        if (hipStreamSynchronize(s) != hipSuccess) return TMAT_E_HIP;
+    }
+    return TMAT_OK;
+}
 
 // The stage pictures of a call (tmat_analyze_batch_ex with stage_out): save_vis of the four arrays the reference dumps, rendered from
 // the pass's own buffers (vis_kernels.hip) and copied to the caller's (n, 4, h, w) array per pass.
@@ -274,8 +313,9 @@ struct StageJob {
 };
 
 // pruning (nullable, the masked form only): the pass's (k, fh, fw) u8 pruning masks on the host, MorseGraph's pruning_mask per image
-static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_row *rows, PassJob *job, const TreeJob *tree = nullptr, int first_img = 0,
-                          const uint8_t *pruning = nullptr, const StageJob *stage = nullptr)
+// rows: the CALL's rows, (T, n); the pass's images are first_img .. first_img + k of every pair
+static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, const GridJob gj, tmat_row *rows, PassJob *job, const TreeJob *tree = nullptr,
+                          int first_img = 0, const uint8_t *pruning = nullptr, const StageJob *stage = nullptr)
 {
     PassBuf &b = c->pass;
     const int h = b.h, w = b.w;
@@ -339,49 +379,81 @@ static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, tmat_ro
     ok = ok && hipStreamSynchronize(s) == hipSuccess;
     if (!ok) { job->rc = TMAT_E_HIP; return; }
     const double t2 = now_s();
-    std::vector<std::vector<double>> tsegs(tree ? k : 0);
-    std::vector<std::vector<int32_t>> tbranch(tree ? k : 0);
-    parallel_images(k, [&](int i) {
+    // the graph stage over (pair, image): every item reads the pass's ONE set of mirrors (field, sorted edge ids, pairing kinds and
+    // persistences: none depends on the thresholds) and runs `collect` (dmt.cpp) with its pair's thresholds
+    const int T = gj.T;
+    const size_t n_all = (size_t)gj.n;
+    std::vector<std::vector<double>> tsegs(tree ? (size_t)T * k : 0);
+    std::vector<std::vector<int32_t>> tbranch(tree ? (size_t)T * k : 0);
+    parallel_images(T * k, [&](int item) {
+        const int t = item / k, i = item % k;
+        const size_t at = (size_t)t * n_all + first_img + i;        // (t, image of the call)
+        tmat_row &row = rows[at];
         const int cap_v = (int)fper + 4, cap_e = 3 * (int)fper + 4;
         std::vector<int32_t> V((size_t)cap_v * 2), E((size_t)cap_e * 2);
         int nv = 0, ne = 0;
-        int rc = dmt_graph_host_sorted(b.f255_host[slot] + i * fper, gp.fh, gp.fw, gp.t1, gp.t2, dmt_dev ? b.dmt_ids_host[slot] + i * nE : nullptr,
+        int rc = dmt_graph_host_sorted(b.f255_host[slot] + i * fper, gp.fh, gp.fw, gj.thresh[2 * t], gj.thresh[2 * t + 1],
+                                       dmt_dev ? b.dmt_ids_host[slot] + i * nE : nullptr,
                                        dmt_dev ? b.dmt_m_host[slot][i] : 0, V.data(), cap_v, E.data(), cap_e, &nv, &ne,
                                        sweep_dev ? b.dmt_kind_host[slot] + i * nE : nullptr, sweep_dev ? b.dmt_pers_host[slot] + i * nE : nullptr);
         if (!rc && !tree)
             rc = tmat_morse_stats(V.data(), nv, E.data(), ne, gp.fh, gp.fw, gp.smooth, gp.min_len, gp.max_len, gp.remove_isolated,
-                                  pruning ? pruning + i * fper : nullptr, &rows[i].count, &rows[i].total_px, &rows[i].avg_px, nullptr, 0);
+                                  pruning ? pruning + i * fper : nullptr, &row.count, &row.total_px, &row.avg_px, nullptr, 0);
         if (!rc && tree) {
             const int cap_s = std::max(nv, 1);       // a forest has fewer edges than vertices
-            tsegs[i].resize((size_t)cap_s * 4); tbranch[i].resize(cap_s);
+            tsegs[item].resize((size_t)cap_s * 4); tbranch[item].resize(cap_s);
             int ns = 0;
             rc = tmat_morse_tree(V.data(), nv, E.data(), ne, gp.fh, gp.fw, gp.smooth, gp.min_len, gp.max_len, gp.remove_isolated,
                                  pruning ? pruning + i * fper : nullptr, tree->sf,
-                                 &rows[i].count, &rows[i].total_px, &rows[i].avg_px, tsegs[i].data(), tbranch[i].data(), cap_s,
-                                 tree->bars_out + (size_t)(first_img + i) * tree->cap_b * 2, tree->cap_b, &ns, tree->n_bars + first_img + i);
-            tsegs[i].resize((size_t)ns * 4); tbranch[i].resize(ns);
+                                 &row.count, &row.total_px, &row.avg_px, tsegs[item].data(), tbranch[item].data(), cap_s,
+                                 tree->bars_out + at * tree->cap_b * 2, tree->cap_b, &ns, tree->n_bars + at);
+            tsegs[item].resize((size_t)ns * 4); tbranch[item].resize(ns);
         }
         if (rc) job->rc = rc;
     });
     if (tree && !job->rc) {
-        std::vector<OverlaySeg> ss;
-        std::vector<int> off(k + 1, 0);
-        int rc = TMAT_OK;
-        for (int i = 0; i < k && !rc; i++) {
-            rc = prep_segments(tsegs[i].data(), tbranch[i].data(), (int)tbranch[i].size(), h, w, tree->cv, ss);
-            off[i + 1] = (int)ss.size();
-        }
-        if (!rc && ss.size() > tree->seg_cap) { set_error("analyze (tree): segment workspace too small"); rc = TMAT_E_CAP; }
+        // the pictures, pair by pair on the third stream: the pass's K canvases (drgb, dbar) and its segment / rectangle tables are reused
+        // by every pair, so each pair ends with a synchronisation (which also releases its host tables)
+        const bool render = tree->rgb_out || tree->tree_png;
         const size_t cper = (size_t)tree->cv.vh * tree->cv.vw * 3;
-        if (!rc && ((!ss.empty() && hipMemcpyAsync(tree->dseg, ss.data(), ss.size() * sizeof(OverlaySeg), hipMemcpyHostToDevice, s) != hipSuccess) ||
-                    hipMemcpyAsync(tree->doff, off.data(), (size_t)(k + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess)) rc = TMAT_E_HIP;
         const uint16_t *bg = tree->bg_all + (size_t)first_img * per;
-        if (!rc && overlay_minmax_dev(bg, 0, k, h, w, tree->dmm, s)) rc = TMAT_E_HIP;
-        if (!rc && overlay_render_dev(bg, 0, tree->dmm, k, h, w, tree->dseg, tree->doff, tree->cv.vh, tree->cv.vw, tree->cv.rp, tree->drgb, s)) {
-            set_error("analyze (tree): overlay launch failed"); rc = TMAT_E_HIP;
+        int rc = TMAT_OK;
+        if (render && overlay_minmax_dev(bg, 0, k, h, w, tree->dmm, s)) rc = TMAT_E_HIP;        // the backgrounds' extrema: once per pass
+        for (int t = 0; t < T && !rc; t++) {
+            const size_t at = (size_t)t * n_all + first_img;
+            std::vector<OverlaySeg> ss;
+            std::vector<int> off(k + 1, 0), roff(k + 1, 0);
+            std::vector<BarRect> rects;
+            if (render) {
+                for (int i = 0; i < k && !rc; i++) {
+                    const size_t item = (size_t)t * k + i;
+                    rc = prep_segments(tsegs[item].data(), tbranch[item].data(), (int)tbranch[item].size(), h, w, tree->cv, ss);
+                    off[i + 1] = (int)ss.size();
+                }
+                if (!rc && ss.size() > tree->seg_cap) { set_error("analyze (tree): segment workspace too small"); rc = TMAT_E_CAP; }
+                if (!rc && ((!ss.empty() && hipMemcpyAsync(tree->dseg, ss.data(), ss.size() * sizeof(OverlaySeg), hipMemcpyHostToDevice, s) != hipSuccess) ||
+                            hipMemcpyAsync(tree->doff, off.data(), (size_t)(k + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess)) rc = TMAT_E_HIP;
+                if (!rc && overlay_render_dev(bg, 0, tree->dmm, k, h, w, tree->dseg, tree->doff, tree->cv.vh, tree->cv.vw, tree->cv.rp, tree->drgb, s)) {
+                    set_error("analyze (tree): overlay launch failed"); rc = TMAT_E_HIP;
+                }
+                if (!rc && tree->rgb_out && hipMemcpyAsync(tree->rgb_out + at * cper, tree->drgb, (size_t)k * cper, hipMemcpyDeviceToHost, s) != hipSuccess) rc = TMAT_E_HIP;
+                if (!rc && tree->tree_png)
+                    rc = png_encode_job(*tree, tree->drgb, k, tree->pg_tree, tree->tree_png + at * tree->tree_png_cap, tree->tree_png_cap, tree->tree_png_sizes + at, s);
+            }
+            if (!rc && tree->barcode_png) {
+                for (int i = 0; i < k; i++) {
+                    barcode_rects(tree->bars_out + (at + i) * tree->cap_b * 2, tree->n_bars[at + i], tree->S, rects);
+                    roff[i + 1] = (int)rects.size();
+                }
+                if ((!rects.empty() && hipMemcpyAsync(tree->drect, rects.data(), rects.size() * sizeof(BarRect), hipMemcpyHostToDevice, s) != hipSuccess) ||
+                    hipMemcpyAsync(tree->drect_off, roff.data(), (size_t)(k + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) rc = TMAT_E_HIP;
+                if (!rc && barcode_render_dev(tree->drect, tree->drect_off, k, tree->S, tree->dbar, s)) { set_error("analyze (grid): barcode launch failed"); rc = TMAT_E_HIP; }
+                if (!rc)
+                    rc = png_encode_job(*tree, tree->dbar, k, tree->pg_bar, tree->barcode_png + at * tree->barcode_png_cap, tree->barcode_png_cap,
+                                        tree->barcode_png_sizes + at, s);
+            }
+            if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = TMAT_E_HIP;       // ss / off / rects are released here
         }
-        if (!rc && hipMemcpyAsync(tree->rgb_out + (size_t)first_img * cper, tree->drgb, (size_t)k * cper, hipMemcpyDeviceToHost, s) != hipSuccess) rc = TMAT_E_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = TMAT_E_HIP;       // ss / off are released here
         if (rc) job->rc = rc;
     }
     if (trace_on())
@@ -394,8 +466,11 @@ struct TreeReq { int vis_width; uint8_t *rgb_out; double *bars_out; int cap_b; i
 // network input and the thresholded mask, pruning (n, fh, fw) u8 is MorseGraph's pruning mask
 struct MaskReq { const uint8_t *well; const uint8_t *pruning; };
 
+// grid (nullable, tmat_analyze_batch_grid* only): the pairs of the call instead of gp.t1 / gp.t2 -- rows and the tree outputs of req gain a
+// leading n_thresh axis, req->rgb_out may be null, and the pictures may leave as PNG files
 static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width, GraphParams gp,
-                       int64_t first_index, tmat_row *rows, const TreeReq *req = nullptr, const MaskReq *masks = nullptr, uint8_t *stage_out = nullptr)
+                       int64_t first_index, tmat_row *rows, const TreeReq *req = nullptr, const MaskReq *masks = nullptr, uint8_t *stage_out = nullptr,
+                       const tmat_grid_opts *grid = nullptr)
 {
     // compute_branches.py:309-312 hands target_shape = round(shape * ds_ratio) = (round(H r), round(W r)) to cv2.resize as
     // dsize, which cv2 reads as (width, height): the resized image has round(W r) rows and round(H r) columns.  Square
@@ -405,6 +480,22 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
     if (h < 1 || w < 1) { set_error("analyze: target shape is empty"); return TMAT_E_ARG; }
     gp.fh = round_half_even((double)H * ((double)ds_width / (double)W));
     gp.fw = round_half_even((double)W * ((double)ds_width / (double)W));
+    // the file capacities of the grid form are checked here, before anything is allocated or queued
+    const float one_pair[2] = {gp.t1, gp.t2};
+    const GridJob gj{grid ? grid->n_thresh : 1, grid ? grid->thresh : one_pair, n};
+    TreeJob tj{}, *tree = nullptr;
+    if (req && !canvas_of(h, w, req->vis_width, tj.cv)) { set_error("analyze (tree): empty canvas"); return TMAT_E_ARG; }
+    if (req && grid && grid->tree_png) {
+        if (!png_shape(tj.cv.vh, tj.cv.vw, 3, tj.pg_tree)) { set_error("tmat_analyze_batch_grid: canvas too large for one PNG file"); return TMAT_E_ARG; }
+        if (grid->tree_png_cap < tj.pg_tree.bound) { set_error("tmat_analyze_batch_grid: tree_png_cap is below tmat_png_bound"); return TMAT_E_CAP; }
+        tj.tree_png = grid->tree_png; tj.tree_png_cap = grid->tree_png_cap; tj.tree_png_sizes = grid->tree_png_sizes;
+    }
+    if (req && grid && grid->barcode_png) {
+        tj.S = barcode_side(req->vis_width);
+        if (!png_shape(tj.S, tj.S, 3, tj.pg_bar)) { set_error("tmat_analyze_batch_grid: empty barcode canvas, or one too large for a PNG file"); return TMAT_E_ARG; }
+        if (grid->barcode_png_cap < tj.pg_bar.bound) { set_error("tmat_analyze_batch_grid: barcode_png_cap is below tmat_png_bound"); return TMAT_E_CAP; }
+        tj.barcode_png = grid->barcode_png; tj.barcode_png_cap = grid->barcode_png_cap; tj.barcode_png_sizes = grid->barcode_png_sizes;
+    }
     TileGeom g = make_geom(h, w, c->patch);
     roi_attach(c, g);       // region form of the up path: g carries the class-major patch order for enqueue_pre / enqueue_back
     const int K = std::min(n, std::max(1, c->max_patches / g.tiles_per_img));      // one image per pass when it needs > max_patches
@@ -412,10 +503,8 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
     int rc = ensure_pass_buffers(c, K, H, W, h, w, gp.fh, gp.fw);
     if (!rc) rc = ensure_ma_table(c);
     if (rc) return rc;
-    for (int i = 0; i < n; i++) { rows[i].index = first_index + i; rows[i].count = 0; rows[i].total_px = 0; rows[i].avg_px = 0; }
-    TreeJob tj{}, *tree = nullptr;
+    for (size_t r = 0; r < (size_t)gj.T * n; r++) { rows[r].index = first_index + (int64_t)(r % (size_t)n); rows[r].count = 0; rows[r].total_px = 0; rows[r].avg_px = 0; }
     if (req) {      // scratch of the "with tree" form: the handle's tool workspaces, sized here before any pass is in flight
-        if (!canvas_of(h, w, req->vis_width, tj.cv)) { set_error("analyze (tree): empty canvas"); return TMAT_E_ARG; }
         const size_t cper = (size_t)tj.cv.vh * tj.cv.vw * 3, fper = (size_t)gp.fh * gp.fw;
         tj.sf = (double)w / (double)gp.fw;
         tj.rgb_out = req->rgb_out; tj.bars_out = req->bars_out; tj.cap_b = req->cap_b; tj.n_bars = req->n_bars;
@@ -427,6 +516,26 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
         if (!bg_all || !tj.dseg || !tj.dmm || !tj.drgb) return TMAT_E_HIP;
         tj.bg_all = bg_all;
         tj.doff = (int *)(tj.dmm + 4 * (size_t)K);
+        if (tj.barcode_png) {       // rectangle tables (<= cap_b bars per image) and the K barcode canvases of a pass
+            tj.drect = (BarRect *)ws_get(c, WS_GRID_BAR_RECT, (size_t)K * (size_t)req->cap_b * sizeof(BarRect) + (size_t)(K + 1) * sizeof(int) + 16);
+            tj.dbar = (uint8_t *)ws_get(c, WS_GRID_BAR_RGB, (size_t)K * tj.S * tj.S * 3);
+            if (!tj.drect || !tj.dbar) return TMAT_E_HIP;
+            tj.drect_off = (int *)(tj.drect + (size_t)K * (size_t)req->cap_b);       // BarRect is five words: word-aligned
+        }
+        if (tj.tree_png || tj.barcode_png) {        // encoder scratch (png.h:png_encode_launch) for the larger of the two shapes
+            size_t filt = 0, slots = 0, files = 0, meta_words = 0, kp_max = 0;
+            for (const PngShape *pg : {tj.tree_png ? &tj.pg_tree : nullptr, tj.barcode_png ? &tj.pg_bar : nullptr}) {
+                if (!pg) continue;
+                const size_t kp = (size_t)png_chunk(*pg, K);
+                filt = std::max(filt, kp * pg->raw); slots = std::max(slots, kp * pg->ns * PNG_SLOT);
+                files = std::max(files, kp * png_fcap(*pg)); meta_words = std::max(meta_words, kp * pg->ns * 4); kp_max = std::max(kp_max, kp);
+            }
+            tj.png_filt = (uint8_t *)ws_get(c, WS_GRID_PNG_FILT, filt); tj.png_slots = (uint8_t *)ws_get(c, WS_GRID_PNG_SLOTS, slots);
+            tj.png_files = (uint8_t *)ws_get(c, WS_GRID_PNG_FILES, files);
+            tj.png_meta = (uint32_t *)ws_get(c, WS_GRID_PNG_META, (meta_words + kp_max) * sizeof(uint32_t));     // the file sizes ride behind the stripe records
+            if (!tj.png_filt || !tj.png_slots || !tj.png_files || !tj.png_meta) return TMAT_E_HIP;
+            tj.png_dsz = tj.png_meta + meta_words;
+        }
         tree = &tj;
     }
     auto bg_at = [&](int p) { return tree ? const_cast<uint16_t *>(tj.bg_all) + (size_t)p * K * h * w : nullptr; };
@@ -487,7 +596,7 @@ static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, do
         if (p + 2 < P && !rc) rc = enqueue_down(c, cnt(p + 2), slot, g);
         for (int i = 0; i < cnt(p) && !rc; i++)
             if (!c->pass.conv_host[slot][i]) { set_error("analyze: Zhang thinning did not converge within its launch budget"); rc = TMAT_E_HIP; }
-        if (!rc) jobs[slot].th = std::thread(run_pass_host, c, slot, cnt(p), gp, rows + (size_t)p * K, &jobs[slot], tree, p * K, prune_at(p), stage);
+        if (!rc) jobs[slot].th = std::thread(run_pass_host, c, slot, cnt(p), gp, gj, rows, &jobs[slot], tree, p * K, prune_at(p), stage);
     }
     for (auto &j : jobs) { j.join(); if (j.rc && !rc) rc = j.rc; }
     hipStreamSynchronize(c->stream2);
@@ -908,6 +1017,48 @@ int tmat_analyze_batch_ex(tmat_handle hd, const uint16_t *imgs, int n, int H, in
     if (!mem.ok) return TMAT_E_HIP;
     if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) return TMAT_E_HIP;
     return tmat_analyze_batch_ex_dev(hd, dimg, n, H, W, o, rows);
+}
+
+// every argument check of the grid form, before the device is touched
+static int grid_args(const Ctx *c, const void *imgs, int n, int H, int W, const tmat_analyze_opts *o, const tmat_grid_opts *g, const tmat_row *rows)
+{
+    if (c && !has_model(c)) { set_error("tmat_analyze_batch_grid: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
+    if (!o || o->size != (uint32_t)sizeof(tmat_analyze_opts)) { set_error("tmat_analyze_batch_grid: unknown tmat_analyze_opts size"); return TMAT_E_ARG; }
+    if (!g || g->size != (uint32_t)sizeof(tmat_grid_opts)) { set_error("tmat_analyze_batch_grid: unknown tmat_grid_opts size"); return TMAT_E_ARG; }
+    if (g->n_thresh < 1 || !g->thresh) { set_error("tmat_analyze_batch_grid: n_thresh < 1 or no thresholds"); return TMAT_E_ARG; }
+    const bool tree = o->rgb_out || g->tree_png || g->barcode_png;
+    if (!c || !imgs || !rows || n < 0 || H < 1 || W < 1 || o->ds_width < 1 || (tree && (o->vis_width < 1 || !o->bars_out || o->cap_b < 0 || !o->n_bars)) ||
+        (g->tree_png && !g->tree_png_sizes) || (g->barcode_png && !g->barcode_png_sizes)) {
+        set_error("tmat_analyze_batch_grid: bad argument");
+        return TMAT_E_ARG;
+    }
+    return TMAT_OK;
+}
+
+int tmat_analyze_batch_grid_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, const tmat_analyze_opts *o, const tmat_grid_opts *g, tmat_row *rows)
+{
+    Ctx *c = (Ctx *)hd;
+    if (int rc = grid_args(c, imgs_dev, n, H, W, o, g, rows)) return rc;
+    if (n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    GraphParams gp{0, 0, g->thresh[0], g->thresh[1], o->smoothing_window_px, o->min_branch_length_px, o->max_branch_length_px, o->remove_isolated};
+    TreeReq req{o->vis_width, o->rgb_out, o->bars_out, o->cap_b, o->n_bars};
+    MaskReq mr{o->well_masks, o->pruning_masks};
+    return analyze_dev(c, imgs_dev, n, H, W, o->ds_ratio, o->ds_width, gp, o->first_index, rows, (o->rgb_out || g->tree_png || g->barcode_png) ? &req : nullptr,
+                       (o->well_masks || o->pruning_masks) ? &mr : nullptr, o->stage_out, g);
+}
+
+int tmat_analyze_batch_grid(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, const tmat_analyze_opts *o, const tmat_grid_opts *g, tmat_row *rows)
+{
+    Ctx *c = (Ctx *)hd;
+    if (int rc = grid_args(c, imgs, n, H, W, o, g, rows)) return rc;
+    if (n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    DevScope mem(c->ws_pool, nullptr);       // blocking copy below: nothing to drain
+    uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
+    if (!mem.ok) return TMAT_E_HIP;
+    if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) return TMAT_E_HIP;
+    return tmat_analyze_batch_grid_dev(hd, dimg, n, H, W, o, g, rows);
 }
 
 // a (n, per) of dtype TMAT_PIC_* -> out (n, per) u8: extrema and picture kernels of vis_kernels.hip, chunked to bound device memory

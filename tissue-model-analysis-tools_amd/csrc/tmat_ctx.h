@@ -143,6 +143,7 @@ enum ToolWs {
     WS_TREE_BG, WS_TREE_SEG, WS_TREE_MM, WS_TREE_RGB,                                                                               // tree overlay
     WS_WELL_MASK, WS_WELL_SEG,                                                                                                      // masked batch pipeline
     WS_STAGE_ORIG, WS_STAGE_PIC, WS_STAGE_MM,                                                                                       // stage pictures of the batch pipeline
+    WS_GRID_BAR_RECT, WS_GRID_BAR_RGB, WS_GRID_PNG_FILT, WS_GRID_PNG_SLOTS, WS_GRID_PNG_FILES, WS_GRID_PNG_META,                    // pictures of the grid form (tmat_analyze_batch_grid*)
     N_TOOL_WS
 };
 

@@ -457,49 +457,59 @@ def main(args=None):
         for i, img_id in enumerate(ids):
             branches.save_stage_pictures(pictures[i], out_root / "visualizations" / img_id, None if well is None else well[i])
 
-    def analyze_fn(batch, width_um, thresh, input_bits, ids):
-        pics = want_pictures(batch)
-        if tree_vis and not detect_well:
-            if pics:
-                rows, ex = branches.analyze_batch_ex(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits,
-                                                     tree=True, vis_width=vis_width, stage_pictures=True)
-                overlays, bars = ex["overlays"], ex["bars"]
-                write_pictures(ids, ex["pictures"])
-            else:
-                rows, overlays, bars = branches.analyze_batch_tree(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh,
-                                                                   input_bits=input_bits, vis_width=vis_width)
-            items = []
-            for img_id, ov, br in zip(ids, overlays, bars):
-                if len(br) == 0:
-                    print(f"No branches found for {img_id}.", flush=True)
-                if encoder is not None:
-                    items += branches.tree_picture_items(ov, br, out_root / "visualizations" / img_id, suffix_of[thresh], vis_width)
-                else:
-                    branches.save_tree_pictures(ov, br, out_root / "visualizations" / img_id, suffix_of[thresh], vis_width)
-            if items:                   # the batch's overlays in one encoder call, its barcodes in another
-                branches.write_png_batch(items, encoder)
-            return rows
-        if not detect_well and pics:
-            rows, ex = branches.analyze_batch_ex(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits,
-                                                 stage_pictures=True)
-            write_pictures(ids, ex["pictures"])
-            return rows
-        if not detect_well:
-            return branches.analyze_batch(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh, input_bits=input_bits)
-        warn_fn = lambda m: print(f"\033[93m[WARNING]\033[0m {m}", flush=True)       # noqa: E731
-        if not tree_vis:
-            # --detect-well through the batch pipeline (branches.analyze_batch_well): the masks do not depend on the graph thresholds --
-            # made once per batch (run_sharded hands the same array to every configuration of the grid), reused over the grid
-            if well_cache.get("batch") is not batch:
-                well_cache.clear()
-                well_cache["batch"] = batch
-            rows, well, pruning, *pictures = branches.analyze_batch_well(model.handle, batch, config, width_um, model.ds_ratio, thresh=thresh,
-                                                                         input_bits=input_bits, well_seed=well_seed, warn=warn_fn,
-                                                                         masks=well_cache.get("masks"), stage_pictures=pics)
-            well_cache["masks"] = (well, pruning)
-            if pics:
+    # The threshold grid from ONE pass of the network (branches.analyze_batch_grid): the first configuration run_sharded asks of a batch
+    # makes the grid call -- rows of every pair, the pictures written then and there --, the others are served from its rows (run_sharded
+    # hands the same array to every configuration of the grid).  The pictures go through in sub-batches that keep the picture buffers
+    # of one call under branches.grid_images_per_call's budget; only rows are held for the batch.
+    pairs = branches.grid_pairs(config)
+    grid_cache = {}
+    warn_fn = lambda m: print(f"\033[93m[WARNING]\033[0m {m}", flush=True)       # noqa: E731
+
+    def grid_rows(batch, width_um, input_bits, ids):
+        if detect_well:
+            # --detect-well through the batch pipeline (branches.analyze_batch_well): masks and pictures do not depend on the thresholds
+            rows_by, well, _, *pictures = branches.analyze_batch_well(model.handle, batch, config, width_um, model.ds_ratio, input_bits=input_bits,
+                                                                      well_seed=well_seed, warn=warn_fn, stage_pictures=vis, pairs=pairs)
+            if vis:
                 write_pictures(ids, pictures[0], well)
-            return rows
+            return rows_by
+        on_device = tree_vis and encoder is not None        # --png-encoder device: the files come out of the call, nothing is uploaded again
+        per = branches.grid_picture_bytes(batch.shape[1:], model.ds_ratio, vis_width, not on_device, on_device, on_device) if tree_vis else 0
+        step = branches.grid_images_per_call(len(pairs), per) if per else len(batch)
+        rows_by = {p: [] for p in pairs}
+        for i0 in range(0, len(batch), step):
+            sub_ids = ids[i0:i0 + step]
+            rb, ex = branches.analyze_batch_grid(model.handle, batch[i0:i0 + step], config, width_um, model.ds_ratio, pairs, first_index=i0,
+                                                 input_bits=input_bits, tree=tree_vis, vis_width=vis_width, stage_pictures=vis,
+                                                 tree_png=on_device, barcode_png=on_device, raw_overlays=not on_device, budget=1 << 62)
+            if vis:
+                write_pictures(sub_ids, ex["pictures"])
+            for p in pairs:
+                rows_by[p] += rb[p]
+                if not tree_vis:
+                    continue
+                items = []
+                for i, img_id in enumerate(sub_ids):
+                    br, vis_dir = ex["bars"][p][i], out_root / "visualizations" / img_id
+                    if len(br) == 0:            # the reference prints this and skips its plots (compute_branches.py:426-429)
+                        print(f"No branches found for {img_id}.", flush=True)
+                    elif on_device:
+                        items += [(ex["tree_png"][p][i], vis_dir, f"morse_tree{suffix_of[p]}.png"),
+                                  (ex["barcode_png"][p][i], vis_dir, f"barcode{suffix_of[p]}.png")]
+                    else:
+                        branches.save_tree_pictures(ex["overlays"][p][i], br, vis_dir, suffix_of[p], vis_width)
+                if items:
+                    branches.write_png_batch(items, encoder)
+        return rows_by
+
+    def analyze_fn(batch, width_um, thresh, input_bits, ids):
+        if not (detect_well and tree_vis):
+            if grid_cache.get("batch") is not batch:
+                grid_cache.clear()
+                grid_cache["batch"] = batch
+                grid_cache["rows"] = grid_rows(batch, width_um, input_bits, ids)
+            return grid_cache["rows"][thresh]
+        pics = want_pictures(batch)
         # with --tree-visualizations the pictures need the fields themselves: the staged entry points, image by image
         # --detect-well (compute_branches.py:318-337): the fields do not depend on the graph thresholds -- one staged pass per
         # batch (run_sharded hands the same array to every configuration of the grid), then the graph stages per configuration

@@ -37,6 +37,12 @@ class AnalyzeOpts(C.Structure):
                 ("rgb_out", C.c_void_p), ("bars_out", C.c_void_p), ("cap_b", C.c_int), ("n_bars", C.c_void_p), ("stage_out", C.c_void_p)]
 
 
+class GridOpts(C.Structure):
+    """tmat_grid_opts (include/tmat.h)"""
+    _fields_ = [("size", C.c_uint32), ("n_thresh", C.c_int), ("thresh", C.c_void_p), ("tree_png", C.c_void_p), ("tree_png_cap", C.c_size_t),
+                ("tree_png_sizes", C.c_void_p), ("barcode_png", C.c_void_p), ("barcode_png_cap", C.c_size_t), ("barcode_png_sizes", C.c_void_p)]
+
+
 class StackOpts(C.Structure):
     """tmat_stack_opts (include/tmat.h)"""
     _fields_ = [("size", C.c_uint32), ("ds_width", C.c_int), ("hessian", C.c_int), ("n_thresh", C.c_int), ("thresh", C.c_void_p),
@@ -141,6 +147,11 @@ def lib():
     L.tmat_analyze_batch_masked.argtypes = [vp, vp, i, i, i, C.c_double, i, f, f, i, i, i, i, C.c_int64, vp, vp, vp]
     L.tmat_analyze_batch_ex.argtypes = [vp, vp, i, i, i, C.POINTER(AnalyzeOpts), vp]
     L.tmat_analyze_batch_ex_dev.argtypes = [vp, vp, i, i, i, C.POINTER(AnalyzeOpts), vp]
+    L.tmat_analyze_batch_grid.argtypes = [vp, vp, i, i, i, C.POINTER(AnalyzeOpts), C.POINTER(GridOpts), vp]
+    L.tmat_analyze_batch_grid_dev.argtypes = [vp, vp, i, i, i, C.POINTER(AnalyzeOpts), C.POINTER(GridOpts), vp]
+    L.tmat_render_barcode.argtypes = [vp, vp, vp, i, i, vp]
+    L.tmat_render_barcode_png.argtypes = [vp, vp, vp, i, i, vp, sz, vp]
+    L.tmat_host_barcode_rects.argtypes = [vp, i, i, vp, i, C.POINTER(i)]
     L.tmat_stage_pictures.argtypes = [vp, vp, i, i, sz, vp]
     L.tmat_host_stage_pictures.argtypes = [vp, i, i, sz, vp]
     L.tmat_png_stripe.argtypes = []
@@ -178,6 +189,7 @@ EXPORTS = [
     "tmat_png_stripe", "tmat_png_bound", "tmat_png_encode_batch", "tmat_png_encode_batch_dev", "tmat_png_encode_batch_timed",
     "tmat_host_png_encode_batch", "tmat_render_tree_png",
     "tmat_analyze_stack_batch", "tmat_vessel_field_batch", "tmat_stack_pass_plan", "tmat_debug_stack_trace",
+    "tmat_analyze_batch_grid", "tmat_analyze_batch_grid_dev", "tmat_render_barcode", "tmat_render_barcode_png", "tmat_host_barcode_rects",
 ]
 
 
@@ -444,6 +456,21 @@ class Handle:
                                                                                 ptr(off), int(vis_width), *a),
                          (bg.shape[0], vh, vw, 3), "tmat_render_tree_png")
 
+    def render_barcode(self, bars_list, vis_width=2000):
+        """tmat_render_barcode: the barcode pictures of a batch on the device -> (n, S, S, 3) u8; bars_list: one (k, 2) f64 array per picture"""
+        bars, off = _barcode_args(bars_list)
+        S = int(round(vis_width * 0.9))
+        out = np.empty((len(bars_list), S, S, 3), np.uint8)
+        check(lib().tmat_render_barcode(self._h, ptr(bars), ptr(off), len(bars_list), int(vis_width), ptr(out)), "tmat_render_barcode")
+        return out
+
+    def render_barcode_png(self, bars_list, vis_width=2000):
+        """tmat_render_barcode_png: Handle.render_barcode's pictures as PNG files (bytes); the canvases stay on the device"""
+        bars, off = _barcode_args(bars_list)
+        S = int(round(vis_width * 0.9))
+        return _png_call(lambda _, n, H, W, ch, *a: lib().tmat_render_barcode_png(self._h, ptr(bars), ptr(off), n, int(vis_width), *a),
+                         (len(bars_list), S, S, 3), "tmat_render_barcode_png")
+
     def debug_poison(self, byte_pattern=0xFF):
         """test-only: fill every scratch workspace of the handle with a byte pattern (include/tmat.h:tmat_debug_poison)"""
         check(lib().tmat_debug_poison(self._h, int(byte_pattern)), "tmat_debug_poison")
@@ -653,6 +680,24 @@ def host_render_barcode(bars, vis_width=2000):
     out = np.empty((S, S, 3), np.uint8)
     check(lib().tmat_host_render_barcode(ptr(bars), len(bars), int(vis_width), ptr(out)), "tmat_host_render_barcode")
     return out
+
+
+def _barcode_args(bars_list):
+    """[(k, 2) bars] -> (concatenated (sum k + 1, 2) f64 with one spare row, offsets (n + 1) i32)"""
+    arrs = [np.asarray(b, np.float64).reshape(-1, 2) for b in bars_list]
+    off = np.zeros(len(arrs) + 1, np.int32)
+    off[1:] = np.cumsum([len(a) for a in arrs])
+    return np.ascontiguousarray(np.concatenate(arrs + [np.zeros((1, 2))])), off
+
+
+def host_barcode_rects(bars, vis_width=2000):
+    """tmat_host_barcode_rects: the (k, 5) int32 rectangle table (xa, xb, ya, yb, rgb) both barcode rasterisers fill; rows [ya, yb) count
+    from the bottom of the canvas, rgb = r | g << 8 | b << 16; empty when nothing is drawn"""
+    bars = np.ascontiguousarray(bars, np.float64).reshape(-1, 2)
+    out = np.zeros((max(len(bars), 1), 5), np.int32)
+    n = C.c_int(0)
+    check(lib().tmat_host_barcode_rects(ptr(bars), len(bars), int(vis_width), ptr(out), len(out), C.byref(n)), "tmat_host_barcode_rects")
+    return out[: n.value].copy()
 
 
 # -- host pixel stages (csrc/postproc.cpp); exposed for stage-wise parity tests --------------------

@@ -157,6 +157,140 @@ def analyze_batch_ex(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_
     return [(r.index, r.count, r.total_px, r.avg_px) for r in rows], extras
 
 
+def grid_pairs(config: dict):
+    """the (graph_thresh_1, graph_thresh_2) pairs of threshold_grid(config), in its order"""
+    return [(cfg["thresh1"], cfg["thresh2"]) for cfg, _ in threshold_grid(config)]
+
+
+def grid_images_per_call(n_thresh: int, bytes_per_picture: int, budget: int = 1 << 30) -> int:
+    """Images one tmat_analyze_batch_grid call takes when every (pair, image) owns bytes_per_picture bytes of the caller's picture
+    buffers: the largest count that keeps them under `budget`, at least one.  The 1 GiB default caps host memory; it is not tuned."""
+    return max(1, int(budget) // max(1, int(n_thresh) * int(bytes_per_picture)))
+
+
+def grid_picture_bytes(img_shape, ds_ratio: float, vis_width: int, raw: bool, tree_png: bool, barcode_png: bool) -> int:
+    """bytes of the caller's picture buffers one (pair, image) of analyze_batch_grid owns, for (H, W) images: the raw overlay, the worst-case
+    overlay file, the worst-case barcode file -- whichever are asked for"""
+    H, W = img_shape
+    vh, vw = _lib.tree_canvas_shape(int(round(W * ds_ratio)), int(round(H * ds_ratio)), vis_width)
+    S = int(round(vis_width * 0.9))
+    return (vh * vw * 3 if raw else 0) + (_lib.png_bound(vh, vw, 3) if tree_png else 0) + (_lib.png_bound(S, S, 3) if barcode_png else 0)
+
+
+def analyze_batch_grid(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_width_microns: float, ds_ratio: float = 0.625, pairs=None,
+                       first_index: int = 0, input_bits: int = 16, well_masks=None, pruning_masks=None, tree: bool = False, vis_width: int = 2000,
+                       stage_pictures: bool = False, tree_png: bool = False, barcode_png: bool = False, raw_overlays: bool = True,
+                       cap_bars: int = 4096, budget: int = 1 << 30):
+    """The threshold grid from ONE pass of the network (tmat_analyze_batch_grid): imgs (n, H, W) uint16, pairs [(graph_thresh_1,
+    graph_thresh_2)] (None: grid_pairs(config)) -> ({pair: rows as analyze_batch returns them at that pair}, extras).  The requests are
+    analyze_batch_ex's; what depends on the pair comes back per pair:
+      tree            extras["bars"] = {pair: [bars (k, 2) f64 per image]} and, with raw_overlays, extras["overlays"] = {pair: (n, vh, vw, 3) u8}
+      tree_png        extras["tree_png"] = {pair: [PNG file (bytes) per image]}: the overlays encoded on the device, nothing raw crosses when
+                      raw_overlays is False
+      barcode_png     extras["barcode_png"] = {pair: [PNG file per image]}: rasterised and encoded on the device from that pair's bars
+      stage_pictures  extras["pictures"] (n, 4, h, w) u8, once: they do not depend on the pair
+    tree_png / barcode_png imply tree.  With pictures the images go through in chunks of grid_images_per_call, so that the picture buffers
+    of one call stay under `budget` bytes."""
+    imgs = np.ascontiguousarray(imgs, np.uint16)
+    n, H, W = imgs.shape
+    pairs = grid_pairs(config) if pairs is None else [(p[0], p[1]) for p in pairs]
+    T = len(pairs)
+    if T < 1:
+        raise ValueError("analyze_batch_grid: no threshold pair")
+    tree = bool(tree or tree_png or barcode_png)
+    raw = bool(tree and raw_overlays)
+    hh, ww = int(round(W * ds_ratio)), int(round(H * ds_ratio))            # cv2 reads dsize as (width, height)
+    fh, fw = dsamp_shape((H, W))
+
+    def as_u8(m, shape, what):
+        if m is None:
+            return None
+        m = np.asarray(m)
+        if m.shape != (n,) + tuple(shape):
+            raise ValueError(f"analyze_batch_grid: {what} have shape {m.shape}, expected {(n,) + tuple(shape)}")
+        return np.ascontiguousarray(m != 0, np.uint8)
+    well = as_u8(well_masks, (hh, ww), "well_masks")
+    pruning = as_u8(pruning_masks, (fh, fw), "pruning_masks")
+    sw_px, min_px, max_px = graph_px_params(config, DOWNSAMPLE_WIDTH, image_width_microns)
+    rows_by = {p: [] for p in pairs}
+    extras = {}
+    if tree:
+        extras["bars"] = {p: [] for p in pairs}
+    if raw:
+        extras["overlays"] = {p: [] for p in pairs}
+    if tree_png:
+        extras["tree_png"] = {p: [] for p in pairs}
+    if barcode_png:
+        extras["barcode_png"] = {p: [] for p in pairs}
+    pics = []
+    if n == 0:
+        if raw:
+            vh, vw = _lib.tree_canvas_shape(hh, ww, vis_width)
+            extras["overlays"] = {p: np.empty((0, vh, vw, 3), np.uint8) for p in pairs}
+        if stage_pictures:
+            extras["pictures"] = np.empty((0, 4, hh, ww), np.uint8)
+        return rows_by, extras
+    thresh = np.ascontiguousarray(np.asarray(pairs, np.float32).reshape(T, 2))
+    L = _lib.lib()
+    _lib.check(L.tmat_set_input_depth(handle.raw, int(input_bits)), "tmat_set_input_depth")
+    vh = vw = S = tcap = bcap = 0
+    if tree:
+        vh, vw = _lib.tree_canvas_shape(hh, ww, vis_width)
+        S = int(round(vis_width * 0.9))
+        tcap = _lib.png_bound(vh, vw, 3) if tree_png else 0
+        bcap = _lib.png_bound(S, S, 3) if barcode_png else 0
+    per_picture = (vh * vw * 3 if raw else 0) + tcap + bcap
+    step = grid_images_per_call(T, per_picture, budget) if per_picture else n
+    for i0 in range(0, n, step):
+        k = min(step, n - i0)
+        rows = (_lib.Row * (T * k))()
+        o = _lib.AnalyzeOpts(size=C.sizeof(_lib.AnalyzeOpts), ds_ratio=float(ds_ratio), ds_width=DOWNSAMPLE_WIDTH, smoothing_window_px=int(sw_px),
+                             min_branch_length_px=int(min_px), max_branch_length_px=int(max_px or 0),
+                             remove_isolated=int(bool(config.get("remove_isolated_branches", False))), first_index=int(first_index) + i0,
+                             well_masks=None if well is None else well[i0:].ctypes.data,
+                             pruning_masks=None if pruning is None else pruning[i0:].ctypes.data)
+        g = _lib.GridOpts(size=C.sizeof(_lib.GridOpts), n_thresh=T, thresh=thresh.ctypes.data)
+        if stage_pictures:
+            pics.append(np.empty((k, 4, hh, ww), np.uint8))
+            o.stage_out = pics[-1].ctypes.data
+        nb = np.zeros((T, k), np.int32)
+        if tree:
+            o.vis_width, o.n_bars = int(vis_width), nb.ctypes.data
+            if raw:
+                rgb = np.empty((T, k, vh, vw, 3), np.uint8)
+                o.rgb_out = rgb.ctypes.data
+            if tree_png:
+                tfiles, tsizes = np.empty((T, k, tcap), np.uint8), np.zeros((T, k), np.uintp)
+                g.tree_png, g.tree_png_cap, g.tree_png_sizes = tfiles.ctypes.data, tcap, tsizes.ctypes.data
+            if barcode_png:
+                bfiles, bsizes = np.empty((T, k, bcap), np.uint8), np.zeros((T, k), np.uintp)
+                g.barcode_png, g.barcode_png_cap, g.barcode_png_sizes = bfiles.ctypes.data, bcap, bsizes.ctypes.data
+        # a branch holds at least one vertex of its own, so fh * fw bars always suffice: one retry with that capacity when cap_bars is too small
+        for cap in (int(cap_bars), max(int(cap_bars), fh * fw)):
+            bars = np.empty((T, k, cap if tree else 0, 2), np.float64)
+            if tree:
+                o.bars_out, o.cap_b = bars.ctypes.data, cap
+            rc = L.tmat_analyze_batch_grid(handle.raw, _lib.ptr(imgs[i0:]), k, H, W, C.byref(o), C.byref(g), rows)
+            if rc != _lib.E_CAP or cap >= fh * fw or not tree:
+                break
+        _lib.check(rc, "tmat_analyze_batch_grid")
+        for t, p in enumerate(pairs):
+            rows_by[p] += [(r.index, r.count, r.total_px, r.avg_px) for r in rows[t * k:(t + 1) * k]]
+            if tree:
+                extras["bars"][p] += [bars[t, i, : nb[t, i]].copy() for i in range(k)]
+            if raw:
+                extras["overlays"][p].append(rgb[t])
+            if tree_png:
+                extras["tree_png"][p] += [tfiles[t, i, : int(tsizes[t, i])].tobytes() for i in range(k)]
+            if barcode_png:
+                extras["barcode_png"][p] += [bfiles[t, i, : int(bsizes[t, i])].tobytes() for i in range(k)]
+    if raw:
+        extras["overlays"] = {p: np.concatenate(v) for p, v in extras["overlays"].items()}
+    if stage_pictures:
+        extras["pictures"] = np.concatenate(pics)
+    return rows_by, extras
+
+
 def _unique_path(vis_dir, name):
     """vis_dir / name under the reference's "-N" unique-name rule (helper.get_unique_output_filepath); makes vis_dir"""
     import os
@@ -336,13 +470,14 @@ def analyze_batch_masked(handle: _lib.Handle, imgs: np.ndarray, config: dict, im
 
 def analyze_batch_well(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_width_microns: float, ds_ratio: float = 0.625,
                        thresh=(5.0, 10.0), first_index: int = 0, input_bits: int = 16, well_seed: int = 0, warn=print, masks=None,
-                       stage_pictures: bool = False):
+                       stage_pictures: bool = False, pairs=None):
     """The --detect-well form of the 2-D branch through the batch pipeline: the rows of well_fields + well_rows.  Lanczos + rescale
     (tmat_preprocess_batch) -> make_well_masks_batch on those images (the superellipse fit of the whole batch on the device) ->
     pruning masks = resize(~shrunken, field shape, order 0) (compute_branches.py:359-361) -> tmat_analyze_batch_masked, which repeats
     the Lanczos pass inside its pipeline.  masks: a (well, pruning) pair from an earlier call on the same images (the masks do not depend
     on the graph thresholds).  Returns (rows, well (n, h, w) bool, pruning (n, fh, fw) bool); with stage_pictures also the (n, 4, h, w) u8
-    pictures of analyze_batch_ex, out of the same call."""
+    pictures of analyze_batch_ex, out of the same call.  pairs (a list of (graph_thresh_1, graph_thresh_2); thresh is then not read): the
+    whole grid from one masked pass (analyze_batch_grid) -- rows is then {pair: rows}."""
     from . import well_mask_generation as wmg
     imgs = np.ascontiguousarray(imgs, np.uint16)
     n, H, W = imgs.shape
@@ -357,6 +492,10 @@ def analyze_batch_well(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
         pruning = np.stack([wmg._resize_nearest(np.logical_not(shrunken[i]), fshape) for i in range(n)]).astype(bool)
     else:
         well, pruning = masks
+    if pairs is not None:
+        rows, extras = analyze_batch_grid(handle, imgs, config, image_width_microns, ds_ratio, pairs, first_index, input_bits, well, pruning,
+                                          stage_pictures=stage_pictures)
+        return (rows, well, pruning, extras["pictures"]) if stage_pictures else (rows, well, pruning)
     if stage_pictures:
         rows, extras = analyze_batch_ex(handle, imgs, config, image_width_microns, ds_ratio, thresh, first_index, input_bits, well, pruning,
                                         stage_pictures=True)
