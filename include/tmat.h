@@ -846,6 +846,22 @@ int tmat_debug_poison(tmat_handle h, int byte_pattern);
 int tmat_debug_held_bytes(tmat_handle h, size_t *device_bytes, size_t *pinned_bytes);
 
 /*
+ * Test-only (tests/test_gpu_morph_stages.py): tmat_filter_mask_batch with its intermediate results.  The same kernels, launches and
+ * workspace as tmat_filter_mask_batch; afterwards the stages are copied out of the workspace.  mask (n, h, w) u8.  Outputs, each of
+ * which may be null (all of them null is a bad argument, as a null `filtered` is for tmat_filter_mask_batch):
+ *   median         (n, h, w) u8    the mask that gets labelled (the 13-tap median of `mask`, or `mask` != 0 with use_median 0)
+ *   labels         (n, h, w) i32   smallest flat pixel index (y * w + x, per image) of the pixel's 8-connected component, -1 on background
+ *   stats          (n, 4, h, w) i32  area and the perimeter code counts n1, n2, n3 (skimage perimeter, 4-neighbourhood: weights 1,
+ *                                  sqrt 2, (1 + sqrt 2) / 2) of each component, stored at its root pixel, 0 everywhere else
+ *   skeleton       (n, h, w) u8    the converged Zhang thinning of `median`
+ *   filtered       (n, h, w) u8    what tmat_filter_mask_batch returns
+ *   thin_launches  (n) i32         thinning launches (4 full iterations each) that removed a pixel of that image
+ * Argument checks and the "thinning did not converge" error are tmat_filter_mask_batch's.  A handle from tmat_create_plain is enough.
+ */
+int tmat_debug_filter_stages(tmat_handle h, const uint8_t *mask, int n, int hh, int ww, int use_median, int remove_isolated, uint8_t *median,
+                             int32_t *labels, int32_t *stats, uint8_t *skeleton, uint8_t *filtered, int32_t *thin_launches);
+
+/*
  * Region plan of the UNet up path for an (hh, ww) image tiled with `patch`-wide windows (host arithmetic, no GPU and no handle).
  * The smooth blend discards the padding ring, so of every patch it reads the rectangle  patch ∩ interior  only; the tiled entry points
  * compute just that rectangle, grown layer by layer by the taps' reach, in every up-path layer (TMAT_ROI=0 at tmat_create: whole

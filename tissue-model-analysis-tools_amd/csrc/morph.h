@@ -7,6 +7,19 @@ namespace tmat {
 size_t morph_workspace_bytes(int k, int H, int W);
 // device pointer to the k per-image "thinning converged" flags inside the workspace (1 = converged)
 const int *morph_done_flags(void *workspace, int k, int H, int W);
+// Where filter_mask_dev keeps its intermediate results inside the workspace (device pointers, valid after the call until the
+// workspace's next one): med, skA (k, H, W) u8 -- the mask that gets labelled and the converged Zhang skeleton (skB holds the same
+// once `done` is set); ML (k, H, W) int -- root pixel index of the mask component, -1 on the background (SL: the same of the
+// skeleton); area, n1, n2, n3 (k, H, W) int, consecutive planes -- pixel count and perimeter code counts at each root's index, 0
+// elsewhere; done (k) as morph_done_flags; changed (launches, k) -- 1 where a thinning launch removed something from that image.
+struct MorphLayout {
+    uint8_t *seg, *med, *skA, *skB;
+    int *ML, *SL, *g, *area, *n1, *n2, *n3, *fork, *drop, *st, *flags, *done, *changed, *tflags;
+    int launches, tiles_x, tiles_y;
+    size_t flag_ints;                  // ints from `flags` to the end of the per-tile flags
+    size_t bytes;                      // what the layout needs from `workspace` on (morph_workspace_bytes adds slack)
+};
+MorphLayout morph_layout(void *workspace, int k, int H, int W);       // workspace null: launches, tiles, flag_ints and bytes only
 // pred (k, H, W) f64 device -> filtered mask (k, H, W) u8 device, EDT of it (k, H, W) f64 device; all async on `s`
 int filter_edt_dev(const double *pred, int k, int H, int W, int remove_isolated, void *workspace, uint8_t *filt_out,
                    double *dist_out, hipStream_t s);

@@ -359,21 +359,29 @@ void launch_edt(const uint8_t *mask, int k, int H, int W, int *g, int *st, int *
 // ---------------------------------------------------------------------------------------------
 // driver
 // ---------------------------------------------------------------------------------------------
-size_t morph_workspace_bytes(int k, int H, int W)
-{
-    const size_t npx = (size_t)k * H * W;
-    // seg, med, skA, skB (u8) + ML, SL, g, area, n1, n2, n3, fork, drop (int) + st (2 ints) + flags
-    const int launches = ((H > W ? H : W) / 2 + 8 + ZH_IT - 1) / ZH_IT + 1;      // thinning launches (filter_edt_dev)
-    const size_t tiles = (size_t)((W + ZH_TI - 1) / ZH_TI) * ((H + ZH_TI - 1) / ZH_TI);
-    return npx * 4 + npx * sizeof(int) * 11 + (3 + (size_t)launches + 3 * tiles) * k * sizeof(int) + 4096;
-}
-const int *morph_done_flags(void *workspace, int k, int H, int W)
+// The one place that knows the workspace's layout: 4 u8 planes (seg, med, skA, skB), then from the next 16-byte boundary 9 int planes
+// (ML, SL, g, area, n1, n2, n3, fork, drop), st (2 int planes) and the flags.  A null workspace gives the counts and `bytes` only.
+MorphLayout morph_layout(void *workspace, int k, int H, int W)
 {
     const size_t n = (size_t)k * H * W;
-    uint8_t *skB = (uint8_t *)workspace + 3 * n;
-    int *ML = (int *)(((uintptr_t)(skB + n) + 15) & ~(uintptr_t)15);
-    return ML + 11 * n + 2 * k;
+    MorphLayout m{};
+    m.launches = ((H > W ? H : W) / 2 + 8 + ZH_IT - 1) / ZH_IT + 1;      // thinning launches (filter_mask_dev)
+    m.tiles_x = (W + ZH_TI - 1) / ZH_TI; m.tiles_y = (H + ZH_TI - 1) / ZH_TI;
+    m.flag_ints = (3 + (size_t)m.launches + 3 * (size_t)m.tiles_x * m.tiles_y) * k;
+    m.bytes = 4 * n + 15 + (11 * n + m.flag_ints) * sizeof(int);         // 15: the most the alignment of ML can skip
+    if (!workspace) return m;
+    m.seg = (uint8_t *)workspace; m.med = m.seg + n; m.skA = m.med + n; m.skB = m.skA + n;
+    m.ML = (int *)(((uintptr_t)(m.skB + n) + 15) & ~(uintptr_t)15);
+    m.SL = m.ML + n; m.g = m.SL + n; m.area = m.g + n; m.n1 = m.area + n; m.n2 = m.n1 + n; m.n3 = m.n2 + n; m.fork = m.n3 + n; m.drop = m.fork + n;
+    m.st = m.drop + n;                  // 2n ints
+    m.flags = m.st + 2 * n;             // [0,k): zhang changed, [k,2k): any_zero, [2k,3k): zhang done
+    m.done = m.flags + 2 * k;
+    m.changed = m.flags + 3 * k;        // [launches][k]
+    m.tflags = m.changed + (size_t)m.launches * k;      // [3][k][tiles]: per-tile "removed something" of the launches it - 1, it, it + 1
+    return m;
 }
+size_t morph_workspace_bytes(int k, int H, int W) { return morph_layout(nullptr, k, H, W).bytes + 4096; }
+const int *morph_done_flags(void *workspace, int k, int H, int W) { return morph_layout(workspace, k, H, W).done; }
 
 int filter_edt_dev(const double *pred, int k, int H, int W, int remove_isolated, void *workspace, uint8_t *filt_out,
                    double *dist_out, hipStream_t s)
@@ -389,11 +397,10 @@ int filter_mask_dev(const double *pred, const uint8_t *mask_in, int k, int H, in
     if (!upload_lut()) { set_error("morph: cannot upload the skeletonize table"); return -2; }
     const int npx = H * W;
     const size_t n = (size_t)k * npx;
-    uint8_t *seg = (uint8_t *)workspace, *med = seg + n, *skA = med + n, *skB = skA + n;
-    int *ML = (int *)(((uintptr_t)(skB + n) + 15) & ~(uintptr_t)15);
-    int *SL = ML + n, *g = SL + n, *area = g + n, *n1 = area + n, *n2 = n1 + n, *n3 = n2 + n, *fork = n3 + n, *drop = fork + n;
-    int *st = drop + n;                 // 2n ints
-    int *flags = st + 2 * n;            // [0,k): zhang changed, [k,2k): any_zero, [2k,3k): zhang done
+    const MorphLayout lay = morph_layout(workspace, k, H, W);
+    uint8_t *seg = lay.seg, *med = lay.med, *skA = lay.skA, *skB = lay.skB;
+    int *ML = lay.ML, *SL = lay.SL, *g = lay.g, *area = lay.area, *n1 = lay.n1, *n2 = lay.n2, *n3 = lay.n3, *fork = lay.fork, *drop = lay.drop;
+    int *st = lay.st, *flags = lay.flags;
     const dim3 grid((npx + 255) / 256 < 1024 ? (npx + 255) / 256 : 1024, k), blk(256);
 
     if (mask_in) hipLaunchKernelGGL(binarize_kernel, grid, blk, 0, s, mask_in, seg, npx);
@@ -411,13 +418,9 @@ int filter_mask_dev(const double *pred, const uint8_t *mask_in, int k, int H, in
     // No host round trip: changed[launch][image] flags live on the device; once a launch removes nothing for an image
     // the remaining launches return at once.  A component of width w needs about w/2 iterations;
     // max(H, W)/2 + 8 always suffice (checked by the caller through flags[2k..3k) == 1, copied back with the results).
-    int *done = flags + 2 * k;
-    const int max_pairs = (H > W ? H : W) / 2 + 8;
-    const int launches = (max_pairs + ZH_IT - 1) / ZH_IT + 1;
-    int *chg = flags + 3 * k;            // [launches][k]
-    const int tiles_x = (W + ZH_TI - 1) / ZH_TI, tiles_y = (H + ZH_TI - 1) / ZH_TI;
-    int *tflags = chg + (size_t)launches * k;          // [3][k][tiles]: per-tile "removed something" of the launches it - 1, it, it + 1
-    if (hipMemsetAsync(flags, 0, (3 + (size_t)launches + 3 * (size_t)tiles_x * tiles_y) * k * sizeof(int), s) != hipSuccess) { set_error("morph: memset"); return -2; }
+    int *done = lay.done, *chg = lay.changed, *tflags = lay.tflags;
+    const int launches = lay.launches, tiles_x = lay.tiles_x, tiles_y = lay.tiles_y;
+    if (hipMemsetAsync(flags, 0, lay.flag_ints * sizeof(int), s) != hipSuccess) { set_error("morph: memset"); return -2; }
     const dim3 zgrid(tiles_x * tiles_y, k);
     for (int it = 0; it < launches; it++) {
         const uint8_t *src = (it & 1) ? skB : skA;

@@ -786,6 +786,42 @@ int tmat_filter_mask_batch(tmat_handle hd, const uint8_t *mask, int n, int hh, i
     return TMAT_OK;
 }
 
+// Test-only (tests/test_gpu_morph_stages.py): tmat_filter_mask_batch's call of filter_mask_dev, plus copies of what its workspace holds
+int tmat_debug_filter_stages(tmat_handle hd, const uint8_t *mask, int n, int hh, int ww, int use_median, int remove_isolated, uint8_t *median,
+                             int32_t *labels, int32_t *stats, uint8_t *skeleton, uint8_t *filtered, int32_t *thin_launches)
+{
+    Ctx *c = (Ctx *)hd;
+    const bool any_out = median || labels || stats || skeleton || filtered || thin_launches;
+    if (!c || !mask || !any_out || n < 0 || hh < 1 || ww < 1) { set_error("tmat_debug_filter_stages: bad argument"); return TMAT_E_ARG; }
+    if (n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    const size_t per = (size_t)hh * ww, npx = (size_t)n * per;
+    DevScope mem(c->ws_pool, c->stream);
+    int *conv = mem.host<int>(n);
+    uint8_t *dm = mem.alloc_from(mask, npx), *df = mem.alloc<uint8_t>(npx);
+    void *ws = mem.alloc_bytes(morph_workspace_bytes(n, hh, ww));
+    if (!mem.ok || filter_mask_dev(nullptr, dm, n, hh, ww, use_median != 0, remove_isolated != 0, ws, df, nullptr, c->stream)) return TMAT_E_HIP;
+    const MorphLayout lay = morph_layout(ws, n, hh, ww);
+    int *chg = mem.host<int>((size_t)lay.launches * n);
+    mem.d2h(median, lay.med, npx);
+    mem.d2h(labels, lay.ML, npx * sizeof(int));
+    for (int i = 0; i < n && stats; i++) {           // area, n1, n2, n3 are consecutive (n, H, W) planes -> (n, 4, H, W)
+        const int *planes[4] = {lay.area, lay.n1, lay.n2, lay.n3};
+        for (int j = 0; j < 4; j++) mem.d2h(stats + ((size_t)i * 4 + j) * per, planes[j] + (size_t)i * per, per * sizeof(int));
+    }
+    mem.d2h(skeleton, lay.skA, npx);
+    mem.d2h(filtered, df, npx);
+    mem.d2h(chg, lay.changed, (size_t)lay.launches * n * sizeof(int));
+    mem.d2h(conv, lay.done, n * sizeof(int));
+    if (mem.finish()) return TMAT_E_HIP;
+    for (int i = 0; i < n && thin_launches; i++) {
+        thin_launches[i] = 0;
+        for (int it = 0; it < lay.launches; it++) thin_launches[i] += chg[(size_t)it * n + i] != 0;
+    }
+    for (int i = 0; i < n; i++) if (!conv[i]) { set_error("tmat_debug_filter_stages: thinning did not converge"); return TMAT_E_HIP; }
+    return TMAT_OK;
+}
+
 int tmat_finish_batch(tmat_handle hd, const double *pred, const double *dist, const uint8_t *skel, int n, int hh, int ww, int out_h,
                       int out_w, float *field, float *field255)
 {

@@ -84,6 +84,7 @@ def lib():
     L.tmat_medial_axis_batch.argtypes = [vp, vp, i, i, i, vp, vp]
     L.tmat_finish_batch.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp]
     L.tmat_filter_mask_batch.argtypes = [vp, vp, i, i, i, i, i, vp]
+    L.tmat_debug_filter_stages.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
     L.tmat_gather_rows.argtypes = [vp, vp, i, vp, vp]
     L.tmat_zproj_batch.argtypes = [vp, vp, i, i, i, i, i, vp]
     L.tmat_zproj_dev.argtypes = [vp, vp, i, i, i, i, i, vp]
@@ -176,7 +177,7 @@ EXPORTS = [
     "tmat_dmt_graph", "tmat_dmt_graph_batch", "tmat_morse_stats",
     "tmat_morse_tree", "tmat_branch_color", "tmat_render_tree", "tmat_render_tree_timed", "tmat_host_render_tree", "tmat_host_render_barcode",
     "tmat_analyze_batch_dev", "tmat_analyze_batch", "tmat_analyze_batch_tree_dev", "tmat_analyze_batch_tree", "tmat_dev_alloc", "tmat_dev_free", "tmat_dev_upload", "tmat_dev_download",
-    "tmat_prof_enable", "tmat_prof_read", "tmat_debug_poison", "tmat_debug_held_bytes", "tmat_set_precision", "tmat_set_input_norm", "tmat_preprocess_batch", "tmat_well_threshold", "tmat_well_threshold_f64", "tmat_canny_mask", "tmat_superellipse_table", "tmat_superellipse_search",
+    "tmat_prof_enable", "tmat_prof_read", "tmat_debug_poison", "tmat_debug_held_bytes", "tmat_debug_filter_stages", "tmat_set_precision", "tmat_set_input_norm", "tmat_preprocess_batch", "tmat_well_threshold", "tmat_well_threshold_f64", "tmat_canny_mask", "tmat_superellipse_table", "tmat_superellipse_search",
     "tmat_superellipse_masks", "tmat_resize_nearest_u8", "tmat_analyze_batch_masked", "tmat_host_lanczos4_u16", "tmat_host_rescale01_u16",
     "tmat_host_rescale255_f32", "tmat_host_filter_mask", "tmat_host_skeletonize", "tmat_host_medial_axis",
     "tmat_host_permutation", "tmat_host_postprocess",
@@ -290,6 +291,20 @@ class Handle:
         check(lib().tmat_filter_mask_batch(self._h, ptr(m), m.shape[0], m.shape[1], m.shape[2], int(bool(use_median)),
                                            int(bool(remove_isolated)), ptr(out)), "tmat_filter_mask_batch")
         return out.astype(bool)
+
+    def debug_filter_stages(self, masks, use_median=True, remove_isolated=True):
+        """test-only: filter_mask with its stages (include/tmat.h:tmat_debug_filter_stages) on (n, h, w) masks -> dict of
+        median, skeleton, filtered (n, h, w) u8, labels (n, h, w) i32, stats (n, 4, h, w) i32 (area, n1, n2, n3), thin_launches (n) i32"""
+        m = np.ascontiguousarray(np.asarray(masks) != 0, np.uint8)
+        n = m.shape[0]
+        out = {k: np.empty(m.shape, np.uint8) for k in ("median", "skeleton", "filtered")}
+        out["labels"] = np.empty(m.shape, np.int32)
+        out["stats"] = np.empty((n, 4) + m.shape[1:], np.int32)
+        out["thin_launches"] = np.empty(n, np.int32)
+        check(lib().tmat_debug_filter_stages(self._h, ptr(m), n, m.shape[1], m.shape[2], int(bool(use_median)), int(bool(remove_isolated)),
+                                             *(ptr(out[k]) for k in ("median", "labels", "stats", "skeleton", "filtered", "thin_launches"))),
+              "tmat_debug_filter_stages")
+        return out
 
     ZPROJ_METHODS = {"fs": 0, "min": 1, "max": 2, "avg": 3, "med": 4}
 
