@@ -985,6 +985,22 @@ int tmat_roi_plan_share_rect(int hh, int ww, int patch, int n_up, const int *up_
                              unsigned fused_mask, int max_classes, int *n_classes, int *share, int *n_rects, int *rects,
                              unsigned char *comp, int fill_cap, int *n_fill, int *fills, double *mac_rect, double *bytes_rect, int *info);
 /*
+ * The shared-interior form of the FUSED levels' rectangle launches (the stride-2 residual 1x1 and the pooling fix-up of the 160² and 80²
+ * levels, the stem at the even pixels; roi_plan.h:RoiDownPlan::fcomp), in tables of its own again: n_rects [6 n_down + 4][max_classes]
+ * and rects [6 n_down + 4][max_classes][4][4] (y0, x0, rows, columns: at most four disjoint rectangles per class inside rect_live, what
+ * tmat_roi_plan_share_rect gives for every layer the form leaves alone), comp [6 n_down + 4][max_classes][2 axes][patch] bytes (the exact
+ * sets in force, every layer, before the columns are rounded), fills [n_fill][7] (layer, class, direction, y0, x0, rows, columns): the
+ * copies of a pooled output as halo strips -- only the shared pixels that the next level's exact sets tap --, fill_on [6 n_down + 4]: 1
+ * where the strips stand in place of the layer's items of tmat_roi_plan_share, totals [6 n_down + 4][6] per image: planned
+ * multiply-accumulates, planned bytes, planned pixels, pixels of rect_live, copied pixels without and with the form, info [3]: some
+ * table differs from the older forms', the mask of levels in force, the longest segment table of a launch.  Host arithmetic, no GPU.
+ * The launches take the form where the rectangle launches' form of the unfused level runs, by the switch TMAT_ROI_SHARE_FUSED_RECT (read
+ * at tmat_create, 0 or 1): unset, the batch pipeline runs it and tmat_predict_smooth does not; 0: nobody; 1: both.
+ */
+int tmat_roi_plan_share_fused_rect(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                   unsigned fused_mask, int max_classes, int *n_classes, int *n_rects, int *rects, unsigned char *comp,
+                                   int fill_cap, int *n_fill, int *fills, int *fill_on, double *totals, int *info);
+/*
  * Test-only: the host-side argument checks of the share-fill launcher on a table of n_items items [7] = first patch, patches,
  * direction, y0, x0, rows, columns of a tensor (n_patches, side, side, channels) and a neighbour table [n_patches][3].  Nothing is
  * launched.  TMAT_OK when the launcher would take them; TMAT_E_ARG with the reason in tmat_last_error otherwise.
@@ -999,6 +1015,9 @@ int tmat_debug_share_fill_check(int n_patches, int side, int channels, const int
 int tmat_debug_sep_tiles(tmat_handle h, int cap, int *n, long long *planned, long long *full);
 /* Test-only: the longest segment table among the rectangle launches of the last down pass, the constant patches' segment included (0: full-frame). */
 int tmat_debug_down_segs(tmat_handle h, int *max_segs);
+/* Test-only: the lengths of the segment tables of all rectangle launches of the last down pass added up (the fused levels' form makes no
+ * table longer than the longest of the unfused level's form: it shows in this sum). */
+int tmat_debug_down_seg_total(tmat_handle h, int *total);
 
 #ifdef __cplusplus
 }

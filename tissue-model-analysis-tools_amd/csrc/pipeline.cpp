@@ -181,7 +181,8 @@ static int enqueue_down(Ctx *c, int k, int slot, const TileGeom &g)
     float *pin = patch_in_of(c, slot, g);
     int rc = oversize ? unet_forward_dev(c, pin, k * g.tiles_per_img, c->patch_out, s)
                       : unet_down_dev(c, pin, k * g.tiles_per_img, c->dout[slot], s, roi_find(c, g),
-                                      c->roi_const != 0 && k <= c->const_cap ? c->padval[slot] : nullptr, c->roi_share != 0, c->roi_share_rect != 0);
+                                      c->roi_const != 0 && k <= c->const_cap ? c->padval[slot] : nullptr, c->roi_share != 0, c->roi_share_rect != 0,
+                                      c->roi_share_fused_rect != 0);
     if (rc) return rc;
     TMAT_HIP(hipEventRecord(c->ev_down[slot], s));
     c->down_pending[slot] = true;

@@ -523,6 +523,145 @@ void share_rect_classes(RoiPlan &p, const std::vector<AxisKey> &keys, const int 
     if (!d.rect_any) d.rect_fill.clear();
 }
 
+// per class: the fused levels' rectangle launches in the shared-interior form and the halo strips of their pooled outputs
+// (RoiDownPlan::fcomp); after share_rect_classes
+void share_fused_rect_classes(RoiPlan &p, const std::vector<AxisKey> &keys, const int *krow, const int *kcol)
+{
+    RoiDownPlan &d = p.down;
+    const int NL = d.n_layers, ws = p.ws, L = 6 * d.n_down, bl = d.n_down - 1;
+    d.fused_rect_any = false; d.fused_fill.clear(); d.fused_rect_segs = 0;
+    for (int l = 0; l < NL; l++) d.fused_fill_on[l] = false;
+    // the exact sets in force: rcomp_mask in the unfused last level, comp elsewhere
+    d.fcomp_mask = d.comp;
+    const size_t per_layer = (size_t)ROI_MAX_CLASSES * 2 * ws;
+    if (d.rect_any)
+        std::copy(d.rcomp_mask.begin() + 6 * bl * per_layer, d.rcomp_mask.begin() + (6 * bl + 6) * per_layer, d.fcomp_mask.begin() + 6 * bl * per_layer);
+    auto mask_at = [&](int l, int k, int axis) { return d.fcomp_mask.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * ws + (size_t)axis * ws; };
+    auto get = [&](int l, int k, int axis) { const unsigned char *m = mask_at(l, k, axis); return Mask(m, m + d.res[l]); };
+    auto within = [](Mask a, Iv lv) { for (int i = 0; i < (int)a.size(); i++) a[i] = a[i] && in_iv(lv, i); return a; };
+    const bool form = d.share_any && d.rect_any;
+    auto in_form = [&](int b) { return form && b >= 0 && b < d.n_down && (((d.fused_mask & ROI_SHARE_LEVELS & ROI_SHARE_FUSED_RECT_LEVELS) >> b) & 1u); };
+    bool takes[ROI_MAX_DOWN][ROI_MAX_CLASSES] = {};
+    // the exact sets, from the deepest level upwards (the strips of level b read the sets of level b + 1)
+    for (int b = d.n_down - 1; b >= 0; b--) {
+        if (!in_form(b)) continue;
+        const int l0 = 6 * b;
+        const bool stem = b == 0 && (d.fused_mask & 1u);
+        for (int k = 0; k < p.n_classes; k++) {
+            const AxisKey &kr = keys[krow[k]], &kc = keys[kcol[k]];
+            bool t = p.class_count[k] > 0 && p.read[k].rh > 0 && p.read[k].rw > 0 && (!empty(kr.share[l0 + 5]) || !empty(kc.share[l0 + 5]));
+            Mask m[3][2];           // pooled output, residual, stem at the even pixels; rows, columns
+            for (int ax = 0; ax < 2 && t; ax++) {
+                const AxisKey &key = ax ? kc : kr;
+                m[0][ax] = key.comp[l0 + 5];
+                m[1][ax] = within(m[0][ax], key.live[l0 + 4]);
+                m[2][ax] = stem ? within(m[1][ax], key.live[L]) : Mask();
+                const int ls[3] = {l0 + 5, l0 + 4, L};
+                for (int j = 0; j < (stem ? 3 : 2); j++) {
+                    const RoiRect rl = d.rect_live[ls[j]][k];
+                    const Iv box = ax ? Iv{rl.x0, rl.x0 + rl.rw} : Iv{rl.y0, rl.y0 + rl.rh};
+                    const std::vector<Iv> runs = runs_of(m[j][ax]);
+                    t = t && !runs.empty() && runs.size() <= 2;
+                    for (const Iv &r : runs) t = t && r.lo >= box.lo && r.hi <= box.hi;
+                }
+            }
+            takes[b][k] = t;
+            if (!t) continue;
+            for (int ax = 0; ax < 2; ax++) {
+                std::copy(m[1][ax].begin(), m[1][ax].end(), mask_at(l0 + 4, k, ax));
+                if (stem) std::copy(m[2][ax].begin(), m[2][ax].end(), mask_at(L, k, ax));
+            }
+        }
+    }
+    // the rectangles as launched, every layer
+    for (int l = 0; l < NL; l++) {
+        d.mac_frect[l] = d.bytes_frect[l] = d.px_frect[l] = d.px_live[l] = d.copy_old[l] = d.copy_new[l] = 0;
+        const double area = (double)d.res[l] * d.res[l] * p.tiles_per_img;
+        const double mpp = area > 0 ? d.mac_full[l] / area : 0, bpp = area > 0 ? d.bytes_full[l] / area : 0;
+        const int b = l == L ? 0 : l / 6, kk = l == L ? 4 : l % 6;
+        const bool cut = l <= L && (kk == 4 || kk == 5) && (l != L || (d.fused_mask & 1u)) && in_form(b);
+        int nseg = 0;
+        for (int k = 0; k < p.n_classes; k++) {
+            const RoiRect rl = d.rect_live[l][k];
+            int &n = d.fcomp_n[l][k];
+            n = 0;
+            for (int i = 0; i < 4; i++) d.fcomp[l][k][i] = RoiRect{0, 0, 0, 0};
+            if (cut && takes[b][k]) {
+                std::vector<Iv> rows = runs_of(get(l, k, 0)), cols = runs_of(get(l, k, 1));
+                for (Iv &c : cols)
+                    if (kk != 5) c = meet(Iv{c.lo & ~3, (c.hi + 3) & ~3}, Iv{rl.x0, rl.x0 + rl.rw});
+                if (cols.size() == 2 && cols[0].hi >= cols[1].lo) { cols[0].hi = cols[1].hi; cols.pop_back(); }
+                for (const Iv &r : rows)
+                    for (const Iv &c : cols) d.fcomp[l][k][n++] = RoiRect{r.lo, c.lo, r.hi - r.lo, c.hi - c.lo};
+                if (n != 1 || d.fcomp[l][k][0].y0 != rl.y0 || d.fcomp[l][k][0].x0 != rl.x0 || d.fcomp[l][k][0].rh != rl.rh || d.fcomp[l][k][0].rw != rl.rw)
+                    d.fused_rect_any = true;
+            } else {
+                n = roi_rect_comp(p, l, k, d.fcomp[l][k]);
+            }
+            for (int i = 0; i < n; i++) {
+                const double px = (double)d.fcomp[l][k][i].rh * d.fcomp[l][k][i].rw * p.class_count[k];
+                d.mac_frect[l] += mpp * px; d.bytes_frect[l] += bpp * px; d.px_frect[l] += px;
+            }
+            d.px_live[l] += (double)rl.rh * rl.rw * p.class_count[k];
+            if (p.class_count[k] > 0) nseg += n;
+        }
+        d.fused_rect_segs = std::max(d.fused_rect_segs, nseg);
+    }
+    // the halo strips of the pooled outputs: the shared pixels the next level's exact sets tap
+    for (int b = 0; b + 1 < d.n_down; b++) {
+        if (!in_form(b)) continue;
+        const int l5 = 6 * b + 5, Ho = d.res[l5], ln = 6 * (b + 1);
+        d.fused_fill_on[l5] = true;
+        for (int k = 0; k < p.n_classes; k++) {
+            if (p.class_count[k] <= 0 || p.read[k].rh <= 0 || p.read[k].rw <= 0) continue;
+            const AxisKey *key[2] = {&keys[krow[k]], &keys[kcol[k]]};
+            std::vector<Iv> own[2], got[2];         // per axis: the tapped pixels the patch computes itself, and those in its shared zone
+            for (int ax = 0; ax < 2; ax++) {
+                const Mask dw = taps_of(get(ln, k, ax), TAP_DW, Ho), ev = taps_of(get(ln + 4, k, ax), TAP_EVEN, Ho);
+                Mask o(Ho, 0), g(Ho, 0);
+                for (int v = 0; v < Ho; v++) {
+                    const bool tap = dw[v] || ev[v];
+                    o[v] = tap && key[ax]->comp[l5][v];
+                    g[v] = tap && in_iv(key[ax]->share[l5], v);
+                }
+                own[ax] = runs_of(o); got[ax] = runs_of(g);
+            }
+            auto put = [&](int dir, const std::vector<Iv> &rows, const std::vector<Iv> &cols) {
+                for (const Iv &r : rows)
+                    for (const Iv &c : cols) {
+                        d.fused_fill.push_back(RoiDownPlan::ShareFill{l5, k, dir, r.lo, c.lo, r.hi - r.lo, c.hi - c.lo});
+                        d.copy_new[l5] += (double)(r.hi - r.lo) * (c.hi - c.lo) * p.class_count[k];
+                    }
+            };
+            put(0, own[0], got[1]); put(1, got[0], own[1]); put(2, got[0], got[1]);
+        }
+        d.fused_rect_any = true;
+    }
+    for (const RoiDownPlan::ShareFill &f : d.share_fill) {
+        const double px = (double)f.rh * f.rw * p.class_count[f.cls];
+        d.copy_old[f.layer] += px;
+        if (!d.fused_fill_on[f.layer]) d.copy_new[f.layer] += px;
+    }
+    // a table that does not fit keeps the form above
+    if (d.fused_rect_any && d.fused_rect_segs > ROI_MAX_SEGS - 1) d.fused_rect_any = false;
+    if (!d.fused_rect_any) {
+        d.fused_fill.clear();
+        d.fused_rect_segs = d.rect_segs;
+        for (int l = 0; l < NL; l++) {
+            d.fused_fill_on[l] = false;
+            d.copy_new[l] = d.copy_old[l];
+            d.mac_frect[l] = d.mac_rect[l]; d.bytes_frect[l] = d.bytes_rect[l]; d.px_frect[l] = 0;
+            for (int k = 0; k < p.n_classes; k++) {
+                d.fcomp_n[l][k] = roi_rect_comp(p, l, k, d.fcomp[l][k]);
+                for (int i = 0; i < d.fcomp_n[l][k]; i++) d.px_frect[l] += (double)d.fcomp[l][k][i].rh * d.fcomp[l][k][i].rw * p.class_count[k];
+            }
+        }
+        d.fcomp_mask = d.comp;
+        if (d.rect_any)
+            std::copy(d.rcomp_mask.begin() + 6 * bl * per_layer, d.rcomp_mask.begin() + (6 * bl + 6) * per_layer, d.fcomp_mask.begin() + 6 * bl * per_layer);
+    }
+}
+
 }  // namespace
 
 void roi_plan_share(RoiPlan &p)
@@ -661,6 +800,7 @@ void roi_plan_share(RoiPlan &p)
         }
     }
     share_rect_classes(p, keys, krow, kcol);
+    share_fused_rect_classes(p, keys, krow, kcol);
 }
 
 void roi_share_neighbours(const RoiPlan &p, int k, std::vector<int> &out)
@@ -709,6 +849,14 @@ int roi_rect_comp(const RoiPlan &p, int l, int k, RoiRect *out)
     if (q.rh <= 0 || q.rw <= 0) return 0;
     out[0] = q;
     return 1;
+}
+
+int roi_fused_rect_comp(const RoiPlan &p, int l, int k, RoiRect *out)
+{
+    const RoiDownPlan &d = p.down;
+    if (!d.fused_rect_any) return roi_rect_comp(p, l, k, out);
+    for (int i = 0; i < d.fcomp_n[l][k]; i++) out[i] = d.fcomp[l][k][i];
+    return d.fcomp_n[l][k];
 }
 
 bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_classes, RoiPlan &out)
@@ -1061,5 +1209,64 @@ extern "C" int tmat_roi_plan_share_rect(int hh, int ww, int patch, int n_up, con
     info[0] = d.rect_any ? 1 : 0;
     info[1] = d.rect_any ? d.n_down - 1 : -1;
     info[2] = d.rect_segs;
+    return TMAT_OK;
+}
+
+// The same for the fused levels' rectangle launches (RoiDownPlan::fcomp ...): n_rects [6 n_down + 4][max_classes], rects [6 n_down + 4]
+// [max_classes][4 rectangles][4] as (y0, x0, rows, columns) -- what roi_fused_rect_comp gives --, comp [6 n_down + 4][max_classes][2 axes]
+// [patch] bytes (the exact sets in force, before the columns are rounded), fills [n_fill][7] as (layer, class, direction, y0, x0, rows,
+// columns): the halo strips, fill_on [6 n_down + 4]: the strips stand in place of the layer's items of tmat_roi_plan_share, totals
+// [6 n_down + 4][6]: planned multiply-accumulates, planned bytes, planned pixels, pixels of rect_live, copied pixels without and with the
+// form (all per image), info: (some table differs from tmat_roi_plan_share_rect's, the mask of levels in force, the longest segment
+// table of a launch).
+extern "C" int tmat_roi_plan_share_fused_rect(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                              unsigned fused_mask, int max_classes, int *n_classes, int *n_rects, int *rects, unsigned char *comp,
+                                              int fill_cap, int *n_fill, int *fills, int *fill_on, double *totals, int *info)
+{
+    if (!up_channels || !down_channels || !n_classes || !n_rects || !rects || !comp || !n_fill || !fills || !fill_on || !totals || !info ||
+        fill_cap < 0 || max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
+        set_error("tmat_roi_plan_share_fused_rect: bad argument");
+        return TMAT_E_ARG;
+    }
+    RoiPlan p;
+    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, max_classes, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
+        set_error("tmat_roi_plan_share_fused_rect: unsupported geometry");
+        return TMAT_E_ARG;
+    }
+    const RoiDownPlan &d = p.down;
+    *n_classes = p.n_classes;
+    unsigned levels = 0;
+    for (int l = 0; l < d.n_layers; l++) {
+        for (int k = 0; k < max_classes; k++) {
+            const bool in = k < p.n_classes;
+            const size_t at = (size_t)l * max_classes + k;
+            RoiRect q[4];
+            const int n = in ? roi_fused_rect_comp(p, l, k, q) : 0;
+            n_rects[at] = n;
+            for (int i = 0; i < 4; i++) {
+                int *o = rects + (at * 4 + i) * 4;
+                o[0] = i < n ? q[i].y0 : 0; o[1] = i < n ? q[i].x0 : 0; o[2] = i < n ? q[i].rh : 0; o[3] = i < n ? q[i].rw : 0;
+            }
+            unsigned char *o = comp + at * 2 * patch;
+            if (in && !d.fcomp_mask.empty()) std::copy_n(d.fcomp_mask.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * patch, 2 * patch, o);
+            else std::fill_n(o, 2 * patch, (unsigned char)0);
+        }
+        fill_on[l] = d.fused_fill_on[l] ? 1 : 0;
+        if (d.fused_fill_on[l]) levels |= 1u << (l / 6);
+        double *t = totals + (size_t)l * 6;
+        t[0] = d.fcomp_mask.empty() ? d.mac_live[l] : d.mac_frect[l];
+        t[1] = d.fcomp_mask.empty() ? d.bytes_live[l] : d.bytes_frect[l];
+        t[2] = d.px_frect[l]; t[3] = d.px_live[l]; t[4] = d.copy_old[l]; t[5] = d.copy_new[l];
+    }
+    *n_fill = (int)d.fused_fill.size();
+    if (*n_fill > fill_cap) { set_error("tmat_roi_plan_share_fused_rect: fill_cap too small"); return TMAT_E_ARG; }
+    for (int i = 0; i < *n_fill; i++) {
+        const RoiDownPlan::ShareFill &f = d.fused_fill[i];
+        int *o = fills + (size_t)i * 7;
+        o[0] = f.layer; o[1] = f.cls; o[2] = f.dir; o[3] = f.y0; o[4] = f.x0; o[5] = f.rh; o[6] = f.rw;
+    }
+    info[0] = d.fused_rect_any ? 1 : 0;
+    info[1] = (int)levels;
+    info[2] = d.fused_rect_any ? d.fused_rect_segs : d.rect_segs;
     return TMAT_OK;
 }

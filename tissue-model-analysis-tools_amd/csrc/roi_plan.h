@@ -113,13 +113,44 @@ struct RoiDownPlan {
     std::vector<ShareFill> rect_fill;
     double mac_rect[ROI_MAX_DOWN_LAYERS] = {}, bytes_rect[ROI_MAX_DOWN_LAYERS] = {};       // mac_planned / bytes_planned of rcomp
     int rect_segs = 0;                          // the longest segment table a launch of the form needs (without the constant patches' segment)
+
+    // The shared-interior form of the FUSED levels' rectangle launches (TMAT_ROI_SHARE_FUSED_RECT), on top of both forms above: the
+    // stride-2 residual 1x1 (6 b + 4) and the pooling fix-up (6 b + 5) of a fused level b in ROI_SHARE_FUSED_RECT_LEVELS, and the stem at
+    // the even pixels (6 n_down) with level 0.  Fields of their own again: everything above keeps its values.  The form exists only
+    // where rect_any holds: while the unfused level reads the pooled outputs whole, their whole zone has to be copied.
+    // fcomp_mask (layout of comp): the exact sets in force under this form, every layer -- comp of the pooled output 6 b + 5 (live \ share)
+    // as it is; the residual 6 b + 4 that set cut by its own live; the stem at the even pixels block 0's residual set cut by its own
+    // live; rcomp_mask for the unfused last level; comp for every other layer.  A class takes the form in all rectangle launches of a
+    // level or in none (its keys share at the level and every set lies inside its rect_live).
+    // fcomp[l][k][0 .. fcomp_n[l][k]): the rectangles as launched (what roi_rect_comp gives for every layer outside the form): rows
+    // exact, the columns of the residual and stem layers rounded outwards to multiples of 4 inside rect_live (two runs that meet after
+    // rounding are one), the pooled layer in single pixels.  At most four, disjoint, inside rect_live, and they hold the exact set.
+    // fused_fill: the copies of a pooled output 6 b + 5 as HALO STRIPS, in place of its items in share_fill (fused_fill_on[6 b + 5]):
+    // only the shared pixels that a consumer's exact set taps in the next level -- the depthwise taps of fcomp_mask[6 (b + 1)], the even
+    // pixels under fcomp_mask[6 (b + 1) + 4] -- per axis, the 2-D list being the product (a superset of both consumers' products).
+    // Same directions and same source rule as share_fill.  A rectangle that rounding or whole tiles add on top of an exact set may read
+    // words nobody wrote: the contract of rect.
+    bool fused_rect_any = false;                // some class's rectangles or some copy list differ from the form above
+    bool fused_fill_on[ROI_MAX_DOWN_LAYERS] = {};
+    int fcomp_n[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {};
+    RoiRect fcomp[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES][4] = {};
+    std::vector<unsigned char> fcomp_mask;
+    std::vector<ShareFill> fused_fill;
+    double mac_frect[ROI_MAX_DOWN_LAYERS] = {}, bytes_frect[ROI_MAX_DOWN_LAYERS] = {};     // mac_planned / bytes_planned of fcomp
+    double px_frect[ROI_MAX_DOWN_LAYERS] = {}, px_live[ROI_MAX_DOWN_LAYERS] = {};          // pixels per image of fcomp, of rect_live
+    double copy_old[ROI_MAX_DOWN_LAYERS] = {}, copy_new[ROI_MAX_DOWN_LAYERS] = {};         // pixels per image copied into the tensor: share_fill, this form
+    int fused_rect_segs = 0;                    // the longest segment table a launch of the form needs (without the constant patches' segment)
 };
 
 // Fused levels (bit b) that take the shared-interior form: a level whose copies cost more than its skipped tiles save is taken out here
 constexpr unsigned ROI_SHARE_LEVELS = 3u;
 // Levels (bit b) whose rectangle launches take it too (RoiDownPlan::rcomp).  Built for the last level where it is unfused -- bit 2, the
-// 40² level; the rectangle launches of the fused levels (bits 0 and 1) have no form yet
+// 40² level; the rectangle launches of the fused levels (bits 0 and 1) have a form of their own, below
 constexpr unsigned ROI_SHARE_RECT_LEVELS = 4u;
+// Fused levels (bit b) whose rectangle launches -- stride-2 residual, pooling fix-up, with bit 0 the stem at the even pixels -- take the
+// shared-interior form (RoiDownPlan::fcomp) and whose pooled output is copied as halo strips.  A level whose form does not pay is taken
+// out here, by one bit
+constexpr unsigned ROI_SHARE_FUSED_RECT_LEVELS = 3u;
 
 struct RoiPlan {
     int hh = 0, ww = 0, ws = 0, n_up = 0;
@@ -182,6 +213,9 @@ void roi_plan_share(RoiPlan &p);
 // The rectangles layer l launches for class k in the rectangle launches' shared-interior form (RoiDownPlan::rcomp; rect_live where the
 // plan has no such form): at most four, disjoint, inside rect_live.  Returns their count.
 int roi_rect_comp(const RoiPlan &p, int l, int k, RoiRect *out);
+// The same with the fused levels' rectangle launches in their shared-interior form (RoiDownPlan::fcomp; what roi_rect_comp gives where
+// the plan has no such form)
+int roi_fused_rect_comp(const RoiPlan &p, int l, int k, RoiRect *out);
 // nbr in the class-major order of a pass of k images: [k tiles_per_img][3] positions, or -1
 void roi_share_neighbours(const RoiPlan &p, int k, std::vector<int> &out);
 

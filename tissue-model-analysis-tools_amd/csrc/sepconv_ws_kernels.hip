@@ -931,17 +931,10 @@ __global__ __launch_bounds__(256) void pool_fix_add_kernel(float *__restrict__ o
 {
     const int n = blockIdx.y;
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
     const int cq = e & ((1 << c4shift) - 1);
-    const int bp = e >> c4shift;                     // boundary pixel: tile * NB + k
-    const int NB = 8 + PR - 1;
-    const int tile = bp / NB, k = bp - tile * NB;
-    const int TH = Hp / PR, TW = Wp >> 3, ty = tile / TW, tx = tile - ty * TW;
-    const int pl = k < 8 ? PR - 1 : k - 8, ql = k < 8 ? k : 7;
-    // region form: only the boundary pixels inside the patch's box of pooled pixels (the others nobody reads)
-    RoiBox rb{};
-    if (!roi_box_of(roi, n, rb)) return;
-    if (ROI && (ty * PR + pl < rb.y0 || ty * PR + pl >= rb.y1 || tx * 8 + ql < rb.x0 || tx * 8 + ql >= rb.x1)) return;
+    const int TH = Hp / PR, TW = Wp >> 3;
+    // one boundary pixel: row pl, column ql of tile (ty, tx)
+    auto finish = [&](int ty, int pl, int tx, int ql) {
     const size_t o = (((size_t)n * Hp + ty * PR + pl) * Wp + tx * 8 + ql) * C + cq * 4;
     float4 m = *reinterpret_cast<const float4 *>(out + o);
     auto take = [&](const float *src) {
@@ -955,6 +948,43 @@ __global__ __launch_bounds__(256) void pool_fix_add_kernel(float *__restrict__ o
     const float4 rv = *reinterpret_cast<const float4 *>(resid + o);
     m.x = m.x + rv.x; m.y = m.y + rv.y; m.z = m.z + rv.z; m.w = m.w + rv.w;
     *reinterpret_cast<float4 *>(out + o) = m;
+    };
+    if (!ROI) {
+        if (e >= total) return;
+        const int bp = e >> c4shift;                     // boundary pixel: tile * NB + k
+        const int NB = 8 + PR - 1;
+        const int tile = bp / NB, k = bp - tile * NB;
+        const int ty = tile / TW, tx = tile - ty * TW;
+        finish(ty, k < 8 ? PR - 1 : k - 8, tx, k < 8 ? k : 7);
+        return;
+    }
+    // Region form: only the boundary pixels inside the patch's box of pooled pixels (the others nobody reads), on a COMPACT grid.  The
+    // box is a product of at most two row intervals and two column intervals; its boundary pixels are (A) its tile-closing rows
+    // (y % PR == PR - 1: tile rows [a / PR, b / PR) of an interval [a, b)) times all of its columns, then (B) all of its rows times its
+    // tile-closing columns (x % 8 == 7), less the rows of (A).  A thread takes position g of that list, one division; grid.x is sized
+    // for the largest box among the pass's own patches (launch_pool_fix_add), a patch with more positions takes further steps.
+    RoiBox2 rb{};
+    if (!roi_box_of(roi, n, rb)) return;
+    const bool two_r = rb.y2 != rb.y0, two_c = rb.x2 != rb.x0;
+    const int nr0 = rb.y1 - rb.y0, nr = rb.rows(), nc0 = rb.x1 - rb.x0, nc = rb.cols();
+    const int br0 = rb.y1 / PR - rb.y0 / PR, br = br0 + (two_r ? rb.y3 / PR - rb.y2 / PR : 0);
+    const int bc0 = (rb.x1 >> 3) - (rb.x0 >> 3), bc = bc0 + (two_c ? (rb.x3 >> 3) - (rb.x2 >> 3) : 0);
+    const int nA = br * nc, nAB = nA + nr * bc;
+    const int step = (int)(gridDim.x * 256) >> c4shift;
+    for (int g = e >> c4shift; g < nAB; g += step) {
+        int y, x;
+        if (g < nA) {
+            const int j = g / nc, i = g - j * nc;
+            y = (j < br0 ? rb.y0 / PR + j : rb.y2 / PR + (j - br0)) * PR + PR - 1;
+            x = i < nc0 ? rb.x0 + i : rb.x2 + (i - nc0);
+        } else {
+            const int j = (g - nA) / bc, i = (g - nA) - j * bc;
+            y = j < nr0 ? rb.y0 + j : rb.y2 + (j - nr0);
+            x = (i < bc0 ? (rb.x0 >> 3) + i : (rb.x2 >> 3) + (i - bc0)) * 8 + 7;
+            if (y % PR == PR - 1) continue;             // in (A)
+        }
+        finish(y / PR, y % PR, x >> 3, x & 7);
+    }
 }
 
 // finishes the tile edges of a pooled separable convolution (tiles of 2 nw rows x 16 columns; Cout / 4 a power of two)
@@ -965,7 +995,16 @@ static void launch_pool_fix_add(float *out, const float *sh, const float *sv, co
     while ((1 << c4shift) < Cout / 4) c4shift++;
     const int total = (H / (2 * nw)) * (W / 16) * (8 + nw - 1) * (Cout / 4);
     const dim3 grid((total + 255) / 256, N);
-    if (roi) hipLaunchKernelGGL(pool_fix_add_kernel<true>, grid, dim3(256), 0, s, out, sh, sv, co, resid, H / 2, W / 2, Cout, c4shift, total, nw, *roi);
+    if (roi) {
+        const int PR = nw;
+        const auto positions = [PR](const RoiBox2 &q) {
+            const long long br = q.y1 / PR - q.y0 / PR + (q.y2 != q.y0 ? q.y3 / PR - q.y2 / PR : 0);
+            const long long bc = (q.x1 >> 3) - (q.x0 >> 3) + (q.x2 != q.x0 ? (q.x3 >> 3) - (q.x2 >> 3) : 0);
+            return br * q.cols() + bc * q.rows();
+        };
+        hipLaunchKernelGGL(pool_fix_add_kernel<true>, dim3(roi_compact_blocks(*roi, H / 2, W / 2, Cout / 4, positions), N), dim3(256), 0, s, out, sh, sv, co,
+                           resid, H / 2, W / 2, Cout, c4shift, total, nw, *roi);
+    }
     else hipLaunchKernelGGL(pool_fix_add_kernel<false>, grid, dim3(256), 0, s, out, sh, sv, co, resid, H / 2, W / 2, Cout, c4shift, total, nw, RoiNone{});
 }
 

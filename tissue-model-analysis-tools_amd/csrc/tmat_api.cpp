@@ -336,7 +336,8 @@ static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, bool live, 
 // every stored tensor's items, built and uploaded on first use, never per pass.  Null + error set: an allocation or a copy failed.
 // rect: the handle may run the rectangle launches' form (TMAT_ROI_SHARE_RECT is not 0: one value per handle, so per entry) -- its item
 // tables are made too; with the switch at 0 the handle holds what the parent form holds
-static const RoiShareTab *roi_share_tab(RoiEntry *e, int k, bool rect)
+// fused: likewise for the fused levels' rectangle launches (TMAT_ROI_SHARE_FUSED_RECT is not 0) -- the halo strips of the pooled outputs
+static const RoiShareTab *roi_share_tab(RoiEntry *e, int k, bool rect, bool fused)
 {
     for (const RoiShareTab &t : e->shares) if (t.k == k) return &t;
     const RoiPlan &p = e->plan;
@@ -354,6 +355,13 @@ static const RoiShareTab *roi_share_tab(RoiEntry *e, int k, bool rect)
         RoiShareTab::Layer *sl = nullptr;
         for (RoiShareTab::Layer &l : t.layers) if (l.layer == f.layer && l.rect) sl = &l;
         if (!sl) { t.layers.emplace_back(); sl = &t.layers.back(); sl->layer = f.layer; sl->rect = true; }
+        sl->items.push_back(ShareItem{k * p.class_base[f.cls], k * p.class_count[f.cls], f.dir, f.y0, f.x0, f.rh, f.rw});
+    }
+    // the halo strips (RoiDownPlan::fused_fill): used in place of the layer's whole-zone items where that form runs
+    for (const RoiDownPlan::ShareFill &f : (rect && fused) ? p.down.fused_fill : std::vector<RoiDownPlan::ShareFill>()) {
+        RoiShareTab::Layer *sl = nullptr;
+        for (RoiShareTab::Layer &l : t.layers) if (l.layer == f.layer && l.fused) sl = &l;
+        if (!sl) { t.layers.emplace_back(); sl = &t.layers.back(); sl->layer = f.layer; sl->fused = true; }
         sl->items.push_back(ShareItem{k * p.class_base[f.cls], k * p.class_count[f.cls], f.dir, f.y0, f.x0, f.rh, f.rw});
     }
     auto up = [](const void *src, size_t bytes, void **dev) {
@@ -406,7 +414,10 @@ static RoiSegs roi_segs(const RoiPlan &p, int l, int k) { return roi_segs_of(p, 
 // each constant fill of a stored tensor of a fused level is followed by the copies out of the neighbour patches (RoiDownPlan::share_fill)
 // share_rect (with share): the rectangle launches of the unfused last level take the form too (RoiDownPlan::rcomp) -- several disjoint
 // rectangles per class in their segment tables, and the bottleneck tensor and its activated copy take their shared zone from the neighbours
-int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval, bool share, bool share_rect)
+// share_fused_rect (with share_rect): the rectangle launches of the fused levels take the form as well (RoiDownPlan::fcomp) -- the stem at
+// the even pixels, the stride-2 residual convolutions and the pooling fix-ups; the pooled outputs take halo strips, not their whole zone
+int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval, bool share, bool share_rect,
+                  bool share_fused_rect)
 {
     if (n <= 0) return TMAT_OK;
     if (n > c->max_patches) { set_error("unet_down_dev: n > max_patches"); return TMAT_E_ARG; }
@@ -422,15 +433,15 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
         n += kimg;              // every launch below runs the constant patches too
     }
     RoiSegs sg{};
-    bool rect_form = false;         // set below, once the share tables are there
-    // the segments of layer k of down block bi (null: full-frame)
-    auto segs = [&](size_t bi, int k) -> const RoiSegs * {
+    bool rect_form = false, fused_form = false;         // set below, once the share tables are there
+    // the segments of layer l of the down plan (null: full-frame)
+    auto segs_of = [&](int l) -> const RoiSegs * {
         if (!roi_b) return nullptr;
         if (rect_form) {            // up to four rectangles per class, the classes in patch order (the table fits: checked where rect_form is set)
             sg = RoiSegs{};
             for (int cl = 0; cl < plan->n_classes; cl++) {
                 RoiRect q[4];
-                const int nq = plan->class_count[cl] > 0 ? roi_rect_comp(*plan, 6 * (int)bi + k, cl, q) : 0;
+                const int nq = plan->class_count[cl] <= 0 ? 0 : fused_form ? roi_fused_rect_comp(*plan, l, cl, q) : roi_rect_comp(*plan, l, cl, q);
                 for (int i = 0; i < nq; i++) {
                     RoiSeg &g = sg.s[sg.nseg++];
                     g.p0 = kimg * plan->class_base[cl]; g.np = kimg * plan->class_count[cl];
@@ -438,16 +449,19 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
                 }
             }
         } else {
-            sg = roi_segs_of(*plan, (cst ? plan->down.rect_live : plan->down.rect)[6 * bi + k], kimg);
+            sg = roi_segs_of(*plan, (cst ? plan->down.rect_live : plan->down.rect)[l], kimg);
         }
         if (cst) {
             RoiSeg &g = sg.s[sg.nseg++];
             g = RoiSeg{};
-            g.p0 = n_own; g.np = kimg; g.rh = g.rw = plan->down.res[6 * bi + k];
+            g.p0 = n_own; g.np = kimg; g.rh = g.rw = plan->down.res[l];
         }
         c->down_segs = std::max(c->down_segs, sg.nseg);
+        c->down_seg_total += sg.nseg;
         return &sg;
     };
+    // of layer k of down block bi
+    auto segs = [&](size_t bi, int k) -> const RoiSegs * { return segs_of(6 * (int)bi + k); };
     // the strips of layer l's tensor t (C channels) that the constant patches hold: after the launch that writes t, before its readers
     auto fill = [&](float *t, int l, int C) -> bool {
         if (!cst) return true;
@@ -467,18 +481,23 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
     if (roi_any && (c->roi_down & 2u))
         for (RoiEntry *e : c->roi_cache) if (&e->plan == plan) ent = e;
     c->sep_tiles.clear();
-    c->down_segs = 0;
+    c->down_segs = c->down_seg_total = 0;
     bool tab_ok = true;
     // the shared-interior form: with the constant-ring form and the tile tables only, and where the plan shares anything
     const RoiShareTab *shr = nullptr;
-    if (share && cst && ent && plan->down.share_any && !(shr = roi_share_tab(ent, kimg, c->roi_share_rect != 0))) return TMAT_E_HIP;
+    if (share && cst && ent && plan->down.share_any && !(shr = roi_share_tab(ent, kimg, c->roi_share_rect != 0, c->roi_share_fused_rect != 0)))
+        return TMAT_E_HIP;
     // the rectangle launches' form: where the shared-interior form runs, bit 0 of TMAT_ROI_DOWN is on and the longest table fits
     rect_form = shr && share_rect && roi_b && plan->down.rect_any && plan->down.rect_segs + 1 <= ROI_MAX_SEGS;
+    // the fused levels' form: where that form runs, the plan has one and its longest table fits (the planner keeps it below the cap)
+    fused_form = rect_form && share_fused_rect && plan->down.fused_rect_any && plan->down.fused_rect_segs + 1 <= ROI_MAX_SEGS;
     // the copies of layer l's tensor t out of the neighbour patches: behind its constant fill, before its first reader
     auto share_fill = [&](float *t, int l, int C) -> bool {
         if (!shr) return true;
+        // (a pooled output whose copies the fused levels' form cuts to halo strips takes those, not its whole zone)
+        const bool strips = fused_form && plan->down.fused_fill_on[l];
         for (const RoiShareTab::Layer &sl : shr->layers)
-            if (sl.layer == l && (!sl.rect || rect_form) && !launch_share_fill(t, n_own, plan->down.res[l], C, shr->nbr.data(), shr->nbr_dev, sl.items.data(), sl.dev, (int)sl.items.size(), s))
+            if (sl.layer == l && (sl.fused ? strips : sl.rect ? rect_form : !strips) && !launch_share_fill(t, n_own, plan->down.res[l], C, shr->nbr.data(), shr->nbr_dev, sl.items.data(), sl.dev, (int)sl.items.size(), s))
                 return false;
         return true;
     };
@@ -503,7 +522,7 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
     const bool stem_in_sep = c->stem_fused && !c->down.empty() && down_block_ws(c, 0) && c->down[0].cin == c->f0 &&
                              !(c->precision == TMAT_PRECISION_BF16X3 && c->sep_bf16);
     if (stem_in_sep) {
-        launch_stem_even(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s, segs(0, 4));      // the pixels block 0's residual 1x1 takes
+        launch_stem_even(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s, fused_form ? segs_of(LD) : segs(0, 4));      // the pixels block 0's residual 1x1 takes
         if (!fill(b0, LD, c->f0)) return TMAT_E_ARG;
     } else launch_stem(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s);
     int H = P / 2;
@@ -723,7 +742,7 @@ int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred
         launch_extract_tiles(xi, mn, k, g, c->patch_in, c->stream);
         // (the constant-ring form only on request: the default launches of this entry point are pinned to the dependency plan's tiles)
         int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan, c->roi_const == 1 ? mn : nullptr,
-                                      c->roi_share == 1, c->roi_share_rect == 1)
+                                      c->roi_share == 1, c->roi_share_rect == 1, c->roi_share_fused_rect == 1)
                       : unet_forward_dev(c, c->patch_in, k * g.tiles_per_img, c->patch_out, c->stream);
         if (!rc && plan) rc = unet_up_dev(c, c->dout[0], k * g.tiles_per_img, c->patch_out, c->stream, plan);
         if (rc) return rc;
@@ -808,6 +827,10 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     if (const char *e = getenv("TMAT_ROI_SHARE_RECT")) {
         if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_SHARE_RECT must be 0 or 1"); delete c; return TMAT_E_ARG; }
         c->roi_share_rect = atoi(e);
+    }
+    if (const char *e = getenv("TMAT_ROI_SHARE_FUSED_RECT")) {
+        if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_SHARE_FUSED_RECT must be 0 or 1"); delete c; return TMAT_E_ARG; }
+        c->roi_share_fused_rect = atoi(e);
     }
     // room for the all-constant patches of a pass behind its patches (tmat_ctx.h): the down-path workspaces and the input buffers only
     c->const_cap = c->roi_const == 0 ? 0 : std::max(4, c->max_patches / 64);
@@ -1118,6 +1141,14 @@ int tmat_debug_down_segs(tmat_handle h, int *max_segs)
     Ctx *c = (Ctx *)h;
     if (!c || !max_segs) { set_error("tmat_debug_down_segs: bad argument"); return TMAT_E_ARG; }
     *max_segs = c->down_segs;
+    return TMAT_OK;
+}
+
+int tmat_debug_down_seg_total(tmat_handle h, int *total)
+{
+    Ctx *c = (Ctx *)h;
+    if (!c || !total) { set_error("tmat_debug_down_seg_total: bad argument"); return TMAT_E_ARG; }
+    *total = c->down_seg_total;
     return TMAT_OK;
 }
 

@@ -37,7 +37,7 @@ struct RoiShareTab {
     int k = 0;
     std::vector<int> nbr;
     int *nbr_dev = nullptr;
-    struct Layer { int layer = 0; std::vector<ShareItem> items; ShareItem *dev = nullptr; bool rect = false; };     // rect: of RoiDownPlan::rect_fill
+    struct Layer { int layer = 0; std::vector<ShareItem> items; ShareItem *dev = nullptr; bool rect = false, fused = false; };     // rect: of RoiDownPlan::rect_fill; fused: of RoiDownPlan::fused_fill
     std::vector<Layer> layers;
 };
 struct RoiEntry {
@@ -241,10 +241,16 @@ struct Ctx {
     // RoiDownPlan::rcomp): several disjoint rectangles per class in their segment tables, the bottleneck tensor's shared zone copied.
     // -1 (unset): the batch pipeline runs it, predict_smooth does not; 0: nobody; 1: both.  Only where the shared-interior form runs.
     int roi_share_rect = -1;
+    // TMAT_ROI_SHARE_FUSED_RECT: the rectangle launches of the fused 160² and 80² levels -- stem at the even pixels, stride-2 residual
+    // 1x1, pooling fix-up -- take the shared-interior form as well (roi_plan.h:RoiDownPlan::fcomp), and the pooled outputs are copied as
+    // halo strips, not as whole zones.  -1 (unset): the batch pipeline runs it, predict_smooth does not; 0: nobody; 1: both.  Only where
+    // the rectangle launches' form of the unfused level runs: while that level reads the pooled outputs whole, strips are not enough.
+    int roi_share_fused_rect = -1;
     float *padval[2] = {nullptr, nullptr};                   // the pad values of a pipeline pass, per slot: c->scratch is rewritten by the front end of the pass after next
     std::vector<RoiEntry *> roi_cache;
     std::vector<std::pair<long long, long long>> sep_tiles;  // (planned, full) tiles of the fused separable launches of the last down pass (tmat_debug_sep_tiles)
     int down_segs = 0;                                       // the longest segment table of the last down pass's launches (tmat_debug_down_segs)
+    int down_seg_total = 0;                                  // the segments of all its rectangle launches together (tmat_debug_down_seg_total)
     bool fused_sep = true;                                   // fused depthwise -> pointwise kernel (sepconv_ws_kernel) where the level allows (TMAT_FUSED_SEP=0: separate kernels)
     // call-scoped device workspaces of the side tools (cell area, invasion depth), kept between calls: with the reference's default batch of 4 images a
     // hipMalloc / hipFree pair per buffer and call costs more than the batch's kernels.  Slot = a ToolWs id per buffer (ws_get below).
@@ -266,7 +272,7 @@ int ensure_patch_io(Ctx *c, int n_patches);
 // padval (nullable, with a plan only): the pad values of the pass's images on the device -- the constant-ring form, where the handle and
 // the pass allow it.  X then has room for n + n / tiles_per_img patches (patch_in and patch_in2 do): the all-constant patches are written there
 int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan = nullptr, const float *padval = nullptr,
-                  bool share = false, bool share_rect = false);
+                  bool share = false, bool share_rect = false, bool share_fused_rect = false);
 // plan (nullable): region form; n is then a whole number of images' patches in the plan's class-major order
 int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s, const RoiPlan *plan = nullptr);
 // the region plan of g's geometry (cached on the handle) and, in g.order, its patch order; null and the image-major order when the region

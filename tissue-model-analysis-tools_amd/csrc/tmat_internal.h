@@ -51,11 +51,20 @@ struct RoiSegs {
 // the pixels [y0, y1) x [x0, x1) of its segment, a patch no segment names computes nothing.  A thread whose pixels lie outside its
 // patch's box returns before its first load; border tests stay against the patch.
 struct RoiBox { int y0, y1, x0, x1; };
-// The product form, for the kernels of the unfused level (depthwise, pooling), whose tables may name a patch range several times: the
+#ifdef __HIPCC__
+#define TMAT_HD __host__ __device__ __forceinline__
+#else
+#define TMAT_HD inline
+#endif
+// The product form, for the kernels whose tables may name a patch range several times (depthwise and pooling of the unfused level; stem at
+// the even pixels and pooling fix-up since the fused levels' rectangle launches have their shared-interior form): the
 // segments of one patch are at most two row intervals times at most two column intervals (one segment: both intervals of an axis coincide).
 struct RoiBox2 {
     int y0, y1, x0, x1;             // first row interval [y0, y1), first column interval [x0, x1)
     int y2, y3, x2, x3;             // second ones (copies of the first where the patch has one)
+    // rows / columns of the box: both intervals of an axis, the second counted where the patch has one
+    TMAT_HD int rows() const { return y1 - y0 + (y2 != y0 ? y3 - y2 : 0); }
+    TMAT_HD int cols() const { return x1 - x0 + (x2 != x0 ? x3 - x2 : 0); }
 #ifdef __HIPCC__
     __device__ __forceinline__ bool row(int y) const { return (y >= y0 && y < y1) || (y >= y2 && y < y3); }
     __device__ __forceinline__ bool col(int x) const { return (x >= x0 && x < x1) || (x >= x2 && x < x3); }
@@ -92,6 +101,31 @@ __device__ __forceinline__ bool roi_box_of(const RoiSegs &r, int n, RoiBox2 &q)
 __device__ __forceinline__ bool roi_box_of(const RoiNone &, int, RoiBox2 &) { return true; }
 __device__ __forceinline__ bool roi_box_of(const RoiNone &, int, RoiBox &) { return true; }
 #endif
+// The COMPACT grids of the region form (stem at the even pixels, pooling fix-up): the workgroups of a patch enumerate the positions of the
+// patch's own box, not of the frame.  Blocks per patch: enough for the largest box of the table -- positions(box) thread positions of C4
+// threads each -- leaving out the boxes that are a whole frame (the all-constant patches, a few per pass: their workgroups take further
+// steps of the grid) unless every box is one.  The segments that name one patch range stand together in the table.
+template <class F>
+inline int roi_compact_blocks(const RoiSegs &r, int frame_h, int frame_w, int C4, F positions)
+{
+    long long best = 0, whole = 0;
+    for (int i = 0; i < r.nseg;) {
+        RoiBox2 q{};
+        int j = i;
+        for (; j < r.nseg && r.s[j].p0 == r.s[i].p0; j++) {     // (the rule of roi_box_of)
+            const int y0 = r.s[j].y0, y1 = y0 + r.s[j].rh, x0 = r.s[j].x0, x1 = x0 + r.s[j].rw;
+            if (j == i) q = RoiBox2{y0, y1, x0, x1, y0, y1, x0, x1};
+            if (y0 != q.y0) { q.y2 = y0; q.y3 = y1; }
+            if (x0 != q.x0) { q.x2 = x0; q.x3 = x1; }
+        }
+        const long long n = positions(q);
+        if (q.rows() >= frame_h && q.cols() >= frame_w) whole = n; else best = best > n ? best : n;
+        i = j;
+    }
+    if (best == 0) best = whole;
+    const long long blocks = (best * C4 + 255) / 256;
+    return (int)(blocks < 1 ? 1 : blocks);
+}
 // returns false (and sets the error) on unsupported shapes; roi (nullable; stride 2 with the 1x1 form only: the rectangles are output
 // pixels): region form
 bool launch_conv(const ConvArgs &a, hipStream_t s, const RoiSegs *roi = nullptr);

@@ -1130,13 +1130,22 @@ __global__ __launch_bounds__(256) void stem_even_kernel(const float *__restrict_
     const int n = blockIdx.y;
     const int e = blockIdx.x * 256 + threadIdx.x;
     const int cq = e & ((1 << c4shift) - 1);
-    const int g = e >> c4shift;
-    if (g >= Ho * WG) return;
-    const int yo = g / WG, xg = g - yo * WG;
-    // region form: the box's columns are whole pixel groups (roi_plan.cpp: multiples of 4)
-    RoiBox rb{};
+    // Region form (template flag: the full-frame launches keep their code): a COMPACT grid.  The workgroups of a patch enumerate the
+    // positions of the patch's own box in the product form -- the rows of its first interval, then of its second, times the pixel groups
+    // of its first column interval, then of its second (the box's columns are whole pixel groups: roi_plan.cpp rounds them to multiples
+    // of 4) -- one division per thread and step.  grid.x is sized for the largest box among the pass's own patches
+    // (launch_stem_even); a patch with more positions, such as an all-constant patch, which is computed whole, takes further steps.
+    RoiBox2 rb{};
     if (!roi_box_of(roi, n, rb)) return;
-    if (ROI && (yo < rb.y0 || yo >= rb.y1 || SE_PX * xg < rb.x0 || SE_PX * xg >= rb.x1)) return;
+    const int nr0 = ROI ? rb.y1 - rb.y0 : Ho, nr = ROI ? rb.rows() : Ho;
+    const int ng0 = ROI ? (rb.x1 - rb.x0) / SE_PX : WG, ng = ROI ? rb.cols() / SE_PX : WG;
+    const int step = ROI ? (int)(gridDim.x * 256) >> c4shift : nr * ng;
+    for (int g = e >> c4shift; g < nr * ng; g += step) {
+    int yo = g / ng, xg = g - yo * ng;
+    if (ROI) {
+        yo = yo < nr0 ? rb.y0 + yo : rb.y2 + (yo - nr0);
+        xg = xg < ng0 ? rb.x0 / SE_PX + xg : rb.x2 / SE_PX + (xg - ng0);
+    }
     const float *xin = x + (size_t)n * H * W + (size_t)(4 * yo) * W + 4 * SE_PX * xg;      // rows 4 yo .. 4 yo + 2 < H, columns < W
     float win[3][4 * SE_PX];
 #pragma unroll
@@ -1165,6 +1174,7 @@ __global__ __launch_bounds__(256) void stem_even_kernel(const float *__restrict_
         o.z = fmaxf(fmaf(acc.z, sc.z, sh.z), 0.f); o.w = fmaxf(fmaf(acc.w, sc.w, sh.w), 0.f);
         *reinterpret_cast<float4 *>(obase + (size_t)px * Cout) = o;
     }
+    }
 }
 
 void launch_stem_even(const float *x, int N, int H, int W, const float *Ws, int Cout, const float *scale,
@@ -1172,7 +1182,8 @@ void launch_stem_even(const float *x, int N, int H, int W, const float *Ws, int 
 {
     const int total = (H / 4) * (W / 4 / SE_PX) * (Cout / 4);
     const dim3 grid((total + 255) / 256, N);
-    if (roi) hipLaunchKernelGGL(stem_even_kernel<true>, grid, dim3(256), 0, s, x, H, W, Ws, Cout, ilog2(Cout / 4), scale, shift, out, *roi);
+    if (roi) hipLaunchKernelGGL(stem_even_kernel<true>, dim3(roi_compact_blocks(*roi, H / 4, W / 4, Cout / 4, [](const RoiBox2 &q) { return (long long)q.rows() * (q.cols() / SE_PX); }), N), dim3(256), 0, s, x, H, W, Ws, Cout,
+                                ilog2(Cout / 4), scale, shift, out, *roi);
     else hipLaunchKernelGGL(stem_even_kernel<false>, grid, dim3(256), 0, s, x, H, W, Ws, Cout, ilog2(Cout / 4), scale, shift, out, RoiNone{});
 }
 
@@ -1195,12 +1206,19 @@ __global__ __launch_bounds__(256) void maxpool_add_kernel(const float *__restric
     const int n = blockIdx.y;
     const int e = blockIdx.x * 256 + threadIdx.x;
     const int cq = e & ((1 << c4shift) - 1);
-    const int p = e >> c4shift;
-    if (p >= Ho * Wo) return;
-    const int yo = p / Wo, xo = p - yo * Wo;
+    // region form: a compact grid over the patch's own box, as in stem_even_kernel (grid.x sized by launch_maxpool_add)
     RoiBox2 rb{};
     if (!roi_box_of(roi, n, rb)) return;
-    if (ROI && (!rb.row(yo) || !rb.col(xo))) return;
+    const int nr0 = ROI ? rb.y1 - rb.y0 : Ho, nr = ROI ? rb.rows() : Ho;
+    const int nc0 = ROI ? rb.x1 - rb.x0 : Wo, nc = ROI ? rb.cols() : Wo;
+    const int step = ROI ? (int)(gridDim.x * 256) >> c4shift : nr * nc;
+    for (int g = e >> c4shift; g < nr * nc; g += step) {
+    int yo = g / nc, xo = g - yo * nc;
+    if (ROI) {
+        yo = yo < nr0 ? rb.y0 + yo : rb.y2 + (yo - nr0);
+        xo = xo < nc0 ? rb.x0 + xo : rb.x2 + (xo - nc0);
+    }
+    const int p = yo * Wo + xo;
     const float *base = p2 + (size_t)n * H * W * C + cq * 4;
     float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
 #pragma unroll
@@ -1220,13 +1238,15 @@ __global__ __launch_bounds__(256) void maxpool_add_kernel(const float *__restric
         m.x = relu_pos0(m.x); m.y = relu_pos0(m.y); m.z = relu_pos0(m.z); m.w = relu_pos0(m.w);
         *reinterpret_cast<float4 *>(out_relu + o) = m;
     }
+    }
 }
 
 void launch_maxpool_add(const float *p2, int N, int H, int W, int C, const float *r, float *out, hipStream_t s, float *out_relu, const RoiSegs *roi)
 {
     const int total = (H / 2) * (W / 2) * (C / 4);
     const dim3 grid((total + 255) / 256, N);
-    if (roi) hipLaunchKernelGGL(maxpool_add_kernel<true>, grid, dim3(256), 0, s, p2, H, W, C, ilog2(C / 4), r, out, out_relu, *roi);
+    if (roi) hipLaunchKernelGGL(maxpool_add_kernel<true>, dim3(roi_compact_blocks(*roi, H / 2, W / 2, C / 4, [](const RoiBox2 &q) { return (long long)q.rows() * q.cols(); }), N),
+                                dim3(256), 0, s, p2, H, W, C, ilog2(C / 4), r, out, out_relu, *roi);
     else hipLaunchKernelGGL(maxpool_add_kernel<false>, grid, dim3(256), 0, s, p2, H, W, C, ilog2(C / 4), r, out, out_relu, RoiNone{});
 }
 

@@ -184,8 +184,8 @@ EXPORTS = [
     "tmat_set_gaussian_table", "tmat_host_gaussian_kernel1d", "tmat_gaussian_f32", "tmat_sato_batch", "tmat_stack_prepare", "tmat_vessel_field",
     "tmat_analyze_stack", "tmat_field_stats", "tmat_field_stats_pruned", "tmat_resize_aa_u16", "tmat_cell_area_batch", "tmat_cell_area_masked", "tmat_resize_linear_u16",
     "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi", "tmat_resnet_set_precision", "tmat_conv2d",
-    "tmat_roi_plan", "tmat_roi_plan_tight", "tmat_roi_plan_exact", "tmat_conv2d_roi", "tmat_conv2d_roi_s2", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles", "tmat_debug_down_segs",
-    "tmat_roi_plan_const", "tmat_roi_sep_tiles_live", "tmat_roi_plan_share", "tmat_roi_sep_tiles_share", "tmat_roi_plan_share_rect", "tmat_debug_share_fill_check",
+    "tmat_roi_plan", "tmat_roi_plan_tight", "tmat_roi_plan_exact", "tmat_conv2d_roi", "tmat_conv2d_roi_s2", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles", "tmat_debug_down_segs", "tmat_debug_down_seg_total",
+    "tmat_roi_plan_const", "tmat_roi_sep_tiles_live", "tmat_roi_plan_share", "tmat_roi_sep_tiles_share", "tmat_roi_plan_share_rect", "tmat_roi_plan_share_fused_rect", "tmat_debug_share_fill_check",
     "tmat_stage_pictures", "tmat_host_stage_pictures", "tmat_analyze_batch_ex", "tmat_analyze_batch_ex_dev",
     "tmat_png_stripe", "tmat_png_bound", "tmat_png_encode_batch", "tmat_png_encode_batch_dev", "tmat_png_encode_batch_timed",
     "tmat_host_png_encode_batch", "tmat_render_tree_png",
@@ -503,6 +503,12 @@ class Handle:
         """test-only: the longest segment table among the rectangle launches of the last down pass (include/tmat.h:tmat_debug_down_segs)"""
         n = C.c_int()
         check(lib().tmat_debug_down_segs(self._h, C.byref(n)), "tmat_debug_down_segs")
+        return n.value
+
+    def debug_down_seg_total(self):
+        """test-only: the segments of all rectangle launches of the last down pass together (include/tmat.h:tmat_debug_down_seg_total)"""
+        n = C.c_int()
+        check(lib().tmat_debug_down_seg_total(self._h, C.byref(n)), "tmat_debug_down_seg_total")
         return n.value
 
     def debug_held_bytes(self):
@@ -841,6 +847,33 @@ def roi_plan_share_rect(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), do
           "roi_plan_share_rect")
     return dict(n_classes=int(ncls[0]), share=share, n_rects=nrect, rects=rects, comp=comp, fills=fills[:int(nfill[0])], mac_rect=mac,
                 bytes_rect=byt, any=bool(info[0]), level=int(info[1]), max_segs=int(info[2]))
+
+
+def roi_plan_share_fused_rect(hh, ww, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3, max_classes=16):
+    """tmat_roi_plan_share_fused_rect (include/tmat.h): the shared-interior tables of the fused levels' rectangle launches; host
+    arithmetic, no GPU.  Returns a dict: n_classes, n_rects [6 n_down + 4][max_classes], rects [6 n_down + 4][max_classes][4][4] (y0, x0,
+    rows, columns), comp [6 n_down + 4][max_classes][2][patch] uint8, fills [n][7] (layer, class, direction, y0, x0, rows, columns: the
+    halo strips), fill_on [6 n_down + 4], mac / bytes / px / px_live / copy_old / copy_new [6 n_down + 4], any, levels, max_segs."""
+    L = lib()
+    L.tmat_roi_plan_share_fused_rect.argtypes = ([C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint, C.c_int] + [C.c_void_p] * 4 +
+                                                 [C.c_int] + [C.c_void_p] * 5)
+    n_up, n_down = len(channels) - 1, len(down_channels) - 1
+    ch, dch = np.asarray(channels, np.int32), np.asarray(down_channels, np.int32)
+    nl = 6 * n_down + 4
+    ncls, nfill, info = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(3, np.int32)
+    nrect = np.zeros((nl, max_classes), np.int32)
+    rects = np.zeros((nl, max_classes, 4, 4), np.int32)
+    comp = np.zeros((nl, max_classes, 2, patch), np.uint8)
+    cap = nl * max_classes * 12
+    fills = np.zeros((cap, 7), np.int32)
+    on = np.zeros(nl, np.int32)
+    tot = np.zeros((nl, 6), np.float64)
+    check(L.tmat_roi_plan_share_fused_rect(hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), max_classes, ptr(ncls), ptr(nrect),
+                                           ptr(rects), ptr(comp), cap, ptr(nfill), ptr(fills), ptr(on), ptr(tot), ptr(info)),
+          "roi_plan_share_fused_rect")
+    return dict(n_classes=int(ncls[0]), n_rects=nrect, rects=rects, comp=comp, fills=fills[:int(nfill[0])], fill_on=on, mac=tot[:, 0],
+                bytes=tot[:, 1], px=tot[:, 2], px_live=tot[:, 3], copy_old=tot[:, 4], copy_new=tot[:, 5], any=bool(info[0]),
+                levels=int(info[1]), max_segs=int(info[2]))
 
 
 def roi_sep_tiles_share(hh, ww, layer, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
