@@ -1001,6 +1001,22 @@ int tmat_roi_plan_share_fused_rect(int hh, int ww, int patch, int n_up, const in
                                    unsigned fused_mask, int max_classes, int *n_classes, int *n_rects, int *rects, unsigned char *comp,
                                    int fill_cap, int *n_fill, int *fills, int *fill_on, double *totals, int *info);
 /*
+ * What a down pass of k images launches under one FORM of the down path, composed from the tables above by the one rule the launches
+ * themselves read (roi_plan.h:RoiDownForm).  form: 1 the region form (tmat_roi_plan_down), 2 the constant-ring form, 3 the
+ * shared-interior form, 4 with the rectangle launches of the unfused level, 5 with those of the fused levels; a form the plan does not
+ * have falls back to the highest one below it that it has.  info [4]: the form that runs, the layer whose table the stem at the even
+ * pixels launches (6 n_down under form 5, else 4), the longest segment table, and the segment tables of all rectangle launches of the
+ * pass added up (with the default kernels, what tmat_debug_down_segs and tmat_debug_down_seg_total report after such a pass).  n_segs [6 n_down + 4] and segs
+ * [6 n_down + 4][64][6] (first patch, patches, y0, x0, rows, columns): every layer's segment table in launch order -- the classes in
+ * the pass's class-major patch order, up to four rectangles each, then from form 2 upwards one segment of whole patches for the k
+ * all-constant patches behind them.  const_fills [n_const][7] (layer, first patch, patches, y0, x0, rows, columns): the strips a
+ * stored tensor takes from the constant patches.  copies [n_copy][8] (layer, first patch, patches, direction, y0, x0, rows, columns):
+ * the items it then takes from the neighbour patches.  TMAT_E_ARG when a cap is too small.  Host arithmetic, no GPU.
+ */
+int tmat_roi_down_schedule(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                           unsigned fused_mask, int form, int k, int *info, int *n_segs, int *segs, int const_cap, int *n_const,
+                           int *const_fills, int copy_cap, int *n_copy, int *copies);
+/*
  * Test-only: the host-side argument checks of the share-fill launcher on a table of n_items items [7] = first patch, patches,
  * direction, y0, x0, rows, columns of a tensor (n_patches, side, side, channels) and a neighbour table [n_patches][3].  Nothing is
  * launched.  TMAT_OK when the launcher would take them; TMAT_E_ARG with the reason in tmat_last_error otherwise.

@@ -179,10 +179,10 @@ static int enqueue_down(Ctx *c, int k, int slot, const TileGeom &g)
     // reading on the second stream (enqueue_back's own wait on ev_blend comes too late: it is issued after this forward)
     if (oversize && tail_on_side_stream() && c->blend_pending[slot ^ 1]) TMAT_HIP(hipStreamWaitEvent(s, c->ev_blend[slot ^ 1], 0));
     float *pin = patch_in_of(c, slot, g);
+    const RoiPlan *plan = roi_find(c, g);
     int rc = oversize ? unet_forward_dev(c, pin, k * g.tiles_per_img, c->patch_out, s)
-                      : unet_down_dev(c, pin, k * g.tiles_per_img, c->dout[slot], s, roi_find(c, g),
-                                      c->roi_const != 0 && k <= c->const_cap ? c->padval[slot] : nullptr, c->roi_share != 0, c->roi_share_rect != 0,
-                                      c->roi_share_fused_rect != 0);
+                      : unet_down_dev(c, pin, k * g.tiles_per_img, c->dout[slot], s, plan, c->padval[slot],
+                                      roi_down_resolve(c, plan, k, c->padval[slot] != nullptr, true));
     if (rc) return rc;
     TMAT_HIP(hipEventRecord(c->ev_down[slot], s));
     c->down_pending[slot] = true;

@@ -291,30 +291,6 @@ bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask)
     return true;
 }
 
-static long long sep_tile_table(const RoiPlan &p, const RoiRect (*rects)[ROI_MAX_CLASSES], int layer, int k, std::vector<int> &out);
-
-long long roi_sep_tile_table(const RoiPlan &p, int layer, int k, std::vector<int> &out) { return sep_tile_table(p, p.down.rect, layer, k, out); }
-long long roi_sep_tile_table_live(const RoiPlan &p, int layer, int k, std::vector<int> &out) { return sep_tile_table(p, p.down.rect_live, layer, k, out); }
-
-static long long sep_tile_table(const RoiPlan &p, const RoiRect (*rects)[ROI_MAX_CLASSES], int layer, int k, std::vector<int> &out)
-{
-    out.clear();
-    const RoiDownPlan &d = p.down;
-    const int b = layer / 6, kk = layer % 6;
-    if (k < 1 || layer < 0 || b >= d.n_down || (kk != 1 && kk != 3) || !((d.fused_mask >> b) & 1u)) return 0;
-    const int TW = d.res[layer] / 16, TPP = TW * TW;
-    const long long full = (long long)k * p.tiles_per_img * TPP;
-    if (full > 0x7fffffffLL) return 0;
-    for (int cl = 0; cl < p.n_classes; cl++) {
-        const RoiRect &q = rects[layer][cl];           // whole tiles (walk_down_axis rounds a fused level's rectangles to 16)
-        const int ty0 = q.y0 / 16, ty1 = (q.y0 + q.rh) / 16, tx0 = q.x0 / 16, tx1 = (q.x0 + q.rw) / 16;
-        for (int pt = k * p.class_base[cl]; pt < k * p.class_base[cl + 1]; pt++)
-            for (int ty = ty0; ty < ty1; ty++)
-                for (int tx = tx0; tx < tx1; tx++) out.push_back(pt * TPP + ty * TW + tx);
-    }
-    return full;
-}
-
 // ---- the shared-interior form (roi_plan.h:RoiDownPlan::share) ----
 namespace {
 
@@ -445,19 +421,69 @@ void share_rect_keys(const RoiPlan &p, std::vector<AxisKey> &keys, const Iv *inn
     }
 }
 
-// per class: the rectangles as launched, the copies of the bottleneck tensor, the totals
+// ---- what the three sharing forms build per class the same way ----
+typedef RoiDownPlan::RectForm RectForm;
+
+bool live_class(const RoiPlan &p, int k) { return p.class_count[k] > 0 && p.read[k].rh > 0 && p.read[k].rw > 0; }
+unsigned char *mask_at(Mask &m, int ws, int l, int k, int axis) { return m.data() + (((size_t)l * ROI_MAX_CLASSES + k) * 2 + axis) * ws; }
+
+// The copies of class k's tensor l out of its neighbours, the product of its axes: from the right neighbour the rows it computes itself
+// by its shared columns, from the lower one its shared rows by its own columns, from the diagonal one shared by shared
+void put_fills(std::vector<RoiDownPlan::ShareFill> &out, int l, int k, const std::vector<Iv> &own_rows, const std::vector<Iv> &got_rows,
+               const std::vector<Iv> &own_cols, const std::vector<Iv> &got_cols)
+{
+    auto put = [&](int dir, const std::vector<Iv> &rows, const std::vector<Iv> &cols) {
+        for (const Iv &r : rows)
+            for (const Iv &c : cols) out.push_back(RoiDownPlan::ShareFill{l, k, dir, r.lo, c.lo, r.hi - r.lo, c.hi - c.lo});
+    };
+    put(0, own_rows, got_cols); put(1, got_rows, own_cols); put(2, got_rows, got_cols);
+}
+
+// The rectangles a class launches for an exact set, the product of at most two runs per axis: rows exact; round4: the columns rounded
+// outwards to multiples of 4 inside rl (the class's rect_live), two runs that meet after rounding being one.  True: they are not rl itself.
+bool launched_rects(const std::vector<Iv> &rows, std::vector<Iv> cols, bool round4, const RoiRect &rl, RoiRect *out, int &n)
+{
+    for (Iv &c : cols)
+        if (round4) c = meet(Iv{c.lo & ~3, (c.hi + 3) & ~3}, Iv{rl.x0, rl.x0 + rl.rw});
+    if (cols.size() == 2 && cols[0].hi >= cols[1].lo) { cols[0].hi = cols[1].hi; cols.pop_back(); }
+    n = 0;
+    for (const Iv &r : rows)
+        for (const Iv &c : cols) out[n++] = RoiRect{r.lo, c.lo, r.hi - r.lo, c.hi - c.lo};
+    return n != 1 || out[0].y0 != rl.y0 || out[0].x0 != rl.x0 || out[0].rh != rl.rh || out[0].rw != rl.rw;
+}
+
+// layer l of a form, once its rectangles stand: the totals, and the form's longest segment table
+void tally(const RoiPlan &p, RectForm &f, int l)
+{
+    const RoiDownPlan &d = p.down;
+    const double area = (double)d.res[l] * d.res[l] * p.tiles_per_img;
+    const double mpp = area > 0 ? d.mac_full[l] / area : 0, bpp = area > 0 ? d.bytes_full[l] / area : 0;
+    f.mac[l] = f.bytes[l] = f.px[l] = 0;
+    int nseg = 0;
+    for (int k = 0; k < p.n_classes; k++) {
+        for (int i = 0; i < f.n[l][k]; i++) {
+            const double px = (double)f.rects[l][k][i].rh * f.rects[l][k][i].rw * p.class_count[k];
+            f.mac[l] += mpp * px; f.bytes[l] += bpp * px; f.px[l] += px;
+        }
+        if (p.class_count[k] > 0) nseg += f.n[l][k];
+    }
+    f.segs = std::max(f.segs, nseg);
+}
+
+// per class: the rectangles as launched, the copies of the bottleneck tensor, the totals (RoiDownPlan::rcomp)
 void share_rect_classes(RoiPlan &p, const std::vector<AxisKey> &keys, const int *krow, const int *kcol)
 {
     RoiDownPlan &d = p.down;
+    RectForm &f = d.rcomp;
     const int NL = d.n_layers, ws = p.ws, bl = d.n_down - 1;
-    d.rect_any = false; d.rect_fill.clear(); d.rect_segs = 0;
-    d.rcomp_mask.assign((size_t)NL * ROI_MAX_CLASSES * 2 * ws, 0);
+    f = RectForm();
+    f.mask.assign((size_t)NL * ROI_MAX_CLASSES * 2 * ws, 0);
     // A class takes the form in all six layers of the level or in none (a layer that fell back to rect_live on its own would compute live
     // over producers whose comp was already cut): only where every layer's comp lies inside its rect_live
     bool takes[ROI_MAX_CLASSES] = {};
     for (int k = 0; k < p.n_classes; k++) {
         const AxisKey &kr = keys[krow[k]], &kc = keys[kcol[k]];
-        takes[k] = bl >= 0 && p.class_count[k] > 0 && p.read[k].rh > 0 && p.read[k].rw > 0 && (!empty(kr.rshare) || !empty(kc.rshare));
+        takes[k] = bl >= 0 && live_class(p, k) && (!empty(kr.rshare) || !empty(kc.rshare));
         for (int kk = 0; takes[k] && kk < 6; kk++) {
             const RoiRect rl = d.rect_live[6 * bl + kk][k];
             for (const Iv &r : runs_of(kr.rc[kk])) takes[k] = takes[k] && r.lo >= rl.y0 && r.hi <= rl.y0 + rl.rh;
@@ -465,62 +491,44 @@ void share_rect_classes(RoiPlan &p, const std::vector<AxisKey> &keys, const int 
         }
     }
     for (int l = 0; l < NL; l++) {
-        d.mac_rect[l] = d.bytes_rect[l] = 0;
-        const double area = (double)d.res[l] * d.res[l] * p.tiles_per_img;
-        const double mpp = area > 0 ? d.mac_full[l] / area : 0, bpp = area > 0 ? d.bytes_full[l] / area : 0;
-        int nseg = 0;
         for (int k = 0; k < p.n_classes; k++) {
             const AxisKey &kr = keys[krow[k]], &kc = keys[kcol[k]];
             const RoiRect rl = d.rect_live[l][k];
-            int &n = d.rcomp_n[l][k];
-            n = 0;
-            for (int i = 0; i < 4; i++) { d.rshare[l][k][i] = 0; d.rcomp[l][k][i] = RoiRect{0, 0, 0, 0}; }
-            const bool live_cls = p.class_count[k] > 0 && p.read[k].rh > 0 && p.read[k].rw > 0;
-            unsigned char *cm = d.rcomp_mask.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * ws;
+            int *sh = d.rshare[l][k];
+            sh[0] = sh[1] = sh[2] = sh[3] = 0;
             const int kk = l - 6 * bl;
-            const bool done = kk >= 0 && kk < 6 && takes[k];
-            if (done) {
-                std::vector<Iv> rows = runs_of(kr.rc[kk]), cols = runs_of(kc.rc[kk]);
-                for (Iv &c : cols)
-                    if (kk < 5) c = meet(Iv{c.lo & ~3, (c.hi + 3) & ~3}, Iv{rl.x0, rl.x0 + rl.rw});
-                if (cols.size() == 2 && cols[0].hi >= cols[1].lo) { cols[0].hi = cols[1].hi; cols.pop_back(); }
-                for (const Iv &r : rows)
-                    for (const Iv &c : cols) d.rcomp[l][k][n++] = RoiRect{r.lo, c.lo, r.hi - r.lo, c.hi - c.lo};
-                std::copy(kr.rc[kk].begin(), kr.rc[kk].end(), cm);
-                std::copy(kc.rc[kk].begin(), kc.rc[kk].end(), cm + ws);
-                if (n != 1 || d.rcomp[l][k][0].y0 != rl.y0 || d.rcomp[l][k][0].x0 != rl.x0 || d.rcomp[l][k][0].rh != rl.rh || d.rcomp[l][k][0].rw != rl.rw)
-                    d.rect_any = true;
+            if (kk >= 0 && kk < 6 && takes[k]) {
+                if (launched_rects(runs_of(kr.rc[kk]), runs_of(kc.rc[kk]), kk < 5, rl, f.rects[l][k], f.n[l][k])) f.any = true;
+                std::copy(kr.rc[kk].begin(), kr.rc[kk].end(), mask_at(f.mask, ws, l, k, 0));
+                std::copy(kc.rc[kk].begin(), kc.rc[kk].end(), mask_at(f.mask, ws, l, k, 1));
+                if (kk == 5) {          // the copies: all of the bottleneck tensor's zone
+                    sh[0] = kr.rshare.lo; sh[1] = kr.rshare.hi; sh[2] = kc.rshare.lo; sh[3] = kc.rshare.hi;
+                    std::vector<Iv> rs, cs;
+                    if (!empty(kr.rshare)) rs.push_back(kr.rshare);
+                    if (!empty(kc.rshare)) cs.push_back(kc.rshare);
+                    put_fills(f.fill, l, k, runs_of(kr.rc[5]), rs, runs_of(kc.rc[5]), cs);
+                }
             } else {
-                if (rl.rh > 0 && rl.rw > 0) d.rcomp[l][k][n++] = rl;
-                if (live_cls) {
+                if (rl.rh > 0 && rl.rw > 0) f.rects[l][k][f.n[l][k]++] = rl;
+                if (live_class(p, k)) {
                     const RoiRect lv = d.live[l][k];
-                    for (int v = lv.y0; v < lv.y0 + lv.rh; v++) cm[v] = 1;
-                    for (int v = lv.x0; v < lv.x0 + lv.rw; v++) cm[ws + v] = 1;
+                    std::fill_n(mask_at(f.mask, ws, l, k, 0) + lv.y0, lv.rh, (unsigned char)1);
+                    std::fill_n(mask_at(f.mask, ws, l, k, 1) + lv.x0, lv.rw, (unsigned char)1);
                 }
             }
-            for (int i = 0; i < n; i++) {
-                d.mac_rect[l] += mpp * d.rcomp[l][k][i].rh * d.rcomp[l][k][i].rw * p.class_count[k];
-                d.bytes_rect[l] += bpp * d.rcomp[l][k][i].rh * d.rcomp[l][k][i].rw * p.class_count[k];
-            }
-            if (p.class_count[k] > 0) nseg += n;
-            // the copies: all of the bottleneck tensor's zone
-            if (done && kk == 5) {
-                int *sh = d.rshare[l][k];
-                sh[0] = kr.rshare.lo; sh[1] = kr.rshare.hi; sh[2] = kc.rshare.lo; sh[3] = kc.rshare.hi;
-                const std::vector<Iv> rc = runs_of(kr.rc[5]), cc = runs_of(kc.rc[5]);
-                std::vector<Iv> rs, cs;
-                if (!empty(kr.rshare)) rs.push_back(kr.rshare);
-                if (!empty(kc.rshare)) cs.push_back(kc.rshare);
-                auto put = [&](int dir, const std::vector<Iv> &rows, const std::vector<Iv> &cols) {
-                    for (const Iv &r : rows)
-                        for (const Iv &c : cols) d.rect_fill.push_back(RoiDownPlan::ShareFill{l, k, dir, r.lo, c.lo, r.hi - r.lo, c.hi - c.lo});
-                };
-                put(0, rc, cs); put(1, rs, cc); put(2, rs, cs);
-            }
         }
-        d.rect_segs = std::max(d.rect_segs, nseg);
+        tally(p, f, l);
     }
-    if (!d.rect_any) d.rect_fill.clear();
+    if (!f.any) f.fill.clear();
+}
+
+// the exact sets in force below the fused levels' form: rcomp's in the unfused last level where the plan has that form, comp elsewhere
+Mask masks_below_fused(const RoiDownPlan &d, int ws)
+{
+    Mask m = d.comp;
+    const size_t per_layer = (size_t)ROI_MAX_CLASSES * 2 * ws, l0 = 6 * (size_t)(d.n_down - 1);
+    if (d.rcomp.any) std::copy(d.rcomp.mask.begin() + l0 * per_layer, d.rcomp.mask.begin() + (l0 + 6) * per_layer, m.begin() + l0 * per_layer);
+    return m;
 }
 
 // per class: the fused levels' rectangle launches in the shared-interior form and the halo strips of their pooled outputs
@@ -528,18 +536,14 @@ void share_rect_classes(RoiPlan &p, const std::vector<AxisKey> &keys, const int 
 void share_fused_rect_classes(RoiPlan &p, const std::vector<AxisKey> &keys, const int *krow, const int *kcol)
 {
     RoiDownPlan &d = p.down;
-    const int NL = d.n_layers, ws = p.ws, L = 6 * d.n_down, bl = d.n_down - 1;
-    d.fused_rect_any = false; d.fused_fill.clear(); d.fused_rect_segs = 0;
+    RectForm &f = d.fcomp;
+    const int NL = d.n_layers, ws = p.ws, L = 6 * d.n_down;
+    f = RectForm();
     for (int l = 0; l < NL; l++) d.fused_fill_on[l] = false;
-    // the exact sets in force: rcomp_mask in the unfused last level, comp elsewhere
-    d.fcomp_mask = d.comp;
-    const size_t per_layer = (size_t)ROI_MAX_CLASSES * 2 * ws;
-    if (d.rect_any)
-        std::copy(d.rcomp_mask.begin() + 6 * bl * per_layer, d.rcomp_mask.begin() + (6 * bl + 6) * per_layer, d.fcomp_mask.begin() + 6 * bl * per_layer);
-    auto mask_at = [&](int l, int k, int axis) { return d.fcomp_mask.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * ws + (size_t)axis * ws; };
-    auto get = [&](int l, int k, int axis) { const unsigned char *m = mask_at(l, k, axis); return Mask(m, m + d.res[l]); };
+    f.mask = masks_below_fused(d, ws);
+    auto get = [&](int l, int k, int axis) { const unsigned char *m = mask_at(f.mask, ws, l, k, axis); return Mask(m, m + d.res[l]); };
     auto within = [](Mask a, Iv lv) { for (int i = 0; i < (int)a.size(); i++) a[i] = a[i] && in_iv(lv, i); return a; };
-    const bool form = d.share_any && d.rect_any;
+    const bool form = d.share_any && d.rcomp.any;
     auto in_form = [&](int b) { return form && b >= 0 && b < d.n_down && (((d.fused_mask & ROI_SHARE_LEVELS & ROI_SHARE_FUSED_RECT_LEVELS) >> b) & 1u); };
     bool takes[ROI_MAX_DOWN][ROI_MAX_CLASSES] = {};
     // the exact sets, from the deepest level upwards (the strips of level b read the sets of level b + 1)
@@ -549,7 +553,7 @@ void share_fused_rect_classes(RoiPlan &p, const std::vector<AxisKey> &keys, cons
         const bool stem = b == 0 && (d.fused_mask & 1u);
         for (int k = 0; k < p.n_classes; k++) {
             const AxisKey &kr = keys[krow[k]], &kc = keys[kcol[k]];
-            bool t = p.class_count[k] > 0 && p.read[k].rh > 0 && p.read[k].rw > 0 && (!empty(kr.share[l0 + 5]) || !empty(kc.share[l0 + 5]));
+            bool t = live_class(p, k) && (!empty(kr.share[l0 + 5]) || !empty(kc.share[l0 + 5]));
             Mask m[3][2];           // pooled output, residual, stem at the even pixels; rows, columns
             for (int ax = 0; ax < 2 && t; ax++) {
                 const AxisKey &key = ax ? kc : kr;
@@ -568,44 +572,27 @@ void share_fused_rect_classes(RoiPlan &p, const std::vector<AxisKey> &keys, cons
             takes[b][k] = t;
             if (!t) continue;
             for (int ax = 0; ax < 2; ax++) {
-                std::copy(m[1][ax].begin(), m[1][ax].end(), mask_at(l0 + 4, k, ax));
-                if (stem) std::copy(m[2][ax].begin(), m[2][ax].end(), mask_at(L, k, ax));
+                std::copy(m[1][ax].begin(), m[1][ax].end(), mask_at(f.mask, ws, l0 + 4, k, ax));
+                if (stem) std::copy(m[2][ax].begin(), m[2][ax].end(), mask_at(f.mask, ws, L, k, ax));
             }
         }
     }
-    // the rectangles as launched, every layer
+    // the rectangles as launched, every layer: of the exact set where the class takes the form, rcomp's elsewhere
     for (int l = 0; l < NL; l++) {
-        d.mac_frect[l] = d.bytes_frect[l] = d.px_frect[l] = d.px_live[l] = d.copy_old[l] = d.copy_new[l] = 0;
-        const double area = (double)d.res[l] * d.res[l] * p.tiles_per_img;
-        const double mpp = area > 0 ? d.mac_full[l] / area : 0, bpp = area > 0 ? d.bytes_full[l] / area : 0;
+        d.px_live[l] = d.copy_old[l] = d.copy_new[l] = 0;
         const int b = l == L ? 0 : l / 6, kk = l == L ? 4 : l % 6;
         const bool cut = l <= L && (kk == 4 || kk == 5) && (l != L || (d.fused_mask & 1u)) && in_form(b);
-        int nseg = 0;
         for (int k = 0; k < p.n_classes; k++) {
             const RoiRect rl = d.rect_live[l][k];
-            int &n = d.fcomp_n[l][k];
-            n = 0;
-            for (int i = 0; i < 4; i++) d.fcomp[l][k][i] = RoiRect{0, 0, 0, 0};
             if (cut && takes[b][k]) {
-                std::vector<Iv> rows = runs_of(get(l, k, 0)), cols = runs_of(get(l, k, 1));
-                for (Iv &c : cols)
-                    if (kk != 5) c = meet(Iv{c.lo & ~3, (c.hi + 3) & ~3}, Iv{rl.x0, rl.x0 + rl.rw});
-                if (cols.size() == 2 && cols[0].hi >= cols[1].lo) { cols[0].hi = cols[1].hi; cols.pop_back(); }
-                for (const Iv &r : rows)
-                    for (const Iv &c : cols) d.fcomp[l][k][n++] = RoiRect{r.lo, c.lo, r.hi - r.lo, c.hi - c.lo};
-                if (n != 1 || d.fcomp[l][k][0].y0 != rl.y0 || d.fcomp[l][k][0].x0 != rl.x0 || d.fcomp[l][k][0].rh != rl.rh || d.fcomp[l][k][0].rw != rl.rw)
-                    d.fused_rect_any = true;
+                if (launched_rects(runs_of(get(l, k, 0)), runs_of(get(l, k, 1)), kk != 5, rl, f.rects[l][k], f.n[l][k])) f.any = true;
             } else {
-                n = roi_rect_comp(p, l, k, d.fcomp[l][k]);
-            }
-            for (int i = 0; i < n; i++) {
-                const double px = (double)d.fcomp[l][k][i].rh * d.fcomp[l][k][i].rw * p.class_count[k];
-                d.mac_frect[l] += mpp * px; d.bytes_frect[l] += bpp * px; d.px_frect[l] += px;
+                f.n[l][k] = d.rcomp.n[l][k];
+                std::copy(d.rcomp.rects[l][k], d.rcomp.rects[l][k] + 4, f.rects[l][k]);
             }
             d.px_live[l] += (double)rl.rh * rl.rw * p.class_count[k];
-            if (p.class_count[k] > 0) nseg += n;
         }
-        d.fused_rect_segs = std::max(d.fused_rect_segs, nseg);
+        tally(p, f, l);
     }
     // the halo strips of the pooled outputs: the shared pixels the next level's exact sets tap
     for (int b = 0; b + 1 < d.n_down; b++) {
@@ -613,7 +600,7 @@ void share_fused_rect_classes(RoiPlan &p, const std::vector<AxisKey> &keys, cons
         const int l5 = 6 * b + 5, Ho = d.res[l5], ln = 6 * (b + 1);
         d.fused_fill_on[l5] = true;
         for (int k = 0; k < p.n_classes; k++) {
-            if (p.class_count[k] <= 0 || p.read[k].rh <= 0 || p.read[k].rw <= 0) continue;
+            if (!live_class(p, k)) continue;
             const AxisKey *key[2] = {&keys[krow[k]], &keys[kcol[k]]};
             std::vector<Iv> own[2], got[2];         // per axis: the tapped pixels the patch computes itself, and those in its shared zone
             for (int ax = 0; ax < 2; ax++) {
@@ -626,39 +613,24 @@ void share_fused_rect_classes(RoiPlan &p, const std::vector<AxisKey> &keys, cons
                 }
                 own[ax] = runs_of(o); got[ax] = runs_of(g);
             }
-            auto put = [&](int dir, const std::vector<Iv> &rows, const std::vector<Iv> &cols) {
-                for (const Iv &r : rows)
-                    for (const Iv &c : cols) {
-                        d.fused_fill.push_back(RoiDownPlan::ShareFill{l5, k, dir, r.lo, c.lo, r.hi - r.lo, c.hi - c.lo});
-                        d.copy_new[l5] += (double)(r.hi - r.lo) * (c.hi - c.lo) * p.class_count[k];
-                    }
-            };
-            put(0, own[0], got[1]); put(1, got[0], own[1]); put(2, got[0], got[1]);
+            put_fills(f.fill, l5, k, own[0], got[0], own[1], got[1]);
         }
-        d.fused_rect_any = true;
+        f.any = true;
     }
-    for (const RoiDownPlan::ShareFill &f : d.share_fill) {
-        const double px = (double)f.rh * f.rw * p.class_count[f.cls];
-        d.copy_old[f.layer] += px;
-        if (!d.fused_fill_on[f.layer]) d.copy_new[f.layer] += px;
+    // a table that does not fit keeps the form below, and so does a plan without the form: rcomp's tables, no strips
+    if (!f.any || f.segs > ROI_MAX_SEGS - 1) {
+        f = d.rcomp;
+        f.any = false;
+        f.fill.clear();
+        f.mask = masks_below_fused(d, ws);
+        for (int l = 0; l < NL; l++) d.fused_fill_on[l] = false;
     }
-    // a table that does not fit keeps the form above
-    if (d.fused_rect_any && d.fused_rect_segs > ROI_MAX_SEGS - 1) d.fused_rect_any = false;
-    if (!d.fused_rect_any) {
-        d.fused_fill.clear();
-        d.fused_rect_segs = d.rect_segs;
-        for (int l = 0; l < NL; l++) {
-            d.fused_fill_on[l] = false;
-            d.copy_new[l] = d.copy_old[l];
-            d.mac_frect[l] = d.mac_rect[l]; d.bytes_frect[l] = d.bytes_rect[l]; d.px_frect[l] = 0;
-            for (int k = 0; k < p.n_classes; k++) {
-                d.fcomp_n[l][k] = roi_rect_comp(p, l, k, d.fcomp[l][k]);
-                for (int i = 0; i < d.fcomp_n[l][k]; i++) d.px_frect[l] += (double)d.fcomp[l][k][i].rh * d.fcomp[l][k][i].rw * p.class_count[k];
-            }
-        }
-        d.fcomp_mask = d.comp;
-        if (d.rect_any)
-            std::copy(d.rcomp_mask.begin() + 6 * bl * per_layer, d.rcomp_mask.begin() + (6 * bl + 6) * per_layer, d.fcomp_mask.begin() + 6 * bl * per_layer);
+    // what is copied into a tensor without and with the form
+    auto px_of = [&](const RoiDownPlan::ShareFill &c) { return (double)c.rh * c.rw * p.class_count[c.cls]; };
+    for (const RoiDownPlan::ShareFill &c : f.fill) d.copy_new[c.layer] += px_of(c);
+    for (const RoiDownPlan::ShareFill &c : d.share_fill) {
+        d.copy_old[c.layer] += px_of(c);
+        if (!d.fused_fill_on[c.layer]) d.copy_new[c.layer] += px_of(c);
     }
 }
 
@@ -778,25 +750,18 @@ void roi_plan_share(RoiPlan &p)
     d.comp.assign((size_t)NL * ROI_MAX_CLASSES * 2 * ws, 0);
     for (int k = 0; k < p.n_classes; k++) {
         const AxisKey &kr = keys[krow[k]], &kc = keys[kcol[k]];
-        const bool live_cls = p.class_count[k] > 0 && p.read[k].rh > 0 && p.read[k].rw > 0;
         for (int l = 0; l < NL; l++) {
             int *sh = d.share[l][k];
             sh[0] = sh[1] = sh[2] = sh[3] = 0;
             d.tile_rows[l][k] = d.tile_cols[l][k] = ~0ull;
-            if (!live_cls) continue;
+            if (!live_class(p, k)) continue;
             sh[0] = kr.share[l].lo; sh[1] = kr.share[l].hi; sh[2] = kc.share[l].lo; sh[3] = kc.share[l].hi;
             d.tile_rows[l][k] = kr.tiles[l]; d.tile_cols[l][k] = kc.tiles[l];
-            unsigned char *cm = d.comp.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * ws;
-            std::copy(kr.comp[l].begin(), kr.comp[l].end(), cm);
-            std::copy(kc.comp[l].begin(), kc.comp[l].end(), cm + ws);
+            std::copy(kr.comp[l].begin(), kr.comp[l].end(), mask_at(d.comp, ws, l, k, 0));
+            std::copy(kc.comp[l].begin(), kc.comp[l].end(), mask_at(d.comp, ws, l, k, 1));
             if (!any(kr.sfill[l]) && !any(kc.sfill[l])) continue;
             d.share_any = true;
-            const std::vector<Iv> rc = runs_of(kr.comp[l]), rs = runs_of(kr.sfill[l]), cc = runs_of(kc.comp[l]), cs = runs_of(kc.sfill[l]);
-            auto put = [&](int dir, const std::vector<Iv> &rows, const std::vector<Iv> &cols) {
-                for (const Iv &r : rows)
-                    for (const Iv &c : cols) d.share_fill.push_back(RoiDownPlan::ShareFill{l, k, dir, r.lo, c.lo, r.hi - r.lo, c.hi - c.lo});
-            };
-            put(0, rc, cs); put(1, rs, cc); put(2, rs, cs);
+            put_fills(d.share_fill, l, k, runs_of(kr.comp[l]), runs_of(kr.sfill[l]), runs_of(kc.comp[l]), runs_of(kc.sfill[l]));
         }
     }
     share_rect_classes(p, keys, krow, kcol);
@@ -815,48 +780,113 @@ void roi_share_neighbours(const RoiPlan &p, int k, std::vector<int> &out)
                 if (p.down.nbr[3 * t + j] >= 0) out[(size_t)3 * pos(img, t) + j] = pos(img, p.down.nbr[3 * t + j]);
 }
 
-long long roi_sep_tile_table_share(const RoiPlan &p, int layer, int k, std::vector<int> &out)
+// ---- what a pass launches under a form (roi_plan.h:RoiDownForm) ----
+RoiDownForm roi_down_form(const RoiPlan &p, RoiDownForm want)
 {
     const RoiDownPlan &d = p.down;
-    if (!d.share_any) return roi_sep_tile_table_live(p, layer, k, out);
+    RoiDownForm has = ROI_DOWN_FULL;
+    if (p.n_classes > 0 && d.n_down > 0) has = ROI_DOWN_CONST;
+    if (has == ROI_DOWN_CONST && d.share_any) has = ROI_DOWN_SHARE;
+    if (has == ROI_DOWN_SHARE && d.rcomp.any && d.rcomp.segs + 1 <= ROI_MAX_SEGS) has = ROI_DOWN_SHARE_RECT;
+    if (has == ROI_DOWN_SHARE_RECT && d.fcomp.any && d.fcomp.segs + 1 <= ROI_MAX_SEGS) has = ROI_DOWN_SHARE_FUSED_RECT;
+    return std::min(has, want);
+}
+
+// the rectangles of one of the two rectangle forms (null: rect_live), the empty ones left out
+static int form_rects(const RoiDownPlan &d, const RoiDownPlan::RectForm *f, int l, int k, RoiRect *out)
+{
+    if (f) {
+        std::copy(f->rects[l][k], f->rects[l][k] + f->n[l][k], out);
+        return f->n[l][k];
+    }
+    out[0] = d.rect_live[l][k];
+    return out[0].rh > 0 && out[0].rw > 0 ? 1 : 0;
+}
+
+int roi_down_rects(const RoiPlan &p, RoiDownForm form, int l, int k, RoiRect out[4])
+{
+    const RoiDownPlan &d = p.down;
+    switch (roi_down_form(p, form)) {
+    case ROI_DOWN_FULL: return 0;
+    case ROI_DOWN_REGION: out[0] = d.rect[l][k]; return out[0].rh > 0 && out[0].rw > 0 ? 1 : 0;
+    case ROI_DOWN_SHARE_RECT: return form_rects(d, &d.rcomp, l, k, out);
+    case ROI_DOWN_SHARE_FUSED_RECT: return form_rects(d, &d.fcomp, l, k, out);
+    default: return form_rects(d, nullptr, l, k, out);
+    }
+}
+
+int roi_down_stem_layer(const RoiPlan &p, RoiDownForm form)
+{
+    return roi_down_form(p, form) == ROI_DOWN_SHARE_FUSED_RECT ? 6 * p.down.n_down : 4;
+}
+
+long long roi_sep_tile_table(const RoiPlan &p, RoiDownForm form, int layer, int k, std::vector<int> &out)
+{
     out.clear();
+    const RoiDownPlan &d = p.down;
+    form = roi_down_form(p, form);
     const int b = layer / 6, kk = layer % 6;
-    if (k < 1 || layer < 0 || b >= d.n_down || (kk != 1 && kk != 3) || !((d.fused_mask >> b) & 1u)) return 0;
+    if (form == ROI_DOWN_FULL || k < 1 || layer < 0 || b >= d.n_down || (kk != 1 && kk != 3) || !((d.fused_mask >> b) & 1u)) return 0;
+    const bool share = form >= ROI_DOWN_SHARE;
     const int TW = d.res[layer] / 16, TPP = TW * TW;
     const long long full = (long long)k * p.tiles_per_img * TPP;
-    if (full > 0x7fffffffLL || TW > 64) return 0;
+    if (full > 0x7fffffffLL || (share && TW > 64)) return 0;
     for (int cl = 0; cl < p.n_classes; cl++) {
-        const RoiRect &q = d.rect_live[layer][cl];
+        const RoiRect &q = (form == ROI_DOWN_REGION ? d.rect : d.rect_live)[layer][cl];         // whole tiles (a fused level's rectangles are rounded to 16)
         const int ty0 = q.y0 / 16, ty1 = (q.y0 + q.rh) / 16, tx0 = q.x0 / 16, tx1 = (q.x0 + q.rw) / 16;
         for (int pt = k * p.class_base[cl]; pt < k * p.class_base[cl + 1]; pt++)
             for (int ty = ty0; ty < ty1; ty++) {
-                if (!((d.tile_rows[layer][cl] >> ty) & 1ull)) continue;
+                if (share && !((d.tile_rows[layer][cl] >> ty) & 1ull)) continue;
                 for (int tx = tx0; tx < tx1; tx++)
-                    if ((d.tile_cols[layer][cl] >> tx) & 1ull) out.push_back(pt * TPP + ty * TW + tx);
+                    if (!share || ((d.tile_cols[layer][cl] >> tx) & 1ull)) out.push_back(pt * TPP + ty * TW + tx);
             }
     }
     return full;
 }
 
-int roi_rect_comp(const RoiPlan &p, int l, int k, RoiRect *out)
+void roi_down_segs(const RoiPlan &p, RoiDownForm form, int l, int k, RoiSegs &out)
 {
-    const RoiDownPlan &d = p.down;
-    if (d.rect_any) {
-        for (int i = 0; i < d.rcomp_n[l][k]; i++) out[i] = d.rcomp[l][k][i];
-        return d.rcomp_n[l][k];
+    out = RoiSegs{};
+    form = roi_down_form(p, form);
+    for (int cl = 0; cl < p.n_classes; cl++) {
+        RoiRect q[4];
+        const int nq = p.class_count[cl] > 0 ? roi_down_rects(p, form, l, cl, q) : 0;
+        for (int i = 0; i < nq; i++) {
+            RoiSeg &g = out.s[out.nseg++];
+            g.p0 = k * p.class_base[cl]; g.np = k * p.class_count[cl];
+            g.y0 = q[i].y0; g.x0 = q[i].x0; g.rh = q[i].rh; g.rw = q[i].rw;
+        }
     }
-    const RoiRect &q = d.rect_live[l][k];
-    if (q.rh <= 0 || q.rw <= 0) return 0;
-    out[0] = q;
-    return 1;
+    if (form >= ROI_DOWN_CONST) {
+        RoiSeg &g = out.s[out.nseg++];
+        g.p0 = k * p.tiles_per_img; g.np = k; g.rh = g.rw = p.down.res[l];
+    }
 }
 
-int roi_fused_rect_comp(const RoiPlan &p, int l, int k, RoiRect *out)
+void roi_down_const_items(const RoiPlan &p, RoiDownForm form, int l, int k, FillItems &out)
 {
+    out = FillItems{};
+    if (roi_down_form(p, form) < ROI_DOWN_CONST) return;
+    for (int cl = 0; cl < p.n_classes; cl++)
+        for (int i = 0; i < 4 && p.class_count[cl] > 0; i++) {
+            const RoiRect &q = p.down.fill[l][cl][i];
+            if (q.rh <= 0 || q.rw <= 0) continue;
+            out.it[out.n++] = FillItem{k * p.class_base[cl], k * p.class_count[cl], p.class_count[cl], q.y0, q.x0, q.rh, q.rw};
+        }
+}
+
+void roi_down_copy_items(const RoiPlan &p, RoiDownForm form, int l, int k, std::vector<ShareItem> &out)
+{
+    out.clear();
     const RoiDownPlan &d = p.down;
-    if (!d.fused_rect_any) return roi_rect_comp(p, l, k, out);
-    for (int i = 0; i < d.fcomp_n[l][k]; i++) out[i] = d.fcomp[l][k][i];
-    return d.fcomp_n[l][k];
+    form = roi_down_form(p, form);
+    if (form < ROI_DOWN_SHARE) return;
+    auto take = [&](const std::vector<RoiDownPlan::ShareFill> &from) {
+        for (const RoiDownPlan::ShareFill &f : from)
+            if (f.layer == l) out.push_back(ShareItem{k * p.class_base[f.cls], k * p.class_count[f.cls], f.dir, f.y0, f.x0, f.rh, f.rw});
+    };
+    take(form == ROI_DOWN_SHARE_FUSED_RECT && d.fused_fill_on[l] ? d.fcomp.fill : d.share_fill);
+    if (form >= ROI_DOWN_SHARE_RECT) take(d.rcomp.fill);
 }
 
 bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_classes, RoiPlan &out)
@@ -1008,30 +1038,73 @@ extern "C" int tmat_roi_plan_exact(int hh, int ww, int patch, int n_up, const in
                            class_count, rects, mac_planned, mac_full);
 }
 
+// ---- the exports of the down plan: what they share ----
+// the argument check (args_ok: the export's own pointers and caps) and the plan; TMAT_OK, or the error set under the export's name
+static int down_plan_for(const char *name, bool args_ok, int hh, int ww, int patch, int n_up, const int *up_channels, int n_down,
+                         const int *down_channels, unsigned fused_mask, int max_classes, RoiPlan &p)
+{
+    if (!args_ok || !up_channels || !down_channels || max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
+        set_error(std::string(name) + ": bad argument");
+        return TMAT_E_ARG;
+    }
+    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, max_classes, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
+        set_error(std::string(name) + ": unsupported geometry");
+        return TMAT_E_ARG;
+    }
+    return TMAT_OK;
+}
+// a rectangle as (y0, x0, rows, columns); `in` false: a class the plan does not have, zeros
+static void put_rect(int *o, const RoiRect &q, bool in = true)
+{
+    o[0] = in ? q.y0 : 0; o[1] = in ? q.x0 : 0; o[2] = in ? q.rh : 0; o[3] = in ? q.rw : 0;
+}
+// [max_classes][4 rectangles][4] and their counts for layer l: the rectangles of form f (null: rect_live)
+static void put_form_rects(const RoiPlan &p, const RoiDownPlan::RectForm *f, int l, int max_classes, int *n_rects, int *rects)
+{
+    for (int k = 0; k < max_classes; k++) {
+        RoiRect q[4] = {};
+        const int n = k < p.n_classes ? form_rects(p.down, f, l, k, q) : 0;
+        n_rects[(size_t)l * max_classes + k] = n;
+        for (int i = 0; i < 4; i++) put_rect(rects + (((size_t)l * max_classes + k) * 4 + i) * 4, q[i], i < n);
+    }
+}
+// [max_classes][2 axes][patch] bytes for layer l out of a table in the layout of RoiDownPlan::comp (empty: zeros)
+static void put_masks(const RoiPlan &p, const std::vector<unsigned char> &m, int l, int max_classes, unsigned char *comp)
+{
+    for (int k = 0; k < max_classes; k++) {
+        unsigned char *o = comp + ((size_t)l * max_classes + k) * 2 * p.ws;
+        if (k < p.n_classes && !m.empty()) std::copy_n(m.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * p.ws, 2 * p.ws, o);
+        else std::fill_n(o, 2 * p.ws, (unsigned char)0);
+    }
+}
+// [n_fill][7] as (layer, class, direction, y0, x0, rows, columns)
+static int put_fill_list(const char *name, const std::vector<RoiDownPlan::ShareFill> &v, int fill_cap, int *n_fill, int *fills)
+{
+    *n_fill = (int)v.size();
+    if (*n_fill > fill_cap) { set_error(std::string(name) + ": fill_cap too small"); return TMAT_E_ARG; }
+    for (size_t i = 0; i < v.size(); i++) {
+        const int o[7] = {v[i].layer, v[i].cls, v[i].dir, v[i].y0, v[i].x0, v[i].rh, v[i].rw};
+        std::copy(o, o + 7, fills + i * 7);
+    }
+    return TMAT_OK;
+}
+
 // The down-path tables of the same plan (roi_plan_down): rects and needs [6 n_down + 4][max_classes][4] as (y0, x0, rows, columns),
 // the four per-layer totals [6 n_down + 4], free_tile [n_down].  down_channels: n_down + 1 entries, the stem's first.
 extern "C" int tmat_roi_plan_down(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
                                   unsigned fused_mask, int max_classes, int *n_classes, int *rects, int *needs, double *mac_planned,
                                   double *mac_full, double *bytes_planned, double *bytes_full, int *free_tile)
 {
-    if (!up_channels || !down_channels || !n_classes || !rects || !needs || !mac_planned || !mac_full || !bytes_planned || !bytes_full ||
-        !free_tile || max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
-        set_error("tmat_roi_plan_down: bad argument");
-        return TMAT_E_ARG;
-    }
     RoiPlan p;
-    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, max_classes, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
-        set_error("tmat_roi_plan_down: unsupported geometry");
-        return TMAT_E_ARG;
-    }
+    const bool args_ok = n_classes && rects && needs && mac_planned && mac_full && bytes_planned && bytes_full && free_tile;
+    if (int rc = down_plan_for("tmat_roi_plan_down", args_ok, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, max_classes, p)) return rc;
     *n_classes = p.n_classes;
     const RoiDownPlan &d = p.down;
     for (int l = 0; l < d.n_layers; l++) {
         for (int k = 0; k < max_classes; k++) {
-            const RoiRect q = k < p.n_classes ? d.rect[l][k] : RoiRect{0, 0, 0, 0}, u = k < p.n_classes ? d.need[l][k] : RoiRect{0, 0, 0, 0};
-            int *o = rects + ((size_t)l * max_classes + k) * 4, *w = needs + ((size_t)l * max_classes + k) * 4;
-            o[0] = q.y0; o[1] = q.x0; o[2] = q.rh; o[3] = q.rw;
-            w[0] = u.y0; w[1] = u.x0; w[2] = u.rh; w[3] = u.rw;
+            const size_t at = ((size_t)l * max_classes + k) * 4;
+            put_rect(rects + at, d.rect[l][k], k < p.n_classes);
+            put_rect(needs + at, d.need[l][k], k < p.n_classes);
         }
         mac_planned[l] = d.mac_planned[l]; mac_full[l] = d.mac_full[l];
         bytes_planned[l] = d.bytes_planned[l]; bytes_full[l] = d.bytes_full[l];
@@ -1042,17 +1115,14 @@ extern "C" int tmat_roi_plan_down(int hh, int ww, int patch, int n_up, const int
 
 // The tile table of a fused separable layer of the same plan for a pass of k images (roi_sep_tile_table): *n_full the full-frame tile
 // count, *n_tiles the planned one; tiles (nullable: counts only) takes the planned tiles' full-frame ids, cap its room.
-static int sep_tiles_export(int live, int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+static int sep_tiles_export(RoiDownForm form, int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
                             unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
 {
-    if (!up_channels || !down_channels || !n_tiles || !n_full || k < 1) { set_error("tmat_roi_sep_tiles: bad argument"); return TMAT_E_ARG; }
     RoiPlan p;
-    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, ROI_MAX_CLASSES, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
-        set_error("tmat_roi_sep_tiles: unsupported geometry");
-        return TMAT_E_ARG;
-    }
+    if (int rc = down_plan_for("tmat_roi_sep_tiles", n_tiles && n_full && k >= 1, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask,
+                               ROI_MAX_CLASSES, p)) return rc;
     std::vector<int> tab;
-    const long long full = live == 2 ? roi_sep_tile_table_share(p, layer, k, tab) : live ? roi_sep_tile_table_live(p, layer, k, tab) : roi_sep_tile_table(p, layer, k, tab);
+    const long long full = roi_sep_tile_table(p, form, layer, k, tab);
     if (full <= 0) { set_error("tmat_roi_sep_tiles: not a fused separable layer of the plan"); return TMAT_E_ARG; }
     *n_full = (int)full;
     *n_tiles = (int)tab.size();
@@ -1063,17 +1133,25 @@ static int sep_tiles_export(int live, int hh, int ww, int patch, int n_up, const
     return TMAT_OK;
 }
 
+// the tiles of ROI_DOWN_REGION
 extern "C" int tmat_roi_sep_tiles(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
                                   unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
 {
-    return sep_tiles_export(0, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
+    return sep_tiles_export(ROI_DOWN_REGION, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
 }
 
-// the same of the constant-ring form (roi_sep_tile_table_live): the tiles of rect_live, a subsequence of tmat_roi_sep_tiles' table
+// the same of ROI_DOWN_CONST: the tiles of rect_live, a subsequence of tmat_roi_sep_tiles' table
 extern "C" int tmat_roi_sep_tiles_live(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
                                        unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
 {
-    return sep_tiles_export(1, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
+    return sep_tiles_export(ROI_DOWN_CONST, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
+}
+
+// the same of ROI_DOWN_SHARE: a subsequence of tmat_roi_sep_tiles_live's table, in its order
+extern "C" int tmat_roi_sep_tiles_share(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                        unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
+{
+    return sep_tiles_export(ROI_DOWN_SHARE, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
 }
 
 // The constant-ring tables of the same plan (RoiDownPlan::nonconst ...): nonconst, live and rect_live [6 n_down + 4][max_classes][4] as
@@ -1082,39 +1160,24 @@ extern "C" int tmat_roi_plan_const(int hh, int ww, int patch, int n_up, const in
                                    unsigned fused_mask, int max_classes, int *n_classes, int *nonconst, int *live, int *rect_live, int *fill,
                                    int *stored, double *mac_live, double *bytes_live)
 {
-    if (!up_channels || !down_channels || !n_classes || !nonconst || !live || !rect_live || !fill || !stored || !mac_live || !bytes_live ||
-        max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
-        set_error("tmat_roi_plan_const: bad argument");
-        return TMAT_E_ARG;
-    }
     RoiPlan p;
-    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, max_classes, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
-        set_error("tmat_roi_plan_const: unsupported geometry");
-        return TMAT_E_ARG;
-    }
+    const bool args_ok = n_classes && nonconst && live && rect_live && fill && stored && mac_live && bytes_live;
+    if (int rc = down_plan_for("tmat_roi_plan_const", args_ok, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, max_classes, p)) return rc;
     *n_classes = p.n_classes;
     const RoiDownPlan &d = p.down;
-    auto put = [](int *o, const RoiRect &q) { o[0] = q.y0; o[1] = q.x0; o[2] = q.rh; o[3] = q.rw; };
     for (int l = 0; l < d.n_layers; l++) {
         for (int k = 0; k < max_classes; k++) {
             const bool in = k < p.n_classes;
             const size_t at = ((size_t)l * max_classes + k) * 4;
-            put(nonconst + at, in ? d.nonconst[l][k] : RoiRect{0, 0, 0, 0});
-            put(live + at, in ? d.live[l][k] : RoiRect{0, 0, 0, 0});
-            put(rect_live + at, in ? d.rect_live[l][k] : RoiRect{0, 0, 0, 0});
-            for (int i = 0; i < 4; i++) put(fill + (at + i) * 4, in ? d.fill[l][k][i] : RoiRect{0, 0, 0, 0});
+            put_rect(nonconst + at, d.nonconst[l][k], in);
+            put_rect(live + at, d.live[l][k], in);
+            put_rect(rect_live + at, d.rect_live[l][k], in);
+            for (int i = 0; i < 4; i++) put_rect(fill + (at + i) * 4, d.fill[l][k][i], in);
         }
         stored[l] = d.stored[l] ? 1 : 0;
         mac_live[l] = d.mac_live[l]; bytes_live[l] = d.bytes_live[l];
     }
     return TMAT_OK;
-}
-
-// the same of the shared-interior form (roi_sep_tile_table_share): a subsequence of tmat_roi_sep_tiles_live's table, in its order
-extern "C" int tmat_roi_sep_tiles_share(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
-                                        unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
-{
-    return sep_tiles_export(2, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
 }
 
 // The shared-interior tables of the same plan (RoiDownPlan::inner ...): inner [6 n_down + 4][max_classes][4] as (y0, x0, rows, columns),
@@ -1124,39 +1187,22 @@ extern "C" int tmat_roi_plan_share(int hh, int ww, int patch, int n_up, const in
                                    unsigned fused_mask, int max_classes, int *n_classes, int *inner, int *share, unsigned char *comp,
                                    int fill_cap, int *n_fill, int *fills, int tiles_cap, int *neighbours)
 {
-    if (!up_channels || !down_channels || !n_classes || !inner || !share || !comp || !n_fill || !fills || !neighbours || fill_cap < 0 ||
-        max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
-        set_error("tmat_roi_plan_share: bad argument");
-        return TMAT_E_ARG;
-    }
     RoiPlan p;
-    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, max_classes, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
-        set_error("tmat_roi_plan_share: unsupported geometry");
-        return TMAT_E_ARG;
-    }
+    const bool args_ok = n_classes && inner && share && comp && n_fill && fills && neighbours && fill_cap >= 0;
+    if (int rc = down_plan_for("tmat_roi_plan_share", args_ok, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, max_classes, p)) return rc;
     const RoiDownPlan &d = p.down;
     if (p.tiles_per_img > tiles_cap || (int)d.nbr.size() != 3 * p.tiles_per_img) { set_error("tmat_roi_plan_share: tiles_cap too small"); return TMAT_E_ARG; }
     *n_classes = p.n_classes;
-    for (int l = 0; l < d.n_layers; l++)
+    for (int l = 0; l < d.n_layers; l++) {
         for (int k = 0; k < max_classes; k++) {
-            const bool in = k < p.n_classes;
             const size_t at = ((size_t)l * max_classes + k) * 4;
-            const RoiRect q = in ? d.inner[l][k] : RoiRect{0, 0, 0, 0};
-            inner[at] = q.y0; inner[at + 1] = q.x0; inner[at + 2] = q.rh; inner[at + 3] = q.rw;
-            for (int i = 0; i < 4; i++) share[at + i] = in ? d.share[l][k][i] : 0;
-            unsigned char *o = comp + ((size_t)l * max_classes + k) * 2 * patch;
-            if (in && !d.comp.empty()) std::copy_n(d.comp.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * patch, 2 * patch, o);
-            else std::fill_n(o, 2 * patch, (unsigned char)0);
+            put_rect(inner + at, d.inner[l][k], k < p.n_classes);
+            for (int i = 0; i < 4; i++) share[at + i] = k < p.n_classes ? d.share[l][k][i] : 0;
         }
-    *n_fill = (int)d.share_fill.size();
-    if (*n_fill > fill_cap) { set_error("tmat_roi_plan_share: fill_cap too small"); return TMAT_E_ARG; }
-    for (int i = 0; i < *n_fill; i++) {
-        const RoiDownPlan::ShareFill &f = d.share_fill[i];
-        int *o = fills + (size_t)i * 7;
-        o[0] = f.layer; o[1] = f.cls; o[2] = f.dir; o[3] = f.y0; o[4] = f.x0; o[5] = f.rh; o[6] = f.rw;
+        put_masks(p, d.comp, l, max_classes, comp);
     }
     std::copy(d.nbr.begin(), d.nbr.end(), neighbours);
-    return TMAT_OK;
+    return put_fill_list("tmat_roi_plan_share", d.share_fill, fill_cap, n_fill, fills);
 }
 
 // The rectangle launches' shared-interior tables of the same plan (RoiDownPlan::rcomp ...): share [6 n_down + 4][max_classes][4] as (row
@@ -1168,105 +1214,104 @@ extern "C" int tmat_roi_plan_share_rect(int hh, int ww, int patch, int n_up, con
                                         unsigned fused_mask, int max_classes, int *n_classes, int *share, int *n_rects, int *rects,
                                         unsigned char *comp, int fill_cap, int *n_fill, int *fills, double *mac_rect, double *bytes_rect, int *info)
 {
-    if (!up_channels || !down_channels || !n_classes || !share || !n_rects || !rects || !comp || !n_fill || !fills || !mac_rect || !bytes_rect ||
-        !info || fill_cap < 0 || max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
-        set_error("tmat_roi_plan_share_rect: bad argument");
-        return TMAT_E_ARG;
-    }
     RoiPlan p;
-    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, max_classes, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
-        set_error("tmat_roi_plan_share_rect: unsupported geometry");
-        return TMAT_E_ARG;
-    }
+    const bool args_ok = n_classes && share && n_rects && rects && comp && n_fill && fills && mac_rect && bytes_rect && info && fill_cap >= 0;
+    if (int rc = down_plan_for("tmat_roi_plan_share_rect", args_ok, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, max_classes, p)) return rc;
     const RoiDownPlan &d = p.down;
+    const RoiDownPlan::RectForm &f = d.rcomp;
     *n_classes = p.n_classes;
     for (int l = 0; l < d.n_layers; l++) {
-        for (int k = 0; k < max_classes; k++) {
-            const bool in = k < p.n_classes;
-            const size_t at = (size_t)l * max_classes + k;
-            RoiRect q[4];
-            const int n = in ? roi_rect_comp(p, l, k, q) : 0;
-            n_rects[at] = n;
-            for (int i = 0; i < 4; i++) {
-                share[at * 4 + i] = in ? d.rshare[l][k][i] : 0;
-                int *o = rects + (at * 4 + i) * 4;
-                o[0] = i < n ? q[i].y0 : 0; o[1] = i < n ? q[i].x0 : 0; o[2] = i < n ? q[i].rh : 0; o[3] = i < n ? q[i].rw : 0;
-            }
-            unsigned char *o = comp + at * 2 * patch;
-            if (in && !d.rcomp_mask.empty()) std::copy_n(d.rcomp_mask.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * patch, 2 * patch, o);
-            else std::fill_n(o, 2 * patch, (unsigned char)0);
-        }
-        mac_rect[l] = d.rcomp_mask.empty() ? d.mac_live[l] : d.mac_rect[l];
-        bytes_rect[l] = d.rcomp_mask.empty() ? d.bytes_live[l] : d.bytes_rect[l];
+        put_form_rects(p, f.any ? &f : nullptr, l, max_classes, n_rects, rects);
+        put_masks(p, f.mask, l, max_classes, comp);
+        for (int k = 0; k < max_classes; k++)
+            for (int i = 0; i < 4; i++) share[((size_t)l * max_classes + k) * 4 + i] = k < p.n_classes ? d.rshare[l][k][i] : 0;
+        mac_rect[l] = f.mask.empty() ? d.mac_live[l] : f.mac[l];
+        bytes_rect[l] = f.mask.empty() ? d.bytes_live[l] : f.bytes[l];
     }
-    *n_fill = (int)d.rect_fill.size();
-    if (*n_fill > fill_cap) { set_error("tmat_roi_plan_share_rect: fill_cap too small"); return TMAT_E_ARG; }
-    for (int i = 0; i < *n_fill; i++) {
-        const RoiDownPlan::ShareFill &f = d.rect_fill[i];
-        int *o = fills + (size_t)i * 7;
-        o[0] = f.layer; o[1] = f.cls; o[2] = f.dir; o[3] = f.y0; o[4] = f.x0; o[5] = f.rh; o[6] = f.rw;
-    }
-    info[0] = d.rect_any ? 1 : 0;
-    info[1] = d.rect_any ? d.n_down - 1 : -1;
-    info[2] = d.rect_segs;
-    return TMAT_OK;
+    info[0] = f.any ? 1 : 0;
+    info[1] = f.any ? d.n_down - 1 : -1;
+    info[2] = f.segs;
+    return put_fill_list("tmat_roi_plan_share_rect", f.fill, fill_cap, n_fill, fills);
 }
 
 // The same for the fused levels' rectangle launches (RoiDownPlan::fcomp ...): n_rects [6 n_down + 4][max_classes], rects [6 n_down + 4]
-// [max_classes][4 rectangles][4] as (y0, x0, rows, columns) -- what roi_fused_rect_comp gives --, comp [6 n_down + 4][max_classes][2 axes]
-// [patch] bytes (the exact sets in force, before the columns are rounded), fills [n_fill][7] as (layer, class, direction, y0, x0, rows,
-// columns): the halo strips, fill_on [6 n_down + 4]: the strips stand in place of the layer's items of tmat_roi_plan_share, totals
-// [6 n_down + 4][6]: planned multiply-accumulates, planned bytes, planned pixels, pixels of rect_live, copied pixels without and with the
-// form (all per image), info: (some table differs from tmat_roi_plan_share_rect's, the mask of levels in force, the longest segment
-// table of a launch).
+// [max_classes][4 rectangles][4] as (y0, x0, rows, columns), comp [6 n_down + 4][max_classes][2 axes][patch] bytes (the exact sets in
+// force, before the columns are rounded), fills [n_fill][7] as (layer, class, direction, y0, x0, rows, columns): the halo strips, fill_on
+// [6 n_down + 4]: the strips stand in place of the layer's items of tmat_roi_plan_share, totals [6 n_down + 4][6]: planned
+// multiply-accumulates, planned bytes, planned pixels, pixels of rect_live, copied pixels without and with the form (all per image),
+// info: (some table differs from tmat_roi_plan_share_rect's, the mask of levels in force, the longest segment table of a launch).
 extern "C" int tmat_roi_plan_share_fused_rect(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
                                               unsigned fused_mask, int max_classes, int *n_classes, int *n_rects, int *rects, unsigned char *comp,
                                               int fill_cap, int *n_fill, int *fills, int *fill_on, double *totals, int *info)
 {
-    if (!up_channels || !down_channels || !n_classes || !n_rects || !rects || !comp || !n_fill || !fills || !fill_on || !totals || !info ||
-        fill_cap < 0 || max_classes < 1 || max_classes > ROI_MAX_CLASSES) {
-        set_error("tmat_roi_plan_share_fused_rect: bad argument");
-        return TMAT_E_ARG;
-    }
     RoiPlan p;
-    if (!roi_make_plan(hh, ww, patch, n_up, up_channels, max_classes, p) || !roi_plan_down(p, n_down, down_channels, fused_mask)) {
-        set_error("tmat_roi_plan_share_fused_rect: unsupported geometry");
-        return TMAT_E_ARG;
-    }
+    const bool args_ok = n_classes && n_rects && rects && comp && n_fill && fills && fill_on && totals && info && fill_cap >= 0;
+    if (int rc = down_plan_for("tmat_roi_plan_share_fused_rect", args_ok, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, max_classes, p))
+        return rc;
     const RoiDownPlan &d = p.down;
+    const RoiDownPlan::RectForm &f = d.fcomp;
     *n_classes = p.n_classes;
     unsigned levels = 0;
     for (int l = 0; l < d.n_layers; l++) {
-        for (int k = 0; k < max_classes; k++) {
-            const bool in = k < p.n_classes;
-            const size_t at = (size_t)l * max_classes + k;
-            RoiRect q[4];
-            const int n = in ? roi_fused_rect_comp(p, l, k, q) : 0;
-            n_rects[at] = n;
-            for (int i = 0; i < 4; i++) {
-                int *o = rects + (at * 4 + i) * 4;
-                o[0] = i < n ? q[i].y0 : 0; o[1] = i < n ? q[i].x0 : 0; o[2] = i < n ? q[i].rh : 0; o[3] = i < n ? q[i].rw : 0;
-            }
-            unsigned char *o = comp + at * 2 * patch;
-            if (in && !d.fcomp_mask.empty()) std::copy_n(d.fcomp_mask.data() + ((size_t)l * ROI_MAX_CLASSES + k) * 2 * patch, 2 * patch, o);
-            else std::fill_n(o, 2 * patch, (unsigned char)0);
-        }
+        put_form_rects(p, f.any ? &f : d.rcomp.any ? &d.rcomp : nullptr, l, max_classes, n_rects, rects);
+        put_masks(p, f.mask, l, max_classes, comp);
         fill_on[l] = d.fused_fill_on[l] ? 1 : 0;
         if (d.fused_fill_on[l]) levels |= 1u << (l / 6);
-        double *t = totals + (size_t)l * 6;
-        t[0] = d.fcomp_mask.empty() ? d.mac_live[l] : d.mac_frect[l];
-        t[1] = d.fcomp_mask.empty() ? d.bytes_live[l] : d.bytes_frect[l];
-        t[2] = d.px_frect[l]; t[3] = d.px_live[l]; t[4] = d.copy_old[l]; t[5] = d.copy_new[l];
+        const double t[6] = {f.mask.empty() ? d.mac_live[l] : f.mac[l], f.mask.empty() ? d.bytes_live[l] : f.bytes[l], f.px[l], d.px_live[l],
+                             d.copy_old[l], d.copy_new[l]};
+        std::copy(t, t + 6, totals + (size_t)l * 6);
     }
-    *n_fill = (int)d.fused_fill.size();
-    if (*n_fill > fill_cap) { set_error("tmat_roi_plan_share_fused_rect: fill_cap too small"); return TMAT_E_ARG; }
-    for (int i = 0; i < *n_fill; i++) {
-        const RoiDownPlan::ShareFill &f = d.fused_fill[i];
-        int *o = fills + (size_t)i * 7;
-        o[0] = f.layer; o[1] = f.cls; o[2] = f.dir; o[3] = f.y0; o[4] = f.x0; o[5] = f.rh; o[6] = f.rw;
-    }
-    info[0] = d.fused_rect_any ? 1 : 0;
+    info[0] = f.any ? 1 : 0;
     info[1] = (int)levels;
-    info[2] = d.fused_rect_any ? d.fused_rect_segs : d.rect_segs;
+    info[2] = f.segs;
+    return put_fill_list("tmat_roi_plan_share_fused_rect", f.fill, fill_cap, n_fill, fills);
+}
+
+// What a pass of k images launches under `form` (a RoiDownForm from ROI_DOWN_REGION upwards; roi_plan.h has the rule), as the planner
+// hands it to the launches.  info: (the form the plan runs -- the one asked for or the highest below it that the plan has --, the
+// layer whose table the stem at the even pixels launches, the longest segment table, all segment tables of the pass's rectangle
+// launches added up: stem at the even pixels where level 0 is fused, residual and fix-up of a fused level, all six layers of an unfused
+// one).  Per layer of the down plan: n_segs [6 n_down + 4] and segs [6 n_down + 4][64][6] as (p0, np, y0, x0, rows, columns) in launch
+// order, the constant patches' segment included.  const_fills [n_const][7] as (layer, p0, np, y0, x0, rows, columns): the strips out
+// of the constant patches.  copies [n_copy][8] as (layer, p0, np, direction, y0, x0, rows, columns): the neighbour items, in launch order.
+extern "C" int tmat_roi_down_schedule(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                      unsigned fused_mask, int form, int k, int *info, int *n_segs, int *segs, int const_cap, int *n_const,
+                                      int *const_fills, int copy_cap, int *n_copy, int *copies)
+{
+    RoiPlan p;
+    const bool args_ok = form >= ROI_DOWN_REGION && form <= ROI_DOWN_SHARE_FUSED_RECT && k >= 1 && info && n_segs && segs && n_const &&
+                         const_fills && n_copy && copies && const_cap >= 0 && copy_cap >= 0;
+    if (int rc = down_plan_for("tmat_roi_down_schedule", args_ok, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, ROI_MAX_CLASSES, p))
+        return rc;
+    const RoiDownPlan &d = p.down;
+    const RoiDownForm f = roi_down_form(p, (RoiDownForm)form);
+    *n_const = *n_copy = 0;
+    for (int l = 0; l < d.n_layers; l++) {
+        RoiSegs sg;
+        FillItems fi;
+        std::vector<ShareItem> sh;
+        roi_down_segs(p, f, l, k, sg);
+        roi_down_const_items(p, f, l, k, fi);
+        roi_down_copy_items(p, f, l, k, sh);
+        n_segs[l] = sg.nseg;
+        for (int i = 0; i < sg.nseg; i++) {
+            const int o[6] = {sg.s[i].p0, sg.s[i].np, sg.s[i].y0, sg.s[i].x0, sg.s[i].rh, sg.s[i].rw};
+            std::copy(o, o + 6, segs + ((size_t)l * ROI_MAX_SEGS + i) * 6);
+        }
+        if (*n_const + fi.n > const_cap || *n_copy + (int)sh.size() > copy_cap) { set_error("tmat_roi_down_schedule: cap too small"); return TMAT_E_ARG; }
+        for (int i = 0; i < fi.n; i++, ++*n_const) {
+            const int o[7] = {l, fi.it[i].p0, fi.it[i].np, fi.it[i].y0, fi.it[i].x0, fi.it[i].rh, fi.it[i].rw};
+            std::copy(o, o + 7, const_fills + (size_t)*n_const * 7);
+        }
+        for (const ShareItem &c : sh) {
+            const int o[8] = {l, c.p0, c.np, c.dir, c.y0, c.x0, c.rh, c.rw};
+            std::copy(o, o + 8, copies + (size_t)(*n_copy)++ * 8);
+        }
+    }
+    info[0] = f; info[1] = roi_down_stem_layer(p, f); info[2] = info[3] = 0;
+    auto launch = [&](int l) { info[2] = std::max(info[2], n_segs[l]); info[3] += n_segs[l]; };
+    if (d.fused_mask & 1u) launch(info[1]);
+    for (int b = 0; b < d.n_down; b++)
+        for (int kk = ((d.fused_mask >> b) & 1u) ? 4 : 0; kk < 6; kk++) launch(6 * b + kk);
     return TMAT_OK;
 }

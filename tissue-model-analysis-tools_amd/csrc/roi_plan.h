@@ -20,6 +20,9 @@ constexpr int ROI_MAX_DOWN = 4;
 constexpr int ROI_MAX_DOWN_LAYERS = 6 * ROI_MAX_DOWN + 4;
 
 struct RoiRect { int y0, x0, rh, rw; };
+struct RoiSegs;
+struct FillItems;
+struct ShareItem;
 
 // Layers of the up plan (bit l: layer l) whose EXACT rectangle is their tight one: none.  (The place for a layer that a per-launch trace
 // shows slower with unrounded columns than with rounded ones; DESIGN 4.1.1 has the trace.)
@@ -37,6 +40,7 @@ constexpr unsigned ROI_EXACT_KEEP_TIGHT = 0u;
 // rule of conv_mfma_kernel<..., ROI> for the pointwise and residual layers and the depthwise strips in front of them, single pixels for
 // the pooling.  A pixel of rect outside need may be computed from operands nobody wrote; nothing needed depends on it.
 struct RoiDownPlan {
+    struct ShareFill { int layer, cls, dir, y0, x0, rh, rw; };     // a copy out of a neighbour patch: see share_fill
     int n_down = 0, n_layers = 0;               // 6 n_down + 4; 0: no down plan
     unsigned fused_mask = 0;
     int res[ROI_MAX_DOWN_LAYERS] = {};
@@ -76,14 +80,13 @@ struct RoiDownPlan {
     // pooled output (6 b + 5).
     // comp ([layer][class][axis][ws] bytes, the first res[layer] used): the NEEDED pixels the patch computes itself -- live \ share for
     // the pooled output, and backwards from there through the taps for the fused layers; live everywhere else (rectangle launches keep
-    // rect_live).  The fused layers run the tiles that hold a comp pixel (roi_sep_tile_table_share: tile_rows x tile_cols, bit t).
+    // rect_live).  The fused layers run the tiles that hold a comp pixel (roi_sep_tile_table: tile_rows x tile_cols, bit t).
     // share_fill: the pixels in share that a consumer's comp taps -- of 6 b + 1 the halo strips of the pooled layer's tiles, except
     // where they lie in a tile of 6 b + 1 that runs anyway (they join comp: the block's input is held whole; at the network's sizes
     // that is all of them), of 6 b + 5 all of share (the next level's rectangle launches read the tensor whole) -- as rectangles
     // with a direction: copied from the
     // right (0), lower (1) or diagonal (2) neighbour at (y, x - S), (y - S, x), (y - S, x - S).  Every source pixel is in its own
     // patch's comp.  Every tap of a comp pixel lies in the producer's comp ∪ fill ∪ share_fill.
-    struct ShareFill { int layer, cls, dir, y0, x0, rh, rw; };
     bool share_any = false;                     // some class shares: the form differs from the constant-ring form
     RoiRect inner[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {};
     int share[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES][4] = {};
@@ -92,55 +95,73 @@ struct RoiDownPlan {
     std::vector<ShareFill> share_fill;
     std::vector<int> nbr;                       // [tiles_per_img][3]: the image-major tile right of, below and diagonally below a tile, or -1
 
-    // The shared-interior form of the RECTANGLE launches (TMAT_ROI_SHARE_RECT), on top of the above: the last level, where it is unfused
-    // and in ROI_SHARE_RECT_LEVELS (layers 6 b + 0 .. 6 b + 5, b = n_down - 1: the 40² level of the network).  Built like share / comp,
-    // per axis and axis key, in fields of their own: everything above keeps its values.
+    // The shared-interior form of RECTANGLE launches comes twice, one on top of the other, and both times as one RectForm, built like
+    // share / comp, per axis and axis key, in fields of its own: everything above keeps its values.
+    //   mask (layout of comp): the exact sets in force under the form, every layer.
+    //   rects[l][k][0 .. n[l][k]): the rectangles layer l launches for class k under the form: at most four, disjoint, inside rect_live,
+    //   and they hold the exact set.  Rows exact; columns as the form says.  A rectangle that rounding or whole tiles add on top of an
+    //   exact set may read words nobody wrote: the contract of rect.
+    //   fill: the copies out of the neighbour patches that the form adds, same directions and same source rule as share_fill.
+    //   any false: the plan has no such form -- every field but mask is then the copy of the form below (of rect_live for rcomp).
+    struct RectForm {
+        bool any = false;                       // some class's rectangles or some copy list differ from the form below
+        int n[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {};
+        RoiRect rects[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES][4] = {};
+        std::vector<unsigned char> mask;
+        std::vector<ShareFill> fill;
+        // mac_planned / bytes_planned of rects, and their pixels per image
+        double mac[ROI_MAX_DOWN_LAYERS] = {}, bytes[ROI_MAX_DOWN_LAYERS] = {}, px[ROI_MAX_DOWN_LAYERS] = {};
+        int segs = 0;                           // the longest segment table a launch of the form needs (without the constant patches' segment)
+    };
+    // rcomp, ROI_DOWN_SHARE_RECT (TMAT_ROI_SHARE_RECT), on top of the shared-interior form: the last level, where it is unfused and in
+    // ROI_SHARE_RECT_LEVELS (layers 6 b + 0 .. 6 b + 5, b = n_down - 1: the 40² level of the network).
     // rshare (row lo, row hi, column lo, column hi): the zone of the bottleneck tensor 6 b + 5, same rule as share.  It is the only
     // tensor of the level that is copied: all of rshare (it lies in live, which is what up block 0 reads), into the tensor and into
-    // its activated copy -- rect_fill, same directions as share_fill.
-    // rcomp_mask (layout of comp): live \ rshare for 6 b + 5, and backwards from there through the taps, inside live, for 6 b + 4 .. 6 b:
+    // its activated copy -- rcomp.fill.
+    // rcomp.mask: live \ rshare for 6 b + 5, and backwards from there through the taps, inside live, for 6 b + 4 .. 6 b:
     // the halo of a consumer's comp (1 pixel per side under a depthwise layer, 2 i .. 2 i + 2 under the pooling) JOINS comp, so no
     // intermediate tensor needs a copy (DESIGN 4.1.5 has the pixels against the bytes).  Per axis comp is live minus one interval: at
-    // most two runs, and a class's 2-D set at most four disjoint rectangles.
-    // rcomp[l][k][0 .. rcomp_n[l][k]): those rectangles as launched, rows exact, the columns of layers 6 b + 0 .. 6 b + 4 rounded
-    // outwards to multiples of 4 inside rect_live (a rounded rectangle may reach into the shared gap: a superset only costs time; two
-    // runs that meet after rounding are one).  Every other layer, and every class that shares nothing: rect_live itself.
-    bool rect_any = false;                      // some class's rectangles differ from rect_live
+    // most two runs, and a class's 2-D set at most four disjoint rectangles.  Every other layer: live.
+    // rcomp.rects: the columns of layers 6 b + 0 .. 6 b + 4 rounded outwards to multiples of 4 inside rect_live (a rounded rectangle may
+    // reach into the shared gap: a superset only costs time; two runs that meet after rounding are one).  Every other layer, and every
+    // class that shares nothing: rect_live itself.
     int rshare[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES][4] = {};
-    int rcomp_n[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {};
-    RoiRect rcomp[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES][4] = {};
-    std::vector<unsigned char> rcomp_mask;
-    std::vector<ShareFill> rect_fill;
-    double mac_rect[ROI_MAX_DOWN_LAYERS] = {}, bytes_rect[ROI_MAX_DOWN_LAYERS] = {};       // mac_planned / bytes_planned of rcomp
-    int rect_segs = 0;                          // the longest segment table a launch of the form needs (without the constant patches' segment)
-
-    // The shared-interior form of the FUSED levels' rectangle launches (TMAT_ROI_SHARE_FUSED_RECT), on top of both forms above: the
-    // stride-2 residual 1x1 (6 b + 4) and the pooling fix-up (6 b + 5) of a fused level b in ROI_SHARE_FUSED_RECT_LEVELS, and the stem at
-    // the even pixels (6 n_down) with level 0.  Fields of their own again: everything above keeps its values.  The form exists only
-    // where rect_any holds: while the unfused level reads the pooled outputs whole, their whole zone has to be copied.
-    // fcomp_mask (layout of comp): the exact sets in force under this form, every layer -- comp of the pooled output 6 b + 5 (live \ share)
-    // as it is; the residual 6 b + 4 that set cut by its own live; the stem at the even pixels block 0's residual set cut by its own
-    // live; rcomp_mask for the unfused last level; comp for every other layer.  A class takes the form in all rectangle launches of a
-    // level or in none (its keys share at the level and every set lies inside its rect_live).
-    // fcomp[l][k][0 .. fcomp_n[l][k]): the rectangles as launched (what roi_rect_comp gives for every layer outside the form): rows
-    // exact, the columns of the residual and stem layers rounded outwards to multiples of 4 inside rect_live (two runs that meet after
-    // rounding are one), the pooled layer in single pixels.  At most four, disjoint, inside rect_live, and they hold the exact set.
-    // fused_fill: the copies of a pooled output 6 b + 5 as HALO STRIPS, in place of its items in share_fill (fused_fill_on[6 b + 5]):
-    // only the shared pixels that a consumer's exact set taps in the next level -- the depthwise taps of fcomp_mask[6 (b + 1)], the even
-    // pixels under fcomp_mask[6 (b + 1) + 4] -- per axis, the 2-D list being the product (a superset of both consumers' products).
-    // Same directions and same source rule as share_fill.  A rectangle that rounding or whole tiles add on top of an exact set may read
-    // words nobody wrote: the contract of rect.
-    bool fused_rect_any = false;                // some class's rectangles or some copy list differ from the form above
+    RectForm rcomp;
+    // fcomp, ROI_DOWN_SHARE_FUSED_RECT (TMAT_ROI_SHARE_FUSED_RECT), on top of both forms above: the rectangle launches of the FUSED
+    // levels -- the stride-2 residual 1x1 (6 b + 4) and the pooling fix-up (6 b + 5) of a fused level b in ROI_SHARE_FUSED_RECT_LEVELS,
+    // and the stem at the even pixels (6 n_down) with level 0.  The form exists only where rcomp.any holds: while the unfused level
+    // reads the pooled outputs whole, their whole zone has to be copied.
+    // fcomp.mask: comp of the pooled output 6 b + 5 (live \ share) as it is; the residual 6 b + 4 that set cut by its own live; the stem
+    // at the even pixels block 0's residual set cut by its own live; rcomp.mask for the unfused last level; comp for every other layer.
+    // A class takes the form in all rectangle launches of a level or in none (its keys share at the level and every set lies inside
+    // its rect_live).
+    // fcomp.rects (rcomp.rects for every layer outside the form): the columns of the residual and stem layers rounded outwards to
+    // multiples of 4 inside rect_live (two runs that meet after rounding are one), the pooled layer in single pixels.
+    // fcomp.fill: the copies of a pooled output 6 b + 5 as HALO STRIPS, in place of its items in share_fill (fused_fill_on[6 b + 5]):
+    // only the shared pixels that a consumer's exact set taps in the next level -- the depthwise taps of fcomp.mask[6 (b + 1)], the even
+    // pixels under fcomp.mask[6 (b + 1) + 4] -- per axis, the 2-D list being the product (a superset of both consumers' products).
+    // A table that does not fit a launch's segments keeps the form below.
     bool fused_fill_on[ROI_MAX_DOWN_LAYERS] = {};
-    int fcomp_n[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES] = {};
-    RoiRect fcomp[ROI_MAX_DOWN_LAYERS][ROI_MAX_CLASSES][4] = {};
-    std::vector<unsigned char> fcomp_mask;
-    std::vector<ShareFill> fused_fill;
-    double mac_frect[ROI_MAX_DOWN_LAYERS] = {}, bytes_frect[ROI_MAX_DOWN_LAYERS] = {};     // mac_planned / bytes_planned of fcomp
-    double px_frect[ROI_MAX_DOWN_LAYERS] = {}, px_live[ROI_MAX_DOWN_LAYERS] = {};          // pixels per image of fcomp, of rect_live
-    double copy_old[ROI_MAX_DOWN_LAYERS] = {}, copy_new[ROI_MAX_DOWN_LAYERS] = {};         // pixels per image copied into the tensor: share_fill, this form
-    int fused_rect_segs = 0;                    // the longest segment table a launch of the form needs (without the constant patches' segment)
+    RectForm fcomp;
+    double px_live[ROI_MAX_DOWN_LAYERS] = {};                                              // pixels per image of rect_live
+    double copy_old[ROI_MAX_DOWN_LAYERS] = {}, copy_new[ROI_MAX_DOWN_LAYERS] = {};         // pixels per image copied into the tensor: share_fill, under fcomp
 };
+
+// The forms of the down path, each on top of the one before it.  A pass runs ONE of them (tmat_api.cpp:roi_down_resolve), and what a
+// layer launches under a form is answered here, by roi_down_segs (roi_down_rects, roi_down_stem_layer), roi_sep_tile_table,
+// roi_down_const_items and roi_down_copy_items -- for the launches and for tmat_roi_down_schedule alike.
+//   ROI_DOWN_FULL              whole patches everywhere: no segment table, no tile table, no copy
+//   ROI_DOWN_REGION            rect; the fused separable layers the tiles of rect
+//   ROI_DOWN_CONST             rect_live, the tiles of rect_live; every stored tensor takes the strips of `fill` from the constant patches
+//   ROI_DOWN_SHARE             the tiles of tile_rows x tile_cols; the stored tensors of the fused levels take share_fill after `fill`
+//   ROI_DOWN_SHARE_RECT        rcomp.rects; the bottleneck tensor (and its activated copy) takes rcomp.fill
+//   ROI_DOWN_SHARE_FUSED_RECT  fcomp.rects, the stem at the even pixels its own layer's; a pooled output in fused_fill_on takes its items
+//                              of fcomp.fill in place of its items of share_fill
+// The copies of a stored tensor, after the launch that writes it and before its first reader, in this order: the constant strips from
+// ROI_DOWN_CONST upwards; then the neighbour items -- the layer's items of share_fill, or of fcomp.fill in their place where
+// fused_fill_on[layer], and the layer's items of rcomp.fill (share_fill has items on fused levels only, rcomp.fill on the unfused last
+// level only: a layer has items in one of them at most).
+enum RoiDownForm { ROI_DOWN_FULL, ROI_DOWN_REGION, ROI_DOWN_CONST, ROI_DOWN_SHARE, ROI_DOWN_SHARE_RECT, ROI_DOWN_SHARE_FUSED_RECT };
 
 // Fused levels (bit b) that take the shared-interior form: a level whose copies cost more than its skipped tiles save is taken out here
 constexpr unsigned ROI_SHARE_LEVELS = 3u;
@@ -197,25 +218,40 @@ bool roi_make_plan(int hh, int ww, int ws, int n_up, const int *chan, int max_cl
 // tile-granular fused separable kernel (bit 0 then also means: the stem is recomputed inside the first separable layer).  Needs a plan
 // with classes; false (p.down left empty) otherwise or on a geometry the down path's kernels do not take.
 bool roi_plan_down(RoiPlan &p, int n_down, const int *chan, unsigned fused_mask);
+// Fills the shared-interior tables of a plan with a down plan (called by roi_plan_down; p.down.share_any stays false where nothing is shared)
+void roi_plan_share(RoiPlan &p);
+
+// ---- what a pass launches under a form (the table at RoiDownForm) ----
+// The form the plan runs where `want` is asked for: the highest form not above `want` that the plan has, and every form below it with
+// it -- ROI_DOWN_FULL without a down plan, no sharing form where no class shares (share_any), neither rectangle form where its `any`
+// is false or its longest table, with the constant patches' segment, does not fit a launch (ROI_MAX_SEGS).  Every accessor below
+// resolves its form through this, so each falls back to the form below exactly where the plan has nothing of its own.
+RoiDownForm roi_down_form(const RoiPlan &p, RoiDownForm want);
+// The rectangles layer l launches for class k: rect under ROI_DOWN_REGION, rect_live under ROI_DOWN_CONST and ROI_DOWN_SHARE, rcomp's
+// under ROI_DOWN_SHARE_RECT, fcomp's under ROI_DOWN_SHARE_FUSED_RECT -- at most four, disjoint, the empty ones left out.  Returns
+// their count (0 under ROI_DOWN_FULL: the launch has no segment table).
+int roi_down_rects(const RoiPlan &p, RoiDownForm form, int l, int k, RoiRect out[4]);
+// The layer whose rectangles the stem at the even pixels launches: its own (6 n_down) under ROI_DOWN_SHARE_FUSED_RECT, block 0's
+// residual 1x1 (4) otherwise -- below that form the two layers have the same rectangles
+int roi_down_stem_layer(const RoiPlan &p, RoiDownForm form);
 // The tiles a fused separable layer of the down plan visits in a pass of k images (layer = 6 b + 1 or 6 b + 3 of a level in fused_mask):
 // full-frame tile ids  patch * TPP + ty * TW + tx  (TW = res / 16 tiles per row, TPP = TW * TW per patch), the patches in the pass's
 // class-major order (class c holds the patches k class_base[c] .. k class_base[c + 1] - 1), row-major inside the class's rectangle of
-// whole tiles.  The table depends on k: a shorter last pass has its own.  Returns the full-frame tile count k tiles_per_img TPP, 0 when
-// the layer has no tile rectangles; out.size() == that count means every patch is computed whole.
-long long roi_sep_tile_table(const RoiPlan &p, int layer, int k, std::vector<int> &out);
-// the same of the constant-ring form: the tiles of RoiDownPlan::rect_live, a subsequence of the table above
-long long roi_sep_tile_table_live(const RoiPlan &p, int layer, int k, std::vector<int> &out);
-// the same of the shared-interior form: the tiles of RoiDownPlan::tile_rows x tile_cols, a subsequence of the live table in its order
-// (the live table itself where no class shares)
-long long roi_sep_tile_table_share(const RoiPlan &p, int layer, int k, std::vector<int> &out);
-// Fills the shared-interior tables of a plan with a down plan (called by roi_plan_down; p.down.share_any stays false where nothing is shared)
-void roi_plan_share(RoiPlan &p);
-// The rectangles layer l launches for class k in the rectangle launches' shared-interior form (RoiDownPlan::rcomp; rect_live where the
-// plan has no such form): at most four, disjoint, inside rect_live.  Returns their count.
-int roi_rect_comp(const RoiPlan &p, int l, int k, RoiRect *out);
-// The same with the fused levels' rectangle launches in their shared-interior form (RoiDownPlan::fcomp; what roi_rect_comp gives where
-// the plan has no such form)
-int roi_fused_rect_comp(const RoiPlan &p, int l, int k, RoiRect *out);
+// whole tiles.  The table depends on k: a shorter last pass has its own.  Under ROI_DOWN_REGION the tiles of rect; under
+// ROI_DOWN_CONST those of rect_live, a subsequence of that table; from ROI_DOWN_SHARE upwards those of tile_rows x tile_cols inside
+// rect_live, a subsequence of the live table in its order.  Returns the full-frame tile count k tiles_per_img TPP, 0 when the layer has
+// no tile rectangles (or under ROI_DOWN_FULL); out.size() == that count means every patch is computed whole.
+long long roi_sep_tile_table(const RoiPlan &p, RoiDownForm form, int layer, int k, std::vector<int> &out);
+// The launch arguments of layer l in a pass of k images (tmat_internal.h has the structs), in the pass's class-major patch order: class
+// c holds the patches k class_base[c] .. k class_base[c + 1] - 1, classes without patches are left out, and the k all-constant
+// patches of ROI_DOWN_CONST and above sit behind them, at k tiles_per_img.
+// roi_down_segs: the segment table -- per class the rectangles of roi_down_rects, then, from ROI_DOWN_CONST upwards, one segment of whole
+// patches for the constant patches (p0 .. rw filled; no segment under ROI_DOWN_FULL: the launch is full-frame).
+// roi_down_const_items: the strips of RoiDownPlan::fill the layer's tensor takes from the constant patches; none below ROI_DOWN_CONST.
+// roi_down_copy_items: the neighbour items it takes after them, by the rule at RoiDownForm; none below ROI_DOWN_SHARE.
+void roi_down_segs(const RoiPlan &p, RoiDownForm form, int l, int k, RoiSegs &out);
+void roi_down_const_items(const RoiPlan &p, RoiDownForm form, int l, int k, FillItems &out);
+void roi_down_copy_items(const RoiPlan &p, RoiDownForm form, int l, int k, std::vector<ShareItem> &out);
 // nbr in the class-major order of a pass of k images: [k tiles_per_img][3] positions, or -1
 void roi_share_neighbours(const RoiPlan &p, int k, std::vector<int> &out);
 

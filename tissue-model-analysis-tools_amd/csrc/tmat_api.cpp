@@ -302,22 +302,22 @@ static bool conv(Ctx *c, ConvArgs a, hipStream_t st, const RoiSegs *roi = nullpt
     return ok;
 }
 
-// The tile table of fused separable layer `layer` for passes of k images, cached on the plan's entry: built and uploaded on first use (a
-// blocking copy into a fresh allocation, as for the patch order), never per pass.  dev stays null when every patch is computed whole.
-// Null + error set: the allocation or the copy failed.
-// live: the constant-ring form's table, then every tile of the k all-constant patches behind the pass's patches.
-// share (with live): the shared-interior form's table
-static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, bool live, bool share = false)
+// The tile table of fused separable layer `layer` for passes of k images under a form, cached on the plan's entry: built and uploaded on
+// first use (a blocking copy into a fresh allocation, as for the patch order), never per pass.  dev stays null when every patch is
+// computed whole.  Null + error set: the allocation or the copy failed.
+// From ROI_DOWN_CONST upwards every tile of the k all-constant patches behind the pass's patches follows; the forms above
+// ROI_DOWN_SHARE keep its table.
+static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, RoiDownForm form)
 {
-    share = share && live;
-    for (const RoiTileTab &t : e->tabs) if (t.layer == layer && t.k == k && t.live == live && t.share == share) return &t;
+    form = roi_down_form(e->plan, std::min(form, ROI_DOWN_SHARE));
+    for (const RoiTileTab &t : e->tabs) if (t.layer == layer && t.k == k && t.form == form) return &t;
     std::vector<int> ids;
     RoiTileTab t;
-    t.layer = layer; t.k = k; t.live = live; t.share = share;
-    t.full = share ? roi_sep_tile_table_share(e->plan, layer, k, ids) : live ? roi_sep_tile_table_live(e->plan, layer, k, ids) : roi_sep_tile_table(e->plan, layer, k, ids);
+    t.layer = layer; t.k = k; t.form = form;
+    t.full = roi_sep_tile_table(e->plan, form, layer, k, ids);
     t.n_rep = (long long)ids.size(); t.full_rep = t.full;
     if (t.full <= 0 || ids.empty()) { set_error("roi_tile_tab: no tile table for this layer"); return nullptr; }
-    if (live) {
+    if (form >= ROI_DOWN_CONST) {
         const int TW = e->plan.down.res[layer] / 16, TPP = TW * TW;
         if (t.full + (long long)k * TPP > 0x7fffffffLL) { set_error("roi_tile_tab: too many tiles"); return nullptr; }
         for (int id = (int)t.full; id < (int)t.full + k * TPP; id++) ids.push_back(id);
@@ -332,37 +332,21 @@ static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, bool live, 
     return &e->tabs.back();
 }
 
-// The copies of the shared-interior form for passes of k images, cached on the plan's entry like the tile tables: the neighbour table and
-// every stored tensor's items, built and uploaded on first use, never per pass.  Null + error set: an allocation or a copy failed.
-// rect: the handle may run the rectangle launches' form (TMAT_ROI_SHARE_RECT is not 0: one value per handle, so per entry) -- its item
-// tables are made too; with the switch at 0 the handle holds what the parent form holds
-// fused: likewise for the fused levels' rectangle launches (TMAT_ROI_SHARE_FUSED_RECT is not 0) -- the halo strips of the pooled outputs
-static const RoiShareTab *roi_share_tab(RoiEntry *e, int k, bool rect, bool fused)
+// The neighbour copies of passes of k images under a form (ROI_DOWN_SHARE or above), cached on the plan's entry like the tile tables:
+// the neighbour table and, per stored tensor, the items the form copies (roi_plan.h:roi_down_copy_items), built and uploaded on first
+// use, never per pass.  Null + error set: an allocation or a copy failed.
+static const RoiShareTab *roi_share_tab(RoiEntry *e, int k, RoiDownForm form)
 {
-    for (const RoiShareTab &t : e->shares) if (t.k == k) return &t;
+    for (const RoiShareTab &t : e->shares) if (t.k == k && t.form == form) return &t;
     const RoiPlan &p = e->plan;
     RoiShareTab t;
-    t.k = k;
+    t.k = k; t.form = form;
     roi_share_neighbours(p, k, t.nbr);
-    for (const RoiDownPlan::ShareFill &f : p.down.share_fill) {
-        RoiShareTab::Layer *sl = nullptr;
-        for (RoiShareTab::Layer &l : t.layers) if (l.layer == f.layer) sl = &l;
-        if (!sl) { t.layers.emplace_back(); sl = &t.layers.back(); sl->layer = f.layer; }
-        sl->items.push_back(ShareItem{k * p.class_base[f.cls], k * p.class_count[f.cls], f.dir, f.y0, f.x0, f.rh, f.rw});
-    }
-    // the rectangle launches' form (RoiDownPlan::rect_fill): tables of its own, used only where that form runs
-    for (const RoiDownPlan::ShareFill &f : rect ? p.down.rect_fill : std::vector<RoiDownPlan::ShareFill>()) {
-        RoiShareTab::Layer *sl = nullptr;
-        for (RoiShareTab::Layer &l : t.layers) if (l.layer == f.layer && l.rect) sl = &l;
-        if (!sl) { t.layers.emplace_back(); sl = &t.layers.back(); sl->layer = f.layer; sl->rect = true; }
-        sl->items.push_back(ShareItem{k * p.class_base[f.cls], k * p.class_count[f.cls], f.dir, f.y0, f.x0, f.rh, f.rw});
-    }
-    // the halo strips (RoiDownPlan::fused_fill): used in place of the layer's whole-zone items where that form runs
-    for (const RoiDownPlan::ShareFill &f : (rect && fused) ? p.down.fused_fill : std::vector<RoiDownPlan::ShareFill>()) {
-        RoiShareTab::Layer *sl = nullptr;
-        for (RoiShareTab::Layer &l : t.layers) if (l.layer == f.layer && l.fused) sl = &l;
-        if (!sl) { t.layers.emplace_back(); sl = &t.layers.back(); sl->layer = f.layer; sl->fused = true; }
-        sl->items.push_back(ShareItem{k * p.class_base[f.cls], k * p.class_count[f.cls], f.dir, f.y0, f.x0, f.rh, f.rw});
+    for (int l = 0; l < p.down.n_layers; l++) {
+        RoiShareTab::Layer sl;
+        sl.layer = l;
+        roi_down_copy_items(p, form, l, k, sl.items);
+        if (!sl.items.empty()) t.layers.push_back(sl);
     }
     auto up = [](const void *src, size_t bytes, void **dev) {
         return bytes == 0 || (hip_ok(hipMalloc(dev, bytes), "hipMalloc(share table)") &&
@@ -388,9 +372,11 @@ static bool down_block_ws(const Ctx *c, size_t bi)
            ((d.cout / 4) & (d.cout / 4 - 1)) == 0;
 }
 
-// the segments of a layer for a pass of k images: one per class with a non-empty rectangle, in the class-major patch order
-static RoiSegs roi_segs_of(const RoiPlan &p, const RoiRect *rects, int k)
+// the segments of a layer of the up path for a pass of k images: one per class with a non-empty rectangle, in the class-major patch
+// order (of the set of up-path rectangles the handle launches: RoiPlan::up_rects)
+static RoiSegs roi_segs(const RoiPlan &p, int l, int k)
 {
+    const RoiRect *rects = p.up_rects(l);
     RoiSegs r{};
     for (int cl = 0; cl < p.n_classes; cl++) {
         const RoiRect &q = rects[cl];
@@ -401,103 +387,80 @@ static RoiSegs roi_segs_of(const RoiPlan &p, const RoiRect *rects, int k)
     }
     return r;
 }
-// (of the set of up-path rectangles the handle launches: RoiPlan::up_rects)
-static RoiSegs roi_segs(const RoiPlan &p, int l, int k) { return roi_segs_of(p, p.up_rects(l), k); }
+
+static RoiEntry *roi_entry_of(const Ctx *c, const RoiPlan *plan)
+{
+    for (RoiEntry *e : c->roi_cache) if (&e->plan == plan) return e;
+    return nullptr;
+}
+
+RoiDownForm roi_down_resolve(const Ctx *c, const RoiPlan *plan, int kimg, bool have_padval, bool by_default)
+{
+    if (!plan || plan->n_classes <= 0 || plan->down.n_down != (int)c->down.size() || kimg < 1) return ROI_DOWN_FULL;
+    auto on = [&](int sw) { return by_default ? sw != 0 : sw == 1; };
+    RoiDownForm want = ROI_DOWN_REGION;
+    // the constant-ring form: f32 path, some region form of the down path on, room for the constant patches and for their segment
+    if (on(c->roi_const) && have_padval && c->roi_down && c->precision == TMAT_PRECISION_F32 && kimg <= c->const_cap &&
+        plan->n_classes < ROI_MAX_CLASSES) want = ROI_DOWN_CONST;
+    // the shared-interior form: with the constant-ring form and the tile tables (TMAT_ROI_DOWN bit 1) only
+    if (want == ROI_DOWN_CONST && on(c->roi_share) && (c->roi_down & 2u) && roi_entry_of(c, plan)) want = ROI_DOWN_SHARE;
+    // the rectangle launches' forms: where the shared-interior form runs and the rectangle launches are on (TMAT_ROI_DOWN bit 0)
+    if (want == ROI_DOWN_SHARE && on(c->roi_share_rect) && (c->roi_down & 1u)) want = ROI_DOWN_SHARE_RECT;
+    if (want == ROI_DOWN_SHARE_RECT && on(c->roi_share_fused_rect)) want = ROI_DOWN_SHARE_FUSED_RECT;
+    // ... and where the plan shares anything, has the form and its longest table fits
+    return roi_down_form(*plan, want);
+}
 
 // Down path (memory-bound kernels + small pointwise GEMMs): X (n, P, P) -> dout (n, P/16, P/16, f_deep)
-// plan (tiled callers; null: whole patches): with a down plan (roi_plan.h:RoiDownPlan) the kernels named by c->roi_down compute only what
-// the region-form up path reads of dout, grown backwards; the patches are then in the plan's class-major order
-// padval (nullable): the constant-ring form (tmat_ctx.h:Ctx::roi_const) -- the k all-constant patches of the pass are written behind X's
-// n patches and run through the same launches as one more segment of whole patches; the launches of the pass's own patches take
-// rect_live, and after each launch that writes a stored tensor the strips of RoiDownPlan::fill are copied out of the constant patches
-// share: the shared-interior form on top of it (tmat_ctx.h:Ctx::roi_share) -- the fused separable layers take the share tile table, and
-// each constant fill of a stored tensor of a fused level is followed by the copies out of the neighbour patches (RoiDownPlan::share_fill)
-// share_rect (with share): the rectangle launches of the unfused last level take the form too (RoiDownPlan::rcomp) -- several disjoint
-// rectangles per class in their segment tables, and the bottleneck tensor and its activated copy take their shared zone from the neighbours
-// share_fused_rect (with share_rect): the rectangle launches of the fused levels take the form as well (RoiDownPlan::fcomp) -- the stem at
-// the even pixels, the stride-2 residual convolutions and the pooling fix-ups; the pooled outputs take halo strips, not their whole zone
-int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval, bool share, bool share_rect,
-                  bool share_fused_rect)
+// plan, form (tiled callers; ROI_DOWN_FULL: whole patches): the form roi_down_resolve gave for the pass; the patches are in the plan's
+// class-major order, and what every launch computes and every stored tensor is copied into is the planner's answer for the form
+// (roi_plan.h:RoiDownForm).  The two bits of TMAT_ROI_DOWN stay independent under every form: bit 0 gates the segment tables of the
+// rectangle launches, bit 1 the tile tables of the fused separable layers.
+// padval: from ROI_DOWN_CONST upwards the k all-constant patches of the pass are written behind X's n patches and run through the same
+// launches as one more segment of whole patches
+int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval, RoiDownForm form)
 {
     if (n <= 0) return TMAT_OK;
     if (n > c->max_patches) { set_error("unet_down_dev: n > max_patches"); return TMAT_E_ARG; }
-    const bool roi_any = plan && plan->n_classes > 0 && plan->down.n_down == (int)c->down.size() && n % plan->tiles_per_img == 0;
-    const bool roi_b = roi_any && (c->roi_down & 1u);
-    const int kimg = roi_any ? n / plan->tiles_per_img : 0;
-    // the constant-ring form: f32 path, some region form of the down path on, room for the constant patches and for their segment
-    const bool cst = roi_any && padval && c->roi_down && c->precision == TMAT_PRECISION_F32 && kimg <= c->const_cap &&
-                     plan->n_classes < ROI_MAX_CLASSES;
+    if (!plan || n % plan->tiles_per_img != 0) form = ROI_DOWN_FULL;
+    if (form >= ROI_DOWN_CONST && !padval) { set_error("unet_down_dev: the constant-ring form needs the pad values"); return TMAT_E_ARG; }
+    const bool roi_b = form != ROI_DOWN_FULL && (c->roi_down & 1u);
+    const int kimg = form != ROI_DOWN_FULL ? n / plan->tiles_per_img : 0;
     const int n_own = n;
-    if (cst) {
+    if (form >= ROI_DOWN_CONST) {
         launch_const_patches(padval, kimg, c->patch * c->patch, const_cast<float *>(X) + (size_t)n * c->patch * c->patch, s);
         n += kimg;              // every launch below runs the constant patches too
     }
+    c->sep_tiles.clear();
+    c->down_segs = c->down_seg_total = 0;
     RoiSegs sg{};
-    bool rect_form = false, fused_form = false;         // set below, once the share tables are there
     // the segments of layer l of the down plan (null: full-frame)
     auto segs_of = [&](int l) -> const RoiSegs * {
         if (!roi_b) return nullptr;
-        if (rect_form) {            // up to four rectangles per class, the classes in patch order (the table fits: checked where rect_form is set)
-            sg = RoiSegs{};
-            for (int cl = 0; cl < plan->n_classes; cl++) {
-                RoiRect q[4];
-                const int nq = plan->class_count[cl] <= 0 ? 0 : fused_form ? roi_fused_rect_comp(*plan, l, cl, q) : roi_rect_comp(*plan, l, cl, q);
-                for (int i = 0; i < nq; i++) {
-                    RoiSeg &g = sg.s[sg.nseg++];
-                    g.p0 = kimg * plan->class_base[cl]; g.np = kimg * plan->class_count[cl];
-                    g.y0 = q[i].y0; g.x0 = q[i].x0; g.rh = q[i].rh; g.rw = q[i].rw;
-                }
-            }
-        } else {
-            sg = roi_segs_of(*plan, (cst ? plan->down.rect_live : plan->down.rect)[l], kimg);
-        }
-        if (cst) {
-            RoiSeg &g = sg.s[sg.nseg++];
-            g = RoiSeg{};
-            g.p0 = n_own; g.np = kimg; g.rh = g.rw = plan->down.res[l];
-        }
+        roi_down_segs(*plan, form, l, kimg, sg);
         c->down_segs = std::max(c->down_segs, sg.nseg);
         c->down_seg_total += sg.nseg;
         return &sg;
     };
     // of layer k of down block bi
     auto segs = [&](size_t bi, int k) -> const RoiSegs * { return segs_of(6 * (int)bi + k); };
-    // the strips of layer l's tensor t (C channels) that the constant patches hold: after the launch that writes t, before its readers
-    auto fill = [&](float *t, int l, int C) -> bool {
-        if (!cst) return true;
-        FillItems f{};
-        for (int cl = 0; cl < plan->n_classes; cl++)
-            for (int i = 0; i < 4 && plan->class_count[cl] > 0; i++) {
-                const RoiRect &q = plan->down.fill[l][cl][i];
-                if (q.rh <= 0 || q.rw <= 0) continue;
-                f.it[f.n++] = FillItem{kimg * plan->class_base[cl], kimg * plan->class_count[cl], plan->class_count[cl], q.y0, q.x0, q.rh, q.rw};
-            }
-        return launch_const_fill(t, n_own, n, plan->down.res[l], C, f, s);
-    };
     const int LD = 6 * (int)c->down.size();
     // TMAT_ROI_DOWN bit 1: the tile table of fused layer k (1 or 3) of down block bi.  dev null: the launch stays full-frame (no plan, bf16x3
     // weights, or every patch whole).  A table that could not be made clears tab_ok (the error is set)
-    RoiEntry *ent = nullptr;
-    if (roi_any && (c->roi_down & 2u))
-        for (RoiEntry *e : c->roi_cache) if (&e->plan == plan) ent = e;
-    c->sep_tiles.clear();
-    c->down_segs = c->down_seg_total = 0;
+    RoiEntry *ent = form != ROI_DOWN_FULL && (c->roi_down & 2u) ? roi_entry_of(c, plan) : nullptr;
     bool tab_ok = true;
-    // the shared-interior form: with the constant-ring form and the tile tables only, and where the plan shares anything
     const RoiShareTab *shr = nullptr;
-    if (share && cst && ent && plan->down.share_any && !(shr = roi_share_tab(ent, kimg, c->roi_share_rect != 0, c->roi_share_fused_rect != 0)))
-        return TMAT_E_HIP;
-    // the rectangle launches' form: where the shared-interior form runs, bit 0 of TMAT_ROI_DOWN is on and the longest table fits
-    rect_form = shr && share_rect && roi_b && plan->down.rect_any && plan->down.rect_segs + 1 <= ROI_MAX_SEGS;
-    // the fused levels' form: where that form runs, the plan has one and its longest table fits (the planner keeps it below the cap)
-    fused_form = rect_form && share_fused_rect && plan->down.fused_rect_any && plan->down.fused_rect_segs + 1 <= ROI_MAX_SEGS;
-    // the copies of layer l's tensor t out of the neighbour patches: behind its constant fill, before its first reader
-    auto share_fill = [&](float *t, int l, int C) -> bool {
+    if (form >= ROI_DOWN_SHARE && !(ent && (shr = roi_share_tab(ent, kimg, form)))) return TMAT_E_HIP;
+    // what layer l's tensor t (C channels) is copied into after the launch that writes it, before its readers: the strips the constant
+    // patches hold, then the items out of the neighbour patches
+    auto copies = [&](float *t, int l, int C) -> bool {
+        if (form < ROI_DOWN_CONST) return true;
+        FillItems f;
+        roi_down_const_items(*plan, form, l, kimg, f);
+        if (!launch_const_fill(t, n_own, n, plan->down.res[l], C, f, s)) return false;
         if (!shr) return true;
-        // (a pooled output whose copies the fused levels' form cuts to halo strips takes those, not its whole zone)
-        const bool strips = fused_form && plan->down.fused_fill_on[l];
         for (const RoiShareTab::Layer &sl : shr->layers)
-            if (sl.layer == l && (sl.fused ? strips : sl.rect ? rect_form : !strips) && !launch_share_fill(t, n_own, plan->down.res[l], C, shr->nbr.data(), shr->nbr_dev, sl.items.data(), sl.dev, (int)sl.items.size(), s))
+            if (sl.layer == l && !launch_share_fill(t, n_own, plan->down.res[l], C, shr->nbr.data(), shr->nbr_dev, sl.items.data(), sl.dev, (int)sl.items.size(), s))
                 return false;
         return true;
     };
@@ -506,7 +469,7 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
         t.full = t.n = n * (H / 16) * (H / 16);
         t.full_rep = t.n_rep = (long long)n_own * (H / 16) * (H / 16);
         if (ent && f32) {
-            if (const RoiTileTab *made = roi_tile_tab(ent, 6 * (int)bi + k, kimg, cst, shr != nullptr)) t = *made;
+            if (const RoiTileTab *made = roi_tile_tab(ent, 6 * (int)bi + k, kimg, form)) t = *made;
             else tab_ok = false;
         }
         c->sep_tiles.push_back({t.dev ? t.n_rep : t.full_rep, t.full_rep});       // (the constant patches' whole tiles are not counted)
@@ -522,8 +485,8 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
     const bool stem_in_sep = c->stem_fused && !c->down.empty() && down_block_ws(c, 0) && c->down[0].cin == c->f0 &&
                              !(c->precision == TMAT_PRECISION_BF16X3 && c->sep_bf16);
     if (stem_in_sep) {
-        launch_stem_even(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s, fused_form ? segs_of(LD) : segs(0, 4));      // the pixels block 0's residual 1x1 takes
-        if (!fill(b0, LD, c->f0)) return TMAT_E_ARG;
+        launch_stem_even(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s, segs_of(form == ROI_DOWN_FULL ? 4 : roi_down_stem_layer(*plan, form)));     // the pixels block 0's residual 1x1 takes
+        if (!copies(b0, LD, c->f0)) return TMAT_E_ARG;
     } else launch_stem(X, n, P, P, c->stem_w, c->f0, c->stem_scale, c->stem_shift, b0, s);
     int H = P / 2;
     for (size_t bi = 0; bi < c->down.size(); bi++) {
@@ -546,12 +509,12 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
                 if (!launch_sepconv_ws_stem(X, n, H, H, d.cin, c->stem_w, c->stem_scale, c->stem_shift, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s,
                                             t0.dev, t0.n)) return TMAT_E_ARG;
             } else if (!launch_sepconv_ws(b0, n, H, H, d.cin, bi > 0, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s, sprec, t0.dev, t0.n)) return TMAT_E_ARG;
-            if (!fill(b2, 6 * (int)bi + 1, d.cout) || !share_fill(b2, 6 * (int)bi + 1, d.cout)) return TMAT_E_ARG;
+            if (!copies(b2, 6 * (int)bi + 1, d.cout)) return TMAT_E_ARG;
             ConvArgs r{};
             r.in = b0; r.N = n; r.h = H; r.w = H; r.Cin = d.cin; r.ksize = 1; r.stride = 2; r.W = d.res_w; r.Cout = d.cout;
             r.scale = nullptr; r.shift = d.res_b; r.out = b1;
             if (stem_here) { r.h = H / 2; r.w = H / 2; r.stride = 1; }      // b0 holds the even pixels only
-            if (!conv(c, r, s, segs(bi, 4)) || !fill(b1, 6 * (int)bi + 4, d.cout)) return TMAT_E_ARG;
+            if (!conv(c, r, s, segs(bi, 4)) || !copies(b1, 6 * (int)bi + 4, d.cout)) return TMAT_E_ARG;
             float *nxt = bi + 1 == c->down.size() ? dout : b0;
             // (outside the residual's rectangle the pooled pixels take values nobody wrote and nobody reads; a tile the table skips leaves
             // its pixels and strips unwritten: a needed pooled pixel's 2 i .. 2 i + 2 lie in the layer's rectangle, strips included)
@@ -563,32 +526,31 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
                 launch_maxpool_add(b3, n, H, H, d.cout, b1, nxt, s, nullptr, segs(bi, 5));
             }
             // (the fix-up pass may have written junk into pooled pixels of skipped tiles: the copies overwrite every one a consumer reads)
-            if (!fill(nxt, 6 * (int)bi + 5, d.cout) || !share_fill(nxt, 6 * (int)bi + 5, d.cout)) return TMAT_E_ARG;
+            if (!copies(nxt, 6 * (int)bi + 5, d.cout)) return TMAT_E_ARG;
             H /= 2;
             continue;
         }
         const int l0 = 6 * (int)bi;
         launch_dwconv(b0, n, H, H, d.cin, 1, d.dw[0], b1, s, segs(bi, 0));
-        if (!fill(b1, l0, d.cin)) return TMAT_E_ARG;
+        if (!copies(b1, l0, d.cin)) return TMAT_E_ARG;
         ConvArgs a{};
         a.in = b1; a.N = n; a.h = H; a.w = H; a.Cin = d.cin; a.relu_in = 0; a.ksize = 1; a.stride = 1;
         a.W = d.pw[0]; a.Cout = d.cout; a.scale = d.scale[0]; a.shift = d.shift[0]; a.resid = nullptr; a.rs = 0;
         a.relu_out = 1; a.out = b2;
-        if (!conv(c, a, s, segs(bi, 1)) || !fill(b2, l0 + 1, d.cout)) return TMAT_E_ARG;
+        if (!conv(c, a, s, segs(bi, 1)) || !copies(b2, l0 + 1, d.cout)) return TMAT_E_ARG;
         launch_dwconv(b2, n, H, H, d.cout, 0, d.dw[1], b3, s, segs(bi, 2));
-        if (!fill(b3, l0 + 2, d.cout)) return TMAT_E_ARG;
+        if (!copies(b3, l0 + 2, d.cout)) return TMAT_E_ARG;
         a.in = b3; a.Cin = d.cout; a.W = d.pw[1]; a.scale = d.scale[1]; a.shift = d.shift[1]; a.relu_out = 0; a.out = b2;
-        if (!conv(c, a, s, segs(bi, 3)) || !fill(b2, l0 + 3, d.cout)) return TMAT_E_ARG;
+        if (!conv(c, a, s, segs(bi, 3)) || !copies(b2, l0 + 3, d.cout)) return TMAT_E_ARG;
         ConvArgs r{};
         r.in = b0; r.N = n; r.h = H; r.w = H; r.Cin = d.cin; r.ksize = 1; r.stride = 2; r.W = d.res_w; r.Cout = d.cout;
         r.scale = nullptr; r.shift = d.res_b; r.out = b1;
-        if (!conv(c, r, s, segs(bi, 4)) || !fill(b1, l0 + 4, d.cout)) return TMAT_E_ARG;
+        if (!conv(c, r, s, segs(bi, 4)) || !copies(b1, l0 + 4, d.cout)) return TMAT_E_ARG;
         const bool last = bi + 1 == c->down.size();
         float *dr = (last && c->relu_copy && dout == c->dout[di]) ? c->dout_relu[di] : nullptr;      // activated copy for the first up block
         launch_maxpool_add(b2, n, H, H, d.cout, b1, last ? dout : b0, s, dr, segs(bi, 5));
-        if (!fill(last ? dout : b0, l0 + 5, d.cout) || (dr && !fill(dr, l0 + 5, d.cout))) return TMAT_E_ARG;
-        // (the rectangle launches' form: the shared zone of the bottleneck tensor and of its activated copy)
-        if (!share_fill(last ? dout : b0, l0 + 5, d.cout) || (dr && !share_fill(dr, l0 + 5, d.cout))) return TMAT_E_ARG;
+        // (the rectangle launches' form: the shared zone of the bottleneck tensor and of its activated copy comes from the neighbours)
+        if (!copies(last ? dout : b0, l0 + 5, d.cout) || (dr && !copies(dr, l0 + 5, d.cout))) return TMAT_E_ARG;
         if (dr) c->dout_relu_ok[di] = true;
         H /= 2;
     }
@@ -741,8 +703,7 @@ int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred
         launch_minmax_f32(xi, k, (size_t)hh * ww, mn, mx, c->stream);
         launch_extract_tiles(xi, mn, k, g, c->patch_in, c->stream);
         // (the constant-ring form only on request: the default launches of this entry point are pinned to the dependency plan's tiles)
-        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan, c->roi_const == 1 ? mn : nullptr,
-                                      c->roi_share == 1, c->roi_share_rect == 1, c->roi_share_fused_rect == 1)
+        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan, mn, roi_down_resolve(c, plan, k, true, false))
                       : unet_forward_dev(c, c->patch_in, k * g.tiles_per_img, c->patch_out, c->stream);
         if (!rc && plan) rc = unet_up_dev(c, c->dout[0], k * g.tiles_per_img, c->patch_out, c->stream, plan);
         if (rc) return rc;

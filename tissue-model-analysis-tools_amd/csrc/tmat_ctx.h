@@ -24,20 +24,21 @@ struct UpBlock {
     float *res_w = nullptr, *res_b = nullptr;
 };
 struct ProfEv { hipEvent_t e0, e1; double flops; };
-// tile table of a fused separable layer for passes of k images (roi_plan.h:roi_sep_tile_table): dev (null: every patch whole, the launch
-// stays full-frame) holds n ids; a constant like `order` -- uploaded once, outside the workspaces tmat_debug_poison fills
-// live: the table of the constant-ring form (roi_sep_tile_table_live) followed by every tile of the pass's k all-constant patches, which
-// sit behind its patches; n_rep of full_rep: the planner's own counts, without those (what tmat_debug_sep_tiles reports)
-// share (with live): the shared-interior form's table (roi_sep_tile_table_share) in place of the constant-ring form's
-struct RoiTileTab { int layer = 0, k = 0, n = 0; long long full = 0; int *dev = nullptr; bool live = false; long long n_rep = 0, full_rep = 0; bool share = false; };
-// the copies of the shared-interior form for passes of k images: the neighbour table in the pass's class-major order and, per stored
-// tensor (layer), the items of RoiDownPlan::share_fill with their classes' patch ranges -- host copies for the launcher's checks,
-// device copies (uploaded once, like the tile tables) for the kernel
+// tile table of a fused separable layer for passes of k images under a form (roi_plan.h:roi_sep_tile_table): dev (null: every patch whole,
+// the launch stays full-frame) holds n ids; a constant like `order` -- uploaded once, outside the workspaces tmat_debug_poison fills
+// form: ROI_DOWN_REGION, ROI_DOWN_CONST or ROI_DOWN_SHARE (the forms above it keep its tiles).  From ROI_DOWN_CONST upwards the table is
+// followed by every tile of the pass's k all-constant patches, which sit behind its patches; n_rep of full_rep: the planner's own
+// counts, without those (what tmat_debug_sep_tiles reports)
+struct RoiTileTab { int layer = 0, k = 0, n = 0; long long full = 0; int *dev = nullptr; RoiDownForm form = ROI_DOWN_REGION; long long n_rep = 0, full_rep = 0; };
+// the neighbour copies of passes of k images under a form (ROI_DOWN_SHARE and above): the neighbour table in the pass's class-major
+// order and, per stored tensor (layer), the items that form copies (roi_plan.h:roi_down_copy_items) -- host copies for the launcher's
+// checks, device copies (uploaded once, like the tile tables) for the kernel
 struct RoiShareTab {
     int k = 0;
+    RoiDownForm form = ROI_DOWN_SHARE;
     std::vector<int> nbr;
     int *nbr_dev = nullptr;
-    struct Layer { int layer = 0; std::vector<ShareItem> items; ShareItem *dev = nullptr; bool rect = false, fused = false; };     // rect: of RoiDownPlan::rect_fill; fused: of RoiDownPlan::fused_fill
+    struct Layer { int layer = 0; std::vector<ShareItem> items; ShareItem *dev = nullptr; };
     std::vector<Layer> layers;
 };
 struct RoiEntry {
@@ -225,26 +226,27 @@ struct Ctx {
     // level, the residual 1x1 layers, the stem at the even pixels, the pooling fix-ups.  Bit 1: the fused separable layers visit only
     // the tiles of their rectangles (RoiEntry::tabs).  0: the down path stays full-frame
     unsigned roi_down = 3u;
-    // TMAT_ROI_CONST: the constant-ring form of the region-form down path (roi_plan.h:RoiDownPlan::live): what the padding ring makes
-    // constant is copied from an all-constant patch per image instead of computed.  -1 (unset): the batch pipeline runs it, predict_smooth
-    // does not (tests pin its launches to the dependency plan's tiles); 0: nobody; 1: both.  The k all-constant patches of a pass of k
-    // images ride behind its patches in the same launches: the down-path workspaces and the input buffers hold const_cap patches more
-    // than max_patches, and a pass of more images (fewer than 64 patches per image at the default size) keeps the dependency plan.
+    // The four switches of the down path's forms above ROI_DOWN_REGION, each on top of the one before it (roi_plan.h:RoiDownForm).  All
+    // are tri-state: -1 (unset): the batch pipeline runs the form, predict_smooth does not (tests pin its launches to the dependency
+    // plan's tiles); 0: nobody; 1: both.  ONE place turns them, the plan and the pass into the form a pass runs: roi_down_resolve.
+    // TMAT_ROI_CONST, ROI_DOWN_CONST (roi_plan.h:RoiDownPlan::live): what the padding ring makes constant is copied from an all-constant
+    // patch per image instead of computed.  The k all-constant patches of a pass of k images ride behind its patches in the same
+    // launches: the down-path workspaces and the input buffers hold const_cap patches more than max_patches, and a pass of more images
+    // (fewer than 64 patches per image at the default size) keeps the dependency plan.
     int roi_const = -1;
     int const_cap = 0;
-    // TMAT_ROI_SHARE: the shared-interior form on top of the constant-ring form (roi_plan.h:RoiDownPlan::share): what a patch's
-    // successor on an axis computes of their overlap is copied, not computed again; the fused separable layers skip the tiles that
-    // leaves without a needed pixel.  -1 (unset): the batch pipeline runs it, predict_smooth does not; 0: nobody; 1: both.  Only where
-    // the constant-ring form runs, and only with the tile tables (TMAT_ROI_DOWN bit 1).
+    // TMAT_ROI_SHARE, ROI_DOWN_SHARE (roi_plan.h:RoiDownPlan::share): what a patch's successor on an axis computes of their overlap is
+    // copied, not computed again; the fused separable layers skip the tiles that leaves without a needed pixel.  Only where the
+    // constant-ring form runs, and only with the tile tables (TMAT_ROI_DOWN bit 1).
     int roi_share = -1;
-    // TMAT_ROI_SHARE_RECT: the rectangle launches of the unfused 40² level take the shared-interior form too (roi_plan.h:
-    // RoiDownPlan::rcomp): several disjoint rectangles per class in their segment tables, the bottleneck tensor's shared zone copied.
-    // -1 (unset): the batch pipeline runs it, predict_smooth does not; 0: nobody; 1: both.  Only where the shared-interior form runs.
+    // TMAT_ROI_SHARE_RECT, ROI_DOWN_SHARE_RECT (roi_plan.h:RoiDownPlan::rcomp): the rectangle launches of the unfused 40² level take the
+    // shared-interior form too: several disjoint rectangles per class in their segment tables, the bottleneck tensor's shared zone
+    // copied.  Only where the shared-interior form runs, and only with the rectangle launches (TMAT_ROI_DOWN bit 0).
     int roi_share_rect = -1;
-    // TMAT_ROI_SHARE_FUSED_RECT: the rectangle launches of the fused 160² and 80² levels -- stem at the even pixels, stride-2 residual
-    // 1x1, pooling fix-up -- take the shared-interior form as well (roi_plan.h:RoiDownPlan::fcomp), and the pooled outputs are copied as
-    // halo strips, not as whole zones.  -1 (unset): the batch pipeline runs it, predict_smooth does not; 0: nobody; 1: both.  Only where
-    // the rectangle launches' form of the unfused level runs: while that level reads the pooled outputs whole, strips are not enough.
+    // TMAT_ROI_SHARE_FUSED_RECT, ROI_DOWN_SHARE_FUSED_RECT (roi_plan.h:RoiDownPlan::fcomp): the rectangle launches of the fused 160² and
+    // 80² levels -- stem at the even pixels, stride-2 residual 1x1, pooling fix-up -- take the shared-interior form as well, and the
+    // pooled outputs are copied as halo strips, not as whole zones.  Only where the rectangle launches' form of the unfused level runs:
+    // while that level reads the pooled outputs whole, strips are not enough.
     int roi_share_fused_rect = -1;
     float *padval[2] = {nullptr, nullptr};                   // the pad values of a pipeline pass, per slot: c->scratch is rewritten by the front end of the pass after next
     std::vector<RoiEntry *> roi_cache;
@@ -269,10 +271,16 @@ struct Ctx {
 
 int unet_forward_dev(Ctx *c, const float *X, int n, float *Y, hipStream_t s);
 int ensure_patch_io(Ctx *c, int n_patches);
-// padval (nullable, with a plan only): the pad values of the pass's images on the device -- the constant-ring form, where the handle and
-// the pass allow it.  X then has room for n + n / tiles_per_img patches (patch_in and patch_in2 do): the all-constant patches are written there
+// The form a down pass of kimg images runs (roi_plan.h:RoiDownForm): the highest one that the handle's switches ask for -- by_default:
+// the entry point runs a form whose switch is unset (the batch pipeline does, predict_smooth does not) --, that the handle and the
+// pass allow and that the plan has.  have_padval: the pad values of the pass's images are on the device.  The one place where the
+// eligibility chain is written down; both tiled entry points go through it.
+RoiDownForm roi_down_resolve(const Ctx *c, const RoiPlan *plan, int kimg, bool have_padval, bool by_default);
+// plan + form (tiled callers): n is a whole number of images' patches in the plan's class-major order and form what roi_down_resolve
+// gave for the pass.  padval: the pad values of the pass's images on the device, from ROI_DOWN_CONST upwards.  X then has room for
+// n + n / tiles_per_img patches (patch_in and patch_in2 do): the all-constant patches are written there
 int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan = nullptr, const float *padval = nullptr,
-                  bool share = false, bool share_rect = false, bool share_fused_rect = false);
+                  RoiDownForm form = ROI_DOWN_FULL);
 // plan (nullable): region form; n is then a whole number of images' patches in the plan's class-major order
 int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s, const RoiPlan *plan = nullptr);
 // the region plan of g's geometry (cached on the handle) and, in g.order, its patch order; null and the image-major order when the region

@@ -185,7 +185,7 @@ EXPORTS = [
     "tmat_analyze_stack", "tmat_field_stats", "tmat_field_stats_pruned", "tmat_resize_aa_u16", "tmat_cell_area_batch", "tmat_cell_area_masked", "tmat_resize_linear_u16",
     "tmat_resnet_load", "tmat_resnet_predict", "tmat_inv_depth_predict", "tmat_inv_depth_predict_multi", "tmat_resnet_set_precision", "tmat_conv2d",
     "tmat_roi_plan", "tmat_roi_plan_tight", "tmat_roi_plan_exact", "tmat_conv2d_roi", "tmat_conv2d_roi_s2", "tmat_roi_plan_down", "tmat_roi_sep_tiles", "tmat_debug_sep_tiles", "tmat_debug_down_segs", "tmat_debug_down_seg_total",
-    "tmat_roi_plan_const", "tmat_roi_sep_tiles_live", "tmat_roi_plan_share", "tmat_roi_sep_tiles_share", "tmat_roi_plan_share_rect", "tmat_roi_plan_share_fused_rect", "tmat_debug_share_fill_check",
+    "tmat_roi_plan_const", "tmat_roi_sep_tiles_live", "tmat_roi_plan_share", "tmat_roi_sep_tiles_share", "tmat_roi_plan_share_rect", "tmat_roi_plan_share_fused_rect", "tmat_roi_down_schedule", "tmat_debug_share_fill_check",
     "tmat_stage_pictures", "tmat_host_stage_pictures", "tmat_analyze_batch_ex", "tmat_analyze_batch_ex_dev",
     "tmat_png_stripe", "tmat_png_bound", "tmat_png_encode_batch", "tmat_png_encode_batch_dev", "tmat_png_encode_batch_timed",
     "tmat_host_png_encode_batch", "tmat_render_tree_png",
@@ -874,6 +874,31 @@ def roi_plan_share_fused_rect(hh, ww, patch=320, channels=(512, 512, 256, 128, 6
     return dict(n_classes=int(ncls[0]), n_rects=nrect, rects=rects, comp=comp, fills=fills[:int(nfill[0])], fill_on=on, mac=tot[:, 0],
                 bytes=tot[:, 1], px=tot[:, 2], px_live=tot[:, 3], copy_old=tot[:, 4], copy_new=tot[:, 5], any=bool(info[0]),
                 levels=int(info[1]), max_segs=int(info[2]))
+
+
+ROI_DOWN_FORMS = ("full", "region", "const", "share", "share_rect", "share_fused_rect")      # csrc/roi_plan.h:RoiDownForm, by value
+
+
+def roi_down_schedule(hh, ww, form, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
+    """tmat_roi_down_schedule (include/tmat.h): what a down pass of k images launches under `form` (a name of ROI_DOWN_FORMS or its value,
+    "region" upwards); host arithmetic, no GPU.  Returns a dict: form (the one that runs, by value), stem_layer, max_segs, seg_total,
+    segs: per layer of the down plan an array [n][6] (first patch, patches, y0, x0, rows, columns) in launch order, const_fills [n][7]
+    (layer, first patch, patches, y0, x0, rows, columns), copies [n][8] (layer, first patch, patches, direction, y0, x0, rows, columns)."""
+    L = lib()
+    L.tmat_roi_down_schedule.argtypes = ([C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint, C.c_int, C.c_int] + [C.c_void_p] * 3 +
+                                         [C.c_int, C.c_void_p, C.c_void_p] * 2)
+    n_up, n_down = len(channels) - 1, len(down_channels) - 1
+    ch, dch = np.asarray(channels, np.int32), np.asarray(down_channels, np.int32)
+    nl = 6 * n_down + 4
+    info, nseg, ncf, ncp = np.zeros(4, np.int32), np.zeros(nl, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+    segs = np.zeros((nl, 64, 6), np.int32)
+    cap = nl * 16 * 12
+    cfill, copies = np.zeros((cap, 7), np.int32), np.zeros((cap, 8), np.int32)
+    f = ROI_DOWN_FORMS.index(form) if isinstance(form, str) else int(form)
+    check(L.tmat_roi_down_schedule(hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), f, int(k), ptr(info), ptr(nseg), ptr(segs),
+                                   cap, ptr(ncf), ptr(cfill), cap, ptr(ncp), ptr(copies)), "roi_down_schedule")
+    return dict(form=int(info[0]), stem_layer=int(info[1]), max_segs=int(info[2]), seg_total=int(info[3]),
+                segs=[segs[l, :int(nseg[l])].copy() for l in range(nl)], const_fills=cfill[:int(ncf[0])], copies=copies[:int(ncp[0])])
 
 
 def roi_sep_tiles_share(hh, ww, layer, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
