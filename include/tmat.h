@@ -123,6 +123,25 @@ int tmat_well_threshold(tmat_handle h, const float *img, int H, int W, uint8_t *
 /* the same for a float64 image: integer images (compute_cell_area.py:127) enter skimage's gaussian through img_as_float */
 int tmat_well_threshold_f64(tmat_handle h, const double *img, int H, int W, uint8_t *out);
 int tmat_canny_mask(tmat_handle h, const uint8_t *mask, int H, int W, double sigma, uint8_t *edges);
+/* n masks of one shape (n, H, W) in one launch set; every mask comes out as from tmat_canny_mask alone (padding, borders and the
+ * hysteresis labels are per image).  n H W <= 2^26. */
+int tmat_canny_mask_batch(tmat_handle h, const uint8_t *masks, int n, int H, int W, double sigma, uint8_t *edges);
+/* The shape generate_well_mask searches on (:153-155): round((h, w) * min(1, 200 / max(h, w))), half to even.  Host only. */
+int tmat_well_small_shape(int h, int w, int *small_h, int *small_w);
+/*
+ * Front end of --detect-well for n Z stacks of one shape that are resident in device memory (compute_branches.py:227-238 and
+ * generate_well_mask up to the ConvexHull call, :153-170), one launch set for all n.  Per stack: max projection; anti-aliased
+ * resize to (out_h, out_w) float64 (the arithmetic of tmat_resize_aa_u16 on that one image, its own clip range);
+ * auto_threshold_well; nearest resize to the small shape (sh, sw) of tmat_well_small_shape(out_h, out_w); canny(sigma 1) of the
+ * small mask plus the mask's own pixels on the image border.  Extrema, histograms, corner medians, the Otsu decision and the
+ * borders of erosion and canny are per stack: a stack leaves a batch exactly as tmat_well_threshold_f64 + tmat_canny_mask
+ * give it alone.
+ * stacks_dev (n, Z, H, W) u16 device (tmat_dev_alloc), read only.  Host outputs: proj_aa_out NULL or (n, out_h, out_w) f64;
+ * thresh_small, border_small (n, sh, sw) u8.  out_h, out_w >= 20, n out_h out_w <= 2^26.  The gaussian tables are those of
+ * tmat_resize_aa_u16 and tmat_well_threshold.  A handle from tmat_create_plain is enough; scratch comes from the handle's pool.
+ */
+int tmat_stack_well_front_dev(tmat_handle h, const uint16_t *stacks_dev, int n, int Z, int H, int W, int out_h, int out_w,
+                              double *proj_aa_out, uint8_t *thresh_small, uint8_t *border_small);
 
 /*
  * The superellipse fit of well detection on the device (csrc/wellfit_kernels.hip), for a batch of images.
@@ -573,13 +592,36 @@ typedef struct tmat_stack_opts {
     uint8_t *proj_pic_out;               /* NULL or (n, H, W) u8: save_vis of the max projection      */
     uint8_t *field_pic_out;              /* NULL or (n, fh, fw) u8: save_vis of the field             */
     int pass_stacks;                     /* 0 = automatic                                             */
+    /* -- the first version of the struct (TMAT_STACK_OPTS_SIZE_V1) ended here; what follows is the tree request, all zero = none -- */
+    int vis_width;                       /* canvas width of the overlays (--vis-width)                */
+    uint8_t *rgb_out;                    /* NULL or (n_thresh, n, vh, vw, 3) u8 host: the overlays    */
+    double *bars_out;                    /* (n_thresh, n, cap_b, 2) f64 host: [birth, death] * W / fw */
+    int cap_b;                           /* bars a (pair, stack) item may have                        */
+    int *n_bars;                         /* (n_thresh, n) host: bars of every item                    */
 } tmat_stack_opts;
+/* sizeof(tmat_stack_opts) before the tree request was added.  A caller that passes it in `size` is served as before: the fields up to
+ * pass_stacks are read, nothing behind them. */
+#define TMAT_STACK_OPTS_SIZE_V1 88u
 /* compute_branches.py:224-306, 366-395, 391-426 for n stacks: rows (n_thresh, n), rows[t * n + i] = stack i at threshold pair t, equal
  * to tmat_analyze_stack (or tmat_field_stats_pruned with the stack's pruning mask) at that pair bit for bit, whatever K is.  The two
  * pictures (:228-229 original_image.png, :303 vesselness_image.png) are the bytes tmat_stage_pictures gives for the stack's max
- * projection and for its field, rendered from the buffers in HBM. */
+ * projection and for its field, rendered from the buffers in HBM.
+ * Tree request (compute_branches.py:431-450; the fields mean what they mean in tmat_analyze_opts for tmat_analyze_batch_grid, each with
+ * a leading n_thresh axis): with bars_out (and n_bars, cap_b) the host graph stage calls tmat_morse_tree for every (pair, stack) with
+ * the stack's pruning mask and the scaling factor W / fw -- the row comes out of the same call and equals the row without a request --
+ * and item (t, i) leaves its bars at bars_out + (t n + i) cap_b 2 and their count in n_bars[t n + i].  With rgb_out as well, a pass
+ * keeps the u16 max projections of its stacks in HBM (taken before the per-slice gaussian) and the overlays are rasterised over them
+ * (tmat_render_tree's picture, bg_dtype u16) on a vis_width x round_half_even(vis_width H / W) canvas: the bytes of
+ * tmat_host_render_tree for the host's max projection and tmat_morse_tree's segments.  The rasteriser runs on the handle's stream in
+ * order with the passes' stages, never beside them.  TMAT_E_CAP: cap_b is too small for some item (n_bars holds what the items that
+ * ran need); TMAT_E_ARG: bars_out without n_bars, cap_b < 0, rgb_out without bars_out or with an empty canvas. */
 int tmat_analyze_stack_batch(tmat_handle h, const uint16_t *stacks, int n, int Z, int H, int W,
                              const tmat_stack_opts *o, tmat_row *rows /* (n_thresh, n) */);
+/* The same for stacks that are already in device memory: stacks_dev (n, Z, H, W) u16 from tmat_dev_alloc / tmat_dev_upload.  A pass
+ * copies its K stacks device to device into the block the per-slice gaussian overwrites; the caller's buffer is only read and holds
+ * after the call what it held before.  Rows, fields and pictures are those of the host-pointer form bit for bit, whatever K. */
+int tmat_analyze_stack_batch_dev(tmat_handle h, const uint16_t *stacks_dev, int n, int Z, int H, int W,
+                                 const tmat_stack_opts *o, tmat_row *rows /* (n_thresh, n) */);
 /* compute_branches.py:258-302 for n prepared stacks vols (n, Z, h, w) in one launch set -> fields (n, h, w); the arrays of `stages`
  * carry a leading n */
 int tmat_vessel_field_batch(tmat_handle h, const float *vols, int n, int Z, int hh, int ww, int hessian,

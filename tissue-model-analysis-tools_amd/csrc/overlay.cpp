@@ -62,6 +62,40 @@ static bool offsets_ok(const int32_t *off, int n)
 static float bg_at(const void *bg, int dtype, size_t i) { return dtype == 0 ? (float)((const uint16_t *)bg)[i] : ((const float *)bg)[i]; }
 
 }  // namespace
+
+int morse_tree_item(const int32_t *verts, int nv, const int32_t *edges, int ne, int fh, int fw, int smooth, int min_len, int max_len, int remove_isolated,
+                    const uint8_t *pruning, double scaling_factor, int64_t *count, double *total_px, double *avg_px, std::vector<double> &segs,
+                    std::vector<int32_t> &branch, double *bars, int cap_b, int *n_bars)
+{
+    const int cap_s = std::max(nv, 1);       // a forest has fewer edges than vertices
+    segs.resize((size_t)cap_s * 4); branch.resize(cap_s);
+    int ns = 0;
+    const int rc = tmat_morse_tree(verts, nv, edges, ne, fh, fw, smooth, min_len, max_len, remove_isolated, pruning, scaling_factor, count, total_px, avg_px,
+                                   segs.data(), branch.data(), cap_s, bars, cap_b, &ns, n_bars);
+    segs.resize((size_t)ns * 4); branch.resize(ns);
+    return rc;
+}
+
+int overlay_pair_dev(const void *bg, int bg_dtype, int k, int bh, int bw, const Canvas &cv, const std::vector<double> *segs,
+                     const std::vector<int32_t> *branch, const OverlayWs &ws, std::vector<OverlaySeg> &ss, std::vector<int> &off, uint8_t *rgb_host,
+                     const char *who, hipStream_t s)
+{
+    const size_t cper = (size_t)cv.vh * cv.vw * 3;
+    auto fail = [who](const char *what, int rc) { set_error(std::string(who) + ": " + what); return rc; };
+    ss.clear();
+    off.assign(k + 1, 0);
+    for (int i = 0; i < k; i++) {
+        if (int rc = prep_segments(segs[i].data(), branch[i].data(), (int)branch[i].size(), bh, bw, cv, ss)) return rc;
+        off[i + 1] = (int)ss.size();
+    }
+    if (ss.size() > ws.seg_cap) return fail("segment workspace too small", TMAT_E_CAP);
+    if ((!ss.empty() && hipMemcpyAsync(ws.dseg, ss.data(), ss.size() * sizeof(OverlaySeg), hipMemcpyHostToDevice, s) != hipSuccess) ||
+        hipMemcpyAsync(ws.doff, off.data(), (size_t)(k + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return fail("segment upload failed", TMAT_E_HIP);
+    if (overlay_render_dev(bg, bg_dtype, ws.dmm, k, bh, bw, ws.dseg, ws.doff, cv.vh, cv.vw, cv.rp, ws.drgb, s)) return fail("overlay launch failed", TMAT_E_HIP);
+    if (rgb_host && hipMemcpyAsync(rgb_host, ws.drgb, (size_t)k * cper, hipMemcpyDeviceToHost, s) != hipSuccess) return fail("overlay copy failed", TMAT_E_HIP);
+    return TMAT_OK;
+}
+
 }  // namespace tmat
 
 using namespace tmat;

@@ -87,6 +87,22 @@ int overlay_minmax_dev(const void *bg, int bg_dtype, int n, int bh, int bw, floa
 int overlay_render_dev(const void *bg, int bg_dtype, const float *mnmx, int n, int bh, int bw, const OverlaySeg *segs, const int *seg_offsets,
                        int vh, int vw, float rp, uint8_t *rgb, hipStream_t s);
 
+// What the "with tree" forms of the batch pipelines share (pipeline.cpp: 2-D images; stack_pipeline.cpp: Z stacks).
+// tmat_morse_tree of one (threshold pair, image) item: the row, the bars into the caller's (cap_b, 2) block and the segments into vectors
+// sized for the item (a forest has fewer edges than vertices)
+int morse_tree_item(const int32_t *verts, int nv, const int32_t *edges, int ne, int fh, int fw, int smooth, int min_len, int max_len, int remove_isolated,
+                    const uint8_t *pruning, double scaling_factor, int64_t *count, double *total_px, double *avg_px, std::vector<double> &segs,
+                    std::vector<int32_t> &branch, double *bars, int cap_b, int *n_bars);
+// device scratch of one pair's overlays of a pass of up to K images: segment table (seg_cap entries), (K, 2) extrema, K + 1 offsets, K canvases
+struct OverlayWs { OverlaySeg *dseg; size_t seg_cap; float *dmm; int *doff; uint8_t *drgb; };
+// One pair's overlays of the k images of a pass on stream s: item i's segments (segs[i], branch[i], background pixels) are mapped onto
+// the canvas, uploaded and rasterised over bg (k, bh, bw) -- whose extrema overlay_minmax_dev has left in ws.dmm -- into ws.drgb; with
+// rgb_host they are copied there.  Nothing is synchronised: ss and off are the host tables of the uploads and must live until the
+// stream has drained.  TMAT_OK, TMAT_E_CAP (segment table too short) or TMAT_E_HIP, with the error set under `who`.
+int overlay_pair_dev(const void *bg, int bg_dtype, int k, int bh, int bw, const Canvas &cv, const std::vector<double> *segs,
+                     const std::vector<int32_t> *branch, const OverlayWs &ws, std::vector<OverlaySeg> &ss, std::vector<int> &off, uint8_t *rgb_host,
+                     const char *who, hipStream_t s);
+
 // Barcode picture (tmat_host_render_barcode / tmat_render_barcode): the host keeps the stable sort by birth, the edge rounding and the
 // branch colours, and emits one rectangle per bar; host twin and barcode_kernel only fill them over a white S x S canvas.
 // Columns [xa, xb), rows [ya, yb) counted from the BOTTOM row of the canvas; rgb = r | g << 8 | b << 16.  Entry k of a picture's table is

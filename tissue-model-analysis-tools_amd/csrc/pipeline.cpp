@@ -400,16 +400,10 @@ static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, const G
         if (!rc && !tree)
             rc = tmat_morse_stats(V.data(), nv, E.data(), ne, gp.fh, gp.fw, gp.smooth, gp.min_len, gp.max_len, gp.remove_isolated,
                                   pruning ? pruning + i * fper : nullptr, &row.count, &row.total_px, &row.avg_px, nullptr, 0);
-        if (!rc && tree) {
-            const int cap_s = std::max(nv, 1);       // a forest has fewer edges than vertices
-            tsegs[item].resize((size_t)cap_s * 4); tbranch[item].resize(cap_s);
-            int ns = 0;
-            rc = tmat_morse_tree(V.data(), nv, E.data(), ne, gp.fh, gp.fw, gp.smooth, gp.min_len, gp.max_len, gp.remove_isolated,
-                                 pruning ? pruning + i * fper : nullptr, tree->sf,
-                                 &row.count, &row.total_px, &row.avg_px, tsegs[item].data(), tbranch[item].data(), cap_s,
-                                 tree->bars_out + at * tree->cap_b * 2, tree->cap_b, &ns, tree->n_bars + at);
-            tsegs[item].resize((size_t)ns * 4); tbranch[item].resize(ns);
-        }
+        if (!rc && tree)
+            rc = morse_tree_item(V.data(), nv, E.data(), ne, gp.fh, gp.fw, gp.smooth, gp.min_len, gp.max_len, gp.remove_isolated,
+                                 pruning ? pruning + i * fper : nullptr, tree->sf, &row.count, &row.total_px, &row.avg_px, tsegs[item], tbranch[item],
+                                 tree->bars_out + at * tree->cap_b * 2, tree->cap_b, tree->n_bars + at);
         if (rc) job->rc = rc;
     });
     if (tree && !job->rc) {
@@ -426,18 +420,9 @@ static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, const G
             std::vector<int> off(k + 1, 0), roff(k + 1, 0);
             std::vector<BarRect> rects;
             if (render) {
-                for (int i = 0; i < k && !rc; i++) {
-                    const size_t item = (size_t)t * k + i;
-                    rc = prep_segments(tsegs[item].data(), tbranch[item].data(), (int)tbranch[item].size(), h, w, tree->cv, ss);
-                    off[i + 1] = (int)ss.size();
-                }
-                if (!rc && ss.size() > tree->seg_cap) { set_error("analyze (tree): segment workspace too small"); rc = TMAT_E_CAP; }
-                if (!rc && ((!ss.empty() && hipMemcpyAsync(tree->dseg, ss.data(), ss.size() * sizeof(OverlaySeg), hipMemcpyHostToDevice, s) != hipSuccess) ||
-                            hipMemcpyAsync(tree->doff, off.data(), (size_t)(k + 1) * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess)) rc = TMAT_E_HIP;
-                if (!rc && overlay_render_dev(bg, 0, tree->dmm, k, h, w, tree->dseg, tree->doff, tree->cv.vh, tree->cv.vw, tree->cv.rp, tree->drgb, s)) {
-                    set_error("analyze (tree): overlay launch failed"); rc = TMAT_E_HIP;
-                }
-                if (!rc && tree->rgb_out && hipMemcpyAsync(tree->rgb_out + at * cper, tree->drgb, (size_t)k * cper, hipMemcpyDeviceToHost, s) != hipSuccess) rc = TMAT_E_HIP;
+                rc = overlay_pair_dev(bg, 0, k, h, w, tree->cv, &tsegs[(size_t)t * k], &tbranch[(size_t)t * k],
+                                      OverlayWs{tree->dseg, tree->seg_cap, tree->dmm, tree->doff, tree->drgb}, ss, off,
+                                      tree->rgb_out ? tree->rgb_out + at * cper : nullptr, "analyze (tree)", s);
                 if (!rc && tree->tree_png)
                     rc = png_encode_job(*tree, tree->drgb, k, tree->pg_tree, tree->tree_png + at * tree->tree_png_cap, tree->tree_png_cap, tree->tree_png_sizes + at, s);
             }

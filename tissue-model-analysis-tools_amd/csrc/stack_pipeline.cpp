@@ -9,12 +9,14 @@
 #include "morph.h"
 #include "sato.h"
 #include "wellmask.h"
+#include "overlay.h"
 #include "host_par.h"
 
 #include <algorithm>
 #include <cmath>
 #include <chrono>
 #include <cstdio>
+#include <cstddef>
 #include <cstring>
 #include <thread>
 
@@ -248,6 +250,84 @@ int stack_prepare_dev(Ctx *c, uint16_t *stack, int n, int Z, int H, int W, int o
     return stack_resize_aa_dev(c, stack, n, Z, H, W, oh, ow, zoomed, vol, s);
 }
 
+// well_mask_generation.py:153-155: the shape generate_well_mask searches on, round(shape * min(1, 200 / max(shape))) half to even
+void well_small_shape(int h, int w, int *sh, int *sw)
+{
+    const double ratio = std::min(1.0, 200.0 / (double)std::max(h, w));
+    *sh = (int)std::nearbyint((double)h * ratio);
+    *sw = (int)std::nearbyint((double)w * ratio);
+}
+
+// auto_threshold_well (reference :236-277) of n images (n, H, W) in device memory, f64 (img64) or f32 (img32, n = 1 only; overwritten)
+// -> thresholded, eroded masks `out` (n, H, W) u8 on the device.  img64 is overwritten by its gaussian
+int well_threshold_dev(Ctx *c, double *img64, float *img32, int n, int H, int W, uint8_t *out, hipStream_t s)
+{
+    const size_t px = (size_t)H * W, tot = (size_t)n * px;
+    DevScope A(c->ws_pool, s);
+    uint8_t *u8 = A.pooled<uint8_t>(tot), *th = A.pooled<uint8_t>(tot);
+    unsigned *hist = A.pooled<unsigned>((size_t)n * 5 * 256);
+    int *decision = A.pooled<int>(2 * (size_t)n), *offs = A.pooled<int>(2 * 81);
+    std::vector<int> o;
+    for (int dy = -5; dy <= 5; dy++) for (int dx = -5; dx <= 5; dx++) if (dy * dy + dx * dx <= 25) { o.push_back(dy); o.push_back(dx); }         // disk(5): 81
+    const int k = (int)o.size() / 2;
+    A.h2d(offs, A.keep(std::move(o)), sizeof(int) * 2 * k);
+    // gaussian(image, sigma=1): ndi.gaussian_filter, mode 'nearest', truncate 4, the image's float type after each axis
+    if (img64) {
+        double *db = A.pooled<double>(tot), *dmm = A.pooled<double>(2 * (size_t)n);
+        if (!A.ok) return TMAT_E_HIP;
+        const GaussTable &gt = gauss_table(c, 1.0, 0, gauss_radius(1.0, 4.0));
+        const double *w = table_dev(c, gt);
+        if (!w) return TMAT_E_HIP;
+        launch_corr1d_f64(img64, db, (size_t)n, H, W, w, gt.r, gt.sym, EXT_NEAREST, s);
+        launch_corr1d_f64(db, img64, (size_t)n * H, W, 1, w, gt.r, gt.sym, EXT_NEAREST, s);
+        launch_wm_rescale_u8_f64(img64, n, px, dmm, u8, s);
+    } else {
+        if (n != 1) { set_error("well threshold: float32 images go one at a time"); return TMAT_E_ARG; }
+        float *b = A.pooled<float>(px), *mm = A.pooled<float>(2);
+        if (!A.ok) return TMAT_E_HIP;
+        if (!gauss_pass_f32(c, img32, b, Pass{1.0, 0, H, W, 1}, 4.0, EXT_NEAREST, s) || !gauss_pass_f32(c, b, img32, Pass{1.0, 0, W, 1, (size_t)H}, 4.0, EXT_NEAREST, s))
+            return TMAT_E_HIP;
+        launch_minmax_f32(img32, 1, px, mm, mm + 1, s);
+        launch_wm_rescale_u8(img32, px, mm, mm + 1, u8, s);
+    }
+    launch_wm_hist(u8, n, H, W, hist, s);
+    launch_wm_decide(hist, n, H, W, decision, s);
+    launch_wm_threshold(u8, n, px, decision, th, s);
+    launch_wm_erode(th, n, H, W, offs, k, out, s);
+    A.check(hipGetLastError(), "tmat_well_threshold: kernel launch");
+    return A.finish();          // the scope's blocks go back to the pool: nothing may be in flight on them
+}
+
+// skimage.feature.canny(mask, sigma) of n boolean images (n, H, W) u8 on the device -> edges (n, H, W) u8 on the device
+int canny_mask_dev(Ctx *c, const uint8_t *m, int n, int H, int W, double sigma, uint8_t *e, hipStream_t s)
+{
+    const int r = gauss_radius(sigma, 4.0);
+    const int Hp = H + 2 * r, Wp = W + 2 * r;
+    const size_t npx = (size_t)n * H * W, npad = (size_t)n * Hp * Wp;
+    DevScope A(c->ws_pool, s);
+    double *pa = A.pooled<double>(npad), *pb = A.pooled<double>(npad), *pt = A.pooled<double>(npad);
+    CannyWs cw{};
+    cw.sm = A.pooled<double>(npx); cw.t0 = A.pooled<double>(npx); cw.is_ = A.pooled<double>(npx); cw.js = A.pooled<double>(npx); cw.mag = A.pooled<double>(npx);
+    cw.low = A.pooled<uint8_t>(npx); cw.high = A.pooled<uint8_t>(npx); cw.L = A.pooled<int>(npx); cw.flag = A.pooled<int>(npx);
+    double *tabs = A.pooled<double>(6);
+    A.h2d(tabs, A.keep(std::vector<double>{-1.0, 0.0, 1.0, 1.0, 2.0, 1.0}), 6 * sizeof(double));
+    cw.w_diff = tabs; cw.w_smooth = tabs + 3;
+    if (!A.ok) return TMAT_E_HIP;
+    // gaussian(x, sigma, mode='constant') of the image and of the all-ones mask (0.18.3 smooth_with_function_and_mask): zero padding
+    // by the kernel radius makes the boundary mode irrelevant
+    launch_wm_pad(m, n, H, W, r, pa, pb, s);
+    const GaussTable &gt = gauss_table(c, sigma, 0, r);
+    const double *w = table_dev(c, gt);
+    if (!w) return TMAT_E_HIP;
+    launch_corr1d_f64(pa, pt, (size_t)n, Hp, Wp, w, gt.r, gt.sym, EXT_NEAREST, s);
+    launch_corr1d_f64(pt, pa, (size_t)n * Hp, Wp, 1, w, gt.r, gt.sym, EXT_NEAREST, s);
+    launch_corr1d_f64(pb, pt, (size_t)n, Hp, Wp, w, gt.r, gt.sym, EXT_NEAREST, s);
+    launch_corr1d_f64(pt, pb, (size_t)n * Hp, Wp, 1, w, gt.r, gt.sym, EXT_NEAREST, s);
+    launch_wm_crop_div(pa, pb, n, H, W, r, cw.sm, s);
+    if (canny_core_dev(n, H, W, cw, e, s)) { set_error("tmat_canny_mask: kernel launch failed"); return TMAT_E_HIP; }
+    return A.finish();
+}
+
 // ---- batch entry point of the branch: K stacks per pass, the host graph stage of pass p - 1 beside the device stages of pass p ----------
 
 // Device bytes one stack of a pass holds at the pass's peak, from the blocks the stages take (DevScope::pooled in tmat_analyze_stack_batch,
@@ -303,12 +383,29 @@ struct StackJob {
     void join() { if (th.joinable()) th.join(); }
 };
 
+// The tree request of a call (tmat_stack_opts.bars_out ...): the host graph stage calls tmat_morse_tree instead of tmat_morse_stats and
+// leaves the segments of its (pair, stack) items here; the pass loop rasterises them over the pass's max projections, which stay in
+// HBM in one of three slots (proj) until then.  Everything on the device is enqueued by the calling thread on the handle's stream,
+// in order with the passes' own stages: a render kernel never runs beside the DMT sweep kernel, whose barrier between workgroups counts
+// on having the chip.
+struct StackTree {
+    double sf;                      // compute_branches.py:437: W / fw
+    double *bars_out; int cap_b; int *n_bars; uint8_t *rgb_out;     // caller's, whole call
+    Canvas cv;
+    uint16_t *proj[3];              // (K, H, W) u16 each, device
+    OverlayWs ws;
+    std::vector<std::vector<double>> segs[2];       // per result slot: (n_thresh, k) items of the pass
+    std::vector<std::vector<int32_t>> branch[2];
+};
+
 // host graph stage of one pass: DMT collect + MorseGraph statistics of every (threshold pair, stack) on the shared worker threads
-void stack_pass_host(const StackSlot sl, int k, int fh, int fw, const tmat_stack_opts o, const uint8_t *pruning, bool sweep_dev, tmat_row *rows, int n,
-                     StackJob *job, double *host_ms)
+// rows: the call's rows (n_thresh, n); the pass's stacks are i0 .. i0 + k of every pair
+void stack_pass_host(const StackSlot sl, int slot, int i0, int k, int fh, int fw, const tmat_stack_opts o, const uint8_t *pruning, bool sweep_dev, tmat_row *rows,
+                     int n, StackTree *tree, StackJob *job, double *host_ms)
 {
     const double t0 = now_ms();
     const size_t npx = (size_t)fh * fw, nE = dmt_edge_count(fh, fw);
+    if (tree) { tree->segs[slot].assign((size_t)o.n_thresh * k, {}); tree->branch[slot].assign((size_t)o.n_thresh * k, {}); }
     parallel_images(o.n_thresh * k, [&](int it) {
         const int t = it / k, i = it - t * k;
         const int cap_v = (int)npx + 4, cap_e = 3 * (int)npx + 4;
@@ -316,20 +413,46 @@ void stack_pass_host(const StackSlot sl, int k, int fh, int fw, const tmat_stack
         int nv = 0, ne = 0;
         int rc = dmt_graph_host_sorted(sl.f255 + i * npx, fh, fw, o.thresh[2 * t], o.thresh[2 * t + 1], sl.ids + i * nE, sl.m[i], V.data(), cap_v, E.data(),
                                        cap_e, &nv, &ne, sweep_dev ? sl.kind + i * nE : nullptr, sweep_dev ? sl.pers + i * nE : nullptr);
-        tmat_row *row = rows + (size_t)t * n + i;
-        if (!rc)
+        const size_t at = (size_t)t * n + i0 + i;
+        tmat_row *row = rows + at;
+        const uint8_t *pm = pruning ? pruning + i * npx : nullptr;
+        if (!rc && !tree)
             rc = tmat_morse_stats(V.data(), nv, E.data(), ne, fh, fw, o.smoothing_window_px, o.min_branch_length_px, o.max_branch_length_px, o.remove_isolated,
-                                  pruning ? pruning + i * npx : nullptr, &row->count, &row->total_px, &row->avg_px, nullptr, 0);
+                                  pm, &row->count, &row->total_px, &row->avg_px, nullptr, 0);
+        if (!rc && tree)
+            rc = morse_tree_item(V.data(), nv, E.data(), ne, fh, fw, o.smoothing_window_px, o.min_branch_length_px, o.max_branch_length_px, o.remove_isolated,
+                                 pm, tree->sf, &row->count, &row->total_px, &row->avg_px, tree->segs[slot][it], tree->branch[slot][it],
+                                 tree->bars_out + at * tree->cap_b * 2, tree->cap_b, tree->n_bars + at);
         if (rc) job->rc = rc;
     });
     *host_ms = now_ms() - t0;
+}
+
+// the overlays of pass p (its host job has ended): pair by pair over the pass's projections, copied to the caller's (n_thresh, n, vh, vw, 3)
+int stack_pass_render(StackTree &tr, int p, int K, int n, int n_thresh, int H, int W, hipStream_t s)
+{
+    const int slot = p & 1, i0 = p * K, k = std::min(K, n - i0);
+    const size_t cper = (size_t)tr.cv.vh * tr.cv.vw * 3;
+    const uint16_t *bg = tr.proj[p % 3];
+    if (overlay_minmax_dev(bg, 0, k, H, W, tr.ws.dmm, s)) { set_error("tmat_analyze_stack_batch (tree): min-max launch failed"); return TMAT_E_HIP; }
+    for (int t = 0; t < n_thresh; t++) {
+        std::vector<OverlaySeg> ss;
+        std::vector<int> off;
+        int rc = overlay_pair_dev(bg, 0, k, H, W, tr.cv, &tr.segs[slot][(size_t)t * k], &tr.branch[slot][(size_t)t * k], tr.ws, ss, off,
+                                  tr.rgb_out + ((size_t)t * n + i0) * cper, "tmat_analyze_stack_batch (tree)", s);
+        if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = TMAT_E_HIP;       // the pair's canvases and tables are reused by the next pair
+        if (rc) return rc;
+    }
+    return TMAT_OK;
 }
 
 bool hessian_ok(int h) { return h == TMAT_SATO_GAUSSIAN_DERIVATIVES || h == TMAT_SATO_GRADIENT; }
 
 }  // namespace
 
-int analyze_stack_batch(Ctx *c, const uint16_t *stacks, int n, int Z, int H, int W, const tmat_stack_opts &o, tmat_row *rows)
+// stacks_on_dev: `stacks` is device memory (tmat_analyze_stack_batch_dev); a pass then copies its stacks device to device into the block
+// the per-slice gaussian overwrites, so the caller's buffer is only ever read
+int analyze_stack_batch(Ctx *c, const uint16_t *stacks, bool stacks_on_dev, int n, int Z, int H, int W, const tmat_stack_opts &o, tmat_row *rows)
 {
     const int fh = (int)std::nearbyint((double)H * ((double)o.ds_width / (double)W)), fw = (int)std::nearbyint((double)W * ((double)o.ds_width / (double)W));
     if (fh < 2 || fw < 2) { set_error("tmat_analyze_stack_batch: downsampled shape is empty"); return TMAT_E_ARG; }
@@ -341,6 +464,27 @@ int analyze_stack_batch(Ctx *c, const uint16_t *stacks, int n, int Z, int H, int
         for (int i = 0; i < n; i++) { tmat_row &r = rows[(size_t)t * n + i]; r.index = o.first_index + i; r.count = 0; r.total_px = 0; r.avg_px = 0; }
     const bool sweep_dev = c->dmt_sweep_device;
     hipStream_t s = c->stream;
+    // the tree request: scratch for the whole call, taken before any pass is in flight (the job threads never touch the pool)
+    DevScope TA(c->ws_pool, s);
+    StackTree tr{}, *tree = nullptr;
+    if (o.bars_out) {
+        tree = &tr;
+        tr.sf = (double)W / (double)fw;
+        tr.bars_out = o.bars_out; tr.cap_b = o.cap_b; tr.n_bars = o.n_bars; tr.rgb_out = o.rgb_out;
+        for (size_t r = 0; r < (size_t)o.n_thresh * n; r++) o.n_bars[r] = 0;
+        if (o.rgb_out) {
+            if (!canvas_of(H, W, o.vis_width, tr.cv)) { set_error("tmat_analyze_stack_batch (tree): empty canvas"); return TMAT_E_ARG; }
+            const size_t cper = (size_t)tr.cv.vh * tr.cv.vw * 3;
+            for (uint16_t *&pr : tr.proj) pr = TA.pooled<uint16_t>((size_t)K * hw);
+            tr.ws.seg_cap = (size_t)K * npx;
+            tr.ws.dseg = TA.pooled<OverlaySeg>(tr.ws.seg_cap);
+            tr.ws.dmm = TA.pooled<float>(4 * (size_t)K);
+            tr.ws.doff = TA.pooled<int>((size_t)K + 1);
+            tr.ws.drgb = TA.pooled<uint8_t>((size_t)K * cper);
+            if (!TA.ok) return TMAT_E_HIP;
+        }
+    }
+    const bool render = tree && o.rgb_out;
     StackJob jobs[2];
     std::vector<double> gpu_ms(P, 0.0), host_ms(P, 0.0);
     int rc = TMAT_OK;
@@ -350,7 +494,8 @@ int analyze_stack_batch(Ctx *c, const uint16_t *stacks, int n, int Z, int H, int
         // every device stage of the pass in order on the handle's stream: passes never run side by side (the DMT sweep kernel's barrier
         // between workgroups counts on having the chip), the overlap is with the HOST stage of the pass before
         DevScope A(c->ws_pool, s);
-        uint16_t *ds = A.pooled_from(stacks + (size_t)i0 * nin, (size_t)k * nin);
+        uint16_t *ds = stacks_on_dev ? A.pooled<uint16_t>((size_t)k * nin) : A.pooled_from(stacks + (size_t)i0 * nin, (size_t)k * nin);
+        if (stacks_on_dev && A.ok) A.check(hipMemcpyAsync(ds, stacks + (size_t)i0 * nin, (size_t)k * nin * sizeof(uint16_t), hipMemcpyDeviceToDevice, s), "D2D");
         float *vol = A.pooled<float>((size_t)k * Z * npx), *field = A.pooled<float>((size_t)k * npx);
         if (!A.ok) { rc = TMAT_E_HIP; break; }
         void *mm = (o.proj_pic_out || o.field_pic_out) ? A.pooled_bytes(vis_scratch_bytes(k)) : nullptr;
@@ -364,6 +509,8 @@ int analyze_stack_batch(Ctx *c, const uint16_t *stacks, int n, int Z, int H, int
                 vis_picture_dev(proj, TMAT_PIC_U16, k, hw, lo, lo + k, pic, s)) { set_error("tmat_analyze_stack_batch: projection picture failed"); rc = TMAT_E_HIP; break; }
             A.d2h(o.proj_pic_out + (size_t)i0 * hw, pic, (size_t)k * hw);
         }
+        // the tree overlays' background, likewise before the gaussian; slot p % 3: pass p - 2 is drawn further down, after this is queued
+        if (render && zproj_dev(ds, k, Z, H, W, TMAT_ZPROJ_MAX, tr.proj[p % 3], s)) { set_error("tmat_analyze_stack_batch (tree): projection failed"); rc = TMAT_E_HIP; break; }
         rc = stack_prepare_dev(c, ds, k, Z, H, W, fh, fw, vol, s);
         if (!rc) rc = vessel_field_dev(c, vol, k, Z, fh, fw, o.hessian, field, nullptr, s);
         if (rc) break;
@@ -392,6 +539,7 @@ int analyze_stack_batch(Ctx *c, const uint16_t *stacks, int n, int Z, int H, int
         // the slot's host buffers are free once the job of the pass before last has ended
         jobs[slot].join();
         if (jobs[slot].rc) { rc = jobs[slot].rc; break; }
+        if (render && p >= 2 && (rc = stack_pass_render(tr, p - 2, K, n, o.n_thresh, H, W, s))) break;
         const StackSlot &sl = slots[slot];
         A.d2h(sl.f255, f255, (size_t)k * npx * 4);
         A.d2h(sl.ids, ids, (size_t)k * nE * sizeof(int32_t));
@@ -399,10 +547,12 @@ int analyze_stack_batch(Ctx *c, const uint16_t *stacks, int n, int Z, int H, int
         if (sweep_dev) { A.d2h(sl.kind, dkind, (size_t)k * nE); A.d2h(sl.pers, dpers, (size_t)k * nE * sizeof(float)); }
         if (A.finish()) { rc = TMAT_E_HIP; break; }
         gpu_ms[p] = now_ms() - t0;
-        jobs[slot].th = std::thread(stack_pass_host, sl, k, fh, fw, o, o.pruning_masks ? o.pruning_masks + (size_t)i0 * npx : nullptr, sweep_dev, rows + i0, n,
-                                    &jobs[slot], &host_ms[p]);
+        jobs[slot].th = std::thread(stack_pass_host, sl, slot, i0, k, fh, fw, o, o.pruning_masks ? o.pruning_masks + (size_t)i0 * npx : nullptr, sweep_dev, rows, n,
+                                    tree, &jobs[slot], &host_ms[p]);
     }
     for (StackJob &j : jobs) { j.join(); if (j.rc && !rc) rc = j.rc; }
+    // the overlays of the last two passes (the loop drew pass p - 2 during pass p); every host job has ended
+    for (int p = std::max(0, P - 2); render && !rc && p < P; p++) rc = stack_pass_render(tr, p, K, n, o.n_thresh, H, W, s);
     c->stack_trace.clear();
     for (int p = 0; p < P; p++) c->stack_trace.push_back({gpu_ms[p], host_ms[p]});
     static const bool trace = [] { const char *e = getenv("TMAT_TRACE"); return e && atoi(e) > 0; }();
@@ -448,36 +598,18 @@ static int well_threshold(tmat_handle hd, const void *img, int is_f64, int H, in
     hipStream_t s = c->stream;
     const size_t n = (size_t)H * W;
     DevScope A(c->ws_pool, s);
-    float *a = A.pooled<float>(is_f64 ? 1 : n), *b = A.pooled<float>(is_f64 ? 1 : n), *mm = A.pooled<float>(2);
-    double *da = A.pooled<double>(is_f64 ? n : 1), *db = A.pooled<double>(is_f64 ? n : 1), *dmm = A.pooled<double>(2);
-    uint8_t *u8 = A.pooled<uint8_t>(n), *th = A.pooled<uint8_t>(n), *er = A.pooled<uint8_t>(n);
-    unsigned *hist = A.pooled<unsigned>(5 * 256);
-    int *decision = A.pooled<int>(2), *offs = A.pooled<int>(2 * 81);
-    std::vector<int> o;
-    for (int dy = -5; dy <= 5; dy++) for (int dx = -5; dx <= 5; dx++) if (dy * dy + dx * dx <= 25) { o.push_back(dy); o.push_back(dx); }         // disk(5): 81
-    const int k = (int)o.size() / 2;
-    A.h2d(offs, A.keep(std::move(o)), sizeof(int) * 2 * k);
-    // gaussian(image, sigma=1): ndi.gaussian_filter, mode 'nearest', truncate 4, the image's float type after each axis
+    uint8_t *er = A.pooled<uint8_t>(n);
+    int rc;
     if (is_f64) {
-        if (!A.h2d(da, img, n * 8)) return TMAT_E_HIP;
-        const GaussTable &gt = gauss_table(c, 1.0, 0, gauss_radius(1.0, 4.0));
-        const double *w = table_dev(c, gt);
-        if (!w) return TMAT_E_HIP;
-        launch_corr1d_f64(da, db, 1, H, W, w, gt.r, gt.sym, EXT_NEAREST, s);
-        launch_corr1d_f64(db, da, (size_t)H, W, 1, w, gt.r, gt.sym, EXT_NEAREST, s);
-        launch_wm_rescale_u8_f64(da, n, dmm, u8, s);
+        double *da = A.pooled_from((const double *)img, n);
+        if (!A.ok) return TMAT_E_HIP;
+        rc = well_threshold_dev(c, da, nullptr, 1, H, W, er, s);
     } else {
-        if (!A.h2d(a, img, n * 4)) return TMAT_E_HIP;
-        if (!gauss_pass_f32(c, a, b, Pass{1.0, 0, H, W, 1}, 4.0, EXT_NEAREST, s) || !gauss_pass_f32(c, b, a, Pass{1.0, 0, W, 1, (size_t)H}, 4.0, EXT_NEAREST, s))
-            return TMAT_E_HIP;
-        launch_minmax_f32(a, 1, n, mm, mm + 1, s);
-        launch_wm_rescale_u8(a, n, mm, mm + 1, u8, s);
+        float *a = A.pooled_from((const float *)img, n);
+        if (!A.ok) return TMAT_E_HIP;
+        rc = well_threshold_dev(c, nullptr, a, 1, H, W, er, s);
     }
-    launch_wm_hist(u8, H, W, hist, s);
-    launch_wm_decide(hist, H, W, decision, s);
-    launch_wm_threshold(u8, n, decision, th, s);
-    launch_wm_erode(th, H, W, offs, k, er, s);
-    A.check(hipGetLastError(), "tmat_well_threshold: kernel launch");
+    if (rc) return rc;
     A.d2h(out, er, n);
     return A.finish();
 }
@@ -485,40 +617,70 @@ static int well_threshold(tmat_handle hd, const void *img, int is_f64, int H, in
 int tmat_well_threshold(tmat_handle hd, const float *img, int H, int W, uint8_t *out) { return well_threshold(hd, img, 0, H, W, out); }
 int tmat_well_threshold_f64(tmat_handle hd, const double *img, int H, int W, uint8_t *out) { return well_threshold(hd, img, 1, H, W, out); }
 
-/* skimage.feature.canny(mask, sigma) of a boolean image with the default thresholds (reference calls:
- * well_mask_generation.py:165, :201): mask (H, W) u8 -> edges u8 */
-int tmat_canny_mask(tmat_handle hd, const uint8_t *mask, int H, int W, double sigma, uint8_t *edges)
+static bool canny_mask_args_ok(int n, int H, int W, double sigma) { return n >= 1 && H >= 3 && W >= 3 && sigma > 0 && sigma <= 16 && (long long)n * H * W <= (1LL << 26); }
+
+/* skimage.feature.canny(mask, sigma) of boolean images with the default thresholds (reference calls:
+ * well_mask_generation.py:165, :201): n masks (n, H, W) u8 -> edges u8, each as from a call of its own */
+int tmat_canny_mask_batch(tmat_handle hd, const uint8_t *masks, int n, int H, int W, double sigma, uint8_t *edges)
 {
     Ctx *c = (Ctx *)hd;
-    if (!c || !mask || !edges || H < 3 || W < 3 || !(sigma > 0) || sigma > 16 || (long long)H * W > (1LL << 26)) { set_error("tmat_canny_mask: bad argument"); return TMAT_E_ARG; }
+    if (!c || !masks || !edges || !canny_mask_args_ok(n, H, W, sigma)) { set_error("tmat_canny_mask: bad argument"); return TMAT_E_ARG; }
     TMAT_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const int r = gauss_radius(sigma, 4.0);
-    const int Hp = H + 2 * r, Wp = W + 2 * r;
-    const size_t npx = (size_t)H * W, npad = (size_t)Hp * Wp;
+    const size_t npx = (size_t)n * H * W;
     DevScope A(c->ws_pool, s);
-    uint8_t *m = A.pooled<uint8_t>(npx), *e = A.pooled<uint8_t>(npx);
-    double *pa = A.pooled<double>(npad), *pb = A.pooled<double>(npad), *pt = A.pooled<double>(npad);
-    CannyWs cw{};
-    cw.sm = A.pooled<double>(npx); cw.t0 = A.pooled<double>(npx); cw.is_ = A.pooled<double>(npx); cw.js = A.pooled<double>(npx); cw.mag = A.pooled<double>(npx);
-    cw.low = A.pooled<uint8_t>(npx); cw.high = A.pooled<uint8_t>(npx); cw.L = A.pooled<int>(npx); cw.flag = A.pooled<int>(npx);
-    double *tabs = A.pooled<double>(6);
-    A.h2d(tabs, A.keep(std::vector<double>{-1.0, 0.0, 1.0, 1.0, 2.0, 1.0}), 6 * sizeof(double));
-    cw.w_diff = tabs; cw.w_smooth = tabs + 3;
-    if (!A.h2d(m, mask, npx)) return TMAT_E_HIP;
-    // gaussian(x, sigma, mode='constant') of the image and of the all-ones mask (0.18.3 smooth_with_function_and_mask): zero padding
-    // by the kernel radius makes the boundary mode irrelevant
-    launch_wm_pad(m, H, W, r, pa, pb, s);
-    const GaussTable &gt = gauss_table(c, sigma, 0, r);
-    const double *w = table_dev(c, gt);
-    if (!w) return TMAT_E_HIP;
-    launch_corr1d_f64(pa, pt, 1, Hp, Wp, w, gt.r, gt.sym, EXT_NEAREST, s);
-    launch_corr1d_f64(pt, pa, (size_t)Hp, Wp, 1, w, gt.r, gt.sym, EXT_NEAREST, s);
-    launch_corr1d_f64(pb, pt, 1, Hp, Wp, w, gt.r, gt.sym, EXT_NEAREST, s);
-    launch_corr1d_f64(pt, pb, (size_t)Hp, Wp, 1, w, gt.r, gt.sym, EXT_NEAREST, s);
-    launch_wm_crop_div(pa, pb, H, W, r, cw.sm, s);
-    if (canny_core_dev(1, H, W, cw, e, s)) { set_error("tmat_canny_mask: kernel launch failed"); return TMAT_E_HIP; }
+    uint8_t *m = A.pooled_from(masks, npx), *e = A.pooled<uint8_t>(npx);
+    if (!A.ok) return TMAT_E_HIP;
+    int rc = canny_mask_dev(c, m, n, H, W, sigma, e, s);
+    if (rc) return rc;
     A.d2h(edges, e, npx);
+    return A.finish();
+}
+
+int tmat_canny_mask(tmat_handle hd, const uint8_t *mask, int H, int W, double sigma, uint8_t *edges) { return tmat_canny_mask_batch(hd, mask, 1, H, W, sigma, edges); }
+
+int tmat_well_small_shape(int h, int w, int *small_h, int *small_w)
+{
+    if (h < 1 || w < 1 || !small_h || !small_w) { set_error("tmat_well_small_shape: bad argument"); return TMAT_E_ARG; }
+    well_small_shape(h, w, small_h, small_w);
+    return TMAT_OK;
+}
+
+int tmat_stack_well_front_dev(tmat_handle hd, const uint16_t *stacks_dev, int n, int Z, int H, int W, int out_h, int out_w, double *proj_aa_out,
+                              uint8_t *thresh_small, uint8_t *border_small)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!c || !stacks_dev || !thresh_small || !border_small || n < 1 || Z < 1 || H < 1 || W < 1 || out_h < 20 || out_w < 20 ||
+        (long long)n * out_h * out_w > (1LL << 26)) {
+        set_error("tmat_stack_well_front_dev: bad argument (n >= 1 stacks, a field of at least 20 x 20)");
+        return TMAT_E_ARG;
+    }
+    TMAT_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int sh, sw;
+    well_small_shape(out_h, out_w, &sh, &sw);
+    if (sh < 3 || sw < 3) { set_error("tmat_stack_well_front_dev: the small mask is below 3 x 3"); return TMAT_E_ARG; }
+    const size_t hw = (size_t)H * W, npx = (size_t)out_h * out_w, spx = (size_t)sh * sw;
+    DevScope A(c->ws_pool, s);
+    uint16_t *proj = A.pooled<uint16_t>((size_t)n * hw);
+    double *aa = A.pooled<double>((size_t)n * npx);
+    uint8_t *th = A.pooled<uint8_t>((size_t)n * npx), *small = A.pooled<uint8_t>((size_t)n * spx), *border = A.pooled<uint8_t>((size_t)n * spx);
+    if (!A.ok) return TMAT_E_HIP;
+    // compute_branches.py:227-238: max projection, anti-aliased resize -- one stack is one image with its own clip range
+    if (zproj_dev(stacks_dev, n, Z, H, W, TMAT_ZPROJ_MAX, proj, s)) { set_error("tmat_stack_well_front_dev: projection failed"); return TMAT_E_HIP; }
+    int rc = stack_resize_aa_dev(c, proj, n, 1, H, W, out_h, out_w, aa, nullptr, s);
+    if (rc) return rc;
+    A.d2h(proj_aa_out, aa, (size_t)n * npx * 8);
+    // generate_well_mask :156-170: threshold, nearest resize to <= 200 px, border of the small mask
+    rc = well_threshold_dev(c, aa, nullptr, n, out_h, out_w, th, s);
+    if (rc) return rc;
+    launch_resize_nearest_u8(th, n, out_h, out_w, sh, sw, small, s);
+    rc = canny_mask_dev(c, small, n, sh, sw, 1.0, border, s);
+    if (rc) return rc;
+    launch_wm_border(small, n, sh, sw, border, s);
+    A.check(hipGetLastError(), "tmat_stack_well_front_dev: kernel launch");
+    A.d2h(thresh_small, small, (size_t)n * spx);
+    A.d2h(border_small, border, (size_t)n * spx);
     return A.finish();
 }
 
@@ -694,18 +856,36 @@ int tmat_stack_pass_plan(int n, int Z, int H, int W, int ds_width, int pass_stac
     return TMAT_OK;
 }
 
-int tmat_analyze_stack_batch(tmat_handle hd, const uint16_t *stacks, int n, int Z, int H, int W, const tmat_stack_opts *o, tmat_row *rows)
+static int analyze_stack_batch_entry(tmat_handle hd, const uint16_t *stacks, bool stacks_on_dev, int n, int Z, int H, int W, const tmat_stack_opts *o, tmat_row *rows)
 {
     Ctx *c = (Ctx *)hd;
-    if (!o || o->size != (uint32_t)sizeof(tmat_stack_opts)) { set_error("tmat_analyze_stack_batch: unknown tmat_stack_opts size"); return TMAT_E_ARG; }
+    static_assert(offsetof(tmat_stack_opts, vis_width) + sizeof(int) == TMAT_STACK_OPTS_SIZE_V1, "the first version of tmat_stack_opts ends with pass_stacks");
+    if (!o || (o->size != (uint32_t)sizeof(tmat_stack_opts) && o->size != TMAT_STACK_OPTS_SIZE_V1)) { set_error("tmat_analyze_stack_batch: unknown tmat_stack_opts size"); return TMAT_E_ARG; }
+    tmat_stack_opts full{};         // a caller of the first version: its fields, no tree request (what follows pass_stacks there is padding)
+    std::memcpy(&full, o, o->size == TMAT_STACK_OPTS_SIZE_V1 ? offsetof(tmat_stack_opts, vis_width) : sizeof(tmat_stack_opts));
+    o = &full;
     if (!c || !stacks || !rows || n < 1 || Z < 2 || H < 2 || W < 2 || o->ds_width < 2 || o->pass_stacks < 0) {
         set_error("tmat_analyze_stack_batch: bad argument (n >= 1 stacks of Z >= 2 slices)");
         return TMAT_E_ARG;
     }
     if (!hessian_ok(o->hessian)) { set_error("tmat_analyze_stack_batch: unknown hessian form"); return TMAT_E_ARG; }
     if (o->n_thresh < 1 || !o->thresh) { set_error("tmat_analyze_stack_batch: needs at least one threshold pair"); return TMAT_E_ARG; }
+    if ((o->bars_out || o->n_bars || o->rgb_out) && (!o->bars_out || !o->n_bars || o->cap_b < 0 || (o->rgb_out && o->vis_width < 1))) {
+        set_error("tmat_analyze_stack_batch: a tree request needs bars_out, n_bars, cap_b >= 0 and, with rgb_out, vis_width >= 1");
+        return TMAT_E_ARG;
+    }
     TMAT_HIP(hipSetDevice(c->device));
-    return analyze_stack_batch(c, stacks, n, Z, H, W, *o, rows);
+    return analyze_stack_batch(c, stacks, stacks_on_dev, n, Z, H, W, *o, rows);
+}
+
+int tmat_analyze_stack_batch(tmat_handle hd, const uint16_t *stacks, int n, int Z, int H, int W, const tmat_stack_opts *o, tmat_row *rows)
+{
+    return analyze_stack_batch_entry(hd, stacks, false, n, Z, H, W, o, rows);
+}
+
+int tmat_analyze_stack_batch_dev(tmat_handle hd, const uint16_t *stacks_dev, int n, int Z, int H, int W, const tmat_stack_opts *o, tmat_row *rows)
+{
+    return analyze_stack_batch_entry(hd, stacks_dev, true, n, Z, H, W, o, rows);
 }
 
 int tmat_vessel_field_batch(tmat_handle hd, const float *vols, int n, int Z, int hh, int ww, int hessian, float *fields, const tmat_vessel_stages *stages)

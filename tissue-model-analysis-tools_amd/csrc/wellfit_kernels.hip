@@ -162,6 +162,10 @@ __global__ __launch_bounds__(SE_BLOCK) void se_resize_nearest_kernel(const uint8
 }
 
 static inline unsigned se_blocks(size_t n) { const size_t b = (n + SE_BLOCK - 1) / SE_BLOCK; return (unsigned)(b < 4096 ? (b ? b : 1) : 4096); }
+void launch_resize_nearest_u8(const uint8_t *in, int n_img, int H, int W, int oh, int ow, uint8_t *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(se_resize_nearest_kernel, dim3(se_blocks((size_t)oh * ow), n_img), dim3(SE_BLOCK), 0, s, in, H, W, oh, ow, out);
+}
 
 // The two places the well mask enters the masked batch pipeline (pipeline.cpp; compute_branches.py:328, :334).
 // img * well_mask on the rescaled image: x >= 0 there, so selecting +0.0f equals the reference's float32 * bool product bit for bit

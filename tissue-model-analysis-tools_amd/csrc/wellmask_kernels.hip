@@ -9,12 +9,16 @@
 //   canny(mask) (:165, :201): gaussian(sigma 1, mode="constant") of the mask and of an all-ones image by zero padding, their
 //   quotient, then the sobel / non-maximum suppression / hysteresis kernels of sato_kernels.hip.
 // oracle/wellmask.py restates the same steps with numpy / scipy and is pinned to the reference by tests/golden/wellmask.npz.
+//
+// Every stage takes n images of one shape in one launch: the image is blockIdx.y, and what the reference computes per image -- extrema,
+// the five histograms, corner medians, the Otsu decision, the borders of the erosion and of canny's padding -- is indexed by it, so an
+// image leaves a batch exactly as it leaves a launch of its own (the Z-stack batch front end, tmat_stack_well_front_dev).
 #include "tmat_internal.h"
 #include "wellmask.h"
 
 namespace tmat {
 
-static inline dim3 wm_grid(size_t n) { const size_t b = (n + 255) / 256; return dim3((unsigned)(b < 4096 ? (b ? b : 1) : 4096)); }
+static inline dim3 wm_grid(size_t n, int n_img = 1) { const size_t b = (n + 255) / 256; return dim3((unsigned)(b < 4096 ? (b ? b : 1) : 4096), (unsigned)n_img); }
 #define WM_LOOP(p, n) for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < (n); p += (size_t)gridDim.x * blockDim.x)
 
 // exposure.py:rescale_intensity on a float32 image: ((x - min) / float32(max - min)) * 255 in float32, widened, truncated
@@ -43,6 +47,8 @@ void launch_wm_rescale_u8(const float *blur, size_t n, const float *mn, const fl
 __global__ __launch_bounds__(1024) void wm_minmax_f64_kernel(const double *__restrict__ x, size_t n, double *__restrict__ mm)
 {
     __shared__ double smn[16], smx[16];
+    x += (size_t)blockIdx.x * n;            // one workgroup per image
+    mm += 2 * (size_t)blockIdx.x;
     double lo = __builtin_inf(), hi = -__builtin_inf();
     for (size_t p = threadIdx.x; p < n; p += 1024) { const double v = x[p]; lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
     for (int o = 32; o > 0; o >>= 1) { const double a = __shfl_down(lo, o), b = __shfl_down(hi, o); lo = a < lo ? a : lo; hi = b > hi ? b : hi; }
@@ -55,6 +61,7 @@ __global__ __launch_bounds__(1024) void wm_minmax_f64_kernel(const double *__res
 }
 __global__ void wm_rescale_u8_f64_kernel(const double *__restrict__ x, size_t n, const double *__restrict__ mm, uint8_t *__restrict__ out)
 {
+    x += (size_t)blockIdx.y * n; out += (size_t)blockIdx.y * n; mm += 2 * (size_t)blockIdx.y;
     const double lo = mm[0], hi = mm[1], rng = hi - lo;
     WM_LOOP(p, n) {
         double v = fmin(fmax(x[p], lo), hi);
@@ -67,15 +74,16 @@ __global__ void wm_rescale_u8_f64_kernel(const double *__restrict__ x, size_t n,
         out[p] = (uint8_t)(int)v;
     }
 }
-void launch_wm_rescale_u8_f64(const double *blur, size_t n, double *mm, uint8_t *out, hipStream_t s)
+void launch_wm_rescale_u8_f64(const double *blur, int n_img, size_t n, double *mm, uint8_t *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(wm_minmax_f64_kernel, dim3(1), dim3(1024), 0, s, blur, n, mm);
-    hipLaunchKernelGGL(wm_rescale_u8_f64_kernel, wm_grid(n), dim3(256), 0, s, blur, n, mm, out);
+    hipLaunchKernelGGL(wm_minmax_f64_kernel, dim3(n_img), dim3(1024), 0, s, blur, n, mm);
+    hipLaunchKernelGGL(wm_rescale_u8_f64_kernel, wm_grid(n, n_img), dim3(256), 0, s, blur, n, mm, out);
 }
 
 __global__ __launch_bounds__(256) void wm_hist_kernel(const uint8_t *__restrict__ img, int H, int W, unsigned *__restrict__ hist)
 {
     __shared__ unsigned h[5 * 256];
+    img += (size_t)blockIdx.y * H * W; hist += 5 * 256 * (size_t)blockIdx.y;
     for (int i = threadIdx.x; i < 5 * 256; i += 256) h[i] = 0;
     __syncthreads();
     const int xl = (int)(H * 0.05), xr = (int)(H * 0.95), yt = (int)(W * 0.05), yb = (int)(W * 0.95);
@@ -92,10 +100,10 @@ __global__ __launch_bounds__(256) void wm_hist_kernel(const uint8_t *__restrict_
     __syncthreads();
     for (int i = threadIdx.x; i < 5 * 256; i += 256) if (h[i]) atomicAdd(&hist[i], h[i]);
 }
-void launch_wm_hist(const uint8_t *img, int H, int W, unsigned *hist, hipStream_t s)
+void launch_wm_hist(const uint8_t *img, int n_img, int H, int W, unsigned *hist, hipStream_t s)
 {
-    hipMemsetAsync(hist, 0, 5 * 256 * sizeof(unsigned), s);
-    hipLaunchKernelGGL(wm_hist_kernel, wm_grid((size_t)H * W), dim3(256), 0, s, img, H, W, hist);
+    hipMemsetAsync(hist, 0, (size_t)n_img * 5 * 256 * sizeof(unsigned), s);
+    hipLaunchKernelGGL(wm_hist_kernel, wm_grid((size_t)H * W, n_img), dim3(256), 0, s, img, H, W, hist);
 }
 
 // np.median of the values counted in h[0..255] (n > 0): the middle value, or the mean of the two middle values
@@ -115,10 +123,13 @@ __device__ double wm_median(const unsigned *h)
     return ((double)a + (double)b) / 2.0;       // np.median: mean of the two middle elements (equal for odd n)
 }
 
-// one thread: the whole decision is a few thousand scalar operations on 1280 counters
+// one thread per image (one workgroup each): the whole decision is a few thousand scalar operations on 1280 counters.  The reversed
+// cumulative sums live in LDS: as private arrays they were 4 KiB of scratch per lane
 __global__ void wm_decide_kernel(const unsigned *__restrict__ hist, int H, int W, int *__restrict__ decision)
 {
-    if (blockIdx.x || threadIdx.x) return;
+    __shared__ double w2[256], s2[256];
+    if (threadIdx.x) return;
+    hist += 5 * 256 * (size_t)blockIdx.x; decision += 2 * (size_t)blockIdx.x;
     int lo = 0, hi = 255;
     while (lo < 255 && hist[lo] == 0) lo++;
     while (hi > 0 && hist[hi] == 0) hi--;
@@ -144,7 +155,6 @@ __global__ void wm_decide_kernel(const unsigned *__restrict__ hist, int H, int W
     }
     // weight2 / mean2 come from cumulative sums of the REVERSED arrays: accumulate from the top
     // (two passes over 256 bins: keep the reversed cumulative sums in registers by walking k downwards first)
-    double w2[256], s2[256];
     {
         double cw = 0.0, cs = 0.0;
         for (int k = nb - 1; k >= 0; k--) {
@@ -168,26 +178,28 @@ __global__ void wm_decide_kernel(const unsigned *__restrict__ hist, int H, int W
     (void)total_w; (void)total_m;
     decision[0] = ilo + arg;
 }
-void launch_wm_decide(const unsigned *hist, int H, int W, int *decision, hipStream_t s)
+void launch_wm_decide(const unsigned *hist, int n_img, int H, int W, int *decision, hipStream_t s)
 {
-    hipLaunchKernelGGL(wm_decide_kernel, dim3(1), dim3(64), 0, s, hist, H, W, decision);
+    hipLaunchKernelGGL(wm_decide_kernel, dim3(n_img), dim3(64), 0, s, hist, H, W, decision);
 }
 
 __global__ void wm_threshold_kernel(const uint8_t *__restrict__ img, size_t n, const int *__restrict__ decision, uint8_t *__restrict__ out)
 {
+    img += (size_t)blockIdx.y * n; out += (size_t)blockIdx.y * n; decision += 2 * (size_t)blockIdx.y;
     const int t = decision[0], inv = decision[1];
     WM_LOOP(p, n) {
         const int v = inv ? 255 - (int)img[p] : (int)img[p];
         out[p] = v >= t;
     }
 }
-void launch_wm_threshold(const uint8_t *img, size_t n, const int *decision, uint8_t *out, hipStream_t s)
+void launch_wm_threshold(const uint8_t *img, int n_img, size_t n, const int *decision, uint8_t *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(wm_threshold_kernel, wm_grid(n), dim3(256), 0, s, img, n, decision, out);
+    hipLaunchKernelGGL(wm_threshold_kernel, wm_grid(n, n_img), dim3(256), 0, s, img, n, decision, out);
 }
 
 __global__ void wm_erode_kernel(const uint8_t *__restrict__ m, int H, int W, const int *__restrict__ off, int noff, uint8_t *__restrict__ out)
 {
+    m += (size_t)blockIdx.y * H * W; out += (size_t)blockIdx.y * H * W;
     WM_LOOP(p, (size_t)H * W) {
         const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
         bool acc = true;
@@ -198,14 +210,15 @@ __global__ void wm_erode_kernel(const uint8_t *__restrict__ m, int H, int W, con
         out[p] = acc;
     }
 }
-void launch_wm_erode(const uint8_t *m, int H, int W, const int *off, int noff, uint8_t *out, hipStream_t s)
+void launch_wm_erode(const uint8_t *m, int n_img, int H, int W, const int *off, int noff, uint8_t *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(wm_erode_kernel, wm_grid((size_t)H * W), dim3(256), 0, s, m, H, W, off, noff, out);
+    hipLaunchKernelGGL(wm_erode_kernel, wm_grid((size_t)H * W, n_img), dim3(256), 0, s, m, H, W, off, noff, out);
 }
 
 __global__ void wm_pad_kernel(const uint8_t *__restrict__ m, int H, int W, int r, double *__restrict__ a, double *__restrict__ b)
 {
     const int Hp = H + 2 * r, Wp = W + 2 * r;
+    m += (size_t)blockIdx.y * H * W; a += (size_t)blockIdx.y * Hp * Wp; b += (size_t)blockIdx.y * Hp * Wp;
     WM_LOOP(p, (size_t)Hp * Wp) {
         const int y = (int)(p / Wp) - r, x = (int)(p % Wp) - r;
         const bool in = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
@@ -213,22 +226,44 @@ __global__ void wm_pad_kernel(const uint8_t *__restrict__ m, int H, int W, int r
         b[p] = in ? 1.0 : 0.0;
     }
 }
-void launch_wm_pad(const uint8_t *m, int H, int W, int r, double *img_pad, double *ones_pad, hipStream_t s)
+void launch_wm_pad(const uint8_t *m, int n_img, int H, int W, int r, double *img_pad, double *ones_pad, hipStream_t s)
 {
-    hipLaunchKernelGGL(wm_pad_kernel, wm_grid((size_t)(H + 2 * r) * (W + 2 * r)), dim3(256), 0, s, m, H, W, r, img_pad, ones_pad);
+    hipLaunchKernelGGL(wm_pad_kernel, wm_grid((size_t)(H + 2 * r) * (W + 2 * r), n_img), dim3(256), 0, s, m, H, W, r, img_pad, ones_pad);
 }
 __global__ void wm_crop_div_kernel(const double *__restrict__ a, const double *__restrict__ b, int H, int W, int r, double *__restrict__ out)
 {
     const int Wp = W + 2 * r;
+    const size_t pad_img = (size_t)blockIdx.y * (H + 2 * r) * Wp;
+    a += pad_img; b += pad_img; out += (size_t)blockIdx.y * H * W;
     WM_LOOP(p, (size_t)H * W) {
         const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
         const size_t q = (size_t)(y + r) * Wp + x + r;
         out[p] = a[q] / (b[q] + 2.220446049250313e-16);
     }
 }
-void launch_wm_crop_div(const double *img_pad, const double *ones_pad, int H, int W, int r, double *out, hipStream_t s)
+void launch_wm_crop_div(const double *img_pad, const double *ones_pad, int n_img, int H, int W, int r, double *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(wm_crop_div_kernel, wm_grid((size_t)H * W), dim3(256), 0, s, img_pad, ones_pad, H, W, r, out);
+    hipLaunchKernelGGL(wm_crop_div_kernel, wm_grid((size_t)H * W, n_img), dim3(256), 0, s, img_pad, ones_pad, H, W, r, out);
+}
+
+// well_mask_generation.py:165-170, :201-205: the mask's own pixels on the image border join canny's edges
+__global__ void wm_border_kernel(const uint8_t *__restrict__ m, int H, int W, uint8_t *__restrict__ edges)
+{
+    m += (size_t)blockIdx.y * H * W; edges += (size_t)blockIdx.y * H * W;
+    const int per = 2 * W + 2 * H;          // row 0, row H - 1, column 0, column W - 1 (corners twice: an OR)
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < per; q += gridDim.x * blockDim.x) {
+        int y, x;
+        if (q < W) { y = 0; x = q; }
+        else if (q < 2 * W) { y = H - 1; x = q - W; }
+        else if (q < 2 * W + H) { y = q - 2 * W; x = 0; }
+        else { y = q - 2 * W - H; x = W - 1; }
+        const size_t p = (size_t)y * W + x;
+        if (m[p]) edges[p] = 1;
+    }
+}
+void launch_wm_border(const uint8_t *m, int n_img, int H, int W, uint8_t *edges, hipStream_t s)
+{
+    hipLaunchKernelGGL(wm_border_kernel, wm_grid((size_t)2 * W + 2 * H, n_img), dim3(256), 0, s, m, H, W, edges);
 }
 
 }  // namespace tmat

@@ -20,6 +20,7 @@ without --image-width-microns (or the config key) the width comes from OME / Ima
 """
 import argparse
 import csv
+import ctypes as C
 import json
 import os
 import sys
@@ -238,10 +239,21 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
     suffix_of = {(cfg["thresh1"], cfg["thresh2"]): sfx for cfg, sfx in grid}
     ids = sorted(paths)
     fields = {}
-    # Batch path (tmat_analyze_stack_batch): consecutive stacks of one shape and width go through the device stages together, the host
-    # graph stage of a pass runs beside the device stages of the next, the threshold grid is swept from fields that stay in HBM.
-    # TMAT_STACK_BATCH=0 keeps every stack on the per-stack path; --tree-visualizations and stacks of a unique shape always take it.
-    batch_on = os.environ.get("TMAT_STACK_BATCH", STACK_BATCH_DEFAULT) != "0" and not tree_vis
+    # Batch path (tmat_analyze_stack_batch_dev): consecutive stacks of one shape and width are uploaded once and go through the device
+    # stages together, the host graph stage of a pass runs beside the device stages of the next, the threshold grid is swept from fields
+    # that stay in HBM; --detect-well makes its masks from the resident chunk (sato.stack_well_masks_batch) and --tree-visualizations
+    # takes geometry and overlays out of the same call.  TMAT_STACK_BATCH=0 keeps every stack on the per-stack path; stacks of a unique
+    # shape always take it.
+    batch_on = os.environ.get("TMAT_STACK_BATCH", STACK_BATCH_DEFAULT) != "0"
+
+    def save_well_mask(img_id, well):
+        # compute_branches.py:239-241 well_mask.png, from the masks the analysis itself uses
+        (out_root / "visualizations" / img_id).mkdir(parents=True, exist_ok=True)
+        if encoder is not None:
+            (out_root / "visualizations" / img_id / "well_mask.png").write_bytes(encoder((well * 255).astype(np.uint8))[0])
+        else:
+            from PIL import Image
+            Image.fromarray((well * 255).astype(np.uint8)).save(out_root / "visualizations" / img_id / "well_mask.png")
 
     def load_fn(img_id):
         try:
@@ -263,25 +275,48 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
         return width_um
 
     def analyze_batch_fn(batch, width_um, thresh, ids):
-        # one call for the whole chunk and the whole grid; run_sharded then asks configuration by configuration
+        # one upload and one pass over the whole chunk and the whole grid; run_sharded then asks configuration by configuration
         if fields.get("batch") is not batch:
             fields.clear()
             fields["batch"] = batch
             sw_px, min_px, max_px = branches.graph_px_params(config, DOWNSAMPLE_WIDTH, width_um)
-            pruning = None
-            if detect_well:
-                out_hw = sato.dsamp_shape(batch.shape, DOWNSAMPLE_WIDTH)
-                pruning = np.stack([sato.stack_well_masks(handle, st, out_hw, well_seed)[1] for st in batch])
             pairs = [(cfg["thresh1"], cfg["thresh2"]) for cfg, _ in grid]
-            res = sato.analyze_stack_batch(handle, batch, pairs, sw_px, min_px, max_px, bool(config.get("remove_isolated_branches", False)),
-                                           DOWNSAMPLE_WIDTH, hessian, pruning_masks=pruning, return_pictures=vis)
-            rows_all, pics = res if vis else (res, None)
+            n, per = len(batch), batch[0].size
+            rows_all = [[] for _ in pairs]
+            with sato.upload_stacks(handle, batch) as dev:
+                pruning = None
+                if detect_well:
+                    well, pruning = sato.stack_well_masks_batch(handle, dev, sato.dsamp_shape(batch.shape, DOWNSAMPLE_WIDTH), well_seed)
+                    if vis:
+                        for i, img_id in enumerate(ids):
+                            save_well_mask(img_id, well[i])
+                # the overlays of one call stay under a gigabyte of host memory, as on the 2-D route
+                vh, vw = _lib.tree_canvas_shape(batch.shape[2], batch.shape[3], vis_width)
+                step = branches.grid_images_per_call(len(pairs), vh * vw * 3) if tree_vis else n
+                for i0 in range(0, n, step):
+                    k = min(step, n - i0)
+                    part = (C.c_void_p(dev.ptr.value + i0 * per * 2), (k,) + batch.shape[1:])
+                    res = sato.analyze_stack_batch(handle, part, pairs, sw_px, min_px, max_px, bool(config.get("remove_isolated_branches", False)),
+                                                   DOWNSAMPLE_WIDTH, hessian, pruning_masks=None if pruning is None else pruning[i0:i0 + k],
+                                                   return_pictures=vis, tree=tree_vis, vis_width=vis_width)
+                    res = res if isinstance(res, tuple) else (res,)
+                    for t in range(len(pairs)):
+                        rows_all[t] += res[0][t]
+                    if vis:
+                        for i, img_id in enumerate(ids[i0:i0 + k]):
+                            vis_dir = out_root / "visualizations" / img_id
+                            branches._save_png_unique(res[1][0][i], vis_dir, "original_image.png", encoder)
+                            branches._save_png_unique(res[1][1][i], vis_dir, "vesselness_image.png", encoder)
+                    if tree_vis:
+                        # compute_branches.py:431-450: the files of every configuration, written while this call's overlays are held
+                        for t, pair in enumerate(pairs):
+                            for i, img_id in enumerate(ids[i0:i0 + k]):
+                                bars = res[-1]["bars"][t][i]
+                                if len(bars) == 0:
+                                    print(f"No branches found for {img_id}.", flush=True)
+                                branches.save_tree_pictures(res[-1]["overlays"][t][i], bars, out_root / "visualizations" / img_id, suffix_of[pair],
+                                                            vis_width, encoder)
             fields["rows"] = {pair: rows_all[t] for t, pair in enumerate(pairs)}
-            if vis:
-                for i, img_id in enumerate(ids):
-                    vis_dir = out_root / "visualizations" / img_id
-                    branches._save_png_unique(pics[0][i], vis_dir, "original_image.png", encoder)
-                    branches._save_png_unique(pics[1][i], vis_dir, "vesselness_image.png", encoder)
         return [(i,) + tuple(r) for i, r in enumerate(fields["rows"][thresh])]
 
     def analyze_fn(batch, width_um, thresh, input_bits, ids):
@@ -297,7 +332,11 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
             if i not in fields:
                 field = sato.stack_field(handle, st, DOWNSAMPLE_WIDTH, hessian)
                 # --detect-well (compute_branches.py:231-243): the well mask of the resized max projection only prunes the graph here
-                pruning = sato.stack_well_masks(handle, st, field.shape, well_seed)[1] if detect_well else None
+                pruning = None
+                if detect_well:
+                    well, pruning = sato.stack_well_masks(handle, st, field.shape, well_seed)
+                    if vis:
+                        save_well_mask(ids[i], well)
                 fields[i] = (field, pruning)
                 if vis:
                     # compute_branches.py:228-229 original_image.png = the max projection, :303 vesselness_image.png: save_vis of the field
@@ -318,26 +357,14 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
                                                   encoder)
         return rows
 
-    def load_and_keep(img_id):
-        st = load_fn(img_id)
-        if vis and detect_well:
-            (out_root / "visualizations" / img_id).mkdir(parents=True, exist_ok=True)
-            well = sato.stack_well_masks(handle, st, sato.dsamp_shape(st.shape, DOWNSAMPLE_WIDTH), well_seed)[0]
-            if encoder is not None:
-                (out_root / "visualizations" / img_id / "well_mask.png").write_bytes(encoder((well * 255).astype(np.uint8))[0])
-            else:
-                from PIL import Image
-                Image.fromarray((well * 255).astype(np.uint8)).save(out_root / "visualizations" / img_id / "well_mask.png")
-        return st
-
     def stack_chunk_ends(held_keys, key, st):
-        # sato.chunk_stacks' rule on the stream of loaded stacks: one key per chunk, at most 8 stacks, the pass's device bytes under the budget
-        nb = sato.stack_pass_plan(1, st.shape[0], st.shape[1], st.shape[2], DOWNSAMPLE_WIDTH)[1]
-        return sato.chunk_ends(held_keys[0], len(held_keys), nb * len(held_keys), key, nb)
+        # sato.chunk_stacks' rule on the stream of loaded stacks: one key per chunk, at most 8 stacks, the pass's device bytes plus the
+        # resident chunk under the budget
+        return sato.stack_chunk_ends(held_keys, key, st.shape, DOWNSAMPLE_WIDTH)
 
     # per-stack path: one stack per analysis call (chunk=1): a stack is the unit the reference streams, and it can be gigabytes
     try:
-        gathered = branches.run_sharded(ids, load_and_keep, width_fn, analyze_fn, config, rank, ws, chunk=sato.STACK_PASS_MAX if batch_on else 1,
+        gathered = branches.run_sharded(ids, load_fn, width_fn, analyze_fn, config, rank, ws, chunk=sato.STACK_PASS_MAX if batch_on else 1,
                                         log=lambda m: print(m, flush=True), pass_ids=True, chunk_ends=stack_chunk_ends if batch_on else None)
     except distributed.RankFailed:
         handle.close()

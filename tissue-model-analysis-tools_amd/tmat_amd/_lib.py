@@ -48,7 +48,11 @@ class StackOpts(C.Structure):
     _fields_ = [("size", C.c_uint32), ("ds_width", C.c_int), ("hessian", C.c_int), ("n_thresh", C.c_int), ("thresh", C.c_void_p),
                 ("smoothing_window_px", C.c_int), ("min_branch_length_px", C.c_int), ("max_branch_length_px", C.c_int), ("remove_isolated", C.c_int),
                 ("first_index", C.c_int64), ("pruning_masks", C.c_void_p), ("fields_out", C.c_void_p), ("proj_pic_out", C.c_void_p),
-                ("field_pic_out", C.c_void_p), ("pass_stacks", C.c_int)]
+                ("field_pic_out", C.c_void_p), ("pass_stacks", C.c_int),
+                ("vis_width", C.c_int), ("rgb_out", C.c_void_p), ("bars_out", C.c_void_p), ("cap_b", C.c_int), ("n_bars", C.c_void_p)]
+
+
+STACK_OPTS_SIZE_V1 = 88              # TMAT_STACK_OPTS_SIZE_V1: the struct before the tree request, still accepted
 
 
 STACK_PASS_MAX = 8                   # TMAT_STACK_PASS_MAX
@@ -119,6 +123,7 @@ def lib():
     L.tmat_field_stats_pruned.argtypes = [vp, vp, i, i, f, f, i, i, i, i, vp, C.c_int64, vp]
     L.tmat_resize_aa_u16.argtypes = [vp, vp, i, i, i, i, i, vp]
     L.tmat_analyze_stack_batch.argtypes = [vp, vp, i, i, i, i, C.POINTER(StackOpts), vp]
+    L.tmat_analyze_stack_batch_dev.argtypes = L.tmat_analyze_stack_batch.argtypes
     L.tmat_vessel_field_batch.argtypes = [vp, vp, i, i, i, i, i, vp, vp]
     L.tmat_stack_pass_plan.argtypes = [i, i, i, i, i, i, C.POINTER(i), C.POINTER(C.c_uint64)]
     L.tmat_debug_stack_trace.argtypes = [vp, i, C.POINTER(i), vp, vp]
@@ -141,6 +146,9 @@ def lib():
     L.tmat_well_threshold.argtypes = [vp, vp, i, i, vp]
     L.tmat_well_threshold_f64.argtypes = [vp, vp, i, i, vp]
     L.tmat_canny_mask.argtypes = [vp, vp, i, i, C.c_double, vp]
+    L.tmat_canny_mask_batch.argtypes = [vp, vp, i, i, i, C.c_double, vp]
+    L.tmat_well_small_shape.argtypes = [i, i, C.POINTER(i), C.POINTER(i)]
+    L.tmat_stack_well_front_dev.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp, vp]
     L.tmat_superellipse_table.argtypes = [vp, vp, i]
     L.tmat_superellipse_search.argtypes = [vp, vp, vp, i, vp, vp, vp, i, C.POINTER(i)]
     L.tmat_superellipse_masks.argtypes = [vp, vp, i, vp, vp, vp, i, i, vp, vp, i, C.POINTER(i)]
@@ -191,6 +199,7 @@ EXPORTS = [
     "tmat_host_png_encode_batch", "tmat_render_tree_png",
     "tmat_analyze_stack_batch", "tmat_vessel_field_batch", "tmat_stack_pass_plan", "tmat_debug_stack_trace",
     "tmat_analyze_batch_grid", "tmat_analyze_batch_grid_dev", "tmat_render_barcode", "tmat_render_barcode_png", "tmat_host_barcode_rects",
+    "tmat_analyze_stack_batch_dev", "tmat_canny_mask_batch", "tmat_well_small_shape", "tmat_stack_well_front_dev",
 ]
 
 

@@ -196,6 +196,20 @@ def chunk_ends(cur_key, cur_len, cur_bytes, key, nbytes, budget=STACK_PASS_BUDGE
     return key != cur_key or cur_len >= max_stacks or cur_bytes + nbytes > budget
 
 
+def stack_chunk_bytes(shape, ds_width=384):
+    """device bytes one stack of (Z, H, W) adds to a chunk of compute_branches.py's batch path: what a pass takes for it
+    (tmat_stack_pass_plan) plus its uint16 copy in the chunk that stays resident for the whole call"""
+    Z, H, W = (int(v) for v in shape)
+    return stack_pass_plan(1, Z, H, W, ds_width)[1] + Z * H * W * 2
+
+
+def stack_chunk_ends(held_keys, key, shape, ds_width=384, budget=STACK_PASS_BUDGET, max_stacks=STACK_PASS_MAX):
+    """chunk_ends for the stream of loaded stacks: does the held chunk (held_keys, one key per stack, all equal) end before a stack of
+    `key` and `shape`?  Every stack counts stack_chunk_bytes"""
+    nb = stack_chunk_bytes(shape, ds_width)
+    return chunk_ends(held_keys[0], len(held_keys), nb * len(held_keys), key, nb, budget, max_stacks)
+
+
 def chunk_stacks(keys, nbytes, budget=STACK_PASS_BUDGET, max_stacks=STACK_PASS_MAX):
     """Grouping rule of compute_branches.py's Z-stack path, as a pure function.  keys[i]: what must be equal for stacks to share a batch
     call ((Z, H, W) and the width in microns); nbytes[i]: device bytes of stack i in a pass.  Consecutive stacks with equal keys form a
@@ -213,19 +227,82 @@ def chunk_stacks(keys, nbytes, budget=STACK_PASS_BUDGET, max_stacks=STACK_PASS_M
     return chunks
 
 
-def analyze_stack_batch(handle: Handle, stacks, thresh_pairs, smoothing_window_px, min_branch_length_px, max_branch_length_px=None,
-                        remove_isolated=False, ds_width=384, hessian="gaussian_derivatives", first_index=0, pruning_masks=None,
-                        return_fields=False, return_pictures=False, pass_stacks=0):
-    """tmat_analyze_stack_batch: n stacks of one shape (n, Z, H, W) and a list of (graph_thresh_1, graph_thresh_2) pairs ->
-    rows[t][i] = (count, total_px, avg_px) of stack i at pair t [, fields (n, fh, fw) float32][, (projection pictures (n, H, W) uint8,
-    field pictures (n, fh, fw) uint8)].  pruning_masks: None or (n, fh, fw) bool, MorseGraph's pruning mask per stack"""
+class DevStacks:
+    """n Z stacks of one shape resident in device memory: `ptr` (a tmat_dev_alloc block of n Z H W uint16) and `shape` (n, Z, H, W).
+    upload_stacks makes one; analyze_stack_batch and stack_well_masks_batch take it in place of an array and only read it."""
+
+    def __init__(self, handle: Handle, ptr_, shape):
+        self.handle, self.ptr, self.shape = handle, ptr_, tuple(int(v) for v in shape)
+
+    @property
+    def nbytes(self):
+        return int(np.prod(self.shape)) * 2
+
+    def download(self) -> np.ndarray:
+        out = np.empty(self.shape, np.uint16)
+        check(lib().tmat_dev_download(self.handle.raw, ptr(out), self.ptr, out.nbytes), "tmat_dev_download")
+        return out
+
+    def free(self):
+        if self.ptr is not None:
+            check(lib().tmat_dev_free(self.handle.raw, self.ptr), "tmat_dev_free")
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+def upload_stacks(handle: Handle, stacks) -> DevStacks:
+    """(n, Z, H, W) uint8 / uint16 stacks -> DevStacks (one upload); free() it, or use it as a context manager"""
     a = np.asarray(stacks)
     if a.ndim != 4 or a.dtype not in (np.uint8, np.uint16):
         raise ValueError("Z stacks: expected (n, Z, H, W) uint8 or uint16")
     a = np.ascontiguousarray(a, np.uint16)
-    n, Z, H, W = a.shape
-    out_hw = dsamp_shape(a.shape, ds_width)
-    install_gaussian_tables(handle, a.shape[2:], out_hw)
+    d = C.c_void_p()
+    check(lib().tmat_dev_alloc(handle.raw, a.nbytes, C.byref(d)), "tmat_dev_alloc")
+    dev = DevStacks(handle, d, a.shape)
+    try:
+        check(lib().tmat_dev_upload(handle.raw, d, ptr(a), a.nbytes), "tmat_dev_upload")
+    except Exception:
+        dev.free()
+        raise
+    return dev
+
+
+def _stacks_arg(stacks):
+    """array, DevStacks or (device pointer, (n, Z, H, W)) -> (what the C entry takes, shape, resident?, the array to keep alive)"""
+    if isinstance(stacks, DevStacks):
+        return stacks.ptr, stacks.shape, True, None
+    if isinstance(stacks, tuple) and len(stacks) == 2 and not isinstance(stacks[0], np.ndarray):
+        shape = tuple(int(v) for v in stacks[1])
+        if len(shape) != 4:
+            raise ValueError("Z stacks on the device: expected (pointer, (n, Z, H, W))")
+        return stacks[0], shape, True, None
+    a = np.asarray(stacks)
+    if a.ndim != 4 or a.dtype not in (np.uint8, np.uint16):
+        raise ValueError("Z stacks: expected (n, Z, H, W) uint8 or uint16")
+    a = np.ascontiguousarray(a, np.uint16)
+    return ptr(a), a.shape, False, a
+
+
+def analyze_stack_batch(handle: Handle, stacks, thresh_pairs, smoothing_window_px, min_branch_length_px, max_branch_length_px=None,
+                        remove_isolated=False, ds_width=384, hessian="gaussian_derivatives", first_index=0, pruning_masks=None,
+                        return_fields=False, return_pictures=False, pass_stacks=0, tree=False, vis_width=2000, overlays=True, cap_bars=4096):
+    """tmat_analyze_stack_batch: n stacks of one shape (n, Z, H, W) and a list of (graph_thresh_1, graph_thresh_2) pairs ->
+    rows[t][i] = (count, total_px, avg_px) of stack i at pair t [, fields (n, fh, fw) float32][, (projection pictures (n, H, W) uint8,
+    field pictures (n, fh, fw) uint8)].  pruning_masks: None or (n, fh, fw) bool, MorseGraph's pruning mask per stack.
+    stacks: an array, or stacks resident in device memory (a DevStacks, or (device pointer, shape)): tmat_analyze_stack_batch_dev, which
+    leaves that buffer as it was.
+    tree: the tree request of tmat_stack_opts; the last element of the result is then {"bars": bars[t][i] (k, 2) float64, scaled by
+    W / fw as field_tree scales them, "overlays": (n_thresh, n, vh, vw, 3) uint8 or None (overlays=False: geometry only)}.  cap_bars: the
+    bars an item may have in the first attempt; the call is repeated once with fh * fw, which always suffices"""
+    src, shape, resident, _keep = _stacks_arg(stacks)
+    n, Z, H, W = shape
+    out_hw = dsamp_shape(shape, ds_width)
+    install_gaussian_tables(handle, shape[2:], out_hw)
     th = np.ascontiguousarray(thresh_pairs, np.float32).reshape(-1, 2)
     o = StackOpts()
     o.size = C.sizeof(StackOpts)
@@ -248,12 +325,35 @@ def analyze_stack_batch(handle: Handle, stacks, thresh_pairs, smoothing_window_p
         pics = (np.empty((n, H, W), np.uint8), np.empty((n,) + tuple(out_hw), np.uint8))
         o.proj_pic_out, o.field_pic_out = pics[0].ctypes.data, pics[1].ctypes.data
     rows = (Row * (max(len(th), 1) * n))()
-    check(lib().tmat_analyze_stack_batch(handle.raw, ptr(a), n, Z, H, W, C.byref(o), rows), "tmat_analyze_stack_batch")
+    entry = lib().tmat_analyze_stack_batch_dev if resident else lib().tmat_analyze_stack_batch
+    what = "tmat_analyze_stack_batch_dev" if resident else "tmat_analyze_stack_batch"
+    T = max(len(th), 1)
+    rgb = nb = bars = None
+    if tree:
+        from ._lib import E_CAP, tree_canvas_shape
+        nb = np.zeros((T, n), np.int32)
+        o.n_bars = nb.ctypes.data
+        if overlays:
+            vh, vw = tree_canvas_shape(H, W, vis_width)
+            rgb = np.empty((T, n, vh, vw, 3), np.uint8)
+            o.vis_width, o.rgb_out = int(vis_width), rgb.ctypes.data
+        full = out_hw[0] * out_hw[1]          # a branch holds at least one vertex of its own
+        for cap in (int(cap_bars), max(int(cap_bars), full)):
+            bars = np.empty((T, n, cap, 2), np.float64)
+            o.bars_out, o.cap_b = bars.ctypes.data, cap
+            rc = entry(handle.raw, src, n, Z, H, W, C.byref(o), rows)
+            if rc != E_CAP or cap >= full:
+                break
+        check(rc, what)
+    else:
+        check(entry(handle.raw, src, n, Z, H, W, C.byref(o), rows), what)
     res = ([[(rows[t * n + i].count, rows[t * n + i].total_px, rows[t * n + i].avg_px) for i in range(n)] for t in range(len(th))],)
     if return_fields:
         res += (fields,)
     if return_pictures:
         res += (pics,)
+    if tree:
+        res += ({"bars": [[bars[t, i, : nb[t, i]].copy() for i in range(n)] for t in range(len(th))], "overlays": rgb},)
     return res[0] if len(res) == 1 else res
 
 
@@ -316,6 +416,36 @@ def stack_well_masks(handle: Handle, stack: np.ndarray, out_hw, seed=0):
     from . import well_mask_generation as wmg
     proj = np.asarray(stack).max(0)
     well, shrunken = wmg.make_well_mask(resize_aa(handle, proj, out_hw), handle=handle, seed=seed)
+    return well, np.logical_not(shrunken)
+
+
+def stack_well_front(handle: Handle, stacks, out_hw, return_proj=False):
+    """tmat_stack_well_front_dev: the front end of --detect-well for n stacks of one shape in one launch set.  stacks: as
+    analyze_stack_batch takes them (an array is uploaded for the call) -> (thresh_small, border_small) (n, sh, sw) uint8
+    [, the anti-alias-resized max projections (n, out_h, out_w) float64]"""
+    from . import well_mask_generation as wmg
+    src, shape, resident, a = _stacks_arg(stacks)
+    if not resident:
+        with upload_stacks(handle, a) as dev:
+            return stack_well_front(handle, dev, out_hw, return_proj)
+    n, Z, H, W = shape
+    out_hw = tuple(int(v) for v in out_hw)
+    install_gaussian_tables(handle, (H, W), out_hw, sigmas=())
+    sh, sw = wmg.small_shape_of(out_hw)
+    thresh, border = np.empty((n, sh, sw), np.uint8), np.empty((n, sh, sw), np.uint8)
+    proj = np.empty((n,) + out_hw, np.float64) if return_proj else None
+    check(lib().tmat_stack_well_front_dev(handle.raw, src, n, Z, H, W, out_hw[0], out_hw[1], ptr(proj) if return_proj else None, ptr(thresh), ptr(border)),
+          "tmat_stack_well_front_dev")
+    return (thresh, border, proj) if return_proj else (thresh, border)
+
+
+def stack_well_masks_batch(handle: Handle, stacks, out_hw, seed=0, warn=print):
+    """--detect-well for n Z stacks of one shape: stack_well_masks of every stack, fallbacks and warnings included, with the pixel
+    stages of all n in one launch set (stack_well_front) and the fit once per batch (make_well_masks_from_front).  stacks: as
+    analyze_stack_batch takes them -> (well (n, fh, fw) bool, pruning (n, fh, fw) bool)"""
+    from . import well_mask_generation as wmg
+    thresh, border = stack_well_front(handle, stacks, out_hw)
+    well, shrunken = wmg.make_well_masks_from_front(thresh, border, out_hw, handle, seed, warn)
     return well, np.logical_not(shrunken)
 
 

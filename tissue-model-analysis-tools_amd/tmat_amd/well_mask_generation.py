@@ -365,39 +365,77 @@ def resize_nearest_dev(handle: _lib.Handle, masks: np.ndarray, shape) -> np.ndar
     return out
 
 
+def small_shape_of(shape):
+    """generate_well_mask :153-155: the shape the hull and the superellipse are searched on (tmat_well_small_shape)"""
+    import ctypes as C
+    sh, sw = C.c_int(), C.c_int()
+    _lib.check(_lib.lib().tmat_well_small_shape(int(shape[0]), int(shape[1]), C.byref(sh), C.byref(sw)), "tmat_well_small_shape")
+    return sh.value, sw.value
+
+
+def _border_batch(handle, masks: np.ndarray) -> np.ndarray:
+    """_border of k masks of one shape (k, h, w) through one tmat_canny_mask_batch call -> (k, h, w) bool"""
+    m = np.ascontiguousarray(np.asarray(masks) != 0, np.uint8)
+    if m.shape[0] == 0:
+        return m.astype(bool)
+    ensure_gaussian_table(handle, 1.0, 0, 4.0)
+    edges = np.empty_like(m)
+    _lib.check(_lib.lib().tmat_canny_mask_batch(handle.raw, _lib.ptr(m), m.shape[0], m.shape[1], m.shape[2], 1.0, _lib.ptr(edges)), "tmat_canny_mask_batch")
+    b = edges.astype(bool)
+    mb = m.astype(bool)
+    b[:, 0, :] |= mb[:, 0, :]; b[:, -1, :] |= mb[:, -1, :]; b[:, :, 0] |= mb[:, :, 0]; b[:, :, -1] |= mb[:, :, -1]
+    return b
+
+
 def make_well_masks_batch(x, handle: _lib.Handle, seed: int = 0, warn=print):
     """make_well_mask for a batch of images of one shape: x (n, h, w), or a sequence of n (h, w) images (their dtypes may differ) ->
-    (well (n, h, w) bool, shrunken (n, h, w) bool), equal to [make_well_mask(x[i]) for i].  Per image: threshold, nearest rescale, canny twice, convex hull, hull mask, the choice of the
-    exponent (generate_well_mask up to :187); then one superellipse search, one rasterisation + resize of the well masks and one
-    rasterisation of the shrunken masks for the whole batch."""
-    from scipy.spatial import ConvexHull
-    try:
-        from scipy.spatial import QhullError
-    except ImportError:                                     # older scipy
-        from scipy.spatial.qhull import QhullError
+    (well (n, h, w) bool, shrunken (n, h, w) bool), equal to [make_well_mask(x[i]) for i].  Per image: threshold, nearest rescale, canny
+    (generate_well_mask up to :170); the rest is make_well_masks_from_front."""
     x = [np.asarray(im) for im in x]
     if any(im.ndim != 2 or im.shape != x[0].shape for im in x):
         raise ValueError("make_well_masks_batch: 2-D images of one shape expected")
     if not x:
         return np.zeros((0, 0, 0), bool), np.zeros((0, 0, 0), bool)
-    n_img, shape = len(x), x[0].shape
-    hulls = {}                                              # image -> (small hull mask, exponent, (x, y) of the hull vertices)
-    small_shape = None
+    shape = x[0].shape
+    downsamp_ratio = min(1, 200 / np.max(shape))
+    small_shape = tuple(int(v) for v in np.round(np.asarray(shape) * downsamp_ratio))
+    thresh_small = np.stack([_resize_nearest(auto_threshold_well(im, handle), small_shape) for im in x])
+    border_small = np.stack([_border(handle, t) for t in thresh_small])
+    return make_well_masks_from_front(thresh_small, border_small, shape, handle, seed, warn)
+
+
+def make_well_masks_from_front(thresh_small, border_small, shape, handle: _lib.Handle, seed: int = 0, warn=print):
+    """The tail of make_well_masks_batch, from the ConvexHull call on (generate_well_mask :172-233, make_well_mask): thresh_small,
+    border_small (n, sh, sw) -- every image's thresholded mask at the small shape and its border (canny + the mask's pixels on the image
+    border), from the per-image calls or from tmat_stack_well_front_dev -- and the images' shape -> (well (n, h, w) bool, shrunken
+    (n, h, w) bool).  Per image: convex hull, hull mask; one batched canny for the hull masks' borders (the choice of the exponent), one
+    superellipse search, one rasterisation + resize of the well masks and one rasterisation of the shrunken masks for the whole batch."""
+    from scipy.spatial import ConvexHull
+    try:
+        from scipy.spatial import QhullError
+    except ImportError:                                     # older scipy
+        from scipy.spatial.qhull import QhullError
+    thresh_small, border_small = np.asarray(thresh_small), np.asarray(border_small)
+    if thresh_small.ndim != 3 or border_small.shape != thresh_small.shape:
+        raise ValueError("make_well_masks_from_front: (n, sh, sw) masks and borders expected")
+    n_img, shape = len(thresh_small), tuple(int(v) for v in shape)
+    small_shape = tuple(thresh_small.shape[1:])
+    hull_of = {}                                            # image -> (small hull mask, hull vertices)
     for i in range(n_img):
-        im_thresh = auto_threshold_well(x[i], handle)
-        downsamp_ratio = min(1, 200 / np.max(im_thresh.shape))
-        small_shape = tuple(int(v) for v in np.round(np.asarray(im_thresh.shape) * downsamp_ratio))
-        im_thresh = _resize_nearest(im_thresh, small_shape)
-        border_points = np.argwhere(_border(handle, im_thresh))
+        border_points = np.argwhere(border_small[i] != 0)
         try:
             hull = ConvexHull(border_points)
         except (ValueError, QhullError):
             continue
         hull_vertices = border_points[hull.vertices]
-        hull_mask = create_convex_hull_mask(im_thresh.shape, hull_vertices)
-        n = 8 if np.sum(_border(handle, hull_mask)) / np.sum(hull_mask) > .027 else 2
-        hulls[i] = (hull_mask, n, (hull_vertices[:, 0] / im_thresh.shape[0] * 2 - 1, hull_vertices[:, 1] / im_thresh.shape[1] * 2 - 1))
-    order = sorted(hulls)
+        hull_of[i] = (create_convex_hull_mask(small_shape, hull_vertices), hull_vertices)
+    order = sorted(hull_of)
+    hull_borders = _border_batch(handle, np.stack([hull_of[i][0] for i in order])) if order else []
+    hulls = {}                                              # image -> (small hull mask, exponent, (x, y) of the hull vertices)
+    for k, i in enumerate(order):
+        hull_mask, hull_vertices = hull_of[i]
+        n = 8 if np.sum(hull_borders[k]) / np.sum(hull_mask) > .027 else 2
+        hulls[i] = (hull_mask, n, (hull_vertices[:, 0] / small_shape[0] * 2 - 1, hull_vertices[:, 1] / small_shape[1] * 2 - 1))
     fits = dict(zip(order, superellipse_search_batch(handle, [hulls[i][2] for i in order], [hulls[i][1] for i in order], seed))) if order else {}
     found = [i for i in order if fits[i] is not None]
     for i in order:

@@ -12,6 +12,16 @@ loop on the same N synthetic stacks, in this process on this handle: old, new, o
 gains "batch": stacks/s of the four runs, the within-pair spreads, whether the rows are equal, the batch call's per-pass split (wall ms
 of the device stages and of the host graph stage, tmat_debug_stack_trace) and the verdict of the project's bar -- the lower new value
 must exceed the higher old value by at least five times the larger within-pair spread.  --batch-only prints that comparison alone.
+
+--batch-only with --detect-well and / or --tree compares, for each flag given, the route compute_branches.py took for Z stacks before
+the batch path knew the flag with the route it takes now, on the same N synthetic stacks with a bright well:
+    --detect-well   old: sato.stack_well_masks stack by stack in front of one analyze_stack_batch call on host buffers
+                    new: one upload, sato.stack_well_masks_batch on the resident chunk, one call on the resident chunk
+    --tree          old: per stack stack_field, field_stats, field_tree and Handle.render_tree over the host's max projection
+                    new: one upload, one analyze_stack_batch call with the tree request
+Same process, same handle, old, new, old, new after one untimed round of each (--repeat runs of the route per window: one run of the
+batch route is under 0.1 s, too short a window to time), wall time around calls that end in a synchronise; rows,
+bars and overlays are checked for equality; the same bar.  --out FILE also writes the JSON line there.
 """
 import argparse
 import json
@@ -37,9 +47,25 @@ def main():
     ap.add_argument("--batch-only", action="store_true", help="only the batch-vs-loop comparison")
     ap.add_argument("--batch-path", choices=["both", "old", "new"], default="both",
                     help="with --batch-only: old / new runs that path alone, twice, untimed (for a kernel trace of one path: tools/gpu_stack_batch_prof.sh)")
+    ap.add_argument("--detect-well", action="store_true", help="with --batch-only: the --detect-well routes of compute_branches.py, old against new")
+    ap.add_argument("--tree", action="store_true", help="with --batch-only: the --tree-visualizations routes, old against new")
+    ap.add_argument("--vis-width", type=int, default=2000)
+    ap.add_argument("--repeat", type=int, default=5,
+                    help="with --detect-well / --tree: times a route runs inside each of the four timed windows (one run of the batch route is under 0.1 s)")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
     from tmat_amd import _lib, branches, sato, synth
     h = _lib.Handle(None, 0)
+    if a.batch_only and (a.detect_well or a.tree):
+        line = json.dumps({"metric": "z_stacks_per_sec_batch_flags", "unit": "stacks/s", "higher_is_better": True, "data": "synthetic",
+                           "config": {"slices": a.slices, "size": a.size, "hessian": a.hessian, "vis_width": a.vis_width, "stacks": a.batch,
+                                      "runs_per_window": a.repeat},
+                           "flags": flags_compare(h, a)})
+        print(line)
+        if a.out:
+            Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(a.out).write_text(line + "\n")
+        return
     if a.batch_only:
         print(json.dumps({"metric": "z_stacks_per_sec_batch", "unit": "stacks/s", "higher_is_better": True, "data": "synthetic",
                           "config": {"slices": a.slices, "size": a.size, "hessian": a.hessian}, "batch": batch_compare(h, a)}))
@@ -137,6 +163,91 @@ def batch_compare(h, a):
             "passes": traces, "stacks_per_pass": sato.stack_pass_plan(a.batch, a.slices, a.size, a.size)[0],
             "lower_new_minus_higher_old": gain, "five_times_larger_spread": need, "bar_met": bool(gain >= need and gain > 0),
             "ratio_of_means": (sum(runs["new"]) / 2) / (sum(runs["old"]) / 2)}
+
+
+def well_stack(index, slices, size):
+    """synth_stack inside a bright well (the vignette of tools/bench_well.py:well_image on every slice): round for even indices, a
+    rounded square for odd ones"""
+    import numpy as np
+    from tmat_amd import synth
+    st = synth.synth_stack(index, slices, size, size, n_vessels=30).astype(np.float64)
+    yy, xx = np.mgrid[0:size, 0:size]
+    u, v = (xx - size * 0.51) / (size * 0.45), (yy - size * 0.49) / (size * 0.45)
+    inside = (u ** 2 + v ** 2 < 1) if index % 2 == 0 else (u ** 8 + v ** 8 < 1)
+    return np.clip(np.where(inside[None], st + 12000.0, 0.0), 0, 65535).astype(np.uint16)
+
+
+def flags_compare(h, a):
+    """per flag: the route of before (see the module text) against the batch route, alternating after one untimed round of each"""
+    import numpy as np
+    from tmat_amd import _lib, branches, sato
+    cfg = {"graph_thresh_1": 5, "graph_thresh_2": 10, "graph_smoothing_window": 12, "min_branch_length": 12, "remove_isolated_branches": False}
+    width_um = 1000.0
+    sw, mn, mx = branches.graph_px_params(cfg, 384, width_um)
+    stacks = np.stack([well_stack(100 + i, a.slices, a.size) for i in range(a.batch)])
+    out_hw = sato.dsamp_shape(stacks.shape, 384)
+    quiet = lambda m: None      # noqa: E731
+    fixed_pruning = sato.stack_well_masks_batch(h, stacks, out_hw, 0, warn=quiet)[1]
+
+    def well_old():
+        pruning = np.stack([sato.stack_well_masks(h, st, out_hw, 0)[1] for st in stacks])
+        return sato.analyze_stack_batch(h, stacks, [(5, 10)], sw, mn, mx, False, hessian=a.hessian, pruning_masks=pruning)[0], pruning
+
+    def well_new():
+        with sato.upload_stacks(h, stacks) as dev:
+            pruning = sato.stack_well_masks_batch(h, dev, out_hw, 0, warn=quiet)[1]
+            return sato.analyze_stack_batch(h, dev, [(5, 10)], sw, mn, mx, False, hessian=a.hessian, pruning_masks=pruning)[0], pruning
+
+    def tree_old():
+        rows, bars, over = [], [], []
+        for i, st in enumerate(stacks):
+            field = sato.stack_field(h, st, 384, a.hessian)
+            rows.append(sato.field_stats(h, field, 5, 10, sw, mn, mx, False, pruning_mask=fixed_pruning[i]))
+            background = st.max(0)
+            tree, b, _ = branches.field_tree(h, _lib.host_rescale255_f32(field), cfg, width_um, (5, 10), fixed_pruning[i], background.shape[1] / field.shape[1])
+            bars.append(b)
+            over.append(h.render_tree(background[None], [tree], a.vis_width)[0])
+        return rows, bars, np.stack(over)
+
+    def tree_new():
+        with sato.upload_stacks(h, stacks) as dev:
+            rows, extra = sato.analyze_stack_batch(h, dev, [(5, 10)], sw, mn, mx, False, hessian=a.hessian, pruning_masks=fixed_pruning, tree=True,
+                                                   vis_width=a.vis_width)
+        return rows[0], extra["bars"][0], extra["overlays"][0]
+
+    def same(x, y):
+        if isinstance(x, np.ndarray):
+            return bool(np.array_equal(x, y))
+        return len(x) == len(y) and all(same(p, q) if isinstance(p, (np.ndarray, list)) else tuple(p) == tuple(q) for p, q in zip(x, y))
+
+    def compare(old, new, names):
+        import contextlib
+        import io
+        res = {}
+        with contextlib.redirect_stdout(io.StringIO()):         # the per-stack mask route prints its warnings
+            old(), new()                                        # untimed: pool blocks, pinned slots, tables
+            runs = {"old": [], "new": []}
+            for _ in range(2):
+                for name, fn in (("old", old), ("new", new)):
+                    t0 = time.perf_counter()
+                    for _ in range(max(a.repeat, 1)):
+                        res[name] = fn()
+                    runs[name].append(max(a.repeat, 1) * a.batch / (time.perf_counter() - t0))
+        spread = {k: abs(v[0] - v[1]) for k, v in runs.items()}
+        gain = min(runs["new"]) - max(runs["old"])
+        need = 5 * max(spread.values())
+        return {"order": "old, new, old, new", "old_stacks_per_s": runs["old"], "new_stacks_per_s": runs["new"], "within_pair_spread": spread,
+                "equal": {nm: same(x, y) for nm, x, y in zip(names, res["old"], res["new"])},
+                "lower_new_minus_higher_old": gain, "five_times_larger_spread": need, "bar_met": bool(gain >= need and gain > 0),
+                "ratio_of_means": (sum(runs["new"]) / 2) / (sum(runs["old"]) / 2)}
+
+    out = {}
+    if a.detect_well:
+        out["detect_well"] = compare(well_old, well_new, ("rows", "pruning_masks"))
+        out["detect_well"]["pruning_pixels"] = [int(m.sum()) for m in fixed_pruning]
+    if a.tree:
+        out["tree"] = compare(tree_old, tree_new, ("rows", "bars", "overlays"))
+    return out
 
 
 if __name__ == "__main__":
