@@ -142,6 +142,17 @@ int tmat_well_small_shape(int h, int w, int *small_h, int *small_w);
  */
 int tmat_stack_well_front_dev(tmat_handle h, const uint16_t *stacks_dev, int n, int Z, int H, int W, int out_h, int out_w,
                               double *proj_aa_out, uint8_t *thresh_small, uint8_t *border_small);
+/*
+ * The same front end for the cell-area tool (compute_cell_area.py:127 hands generate_well_mask the down-sampled INTEGER image;
+ * well_mask_generation.py:153-170): small_dev (n, hh, ww) u16 device (tmat_cell_small_dev), read only.  Per image: img_as_float,
+ * (double)v * (1.0 / 65535.0), or 1.0 / 255.0 for src_bits == 8 (explicit; the handle's input depth is not read);
+ * auto_threshold_well; nearest resize to the small shape (sh, sw) of tmat_well_small_shape(hh, ww); canny(sigma 1) plus the mask's
+ * own pixels on the image border.  An image leaves a batch exactly as tmat_well_threshold_f64 + tmat_canny_mask give it alone.
+ * Host outputs: thresh_small, border_small (n, sh, sw) u8.  n >= 1, hh, ww >= 20, small shape >= 3 x 3, n hh ww <= 2^26, src_bits 8
+ * or 16: TMAT_E_ARG otherwise, nothing written.  The gaussian table is that of tmat_well_threshold; scratch comes from the handle's pool.
+ */
+int tmat_cell_well_front_dev(tmat_handle h, const uint16_t *small_dev, int n, int hh, int ww, int src_bits, uint8_t *thresh_small,
+                             uint8_t *border_small);
 
 /*
  * The superellipse fit of well detection on the device (csrc/wellfit_kernels.hip), for a batch of images.
@@ -673,6 +684,30 @@ int tmat_cell_area_batch(tmat_handle h, const uint16_t *imgs, int n, int H, int 
 int tmat_cell_area_masked(tmat_handle h, const uint16_t *imgs, const uint8_t *masks, int n, int H, int W, double sd_coef, double *area,
                           uint8_t *thresholded, double *params);
 int tmat_resize_linear_u16(tmat_handle h, const uint16_t *imgs, int n, int H, int W, int out_h, int out_w, uint16_t *out);
+
+/*
+ * Max projection and down-sampling of n Z stacks in one kernel (compute_cell_area.py:50-57: img.max(0), then cv2.resize), for
+ * stacks that are resident in device memory: src_dev (n, Z, H, W) u16 (tmat_dev_alloc; 8-bit sources widened), read only ->
+ * small_dev (n, out_h, out_w) u16, device.  Every output pixel takes the maximum over Z of each of its source taps and then the
+ * arithmetic of tmat_resize_linear_u16 on those maxima: the float bilinear form (src_bits 16), cv2's fixed-point form (src_bits 8),
+ * the integer 2 x 2 mean when H == 2 out_h && W == 2 out_w.  The full-resolution projection is never written and only the rows
+ * the taps touch are read.  Z == 1 is tmat_resize_linear_u16 without the copies.  out_h = out_w = 0: the plain max projection,
+ * small_dev (n, H, W).  src_bits is explicit: tmat_set_input_depth is not read.
+ * Z >= 1, n <= 65535, H W <= 2^30, src_bits 8 or 16, out_h / out_w both 0 or both positive: TMAT_E_ARG otherwise, nothing written.
+ * Returns after the kernel has run.
+ */
+int tmat_cell_small_dev(tmat_handle h, const uint16_t *src_dev, int n, int Z, int H, int W, int src_bits, int out_h, int out_w,
+                        uint16_t *small_dev);
+
+/*
+ * The tail of tmat_cell_area_batch / tmat_cell_area_masked (rescale_intensity, mixture fit, threshold, area: compute_cell_area.py:79-87,
+ * preprocessing.py:44-93) on images that are already down-sampled and resident: small_dev (n, hh, ww) u16 device, read only.
+ * masks: host, NULL (the unmasked form of tmat_cell_area_batch) or (n, hh, ww) u8 with the meaning of tmat_cell_area_masked (extrema
+ * of the whole image, mixture inside the mask, area[i] = kept pixels / (hh ww)).  area, thresholded (nullable, (n, hh, ww) u8) and
+ * params (nullable, n x 9) are host buffers as there; the three entry points run the same code from here on.  n <= 65535.
+ */
+int tmat_cell_area_fit_dev(tmat_handle h, const uint16_t *small_dev, const uint8_t *masks, int n, int hh, int ww, double sd_coef,
+                           double *area, uint8_t *thresholded, double *params);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Invasion-depth tool: reference scripts/compute_inv_depth.py:96-172, models.py:33-82 (build_ResNet50_TL),

@@ -9,6 +9,7 @@
 // Arithmetic contract: oracle/cellarea.py (same formulas in float64; block-tree instead of sequential summation).
 #include "../../include/tmat.h"
 #include "tmat_ctx.h"
+#include "morph.h"
 
 #include <cmath>
 #include <cstring>
@@ -64,6 +65,55 @@ __global__ __launch_bounds__(256) void resize_area2_u16_kernel(const uint16_t *_
         const int y = p / ow, x = p - y * ow;
         const uint16_t *q = src + (size_t)(2 * y) * W + 2 * x;
         out[(size_t)blockIdx.y * oh * ow + p] = (uint16_t)(((unsigned)q[0] + q[1] + q[W] + q[W + 1] + 2u) >> 2);
+    }
+}
+
+// Max projection of a Z stack fused with the resize above (tmat_cell_small_dev): img (n, Z, H, W), one thread per OUTPUT pixel takes the
+// maximum over Z of each of its four source taps and then evaluates the arithmetic of the resize kernel of the same form on the maxima
+// (FORM 0: resize_linear_u16_kernel, 1: resize_linear_u8_kernel, 2: resize_area2_u16_kernel -- the same expressions, so Z = 1 gives
+// their bits).  The full-resolution projection is never written, and only the source rows the taps touch are read: a wave's 64 lanes
+// read neighbouring taps of one row, so every cache line of such a row is fetched once per slice.  The Z loop is unrolled by four:
+// sixteen independent loads in flight per lane.  wr / wc: float weights (FORM 0, as bits) or cv2's 11-bit integers (FORM 1).
+template <int FORM>
+__global__ __launch_bounds__(256) void cell_small_kernel(const uint16_t *__restrict__ img, int Z, int H, int W, int oh, int ow, const int *__restrict__ r0,
+                                                         const int *__restrict__ r1, const int *__restrict__ wr0, const int *__restrict__ wr1,
+                                                         const int *__restrict__ c0, const int *__restrict__ c1, const int *__restrict__ wc0,
+                                                         const int *__restrict__ wc1, uint16_t *__restrict__ out)
+{
+    const size_t hw = (size_t)H * W;
+    const uint16_t *src = img + (size_t)blockIdx.y * Z * hw;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < oh * ow; p += gridDim.x * 256) {
+        const int y = p / ow, x = p - y * ow;
+        size_t i00, i01, i10, i11;
+        if constexpr (FORM == 2) {
+            i00 = (size_t)(2 * y) * W + 2 * x; i01 = i00 + 1; i10 = i00 + W; i11 = i10 + 1;
+        } else {
+            const size_t ra = (size_t)r0[y] * W, rb = (size_t)r1[y] * W;
+            i00 = ra + c0[x]; i01 = ra + c1[x]; i10 = rb + c0[x]; i11 = rb + c1[x];
+        }
+        unsigned m00 = 0, m01 = 0, m10 = 0, m11 = 0;
+#pragma unroll 4
+        for (int z = 0; z < Z; z++) {
+            const uint16_t *q = src + (size_t)z * hw;
+            const unsigned a = q[i00], b = q[i01], c = q[i10], d = q[i11];
+            m00 = a > m00 ? a : m00; m01 = b > m01 ? b : m01; m10 = c > m10 ? c : m10; m11 = d > m11 ? d : m11;
+        }
+        uint16_t res;
+        if constexpr (FORM == 2) {
+            res = (uint16_t)((m00 + m01 + m10 + m11 + 2u) >> 2);
+        } else if constexpr (FORM == 1) {
+            const int h0 = (int)m00 * wc0[x] + (int)m01 * wc1[x];
+            const int h1 = (int)m10 * wc0[x] + (int)m11 * wc1[x];
+            const int v = (((wr0[y] * (h0 >> 4)) >> 16) + ((wr1[y] * (h1 >> 4)) >> 16) + 2) >> 2;
+            res = (uint16_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+        } else {
+            const float fc0 = __int_as_float(wc0[x]), fc1 = __int_as_float(wc1[x]);
+            const float a = (float)m00 * fc0 + (float)m01 * fc1;
+            const float b = (float)m10 * fc0 + (float)m11 * fc1;
+            const float v = rintf(a * __int_as_float(wr0[y]) + b * __int_as_float(wr1[y]));
+            res = (uint16_t)fminf(fmaxf(v, 0.f), 65535.f);
+        }
+        out[(size_t)blockIdx.y * oh * ow + p] = res;
     }
 }
 
@@ -281,12 +331,17 @@ static void linear_axis(int n_src, int n_dst, std::vector<int> &i0, std::vector<
 // tables into `tab` ((oh + ow) * 4 dwords, device; must stay allocated until the stream has run the kernel) and launches the arithmetic of
 // the SOURCE depth -- eight_bit: cv2's fixed-point path (tmat_set_input_depth(h, 8)), else the float path; an exact halving on both axes
 // is INTER_AREA's integer mean for both depths.  Also used by tmat_inv_depth_predict (resnet_kernels.hip).
-int launch_resize_linear_dev(const uint16_t *din, int n, int H, int W, int oh, int ow, bool eight_bit, int *tab, uint16_t *dsm, hipStream_t s)
+// Z = 1: the resize kernels; Z > 1 (tmat_cell_small_dev): din is (n, Z, H, W) and the maximum over Z is taken per tap (cell_small_kernel).
+// before (nullable): an event recorded on the stream in front of the kernel, behind the blocking table upload
+static int launch_small_dev(const uint16_t *din, int n, int Z, int H, int W, int oh, int ow, bool eight_bit, int *tab, uint16_t *dsm, hipStream_t s,
+                            hipEvent_t before = nullptr)
 {
     const int blocks = (oh * ow + 255) / 256;
     const dim3 grid(blocks < 1024 ? blocks : 1024, n);
     if (H == 2 * oh && W == 2 * ow) {
-        hipLaunchKernelGGL(resize_area2_u16_kernel, grid, dim3(256), 0, s, din, H, W, dsm);
+        if (before) hipEventRecord(before, s);
+        if (Z == 1) hipLaunchKernelGGL(resize_area2_u16_kernel, grid, dim3(256), 0, s, din, H, W, dsm);
+        else hipLaunchKernelGGL(cell_small_kernel<2>, grid, dim3(256), 0, s, din, Z, H, W, oh, ow, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dsm);
         return 0;
     }
     std::vector<int> r0, r1, c0, c1;
@@ -308,6 +363,12 @@ int launch_resize_linear_dev(const uint16_t *din, int n, int H, int W, int oh, i
     // synchronous copy: `host` goes out of scope at return
     if (hipMemcpy(tab, host.data(), host.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_error("resize: table upload failed"); return -2; }
     const int *dr0 = tab, *dr1 = dr0 + oh, *dc0 = dr1 + oh, *dc1 = dc0 + ow, *dw = dc1 + ow;
+    if (before) hipEventRecord(before, s);
+    if (Z != 1) {
+        if (eight_bit) hipLaunchKernelGGL(cell_small_kernel<1>, grid, dim3(256), 0, s, din, Z, H, W, oh, ow, dr0, dr1, dw, dw + oh, dc0, dc1, dw + 2 * oh, dw + 2 * oh + ow, dsm);
+        else hipLaunchKernelGGL(cell_small_kernel<0>, grid, dim3(256), 0, s, din, Z, H, W, oh, ow, dr0, dr1, dw, dw + oh, dc0, dc1, dw + 2 * oh, dw + 2 * oh + ow, dsm);
+        return 0;
+    }
     if (eight_bit)
         hipLaunchKernelGGL(resize_linear_u8_kernel, grid, dim3(256), 0, s, din, H, W, oh, ow, dr0, dr1, dw, dw + oh, dc0, dc1, dw + 2 * oh, dw + 2 * oh + ow, dsm);
     else
@@ -316,51 +377,30 @@ int launch_resize_linear_dev(const uint16_t *din, int n, int H, int W, int oh, i
     return 0;
 }
 
+int launch_resize_linear_dev(const uint16_t *din, int n, int H, int W, int oh, int ow, bool eight_bit, int *tab, uint16_t *dsm, hipStream_t s)
+{
+    return launch_small_dev(din, n, 1, H, W, oh, ow, eight_bit, tab, dsm, s);
+}
+
 }  // namespace tmat
 
 using namespace tmat;
 
-// masks (nullable): (n, oh, ow) u8 well masks on the DOWN-SAMPLED grid; small_out (nullable): the down-sampled images back to the host;
-// area = kept pixels / pixels (the caller divides by the well area when it masks)
-static int cell_area_impl(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, int out_h, int out_w, double sd_coef, double *area,
-                          uint8_t *thresholded, double *params, const uint8_t *masks, uint16_t *small_out, int fit)
+// The tail every entry point shares, on n images (n, oh, ow) u16 that are in device memory: extrema, histogram, mixture fit, threshold.
+// masks (nullable, host): (n, oh, ow) u8 well masks; area = kept pixels / pixels (the caller divides by the well area when it masks).
+// The workspaces live on the handle between calls (tmat_ctx.h:ws_get); the caller's scope carries the copies and is drained here.
+static int cell_area_fit_tail(Ctx *c, DevScope &mem, const uint16_t *small, int n, int oh, int ow, double sd_coef, const uint8_t *masks, double *area,
+                              uint8_t *thresholded, double *params)
 {
-    if (!hd || !imgs || !area || n < 0 || H < 1 || W < 1 || out_h < 0 || out_w < 0 || (out_h == 0) != (out_w == 0)) {
-        set_error("tmat_cell_area_batch: bad argument");
-        return TMAT_E_ARG;
-    }
-    if (n == 0) return TMAT_OK;
-    Ctx *c = (Ctx *)hd;
-    TMAT_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const int oh = out_h ? out_h : H, ow = out_w ? out_w : W;
-    const size_t nin = (size_t)n * H * W, nout = (size_t)n * oh * ow;
-    // workspaces live on the handle between calls (tmat_ctx.h:ws_get); the scope carries the copies, and a failed call leaves nothing in
-    // flight on them
-    uint16_t *din = (uint16_t *)ws_get(c, WS_CELL_IN, nin * 2);
+    const size_t nout = (size_t)n * oh * ow;
     unsigned *hist = (unsigned *)ws_get(c, WS_CELL_HIST, (size_t)n * 65536 * 4), *kept = (unsigned *)ws_get(c, WS_CELL_KEPT, (size_t)n * 4);
     double *dpar = (double *)ws_get(c, WS_CELL_PAR, (size_t)n * 11 * 8);
     uint8_t *dthr = thresholded ? (uint8_t *)ws_get(c, WS_CELL_THR, nout) : nullptr;
-    if (!din || !hist || !kept || !dpar || (thresholded && !dthr)) return TMAT_E_HIP;
-    DevScope mem(c->ws_pool, s);
-    if (!mem.h2d(din, imgs, nin * 2)) return TMAT_E_HIP;
-    const uint16_t *small = din;
-    if (out_h) {
-        uint16_t *dsm = (uint16_t *)ws_get(c, WS_CELL_SMALL, nout * 2);
-        int *itab = (int *)ws_get(c, WS_CELL_TAB, (size_t)(oh + ow) * 4 * 4);
-        // 8-bit sources (tmat_set_input_depth(h, 8)) take cv2's fixed-point arithmetic
-        if (!dsm || !itab || launch_resize_linear_dev(din, n, H, W, oh, ow, c->input_sat == 255.f, itab, dsm, s)) return TMAT_E_HIP;
-        small = dsm;
-    }
-    if (!fit) {          // tmat_resize_linear_u16: only the down-sampled images are wanted
-        mem.check(hipGetLastError(), "launch");
-        mem.d2h(small_out, small, nout * 2);
-        return mem.finish();
-    }
+    if (!hist || !kept || !dpar || (thresholded && !dthr)) return TMAT_E_HIP;
     const int npx = oh * ow, blocks = (npx + 255) / 256;
     const dim3 grid(blocks < 512 ? blocks : 512, n);
-    if (!mem.check(hipMemsetAsync(hist, 0, (size_t)n * 65536 * 4, s), "memset") || !mem.check(hipMemsetAsync(kept, 0, n * 4, s), "memset") ||
-        !mem.d2h(small_out, small, nout * 2)) return TMAT_E_HIP;
+    if (!mem.check(hipMemsetAsync(hist, 0, (size_t)n * 65536 * 4, s), "memset") || !mem.check(hipMemsetAsync(kept, 0, n * 4, s), "memset")) return TMAT_E_HIP;
     const uint8_t *dmask = nullptr;
     int *lohi = nullptr;
     if (masks) {
@@ -388,6 +428,41 @@ static int cell_area_impl(tmat_handle hd, const uint16_t *imgs, int n, int H, in
     return TMAT_OK;
 }
 
+// masks (nullable): (n, oh, ow) u8 well masks on the DOWN-SAMPLED grid; small_out: the down-sampled images back to the host when only
+// they are wanted (fit = 0)
+static int cell_area_impl(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, int out_h, int out_w, double sd_coef, double *area,
+                          uint8_t *thresholded, double *params, const uint8_t *masks, uint16_t *small_out, int fit)
+{
+    if (!hd || !imgs || !area || n < 0 || H < 1 || W < 1 || out_h < 0 || out_w < 0 || (out_h == 0) != (out_w == 0)) {
+        set_error("tmat_cell_area_batch: bad argument");
+        return TMAT_E_ARG;
+    }
+    if (n == 0) return TMAT_OK;
+    Ctx *c = (Ctx *)hd;
+    TMAT_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int oh = out_h ? out_h : H, ow = out_w ? out_w : W;
+    const size_t nin = (size_t)n * H * W, nout = (size_t)n * oh * ow;
+    uint16_t *din = (uint16_t *)ws_get(c, WS_CELL_IN, nin * 2);
+    if (!din) return TMAT_E_HIP;
+    DevScope mem(c->ws_pool, s);
+    if (!mem.h2d(din, imgs, nin * 2)) return TMAT_E_HIP;
+    const uint16_t *small = din;
+    if (out_h) {
+        uint16_t *dsm = (uint16_t *)ws_get(c, WS_CELL_SMALL, nout * 2);
+        int *itab = (int *)ws_get(c, WS_CELL_TAB, (size_t)(oh + ow) * 4 * 4);
+        // 8-bit sources (tmat_set_input_depth(h, 8)) take cv2's fixed-point arithmetic
+        if (!dsm || !itab || launch_resize_linear_dev(din, n, H, W, oh, ow, c->input_sat == 255.f, itab, dsm, s)) return TMAT_E_HIP;
+        small = dsm;
+    }
+    if (!fit) {          // tmat_resize_linear_u16: only the down-sampled images are wanted
+        mem.check(hipGetLastError(), "launch");
+        mem.d2h(small_out, small, nout * 2);
+        return mem.finish();
+    }
+    return cell_area_fit_tail(c, mem, small, n, oh, ow, sd_coef, masks, area, thresholded, params);
+}
+
 extern "C" int tmat_cell_area_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, int out_h, int out_w, double sd_coef, double *area,
                                     uint8_t *thresholded, double *params)
 {
@@ -406,4 +481,52 @@ extern "C" int tmat_resize_linear_u16(tmat_handle hd, const uint16_t *imgs, int 
     if (!out || out_h < 1 || out_w < 1) { set_error("tmat_resize_linear_u16: bad argument"); return TMAT_E_ARG; }
     std::vector<double> area((size_t)(n > 0 ? n : 1));
     return cell_area_impl(hd, imgs, n, H, W, out_h, out_w, 0.0, area.data(), nullptr, nullptr, nullptr, out, 0);
+}
+
+extern "C" int tmat_cell_small_dev(tmat_handle hd, const uint16_t *src_dev, int n, int Z, int H, int W, int src_bits, int out_h, int out_w,
+                                   uint16_t *small_dev)
+{
+    if (!hd || !src_dev || !small_dev || n < 0 || n > 65535 || H < 1 || W < 1 || out_h < 0 || out_w < 0 || (long long)out_h * out_w > (1LL << 30) ||
+        (long long)H * W > (1LL << 30)) {
+        set_error("tmat_cell_small_dev: bad argument");
+        return TMAT_E_ARG;
+    }
+    if (Z < 1) { set_error("tmat_cell_small_dev: a stack has at least one slice"); return TMAT_E_ARG; }
+    if (src_bits != 8 && src_bits != 16) { set_error("tmat_cell_small_dev: src_bits must be 8 or 16"); return TMAT_E_ARG; }
+    if ((out_h == 0) != (out_w == 0)) { set_error("tmat_cell_small_dev: out_h and out_w are both 0 (no resize) or both positive"); return TMAT_E_ARG; }
+    if (n == 0) return TMAT_OK;
+    Ctx *c = (Ctx *)hd;
+    TMAT_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DevScope mem(c->ws_pool, s);
+    // tmat_prof_enable: an event pair around the kernel alone (tools/bench_cell_area.py reads it with tmat_prof_read)
+    ProfEv ev{};
+    if (c->prof_on && c->ev_pool.size() >= 2) { ev.e0 = c->ev_pool.back(); c->ev_pool.pop_back(); ev.e1 = c->ev_pool.back(); c->ev_pool.pop_back(); }
+    else if (c->prof_on && (!mem.check(hipEventCreate(&ev.e0), "hipEventCreate") || !mem.check(hipEventCreate(&ev.e1), "hipEventCreate"))) return TMAT_E_HIP;
+    int rc;
+    if (!out_h) {        // the plain max projection
+        if (c->prof_on) hipEventRecord(ev.e0, s);
+        rc = zproj_dev(src_dev, n, Z, H, W, TMAT_ZPROJ_MAX, small_dev, s);
+    } else {
+        int *itab = (int *)ws_get(c, WS_CELL_TAB, (size_t)(out_h + out_w) * 4 * 4);
+        rc = itab ? launch_small_dev(src_dev, n, Z, H, W, out_h, out_w, src_bits == 8, itab, small_dev, s, ev.e0) : -2;
+    }
+    if (c->prof_on) { hipEventRecord(ev.e1, s); c->ev_open.push_back(ev); }          // tmat_prof_read takes them back
+    if (rc) return TMAT_E_HIP;
+    mem.check(hipGetLastError(), "tmat_cell_small_dev: kernel launch");
+    return mem.finish();          // the table slot is free for the next call
+}
+
+extern "C" int tmat_cell_area_fit_dev(tmat_handle hd, const uint16_t *small_dev, const uint8_t *masks, int n, int hh, int ww, double sd_coef, double *area,
+                                      uint8_t *thresholded, double *params)
+{
+    if (!hd || !small_dev || !area || n < 0 || n > 65535 || hh < 1 || ww < 1 || (long long)hh * ww > (1LL << 30)) {
+        set_error("tmat_cell_area_fit_dev: bad argument");
+        return TMAT_E_ARG;
+    }
+    if (n == 0) return TMAT_OK;
+    Ctx *c = (Ctx *)hd;
+    TMAT_HIP(hipSetDevice(c->device));
+    DevScope mem(c->ws_pool, c->stream);
+    return cell_area_fit_tail(c, mem, small_dev, n, hh, ww, sd_coef, masks, area, thresholded, params);
 }

@@ -684,6 +684,39 @@ int tmat_stack_well_front_dev(tmat_handle hd, const uint16_t *stacks_dev, int n,
     return A.finish();
 }
 
+int tmat_cell_well_front_dev(tmat_handle hd, const uint16_t *small_dev, int n, int hh, int ww, int src_bits, uint8_t *thresh_small, uint8_t *border_small)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!c || !small_dev || !thresh_small || !border_small || n < 1 || hh < 20 || ww < 20 || (long long)n * hh * ww > (1LL << 26)) {
+        set_error("tmat_cell_well_front_dev: bad argument (n >= 1 images of at least 20 x 20, n hh ww <= 2^26)");
+        return TMAT_E_ARG;
+    }
+    if (src_bits != 8 && src_bits != 16) { set_error("tmat_cell_well_front_dev: src_bits must be 8 or 16"); return TMAT_E_ARG; }
+    TMAT_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int sh, sw;
+    well_small_shape(hh, ww, &sh, &sw);
+    if (sh < 3 || sw < 3) { set_error("tmat_cell_well_front_dev: the small mask is below 3 x 3"); return TMAT_E_ARG; }
+    const size_t npx = (size_t)hh * ww, spx = (size_t)sh * sw;
+    DevScope A(c->ws_pool, s);
+    double *f = A.pooled<double>((size_t)n * npx);
+    uint8_t *th = A.pooled<uint8_t>((size_t)n * npx), *small = A.pooled<uint8_t>((size_t)n * spx), *border = A.pooled<uint8_t>((size_t)n * spx);
+    if (!A.ok) return TMAT_E_HIP;
+    // auto_threshold_well of an integer image: gaussian() converts with img_as_float first
+    launch_wm_unit_f64(small_dev, (size_t)n * npx, src_bits == 8 ? 1.0 / 255.0 : 1.0 / 65535.0, f, s);
+    // generate_well_mask :156-170: threshold, nearest resize to <= 200 px, border of the small mask
+    int rc = well_threshold_dev(c, f, nullptr, n, hh, ww, th, s);
+    if (rc) return rc;
+    launch_resize_nearest_u8(th, n, hh, ww, sh, sw, small, s);
+    rc = canny_mask_dev(c, small, n, sh, sw, 1.0, border, s);
+    if (rc) return rc;
+    launch_wm_border(small, n, sh, sw, border, s);
+    A.check(hipGetLastError(), "tmat_cell_well_front_dev: kernel launch");
+    A.d2h(thresh_small, small, (size_t)n * spx);
+    A.d2h(border_small, border, (size_t)n * spx);
+    return A.finish();
+}
+
 int tmat_sato_batch(tmat_handle hd, const float *imgs, int n, int hh, int ww, const double *sigmas, int n_sigmas, int hessian, float *out)
 {
     Ctx *c = (Ctx *)hd;

@@ -18,6 +18,8 @@ void launch_wm_erode(const uint8_t *m, int n_img, int H, int W, const int *off, 
 // canny's smoothing of a 0 / 1 mask with mode="constant": pad (zeros, and a second padded image of ones inside), crop + divide
 void launch_wm_pad(const uint8_t *m, int n_img, int H, int W, int r, double *img_pad, double *ones_pad, hipStream_t s);
 void launch_wm_crop_div(const double *img_pad, const double *ones_pad, int n_img, int H, int W, int r, double *out, hipStream_t s);
+// img_as_float of n unsigned integer values (widened to u16): out = (double)v * inv_max, inv_max = 1.0 / 65535.0 or 1.0 / 255.0
+void launch_wm_unit_f64(const uint16_t *img, size_t n, double inv_max, double *out, hipStream_t s);
 // edges |= the mask's pixels in the first / last row and column (:165-170)
 void launch_wm_border(const uint8_t *m, int n_img, int H, int W, uint8_t *edges, hipStream_t s);
 // well_mask_generation.py:_resize_nearest of n_img masks (wellfit_kernels.hip)

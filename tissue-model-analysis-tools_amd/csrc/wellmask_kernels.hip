@@ -246,6 +246,16 @@ void launch_wm_crop_div(const double *img_pad, const double *ones_pad, int n_img
     hipLaunchKernelGGL(wm_crop_div_kernel, wm_grid((size_t)H * W, n_img), dim3(256), 0, s, img_pad, ones_pad, H, W, r, out);
 }
 
+// skimage's img_as_float of an unsigned integer image (what gaussian() does to it first): np.multiply(image, 1.0 / max, dtype=float64)
+__global__ void wm_unit_f64_kernel(const uint16_t *__restrict__ img, size_t n, double inv_max, double *__restrict__ out)
+{
+    WM_LOOP(p, n) out[p] = (double)img[p] * inv_max;
+}
+void launch_wm_unit_f64(const uint16_t *img, size_t n, double inv_max, double *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(wm_unit_f64_kernel, wm_grid(n), dim3(256), 0, s, img, n, inv_max, out);
+}
+
 // well_mask_generation.py:165-170, :201-205: the mask's own pixels on the image border join canny's edges
 __global__ void wm_border_kernel(const uint8_t *__restrict__ m, int H, int W, uint8_t *__restrict__ edges)
 {

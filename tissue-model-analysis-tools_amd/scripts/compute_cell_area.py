@@ -6,7 +6,7 @@ same positional arguments, flags and config keys, same outputs (`thresholded/<id
     python compute_cell_area.py IN_ROOT OUT_ROOT [--channel N] [--time N] [--sd-coef F] [-c CONFIG] [-w [--well-seed N]]
 
 Z stacks (slice sequences or multi-page files) are max-projected first, as in the reference.  Differences
-(INTEGRATION.md): images are thresholded in batches on the GPU (tmat_cell_area_batch); the gaussian-mixture fit is
+(INTEGRATION.md): images are thresholded in batches on the GPU (tmat_cell_area_batch; -w: preprocessing.cell_area_stacks); the gaussian-mixture fit is
 deterministic, so `rs_seed` has no effect; -w/--detect-well takes an explicit --well-seed (the reference's superellipse search is
 unseeded); --time / --channel follow the reference's helper.load_image; files are read and written with Pillow.
 """
@@ -100,6 +100,10 @@ def main(argv=None):
 
     from PIL import Image
     from tmat_amd import _lib, distributed, preprocessing, zstacks
+    # Routes (tools/bench_cell_area.py; a case moves to preprocessing.cell_area_stacks only where its median beat the old route's by
+    # more than the spread of the old route's repeats): -w, on images and on Z stacks, goes through cell_area_stacks (17.8x and 10.9x); plain
+    # images stay on cell_area_batch (the new route measured 4 % slower); Z stacks without -w are still projected one by one (the new route's
+    # median was 1.9x better, 22.6 against 43.6 ms, but the old route's repeats spread over 24 ms)
     # one process per GPU under torch.distributed.run: images are independent, every rank takes a contiguous block of them,
     # rank 0 writes the CSV from the gathered rows; every rank writes the thresholded pictures of its own images
     ws, rank, local_rank = distributed.init_process_group_from_env()
@@ -112,13 +116,16 @@ def main(argv=None):
 
     def flush(group):
         for (shape, dtype), items in group.items():          # one dtype per batch: np.stack would silently widen a mixed group
-            batch = np.stack([im for _, im in items])
+            batch = np.stack([im for _, im in items])        # (k, H, W); -w on Z stacks: (k, Z, H, W), the key holds Z
+            well = None
             if args.detect_well:
-                area, kept, well = preprocessing.cell_area_batch_well(handle, batch, dsamp_size, sd_coef, args.well_seed)
-                for (img_id, _), wm_ in zip(items, well):
-                    wells[img_id] = wm_
+                # one resident path: projection fused with the down-sampling, well front, mask tail and fit once for the whole batch
+                area, kept, well = preprocessing.cell_area_stacks(handle, batch, dsamp_size, sd_coef, detect_well=True, well_seed=args.well_seed)
             else:
                 area, kept = preprocessing.cell_area_batch(handle, batch, dsamp_size, sd_coef)
+            if well is not None:
+                for (img_id, _), wm_ in zip(items, well):
+                    wells[img_id] = wm_
             for (img_id, _), a, k in zip(items, area, kept):
                 areas[img_id], kept_all[img_id] = a, k
 
@@ -129,7 +136,9 @@ def main(argv=None):
             for img_id in mine[i0:i0 + batch_size]:
                 try:
                     if is_stack:
-                        img = zstacks.proj_max(load_stack(paths[img_id], args.channel, args.time), handle=handle)     # compute_cell_area.py:50-52
+                        img = load_stack(paths[img_id], args.channel, args.time)
+                        if not args.detect_well:
+                            img = zstacks.proj_max(img, handle=handle)                       # compute_cell_area.py:50-52
                     else:
                         img = load_image_2d(paths[img_id], args.channel, args.time)
                 except (OSError, ValueError) as error:

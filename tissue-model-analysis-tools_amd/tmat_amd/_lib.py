@@ -130,6 +130,9 @@ def lib():
     L.tmat_cell_area_batch.argtypes = [vp, vp, i, i, i, i, i, d, vp, vp, vp]
     L.tmat_cell_area_masked.argtypes = [vp, vp, vp, i, i, i, d, vp, vp, vp]
     L.tmat_resize_linear_u16.argtypes = [vp, vp, i, i, i, i, i, vp]
+    L.tmat_cell_small_dev.argtypes = [vp, vp, i, i, i, i, i, i, i, vp]
+    L.tmat_cell_well_front_dev.argtypes = [vp, vp, i, i, i, i, vp, vp]
+    L.tmat_cell_area_fit_dev.argtypes = [vp, vp, vp, i, i, i, d, vp, vp, vp]
     L.tmat_resnet_load.argtypes = [vp, vp, sz, C.POINTER(i)]
     L.tmat_resnet_predict.argtypes = [vp, i, vp, i, i, vp]
     L.tmat_inv_depth_predict.argtypes = [vp, vp, i, vp, i, i, i, i, vp, vp]
@@ -200,6 +203,7 @@ EXPORTS = [
     "tmat_analyze_stack_batch", "tmat_vessel_field_batch", "tmat_stack_pass_plan", "tmat_debug_stack_trace",
     "tmat_analyze_batch_grid", "tmat_analyze_batch_grid_dev", "tmat_render_barcode", "tmat_render_barcode_png", "tmat_host_barcode_rects",
     "tmat_analyze_stack_batch_dev", "tmat_canny_mask_batch", "tmat_well_small_shape", "tmat_stack_well_front_dev",
+    "tmat_cell_small_dev", "tmat_cell_well_front_dev", "tmat_cell_area_fit_dev",
 ]
 
 

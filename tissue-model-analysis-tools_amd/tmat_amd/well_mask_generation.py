@@ -404,12 +404,12 @@ def make_well_masks_batch(x, handle: _lib.Handle, seed: int = 0, warn=print):
     return make_well_masks_from_front(thresh_small, border_small, shape, handle, seed, warn)
 
 
-def make_well_masks_from_front(thresh_small, border_small, shape, handle: _lib.Handle, seed: int = 0, warn=print):
-    """The tail of make_well_masks_batch, from the ConvexHull call on (generate_well_mask :172-233, make_well_mask): thresh_small,
-    border_small (n, sh, sw) -- every image's thresholded mask at the small shape and its border (canny + the mask's pixels on the image
-    border), from the per-image calls or from tmat_stack_well_front_dev -- and the images' shape -> (well (n, h, w) bool, shrunken
-    (n, h, w) bool).  Per image: convex hull, hull mask; one batched canny for the hull masks' borders (the choice of the exponent), one
-    superellipse search, one rasterisation + resize of the well masks and one rasterisation of the shrunken masks for the whole batch."""
+def _well_masks_from_front(thresh_small, border_small, shape, handle: _lib.Handle, seed: int, what: str):
+    """generate_well_mask from the ConvexHull call on (:172-233) for a batch, the part make_well_masks_from_front and
+    generate_well_masks_from_front share -> (well (n, h, w) bool, found, p_well, n_found): the well masks with generate_well_mask's own
+    fallbacks (the circle of get_circ_mask without a hull, the hull mask without a fit), the images that have a superellipse, and its
+    parameters (d already times 0.9) and exponent for each of those.  Per image: convex hull, hull mask; one batched canny for the hull
+    masks' borders (the choice of the exponent), one superellipse search, one rasterisation + resize of the well masks for the batch."""
     from scipy.spatial import ConvexHull
     try:
         from scipy.spatial import QhullError
@@ -417,8 +417,8 @@ def make_well_masks_from_front(thresh_small, border_small, shape, handle: _lib.H
         from scipy.spatial.qhull import QhullError
     thresh_small, border_small = np.asarray(thresh_small), np.asarray(border_small)
     if thresh_small.ndim != 3 or border_small.shape != thresh_small.shape:
-        raise ValueError("make_well_masks_from_front: (n, sh, sw) masks and borders expected")
-    n_img, shape = len(thresh_small), tuple(int(v) for v in shape)
+        raise ValueError(f"{what}: (n, sh, sw) masks and borders expected")
+    n_img = len(thresh_small)
     small_shape = tuple(thresh_small.shape[1:])
     hull_of = {}                                            # image -> (small hull mask, hull vertices)
     for i in range(n_img):
@@ -441,9 +441,8 @@ def make_well_masks_from_front(thresh_small, border_small, shape, handle: _lib.H
     for i in order:
         if fits[i] is None:
             print("Falling back to convex hull well mask.", flush=True)
-    # generate_well_mask: d *= 0.9, the mask at the small shape, resized; make_well_mask: d *= 0.9 once more, at the image shape
+    # generate_well_mask: d *= 0.9, the mask at the small shape, resized
     p_well = [(t, d * 0.9, s_a, s_b, c_x, c_y) for t, d, s_a, s_b, c_x, c_y in (fits[i] for i in found)]
-    p_shrunk = [(t, d * 0.9, s_a, s_b, c_x, c_y) for t, d, s_a, s_b, c_x, c_y in p_well]
     n_found = [hulls[i][1] for i in found]
     small = {i: hulls[i][0] for i in order}
     if found:
@@ -451,13 +450,35 @@ def make_well_masks_from_front(thresh_small, border_small, shape, handle: _lib.H
     well = np.zeros((n_img,) + tuple(shape), bool)
     if order:
         well[order] = resize_nearest_dev(handle, np.stack([small[i] for i in order]), shape) > 0
-    shrunken = np.zeros_like(well)
-    if found:
-        shrunken[found] = gen_superellipse_masks_dev(handle, p_shrunk, n_found, shape)
     for i in range(n_img):
         if i not in hulls:                                  # get_circ_mask (:172-182)
             rr, cc = np.indices(shape)
             well[i] = (rr - shape[0] // 2) ** 2 + (cc - shape[1] // 2) ** 2 < int(shape[0] * 0.5 * (1 - 0.95)) ** 2
+    return well, found, p_well, n_found
+
+
+def generate_well_masks_from_front(thresh_small, border_small, shape, handle: _lib.Handle, seed: int = 0, mask_val: Integral = 255):
+    """The tail of generate_well_mask (:172-233) for a batch: thresh_small, border_small (n, sh, sw) from tmat_cell_well_front_dev (or
+    the per-image calls) and the images' shape -> (n, h, w) uint8 masks, 0 / mask_val, equal to [generate_well_mask(x[i], mask_val)].
+    None of make_well_mask's rules applies here: a mask of low coverage stays as it is, and there is no shrunken mask."""
+    shape = tuple(int(v) for v in shape)
+    well = _well_masks_from_front(thresh_small, border_small, shape, handle, seed, "generate_well_masks_from_front")[0]
+    return well.astype(np.uint8) * np.uint8(mask_val)
+
+
+def make_well_masks_from_front(thresh_small, border_small, shape, handle: _lib.Handle, seed: int = 0, warn=print):
+    """The tail of make_well_masks_batch, from the ConvexHull call on (generate_well_mask :172-233, make_well_mask): thresh_small,
+    border_small (n, sh, sw) -- every image's thresholded mask at the small shape and its border (canny + the mask's pixels on the image
+    border), from the per-image calls or from tmat_stack_well_front_dev -- and the images' shape -> (well (n, h, w) bool, shrunken
+    (n, h, w) bool).  The well masks are _well_masks_from_front's; then make_well_mask's rules: one rasterisation of the shrunken masks
+    for the whole batch (d *= 0.9 once more, at the image shape), the eroded mask where the fit failed, the coverage rule."""
+    shape = tuple(int(v) for v in shape)
+    well, found, p_well, n_found = _well_masks_from_front(thresh_small, border_small, shape, handle, seed, "make_well_masks_from_front")
+    p_shrunk = [(t, d * 0.9, s_a, s_b, c_x, c_y) for t, d, s_a, s_b, c_x, c_y in p_well]
+    shrunken = np.zeros_like(well)
+    if found:
+        shrunken[found] = gen_superellipse_masks_dev(handle, p_shrunk, n_found, shape)
+    for i in range(len(well)):
         if i not in found:
             shrunken[i] = _erode_disk5(well[i])
         coverage = np.sum(well[i]) / well[i].size
