@@ -80,6 +80,20 @@ def test_null_handle_and_bad_opts_are_refused_without_a_device():
         assert fn(None, _lib.ptr(imgs), 1, 64, 64, C.byref(o), C.byref(bad_g), rows) == _lib.E_ARG
         assert fn(None, _lib.ptr(imgs), 1, 64, 64, None, C.byref(g), rows) == _lib.E_ARG
         assert fn(None, _lib.ptr(imgs), 1, 64, 64, C.byref(o), None, rows) == _lib.E_ARG
+    for fn in (L.tmat_analyze_batch_ex, L.tmat_analyze_batch_ex_dev):
+        assert fn(None, _lib.ptr(imgs), 1, 64, 64, C.byref(o), rows) == _lib.E_ARG                              # NULL handle
+        bad_o = _lib.AnalyzeOpts(size=C.sizeof(_lib.AnalyzeOpts) - 8, ds_ratio=0.625, ds_width=384)
+        assert fn(None, _lib.ptr(imgs), 1, 64, 64, C.byref(bad_o), rows) == _lib.E_ARG
+        assert fn(None, _lib.ptr(imgs), 1, 64, 64, None, rows) == _lib.E_ARG
+    # the five positional entries with a NULL handle
+    positional = (1, 64, 64, 0.625, 384, 5.0, 10.0, 12, 12, 0, 0, 0)
+    rgb, bars, nb = np.zeros((1, 100, 100, 3), np.uint8), np.zeros((1, 8, 2)), np.zeros(1, np.int32)
+    tree = (100, _lib.ptr(rgb), _lib.ptr(bars), 8, _lib.ptr(nb))
+    assert L.tmat_analyze_batch(None, _lib.ptr(imgs), *positional, rows) == _lib.E_ARG
+    assert L.tmat_analyze_batch_dev(None, _lib.ptr(imgs), *positional, rows) == _lib.E_ARG
+    assert L.tmat_analyze_batch_masked(None, _lib.ptr(imgs), *positional, None, None, rows) == _lib.E_ARG
+    assert L.tmat_analyze_batch_tree(None, _lib.ptr(imgs), *positional, rows, *tree) == _lib.E_ARG
+    assert L.tmat_analyze_batch_tree_dev(None, _lib.ptr(imgs), *positional, rows, *tree) == _lib.E_ARG
     assert all(r.index == -7 for r in rows)
     assert L.tmat_render_barcode(None, None, _lib.ptr(np.zeros(1, np.int32)), 0, 100, _lib.ptr(np.zeros(4, np.uint8))) == _lib.E_ARG
 

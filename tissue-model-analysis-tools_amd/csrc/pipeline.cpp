@@ -261,7 +261,7 @@ struct TreeJob {
     Canvas cv;
     double sf;                      // compute_branches.py:437: original_image.shape[1] / img_dsamp_res[1]
     uint8_t *rgb_out; double *bars_out; int cap_b; int *n_bars;     // caller's, whole call
-    const uint16_t *bg_all;         // (n, h, w) u16 on the device
+    uint16_t *bg_all;               // (n, h, w) u16 on the device, written by enqueue_pre
     OverlaySeg *dseg; size_t seg_cap; float *dmm; int *doff; uint8_t *drgb;
     // the grid form only (tmat_analyze_batch_grid*): rgb_out may then be null, and the pictures may leave as PNG files, encoded on the
     // third stream from the rasters in HBM (png_kernels.hip) -- the overlays from drgb, the barcodes from dbar (overlay_kernels.hip)
@@ -307,7 +307,7 @@ static int png_encode_job(const TreeJob &tj, const uint8_t *pics_dev, int k, con
 // the pass's own buffers (vis_kernels.hip) and copied to the caller's (n, 4, h, w) array per pass.
 struct StageJob {
     uint8_t *out;                   // caller's, whole call
-    const uint8_t *orig_all;        // (n, h, w) u8 on the device, written by enqueue_pre
+    uint8_t *orig_all;              // (n, h, w) u8 on the device, written by enqueue_pre
     uint8_t *pics;                  // (3, K, h, w) u8 on the device: prediction, mask, weighted of one pass
     void *mm;                       // vis_scratch_bytes(K)
     int K;
@@ -447,110 +447,150 @@ static void run_pass_host(Ctx *c, int slot, int k, const GraphParams gp, const G
                 (t1 - t0) * 1e3, (t_perm - t0) * 1e3, (t2 - t1) * 1e3, (now_s() - t2) * 1e3);
 }
 
-struct TreeReq { int vis_width; uint8_t *rgb_out; double *bars_out; int cap_b; int *n_bars; };
-// The masked form of a call (tmat_analyze_batch_masked), both on the HOST and either may be null: well (n, h, w) u8 multiplies the
-// network input and the thresholded mask, pruning (n, fh, fw) u8 is MorseGraph's pruning mask
-struct MaskReq { const uint8_t *well; const uint8_t *pruning; };
+// One call of the 2-D batch analysis family: what any tmat_analyze_batch* entry point can ask for.  Every entry fills one and hands it to
+// analyze_entry (below), which checks it, uploads host images and runs analyze_dev.
+struct AnalyzeCall {
+    const char *name;               // the entry point the caller called: heads the error messages
+    const uint16_t *imgs; bool host;        // (n, H, W) u16, on the host (analyze_entry uploads them) or on the device
+    int n, H, W;
+    double ds_ratio; int ds_width;
+    GraphParams gp;                 // fh / fw are filled by analyze_dev; t1 / t2 are not read in the grid form
+    int64_t first_index;
+    tmat_row *rows;
+    // the "with tree" form: rgb_out may be null in the grid form when the pictures leave as PNG files
+    bool tree; int vis_width; uint8_t *rgb_out; double *bars_out; int cap_b; int *n_bars;
+    // the masked form, both on the HOST and either may be null: well (n, h, w) u8 multiplies the network input and the thresholded mask,
+    // pruning (n, fh, fw) u8 is MorseGraph's pruning mask
+    const uint8_t *well, *pruning;
+    uint8_t *stage_out;             // nullable: (n, 4, h, w) u8 stage pictures
+    // nullable, tmat_analyze_batch_grid* only: the pairs of the call instead of gp.t1 / gp.t2 -- rows and the tree outputs gain a leading
+    // n_thresh axis, and the pictures may leave as PNG files
+    const tmat_grid_opts *grid;
+};
 
-// grid (nullable, tmat_analyze_batch_grid* only): the pairs of the call instead of gp.t1 / gp.t2 -- rows and the tree outputs of req gain a
-// leading n_thresh axis, req->rgb_out may be null, and the pictures may leave as PNG files
-static int analyze_dev(Ctx *c, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width, GraphParams gp,
-                       int64_t first_index, tmat_row *rows, const TreeReq *req = nullptr, const MaskReq *masks = nullptr, uint8_t *stage_out = nullptr,
-                       const tmat_grid_opts *grid = nullptr)
+// The canvas of a tree request and the file shapes of the grid form's PNG outputs: checked (capacities included) before anything is
+// allocated or queued
+static int tree_shapes(const AnalyzeCall &call, int h, int w, TreeJob &tj)
 {
+    const std::string name = call.name;
+    const tmat_grid_opts *grid = call.grid;
+    if (!canvas_of(h, w, call.vis_width, tj.cv)) { set_error("analyze (tree): empty canvas"); return TMAT_E_ARG; }
+    if (grid && grid->tree_png) {
+        if (!png_shape(tj.cv.vh, tj.cv.vw, 3, tj.pg_tree)) { set_error(name + ": canvas too large for one PNG file"); return TMAT_E_ARG; }
+        if (grid->tree_png_cap < tj.pg_tree.bound) { set_error(name + ": tree_png_cap is below tmat_png_bound"); return TMAT_E_CAP; }
+        tj.tree_png = grid->tree_png; tj.tree_png_cap = grid->tree_png_cap; tj.tree_png_sizes = grid->tree_png_sizes;
+    }
+    if (grid && grid->barcode_png) {
+        tj.S = barcode_side(call.vis_width);
+        if (!png_shape(tj.S, tj.S, 3, tj.pg_bar)) { set_error(name + ": empty barcode canvas, or one too large for a PNG file"); return TMAT_E_ARG; }
+        if (grid->barcode_png_cap < tj.pg_bar.bound) { set_error(name + ": barcode_png_cap is below tmat_png_bound"); return TMAT_E_CAP; }
+        tj.barcode_png = grid->barcode_png; tj.barcode_png_cap = grid->barcode_png_cap; tj.barcode_png_sizes = grid->barcode_png_sizes;
+    }
+    return TMAT_OK;
+}
+
+// scratch of the "with tree" form: the handle's tool workspaces, sized before any pass is in flight (tj holds tree_shapes' results)
+static int tree_setup(Ctx *c, const AnalyzeCall &call, int h, int w, int K, const GraphParams &gp, TreeJob &tj)
+{
+    const size_t cper = (size_t)tj.cv.vh * tj.cv.vw * 3, fper = (size_t)gp.fh * gp.fw;
+    tj.sf = (double)w / (double)gp.fw;
+    tj.rgb_out = call.rgb_out; tj.bars_out = call.bars_out; tj.cap_b = call.cap_b; tj.n_bars = call.n_bars;
+    tj.seg_cap = (size_t)K * fper;
+    tj.bg_all = (uint16_t *)ws_get(c, WS_TREE_BG, (size_t)call.n * h * w * sizeof(uint16_t));
+    tj.dseg = (OverlaySeg *)ws_get(c, WS_TREE_SEG, tj.seg_cap * sizeof(OverlaySeg));
+    tj.dmm = (float *)ws_get(c, WS_TREE_MM, (size_t)K * 4 * sizeof(float) + (size_t)(K + 1) * sizeof(int));
+    tj.drgb = (uint8_t *)ws_get(c, WS_TREE_RGB, (size_t)K * cper);
+    if (!tj.bg_all || !tj.dseg || !tj.dmm || !tj.drgb) return TMAT_E_HIP;
+    tj.doff = (int *)(tj.dmm + 4 * (size_t)K);
+    if (tj.barcode_png) {       // rectangle tables (<= cap_b bars per image) and the K barcode canvases of a pass
+        tj.drect = (BarRect *)ws_get(c, WS_GRID_BAR_RECT, (size_t)K * (size_t)call.cap_b * sizeof(BarRect) + (size_t)(K + 1) * sizeof(int) + 16);
+        tj.dbar = (uint8_t *)ws_get(c, WS_GRID_BAR_RGB, (size_t)K * tj.S * tj.S * 3);
+        if (!tj.drect || !tj.dbar) return TMAT_E_HIP;
+        tj.drect_off = (int *)(tj.drect + (size_t)K * (size_t)call.cap_b);       // BarRect is five words: word-aligned
+    }
+    if (tj.tree_png || tj.barcode_png) {        // encoder scratch (png.h:png_encode_launch) for the larger of the two shapes
+        size_t filt = 0, slots = 0, files = 0, meta_words = 0, kp_max = 0;
+        for (const PngShape *pg : {tj.tree_png ? &tj.pg_tree : nullptr, tj.barcode_png ? &tj.pg_bar : nullptr}) {
+            if (!pg) continue;
+            const size_t kp = (size_t)png_chunk(*pg, K);
+            filt = std::max(filt, kp * pg->raw); slots = std::max(slots, kp * pg->ns * PNG_SLOT);
+            files = std::max(files, kp * png_fcap(*pg)); meta_words = std::max(meta_words, kp * pg->ns * 4); kp_max = std::max(kp_max, kp);
+        }
+        tj.png_filt = (uint8_t *)ws_get(c, WS_GRID_PNG_FILT, filt); tj.png_slots = (uint8_t *)ws_get(c, WS_GRID_PNG_SLOTS, slots);
+        tj.png_files = (uint8_t *)ws_get(c, WS_GRID_PNG_FILES, files);
+        tj.png_meta = (uint32_t *)ws_get(c, WS_GRID_PNG_META, (meta_words + kp_max) * sizeof(uint32_t));     // the file sizes ride behind the stripe records
+        if (!tj.png_filt || !tj.png_slots || !tj.png_files || !tj.png_meta) return TMAT_E_HIP;
+        tj.png_dsz = tj.png_meta + meta_words;
+    }
+    return TMAT_OK;
+}
+
+// the well masks go up once per call, into a workspace of the handle; one seg buffer serves every pass (the tails share a stream)
+static int well_setup(Ctx *c, const AnalyzeCall &call, int h, int w, int K, const uint8_t *&well_all, uint8_t *&seg)
+{
+    uint8_t *wd = (uint8_t *)ws_get(c, WS_WELL_MASK, (size_t)call.n * h * w);
+    seg = (uint8_t *)ws_get(c, WS_WELL_SEG, (size_t)K * h * w);
+    if (!wd || !seg) return TMAT_E_HIP;
+    if (!hip_ok(hipMemcpy(wd, call.well, (size_t)call.n * h * w, hipMemcpyHostToDevice), "H2D(well masks)")) return TMAT_E_HIP;
+    well_all = wd;
+    return TMAT_OK;
+}
+
+// scratch of the stage pictures: tool workspaces as well, sized before any pass is in flight
+static int stage_setup(Ctx *c, const AnalyzeCall &call, int h, int w, int K, StageJob &sj)
+{
+    sj.orig_all = (uint8_t *)ws_get(c, WS_STAGE_ORIG, (size_t)call.n * h * w);
+    sj.pics = (uint8_t *)ws_get(c, WS_STAGE_PIC, 3 * (size_t)K * h * w);
+    sj.mm = ws_get(c, WS_STAGE_MM, vis_scratch_bytes(K));
+    if (!sj.orig_all || !sj.pics || !sj.mm) return TMAT_E_HIP;
+    sj.out = call.stage_out; sj.K = K;
+    return TMAT_OK;
+}
+
+// a checked call with its images on the device: geometry, buffers, the three set-up steps, the pass loop
+static int analyze_dev(Ctx *c, const AnalyzeCall &call)
+{
+    const int n = call.n, H = call.H, W = call.W;
+    tmat_row *rows = call.rows;
     // compute_branches.py:309-312 hands target_shape = round(shape * ds_ratio) = (round(H r), round(W r)) to cv2.resize as
     // dsize, which cv2 reads as (width, height): the resized image has round(W r) rows and round(H r) columns.  Square
     // images are unaffected; for the others the network sees the reference's (anisotropically scaled) image and the
     // later resize to (fh, fw) restores the aspect ratio, exactly as in the reference.
-    const int h = round_half_even((double)W * ds_ratio), w = round_half_even((double)H * ds_ratio);
+    const int h = round_half_even((double)W * call.ds_ratio), w = round_half_even((double)H * call.ds_ratio);
     if (h < 1 || w < 1) { set_error("analyze: target shape is empty"); return TMAT_E_ARG; }
-    gp.fh = round_half_even((double)H * ((double)ds_width / (double)W));
-    gp.fw = round_half_even((double)W * ((double)ds_width / (double)W));
-    // the file capacities of the grid form are checked here, before anything is allocated or queued
+    GraphParams gp = call.gp;
+    gp.fh = round_half_even((double)H * ((double)call.ds_width / (double)W));
+    gp.fw = round_half_even((double)W * ((double)call.ds_width / (double)W));
     const float one_pair[2] = {gp.t1, gp.t2};
-    const GridJob gj{grid ? grid->n_thresh : 1, grid ? grid->thresh : one_pair, n};
-    TreeJob tj{}, *tree = nullptr;
-    if (req && !canvas_of(h, w, req->vis_width, tj.cv)) { set_error("analyze (tree): empty canvas"); return TMAT_E_ARG; }
-    if (req && grid && grid->tree_png) {
-        if (!png_shape(tj.cv.vh, tj.cv.vw, 3, tj.pg_tree)) { set_error("tmat_analyze_batch_grid: canvas too large for one PNG file"); return TMAT_E_ARG; }
-        if (grid->tree_png_cap < tj.pg_tree.bound) { set_error("tmat_analyze_batch_grid: tree_png_cap is below tmat_png_bound"); return TMAT_E_CAP; }
-        tj.tree_png = grid->tree_png; tj.tree_png_cap = grid->tree_png_cap; tj.tree_png_sizes = grid->tree_png_sizes;
-    }
-    if (req && grid && grid->barcode_png) {
-        tj.S = barcode_side(req->vis_width);
-        if (!png_shape(tj.S, tj.S, 3, tj.pg_bar)) { set_error("tmat_analyze_batch_grid: empty barcode canvas, or one too large for a PNG file"); return TMAT_E_ARG; }
-        if (grid->barcode_png_cap < tj.pg_bar.bound) { set_error("tmat_analyze_batch_grid: barcode_png_cap is below tmat_png_bound"); return TMAT_E_CAP; }
-        tj.barcode_png = grid->barcode_png; tj.barcode_png_cap = grid->barcode_png_cap; tj.barcode_png_sizes = grid->barcode_png_sizes;
-    }
+    const GridJob gj{call.grid ? call.grid->n_thresh : 1, call.grid ? call.grid->thresh : one_pair, n};
+    TreeJob tj{};
+    StageJob sj{};
+    TreeJob *tree = call.tree ? &tj : nullptr;
+    StageJob *stage = call.stage_out ? &sj : nullptr;
+    int rc = tree ? tree_shapes(call, h, w, tj) : TMAT_OK;
+    if (rc) return rc;
     TileGeom g = make_geom(h, w, c->patch);
     roi_attach(c, g);       // region form of the up path: g carries the class-major patch order for enqueue_pre / enqueue_back
     const int K = std::min(n, std::max(1, c->max_patches / g.tiles_per_img));      // one image per pass when it needs > max_patches
-    { int rc0 = ensure_patch_io(c, K * g.tiles_per_img); if (rc0) return rc0; }
-    int rc = ensure_pass_buffers(c, K, H, W, h, w, gp.fh, gp.fw);
+    rc = ensure_patch_io(c, K * g.tiles_per_img);
+    if (!rc) rc = ensure_pass_buffers(c, K, H, W, h, w, gp.fh, gp.fw);
     if (!rc) rc = ensure_ma_table(c);
     if (rc) return rc;
-    for (size_t r = 0; r < (size_t)gj.T * n; r++) { rows[r].index = first_index + (int64_t)(r % (size_t)n); rows[r].count = 0; rows[r].total_px = 0; rows[r].avg_px = 0; }
-    if (req) {      // scratch of the "with tree" form: the handle's tool workspaces, sized here before any pass is in flight
-        const size_t cper = (size_t)tj.cv.vh * tj.cv.vw * 3, fper = (size_t)gp.fh * gp.fw;
-        tj.sf = (double)w / (double)gp.fw;
-        tj.rgb_out = req->rgb_out; tj.bars_out = req->bars_out; tj.cap_b = req->cap_b; tj.n_bars = req->n_bars;
-        tj.seg_cap = (size_t)K * fper;
-        uint16_t *bg_all = (uint16_t *)ws_get(c, WS_TREE_BG, (size_t)n * h * w * sizeof(uint16_t));
-        tj.dseg = (OverlaySeg *)ws_get(c, WS_TREE_SEG, tj.seg_cap * sizeof(OverlaySeg));
-        tj.dmm = (float *)ws_get(c, WS_TREE_MM, (size_t)K * 4 * sizeof(float) + (size_t)(K + 1) * sizeof(int));
-        tj.drgb = (uint8_t *)ws_get(c, WS_TREE_RGB, (size_t)K * cper);
-        if (!bg_all || !tj.dseg || !tj.dmm || !tj.drgb) return TMAT_E_HIP;
-        tj.bg_all = bg_all;
-        tj.doff = (int *)(tj.dmm + 4 * (size_t)K);
-        if (tj.barcode_png) {       // rectangle tables (<= cap_b bars per image) and the K barcode canvases of a pass
-            tj.drect = (BarRect *)ws_get(c, WS_GRID_BAR_RECT, (size_t)K * (size_t)req->cap_b * sizeof(BarRect) + (size_t)(K + 1) * sizeof(int) + 16);
-            tj.dbar = (uint8_t *)ws_get(c, WS_GRID_BAR_RGB, (size_t)K * tj.S * tj.S * 3);
-            if (!tj.drect || !tj.dbar) return TMAT_E_HIP;
-            tj.drect_off = (int *)(tj.drect + (size_t)K * (size_t)req->cap_b);       // BarRect is five words: word-aligned
-        }
-        if (tj.tree_png || tj.barcode_png) {        // encoder scratch (png.h:png_encode_launch) for the larger of the two shapes
-            size_t filt = 0, slots = 0, files = 0, meta_words = 0, kp_max = 0;
-            for (const PngShape *pg : {tj.tree_png ? &tj.pg_tree : nullptr, tj.barcode_png ? &tj.pg_bar : nullptr}) {
-                if (!pg) continue;
-                const size_t kp = (size_t)png_chunk(*pg, K);
-                filt = std::max(filt, kp * pg->raw); slots = std::max(slots, kp * pg->ns * PNG_SLOT);
-                files = std::max(files, kp * png_fcap(*pg)); meta_words = std::max(meta_words, kp * pg->ns * 4); kp_max = std::max(kp_max, kp);
-            }
-            tj.png_filt = (uint8_t *)ws_get(c, WS_GRID_PNG_FILT, filt); tj.png_slots = (uint8_t *)ws_get(c, WS_GRID_PNG_SLOTS, slots);
-            tj.png_files = (uint8_t *)ws_get(c, WS_GRID_PNG_FILES, files);
-            tj.png_meta = (uint32_t *)ws_get(c, WS_GRID_PNG_META, (meta_words + kp_max) * sizeof(uint32_t));     // the file sizes ride behind the stripe records
-            if (!tj.png_filt || !tj.png_slots || !tj.png_files || !tj.png_meta) return TMAT_E_HIP;
-            tj.png_dsz = tj.png_meta + meta_words;
-        }
-        tree = &tj;
-    }
-    auto bg_at = [&](int p) { return tree ? const_cast<uint16_t *>(tj.bg_all) + (size_t)p * K * h * w : nullptr; };
-    // the well masks go up once per call, into a workspace of the handle; one seg buffer serves every pass (the tails share a stream)
-    const uint8_t *well_all = nullptr, *pruning = masks ? masks->pruning : nullptr;
+    for (size_t r = 0; r < (size_t)gj.T * n; r++) { rows[r].index = call.first_index + (int64_t)(r % (size_t)n); rows[r].count = 0; rows[r].total_px = 0; rows[r].avg_px = 0; }
+    const uint8_t *well_all = nullptr, *pruning = call.pruning;
     uint8_t *seg = nullptr;
-    if (masks && masks->well) {
-        uint8_t *wd = (uint8_t *)ws_get(c, WS_WELL_MASK, (size_t)n * h * w);
-        seg = (uint8_t *)ws_get(c, WS_WELL_SEG, (size_t)K * h * w);
-        if (!wd || !seg) return TMAT_E_HIP;
-        if (!hip_ok(hipMemcpy(wd, masks->well, (size_t)n * h * w, hipMemcpyHostToDevice), "H2D(well masks)")) return TMAT_E_HIP;
-        well_all = wd;
-    }
-    StageJob sj{}, *stage = nullptr;
-    if (stage_out) {    // scratch of the stage pictures: tool workspaces as well, sized here before any pass is in flight
-        uint8_t *orig_all = (uint8_t *)ws_get(c, WS_STAGE_ORIG, (size_t)n * h * w);
-        sj.pics = (uint8_t *)ws_get(c, WS_STAGE_PIC, 3 * (size_t)K * h * w);
-        sj.mm = ws_get(c, WS_STAGE_MM, vis_scratch_bytes(K));
-        if (!orig_all || !sj.pics || !sj.mm) return TMAT_E_HIP;
-        sj.out = stage_out; sj.orig_all = orig_all; sj.K = K;
-        stage = &sj;
-    }
-    auto orig_at = [&](int p) { return stage ? const_cast<uint8_t *>(sj.orig_all) + (size_t)p * K * h * w : nullptr; };
+    if (tree) rc = tree_setup(c, call, h, w, K, gp, tj);
+    if (!rc && call.well) rc = well_setup(c, call, h, w, K, well_all, seg);
+    if (!rc && stage) rc = stage_setup(c, call, h, w, K, sj);
+    if (rc) return rc;
+    auto bg_at = [&](int p) { return tree ? tj.bg_all + (size_t)p * K * h * w : nullptr; };
+    auto orig_at = [&](int p) { return stage ? sj.orig_all + (size_t)p * K * h * w : nullptr; };
     auto well_at = [&](int p) { return well_all ? well_all + (size_t)p * K * h * w : nullptr; };
     auto prune_at = [&](int p) { return pruning ? pruning + (size_t)p * K * gp.fh * gp.fw : nullptr; };
     const int P = (n + K - 1) / K;
     PassJob jobs[2];
     auto cnt = [&](int p) { return std::min(K, n - p * K); };
-    auto img_at = [&](int p) { return imgs_dev + (size_t)p * K * H * W; };
+    auto img_at = [&](int p) { return call.imgs + (size_t)p * K * H * W; };
     // the caller may have queued work that produces the images on the main stream (tmat_zproj_dev, tmat_dev_upload)
     if (!use_one_stream() && !hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize")) return TMAT_E_HIP;
     // second input buffer for the front end that runs ahead on the second stream (enqueue_pre)
@@ -936,17 +976,70 @@ int tmat_medial_axis_batch(tmat_handle hd, const uint8_t *mask, int n, int hh, i
     return mem.finish();
 }
 
+// The 2-D batch analysis family: nine entry points, one path.  Each fills an AnalyzeCall and hands it to analyze_entry.
+
+// the one complete argument check, the same for host and device images
+static bool analyze_args_ok(const Ctx *c, const AnalyzeCall &call)
+{
+    const tmat_grid_opts *g = call.grid;
+    const bool png = g && (g->tree_png || g->barcode_png);
+    return c && call.imgs && call.rows && call.n >= 0 && call.H >= 1 && call.W >= 1 && call.ds_width >= 1 &&
+           (!call.tree || (call.vis_width >= 1 && call.bars_out && call.cap_b >= 0 && call.n_bars && (call.rgb_out || png))) &&
+           (!g || ((!g->tree_png || g->tree_png_sizes) && (!g->barcode_png || g->barcode_png_sizes)));
+}
+
+// model, arguments, n == 0, device, upload of host images, analyze_dev -- in this order: a refused call has touched nothing
+static int analyze_entry(tmat_handle hd, const AnalyzeCall &call)
+{
+    Ctx *c = (Ctx *)hd;
+    const std::string name = call.name;
+    if (c && !has_model(c)) { set_error(name + ": this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
+    if (call.grid && (call.grid->n_thresh < 1 || !call.grid->thresh)) { set_error(name + ": n_thresh < 1 or no thresholds"); return TMAT_E_ARG; }
+    if (!analyze_args_ok(c, call)) { set_error(name + ": bad argument"); return TMAT_E_ARG; }
+    if (call.n == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    if (!call.host) return analyze_dev(c, call);
+    DevScope mem(c->ws_pool, nullptr);       // blocking copy below: nothing to drain
+    const size_t px = (size_t)call.n * call.H * call.W;
+    uint16_t *dimg = mem.alloc<uint16_t>(px);
+    if (!mem.ok) return TMAT_E_HIP;
+    if (!hip_ok(hipMemcpy(dimg, call.imgs, px * 2, hipMemcpyHostToDevice), "H2D")) return TMAT_E_HIP;
+    AnalyzeCall dev = call;
+    dev.imgs = dimg;
+    return analyze_dev(c, dev);
+}
+
+// the extensible forms: the structs' sizes are checked here, where they are first read and before any field is touched
+static int analyze_entry_opts(const char *name, tmat_handle hd, const uint16_t *imgs, bool host, int n, int H, int W, const tmat_analyze_opts *o,
+                              const tmat_grid_opts *g, bool grid_form, tmat_row *rows)
+{
+    if (!o || o->size != (uint32_t)sizeof(tmat_analyze_opts)) { set_error(std::string(name) + ": unknown tmat_analyze_opts size"); return TMAT_E_ARG; }
+    if (grid_form && (!g || g->size != (uint32_t)sizeof(tmat_grid_opts))) { set_error(std::string(name) + ": unknown tmat_grid_opts size"); return TMAT_E_ARG; }
+    const bool tree = o->rgb_out || (g && (g->tree_png || g->barcode_png));
+    return analyze_entry(hd, AnalyzeCall{name, imgs, host, n, H, W, o->ds_ratio, o->ds_width,
+                                         {0, 0, o->graph_thresh_1, o->graph_thresh_2, o->smoothing_window_px, o->min_branch_length_px, o->max_branch_length_px, o->remove_isolated},
+                                         o->first_index, rows, tree, o->vis_width, o->rgb_out, o->bars_out, o->cap_b, o->n_bars, o->well_masks, o->pruning_masks,
+                                         o->stage_out, g});
+}
+
+int tmat_analyze_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, double ds_ratio, int ds_width,
+                       float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
+                       int max_branch_length_px, int remove_isolated, int64_t first_index, tmat_row *rows)
+{
+    AnalyzeCall call{"tmat_analyze_batch", imgs, true, n, H, W, ds_ratio, ds_width,
+                  {0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated},
+                  first_index, rows};
+    return analyze_entry(hd, call);
+}
+
 int tmat_analyze_batch_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width,
                            float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
                            int max_branch_length_px, int remove_isolated, int64_t first_index, tmat_row *rows)
 {
-    Ctx *c = (Ctx *)hd;
-    if (c && !has_model(c)) { set_error("tmat_analyze_batch_dev: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
-    if (!c || !imgs_dev || !rows || n < 0 || H < 1 || W < 1 || ds_width < 1) { set_error("tmat_analyze_batch_dev: bad argument"); return TMAT_E_ARG; }
-    if (n == 0) return TMAT_OK;
-    TMAT_HIP(hipSetDevice(c->device));
-    GraphParams gp{0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated};
-    return analyze_dev(c, imgs_dev, n, H, W, ds_ratio, ds_width, gp, first_index, rows);
+    AnalyzeCall call{"tmat_analyze_batch_dev", imgs_dev, false, n, H, W, ds_ratio, ds_width,
+                  {0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated},
+                  first_index, rows};
+    return analyze_entry(hd, call);
 }
 
 int tmat_analyze_batch_masked(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, double ds_ratio, int ds_width,
@@ -954,36 +1047,11 @@ int tmat_analyze_batch_masked(tmat_handle hd, const uint16_t *imgs, int n, int H
                               int max_branch_length_px, int remove_isolated, int64_t first_index, const uint8_t *well_masks,
                               const uint8_t *pruning_masks, tmat_row *rows)
 {
-    Ctx *c = (Ctx *)hd;
-    if (c && !has_model(c)) { set_error("tmat_analyze_batch_masked: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
-    if (!c || !imgs || !rows || n < 0 || H < 1 || W < 1 || ds_width < 1) { set_error("tmat_analyze_batch_masked: bad argument"); return TMAT_E_ARG; }
-    if (n == 0) return TMAT_OK;
-    TMAT_HIP(hipSetDevice(c->device));
-    DevScope mem(c->ws_pool, nullptr);       // blocking copy below: nothing to drain
-    uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
-    if (!mem.ok) return TMAT_E_HIP;
-    if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) return TMAT_E_HIP;
-    GraphParams gp{0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated};
-    MaskReq mr{well_masks, pruning_masks};
-    return analyze_dev(c, dimg, n, H, W, ds_ratio, ds_width, gp, first_index, rows, nullptr, &mr);
-}
-
-int tmat_analyze_batch_tree_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width,
-                                float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
-                                int max_branch_length_px, int remove_isolated, int64_t first_index, tmat_row *rows, int vis_width,
-                                uint8_t *rgb_out, double *bars_out, int cap_b, int *n_bars)
-{
-    Ctx *c = (Ctx *)hd;
-    if (c && !has_model(c)) { set_error("tmat_analyze_batch_tree_dev: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
-    if (!c || !imgs_dev || !rows || n < 0 || H < 1 || W < 1 || ds_width < 1 || vis_width < 1 || !rgb_out || !bars_out || cap_b < 0 || !n_bars) {
-        set_error("tmat_analyze_batch_tree_dev: bad argument");
-        return TMAT_E_ARG;
-    }
-    if (n == 0) return TMAT_OK;
-    TMAT_HIP(hipSetDevice(c->device));
-    GraphParams gp{0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated};
-    TreeReq req{vis_width, rgb_out, bars_out, cap_b, n_bars};
-    return analyze_dev(c, imgs_dev, n, H, W, ds_ratio, ds_width, gp, first_index, rows, &req);
+    AnalyzeCall call{"tmat_analyze_batch_masked", imgs, true, n, H, W, ds_ratio, ds_width,
+                  {0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated},
+                  first_index, rows};
+    call.well = well_masks; call.pruning = pruning_masks;
+    return analyze_entry(hd, call);
 }
 
 int tmat_analyze_batch_tree(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, double ds_ratio, int ds_width,
@@ -991,96 +1059,43 @@ int tmat_analyze_batch_tree(tmat_handle hd, const uint16_t *imgs, int n, int H, 
                             int max_branch_length_px, int remove_isolated, int64_t first_index, tmat_row *rows, int vis_width,
                             uint8_t *rgb_out, double *bars_out, int cap_b, int *n_bars)
 {
-    Ctx *c = (Ctx *)hd;
-    if (c && !has_model(c)) { set_error("tmat_analyze_batch_tree: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
-    if (!c || !imgs || !rows || n < 0 || H < 1 || W < 1) { set_error("tmat_analyze_batch_tree: bad argument"); return TMAT_E_ARG; }
-    if (n == 0) return TMAT_OK;
-    TMAT_HIP(hipSetDevice(c->device));
-    DevScope mem(c->ws_pool, nullptr);       // blocking copy below: nothing to drain
-    uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
-    if (!mem.ok) return TMAT_E_HIP;
-    int rc = TMAT_OK;
-    if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) rc = TMAT_E_HIP;
-    if (!rc) rc = tmat_analyze_batch_tree_dev(hd, dimg, n, H, W, ds_ratio, ds_width, graph_thresh_1, graph_thresh_2, smoothing_window_px,
-                                              min_branch_length_px, max_branch_length_px, remove_isolated, first_index, rows, vis_width,
-                                              rgb_out, bars_out, cap_b, n_bars);
-    return rc;
+    AnalyzeCall call{"tmat_analyze_batch_tree", imgs, true, n, H, W, ds_ratio, ds_width,
+                  {0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated},
+                  first_index, rows};
+    call.tree = true; call.vis_width = vis_width; call.rgb_out = rgb_out; call.bars_out = bars_out; call.cap_b = cap_b; call.n_bars = n_bars;
+    return analyze_entry(hd, call);
 }
 
-int tmat_analyze_batch_ex_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, const tmat_analyze_opts *o, tmat_row *rows)
+int tmat_analyze_batch_tree_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, double ds_ratio, int ds_width,
+                                float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
+                                int max_branch_length_px, int remove_isolated, int64_t first_index, tmat_row *rows, int vis_width,
+                                uint8_t *rgb_out, double *bars_out, int cap_b, int *n_bars)
 {
-    Ctx *c = (Ctx *)hd;
-    if (c && !has_model(c)) { set_error("tmat_analyze_batch_ex: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
-    if (!o || o->size != (uint32_t)sizeof(tmat_analyze_opts)) { set_error("tmat_analyze_batch_ex: unknown tmat_analyze_opts size"); return TMAT_E_ARG; }
-    if (!c || !imgs_dev || !rows || n < 0 || H < 1 || W < 1 || o->ds_width < 1 ||
-        (o->rgb_out && (o->vis_width < 1 || !o->bars_out || o->cap_b < 0 || !o->n_bars))) {
-        set_error("tmat_analyze_batch_ex: bad argument");
-        return TMAT_E_ARG;
-    }
-    if (n == 0) return TMAT_OK;
-    TMAT_HIP(hipSetDevice(c->device));
-    GraphParams gp{0, 0, o->graph_thresh_1, o->graph_thresh_2, o->smoothing_window_px, o->min_branch_length_px, o->max_branch_length_px, o->remove_isolated};
-    TreeReq req{o->vis_width, o->rgb_out, o->bars_out, o->cap_b, o->n_bars};
-    MaskReq mr{o->well_masks, o->pruning_masks};
-    return analyze_dev(c, imgs_dev, n, H, W, o->ds_ratio, o->ds_width, gp, o->first_index, rows, o->rgb_out ? &req : nullptr,
-                       (o->well_masks || o->pruning_masks) ? &mr : nullptr, o->stage_out);
+    AnalyzeCall call{"tmat_analyze_batch_tree_dev", imgs_dev, false, n, H, W, ds_ratio, ds_width,
+                  {0, 0, graph_thresh_1, graph_thresh_2, smoothing_window_px, min_branch_length_px, max_branch_length_px, remove_isolated},
+                  first_index, rows};
+    call.tree = true; call.vis_width = vis_width; call.rgb_out = rgb_out; call.bars_out = bars_out; call.cap_b = cap_b; call.n_bars = n_bars;
+    return analyze_entry(hd, call);
 }
 
 int tmat_analyze_batch_ex(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, const tmat_analyze_opts *o, tmat_row *rows)
 {
-    Ctx *c = (Ctx *)hd;
-    if (c && !has_model(c)) { set_error("tmat_analyze_batch_ex: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
-    if (!o || o->size != (uint32_t)sizeof(tmat_analyze_opts)) { set_error("tmat_analyze_batch_ex: unknown tmat_analyze_opts size"); return TMAT_E_ARG; }
-    if (!c || !imgs || !rows || n < 0 || H < 1 || W < 1) { set_error("tmat_analyze_batch_ex: bad argument"); return TMAT_E_ARG; }
-    if (n == 0) return TMAT_OK;
-    TMAT_HIP(hipSetDevice(c->device));
-    DevScope mem(c->ws_pool, nullptr);       // blocking copy below: nothing to drain
-    uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
-    if (!mem.ok) return TMAT_E_HIP;
-    if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) return TMAT_E_HIP;
-    return tmat_analyze_batch_ex_dev(hd, dimg, n, H, W, o, rows);
+    return analyze_entry_opts("tmat_analyze_batch_ex", hd, imgs, true, n, H, W, o, nullptr, false, rows);
 }
 
-// every argument check of the grid form, before the device is touched
-static int grid_args(const Ctx *c, const void *imgs, int n, int H, int W, const tmat_analyze_opts *o, const tmat_grid_opts *g, const tmat_row *rows)
+int tmat_analyze_batch_ex_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, const tmat_analyze_opts *o, tmat_row *rows)
 {
-    if (c && !has_model(c)) { set_error("tmat_analyze_batch_grid: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
-    if (!o || o->size != (uint32_t)sizeof(tmat_analyze_opts)) { set_error("tmat_analyze_batch_grid: unknown tmat_analyze_opts size"); return TMAT_E_ARG; }
-    if (!g || g->size != (uint32_t)sizeof(tmat_grid_opts)) { set_error("tmat_analyze_batch_grid: unknown tmat_grid_opts size"); return TMAT_E_ARG; }
-    if (g->n_thresh < 1 || !g->thresh) { set_error("tmat_analyze_batch_grid: n_thresh < 1 or no thresholds"); return TMAT_E_ARG; }
-    const bool tree = o->rgb_out || g->tree_png || g->barcode_png;
-    if (!c || !imgs || !rows || n < 0 || H < 1 || W < 1 || o->ds_width < 1 || (tree && (o->vis_width < 1 || !o->bars_out || o->cap_b < 0 || !o->n_bars)) ||
-        (g->tree_png && !g->tree_png_sizes) || (g->barcode_png && !g->barcode_png_sizes)) {
-        set_error("tmat_analyze_batch_grid: bad argument");
-        return TMAT_E_ARG;
-    }
-    return TMAT_OK;
-}
-
-int tmat_analyze_batch_grid_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, const tmat_analyze_opts *o, const tmat_grid_opts *g, tmat_row *rows)
-{
-    Ctx *c = (Ctx *)hd;
-    if (int rc = grid_args(c, imgs_dev, n, H, W, o, g, rows)) return rc;
-    if (n == 0) return TMAT_OK;
-    TMAT_HIP(hipSetDevice(c->device));
-    GraphParams gp{0, 0, g->thresh[0], g->thresh[1], o->smoothing_window_px, o->min_branch_length_px, o->max_branch_length_px, o->remove_isolated};
-    TreeReq req{o->vis_width, o->rgb_out, o->bars_out, o->cap_b, o->n_bars};
-    MaskReq mr{o->well_masks, o->pruning_masks};
-    return analyze_dev(c, imgs_dev, n, H, W, o->ds_ratio, o->ds_width, gp, o->first_index, rows, (o->rgb_out || g->tree_png || g->barcode_png) ? &req : nullptr,
-                       (o->well_masks || o->pruning_masks) ? &mr : nullptr, o->stage_out, g);
+    return analyze_entry_opts("tmat_analyze_batch_ex_dev", hd, imgs_dev, false, n, H, W, o, nullptr, false, rows);
 }
 
 int tmat_analyze_batch_grid(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, const tmat_analyze_opts *o, const tmat_grid_opts *g, tmat_row *rows)
 {
-    Ctx *c = (Ctx *)hd;
-    if (int rc = grid_args(c, imgs, n, H, W, o, g, rows)) return rc;
-    if (n == 0) return TMAT_OK;
-    TMAT_HIP(hipSetDevice(c->device));
-    DevScope mem(c->ws_pool, nullptr);       // blocking copy below: nothing to drain
-    uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
-    if (!mem.ok) return TMAT_E_HIP;
-    if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) return TMAT_E_HIP;
-    return tmat_analyze_batch_grid_dev(hd, dimg, n, H, W, o, g, rows);
+    return analyze_entry_opts("tmat_analyze_batch_grid", hd, imgs, true, n, H, W, o, g, true, rows);
+}
+
+int tmat_analyze_batch_grid_dev(tmat_handle hd, const uint16_t *imgs_dev, int n, int H, int W, const tmat_analyze_opts *o, const tmat_grid_opts *g, tmat_row *rows)
+{
+    return analyze_entry_opts("tmat_analyze_batch_grid_dev", hd, imgs_dev, false, n, H, W, o, g, true, rows);
 }
 
 // a (n, per) of dtype TMAT_PIC_* -> out (n, per) u8: extrema and picture kernels of vis_kernels.hip, chunked to bound device memory
@@ -1110,25 +1125,6 @@ int tmat_stage_pictures(tmat_handle hd, const void *a, int dtype, int n, size_t 
         if (mem.finish()) return TMAT_E_HIP;
     }
     return TMAT_OK;
-}
-
-int tmat_analyze_batch(tmat_handle hd, const uint16_t *imgs, int n, int H, int W, double ds_ratio, int ds_width,
-                       float graph_thresh_1, float graph_thresh_2, int smoothing_window_px, int min_branch_length_px,
-                       int max_branch_length_px, int remove_isolated, int64_t first_index, tmat_row *rows)
-{
-    Ctx *c = (Ctx *)hd;
-    if (c && !has_model(c)) { set_error("tmat_analyze_batch: this handle has no model (tmat_create_plain)"); return TMAT_E_ARG; }
-    if (!c || !imgs || !rows || n < 0) { set_error("tmat_analyze_batch: bad argument"); return TMAT_E_ARG; }
-    if (n == 0) return TMAT_OK;
-    TMAT_HIP(hipSetDevice(c->device));
-    DevScope mem(c->ws_pool, nullptr);       // blocking copy below: nothing to drain
-    uint16_t *dimg = mem.alloc<uint16_t>((size_t)n * H * W);
-    if (!mem.ok) return TMAT_E_HIP;
-    int rc = TMAT_OK;
-    if (!hip_ok(hipMemcpy(dimg, imgs, (size_t)n * H * W * 2, hipMemcpyHostToDevice), "H2D")) rc = TMAT_E_HIP;
-    if (!rc) rc = tmat_analyze_batch_dev(hd, dimg, n, H, W, ds_ratio, ds_width, graph_thresh_1, graph_thresh_2, smoothing_window_px,
-                                         min_branch_length_px, max_branch_length_px, remove_isolated, first_index, rows);
-    return rc;
 }
 
 }  // extern "C"

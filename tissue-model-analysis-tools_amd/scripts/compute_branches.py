@@ -190,6 +190,39 @@ def load_stack(files, channel=None, time=None) -> np.ndarray:
     return a
 
 
+def make_load_fn(loader, paths, args):
+    """run_sharded's load_fn over loader (load_image_2d or load_stack): an unreadable entry prints the failure and raises InputError"""
+    from tmat_amd import branches
+
+    def load_fn(img_id):
+        try:
+            return loader(paths[img_id], args.channel, args.time)
+        except (OSError, ValueError) as error:
+            print(f"{FAIL}{error}", flush=True)
+            raise branches.InputError(str(error))
+    return load_fn
+
+
+def make_width_fn(config, paths):
+    """run_sharded's width_fn.  image_width_microns: the option / config key, else per image from the file's metadata (reference
+    compute_branches.py:184-212: img.shape[-1] * PhysicalPixelSizes.X; of a slice sequence: its first file), else the reference's
+    failure message"""
+    from tmat_amd import branches, helper
+
+    def width_fn(img_id, img):
+        width_um = config.get("image_width_microns")
+        if width_um is None:
+            px = helper.physical_pixel_sizes(str(np.atleast_1d(paths[img_id])[0])).X
+            if px is None:
+                print(f"{FAIL} The --image-width-microns parameter was not specified, and the pixel to micron conversion "
+                      f"factor was not found in the image metadata ({img_id}). Specify --image-width-microns and try again. "
+                      "Exiting...", flush=True)
+                raise branches.InputError(img_id)
+            width_um = img.shape[-1] * px
+        return width_um
+    return width_fn
+
+
 def write_results(args, config, ids, gathered, out_root: Path, rank: int):
     """the CSV per threshold configuration and config.json (compute_branches.py:459-500, 596-600), written by rank 0"""
     from tmat_amd import branches
@@ -226,7 +259,7 @@ def finish_distributed(ws: int):
 
 def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_rank: int):
     """Z-stack entries: the Sato branch (compute_branches.py:224-306) on this rank's share of the stacks"""
-    from tmat_amd import _lib, branches, distributed, helper, sato
+    from tmat_amd import _lib, branches, distributed, sato
     handle = _lib.Handle(None, local_rank)          # this branch needs no segmentation model
     hessian = getattr(args, "sato_hessian", "gaussian_derivatives")
     vis = bool(getattr(args, "visualizations", False))
@@ -255,24 +288,7 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
             from PIL import Image
             Image.fromarray((well * 255).astype(np.uint8)).save(out_root / "visualizations" / img_id / "well_mask.png")
 
-    def load_fn(img_id):
-        try:
-            return load_stack(paths[img_id], args.channel, args.time)
-        except (OSError, ValueError) as error:
-            print(f"{FAIL}{error}", flush=True)
-            raise branches.InputError(str(error))
-
-    def width_fn(img_id, st):
-        width_um = config.get("image_width_microns")
-        if width_um is None:
-            px = helper.physical_pixel_sizes(np.atleast_1d(paths[img_id])[0]).X
-            if px is None:
-                print(f"{FAIL} The --image-width-microns parameter was not specified, and the pixel to micron conversion "
-                      f"factor was not found in the image metadata ({img_id}). Specify --image-width-microns and try again. "
-                      "Exiting...", flush=True)
-                raise branches.InputError(img_id)
-            width_um = st.shape[-1] * px
-        return width_um
+    load_fn, width_fn = make_load_fn(load_stack, paths, args), make_width_fn(config, paths)
 
     def analyze_batch_fn(batch, width_um, thresh, ids):
         # one upload and one pass over the whole chunk and the whole grid; run_sharded then asks configuration by configuration
@@ -416,7 +432,7 @@ def main(args=None):
         sys.exit(1)
     # image_width_microns: the option / config key, else per image from the file's metadata (reference
     # compute_branches.py:184-212: img.shape[-1] * PhysicalPixelSizes.X), else the reference's failure message
-    from tmat_amd import branches, distributed, helper, models
+    from tmat_amd import branches, distributed, models
     ws = distributed.world()[0]
     # host stages (thinning, DMT, MorseGraph) run on worker threads of every rank: share the cores between the ranks
     os.environ.setdefault("TMAT_HOST_THREADS", str(distributed.host_threads_per_rank(ws)))
@@ -434,27 +450,7 @@ def main(args=None):
 
     # ids are file stems, as in the reference (compute_branches.py:565-569: two files with one stem are one entry there too)
     ids = sorted(paths)
-
-    def load_fn(img_id):
-        try:
-            return load_image_2d(paths[img_id], args.channel, args.time)
-        except (OSError, ValueError) as error:
-            print(f"{FAIL}{error}", flush=True)
-            raise branches.InputError(str(error))
-
-    def width_fn(img_id, img):
-        # image_width_microns: the option / config key, else per image from the file's metadata (reference
-        # compute_branches.py:184-212: img.shape[-1] * PhysicalPixelSizes.X), else the reference's failure message
-        width_um = config.get("image_width_microns")
-        if width_um is None:
-            px = helper.physical_pixel_sizes(paths[img_id]).X
-            if px is None:
-                print(f"{FAIL} The --image-width-microns parameter was not specified, and the pixel to micron conversion "
-                      f"factor was not found in the image metadata ({img_id}). Specify --image-width-microns and try again. "
-                      "Exiting...", flush=True)
-                raise branches.InputError(img_id)
-            width_um = img.shape[-1] * px
-        return width_um
+    load_fn, width_fn = make_load_fn(load_image_2d, paths, args), make_width_fn(config, paths)
 
     well_cache = {}
 

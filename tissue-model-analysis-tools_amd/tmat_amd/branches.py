@@ -53,26 +53,79 @@ def threshold_grid(config: dict):
     return out
 
 
+# The marshalling the analyze_batch* functions share: every one of them describes its call with these and hands it to its own C entry.
+
+def _shapes(H: int, W: int, ds_ratio: float):
+    """((hh, ww), (fh, fw)) of (H, W) images: the network's input shape -- cv2 reads dsize as (width, height) -- and the field's"""
+    return (int(round(W * ds_ratio)), int(round(H * ds_ratio))), dsamp_shape((H, W))
+
+
+def _as_u8(m, shape, who: str, what: str):
+    """a caller's masks (None passes through) as a contiguous 0 / 1 u8 array of `shape`"""
+    if m is None:
+        return None
+    m = np.asarray(m)
+    if m.shape != tuple(shape):
+        raise ValueError(f"{who}: {what} have shape {m.shape}, expected {tuple(shape)}")
+    return np.ascontiguousarray(m != 0, np.uint8)
+
+
+def _graph_fields(config: dict, image_width_microns: float, first_index: int) -> dict:
+    """the graph parameters in pixels and the first index, under tmat_analyze_opts' field names and in the positional entries' order"""
+    sw_px, min_px, max_px = graph_px_params(config, DOWNSAMPLE_WIDTH, image_width_microns)
+    return dict(smoothing_window_px=int(sw_px), min_branch_length_px=int(min_px), max_branch_length_px=int(max_px or 0),
+                remove_isolated=int(bool(config.get("remove_isolated_branches", False))), first_index=int(first_index))
+
+
+def _positional_args(shape, config: dict, image_width_microns: float, ds_ratio: float, thresh, first_index: int):
+    """what tmat_analyze_batch, _masked and _tree take between the image pointer and their own outputs; shape = (n, H, W)"""
+    return (*shape, float(ds_ratio), DOWNSAMPLE_WIDTH, float(thresh[0]), float(thresh[1]),
+            *_graph_fields(config, image_width_microns, first_index).values())
+
+
+def _analyze_opts(config: dict, image_width_microns: float, ds_ratio: float, first_index: int, thresh=(0.0, 0.0), well=None, pruning=None):
+    """tmat_analyze_opts without requests; well / pruning: _as_u8's arrays, which the caller keeps alive"""
+    return _lib.AnalyzeOpts(size=C.sizeof(_lib.AnalyzeOpts), ds_ratio=float(ds_ratio), ds_width=DOWNSAMPLE_WIDTH, graph_thresh_1=float(thresh[0]),
+                            graph_thresh_2=float(thresh[1]), well_masks=None if well is None else well.ctypes.data,
+                            pruning_masks=None if pruning is None else pruning.ctypes.data,
+                            **_graph_fields(config, image_width_microns, first_index))
+
+
+def _entry(handle: _lib.Handle, name: str, input_bits: int):
+    """C entry point `name` bound to the handle, whose input depth is set first"""
+    L = _lib.lib()
+    _lib.check(L.tmat_set_input_depth(handle.raw, int(input_bits)), "tmat_set_input_depth")
+    fn = getattr(L, name)
+    return lambda *args: fn(handle.raw, *args)
+
+
+def _retry_bars(lead_shape, cap_bars: int, full: int, call):
+    """call(bars, cap) -> return code, with bars an empty (*lead_shape, cap, 2) f64 array.  A branch holds at least one vertex of its own,
+    so `full` = fh * fw bars always suffice: one retry with that capacity when cap_bars is too small.  Returns (code, bars)."""
+    for cap in (int(cap_bars), max(int(cap_bars), full)):
+        bars = np.empty(tuple(lead_shape) + (cap, 2), np.float64)
+        rc = call(bars, cap)
+        if rc != _lib.E_CAP or cap >= full:
+            break
+    return rc, bars
+
+
+def _row_tuples(rows):
+    return [(r.index, r.count, r.total_px, r.avg_px) for r in rows]
+
+
 def analyze_batch(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_width_microns: float, ds_ratio: float = 0.625,
                   thresh=(5.0, 10.0), first_index: int = 0, dev_ptr=None, input_bits: int = 16):
     """imgs (n, H, W) uint16 (host) or a device pointer + shape -> list of (index, count, total_px, avg_px).
     `input_bits` = 8 for images that were uint8 before widening (cv2.resize saturates to the source depth)."""
     if dev_ptr is None:
         imgs = np.ascontiguousarray(imgs, np.uint16)
-        n, H, W = imgs.shape
-    else:
-        n, H, W = imgs       # shape tuple
-    sw_px, min_px, max_px = graph_px_params(config, DOWNSAMPLE_WIDTH, image_width_microns)
-    rows = (_lib.Row * n)()
-    L = _lib.lib()
-    _lib.check(L.tmat_set_input_depth(handle.raw, int(input_bits)), "tmat_set_input_depth")
-    args = (n, H, W, float(ds_ratio), DOWNSAMPLE_WIDTH, float(thresh[0]), float(thresh[1]), int(sw_px), int(min_px),
-            int(max_px or 0), int(bool(config.get("remove_isolated_branches", False))), int(first_index), rows)
-    if dev_ptr is None:
-        _lib.check(L.tmat_analyze_batch(handle.raw, _lib.ptr(imgs), *args), "tmat_analyze_batch")
-    else:
-        _lib.check(L.tmat_analyze_batch_dev(handle.raw, C.c_void_p(dev_ptr), *args), "tmat_analyze_batch_dev")
-    return [(r.index, r.count, r.total_px, r.avg_px) for r in rows]
+    shape = imgs.shape if dev_ptr is None else tuple(imgs)
+    rows = (_lib.Row * shape[0])()
+    name = "tmat_analyze_batch" if dev_ptr is None else "tmat_analyze_batch_dev"
+    _lib.check(_entry(handle, name, input_bits)(_lib.ptr(imgs) if dev_ptr is None else C.c_void_p(dev_ptr),
+                                                *_positional_args(shape, config, image_width_microns, ds_ratio, thresh, first_index), rows), name)
+    return _row_tuples(rows)
 
 
 def analyze_batch_tree(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_width_microns: float, ds_ratio: float = 0.625,
@@ -81,25 +134,16 @@ def analyze_batch_tree(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
     (n, vh, vw, 3) u8 drawn per pass on the device over the down-sampled images, [bars (k, 2) f64 scaled] per image)."""
     imgs = np.ascontiguousarray(imgs, np.uint16)
     n, H, W = imgs.shape
-    sw_px, min_px, max_px = graph_px_params(config, DOWNSAMPLE_WIDTH, image_width_microns)
+    (hh, ww), (fh, fw) = _shapes(H, W, ds_ratio)
     rows = (_lib.Row * n)()
-    hh, ww = int(round(W * ds_ratio)), int(round(H * ds_ratio))            # cv2 reads dsize as (width, height)
-    vh, vw = _lib.tree_canvas_shape(hh, ww, vis_width)
-    rgb = np.empty((n, vh, vw, 3), np.uint8)
+    rgb = np.empty((n,) + tuple(_lib.tree_canvas_shape(hh, ww, vis_width)) + (3,), np.uint8)
     nb = np.zeros(n, np.int32)
-    L = _lib.lib()
-    _lib.check(L.tmat_set_input_depth(handle.raw, int(input_bits)), "tmat_set_input_depth")
-    fh, fw = dsamp_shape((H, W))
-    # a branch holds at least one vertex of its own, so fh * fw bars always suffice: one retry with that capacity when cap_bars is too small
-    for cap in (int(cap_bars), max(int(cap_bars), fh * fw)):
-        bars = np.empty((n, cap, 2), np.float64)
-        rc = L.tmat_analyze_batch_tree(handle.raw, _lib.ptr(imgs), n, H, W, float(ds_ratio), DOWNSAMPLE_WIDTH, float(thresh[0]), float(thresh[1]),
-                                       int(sw_px), int(min_px), int(max_px or 0), int(bool(config.get("remove_isolated_branches", False))),
-                                       int(first_index), rows, int(vis_width), _lib.ptr(rgb), _lib.ptr(bars), cap, _lib.ptr(nb))
-        if rc != _lib.E_CAP or cap >= fh * fw:
-            break
+    fn = _entry(handle, "tmat_analyze_batch_tree", input_bits)
+    args = _positional_args(imgs.shape, config, image_width_microns, ds_ratio, thresh, first_index)
+    rc, bars = _retry_bars((n,), cap_bars, fh * fw, lambda bars, cap: fn(_lib.ptr(imgs), *args, rows, int(vis_width), _lib.ptr(rgb), _lib.ptr(bars),
+                                                                          cap, _lib.ptr(nb)))
     _lib.check(rc, "tmat_analyze_batch_tree")
-    return [(r.index, r.count, r.total_px, r.avg_px) for r in rows], rgb, [bars[i, : nb[i]].copy() for i in range(n)]
+    return _row_tuples(rows), rgb, [bars[i, : nb[i]].copy() for i in range(n)]
 
 
 def analyze_batch_ex(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_width_microns: float, ds_ratio: float = 0.625,
@@ -113,25 +157,11 @@ def analyze_batch_ex(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_
     Returns (rows, extras) with extras a dict holding "overlays" and "bars" (tree) and "pictures" (stage_pictures)."""
     imgs = np.ascontiguousarray(imgs, np.uint16)
     n, H, W = imgs.shape
-    hh, ww = int(round(W * ds_ratio)), int(round(H * ds_ratio))            # cv2 reads dsize as (width, height)
-    fh, fw = dsamp_shape((H, W))
-
-    def as_u8(m, shape, what):
-        if m is None:
-            return None
-        m = np.asarray(m)
-        if m.shape != (n,) + tuple(shape):
-            raise ValueError(f"analyze_batch_ex: {what} have shape {m.shape}, expected {(n,) + tuple(shape)}")
-        return np.ascontiguousarray(m != 0, np.uint8)
-    well = as_u8(well_masks, (hh, ww), "well_masks")
-    pruning = as_u8(pruning_masks, (fh, fw), "pruning_masks")
-    sw_px, min_px, max_px = graph_px_params(config, DOWNSAMPLE_WIDTH, image_width_microns)
+    (hh, ww), (fh, fw) = _shapes(H, W, ds_ratio)
+    well = _as_u8(well_masks, (n, hh, ww), "analyze_batch_ex", "well_masks")
+    pruning = _as_u8(pruning_masks, (n, fh, fw), "analyze_batch_ex", "pruning_masks")
     rows = (_lib.Row * n)()
-    o = _lib.AnalyzeOpts(size=C.sizeof(_lib.AnalyzeOpts), ds_ratio=float(ds_ratio), ds_width=DOWNSAMPLE_WIDTH, graph_thresh_1=float(thresh[0]),
-                         graph_thresh_2=float(thresh[1]), smoothing_window_px=int(sw_px), min_branch_length_px=int(min_px),
-                         max_branch_length_px=int(max_px or 0), remove_isolated=int(bool(config.get("remove_isolated_branches", False))),
-                         first_index=int(first_index), well_masks=None if well is None else well.ctypes.data,
-                         pruning_masks=None if pruning is None else pruning.ctypes.data)
+    o = _analyze_opts(config, image_width_microns, ds_ratio, first_index, thresh, well, pruning)
     extras = {}
     if stage_pictures:
         extras["pictures"] = np.empty((n, 4, hh, ww), np.uint8)
@@ -141,20 +171,17 @@ def analyze_batch_ex(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_
         vh, vw = _lib.tree_canvas_shape(hh, ww, vis_width)
         extras["overlays"] = np.empty((n, vh, vw, 3), np.uint8)
         o.vis_width, o.rgb_out, o.n_bars = int(vis_width), extras["overlays"].ctypes.data, nb.ctypes.data
-    L = _lib.lib()
-    _lib.check(L.tmat_set_input_depth(handle.raw, int(input_bits)), "tmat_set_input_depth")
-    # a branch holds at least one vertex of its own, so fh * fw bars always suffice: one retry with that capacity when cap_bars is too small
-    for cap in (int(cap_bars), max(int(cap_bars), fh * fw)):
-        bars = np.empty((n, cap if tree else 0, 2), np.float64)
+    fn = _entry(handle, "tmat_analyze_batch_ex", input_bits)
+
+    def call(bars, cap):
         if tree:
             o.bars_out, o.cap_b = bars.ctypes.data, cap
-        rc = L.tmat_analyze_batch_ex(handle.raw, _lib.ptr(imgs), n, H, W, C.byref(o), rows) if n else 0
-        if rc != _lib.E_CAP or cap >= fh * fw:
-            break
+        return fn(_lib.ptr(imgs), n, H, W, C.byref(o), rows) if n else 0
+    rc, bars = _retry_bars((n,), cap_bars, fh * fw, call) if tree else (call(None, 0), None)
     _lib.check(rc, "tmat_analyze_batch_ex")
     if tree:
         extras["bars"] = [bars[i, : nb[i]].copy() for i in range(n)]
-    return [(r.index, r.count, r.total_px, r.avg_px) for r in rows], extras
+    return _row_tuples(rows), extras
 
 
 def grid_pairs(config: dict):
@@ -199,19 +226,9 @@ def analyze_batch_grid(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
         raise ValueError("analyze_batch_grid: no threshold pair")
     tree = bool(tree or tree_png or barcode_png)
     raw = bool(tree and raw_overlays)
-    hh, ww = int(round(W * ds_ratio)), int(round(H * ds_ratio))            # cv2 reads dsize as (width, height)
-    fh, fw = dsamp_shape((H, W))
-
-    def as_u8(m, shape, what):
-        if m is None:
-            return None
-        m = np.asarray(m)
-        if m.shape != (n,) + tuple(shape):
-            raise ValueError(f"analyze_batch_grid: {what} have shape {m.shape}, expected {(n,) + tuple(shape)}")
-        return np.ascontiguousarray(m != 0, np.uint8)
-    well = as_u8(well_masks, (hh, ww), "well_masks")
-    pruning = as_u8(pruning_masks, (fh, fw), "pruning_masks")
-    sw_px, min_px, max_px = graph_px_params(config, DOWNSAMPLE_WIDTH, image_width_microns)
+    (hh, ww), (fh, fw) = _shapes(H, W, ds_ratio)
+    well = _as_u8(well_masks, (n, hh, ww), "analyze_batch_grid", "well_masks")
+    pruning = _as_u8(pruning_masks, (n, fh, fw), "analyze_batch_grid", "pruning_masks")
     rows_by = {p: [] for p in pairs}
     extras = {}
     if tree:
@@ -231,8 +248,7 @@ def analyze_batch_grid(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
             extras["pictures"] = np.empty((0, 4, hh, ww), np.uint8)
         return rows_by, extras
     thresh = np.ascontiguousarray(np.asarray(pairs, np.float32).reshape(T, 2))
-    L = _lib.lib()
-    _lib.check(L.tmat_set_input_depth(handle.raw, int(input_bits)), "tmat_set_input_depth")
+    fn = _entry(handle, "tmat_analyze_batch_grid", input_bits)
     vh = vw = S = tcap = bcap = 0
     if tree:
         vh, vw = _lib.tree_canvas_shape(hh, ww, vis_width)
@@ -244,11 +260,8 @@ def analyze_batch_grid(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
     for i0 in range(0, n, step):
         k = min(step, n - i0)
         rows = (_lib.Row * (T * k))()
-        o = _lib.AnalyzeOpts(size=C.sizeof(_lib.AnalyzeOpts), ds_ratio=float(ds_ratio), ds_width=DOWNSAMPLE_WIDTH, smoothing_window_px=int(sw_px),
-                             min_branch_length_px=int(min_px), max_branch_length_px=int(max_px or 0),
-                             remove_isolated=int(bool(config.get("remove_isolated_branches", False))), first_index=int(first_index) + i0,
-                             well_masks=None if well is None else well[i0:].ctypes.data,
-                             pruning_masks=None if pruning is None else pruning[i0:].ctypes.data)
+        o = _analyze_opts(config, image_width_microns, ds_ratio, int(first_index) + i0, well=None if well is None else well[i0:],
+                          pruning=None if pruning is None else pruning[i0:])
         g = _lib.GridOpts(size=C.sizeof(_lib.GridOpts), n_thresh=T, thresh=thresh.ctypes.data)
         if stage_pictures:
             pics.append(np.empty((k, 4, hh, ww), np.uint8))
@@ -265,17 +278,15 @@ def analyze_batch_grid(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
             if barcode_png:
                 bfiles, bsizes = np.empty((T, k, bcap), np.uint8), np.zeros((T, k), np.uintp)
                 g.barcode_png, g.barcode_png_cap, g.barcode_png_sizes = bfiles.ctypes.data, bcap, bsizes.ctypes.data
-        # a branch holds at least one vertex of its own, so fh * fw bars always suffice: one retry with that capacity when cap_bars is too small
-        for cap in (int(cap_bars), max(int(cap_bars), fh * fw)):
-            bars = np.empty((T, k, cap if tree else 0, 2), np.float64)
+
+        def call(bars, cap):
             if tree:
                 o.bars_out, o.cap_b = bars.ctypes.data, cap
-            rc = L.tmat_analyze_batch_grid(handle.raw, _lib.ptr(imgs[i0:]), k, H, W, C.byref(o), C.byref(g), rows)
-            if rc != _lib.E_CAP or cap >= fh * fw or not tree:
-                break
+            return fn(_lib.ptr(imgs[i0:]), k, H, W, C.byref(o), C.byref(g), rows)
+        rc, bars = _retry_bars((T, k), cap_bars, fh * fw, call) if tree else (call(None, 0), None)
         _lib.check(rc, "tmat_analyze_batch_grid")
         for t, p in enumerate(pairs):
-            rows_by[p] += [(r.index, r.count, r.total_px, r.avg_px) for r in rows[t * k:(t + 1) * k]]
+            rows_by[p] += _row_tuples(rows[t * k:(t + 1) * k])
             if tree:
                 extras["bars"][p] += [bars[t, i, : nb[t, i]].copy() for i in range(k)]
             if raw:
@@ -445,27 +456,14 @@ def analyze_batch_masked(handle: _lib.Handle, imgs: np.ndarray, config: dict, im
     fields, (fh, fw) = dsamp_shape((H, W)), prune the graphs.  Either may be None; with both None the rows are analyze_batch's."""
     imgs = np.ascontiguousarray(imgs, np.uint16)
     n, H, W = imgs.shape
-    hh, ww = int(round(W * ds_ratio)), int(round(H * ds_ratio))            # cv2 reads dsize as (width, height)
-    fshape = dsamp_shape((H, W))
-
-    def as_u8(m, shape, what):
-        if m is None:
-            return None
-        m = np.asarray(m)
-        if m.shape != (n,) + tuple(shape):
-            raise ValueError(f"analyze_batch_masked: {what} have shape {m.shape}, expected {(n,) + tuple(shape)}")
-        return np.ascontiguousarray(m != 0, np.uint8)
-    well = as_u8(well_masks, (hh, ww), "well_masks")
-    pruning = as_u8(pruning_masks, fshape, "pruning_masks")
-    sw_px, min_px, max_px = graph_px_params(config, DOWNSAMPLE_WIDTH, image_width_microns)
+    (hh, ww), (fh, fw) = _shapes(H, W, ds_ratio)
+    well = _as_u8(well_masks, (n, hh, ww), "analyze_batch_masked", "well_masks")
+    pruning = _as_u8(pruning_masks, (n, fh, fw), "analyze_batch_masked", "pruning_masks")
     rows = (_lib.Row * n)()
-    L = _lib.lib()
-    _lib.check(L.tmat_set_input_depth(handle.raw, int(input_bits)), "tmat_set_input_depth")
-    _lib.check(L.tmat_analyze_batch_masked(handle.raw, _lib.ptr(imgs), n, H, W, float(ds_ratio), DOWNSAMPLE_WIDTH, float(thresh[0]), float(thresh[1]),
-                                           int(sw_px), int(min_px), int(max_px or 0), int(bool(config.get("remove_isolated_branches", False))),
-                                           int(first_index), None if well is None else _lib.ptr(well), None if pruning is None else _lib.ptr(pruning),
-                                           rows), "tmat_analyze_batch_masked")
-    return [(r.index, r.count, r.total_px, r.avg_px) for r in rows]
+    _lib.check(_entry(handle, "tmat_analyze_batch_masked", input_bits)(
+        _lib.ptr(imgs), *_positional_args(imgs.shape, config, image_width_microns, ds_ratio, thresh, first_index),
+        None if well is None else _lib.ptr(well), None if pruning is None else _lib.ptr(pruning), rows), "tmat_analyze_batch_masked")
+    return _row_tuples(rows)
 
 
 def analyze_batch_well(handle: _lib.Handle, imgs: np.ndarray, config: dict, image_width_microns: float, ds_ratio: float = 0.625,
