@@ -1099,6 +1099,31 @@ int tmat_roi_down_schedule(int hh, int ww, int patch, int n_up, const int *up_ch
  * launched.  TMAT_OK when the launcher would take them; TMAT_E_ARG with the reason in tmat_last_error otherwise.
  */
 int tmat_debug_share_fill_check(int n_patches, int side, int channels, const int *neighbours, int n_items, const int *items);
+/*
+ * The QUADRANT table of a plain fused separable layer (layer = 6 b + 1 of a fused level) for a pass of k images under form 3, 4 or 5
+ * (the numbers of tmat_roi_down_schedule; anything else, and every other layer, is refused).  The kernel is organised in 8 x 8
+ * quadrants, so a launch may visit any four of them as one packed tile: the table walks the tiles of tmat_roi_sep_tiles_share in
+ * their order and lists, per tile in (qy, qx) row-major order, the full-frame id  patch * QW * QW + qy * QW + qx  (QW = side / 8) of
+ * every quadrant that holds a pixel of comp (tmat_roi_plan_share); then all four quadrants of every tile of the k all-constant patches
+ * behind the pass's patches; then the last id again until the length is a multiple of 4.  counts [4]: the table's length, the ids of
+ * the pass's own patches, all ids before the padding, the full-frame tile count of the pass's own patches.  ids (nullable: counts
+ * only) takes the table, cap its room.  Host arithmetic, no GPU.
+ * The plain fused launches take the table where the shared-interior form or one above it runs, by the switch TMAT_ROI_QUAD (read at
+ * tmat_create, 0 or 1): unset, the batch pipeline uses it and tmat_predict_smooth does not; 0: nobody; 1: both.  tmat_debug_sep_tiles
+ * then reports the launch's packed tiles (without the constant patches': ceil(counts[1] / 4)) as planned.
+ */
+int tmat_roi_sep_quads(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                       unsigned fused_mask, int form, int layer, int k, int cap, int *counts, int *ids);
+/*
+ * Test-only (tests/test_gpu_sep_quads.py): ONE plain fused separable launch in quadrant form on host buffers with the caller's list of
+ * n_quads full-frame quadrant ids (any order, any patches, repeats allowed; padded to a multiple of 4 with the last id).  x: (n, hh, ww,
+ * cin) float32, or, with the stem's taps [9][cin] and folded batch norm given (all three or none; relu_in 0), the single-channel patches
+ * (n, 2 hh, 2 ww) the stem is recomputed from.  dw9: depthwise taps [9][cin]; pw: pointwise weights in the Keras layout (cin, cout).
+ * out (n, hh, ww, cout) is caller-filled and changed in place: words of quadrants that are not listed come back as they went in.
+ */
+int tmat_debug_sepconv_quads(tmat_handle h, const float *x, int n, int hh, int ww, int cin, int relu_in, const float *dw9, const float *pw,
+                             int cout, const float *scale, const float *shift, int relu_out, const float *stem_w, const float *stem_scale,
+                             const float *stem_shift, const int *quads, int n_quads, float *out);
 
 /*
  * Test-only (tests/test_gpu_roi_sep.py): the fused separable launches of the handle's last down pass, in launch order -- planned[i]

@@ -844,6 +844,42 @@ long long roi_sep_tile_table(const RoiPlan &p, RoiDownForm form, int layer, int 
     return full;
 }
 
+long long roi_sep_quad_table(const RoiPlan &p, RoiDownForm form, int layer, int k, std::vector<int> &out, long long *n_own, long long *n_ids)
+{
+    out.clear();
+    *n_own = *n_ids = 0;
+    const RoiDownPlan &d = p.down;
+    // (asked for the shared-interior form or above: a plan in which no class shares resolves it to the constant-ring form, whose comp is live)
+    if (form < ROI_DOWN_SHARE || roi_down_form(p, form) < ROI_DOWN_CONST || layer < 0 || layer % 6 != 1 || d.comp.empty()) return 0;
+    form = roi_down_form(p, form);
+    std::vector<int> tiles;
+    const long long full = roi_sep_tile_table(p, form, layer, k, tiles);
+    if (full <= 0) return 0;
+    const int TW = d.res[layer] / 16, TPP = TW * TW, QW = 2 * TW, QPP = QW * QW;
+    if (((long long)k * p.tiles_per_img + k) * QPP > 0x7fffffffLL) return 0;
+    // the class of a patch of the pass's class-major order
+    std::vector<int> cls_of((size_t)k * p.tiles_per_img, 0);
+    for (int cl = 0; cl < p.n_classes; cl++)
+        for (int pt = k * p.class_base[cl]; pt < k * p.class_base[cl + 1]; pt++) cls_of[pt] = cl;
+    auto holds = [&](int cl, int axis, int q) {         // does quadrant row / column q hold a comp row / column of the class?
+        const unsigned char *m = d.comp.data() + (((size_t)layer * ROI_MAX_CLASSES + cl) * 2 + axis) * p.ws + 8 * q;
+        return std::any_of(m, m + 8, [](unsigned char v) { return v != 0; });
+    };
+    for (int id : tiles) {
+        const int pt = id / TPP, tr = id % TPP, ty = tr / TW, tx = tr % TW, cl = cls_of[pt];
+        for (int qy = 2 * ty; qy < 2 * ty + 2; qy++)
+            for (int qx = 2 * tx; qx < 2 * tx + 2; qx++)
+                if (holds(cl, 0, qy) && holds(cl, 1, qx)) out.push_back(pt * QPP + qy * QW + qx);
+    }
+    *n_own = (long long)out.size();
+    for (int pt = k * p.tiles_per_img; pt < k * p.tiles_per_img + k; pt++)      // tile by tile: a whole tile comes out as itself
+        for (int tr = 0; tr < TPP; tr++)
+            for (int s = 0; s < 4; s++) out.push_back(pt * QPP + (2 * (tr / TW) + (s >> 1)) * QW + 2 * (tr % TW) + (s & 1));
+    *n_ids = (long long)out.size();
+    while (out.size() % 4) out.push_back(out.back());
+    return full;
+}
+
 void roi_down_segs(const RoiPlan &p, RoiDownForm form, int l, int k, RoiSegs &out)
 {
     out = RoiSegs{};
@@ -1152,6 +1188,28 @@ extern "C" int tmat_roi_sep_tiles_share(int hh, int ww, int patch, int n_up, con
                                         unsigned fused_mask, int layer, int k, int cap, int *n_tiles, int *n_full, int *tiles)
 {
     return sep_tiles_export(ROI_DOWN_SHARE, hh, ww, patch, n_up, up_channels, n_down, down_channels, fused_mask, layer, k, cap, n_tiles, n_full, tiles);
+}
+
+// The quadrant table of plain fused layer 6 b + 1 of the same plan for a pass of k images under `form` (roi_sep_quad_table; refused below
+// ROI_DOWN_SHARE and for every other layer).  counts[4]: the table's length (a multiple of 4: the packed tiles x 4), the ids of the
+// pass's own patches, all ids before the padding, the full-frame tile count of the pass's own patches.  ids (nullable: counts only)
+// takes the table, cap its room.
+extern "C" int tmat_roi_sep_quads(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                  unsigned fused_mask, int form, int layer, int k, int cap, int *counts, int *ids)
+{
+    RoiPlan p;
+    if (int rc = down_plan_for("tmat_roi_sep_quads", counts && k >= 1 && form >= ROI_DOWN_FULL && form <= ROI_DOWN_SHARE_FUSED_RECT, hh, ww, patch, n_up,
+                               up_channels, n_down, down_channels, fused_mask, ROI_MAX_CLASSES, p)) return rc;
+    std::vector<int> tab;
+    long long n_own = 0, n_ids = 0;
+    const long long full = roi_sep_quad_table(p, (RoiDownForm)form, layer, k, tab, &n_own, &n_ids);
+    if (full <= 0) { set_error("tmat_roi_sep_quads: not a plain fused layer of the plan under a sharing form"); return TMAT_E_ARG; }
+    counts[0] = (int)tab.size(); counts[1] = (int)n_own; counts[2] = (int)n_ids; counts[3] = (int)full;
+    if (ids) {
+        if ((int)tab.size() > cap) { set_error("tmat_roi_sep_quads: cap too small"); return TMAT_E_ARG; }
+        std::copy(tab.begin(), tab.end(), ids);
+    }
+    return TMAT_OK;
 }
 
 // The constant-ring tables of the same plan (RoiDownPlan::nonconst ...): nonconst, live and rect_live [6 n_down + 4][max_classes][4] as

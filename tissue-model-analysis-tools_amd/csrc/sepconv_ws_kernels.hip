@@ -110,10 +110,19 @@ __device__ __forceinline__ int ws_tab_read(int mt, const int *tab)
     return *((const __attribute__((address_space(4))) int *)(unsigned long long)tab + mt);
 }
 
-template <bool RELU_IN, bool POOL, int PREC = 0, bool STEM = false, bool ROI = false>
+//
+// QUAD (plain ROI forms only; roi_plan.h:roi_sep_quad_table): the kernel is organised in 8 x 8 quadrants already -- producer p owns one with a
+// private halo, base pointer, border masks and (STEM) window; the consumers multiply 256 A rows without knowing which pixels they are; each
+// 16-byte store of the plain epilogue covers 8 pixels of one tile row inside one quadrant.  So a "tile" can be ANY four quadrants: nMt
+// is then the number of PACKED tiles and tab[4 mt + slot] the full-frame quadrant n QPP + qy QW + qx of slot (qy, qx) of packed tile mt.
+// Producer p takes the entry of its slot where the tile form derives its quadrant's position from the tile; consumer wave w, which holds
+// rows 2 (w & 3), 2 (w & 3) + 1 of slots 2 (w >> 2) and 2 (w >> 2) + 1, stores through one descriptor per slot.  Per-pixel arithmetic,
+// LDS map, phases and MFMA order are untouched, so a visited quadrant gets the bits of the tile form.
+template <bool RELU_IN, bool POOL, int PREC = 0, bool STEM = false, bool ROI = false, bool QUAD = false>
 __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, int nNt, int G, std::conditional_t<ROI, const int *, RoiNone> tab)
 {
     static_assert(!ROI || PREC == 0, "ROI: f32 path only");
+    static_assert(!QUAD || (ROI && !POOL && PREC == 0), "QUAD: plain region form of the f32 path only");
     __shared__ __attribute__((aligned(16))) float smem[STEM ? WS_TOTAL_STEM : WS_TOTAL];
 
     // persistent ranges: blocks b and b + 8 share an XCD; every XCD gets a contiguous super-range of the (pixel tile, channel tile) pairs and
@@ -127,7 +136,7 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
 
     const int t = threadIdx.x;
     const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int TW = a.W >> 4, TPP = (a.H >> 4) * TW;          // tiles per row / per patch
+    const int TW = QUAD ? a.W >> 3 : a.W >> 4, TPP = QUAD ? (a.H >> 3) * TW : (a.H >> 4) * TW;          // tiles (QUAD: quadrants) per row / per patch
     const int Cin = a.Cin;
     const int nchunks = Cin >> 5;
     const int total = (j1 - j0) * nchunks;                   // steps of this workgroup
@@ -204,12 +213,13 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
         // ROI: the table entry of the tile the next tile_setup starts, requested one tile ahead -- tile_setup runs in the vector phase, and
         // a scalar load's latency in front of its address arithmetic would lengthen that phase; requested here, it returns under the
         // producers' own wait for their LDS-DMA in the next MFMA phase
-        int tnext = ws_tab_read(j0 / nNt, tab);
+        int tnext = ws_tab_read(QUAD ? 4 * (j0 / nNt) + p : j0 / nNt, tab);
         auto tile_setup = [&](int jj) {
             const int mt = ROI ? tnext : jj / nNt;
-            if (ROI) tnext = ws_tab_read((jj + 1 < j1 ? jj + 1 : jj) / nNt, tab);
+            if (ROI) { const int mn = (jj + 1 < j1 ? jj + 1 : jj) / nNt; tnext = ws_tab_read(QUAD ? 4 * mn + p : mn, tab); }
             const int n = mt / TPP, tr = mt - n * TPP;
-            const int Y0 = (tr / TW) * 16 + oy - 1, X0 = (tr % TW) * 16 + ox - 1;      // image position of the halo's first pixel
+            // image position of the halo's first pixel (QUAD: mt is this producer's own quadrant)
+            const int Y0 = QUAD ? (tr / TW) * 8 - 1 : (tr / TW) * 16 + oy - 1, X0 = QUAD ? (tr % TW) * 8 - 1 : (tr % TW) * 16 + ox - 1;
             const unsigned bad = m_inv | (Y0 < 0 ? m_top : 0u) | (Y0 + 9 >= a.H ? m_bot : 0u) | (X0 < 0 ? m_left : 0u) | (X0 + 9 >= a.W ? m_right : 0u);
             if (STEM) {
                 hA = a.in + ((long)n * a.H * a.W * 4 + (long)(2 * Y0) * (2 * a.W) + 2 * X0);       // may lie before the tensor for border tiles: those lanes are masked
@@ -499,7 +509,10 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
     float rv[4][4];
     // ROI: the full-frame tile of the pair cj the consumers work on, re-read behind every epilogue (nothing of a tile uses it before the
     // next step: the load returns while the wave waits at the step's closing barrier)
-    int ctile = ws_tab_read(j0 / nNt, tab);
+    // QUAD: the quadrants of this wave's two slots, 2 (wave >> 2) and the one behind it
+    const int cslot = 2 * (wave >> 2);
+    int ctile = ws_tab_read(QUAD ? 4 * (j0 / nNt) + cslot : j0 / nNt, tab);
+    int ctile1 = QUAD ? ws_tab_read(4 * (j0 / nNt) + cslot + 1, tab) : 0;
     auto load_resid = [&](int jj) {
         const int mc = jj / nNt, nt = jj - mc * nNt;
         const int mt = ROI ? ctile : mc;
@@ -523,19 +536,24 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
     // A stage the tile's last step has just consumed instead -- [32 tile pixels][32 channels], one 32-channel slab (jn) at a time --
     // and leave as 16-byte stores: 16 store instructions per wave and tile, each 8 pixels x one full 128-byte line.  No barrier:
     // LDS operations of one wave execute in order.
+    // (QUAD: relative to the quadrant of the store's slot -- stores 0, 2 go to the left slot's rows 0, 1, stores 1, 3 to the right slot's)
     unsigned vo_t[4];            // tile pixel 8 i + (lane >> 3) of this wave's two rows, channel quad lane & 7
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int pix = 8 * i + (lane >> 3);
-        vo_t[i] = (unsigned)(((pix >> 4) * a.W + (pix & 15)) * a.Cout + (lane & 7) * 4) * 4u;
+        vo_t[i] = (unsigned)(((pix >> 4) * a.W + (QUAD ? pix & 7 : pix & 15)) * a.Cout + (lane & 7) * 4) * 4u;
     }
     auto store_tile = [&](int jj, float *xw) {
         const int mc = jj / nNt, nt = jj - mc * nNt;
         const int mt = ROI ? ctile : mc;
         const int n = mt / TPP, tr = mt - n * TPP;
-        const int ty0 = (tr / TW) * 16, tx0 = (tr % TW) * 16;
+        const int ty0 = QUAD ? (tr / TW) * 8 : (tr / TW) * 16, tx0 = QUAD ? (tr % TW) * 8 : (tr % TW) * 16;
+        const int trow = QUAD ? 2 * (wave & 3) : 2 * wave;       // this wave's first row inside the tile (QUAD: inside the slot's quadrant)
         const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(a.out + ((size_t)n * a.H * a.W + (size_t)(ty0 + 2 * wave) * a.W + tx0) * a.Cout + nt * 128), 0, 0x7fffffff, 0x00020000);
+            (void *)(a.out + ((size_t)n * a.H * a.W + (size_t)(ty0 + trow) * a.W + tx0) * a.Cout + nt * 128), 0, 0x7fffffff, 0x00020000);
+        const int n1 = ctile1 / TPP, tr1 = ctile1 - n1 * TPP;
+        const __amdgpu_buffer_rsrc_t rsO1 = !QUAD ? rsO : __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(a.out + ((size_t)n1 * a.H * a.W + (size_t)((tr1 / TW) * 8 + trow) * a.W + (tr1 % TW) * 8) * a.Cout + nt * 128), 0, 0x7fffffff, 0x00020000);
         float *xl = xw + r;
         const float *xr = xw + lane * 4;
 #pragma unroll
@@ -552,7 +570,7 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
             for (int i = 0; i < 4; i++) o[i] = *reinterpret_cast<const float4 *>(xr + i * 256);
 #pragma unroll
             for (int i = 0; i < 4; i++)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, o[i]), rsO, vo_t[i], jn * 128, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, o[i]), (i & 1) ? rsO1 : rsO, vo_t[i], jn * 128, 0);
         }
     };
 
@@ -786,7 +804,10 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
             if (POOL) store_tile_pool(cj, smem + (stage ? WS_A : 0));
             else store_tile(cj, smem + (stage ? WS_A1 : WS_A0) + wave * 1024);
             cj++;
-            if (ROI && s + 1 < total) ctile = ws_tab_read(cj / nNt, tab);
+            if (ROI && s + 1 < total) {
+                ctile = ws_tab_read(QUAD ? 4 * (cj / nNt) + cslot : cj / nNt, tab);
+                if (QUAD) ctile1 = ws_tab_read(4 * (cj / nNt) + cslot + 1, tab);
+            }
         }
         WS_PIN()
         if (s + 1 < total) {
@@ -828,9 +849,13 @@ bool sepconv_ws_supported(int H, int W, int Cin, int Cout)
 }
 
 // region form: a table of 1 .. N TPP tile ids (the caller built it for this N and geometry), f32 path only
-static bool ws_tiles_ok(const int *tiles, int n_tiles, int N, int H, int W, int prec)
+// quadrant form: n_tiles packed tiles of four quadrant ids each (a planner's table lists a quadrant once, so it has no more packed tiles
+// than the patches have tiles; a test's list may repeat quadrants: bounded by the walk's 32-bit pair index instead)
+static bool ws_tiles_ok(const int *tiles, int n_tiles, int N, int H, int W, int prec, bool quad = false)
 {
-    return !tiles || (prec == 0 && n_tiles > 0 && (long long)n_tiles <= (long long)N * (H / 16) * (W / 16));
+    if (!tiles) return !quad;
+    if (quad) return prec == 0 && n_tiles > 0 && n_tiles <= 0x0fffffff;
+    return prec == 0 && n_tiles > 0 && (long long)n_tiles <= (long long)N * (H / 16) * (W / 16);
 }
 
 static int ws_cus()
@@ -846,11 +871,19 @@ static int ws_cus()
 }
 
 // tiles (nullable, prec 0 only): region form -- the n_tiles full-frame tile ids the launch visits (device, roi_sep_tile_table)
+// quad (plain form only, with tiles): the table holds n_tiles packed tiles of four quadrant ids each (roi_sep_quad_table)
 template <bool POOL>
-static void launch_ws_any(const WsArgs &a, int relu_in, int prec, hipStream_t s, const int *tiles = nullptr, int n_tiles = 0)
+static void launch_ws_any(const WsArgs &a, int relu_in, int prec, hipStream_t s, const int *tiles = nullptr, int n_tiles = 0, bool quad = false)
 {
     const int nMt = tiles ? n_tiles : a.N * (a.H / 16) * (a.W / 16), nNt = a.Cout / 128;
     const int G = (ws_cus() / 8) * 8;                       // one persistent 12-wave workgroup per CU (152 KiB of LDS)
+    if constexpr (!POOL) {
+        if (quad && tiles && prec == 0) {
+            if (relu_in) hipLaunchKernelGGL((sepconv_ws_kernel<true, false, 0, false, true, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, tiles);
+            else hipLaunchKernelGGL((sepconv_ws_kernel<false, false, 0, false, true, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, tiles);
+            return;
+        }
+    }
     if (prec == 1) {
         if (relu_in) hipLaunchKernelGGL((sepconv_ws_kernel<true, POOL, 1>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, RoiNone{});
         else hipLaunchKernelGGL((sepconv_ws_kernel<false, POOL, 1>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, RoiNone{});
@@ -889,33 +922,34 @@ static void launch_ws_any(const WsArgs &a, int relu_in, int prec, hipStream_t s,
 }
 
 bool launch_sepconv_ws(const float *in, int N, int H, int W, int Cin, int relu_in, const float *dw9, const float *pwk, int Cout,
-                       const float *scale, const float *shift, int relu_out, float *out, hipStream_t s, int prec, const int *tiles, int n_tiles)
+                       const float *scale, const float *shift, int relu_out, float *out, hipStream_t s, int prec, const int *tiles, int n_tiles, bool quad)
 {
     if (!sepconv_ws_supported(H, W, Cin, Cout) || N <= 0 || (long long)N * (H / 16) * (W / 16) * (Cout / 128) > 0x3fffffffLL ||
-        !ws_tiles_ok(tiles, n_tiles, N, H, W, prec)) {
+        !ws_tiles_ok(tiles, n_tiles, N, H, W, prec, quad) || (quad && (long long)n_tiles * (Cout / 128) > 0x3fffffffLL)) {
         set_error("launch_sepconv_ws: unsupported shape");
         return false;
     }
     WsArgs a{in, N, H, W, Cin, Cout, dw9, pwk, scale, shift, relu_out, out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    launch_ws_any<false>(a, relu_in, prec, s, tiles, n_tiles);
+    launch_ws_any<false>(a, relu_in, prec, s, tiles, n_tiles, quad);
     return true;
 }
 
 bool launch_sepconv_ws_stem(const float *x, int N, int H, int W, int Cin, const float *stem_w, const float *stem_scale, const float *stem_shift,
                             const float *dw9, const float *pwk, int Cout, const float *scale, const float *shift, int relu_out, float *out,
-                            hipStream_t s, const int *tiles, int n_tiles)
+                            hipStream_t s, const int *tiles, int n_tiles, bool quad)
 {
     // the patch window offsets are 32-bit byte offsets from the tile's first window pixel: (21 rows of 2 W floats) always fits; the patch
     // itself is addressed through a 64-bit base
     if (!sepconv_ws_supported(H, W, Cin, Cout) || N <= 0 || (long long)N * (H / 16) * (W / 16) * (Cout / 128) > 0x3fffffffLL || 9 * Cin > WS_X ||
-        !ws_tiles_ok(tiles, n_tiles, N, H, W, 0)) {
+        !ws_tiles_ok(tiles, n_tiles, N, H, W, 0, quad) || (quad && (long long)n_tiles * (Cout / 128) > 0x3fffffffLL)) {
         set_error("launch_sepconv_ws_stem: unsupported shape");
         return false;
     }
     WsArgs a{x, N, H, W, Cin, Cout, dw9, pwk, scale, shift, relu_out, out, nullptr, nullptr, nullptr, nullptr, stem_w, stem_scale, stem_shift};
     const int nMt = tiles ? n_tiles : N * (H / 16) * (W / 16), nNt = Cout / 128;
     const int G = (ws_cus() / 8) * 8;
-    if (tiles) hipLaunchKernelGGL((sepconv_ws_kernel<false, false, 0, true, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, tiles);
+    if (tiles && quad) hipLaunchKernelGGL((sepconv_ws_kernel<false, false, 0, true, true, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, tiles);
+    else if (tiles) hipLaunchKernelGGL((sepconv_ws_kernel<false, false, 0, true, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, tiles);
     else hipLaunchKernelGGL((sepconv_ws_kernel<false, false, 0, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, RoiNone{});
     return true;
 }

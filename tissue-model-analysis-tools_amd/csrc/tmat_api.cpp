@@ -307,13 +307,29 @@ static bool conv(Ctx *c, ConvArgs a, hipStream_t st, const RoiSegs *roi = nullpt
 // computed whole.  Null + error set: the allocation or the copy failed.
 // From ROI_DOWN_CONST upwards every tile of the k all-constant patches behind the pass's patches follows; the forms above
 // ROI_DOWN_SHARE keep its table.
-static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, RoiDownForm form)
+// quad: the quadrant table of a plain fused layer (roi_plan.h:roi_sep_quad_table) where the plan has one for the form -- n packed tiles
+// of four ids, the constant patches' quadrants and the padding included, always on the device; the tile table otherwise
+static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, RoiDownForm form, bool quad = false)
 {
     form = roi_down_form(e->plan, std::min(form, ROI_DOWN_SHARE));
-    for (const RoiTileTab &t : e->tabs) if (t.layer == layer && t.k == k && t.form == form) return &t;
+    for (const RoiTileTab &t : e->tabs) if (t.layer == layer && t.k == k && t.form == form && t.quad == quad) return &t;
     std::vector<int> ids;
     RoiTileTab t;
     t.layer = layer; t.k = k; t.form = form;
+    if (quad) {
+        long long n_own = 0, n_ids = 0;
+        t.full_rep = t.full = roi_sep_quad_table(e->plan, form, layer, k, ids, &n_own, &n_ids);
+        if (t.full > 0) {
+            t.quad = true;
+            t.n = (int)(ids.size() / 4);
+            t.n_rep = (n_own + 3) / 4;              // packed tiles of the pass's own patches
+            if (!hip_ok(hipMalloc((void **)&t.dev, ids.size() * sizeof(int)), "hipMalloc(quadrant table)")) return nullptr;
+            if (!hip_ok(hipMemcpy(t.dev, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy(quadrant table)")) { hipFree(t.dev); return nullptr; }
+            e->tabs.push_back(t);
+            return &e->tabs.back();
+        }
+        return roi_tile_tab(e, layer, k, form);     // no quadrant table for this layer and form: the tile table
+    }
     t.full = roi_sep_tile_table(e->plan, form, layer, k, ids);
     t.n_rep = (long long)ids.size(); t.full_rep = t.full;
     if (t.full <= 0 || ids.empty()) { set_error("roi_tile_tab: no tile table for this layer"); return nullptr; }
@@ -418,7 +434,7 @@ RoiDownForm roi_down_resolve(const Ctx *c, const RoiPlan *plan, int kimg, bool h
 // rectangle launches, bit 1 the tile tables of the fused separable layers.
 // padval: from ROI_DOWN_CONST upwards the k all-constant patches of the pass are written behind X's n patches and run through the same
 // launches as one more segment of whole patches
-int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval, RoiDownForm form)
+int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval, RoiDownForm form, bool quad)
 {
     if (n <= 0) return TMAT_OK;
     if (n > c->max_patches) { set_error("unet_down_dev: n > max_patches"); return TMAT_E_ARG; }
@@ -469,10 +485,13 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
         t.full = t.n = n * (H / 16) * (H / 16);
         t.full_rep = t.n_rep = (long long)n_own * (H / 16) * (H / 16);
         if (ent && f32) {
-            if (const RoiTileTab *made = roi_tile_tab(ent, 6 * (int)bi + k, kimg, form)) t = *made;
+            // the plain layer of a level in ROI_QUAD_LEVELS: its quadrant table where the pass runs the quadrant form
+            const bool q = quad && k == 1 && form >= ROI_DOWN_SHARE && ((ROI_QUAD_LEVELS >> bi) & 1u);
+            if (const RoiTileTab *made = roi_tile_tab(ent, 6 * (int)bi + k, kimg, form, q)) t = *made;
             else tab_ok = false;
         }
-        c->sep_tiles.push_back({t.dev ? t.n_rep : t.full_rep, t.full_rep});       // (the constant patches' whole tiles are not counted)
+        // (the constant patches' whole tiles are not counted; a quadrant table reports its packed tiles)
+        c->sep_tiles.push_back({t.dev ? t.n_rep : t.full_rep, t.full_rep});
         return t;
     };
     const int P = c->patch;
@@ -507,8 +526,8 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
             if (!tab_ok) return TMAT_E_HIP;
             if (stem_here) {
                 if (!launch_sepconv_ws_stem(X, n, H, H, d.cin, c->stem_w, c->stem_scale, c->stem_shift, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s,
-                                            t0.dev, t0.n)) return TMAT_E_ARG;
-            } else if (!launch_sepconv_ws(b0, n, H, H, d.cin, bi > 0, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s, sprec, t0.dev, t0.n)) return TMAT_E_ARG;
+                                            t0.dev, t0.n, t0.quad)) return TMAT_E_ARG;
+            } else if (!launch_sepconv_ws(b0, n, H, H, d.cin, bi > 0, d.dw[0], pw0, d.cout, d.scale[0], d.shift[0], 1, b2, s, sprec, t0.dev, t0.n, t0.quad)) return TMAT_E_ARG;
             if (!copies(b2, 6 * (int)bi + 1, d.cout)) return TMAT_E_ARG;
             ConvArgs r{};
             r.in = b0; r.N = n; r.h = H; r.w = H; r.Cin = d.cin; r.ksize = 1; r.stride = 2; r.W = d.res_w; r.Cout = d.cout;
@@ -703,7 +722,7 @@ int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred
         launch_minmax_f32(xi, k, (size_t)hh * ww, mn, mx, c->stream);
         launch_extract_tiles(xi, mn, k, g, c->patch_in, c->stream);
         // (the constant-ring form only on request: the default launches of this entry point are pinned to the dependency plan's tiles)
-        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan, mn, roi_down_resolve(c, plan, k, true, false))
+        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan, mn, roi_down_resolve(c, plan, k, true, false), roi_quad_on(c, false))
                       : unet_forward_dev(c, c->patch_in, k * g.tiles_per_img, c->patch_out, c->stream);
         if (!rc && plan) rc = unet_up_dev(c, c->dout[0], k * g.tiles_per_img, c->patch_out, c->stream, plan);
         if (rc) return rc;
@@ -792,6 +811,10 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     if (const char *e = getenv("TMAT_ROI_SHARE_FUSED_RECT")) {
         if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_SHARE_FUSED_RECT must be 0 or 1"); delete c; return TMAT_E_ARG; }
         c->roi_share_fused_rect = atoi(e);
+    }
+    if (const char *e = getenv("TMAT_ROI_QUAD")) {
+        if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_QUAD must be 0 or 1"); delete c; return TMAT_E_ARG; }
+        c->roi_quad = atoi(e);
     }
     // room for the all-constant patches of a pass behind its patches (tmat_ctx.h): the down-path workspaces and the input buffers only
     c->const_cap = c->roi_const == 0 ? 0 : std::max(4, c->max_patches / 64);
@@ -1087,13 +1110,58 @@ int tmat_debug_held_bytes(tmat_handle h, size_t *device_bytes, size_t *pinned_by
     return TMAT_OK;
 }
 
-// Test-only (tests/test_gpu_roi_sep.py): planned and full tile counts of the fused separable launches of the last down pass
+// Test-only (tests/test_gpu_roi_sep.py): planned and full tile counts of the fused separable launches of the last down pass; a launch
+// in quadrant form reports its packed tiles as planned
 int tmat_debug_sep_tiles(tmat_handle h, int cap, int *n, long long *planned, long long *full)
 {
     Ctx *c = (Ctx *)h;
     if (!c || !n || cap < 0 || (cap > 0 && (!planned || !full))) { set_error("tmat_debug_sep_tiles: bad argument"); return TMAT_E_ARG; }
     *n = (int)c->sep_tiles.size();
     for (int i = 0; i < *n && i < cap; i++) { planned[i] = c->sep_tiles[i].first; full[i] = c->sep_tiles[i].second; }
+    return TMAT_OK;
+}
+
+// Test-only (tests/test_gpu_sep_quads.py): ONE plain fused separable launch in quadrant form on host buffers with the caller's quadrant
+// list (full-frame ids n QPP + qy QW + qx, any order, any patches; padded here to a multiple of 4 by repeating the last id).  x: (n, hh, ww,
+// cin), or with the stem's weights (all three or none; relu_in 0) the single-channel patches (n, 2 hh, 2 ww).  dw9 [9][cin], pw in the Keras
+// layout (cin, cout).  The caller fills out (n, hh, ww, cout): words of quadrants not listed come back as they went in.
+int tmat_debug_sepconv_quads(tmat_handle hd, const float *x, int n, int hh, int ww, int cin, int relu_in, const float *dw9, const float *pw, int cout,
+                             const float *scale, const float *shift, int relu_out, const float *stem_w, const float *stem_scale,
+                             const float *stem_shift, const int *quads, int n_quads, float *out)
+{
+    Ctx *c = (Ctx *)hd;
+    const bool stem = stem_w != nullptr;
+    if (!c || !x || !dw9 || !pw || !scale || !shift || !quads || !out || n < 1 || n_quads < 1 || n_quads > (1 << 24) || hh < 16 || ww < 16 || cin < 1 ||
+        cout < 1 || stem != (stem_scale != nullptr) || stem != (stem_shift != nullptr) || (stem && relu_in) || !sepconv_ws_supported(hh, ww, cin, cout) ||
+        (long long)n * hh * ww * std::max(cin, cout) > 0x3fffffffLL) {
+        set_error("tmat_debug_sepconv_quads: bad argument");
+        return TMAT_E_ARG;
+    }
+    const long long nq = (long long)n * (hh / 8) * (ww / 8);
+    std::vector<int> ids(quads, quads + n_quads);
+    for (int id : ids) if (id < 0 || id >= nq) { set_error("tmat_debug_sepconv_quads: a quadrant id lies outside the tensor"); return TMAT_E_ARG; }
+    while (ids.size() % 4) ids.push_back(ids.back());
+    TMAT_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DevScope mem(c->ws_pool, s);
+    const size_t nx = stem ? (size_t)n * hh * ww * 4 : (size_t)n * hh * ww * cin, no = (size_t)n * hh * ww * cout;
+    std::vector<float> wk = k_contiguous(pw, 1, cin, cout);
+    const size_t nw = wk.size();
+    const float *hw = mem.keep(std::move(wk));
+    const size_t n_ids = ids.size();
+    const int *hid = mem.keep(std::move(ids));
+    float *dx = mem.alloc_from(x, nx), *dd = mem.alloc_from(dw9, (size_t)9 * cin), *dw = mem.alloc_from(hw, nw);
+    float *dsc = mem.alloc_from(scale, cout), *dsh = mem.alloc_from(shift, cout), *dout = mem.alloc_from((const float *)out, no);
+    float *sw = stem ? mem.alloc_from(stem_w, (size_t)9 * cin) : nullptr, *ssc = stem ? mem.alloc_from(stem_scale, cin) : nullptr;
+    float *ssh = stem ? mem.alloc_from(stem_shift, cin) : nullptr;
+    int *dq = mem.alloc_from(hid, n_ids);
+    if (!mem.ok) return TMAT_E_HIP;
+    const bool ok = stem ? launch_sepconv_ws_stem(dx, n, hh, ww, cin, sw, ssc, ssh, dd, dw, cout, dsc, dsh, relu_out != 0, dout, s, dq, (int)(n_ids / 4), true)
+                         : launch_sepconv_ws(dx, n, hh, ww, cin, relu_in != 0, dd, dw, cout, dsc, dsh, relu_out != 0, dout, s, 0, dq, (int)(n_ids / 4), true);
+    if (!ok) return TMAT_E_ARG;
+    mem.check(hipGetLastError(), "tmat_debug_sepconv_quads launch");
+    mem.d2h(out, dout, no * sizeof(float));
+    if (mem.finish()) return TMAT_E_HIP;
     return TMAT_OK;
 }
 

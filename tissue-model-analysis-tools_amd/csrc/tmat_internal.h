@@ -152,7 +152,7 @@ size_t sepconv_pool_scratch_floats(int N, int H, int W, int Cout);
 bool sepconv_ws_supported(int H, int W, int Cin, int Cout);
 bool launch_sepconv_ws(const float *in, int N, int H, int W, int Cin, int relu_in, const float *dw9, const float *pwk, int Cout,
                        const float *scale, const float *shift, int relu_out, float *out, hipStream_t s, int prec = 0,
-                       const int *tiles = nullptr, int n_tiles = 0);
+                       const int *tiles = nullptr, int n_tiles = 0, bool quad = false);
 bool launch_sepconv_pool_ws(const float *in, int N, int H, int W, int Cin, int relu_in, const float *dw9, const float *pwk, int Cout,
                             const float *scale, const float *shift, int relu_out, float *scratch, const float *resid, float *out, hipStream_t s, int prec = 0,
                             const RoiSegs *roi_fix = nullptr,       // roi_fix: pooled pixels the fix-up pass finishes
@@ -160,6 +160,8 @@ bool launch_sepconv_pool_ws(const float *in, int N, int H, int W, int Cin, int r
 // tiles (nullable, prec 0 only; here, above and in the stem form): region form of the convolution itself -- a device table of the n_tiles
 // full-frame 16 x 16 tile ids (patch * tiles per patch + ty * tiles per row + tx) the launch visits (roi_plan.h:roi_sep_tile_table);
 // the other tiles' outputs and strips stay unwritten
+// quad (the two plain forms only): the table holds n_tiles PACKED tiles of four full-frame 8 x 8 quadrant ids each (patch * quadrants per
+// patch + qy * quadrants per row + qx; roi_plan.h:roi_sep_quad_table) -- any four quadrants, of any patches; the others stay unwritten
 // roi (nullable, here and below): the region form -- rows of a strip outside the box are neither loaded for nor computed
 void launch_dwconv(const float *in, int N, int H, int W, int C, int relu_in, const float *Wd, float *out, hipStream_t s, const RoiSegs *roi = nullptr);
 void launch_stem(const float *x, int N, int H, int W, const float *Ws, int Cout, const float *scale,
@@ -172,7 +174,7 @@ void launch_stem_even(const float *x, int N, int H, int W, const float *Ws, int 
 // producers recompute stem = relu(bn(conv3x3/s2(x))) (H x W x Cin) for their halo.  Same results as launch_stem + launch_sepconv_ws.
 bool launch_sepconv_ws_stem(const float *x, int N, int H, int W, int Cin, const float *stem_w, const float *stem_scale, const float *stem_shift,
                             const float *dw9, const float *pwk, int Cout, const float *scale, const float *shift, int relu_out, float *out,
-                            hipStream_t s, const int *tiles = nullptr, int n_tiles = 0);
+                            hipStream_t s, const int *tiles = nullptr, int n_tiles = 0, bool quad = false);
 void launch_maxpool_add(const float *p2, int N, int H, int W, int C, const float *r, float *out, hipStream_t s, float *out_relu = nullptr,
                         const RoiSegs *roi = nullptr);
 // roi (nullable): workgroups whose 8 x 16 stored pixels lie outside their patch's rectangle return at once

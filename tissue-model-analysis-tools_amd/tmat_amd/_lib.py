@@ -204,6 +204,7 @@ EXPORTS = [
     "tmat_analyze_batch_grid", "tmat_analyze_batch_grid_dev", "tmat_render_barcode", "tmat_render_barcode_png", "tmat_host_barcode_rects",
     "tmat_analyze_stack_batch_dev", "tmat_canny_mask_batch", "tmat_well_small_shape", "tmat_stack_well_front_dev",
     "tmat_cell_small_dev", "tmat_cell_well_front_dev", "tmat_cell_area_fit_dev",
+    "tmat_roi_sep_quads", "tmat_debug_sepconv_quads",
 ]
 
 
@@ -511,6 +512,27 @@ class Handle:
         planned, full = np.zeros(16, np.int64), np.zeros(16, np.int64)
         check(L.tmat_debug_sep_tiles(self._h, 16, ptr(n), ptr(planned), ptr(full)), "tmat_debug_sep_tiles")
         return [(int(planned[i]), int(full[i])) for i in range(min(int(n[0]), 16))]
+
+    def debug_sepconv_quads(self, x, dw9, pw, scale, shift, quads, out, relu_in=False, relu_out=True, stem=None):
+        """test-only (include/tmat.h:tmat_debug_sepconv_quads): one plain fused separable launch in quadrant form.  x (n, h, w, cin), or
+        with stem = (taps [9][cin], scale, shift) the single-channel patches (n, 2 h, 2 w); dw9 [9][cin]; pw (cin, cout) in the Keras layout;
+        quads: full-frame quadrant ids; out (n, h, w, cout) float32, caller-filled, changed in place and returned."""
+        x, dw9, pw = (np.ascontiguousarray(a, np.float32) for a in (x, dw9, pw))
+        scale, shift = np.ascontiguousarray(scale, np.float32), np.ascontiguousarray(shift, np.float32)
+        q = np.ascontiguousarray(quads, np.int32).ravel()
+        cin, cout = pw.shape
+        n, hh, ww = out.shape[:3]
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (n, hh, ww, cout) and dw9.shape == (9, cin)
+        assert x.shape == ((n, 2 * hh, 2 * ww) if stem is not None else (n, hh, ww, cin)), x.shape
+        st = [None] * 3 if stem is None else [np.ascontiguousarray(a, np.float32) for a in stem]
+        assert stem is None or (st[0].shape == (9, cin) and st[1].shape == (cin,) and st[2].shape == (cin,))
+        L = lib()
+        vp, i = C.c_void_p, C.c_int
+        L.tmat_debug_sepconv_quads.argtypes = [vp, vp, i, i, i, i, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp, i, vp]
+        check(L.tmat_debug_sepconv_quads(self._h, ptr(x), n, hh, ww, cin, int(bool(relu_in)), ptr(dw9), ptr(pw), cout, ptr(scale), ptr(shift),
+                                         int(bool(relu_out)), *(None if a is None else ptr(a) for a in st), ptr(q), len(q), ptr(out)),
+              "tmat_debug_sepconv_quads")
+        return out
 
     def debug_down_segs(self):
         """test-only: the longest segment table among the rectangle launches of the last down pass (include/tmat.h:tmat_debug_down_segs)"""
@@ -917,6 +939,24 @@ def roi_down_schedule(hh, ww, form, k, patch=320, channels=(512, 512, 256, 128, 
 def roi_sep_tiles_share(hh, ww, layer, k, patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
     """tmat_roi_sep_tiles_share (include/tmat.h): roi_sep_tiles for the shared-interior form (the tiles that hold a comp pixel)."""
     return roi_sep_tiles(hh, ww, layer, k, patch, channels, down_channels, fused_mask, _export="tmat_roi_sep_tiles_share")
+
+
+def roi_sep_quads(hh, ww, layer, k, form="share", patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
+    """tmat_roi_sep_quads (include/tmat.h): the quadrant table of plain fused layer `layer` (6 b + 1) for a pass of k images under `form`
+    (a name of ROI_DOWN_FORMS or its value; "share" upwards); host arithmetic, no GPU.  Returns (ids int32 [4 x packed tiles]: the own
+    patches' quadrants, the constant patches', the padding; own: the ids of the pass's own patches; n_ids: all ids before the padding;
+    full: the full-frame tile count of the pass's own patches)."""
+    L = lib()
+    L.tmat_roi_sep_quads.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint] + [C.c_int] * 4 + [C.c_void_p] * 2
+    n_up, n_down = len(channels) - 1, len(down_channels) - 1
+    ch, dch = np.asarray(channels, np.int32), np.asarray(down_channels, np.int32)
+    f = ROI_DOWN_FORMS.index(form) if isinstance(form, str) else int(form)
+    counts = np.zeros(4, np.int32)
+    args = (hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), f, int(layer), int(k))
+    check(L.tmat_roi_sep_quads(*args, 0, ptr(counts), None), "roi_sep_quads")
+    ids = np.zeros(max(int(counts[0]), 1), np.int32)
+    check(L.tmat_roi_sep_quads(*args, len(ids), ptr(counts), ptr(ids)), "roi_sep_quads")
+    return ids[:int(counts[0])], int(counts[1]), int(counts[2]), int(counts[3])
 
 
 def debug_share_fill_check(n_patches, side, channels, neighbours, items):
