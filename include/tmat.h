@@ -812,6 +812,35 @@ int tmat_conv2d_roi(tmat_handle h, const float *x, int n, int hh, int ww, int ci
  * residual, out (and out_relu) (n, hh / 2, ww / 2, cout), the segments' rectangles in output pixels. */
 int tmat_conv2d_roi_s2(tmat_handle h, const float *x, int n, int hh, int ww, int cin, const float *w, int cout, const float *scale,
                        const float *shift, int relu_in, int relu_out, const int *segs, int nseg, float *out, float *out_relu);
+/*
+ * Stage-wise test entry point of the NARROW layers' kernel (csrc/conv_narrow_kernels.hip: what the UNet driver launches for the
+ * convolutions conv_mfma_kernel refuses -- the 16- and 32-channel layers of models with filter_counts (32, 64, 128, 256) or
+ * (16, 32, 64, 128)): tmat_conv2d_roi's contract on host buffers, with the stride as an argument.  w in the Keras layout; out and
+ * out_relu caller-filled; nseg == 0: the full-frame launch; segments as above (stride 2: output pixels, sub-pixel: stored pixels), any
+ * first column, any width >= 2.  f32 contract only: bit for bit oracle/unet.py:_conv / _conv_subpixel, and bit for bit conv_mfma_kernel
+ * on the shapes both take.
+ * Accepted shapes (anything else returns TMAT_E_ARG with "launch_conv_narrow: unsupported shape" or this entry point's own message,
+ * launches nothing and leaves out as it was):
+ *   cin % 16 == 0 and cout % 16 == 0, both >= 16 (48 and 80 included: a last K block of 16 channels is short, a last column tile half empty);
+ *   ksize 3 at stride 1; ksize 1 at stride 1 or 2 (hh and ww even, no resid); subpixel != 0 (ksize 3, stride 1, no resid, no out_relu);
+ *   rs 0 or 1 (hh, ww even for rs 1); ww / stride >= 2 (one row is fine); n (hh / stride) (ww / stride) < 2^30.
+ * A handle from tmat_create_plain is enough.
+ */
+int tmat_conv2d_narrow(tmat_handle h, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int stride, int subpixel,
+                       int cout, const float *scale, const float *shift, const float *resid, int rs, int relu_in, int relu_out,
+                       const int *segs, int nseg, float *out, float *out_relu);
+/*
+ * Which kernel every convolution of a weight blob runs on.  Host arithmetic: no GPU, no handle.  layers (cap, 6) i32 receives, in the
+ * launch order of one forward (down path, then up path), [ksize, stride, cin, cout, output side, launcher] per convolution launch:
+ * ksize 2 is the sub-pixel form; a 1x1 over the stem at its even pixels counts as 1x1 stride 1; a fused separable layer is ksize 1.
+ * launcher: 0 conv_mfma_kernel, 1 the narrow kernel, 2 the fused separable kernel.  *n_layers: the number of launches (TMAT_E_CAP, with
+ * *n_layers set, when it exceeds cap).  The environment switches that choose between kernels (TMAT_FUSED_SEP, TMAT_STEM_FUSED,
+ * TMAT_FUSED_POOL) are read as tmat_create reads them.
+ * TMAT_E_WEIGHTS, with the rule in tmat_last_error, for a blob tmat_create refuses for its shapes: every filter count has to be a
+ * multiple of 16 (at least 16) and, on the down path, 4 times a power of two -- filter_counts (64, 128, 256, 512), (32, 64, 128, 256) and
+ * (16, 32, 64, 128) run; (8, 16, 32, 64) or a count of 24 do not.  tmat_create runs the same check before it allocates anything.
+ */
+int tmat_model_layers(const void *blob, size_t n_bytes, int cap, int *layers, int *n_layers);
 
 /* device memory helpers so a ctypes host can stage inputs in HBM without torch; upload and download are ordered on the handle's
  * stream (a download sees the work queued before it, e.g. tmat_zproj_dev) and return when the copy is done */
@@ -883,6 +912,8 @@ int tmat_zproj_dev(tmat_handle h, const uint16_t *stacks_dev, int n, int Z, int 
  *   separable layers stay f32 (three planes do not fit the kernel's LDS budget); depthwise taps, stem and final layer are always f32.
  * Takes effect for the calls that follow (all three streams of the handle are drained first).  The environment variable
  * TMAT_PRECISION=f32|bf16x3|bf16x6 selects the mode at tmat_create.
+ * A model with narrow layers (tmat_model_layers reports launcher 1 somewhere: filter counts of 16 or 32) is f32 only: an opt-in mode
+ * returns TMAT_E_ARG with a message and leaves the handle in f32, through the environment variable it fails tmat_create.
  */
 #define TMAT_PRECISION_F32 0
 #define TMAT_PRECISION_BF16X3 1

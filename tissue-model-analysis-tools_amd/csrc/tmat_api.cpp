@@ -267,6 +267,108 @@ static bool build_model(Ctx *c, const std::map<std::string, Tensor> &m)
 }
 
 // ---------------------------------------------------------------------------------------------
+// What a blob's forward launches (host arithmetic only: tmat_model_layers, and tmat_create before it allocates anything)
+// ---------------------------------------------------------------------------------------------
+struct ModelShape {
+    int patch = 0, f0 = 0;
+    std::vector<std::pair<int, int>> down, up;      // (cin, cout) per block
+};
+struct ModelLayer { int ksize, stride, cin, cout, side, launcher; };
+
+// the channel counts of the blob's blocks, from the tensors build_model reads them from
+static bool model_shape(const std::map<std::string, Tensor> &m, int patch, ModelShape &ms)
+{
+    ms = ModelShape();
+    ms.patch = patch;
+    Tensor w;
+    if (!need(m, "stem.w", w)) return false;
+    if (w.shape.size() != 4 || w.shape[2] != 1) { set_error("weights: only channels=1 supported"); return false; }
+    int cin = ms.f0 = w.shape[3];
+    for (int i = 0;; i++) {
+        const std::string p = "down" + std::to_string(i);
+        if (!m.count(p + ".sep1.dw")) break;
+        if (!need(m, p + ".sep1.pw", w)) return false;
+        if (w.shape.size() != 2 || w.shape[0] != cin) { set_error("weights: separable convolution tensors of " + p + ".sep1 have unexpected shapes"); return false; }
+        ms.down.push_back({cin, w.shape[1]});
+        cin = w.shape[1];
+    }
+    for (int j = 0;; j++) {
+        const std::string p = "up" + std::to_string(j);
+        if (!m.count(p + ".ct1.w")) break;
+        if (!need(m, p + ".ct1.w", w)) return false;
+        if (w.shape.size() != 4 || w.shape[3] != cin) { set_error("weights: transposed convolution tensors of " + p + ".ct1 have unexpected shapes"); return false; }
+        ms.up.push_back({cin, w.shape[2]});
+        cin = w.shape[2];
+    }
+    if (ms.down.empty() || ms.up.size() != ms.down.size() + 1) { set_error("weights: unexpected block structure"); return false; }
+    if (patch <= 0 || patch % (8 << ms.down.size())) { set_error("weights: patch size must be divisible by 2^(blocks+1)"); return false; }
+    return true;
+}
+
+// does a down block at input side H run on the wave-specialised fused separable kernel?
+static bool fused_level(bool fused_sep, int H, int cin, int cout)
+{
+    return fused_sep && sepconv_ws_supported(H, H, cin, cout) && sepconv_ws_supported(H, H, cout, cout) && ((cout / 4) & (cout / 4 - 1)) == 0;
+}
+
+// The switches of tmat_create that decide which kernel a layer runs on
+struct UnetSwitches { bool fused_sep = true, stem_fused = true, fused_pool = true; };
+static UnetSwitches unet_switches_from_env()
+{
+    UnetSwitches s;
+    if (const char *e = getenv("TMAT_FUSED_SEP")) s.fused_sep = atoi(e) != 0;
+    if (const char *e = getenv("TMAT_FUSED_POOL")) s.fused_pool = atoi(e) != 0;
+    if (const char *e = getenv("TMAT_STEM_FUSED")) s.stem_fused = atoi(e) != 0;
+    return s;
+}
+
+// Every convolution launch of one f32 forward (unet_down_dev, then unet_up_dev), in launch order: launcher 0 conv_mfma_kernel, 1 the
+// narrow kernel (conv_narrow_kernels.hip), 2 the fused separable kernel; side: of the launch's output.  False with the rule in the
+// error: a convolution neither launcher takes, or a channel count the down path's other kernels do not take.
+static bool model_layers(const ModelShape &ms, const UnetSwitches &sw, std::vector<ModelLayer> &out)
+{
+    static const float mark = 0.f;          // a residual's presence is all the shape rules look at
+    out.clear();
+    auto pow2x4 = [](int C) { return C >= 4 && C % 4 == 0 && ((C / 4) & (C / 4 - 1)) == 0; };
+    auto conv = [&](int ksize, int stride, int cin, int cout, int side_in, bool resid, int rs) {
+        ConvArgs a{};
+        a.N = 1; a.h = a.w = side_in; a.Cin = cin; a.ksize = ksize; a.stride = stride; a.Cout = cout; a.resid = resid ? &mark : nullptr; a.rs = rs;
+        const int launcher = conv_mfma_takes(a) ? 0 : conv_narrow_takes(a) ? 1 : -1;
+        if (launcher < 0) {
+            set_error("weights: the convolution " + std::to_string(cin) + " -> " + std::to_string(cout) + " (ksize " + std::to_string(ksize) +
+                      ") runs on neither convolution kernel: every filter count must be a multiple of 16, at least 16 (conv_mfma_kernel takes cin % 64 == 0, "
+                      "% 32 in the sub-pixel form, and cout % 64 == 0; the narrow kernel cin % 16 == 0 and cout % 16 == 0)");
+            return false;
+        }
+        out.push_back({ksize, stride, cin, cout, side_in / stride * (ksize == 2 ? 2 : 1), launcher});
+        return true;
+    };
+    if (!pow2x4(ms.f0)) { set_error("weights: the stem's filter count must be 4 times a power of two"); return false; }
+    int H = ms.patch / 2;
+    for (size_t bi = 0; bi < ms.down.size(); bi++) {
+        const int cin = ms.down[bi].first, cout = ms.down[bi].second;
+        if (fused_level(sw.fused_sep, H, cin, cout)) {
+            const bool stem_here = bi == 0 && sw.stem_fused && cin == ms.f0;        // the residual then reads the stem at the even pixels
+            out.push_back({1, 1, cin, cout, H, 2});
+            if (!conv(1, stem_here ? 1 : 2, cin, cout, stem_here ? H / 2 : H, false, 0)) return false;
+            out.push_back({1, 1, cout, cout, sw.fused_pool ? H / 2 : H, 2});
+        } else {
+            // depthwise, pooling and pooling fix-up kernels index channel groups by shifts
+            if (!pow2x4(cin) || !pow2x4(cout)) { set_error("weights: the filter counts of the down path must be 4 times a power of two"); return false; }
+            if (!conv(1, 1, cin, cout, H, false, 0) || !conv(1, 1, cout, cout, H, false, 0) || !conv(1, 2, cin, cout, H, false, 0)) return false;
+        }
+        H /= 2;
+    }
+    int Hs = ms.patch >> (1 + ms.down.size()), up = 0;
+    for (size_t j = 0; j < ms.up.size(); j++) {
+        const int cin = ms.up[j].first, cout = ms.up[j].second;
+        if (!conv(up ? 2 : 3, 1, cin, cout, Hs, false, 0) || !conv(1, 1, cin, cout, Hs, false, 0) || !conv(3, 1, cout, cout, Hs << up, true, up)) return false;
+        Hs <<= up; up = 1;
+    }
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------
 // UNet forward on device patches X (n, P, P) -> Y (n, P, P); n <= max_patches.
 // Buffer plan (4 ping-pong activation buffers) is documented in DESIGN.md.
 // ---------------------------------------------------------------------------------------------
@@ -297,7 +399,9 @@ static bool conv(Ctx *c, ConvArgs a, hipStream_t st, const RoiSegs *roi = nullpt
         auto it = mp.find(a.W);
         if (it != mp.end()) { a.W = it->second; a.prec = c->precision; }
     }
-    bool ok = launch_conv(a, st, roi);
+    // the narrow layers (16 / 32 channels: filter_counts below the shipped model's) run on the kernel of conv_narrow_kernels.hip; a
+    // shape conv_mfma_kernel takes never does
+    bool ok = conv_mfma_takes(a) ? launch_conv(a, st, roi) : launch_conv_narrow(a, st, roi);
     if (dom) prof_end(c, st);
     return ok;
 }
@@ -384,8 +488,7 @@ static bool down_block_ws(const Ctx *c, size_t bi)
 {
     const DownBlock &d = c->down[bi];
     const int H = (c->patch / 2) >> bi;
-    return c->fused_sep && sepconv_ws_supported(H, H, d.cin, d.cout) && sepconv_ws_supported(H, H, d.cout, d.cout) &&
-           ((d.cout / 4) & (d.cout / 4 - 1)) == 0;
+    return fused_level(c->fused_sep, H, d.cin, d.cout);
 }
 
 // the segments of a layer of the up path for a pass of k images: one per class with a non-empty rectangle, in the class-major patch
@@ -782,11 +885,21 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     std::map<std::string, Tensor> m;
     int patch = 0;
     if (!parse_blob(weights_blob, n_bytes, m, patch)) return TMAT_E_WEIGHTS;
+    // a blob whose convolutions no kernel takes is refused here, with the rule, before anything is allocated
+    const UnetSwitches sw = unet_switches_from_env();
+    bool narrow = false;
+    {
+        ModelShape ms;
+        std::vector<ModelLayer> layers;
+        if (!model_shape(m, patch, ms) || !model_layers(ms, sw, layers)) return TMAT_E_WEIGHTS;
+        for (const ModelLayer &l : layers) narrow = narrow || l.launcher == 1;
+    }
     Ctx *c = new Ctx();
     c->device = device_id;
     c->patch = patch;
     c->max_patches = max_patches > 0 ? max_patches : 400;
-    if (const char *e = getenv("TMAT_FUSED_SEP")) c->fused_sep = atoi(e) != 0;
+    c->narrow = narrow;
+    c->fused_sep = sw.fused_sep; c->fused_pool = sw.fused_pool; c->stem_fused = sw.stem_fused;
     if (const char *e = getenv("TMAT_ROI")) c->roi_on = atoi(e) != 0;
     if (const char *e = getenv("TMAT_ROI_TIGHT")) c->roi_tight = atoi(e) != 0;
     if (const char *e = getenv("TMAT_ROI_EXACT")) c->roi_exact = atoi(e) != 0;
@@ -818,8 +931,6 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     }
     // room for the all-constant patches of a pass behind its patches (tmat_ctx.h): the down-path workspaces and the input buffers only
     c->const_cap = c->roi_const == 0 ? 0 : std::max(4, c->max_patches / 64);
-    if (const char *e = getenv("TMAT_FUSED_POOL")) c->fused_pool = atoi(e) != 0;
-    if (const char *e = getenv("TMAT_STEM_FUSED")) c->stem_fused = atoi(e) != 0;
     if (const char *e = getenv("TMAT_SEP_BF16")) c->sep_bf16 = atoi(e) != 0;
     const char *prec_env = getenv("TMAT_PRECISION");
     if (prec_env && strcmp(prec_env, "f32") && strcmp(prec_env, "bf16x3") && strcmp(prec_env, "bf16x6")) {
@@ -1049,6 +1160,10 @@ int tmat_set_precision(tmat_handle h, int mode)
         set_error("tmat_set_precision: needs a model handle and mode TMAT_PRECISION_F32, TMAT_PRECISION_BF16X3 or TMAT_PRECISION_BF16X6");
         return TMAT_E_ARG;
     }
+    if (mode != TMAT_PRECISION_F32 && c->narrow) {
+        set_error("tmat_set_precision: this model has layers of 16 or 32 channels, which run on the narrow convolution kernel in f32 only");
+        return TMAT_E_ARG;
+    }
     TMAT_HIP(hipSetDevice(c->device));
     if (mode != TMAT_PRECISION_F32) {
         auto &mp = c->wsplit[mode];
@@ -1186,13 +1301,14 @@ int tmat_debug_down_seg_total(tmat_handle h, int *total)
 // of the same convolution.
 static int conv2d_roi_impl(tmat_handle hd, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int stride, int subpixel, int cout,
                            const float *scale, const float *shift, const float *resid, int rs, int relu_in, int relu_out, const int *segs, int nseg,
-                           float *out, float *out_relu)
+                           float *out, float *out_relu, bool narrow = false)
 {
     Ctx *c = (Ctx *)hd;
+    const std::string who = narrow ? "tmat_conv2d_narrow" : "tmat_conv2d_roi";
     if (!c || !x || !w || !shift || !out || n < 1 || hh < 1 || ww < 1 || cin < 1 || cout < 1 || (ksize != 1 && ksize != 3) || (subpixel && ksize != 3) ||
         (subpixel && (resid || out_relu)) || (rs != 0 && rs != 1) || (rs && ((hh | ww) & 1)) || nseg < 0 || nseg > ROI_MAX_SEGS || (nseg && !segs) ||
         (stride != 1 && (stride != 2 || ksize != 1 || subpixel || resid || ((hh | ww) & 1)))) {
-        set_error("tmat_conv2d_roi: bad argument (ksize 1 or 3, sub-pixel form of a 3x3 without residual or activated copy, rs 0 or 1, stride 2 with the "
+        set_error(who + ": bad argument (ksize 1 or 3, sub-pixel form of a 3x3 without residual or activated copy, rs 0 or 1, stride 2 with the "
                   "1x1 form without residual on even sides only, at most 64 segments)");
         return TMAT_E_ARG;
     }
@@ -1219,8 +1335,8 @@ static int conv2d_roi_impl(tmat_handle hd, const float *x, int n, int hh, int ww
         RoiSeg &g = sg.s[sg.nseg++];
         g.p0 = segs[6 * i]; g.np = segs[6 * i + 1]; g.y0 = segs[6 * i + 2]; g.x0 = segs[6 * i + 3]; g.rh = segs[6 * i + 4]; g.rw = segs[6 * i + 5];
     }
-    if (!launch_conv(a, s, nseg ? &sg : nullptr)) return TMAT_E_ARG;
-    mem.check(hipGetLastError(), "tmat_conv2d_roi launch");
+    if (!(narrow ? launch_conv_narrow(a, s, nseg ? &sg : nullptr) : launch_conv(a, s, nseg ? &sg : nullptr))) return TMAT_E_ARG;
+    mem.check(hipGetLastError(), narrow ? "tmat_conv2d_narrow launch" : "tmat_conv2d_roi launch");
     mem.d2h(out, dout, no * sizeof(float));
     if (out_relu) mem.d2h(out_relu, dout2, no * sizeof(float));
     if (mem.finish()) return TMAT_E_HIP;
@@ -1239,6 +1355,32 @@ int tmat_conv2d_roi_s2(tmat_handle hd, const float *x, int n, int hh, int ww, in
                        const float *shift, int relu_in, int relu_out, const int *segs, int nseg, float *out, float *out_relu)
 {
     return conv2d_roi_impl(hd, x, n, hh, ww, cin, w, 1, 2, 0, cout, scale, shift, nullptr, 0, relu_in, relu_out, segs, nseg, out, out_relu);
+}
+
+// The same entry point on the narrow layers' kernel (conv_narrow_kernels.hip; tests/test_gpu_conv_narrow.py): ONE launch_conv_narrow
+int tmat_conv2d_narrow(tmat_handle hd, const float *x, int n, int hh, int ww, int cin, const float *w, int ksize, int stride, int subpixel, int cout,
+                       const float *scale, const float *shift, const float *resid, int rs, int relu_in, int relu_out, const int *segs, int nseg,
+                       float *out, float *out_relu)
+{
+    return conv2d_roi_impl(hd, x, n, hh, ww, cin, w, ksize, stride, subpixel, cout, scale, shift, resid, rs, relu_in, relu_out, segs, nseg, out, out_relu, true);
+}
+
+int tmat_model_layers(const void *blob, size_t n_bytes, int cap, int *layers, int *n_layers)
+{
+    if (!blob || !n_layers || cap < 0 || (cap > 0 && !layers)) { set_error("tmat_model_layers: bad argument"); return TMAT_E_ARG; }
+    *n_layers = 0;
+    std::map<std::string, Tensor> m;
+    int patch = 0;
+    ModelShape ms;
+    std::vector<ModelLayer> ls;
+    if (!parse_blob(blob, n_bytes, m, patch) || !model_shape(m, patch, ms) || !model_layers(ms, unet_switches_from_env(), ls)) return TMAT_E_WEIGHTS;
+    *n_layers = (int)ls.size();
+    if (*n_layers > cap) { set_error("tmat_model_layers: cap is below the number of launches (n_layers holds it)"); return TMAT_E_CAP; }
+    for (size_t i = 0; i < ls.size(); i++) {
+        const int v[6] = {ls[i].ksize, ls[i].stride, ls[i].cin, ls[i].cout, ls[i].side, ls[i].launcher};
+        memcpy(layers + 6 * i, v, sizeof(v));
+    }
+    return TMAT_OK;
 }
 
 int tmat_prof_enable(tmat_handle h, int on)

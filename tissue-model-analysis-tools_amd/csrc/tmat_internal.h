@@ -129,6 +129,15 @@ inline int roi_compact_blocks(const RoiSegs &r, int frame_h, int frame_w, int C4
 // returns false (and sets the error) on unsupported shapes; roi (nullable; stride 2 with the 1x1 form only: the rectangles are output
 // pixels): region form
 bool launch_conv(const ConvArgs &a, hipStream_t s, const RoiSegs *roi = nullptr);
+// launch_conv's shape rule (pointers are only tested for null): cin % 64 == 0 for ksize 1 and 3, % 32 for the sub-pixel form, cout % 64 == 0, ...
+bool conv_mfma_takes(const ConvArgs &a);
+// The narrow layers' convolution (conv_narrow_kernels.hip), f32 contract only (prec 0): Cin and Cout multiples of 16, both >= 16, and
+// everything else of launch_conv's contract -- ksize 3 stride 1; ksize 1 stride 1 or 2 (even sizes); ksize 2 without resid / out_relu;
+// relu_in, nullable scale, resid with rs 0 or 1, relu_out, out_relu; Wo >= 2; M < 2^30; roi: the same table with the same meaning, any
+// first column and width.  The same bits as launch_conv where both take a shape.  False ("launch_conv_narrow: unsupported shape", before
+// any launch) otherwise.  The UNet driver launches it where conv_mfma_takes says no.
+bool conv_narrow_takes(const ConvArgs &a);
+bool launch_conv_narrow(const ConvArgs &a, hipStream_t s, const RoiSegs *roi = nullptr);
 // Convolution with f16 activations in memory (conv_f16act_kernels.hip; the invasion-depth classifier's TMAT_RESNET_PRECISION_F16ACT):
 // in / resid / out NHWC IEEE binary16 bits, W the f16 plane [ksize*ksize][Cout][Cin], scale (nullable) / shift f32.  ksize 1 (stride 1
 // or 2) or 3 (stride 1), Cin and Cout multiples of 64.  Returns false (and sets the error) on unsupported shapes.

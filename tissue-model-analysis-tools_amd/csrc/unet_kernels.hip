@@ -920,18 +920,28 @@ static void launch_conv_cfg(const ConvArgs &a, int M, int Ho, int Wo, hipStream_
 #define TMAT_64S_WN 1
 #endif
 
-bool launch_conv(const ConvArgs &a, hipStream_t s, const RoiSegs *roi)
+// The shapes conv_mfma_kernel takes -- the one statement of the rule: launch_conv refuses everything else, and the UNet driver
+// (tmat_api.cpp:conv, model_layers) sends what it refuses to launch_conv_narrow.
+bool conv_mfma_takes(const ConvArgs &a)
 {
+    if (a.stride < 1 || a.stride > 2) return false;
     const int Ho = a.h / a.stride, Wo = a.w / a.stride;
     const long long Mll = (long long)a.N * Ho * Wo;
-    if (!((a.ksize == 3 && a.stride == 1) || (a.ksize == 2 && a.stride == 1 && !a.resid) ||
+    const bool refused = (!((a.ksize == 3 && a.stride == 1) || (a.ksize == 2 && a.stride == 1 && !a.resid) ||
           (a.ksize == 1 && (a.stride == 1 || a.stride == 2))) || a.prec < 0 || a.prec > 3 || (a.prec == 3 && a.ksize == 2) || a.Cin % 32 || a.Cout % 64 ||
         ((a.ksize == 2 ? 4 : a.ksize * a.ksize) * (a.Cin / 32)) % ((a.ksize & 1) ? 2 * a.ksize * a.ksize : 4) || Mll <= 0 ||
-        Mll > 0x7fffffffLL / 2 || (a.resid && a.rs && ((Ho | Wo) & 1)) || Wo < 2 || (a.out_relu && a.ksize == 2)) {
+        Mll > 0x7fffffffLL / 2 || (a.resid && a.rs && ((Ho | Wo) & 1)) || Wo < 2 || (a.out_relu && a.ksize == 2));
+    return !refused;
+}
+
+bool launch_conv(const ConvArgs &a, hipStream_t s, const RoiSegs *roi)
+{
+    if (!conv_mfma_takes(a)) {
         set_error("launch_conv: unsupported shape");
         return false;
     }
-    const int M = (int)Mll;
+    const int Ho = a.h / a.stride, Wo = a.w / a.stride;
+    const int M = a.N * Ho * Wo;
     if (roi) {      // every segment inside the batch and the patch, at least two pixels wide; patch ranges in ascending order, or the
                     // previous segment's range again with a rectangle disjoint from every other one of that range
         bool ok = (a.stride == 1 || a.ksize == 1) && a.prec != 3 && roi->nseg >= 1 && roi->nseg <= ROI_MAX_SEGS;

@@ -140,6 +140,8 @@ def lib():
     L.tmat_resnet_set_precision.argtypes = [vp, i]
     L.tmat_conv2d.argtypes = [vp, i, vp, i, i, i, i, vp, i, i, i, vp, vp, vp, i, i, vp]
     L.tmat_conv2d_roi.argtypes = [vp, vp, i, i, i, i, vp, i, i, i, vp, vp, vp, i, i, i, vp, i, vp, vp]
+    L.tmat_conv2d_narrow.argtypes = [vp, vp, i, i, i, i, vp, i, i, i, i, vp, vp, vp, i, i, i, vp, i, vp, vp]
+    L.tmat_model_layers.argtypes = [vp, sz, i, vp, C.POINTER(i)]
     L.tmat_prof_enable.argtypes = [vp, i]
     L.tmat_debug_poison.argtypes = [vp, i]
     L.tmat_debug_held_bytes.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
@@ -205,7 +207,23 @@ EXPORTS = [
     "tmat_analyze_stack_batch_dev", "tmat_canny_mask_batch", "tmat_well_small_shape", "tmat_stack_well_front_dev",
     "tmat_cell_small_dev", "tmat_cell_well_front_dev", "tmat_cell_area_fit_dev",
     "tmat_roi_sep_quads", "tmat_debug_sepconv_quads",
+    "tmat_conv2d_narrow", "tmat_model_layers",
 ]
+
+
+MODEL_LAUNCHERS = ("conv_mfma_kernel", "conv_narrow_kernel", "sepconv_ws_kernel")
+
+
+def model_layers(weights_blob: bytes) -> np.ndarray:
+    """tmat_model_layers (include/tmat.h): the convolution launches of one forward of a weight blob, in launch order, as an (n, 6) int32
+    array of [ksize (2: sub-pixel form), stride, cin, cout, output side, launcher (index into MODEL_LAUNCHERS)].  Host only: no GPU, no
+    handle.  Raises TmatError (TMAT_E_WEIGHTS, with the rule) for a blob whose filter counts no kernel takes."""
+    L = lib()
+    buf = (C.c_char * len(weights_blob)).from_buffer_copy(weights_blob)
+    out = np.zeros((64, 6), np.int32)
+    n = C.c_int(0)
+    check(L.tmat_model_layers(C.cast(buf, C.c_void_p), len(weights_blob), out.shape[0], ptr(out), C.byref(n)), "tmat_model_layers")
+    return out[:n.value].copy()
 
 
 def check(rc: int, what: str = ""):
@@ -433,6 +451,35 @@ class Handle:
         check(L.tmat_conv2d_roi_s2(self._h, ptr(x), n, hh, ww, cin, ptr(w), cout, None if scale is None else ptr(scale), ptr(shift),
                                    int(bool(relu_in)), int(bool(relu_out)), ptr(sg) if len(sg) else None, len(sg), ptr(out),
                                    None if out_relu is None else ptr(out_relu)), "tmat_conv2d_roi_s2")
+        return out
+
+    def conv2d_narrow(self, x, w, scale, shift, segs, out, stride=1, resid=None, rs=0, subpixel=False, relu_in=False, relu_out=False, out_relu=None):
+        """conv2d_roi on the narrow layers' kernel (include/tmat.h:tmat_conv2d_narrow): cin and cout multiples of 16, stride 1 or 2 (ksize 1).
+        out (and out_relu, nullable) caller-filled (n, h up / stride, w up / stride, cout), up = 2 for the sub-pixel form; segs none for the
+        full-frame launch.  Returns out."""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(w, np.float32)
+        n, hh, ww, cin = x.shape
+        k, k2, ci2, cout = w.shape
+        if k != k2 or ci2 != cin:
+            raise ValueError("conv2d_narrow: weight shape does not match the input")
+        up = 2 if subpixel else 1
+        for o in (out, out_relu):
+            if o is not None and (o.dtype != np.float32 or not o.flags.c_contiguous or o.shape != (n, hh * up // stride, ww * up // stride, cout)):
+                raise ValueError("conv2d_narrow: out / out_relu must be C-contiguous float32 arrays of the result's shape")
+        shift = np.ascontiguousarray(shift, np.float32)
+        scale = None if scale is None else np.ascontiguousarray(scale, np.float32)
+        if resid is not None:
+            resid = np.ascontiguousarray(resid, np.float32)
+            if resid.shape != (n, hh >> rs, ww >> rs, cout):
+                raise ValueError("conv2d_narrow: resid must be (n, h >> rs, w >> rs, cout)")
+        if shift.shape != (cout,) or (scale is not None and scale.shape != (cout,)):
+            raise ValueError("conv2d_narrow: scale / shift must have cout entries")
+        sg = np.ascontiguousarray(np.asarray(segs, np.int32).reshape(-1, 6))
+        check(lib().tmat_conv2d_narrow(self._h, ptr(x), n, hh, ww, cin, ptr(w), k, int(stride), int(bool(subpixel)), cout,
+                                       None if scale is None else ptr(scale), ptr(shift), None if resid is None else ptr(resid), int(rs),
+                                       int(bool(relu_in)), int(bool(relu_out)), ptr(sg) if len(sg) else None, len(sg), ptr(out),
+                                       None if out_relu is None else ptr(out_relu)), "tmat_conv2d_narrow")
         return out
 
     def render_tree(self, backgrounds, trees, vis_width=2000):
