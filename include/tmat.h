@@ -72,6 +72,77 @@ int tmat_unet_predict(tmat_handle h, const float *x, int n, float *y);
 int tmat_predict_smooth(tmat_handle h, const float *x, int n, int hh, int ww, double *pred);
 
 /*
+ * The same for any `subdivisions` (smooth_tiled_predictions.py:220-267 with the library's own network as pred_func; the reference's
+ * comments :242-247 name 4).  subdivisions == 2 IS tmat_predict_smooth: the same code path, launches and region forms.  Any other
+ * value applies the input norm (tmat_set_input_norm) likewise, tiles with the general geometry of tmat_smooth_plan, runs the network
+ * full-frame in chunks of at most max_patches and blends on the device; the tile predictions (n_tiles P P floats) are allocated for
+ * the call, TMAT_E_HIP when that fails.
+ */
+int tmat_predict_smooth_ex(tmat_handle h, const float *x, int n, int hh, int ww, int subdivisions, double *pred);
+
+/*
+ * Smooth tiling around a predictor the CALLER runs (a Keras model.predict, say): the stage between tmat_preprocess_batch and
+ * tmat_postprocess_batch for a lab that keeps its own network.  Replaces everything of predict_img_with_smooth_windowing
+ * (smooth_tiled_predictions.py:220-267) but the pred_func calls of :174-182, for a 2-D single-channel image, any window_size >= 4
+ * and any 2 <= subdivisions <= window_size, bit for bit.
+ *
+ * tmat_smooth_plan (host, no handle) -- the geometry of _pad_img :74, _windowed_subdivs :152-163:
+ *   aug = int(round(ws (1 - 1 / s))) (Python's round: 4.5 -> 4, 7.5 -> 8), step = int(ws / s); the padded image is
+ *   (hh + 2 aug) x (ww + 2 aug); eight frames in the order of _rotate_mirror_do :95-113, even ones padded-height x padded-width, odd
+ *   ones transposed; per frame na x nb tiles at i, j in range(0, side - ws + 1, step), row-major.  counts = {na, nb of the even
+ *   frames, na, nb of the odd ones}; n_tiles their sum over the eight frames.  Global tile index: frame, then a, then b.  The step need
+ *   not divide side - ws: the strip no tile covers contributes 0.0 in that frame, as in the reference.  Any output pointer may be
+ *   null.  TMAT_E_ARG for window_size < 4, subdivisions < 2 or > window_size, an empty image, a frame side below window_size (the
+ *   reference returns an empty array or crashes on these).
+ * tmat_spline_window (host, no handle) -- _spline_window :26-41: win[window_size] f64, window_size >= 4, odd sizes included.
+ *
+ * The session, on any handle (tmat_create_plain is enough); one per handle, a second begin discards an open one:
+ * tmat_smooth_begin   uploads x (hh, ww) f32 and takes its minimum, the pad value of :77.  tmat_set_input_norm does not apply: the
+ *                     caller owns x.
+ * tmat_smooth_tiles   patches (count, ws, ws) f32 = the tiles [first, first + count), what :157-171 builds; any ranges, any order.
+ * tmat_smooth_put     preds (count, ws, ws) of dtype TMAT_SMOOTH_F32 or TMAT_SMOOTH_F64 = pred_func's results for those tiles (the
+ *                     trailing channel axis of size 1 implicit).  A session holds one dtype: a float64 put into a float32 session
+ *                     widens what is stored (no bit of the result changes), a float32 put into a float64 session is TMAT_E_ARG.  The
+ *                     buffer, n_tiles ws ws values (968 tiles, 400 MB at 640 x 640, ws 320, subdivisions 4), is allocated by the
+ *                     first put: TMAT_E_HIP when that fails.
+ * tmat_smooth_end     out (hh, ww) f64 = :185-265 (window, overlap-add, / s^2, D4 undo, mean, unpad); releases the session.
+ *                     TMAT_E_ARG, with the session left open, while a tile has not been put.
+ * A tile range outside [0, n_tiles) and a call without an open session are TMAT_E_ARG.
+ */
+#define TMAT_SMOOTH_F32 0
+#define TMAT_SMOOTH_F64 1
+int tmat_smooth_plan(int hh, int ww, int window_size, int subdivisions, int *aug, int *step, int counts[4], int *n_tiles);
+int tmat_spline_window(int window_size, double *win);
+int tmat_smooth_begin(tmat_handle h, const float *x, int hh, int ww, int window_size, int subdivisions, int *n_tiles);
+int tmat_smooth_tiles(tmat_handle h, int first, int count, float *patches);
+int tmat_smooth_put(tmat_handle h, int first, int count, const void *preds, int dtype);
+int tmat_smooth_end(tmat_handle h, double *out);
+/*
+ * PIL.Image.fromarray(x float32).resize((out_w, out_h), resample) for n mode-"F" images (n, H, W) -> (n, out_h, out_w): the two
+ * calls UNetXceptionPatchSegmentor.predict(x, auto_resample=True) makes around the smooth prediction (reference models.py:631-635
+ * LANCZOS, :647-651 NEAREST).  filter: TMAT_PIL_NEAREST or TMAT_PIL_LANCZOS (Pillow's own numbers).  Bit for bit Pillow's result
+ * (checked against Pillow 12.2.0): the convolution resample with f64 taps and f64 sums stored as f32, horizontal pass first, a pass
+ * whose sizes are equal skipped; the affine nearest scale whose source coordinate accumulates.  Sizes up to 32768 a side.
+ * tmat_resize_pil_f32 runs on the handle's device (tmat_create_plain is enough; the tap tables are made on the host and uploaded),
+ * tmat_host_resize_pil_f32 is its host twin.
+ *
+ * tmat_predict_auto_resample -- predict(x, auto_resample=True) (models.py:624-653) for one image without leaving the device: upload x
+ * (H, W) -> LANCZOS to (mid_h, mid_w) -> the input norm where tmat_set_input_norm is on (:637-638) -> the smooth prediction of
+ * tmat_predict_smooth -> float32 (Image.fromarray of a float64 array makes a mode-"F" image) -> NEAREST to (out_h, out_w) -> download.
+ * The reference hands Pillow its (rows, cols) shapes as sizes, which Pillow reads as (width, height): for an H x W input and
+ * target_shape = round((H, W) ds_ratio) = (th, tw) the caller passes mid = (tw, th) and out = (W, H), as the Python mirror does.
+ */
+#define TMAT_PIL_NEAREST 0
+#define TMAT_PIL_LANCZOS 1
+int tmat_resize_pil_f32(tmat_handle h, const float *x, int n, int H, int W, int out_h, int out_w, int filter, float *out);
+int tmat_host_resize_pil_f32(const float *x, int n, int H, int W, int out_h, int out_w, int filter, float *out);
+int tmat_predict_auto_resample(tmat_handle h, const float *x, int H, int W, int mid_h, int mid_w, int out_h, int out_w, float *out);
+
+/* Measurement only (tools/bench_smooth.py): device time, by HIP events, of the tile-gather launches and of the blend launch of the
+ * handle's last session. */
+int tmat_debug_smooth_times(tmat_handle h, double *tiles_ms, double *blend_ms);
+
+/*
  * compute_branches.py:309-328 for a batch: cv2.resize(img, round(shape * ds_ratio), INTER_LANCZOS4)
  * -> rescale_intensity(out_range=(0,1)).astype(f32) -> model.predict(auto_resample=False).
  * imgs: (n, H, W) u16; pred: (n, round(W*ds_ratio), round(H*ds_ratio)) f64 -- the reference passes its target shape to

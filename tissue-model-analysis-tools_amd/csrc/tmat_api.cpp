@@ -835,6 +835,28 @@ int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred
     return TMAT_OK;
 }
 
+// smooth_tiled_predictions.py:26-41 in f64.  scipy.signal.windows.triang(M): (2 n - 1) / M for even M, 2 n / (M + 1) for odd M,
+// n = 1 .. (M + 1) / 2, mirrored (the odd form without repeating its centre); np.average is np.mean: numpy's pairwise sum over ws.
+std::vector<double> spline_window_host(int ws)
+{
+    std::vector<double> tri(ws), wind(ws);
+    for (int i = 0; i < (ws + 1) / 2; i++) {
+        tri[i] = ws % 2 == 0 ? (2.0 * (i + 1) - 1.0) / ws : (2.0 * (i + 1)) / (ws + 1.0);
+        tri[ws - 1 - i] = tri[i];
+    }
+    const int isec = ws / 4;
+    for (int i = 0; i < ws; i++) {
+        double a2 = std::fabs(2 * tri[i]); double outer = (a2 * a2) / 2;
+        if (i >= isec && i < ws - isec) outer = 0;
+        double b2 = std::fabs(2 * (tri[i] - 1)); double inner = 1 - (b2 * b2) / 2;
+        if (i < isec || i >= ws - isec) inner = 0;
+        wind[i] = inner + outer;
+    }
+    const double avg = numpy_pairwise_sum(wind.data(), ws) / ws;
+    for (int i = 0; i < ws; i++) wind[i] = wind[i] / avg;
+    return wind;
+}
+
 }  // namespace tmat
 
 using namespace tmat;
@@ -994,23 +1016,7 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     // squared-spline window (smooth_tiled_predictions.py:26-41), f64, on host then uploaded
     {
         const int ws = patch;
-        std::vector<double> tri(ws), wind(ws);
-        for (int i = 0; i < ws / 2; i++) { tri[i] = (2.0 * (i + 1) - 1.0) / ws; tri[ws - 1 - i] = tri[i]; }
-        const int isec = ws / 4;
-        double sum = 0;
-        for (int i = 0; i < ws; i++) {
-            double a2 = std::fabs(2 * tri[i]); double outer = (a2 * a2) / 2;
-            if (i >= isec && i < ws - isec) outer = 0;
-            double b2 = std::fabs(2 * (tri[i] - 1)); double inner = 1 - (b2 * b2) / 2;
-            if (i < isec || i >= ws - isec) inner = 0;
-            wind[i] = inner + outer;
-        }
-        // np.average = np.mean: pairwise summation in numpy; ws <= 8*128 blocks... restate numpy's
-        // pairwise add.reduce for n < 8*PW_BLOCKSIZE? (n=320 > 128 -> pairwise halves)
-        c->win_host = wind;
-        sum = numpy_pairwise_sum(wind.data(), ws);
-        double avg = sum / ws;
-        for (int i = 0; i < ws; i++) wind[i] = wind[i] / avg;
+        const std::vector<double> wind = spline_window_host(ws);
         if (!hip_ok(hipMalloc((void **)&c->win1d, ws * sizeof(double)), "hipMalloc(win)") ||
             !hip_ok(hipMemcpy(c->win1d, wind.data(), ws * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(win)")) {
             tmat_destroy((tmat_handle)c); return TMAT_E_HIP;
@@ -1037,6 +1043,8 @@ void tmat_destroy(tmat_handle h)
     if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->stream3) { hipStreamSynchronize(c->stream3); hipStreamDestroy(c->stream3); }
     c->ws.free_all();
+    c->smooth.close();
+    for (hipEvent_t e : c->smooth.ev) if (e) hipEventDestroy(e);
     for (RoiEntry *e : c->roi_cache) { e->free_tabs(); if (e->order) hipFree(e->order); delete e; }
     if (c->win1d) hipFree(c->win1d);
     if (c->ma_table) hipFree(c->ma_table);

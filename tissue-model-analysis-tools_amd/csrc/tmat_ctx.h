@@ -153,8 +153,30 @@ enum ToolWs {
     N_TOOL_WS
 };
 
+// An open smooth-tiling session (smooth_kernels.hip: tmat_smooth_begin ... tmat_smooth_end): the uploaded image, its minimum, the window
+// and the predictions the caller has put so far.  It lives across calls and holds the caller's data, so it is no workspace:
+// tmat_debug_poison leaves it alone; `mem` owns every block and tmat_smooth_end, the next begin and tmat_destroy release them.
+struct SmoothSession {
+    bool open = false;
+    SmoothGeom g{};
+    float *x = nullptr, *padval = nullptr;      // (hh, ww); [min, max]
+    double *win = nullptr;                      // [ws]
+    void *pred = nullptr;                       // (n_tiles, ws, ws), made by the first put
+    bool pred_f64 = false;
+    std::vector<uint8_t> have;                  // per tile: put
+    WsList mem;
+    hipEvent_t ev[2] = {nullptr, nullptr};      // around the last kernel launch
+    double tiles_ms = 0, blend_ms = 0;          // device time of the gather launches / the blend of the last session (tmat_debug_smooth_times)
+    void close()
+    {
+        mem.free_all();
+        x = padval = nullptr; win = nullptr; pred = nullptr; pred_f64 = false; have.clear(); open = false;
+    }
+};
+
 struct Ctx {
     int device = 0;
+    SmoothSession smooth;
     std::vector<ResNetModel> resnets;                        // invasion-depth classifiers loaded on this handle (tmat_resnet_load)
     std::map<GaussKey, GaussTable> gauss;                    // gaussian kernel tables (gauss_tables.cpp)
     std::map<const GaussTable *, double *> gauss_dev;        // their device copies (stack_pipeline.cpp)
@@ -300,6 +322,9 @@ int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s, const
 const RoiPlan *roi_attach(Ctx *c, TileGeom &g);
 const RoiPlan *roi_find(const Ctx *c, const TileGeom &g);
 int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred_dev);      // x_dev is normalised in place when tmat_set_input_norm is on
+
+// squared-spline window of smooth_tiled_predictions.py:26-41 for any ws >= 4 (scipy's triang in its even and odd forms, numpy's mean)
+std::vector<double> spline_window_host(int ws);
 
 // numpy's pairwise summation of a contiguous f64 vector (np.add.reduce / np.mean inner loop):
 // 8 interleaved partial sums on blocks <= 128, recursive halves (rounded down to a multiple of 8) above.

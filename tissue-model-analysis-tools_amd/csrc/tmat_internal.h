@@ -228,6 +228,26 @@ void launch_norm_f32(float *x, size_t n, float mean, float sd, hipStream_t s);  
 void launch_extract_tiles(const float *x, const float *padval, int n, const TileGeom &g, float *patches, hipStream_t s);
 void launch_blend(const float *pred_patches, const double *win1d, int n, const TileGeom &g, double *out, hipStream_t s);
 
+// ---- smooth tiling for any window size and subdivision count (smooth_kernels.hip) -----------
+// One image.  Tile index: orientation-major, then a, then b (TileGeom's, image-major); a frame's tiles start at a step, b step for
+// a in [0, na), b in [0, nb), and the strip behind the last tile belongs to no tile when the step does not divide the frame.
+struct SmoothGeom {
+    int hh, ww;
+    int ws, sub, step, aug;
+    int Hp, Wp;
+    int na[2], nb[2];       // even / odd rotations
+    int tile_off[8];
+    int n_tiles;
+};
+// false (and the error set) for the geometries the stage refuses: ws < 4, sub < 2, sub > ws, an image side < 1, a frame side < ws,
+// or more tiles than an int counts
+bool smooth_geom(int hh, int ww, int ws, int sub, SmoothGeom &g);
+// patches (count, ws, ws): the tiles [first, first + count) of x (hh, ww) padded with padval[0]
+void launch_smooth_tiles(const float *x, const float *padval, const SmoothGeom &g, int first, int count, float *patches, hipStream_t s);
+// pred (n_tiles, ws, ws) f32 (f64: pred_f64) -> out (hh, ww) f64
+void launch_smooth_blend(const void *pred, bool pred_f64, const double *win1d, const SmoothGeom &g, double *out, hipStream_t s);
+void launch_widen_f32(const float *in, double *out, size_t n, hipStream_t s);
+
 // ---- ordered medial-axis thinning on the device (thin_kernels.hip) ------------------------------------
 bool thin_dev_supported(int H, int W);
 size_t thin_workspace_bytes(int n, int H, int W);

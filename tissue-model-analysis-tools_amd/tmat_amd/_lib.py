@@ -82,6 +82,17 @@ def lib():
     L.tmat_set_input_depth.argtypes = [vp, i]
     L.tmat_unet_predict.argtypes = [vp, vp, i, vp]
     L.tmat_predict_smooth.argtypes = [vp, vp, i, i, i, vp]
+    L.tmat_predict_smooth_ex.argtypes = [vp, vp, i, i, i, i, vp]
+    L.tmat_smooth_plan.argtypes = [i, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+    L.tmat_spline_window.argtypes = [i, vp]
+    L.tmat_smooth_begin.argtypes = [vp, vp, i, i, i, i, C.POINTER(i)]
+    L.tmat_smooth_tiles.argtypes = [vp, i, i, vp]
+    L.tmat_smooth_put.argtypes = [vp, i, i, vp, i]
+    L.tmat_smooth_end.argtypes = [vp, vp]
+    L.tmat_debug_smooth_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.tmat_resize_pil_f32.argtypes = [vp, vp, i, i, i, i, i, i, vp]
+    L.tmat_host_resize_pil_f32.argtypes = [vp, i, i, i, i, i, i, vp]
+    L.tmat_predict_auto_resample.argtypes = [vp, vp, i, i, i, i, i, i, vp]
     L.tmat_segment_batch.argtypes = [vp, vp, i, i, i, C.c_double, vp]
     L.tmat_postprocess_batch.argtypes = [vp, vp, i, i, i, i, i, vp]
     L.tmat_filter_edt_batch.argtypes = [vp, vp, i, i, i, vp, vp]
@@ -208,7 +219,43 @@ EXPORTS = [
     "tmat_cell_small_dev", "tmat_cell_well_front_dev", "tmat_cell_area_fit_dev",
     "tmat_roi_sep_quads", "tmat_debug_sepconv_quads",
     "tmat_conv2d_narrow", "tmat_model_layers",
+    "tmat_predict_smooth_ex", "tmat_smooth_plan", "tmat_spline_window", "tmat_smooth_begin", "tmat_smooth_tiles", "tmat_smooth_put",
+    "tmat_smooth_end", "tmat_debug_smooth_times", "tmat_resize_pil_f32", "tmat_host_resize_pil_f32", "tmat_predict_auto_resample",
 ]
+
+PIL_FILTERS = {"nearest": 0, "lanczos": 1}      # TMAT_PIL_*, Pillow's Image.Resampling numbers
+
+
+def host_resize_pil_f32(x: np.ndarray, out_shape, resample: str) -> np.ndarray:
+    """tmat_host_resize_pil_f32: PIL.Image.fromarray(x).resize(out_shape[::-1], resample) of float32 images (H, W) or (n, H, W) on the
+    host; resample "lanczos" or "nearest"; out_shape (rows, cols)"""
+    x = np.ascontiguousarray(x, np.float32)
+    single = x.ndim == 2
+    xb = x[None] if single else x
+    out = np.empty((xb.shape[0], int(out_shape[0]), int(out_shape[1])), np.float32)
+    check(lib().tmat_host_resize_pil_f32(ptr(xb), xb.shape[0], xb.shape[1], xb.shape[2], out.shape[1], out.shape[2], PIL_FILTERS[resample], ptr(out)),
+          "tmat_host_resize_pil_f32")
+    return out[0] if single else out
+
+
+SMOOTH_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}       # TMAT_SMOOTH_*
+
+
+def smooth_plan(hh: int, ww: int, window_size: int, subdivisions: int):
+    """tmat_smooth_plan (include/tmat.h): (aug, step, (na, nb of the even frames, na, nb of the odd ones), n_tiles) of the smooth
+    tiling of an hh x ww image.  Host only.  Raises TmatError (TMAT_E_ARG) for the geometries the stage refuses."""
+    aug, step, n = C.c_int(0), C.c_int(0), C.c_int(0)
+    counts = (C.c_int * 4)()
+    check(lib().tmat_smooth_plan(int(hh), int(ww), int(window_size), int(subdivisions), C.byref(aug), C.byref(step), counts, C.byref(n)),
+          "tmat_smooth_plan")
+    return aug.value, step.value, tuple(counts), n.value
+
+
+def spline_window(window_size: int) -> np.ndarray:
+    """tmat_spline_window: smooth_tiled_predictions._spline_window(window_size) (reference :26-41), float64.  Host only."""
+    win = np.empty(max(int(window_size), 0), np.float64)
+    check(lib().tmat_spline_window(int(window_size), ptr(win)), "tmat_spline_window")
+    return win
 
 
 MODEL_LAUNCHERS = ("conv_mfma_kernel", "conv_narrow_kernel", "sepconv_ws_kernel")
@@ -286,6 +333,78 @@ class Handle:
         check(lib().tmat_predict_smooth(self._h, ptr(xb), xb.shape[0], xb.shape[1], xb.shape[2], ptr(out)),
               "tmat_predict_smooth")
         return out[0] if single else out
+
+    def predict_smooth_ex(self, x: np.ndarray, subdivisions: int) -> np.ndarray:
+        """tmat_predict_smooth_ex: predict_smooth for any subdivisions (2: predict_smooth itself)"""
+        x = np.ascontiguousarray(x, np.float32)
+        single = x.ndim == 2
+        xb = x[None] if single else x
+        out = np.empty(xb.shape, np.float64)
+        check(lib().tmat_predict_smooth_ex(self._h, ptr(xb), xb.shape[0], xb.shape[1], xb.shape[2], int(subdivisions), ptr(out)),
+              "tmat_predict_smooth_ex")
+        return out[0] if single else out
+
+    def resize_pil_f32(self, x: np.ndarray, out_shape, resample: str) -> np.ndarray:
+        """tmat_resize_pil_f32: host_resize_pil_f32 on the device"""
+        x = np.ascontiguousarray(x, np.float32)
+        single = x.ndim == 2
+        xb = x[None] if single else x
+        out = np.empty((xb.shape[0], int(out_shape[0]), int(out_shape[1])), np.float32)
+        check(lib().tmat_resize_pil_f32(self._h, ptr(xb), xb.shape[0], xb.shape[1], xb.shape[2], out.shape[1], out.shape[2], PIL_FILTERS[resample],
+                                        ptr(out)), "tmat_resize_pil_f32")
+        return out[0] if single else out
+
+    def predict_auto_resample(self, x: np.ndarray, mid_shape, out_shape) -> np.ndarray:
+        """tmat_predict_auto_resample: x (H, W) float32 -> LANCZOS to mid_shape (rows, cols) -> input norm -> smooth prediction ->
+        float32 -> NEAREST to out_shape (rows, cols), one device chain"""
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim != 2:
+            raise ValueError("predict_auto_resample: expected a 2-D single-channel image")
+        out = np.empty((int(out_shape[0]), int(out_shape[1])), np.float32)
+        check(lib().tmat_predict_auto_resample(self._h, ptr(x), x.shape[0], x.shape[1], int(mid_shape[0]), int(mid_shape[1]), out.shape[0], out.shape[1],
+                                               ptr(out)), "tmat_predict_auto_resample")
+        return out
+
+    # smooth tiling around a predictor the caller runs (include/tmat.h: tmat_smooth_begin ... tmat_smooth_end)
+    def smooth_begin(self, x: np.ndarray, window_size: int, subdivisions: int) -> int:
+        """opens the session on x (hh, ww) float32 (a second begin discards an open one) -> n_tiles"""
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim != 2:
+            raise ValueError("smooth_begin: expected a 2-D single-channel image")
+        n = C.c_int(0)
+        check(lib().tmat_smooth_begin(self._h, ptr(x), x.shape[0], x.shape[1], int(window_size), int(subdivisions), C.byref(n)),
+              "tmat_smooth_begin")
+        self._smooth_ws = int(window_size)
+        return n.value
+
+    def smooth_tiles(self, first: int, count: int) -> np.ndarray:
+        """the tiles [first, first + count) of the open session, (count, ws, ws) float32"""
+        ws = getattr(self, "_smooth_ws", 0)
+        out = np.empty((max(int(count), 0), ws, ws), np.float32)
+        check(lib().tmat_smooth_tiles(self._h, int(first), int(count), ptr(out)), "tmat_smooth_tiles")
+        return out
+
+    def smooth_put(self, first: int, preds: np.ndarray):
+        """the predictor's results for the tiles [first, first + len(preds)): (k, ws, ws) or (k, ws, ws, 1), float32 or float64"""
+        p = np.ascontiguousarray(preds)
+        ws = getattr(self, "_smooth_ws", 0)
+        if p.ndim == 4 and p.shape[-1] == 1:
+            p = p.reshape(p.shape[:3])
+        if p.dtype not in SMOOTH_DTYPES or p.ndim != 3 or p.shape[1:] != (ws, ws):
+            raise ValueError(f"smooth_put: expected (k, {ws}, {ws}) float32 or float64 predictions")
+        check(lib().tmat_smooth_put(self._h, int(first), p.shape[0], ptr(p), SMOOTH_DTYPES[p.dtype]), "tmat_smooth_put")
+
+    def smooth_end(self, shape) -> np.ndarray:
+        """blends what was put -> (hh, ww) float64 (shape: the image's); releases the session"""
+        out = np.empty(tuple(shape), np.float64)
+        check(lib().tmat_smooth_end(self._h, ptr(out)), "tmat_smooth_end")
+        return out
+
+    def smooth_times(self):
+        """(tile gather ms, blend ms) on the device for the last session (tmat_debug_smooth_times)"""
+        a, b = C.c_double(0), C.c_double(0)
+        check(lib().tmat_debug_smooth_times(self._h, C.byref(a), C.byref(b)), "tmat_debug_smooth_times")
+        return a.value, b.value
 
     def medial_axis(self, mask: np.ndarray):
         """tmat_medial_axis_batch: mask (n, h, w) bool/u8 -> (skel (n, h, w) bool, dist (n, h, w) f64), on the device"""

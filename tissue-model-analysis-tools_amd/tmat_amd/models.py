@@ -2,7 +2,8 @@
 
 `UNetXceptionPatchSegmentor` keeps the reference constructor and `predict(x, auto_resample=True)`
 contract; the UNet of models.py:85-171 and the smooth tiled prediction run in HIP kernels behind
-the C-ABI (tmat_create / tmat_predict_smooth).  Weights come from a "TMATW001" container (Keras
+the C-ABI (tmat_create / tmat_predict_smooth; with the default auto_resample, Pillow's two resizes around it too, as one device
+chain: tmat_predict_auto_resample).  Weights come from a "TMATW001" container (Keras
 tensor layouts; tools/convert_keras_h5.py turns checkpoint_N.h5 into one where h5py exists).
 """
 from __future__ import annotations
@@ -84,17 +85,23 @@ class UNetXceptionPatchSegmentor:
         original_shape = x.shape
         target_shape = tuple(np.round(np.multiply(original_shape[:2], self.ds_ratio)).astype(int))
         do_resampling = original_shape != target_shape and auto_resample
+        normed = self.norm_mean is not None and self.norm_std is not None
         if do_resampling:
-            from PIL import Image
-            x = np.array(Image.fromarray(x).resize(target_shape, resample=Image.Resampling.LANCZOS))
-        if self.norm_mean is not None and self.norm_std is not None:
+            # Image.fromarray(x).resize(target_shape, LANCZOS) -> norm -> smooth prediction -> Image.fromarray(pred).resize(original_shape,
+            # NEAREST) as one device chain (tmat_predict_auto_resample).  Pillow reads a size as (width, height) and the reference passes
+            # (rows, cols): the network sees a (target cols, target rows) image and an H x W input comes back as a float32 (W, H) array
+            if x.ndim != 2:
+                raise ValueError("expected a 2-D single-channel image")
+            if not normed:
+                return self.handle.predict_auto_resample(x, target_shape[::-1], original_shape[::-1])
+            self.handle.set_input_norm(self.norm_mean, self.norm_std)       # (x - norm_mean) / norm_std between the resize and the tiling
+            try:
+                return self.handle.predict_auto_resample(x, target_shape[::-1], original_shape[::-1])
+            finally:
+                self.handle.set_input_norm(None, None)
+        if normed:
             x = ((x - self.norm_mean) / self.norm_std).astype(np.float32)
-        pred = predict_img_with_smooth_windowing(x, window_size=self.patch_size, subdivisions=2,
-                                                 pred_func=self.model.predict)
-        if do_resampling:
-            from PIL import Image
-            pred = np.array(Image.fromarray(pred).resize(original_shape, resample=Image.Resampling.NEAREST))
-        return pred
+        return predict_img_with_smooth_windowing(x, window_size=self.patch_size, subdivisions=2, pred_func=self.model.predict)
 
 
 def get_unet_patch_segmentor_from_cfg(cfg_json: str, **kw) -> UNetXceptionPatchSegmentor:

@@ -3,7 +3,7 @@
 /root/reference (read-only, this container only; the reference never travels to the GPU box).
 
 Only inputs and expected outputs are stored -- no reference source text.
-Run:  python tools/make_goldens.py [blend] [dmt] [morse] [filter]
+Run:  python tools/make_goldens.py [blend] [smooth_general] [pil_resize] [dmt] [morse] [filter]
 The `filter` group needs scikit-image and therefore /opt/conda/bin/python3.9 (skimage 0.18.3).
 Shims for absent third-party modules (numba.njit = identity decorator, cv2 colour stub used only
 by plotting code) are created in a temp dir, exactly as SURVEY.md section 8c describes.
@@ -61,6 +61,63 @@ def gen_blend():
     out["ident640_maxerr"] = np.float64(np.abs(res - img).max())
     np.savez_compressed(GOLD / "blend.npz", **out)
     print("blend.npz", {k: getattr(v, "shape", None) for k, v in out.items()})
+
+
+def gen_smooth_general():
+    """the reference driver at subdivisions 2, 3 and 4, odd windows, steps that do not divide the frame (tests/helpers/smooth_cases.py):
+    inputs, outputs, windows, geometry and the log of predictor calls"""
+    from fl_tissue_model_tools import smooth_tiled_predictions as stp
+    sys.path.insert(0, str(REPO / "tests" / "helpers"))
+    import smooth_cases as sc
+
+    out = {"names": np.array(sc.NAMES)}
+    for ws in sc.WINDOWS:
+        out[f"window{ws}"] = stp._spline_window(ws)
+    for name, shape, ws, sub, kind in sc.CASES:
+        img = sc.case_image(name)
+        pred = sc.predictor_of(name)
+        stp.cached_2d_windows.clear()
+        res = np.asarray(stp.predict_img_with_smooth_windowing(img, ws, sub, pred))
+        assert res.shape == img.shape and res.dtype == np.float64, (name, res.shape, res.dtype)
+        shapes, sha = pred.log()
+        aug = int(round(ws * (1 - 1.0 / sub)))
+        step = int(ws / sub)
+        frames = [(img.shape[0] + 2 * aug, img.shape[1] + 2 * aug), (img.shape[1] + 2 * aug, img.shape[0] + 2 * aug)]
+        counts = [len(range(0, side - ws + 1, step)) for f in frames for side in f]
+        assert int(shapes[:, 0].sum()) == 4 * (counts[0] * counts[1] + counts[2] * counts[3]), name
+        out[name + "_in"] = img
+        out[name + "_out"] = res
+        out[name + "_geom"] = np.array([ws, sub, aug, step] + counts + [int(shapes[:, 0].sum()), len(shapes)], np.int64)
+        out[name + "_calls"] = shapes
+        out[name + "_calls_sha256"] = sha
+        if kind == "identity":
+            out[name + "_maxerr"] = np.float64(np.abs(res - img).max())
+        print(name, "geom", out[name + "_geom"].tolist(), "calls", len(shapes))
+    np.savez_compressed(GOLD / "smooth_general.npz", **out)
+    print("smooth_general.npz", (GOLD / "smooth_general.npz").stat().st_size, "bytes")
+
+
+def gen_pil_resize():
+    """Pillow's own resize of mode-"F" images, LANCZOS and NEAREST (tests/helpers/pil_resize_ref.py:cases): a SHA-256 of every result, the
+    results themselves for the smallest input"""
+    import PIL
+    from PIL import Image
+    sys.path.insert(0, str(REPO / "tests" / "helpers"))
+    import pil_resize_ref as pr
+
+    flt = {"lanczos": Image.Resampling.LANCZOS, "nearest": Image.Resampling.NEAREST}
+    out = {"pillow_version": np.array(PIL.__version__), "keys": np.array([c[0] for c in pr.cases()])}
+    for shape in pr.SHAPES:
+        x = pr.case_input(shape)
+        out[f"in_{shape[0]}x{shape[1]}_sha256"] = np.frombuffer(hashlib.sha256(x.tobytes()).digest(), np.uint8)
+    for key, shape, tgt, f in pr.cases():
+        res = np.array(Image.fromarray(pr.case_input(shape)).resize(tgt[::-1], resample=flt[f]))
+        assert res.shape == tgt and res.dtype == np.float32, (key, res.shape, res.dtype)
+        out[key + "_sha256"] = np.frombuffer(hashlib.sha256(np.ascontiguousarray(res).tobytes()).digest(), np.uint8)
+        if shape == pr.SHAPES[0]:
+            out[key + "_out"] = res
+    np.savez_compressed(GOLD / "pil_resize.npz", **out)
+    print("pil_resize.npz", len(pr.cases()), "cases,", (GOLD / "pil_resize.npz").stat().st_size, "bytes")
 
 
 
