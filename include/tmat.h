@@ -1226,6 +1226,28 @@ int tmat_roi_sep_quads(int hh, int ww, int patch, int n_up, const int *up_channe
 int tmat_debug_sepconv_quads(tmat_handle h, const float *x, int n, int hh, int ww, int cin, int relu_in, const float *dw9, const float *pw,
                              int cout, const float *scale, const float *shift, int relu_out, const float *stem_w, const float *stem_scale,
                              const float *stem_shift, const int *quads, int n_quads, float *out);
+/*
+ * The quadrant table of a POOLED fused separable layer (layer = 6 b + 3 of a fused level): the rule, order, counts and refusals of
+ * tmat_roi_sep_quads on that layer's comp.  For every pooled pixel a later launch or copy reads, every quadrant that holds a pixel of
+ * its 3 x 3 window inside the patch is listed.  Host arithmetic, no GPU.
+ * The pooled fused launches and the pooling fix-up launches behind them take the table where the shared-interior form or one above it
+ * runs, by the switch TMAT_ROI_QUAD_POOL (read at tmat_create, 0 or 1; independent of TMAT_ROI_QUAD): unset, the batch pipeline uses it
+ * for the levels of ROI_QUAD_POOL_LEVELS (csrc/roi_plan.h) and tmat_predict_smooth does not; 0: nobody; 1: both.  tmat_debug_sep_tiles
+ * then reports the launch's packed tiles as planned.
+ */
+int tmat_roi_sep_quads_pool(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                            unsigned fused_mask, int form, int layer, int k, int cap, int *counts, int *ids);
+/*
+ * Test-only (tests/test_gpu_sep_quads_pool.py): ONE pooled fused separable launch in quadrant form, and the full-frame quadrant fix-up
+ * launch behind it, on host buffers with the caller's list of quadrant ids (as tmat_debug_sepconv_quads).  x: (n, hh, ww, cin); resid
+ * and out: (n, hh / 2, ww / 2, cout), cout / 4 a power of two.  out is caller-filled and changed in place: a pooled pixel equals
+ * MaxPooling2D(3, 2, "same") + resid where every quadrant its window touches inside the patch is listed; the pooled pixels of a quadrant
+ * that is not listed come back as they went in, except its boundary pixels (row 3 and column 3 of its 4 x 4), which the fix-up
+ * launch rewrites.
+ */
+int tmat_debug_sepconv_pool_quads(tmat_handle h, const float *x, int n, int hh, int ww, int cin, int relu_in, const float *dw9, const float *pw,
+                                  int cout, const float *scale, const float *shift, int relu_out, const float *resid, const int *quads,
+                                  int n_quads, float *out);
 
 /*
  * Test-only (tests/test_gpu_roi_sep.py): the fused separable launches of the handle's last down pass, in launch order -- planned[i]

@@ -182,7 +182,7 @@ static int enqueue_down(Ctx *c, int k, int slot, const TileGeom &g)
     const RoiPlan *plan = roi_find(c, g);
     int rc = oversize ? unet_forward_dev(c, pin, k * g.tiles_per_img, c->patch_out, s)
                       : unet_down_dev(c, pin, k * g.tiles_per_img, c->dout[slot], s, plan, c->padval[slot],
-                                      roi_down_resolve(c, plan, k, c->padval[slot] != nullptr, true), roi_quad_on(c, true));
+                                      roi_down_resolve(c, plan, k, c->padval[slot] != nullptr, true), roi_quad_on(c, true), roi_quad_pool_on(c, true));
     if (rc) return rc;
     TMAT_HIP(hipEventRecord(c->ev_down[slot], s));
     c->down_pending[slot] = true;

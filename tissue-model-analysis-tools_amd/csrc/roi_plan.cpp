@@ -844,13 +844,14 @@ long long roi_sep_tile_table(const RoiPlan &p, RoiDownForm form, int layer, int 
     return full;
 }
 
-long long roi_sep_quad_table(const RoiPlan &p, RoiDownForm form, int layer, int k, std::vector<int> &out, long long *n_own, long long *n_ids)
+// the quadrant table of fused layer 6 b + kk (kk = 1: roi_sep_quad_table, 3: roi_sep_quad_pool_table) -- one rule, one order
+static long long sep_quad_table(const RoiPlan &p, RoiDownForm form, int layer, int kk, int k, std::vector<int> &out, long long *n_own, long long *n_ids)
 {
     out.clear();
     *n_own = *n_ids = 0;
     const RoiDownPlan &d = p.down;
     // (asked for the shared-interior form or above: a plan in which no class shares resolves it to the constant-ring form, whose comp is live)
-    if (form < ROI_DOWN_SHARE || roi_down_form(p, form) < ROI_DOWN_CONST || layer < 0 || layer % 6 != 1 || d.comp.empty()) return 0;
+    if (form < ROI_DOWN_SHARE || roi_down_form(p, form) < ROI_DOWN_CONST || layer < 0 || layer % 6 != kk || d.comp.empty()) return 0;
     form = roi_down_form(p, form);
     std::vector<int> tiles;
     const long long full = roi_sep_tile_table(p, form, layer, k, tiles);
@@ -878,6 +879,16 @@ long long roi_sep_quad_table(const RoiPlan &p, RoiDownForm form, int layer, int 
     *n_ids = (long long)out.size();
     while (out.size() % 4) out.push_back(out.back());
     return full;
+}
+
+long long roi_sep_quad_table(const RoiPlan &p, RoiDownForm form, int layer, int k, std::vector<int> &out, long long *n_own, long long *n_ids)
+{
+    return sep_quad_table(p, form, layer, 1, k, out, n_own, n_ids);
+}
+
+long long roi_sep_quad_pool_table(const RoiPlan &p, RoiDownForm form, int layer, int k, std::vector<int> &out, long long *n_own, long long *n_ids)
+{
+    return sep_quad_table(p, form, layer, 3, k, out, n_own, n_ids);
 }
 
 void roi_down_segs(const RoiPlan &p, RoiDownForm form, int l, int k, RoiSegs &out)
@@ -1207,6 +1218,25 @@ extern "C" int tmat_roi_sep_quads(int hh, int ww, int patch, int n_up, const int
     counts[0] = (int)tab.size(); counts[1] = (int)n_own; counts[2] = (int)n_ids; counts[3] = (int)full;
     if (ids) {
         if ((int)tab.size() > cap) { set_error("tmat_roi_sep_quads: cap too small"); return TMAT_E_ARG; }
+        std::copy(tab.begin(), tab.end(), ids);
+    }
+    return TMAT_OK;
+}
+
+// The same of pooled fused layer 6 b + 3 (roi_sep_quad_pool_table; refused below ROI_DOWN_SHARE and for every other layer): same counts
+extern "C" int tmat_roi_sep_quads_pool(int hh, int ww, int patch, int n_up, const int *up_channels, int n_down, const int *down_channels,
+                                       unsigned fused_mask, int form, int layer, int k, int cap, int *counts, int *ids)
+{
+    RoiPlan p;
+    if (int rc = down_plan_for("tmat_roi_sep_quads_pool", counts && k >= 1 && form >= ROI_DOWN_FULL && form <= ROI_DOWN_SHARE_FUSED_RECT, hh, ww, patch,
+                               n_up, up_channels, n_down, down_channels, fused_mask, ROI_MAX_CLASSES, p)) return rc;
+    std::vector<int> tab;
+    long long n_own = 0, n_ids = 0;
+    const long long full = roi_sep_quad_pool_table(p, (RoiDownForm)form, layer, k, tab, &n_own, &n_ids);
+    if (full <= 0) { set_error("tmat_roi_sep_quads_pool: not a pooled fused layer of the plan under a sharing form"); return TMAT_E_ARG; }
+    counts[0] = (int)tab.size(); counts[1] = (int)n_own; counts[2] = (int)n_ids; counts[3] = (int)full;
+    if (ids) {
+        if ((int)tab.size() > cap) { set_error("tmat_roi_sep_quads_pool: cap too small"); return TMAT_E_ARG; }
         std::copy(tab.begin(), tab.end(), ids);
     }
     return TMAT_OK;

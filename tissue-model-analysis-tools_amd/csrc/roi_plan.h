@@ -175,6 +175,9 @@ constexpr unsigned ROI_SHARE_FUSED_RECT_LEVELS = 3u;
 // Fused levels (bit b) whose plain layer 6 b + 1 visits 8 x 8 quadrants instead of 16 x 16 tiles (roi_sep_quad_table) where a pass runs
 // the quadrant form (TMAT_ROI_QUAD).  A level whose launch does not pay is taken out here, by one bit; it keeps its tile table
 constexpr unsigned ROI_QUAD_LEVELS = 3u;
+// The same for the pooled layer 6 b + 3 (roi_sep_quad_pool_table; TMAT_ROI_QUAD_POOL): its launch and the pooling fix-up behind it then
+// work in quadrants.  Set by the per-launch trace of DESIGN 4.1.9
+constexpr unsigned ROI_QUAD_POOL_LEVELS = 3u;
 
 struct RoiPlan {
     int hh = 0, ww = 0, ws = 0, n_up = 0;
@@ -245,8 +248,8 @@ int roi_down_stem_layer(const RoiPlan &p, RoiDownForm form);
 // rect_live, a subsequence of the live table in its order.  Returns the full-frame tile count k tiles_per_img TPP, 0 when the layer has
 // no tile rectangles (or under ROI_DOWN_FULL); out.size() == that count means every patch is computed whole.
 long long roi_sep_tile_table(const RoiPlan &p, RoiDownForm form, int layer, int k, std::vector<int> &out);
-// The same launch at 8 x 8 QUADRANT granularity, for the plain fused layer 6 b + 1 from ROI_DOWN_SHARE upwards only (the pooled layer's
-// exchange crosses the quadrant borders and its strips are addressed by tile: it keeps its tile table).  Walks the tiles of
+// The same launch at 8 x 8 QUADRANT granularity, for the plain fused layer 6 b + 1 from ROI_DOWN_SHARE upwards only (the pooled layer
+// 6 b + 3 has a table of its own, below).  Walks the tiles of
 // roi_sep_tile_table in their order and emits, per tile in slot order (qy, qx) row-major, the full-frame id
 // patch * QW * QW + (2 ty + qy) * QW + 2 tx + qx  (QW = res / 8) of every quadrant that holds a comp pixel; then all four quadrants of
 // every tile of the k all-constant patches behind the pass's patches.  The kernel takes the ids four to a packed tile, so the last
@@ -254,6 +257,12 @@ long long roi_sep_tile_table(const RoiPlan &p, RoiDownForm form, int layer, int 
 // *n_own: the ids of the pass's own patches, *n_ids: all ids before the padding.  Returns the full-frame tile count of the pass's own
 // patches like roi_sep_tile_table, 0 (out empty) for any other layer or form.
 long long roi_sep_quad_table(const RoiPlan &p, RoiDownForm form, int layer, int k, std::vector<int> &out, long long *n_own, long long *n_ids);
+// The quadrant table of the POOLED fused layer 6 b + 3, from ROI_DOWN_SHARE upwards: the same rule, order, constant patches and padding
+// on the layer's own comp (the 3 x 3 windows of the pooled pixels the patch computes itself: comp of 6 b + 5 through the pooling's taps).
+// So for every pooled pixel a later launch or copy reads, every quadrant that holds a pixel of its window inside the patch is listed --
+// what the tile table guarantees one level coarser: the launch leaves a quadrant's last pooled row and column as partial maxima and
+// the fix-up pass completes them from the strips of the quadrants below and to the right.  0 (out empty) for any other layer or form.
+long long roi_sep_quad_pool_table(const RoiPlan &p, RoiDownForm form, int layer, int k, std::vector<int> &out, long long *n_own, long long *n_ids);
 // The launch arguments of layer l in a pass of k images (tmat_internal.h has the structs), in the pass's class-major patch order: class
 // c holds the patches k class_base[c] .. k class_base[c + 1] - 1, classes without patches are left out, and the k all-constant
 // patches of ROI_DOWN_CONST and above sit behind them, at k tiles_per_img.

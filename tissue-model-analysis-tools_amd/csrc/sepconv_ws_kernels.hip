@@ -48,6 +48,7 @@ static_assert(WS_TOTAL * 4 <= 160 * 1024, "LDS budget");
 constexpr int WS_WPITCH = 22, WS_WP = 21 * WS_WPITCH, WS_NWP = (WS_WP + 63) / 64, WS_WIN = WS_TOTAL, WS_TOTAL_STEM = WS_WIN + 4 * WS_NWP * 64;
 static_assert(WS_TOTAL_STEM * 4 <= 160 * 1024, "LDS budget (stem form)");
 static_assert(8 * 9 * 128 <= WS_A + WS_X, "exchange buffer fits an A stage + gap");
+static_assert(6 * 10 * 128 <= 8 * 9 * 128, "the quadrant form's exchange fits the tile form's buffer");
 
 struct WsArgs {
     const float *in;      // (N, H, W, Cin)
@@ -111,18 +112,20 @@ __device__ __forceinline__ int ws_tab_read(int mt, const int *tab)
 }
 
 //
-// QUAD (plain ROI forms only; roi_plan.h:roi_sep_quad_table): the kernel is organised in 8 x 8 quadrants already -- producer p owns one with a
+// QUAD (ROI forms of the f32 path; roi_plan.h:roi_sep_quad_table): the kernel is organised in 8 x 8 quadrants already -- producer p owns one with a
 // private halo, base pointer, border masks and (STEM) window; the consumers multiply 256 A rows without knowing which pixels they are; each
 // 16-byte store of the plain epilogue covers 8 pixels of one tile row inside one quadrant.  So a "tile" can be ANY four quadrants: nMt
 // is then the number of PACKED tiles and tab[4 mt + slot] the full-frame quadrant n QPP + qy QW + qx of slot (qy, qx) of packed tile mt.
 // Producer p takes the entry of its slot where the tile form derives its quadrant's position from the tile; consumer wave w, which holds
 // rows 2 (w & 3), 2 (w & 3) + 1 of slots 2 (w >> 2) and 2 (w >> 2) + 1, stores through one descriptor per slot.  Per-pixel arithmetic,
 // LDS map, phases and MFMA order are untouched, so a visited quadrant gets the bits of the tile form.
+// QUAD with POOL (roi_plan.h:roi_sep_quad_pool_table): the producers and the MFMA phase are those of the plain QUAD form; the pooling
+// epilogue works per quadrant (store_tile_pool_quad) and pool_fix_add_quad_kernel finishes the quadrant edges.
 template <bool RELU_IN, bool POOL, int PREC = 0, bool STEM = false, bool ROI = false, bool QUAD = false>
 __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, int nNt, int G, std::conditional_t<ROI, const int *, RoiNone> tab)
 {
     static_assert(!ROI || PREC == 0, "ROI: f32 path only");
-    static_assert(!QUAD || (ROI && !POOL && PREC == 0), "QUAD: plain region form of the f32 path only");
+    static_assert(!QUAD || (ROI && PREC == 0 && !(POOL && STEM)), "QUAD: region forms of the f32 path only");
     __shared__ __attribute__((aligned(16))) float smem[STEM ? WS_TOTAL_STEM : WS_TOTAL];
 
     // persistent ranges: blocks b and b + 8 share an XCD; every XCD gets a contiguous super-range of the (pixel tile, channel tile) pairs and
@@ -505,7 +508,7 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
     // vector phase every vector instruction of the 8 consumer waves delays the producers' depthwise arithmetic and vice versa.
     const int CoutB = a.Cout * 4;
     const float relu_lo = a.relu_out ? 0.f : -__builtin_inff();        // fmaxf(v, relu_lo): ReLU or identity without a select per value
-    const unsigned vo_pool = (unsigned)(4 * h * a.Cout + r) * 4u;        // pooled pixel 4h (+ q), channel r (+ 32 jn)
+    const unsigned vo_pool = (unsigned)((QUAD ? h : 4 * h) * a.Cout + r) * 4u;        // pooled pixel 4h (+ q), channel r (+ 32 jn); QUAD: pixel h (+ 2 pair)
     float rv[4][4];
     // ROI: the full-frame tile of the pair cj the consumers work on, re-read behind every epilogue (nothing of a tile uses it before the
     // next step: the load returns while the wave waits at the step's closing barrier)
@@ -515,6 +518,26 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
     int ctile1 = QUAD ? ws_tab_read(4 * (j0 / nNt) + cslot + 1, tab) : 0;
     auto load_resid = [&](int jj) {
         const int mc = jj / nNt, nt = jj - mc * nNt;
+        if constexpr (QUAD && POOL) {
+            // pooled row wave & 3 of both slots' quadrants, in the layout the stores use (store_tile_pool_quad): rv[jn][2 pair + slot] is
+            // pooled pixel 2 pair + h of the slot.  A quadrant's last pooled row and column get their residual in pool_fix_add_quad_kernel
+            if ((wave & 3) < 3) {
+#pragma unroll
+                for (int sl = 0; sl < 2; sl++) {
+                    const int qd = sl ? ctile1 : ctile;
+                    const int n = qd / TPP, tr = qd - n * TPP;
+                    const int qy = tr / TW, qx = tr - qy * TW;
+                    const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(
+                        (void *)(a.resid + (((size_t)n * (a.H >> 1) + qy * 4 + (wave & 3)) * (a.W >> 1) + qx * 4) * a.Cout + nt * 128), 0, 0x7fffffff, 0x00020000);
+#pragma unroll
+                    for (int jn = 0; jn < 4; jn++)
+#pragma unroll
+                        for (int pr = 0; pr < 2; pr++)      // pair 1, h = 1 is column 3: loaded but not used
+                            rv[jn][2 * pr + sl] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsR, vo_pool, pr * 2 * CoutB + jn * 128, 0));
+                }
+            }
+            return;
+        }
         const int mt = ROI ? ctile : mc;
         const int n = mt / TPP, tr = mt - n * TPP;
         const int ty = tr / TW, tx = tr - ty * TW;
@@ -686,6 +709,123 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
         WS_TL(12)
     };
 
+    // ---- POOL epilogue at quadrant granularity (QUAD).  Half wave h holds the columns of slot 2 (wave >> 2) + h, wave w the rows 2 (w & 3),
+    // 2 (w & 3) + 1 of both slots: the cross-half swap that separates a slot's two rows stays, column 8 of half 0 is another quadrant's and
+    // is not taken (pooled column 3 of every quadrant is a partial maximum), and the row exchange stays inside a slot: waves with
+    // (w & 3) > 0 publish their even row (pooled along x: 8 entries, and its column 0 per slot: 2), waves with (w & 3) < 3 take the entries
+    // of wave w + 1; pooled row 3 of every quadrant is a partial maximum.  6 publishing waves x 10 entries fit the tile form's buffer.
+    // Every quadrant writes its own strips -- row 0 pooled along x (4 pixels), column 0 pooled along y (4), its corner (1), indexed by
+    // the full-frame quadrant -- and pool_fix_add_quad_kernel finishes the 7 boundary pixels per quadrant.
+    // A half wave's values belong to ITS slot, a store takes one descriptor: two values of a half (two pooled pixels, or two channel
+    // slabs) go through one more v_permlane32_swap_b32, after which register A holds slot 0's pair (first value in the lower half wave,
+    // second in the upper) and B slot 1's.  The store count per wave is the tile form's.  The maxima are the tile form's in another
+    // grouping and the residual is added once, behind the last one: a visited pixel gets the tile form's bits.
+    auto store_tile_pool_quad = [&](int jj, float *xch) {
+        constexpr int XC = 128, XE = 10;
+        const int mc = jj / nNt, nt = jj - mc * nNt;
+        const int n0 = nt * 128;
+        const int wq = wave & 3;
+        const int xr = wave - (wave >> 2);              // exchange rows: this wave reads xr (written by wave + 1), writes xr - 1
+        float hm[4][4], vs[4];
+        constexpr float NEG = -__builtin_inff();
+        auto to_slots = [](float &A, float &B) { asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(A), "+v"(B)); };
+        auto st = [](float v, __amdgpu_buffer_rsrc_t rs, unsigned vo, int so) {
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, vo, so, 0);
+        };
+        const int nA = ctile / TPP, trA = ctile - nA * TPP, nB = ctile1 / TPP, trB = ctile1 - nB * TPP;
+        const __amdgpu_buffer_rsrc_t rsP0 = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(a.out + (((size_t)nA * (a.H >> 1) + (trA / TW) * 4 + wq) * (a.W >> 1) + (trA % TW) * 4) * a.Cout + n0), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsP1 = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(a.out + (((size_t)nB * (a.H >> 1) + (trB / TW) * 4 + wq) * (a.W >> 1) + (trB % TW) * 4) * a.Cout + n0), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsSH0 = __builtin_amdgcn_make_buffer_rsrc((void *)(a.strip_h + (size_t)ctile * 4 * a.Cout + n0), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsSH1 = __builtin_amdgcn_make_buffer_rsrc((void *)(a.strip_h + (size_t)ctile1 * 4 * a.Cout + n0), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsSV0 = __builtin_amdgcn_make_buffer_rsrc((void *)(a.strip_v + ((size_t)ctile * 4 + wq) * a.Cout + n0), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsSV1 = __builtin_amdgcn_make_buffer_rsrc((void *)(a.strip_v + ((size_t)ctile1 * 4 + wq) * a.Cout + n0), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsCO0 = __builtin_amdgcn_make_buffer_rsrc((void *)(a.corner + (size_t)ctile * a.Cout + n0), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsCO1 = __builtin_amdgcn_make_buffer_rsrc((void *)(a.corner + (size_t)ctile1 * a.Cout + n0), 0, 0x7fffffff, 0x00020000);
+        float c0 = 0.f;             // the corner value of the even channel slab, until the odd one pairs with it
+#pragma unroll
+        for (int jn = 0; jn < 4; jn++) {
+            const float sc = scv[jn], sh = shv[jn];
+            float v[16];
+            if (a.relu_out) {
+#pragma unroll
+                for (int e = 0; e < 16; e++) v[e] = fmaxf(fmaf(acc[jn][e], sc, sh), 0.f);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 16; e++) v[e] = fmaf(acc[jn][e], sc, sh);
+            }
+#pragma unroll
+            for (int e = 0; e < 16; e++) acc[jn][e] = 0.f;
+            float y0[9], m01[9];
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                float A = v[k], B = v[8 + k];
+                to_slots(A, B);                                  // (here: both rows of column 8 h + k, as in the tile form)
+                m01[k] = fmaxf(A, B);
+                y0[k] = ((h != 0) != (k >= 4)) ? B : A;
+            }
+            y0[8] = NEG;            // column 8 of the slot: another quadrant's
+            m01[8] = NEG;
+            float h0[4];
+#pragma unroll
+            for (int qq = 0; qq < 4; qq++) {
+                hm[jn][qq] = fmaxf(fmaxf(m01[2 * qq], m01[2 * qq + 1]), m01[2 * qq + 2]);
+                h0[qq] = fmaxf(fmaxf(y0[2 * qq], y0[2 * qq + 1]), y0[2 * qq + 2]);
+            }
+            vs[jn] = m01[0];
+            if (wq != 0) {
+#pragma unroll
+                for (int qq = 0; qq < 4; qq++) xch[((xr - 1) * XE + 4 * h + qq) * XC + jn * 32 + r] = h0[qq];
+                xch[((xr - 1) * XE + 8 + h) * XC + jn * 32 + r] = y0[0];
+            } else {
+                // the quadrant's row 0 and corner: its strips
+#pragma unroll
+                for (int pr = 0; pr < 2; pr++) {
+                    float A = h0[2 * pr], B = h0[2 * pr + 1];
+                    to_slots(A, B);
+                    st(A, rsSH0, vo_pool, pr * 2 * CoutB + jn * 128);
+                    st(B, rsSH1, vo_pool, pr * 2 * CoutB + jn * 128);
+                }
+                if (jn & 1) {
+                    float A = c0, B = y0[0];
+                    to_slots(A, B);
+                    st(A, rsCO0, lane * 4, (jn - 1) * 128);
+                    st(B, rsCO1, lane * 4, (jn - 1) * 128);
+                } else c0 = y0[0];
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        WS_BAR()
+        float cv0 = 0.f;
+#pragma unroll
+        for (int jn = 0; jn < 4; jn++) {
+            float pv[4];
+#pragma unroll
+            for (int qq = 0; qq < 4; qq++) {
+                pv[qq] = hm[jn][qq];
+                if (wq < 3) pv[qq] = fmaxf(pv[qq], xch[(xr * XE + 4 * h + qq) * XC + jn * 32 + r]);
+            }
+#pragma unroll
+            for (int pr = 0; pr < 2; pr++) {
+                float A = pv[2 * pr], B = pv[2 * pr + 1];
+                to_slots(A, B);                                  // pooled pixel 2 pr + h of slot 0 (A) and of slot 1 (B)
+                if (wq < 3 && (pr == 0 || h == 0)) { A = A + rv[jn][2 * pr]; B = B + rv[jn][2 * pr + 1]; }
+                st(A, rsP0, vo_pool, pr * 2 * CoutB + jn * 128);
+                st(B, rsP1, vo_pool, pr * 2 * CoutB + jn * 128);
+            }
+            float cv = vs[jn];
+            if (wq < 3) cv = fmaxf(cv, xch[(xr * XE + 8 + h) * XC + jn * 32 + r]);
+            if (jn & 1) {
+                float A = cv0, B = cv;
+                to_slots(A, B);
+                st(A, rsSV0, lane * 4, (jn - 1) * 128);
+                st(B, rsSV1, lane * 4, (jn - 1) * 128);
+            } else cv0 = cv;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // exchange values read before the step's closing barrier
+    };
+
     WS_DIAG_DECL
     WS_BAR()                                                 // step 0's operands are in LDS
     // Fragment reads.  The pointwise weights of step s + 1 are complete in LDS when the MFMA phase of step s ends (the producers
@@ -801,7 +941,8 @@ __global__ __launch_bounds__(768, 3) void sepconv_ws_kernel(WsArgs a, int nMt, i
         if (++cc == nchunks) {
             cc = 0;
             tl_s = s;
-            if (POOL) store_tile_pool(cj, smem + (stage ? WS_A : 0));
+            if constexpr (POOL && QUAD) store_tile_pool_quad(cj, smem + (stage ? WS_A : 0));
+            else if (POOL) store_tile_pool(cj, smem + (stage ? WS_A : 0));
             else store_tile(cj, smem + (stage ? WS_A1 : WS_A0) + wave * 1024);
             cj++;
             if (ROI && s + 1 < total) {
@@ -883,6 +1024,12 @@ static void launch_ws_any(const WsArgs &a, int relu_in, int prec, hipStream_t s,
             else hipLaunchKernelGGL((sepconv_ws_kernel<false, false, 0, false, true, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, tiles);
             return;
         }
+    } else {
+        if (quad && tiles && prec == 0) {
+            if (relu_in) hipLaunchKernelGGL((sepconv_ws_kernel<true, true, 0, false, true, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, tiles);
+            else hipLaunchKernelGGL((sepconv_ws_kernel<false, true, 0, false, true, true>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, tiles);
+            return;
+        }
     }
     if (prec == 1) {
         if (relu_in) hipLaunchKernelGGL((sepconv_ws_kernel<true, POOL, 1>), dim3(G), dim3(768), 0, s, a, nMt, nNt, G, RoiNone{});
@@ -958,25 +1105,28 @@ bool launch_sepconv_ws_stem(const float *x, int N, int H, int W, int Cin, const 
 // column take the missing row / column from the strips of the tile below / to the right (nothing at the patch border: TF pads
 // with -inf) and get their residual, in place.  A tile has PR x 8 pooled pixels (PR = waves per workgroup of the convolution);
 // one thread = 4 channels of one of its 8 + PR - 1 boundary pixels.
-template <bool ROI>
-__global__ __launch_bounds__(256) void pool_fix_add_kernel(float *__restrict__ out, const float *__restrict__ strip_h, const float *__restrict__ strip_v,
-                                                           const float *__restrict__ corner, const float *__restrict__ resid, int Hp, int Wp, int C,
-                                                           int c4shift, int total, int PR, std::conditional_t<ROI, RoiSegs, RoiNone> roi)
+// QUADM: behind a launch in quadrant form (sepconv_ws_kernel<.., POOL, .., QUAD>) the unit is the 8 x 8 quadrant: PR = 4 pooled rows x 4
+// pooled columns, 7 boundary pixels, the strips indexed by the full-frame quadrant; the same code with a column period of 4.
+template <bool ROI, bool QUADM>
+__device__ __forceinline__ void pool_fix_add_body(float *__restrict__ out, const float *__restrict__ strip_h, const float *__restrict__ strip_v,
+                                                  const float *__restrict__ corner, const float *__restrict__ resid, int Hp, int Wp, int C,
+                                                  int c4shift, int total, int PR, const std::conditional_t<ROI, RoiSegs, RoiNone> &roi)
 {
+    constexpr int CS = QUADM ? 2 : 3, CW = 1 << CS;         // pooled columns of a unit
     const int n = blockIdx.y;
     const int e = blockIdx.x * 256 + threadIdx.x;
     const int cq = e & ((1 << c4shift) - 1);
-    const int TH = Hp / PR, TW = Wp >> 3;
+    const int TH = Hp / PR, TW = Wp >> CS;
     // one boundary pixel: row pl, column ql of tile (ty, tx)
     auto finish = [&](int ty, int pl, int tx, int ql) {
-    const size_t o = (((size_t)n * Hp + ty * PR + pl) * Wp + tx * 8 + ql) * C + cq * 4;
+    const size_t o = (((size_t)n * Hp + ty * PR + pl) * Wp + tx * CW + ql) * C + cq * 4;
     float4 m = *reinterpret_cast<const float4 *>(out + o);
     auto take = [&](const float *src) {
         const float4 v = *reinterpret_cast<const float4 *>(src + cq * 4);
         m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
     };
-    const bool below = pl == PR - 1 && ty + 1 < TH, right = ql == 7 && tx + 1 < TW;
-    if (below) take(strip_h + ((((size_t)n * TH + ty + 1) * TW + tx) * 8 + ql) * C);
+    const bool below = pl == PR - 1 && ty + 1 < TH, right = ql == CW - 1 && tx + 1 < TW;
+    if (below) take(strip_h + ((((size_t)n * TH + ty + 1) * TW + tx) * CW + ql) * C);
     if (right) take(strip_v + ((((size_t)n * TH + ty) * TW + tx + 1) * PR + pl) * C);
     if (below && right) take(corner + (((size_t)n * TH + ty + 1) * TW + tx + 1) * C);
     const float4 rv = *reinterpret_cast<const float4 *>(resid + o);
@@ -986,10 +1136,10 @@ __global__ __launch_bounds__(256) void pool_fix_add_kernel(float *__restrict__ o
     if (!ROI) {
         if (e >= total) return;
         const int bp = e >> c4shift;                     // boundary pixel: tile * NB + k
-        const int NB = 8 + PR - 1;
+        const int NB = CW + PR - 1;
         const int tile = bp / NB, k = bp - tile * NB;
         const int ty = tile / TW, tx = tile - ty * TW;
-        finish(ty, k < 8 ? PR - 1 : k - 8, tx, k < 8 ? k : 7);
+        finish(ty, k < CW ? PR - 1 : k - CW, tx, k < CW ? k : CW - 1);
         return;
     }
     // Region form: only the boundary pixels inside the patch's box of pooled pixels (the others nobody reads), on a COMPACT grid.  The
@@ -1002,7 +1152,7 @@ __global__ __launch_bounds__(256) void pool_fix_add_kernel(float *__restrict__ o
     const bool two_r = rb.y2 != rb.y0, two_c = rb.x2 != rb.x0;
     const int nr0 = rb.y1 - rb.y0, nr = rb.rows(), nc0 = rb.x1 - rb.x0, nc = rb.cols();
     const int br0 = rb.y1 / PR - rb.y0 / PR, br = br0 + (two_r ? rb.y3 / PR - rb.y2 / PR : 0);
-    const int bc0 = (rb.x1 >> 3) - (rb.x0 >> 3), bc = bc0 + (two_c ? (rb.x3 >> 3) - (rb.x2 >> 3) : 0);
+    const int bc0 = (rb.x1 >> CS) - (rb.x0 >> CS), bc = bc0 + (two_c ? (rb.x3 >> CS) - (rb.x2 >> CS) : 0);
     const int nA = br * nc, nAB = nA + nr * bc;
     const int step = (int)(gridDim.x * 256) >> c4shift;
     for (int g = e >> c4shift; g < nAB; g += step) {
@@ -1014,55 +1164,81 @@ __global__ __launch_bounds__(256) void pool_fix_add_kernel(float *__restrict__ o
         } else {
             const int j = (g - nA) / bc, i = (g - nA) - j * bc;
             y = j < nr0 ? rb.y0 + j : rb.y2 + (j - nr0);
-            x = (i < bc0 ? (rb.x0 >> 3) + i : (rb.x2 >> 3) + (i - bc0)) * 8 + 7;
+            x = (i < bc0 ? (rb.x0 >> CS) + i : (rb.x2 >> CS) + (i - bc0)) * CW + CW - 1;
             if (y % PR == PR - 1) continue;             // in (A)
         }
-        finish(y / PR, y % PR, x >> 3, x & 7);
+        finish(y / PR, y % PR, x >> CS, x & (CW - 1));
     }
 }
 
+template <bool ROI>
+__global__ __launch_bounds__(256) void pool_fix_add_kernel(float *__restrict__ out, const float *__restrict__ strip_h, const float *__restrict__ strip_v,
+                                                           const float *__restrict__ corner, const float *__restrict__ resid, int Hp, int Wp, int C,
+                                                           int c4shift, int total, int PR, std::conditional_t<ROI, RoiSegs, RoiNone> roi)
+{
+    pool_fix_add_body<ROI, false>(out, strip_h, strip_v, corner, resid, Hp, Wp, C, c4shift, total, PR, roi);
+}
+
+template <bool ROI>
+__global__ __launch_bounds__(256) void pool_fix_add_quad_kernel(float *__restrict__ out, const float *__restrict__ strip_h, const float *__restrict__ strip_v,
+                                                                const float *__restrict__ corner, const float *__restrict__ resid, int Hp, int Wp, int C,
+                                                                int c4shift, int total, int PR, std::conditional_t<ROI, RoiSegs, RoiNone> roi)
+{
+    pool_fix_add_body<ROI, true>(out, strip_h, strip_v, corner, resid, Hp, Wp, C, c4shift, total, PR, roi);
+}
+
 // finishes the tile edges of a pooled separable convolution (tiles of 2 nw rows x 16 columns; Cout / 4 a power of two)
+// quad: the quadrant edges behind a launch in quadrant form (units of 8 rows x 8 columns)
 static void launch_pool_fix_add(float *out, const float *sh, const float *sv, const float *co, const float *resid, int N, int H, int W, int Cout, int nw,
-                         hipStream_t s, const RoiSegs *roi)
+                         hipStream_t s, const RoiSegs *roi, bool quad = false)
 {
     int c4shift = 0;
     while ((1 << c4shift) < Cout / 4) c4shift++;
-    const int total = (H / (2 * nw)) * (W / 16) * (8 + nw - 1) * (Cout / 4);
+    if (quad) nw = 4;
+    const int cs = quad ? 2 : 3;
+    const int total = (H / (2 * nw)) * (W >> (cs + 1)) * ((1 << cs) + nw - 1) * (Cout / 4);
     const dim3 grid((total + 255) / 256, N);
     if (roi) {
         const int PR = nw;
-        const auto positions = [PR](const RoiBox2 &q) {
+        const auto positions = [PR, cs](const RoiBox2 &q) {
             const long long br = q.y1 / PR - q.y0 / PR + (q.y2 != q.y0 ? q.y3 / PR - q.y2 / PR : 0);
-            const long long bc = (q.x1 >> 3) - (q.x0 >> 3) + (q.x2 != q.x0 ? (q.x3 >> 3) - (q.x2 >> 3) : 0);
+            const long long bc = (q.x1 >> cs) - (q.x0 >> cs) + (q.x2 != q.x0 ? (q.x3 >> cs) - (q.x2 >> cs) : 0);
             return br * q.cols() + bc * q.rows();
         };
-        hipLaunchKernelGGL(pool_fix_add_kernel<true>, dim3(roi_compact_blocks(*roi, H / 2, W / 2, Cout / 4, positions), N), dim3(256), 0, s, out, sh, sv, co,
-                           resid, H / 2, W / 2, Cout, c4shift, total, nw, *roi);
+        const dim3 rgrid(roi_compact_blocks(*roi, H / 2, W / 2, Cout / 4, positions), N);
+        if (quad) hipLaunchKernelGGL(pool_fix_add_quad_kernel<true>, rgrid, dim3(256), 0, s, out, sh, sv, co, resid, H / 2, W / 2, Cout, c4shift, total, nw, *roi);
+        else hipLaunchKernelGGL(pool_fix_add_kernel<true>, rgrid, dim3(256), 0, s, out, sh, sv, co, resid, H / 2, W / 2, Cout, c4shift, total, nw, *roi);
     }
+    else if (quad) hipLaunchKernelGGL(pool_fix_add_quad_kernel<false>, grid, dim3(256), 0, s, out, sh, sv, co, resid, H / 2, W / 2, Cout, c4shift, total, nw, RoiNone{});
     else hipLaunchKernelGGL(pool_fix_add_kernel<false>, grid, dim3(256), 0, s, out, sh, sv, co, resid, H / 2, W / 2, Cout, c4shift, total, nw, RoiNone{});
 }
 
 // strips of the pooled form: row 0 / column 0 of every tile, already pooled along the row / column, and its corner pixel (8 + 8 + 1 pixels per 16 x 16 tile)
-size_t sepconv_pool_scratch_floats(int N, int H, int W, int Cout)
+// quad: of every 8 x 8 quadrant (4 + 4 + 1 pixels each: 36 per 16 x 16 tile)
+size_t sepconv_pool_scratch_floats(int N, int H, int W, int Cout, bool quad)
 {
-    return (size_t)N * (H / 16) * (W / 16) * 17 * Cout;
+    return (size_t)N * (H / 16) * (W / 16) * (quad ? 36 : 17) * Cout;
 }
 
 
 bool launch_sepconv_pool_ws(const float *in, int N, int H, int W, int Cin, int relu_in, const float *dw9, const float *pwk, int Cout,
                             const float *scale, const float *shift, int relu_out, float *scratch, const float *resid, float *out, hipStream_t s, int prec,
-                            const RoiSegs *roi_fix, const int *tiles, int n_tiles)
+                            const RoiSegs *roi_fix, const int *tiles, int n_tiles, bool quad)
 {
     if (!sepconv_ws_supported(H, W, Cin, Cout) || N <= 0 || (long long)N * (H / 16) * (W / 16) * (Cout / 128) > 0x3fffffffLL ||
-        ((Cout / 4) & (Cout / 4 - 1)) || !ws_tiles_ok(tiles, n_tiles, N, H, W, prec)) {
+        ((Cout / 4) & (Cout / 4 - 1)) || !ws_tiles_ok(tiles, n_tiles, N, H, W, prec, quad) || (quad && (long long)n_tiles * (Cout / 128) > 0x3fffffffLL) ||
+        (quad && (long long)N * (H / 8) * (W / 8) > 0x7fffffffLL)) {
         set_error("launch_sepconv_pool_ws: unsupported shape");
         return false;
     }
-    const size_t ntl = (size_t)N * (H / 16) * (W / 16);
-    float *sh = scratch, *sv = sh + ntl * 8 * Cout, *co = sv + ntl * 8 * Cout;
+    // the strips: [unit][pooled pixels of its row 0][Cout], [unit][of its column 0][Cout], [unit][Cout]; a unit is a tile (8 pixels) or,
+    // in quadrant form, a quadrant (4).  `quad` reaches both launches from here, so the fix-up runs the mode of the launch in front of it
+    const size_t ntl = (size_t)N * (H / 16) * (W / 16) * (quad ? 4 : 1);
+    const int sp = quad ? 4 : 8;
+    float *sh = scratch, *sv = sh + ntl * sp * Cout, *co = sv + ntl * sp * Cout;
     WsArgs a{in, N, H, W, Cin, Cout, dw9, pwk, scale, shift, relu_out, out, resid, sh, sv, co, nullptr, nullptr, nullptr};
-    launch_ws_any<true>(a, relu_in, prec, s, tiles, n_tiles);
-    launch_pool_fix_add(out, sh, sv, co, resid, N, H, W, Cout, 8, s, roi_fix);
+    launch_ws_any<true>(a, relu_in, prec, s, tiles, n_tiles, quad);
+    launch_pool_fix_add(out, sh, sv, co, resid, N, H, W, Cout, 8, s, roi_fix, quad);
     return true;
 }
 

@@ -411,8 +411,9 @@ static bool conv(Ctx *c, ConvArgs a, hipStream_t st, const RoiSegs *roi = nullpt
 // computed whole.  Null + error set: the allocation or the copy failed.
 // From ROI_DOWN_CONST upwards every tile of the k all-constant patches behind the pass's patches follows; the forms above
 // ROI_DOWN_SHARE keep its table.
-// quad: the quadrant table of a plain fused layer (roi_plan.h:roi_sep_quad_table) where the plan has one for the form -- n packed tiles
-// of four ids, the constant patches' quadrants and the padding included, always on the device; the tile table otherwise
+// quad: the quadrant table of the layer (roi_plan.h:roi_sep_quad_table for a plain layer 6 b + 1, roi_sep_quad_pool_table for a pooled
+// layer 6 b + 3) where the plan has one for the form -- n packed tiles of four ids, the constant patches' quadrants and the padding
+// included, always on the device; the tile table otherwise
 static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, RoiDownForm form, bool quad = false)
 {
     form = roi_down_form(e->plan, std::min(form, ROI_DOWN_SHARE));
@@ -422,7 +423,7 @@ static const RoiTileTab *roi_tile_tab(RoiEntry *e, int layer, int k, RoiDownForm
     t.layer = layer; t.k = k; t.form = form;
     if (quad) {
         long long n_own = 0, n_ids = 0;
-        t.full_rep = t.full = roi_sep_quad_table(e->plan, form, layer, k, ids, &n_own, &n_ids);
+        t.full_rep = t.full = (layer % 6 == 3 ? roi_sep_quad_pool_table : roi_sep_quad_table)(e->plan, form, layer, k, ids, &n_own, &n_ids);
         if (t.full > 0) {
             t.quad = true;
             t.n = (int)(ids.size() / 4);
@@ -537,7 +538,8 @@ RoiDownForm roi_down_resolve(const Ctx *c, const RoiPlan *plan, int kimg, bool h
 // rectangle launches, bit 1 the tile tables of the fused separable layers.
 // padval: from ROI_DOWN_CONST upwards the k all-constant patches of the pass are written behind X's n patches and run through the same
 // launches as one more segment of whole patches
-int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval, RoiDownForm form, bool quad)
+int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan, const float *padval, RoiDownForm form, bool quad,
+                  bool quad_pool)
 {
     if (n <= 0) return TMAT_OK;
     if (n > c->max_patches) { set_error("unet_down_dev: n > max_patches"); return TMAT_E_ARG; }
@@ -588,8 +590,10 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
         t.full = t.n = n * (H / 16) * (H / 16);
         t.full_rep = t.n_rep = (long long)n_own * (H / 16) * (H / 16);
         if (ent && f32) {
-            // the plain layer of a level in ROI_QUAD_LEVELS: its quadrant table where the pass runs the quadrant form
-            const bool q = quad && k == 1 && form >= ROI_DOWN_SHARE && ((ROI_QUAD_LEVELS >> bi) & 1u);
+            // the plain layer of a level in ROI_QUAD_LEVELS, the pooled layer (on the fused pooling kernel) of a level in
+            // ROI_QUAD_POOL_LEVELS: its quadrant table where the pass runs that quadrant form
+            const bool q = form >= ROI_DOWN_SHARE && (k == 1 ? quad && ((ROI_QUAD_LEVELS >> bi) & 1u)
+                                                             : quad_pool && c->fused_pool && ((ROI_QUAD_POOL_LEVELS >> bi) & 1u));
             if (const RoiTileTab *made = roi_tile_tab(ent, 6 * (int)bi + k, kimg, form, q)) t = *made;
             else tab_ok = false;
         }
@@ -642,7 +646,7 @@ int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, con
             // its pixels and strips unwritten: a needed pooled pixel's 2 i .. 2 i + 2 lie in the layer's rectangle, strips included)
             if (c->fused_pool) {
                 if (!launch_sepconv_pool_ws(b2, n, H, H, d.cout, 0, d.dw[1], pw1, d.cout, d.scale[1], d.shift[1], 0, b3, b1, nxt, s, sprec, segs(bi, 5),
-                                            t1.dev, t1.n)) return TMAT_E_ARG;
+                                            t1.dev, t1.n, t1.quad)) return TMAT_E_ARG;
             } else {
                 if (!launch_sepconv_ws(b2, n, H, H, d.cout, 0, d.dw[1], pw1, d.cout, d.scale[1], d.shift[1], 0, b3, s, sprec, t1.dev, t1.n)) return TMAT_E_ARG;
                 launch_maxpool_add(b3, n, H, H, d.cout, b1, nxt, s, nullptr, segs(bi, 5));
@@ -825,7 +829,7 @@ int predict_smooth_dev(Ctx *c, float *x_dev, int n, int hh, int ww, double *pred
         launch_minmax_f32(xi, k, (size_t)hh * ww, mn, mx, c->stream);
         launch_extract_tiles(xi, mn, k, g, c->patch_in, c->stream);
         // (the constant-ring form only on request: the default launches of this entry point are pinned to the dependency plan's tiles)
-        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan, mn, roi_down_resolve(c, plan, k, true, false), roi_quad_on(c, false))
+        int rc = plan ? unet_down_dev(c, c->patch_in, k * g.tiles_per_img, c->dout[0], c->stream, plan, mn, roi_down_resolve(c, plan, k, true, false), roi_quad_on(c, false), roi_quad_pool_on(c, false))
                       : unet_forward_dev(c, c->patch_in, k * g.tiles_per_img, c->patch_out, c->stream);
         if (!rc && plan) rc = unet_up_dev(c, c->dout[0], k * g.tiles_per_img, c->patch_out, c->stream, plan);
         if (rc) return rc;
@@ -950,6 +954,10 @@ int tmat_create(int device_id, const void *weights_blob, size_t n_bytes, int max
     if (const char *e = getenv("TMAT_ROI_QUAD")) {
         if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_QUAD must be 0 or 1"); delete c; return TMAT_E_ARG; }
         c->roi_quad = atoi(e);
+    }
+    if (const char *e = getenv("TMAT_ROI_QUAD_POOL")) {
+        if (strcmp(e, "0") && strcmp(e, "1")) { set_error("tmat_create: TMAT_ROI_QUAD_POOL must be 0 or 1"); delete c; return TMAT_E_ARG; }
+        c->roi_quad_pool = atoi(e);
     }
     // room for the all-constant patches of a pass behind its patches (tmat_ctx.h): the down-path workspaces and the input buffers only
     c->const_cap = c->roi_const == 0 ? 0 : std::max(4, c->max_patches / 64);
@@ -1283,6 +1291,47 @@ int tmat_debug_sepconv_quads(tmat_handle hd, const float *x, int n, int hh, int 
                          : launch_sepconv_ws(dx, n, hh, ww, cin, relu_in != 0, dd, dw, cout, dsc, dsh, relu_out != 0, dout, s, 0, dq, (int)(n_ids / 4), true);
     if (!ok) return TMAT_E_ARG;
     mem.check(hipGetLastError(), "tmat_debug_sepconv_quads launch");
+    mem.d2h(out, dout, no * sizeof(float));
+    if (mem.finish()) return TMAT_E_HIP;
+    return TMAT_OK;
+}
+
+// Test-only (tests/test_gpu_sep_quads_pool.py): ONE pooled fused separable launch in quadrant form and the full-frame quadrant fix-up
+// behind it on host buffers with the caller's quadrant list (as tmat_debug_sepconv_quads).  x (n, hh, ww, cin); resid and out
+// (n, hh / 2, ww / 2, cout).  The caller fills out: pooled pixels of quadrants not listed that are no boundary pixels of their quadrant
+// (row or column 3 of its 4 x 4) come back as they went in; the fix-up pass rewrites every boundary pixel.
+int tmat_debug_sepconv_pool_quads(tmat_handle hd, const float *x, int n, int hh, int ww, int cin, int relu_in, const float *dw9, const float *pw, int cout,
+                                  const float *scale, const float *shift, int relu_out, const float *resid, const int *quads, int n_quads, float *out)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!c || !x || !dw9 || !pw || !scale || !shift || !resid || !quads || !out || n < 1 || n_quads < 1 || n_quads > (1 << 24) || hh < 16 || ww < 16 ||
+        cin < 1 || cout < 4 || ((cout / 4) & (cout / 4 - 1)) || !sepconv_ws_supported(hh, ww, cin, cout) ||
+        (long long)n * hh * ww * std::max(cin, cout) > 0x3fffffffLL) {
+        set_error("tmat_debug_sepconv_pool_quads: bad argument");
+        return TMAT_E_ARG;
+    }
+    const long long nq = (long long)n * (hh / 8) * (ww / 8);
+    std::vector<int> ids(quads, quads + n_quads);
+    for (int id : ids) if (id < 0 || id >= nq) { set_error("tmat_debug_sepconv_pool_quads: a quadrant id lies outside the tensor"); return TMAT_E_ARG; }
+    while (ids.size() % 4) ids.push_back(ids.back());
+    TMAT_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DevScope mem(c->ws_pool, s);
+    const size_t nx = (size_t)n * hh * ww * cin, no = (size_t)n * (hh / 2) * (ww / 2) * cout;
+    std::vector<float> wk = k_contiguous(pw, 1, cin, cout);
+    const size_t nw = wk.size();
+    const float *hw = mem.keep(std::move(wk));
+    const size_t n_ids = ids.size();
+    const int *hid = mem.keep(std::move(ids));
+    float *dx = mem.alloc_from(x, nx), *dd = mem.alloc_from(dw9, (size_t)9 * cin), *dw = mem.alloc_from(hw, nw);
+    float *dsc = mem.alloc_from(scale, cout), *dsh = mem.alloc_from(shift, cout), *dres = mem.alloc_from(resid, no);
+    float *dout = mem.alloc_from((const float *)out, no);
+    float *strips = mem.alloc<float>(sepconv_pool_scratch_floats(n, hh, ww, cout, true));
+    int *dq = mem.alloc_from(hid, n_ids);
+    if (!mem.ok) return TMAT_E_HIP;
+    if (!launch_sepconv_pool_ws(dx, n, hh, ww, cin, relu_in != 0, dd, dw, cout, dsc, dsh, relu_out != 0, strips, dres, dout, s, 0, nullptr, dq,
+                                (int)(n_ids / 4), true)) return TMAT_E_ARG;
+    mem.check(hipGetLastError(), "tmat_debug_sepconv_pool_quads launch");
     mem.d2h(out, dout, no * sizeof(float));
     if (mem.finish()) return TMAT_E_HIP;
     return TMAT_OK;

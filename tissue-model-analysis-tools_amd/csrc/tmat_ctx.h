@@ -29,8 +29,9 @@ struct ProfEv { hipEvent_t e0, e1; double flops; };
 // form: ROI_DOWN_REGION, ROI_DOWN_CONST or ROI_DOWN_SHARE (the forms above it keep its tiles).  From ROI_DOWN_CONST upwards the table is
 // followed by every tile of the pass's k all-constant patches, which sit behind its patches; n_rep of full_rep: the planner's own
 // counts, without those (what tmat_debug_sep_tiles reports)
-// quad: the quadrant table of a plain fused layer instead (roi_plan.h:roi_sep_quad_table): dev holds n packed tiles of four quadrant ids, the
-// constant patches' included; n_rep the packed tiles of the pass's own patches, full and full_rep their full-frame tiles
+// quad: the quadrant table of a fused layer instead (roi_plan.h:roi_sep_quad_table for a plain layer, roi_sep_quad_pool_table for a pooled
+// one): dev holds n packed tiles of four quadrant ids, the constant patches' included; n_rep the packed tiles of the pass's own patches,
+// full and full_rep their full-frame tiles
 struct RoiTileTab {
     int layer = 0, k = 0, n = 0; long long full = 0; int *dev = nullptr; RoiDownForm form = ROI_DOWN_REGION; long long n_rep = 0, full_rep = 0;
     bool quad = false;
@@ -280,6 +281,11 @@ struct Ctx {
     // packed tile, instead of 16 x 16 tiles (roi_plan.h:roi_sep_quad_table).  No form of its own (the rectangles, copies and the pooled
     // layers' tiles are those of the resolved form): a property of those launches where the shared-interior form or one above it runs.
     int roi_quad = -1;
+    // TMAT_ROI_QUAD_POOL, the same tri-state and independent of TMAT_ROI_QUAD: the pooled fused layers 6 b + 3 of the levels in
+    // ROI_QUAD_POOL_LEVELS visit quadrants too (roi_plan.h:roi_sep_quad_pool_table), their strips are kept per quadrant and the pooling
+    // fix-up behind them finishes the quadrant edges.  The strips live in buf[3], which holds a whole second-layer tensor per patch: 36
+    // strip pixels per 256-pixel tile (17 in the tile form) fit with room to spare, so the handle holds the same bytes under every setting.
+    int roi_quad_pool = -1;
     float *padval[2] = {nullptr, nullptr};                   // the pad values of a pipeline pass, per slot: c->scratch is rewritten by the front end of the pass after next
     std::vector<RoiEntry *> roi_cache;
     std::vector<std::pair<long long, long long>> sep_tiles;  // (planned, full) tiles of the fused separable launches of the last down pass (tmat_debug_sep_tiles)
@@ -312,9 +318,11 @@ RoiDownForm roi_down_resolve(const Ctx *c, const RoiPlan *plan, int kimg, bool h
 // gave for the pass.  padval: the pad values of the pass's images on the device, from ROI_DOWN_CONST upwards.  X then has room for
 // n + n / tiles_per_img patches (patch_in and patch_in2 do): the all-constant patches are written there
 // quad: roi_quad_on of the entry point -- from ROI_DOWN_SHARE upwards the plain fused layers take their quadrant tables
+// quad_pool: roi_quad_pool_on of the entry point -- the same for the pooled fused layers and their fix-up launches
 int unet_down_dev(Ctx *c, const float *X, int n, float *dout, hipStream_t s, const RoiPlan *plan = nullptr, const float *padval = nullptr,
-                  RoiDownForm form = ROI_DOWN_FULL, bool quad = false);
+                  RoiDownForm form = ROI_DOWN_FULL, bool quad = false, bool quad_pool = false);
 inline bool roi_quad_on(const Ctx *c, bool by_default) { return by_default ? c->roi_quad != 0 : c->roi_quad == 1; }
+inline bool roi_quad_pool_on(const Ctx *c, bool by_default) { return by_default ? c->roi_quad_pool != 0 : c->roi_quad_pool == 1; }
 // plan (nullable): region form; n is then a whole number of images' patches in the plan's class-major order
 int unet_up_dev(Ctx *c, const float *dout, int n, float *Y, hipStream_t s, const RoiPlan *plan = nullptr);
 // the region plan of g's geometry (cached on the handle) and, in g.order, its patch order; null and the image-major order when the region

@@ -155,7 +155,7 @@ struct ConvF16Args {
 };
 bool launch_conv_f16act(const ConvF16Args &a, hipStream_t s);
 // strips of the pooled separable convolution (floats): sepconv_ws_kernels.hip
-size_t sepconv_pool_scratch_floats(int N, int H, int W, int Cout);
+size_t sepconv_pool_scratch_floats(int N, int H, int W, int Cout, bool quad = false);
 // fused SeparableConv2D, wave-specialised (sepconv_ws_kernels.hip): depthwise taps dw9 [9][Cin], pointwise pwk [Cout][Cin] (k contiguous);
 // the pooled form fuses MaxPooling2D(3, 2, "same") + the residual add behind it: out (N, H/2, W/2, Cout), scratch: sepconv_pool_scratch_floats
 bool sepconv_ws_supported(int H, int W, int Cin, int Cout);
@@ -165,12 +165,14 @@ bool launch_sepconv_ws(const float *in, int N, int H, int W, int Cin, int relu_i
 bool launch_sepconv_pool_ws(const float *in, int N, int H, int W, int Cin, int relu_in, const float *dw9, const float *pwk, int Cout,
                             const float *scale, const float *shift, int relu_out, float *scratch, const float *resid, float *out, hipStream_t s, int prec = 0,
                             const RoiSegs *roi_fix = nullptr,       // roi_fix: pooled pixels the fix-up pass finishes
-                            const int *tiles = nullptr, int n_tiles = 0);
+                            const int *tiles = nullptr, int n_tiles = 0, bool quad = false);
 // tiles (nullable, prec 0 only; here, above and in the stem form): region form of the convolution itself -- a device table of the n_tiles
 // full-frame 16 x 16 tile ids (patch * tiles per patch + ty * tiles per row + tx) the launch visits (roi_plan.h:roi_sep_tile_table);
 // the other tiles' outputs and strips stay unwritten
-// quad (the two plain forms only): the table holds n_tiles PACKED tiles of four full-frame 8 x 8 quadrant ids each (patch * quadrants per
-// patch + qy * quadrants per row + qx; roi_plan.h:roi_sep_quad_table) -- any four quadrants, of any patches; the others stay unwritten
+// quad (f32 path, with tiles): the table holds n_tiles PACKED tiles of four full-frame 8 x 8 quadrant ids each (patch * quadrants per
+// patch + qy * quadrants per row + qx; roi_plan.h:roi_sep_quad_table, roi_sep_quad_pool_table) -- any four quadrants, of any patches; the
+// others stay unwritten.  The pooled form then keeps its strips per quadrant (scratch: sepconv_pool_scratch_floats(.., true)) and its
+// fix-up pass finishes the quadrant edges
 // roi (nullable, here and below): the region form -- rows of a strip outside the box are neither loaded for nor computed
 void launch_dwconv(const float *in, int N, int H, int W, int C, int relu_in, const float *Wd, float *out, hipStream_t s, const RoiSegs *roi = nullptr);
 void launch_stem(const float *x, int N, int H, int W, const float *Ws, int Cout, const float *scale,

@@ -217,7 +217,7 @@ EXPORTS = [
     "tmat_analyze_batch_grid", "tmat_analyze_batch_grid_dev", "tmat_render_barcode", "tmat_render_barcode_png", "tmat_host_barcode_rects",
     "tmat_analyze_stack_batch_dev", "tmat_canny_mask_batch", "tmat_well_small_shape", "tmat_stack_well_front_dev",
     "tmat_cell_small_dev", "tmat_cell_well_front_dev", "tmat_cell_area_fit_dev",
-    "tmat_roi_sep_quads", "tmat_debug_sepconv_quads",
+    "tmat_roi_sep_quads", "tmat_debug_sepconv_quads", "tmat_roi_sep_quads_pool", "tmat_debug_sepconv_pool_quads",
     "tmat_conv2d_narrow", "tmat_model_layers",
     "tmat_predict_smooth_ex", "tmat_smooth_plan", "tmat_spline_window", "tmat_smooth_begin", "tmat_smooth_tiles", "tmat_smooth_put",
     "tmat_smooth_end", "tmat_debug_smooth_times", "tmat_resize_pil_f32", "tmat_host_resize_pil_f32", "tmat_predict_auto_resample",
@@ -700,6 +700,24 @@ class Handle:
               "tmat_debug_sepconv_quads")
         return out
 
+    def debug_sepconv_pool_quads(self, x, dw9, pw, scale, shift, resid, quads, out, relu_in=False, relu_out=False):
+        """test-only (include/tmat.h:tmat_debug_sepconv_pool_quads): one pooled fused separable launch in quadrant form and its fix-up.
+        x (n, h, w, cin); dw9 [9][cin]; pw (cin, cout) in the Keras layout; resid and out (n, h / 2, w / 2, cout) float32; quads: full-frame
+        quadrant ids; out is caller-filled, changed in place and returned."""
+        x, dw9, pw, resid = (np.ascontiguousarray(a, np.float32) for a in (x, dw9, pw, resid))
+        scale, shift = np.ascontiguousarray(scale, np.float32), np.ascontiguousarray(shift, np.float32)
+        q = np.ascontiguousarray(quads, np.int32).ravel()
+        cin, cout = pw.shape
+        n, hh, ww = x.shape[:3]
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (n, hh // 2, ww // 2, cout) and dw9.shape == (9, cin)
+        assert x.shape == (n, hh, ww, cin) and resid.shape == out.shape
+        L = lib()
+        vp, i = C.c_void_p, C.c_int
+        L.tmat_debug_sepconv_pool_quads.argtypes = [vp, vp, i, i, i, i, i, vp, vp, i, vp, vp, i, vp, vp, i, vp]
+        check(L.tmat_debug_sepconv_pool_quads(self._h, ptr(x), n, hh, ww, cin, int(bool(relu_in)), ptr(dw9), ptr(pw), cout, ptr(scale), ptr(shift),
+                                              int(bool(relu_out)), ptr(resid), ptr(q), len(q), ptr(out)), "tmat_debug_sepconv_pool_quads")
+        return out
+
     def debug_down_segs(self):
         """test-only: the longest segment table among the rectangle launches of the last down pass (include/tmat.h:tmat_debug_down_segs)"""
         n = C.c_int()
@@ -1122,6 +1140,21 @@ def roi_sep_quads(hh, ww, layer, k, form="share", patch=320, channels=(512, 512,
     check(L.tmat_roi_sep_quads(*args, 0, ptr(counts), None), "roi_sep_quads")
     ids = np.zeros(max(int(counts[0]), 1), np.int32)
     check(L.tmat_roi_sep_quads(*args, len(ids), ptr(counts), ptr(ids)), "roi_sep_quads")
+    return ids[:int(counts[0])], int(counts[1]), int(counts[2]), int(counts[3])
+
+
+def roi_sep_quads_pool(hh, ww, layer, k, form="share", patch=320, channels=(512, 512, 256, 128, 64), down_channels=(64, 128, 256, 512), fused_mask=3):
+    """tmat_roi_sep_quads_pool (include/tmat.h): roi_sep_quads for the pooled fused layer `layer` (6 b + 3); the same return values."""
+    L = lib()
+    L.tmat_roi_sep_quads_pool.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint] + [C.c_int] * 4 + [C.c_void_p] * 2
+    n_up, n_down = len(channels) - 1, len(down_channels) - 1
+    ch, dch = np.asarray(channels, np.int32), np.asarray(down_channels, np.int32)
+    f = ROI_DOWN_FORMS.index(form) if isinstance(form, str) else int(form)
+    counts = np.zeros(4, np.int32)
+    args = (hh, ww, patch, n_up, ptr(ch), n_down, ptr(dch), int(fused_mask), f, int(layer), int(k))
+    check(L.tmat_roi_sep_quads_pool(*args, 0, ptr(counts), None), "roi_sep_quads_pool")
+    ids = np.zeros(max(int(counts[0]), 1), np.int32)
+    check(L.tmat_roi_sep_quads_pool(*args, len(ids), ptr(counts), ptr(ids)), "roi_sep_quads_pool")
     return ids[:int(counts[0])], int(counts[1]), int(counts[2]), int(counts[3])
 
 
