@@ -432,6 +432,34 @@ int tmat_host_png_encode_batch(const uint8_t *pics, int n, int H, int W, int cha
 int tmat_render_tree_png(tmat_handle h, const void *background, int bg_dtype, int n, int bh, int bw, const double *segs,
                          const int32_t *seg_branch, const int32_t *seg_offsets, int vis_width, uint8_t *out, size_t cap_each, size_t *sizes);
 
+/*
+ * The encoder's two modes.  TMAT_PNG_FAST (the default) is the encoder described above.  TMAT_PNG_COMPACT (opt-in) keeps the filter,
+ * the stripes, the match rule and tmat_png_bound and changes the parse and the blocks: a match gives way to a literal when the match at
+ * the next position is longer (one-step lazy), and every stripe becomes a stored, a fixed-Huffman or a dynamic-Huffman block
+ * (RFC 1951 3.2.7: code lengths from the stripe's own histograms, limited to 15 bits, header trimmed and run-length coded), whichever
+ * is the fewest bytes by exact count, the earlier of the three on a tie.  A compact file is again a function of the picture and
+ * (H, W, channels) alone, and the device and the host twin produce the same bytes.
+ * tmat_png_set_mode: a property of the handle, like tmat_set_precision.  It applies to the calls that follow and covers every entry
+ * point that encodes -- tmat_png_encode_batch, _dev and _timed, tmat_render_tree_png, tmat_render_barcode_png and the tree_png /
+ * barcode_png outputs of tmat_analyze_batch_grid*.  A handle from tmat_create_plain is enough.  Any other mode: TMAT_E_ARG, the handle
+ * keeps its mode.
+ * tmat_host_png_encode_batch_mode: the host twin with the mode as an argument (tmat_host_png_encode_batch is its TMAT_PNG_FAST); a
+ * mode outside the two: TMAT_E_ARG, nothing written.
+ * tmat_host_png_code_lengths (test entry): the code lengths both implementations derive from a histogram freq[0, n): len[i] = 0
+ * exactly where freq[i] = 0, no length above limit, Kraft sum exactly 1, and the optimal total cost wherever the Huffman tree is no
+ * deeper than limit.  A histogram with ONE used symbol gets the one-bit code (Kraft sum 1/2: no complete set has one member; the
+ * encoder never asks for it).  1 <= n <= 286, 1 <= limit <= 15, 2^limit >= n, sum of the frequencies below 2^22; else TMAT_E_ARG.
+ * tmat_debug_png_code_lengths: the same function on the device for k histograms (freqs (k, n) u32, lens (k, n) u8, host pointers) in
+ * one launch, one lane each; the same argument rules for every histogram; k == 0 succeeds.
+ */
+#define TMAT_PNG_FAST 0
+#define TMAT_PNG_COMPACT 1
+int tmat_png_set_mode(tmat_handle h, int mode);
+int tmat_host_png_encode_batch_mode(const uint8_t *pics, int n, int H, int W, int channels, uint8_t *out, size_t cap_each, size_t *sizes,
+                                    int mode);
+int tmat_host_png_code_lengths(const uint32_t *freq, int n, int limit, uint8_t *len);
+int tmat_debug_png_code_lengths(tmat_handle h, const uint32_t *freqs, int k, int n, int limit, uint8_t *lens);
+
 /* One result row per image, the payload gathered across ranks. */
 typedef struct tmat_row {
     int64_t index;   /* image index in the run                      */

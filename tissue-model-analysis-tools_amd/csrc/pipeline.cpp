@@ -268,7 +268,7 @@ struct TreeJob {
     uint8_t *tree_png; size_t tree_png_cap; size_t *tree_png_sizes; PngShape pg_tree;
     uint8_t *barcode_png; size_t barcode_png_cap; size_t *barcode_png_sizes; PngShape pg_bar;
     int S; BarRect *drect; int *drect_off; uint8_t *dbar;
-    uint8_t *png_filt, *png_slots, *png_files; uint32_t *png_meta, *png_dsz;
+    uint8_t *png_filt, *png_slots, *png_files; uint32_t *png_meta, *png_dsz; int png_mode;
 };
 
 // The pairs of a call: tmat_analyze_batch_grid* sweeps T (graph_thresh_1, graph_thresh_2) pairs from ONE pass of the network; every
@@ -288,7 +288,7 @@ static int png_encode_job(const TreeJob &tj, const uint8_t *pics_dev, int k, con
     std::vector<uint32_t> hsz(Kp);
     for (int i0 = 0; i0 < k; i0 += Kp) {
         const int kk = std::min(Kp, k - i0);
-        if (png_encode_launch(pics_dev + (size_t)i0 * pic_bytes, kk, g, tj.png_filt, tj.png_slots, tj.png_meta, tj.png_files, fcap, tj.png_dsz, s)) {
+        if (png_encode_launch(pics_dev + (size_t)i0 * pic_bytes, kk, g, tj.png_mode, tj.png_filt, tj.png_slots, tj.png_meta, tj.png_files, fcap, tj.png_dsz, s)) {
             set_error("analyze (grid): png encoder launch failed");
             return TMAT_E_HIP;
         }
@@ -508,6 +508,7 @@ static int tree_setup(Ctx *c, const AnalyzeCall &call, int h, int w, int K, cons
         if (!tj.drect || !tj.dbar) return TMAT_E_HIP;
         tj.drect_off = (int *)(tj.drect + (size_t)K * (size_t)call.cap_b);       // BarRect is five words: word-aligned
     }
+    tj.png_mode = c->png_mode;
     if (tj.tree_png || tj.barcode_png) {        // encoder scratch (png.h:png_encode_launch) for the larger of the two shapes
         size_t filt = 0, slots = 0, files = 0, meta_words = 0, kp_max = 0;
         for (const PngShape *pg : {tj.tree_png ? &tj.pg_tree : nullptr, tj.barcode_png ? &tj.pg_bar : nullptr}) {

@@ -63,8 +63,8 @@ struct BitWriter {
     void align() { bit = (bit + 7) & ~(size_t)7; }
 };
 
-// the deflate data of the stripe s[0, n) into dst[0, cap); returns its length
-size_t deflate_stripe(const uint8_t *s, int n, bool last, int ch, int rowlen, uint8_t *dst, size_t cap, std::vector<uint32_t> &m)
+// the deflate data of the stripe s[0, n) into dst[0, cap) in the given mode; returns its length
+size_t deflate_stripe(const uint8_t *s, int n, bool last, int ch, int rowlen, int mode, uint8_t *dst, size_t cap, std::vector<uint32_t> &m)
 {
     std::vector<uint32_t> table((size_t)1 << PNG_HASH_BITS, 0);
     int cand[PNG_SUB];
@@ -75,28 +75,63 @@ size_t deflate_stripe(const uint8_t *s, int n, bool last, int ch, int rowlen, ui
             if (p + 2 < n) { uint32_t &t = table[png_hash3(s + p)]; t = std::max(t, (uint32_t)p + 1); }
         for (int p = c0; p < e; p++) m[p] = png_best_match(s, n, p, cand[p - c0], ch, rowlen);
     }
-    uint32_t tok_bits = 0;
+    const bool compact = mode == PNG_COMPACT;
+    uint32_t tok_bits = 0, extra_bits = 0, llf[PNG_NLL] = {0}, df[PNG_ND] = {0};
     for (int p = 0; p < n;) {
         int bits;
-        const int len = (int)(m[p] & 0xffff);
-        png_token(len, (int)(m[p] >> 16), s[p], bits);
+        const int len = png_take(m.data(), n, p, compact), dist = (int)(m[p] >> 16);
+        png_token(len, dist, s[p], bits);
         tok_bits += (uint32_t)bits;
+        if (compact) {
+            if (len == 0) llf[s[p]]++;
+            else {
+                int code, ext, val;
+                png_len_sym(len, code, ext, val);
+                llf[257 + code]++; extra_bits += (uint32_t)ext;
+                png_dist_sym(dist, code, ext, val);
+                df[code]++; extra_bits += (uint32_t)ext;
+            }
+        }
         p += len ? len : 1;
     }
     const uint32_t fixed = png_fixed_bytes(tok_bits, last), stored = png_stored_bytes(n);
-    if (fixed < stored && fixed <= cap) {
-        BitWriter w(dst, fixed);
-        w.put((last ? 1u : 0u) | 2u, 3);
+    int kind = fixed < stored ? 1 : 0;              // 0 stored, 1 fixed, 2 dynamic
+    uint32_t bytes = kind ? fixed : stored;
+    PngDyn D;
+    uint32_t ws[PNG_WS_WORDS], llc[PNG_NLL], dc[PNG_ND], clc[PNG_NCL];
+    if (compact) {
+        llf[256]++;
+        png_dyn_plan(llf, df, extra_bits, D, ws);
+        const uint32_t dyn = png_block_bytes(D.bits, last);
+        if (dyn < bytes) { kind = 2; bytes = dyn; }
+    }
+    if (kind && bytes <= cap) {
+        BitWriter w(dst, bytes);
+        if (kind == 1) w.put((last ? 1u : 0u) | 2u, 3);
+        else {
+            png_canonical(D.ll_len, PNG_NLL, llc, ws);
+            png_canonical(D.d_len, PNG_ND, dc, ws);
+            png_canonical(D.cl_len, PNG_NCL, clc, ws);
+            png_dyn_header(D, clc, last, [&](uint32_t v, int bits) { w.put(v, bits); });
+        }
         for (int p = 0; p < n;) {
-            int bits;
-            const int len = (int)(m[p] & 0xffff);
-            const uint32_t v = png_token(len, (int)(m[p] >> 16), s[p], bits);
-            w.put(v, bits);
+            const int len = png_take(m.data(), n, p, compact), dist = (int)(m[p] >> 16);
+            if (kind == 1) {
+                int bits;
+                const uint32_t v = png_token(len, dist, s[p], bits);
+                w.put(v, bits);
+            } else {
+                uint32_t v1, v2;
+                int b1, b2;
+                png_dyn_token(llc, dc, len, dist, s[p], v1, b1, v2, b2);
+                w.put(v1, b1);
+                w.put(v2, b2);
+            }
             p += len ? len : 1;
         }
-        w.put(0, 7);
+        if (kind == 1) w.put(0, 7); else w.put(llc[256] & 0xffffu, (int)(llc[256] >> 16));
         if (!last) { w.put(0, 3); w.align(); w.put(0xffff0000u, 32); }
-        if (w.ok) return fixed;
+        if (w.ok) return bytes;
     }
     dst[0] = last ? 1 : 0;
     dst[1] = (uint8_t)n; dst[2] = (uint8_t)(n >> 8);
@@ -107,7 +142,7 @@ size_t deflate_stripe(const uint8_t *s, int n, bool last, int ch, int rowlen, ui
 
 }  // namespace
 
-void png_encode_host(const uint8_t *pic, const PngShape &g, uint8_t *out, size_t *size)
+void png_encode_host(const uint8_t *pic, const PngShape &g, int mode, uint8_t *out, size_t *size)
 {
     std::vector<uint8_t> filt(g.raw);
     filter_rows(pic, g, filt.data());
@@ -128,7 +163,7 @@ void png_encode_host(const uint8_t *pic, const PngShape &g, uint8_t *out, size_t
         const uint8_t *s = filt.data() + b0;
         const int pre = k == 0 ? 2 : 0;
         if (pre) { slot[8] = 0x78; slot[9] = 0x01; }
-        const size_t dl = deflate_stripe(s, n, k == g.ns - 1, g.ch, g.rb + 1, slot + 8 + pre, PNG_SLOT - 12 - pre, m);
+        const size_t dl = deflate_stripe(s, n, k == g.ns - 1, g.ch, g.rb + 1, mode, slot + 8 + pre, PNG_SLOT - 12 - pre, m);
         const size_t total = close_chunk(slot, "IDAT", pre + dl);
         std::memcpy(o, slot, total);
         o += total;

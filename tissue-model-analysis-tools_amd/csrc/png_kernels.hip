@@ -2,7 +2,7 @@
 // waits for another, every loop is bounded by the stripe length:
 //   png_filter_kernel   one wave per row: the five residual sums, the choice, the filtered row
 //   png_stripe_kernel   one workgroup per stripe: matches, greedy parse, bits packed in LDS, the chunk's CRC, Adler-32 partial sums;
-//                       the finished IDAT chunk goes to the stripe's worst-case slot
+//                       the finished IDAT chunk goes to the stripe's worst-case slot.  <true>: PNG_COMPACT (lazy parse, dynamic blocks)
 //   png_layout_kernel   one workgroup per picture: prefix sum of the chunk sizes, Adler-32 combined, signature / IHDR / trailer written
 //   png_gather_kernel   one workgroup per stripe: slot -> its place in the contiguous file
 #include "png.h"
@@ -70,17 +70,24 @@ __device__ __forceinline__ bool put_bits(uint32_t *w, int cap_words, uint32_t po
 }
 
 // meta per stripe: {chunk bytes, Adler sum of bytes mod 65521, Adler weighted sum mod 65521, offset in the file (png_layout_kernel)}
+// COMPACT (PNG_COMPACT): the lazy parse, histograms by LDS atomics over the first walk, one lane builds the code lengths and tables with
+// the host's own functions (png_dyn_plan, png_canonical; its scratch is the union region, free between the parse and the zeroing of the
+// chunk), a second walk counts the dynamic block's bits per thread, the third emits.  A template parameter: the fast kernel holds none of it
+template <bool COMPACT>
 __global__ __launch_bounds__(NT) void png_stripe_kernel(const uint8_t *__restrict__ filt, size_t raw, int ns, int ch, int rowlen,
                                                          uint8_t *__restrict__ slots, uint32_t *__restrict__ meta)
 {
     __shared__ uint8_t s_data[PNG_STRIPE];
     __shared__ uint32_t s_m[PNG_STRIPE];
-    __shared__ uint32_t s_u[PNG_STRIPE / 2];     // in turn: the hash table, the parse's exit positions (u16), the chunk being built
+    __shared__ uint32_t s_u[PNG_STRIPE / 2];     // in turn: the hash table, the parse's exit positions (u16), [compact: scratch], the chunk being built
     __shared__ uint16_t s_entry[NT];
     __shared__ uint32_t s_red[12];
     __shared__ int s_bad;
+    __shared__ uint32_t s_ll[COMPACT ? PNG_NLL : 1], s_d[COMPACT ? PNG_ND : 1], s_cl[COMPACT ? PNG_NCL : 1];     // histograms, then code tables
+    __shared__ PngDyn s_dyn;
     uint16_t *s_exit = (uint16_t *)s_u;
     uint8_t *s_out = (uint8_t *)s_u;
+    static_assert(PNG_WS_WORDS <= PNG_STRIPE / 2, "the union buffer holds the scratch of the code lengths");
 
     const int t = threadIdx.x, k = blockIdx.x, pic = blockIdx.y, lane = t & 63, wv = t >> 6;
     const size_t b0 = (size_t)k * PNG_STRIPE;
@@ -92,6 +99,10 @@ __global__ __launch_bounds__(NT) void png_stripe_kernel(const uint8_t *__restric
     for (int j = t; j < (1 << PNG_HASH_BITS); j += NT) s_u[j] = 0;
     s_entry[t] = 0xffff;
     if (t == 0) s_bad = 0;
+    if constexpr (COMPACT) {
+        for (int j = t; j < PNG_NLL; j += NT) s_ll[j] = 0;
+        if (t < PNG_ND) s_d[t] = 0;
+    }
     __syncthreads();
 
     // Adler-32 partial sums over this thread's SEG bytes (at most 32 * 8192 * 255 per thread)
@@ -111,11 +122,11 @@ __global__ __launch_bounds__(NT) void png_stripe_kernel(const uint8_t *__restric
         __syncthreads();
     }
 
-    // greedy parse: per thread the exit of every position of its segment, one lane hops over the segments, then every segment is
-    // walked from its entry
+    // the parse (greedy, or lazy when compact): per thread the exit of every position of its segment, one lane hops over the segments,
+    // then every segment is walked from its entry
     const int seg0 = t * SEG, seg1 = min(n, seg0 + SEG);
     for (int p = seg1 - 1; p >= seg0; p--) {
-        const int len = (int)(s_m[p] & 0xffff);
+        const int len = png_take(s_m, n, p, COMPACT);
         const int nx = p + (len ? len : 1);
         s_exit[p] = (uint16_t)(nx >= seg1 ? nx : s_exit[nx]);
     }
@@ -126,53 +137,119 @@ __global__ __launch_bounds__(NT) void png_stripe_kernel(const uint8_t *__restric
     }
     __syncthreads();
     const int entry = s_entry[t];
-    uint32_t my_bits = 0;
+    uint32_t my_bits = 0, my_extra = 0;
     if (entry != 0xffff)
         for (int p = entry; p < seg1;) {
             int bits;
             const uint32_t mm = s_m[p];
-            const int len = (int)(mm & 0xffff);
+            const int len = png_take(s_m, n, p, COMPACT);
             png_token(len, (int)(mm >> 16), s_data[p], bits);
             my_bits += (uint32_t)bits;
+            if constexpr (COMPACT) {
+                if (len == 0) atomicAdd(&s_ll[s_data[p]], 1u);
+                else {
+                    int code, ext, val;
+                    png_len_sym(len, code, ext, val);
+                    atomicAdd(&s_ll[257 + code], 1u); my_extra += (uint32_t)ext;
+                    png_dist_sym((int)(mm >> 16), code, ext, val);
+                    atomicAdd(&s_d[code], 1u); my_extra += (uint32_t)ext;
+                }
+            }
             p += len ? len : 1;
         }
     // exclusive prefix sum of my_bits over the workgroup
     uint32_t incl = my_bits;
     for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
     if (lane == 63) s_red[wv] = incl;
-    for (int j = t; j < OUT_WORDS; j += NT) s_u[j] = 0;          // the exits are dead: the region becomes the zeroed chunk
+    if constexpr (COMPACT) {
+        my_extra = wave_sum(my_extra);
+        if (lane == 0) s_red[4 + wv] = my_extra;
+    } else {
+        for (int j = t; j < OUT_WORDS; j += NT) s_u[j] = 0;      // the exits are dead: the region becomes the zeroed chunk
+    }
     __syncthreads();
     uint32_t base_bits = 0, tok_bits = 0;
     for (int w = 0; w < 4; w++) { if (w < wv) base_bits += s_red[w]; tok_bits += s_red[w]; }
-    const uint32_t excl = base_bits + incl - my_bits;
+    uint32_t excl = base_bits + incl - my_bits;
 
     const int pre = k == 0 ? 2 : 0;
     const uint32_t fixed = png_fixed_bytes(tok_bits, last), stored = png_stored_bytes(n);
-    const bool use_fixed = fixed < stored && 12u + pre + fixed <= (uint32_t)PNG_SLOT;
-    if (use_fixed) {
-        uint32_t pos = (8 + pre) * 8 + 3 + excl;
+    int kind = fixed < stored ? 1 : 0;               // 0 stored, 1 fixed, 2 dynamic
+    uint32_t bytes = kind ? fixed : stored;
+    uint32_t dyn_tok = 0;                            // bits of the dynamic block's tokens
+    if constexpr (COMPACT) {
+        if (t == 0) {                                // the exits are dead: the region is this lane's scratch
+            s_ll[256] += 1;
+            png_dyn_plan(s_ll, s_d, s_red[4] + s_red[5] + s_red[6] + s_red[7], s_dyn, s_u);
+            png_canonical(s_dyn.ll_len, PNG_NLL, s_ll, s_u);
+            png_canonical(s_dyn.d_len, PNG_ND, s_d, s_u);
+            png_canonical(s_dyn.cl_len, PNG_NCL, s_cl, s_u);
+        }
+        __syncthreads();
+        const uint32_t dyn = png_block_bytes(s_dyn.bits, last);
+        if (dyn < bytes) { kind = 2; bytes = dyn; }
+        for (int j = t; j < OUT_WORDS; j += NT) s_u[j] = 0;      // the scratch is dead: the region becomes the zeroed chunk
+        if (kind == 2) {                             // the whole workgroup or none of it: the choice is made from shared values
+            my_bits = 0;
+            if (entry != 0xffff)
+                for (int p = entry; p < seg1;) {
+                    uint32_t v1, v2;
+                    int b1, b2;
+                    const int len = png_take(s_m, n, p, true);
+                    png_dyn_token(s_ll, s_d, len, (int)(s_m[p] >> 16), s_data[p], v1, b1, v2, b2);
+                    my_bits += (uint32_t)(b1 + b2);
+                    p += len ? len : 1;
+                }
+            incl = my_bits;
+            for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
+            if (lane == 63) s_red[wv] = incl;        // every thread has read the fixed block's sums before the barrier above
+        }
+        __syncthreads();
+        if (kind == 2) {
+            base_bits = 0;
+            for (int w = 0; w < 4; w++) { if (w < wv) base_bits += s_red[w]; dyn_tok += s_red[w]; }
+            excl = base_bits + incl - my_bits;
+        }
+    }
+    const bool use_block = kind != 0 && 12u + pre + bytes <= (uint32_t)PNG_SLOT;
+    if (use_block) {
+        uint32_t pos = (8 + pre) * 8 + (COMPACT && kind == 2 ? s_dyn.hdr : 3u) + excl;
         bool ok = true;
         if (entry != 0xffff)
             for (int p = entry; p < seg1;) {
-                int bits;
                 const uint32_t mm = s_m[p];
-                const int len = (int)(mm & 0xffff);
-                const uint32_t v = png_token(len, (int)(mm >> 16), s_data[p], bits);
-                ok = put_bits(s_u, OUT_WORDS, pos, v, bits) && ok;
-                pos += bits;
+                const int len = png_take(s_m, n, p, COMPACT);
+                if (!COMPACT || kind == 1) {
+                    int bits;
+                    const uint32_t v = png_token(len, (int)(mm >> 16), s_data[p], bits);
+                    ok = put_bits(s_u, OUT_WORDS, pos, v, bits) && ok;
+                    pos += bits;
+                } else {                             // up to 48 bits: the literal or length, then the distance
+                    uint32_t v1, v2;
+                    int b1, b2;
+                    png_dyn_token(s_ll, s_d, len, (int)(mm >> 16), s_data[p], v1, b1, v2, b2);
+                    ok = put_bits(s_u, OUT_WORDS, pos, v1, b1) && ok;
+                    ok = put_bits(s_u, OUT_WORDS, pos + b1, v2, b2) && ok;
+                    pos += b1 + b2;
+                }
                 p += len ? len : 1;
             }
         if (t == 0) {
-            ok = put_bits(s_u, OUT_WORDS, (8 + pre) * 8, (last ? 1u : 0u) | 2u, 3) && ok;
-            if (!last) ok = put_bits(s_u, OUT_WORDS, (8 + pre + fixed - 4) * 8, 0xffff0000u, 32) && ok;
+            if (!COMPACT || kind == 1) ok = put_bits(s_u, OUT_WORDS, (8 + pre) * 8, (last ? 1u : 0u) | 2u, 3) && ok;
+            else {
+                uint32_t hp = (8 + pre) * 8;
+                png_dyn_header(s_dyn, s_cl, last, [&](uint32_t v, int bits) { ok = put_bits(s_u, OUT_WORDS, hp, v, bits) && ok; hp += bits; });
+                ok = put_bits(s_u, OUT_WORDS, (8 + pre) * 8 + s_dyn.hdr + dyn_tok, s_ll[256] & 0xffffu, (int)(s_ll[256] >> 16)) && ok;
+            }
+            if (!last) ok = put_bits(s_u, OUT_WORDS, (8 + pre + bytes - 4) * 8, 0xffff0000u, 32) && ok;
         }
         if (!ok) s_bad = 1;
     }
     __syncthreads();
-    const bool fixed_done = use_fixed && !s_bad;     // a write refused by the capacity check: the stripe is stored instead
+    const bool block_done = use_block && !s_bad;     // a write refused by the capacity check: the stripe is stored instead
     __syncthreads();
-    if (!fixed_done) {
-        if (use_fixed) {                             // clear what the refused attempt left
+    if (!block_done) {
+        if (use_block) {                             // clear what the refused attempt left
             for (int j = t; j < OUT_WORDS; j += NT) s_u[j] = 0;
             __syncthreads();
         }
@@ -184,7 +261,7 @@ __global__ __launch_bounds__(NT) void png_stripe_kernel(const uint8_t *__restric
         }
         for (int j = t; j < n; j += NT) d[5 + j] = s_data[j];
     }
-    const uint32_t dlen = pre + (fixed_done ? fixed : stored);
+    const uint32_t dlen = pre + (block_done ? bytes : stored);
     if (t == 0) {
         s_out[0] = (uint8_t)(dlen >> 24); s_out[1] = (uint8_t)(dlen >> 16); s_out[2] = (uint8_t)(dlen >> 8); s_out[3] = (uint8_t)dlen;
         s_out[4] = 'I'; s_out[5] = 'D'; s_out[6] = 'A'; s_out[7] = 'T';
@@ -294,16 +371,33 @@ __global__ __launch_bounds__(256) void png_gather_kernel(const uint8_t *__restri
     for (uint32_t j = threadIdx.x; j < bytes; j += 256) dst[j] = src[j];
 }
 
+// tmat_debug_png_code_lengths: histogram i of n symbols -> its code lengths, one lane each (the scratch is private memory here)
+__global__ __launch_bounds__(64) void png_code_lengths_kernel(const uint32_t *__restrict__ freqs, int k, int n, int limit, uint8_t *__restrict__ lens)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < k) png_code_lengths(freqs + (size_t)i * n, n, limit, lens + (size_t)i * n);
+}
+
 }  // namespace
 
-int png_encode_launch(const uint8_t *pics, int k, const PngShape &g, uint8_t *filt, uint8_t *slots, uint32_t *meta, uint8_t *files, size_t fcap,
+int png_code_lengths_launch(const uint32_t *freqs, int k, int n, int limit, uint8_t *lens, hipStream_t s)
+{
+    if (k < 1 || n < 1 || n > PNG_NLL || limit < 1 || limit > 15 || (1 << limit) < n) return -1;
+    hipLaunchKernelGGL(png_code_lengths_kernel, dim3((k + 63) / 64), dim3(64), 0, s, freqs, k, n, limit, lens);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int png_encode_launch(const uint8_t *pics, int k, const PngShape &g, int mode, uint8_t *filt, uint8_t *slots, uint32_t *meta, uint8_t *files, size_t fcap,
                       uint32_t *file_size, hipStream_t s)
 {
-    if (k < 1 || k > 65535 || fcap < g.bound) return -1;
+    if (k < 1 || k > 65535 || fcap < g.bound || (mode != PNG_FAST && mode != PNG_COMPACT)) return -1;
     const long long rows = (long long)k * g.H;
     if ((rows + 3) / 4 > 0x7fffffffLL) return -1;
     hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, pics, rows, g.H, g.rb, g.ch, filt);
-    hipLaunchKernelGGL(png_stripe_kernel, dim3(g.ns, k), dim3(NT), 0, s, (const uint8_t *)filt, g.raw, g.ns, g.ch, g.rb + 1, slots, meta);
+    if (mode == PNG_COMPACT)
+        hipLaunchKernelGGL(png_stripe_kernel<true>, dim3(g.ns, k), dim3(NT), 0, s, (const uint8_t *)filt, g.raw, g.ns, g.ch, g.rb + 1, slots, meta);
+    else
+        hipLaunchKernelGGL(png_stripe_kernel<false>, dim3(g.ns, k), dim3(NT), 0, s, (const uint8_t *)filt, g.raw, g.ns, g.ch, g.rb + 1, slots, meta);
     hipLaunchKernelGGL(png_layout_kernel, dim3(k), dim3(256), 0, s, meta, g.ns, g.raw, g.H, g.W, g.ch, files, fcap, file_size);
     hipLaunchKernelGGL(png_gather_kernel, dim3(g.ns, k), dim3(256), 0, s, (const uint8_t *)slots, (const uint32_t *)meta, g.ns, files, fcap);
     return hipGetLastError() == hipSuccess ? 0 : 1;

@@ -1492,8 +1492,64 @@ int tmat_host_png_encode_batch(const uint8_t *pics, int n, int H, int W, int cha
 {
     PngShape g;
     if (int rc = png_args("tmat_host_png_encode_batch", pics, n, H, W, channels, out, cap_each, sizes, g)) return rc;
-    for (int i = 0; i < n; i++) png_encode_host(pics + (size_t)i * H * g.rb, g, out + (size_t)i * cap_each, &sizes[i]);
+    for (int i = 0; i < n; i++) png_encode_host(pics + (size_t)i * H * g.rb, g, PNG_FAST, out + (size_t)i * cap_each, &sizes[i]);
     return TMAT_OK;
+}
+
+int tmat_host_png_encode_batch_mode(const uint8_t *pics, int n, int H, int W, int channels, uint8_t *out, size_t cap_each, size_t *sizes, int mode)
+{
+    PngShape g;
+    if (mode != TMAT_PNG_FAST && mode != TMAT_PNG_COMPACT) { set_error("tmat_host_png_encode_batch_mode: mode must be TMAT_PNG_FAST or TMAT_PNG_COMPACT"); return TMAT_E_ARG; }
+    if (int rc = png_args("tmat_host_png_encode_batch_mode", pics, n, H, W, channels, out, cap_each, sizes, g)) return rc;
+    for (int i = 0; i < n; i++) png_encode_host(pics + (size_t)i * H * g.rb, g, mode, out + (size_t)i * cap_each, &sizes[i]);
+    return TMAT_OK;
+}
+
+int tmat_png_set_mode(tmat_handle h, int mode)
+{
+    Ctx *c = (Ctx *)h;
+    if (!c || (mode != TMAT_PNG_FAST && mode != TMAT_PNG_COMPACT)) { set_error("tmat_png_set_mode: needs a handle and mode TMAT_PNG_FAST or TMAT_PNG_COMPACT"); return TMAT_E_ARG; }
+    c->png_mode = mode;
+    return TMAT_OK;
+}
+
+// the contract of png_code_lengths (png.h)
+static bool png_code_lengths_args(const uint32_t *freq, size_t k, int n, int limit, const uint8_t *len)
+{
+    if (!freq || !len || n < 1 || n > PNG_NLL || limit < 1 || limit > 15 || (1 << limit) < n) return false;
+    for (size_t i = 0; i < k; i++) {
+        uint64_t sum = 0;
+        for (int j = 0; j < n; j++) sum += freq[i * n + j];
+        if (sum >= (1u << 22)) return false;
+    }
+    return true;
+}
+
+int tmat_host_png_code_lengths(const uint32_t *freq, int n, int limit, uint8_t *len)
+{
+    if (!png_code_lengths_args(freq, 1, n, limit, len)) { set_error("tmat_host_png_code_lengths: bad argument (1 <= n <= 286, 2^limit >= n, limit <= 15, sum of frequencies below 2^22)"); return TMAT_E_ARG; }
+    png_code_lengths(freq, n, limit, len);
+    return TMAT_OK;
+}
+
+int tmat_debug_png_code_lengths(tmat_handle h, const uint32_t *freqs, int k, int n, int limit, uint8_t *lens)
+{
+    Ctx *c = (Ctx *)h;
+    if (!c || k < 0 || (k && !png_code_lengths_args(freqs, (size_t)k, n, limit, lens))) {
+        set_error("tmat_debug_png_code_lengths: bad argument (a handle, 1 <= n <= 286, 2^limit >= n, limit <= 15, sums of frequencies below 2^22)");
+        return TMAT_E_ARG;
+    }
+    if (k == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    DevScope mem(c->ws_pool, c->stream);
+    uint32_t *df = mem.pooled<uint32_t>((size_t)k * n);
+    uint8_t *dl = mem.pooled<uint8_t>((size_t)k * n);
+    if (!mem.ok) return TMAT_E_HIP;
+    mem.h2d(df, freqs, (size_t)k * n * sizeof(uint32_t));
+    if (!mem.ok) return TMAT_E_HIP;
+    if (png_code_lengths_launch(df, k, n, limit, dl, c->stream)) { set_error("tmat_debug_png_code_lengths: kernel launch failed"); return TMAT_E_HIP; }
+    mem.d2h(lens, dl, (size_t)k * n);
+    return mem.finish() ? TMAT_E_HIP : TMAT_OK;
 }
 
 static int png_encode_api(const char *who, tmat_handle hd, const uint8_t *pics, bool on_host, int n, int H, int W, int channels, uint8_t *out,
@@ -1551,7 +1607,7 @@ int png_encode_ctx(Ctx *c, const uint8_t *pics, bool on_host, int n, const PngSh
         if (on_host) { mem.h2d(dpic, src, (size_t)k * pic_bytes); src = dpic; }
         mark(1);
         if (!mem.ok) return TMAT_E_HIP;
-        if (png_encode_launch(src, k, g, filt, slots, meta, files, fcap, dsz, s)) { set_error("png encoder: kernel launch failed"); return TMAT_E_HIP; }
+        if (png_encode_launch(src, k, g, c->png_mode, filt, slots, meta, files, fcap, dsz, s)) { set_error("png encoder: kernel launch failed"); return TMAT_E_HIP; }
         mark(2);
         mem.d2h(hsz, dsz, (size_t)k * sizeof(uint32_t));
         if (mem.finish()) return TMAT_E_HIP;

@@ -238,6 +238,7 @@ struct Ctx {
     float norm_mean = 0.f, norm_std = 1.f;
     int resnet_precision = 0;                                // invasion-depth classifiers: TMAT_RESNET_PRECISION_F32 (bit-exact contract), _F16 or _F16ACT (opt-in, tmat_resnet_set_precision)
     bool narrow = false;                                     // some convolution of the model runs on the narrow kernel (conv_narrow_kernels.hip): f32 only
+    int png_mode = 0;                                        // TMAT_PNG_FAST or TMAT_PNG_COMPACT (opt-in, tmat_png_set_mode): every PNG file this handle encodes
     int precision = 0;                                       // TMAT_PRECISION_F32 (bit-exact contract) or TMAT_PRECISION_BF16X3 / _BF16X6 (opt-in, tmat_set_precision)
     std::map<const float *, ConvWHost> conv_w_host;          // device pointer of every MFMA convolution weight tensor -> its host copy
     std::map<int, std::map<const float *, float *>> wsplit;  // precision mode -> (... -> its split-precision copy on the device, made on first use)

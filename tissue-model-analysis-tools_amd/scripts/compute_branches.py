@@ -72,6 +72,9 @@ def parse_branching_args(arg_defaults):
                    help="who encodes the PNG pictures of --visualizations / --tree-visualizations: pil (the default: Pillow on the host, one "
                         "file after the other) or device (the library's deflate / PNG kernels: all pictures of one shape of a pass in one "
                         "batched call, only file bytes cross to the host).  The pixels are the same; the files differ in size")
+    p.add_argument("--png-compression", choices=["fast", "compact"], default="fast",
+                   help="with --png-encoder device: fast (the default: fixed Huffman blocks) or compact (lazy matching and dynamic Huffman "
+                        "blocks: smaller files for more time on the device).  The pixels are the same")
     p.add_argument("--sato-hessian", choices=["gaussian_derivatives", "gradient"], default="gaussian_derivatives",
                    help="Z stacks: Hessian of skimage.filters.sato -- gaussian_derivatives (scikit-image >= 0.20, the reference's pinned "
                         "0.22.0) or gradient (scikit-image <= 0.19)")
@@ -268,6 +271,7 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
     tree_vis = bool(getattr(args, "tree_visualizations", False))
     vis_width = int(getattr(args, "vis_width", 2000) or 2000)
     encoder = handle.png_encode if getattr(args, "png_encoder", "pil") == "device" else None
+    handle.png_set_mode(getattr(args, "png_compression", "fast"))
     grid = branches.threshold_grid(config)
     suffix_of = {(cfg["thresh1"], cfg["thresh2"]): sfx for cfg, sfx in grid}
     ids = sorted(paths)
@@ -402,6 +406,9 @@ def main(args=None):
     else:
         config = {}
     ad = vars(args)
+    if ad.get("png_compression", "fast") != "fast" and ad.get("png_encoder", "pil") != "device":
+        print(f"{FAIL} --png-compression {ad['png_compression']} needs --png-encoder device.", flush=True)
+        sys.exit(1)
     for prm in ("image_width_microns", "graph_thresh_1", "graph_thresh_2", "graph_smoothing_window", "min_branch_length",
                 "max_branch_length", "remove_isolated_branches"):
         if prm not in config or ad.get(prm) is not None:
@@ -447,6 +454,7 @@ def main(args=None):
     well_seed = int(getattr(args, "well_seed", 0) or 0)
     # --png-encoder device: every PNG below goes through the handle's encoder, batched by shape; pil (the default): Pillow, file by file
     encoder = model.handle.png_encode if getattr(args, "png_encoder", "pil") == "device" else None
+    model.handle.png_set_mode(getattr(args, "png_compression", "fast"))
 
     # ids are file stems, as in the reference (compute_branches.py:565-569: two files with one stem are one entry there too)
     ids = sorted(paths)

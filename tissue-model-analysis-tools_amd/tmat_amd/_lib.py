@@ -185,6 +185,10 @@ def lib():
     L.tmat_png_encode_batch_dev.argtypes = L.tmat_png_encode_batch.argtypes
     L.tmat_png_encode_batch_timed.argtypes = L.tmat_png_encode_batch.argtypes + [vp]
     L.tmat_host_png_encode_batch.argtypes = [vp, i, i, i, i, vp, sz, vp]
+    L.tmat_host_png_encode_batch_mode.argtypes = [vp, i, i, i, i, vp, sz, vp, i]
+    L.tmat_png_set_mode.argtypes = [vp, i]
+    L.tmat_host_png_code_lengths.argtypes = [vp, i, i, vp]
+    L.tmat_debug_png_code_lengths.argtypes = [vp, vp, i, i, i, vp]
     L.tmat_render_tree_png.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, i, vp, sz, vp]
     L.tmat_prof_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), i]
     for name in EXPORTS:
@@ -221,6 +225,7 @@ EXPORTS = [
     "tmat_conv2d_narrow", "tmat_model_layers",
     "tmat_predict_smooth_ex", "tmat_smooth_plan", "tmat_spline_window", "tmat_smooth_begin", "tmat_smooth_tiles", "tmat_smooth_put",
     "tmat_smooth_end", "tmat_debug_smooth_times", "tmat_resize_pil_f32", "tmat_host_resize_pil_f32", "tmat_predict_auto_resample",
+    "tmat_png_set_mode", "tmat_host_png_encode_batch_mode", "tmat_host_png_code_lengths", "tmat_debug_png_code_lengths",
 ]
 
 PIL_FILTERS = {"nearest": 0, "lanczos": 1}      # TMAT_PIL_*, Pillow's Image.Resampling numbers
@@ -626,6 +631,18 @@ class Handle:
             check(lib().tmat_stage_pictures(self._h, ptr(a), PIC_DTYPES[a.dtype], a.shape[0], a[0].size, ptr(out)), "tmat_stage_pictures")
         return out.reshape(shape)
 
+    def png_set_mode(self, mode="fast"):
+        """tmat_png_set_mode: "fast" (the default) or "compact" (lazy parse, dynamic Huffman blocks: smaller files) for every PNG file the
+        handle encodes from now on"""
+        check(lib().tmat_png_set_mode(self._h, _png_mode(mode)), "tmat_png_set_mode")
+
+    def debug_png_code_lengths(self, freqs, limit):
+        """tmat_debug_png_code_lengths: (k, n) histograms -> (k, n) u8 code lengths, computed on the device"""
+        f = np.ascontiguousarray(freqs, np.uint32)
+        lens = np.zeros(f.shape, np.uint8)
+        check(lib().tmat_debug_png_code_lengths(self._h, ptr(f), f.shape[0], f.shape[1], int(limit), ptr(lens)), "tmat_debug_png_code_lengths")
+        return lens
+
     def png_encode(self, pics):
         """tmat_png_encode_batch: (n, H, W) grey or (n, H, W, 3) RGB u8 pictures -> n PNG files (bytes), encoded on the device; a 2-D or
         (H, W, 3) array is one picture"""
@@ -887,9 +904,27 @@ def _png_call(fn, pics, what):
     return [out[i, : int(sizes[i])].tobytes() for i in range(n)]
 
 
-def host_png_encode(pics):
-    """tmat_host_png_encode_batch: the host twin of Handle.png_encode (same bytes, no GPU)"""
-    return _png_call(lib().tmat_host_png_encode_batch, _png_arg(pics), "tmat_host_png_encode_batch")
+PNG_MODES = {"fast": 0, "compact": 1}       # TMAT_PNG_FAST, TMAT_PNG_COMPACT
+
+
+def _png_mode(mode):
+    if mode not in PNG_MODES:
+        raise ValueError(f"png mode must be one of {sorted(PNG_MODES)}")
+    return PNG_MODES[mode]
+
+
+def host_png_encode(pics, mode="fast"):
+    """tmat_host_png_encode_batch_mode: the host twin of Handle.png_encode in the given mode (same bytes, no GPU)"""
+    m = _png_mode(mode)
+    return _png_call(lambda *a: lib().tmat_host_png_encode_batch_mode(*a, m), _png_arg(pics), "tmat_host_png_encode_batch_mode")
+
+
+def host_png_code_lengths(freq, limit):
+    """tmat_host_png_code_lengths: a histogram (n) -> its code lengths (n) u8"""
+    f = np.ascontiguousarray(freq, np.uint32)
+    lens = np.zeros(f.shape, np.uint8)
+    check(lib().tmat_host_png_code_lengths(ptr(f), f.shape[0], int(limit), ptr(lens)), "tmat_host_png_code_lengths")
+    return lens
 
 
 def _stage_pictures_arg(a):

@@ -11,8 +11,11 @@ profiles/png_bench.json.
   more than (b)'s round-to-round spread, and whether encode + write per image in (c) is below (a)'s time per image.
 * overlays: render_tree + PIL against render_tree_png + write, the same rounds.
 * --merge-bench FILE: bench.py result lines of one session, each prefixed "parent " or "branch " (tools/bench_overlay.py:bench_series).
+* --compact: the same report for the encoder's two modes (Handle.png_set_mode) side by side, written to profiles/png_compact_bench.json:
+  per kind the two modes alternate call by call after one warm-up call each (medians of --repeats), every compact file is checked against
+  the host twin's, and the end-to-end rounds run (c) once per mode -- (c) fast and (c) compact alternate in the same rounds.
 
-    python tools/bench_png.py [--n 64] [--rounds 3] [--repeats 5] [--vis-width 2000] [--quick]
+    python tools/bench_png.py [--n 64] [--rounds 3] [--repeats 5] [--vis-width 2000] [--quick] [--compact]
 """
 import argparse
 import io
@@ -41,20 +44,35 @@ def pil_files(pics):
     return out, (time.perf_counter() - t0) * 1e3 / len(pics)
 
 
-def kind_report(handle, pics, repeats):
-    """one kind of picture: PIL against the device, per picture"""
+def kind_report(handle, pics, repeats, modes=("fast",)):
+    """one kind of picture: PIL against the device, per picture.  One mode: the report itself; several: {mode: report}, the modes
+    alternating call by call"""
     from PIL import Image
+    from tmat_amd import _lib
     pil, pil_ms = pil_files(pics)
-    files, _ = handle.png_encode_timed(pics)                                    # warm-up: pool blocks, code objects
-    runs = [handle.png_encode_timed(pics)[1] for _ in range(repeats)]
-    same = all(np.array_equal(np.asarray(Image.open(io.BytesIO(f))), p) for f, p in zip(files, pics))
+    files, runs = {}, {m: [] for m in modes}
+    for m in modes:
+        handle.png_set_mode(m)
+        files[m], _ = handle.png_encode_timed(pics)                             # warm-up: pool blocks, code objects
+    for _ in range(repeats):
+        for m in modes:
+            handle.png_set_mode(m)
+            runs[m].append(handle.png_encode_timed(pics)[1])
+    handle.png_set_mode("fast")
     n = len(pics)
-    ms = {k: float(np.median([r[k] for r in runs])) / n for k in ("upload", "kernels", "copy_back")}
-    dev_bytes, pil_bytes = sum(map(len, files)), sum(map(len, pil))
-    return dict(pictures=n, shape=list(pics.shape[1:]), pil_ms_per_picture=pil_ms, device_ms_per_picture=ms,
-                device_total_ms_per_picture=sum(ms.values()), file_size_device_over_pil=dev_bytes / pil_bytes,
-                bytes_copied_back_over_raw=dev_bytes / pics.nbytes, device_file_bytes_mean=dev_bytes / n, pil_file_bytes_mean=pil_bytes / n,
-                pillow_decodes_to_the_pictures=bool(same))
+    out = {}
+    for m in modes:
+        same = all(np.array_equal(np.asarray(Image.open(io.BytesIO(f))), p) for f, p in zip(files[m], pics))
+        ms = {k: float(np.median([r[k] for r in runs[m]])) / n for k in ("upload", "kernels", "copy_back")}
+        dev_bytes, pil_bytes = sum(map(len, files[m])), sum(map(len, pil))
+        out[m] = dict(pictures=n, shape=list(pics.shape[1:]), pil_ms_per_picture=pil_ms, device_ms_per_picture=ms,
+                      device_total_ms_per_picture=sum(ms.values()), file_size_device_over_pil=dev_bytes / pil_bytes,
+                      bytes_copied_back_over_raw=dev_bytes / pics.nbytes, device_file_bytes_mean=dev_bytes / n, pil_file_bytes_mean=pil_bytes / n,
+                      pillow_decodes_to_the_pictures=bool(same))
+        if len(modes) > 1 and len(pics) <= 16:
+            out[m]["equals_the_host_twin"] = bool(files[m] == _lib.host_png_encode(pics, mode=m))
+            out[m]["pillow_decodes_to_the_pictures"] = bool(same and out[m]["equals_the_host_twin"])
+    return out[modes[0]] if len(modes) == 1 else out
 
 
 def main():
@@ -65,6 +83,7 @@ def main():
     ap.add_argument("--vis-width", type=int, default=2000)
     ap.add_argument("--quick", action="store_true", help="8 images, 2 repeats, overlays 600 wide, no file written")
     ap.add_argument("--merge-bench", type=str, default=None, metavar="FILE")
+    ap.add_argument("--compact", action="store_true", help="fast and compact side by side; writes profiles/png_compact_bench.json")
     a = ap.parse_args()
     if a.quick:
         a.n, a.repeats, a.vis_width = 8, 2, 600
@@ -83,17 +102,21 @@ def main():
     handle = _lib.Handle(synth.pack_weights(synth.synth_weights(0)), 0, 0)
     res = dict(stripe_bytes=_lib.png_stripe(), images=a.n, rounds=a.rounds, vis_width=a.vis_width)
     ok = True
+    modes = ("fast", "compact") if a.compact else ("fast",)
+
+    def all_decode(report):
+        return all(r["pillow_decodes_to_the_pictures"] for r in (report.values() if a.compact else [report]))
     try:
         # ---- per kind of picture ----
         _, ex = branches.analyze_batch_ex(handle, imgs[:n_ov], CFG, 500.0, stage_pictures=True)
         stage = np.ascontiguousarray(ex["pictures"]).reshape((-1,) + ex["pictures"].shape[2:])
         overlays = handle.render_tree(bgs, trees, a.vis_width)
-        kinds = dict(stage_pictures=kind_report(handle, stage, a.repeats), overlays=kind_report(handle, overlays, a.repeats),
-                     barcode=kind_report(handle, _lib.host_render_barcode(bars, a.vis_width)[None], a.repeats))
+        kinds = dict(stage_pictures=kind_report(handle, stage, a.repeats, modes), overlays=kind_report(handle, overlays, a.repeats, modes),
+                     barcode=kind_report(handle, _lib.host_render_barcode(bars, a.vis_width)[None], a.repeats, modes))
         for name, plane in zip(_lib.STAGE_PLANES, range(4)):
-            kinds["stage_" + name] = kind_report(handle, np.ascontiguousarray(stage[plane::4]), max(2, a.repeats // 2))
+            kinds["stage_" + name] = kind_report(handle, np.ascontiguousarray(stage[plane::4]), a.repeats if a.compact else max(2, a.repeats // 2), modes)
         res["kinds"] = kinds
-        ok = all(k["pillow_decodes_to_the_pictures"] for k in kinds.values())
+        ok = all(all_decode(k) for k in kinds.values())
 
         # ---- end to end ----
         enc_write = []
@@ -107,15 +130,24 @@ def main():
                 branches.save_stage_pictures(e["pictures"][i], Path(d) / f"img_{i}")
             return rows
 
-        def form_c(d):
+        file_bytes = {}
+
+        def form_c(d, mode="fast"):
+            handle.png_set_mode(mode)
             rows, e = branches.analyze_batch_ex(handle, imgs, CFG, 500.0, stage_pictures=True)
             t0 = time.perf_counter()
             items = []
             for i in range(a.n):
                 items += branches.stage_picture_items(e["pictures"][i], Path(d) / f"img_{i}")
             branches.write_png_batch(items, handle.png_encode)
-            enc_write.append(time.perf_counter() - t0)
+            if mode == "fast":
+                enc_write.append(time.perf_counter() - t0)
+            handle.png_set_mode("fast")
+            file_bytes[mode] = sum(p.stat().st_size for p in Path(d).rglob("*.png"))
             return rows
+
+        def form_c_compact(d):
+            return form_c(d, "compact")
 
         def rounds_of(forms):
             times, rows = {k: [] for k, _ in forms}, {}
@@ -131,7 +163,7 @@ def main():
                     print(f"[bench_png] round {r + 1}/{a.rounds}: " + ", ".join(f"({k}) {times[k][-1]:.3f} s" for k, _ in forms), file=sys.stderr, flush=True)
             return times, rows
 
-        times, rows = rounds_of((("a", form_a), ("b", form_b), ("c", form_c)))
+        times, rows = rounds_of((("a", form_a), ("b", form_b), ("c", form_c)) + ((("c_compact", form_c_compact),) if a.compact else ()))
         med = {k: float(np.median(v)) for k, v in times.items()}
         b_spread = max(times["b"]) - min(times["b"])
         ew_ms = 1e3 * float(np.median(enc_write)) / a.n
@@ -145,6 +177,12 @@ def main():
             k = kinds["stage_pictures"]
             parts = dict(k["device_ms_per_picture"], host_python_and_file_write=ew_ms / 4 - k["device_total_ms_per_picture"])
             e2e["largest_phase_of_the_rest"] = max(parts, key=parts.get)
+        if a.compact:
+            mc = float(np.median(times["c_compact"]))
+            e2e.update(c_compact_s=times["c_compact"], c_compact_images_per_s=a.n / mc, b_minus_c_compact_median_s=med["b"] - mc,
+                       c_compact_faster_than_b_by_more_than_b_spread=bool(med["b"] - mc > b_spread),
+                       c_compact_minus_c_median_s=mc - med["c"], png_bytes_written=dict(file_bytes),
+                       rows_equal=bool(e2e["rows_equal"] and rows["c_compact"] == rows["a"]))
         res["end_to_end"] = e2e
         ok = ok and e2e["rows_equal"]
 
@@ -155,21 +193,29 @@ def main():
             for i, o in enumerate(handle.render_tree(bgs, trees, a.vis_width)):
                 Image.fromarray(o, "RGB").save(d / f"morse_tree_{i}.png")
 
-        def ov_dev(d):
+        def ov_dev(d, mode="fast"):
             d.mkdir(parents=True)
+            handle.png_set_mode(mode)
             for i, f in enumerate(handle.render_tree_png(bgs, trees, a.vis_width)):
                 (d / f"morse_tree_{i}.png").write_bytes(f)
+            handle.png_set_mode("fast")
 
-        t2, _ = rounds_of((("pil", ov_pil), ("device", ov_dev)))
+        def ov_dev_compact(d):
+            ov_dev(d, "compact")
+
+        t2, _ = rounds_of((("pil", ov_pil), ("device", ov_dev)) + ((("device_compact", ov_dev_compact),) if a.compact else ()))
         res["overlays_end_to_end"] = dict(overlays=n_ov, render_tree_plus_pil_s=t2["pil"], render_tree_png_plus_write_s=t2["device"],
                                           pil_ms_per_overlay=1e3 * float(np.median(t2["pil"])) / n_ov,
                                           device_ms_per_overlay=1e3 * float(np.median(t2["device"])) / n_ov)
+        if a.compact:
+            res["overlays_end_to_end"].update(render_tree_png_compact_plus_write_s=t2["device_compact"],
+                                              device_compact_ms_per_overlay=1e3 * float(np.median(t2["device_compact"])) / n_ov)
     finally:
         handle.close()
     if a.merge_bench:
         res["bench_py_default_path"] = bench_series(a.merge_bench)
     if not a.quick:
-        (REPO / "profiles" / "png_bench.json").write_text(json.dumps(res, indent=1) + "\n")
+        (REPO / "profiles" / ("png_compact_bench.json" if a.compact else "png_bench.json")).write_text(json.dumps(res, indent=1) + "\n")
     print(json.dumps(res))
     return 0 if ok else 1
 
