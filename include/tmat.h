@@ -460,6 +460,73 @@ int tmat_host_png_encode_batch_mode(const uint8_t *pics, int n, int H, int W, in
 int tmat_host_png_code_lengths(const uint32_t *freq, int n, int limit, uint8_t *len);
 int tmat_debug_png_code_lengths(tmat_handle h, const uint32_t *freqs, int k, int n, int limit, uint8_t *lens);
 
+/*
+ * TIFF pixels decoded on the device (csrc/tiff.h, tiff_host.cpp, tiff_kernels.hip): the ingest-side counterpart of the
+ * PNG encoder.  It replaces the per-page host decode of the reference's helper.py:23-95 (load_image: PIL's Image.open / seek /
+ * np.array, one page at a time) for the files it supports: only the file's bytes cross to the device, and the pixels land where the
+ * _dev entry points read them.  The file is untrusted: every offset, count and product is checked against its size.
+ *
+ * tmat_tiff_probe walks the IFD chain of a classic TIFF (II or MM) in host memory; no handle, no GPU.  It fills
+ * pages[0, min(cap_pages, *n_pages)) and sets *n_pages to the number of pages found.  status per page:
+ *   TMAT_TIFF_OK        the device path decodes it: strips, SamplesPerPixel 1, BitsPerSample 8 or 16, SampleFormat 1 or absent,
+ *                       Photometric 1, FillOrder 1, PlanarConfiguration 1 or absent, Compression 1 (none), 5 (LZW, MSB first) or 32773
+ *                       (PackBits), Predictor 1, or 2 with LZW, and every strip inside the file
+ *   TMAT_TIFF_FALLBACK  a valid file of another kind (reason TMAT_TIFF_R_BIGTIFF and above): the caller decodes it as before
+ *   TMAT_TIFF_CORRUPT   inconsistent (reason below TMAT_TIFF_R_BIGTIFF).  Damage to the header or to the chain itself (an IFD outside the
+ *                       file, an entry count that overruns it, a chain that loops) ends the walk with one last page of this status
+ * A NULL file or a NULL n_pages, cap_pages < 0, or pages NULL with cap_pages > 0: TMAT_E_ARG.
+ *
+ * The decode calls take planes: plane i is page page_of[i] of file file_of[i] (files[k] with n_bytes[k] bytes, host memory).  All
+ * planes of a call have one shape (H, W) and one bit depth; the output is (n_planes, H, W) uint16, 8-bit samples widened, and *bits
+ * says 8 or 16 (0 when no plane decoded) for the callers' input_bits.  status[i] is the plane's: a plane that is not TMAT_TIFF_OK --
+ * not supported, a page the file does not have, or a strip whose stream turns out corrupt while it is decoded -- leaves its output
+ * slice untouched and does not fail the call.  A supported plane of another shape, or two of different depth: TMAT_E_ARG.
+ * Stream rules (csrc/tiff.h): LZW codes of 9 to 12 bits read MSB first, widened when the next free entry is (1 << width) - 1, Clear
+ * 256, EOI 257, a code equal to the next free entry is the previous string plus its first byte and a code above it is corrupt, a full
+ * table (4096) stops growing, a strip ends when rows W bytes are produced and EOI or the end of the input before that is corrupt;
+ * PackBits with the same count rules; then byte swap (MM), predictor 2 per row modulo 2^bits, widen.
+ * tmat_host_tiff_decode_batch is the host twin (no handle, no GPU); tmat_tiff_decode_batch decodes on the device into host memory,
+ * tmat_tiff_decode_batch_dev into out_dev, a tmat_dev_alloc block of n_planes H W uint16.  All three give the same pixels and status.
+ * A handle from tmat_create_plain is enough; device memory comes from the handle's pool on first use, in chunks of bounded size.
+ */
+#define TMAT_TIFF_OK 0
+#define TMAT_TIFF_FALLBACK 1
+#define TMAT_TIFF_CORRUPT 2
+#define TMAT_TIFF_R_NONE 0
+#define TMAT_TIFF_R_HEADER 1        /* not a TIFF header, or shorter than one */
+#define TMAT_TIFF_R_IFD 2           /* an IFD position or entry count outside the file */
+#define TMAT_TIFF_R_LOOP 3          /* the IFD chain returns to an IFD it has visited */
+#define TMAT_TIFF_R_TAG 4           /* a needed tag is missing, of a wrong type, or its values lie outside the file */
+#define TMAT_TIFF_R_STRIPS 5        /* strip tables inconsistent with the height, or a strip outside the file */
+#define TMAT_TIFF_R_STREAM 6        /* reserved for a strip stream found corrupt while decoding (the decode calls report status only) */
+#define TMAT_TIFF_R_PAGE 7
+#define TMAT_TIFF_R_BIGTIFF 20
+#define TMAT_TIFF_R_TILES 21
+#define TMAT_TIFF_R_SAMPLES 22      /* SamplesPerPixel other than 1 (RGB, interleaved) */
+#define TMAT_TIFF_R_BITS 23         /* BitsPerSample other than 8 or 16 */
+#define TMAT_TIFF_R_SAMPLE_FORMAT 24
+#define TMAT_TIFF_R_PHOTOMETRIC 25
+#define TMAT_TIFF_R_FILL_ORDER 26
+#define TMAT_TIFF_R_PLANAR 27
+#define TMAT_TIFF_R_COMPRESSION 28  /* Deflate, JPEG, ... */
+#define TMAT_TIFF_R_PREDICTOR 29    /* predictor 3, or 2 without LZW */
+#define TMAT_TIFF_R_OLD_LZW 30      /* old-style LZW stream (first byte 0, low bit of the second set) */
+#define TMAT_TIFF_R_SIZE 31         /* a plane above 2^30 bytes */
+typedef struct tmat_tiff_page {
+    int32_t width, height, bits, compression, predictor, big_endian, rows_per_strip, n_strips, status, reason;
+} tmat_tiff_page;
+int tmat_tiff_probe(const uint8_t *file, size_t n_bytes, int cap_pages, tmat_tiff_page *pages, int *n_pages);
+int tmat_host_tiff_decode_batch(const uint8_t *const *files, const size_t *n_bytes, const int *file_of, const int *page_of, int n_planes,
+                                int H, int W, uint16_t *out, int *bits, int *status);
+int tmat_tiff_decode_batch(tmat_handle h, const uint8_t *const *files, const size_t *n_bytes, const int *file_of, const int *page_of,
+                           int n_planes, int H, int W, uint16_t *out_host, int *bits, int *status);
+int tmat_tiff_decode_batch_dev(tmat_handle h, const uint8_t *const *files, const size_t *n_bytes, const int *file_of, const int *page_of,
+                               int n_planes, int H, int W, void *out_dev, int *bits, int *status);
+/* tmat_tiff_decode_batch_dev that also reports ms2 = HIP-event milliseconds on the handle's stream of {upload of the file bytes and the
+ * strip tables, kernels} (tools/bench_tiff.py) */
+int tmat_tiff_decode_batch_dev_timed(tmat_handle h, const uint8_t *const *files, const size_t *n_bytes, const int *file_of, const int *page_of,
+                                     int n_planes, int H, int W, void *out_dev, int *bits, int *status, float *ms2);
+
 /* One result row per image, the payload gathered across ranks. */
 typedef struct tmat_row {
     int64_t index;   /* image index in the run                      */

@@ -4,6 +4,7 @@
 #include "../../include/tmat.h"
 #include "tmat_ctx.h"
 #include "png.h"
+#include "tiff.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1580,6 +1581,68 @@ int tmat_png_encode_batch_timed(tmat_handle h, const uint8_t *pics, int n, int H
     return png_encode_api("tmat_png_encode_batch_timed", h, pics, true, n, H, W, channels, out, cap_each, sizes, ms3);
 }
 
+// ---- TIFF decoder (tiff.h) ----
+
+int tmat_tiff_probe(const uint8_t *file, size_t n_bytes, int cap_pages, tmat_tiff_page *pages, int *n_pages)
+{
+    static_assert(sizeof(tmat_tiff_page) == sizeof(TiffPageInfo), "tmat_tiff_page and TiffPageInfo are one layout");
+    if (!file || !n_pages || cap_pages < 0 || (cap_pages > 0 && !pages)) { set_error("tmat_tiff_probe: bad argument"); return TMAT_E_ARG; }
+    tiff_walk(file, n_bytes, cap_pages, (TiffPageInfo *)pages, n_pages, -1, nullptr);
+    return TMAT_OK;
+}
+
+static int tiff_args(const char *who, const uint8_t *const *files, const size_t *n_bytes, const int *file_of, const int *page_of, int n_planes,
+                     int H, int W, const void *out, int *bits, int *status, TiffPlan &plan)
+{
+    bool ok = n_planes >= 0 && H >= 1 && W >= 1 && bits && (n_planes == 0 || (files && n_bytes && file_of && page_of && out && status));
+    ok = ok && (uint64_t)H * (uint64_t)W * 2 <= TIFF_MAX_PLANE_BYTES;
+    for (int i = 0; ok && i < n_planes; i++) ok = file_of[i] >= 0 && page_of[i] >= 0 && page_of[i] < (1 << 20);
+    if (!ok) { set_error(std::string(who) + ": bad argument (planes of one shape H, W >= 1 of at most 2^30 bytes, pages below 2^20)"); return TMAT_E_ARG; }
+    std::string err;
+    if (!tiff_plan(files, n_bytes, file_of, page_of, n_planes, H, W, plan, status, err)) { set_error(std::string(who) + ": " + err); return TMAT_E_ARG; }
+    *bits = plan.bits;
+    return TMAT_OK;
+}
+
+int tmat_host_tiff_decode_batch(const uint8_t *const *files, const size_t *n_bytes, const int *file_of, const int *page_of, int n_planes,
+                                int H, int W, uint16_t *out, int *bits, int *status)
+{
+    TiffPlan plan;
+    if (int rc = tiff_args("tmat_host_tiff_decode_batch", files, n_bytes, file_of, page_of, n_planes, H, W, out, bits, status, plan)) return rc;
+    tiff_decode_host(files, file_of, plan, H, W, out, status);
+    return TMAT_OK;
+}
+
+static int tiff_decode_api(const char *who, tmat_handle hd, const uint8_t *const *files, const size_t *n_bytes, const int *file_of,
+                           const int *page_of, int n_planes, int H, int W, void *out, bool out_on_host, int *bits, int *status, float *ms2 = nullptr)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!c) { set_error(std::string(who) + ": null handle"); return TMAT_E_ARG; }
+    TiffPlan plan;
+    if (int rc = tiff_args(who, files, n_bytes, file_of, page_of, n_planes, H, W, out, bits, status, plan)) return rc;
+    if (ms2) ms2[0] = ms2[1] = 0.0f;
+    if (n_planes == 0) return TMAT_OK;
+    TMAT_HIP(hipSetDevice(c->device));
+    return tiff_decode_ctx(c, files, n_bytes, file_of, plan, H, W, (uint16_t *)out, out_on_host, status, ms2);
+}
+
+int tmat_tiff_decode_batch(tmat_handle h, const uint8_t *const *files, const size_t *n_bytes, const int *file_of, const int *page_of,
+                           int n_planes, int H, int W, uint16_t *out_host, int *bits, int *status)
+{
+    return tiff_decode_api("tmat_tiff_decode_batch", h, files, n_bytes, file_of, page_of, n_planes, H, W, out_host, true, bits, status);
+}
+int tmat_tiff_decode_batch_dev(tmat_handle h, const uint8_t *const *files, const size_t *n_bytes, const int *file_of, const int *page_of,
+                               int n_planes, int H, int W, void *out_dev, int *bits, int *status)
+{
+    return tiff_decode_api("tmat_tiff_decode_batch_dev", h, files, n_bytes, file_of, page_of, n_planes, H, W, out_dev, false, bits, status);
+}
+int tmat_tiff_decode_batch_dev_timed(tmat_handle h, const uint8_t *const *files, const size_t *n_bytes, const int *file_of, const int *page_of,
+                                     int n_planes, int H, int W, void *out_dev, int *bits, int *status, float *ms2)
+{
+    if (!ms2) { set_error("tmat_tiff_decode_batch_dev_timed: bad argument"); return TMAT_E_ARG; }
+    return tiff_decode_api("tmat_tiff_decode_batch_dev_timed", h, files, n_bytes, file_of, page_of, n_planes, H, W, out_dev, false, bits, status, ms2);
+}
+
 }  // extern "C"
 
 namespace tmat {
@@ -1619,6 +1682,91 @@ int png_encode_ctx(Ctx *c, const uint8_t *pics, bool on_host, int n, const PngSh
         mark(3);
         if (mem.finish()) return TMAT_E_HIP;
         span(0, 1, 0); span(1, 2, 1); span(2, 3, 2);
+    }
+    return TMAT_OK;
+}
+
+// pool requests of the decoder in a few sizes per magnitude, so that calls of different batches share the pool's blocks
+static size_t tiff_pool_size(size_t bytes)
+{
+    size_t step = 4096;
+    while (step * 8 < bytes) step *= 2;
+    return (bytes + step - 1) / step * step;
+}
+
+// The planes of `plan` in chunks of consecutive planes: at most TIFF_CHUNK_BYTES of file bytes, of raw strip bytes and (out_on_host) of
+// pixels per chunk -- one plane at least -- each file uploaded once per chunk, whole.
+int tiff_decode_ctx(Ctx *c, const uint8_t *const *files, const size_t *n_bytes, const int *file_of, const TiffPlan &plan, int H, int W,
+                    uint16_t *out, bool out_on_host, int *status, float *ms2)
+{
+    constexpr size_t TIFF_CHUNK_BYTES = (size_t)256 << 20;
+    hipStream_t s = c->stream;
+    const size_t n = plan.planes.size(), px = (size_t)H * W;
+    struct Events { hipEvent_t e[3] = {nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) hipEventDestroy(x); } } ev;
+    if (ms2) for (hipEvent_t &e : ev.e) TMAT_HIP(hipEventCreate(&e));
+    for (size_t i0 = 0; i0 < n;) {
+        // the chunk [i0, i1): its files, strips and planes with chunk-relative indices
+        std::map<int, uint64_t> base;           // file -> first byte in the blob
+        std::vector<TiffPlane> planes;
+        std::vector<TiffStrip> strips;
+        size_t blob_bytes = 0, raw_bytes = 0, i1 = i0;
+        for (; i1 < n && i1 - i0 < 65535; i1++) {
+            TiffPlane p = plan.planes[i1];
+            size_t add_blob = 0, add_raw = 0;
+            if (p.ok) {
+                if (!base.count(file_of[i1])) add_blob = (n_bytes[file_of[i1]] + 15) & ~(size_t)15;
+                if (p.comp != TIFF_COMP_NONE) add_raw = (px * (size_t)p.bytes + 15) & ~(size_t)15;
+                if (i1 > i0 && (blob_bytes + add_blob > TIFF_CHUNK_BYTES || raw_bytes + add_raw > TIFF_CHUNK_BYTES ||
+                                (out_on_host && (i1 - i0 + 1) * px * 2 > TIFF_CHUNK_BYTES))) break;
+                if (add_blob) { base[file_of[i1]] = blob_bytes; blob_bytes += add_blob; }
+                p.file_base = base[file_of[i1]];
+                p.raw = raw_bytes;
+                raw_bytes += add_raw;
+                const int ns = (H + p.rps - 1) / p.rps, first = (int)strips.size();
+                for (int k = 0; k < ns; k++) {
+                    TiffStrip st = plan.strips[(size_t)p.first_strip + k];
+                    st.plane = (int32_t)(i1 - i0);
+                    strips.push_back(st);
+                }
+                p.first_strip = first;
+            }
+            p.out_index = (int32_t)(out_on_host ? i1 - i0 : i1);
+            planes.push_back(p);
+        }
+        const size_t k = i1 - i0;
+        if (!strips.empty()) {
+            DevScope mem(c->ws_pool, s);
+            uint8_t *blob = (uint8_t *)mem.pooled_bytes(tiff_pool_size(blob_bytes));
+            uint8_t *raw = (uint8_t *)mem.pooled_bytes(tiff_pool_size(std::max<size_t>(raw_bytes, 16)));
+            uint16_t *dout = out_on_host ? (uint16_t *)mem.pooled_bytes(tiff_pool_size(k * px * 2)) : out;
+            TiffStrip *dstrips = (TiffStrip *)mem.pooled_bytes(tiff_pool_size(strips.size() * sizeof(TiffStrip)));
+            TiffPlane *dplanes = (TiffPlane *)mem.pooled_bytes(tiff_pool_size(k * sizeof(TiffPlane)));
+            int *dbad = (int *)mem.pooled_bytes(tiff_pool_size(k * sizeof(int)));
+            int *hbad = mem.host<int>(k);
+            if (!mem.ok) return TMAT_E_HIP;
+            auto mark = [&](int i) { if (ms2 && mem.ok) mem.check(hipEventRecord(ev.e[i], s), "hipEventRecord"); };
+            mark(0);
+            for (auto &fb : base) mem.h2d(blob + fb.second, files[fb.first], n_bytes[fb.first]);
+            mem.h2d(dstrips, strips.data(), strips.size() * sizeof(TiffStrip));
+            mem.h2d(dplanes, planes.data(), k * sizeof(TiffPlane));
+            mark(1);
+            if (!mem.ok) return TMAT_E_HIP;
+            if (tiff_decode_launch(blob, dstrips, (int)strips.size(), dplanes, (int)k, H, W, raw, dout, dbad, s)) {
+                set_error("tiff decoder: kernel launch failed");
+                return TMAT_E_HIP;
+            }
+            mark(2);
+            mem.d2h(hbad, dbad, k * sizeof(int));
+            if (mem.finish()) return TMAT_E_HIP;           // strips and planes are host temporaries of this turn: drained before they go
+            for (int a = 0; ms2 && a < 2; a++) { float t = 0.0f; if (hipEventElapsedTime(&t, ev.e[a], ev.e[a + 1]) == hipSuccess) ms2[a] += t; }
+            for (size_t j = 0; j < k; j++) {
+                if (!planes[j].ok) continue;
+                if (hbad[j]) status[i0 + j] = TIFF_CORRUPT;
+                else if (out_on_host) mem.d2h(out + (i0 + j) * px, dout + j * px, px * 2);
+            }
+            if (mem.finish()) return TMAT_E_HIP;
+        }
+        i0 = i1;
     }
     return TMAT_OK;
 }

@@ -19,6 +19,7 @@ without --image-width-microns (or the config key) the width comes from OME / Ima
 (tmat_amd/helper.py), as in the reference.
 """
 import argparse
+import contextlib
 import csv
 import ctypes as C
 import json
@@ -72,6 +73,10 @@ def parse_branching_args(arg_defaults):
                    help="who encodes the PNG pictures of --visualizations / --tree-visualizations: pil (the default: Pillow on the host, one "
                         "file after the other) or device (the library's deflate / PNG kernels: all pictures of one shape of a pass in one "
                         "batched call, only file bytes cross to the host).  The pixels are the same; the files differ in size")
+    p.add_argument("--tiff-decoder", choices=["pil", "device"], default="pil",
+                   help="Where TIFF pixels are decoded: pil (default; Pillow on the host, then an upload of raw pixels) or device (only the "
+                        "file bytes are uploaded, the strips are decoded on the GPU and the batch routes read them where they land; files "
+                        "the device path does not take still go through Pillow). The rows and pictures are the same.")
     p.add_argument("--png-compression", choices=["fast", "compact"], default="fast",
                    help="with --png-encoder device: fast (the default: fixed Huffman blocks) or compact (lazy matching and dynamic Huffman "
                         "blocks: smaller files for more time on the device).  The pixels are the same")
@@ -193,6 +198,61 @@ def load_stack(files, channel=None, time=None) -> np.ndarray:
     return a
 
 
+def plan_image_2d(path: str, channel=None, time=None):
+    """load_image_2d without the decode (--tiff-decoder device): a helper.PlaneSource of the plane, with load_image_2d's checks; .npy
+    arrays are loaded as before"""
+    from tmat_amd import helper
+    if path.endswith(".npy"):
+        return load_image_2d(path, channel, time)
+    src = helper.plan_planes(path, time, channel)
+    if len(src.shape) == 3:
+        raise ValueError(f"{path}: multi-page file (Z stack); project it first with compute_zproj.py")
+    if src.dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"{path}: expected uint8/uint16 pixels, got {src.dtype}")
+    return src
+
+
+def plan_stack(files, channel=None, time=None):
+    """load_stack without the decode (--tiff-decoder device), with its checks"""
+    from tmat_amd import helper
+    if isinstance(files, str) and files.endswith(".npy"):
+        return load_stack(files, channel, time)
+    src = helper.plan_planes(files, time, channel)
+    if len(src.shape) != 3:
+        raise ValueError(f"{np.atleast_1d(files)[0]}: expected a Z stack, got shape {src.shape}")
+    if src.dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"{np.atleast_1d(files)[0]}: expected uint8/uint16 pixels, got {src.dtype}")
+    if src.shape[0] < 2:
+        raise ValueError(f"{np.atleast_1d(files)[0]}: a Z stack needs at least 2 slices")
+    return src
+
+
+def make_stack_fn(handle):
+    """run_sharded's stack_fn for --tiff-decoder device: the group's files are decoded on the device into one resident block
+    (helper.load_planes_dev), shaped like the batch np.stack would give; a group that holds .npy arrays is stacked on the host"""
+    from tmat_amd import helper
+
+    def stack_fn(items):
+        if all(isinstance(it, helper.PlaneSource) for it in items):
+            dev = helper.load_planes_dev(handle, items)
+            dev.shape = (len(items),) + items[0].shape
+            return dev
+        arrays = []
+        for it in items:
+            if isinstance(it, helper.PlaneSource):
+                with helper.load_planes_dev(handle, [it]) as dev:
+                    it = dev.download().reshape(it.shape)
+            arrays.append(it)
+        return np.stack(arrays).astype(np.uint16)
+    return stack_fn
+
+
+def resident(batch) -> bool:
+    """a batch decoded on the device and still there (helper.DevPlanes), not a host array"""
+    from tmat_amd import helper
+    return isinstance(batch, helper.DevPlanes)
+
+
 def make_load_fn(loader, paths, args):
     """run_sharded's load_fn over loader (load_image_2d or load_stack): an unreadable entry prints the failure and raises InputError"""
     from tmat_amd import branches
@@ -292,7 +352,8 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
             from PIL import Image
             Image.fromarray((well * 255).astype(np.uint8)).save(out_root / "visualizations" / img_id / "well_mask.png")
 
-    load_fn, width_fn = make_load_fn(load_stack, paths, args), make_width_fn(config, paths)
+    device_decode = getattr(args, "tiff_decoder", "pil") == "device"
+    load_fn, width_fn = make_load_fn(plan_stack if device_decode else load_stack, paths, args), make_width_fn(config, paths)
 
     def analyze_batch_fn(batch, width_um, thresh, ids):
         # one upload and one pass over the whole chunk and the whole grid; run_sharded then asks configuration by configuration
@@ -301,9 +362,10 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
             fields["batch"] = batch
             sw_px, min_px, max_px = branches.graph_px_params(config, DOWNSAMPLE_WIDTH, width_um)
             pairs = [(cfg["thresh1"], cfg["thresh2"]) for cfg, _ in grid]
-            n, per = len(batch), batch[0].size
+            n, per = len(batch), int(np.prod(batch.shape[1:]))
             rows_all = [[] for _ in pairs]
-            with sato.upload_stacks(handle, batch) as dev:
+            # --tiff-decoder device: the decoded block is the resident chunk (run_sharded frees it); else one upload
+            with (contextlib.nullcontext(sato.DevStacks(handle, batch.ptr, batch.shape)) if resident(batch) else sato.upload_stacks(handle, batch)) as dev:
                 pruning = None
                 if detect_well:
                     well, pruning = sato.stack_well_masks_batch(handle, dev, sato.dsamp_shape(batch.shape, DOWNSAMPLE_WIDTH), well_seed)
@@ -342,6 +404,8 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
     def analyze_fn(batch, width_um, thresh, input_bits, ids):
         if batch_on and len(batch) > 1:
             return analyze_batch_fn(batch, width_um, thresh, ids)
+        if resident(batch):         # the per-stack path works on host arrays: the decoded block is downloaded once
+            batch = batch.host()
         # the vesselness image does not depend on the graph thresholds: one field per stack, swept over the grid
         sw_px, min_px, max_px = branches.graph_px_params(config, DOWNSAMPLE_WIDTH, width_um)
         rows = []
@@ -385,7 +449,8 @@ def run_stacks(args, config, paths, out_root: Path, rank: int, ws: int, local_ra
     # per-stack path: one stack per analysis call (chunk=1): a stack is the unit the reference streams, and it can be gigabytes
     try:
         gathered = branches.run_sharded(ids, load_fn, width_fn, analyze_fn, config, rank, ws, chunk=sato.STACK_PASS_MAX if batch_on else 1,
-                                        log=lambda m: print(m, flush=True), pass_ids=True, chunk_ends=stack_chunk_ends if batch_on else None)
+                                        log=lambda m: print(m, flush=True), pass_ids=True, chunk_ends=stack_chunk_ends if batch_on else None,
+                                        stack_fn=make_stack_fn(handle) if device_decode else None)
     except distributed.RankFailed:
         handle.close()
         finish_distributed(ws)
@@ -458,7 +523,8 @@ def main(args=None):
 
     # ids are file stems, as in the reference (compute_branches.py:565-569: two files with one stem are one entry there too)
     ids = sorted(paths)
-    load_fn, width_fn = make_load_fn(load_image_2d, paths, args), make_width_fn(config, paths)
+    device_decode = getattr(args, "tiff_decoder", "pil") == "device"
+    load_fn, width_fn = make_load_fn(plan_image_2d if device_decode else load_image_2d, paths, args), make_width_fn(config, paths)
 
     well_cache = {}
 
@@ -510,7 +576,8 @@ def main(args=None):
         rows_by = {p: [] for p in pairs}
         for i0 in range(0, len(batch), step):
             sub_ids = ids[i0:i0 + step]
-            rb, ex = branches.analyze_batch_grid(model.handle, batch[i0:i0 + step], config, width_um, model.ds_ratio, pairs, first_index=i0,
+            sub = batch.part(i0, min(step, len(batch) - i0)) if resident(batch) else batch[i0:i0 + step]      # resident: tmat_analyze_batch_grid_dev
+            rb, ex = branches.analyze_batch_grid(model.handle, sub, config, width_um, model.ds_ratio, pairs, first_index=i0,
                                                  input_bits=input_bits, tree=tree_vis, vis_width=vis_width, stage_pictures=vis,
                                                  tree_png=on_device, barcode_png=on_device, raw_overlays=not on_device, budget=1 << 62)
             if vis:
@@ -534,6 +601,8 @@ def main(args=None):
         return rows_by
 
     def analyze_fn(batch, width_um, thresh, input_bits, ids):
+        if resident(batch) and detect_well:         # the -w routes take host arrays: the decoded block is downloaded once
+            batch = batch.host()
         if not (detect_well and tree_vis):
             if grid_cache.get("batch") is not batch:
                 grid_cache.clear()
@@ -569,7 +638,8 @@ def main(args=None):
 
     try:
         gathered = branches.run_sharded(ids, load_fn, width_fn, analyze_fn, config, rank, ws,
-                                        log=lambda m: print(m, flush=True), pass_ids=True)
+                                        log=lambda m: print(m, flush=True), pass_ids=True,
+                                        stack_fn=make_stack_fn(model.handle) if device_decode else None)
     except distributed.RankFailed:          # the failing rank has printed the reference's message; every rank exits with code 1
         model.handle.close()
         finish_distributed(ws)

@@ -40,6 +40,10 @@ def parse_zproj_args(argv=None):
     p.add_argument("-m", "--method", type=str, default="max", choices=["min", "max", "med", "avg", "fs"],
                    help="Z projection method (min, max, med, avg, fs = focus stacking). Defaults to 'max'.")
     p.add_argument("-a", "--area", action="store_true", help="Compute cell area after computing Z projection.")
+    p.add_argument("--tiff-decoder", choices=["pil", "device"], default="pil",
+                   help="Where TIFF pixels are decoded: pil (default; Pillow on the host, then an upload of raw pixels) or device (only the "
+                        "file bytes are uploaded and the strips are decoded on the GPU; files the device path does not take still go "
+                        "through Pillow). The projections are the same.")
     args = p.parse_args(argv)
     for k, v in vars(args).items():
         if isinstance(v, str):
@@ -86,6 +90,17 @@ def load_stack(path_or_paths, channel=None, time=None) -> np.ndarray:
     if st.dtype not in (np.uint8, np.uint16):
         raise ValueError(f"expected uint8/uint16 pixels, got {st.dtype}")
     return st
+
+
+def plan_stack(path_or_paths, channel=None, time=None):
+    """load_stack without the decode (--tiff-decoder device): a helper.PlaneSource with the stack's shape and pixel type"""
+    from tmat_amd import helper
+    src = helper.plan_planes(list(path_or_paths) if isinstance(path_or_paths, (list, tuple)) else path_or_paths, time, channel)
+    if len(src.shape) == 2:
+        src.shape = (1,) + src.shape
+    if src.dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"expected uint8/uint16 pixels, got {src.dtype}")
+    return src
 
 
 def save_projection(path, img):
@@ -149,7 +164,13 @@ def main(args=None):
 
     def flush(groups):
         for members in groups.values():
-            proj = handle.zproj(np.stack([m[2] for m in members]), args.method)
+            if device_decode:       # one resident block per group: file bytes up, strips decoded on the device, projected in place
+                from tmat_amd import helper
+                srcs = [m[2] for m in members]
+                with helper.load_planes_dev(handle, srcs) as dev:
+                    proj = handle.zproj_dev(dev.ptr, (len(srcs),) + srcs[0].shape, args.method, srcs[0].dtype)
+            else:
+                proj = handle.zproj(np.stack([m[2] for m in members]), args.method)
             for (zs_id, zs_path, _), img in zip(members, proj):
                 out_ext = Path(np.atleast_1d(zs_path)[0]).suffix.lower()
                 if out_ext not in (".tif", ".tiff", ".png"):
@@ -161,11 +182,12 @@ def main(args=None):
                 save_projection(save_path, img)
                 print(f"Z projection saved to {save_path}", flush=True)
 
+    device_decode = getattr(args, "tiff_decoder", "pil") == "device"
     groups, held = {}, 0
     for zs_id, zs_path in zstack_paths.items():
         print(f"Processing {zs_id}...", flush=True)
         try:
-            st = load_stack(zs_path, args.channel, getattr(args, "time", None))
+            st = (plan_stack if device_decode else load_stack)(zs_path, args.channel, getattr(args, "time", None))
         except (OSError, ValueError) as error:
             print(f"{FAIL}{error}", flush=True)
             sys.exit(1)
@@ -189,10 +211,10 @@ def main(args=None):
             if arg in ("-a", "--area", args.in_root, args.out_root):
                 continue
             # options that describe the INPUT stacks: the projections written above are single-plane files
-            if arg in ("-m", "--method", "--time", "--channel"):
+            if arg in ("-m", "--method", "--time", "--channel", "--tiff-decoder"):
                 skip = True
                 continue
-            if arg.startswith(("--method=", "--time=", "--channel=")) or (arg.startswith("-m") and len(arg) > 2 and not arg.startswith("--")):
+            if arg.startswith(("--method=", "--time=", "--channel=", "--tiff-decoder=")) or (arg.startswith("-m") and len(arg) > 2 and not arg.startswith("--")):
                 continue
             options.append(arg)
         script_path = Path(__file__).resolve().parent / "compute_cell_area.py"

@@ -190,6 +190,11 @@ def lib():
     L.tmat_host_png_code_lengths.argtypes = [vp, i, i, vp]
     L.tmat_debug_png_code_lengths.argtypes = [vp, vp, i, i, i, vp]
     L.tmat_render_tree_png.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, i, vp, sz, vp]
+    L.tmat_tiff_probe.argtypes = [vp, sz, i, vp, C.POINTER(i)]
+    L.tmat_host_tiff_decode_batch.argtypes = [vp, vp, vp, vp, i, i, i, vp, C.POINTER(i), vp]
+    L.tmat_tiff_decode_batch.argtypes = [vp] + L.tmat_host_tiff_decode_batch.argtypes
+    L.tmat_tiff_decode_batch_dev.argtypes = L.tmat_tiff_decode_batch.argtypes
+    L.tmat_tiff_decode_batch_dev_timed.argtypes = L.tmat_tiff_decode_batch.argtypes + [vp]
     L.tmat_prof_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), i]
     for name in EXPORTS:
         fn = getattr(L, name)
@@ -226,6 +231,8 @@ EXPORTS = [
     "tmat_predict_smooth_ex", "tmat_smooth_plan", "tmat_spline_window", "tmat_smooth_begin", "tmat_smooth_tiles", "tmat_smooth_put",
     "tmat_smooth_end", "tmat_debug_smooth_times", "tmat_resize_pil_f32", "tmat_host_resize_pil_f32", "tmat_predict_auto_resample",
     "tmat_png_set_mode", "tmat_host_png_encode_batch_mode", "tmat_host_png_code_lengths", "tmat_debug_png_code_lengths",
+    "tmat_tiff_probe", "tmat_host_tiff_decode_batch", "tmat_tiff_decode_batch", "tmat_tiff_decode_batch_dev",
+    "tmat_tiff_decode_batch_dev_timed",
 ]
 
 PIL_FILTERS = {"nearest": 0, "lanczos": 1}      # TMAT_PIL_*, Pillow's Image.Resampling numbers
@@ -477,6 +484,21 @@ class Handle:
         check(lib().tmat_zproj_batch(self._h, ptr(a), n, Z, H, W, m, ptr(out)), "tmat_zproj_batch")
         return out.astype(stacks.dtype) if m < 3 else out
 
+    def zproj_dev(self, stacks_dev, shape, method="fs", dtype=np.uint16):
+        """tmat_zproj_dev: the same for (n, Z, H, W) uint16 stacks resident in a tmat_dev_alloc block (8-bit sources widened: pass
+        dtype=np.uint8 to get fs / min / max back as zproj returns them)"""
+        m = self.ZPROJ_METHODS[method]
+        n, Z, H, W = (int(v) for v in shape)
+        out = np.empty((n, H, W), np.float64 if m >= 3 else np.uint16)
+        d = C.c_void_p()
+        check(lib().tmat_dev_alloc(self._h, max(out.nbytes, 1), C.byref(d)), "tmat_dev_alloc")
+        try:
+            check(lib().tmat_zproj_dev(self._h, stacks_dev, n, Z, H, W, m, d), "tmat_zproj_dev")
+            check(lib().tmat_dev_download(self._h, ptr(out), d, out.nbytes), "tmat_dev_download")
+        finally:
+            lib().tmat_dev_free(self._h, d)
+        return out.astype(dtype) if m < 3 else out
+
     def set_input_norm(self, norm_mean=None, norm_std=None):
         """models.py:636-637 on the device: x = (x - norm_mean) / norm_std in front of the smooth prediction; None turns it off"""
         on = norm_mean is not None and norm_std is not None
@@ -659,6 +681,26 @@ class Handle:
         ms = np.zeros(3, np.float32)
         files = _png_call(lambda *a: lib().tmat_png_encode_batch_timed(self._h, *a, ptr(ms)), pics, "tmat_png_encode_batch_timed")
         return files, dict(zip(("upload", "kernels", "copy_back"), (float(v) for v in ms)))
+
+    def tiff_decode(self, files, planes, H, W, out=None):
+        """tmat_tiff_decode_batch: planes (a list of (file index, page)) of the TIFF files (a list of bytes), decoded on the device ->
+        (pixels (n, H, W) uint16, bits, status (n,)); planes whose status is not TIFF_OK keep what `out` held (zeros without one)"""
+        if out is None:
+            out = np.zeros((len(planes), int(H), int(W)), np.uint16)
+        assert out.dtype == np.uint16 and out.flags.c_contiguous and out.shape == (len(planes), int(H), int(W))
+        bits, status = _tiff_call(lambda *a: lib().tmat_tiff_decode_batch(self._h, *a), files, planes, H, W, ptr(out), "tmat_tiff_decode_batch")
+        return out, bits, status
+
+    def tiff_decode_dev(self, files, planes, H, W, out_dev):
+        """tmat_tiff_decode_batch_dev: the same into out_dev, a tmat_dev_alloc block of n H W uint16 -> (bits, status (n,))"""
+        return _tiff_call(lambda *a: lib().tmat_tiff_decode_batch_dev(self._h, *a), files, planes, H, W, out_dev, "tmat_tiff_decode_batch_dev")
+
+    def tiff_decode_dev_timed(self, files, planes, H, W, out_dev):
+        """tmat_tiff_decode_batch_dev_timed: (bits, status, {phase: HIP-event ms}) with the phases upload and kernels"""
+        ms = np.zeros(2, np.float32)
+        bits, status = _tiff_call(lambda *a: lib().tmat_tiff_decode_batch_dev_timed(self._h, *a, ptr(ms)), files, planes, H, W, out_dev,
+                                  "tmat_tiff_decode_batch_dev_timed")
+        return bits, status, dict(upload=float(ms[0]), kernels=float(ms[1]))
 
     def render_tree_png(self, backgrounds, trees, vis_width=2000):
         """tmat_render_tree_png: Handle.render_tree's overlays as n PNG files (bytes); the raw overlays stay on the device"""
@@ -925,6 +967,57 @@ def host_png_code_lengths(freq, limit):
     lens = np.zeros(f.shape, np.uint8)
     check(lib().tmat_host_png_code_lengths(ptr(f), f.shape[0], int(limit), ptr(lens)), "tmat_host_png_code_lengths")
     return lens
+
+
+TIFF_OK, TIFF_FALLBACK, TIFF_CORRUPT = 0, 1, 2          # TMAT_TIFF_OK, TMAT_TIFF_FALLBACK, TMAT_TIFF_CORRUPT
+TIFF_REASONS = {0: "none", 1: "header", 2: "ifd", 3: "loop", 4: "tag", 5: "strips", 6: "stream", 7: "page", 20: "bigtiff", 21: "tiles",
+                22: "samples", 23: "bits", 24: "sample_format", 25: "photometric", 26: "fill_order", 27: "planar", 28: "compression",
+                29: "predictor", 30: "old_lzw", 31: "size"}                                     # TMAT_TIFF_R_*
+TIFF_PAGE_FIELDS = ("width", "height", "bits", "compression", "predictor", "big_endian", "rows_per_strip", "n_strips", "status", "reason")
+
+
+def tiff_probe(data: bytes):
+    """tmat_tiff_probe: the pages of a TIFF file held in memory, one dict per page with the fields of tmat_tiff_page (`reason` as its
+    name in TIFF_REASONS).  Host only: no GPU, no handle.  A damaged header or IFD chain ends the list with a page of status TIFF_CORRUPT."""
+    buf = np.frombuffer(data, np.uint8) if len(data) else np.zeros(1, np.uint8)
+    n, cap = C.c_int(0), 16
+    while True:
+        pages = np.zeros((cap, len(TIFF_PAGE_FIELDS)), np.int32)
+        check(lib().tmat_tiff_probe(ptr(buf), len(data), cap, ptr(pages), C.byref(n)), "tmat_tiff_probe")
+        if n.value <= cap:
+            break
+        cap = n.value
+    out = [dict(zip(TIFF_PAGE_FIELDS, (int(v) for v in row))) for row in pages[: n.value]]
+    for p in out:
+        p["reason"] = TIFF_REASONS.get(p["reason"], str(p["reason"]))
+    return out
+
+
+def _tiff_call(fn, files, planes, H, W, out, what):
+    """fn(files, n_bytes, file_of, page_of, n_planes, H, W, out, bits, status) over files (a list of bytes) and planes (a list of
+    (file index, page)) -> (bits, status (n_planes,) int32)"""
+    bufs = [np.frombuffer(f, np.uint8) if len(f) else np.zeros(1, np.uint8) for f in files]
+    for fi, pg in planes:
+        if not 0 <= int(fi) < len(files):
+            raise ValueError(f"{what}: file index {fi} outside the {len(files)} files")
+    fptr = (C.c_void_p * max(len(bufs), 1))(*[b.ctypes.data for b in bufs])
+    nb = np.array([len(f) for f in files] or [0], np.uintp)
+    fo = np.array([int(p[0]) for p in planes] or [0], np.int32)
+    po = np.array([int(p[1]) for p in planes] or [0], np.int32)
+    status = np.zeros(max(len(planes), 1), np.int32)
+    bits = C.c_int(0)
+    check(fn(C.cast(fptr, C.c_void_p), ptr(nb), ptr(fo), ptr(po), len(planes), int(H), int(W), out, C.byref(bits), ptr(status)), what)
+    return bits.value, status[: len(planes)]
+
+
+def host_tiff_decode(files, planes, H, W, out=None):
+    """tmat_host_tiff_decode_batch: the host twin of Handle.tiff_decode (same pixels and status, no GPU) -> (pixels (n, H, W) uint16,
+    bits, status); `out`: an (n, H, W) uint16 array to decode into (planes that are not TIFF_OK keep what it holds)"""
+    if out is None:
+        out = np.zeros((len(planes), int(H), int(W)), np.uint16)
+    assert out.dtype == np.uint16 and out.flags.c_contiguous and out.shape == (len(planes), int(H), int(W))
+    bits, status = _tiff_call(lib().tmat_host_tiff_decode_batch, files, planes, H, W, ptr(out), "tmat_host_tiff_decode_batch")
+    return out, bits, status
 
 
 def _stage_pictures_arg(a):

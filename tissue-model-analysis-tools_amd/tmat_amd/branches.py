@@ -208,7 +208,8 @@ def analyze_batch_grid(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
                        first_index: int = 0, input_bits: int = 16, well_masks=None, pruning_masks=None, tree: bool = False, vis_width: int = 2000,
                        stage_pictures: bool = False, tree_png: bool = False, barcode_png: bool = False, raw_overlays: bool = True,
                        cap_bars: int = 4096, budget: int = 1 << 30):
-    """The threshold grid from ONE pass of the network (tmat_analyze_batch_grid): imgs (n, H, W) uint16, pairs [(graph_thresh_1,
+    """The threshold grid from ONE pass of the network (tmat_analyze_batch_grid): imgs (n, H, W) uint16 -- or (device pointer, (n, H, W))
+    for images resident in a tmat_dev_alloc block, through tmat_analyze_batch_grid_dev -- pairs [(graph_thresh_1,
     graph_thresh_2)] (None: grid_pairs(config)) -> ({pair: rows as analyze_batch returns them at that pair}, extras).  The requests are
     analyze_batch_ex's; what depends on the pair comes back per pair:
       tree            extras["bars"] = {pair: [bars (k, 2) f64 per image]} and, with raw_overlays, extras["overlays"] = {pair: (n, vh, vw, 3) u8}
@@ -218,8 +219,13 @@ def analyze_batch_grid(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
       stage_pictures  extras["pictures"] (n, 4, h, w) u8, once: they do not depend on the pair
     tree_png / barcode_png imply tree.  With pictures the images go through in chunks of grid_images_per_call, so that the picture buffers
     of one call stay under `budget` bytes."""
-    imgs = np.ascontiguousarray(imgs, np.uint16)
-    n, H, W = imgs.shape
+    resident = isinstance(imgs, tuple)          # (device pointer, (n, H, W)): uint16 images in a tmat_dev_alloc block, read in place
+    if resident:
+        dev_ptr, (n, H, W) = imgs[0], (int(v) for v in imgs[1])
+        dev_base = dev_ptr.value if isinstance(dev_ptr, C.c_void_p) else int(dev_ptr)
+    else:
+        imgs = np.ascontiguousarray(imgs, np.uint16)
+        n, H, W = imgs.shape
     pairs = grid_pairs(config) if pairs is None else [(p[0], p[1]) for p in pairs]
     T = len(pairs)
     if T < 1:
@@ -248,7 +254,7 @@ def analyze_batch_grid(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
             extras["pictures"] = np.empty((0, 4, hh, ww), np.uint8)
         return rows_by, extras
     thresh = np.ascontiguousarray(np.asarray(pairs, np.float32).reshape(T, 2))
-    fn = _entry(handle, "tmat_analyze_batch_grid", input_bits)
+    fn = _entry(handle, "tmat_analyze_batch_grid_dev" if resident else "tmat_analyze_batch_grid", input_bits)
     vh = vw = S = tcap = bcap = 0
     if tree:
         vh, vw = _lib.tree_canvas_shape(hh, ww, vis_width)
@@ -282,7 +288,8 @@ def analyze_batch_grid(handle: _lib.Handle, imgs: np.ndarray, config: dict, imag
         def call(bars, cap):
             if tree:
                 o.bars_out, o.cap_b = bars.ctypes.data, cap
-            return fn(_lib.ptr(imgs[i0:]), k, H, W, C.byref(o), C.byref(g), rows)
+            src = C.c_void_p(dev_base + i0 * H * W * 2) if resident else _lib.ptr(imgs[i0:])
+            return fn(src, k, H, W, C.byref(o), C.byref(g), rows)
         rc, bars = _retry_bars((T, k), cap_bars, fh * fw, call) if tree else (call(None, 0), None)
         _lib.check(rc, "tmat_analyze_batch_grid")
         for t, p in enumerate(pairs):
@@ -520,7 +527,7 @@ class InputError(Exception):
 
 
 def run_sharded(ids, load_fn, width_fn, analyze_fn, config: dict, rank: int = 0, world_size: int = 1, chunk: int = 64,
-                log=print, pass_ids: bool = False, chunk_ends=None):
+                log=print, pass_ids: bool = False, chunk_ends=None, stack_fn=None):
     """The per-run driver of scripts/compute_branches.py (reference :585-594 loops over the images one by one):
     rank `rank` of `world_size` takes a contiguous block of `ids`, loads its images in bounded chunks of at most `chunk`
     (images of equal shape, physical width and bit depth are analysed as one batch), and all ranks exchange their rows
@@ -532,6 +539,9 @@ def run_sharded(ids, load_fn, width_fn, analyze_fn, config: dict, rank: int = 0,
     are written per image inside analyze_fn).
     chunk_ends (optional): chunk_ends(keys of the images held, key of the next image, next image) -> bool, asked before an image joins
     the held chunk; True analyses the held chunk first (the Z-stack path groups consecutive stacks of one key under a byte budget).
+    stack_fn (optional): stack_fn([what load_fn returned for the images of one group]) -> the batch handed to analyze_fn in place of
+    np.stack(...).astype(np.uint16); load_fn may then return any object with shape and dtype (helper.PlaneSource: files not yet decoded,
+    the group is decoded in flush).  A batch with a free() method is freed when its group is done.
     Returns {file-name suffix: [(global index, count, total_um, avg_um)] sorted by index}, on every rank."""
     from . import distributed
     ids = list(ids)
@@ -541,13 +551,17 @@ def run_sharded(ids, load_fn, width_fn, analyze_fn, config: dict, rank: int = 0,
 
     def flush(groups):
         for (shape, width_um, bits), items in groups.items():
-            batch = np.stack([im for _, im in items]).astype(np.uint16)
+            batch = stack_fn([im for _, im in items]) if stack_fn is not None else np.stack([im for _, im in items]).astype(np.uint16)
             extra = {"ids": [ids[g] for g, _ in items]} if pass_ids else {}
-            for cfg, suffix in grid:
-                rows = analyze_fn(batch, width_um, thresh=(cfg["thresh1"], cfg["thresh2"]), input_bits=bits, **extra)
-                for (gidx, _), r in zip(items, rows):
-                    results[suffix].append((gidx, r[1], pixels_to_microns(r[2], DOWNSAMPLE_WIDTH, width_um),
-                                            pixels_to_microns(r[3], DOWNSAMPLE_WIDTH, width_um)))
+            try:
+                for cfg, suffix in grid:
+                    rows = analyze_fn(batch, width_um, thresh=(cfg["thresh1"], cfg["thresh2"]), input_bits=bits, **extra)
+                    for (gidx, _), r in zip(items, rows):
+                        results[suffix].append((gidx, r[1], pixels_to_microns(r[2], DOWNSAMPLE_WIDTH, width_um),
+                                                pixels_to_microns(r[3], DOWNSAMPLE_WIDTH, width_um)))
+            finally:
+                if hasattr(batch, "free"):
+                    batch.free()
 
     # Whatever goes wrong on this rank -- an unreadable image (InputError), a HIP / library error out of analyze_fn, a shape
     # surprise in np.stack -- the rank must still enter the collective below: the other ranks are waiting in it and would block

@@ -156,3 +156,181 @@ def load_image(file_path, T: Optional[int] = None, C: Optional[int] = None):
             planes.append(a[..., C] if interleaved else a)
     arr = planes[0] if len(planes) == 1 else np.stack(planes)
     return arr, physical_pixel_sizes(file_path)
+
+
+# ---- TIFF pixels decoded on the device (include/tmat.h: tmat_tiff_decode_batch_dev) ----
+
+def tiff_probe(path_or_bytes):
+    """tmat_tiff_probe on a file (a path, or its bytes): one dict per page -- width, height, bits, compression, predictor, big_endian,
+    rows_per_strip, n_strips, status (_lib.TIFF_OK / TIFF_FALLBACK / TIFF_CORRUPT) and reason.  No GPU."""
+    from . import _lib
+    data = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray, memoryview)) else open(path_or_bytes, "rb").read()
+    return _lib.tiff_probe(bytes(data))
+
+
+class PlaneSource:
+    """What load_image(file_path, T, C) would return, not yet decoded: the files' bytes, the (file, page, channel inside the page or
+    None) of every plane, and `shape` ((Z, H, W), or (H, W) for a single plane), `dtype` and `nbytes` of the array, so that code
+    which groups images by shape and depth takes it in place of the array."""
+
+    def __init__(self, paths, blobs, planes, plane_shape, dtype, supported):
+        self.paths, self.blobs, self.planes, self.supported = paths, blobs, planes, supported
+        self.dtype = np.dtype(dtype)
+        self.shape = tuple(plane_shape) if len(planes) == 1 else (len(planes),) + tuple(plane_shape)
+        self.ndim = len(self.shape)
+        self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
+
+    def pil_plane(self, k):
+        """plane k through Pillow, as load_image reads it"""
+        from PIL import Image
+        fi, page, ch = self.planes[k]
+        with Image.open(self.paths[fi]) as im:
+            im.seek(page)
+            a = np.array(im)
+        return a if ch is None else a[..., ch]
+
+
+def plan_planes(file_path, T: Optional[int] = None, C: Optional[int] = None) -> PlaneSource:
+    """load_image's page selection without the decode: the same T / C / Z rules through page_layout and the same error messages.  The
+    containers are opened with Pillow for their description and page count only, and probed with tmat_tiff_probe."""
+    from PIL import Image
+    from . import _lib
+    paths = [str(p) for p in file_path] if isinstance(file_path, (list, tuple)) else [str(file_path)]
+    blobs, planes, shapes, dtypes, supported = [], [], set(), set(), []
+    for fi, path in enumerate(paths):
+        with Image.open(path) as im:
+            n_pages = getattr(im, "n_frames", 1)
+            tags = dict(getattr(im, "tag_v2", {}) or {})
+            desc = tags.get(270, "")
+            if isinstance(desc, (tuple, list)):
+                desc = desc[0] if desc else ""
+            if isinstance(desc, bytes):
+                desc = desc.decode("utf8", "replace")
+            st, sz, sc, order = page_layout(desc, n_pages)
+            im.seek(0)
+            bands = len(im.getbands())
+            interleaved = bands > 1                     # RGB(A) pages: the channel axis is inside the page
+            size, mode = im.size, im.mode
+        n_c = bands if interleaved else sc
+        t, c = T, C
+        if t is None:
+            if st > 1:
+                raise ValueError(f"{path} is a time series image but no time index was specified.")
+            t = 0
+        elif t >= st or t < 0:
+            raise ValueError(f"Time {t} is out of range for {path} with times: 0 - {st - 1}")
+        if c is None:
+            if n_c > 1:
+                raise ValueError(f"{path} is a multi channel image but no color channel index was specified.")
+            c = 0
+        elif c >= n_c or c < 0:
+            raise ValueError(f"Color channel {c} is out of range for {path} with color channels: 0 - {n_c - 1}")
+        sizes = {"T": st, "Z": sz, "C": sc}
+        stride, strides = 1, {}
+        for ax in order:
+            strides[ax] = stride
+            stride *= sizes[ax]
+        blob = open(path, "rb").read()
+        probed = _lib.tiff_probe(blob) if blob[:2] in (b"II", b"MM") else []
+        blobs.append(blob)
+        for z in range(sz):
+            page = t * strides["T"] + z * strides["Z"] + (0 if interleaved else c) * strides["C"]
+            ok = page < len(probed) and probed[page]["status"] == _lib.TIFF_OK
+            if ok:
+                shapes.add((probed[page]["height"], probed[page]["width"]))
+                dtypes.add(np.dtype(np.uint8 if probed[page]["bits"] == 8 else np.uint16))
+            else:                                       # what Pillow will make of it: page 0's size and mode stand for the file's pages
+                shapes.add((size[1], size[0]))
+                dtypes.add(np.dtype({"L": np.uint8, "P": np.uint8, "RGB": np.uint8, "RGBA": np.uint8, "1": np.bool_, "F": np.float32,
+                                     "I": np.int32}.get(mode, np.uint16)))
+            supported.append(ok)
+            planes.append((fi, page, c if interleaved else None))
+    if len(shapes) != 1 or len(dtypes) != 1:
+        raise ValueError(f"{paths[0]}: the planes differ in shape or pixel type")
+    return PlaneSource(paths, blobs, planes, shapes.pop(), dtypes.pop(), supported)
+
+
+class DevPlanes:
+    """planes resident in device memory: `ptr` (a tmat_dev_alloc block of n H W uint16), `shape` (n, H, W), `bits` (8 or 16: what the
+    callers pass on as input_bits) and `counts` (planes per source, in order).  free() it, or use it as a context manager."""
+
+    def __init__(self, handle, ptr_, shape, bits, counts):
+        self.handle, self.ptr, self.shape, self.bits, self.counts = handle, ptr_, tuple(shape), int(bits), list(counts)
+
+    def __len__(self):
+        return self.shape[0]
+
+    def host(self):
+        """the pixels as an array, downloaded once and kept (the same object on every call)"""
+        if getattr(self, "_host", None) is None:
+            self._host = self.download()
+        return self._host
+
+    def part(self, i0, k):
+        """(device pointer, shape) of the items [i0, i0 + k) along the first axis"""
+        import ctypes as C_
+        per = int(np.prod(self.shape[1:]))
+        return C_.c_void_p(self.ptr.value + int(i0) * per * 2), (int(k),) + self.shape[1:]
+
+    def download(self):
+        from . import _lib
+        out = np.empty(self.shape, np.uint16)
+        _lib.check(_lib.lib().tmat_dev_download(self.handle.raw, _lib.ptr(out), self.ptr, out.nbytes), "tmat_dev_download")
+        return out
+
+    def free(self):
+        from . import _lib
+        if self.ptr is not None:
+            _lib.check(_lib.lib().tmat_dev_free(self.handle.raw, self.ptr), "tmat_dev_free")
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+def load_planes_dev(handle, sources) -> DevPlanes:
+    """The planes of `sources` (PlaneSource objects of one plane shape and pixel type, or (file_path, T, C) requests for plan_planes)
+    decoded into ONE resident block: only the files' bytes cross to the device (tmat_tiff_decode_batch_dev).  A plane the device path
+    does not take (tiles, Deflate, BigTIFF, RGB pages, PNG files, ...) is decoded by Pillow exactly as load_image does and uploaded into
+    its slice, so the block always holds complete pixels.  Physical pixel sizes still come from physical_pixel_sizes."""
+    import ctypes as C_
+    from . import _lib
+    sources = [s if isinstance(s, PlaneSource) else plan_planes(*s) for s in sources]
+    if not sources:
+        raise ValueError("load_planes_dev: no source")
+    hw, dtype = sources[0].shape[-2:], sources[0].dtype
+    for s in sources:
+        if s.shape[-2:] != hw or s.dtype != dtype:
+            raise ValueError("load_planes_dev: the sources differ in plane shape or pixel type")
+    if dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"expected uint8/uint16 pixels, got {dtype}")
+    H, W = hw
+    files, planes, owner = [], [], []
+    for s in sources:
+        base = len(files)
+        files += s.blobs
+        for k, (fi, page, _) in enumerate(s.planes):
+            planes.append((base + fi, page))
+            owner.append((s, k))
+    n = len(planes)
+    L = _lib.lib()
+    d = C_.c_void_p()
+    _lib.check(L.tmat_dev_alloc(handle.raw, n * H * W * 2, C_.byref(d)), "tmat_dev_alloc")
+    dev = DevPlanes(handle, d, (n, H, W), 8 * dtype.itemsize, [len(s.planes) for s in sources])
+    try:
+        _, status = handle.tiff_decode_dev(files, planes, H, W, d)       # planes that are not TIFF_OK are left alone and reported
+        todo = [i for i, st in enumerate(status) if st != _lib.TIFF_OK]     # unsupported kinds; a corrupt one fails in Pillow as before
+        for i in todo:
+            s, k = owner[i]
+            a = np.ascontiguousarray(s.pil_plane(k))
+            if a.shape != (H, W) or a.dtype != dtype:
+                raise ValueError(f"{s.paths[s.planes[k][0]]}: expected a {H} x {W} {dtype} plane, got {a.shape} {a.dtype}")
+            a = a.astype(np.uint16)
+            _lib.check(L.tmat_dev_upload(handle.raw, C_.c_void_p(d.value + i * H * W * 2), _lib.ptr(a), a.nbytes), "tmat_dev_upload")
+    except Exception:
+        dev.free()
+        raise
+    return dev
