@@ -1136,6 +1136,22 @@ int tmat_debug_filter_stages(tmat_handle h, const uint8_t *mask, int n, int hh, 
                              int32_t *labels, int32_t *stats, uint8_t *skeleton, uint8_t *filtered, int32_t *thin_launches);
 
 /*
+ * Test-only (tests/test_gpu_medial_stages.py): tmat_medial_axis_batch with the intermediate results of its ordered thinning.  The same
+ * kernels, launches and workspace as tmat_medial_axis_batch; afterwards the stages are copied out of the workspace.  mask (n, h, w) u8.
+ * Outputs, each of which may be null (all of them null is a bad argument):
+ *   skel      (n, h, w) u8    what tmat_medial_axis_batch returns
+ *   dist      (n, h, w) f64   what tmat_medial_axis_batch returns
+ *   keys      (n, h, w) u64   the order key of every pixel: rint(dist^2) << 36 | (9 - foreground count of its 3 x 3 window) << 32 |
+ *                             tie[raster-order rank among the image's foreground pixels]; 2^64 - 1 on the background
+ *   dep       (n, h, w) u8    the predecessor byte: bit k set when neighbour k (raster order of the 3 x 3 window without its centre,
+ *                             NW = bit 0 ... SE = bit 7) lies inside the frame and has a smaller key; 0 on the background
+ *   launches  (1) i32         launches of the thinning's round kernel (16 Jacobi rounds each) the call issued, for all n images together
+ * Argument checks and the "image too large" refusal are tmat_medial_axis_batch's.  A handle from tmat_create_plain is enough.
+ */
+int tmat_debug_medial_stages(tmat_handle h, const uint8_t *mask, int n, int hh, int ww, uint8_t *skel, double *dist, uint64_t *keys, uint8_t *dep,
+                             int32_t *launches);
+
+/*
  * Region plan of the UNet up path for an (hh, ww) image tiled with `patch`-wide windows (host arithmetic, no GPU and no handle).
  * The smooth blend discards the padding ring, so of every patch it reads the rectangle  patch ∩ interior  only; the tiled entry points
  * compute just that rectangle, grown layer by layer by the taps' reach, in every up-path layer (TMAT_ROI=0 at tmat_create: whole

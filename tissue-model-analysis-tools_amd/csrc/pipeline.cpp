@@ -633,7 +633,11 @@ static int analyze_dev(Ctx *c, const AnalyzeCall &call)
 
 // medial_axis on the device for k masks that are in HBM with their EDT: foreground counts -> host permutations -> keys,
 // sort, ordered thinning (thin_kernels.hip).  Synchronises the stream once (the counts come back to the host).
-int medial_thin_batch_dev(Ctx *c, const uint8_t *mask_dev, const double *dist_dev, int k, int hh, int ww, uint8_t *skel_dev, hipStream_t s)
+// stages (test-only, tmat_debug_medial_stages; null for every other caller): host arrays, each of which may be null, that receive
+// copies of what thin_dev left in its workspace.
+struct ThinStages { uint64_t *keys; uint8_t *dep; int32_t *launches; };
+static int medial_thin_stages_dev(Ctx *c, const uint8_t *mask_dev, const double *dist_dev, int k, int hh, int ww, uint8_t *skel_dev, hipStream_t s,
+                                  const ThinStages *stages)
 {
     int rc = ensure_ma_table(c);
     if (rc) return rc;
@@ -641,8 +645,11 @@ int medial_thin_batch_dev(Ctx *c, const uint8_t *mask_dev, const double *dist_de
     DevScope mem(c->ws_pool, s);
     int *nfg_host = mem.host<int>(k);
     int *nfg = mem.alloc<int>(k);
-    uint32_t *tie = mem.alloc<uint32_t>(k * per);
-    void *ws = mem.alloc_bytes(thin_workspace_bytes(k, hh, ww));
+    // the permutations and the workspace come from the handle's pool: the next call of the same geometry gets the same blocks back, with
+    // whatever this one left in them (tmat_debug_poison fills the pool) -- thin_dev's memset of its per-tile flags is what the
+    // repeat-after-poison test holds
+    uint32_t *tie = mem.pooled<uint32_t>(k * per);
+    void *ws = mem.pooled_bytes(thin_workspace_bytes(k, hh, ww));
     if (!mem.ok || thin_count_dev(mask_dev, k, hh, ww, nfg, s)) return TMAT_E_HIP;
     mem.d2h(nfg_host, nfg, k * sizeof(int));
     if (mem.finish()) return TMAT_E_HIP;
@@ -653,8 +660,24 @@ int medial_thin_batch_dev(Ctx *c, const uint8_t *mask_dev, const double *dist_de
         if (bytes) mem.h2d(tie + i * per, mem.keep(std::move(perms[i])), bytes);
     }
     if (!mem.ok) return TMAT_E_HIP;
-    if (thin_dev(mask_dev, dist_dev, tie, nfg, k, hh, ww, ws, c->ma_table, skel_dev, s)) { set_error("medial axis: device thinning failed"); return TMAT_E_HIP; }
+    int launches = 0;
+    if (const int trc = thin_dev(mask_dev, dist_dev, tie, nfg, k, hh, ww, ws, c->ma_table, skel_dev, s, &launches)) {
+        // -3: the launch budget is used up and pixels are still undone; -2: a HIP call failed
+        set_error("medial axis: device thinning failed (" + std::to_string(trc) + " after " + std::to_string(launches) + " launches)");
+        return TMAT_E_HIP;
+    }
+    if (stages) {
+        const ThinLayout lay = thin_layout(ws, k, hh, ww);
+        mem.d2h(stages->keys, lay.keys, k * per * sizeof(uint64_t));
+        mem.d2h(stages->dep, lay.dep, k * per);
+        if (stages->launches) *stages->launches = launches;
+    }
     return mem.finish();
+}
+
+int medial_thin_batch_dev(Ctx *c, const uint8_t *mask_dev, const double *dist_dev, int k, int hh, int ww, uint8_t *skel_dev, hipStream_t s)
+{
+    return medial_thin_stages_dev(c, mask_dev, dist_dev, k, hh, ww, skel_dev, s, nullptr);
 }
 
 // tmat_dmt_graph / tmat_dmt_graph_batch with a handle: key build + sort + the two persistence sweeps of all n fields on the handle's
@@ -955,12 +978,12 @@ int tmat_postprocess_batch(tmat_handle hd, const double *pred, int n, int hh, in
     return TMAT_OK;
 }
 
-int tmat_medial_axis_batch(tmat_handle hd, const uint8_t *mask, int n, int hh, int ww, uint8_t *skel, double *dist)
+// tmat_medial_axis_batch and, with `stages`, tmat_debug_medial_stages: one body, so that the test-only entry point cannot drift
+// from the one it looks into.  The caller has checked its arguments; skel and dist may be null with stages.
+static int medial_axis_entry(Ctx *c, const char *name, const uint8_t *mask, int n, int hh, int ww, uint8_t *skel, double *dist, const ThinStages *stages)
 {
-    Ctx *c = (Ctx *)hd;
-    if (!c || !mask || !skel || !dist || n < 0 || hh < 1 || ww < 1) { set_error("tmat_medial_axis_batch: bad argument"); return TMAT_E_ARG; }
     if (n == 0) return TMAT_OK;
-    if (!thin_dev_supported(hh, ww)) { set_error("tmat_medial_axis_batch: image too large for the device thinning kernel (use tmat_host_medial_axis)"); return TMAT_E_ARG; }
+    if (!thin_dev_supported(hh, ww)) { set_error(std::string(name) + ": image too large for the device thinning kernel (use tmat_host_medial_axis)"); return TMAT_E_ARG; }
     TMAT_HIP(hipSetDevice(c->device));
     const size_t npx = (size_t)n * hh * ww;
     hipStream_t s = c->stream;
@@ -970,11 +993,29 @@ int tmat_medial_axis_batch(tmat_handle hd, const uint8_t *mask, int n, int hh, i
     int *g = mem.alloc<int>(npx), *anyz = mem.alloc<int>(n);
     if (!mem.ok) return TMAT_E_HIP;
     launch_edt(dm, n, hh, ww, g, nullptr, anyz, dd, s);
-    int rc = medial_thin_batch_dev(c, dm, dd, n, hh, ww, dsk, s);
+    int rc = medial_thin_stages_dev(c, dm, dd, n, hh, ww, dsk, s, stages);
     if (rc) return rc;
     mem.d2h(skel, dsk, npx);
     mem.d2h(dist, dd, npx * 8);
     return mem.finish();
+}
+
+int tmat_medial_axis_batch(tmat_handle hd, const uint8_t *mask, int n, int hh, int ww, uint8_t *skel, double *dist)
+{
+    Ctx *c = (Ctx *)hd;
+    if (!c || !mask || !skel || !dist || n < 0 || hh < 1 || ww < 1) { set_error("tmat_medial_axis_batch: bad argument"); return TMAT_E_ARG; }
+    return medial_axis_entry(c, "tmat_medial_axis_batch", mask, n, hh, ww, skel, dist, nullptr);
+}
+
+// Test-only (tests/test_gpu_medial_stages.py): tmat_medial_axis_batch's calls, plus copies of what thin_dev's workspace holds
+int tmat_debug_medial_stages(tmat_handle hd, const uint8_t *mask, int n, int hh, int ww, uint8_t *skel, double *dist, uint64_t *keys, uint8_t *dep,
+                             int32_t *launches)
+{
+    Ctx *c = (Ctx *)hd;
+    const bool any_out = skel || dist || keys || dep || launches;
+    if (!c || !mask || !any_out || n < 0 || hh < 1 || ww < 1) { set_error("tmat_debug_medial_stages: bad argument"); return TMAT_E_ARG; }
+    const ThinStages stages{keys, dep, launches};
+    return medial_axis_entry(c, "tmat_debug_medial_stages", mask, n, hh, ww, skel, dist, &stages);
 }
 
 // The 2-D batch analysis family: nine entry points, one path.  Each fills an AnalyzeCall and hands it to analyze_entry.

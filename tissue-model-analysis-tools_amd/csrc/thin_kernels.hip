@@ -20,8 +20,15 @@
 //                     never depends on pixels beyond its 16-pixel halo -- with in-place updates a workgroup could resolve a
 //                     longer chain in one launch than its neighbour can see, and write back a pixel whose predecessor (in
 //                     the neighbour's tile) is still undone in global memory.  Launches
-//                     ping-pong between two copies of the bytes (every workgroup stages the same snapshot) and repeat until no image has an undone pixel (a flag per image; the depth of the DAG is about the largest
-//                     distance value: a few launches of ~30 us on all CUs instead of one wave per image for 20 ms).
+//                     ping-pong between two copies of the bytes (every workgroup stages the same snapshot) and repeat until no
+//                     image has an undone pixel (a flag per image, read every 4 launches).  A launch finishes the next 16 levels
+//                     of the DAG.  Its depth is NOT bounded by the largest distance value: on filtered vessel masks it is some
+//                     30 to 70 levels (4 or 8 launches of ~30 us on all CUs instead of one wave per image for 20 ms), but where
+//                     many neighbours share a distance the tie-break chains them, and solid shapes run deep -- a whole 320 x 320
+//                     frame has 1276 levels (80 launches), a 450-px right triangle 1423 (92), a disc of radius 220 721 (48).
+//                     Those are also the inputs on which tiles sleep and wake (tests/helpers/medial_cases.py computes the
+//                     levels, the launch count 4 ceil(depth / 64) and the sleeping tiles from the mask alone;
+//                     tests/test_gpu_medial_stages.py holds the kernels to them through tmat_debug_medial_stages).
 #include "tmat_internal.h"
 #include "dev_guard.h"
 
@@ -274,6 +281,25 @@ size_t thin_workspace_bytes(int n, int H, int W)
     return (size_t)n * per * (8 + 1 + 1 + 1) + (size_t)n * 2 * sizeof(int) * 64 + (size_t)n * ((per + 1023) / 1024) * sizeof(int) + n * tiles * (2 + 3 * sizeof(int)) + 1024;
 }
 
+// where thin_dev keeps what in its workspace (the test-only stage copies of pipeline.cpp read keys and dep from here)
+ThinLayout thin_layout(void *ws, int n, int H, int W)
+{
+    const size_t per = (size_t)H * W;
+    ThinLayout l{};
+    l.keys = (uint64_t *)ws;
+    l.sd = (uint8_t *)(l.keys + (size_t)n * per);
+    l.sd2 = l.sd + (size_t)n * per;
+    l.dep = l.sd2 + (size_t)n * per;
+    l.flags = (int *)(((uintptr_t)(l.dep + (size_t)n * per) + 15) & ~(uintptr_t)15);         // [launch][image] undone flags
+    l.chunk = l.flags + (size_t)n * 2 * 64;                                                  // per-chunk foreground counts -> offsets
+    l.nchunk = (int)((per + 1023) / 1024);
+    l.tiles = (size_t)((H + MA_T - 1) / MA_T) * ((W + MA_T - 1) / MA_T);
+    l.tile_final = (uint8_t *)(l.chunk + (size_t)n * l.nchunk);                              // [image][tile]: both snapshots hold the tile's final values
+    l.tile_left = l.tile_final + (size_t)n * l.tiles;                                        // [image][tile]: the tile had undone pixels when it last ran
+    l.tprog = (int *)(((uintptr_t)(l.tile_left + (size_t)n * l.tiles) + 15) & ~(uintptr_t)15);      // [3][image][tile]: progress flags of launches l - 1, l, l + 1
+    return l;
+}
+
 int thin_count_dev(const uint8_t *mask, int n, int H, int W, int *nfg, hipStream_t s)
 {
     if (hipMemsetAsync(nfg, 0, n * sizeof(int), s) != hipSuccess) return -2;
@@ -284,30 +310,32 @@ int thin_count_dev(const uint8_t *mask, int n, int H, int W, int *nfg, hipStream
 
 // mask (n, H, W) u8, dist (n, H, W) f64 (its exact EDT), tie (n, H*W) u32: per image the legacy permutation of its
 // foreground count (first nfg[i] entries) -> skel (n, H, W) u8.  table_dev: 16 words.  Synchronises `s` (the round
-// launches repeat until a flag read back from the device says that every pixel is done).
+// launches repeat until a flag read back from the device says that every pixel is done).  launches (may be null): the number of
+// ma_round_kernel launches issued.
 int thin_dev(const uint8_t *mask, const double *dist, const uint32_t *tie, const int * /*nfg*/, int n, int H, int W, void *ws,
-             const uint32_t *table_dev, uint8_t *skel, hipStream_t s)
+             const uint32_t *table_dev, uint8_t *skel, hipStream_t s, int *launches)
 {
+    if (launches) *launches = 0;
     if (n <= 0) return 0;
     if (!thin_dev_supported(H, W)) return -1;
     const size_t per = (size_t)H * W;
-    uint64_t *keys = (uint64_t *)ws;
-    uint8_t *sd = (uint8_t *)(keys + (size_t)n * per), *sd2 = sd + (size_t)n * per, *dep = sd2 + (size_t)n * per;
-    int *flags = (int *)(((uintptr_t)(dep + (size_t)n * per) + 15) & ~(uintptr_t)15);       // [launch][image] undone flags
-    int *chunk = flags + (size_t)n * 2 * 64;                                                // per-chunk foreground counts -> offsets
-    const int nchunk = (int)((per + 1023) / 1024);
-    const size_t tiles = (size_t)((H + MA_T - 1) / MA_T) * ((W + MA_T - 1) / MA_T);
-    uint8_t *tile_final = (uint8_t *)(chunk + (size_t)n * nchunk);                          // [image][tile]: both snapshots hold the tile's final values
-    uint8_t *tile_left = tile_final + (size_t)n * tiles;                                    // [image][tile]: the tile had undone pixels when it last ran
-    int *tprog = (int *)(((uintptr_t)(tile_left + (size_t)n * tiles) + 15) & ~(uintptr_t)15);      // [3][image][tile]: progress flags of launches l - 1, l, l + 1
+    const ThinLayout lay = thin_layout(ws, n, H, W);
+    uint64_t *keys = lay.keys;
+    uint8_t *sd = lay.sd, *sd2 = lay.sd2, *dep = lay.dep, *tile_final = lay.tile_final, *tile_left = lay.tile_left;
+    int *flags = lay.flags, *chunk = lay.chunk, *tprog = lay.tprog;
+    const int nchunk = lay.nchunk;
+    const size_t tiles = lay.tiles;
     if (hipMemsetAsync(tile_final, 0, (size_t)n * tiles * 2 + 16 + 3 * (size_t)n * tiles * sizeof(int), s) != hipSuccess) return -2;
     hipLaunchKernelGGL(ma_chunk_count_kernel, dim3(nchunk, n), dim3(1024), 0, s, mask, per, nchunk, chunk);
     hipLaunchKernelGGL(ma_chunk_scan_kernel, dim3(n), dim3(1024), 0, s, chunk, nchunk);
     hipLaunchKernelGGL(ma_keys_kernel, dim3(nchunk, n), dim3(1024), 0, s, mask, dist, H, W, tie, chunk, nchunk, keys);
     hipLaunchKernelGGL(ma_dep_kernel, dim3((unsigned)((per + 255) / 256), n), dim3(256), 0, s, keys, H, W, sd, dep);
     const dim3 grid((W + MA_T - 1) / MA_T, (H + MA_T - 1) / MA_T, n);
-    const int max_launches = (H + W) / MA_R + 8;            // a chain of predecessors cannot be longer than the pixel count of a
-                                                            // monotone path; in practice the depth is about the largest distance
+    // Launch budget: 64 ((H + W) / 16 + 8), i.e. some 4 (H + W) launches = 64 (H + W) levels.  This is a safety net, not a bound
+    // derived from the DAG: chains follow the tie-break through plateaus of equal distance and are neither monotone paths nor
+    // limited by the largest distance (a whole 320 x 320 frame: 1276 levels, twice H + W; tests/helpers/medial_cases.py computes
+    // the depth of any mask).  The deepest input known, a 450-px triangle, needs 92 launches of the 4096 allowed.
+    const int max_launches = (H + W) / MA_R + 8;
     std::vector<int> host(n);
     constexpr int GROUP = 4;                                // launches between two looks at the flags
     for (int l = 0;; l += GROUP) {
@@ -316,12 +344,13 @@ int thin_dev(const uint8_t *mask, const double *dist, const uint32_t *tie, const
             hipLaunchKernelGGL(ma_round_kernel, grid, dim3(256), 0, s, (g & 1) ? sd2 : sd, (g & 1) ? sd : sd2, dep, H, W, table_dev,
                                flags + (size_t)g * n, g ? flags + (size_t)(g - 1) * n : (const int *)nullptr, tile_final, tprog, tile_left, l + g);
         }
+        if (launches) *launches = l + GROUP;
         if (hipMemcpyAsync(host.data(), flags + (size_t)(GROUP - 1) * n, n * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess) return -2;
         bool left = false;
         for (int i = 0; i < n; i++) left |= host[i] != 0;
         if (!left) break;
-        if (l + GROUP > 64 * max_launches) return -3;       // cannot happen: every launch finishes at least one pixel per undone image
+        if (l + GROUP > 64 * max_launches) return -3;       // budget used up with pixels left: a launch finishes 16 levels, unless a tile that should run sleeps
     }
     hipLaunchKernelGGL(ma_finish_kernel, dim3(1024), dim3(256), 0, s, sd, (size_t)n * per, skel);
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -254,8 +254,17 @@ void launch_widen_f32(const float *in, double *out, size_t n, hipStream_t s);
 bool thin_dev_supported(int H, int W);
 size_t thin_workspace_bytes(int n, int H, int W);
 int thin_count_dev(const uint8_t *mask, int n, int H, int W, int *nfg, hipStream_t s);
+struct ThinLayout {          // thin_dev's workspace
+    uint64_t *keys;          // (n, H, W) order keys, ~0 on the background
+    uint8_t *sd, *sd2, *dep; // (n, H, W) each: the two (value, done) snapshots, the predecessor bytes
+    int *flags, *chunk, *tprog;
+    uint8_t *tile_final, *tile_left;
+    int nchunk;
+    size_t tiles;
+};
+ThinLayout thin_layout(void *ws, int n, int H, int W);
 int thin_dev(const uint8_t *mask, const double *dist, const uint32_t *tie, const int *nfg, int n, int H, int W, void *ws,
-             const uint32_t *table_dev, uint8_t *skel, hipStream_t s);
+             const uint32_t *table_dev, uint8_t *skel, hipStream_t s, int *launches = nullptr);
 
 // ---- DMT front end on the device (dmt_kernels.hip) -------------------------------------------------
 inline size_t dmt_edge_count(int R, int C) { return (size_t)(R - 1) * C + (size_t)R * (C - 1) + (size_t)(R - 1) * (C - 1); }

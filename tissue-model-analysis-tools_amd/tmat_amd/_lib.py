@@ -100,6 +100,7 @@ def lib():
     L.tmat_finish_batch.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp]
     L.tmat_filter_mask_batch.argtypes = [vp, vp, i, i, i, i, i, vp]
     L.tmat_debug_filter_stages.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
+    L.tmat_debug_medial_stages.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp]
     L.tmat_gather_rows.argtypes = [vp, vp, i, vp, vp]
     L.tmat_zproj_batch.argtypes = [vp, vp, i, i, i, i, i, vp]
     L.tmat_zproj_dev.argtypes = [vp, vp, i, i, i, i, i, vp]
@@ -210,7 +211,7 @@ EXPORTS = [
     "tmat_dmt_graph", "tmat_dmt_graph_batch", "tmat_morse_stats",
     "tmat_morse_tree", "tmat_branch_color", "tmat_render_tree", "tmat_render_tree_timed", "tmat_host_render_tree", "tmat_host_render_barcode",
     "tmat_analyze_batch_dev", "tmat_analyze_batch", "tmat_analyze_batch_tree_dev", "tmat_analyze_batch_tree", "tmat_dev_alloc", "tmat_dev_free", "tmat_dev_upload", "tmat_dev_download",
-    "tmat_prof_enable", "tmat_prof_read", "tmat_debug_poison", "tmat_debug_held_bytes", "tmat_debug_filter_stages", "tmat_set_precision", "tmat_set_input_norm", "tmat_preprocess_batch", "tmat_well_threshold", "tmat_well_threshold_f64", "tmat_canny_mask", "tmat_superellipse_table", "tmat_superellipse_search",
+    "tmat_prof_enable", "tmat_prof_read", "tmat_debug_poison", "tmat_debug_held_bytes", "tmat_debug_filter_stages", "tmat_debug_medial_stages", "tmat_set_precision", "tmat_set_input_norm", "tmat_preprocess_batch", "tmat_well_threshold", "tmat_well_threshold_f64", "tmat_canny_mask", "tmat_superellipse_table", "tmat_superellipse_search",
     "tmat_superellipse_masks", "tmat_resize_nearest_u8", "tmat_analyze_batch_masked", "tmat_host_lanczos4_u16", "tmat_host_rescale01_u16",
     "tmat_host_rescale255_f32", "tmat_host_filter_mask", "tmat_host_skeletonize", "tmat_host_medial_axis",
     "tmat_host_permutation", "tmat_host_postprocess",
@@ -467,6 +468,16 @@ class Handle:
         check(lib().tmat_debug_filter_stages(self._h, ptr(m), n, m.shape[1], m.shape[2], int(bool(use_median)), int(bool(remove_isolated)),
                                              *(ptr(out[k]) for k in ("median", "labels", "stats", "skeleton", "filtered", "thin_launches"))),
               "tmat_debug_filter_stages")
+        return out
+
+    def debug_medial_stages(self, masks):
+        """test-only: medial_axis with the stages of its ordered thinning (include/tmat.h:tmat_debug_medial_stages) on (n, h, w) masks
+        -> dict of skel, dep (n, h, w) u8, dist (n, h, w) f64, keys (n, h, w) u64, launches (1) i32"""
+        m = np.ascontiguousarray(np.asarray(masks) != 0, np.uint8)
+        out = {"skel": np.empty(m.shape, np.uint8), "dist": np.empty(m.shape, np.float64), "keys": np.empty(m.shape, np.uint64),
+               "dep": np.empty(m.shape, np.uint8), "launches": np.zeros(1, np.int32)}
+        check(lib().tmat_debug_medial_stages(self._h, ptr(m), m.shape[0], m.shape[1], m.shape[2],
+                                             *(ptr(out[k]) for k in ("skel", "dist", "keys", "dep", "launches"))), "tmat_debug_medial_stages")
         return out
 
     ZPROJ_METHODS = {"fs": 0, "min": 1, "max": 2, "avg": 3, "med": 4}
